@@ -1,11 +1,11 @@
 """Hardware-queue-aware stream choice for callers that keep several contexts in flight beside other stream work (a collective).
 
-The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (include/aruco3_hip.h, "Hardware queues"),
+The HIP runtime multiplexes a process's streams onto the hardware queues its environment grants (include/aruco3_hip.h, "Hardware queues"),
 and two streams that share a queue run IN ORDER whatever their events say -- a stream that merely WAITS (a collective waiting for
 its peers, a stream waiting for an event) holds up every other stream of its queue.  Which streams share a queue is not something
 the runtime tells; it can be measured: put something slow on one stream and see which other streams' work is held up behind it.
 
-Measured on MI355X / ROCm 7.2 with GPU_MAX_HW_QUEUES=8 (profiles/r05_queue_collisions.txt): PyTorch creates its pool of 32 streams
+Measured on MI355X / ROCm 7.2 with eight queues per process (profiles/r05_queue_collisions.txt): PyTorch creates its pool of 32 streams
 per priority at once, the library's own context streams come later, and the context stream of a burst's LAST member landed on
 the queue of the bench's side stream -- every collective then stalled that context for its whole duration.
 

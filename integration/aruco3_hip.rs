@@ -631,7 +631,7 @@ impl Detector {
 /// The burst stepping is what the library does with these calls by itself (include/aruco3_hip.h, a3_order_after: a context that
 /// declared gates holds its chain back behind its threshold kernel, the rotation's last context releases them) -- this type calls
 /// nothing outside the public header, and `last_stepping()` reports what the library did with the batch just collected.
-/// Export GPU_MAX_HW_QUEUES=8 before the process touches HIP (header, "Hardware queues").
+/// With fewer hardware queues than streams the batches overlap less (header, "Hardware queues").
 pub struct BatchQueue {
     ctxs: Vec<HipCtx>,
     frames_in: Vec<usize>, // frames of the batch in flight on each context

@@ -15,7 +15,6 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 import os
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 DEFAULT = "shared:2:2:2,own:2:2:0,own:2:1:0,own:3:1:0,own:3:2:0,shared:2:1:2"
 

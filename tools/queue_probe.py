@@ -1,6 +1,6 @@
 """Which streams of a bench-like process share a hardware queue?  (profiles/r05_queue_collisions.txt)
 
-  GPU_MAX_HW_QUEUES=8 python tools/queue_probe.py [nccl]
+  python tools/queue_probe.py [nccl]      (with the hardware queues the environment grants)
 
 Creates what bench.py creates -- (optionally) a one-rank NCCL process group, torch's explicit stream and side stream, four contexts
 on streams of their own, twelve more torch pool streams -- then, for every stream S, puts a 1.5 ms sleep on S and measures how long
@@ -10,7 +10,6 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import torch.distributed as dist
 

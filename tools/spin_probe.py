@@ -12,7 +12,6 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 CASES = [(0, 0, 0), (0, 0, -1), (8, 50, 0), (16, 50, 0), (16, 50, 1), (32, 50, 0), (32, 50, 1), (32, 200, 0), (32, 200, 1), (16, 600, 0), (16, 600, 1)]   # (W, T, mode): mode 0 = the
 # spinner is released at once (the product: no event behind the threshold kernel); 1 = it waits for the threshold kernel of the batch just submitted
