@@ -23,6 +23,7 @@ PROFILE_OFF, PROFILE_STAGES, PROFILE_THRESHOLD_ONLY, PROFILE_THRESHOLD_SAMPLED =
 STAGE_THRESHOLD, STAGE_CONTOUR, STAGE_DECODE = 0, 1, 2
 # a3_stats.stepping & 0xFF (include/aruco3_hip.h A3_STEP_*)
 STEP_WHOLE, STEP_DECODE_DEFERRED, STEP_HELD_RELEASED_BY_LAST, STEP_HELD_RELEASED_EARLY, STEP_BURST_LAST, STEP_HELD = 0, 1, 2, 3, 4, 5
+REFINE_NONE, REFINE_SUBPIX = 0, 1
 STEP_NAMES = {0: "whole", 1: "decode_deferred", 2: "held_released_by_last", 3: "held_released_early", 4: "burst_last", 5: "held"}
 
 # every symbol include/aruco3_hip.h declares
@@ -33,6 +34,7 @@ SYMBOLS = [
     "a3_candidate_count", "a3_download_candidates", "a3_download_homographies", "a3_estimate_pose", "a3_estimate_pose_normalized",
     "a3_find_nearest", "a3_calculate_tau", "a3_set_profiling", "a3_get_profile",
     "a3_contour_count", "a3_download_contours", "a3_detection_record_bytes", "a3_pack_detections",
+    "a3_default_refine_config", "a3_set_corner_refinement", "a3_get_refined_corners", "a3_refine_corners",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
 INTERNAL_SYMBOLS = ["a3_debug_set_k1_stream", "a3_debug_set_overlap", "a3_debug_set_k1_waves", "a3_debug_set_partition", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_mark_threshold", "a3_debug_set_hold", "a3_debug_launch_threshold", "a3_debug_stream_wait_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
@@ -79,6 +81,12 @@ class PoseRec(C.Structure):
 class Intrinsics(C.Structure):
     _fields_ = [("image_width", C.c_uint32), ("image_height", C.c_uint32), ("focal_x", C.c_float), ("focal_y", C.c_float),
                 ("principal_x", C.c_float), ("principal_y", C.c_float)]
+
+
+class RefineConfig(C.Structure):
+    """a3_refine_config: sub-pixel corner refinement (an extension beyond the reference; include/aruco3_hip.h states the algorithm)"""
+    _fields_ = [("method", C.c_uint32), ("win_half", C.c_uint32), ("relative_win", C.c_float), ("max_iterations", C.c_uint32),
+                ("min_shift", C.c_float)]
 
 
 class Stats(C.Structure):
@@ -232,6 +240,15 @@ def load():
     L.a3_debug_rotate_bits.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, u8p]
     L.a3_debug_inject_candidates.restype = C.c_int
     L.a3_debug_inject_candidates.argtypes = [vp, u32p, C.c_size_t]
+    if hasattr(L, "a3_refine_corners"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack corner refinement)
+        L.a3_default_refine_config.restype = None
+        L.a3_default_refine_config.argtypes = [C.POINTER(RefineConfig)]
+        L.a3_set_corner_refinement.restype = C.c_int
+        L.a3_set_corner_refinement.argtypes = [vp, C.POINTER(RefineConfig)]
+        L.a3_get_refined_corners.restype = C.c_int
+        L.a3_get_refined_corners.argtypes = [vp, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.a3_refine_corners.restype = C.c_int
+        L.a3_refine_corners.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, f32p, f32p, C.c_size_t]
     L.a3_debug_discard_too_near.restype = C.c_int
     L.a3_debug_discard_too_near.argtypes = [vp, u32p, C.c_size_t, C.c_float, u32p, C.POINTER(C.c_size_t)]
     _lib = L
@@ -283,6 +300,12 @@ def check(rc, ctx=None):
 def default_config() -> Config:
     cfg = Config()
     load().a3_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_refine_config() -> RefineConfig:
+    cfg = RefineConfig()
+    load().a3_default_refine_config(C.byref(cfg))
     return cfg
 
 
@@ -424,6 +447,33 @@ class Context:
         check(load().a3_detect_batch_pose_collect(self.handle, out.ctypes.data_as(C.c_void_p), poses.ctypes.data_as(C.c_void_p), cap,
                                                   _p(per, C.c_uint32), C.byref(n)), self.handle)
         return out[: n.value], per[:n_frames], poses[: n.value]
+
+    # ---- sub-pixel corner refinement ----
+    def set_corner_refinement(self, cfg: "RefineConfig" = None):
+        """a3_set_corner_refinement: None (or method REFINE_NONE) turns it off; applies to batches submitted afterwards"""
+        check(load().a3_set_corner_refinement(self.handle, C.byref(cfg) if cfg is not None else None), self.handle)
+
+    def refined_corners(self) -> np.ndarray:
+        """a3_get_refined_corners: float32 [n_markers, 4, 2] of the last collected batch, in marker order"""
+        n = C.c_size_t()
+        L = load()
+        rc = L.a3_get_refined_corners(self.handle, None, 0, C.byref(n))
+        if rc not in (OK, ERR_CAPACITY):
+            check(rc, self.handle)
+        out = np.zeros((max(n.value, 1), 4, 2), dtype=np.float32)
+        check(L.a3_get_refined_corners(self.handle, _p(out, C.c_float), max(n.value, 1), C.byref(n)), self.handle)
+        return out[: n.value]
+
+    def refine_corners(self, pixels_ptr: int, memory: int, fmt: int, width: int, height: int, row_stride: int, corners: np.ndarray,
+                       cell_px: np.ndarray = None) -> np.ndarray:
+        """a3_refine_corners (stand-alone, one frame): corners (..., 2) -> refined float32 (n, 2)"""
+        xy = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 2)).copy()
+        cp = None if cell_px is None else np.ascontiguousarray(np.asarray(cell_px, dtype=np.float32).reshape(-1))
+        if cp is not None and cp.size != xy.shape[0]:
+            raise ValueError("cell_px needs one value per corner")
+        check(load().a3_refine_corners(self.handle, C.c_void_p(pixels_ptr), memory, fmt, width, height, row_stride, _p(xy, C.c_float),
+                                       None if cp is None else _p(cp, C.c_float), xy.shape[0]), self.handle)
+        return xy
 
     # ---- Detection.grey / thresholded / candidates / homographies of the last batch ----
     def download_grey(self, frame: int, w: int, h: int, thresholded: bool = False) -> np.ndarray:

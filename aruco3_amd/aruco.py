@@ -34,12 +34,26 @@ class DetectorConfig:
 
 
 @dataclass
+class CornerRefinement:
+    """Sub-pixel corner refinement (a3_refine_config; not in the reference -- include/aruco3_hip.h states the algorithm).
+    Passing one to `Detector(refinement=...)` fills `Marker.corners_refined` and makes the pose calls solve from those corners."""
+    win_half: int = 5
+    relative_win: float = 0.4
+    max_iterations: int = 30
+    min_shift: float = 0.01
+
+    def _c(self) -> _lib.RefineConfig:
+        return _lib.RefineConfig(_lib.REFINE_SUBPIX, self.win_half, self.relative_win, self.max_iterations, self.min_shift)
+
+
+@dataclass
 class Marker:
-    """src/aruco.rs:8-13"""
+    """src/aruco.rs:8-13, plus the refined corners when the detector refines them (an extension; None otherwise)"""
     id: int
     code: int
     corners: List[Tuple[int, int]]
     hamming_distance: int
+    corners_refined: Optional[List[Tuple[float, float]]] = None
 
 
 @dataclass
@@ -89,12 +103,20 @@ def _as_frames(image):
 class Detector:
     """`Detector { config, dictionary }` (src/aruco.rs:46-49)."""
 
-    def __init__(self, config: DetectorConfig = None, dictionary: ARDictionary = None, device: int = 0):
+    def __init__(self, config: DetectorConfig = None, dictionary: ARDictionary = None, device: int = 0,
+                 refinement: Optional[CornerRefinement] = None):
         self.config = config or DetectorConfig()
         self.dictionary = dictionary or ARDictionary.new_from_named_dict("ARUCO")
         self.device = device
+        self.refinement = refinement
         self._ctx = None
         self._ctx_key = None
+
+    def _apply_refinement(self, ctx: _lib.Context) -> bool:
+        """hands the detector's refinement setting to the context before a call -> whether it is on"""
+        r = self.refinement
+        ctx.set_corner_refinement(r._c() if r is not None else None)
+        return r is not None
 
     def _context(self) -> _lib.Context:
         key = (tuple(vars(self.config).items()), id(self.dictionary), self.device)
@@ -120,15 +142,15 @@ class Detector:
         if stream is not None:
             ctx.set_stream(stream)
         ctx.set_debug_taps(populate)
+        refine = self._apply_refinement(ctx)
         markers, per = ctx.detect_batch(ptr, mem, fmt, w, h, rs, fs, n, out_cap)
+        refined = ctx.refined_corners() if refine else None
         out = []
         pos = 0
         for f in range(n):
             det = Detection()
-            for m in markers[pos: pos + int(per[f])]:
-                c = m["corners"]
-                det.markers.append(Marker(int(m["id"]), int(m["code"]), [(int(c[2 * i]), int(c[2 * i + 1])) for i in range(4)],
-                                          int(m["hamming_distance"])))
+            for i in range(pos, pos + int(per[f])):
+                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None))
             pos += int(per[f])
             if populate:
                 det.grey = ctx.download_grey(f, w, h)
@@ -148,21 +170,20 @@ class Detector:
         if stream is not None:
             ctx.set_stream(stream)
         ctx.set_debug_taps(False)
+        refine = self._apply_refinement(ctx)
         intr = None
         if intrinsics is not None:
             ci = intrinsics
             intr = _lib.Intrinsics(ci.image_width, ci.image_height, ci.focal_x, ci.focal_y, ci.principal_x, ci.principal_y)
         markers, per, poses = ctx.detect_batch_pose(ptr, mem, fmt, w, h, rs, fs, n, marker_size_mm, intr, out_cap)
+        refined = ctx.refined_corners() if refine else None
         out = []
         pos = 0
         for f in range(n):
             det = Detection()
             pp = []
             for i in range(pos, pos + int(per[f])):
-                m = markers[i]
-                c = m["corners"]
-                det.markers.append(Marker(int(m["id"]), int(m["code"]), [(int(c[2 * k]), int(c[2 * k + 1])) for k in range(4)],
-                                          int(m["hamming_distance"])))
+                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None))
                 pp.append(tuple(MarkerPose(float(q[0]), q[1:10].reshape(3, 3).copy(), q[10:13].copy()) for q in poses[i]))
             pos += int(per[f])
             out.append((det, pp))
@@ -174,16 +195,22 @@ class Detector:
         ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
         if stream is not None:
             ctx.set_stream(stream)
+        self._apply_refinement(ctx)   # (the refined corners are not returned here: Context.refined_corners() has them)
         return ctx.detect_batch(ptr, mem, fmt, w, h, rs, fs, n, out_cap)
 
 
-def _detections(markers, per) -> List[Detection]:
+def _marker(m, refined=None) -> Marker:
+    c = m["corners"]
+    return Marker(int(m["id"]), int(m["code"]), [(int(c[2 * i]), int(c[2 * i + 1])) for i in range(4)], int(m["hamming_distance"]),
+                  None if refined is None else [(float(x), float(y)) for x, y in refined])
+
+
+def _detections(markers, per, refined=None) -> List[Detection]:
     out, pos = [], 0
     for f in range(len(per)):
         det = Detection()
-        for m in markers[pos: pos + int(per[f])]:
-            c = m["corners"]
-            det.markers.append(Marker(int(m["id"]), int(m["code"]), [(int(c[2 * i]), int(c[2 * i + 1])) for i in range(4)], int(m["hamming_distance"])))
+        for i in range(pos, pos + int(per[f])):
+            det.markers.append(_marker(markers[i], refined[i] if refined is not None else None))
         pos += int(per[f])
         out.append(det)
     return out
@@ -205,6 +232,8 @@ class BatchQueue:
             raise ValueError("depth must be in 1..8")
         d = detector.dictionary
         self._ctxs = [_lib.Context(detector.config._c(), d.code_list, d.num_bits, d._tau, detector.device) for _ in range(depth)]
+        self._refinement = detector.refinement   # (the detector's setting when the queue was made; each batch keeps the one in force at its submit)
+        self._refine_on = [False] * depth
         self._keep = [None] * depth
         self._gates = gates
         self._head = self._in_flight = self._submitted = 0
@@ -228,6 +257,8 @@ class BatchQueue:
                 ctx.order_after(self._ctxs[m])
         ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
         ctx.set_debug_taps(False)
+        ctx.set_corner_refinement(self._refinement._c() if self._refinement is not None else None)
+        self._refine_on[k] = self._refinement is not None
         ctx.submit(ptr, mem, fmt, w, h, rs, fs, n, out_cap=out_cap or n * 64)
         self._keep[k] = keep
         self._submitted += 1
@@ -245,7 +276,7 @@ class BatchQueue:
         finally:
             self._keep[k] = None
         self.last_stepping = ctx.stats()["stepping"]
-        return _detections(markers, per)
+        return _detections(markers, per, ctx.refined_corners() if self._refine_on[k] else None)
 
     def close(self) -> None:
         while self._in_flight:

@@ -65,6 +65,10 @@ hipError_t launch_gather_patches(hipStream_t, const void*, uint32_t, const uint8
 hipError_t launch_pose(hipStream_t, const uint32_t*, uint32_t, const float*, uint32_t, const unsigned int*, int, float, float, float, float,
                        float, float, float, a3_pose*);
 hipError_t launch_find_nearest(hipStream_t, const uint64_t*, uint32_t, const uint64_t*, uint32_t, uint32_t*, uint8_t*);
+size_t refine_params_bytes();
+void refine_params(void*, const a3_refine_config&, uint32_t);
+hipError_t launch_refine_corners(hipStream_t, PixelSrc, uint32_t, uint32_t, const a3_marker*, const unsigned int*, const float*, const float*, uint32_t,
+                                 const void*, float*);
 hipError_t launch_calc_tau(hipStream_t, const uint64_t*, uint32_t, unsigned int*);
 hipError_t launch_synth_render(hipStream_t, const a3_synth_frame*, uint32_t, const a3_synth_marker*, uint32_t, uint32_t, int, float, float, int,
                                uint8_t*, size_t, size_t);
@@ -124,6 +128,8 @@ struct BackArgs {
     float pose_size_mm = 0.0f;
     a3_intrinsics pose_intr{};
     int profiling = 0;
+    a3_refine_config refine{};   // the batch's corner refinement (method NONE: none)
+    size_t refine_bytes = 0;     // 32 (8 floats per marker) with refinement, else 0
 };
 
 // what finish_batch needs to know about the batch enqueue_batch put on the stream
@@ -137,6 +143,10 @@ struct Pending {
     // the submitted call, for the synchronous re-run when the device asks for one
     const uint8_t* pixels = nullptr; int fmt = 0; size_t row_stride = 0, frame_stride = 0;
     bool want_pose = false;   // a3_detect_batch_pose_submit: the re-run must solve the poses again
+    // corner refinement in force for this batch, captured when it was submitted (a3_set_corner_refinement affects later batches;
+    // a held chain and a re-run use this copy)
+    a3_refine_config refine{};
+    size_t refine_bytes = 0;
 };
 
 }  // namespace
@@ -239,6 +249,14 @@ struct a3_ctx {
     DevBuf wtab;                // triangle-resize weights of a full patch (sample -> mark_size), written once at a3_create
     DevBuf pose_buf;            // a3_detect_batch_pose: both poses of every marker of the last batch (kept for a3_pack_detections)
     bool poses_valid = false;
+    // a3_set_corner_refinement: the setting later batches capture; refine_prm holds the kernel parameters (weight tables) built for
+    // refine_prm_cfg, rebuilt when a batch brings another setting
+    a3_refine_config refine{};
+    a3_refine_config refine_prm_cfg{};
+    std::vector<float> refine_prm;
+    DevBuf refined_buf;          // refined corners of the last batch on the device (8 floats per marker, marker order)
+    std::vector<float> h_refined;
+    bool refined_valid = false;  // the last collected batch ran with refinement: h_refined holds its corners
     void* pinned = nullptr;
     size_t pinned_cap = 0;
     // debug taps: per-frame candidate counts of the last batch (before / after discard_too_near), read back with the results so
@@ -423,6 +441,16 @@ int release_mode() {
 // (The decode stream has default priority: the lowest one measured the same, and is the wrong thing to hold when two processes
 // share a GPU.)
 
+// the refinement kernel's parameters for setting `cfg` (weight tables from libm: built once per setting, not per batch)
+const void* refine_params_for(a3_ctx* ctx, const a3_refine_config& cfg) {
+    if (ctx->refine_prm.empty() || memcmp(&ctx->refine_prm_cfg, &cfg, sizeof cfg) != 0) {
+        ctx->refine_prm.assign((refine_params_bytes() + 3) / 4, 0.0f);
+        refine_params(ctx->refine_prm.data(), cfg, ctx->mark_size);
+        ctx->refine_prm_cfg = cfg;
+    }
+    return ctx->refine_prm.data();
+}
+
 // candidates -> markers -> read-back of one batch, on stream `st` (the context's stream, or its decode stream when deferred)
 int enqueue_back(a3_ctx* ctx, hipStream_t st, const BackArgs& b) {
     unsigned int* d_work_count = ctx->scratch_u32 + 0;
@@ -449,11 +477,18 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const BackArgs& b) {
                          few));
     A3_HIP(launch_compact_markers(st, ctx->outs.p, ctx->fin_xy.as<uint16_t>(), ctx->fin_count.as<uint32_t>(), b.n, 0, b.max_cand,
                                   ctx->markers_ptr, b.marker_cap, ctx->per_frame, d_marker_total, d_err, ctx->cand_count, ctx->scratch_u32 + 2));
+    if (b.refine_bytes)   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
+        A3_HIP(launch_refine_corners(st, b.src, b.W, b.H, ctx->markers_ptr, d_marker_total, nullptr, nullptr, b.marker_cap,
+                                     refine_params_for(ctx, b.refine), ctx->refined_buf.as<float>()));
     if (b.want_pose) {   // IPPE on the device-resident marker list (src/pose.rs:52-81), no extra round trip
         const a3_intrinsics& in = b.pose_intr;
-        A3_HIP(launch_pose(st, reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(ctx->markers_ptr) + offsetof(a3_marker, corners)),
-                           (uint32_t)(sizeof(a3_marker) / 4), nullptr, b.marker_cap, d_marker_total, b.pose_has_intr ? 1 : 0, b.pose_size_mm,
-                           (float)b.W, (float)b.H, in.focal_x, in.focal_y, in.principal_x, in.principal_y, ctx->pose_buf.as<a3_pose>()));
+        if (b.refine_bytes)   // from the refined float corners (k_pose modes 3 / 4)
+            A3_HIP(launch_pose(st, nullptr, 8u, ctx->refined_buf.as<float>(), b.marker_cap, d_marker_total, b.pose_has_intr ? 4 : 3, b.pose_size_mm,
+                               (float)b.W, (float)b.H, in.focal_x, in.focal_y, in.principal_x, in.principal_y, ctx->pose_buf.as<a3_pose>()));
+        else
+            A3_HIP(launch_pose(st, reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(ctx->markers_ptr) + offsetof(a3_marker, corners)),
+                               (uint32_t)(sizeof(a3_marker) / 4), nullptr, b.marker_cap, d_marker_total, b.pose_has_intr ? 1 : 0, b.pose_size_mm,
+                               (float)b.W, (float)b.H, in.focal_x, in.focal_y, in.principal_x, in.principal_y, ctx->pose_buf.as<a3_pose>()));
     }
     if (b.profiling >= 2) A3_HIP(hipEventRecord(ctx->ev[3], st));
     // ---- results: one copy of [scratch | counters | per-frame counts | `guess` markers], then the poses and (taps) the counts ----
@@ -461,6 +496,9 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const BackArgs& b) {
     a3_pose* h_poses = reinterpret_cast<a3_pose*>(hp + b.head_bytes + (size_t)b.guess * sizeof(a3_marker));
     A3_HIP(hipMemcpyAsync(hp, ctx->scratch_u32, b.head_bytes + (size_t)b.guess * sizeof(a3_marker), hipMemcpyDeviceToHost, st));
     if (b.pose_bytes) A3_HIP(hipMemcpyAsync(h_poses, ctx->pose_buf.p, (size_t)b.guess * b.pose_bytes, hipMemcpyDeviceToHost, st));
+    if (b.refine_bytes)   // (staged behind the poses)
+        A3_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(h_poses) + (size_t)b.guess * b.pose_bytes, ctx->refined_buf.p, (size_t)b.guess * b.refine_bytes,
+                              hipMemcpyDeviceToHost, st));
     if (b.taps) {   // Detection.candidates / .homographies will be asked for frame by frame: their counts travel now
         A3_HIP(hipMemcpyAsync(ctx->pinned_counts, ctx->cand_count, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
         A3_HIP(hipMemcpyAsync((uint8_t*)ctx->pinned_counts + (size_t)b.n * 4, ctx->fin_count.p, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
@@ -588,7 +626,9 @@ int ensure_chain_buffers(a3_ctx* ctx, hipStream_t st, uint32_t n, uint32_t W, ui
     A3_HIP(ctx->cyc_start_off.ensure((size_t)ctx->max_contours * 4));
     A3_HIP(ctx->points.ensure(ctx->max_points * 4));
     if (ctx->want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)marker_cap * 2 * sizeof(a3_pose)));
-    if (int rc = ensure_pinned(ctx, z.head_bytes + (size_t)marker_guess_of(ctx, marker_cap) * (sizeof(a3_marker) + 2 * sizeof(a3_pose)) + (1 << 16))) return rc;
+    const size_t refine_bytes = ctx->pending.refine.method != A3_REFINE_NONE ? 8 * sizeof(float) : 0;
+    if (refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)marker_cap * refine_bytes));
+    if (int rc = ensure_pinned(ctx, z.head_bytes + (size_t)marker_guess_of(ctx, marker_cap) * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + (1 << 16))) return rc;
     if (ctx->debug_taps && ctx->pinned_counts_cap < (size_t)n * 8) {
         if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
         ctx->pinned_counts = nullptr; ctx->pinned_counts_cap = 0;
@@ -866,7 +906,9 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
     // every allocation of the second half happens here, at submit time: pose buffer, pinned staging for the head and `guess`
     // markers (+ poses; a longer list is fetched by finish_batch after growing it), pinned staging for the tap counts
     if (ctx->want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)marker_cap * 2 * sizeof(a3_pose)));
-    if (int rc = ensure_pinned(ctx, head_pad + (size_t)guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose)) + (1 << 16))) return rc;
+    const size_t refine_bytes = ctx->pending.refine.method != A3_REFINE_NONE ? 8 * sizeof(float) : 0;   // (captured at submit)
+    if (refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)marker_cap * refine_bytes));
+    if (int rc = ensure_pinned(ctx, head_pad + (size_t)guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + (1 << 16))) return rc;
     ctx->counts_valid = false;
     if (ctx->debug_taps && ctx->pinned_counts_cap < (size_t)n * 8) {
         if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -879,6 +921,7 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
     bk.min_corner_separation = min_corner_separation; bk.src = src; bk.head_bytes = head_bytes; bk.pose_bytes = pose_bytes;
     bk.taps = ctx->debug_taps; bk.want_pose = ctx->want_pose; bk.pose_has_intr = ctx->pose_has_intr; bk.pose_size_mm = ctx->pose_size_mm;
     bk.pose_intr = ctx->pose_intr; bk.profiling = prof;
+    bk.refine = ctx->pending.refine; bk.refine_bytes = refine_bytes;
     // Deferral: only for submitted batches (somebody will submit again or collect), and not while every stage is being timed
     // (the stage times are those of stages that run alone).  The decode stage then waits on the context's decode stream until
     // (a) another context submits a batch -- it is released behind that batch's threshold kernel and shares the GPU with its
@@ -895,7 +938,7 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
     Pending& pd = ctx->pending;
     pd.active = true; pd.n_chunks = chunks.size(); pd.chunk0_darts = chunks.empty() ? 0 : chunks[0].darts; pd.ctr_bytes = ctr_bytes;
     pd.head_pad = head_pad; pd.marker_cap = marker_cap; pd.guess = guess; pd.pose_bytes = pose_bytes; pd.device_plan = device_plan;
-    pd.rounds_max = rounds_max; pd.n = n; pd.W = W; pd.H = H; pd.profiling = prof; pd.taps = ctx->debug_taps;
+    pd.rounds_max = rounds_max; pd.n = n; pd.W = W; pd.H = H; pd.profiling = prof; pd.taps = ctx->debug_taps; pd.refine_bytes = refine_bytes;
     return A3_OK;
 }
 
@@ -909,13 +952,14 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
     }
     pd.active = false;
     hipStream_t st = ctx->stream;
-    const size_t ctr_bytes = pd.ctr_bytes, head_pad = pd.head_pad, pose_bytes = pd.pose_bytes, n_chunks = pd.n_chunks;
+    const size_t ctr_bytes = pd.ctr_bytes, head_pad = pd.head_pad, pose_bytes = pd.pose_bytes, n_chunks = pd.n_chunks, refine_bytes = pd.refine_bytes;
     const uint32_t marker_cap = pd.marker_cap, guess = pd.guess, n = pd.n, W = pd.W, H = pd.H;
     const bool device_plan = pd.device_plan;
     const int rounds_max = pd.rounds_max;
     uint8_t* hp = (uint8_t*)ctx->pinned;
     a3_marker* h_markers = reinterpret_cast<a3_marker*>(hp + head_pad);
     a3_pose* h_poses = reinterpret_cast<a3_pose*>(hp + head_pad + (size_t)guess * sizeof(a3_marker));
+    const float* h_refined = reinterpret_cast<const float*>(hp + head_pad + (size_t)guess * (sizeof(a3_marker) + pose_bytes));
     (void)marker_cap;
     {   // nobody submitted behind this batch: its decode stage goes out now
         std::lock_guard<std::mutex> lk(g_defer_mu);
@@ -1004,17 +1048,21 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
     const uint32_t n_work = hs[0], n_pre = hs[2];
     const uint32_t tap_contours = n_chunks ? hc[0].contours : 0u; const uint64_t tap_points = n_chunks ? hc[0].points : 0ull;
     if (total > guess) {   // the guess was short: the staging area grows (the head has been consumed) and the whole list is fetched
-        if (int rc = ensure_pinned(ctx, (size_t)total * (sizeof(a3_marker) + 2 * sizeof(a3_pose)) + (1 << 16))) return rc;
+        if (int rc = ensure_pinned(ctx, (size_t)total * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + (1 << 16))) return rc;
         h_markers = reinterpret_cast<a3_marker*>(ctx->pinned);
         h_poses = reinterpret_cast<a3_pose*>((uint8_t*)ctx->pinned + (size_t)total * sizeof(a3_marker));
+        h_refined = reinterpret_cast<const float*>((uint8_t*)ctx->pinned + (size_t)total * (sizeof(a3_marker) + pose_bytes));
         A3_HIP(hipMemcpyAsync(h_markers, ctx->markers_ptr, (size_t)total * sizeof(a3_marker), hipMemcpyDeviceToHost, st));
         if (pose_bytes) A3_HIP(hipMemcpyAsync(h_poses, ctx->pose_buf.p, (size_t)total * pose_bytes, hipMemcpyDeviceToHost, st));
+        if (refine_bytes) A3_HIP(hipMemcpyAsync(const_cast<float*>(h_refined), ctx->refined_buf.p, (size_t)total * refine_bytes, hipMemcpyDeviceToHost, st));
         A3_HIP(hipStreamSynchronize(st));
     }
     if (total) {
         memcpy(out, h_markers, (size_t)total * sizeof(a3_marker));
         if (pose_bytes && ctx->pose_out) memcpy(ctx->pose_out, h_poses, (size_t)total * pose_bytes);
     }
+    if (refine_bytes) ctx->h_refined.assign(h_refined, h_refined + (size_t)total * 8);
+    ctx->refined_valid = refine_bytes != 0;
     if (pd.taps) {
         const uint32_t* hc32 = reinterpret_cast<const uint32_t*>(ctx->pinned_counts);
         ctx->h_cand_pre.assign(hc32, hc32 + n);
@@ -1172,7 +1220,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->leader_list, &ctx->leader_keep, &ctx->entry_list, &ctx->es_a, &ctx->es_b,
                       &ctx->contours, &ctx->cyc_start_off, &ctx->points, &ctx->zero_blk, &ctx->cands,
                       &ctx->pre_xy, &ctx->fin_xy, &ctx->fin_count, &ctx->work, &ctx->outs, &ctx->proj, &ctx->patches, &ctx->cand_big,
-                      &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab};
+                      &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1334,10 +1382,12 @@ int a3_detect_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32
     if (!out_n || (!out && out_cap)) return fail(ctx, A3_ERR_INVALID, "a3_detect_batch: null output");
     *out_n = 0;
     if (ctx->pending.active) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");
+    ctx->pending.refine = ctx->refine;
     const uint8_t* d_pixels = nullptr;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, n_frames, &d_pixels);
     if (rc == kNothingToDo) {
         if (per_frame_count && n_frames) memset(per_frame_count, 0, (size_t)n_frames * 4);
+        ctx->h_refined.clear(); ctx->refined_valid = ctx->refine.method != A3_REFINE_NONE;
         return A3_OK;
     }
     if (rc != A3_OK) return rc;
@@ -1349,6 +1399,7 @@ int a3_detect_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32
 static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
                          size_t frame_stride, uint32_t n_frames, size_t out_cap, bool want_pose) {
     if (ctx->pending.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");
+    ctx->pending.refine = ctx->refine;   // (the batch keeps the setting in force at its submit)
     const uint8_t* d_pixels = nullptr;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, n_frames, &d_pixels);
     if (rc == kNothingToDo) { ctx->pending_trivial = true; ctx->pending.n = n_frames; return A3_OK; }
@@ -1416,6 +1467,7 @@ static int collect_common(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t ou
     if (ctx->pending_trivial) {
         ctx->pending_trivial = false;
         if (per_frame_count && ctx->pending.n) memset(per_frame_count, 0, (size_t)ctx->pending.n * 4);
+        ctx->h_refined.clear(); ctx->refined_valid = ctx->pending.refine.method != A3_REFINE_NONE;
         return A3_OK;
     }
     A3_HIP(hipSetDevice(ctx->device));
@@ -1911,6 +1963,76 @@ int a3_debug_inject_candidates(a3_ctx* ctx, const uint32_t* quads_xy, size_t n) 
         }
     }
     ctx->inject_armed = true;
+    return A3_OK;
+}
+
+// ---- sub-pixel corner refinement (an extension beyond the reference; contract in include/aruco3_hip.h) ----
+void a3_default_refine_config(a3_refine_config* cfg) {
+    if (!cfg) return;
+    cfg->method = A3_REFINE_SUBPIX; cfg->win_half = 5; cfg->relative_win = 0.4f; cfg->max_iterations = 30; cfg->min_shift = 0.01f;
+}
+
+static int check_refine_config(a3_ctx* ctx, const a3_refine_config& c) {
+    if (c.method != A3_REFINE_NONE && c.method != A3_REFINE_SUBPIX) return fail(ctx, A3_ERR_INVALID, "a3_refine_config.method: unknown method");
+    if (c.method == A3_REFINE_NONE) return A3_OK;
+    if (c.win_half < 1 || c.win_half > 10) return fail(ctx, A3_ERR_INVALID, "a3_refine_config.win_half must be in 1..10");
+    if (!(c.relative_win >= 0.0f) || !std::isfinite(c.relative_win)) return fail(ctx, A3_ERR_INVALID, "a3_refine_config.relative_win must be finite and >= 0");
+    if (c.max_iterations > 100) return fail(ctx, A3_ERR_INVALID, "a3_refine_config.max_iterations must be at most 100");
+    if (!(c.min_shift >= 0.0f) || !std::isfinite(c.min_shift)) return fail(ctx, A3_ERR_INVALID, "a3_refine_config.min_shift must be finite and >= 0");
+    return A3_OK;
+}
+
+int a3_set_corner_refinement(a3_ctx* ctx, const a3_refine_config* cfg) {
+    if (!ctx) return A3_ERR_INVALID;
+    a3_refine_config c{};   // NULL: off
+    if (cfg) c = *cfg;
+    if (int rc = check_refine_config(ctx, c)) return rc;
+    if (c.method == A3_REFINE_NONE) c = a3_refine_config{};
+    ctx->refine = c;
+    return A3_OK;
+}
+
+int a3_get_refined_corners(a3_ctx* ctx, float* dst_xy, size_t cap_markers, size_t* n) {
+    if (!ctx || !n || (!dst_xy && cap_markers)) return A3_ERR_INVALID;
+    *n = 0;
+    if (!ctx->refined_valid) return fail(ctx, A3_ERR_INVALID, "a3_get_refined_corners: the last collected batch ran without corner refinement");
+    const size_t total = ctx->h_refined.size() / 8;
+    *n = total;
+    if (total > cap_markers) return fail(ctx, A3_ERR_CAPACITY, "a3_get_refined_corners: cap_markers is smaller than the number of markers");
+    if (total) memcpy(dst_xy, ctx->h_refined.data(), total * 8 * sizeof(float));
+    return A3_OK;
+}
+
+int a3_refine_corners(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride, float* corners_xy,
+                      const float* cell_px, size_t n) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!corners_xy && n) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: null corners");
+    if (ctx->pending.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: a submitted batch has not been collected");
+    if (n == 0) return A3_OK;
+    if (width == 0 || height == 0) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: empty image");
+    if (n > (1u << 30)) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: more than 2^30 corners in one call");
+    for (size_t k = 0; k < n; k++) {   // (the kernel's tile origin is an int near the corner)
+        const float x = corners_xy[2 * k], y = corners_xy[2 * k + 1];
+        if (!(x >= -64.0f && x <= (float)width + 64.0f && y >= -64.0f && y <= (float)height + 64.0f))
+            return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: a corner is not finite or lies more than 64 px outside the frame");
+    }
+    a3_refine_config cfg = ctx->refine;
+    if (cfg.method == A3_REFINE_NONE) a3_default_refine_config(&cfg);
+    size_t frame_stride = 0;
+    const uint8_t* d_pixels = nullptr;
+    const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, 1, &d_pixels);
+    if (rc != A3_OK) return rc == kNothingToDo ? A3_OK : rc;
+    const size_t pts_bytes = n * 2 * sizeof(float), cell_off = (pts_bytes + 255) & ~(size_t)255;
+    A3_HIP(ctx->tmp_a.ensure(cell_off + (cell_px ? n * sizeof(float) : 0)));
+    A3_HIP(ctx->tmp_b.ensure(pts_bytes));
+    float* d_pts = ctx->tmp_a.as<float>();
+    float* d_cell = cell_px ? reinterpret_cast<float*>(ctx->tmp_a.as<uint8_t>() + cell_off) : nullptr;
+    A3_HIP(hipMemcpyAsync(d_pts, corners_xy, pts_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (cell_px) A3_HIP(hipMemcpyAsync(d_cell, cell_px, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(launch_refine_corners(ctx->stream, PixelSrc{d_pixels, row_stride, frame_stride, fmt}, width, height, nullptr, nullptr, d_pts, d_cell, (uint32_t)n,
+                                 refine_params_for(ctx, cfg), ctx->tmp_b.as<float>()));
+    A3_HIP(hipMemcpyAsync(corners_xy, ctx->tmp_b.p, pts_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }
 

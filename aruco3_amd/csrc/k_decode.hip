@@ -1142,7 +1142,8 @@ __device__ void solve_normalized(const float pts[8], float marker_size_mm, a3_po
     if (a.error < b.error) { *o1 = a; *o2 = b; } else { *o1 = b; *o2 = a; }
 }
 
-// mode 0: pts = corners / (w,h) (solve_with_undistorted_points); 1: unproject through intrinsics; 2: already normalised
+// mode 0: pts = corners / (w,h) (solve_with_undistorted_points); 1: unproject through intrinsics; 2: already normalised;
+// 3 / 4: as 0 / 1 from float corners in norm_pts (8 per marker: the refined corners of a3_set_corner_refinement)
 // corner_stride: u32 words between the corner lists of consecutive markers (8 for a packed list, 14 inside a3_marker[]);
 // n_dev (optional): marker count produced on the device by k_compact_markers.
 __global__ void k_pose(const uint32_t* __restrict__ corners, uint32_t corner_stride, const float* __restrict__ norm_pts, uint32_t n,
@@ -1154,8 +1155,9 @@ __global__ void k_pose(const uint32_t* __restrict__ corners, uint32_t corner_str
     float pts[8];
     for (int k = 0; k < 4; k++) {
         if (mode == 2) { pts[2 * k] = norm_pts[8 * i + 2 * k]; pts[2 * k + 1] = norm_pts[8 * i + 2 * k + 1]; continue; }
-        const float x = (float)corners[(size_t)corner_stride * i + 2 * k], y = (float)corners[(size_t)corner_stride * i + 2 * k + 1];
-        if (mode == 0) { pts[2 * k] = x / iw; pts[2 * k + 1] = y / ih; }            // src/pose.rs:60
+        const float x = mode >= 3 ? norm_pts[8 * i + 2 * k] : (float)corners[(size_t)corner_stride * i + 2 * k];
+        const float y = mode >= 3 ? norm_pts[8 * i + 2 * k + 1] : (float)corners[(size_t)corner_stride * i + 2 * k + 1];
+        if (mode == 0 || mode == 3) { pts[2 * k] = x / iw; pts[2 * k + 1] = y / ih; }   // src/pose.rs:60
         else { pts[2 * k] = (x - cx) / fx; pts[2 * k + 1] = (y - cy) / fy; }         // src/pinhole.rs:88-93
     }
     a3_pose p1, p2;

@@ -1,0 +1,161 @@
+// k_refine.hip -- sub-pixel corner refinement (a3_set_corner_refinement / a3_refine_corners).  Not part of the reference, which
+// keeps the integer contour corners: an extension stated in include/aruco3_hip.h, restated on the CPU by tests/refine_oracle.c
+// (a3o_refine_corners), which this kernel matches bit for bit.
+//
+// One wave64 per corner, four per workgroup (the four corners of one marker, or four consecutive caller corners).  The integer grey
+// levels any allowed estimate can touch are loaded into LDS once; every iteration after that is LDS and VALU only.  The estimate and
+// the five sums are wave-uniform (the xor butterfly leaves the same bits in every lane), so the iteration loop never diverges.
+#include <algorithm>
+#include <cmath>
+
+#include "a3_common.h"
+
+namespace a3 {
+
+constexpr int kRefineMaxWin = 10;
+// Estimates stay within w of the start q0 (the revert rule), samples lie within w + 1 of an estimate, and a bilinear sample reads
+// floor(x) and floor(x) + 1: 4w + 4 columns from floor(q0.x) - 2w - 1.  One guard column / row on each side absorbs the rounding
+// of c + i in float: 4w + 6, 46 at w = 10 (2116 bytes per wave).
+constexpr int kRefineTile = 4 * kRefineMaxWin + 6;
+
+struct RefineParams {
+    uint32_t win_half, max_iterations, cells;
+    float relative_win, min_shift;
+    float g[kRefineMaxWin + 1][2 * kRefineMaxWin + 1];   // g[w][i + w] = (float)exp(-(double)(i*i) / (double)(w*w)), host libm
+};
+
+// the contract's window: win_half, or min(win_half, max(2, floor(relative_win * cell_px))) (NaN -> 2)
+__device__ __forceinline__ int refine_window(const RefineParams& p, float cell_px) {
+    const int wh = (int)p.win_half;
+    if (!(p.relative_win > 0.0f)) return wh;
+    const float t = floorf(p.relative_win * cell_px);
+    const int v = t >= 2.0f ? (t >= (float)wh ? wh : (int)t) : 2;
+    return min(v, wh);
+}
+
+// into_luma8 grey level of pixel (x, y) of a frame (the grey plane K1 wrote, or the caller's pixel: same integers)
+__device__ __forceinline__ uint32_t refine_grey(const uint8_t* __restrict__ frame, unsigned long long row_stride, int fmt, uint32_t x, uint32_t y) {
+    const uint8_t* row = frame + (size_t)y * row_stride;
+    if (fmt == A3_FMT_L8 || fmt == kFmtGreyPlane) return row[x];
+    if (fmt == A3_FMT_RGB8) { const uint8_t* q = row + 3u * (size_t)x; return luma_of(q[0], q[1], q[2]); }
+    const uint8_t* q = row + 4u * (size_t)x;
+    return fmt == A3_FMT_BGRA8 ? luma_of(q[2], q[1], q[0]) : luma_of(q[0], q[1], q[2]);
+}
+
+// bilinear sample at (x, y) from the wave's tile (origin ox, oy; border replicate is baked into the tile), the contract's order
+__device__ __forceinline__ float refine_sample(const uint8_t* __restrict__ tile, int T, int ox, int oy, float x, float y) {
+    const float x0f = floorf(x), y0f = floorf(y);
+    const float fx = x - x0f, fy = y - y0f;
+    const int tx = min(max((int)x0f - ox, 0), T - 2), ty = min(max((int)y0f - oy, 0), T - 2);   // (a guard: never active, see kRefineTile)
+    const uint8_t* r = tile + ty * T + tx;
+    const float i00 = (float)r[0], i01 = (float)r[1], i10 = (float)r[T], i11 = (float)r[T + 1];
+    return (1.0f - fy) * ((1.0f - fx) * i00 + fx * i01) + fy * ((1.0f - fx) * i10 + fx * i11);
+}
+
+// markers != nullptr: the accepted markers of a batch (min(n, *n_dev) of them), 4 corners each, window from the quad's cell size.
+// markers == nullptr: n caller corners `pts` of frame 0, window from cell_px[k] (nullable).  out: x, y per corner, in corner order.
+__global__ __launch_bounds__(256) void k_refine_corners(PixelSrc src, uint32_t W, uint32_t H, const a3_marker* __restrict__ markers,
+                                                        const unsigned int* __restrict__ n_dev, const float* __restrict__ pts,
+                                                        const float* __restrict__ cell_px, uint32_t n, RefineParams p, float* __restrict__ out) {
+    __shared__ uint8_t s_tile[4][kRefineTile * kRefineTile];
+    __shared__ float s_g[4][2 * kRefineMaxWin + 1];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t units = markers ? min(n, *n_dev) : (n + 3u) / 4u;
+    const float eps2 = p.min_shift * p.min_shift;
+    for (uint32_t u = blockIdx.x; u < units; u += gridDim.x) {   // (uniform over the workgroup: the barriers below are safe)
+        const uint32_t k = u * 4u + (uint32_t)wave;
+        const bool live = markers || k < n;
+        float q0x = 0.0f, q0y = 0.0f, cell = __builtin_nanf("");
+        uint32_t frame = 0;
+        if (markers) {
+            const uint32_t* c = markers[u].corners;
+            float best = 0.0f;
+            for (int e = 0; e < 4; e++) {   // shortest side (a3o_quad_cell_px)
+                const int e2 = (e + 1) & 3;
+                const float dx = (float)c[2 * e2] - (float)c[2 * e], dy = (float)c[2 * e2 + 1] - (float)c[2 * e + 1];
+                const float len = sqrtf(dx * dx + dy * dy);
+                if (e == 0 || len < best) best = len;
+            }
+            cell = best / (float)p.cells;
+            q0x = (float)c[2 * wave]; q0y = (float)c[2 * wave + 1];
+            frame = markers[u].frame;
+        } else if (live) {
+            q0x = pts[2 * k]; q0y = pts[2 * k + 1];
+            if (cell_px) cell = cell_px[k];
+        }
+        const int w = markers || cell_px ? refine_window(p, cell) : (int)p.win_half;
+        const int T = 4 * w + 6;
+        const int ox = (int)floorf(q0x) - 2 * w - 2, oy = (int)floorf(q0y) - 2 * w - 2;
+        uint8_t* tile = s_tile[wave];
+        if (live) {
+            const uint8_t* fb = src.base + (size_t)frame * src.frame_stride;
+            for (int t = lane; t < T * T; t += 64) {
+                const int x = min(max(ox + t % T, 0), (int)W - 1), y = min(max(oy + t / T, 0), (int)H - 1);
+                tile[t] = (uint8_t)refine_grey(fb, src.row_stride, src.fmt, (uint32_t)x, (uint32_t)y);
+            }
+            if (lane <= 2 * w) s_g[wave][lane] = p.g[w][lane];
+        }
+        __syncthreads();
+        if (live) {
+            const float* g = s_g[wave];
+            const int side = 2 * w + 1, npx = side * side;
+            float cx = q0x, cy = q0y;
+            for (uint32_t it = 0; it < p.max_iterations; it++) {
+                float a = 0.0f, b = 0.0f, c2 = 0.0f, bb1 = 0.0f, bb2 = 0.0f;
+                for (int q = lane; q < npx; q += 64) {   // lane l: pixels l, l + 64, ... of the window, row-major
+                    const int i = q % side - w, j = q / side - w;
+                    const float m = g[i + w] * g[j + w];
+                    const float gx = refine_sample(tile, T, ox, oy, cx + (float)(i + 1), cy + (float)j) -
+                                     refine_sample(tile, T, ox, oy, cx + (float)(i - 1), cy + (float)j);
+                    const float gy = refine_sample(tile, T, ox, oy, cx + (float)i, cy + (float)(j + 1)) -
+                                     refine_sample(tile, T, ox, oy, cx + (float)i, cy + (float)(j - 1));
+                    const float fi = (float)i, fj = (float)j;
+                    a += gx * gx * m;
+                    b += gx * gy * m;
+                    c2 += gy * gy * m;
+                    bb1 += gx * gx * m * fi + gx * gy * m * fj;
+                    bb2 += gx * gy * m * fi + gy * gy * m * fj;
+                }
+                for (int o = 32; o >= 1; o >>= 1) {   // xor butterfly: a + b == b + a, so every lane ends with the same bits
+                    a += __shfl_xor(a, o); b += __shfl_xor(b, o); c2 += __shfl_xor(c2, o);
+                    bb1 += __shfl_xor(bb1, o); bb2 += __shfl_xor(bb2, o);
+                }
+                const float det = a * c2 - b * b;
+                if (det == 0.0f || !isfinite(det)) break;
+                const float s = 1.0f / det;
+                const float nx = cx + (c2 * s * bb1 - b * s * bb2), ny = cy + (-b * s * bb1 + a * s * bb2);
+                if (!(fabsf(nx - q0x) <= (float)w && fabsf(ny - q0y) <= (float)w)) { cx = q0x; cy = q0y; break; }
+                const float dx = nx - cx, dy = ny - cy;
+                cx = nx; cy = ny;
+                if (dx * dx + dy * dy <= eps2) break;
+            }
+            if (lane == 0) { out[2 * (size_t)k] = cx; out[2 * (size_t)k + 1] = cy; }
+        }
+        __syncthreads();   // (the next unit overwrites the tiles)
+    }
+}
+
+void refine_params(void* out, const a3_refine_config& cfg, uint32_t cells) {
+    RefineParams* p = reinterpret_cast<RefineParams*>(out);
+    p->win_half = cfg.win_half; p->max_iterations = cfg.max_iterations; p->cells = cells;
+    p->relative_win = cfg.relative_win; p->min_shift = cfg.min_shift;
+    for (int w = 0; w <= kRefineMaxWin; w++)
+        for (int k = 0; k <= 2 * kRefineMaxWin; k++) {
+            const int i = k - w;
+            p->g[w][k] = w > 0 && k <= 2 * w ? (float)exp(-(double)(i * i) / (double)(w * w)) : 0.0f;
+        }
+}
+
+size_t refine_params_bytes() { return sizeof(RefineParams); }
+
+// (grid: one workgroup per marker up to 1024, then a workgroup-stride loop; the marker count is read on the device)
+hipError_t launch_refine_corners(hipStream_t st, PixelSrc src, uint32_t W, uint32_t H, const a3_marker* markers, const unsigned int* n_dev,
+                                 const float* pts, const float* cell_px, uint32_t n, const void* params, float* out) {
+    const uint32_t units = markers ? n : (n + 3u) / 4u;
+    if (units == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_refine_corners, dim3(std::min<uint32_t>(units, 1024u)), dim3(256), 0, st, src, W, H, markers, n_dev, pts, cell_px, n,
+                       *reinterpret_cast<const RefineParams*>(params), out);
+    return hipGetLastError();
+}
+
+}  // namespace a3

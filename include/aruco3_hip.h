@@ -263,6 +263,47 @@ int  a3_estimate_pose(a3_ctx *ctx, const uint32_t *corners_xy, size_t n, float m
 /* pose::solve_with_normalized_points (src/pose.rs:64-81) */
 int  a3_estimate_pose_normalized(a3_ctx *ctx, const float *points_xy, size_t n, float marker_size_mm, a3_pose *out);
 
+/* Sub-pixel corner refinement.  NOT in the reference (its Marker.corners are the integer contour pixels approximate_polygon_dp kept,
+ * src/aruco.rs:8-13, and about half a pixel inside the black frame on an anti-aliased edge): an opt-in extension, off by default;
+ * with it off no launch, buffer, copy or result of a batch changes.  With it on, every accepted marker's four corners (a3_marker
+ * order) are refined on the device right after detection, and a3_detect_batch_pose* solve the poses from the refined corners.
+ * The algorithm (iterative gradient orthogonality, "cornerSubPix"), fixed to the bit -- tests/refine_oracle.c a3o_refine_corners
+ * restates it:
+ *   - grey levels are into_luma8 integers; pixel centres sit at integer coordinates; the start q0 is the integer corner;
+ *   - window half-width w: win_half, or, relative_win > 0, min(win_half, max(2, floorf(relative_win * cell_px))) with
+ *     cell_px = (shortest side of the quad, sqrtf of float squares) / (cells across the marker, black border included);
+ *   - weights m(i, j) = g(i) g(j), g(i) = (float)exp(-(double)(i*i) / (double)(w*w));
+ *   - one iteration at c: bilinear samples P at (c.x + i, c.y + j) (x0 = floor(x), fx = x - x0,
+ *     (1-fy)*((1-fx)*I00 + fx*I01) + fy*((1-fx)*I10 + fx*I11), no fused multiply-add, image coordinates clamped to the frame);
+ *     for (i, j) in [-w, w]^2: gx = P(i+1, j) - P(i-1, j), gy = P(i, j+1) - P(i, j-1), a += gx*gx*m, b += gx*gy*m, c2 += gy*gy*m,
+ *     bb1 += gx*gx*m*i + gx*gy*m*j, bb2 += gx*gy*m*i + gy*gy*m*j, summed by lane l of 64 over the row-major window indices
+ *     l, l + 64, ... and combined by an xor butterfly 32, 16, 8, 4, 2, 1;
+ *     det = a*c2 - b*b: 0 or not finite -> stop at c; else s = 1/det, c' = c + (c2*s*bb1 - b*s*bb2, -b*s*bb1 + a*s*bb2);
+ *     c' farther than w from q0 in x or y (or not finite) -> the corner is q0, stop; else c = c' and stop once
+ *     |c' - c|^2 <= min_shift^2 or after max_iterations.
+ * Out of scope: a3_pack_detections records keep their layout and carry the integer corners only. */
+enum { A3_REFINE_NONE = 0, A3_REFINE_SUBPIX = 1 };
+typedef struct a3_refine_config {
+    uint32_t method;          /* A3_REFINE_NONE (default) */
+    uint32_t win_half;        /* 5, 1 .. 10 */
+    float    relative_win;    /* 0.4; 0 = always win_half */
+    uint32_t max_iterations;  /* 30, at most 100 */
+    float    min_shift;       /* 0.01 px */
+} a3_refine_config;
+/* method A3_REFINE_SUBPIX, win_half 5, relative_win 0.4, max_iterations 30, min_shift 0.01 */
+void a3_default_refine_config(a3_refine_config *cfg);
+/* applies to batches submitted after the call; NULL or method NONE turns it off */
+int  a3_set_corner_refinement(a3_ctx *ctx, const a3_refine_config *cfg);
+/* refined corners of the last collected batch: 8 floats per marker, in the order of `out`, the corners in a3_marker order.
+ * A3_ERR_INVALID when that batch ran without refinement, A3_ERR_CAPACITY when cap_markers is short (*n says how many there are). */
+int  a3_get_refined_corners(a3_ctx *ctx, float *dst_xy, size_t cap_markers, size_t *n);
+/* stand-alone: refine n caller-given corners (x, y float pairs, in place, each within 64 px of the frame) of one frame -- a tracker's
+ * corners, or tests; cell_px (nullable) per corner for relative_win, NULL = always win_half.  The window and iteration settings are
+ * the context's (a3_set_corner_refinement) when refinement is on, a3_default_refine_config's otherwise.  Synchronous; not while a
+ * submitted batch is in flight. */
+int  a3_refine_corners(a3_ctx *ctx, const void *pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
+                       float *corners_xy, const float *cell_px, size_t n);
+
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);
 int  a3_calculate_tau(int device, const uint64_t *codes, size_t n_codes, uint8_t *tau);

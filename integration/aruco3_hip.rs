@@ -67,6 +67,8 @@ pub const A3_PROFILE_OFF: c_int = 0;
 pub const A3_PROFILE_STAGES: c_int = 1;
 pub const A3_PROFILE_THRESHOLD_ONLY: c_int = 2;
 pub const A3_PROFILE_THRESHOLD_SAMPLED: c_int = 3;
+pub const A3_REFINE_NONE: u32 = 0;
+pub const A3_REFINE_SUBPIX: u32 = 1;
 
 /// a3_config <-> DetectorConfig, src/aruco.rs:23-30
 #[repr(C)]
@@ -112,6 +114,17 @@ pub struct A3Intrinsics {
     pub focal_y: f32,
     pub principal_x: f32,
     pub principal_y: f32,
+}
+
+/// a3_refine_config: sub-pixel corner refinement (not in the reference; include/aruco3_hip.h states the algorithm)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3RefineConfig {
+    pub method: u32,
+    pub win_half: u32,
+    pub relative_win: f32,
+    pub max_iterations: u32,
+    pub min_shift: f32,
 }
 
 /// a3_stats: per-batch stage counters (the reference prints its rejects in debug builds, src/aruco.rs:163-164)
@@ -215,6 +228,11 @@ extern "C" {
     pub fn a3_estimate_pose_normalized(ctx: *mut A3Ctx, points_xy: *const f32, n: usize, marker_size_mm: f32,
                                        out: *mut A3Pose) -> c_int;
     pub fn a3_find_nearest(ctx: *mut A3Ctx, bits: *const u64, n: usize, idx: *mut u32, dist: *mut u8) -> c_int;
+    pub fn a3_default_refine_config(cfg: *mut A3RefineConfig);
+    pub fn a3_set_corner_refinement(ctx: *mut A3Ctx, cfg: *const A3RefineConfig) -> c_int;
+    pub fn a3_get_refined_corners(ctx: *mut A3Ctx, dst_xy: *mut f32, cap_markers: usize, n: *mut usize) -> c_int;
+    pub fn a3_refine_corners(ctx: *mut A3Ctx, pixels: *const c_void, memory: c_int, fmt: c_int, width: u32, height: u32,
+                             row_stride: usize, corners_xy: *mut f32, cell_px: *const f32, n: usize) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
@@ -514,7 +532,72 @@ const MAX_TAPPED_FRAMES: usize = 1024;
 /// most up to that many markers per frame.
 const MAX_MARKERS_PER_FRAME: usize = 65536;
 
+/// Sub-pixel corner refinement settings for `Detector::detect_refined` (an extension: the reference has no refinement).
+/// `Default` gives a3_default_refine_config's values.
+#[derive(Clone, Copy, Debug)]
+pub struct RefineConfig {
+    pub win_half: u32,       // 1..10
+    pub relative_win: f32,   // 0 = always win_half
+    pub max_iterations: u32, // at most 100
+    pub min_shift: f32,      // px
+}
+impl Default for RefineConfig {
+    fn default() -> Self {
+        RefineConfig { win_half: 5, relative_win: 0.4, max_iterations: 30, min_shift: 0.01 }
+    }
+}
+impl RefineConfig {
+    fn to_a3(&self) -> A3RefineConfig {
+        A3RefineConfig { method: A3_REFINE_SUBPIX, win_half: self.win_half, relative_win: self.relative_win,
+                         max_iterations: self.max_iterations, min_shift: self.min_shift }
+    }
+}
+
 impl Detector {
+    /// New (additive): `detect` plus the sub-pixel corners of every marker, in the order of `Detection.markers`, each
+    /// in `Marker.corners` order.  The Detection is the one `detect` returns; `Detector` itself gains no field (the setting
+    /// is handed to the shared context for this call only, under its lock).
+    pub fn detect_refined(&self, image: DynamicImage, refine: &RefineConfig) -> (Detection, Vec<[(f32, f32); 4]>) {
+        let populate = POPULATE.load(Ordering::Relaxed);
+        let slot = slot_for(self);
+        let mut ctx = slot.lock().unwrap();
+        let images = std::slice::from_ref(&image);
+        let p = pack(images, &mut ctx.staging);
+        ctx.check(unsafe { a3_set_debug_taps(ctx.raw, populate as c_int) }, "a3_set_debug_taps");
+        let cfg = refine.to_a3();
+        ctx.check(unsafe { a3_set_corner_refinement(ctx.raw, &cfg) }, "a3_set_corner_refinement");
+        let mut markers = vec![A3Marker::default(); 64];
+        let mut per = vec![0u32; 1];
+        let mut found = 0usize;
+        let rc = loop {
+            let rc = unsafe {
+                a3_detect_batch(ctx.raw, p.bytes as *const c_void, A3_MEM_HOST, p.fmt, p.width, p.height, p.width as usize * p.bpp,
+                                p.width as usize * p.height as usize * p.bpp, 1, markers.as_mut_ptr(), markers.len(), per.as_mut_ptr(),
+                                &mut found)
+            };
+            if rc == A3_ERR_CAPACITY && markers.len() < MAX_MARKERS_PER_FRAME {
+                markers.resize(markers.len() * 4, A3Marker::default());
+                continue;
+            }
+            break rc;
+        };
+        let mut xy = vec![0f32; 8 * found.max(1)];
+        let mut n = 0usize;
+        let rc2 = if rc == A3_OK { unsafe { a3_get_refined_corners(ctx.raw, xy.as_mut_ptr(), found.max(1), &mut n) } } else { rc };
+        unsafe { a3_set_corner_refinement(ctx.raw, std::ptr::null()) }; // the shared context goes back to the plain detect
+        ctx.check(rc, "a3_detect_batch");
+        ctx.check(rc2, "a3_get_refined_corners");
+        let mut det = Detection { grey: None, candidates: vec![], homographies: vec![], markers: markers[..found].iter().map(marker_of).collect() };
+        if populate {
+            fill_debug_outputs(&ctx, 0, p.width, p.height, self.config.homography_sample_size as u32, &mut det);
+        }
+        let refined = (0..n).map(|i| {
+            let q = &xy[8 * i..8 * i + 8];
+            [(q[0], q[1]), (q[2], q[3]), (q[4], q[5]), (q[6], q[7])]
+        }).collect();
+        (det, refined)
+    }
+
     /// src/aruco.rs:52-121, same signature.  One frame = a batch of one.
     pub fn detect(&self, image: DynamicImage) -> Detection {
         self.detect_batch(std::slice::from_ref(&image)).pop().unwrap()
