@@ -22,6 +22,10 @@ def __getattr__(name):
         from . import pose
 
         return getattr(pose, name)
+    if name in ("Board", "GridBoard", "BoardPose"):
+        from . import board
+
+        return getattr(board, name)
     if name == "pose":
         import importlib
 

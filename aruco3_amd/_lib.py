@@ -24,6 +24,8 @@ STAGE_THRESHOLD, STAGE_CONTOUR, STAGE_DECODE = 0, 1, 2
 # a3_stats.stepping & 0xFF (include/aruco3_hip.h A3_STEP_*)
 STEP_WHOLE, STEP_DECODE_DEFERRED, STEP_HELD_RELEASED_BY_LAST, STEP_HELD_RELEASED_EARLY, STEP_BURST_LAST, STEP_HELD = 0, 1, 2, 3, 4, 5
 REFINE_NONE, REFINE_SUBPIX = 0, 1
+BOARD_NONE, BOARD_OK = 0, 1
+BOARD_MAX_MARKERS = 1024
 STEP_NAMES = {0: "whole", 1: "decode_deferred", 2: "held_released_by_last", 3: "held_released_early", 4: "burst_last", 5: "held"}
 
 # every symbol include/aruco3_hip.h declares
@@ -35,6 +37,7 @@ SYMBOLS = [
     "a3_find_nearest", "a3_calculate_tau", "a3_set_profiling", "a3_get_profile",
     "a3_contour_count", "a3_download_contours", "a3_detection_record_bytes", "a3_pack_detections",
     "a3_default_refine_config", "a3_set_corner_refinement", "a3_get_refined_corners", "a3_refine_corners",
+    "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
 INTERNAL_SYMBOLS = ["a3_debug_set_k1_stream", "a3_debug_set_overlap", "a3_debug_set_k1_waves", "a3_debug_set_partition", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_mark_threshold", "a3_debug_set_hold", "a3_debug_launch_threshold", "a3_debug_stream_wait_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
@@ -87,6 +90,16 @@ class RefineConfig(C.Structure):
     """a3_refine_config: sub-pixel corner refinement (an extension beyond the reference; include/aruco3_hip.h states the algorithm)"""
     _fields_ = [("method", C.c_uint32), ("win_half", C.c_uint32), ("relative_win", C.c_float), ("max_iterations", C.c_uint32),
                 ("min_shift", C.c_float)]
+
+
+class BoardPoseRec(C.Structure):
+    """a3_board_pose: one board pose per frame (an extension beyond the reference; include/aruco3_hip.h states the solve)"""
+    _fields_ = [("status", C.c_uint32), ("markers_used", C.c_uint32), ("markers_rejected", C.c_uint32), ("iterations", C.c_uint32),
+                ("rms_px", C.c_float), ("alt_rms_px", C.c_float), ("rotation", C.c_float * 9), ("translation", C.c_float * 3)]
+
+
+BOARD_POSE_DTYPE = np.dtype([("status", "<u4"), ("markers_used", "<u4"), ("markers_rejected", "<u4"), ("iterations", "<u4"),
+                             ("rms_px", "<f4"), ("alt_rms_px", "<f4"), ("rotation", "<f4", (9,)), ("translation", "<f4", (3,))])
 
 
 class Stats(C.Structure):
@@ -249,6 +262,13 @@ def load():
         L.a3_get_refined_corners.argtypes = [vp, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.a3_refine_corners.restype = C.c_int
         L.a3_refine_corners.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, f32p, f32p, C.c_size_t]
+    if hasattr(L, "a3_set_board"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack the board pose)
+        L.a3_set_board.restype = C.c_int
+        L.a3_set_board.argtypes = [vp, u32p, f32p, C.c_size_t]
+        L.a3_get_board_poses.restype = C.c_int
+        L.a3_get_board_poses.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.a3_estimate_board_pose.restype = C.c_int
+        L.a3_estimate_board_pose.argtypes = [vp, u32p, f32p, C.c_size_t, C.POINTER(Intrinsics), C.c_uint32, C.c_uint32, C.POINTER(BoardPoseRec)]
     L.a3_debug_discard_too_near.restype = C.c_int
     L.a3_debug_discard_too_near.argtypes = [vp, u32p, C.c_size_t, C.c_float, u32p, C.POINTER(C.c_size_t)]
     _lib = L
@@ -474,6 +494,43 @@ class Context:
         check(load().a3_refine_corners(self.handle, C.c_void_p(pixels_ptr), memory, fmt, width, height, row_stride, _p(xy, C.c_float),
                                        None if cp is None else _p(cp, C.c_float), xy.shape[0]), self.handle)
         return xy
+
+    # ---- board pose ----
+    def set_board(self, ids=None, corners=None):
+        """a3_set_board: ids (n,), corners (n, 4, 2) float in board units; None / empty clears it; applies to batches submitted afterwards"""
+        if ids is None or len(ids) == 0:
+            check(load().a3_set_board(self.handle, None, None, 0), self.handle)
+            return
+        i = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 8))
+        if c.shape[0] != i.size:
+            raise ValueError("set_board needs four corners per id")
+        check(load().a3_set_board(self.handle, _p(i, C.c_uint32), _p(c, C.c_float), i.size), self.handle)
+
+    def board_poses(self) -> np.ndarray:
+        """a3_get_board_poses: BOARD_POSE_DTYPE records of the last collected batch, one per frame"""
+        n = C.c_size_t()
+        L = load()
+        rc = L.a3_get_board_poses(self.handle, None, 0, C.byref(n))
+        if rc not in (OK, ERR_CAPACITY):
+            check(rc, self.handle)
+        out = np.zeros(max(n.value, 1), dtype=BOARD_POSE_DTYPE)
+        check(L.a3_get_board_poses(self.handle, out.ctypes.data_as(C.c_void_p), max(n.value, 1), C.byref(n)), self.handle)
+        return out[: n.value]
+
+    def estimate_board_pose(self, ids, corners, image_size=None, intrinsics: "Intrinsics" = None) -> np.ndarray:
+        """a3_estimate_board_pose (stand-alone, one frame): ids (n,), image corners (n, 4, 2) in pixels -> one BOARD_POSE_DTYPE record"""
+        i = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 8))
+        if c.shape[0] != i.size:
+            raise ValueError("estimate_board_pose needs four corners per id")
+        iw, ih = image_size if image_size else (0, 0)
+        rec = BoardPoseRec()
+        check(load().a3_estimate_board_pose(self.handle, _p(i, C.c_uint32), _p(c, C.c_float), i.size, C.byref(intrinsics) if intrinsics else None,
+                                            iw, ih, C.byref(rec)), self.handle)
+        out = np.zeros(1, dtype=BOARD_POSE_DTYPE)
+        C.memmove(out.ctypes.data, C.addressof(rec), C.sizeof(rec))
+        return out[0]
 
     # ---- Detection.grey / thresholded / candidates / homographies of the last batch ----
     def download_grey(self, frame: int, w: int, h: int, thresholded: bool = False) -> np.ndarray:

@@ -104,11 +104,12 @@ class Detector:
     """`Detector { config, dictionary }` (src/aruco.rs:46-49)."""
 
     def __init__(self, config: DetectorConfig = None, dictionary: ARDictionary = None, device: int = 0,
-                 refinement: Optional[CornerRefinement] = None):
+                 refinement: Optional[CornerRefinement] = None, board=None):
         self.config = config or DetectorConfig()
         self.dictionary = dictionary or ARDictionary.new_from_named_dict("ARUCO")
         self.device = device
         self.refinement = refinement
+        self.board = board   # aruco3_amd.board.Board: detect_batch_with_board_pose solves one pose per frame from it
         self._ctx = None
         self._ctx_key = None
 
@@ -117,6 +118,15 @@ class Detector:
         r = self.refinement
         ctx.set_corner_refinement(r._c() if r is not None else None)
         return r is not None
+
+    def _apply_board(self, ctx: _lib.Context) -> bool:
+        """hands the detector's board to the context before a pose call -> whether one is set"""
+        b = self.board
+        applied = getattr(self, "_board_applied", None)
+        if applied is None or applied[0] is not ctx or applied[1] is not b:   # (a3_set_board re-uploads the tables: only on a change)
+            ctx.set_board(None if b is None else b.ids, None if b is None else b.corners)
+            self._board_applied = (ctx, b)
+        return b is not None
 
     def _context(self) -> _lib.Context:
         key = (tuple(vars(self.config).items()), id(self.dictionary), self.device)
@@ -188,6 +198,30 @@ class Detector:
             pos += int(per[f])
             out.append((det, pp))
         return out
+
+    def detect_batch_with_board_pose(self, images, intrinsics=None, marker_size_mm: float = 1.0, stream: int = None, out_cap: int = 0):
+        """detect + one board pose per frame (the detector's `board`), solved on the device from every board marker of the frame
+        (include/aruco3_hip.h states the solve).  -> [(Detection, BoardPose)]; the per-marker poses of the same call are solved too
+        (with `marker_size_mm`) and left out here -- detect_batch_with_pose returns them."""
+        from .board import BoardPose
+
+        if self.board is None:
+            raise ValueError("detect_batch_with_board_pose needs Detector(board=...)")
+        ctx = self._context()
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
+        if stream is not None:
+            ctx.set_stream(stream)
+        ctx.set_debug_taps(False)
+        refine = self._apply_refinement(ctx)
+        self._apply_board(ctx)
+        intr = None
+        if intrinsics is not None:
+            ci = intrinsics
+            intr = _lib.Intrinsics(ci.image_width, ci.image_height, ci.focal_x, ci.focal_y, ci.principal_x, ci.principal_y)
+        markers, per, _ = ctx.detect_batch_pose(ptr, mem, fmt, w, h, rs, fs, n, marker_size_mm, intr, out_cap)
+        refined = ctx.refined_corners() if refine else None
+        boards = ctx.board_poses()
+        return [(d, BoardPose._from(boards[f])) for f, d in enumerate(_detections(markers, per, refined))]
 
     def detect_batch_raw(self, images, stream: int = None, out_cap: int = 0):
         """Batch entry without Python object construction: (structured marker array, per-frame counts)."""

@@ -69,6 +69,10 @@ size_t refine_params_bytes();
 void refine_params(void*, const a3_refine_config&, uint32_t);
 hipError_t launch_refine_corners(hipStream_t, PixelSrc, uint32_t, uint32_t, const a3_marker*, const unsigned int*, const float*, const float*, uint32_t,
                                  const void*, float*);
+size_t board_slot_bytes();
+void board_slot_from(const float*, void*);
+hipError_t launch_board_pose(hipStream_t, const a3_marker*, const uint32_t*, const float*, const float*, const unsigned int*, const uint32_t*,
+                             uint32_t, uint32_t, const uint16_t*, uint32_t, const void*, const a3_intrinsics*, uint32_t, uint32_t, a3_board_pose*);
 hipError_t launch_calc_tau(hipStream_t, const uint64_t*, uint32_t, unsigned int*);
 hipError_t launch_synth_render(hipStream_t, const a3_synth_frame*, uint32_t, const a3_synth_marker*, uint32_t, uint32_t, int, float, float, int,
                                uint8_t*, size_t, size_t);
@@ -130,6 +134,7 @@ struct BackArgs {
     int profiling = 0;
     a3_refine_config refine{};   // the batch's corner refinement (method NONE: none)
     size_t refine_bytes = 0;     // 32 (8 floats per marker) with refinement, else 0
+    bool board = false;          // a pose batch with a board: k_board_pose runs behind k_pose
 };
 
 // what finish_batch needs to know about the batch enqueue_batch put on the stream
@@ -147,6 +152,7 @@ struct Pending {
     // a held chain and a re-run use this copy)
     a3_refine_config refine{};
     size_t refine_bytes = 0;
+    bool board = false;   // a pose batch submitted with a board set (the board's device tables were brought up to date at submit)
 };
 
 }  // namespace
@@ -257,6 +263,17 @@ struct a3_ctx {
     DevBuf refined_buf;          // refined corners of the last batch on the device (8 floats per marker, marker order)
     std::vector<float> h_refined;
     bool refined_valid = false;  // the last collected batch ran with refinement: h_refined holds its corners
+    // a3_set_board: the board later batches capture (board_ids; board_slots: one BoardSlot record per marker) and its device tables
+    // (id -> slot, slot records), brought up to date at the next submit when board_version moved -- never while a batch of this
+    // context is in flight, so a batch keeps the board it was submitted with
+    std::vector<uint32_t> board_ids;
+    std::vector<uint8_t> board_slots;
+    uint64_t board_version = 0, board_dev_version = 0;
+    std::vector<uint16_t> board_slot_up;   // (the sources of the last upload, untouched until the next one)
+    std::vector<uint8_t> board_slots_up;
+    DevBuf board_slot_of, board_slot_rec, board_buf;   // id -> slot (n_codes x u16), slot records, board poses of the last batch (per frame)
+    std::vector<a3_board_pose> h_board;
+    bool board_valid = false;   // the last collected batch was a pose batch with a board: h_board holds its poses
     void* pinned = nullptr;
     size_t pinned_cap = 0;
     // debug taps: per-frame candidate counts of the last batch (before / after discard_too_near), read back with the results so
@@ -489,6 +506,10 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const BackArgs& b) {
             A3_HIP(launch_pose(st, reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(ctx->markers_ptr) + offsetof(a3_marker, corners)),
                                (uint32_t)(sizeof(a3_marker) / 4), nullptr, b.marker_cap, d_marker_total, b.pose_has_intr ? 1 : 0, b.pose_size_mm,
                                (float)b.W, (float)b.H, in.focal_x, in.focal_y, in.principal_x, in.principal_y, ctx->pose_buf.as<a3_pose>()));
+        if (b.board)   // one board pose per frame from the same device-resident markers (and refined corners), no extra round trip
+            A3_HIP(launch_board_pose(st, ctx->markers_ptr, nullptr, nullptr, b.refine_bytes ? ctx->refined_buf.as<float>() : nullptr, d_marker_total,
+                                     ctx->per_frame, b.marker_cap, b.n, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p,
+                                     b.pose_has_intr ? &in : nullptr, b.W, b.H, ctx->board_buf.as<a3_board_pose>()));
     }
     if (b.profiling >= 2) A3_HIP(hipEventRecord(ctx->ev[3], st));
     // ---- results: one copy of [scratch | counters | per-frame counts | `guess` markers], then the poses and (taps) the counts ----
@@ -499,6 +520,9 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const BackArgs& b) {
     if (b.refine_bytes)   // (staged behind the poses)
         A3_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(h_poses) + (size_t)b.guess * b.pose_bytes, ctx->refined_buf.p, (size_t)b.guess * b.refine_bytes,
                               hipMemcpyDeviceToHost, st));
+    if (b.board)   // (staged behind the refined corners; one record per frame, whatever the marker count)
+        A3_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(h_poses) + (size_t)b.guess * (b.pose_bytes + b.refine_bytes), ctx->board_buf.p,
+                              (size_t)b.n * sizeof(a3_board_pose), hipMemcpyDeviceToHost, st));
     if (b.taps) {   // Detection.candidates / .homographies will be asked for frame by frame: their counts travel now
         A3_HIP(hipMemcpyAsync(ctx->pinned_counts, ctx->cand_count, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
         A3_HIP(hipMemcpyAsync((uint8_t*)ctx->pinned_counts + (size_t)b.n * 4, ctx->fin_count.p, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
@@ -628,7 +652,9 @@ int ensure_chain_buffers(a3_ctx* ctx, hipStream_t st, uint32_t n, uint32_t W, ui
     if (ctx->want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)marker_cap * 2 * sizeof(a3_pose)));
     const size_t refine_bytes = ctx->pending.refine.method != A3_REFINE_NONE ? 8 * sizeof(float) : 0;
     if (refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)marker_cap * refine_bytes));
-    if (int rc = ensure_pinned(ctx, z.head_bytes + (size_t)marker_guess_of(ctx, marker_cap) * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + (1 << 16))) return rc;
+    const size_t board_bytes = ctx->pending.board ? (size_t)n * sizeof(a3_board_pose) : 0;
+    if (board_bytes) A3_HIP(ctx->board_buf.ensure(board_bytes));
+    if (int rc = ensure_pinned(ctx, z.head_bytes + (size_t)marker_guess_of(ctx, marker_cap) * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + board_bytes + (1 << 16))) return rc;
     if (ctx->debug_taps && ctx->pinned_counts_cap < (size_t)n * 8) {
         if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
         ctx->pinned_counts = nullptr; ctx->pinned_counts_cap = 0;
@@ -908,7 +934,10 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
     if (ctx->want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)marker_cap * 2 * sizeof(a3_pose)));
     const size_t refine_bytes = ctx->pending.refine.method != A3_REFINE_NONE ? 8 * sizeof(float) : 0;   // (captured at submit)
     if (refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)marker_cap * refine_bytes));
-    if (int rc = ensure_pinned(ctx, head_pad + (size_t)guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + (1 << 16))) return rc;
+    const bool board = ctx->pending.board;   // (captured at submit)
+    const size_t board_bytes = board ? (size_t)n * sizeof(a3_board_pose) : 0;
+    if (board_bytes) A3_HIP(ctx->board_buf.ensure(board_bytes));
+    if (int rc = ensure_pinned(ctx, head_pad + (size_t)guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + board_bytes + (1 << 16))) return rc;
     ctx->counts_valid = false;
     if (ctx->debug_taps && ctx->pinned_counts_cap < (size_t)n * 8) {
         if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -921,7 +950,7 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
     bk.min_corner_separation = min_corner_separation; bk.src = src; bk.head_bytes = head_bytes; bk.pose_bytes = pose_bytes;
     bk.taps = ctx->debug_taps; bk.want_pose = ctx->want_pose; bk.pose_has_intr = ctx->pose_has_intr; bk.pose_size_mm = ctx->pose_size_mm;
     bk.pose_intr = ctx->pose_intr; bk.profiling = prof;
-    bk.refine = ctx->pending.refine; bk.refine_bytes = refine_bytes;
+    bk.refine = ctx->pending.refine; bk.refine_bytes = refine_bytes; bk.board = board;
     // Deferral: only for submitted batches (somebody will submit again or collect), and not while every stage is being timed
     // (the stage times are those of stages that run alone).  The decode stage then waits on the context's decode stream until
     // (a) another context submits a batch -- it is released behind that batch's threshold kernel and shares the GPU with its
@@ -1046,6 +1075,10 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
     uint32_t max_per_frame = 0;   // (read now: the staging buffer may be re-allocated below)
     for (uint32_t f = 0; f < n; f++) max_per_frame = std::max(max_per_frame, hpf[f]);
     const uint32_t n_work = hs[0], n_pre = hs[2];
+    if (pd.board) {   // (read now: the staging buffer may be re-allocated below)
+        const a3_board_pose* hb = reinterpret_cast<const a3_board_pose*>(hp + head_pad + (size_t)guess * (sizeof(a3_marker) + pose_bytes + refine_bytes));
+        ctx->h_board.assign(hb, hb + n);
+    }
     const uint32_t tap_contours = n_chunks ? hc[0].contours : 0u; const uint64_t tap_points = n_chunks ? hc[0].points : 0ull;
     if (total > guess) {   // the guess was short: the staging area grows (the head has been consumed) and the whole list is fetched
         if (int rc = ensure_pinned(ctx, (size_t)total * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + (1 << 16))) return rc;
@@ -1063,6 +1096,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
     }
     if (refine_bytes) ctx->h_refined.assign(h_refined, h_refined + (size_t)total * 8);
     ctx->refined_valid = refine_bytes != 0;
+    ctx->board_valid = pd.board;
     if (pd.taps) {
         const uint32_t* hc32 = reinterpret_cast<const uint32_t*>(ctx->pinned_counts);
         ctx->h_cand_pre.assign(hc32, hc32 + n);
@@ -1220,7 +1254,8 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->leader_list, &ctx->leader_keep, &ctx->entry_list, &ctx->es_a, &ctx->es_b,
                       &ctx->contours, &ctx->cyc_start_off, &ctx->points, &ctx->zero_blk, &ctx->cands,
                       &ctx->pre_xy, &ctx->fin_xy, &ctx->fin_count, &ctx->work, &ctx->outs, &ctx->proj, &ctx->patches, &ctx->cand_big,
-                      &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf};
+                      &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
+                      &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1366,6 +1401,21 @@ static int stage_input(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
     return A3_OK;
 }
 
+// the board's device tables (id -> slot, slot records) for the board set now, when they are not current: at submit (no batch of this
+// context in flight), on the context's stream ahead of the batch
+static int upload_board(a3_ctx* ctx) {
+    if (ctx->board_dev_version == ctx->board_version) return A3_OK;
+    ctx->board_slot_up.assign(std::max<size_t>(ctx->n_codes, 1), 0xFFFF);
+    for (size_t i = 0; i < ctx->board_ids.size(); i++) ctx->board_slot_up[ctx->board_ids[i]] = (uint16_t)i;
+    ctx->board_slots_up = ctx->board_slots;
+    A3_HIP(ctx->board_slot_of.ensure(ctx->board_slot_up.size() * 2));
+    A3_HIP(ctx->board_slot_rec.ensure(ctx->board_slots_up.size()));
+    A3_HIP(hipMemcpyAsync(ctx->board_slot_of.p, ctx->board_slot_up.data(), ctx->board_slot_up.size() * 2, hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(ctx->board_slot_rec.p, ctx->board_slots_up.data(), ctx->board_slots_up.size(), hipMemcpyHostToDevice, ctx->stream));
+    ctx->board_dev_version = ctx->board_version;
+    return A3_OK;
+}
+
 static int run_batch_with_retries(a3_ctx* ctx, const uint8_t* d_pixels, int fmt, uint32_t width, uint32_t height, size_t row_stride,
                                   size_t frame_stride, uint32_t n_frames, a3_marker* out, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
     for (int attempt = 0; attempt < 8; attempt++) {
@@ -1383,14 +1433,18 @@ int a3_detect_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32
     *out_n = 0;
     if (ctx->pending.active) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");
     ctx->pending.refine = ctx->refine;
+    ctx->pending.board = ctx->want_pose && !ctx->board_ids.empty();
+    ctx->board_valid = false;
     const uint8_t* d_pixels = nullptr;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, n_frames, &d_pixels);
     if (rc == kNothingToDo) {
         if (per_frame_count && n_frames) memset(per_frame_count, 0, (size_t)n_frames * 4);
         ctx->h_refined.clear(); ctx->refined_valid = ctx->refine.method != A3_REFINE_NONE;
+        ctx->h_board.assign(n_frames, a3_board_pose{}); ctx->board_valid = ctx->pending.board;
         return A3_OK;
     }
     if (rc != A3_OK) return rc;
+    if (ctx->pending.board) { if (int urc = upload_board(ctx)) return urc; }
     ctx->force_host_plan = false;
     ctx->reruns = 0; ctx->released_others = 0;
     return run_batch_with_retries(ctx, d_pixels, fmt, width, height, row_stride, frame_stride, n_frames, out, out_cap, per_frame_count, out_n);
@@ -1400,10 +1454,13 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
                          size_t frame_stride, uint32_t n_frames, size_t out_cap, bool want_pose) {
     if (ctx->pending.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");
     ctx->pending.refine = ctx->refine;   // (the batch keeps the setting in force at its submit)
+    ctx->pending.board = want_pose && !ctx->board_ids.empty();   // (and the board)
+    ctx->board_valid = false;
     const uint8_t* d_pixels = nullptr;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, n_frames, &d_pixels);
     if (rc == kNothingToDo) { ctx->pending_trivial = true; ctx->pending.n = n_frames; return A3_OK; }
     if (rc != A3_OK) return rc;
+    if (ctx->pending.board) { if (int urc = upload_board(ctx)) return urc; }
     ctx->force_host_plan = false;
     ctx->want_pose = want_pose;
     Pending& pd = ctx->pending;
@@ -1468,6 +1525,7 @@ static int collect_common(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t ou
         ctx->pending_trivial = false;
         if (per_frame_count && ctx->pending.n) memset(per_frame_count, 0, (size_t)ctx->pending.n * 4);
         ctx->h_refined.clear(); ctx->refined_valid = ctx->pending.refine.method != A3_REFINE_NONE;
+        ctx->h_board.assign(ctx->pending.n, a3_board_pose{}); ctx->board_valid = ctx->pending.board;
         return A3_OK;
     }
     A3_HIP(hipSetDevice(ctx->device));
@@ -2032,6 +2090,79 @@ int a3_refine_corners(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint
     A3_HIP(launch_refine_corners(ctx->stream, PixelSrc{d_pixels, row_stride, frame_stride, fmt}, width, height, nullptr, nullptr, d_pts, d_cell, (uint32_t)n,
                                  refine_params_for(ctx, cfg), ctx->tmp_b.as<float>()));
     A3_HIP(hipMemcpyAsync(corners_xy, ctx->tmp_b.p, pts_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+// ---- board pose (an extension beyond the reference; contract in include/aruco3_hip.h) ----
+int a3_set_board(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size_t n) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (n > A3_BOARD_MAX_MARKERS) return fail(ctx, A3_ERR_INVALID, "a3_set_board: more than A3_BOARD_MAX_MARKERS markers");
+    if (n && (!ids || !corners_xy)) return fail(ctx, A3_ERR_INVALID, "a3_set_board: null ids or corners");
+    std::vector<uint8_t> seen(ctx->n_codes, 0);
+    std::vector<uint8_t> slots(n * board_slot_bytes());
+    for (size_t i = 0; i < n; i++) {
+        if (ids[i] >= ctx->n_codes) return fail(ctx, A3_ERR_INVALID, "a3_set_board: an id is not in the dictionary");
+        if (seen[ids[i]]++) return fail(ctx, A3_ERR_INVALID, "a3_set_board: an id appears twice on the board");
+        const float* c = corners_xy + 8 * i;
+        for (int k = 0; k < 8; k++)
+            if (!std::isfinite(c[k])) return fail(ctx, A3_ERR_INVALID, "a3_set_board: a corner is not finite");
+        double ex[4], ey[4];
+        for (int k = 0; k < 4; k++) { ex[k] = (double)c[2 * ((k + 1) & 3)] - c[2 * k]; ey[k] = (double)c[2 * ((k + 1) & 3) + 1] - c[2 * k + 1]; }
+        const double s = std::sqrt(ex[0] * ex[0] + ey[0] * ey[0]);
+        if (!(s > 0.0)) return fail(ctx, A3_ERR_INVALID, "a3_set_board: a marker has no size");
+        for (int k = 0; k < 4; k++) {
+            const int k1 = (k + 1) & 3;
+            if (std::fabs(std::sqrt(ex[k] * ex[k] + ey[k] * ey[k]) - s) > 1e-3 * s)
+                return fail(ctx, A3_ERR_INVALID, "a3_set_board: a marker's sides differ (its corners must form a square)");
+            if (std::fabs(ex[k] * ex[k1] + ey[k] * ey[k1]) > 1e-3 * s * s)
+                return fail(ctx, A3_ERR_INVALID, "a3_set_board: a marker's corners are not at right angles (they must form a square)");
+        }
+        if (!(ex[0] * ey[1] - ey[0] * ex[1] < 0.0))
+            return fail(ctx, A3_ERR_INVALID, "a3_set_board: a marker is wound the wrong way (corner order top-left, top-right, bottom-right, "
+                                             "bottom-left with y up)");
+        board_slot_from(c, slots.data() + i * board_slot_bytes());
+    }
+    ctx->board_ids.assign(ids, ids + n);
+    ctx->board_slots.swap(slots);
+    ctx->board_version++;
+    return A3_OK;
+}
+
+int a3_get_board_poses(a3_ctx* ctx, a3_board_pose* dst, size_t cap_frames, size_t* n) {
+    if (!ctx || !n || (!dst && cap_frames)) return A3_ERR_INVALID;
+    *n = 0;
+    if (!ctx->board_valid)
+        return fail(ctx, A3_ERR_INVALID, "a3_get_board_poses: the last collected batch was not a pose batch with a board set");
+    *n = ctx->h_board.size();
+    if (*n > cap_frames) return fail(ctx, A3_ERR_CAPACITY, "a3_get_board_poses: cap_frames is smaller than the number of frames");
+    if (*n) memcpy(dst, ctx->h_board.data(), *n * sizeof(a3_board_pose));
+    return A3_OK;
+}
+
+int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size_t n_markers, const a3_intrinsics* intr,
+                           uint32_t image_width, uint32_t image_height, a3_board_pose* out) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!out || (n_markers && (!ids || !corners_xy))) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: null argument");
+    if (ctx->pending.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: a submitted batch has not been collected");
+    if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: no board is set (a3_set_board)");
+    if (!intr && (image_width == 0 || image_height == 0)) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: empty image");
+    if (n_markers > (1u << 20)) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: more than 2^20 markers in one call");
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    if (int urc = upload_board(ctx)) return urc;
+    const size_t id_bytes = (n_markers * 4 + 255) & ~(size_t)255, pts_bytes = n_markers * 8 * sizeof(float);
+    A3_HIP(ctx->tmp_a.ensure(std::max<size_t>(id_bytes + pts_bytes, 256)));
+    A3_HIP(ctx->tmp_b.ensure(sizeof(a3_board_pose)));
+    uint32_t* d_ids = ctx->tmp_a.as<uint32_t>();
+    float* d_pts = reinterpret_cast<float*>(ctx->tmp_a.as<uint8_t>() + id_bytes);
+    if (n_markers) {
+        A3_HIP(hipMemcpyAsync(d_ids, ids, n_markers * 4, hipMemcpyHostToDevice, ctx->stream));
+        A3_HIP(hipMemcpyAsync(d_pts, corners_xy, pts_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    A3_HIP(launch_board_pose(ctx->stream, nullptr, d_ids, d_pts, nullptr, nullptr, nullptr, (uint32_t)n_markers, 1u, ctx->board_slot_of.as<uint16_t>(),
+                             ctx->n_codes, ctx->board_slot_rec.p, intr, image_width, image_height, ctx->tmp_b.as<a3_board_pose>()));
+    A3_HIP(hipMemcpyAsync(out, ctx->tmp_b.p, sizeof(a3_board_pose), hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }

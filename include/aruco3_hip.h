@@ -304,6 +304,62 @@ int  a3_get_refined_corners(a3_ctx *ctx, float *dst_xy, size_t cap_markers, size
 int  a3_refine_corners(a3_ctx *ctx, const void *pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
                        float *corners_xy, const float *cell_px, size_t n);
 
+/* Board pose.  NOT in the reference: an opt-in extension (OpenCV's estimatePoseBoard), off by default; with no board set no launch,
+ * buffer, copy or result of a batch changes.  A board is n markers (1 <= n <= A3_BOARD_MAX_MARKERS), each a dictionary id (unique,
+ * < the context's n_codes) and its four corners (x, y) in board units, a3_marker corner order, on the plane z = 0 with x to the right
+ * and y UP -- the convention of the IPPE solver's square (-hw, hw), (hw, hw), (hw, -hw), (-hw, -hw): corner 0 is the top-left.
+ * a3_set_board checks that each marker's corners form a square wound that way: with side s = |c1 - c0|, every side within 1e-3 s of
+ * s, every |e_k . e_(k+1)| <= 1e-3 s^2 (e_k = c_(k+1) - c_k) and e_0 x e_1 < 0; any in-plane rotation, position and size.  With
+ * a board set, every a3_detect_batch_pose* batch also solves one board pose per frame on the device (k_board_pose, right behind the
+ * per-marker poses), fixed as follows -- tests/board_oracle.c a3o_board_pose restates it:
+ *   - slot data (float, host, once per board): s as above (sqrtf of float squares), cs = (x1 - x0) / s, sn = (y1 - y0) / s,
+ *     c = (0.25f * ((x0 + x1) + (x2 + x3)), 0.25f * ((y0 + y1) + (y2 + y3)));
+ *   - correspondences: the frame's markers (batch order) whose id is on the board; an id seen more than once in the frame is
+ *     excluded in all its instances (counted in markers_rejected).  Image points are the integer corners, or the refined corners
+ *     with refinement on, normalised as the per-marker poses of the call: x / w, y / h without intrinsics, (x - cx) / fx,
+ *     (y - cy) / fy with them;
+ *   - start: of the used markers whose two IPPE poses (a3_estimate_pose_normalized of its normalised points with marker size s)
+ *     are finite, the one with the largest image quad (in pixels, 0.5f * |shoelace sum over corners 0..3 of x_k y_(k+1) -
+ *     x_(k+1) y_k|; ties: the lowest board slot); its two poses carried into the board frame: R_b = R_m Q^T, t_b = t_m - R_b c
+ *     with Q the in-plane rotation (cs, -sn; sn, cs);
+ *   - Levenberg-Marquardt from each start on the squared residuals r = (px / z', py / z') - m in the normalised plane, p = R X + t
+ *     ((R00 X + R01 Y) + t0, ...), z' = max(pz, 1e-5).  One evaluation builds, per used corner, with q = R X, a = 1 / z', u, v the
+ *     projection: J_u = (-2a u qy, 2a (qz + u qx), -2a qy, a, 0, -a u), J_v = (-2a (qz + v qy), 2a v qx, 2a qx, 0, a, -a v), and
+ *     sums J^T J (21 terms, upper triangle row by row), J^T r (6), the cost r.r and the pixel cost (ru sx)^2 + (rv sy)^2
+ *     ((sx, sy) = (w, h) or (fx, fy)), summed by lane l of 64 over the corners l, l + 64, ... (corner 4 i + k: corner k of the
+ *     frame's i-th marker; corners of markers not used add nothing) and combined by an xor butterfly 32, 16, 8, 4, 2, 1.
+ *     lambda = 1e-3; while evaluations < A3_BOARD_MAX_EVALS and cost > 0: solve (J^T J + lambda diag(J^T J)) d = -J^T r by
+ *     LDL^T (a pivot <= 0 or not finite: lambda *= 10, the attempt counts as a rejected evaluation); candidate R' = cay(w) R,
+ *     cay(w) = I + k ([w]x + [w]x^2), k = 2 / (1 + |w|^2), [w]x^2 = w w^T - |w|^2 I, t' = t + d[3..5]; evaluate it; a lower cost
+ *     is accepted (lambda /= 10; the loop ends when (cost - cost') / cost < A3_BOARD_REL_TOL), anything else rejected
+ *     (lambda *= 10).  The start with the lower final cost is kept (ties: the first IPPE pose);
+ *   - rms_px = sqrtf(pixel cost / corners used) of the kept start, alt_rms_px the other's.  A frame without a used marker, or
+ *     without one whose IPPE poses are finite, has status A3_BOARD_NONE, its counts, and zeros everywhere else.
+ * a3_pack_detections records keep their layout: board poses are not gathered across ranks. */
+#define A3_BOARD_MAX_MARKERS 1024
+#define A3_BOARD_MAX_EVALS   30
+#define A3_BOARD_REL_TOL     1e-6f
+enum { A3_BOARD_NONE = 0 /* no usable board marker in the frame */, A3_BOARD_OK = 1 };
+typedef struct a3_board_pose {
+    uint32_t status;
+    uint32_t markers_used;
+    uint32_t markers_rejected;   /* instances of board ids seen more than once in the frame */
+    uint32_t iterations;         /* LM evaluations of the kept start (the first one at the start included) */
+    float    rms_px;             /* RMS reprojection distance of the used corners, in pixels */
+    float    alt_rms_px;         /* the other start's final RMS: close to rms_px means the pose is ambiguous */
+    float    rotation[9];        /* board -> camera, row-major as a3_pose */
+    float    translation[3];     /* board units */
+} a3_board_pose;
+/* applies to batches submitted after the call; n == 0 clears the board.  corners_xy: 8 floats per marker. */
+int  a3_set_board(a3_ctx *ctx, const uint32_t *ids, const float *corners_xy, size_t n);
+/* the board poses of the last collected batch, one per frame.  A3_ERR_INVALID when that batch ran without a board or was not an
+ * a3_detect_batch_pose* batch, A3_ERR_CAPACITY when cap_frames is short (*n says how many there are). */
+int  a3_get_board_poses(a3_ctx *ctx, a3_board_pose *dst, size_t cap_frames, size_t *n);
+/* stand-alone, one frame: the board pose from n_markers caller-given markers (ids, 8 float corners each, in pixels), on the same
+ * kernel; intr NULL normalises by image_width / image_height.  Needs a board; synchronous; not while a submitted batch is in flight. */
+int  a3_estimate_board_pose(a3_ctx *ctx, const uint32_t *ids, const float *corners_xy, size_t n_markers, const a3_intrinsics *intr,
+                            uint32_t image_width, uint32_t image_height, a3_board_pose *out);
+
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);
 int  a3_calculate_tau(int device, const uint64_t *codes, size_t n_codes, uint8_t *tau);

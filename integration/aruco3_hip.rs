@@ -69,6 +69,9 @@ pub const A3_PROFILE_THRESHOLD_ONLY: c_int = 2;
 pub const A3_PROFILE_THRESHOLD_SAMPLED: c_int = 3;
 pub const A3_REFINE_NONE: u32 = 0;
 pub const A3_REFINE_SUBPIX: u32 = 1;
+pub const A3_BOARD_NONE: u32 = 0;
+pub const A3_BOARD_OK: u32 = 1;
+pub const A3_BOARD_MAX_MARKERS: usize = 1024;
 
 /// a3_config <-> DetectorConfig, src/aruco.rs:23-30
 #[repr(C)]
@@ -125,6 +128,20 @@ pub struct A3RefineConfig {
     pub relative_win: f32,
     pub max_iterations: u32,
     pub min_shift: f32,
+}
+
+/// a3_board_pose: one board pose per frame (not in the reference; include/aruco3_hip.h states the solve)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3BoardPose {
+    pub status: u32,
+    pub markers_used: u32,
+    pub markers_rejected: u32,
+    pub iterations: u32,
+    pub rms_px: f32,
+    pub alt_rms_px: f32,
+    pub rotation: [f32; 9],
+    pub translation: [f32; 3],
 }
 
 /// a3_stats: per-batch stage counters (the reference prints its rejects in debug builds, src/aruco.rs:163-164)
@@ -233,6 +250,10 @@ extern "C" {
     pub fn a3_get_refined_corners(ctx: *mut A3Ctx, dst_xy: *mut f32, cap_markers: usize, n: *mut usize) -> c_int;
     pub fn a3_refine_corners(ctx: *mut A3Ctx, pixels: *const c_void, memory: c_int, fmt: c_int, width: u32, height: u32,
                              row_stride: usize, corners_xy: *mut f32, cell_px: *const f32, n: usize) -> c_int;
+    pub fn a3_set_board(ctx: *mut A3Ctx, ids: *const u32, corners_xy: *const f32, n: usize) -> c_int;
+    pub fn a3_get_board_poses(ctx: *mut A3Ctx, dst: *mut A3BoardPose, cap_frames: usize, n: *mut usize) -> c_int;
+    pub fn a3_estimate_board_pose(ctx: *mut A3Ctx, ids: *const u32, corners_xy: *const f32, n_markers: usize, intr: *const A3Intrinsics,
+                                  image_width: u32, image_height: u32, out: *mut A3BoardPose) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
@@ -596,6 +617,52 @@ impl Detector {
             [(q[0], q[1]), (q[2], q[3]), (q[4], q[5]), (q[6], q[7])]
         }).collect();
         (det, refined)
+    }
+
+    /// New (additive): `detect` of one image plus the pose of a planar board (OpenCV's estimatePoseBoard), solved on the device
+    /// from every board marker of the image.  `board_ids[k]` is a dictionary index and `board_corners[k]` its four corners in board
+    /// units (z = 0, x right, y up, `Marker.corners` order: a square).  `marker_size_mm` sizes the per-marker poses the same call
+    /// solves (not returned here).  Panics, like the other calls, on an invalid board.  `Detector` itself gains no field: the board is
+    /// handed to the shared context for this call only, under its lock.
+    pub fn detect_board_pose(&self, image: DynamicImage, board_ids: &[u32], board_corners: &[[(f32, f32); 4]], marker_size_mm: f32,
+                             intrinsics: Option<&CameraIntrinsics>) -> (Detection, A3BoardPose) {
+        assert_eq!(board_ids.len(), board_corners.len(), "one corner quad per board id");
+        let slot = slot_for(self);
+        let mut ctx = slot.lock().unwrap();
+        let images = std::slice::from_ref(&image);
+        let p = pack(images, &mut ctx.staging);
+        ctx.check(unsafe { a3_set_debug_taps(ctx.raw, 0) }, "a3_set_debug_taps");
+        let xy: Vec<f32> = board_corners.iter().flat_map(|q| q.iter().flat_map(|&(x, y)| [x, y])).collect();
+        ctx.check(unsafe { a3_set_board(ctx.raw, board_ids.as_ptr(), xy.as_ptr(), board_ids.len()) }, "a3_set_board");
+        let intr = intrinsics.map(to_a3_intrinsics);
+        let intr_ptr = intr.as_ref().map_or(std::ptr::null(), |i| i as *const A3Intrinsics);
+        let mut cap = 64usize;
+        let mut markers = vec![A3Marker::default(); cap];
+        let mut poses = vec![A3Pose::default(); 2 * cap];
+        let mut per = vec![0u32; 1];
+        let mut found = 0usize;
+        let rc = loop {
+            let rc = unsafe {
+                a3_detect_batch_pose(ctx.raw, p.bytes as *const c_void, A3_MEM_HOST, p.fmt, p.width, p.height, p.width as usize * p.bpp,
+                                     p.width as usize * p.height as usize * p.bpp, 1, marker_size_mm, intr_ptr, markers.as_mut_ptr(),
+                                     poses.as_mut_ptr(), cap, per.as_mut_ptr(), &mut found)
+            };
+            if rc == A3_ERR_CAPACITY && cap < MAX_MARKERS_PER_FRAME {
+                cap *= 4;
+                markers.resize(cap, A3Marker::default());
+                poses.resize(2 * cap, A3Pose::default());
+                continue;
+            }
+            break rc;
+        };
+        let mut board = A3BoardPose::default();
+        let mut n = 0usize;
+        let rc2 = if rc == A3_OK { unsafe { a3_get_board_poses(ctx.raw, &mut board, 1, &mut n) } } else { rc };
+        unsafe { a3_set_board(ctx.raw, std::ptr::null(), std::ptr::null(), 0) }; // the shared context goes back to no board
+        ctx.check(rc, "a3_detect_batch_pose");
+        ctx.check(rc2, "a3_get_board_poses");
+        let det = Detection { grey: None, candidates: vec![], homographies: vec![], markers: markers[..found].iter().map(marker_of).collect() };
+        (det, board)
     }
 
     /// src/aruco.rs:52-121, same signature.  One frame = a batch of one.
