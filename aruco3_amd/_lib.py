@@ -40,7 +40,7 @@ SYMBOLS = [
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
-INTERNAL_SYMBOLS = ["a3_debug_set_k1_stream", "a3_debug_set_overlap", "a3_debug_set_k1_waves", "a3_debug_set_partition", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_mark_threshold", "a3_debug_set_hold", "a3_debug_launch_threshold", "a3_debug_stream_wait_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
+INTERNAL_SYMBOLS = ["a3_debug_set_k1_stream", "a3_debug_set_overlap", "a3_debug_set_k1_waves", "a3_debug_set_partition", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_mark_threshold", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_stream_wait_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
 
 
 class A3Error(RuntimeError):
@@ -197,6 +197,9 @@ def load():
     if hasattr(L, "a3_debug_set_hold"):
         L.a3_debug_set_hold.restype = C.c_int
         L.a3_debug_set_hold.argtypes = [C.c_int]
+    if hasattr(L, "a3_debug_set_jump_rounds"):
+        L.a3_debug_set_jump_rounds.restype = C.c_int
+        L.a3_debug_set_jump_rounds.argtypes = [C.c_int]
     if hasattr(L, "a3_debug_set_mark_threshold"):
         L.a3_debug_set_mark_threshold.restype = C.c_int
         L.a3_debug_set_mark_threshold.argtypes = [C.c_int]

@@ -31,18 +31,19 @@ hipError_t launch_dart_build(hipStream_t, const uint64_t*, int, int, uint32_t, u
                              uint64_t*, uint32_t*, uint32_t, const uint32_t*, int, const unsigned long long*);
 hipError_t launch_zero(hipStream_t, void*, size_t);
 size_t entry_state_bytes();
+bool finalize_inline(bool frame_entries, bool trust_natural);
 size_t fin_state_bytes();
 size_t entry_slots(uint32_t);
 size_t leader_list_bytes(uint32_t);
-hipError_t launch_rank_cycles(hipStream_t, uint32_t, int, const uint64_t*, const uint32_t*, JumpState*,
+hipError_t launch_rank_cycles(hipStream_t, uint32_t, int, const uint64_t*, const uint32_t*,
                               uint32_t*, unsigned int*, void*, void*, void*, uint32_t*, unsigned int*, int, DeviceCounters*, const uint32_t*, int,
                               const uint32_t*, uint32_t*, uint32_t, int, uint32_t, unsigned int*, int);
-hipError_t launch_resolve(hipStream_t, const JumpState*, const void*, uint32_t, int, const uint64_t*, const uint32_t*, const unsigned int*, uint64_t*, uint64_t*,
+hipError_t launch_resolve(hipStream_t, const void*, uint32_t, int, const uint64_t*, const uint32_t*, const unsigned int*, uint64_t*, uint64_t*,
                           DeviceCounters*, int, const uint32_t*);
-hipError_t launch_select_scatter(hipStream_t, const JumpState*, const void*, uint32_t, const uint32_t*, const unsigned int*, const uint32_t*, const uint64_t*,
+hipError_t launch_select_scatter(hipStream_t, const void*, uint32_t, const uint32_t*, const unsigned int*, const uint32_t*, const uint64_t*,
                                  const uint32_t*, uint32_t, uint32_t,
                                  uint32_t, double, double, ContourRec*, uint32_t*, uint32_t, uint64_t, DeviceCounters*,
-                                 const uint64_t*, uint32_t*, const uint32_t*, int, uint32_t*, int);
+                                 const uint64_t*, uint32_t*, const uint32_t*, int, uint32_t*, int, const void*);
 hipError_t launch_debug_clockwise(hipStream_t, const int32_t*, uint32_t, int32_t*);
 hipError_t launch_unpack_bits(hipStream_t, const uint64_t*, int, int, uint8_t*);
 hipError_t launch_contour_quads(hipStream_t, const ContourRec*, const DeviceCounters*, uint32_t, const uint32_t*, double, uint32_t, uint32_t,
@@ -97,7 +98,9 @@ static_assert(kMaxCandLimit == 65536, "a3_marker.candidate_index is a uint16_t")
 constexpr uint32_t kMaxContoursDefault = 1u << 20;
 constexpr uint64_t kMaxDartsDefault = 48ull << 20;
 constexpr uint64_t kMaxPointsDefault = 64ull << 20;
-constexpr uint64_t kHardMaxDarts = 3ull << 30;   // 32-bit dart indices
+// dart indices and entry slots (at most 32 k above the darts) stay below 2^30: a pending FinState holds a 30-bit slot beside its
+// marker bit (k_contours.hip)
+constexpr uint64_t kHardMaxDarts = (1ull << 30) - (1ull << 16);
 constexpr uint64_t kHardMaxPoints = 3ull << 30;
 constexpr int kResolveItersMax = 16;        // == DeviceCounters::resolve_changed slots
 // debug taps: warped patches kept per batch (one per candidate that reaches the decode stage).  The tap holds a patch for every
@@ -240,7 +243,7 @@ struct a3_ctx {
     uint32_t W = 0, H = 0, frames = 0;
 
     DevBuf dict, in, grey, bin, frame_darts, frame_darts_dev, frame_base, pix_base, tile_darts;
-    DevBuf d_xy, d_succ, stA, stB, t_cur, t_next;
+    DevBuf d_xy, d_succ, fin, t_cur, t_next;
     DevBuf leader_list, leader_keep, entry_list, es_a, es_b;
     DevBuf contours, cyc_start_off, points;
     DevBuf cands, pre_xy, fin_xy, fin_count, work, outs, proj, patches, cand_big;
@@ -347,8 +350,7 @@ uint32_t mark_size_of(uint8_t num_bits) {  // src/dictionaries.rs:154-156
 int ensure_dart_pool(a3_ctx* ctx, uint64_t darts) {
     A3_HIP(ctx->d_xy.ensure(darts * 8));   // dart records (dart_rec)
     A3_HIP(ctx->d_succ.ensure(darts * 4));
-    A3_HIP(ctx->stA.ensure(darts * sizeof(JumpState)));
-    A3_HIP(ctx->stB.ensure(darts * fin_state_bytes()));   // the 8-byte final states (leader, hops | flags) of k_jump_finalize
+    A3_HIP(ctx->fin.ensure(darts * fin_state_bytes()));   // the 8-byte states (leader, hops | flags, or pending) of k_local_contract / k_jump_finalize
     A3_HIP(ctx->t_cur.ensure(darts * 8));
     A3_HIP(ctx->t_next.ensure(darts * 8));
     A3_HIP(ctx->leader_list.ensure(leader_list_bytes((uint32_t)darts)));   // leaders of cycles with a start event, 16 shards
@@ -379,6 +381,7 @@ int g_part_k1_cus = 0, g_part_pattern = 0;
 // HIGHEST priority (no CU mask), ordered against the context's stream by two events
 int g_k1_stream_prio = 0;
 bool g_hold_rests = true;        // a3_debug_set_hold: bursts hold their chains back (see submit_common); 0 for A/B
+std::atomic<int> g_jump_rounds_cap{0};   // a3_debug_set_jump_rounds: at most this many global doubling rounds (0: no cap)
 bool g_mark_threshold = false;   // a3_debug_set_mark_threshold: record an event behind every threshold kernel (costs ~2 % of a step: tools/spin_probe.py)
 enum { kStreamCopy = 0, kStreamDecode = 1, kStreamK1 = 2 };
 
@@ -875,6 +878,8 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
         while ((1ull << rounds) < (uint64_t)c.max_frame_darts && rounds < 31) rounds++;
         rounds += 1;  // the round that observes "nothing moved"
         rounds = std::min(rounds, ctx->jump_rounds_hint);
+        // a3_debug_set_jump_rounds: too few rounds on purpose (not for the re-run with all rounds that a short launch asks for)
+        if (const int cap = g_jump_rounds_cap.load(std::memory_order_relaxed); cap > 0 && ctx->jump_rounds_hint < 32) rounds = std::min(rounds, cap);
         rounds_max = std::max(rounds_max, rounds);
         uint32_t* const frame_entries = ctx->entry_global_ttl > 0 ? nullptr : ctx->frame_cursor;   // per-frame entry counts
         const double eps_factor = ctx->cfg.contour_simplification_epsilon;
@@ -890,27 +895,26 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
         unsigned int* const dead_ctr = (keep_all || !dense_graph) ? nullptr : d_dead_count;
         const Chunk cc = c;
         // first half: the doubling rounds inside LDS tiles
-        A3_HIP(launch_rank_cycles(st, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(), ctx->stA.as<JumpState>(),
+        A3_HIP(launch_rank_cycles(st, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(),
                                   ctx->entry_list.as<uint32_t>(), d_entry_count, ctx->es_a.p, ctx->es_b.p,
-                                  ctx->stB.p, ctx->leader_list.as<uint32_t>(), d_leader_count, rounds, ctr, n_live, 0, fb,
+                                  ctx->fin.p, ctx->leader_list.as<uint32_t>(), d_leader_count, rounds, ctr, n_live, 0, fb,
                                   frame_entries, cc.count, 1, min_edge_length, dead_ctr, inline_resolve_W > 0 ? 1 : 0));
         if (rel_mode == 2) { if (int rc = release_waiting()) return rc; }   // waiting decode stages go out behind this k_local_contract
         ctx->dbg_nd = nd; ctx->dbg_frames = c.count; ctx->dbg_chunks = (uint32_t)chunks.size();
         // second half: entry resolution, final states (+ border selection), point scatter, quads -- on `s2`
         auto chunk_back = [=](hipStream_t s2) -> int {
-            A3_HIP(launch_rank_cycles(s2, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(), ctx->stA.as<JumpState>(),
+            A3_HIP(launch_rank_cycles(s2, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(),
                                       ctx->entry_list.as<uint32_t>(), d_entry_count, ctx->es_a.p, ctx->es_b.p,
-                                      ctx->stB.p /* the 8-byte final states */, ctx->leader_list.as<uint32_t>(), d_leader_count, rounds, ctr,
+                                      ctx->fin.p /* the 8-byte states */, ctx->leader_list.as<uint32_t>(), d_leader_count, rounds, ctr,
                                       n_live, 0, fb, frame_entries, cc.count, 2, min_edge_length, dead_ctr, inline_resolve_W > 0 ? 1 : 0));
-            const JumpState* loc = ctx->stA.as<JumpState>();
-            const void* fin = ctx->stB.p;
-            A3_HIP(launch_resolve(s2, loc, fin, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->leader_list.as<uint32_t>(), d_leader_count,
+            const void* fin = ctx->fin.p;
+            A3_HIP(launch_resolve(s2, fin, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->leader_list.as<uint32_t>(), d_leader_count,
                                   ctx->t_cur.as<uint64_t>(), ctx->t_next.as<uint64_t>(), ctr, resolve_iters, n_live));
-            A3_HIP(launch_select_scatter(s2, loc, fin, nd, ctx->leader_list.as<uint32_t>(), d_leader_count, ctx->d_succ.as<uint32_t>(), ctx->t_cur.as<uint64_t>(), fb,
+            A3_HIP(launch_select_scatter(s2, fin, nd, ctx->leader_list.as<uint32_t>(), d_leader_count, ctx->d_succ.as<uint32_t>(), ctx->t_cur.as<uint64_t>(), fb,
                                          cc.count, cc.first, min_edge_length, eps_factor, image_diag,
                                          ctx->contours.as<ContourRec>(), ctx->cyc_start_off.as<uint32_t>(), max_contours, max_points, ctr,
                                          ctx->d_xy.as<uint64_t>(), ctx->points.as<uint32_t>(), n_live, inline_resolve_W, ctx->leader_keep.as<uint32_t>(),
-                                         keep_all));
+                                         keep_all, finalize_inline(frame_entries != nullptr, inline_resolve_W > 0) ? ctx->es_a.p : nullptr));
             A3_HIP(launch_contour_quads(s2, ctx->contours.as<ContourRec>(), ctr, max_contours, ctx->points.as<uint32_t>(),
                                         eps_factor, min_edge_length, cc.first, kMaxCand,
                                         ctx->cands.as<CandRec>() + (size_t)cc.first * kMaxCand, ctx->cand_count + cc.first, d_err,
@@ -1046,6 +1050,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
         return 1;  // retry
     }
     if (flags & kErrBrokenEvent) return fail(ctx, A3_ERR_INTERNAL, "contour graph: a start event lies on an open chain");
+    if (flags & kErrScatter) return fail(ctx, A3_ERR_INTERNAL, "contour points: a border slot, rank or point index out of range");
     if (flags & kErrResolve) return fail(ctx, A3_ERR_INTERNAL, "contour start resolution did not converge");
     if (flags & kErrCandTable) {   // a frame has more quad candidates than its table: twice the table and again
         // straight to the table that holds the fullest frame (hs[5], from the marker gather): 2048, 4096, 6144 (the last that
@@ -1250,7 +1255,7 @@ void a3_destroy(a3_ctx* ctx) {
     }
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     DevBuf* bufs[] = {&ctx->dict, &ctx->in, &ctx->grey, &ctx->bin, &ctx->frame_darts, &ctx->frame_darts_dev, &ctx->frame_base, &ctx->pix_base,
-                      &ctx->tile_darts, &ctx->d_xy, &ctx->d_succ, &ctx->stA, &ctx->stB, &ctx->t_cur, &ctx->t_next,
+                      &ctx->tile_darts, &ctx->d_xy, &ctx->d_succ, &ctx->fin, &ctx->t_cur, &ctx->t_next,
                       &ctx->leader_list, &ctx->leader_keep, &ctx->entry_list, &ctx->es_a, &ctx->es_b,
                       &ctx->contours, &ctx->cyc_start_off, &ctx->points, &ctx->zero_blk, &ctx->cands,
                       &ctx->pre_xy, &ctx->fin_xy, &ctx->fin_count, &ctx->work, &ctx->outs, &ctx->proj, &ctx->patches, &ctx->cand_big,
@@ -1624,9 +1629,9 @@ int a3_debug_kernel_time(a3_ctx* ctx, int kernel, int dbg, int reps, float* avg_
                                      ctx->d_succ.as<uint32_t>(), ctx->dbg_nd, nullptr, dbg ? dbg : 5,
                                      reinterpret_cast<const unsigned long long*>(ctx->tile_darts.as<uint8_t>() + tile_mask_offset_bytes(ctx->W, ctx->H, ctx->frames))));
         } else if (kernel == 2) {
-            A3_HIP(launch_rank_cycles(st, ctx->dbg_nd, (int)ctx->W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(), ctx->stA.as<JumpState>(),
+            A3_HIP(launch_rank_cycles(st, ctx->dbg_nd, (int)ctx->W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(),
                                       ctx->entry_list.as<uint32_t>(),
-                                      d_entry_count, ctx->es_a.p, ctx->es_b.p, ctx->stB.p,
+                                      d_entry_count, ctx->es_a.p, ctx->es_b.p, ctx->fin.p,
                                       ctx->leader_list.as<uint32_t>(), d_leader_count, 0, ctx->counters, nullptr, dbg ? dbg : 11, ctx->frame_base.as<uint32_t>(), nullptr, ctx->dbg_frames, 0,
                                       0u, nullptr, 0));
         } else if (kernel == 3 || kernel == 4) {   // dbg < 0: k_decode alone (variant -dbg; -5: the whole kernel), dbg >= 0: k_projection + k_decode
@@ -1725,6 +1730,12 @@ int a3_debug_set_hold(int on) {
 }
 
 int a3_debug_set_k1_waves(int waves_per_simd) { set_k1_waves(waves_per_simd); return A3_OK; }
+
+int a3_debug_set_jump_rounds(int rounds) {
+    if (rounds < 0 || rounds > 32) return A3_ERR_INVALID;
+    g_jump_rounds_cap.store(rounds, std::memory_order_relaxed);
+    return A3_OK;
+}
 
 int a3_synth_render(int device, void* hip_stream, const a3_synth_frame* frames, uint32_t n_frames, const a3_synth_marker* markers,
                     uint32_t n_markers, uint32_t width, uint32_t height, int paper, float black, float white, int supersample,

@@ -48,14 +48,6 @@ __host__ __device__ inline uint32_t rec_xy(uint64_t r) { return (uint32_t)r; }
 __host__ __device__ inline uint32_t rec_F(uint64_t r) { return (uint32_t)(r >> 32) & 0xFFu; }
 __host__ __device__ inline uint32_t rec_info(uint64_t r) { return (uint32_t)(r >> 40) & 0xFFu; }
 
-// state carried by the pointer-doubling rounds (16 bytes per dart = one dwordx4, ping-pong)
-struct __attribute__((aligned(16))) JumpState {
-    uint64_t key;   // (start-event key << 32) | dart index : minimum over the window
-    uint32_t ptr;   // succ^(2^round)
-    uint32_t off;   // hops from this dart to the first dart holding `key`
-};
-static_assert(sizeof(JumpState) == 16, "JumpState layout");
-
 // The thresholded image is kept bit-packed: row y of a frame is `words_per_row(W)` little-endian u64 words,
 // bit i of word j is pixel x = 64 j + i (1 = white / foreground); bits past the image width are 0.
 __host__ __device__ inline uint32_t words_per_row(uint32_t W) { return (W + 63u) / 64u; }
@@ -109,6 +101,7 @@ struct DeviceCounters {
     unsigned int pad[1];
 };
 
-constexpr unsigned kErrBrokenEvent = 1u, kErrPointPool = 2u, kErrContourTable = 4u, kErrCandTable = 8u, kErrResolve = 16u, kErrMarkerCap = 32u;
+constexpr unsigned kErrBrokenEvent = 1u, kErrPointPool = 2u, kErrContourTable = 4u, kErrCandTable = 8u, kErrResolve = 16u, kErrMarkerCap = 32u,
+                   kErrScatter = 64u;   // k_scatter_points / k_cycle_select: a store's index failed its bounds check (nothing was stored)
 
 }  // namespace a3

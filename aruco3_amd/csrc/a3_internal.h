@@ -48,6 +48,11 @@ int  a3_debug_stream_wait_threshold(a3_ctx *ctx, void *hip_stream);
  * Process-wide, for A/B timing; results are identical. */
 int  a3_debug_set_hold(int on);
 
+/* At most `rounds` global pointer-doubling rounds per chunk (the dense-graph path of the contour stage; 0 = no cap, the default).
+ * Process-wide.  Fewer rounds than a graph needs leave its entry states unconverged: the library sees it and re-runs the batch with
+ * all rounds, so results are identical -- tests/ use it to walk that path on purpose. */
+int  a3_debug_set_jump_rounds(int rounds);
+
 /* the threshold kernel alone, asynchronously, on the context's stream (tools/k1_concurrency.py: how several launches in flight
  * at once share the chip) */
 int  a3_debug_launch_threshold(a3_ctx *ctx, const void *pixels_device, int fmt, uint32_t width, uint32_t height, uint32_t n_frames);

@@ -720,6 +720,11 @@ constexpr int kLTFrame = 1024;
 // shard t & 15, whose slots are [shard * cap, shard * cap + count[shard]); a tile holds at most kLT entries, so
 // cap = ceil(tiles / 16) * kLT can never overflow.
 constexpr uint32_t kEntryShards = 16;
+// The leaders of cycles that carry a start event are listed in 16 shards of leader_shard_cap slots each (one atomic per workgroup and
+// shard).  k_jump_finalize: the darts handled by the blocks of one shard, n/16 plus at most one 256-dart slice per block of the shard and
+// iteration; k_local_contract + k_entry_frame: leaders of the shard's 1024-dart tiles, at most n/16 + 1024.
+constexpr uint32_t kLeaderShards = 16;
+__host__ __device__ inline uint32_t leader_shard_cap(uint32_t n_darts) { return n_darts / kLeaderShards + n_darts / 64u + 262144u; }
 __host__ __device__ inline uint32_t entry_shard_cap(uint32_t n_darts) {
     const uint32_t tiles = (n_darts + kLT - 1) / kLT;
     return ((tiles + kEntryShards - 1) / kEntryShards) * kLT;
@@ -743,35 +748,79 @@ struct EntrySpace {
         return i < c ? sh * cap + i : kNone;
     }
 };
-constexpr uint32_t kFrozen = 0x80000000u;     // the window reached a dart outside the tile
-// k_local_contract's result per dart is one JumpState whose `off` word carries three things: hops to the window's minimum
-// (bits 0-11, <= 2047), window length in hops (bits 12-24, <= 2048) and kFrozen
-__device__ __forceinline__ uint32_t loc_pack(uint32_t off, uint32_t dist, bool frozen) { return off | (dist << 12) | (frozen ? kFrozen : 0u); }
-__device__ __forceinline__ uint32_t loc_off(uint32_t w) { return w & 0xFFFu; }
-// After k_jump_finalize the `off` word of a dart is either still the packed local one (the local window was final: its low 12
-// bits are the hop count) or kFinal | hops to the leader (< 2^30)
-constexpr uint32_t kFinal = 0x40000000u;
-// k_local_contract: the dart lies on a DEAD cycle -- one that closed inside its tile, carries a start event, is too short ever to be
-// materialised (k_cycle_select's parity-safe length test) and whose smallest event fires whatever the other borders do (see
-// static_fire).  Nothing downstream lists, evaluates or scatters it; its key stays in place: the start resolution of OTHER
-// borders through shared pixels reads it (a traced border labels its pixels however short it is).  Only in states whose window
-// did not freeze (kFinal and kDead never meet: k_jump_finalize rewrites frozen windows only).
-constexpr uint32_t kDead = 0x20000000u;
-// (readers test both bits: in a kFinal word bit 29 belongs to the hop count -- a dart 2^29 or more hops from its leader is not a dead one)
-__device__ __forceinline__ bool is_dead(uint32_t off_word) { return (off_word & (kFinal | kDead)) == kDead; }
-__device__ __forceinline__ uint32_t fin_off(uint32_t w) { return (w & kFinal) ? (w & 0x3FFFFFFFu) : (w & 0xFFFu); }
-__device__ __forceinline__ uint32_t loc_dist(uint32_t w) { return (w >> 12) & 0x1FFFu; }
 // What every dart knows once k_jump_finalize has run, in 8 bytes: its cycle's leader and its hop distance to it, plus whether the
-// cycle carries a start event and whether it is a dead one (k_local_contract).  Round 6: the sweeps that need the final answer per dart
-// (k_scatter_points, the fixpoint passes) read this array, and k_jump_finalize writes it front to back instead of patching a third
-// of the 16-byte local states in place (93 MB of scattered line write-backs per 256 frames, and 98 MB for k_scatter_points to read).
-// The 16-byte LOCAL states stay as k_local_contract left them; a LEADER's local key is already final (its own key is the smallest
-// of its cycle, hence of every window that holds it).  k_cycle_select parks a listed leader's border slot in the hops field of the
-// leader's OWN FinState (a leader is 0 hops from itself; kFinHops = no slot): k_scatter_points then finds "does my leader lead" and
-// "where do its points go" in one 8-byte load -- and the test is made on FINAL states: in a run that has not converged (too few
-// global rounds: the batch is re-run) a dart may name a leader that does not hold its own key, and nothing of such a dart is used.
+// cycle carries a start event and whether it is a DEAD one: a cycle that closed inside its tile, carries a start event, is too short
+// ever to be materialised (k_cycle_select's parity-safe length test) and whose smallest event fires whatever the other borders do (see
+// static_fire).  Nothing downstream lists, evaluates or scatters a dead cycle; its leader stays in place: the start resolution of
+// OTHER borders through shared pixels reads it (a traced border labels its pixels however short it is).
+// k_local_contract writes this array itself, and there is no other per-dart state: a dart whose window did not freeze gets its final
+// state at once (leader = the window's minimum, hops to it | flags); a dart whose window froze at a tile exit gets a PENDING state
+// (kPend in the leader word, which leaves dart indices and entry slots below 2^30: a3_api's kHardMaxDarts) that carries
+//   slot  the entry the window ends on (30 bits),
+//   dist  the window's length in hops (1..2048, stored - 1 in 11 bits),
+//   off   hops from the dart to the window's minimum (11 bits),
+//   min   the low 11 bits of that minimum's dart index (a window never leaves its 1024/2048-dart tile, which lies in one
+//         2048-aligned block: the dart's own upper bits complete it).
+// Once the entries have converged (es[slot]: the smallest key of the cycle, hops from the entry to it), the final state follows
+// (resolve_pending): the cycle's leader is es[slot]'s dart; if that is the window's own minimum the hops are `off`, else the leader lies
+// beyond the window and the hops are dist + es[slot].off.  (k_local_contract used to write a 16-byte local state {key, ptr, off}
+// per dart, and k_jump_finalize rewrote all of them as FinStates: 99 MB written and 106 MB read per batch for an answer two darts in
+// three already had.)  A leader's event key is a function of its record (event_key), which is where its readers get it.
+// k_cycle_select parks a listed leader's border slot in the hops field of the leader's OWN FinState (a leader is 0 hops from itself;
+// kFinHops = no slot): k_scatter_points then finds "does my leader lead" and "where do its points go" in one 8-byte load -- and the
+// test is made on FINAL states: in a run that has not converged (too few global rounds: the batch is re-run) a dart may name a leader
+// that does not lead itself, and nothing of such a dart is used.
 struct __attribute__((aligned(8))) FinState { uint32_t leader; uint32_t w; };
 constexpr uint32_t kFinEvent = 0x80000000u, kFinDead = 0x40000000u, kFinHops = 0x3FFFFFFFu;
+constexpr uint32_t kPend = 0x80000000u, kPendSlot = 0x3FFFFFFFu;
+__device__ __forceinline__ bool is_pending(FinState s) { return (s.leader & kPend) != 0u; }
+__device__ __forceinline__ FinState pend_pack(uint32_t slot, uint32_t dist, uint32_t off, uint32_t min_dart) {
+    const uint32_t m = min_dart & 0x7FFu;
+    return FinState{kPend | ((m >> 10) << 30) | (slot & kPendSlot), (dist - 1u) | (off << 11) | ((m & 0x3FFu) << 22)};
+}
+__device__ __forceinline__ uint32_t pend_slot(FinState s) { return s.leader & kPendSlot; }
+__device__ __forceinline__ uint32_t pend_dist(FinState s) { return (s.w & 0x7FFu) + 1u; }
+__device__ __forceinline__ uint32_t pend_off(FinState s) { return (s.w >> 11) & 0x7FFu; }
+__device__ __forceinline__ uint32_t pend_min(FinState s, uint32_t d) { return (d & ~0x7FFu) | (((s.leader >> 30) & 1u) << 10) | (s.w >> 22); }
+// the start-event key of a dart: 2q for a W-event at pixel q (raster index), 2q + 1 for an E-event, kNoKey for neither
+__device__ __forceinline__ uint32_t event_key(uint64_t rec, int W) {
+    const uint32_t xy = rec_xy(rec), info = rec_info(rec);
+    const uint32_t q = (xy >> 16) * (uint32_t)W + (xy & 0xFFFF);
+    return (info & kInfoW) ? 2u * q : ((info & kInfoE) ? 2u * q + 1u : kNoKey);
+}
+// a dart's ordering key: (event key << 32) | dart -- unique per dart
+__device__ __forceinline__ uint64_t dart_key(uint32_t d, uint64_t rec, int W) { return ((uint64_t)event_key(rec, W) << 32) | d; }
+
+// Phase 2's state per entry: the window [entry, ptr) over the reduced list, `key` its smallest dart key and `off` the hops to it,
+// `dist` its length in hops
+struct __attribute__((aligned(8))) EntryState { uint64_t key; uint32_t ptr; uint32_t off; uint32_t dist; uint32_t pad; };
+
+// the final state of a pending dart d, once es[pend_slot] has converged
+__device__ __forceinline__ FinState resolve_pending(FinState s, uint32_t d, const EntryState& g) {
+    const uint32_t leader = (uint32_t)g.key;
+    const uint32_t hops = leader == pend_min(s, d) ? pend_off(s) : (pend_dist(s) + g.off) & kFinHops;
+    return FinState{leader, hops | ((uint32_t)(g.key >> 32) != kNoKey ? kFinEvent : 0u)};
+}
+// an entry's initial window over the reduced list, from the entry dart's state as k_local_contract left it: pending (its window froze
+// at the entry of slot pend_slot) or final (its chain dead-ends inside its tile: the window points at the entry itself, slot `self`)
+__device__ __forceinline__ EntryState entry_start(uint32_t e, FinState s, uint64_t min_rec, int W, uint32_t self) {
+    EntryState r;
+    const bool pend = is_pending(s);
+    r.key = dart_key(pend ? pend_min(s, e) : s.leader, min_rec, W);
+    r.off = pend ? pend_off(s) : (s.w & kFinHops);
+    r.dist = pend ? pend_dist(s) : 0u;
+    r.ptr = pend ? pend_slot(s) : self;
+    r.pad = 0;
+    return r;
+}
+// the dart whose record entry_start needs (the window's minimum)
+__device__ __forceinline__ uint32_t entry_min_dart(uint32_t e, FinState s) { return is_pending(s) ? pend_min(s, e) : s.leader; }
+// dart d's final state from what the array holds: pending states resolved through the converged entry table.  es == nullptr: k_jump_finalize
+// has run (the dense path, the fixpoint passes), nothing is pending any more.  On the clean-frame path k_jump_finalize is not launched and
+// the readers -- k_cycle_select, natural_start_fires, k_scatter_points -- resolve the few pending states they meet themselves.
+__device__ __forceinline__ FinState fin_final(FinState s, uint32_t d, const EntryState* __restrict__ es) {
+    return (es != nullptr && is_pending(s)) ? resolve_pending(s, d, es[pend_slot(s)]) : s;
+}
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every global load, store and returning
 // atomic the wave has in flight (s_waitcnt vmcnt(0)); where the barrier only hands LDS data between waves that wait would
@@ -798,13 +847,15 @@ __device__ __forceinline__ bool static_fire(uint64_t rec) {
 template <int LT, bool DEAD /* the early finish of short borders (dense graphs) is compiled in: its LDS and registers cost the clean-frame instantiation a wave per SIMD */>
 __global__ __launch_bounds__(256, (LT >= 2048 || DEAD) ? 4 : 8) void k_local_contract(uint32_t n_darts, int W, const uint64_t* __restrict__ d_rec,
                                                         const uint32_t* __restrict__ d_succ,
-                                                        JumpState* __restrict__ loc,
+                                                        FinState* __restrict__ fin,
                                                         uint32_t* __restrict__ entry_list,
                                                         unsigned int* __restrict__ entry_count, uint32_t ecap,
                                                         const uint32_t* __restrict__ frame_base, uint32_t* __restrict__ frame_entries,
                                                         const uint32_t* __restrict__ n_live, int dbg,
                                                         uint32_t min_edge_length, unsigned int* __restrict__ dead_count /*[16]; nullptr: mark nothing dead*/,
-                                                        int trust_natural /* the launch sequence ends in k_cycle_select's inline check (no fixpoint passes): see the epilogue */) {
+                                                        int trust_natural /* the launch sequence ends in k_cycle_select's inline check (no fixpoint passes): see the epilogue */,
+                                                        uint32_t* __restrict__ leader_list /* nullptr: k_jump_finalize lists the leaders */,
+                                                        unsigned int* __restrict__ leader_count /*[kLeaderShards]*/, uint32_t leader_cap) {
     // frame_entries != nullptr: entries get slots grouped by frame (slot = frame_base[f] + running count of the frame: a
     // frame has at most as many entries as darts), for k_entry_frame; else the 16-shard allocation of the global rounds
     // dbg (a3_debug_kernel_time only; 0 in the product path): n > 0 runs n doubling rounds instead of 11; -1 = none
@@ -846,9 +897,8 @@ __global__ __launch_bounds__(256, (LT >= 2048 || DEAD) ? 4 : 8) void k_local_con
     for (int u = 0; u < PER; u++) {
         const uint32_t i = threadIdx.x + u * 256;
         const uint64_t rec = recs[u];
-        const uint32_t xy = rec_xy(rec), info = rec_info(rec);
-        const uint32_t q = (xy >> 16) * (uint32_t)W + (xy & 0xFFFF);
-        const uint32_t ek = (info & kInfoW) ? 2u * q : ((info & kInfoE) ? 2u * q + 1u : kNoKey);
+        const uint32_t info = rec_info(rec);
+        const uint32_t ek = event_key(rec, W);
         frm[u] = rec_frame(rec);   // kept, like succ0, for the entry registration (no second read)
         // A successor outside the tile freezes the window at once; its pointer then names the dart INSIDE the tile that the window
         // ends on -- lo + LT + i: outside [lo, lo + cnt) whatever the arithmetic wraps to -- because that dart's lane knows the slot
@@ -1040,6 +1090,7 @@ __global__ __launch_bounds__(256, (LT >= 2048 || DEAD) ? 4 : 8) void k_local_con
             entry_list[slot] = succ0[u];
         }
     lds_barrier();
+    uint32_t lmask = 0;   // bit u: my dart u is listed as a leader (leader_list only)
 #pragma unroll
     for (int u = 0; u < PER; u++) {
         const uint32_t i = threadIdx.x + u * 256;
@@ -1048,13 +1099,33 @@ __global__ __launch_bounds__(256, (LT >= 2048 || DEAD) ? 4 : 8) void k_local_con
         const bool frozen = (e - lo) >= cnt;
         const uint32_t li = (uint32_t)nk[u] - lo;                                      // my window's minimum: in the tile when it did not freeze
         const bool dead = dead_count != nullptr && !frozen && li < cnt && (s_dead[li] & 1u) != 0;
-        JumpState r;
-        r.key = nk[u]; r.ptr = frozen ? s_slot[(e - lo - (uint32_t)LT) & (uint32_t)(LT - 1)] : e; r.off = loc_pack(no[u], nd[u], frozen) | (dead ? kDead : 0u);
-        loc[lo + i] = r;
+        const bool event = (uint32_t)(nk[u] >> 32) != kNoKey;
+        // final unless the window froze: then pending on the entry it ends on (FinState above)
+        fin[lo + i] = frozen ? pend_pack(s_slot[(e - lo - (uint32_t)LT) & (uint32_t)(LT - 1)], nd[u], no[u], (uint32_t)nk[u])
+                             : FinState{(uint32_t)nk[u], no[u] | (event ? kFinEvent : 0u) | (dead ? kFinDead : 0u)};
+        if (!frozen && (uint32_t)nk[u] == lo + i && event && !dead) lmask |= 1u << u;   // leads a cycle that closed in the tile
+    }
+    // Without k_jump_finalize (clean frames): the leaders of the cycles that closed inside the tile, carry an event and are not dead are
+    // listed here -- counted in a block scan, one global atomic per workgroup, shard = tile & 15 (k_entry_frame lists the others in the
+    // shard of their leader's tile: a shard holds darts of its own tiles only, which leader_shard_cap covers).
+    if (leader_list) {   // (uniform)
+        __shared__ uint32_t s_lw[4];
+        __shared__ uint32_t s_lbase;
+        uint32_t total;
+        const uint32_t excl = block_excl_scan_256((uint32_t)__popc(lmask), s_lw, &total);
+        if (total) {     // (uniform)
+            const uint32_t shard = blockIdx.x & (kLeaderShards - 1);
+            if (threadIdx.x == 0) s_lbase = atomicAdd(&leader_count[shard], total);
+            __syncthreads();
+            uint32_t slot = s_lbase + excl;
+            while (lmask) {
+                const int u = __ffs(lmask) - 1;
+                lmask &= lmask - 1;
+                leader_list[(size_t)shard * leader_cap + slot++] = lo + threadIdx.x + (uint32_t)u * 256u;
+            }
+        }
     }
 }
-
-struct __attribute__((aligned(8))) EntryState { uint64_t key; uint32_t ptr; uint32_t off; uint32_t dist; uint32_t pad; };
 
 // Phase 2, one workgroup per frame, all rounds in LDS: the entries of a clean frame number a few hundred, and a border never
 // leaves its frame, so the reduced list of a frame closes on itself.  Replaces k_entry_init + ~8 k_entry_jump launches (each
@@ -1062,8 +1133,11 @@ struct __attribute__((aligned(8))) EntryState { uint64_t key; uint32_t ptr; uint
 // with the global rounds below (noise-like frames).
 constexpr uint32_t kEntryLdsCap = 2048;
 __global__ __launch_bounds__(256) void k_entry_frame(const uint32_t* __restrict__ entry_list, const uint32_t* __restrict__ frame_entries,
-                                                     const uint32_t* __restrict__ frame_base, const JumpState* __restrict__ loc,
-                                                     EntryState* __restrict__ es, DeviceCounters* __restrict__ ctr) {
+                                                     const uint32_t* __restrict__ frame_base, const FinState* __restrict__ fin,
+                                                     const uint64_t* __restrict__ d_rec, int W,
+                                                     EntryState* __restrict__ es, DeviceCounters* __restrict__ ctr,
+                                                     uint32_t* __restrict__ leader_list /* nullptr: k_jump_finalize lists the leaders */,
+                                                     unsigned int* __restrict__ leader_count /*[kLeaderShards]*/, uint32_t leader_cap) {
     // one 16-byte record per entry (a single ds_read_b128 fetches the window an entry is joined with) + its length
     struct __attribute__((aligned(16))) Rec { uint64_t key; uint32_t ptr; uint32_t off; };
     __shared__ Rec s_rec[kEntryLdsCap];
@@ -1076,31 +1150,34 @@ __global__ __launch_bounds__(256) void k_entry_frame(const uint32_t* __restrict_
     // copy the other lanes read
     constexpr int PER = kEntryLdsCap / 256;
     uint64_t nk[PER]; uint32_t np[PER], no[PER], nd[PER];
-    // the two dependent loads (entry -> its local state, which names the slot of the entry it froze at) for four entries per lane at
-    // a time: a clean frame has several hundred entries, i.e. one trip of this loop
+    uint32_t m0[PER];   // the smallest dart of the entry's own segment (its cycle's leader if the cycle's minimum lies there)
+    // the three dependent loads (entry -> its dart's state as k_local_contract left it, which names the slot of the entry it froze at
+    // and the window's minimum -> that minimum's record, for its event key) for four entries per lane at a time: a clean frame has
+    // several hundred entries, i.e. one trip of this loop
     constexpr int EB = 4;
     static_assert(PER % EB == 0, "whole batches");
 #pragma unroll
     for (int u0 = 0; u0 < PER; u0 += EB) {
         if ((uint32_t)u0 * 256u >= cnt) break;   // uniform
-        uint32_t e[EB], pos[EB];
-        JumpState l[EB];
+        uint32_t e[EB];
+        FinState l[EB];
+        uint64_t mr[EB];
 #pragma unroll
         for (int u = 0; u < EB; u++) e[u] = entry_list[base + min(threadIdx.x + 256u * (uint32_t)(u0 + u), cnt - 1u)];
 #pragma unroll
-        for (int u = 0; u < EB; u++) l[u] = loc[e[u]];
+        for (int u = 0; u < EB; u++) l[u] = fin[e[u]];
 #pragma unroll
-        for (int u = 0; u < EB; u++) pos[u] = l[u].ptr;   // (some dart, and ignored, when the window did not freeze)
+        for (int u = 0; u < EB; u++) mr[u] = d_rec[entry_min_dart(e[u], l[u])];
         // (the values are "used" here so that the compiler cannot sink the later entries' loads into the `i < cnt` test below,
         // which would turn overlapped chains of round trips into chains in a row)
 #pragma unroll
-        for (int u = 0; u < EB; u++) asm volatile("" : "+v"(pos[u]), "+v"(l[u].key), "+v"(l[u].off));
+        for (int u = 0; u < EB; u++) asm volatile("" : "+v"(mr[u]), "+v"(l[u].leader), "+v"(l[u].w));
 #pragma unroll
         for (int u = 0; u < EB; u++) {
             const uint32_t i = threadIdx.x + 256u * (uint32_t)(u0 + u);
-            nk[u0 + u] = l[u].key; no[u0 + u] = loc_off(l[u].off); nd[u0 + u] = loc_dist(l[u].off);
             // an entry's local window always freezes (its predecessor lies in another tile) unless its chain dead-ends in the tile
-            np[u0 + u] = (l[u].off & kFrozen) ? pos[u] - base : i;
+            const EntryState s0 = entry_start(e[u], l[u], mr[u], W, base + i);
+            nk[u0 + u] = s0.key; no[u0 + u] = s0.off; nd[u0 + u] = s0.dist; np[u0 + u] = s0.ptr - base; m0[u0 + u] = (uint32_t)s0.key;
             if (i < cnt) { s_rec[i] = Rec{nk[u0 + u], np[u0 + u], no[u0 + u]}; s_dist[i] = nd[u0 + u]; }
         }
     }
@@ -1137,22 +1214,43 @@ __global__ __launch_bounds__(256) void k_entry_frame(const uint32_t* __restrict_
             es[base + i] = o;
         }
     }
+    // Without k_jump_finalize (clean frames): every cycle that crosses tiles is listed once, by the entry whose own segment holds the
+    // cycle's minimum -- its leader -- when that carries an event; in the shard of the leader's 1024-dart tile (see k_local_contract).
+    if (leader_list) {
+        __shared__ uint32_t s_lcnt[kLeaderShards], s_lbase[kLeaderShards];
+        if (threadIdx.x < kLeaderShards) s_lcnt[threadIdx.x] = 0;
+        __syncthreads();
+        uint32_t rank[PER];
+#pragma unroll
+        for (int u = 0; u < PER; u++) {
+            const uint32_t i = threadIdx.x + u * 256;
+            const uint32_t L = (uint32_t)nk[u];
+            rank[u] = kNone;
+            if (i < cnt && L == m0[u] && (uint32_t)(nk[u] >> 32) != kNoKey) rank[u] = atomicAdd(&s_lcnt[(L >> 10) & (kLeaderShards - 1)], 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x < kLeaderShards && s_lcnt[threadIdx.x]) s_lbase[threadIdx.x] = atomicAdd(&leader_count[threadIdx.x], s_lcnt[threadIdx.x]);
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < PER; u++)
+            if (rank[u] != kNone) {
+                const uint32_t L = (uint32_t)nk[u], sh = (L >> 10) & (kLeaderShards - 1);
+                leader_list[(size_t)sh * leader_cap + s_lbase[sh] + rank[u]] = L;
+            }
+    }
 }
 
 // Phase 2 set-up: the reduced list over entries.  An entry's local window always freezes (its predecessor lies in another
 // tile, so it cannot sit on a tile-local cycle) unless its chain dead-ends inside the tile; then it points at itself.
 __global__ void k_entry_init(const uint32_t* __restrict__ entry_list, const unsigned int* __restrict__ entry_count,
-                             const JumpState* __restrict__ loc, EntryState* __restrict__ es, uint32_t cap) {
+                             const FinState* __restrict__ fin, const uint64_t* __restrict__ d_rec, int W, EntryState* __restrict__ es, uint32_t cap) {
     const EntrySpace sp(entry_count);
     for (uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < sp.total; i0 += gridDim.x * blockDim.x) {
         const uint32_t i = sp.slot(i0, cap);
         if (i == kNone) continue;
         const uint32_t e = entry_list[i];
-        const JumpState l = loc[e];
-        EntryState s;
-        s.key = l.key; s.off = loc_off(l.off); s.dist = loc_dist(l.off); s.pad = 0;
-        s.ptr = (l.off & kFrozen) ? l.ptr : i;
-        es[i] = s;
+        const FinState l = fin[e];
+        es[i] = entry_start(e, l, d_rec[entry_min_dart(e, l)], W, i);
     }
 }
 
@@ -1186,13 +1284,10 @@ __global__ __launch_bounds__(256) void k_entry_jump(const EntryState* __restrict
 }
 
 // Phase 3: every dart learns its cycle's leader and its hop distance to it
-constexpr uint32_t kLeaderShards = 16;
-// darts handled by the blocks of one shard: n/16 plus at most one 256-dart slice per block of the shard and iteration
-__host__ __device__ inline uint32_t leader_shard_cap(uint32_t n_darts) { return n_darts / kLeaderShards + n_darts / 64u + 262144u; }
-
 // ... and the leaders of cycles that carry at least one start event are collected (one atomic per wave) for the
-// per-border kernels that follow.
-__global__ __launch_bounds__(256) void k_jump_finalize(uint32_t n_darts, const JumpState* __restrict__ loc,
+// per-border kernels that follow.  Only the pending states (windows that froze at a tile exit) are rewritten; the others are final
+// as k_local_contract left them.
+__global__ __launch_bounds__(256) void k_jump_finalize(uint32_t n_darts,
                                                        const EntryState* __restrict__ es,
                                                        FinState* __restrict__ fin,
                                                        uint32_t* __restrict__ leader_list,
@@ -1207,34 +1302,28 @@ __global__ __launch_bounds__(256) void k_jump_finalize(uint32_t n_darts, const J
     const uint32_t shard = blockIdx.x & (kLeaderShards - 1);   // spread the slot counter over 16 addresses
     const uint32_t stride = gridDim.x * blockDim.x;            // the launcher keeps ceil(n_darts / stride) <= 32
     uint32_t mask = 0;                                          // bit i: my i-th dart leads a cycle that has a start event
-    // B darts per lane at a time, each of the two dependent loads (local state, which names the slot of the entry the window froze
-    // at -> that entry's state) issued for all of them before the first is used: the kernel is a chain of round trips to memory.
-    // Loads are unconditional from clamped indices (slot 0 for windows that did not freeze: a cached line); behind an `if` the
-    // compiler would issue them one at a time again.  (Round 6: the slot comes with the state; rounds 2-5 fetched it from an
-    // entry_pos[] array in between, a third dependent, scattered load.)
+    // B darts per lane at a time, each of the two dependent loads (the dart's state, which names the slot of the entry a pending
+    // window froze at -> that entry's state) issued for all of them before the first is used: the kernel is a chain of round trips
+    // to memory.  Loads are unconditional from clamped indices (slot 0 for final states: a cached line); behind an `if` the
+    // compiler would issue them one at a time again.
     constexpr int B = A3_FIN_B;
     int it = 0;
     for (uint32_t d0 = blockIdx.x * blockDim.x + threadIdx.x; d0 < n_darts; d0 += B * stride, it += B) {
-        JumpState s[B];
-        uint32_t od[B], pos[B];
+        FinState s[B];
+        uint32_t pos[B];
         EntryState g[B];
 #pragma unroll
-        for (int u = 0; u < B; u++) s[u] = loc[min(d0 + (uint32_t)u * stride, n_darts - 1u)];
+        for (int u = 0; u < B; u++) s[u] = fin[min(d0 + (uint32_t)u * stride, n_darts - 1u)];
 #pragma unroll
-        for (int u = 0; u < B; u++) { od[u] = s[u].off; pos[u] = (od[u] & kFrozen) ? s[u].ptr : 0u; }
+        for (int u = 0; u < B; u++) pos[u] = is_pending(s[u]) ? pend_slot(s[u]) : 0u;
 #pragma unroll
         for (int u = 0; u < B; u++) g[u] = es[pos[u]];
 #pragma unroll
         for (int u = 0; u < B; u++) {
             const uint32_t d = d0 + (uint32_t)u * stride;
             if (d >= n_darts) break;
-            // a window that was final inside its tile -- wrapped, or frozen at an entry whose own cycle minimum is not smaller --
-            // keeps its local answer; the others take the entry's
-            const bool better = (od[u] & kFrozen) && g[u].key < s[u].key;
-            if (better) { s[u].key = g[u].key; s[u].off = (loc_dist(od[u]) + g[u].off) | kFinal; }
-            const bool event = (uint32_t)(s[u].key >> 32) != kNoKey, dead = is_dead(s[u].off);
-            fin[d] = FinState{(uint32_t)s[u].key, fin_off(s[u].off) | (event ? kFinEvent : 0u) | (dead ? kFinDead : 0u)};
-            if ((uint32_t)s[u].key == d && event && !dead) mask |= 1u << (it + u);
+            if (is_pending(s[u])) { s[u] = resolve_pending(s[u], d, g[u]); fin[d] = s[u]; }
+            if (s[u].leader == d && (s[u].w & (kFinEvent | kFinDead)) == kFinEvent) mask |= 1u << (it + u);
         }
     }
     // one global atomic per workgroup: leaders are counted in a block scan first
@@ -1260,9 +1349,9 @@ constexpr uint64_t kInf64 = ~0ull;
 // step of k_resolve_eval maps T0 to itself (T'(c) = min firing event >= min event = T0(c)), so T0 is the fixpoint and the
 // passes over all darts below are skipped; this is the case unless a component's first pixel lies in column 0.
 // T0 is written for the listed leaders only -- the only slots k_cycle_select reads.
-// does the smallest event of the border led by dart d (key0 = st[d].key) fire under the natural assignment?
-__device__ __forceinline__ bool natural_start_fires(uint32_t d, uint64_t key0, const JumpState* __restrict__ st, const FinState* __restrict__ fin,
-                                                    const uint64_t* __restrict__ d_rec, int W) {
+// does the smallest event of the border led by dart d (its own event: a leader's key is the smallest of its cycle) fire under the
+// natural assignment?
+__device__ __forceinline__ bool natural_start_fires(uint32_t d, const FinState* fin, const EntryState* __restrict__ es, const uint64_t* __restrict__ d_rec, int W) {
     const uint64_t rec = d_rec[d];
     if (static_fire(rec)) return true;   // (the leader's key is its own event's: no look at the neighbours' states needed)
     const uint32_t info = rec_info(rec);
@@ -1274,30 +1363,30 @@ __device__ __forceinline__ bool natural_start_fires(uint32_t d, uint64_t key0, c
     const uint32_t base = d - __popc(P & ((1u << k) - 1u));
     const int cnt = __popc(P);
     bool wfires = true;
-    // a pixel owns at most four darts: their leaders, then the leaders' own keys (a leader's local state is final), each as one batch
-    // of loads (clamped indices) rather than a chain of up to eight round trips with an early exit
-    uint32_t lj[4];
-    uint64_t lk[4];
+    // a pixel owns at most four darts: their leaders, then the leaders' records (event keys) and own leaders, each as one batch of
+    // loads (clamped indices) rather than a chain of up to eight round trips with an early exit
+    uint32_t lj[4], ll[4];
+    uint64_t lr[4];
 #pragma unroll
-    for (int j = 0; j < 4; j++) lj[j] = fin[base + (uint32_t)min(j, cnt - 1)].leader;
+    for (int j = 0; j < 4; j++) { const uint32_t dj = base + (uint32_t)min(j, cnt - 1); lj[j] = fin_final(fin[dj], dj, es).leader; }
 #pragma unroll
-    for (int j = 0; j < 4; j++) lk[j] = st[lj[j]].key;
+    for (int j = 0; j < 4; j++) { lr[j] = d_rec[lj[j]]; ll[j] = fin_final(fin[lj[j]], lj[j], es).leader; }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         // T0 of the border through this dart: its leader's event key, provided the dart sits on an intact cycle with an event
-        uint32_t t = (uint32_t)(lk[j] >> 32);
-        if (lj[j] != d && (uint32_t)lk[j] != lj[j]) t = kNoKey;
+        uint32_t t = event_key(lr[j], W);
+        if (lj[j] != d && ll[j] != lj[j]) t = kNoKey;
         if (j < cnt && t < 2u * q) wfires = false;
     }
     const bool has_w = x > 0 && !(F & 1u);
     uint32_t key = kNoKey;
     if ((info & kInfoW) && wfires) key = 2u * q;
     else if ((info & kInfoE) && !(has_w && wfires)) key = 2u * q + 1u;
-    return key == (uint32_t)(key0 >> 32);
+    return key == event_key(rec, W);
 }
 
 // (Launched only when the full passes below are in the launch sequence; otherwise k_cycle_select does this check itself.)
-__global__ __launch_bounds__(256) void k_resolve_fast(const JumpState* __restrict__ st, const FinState* __restrict__ fin, const uint32_t* __restrict__ leader_list,
+__global__ __launch_bounds__(256) void k_resolve_fast(const FinState* __restrict__ fin, const uint32_t* __restrict__ leader_list,
                                                       const unsigned int* __restrict__ leader_count, uint32_t shard_cap, int W,
                                                       const uint64_t* __restrict__ d_rec, uint64_t* __restrict__ t_cur,
                                                       DeviceCounters* __restrict__ ctr) {
@@ -1310,22 +1399,21 @@ __global__ __launch_bounds__(256) void k_resolve_fast(const JumpState* __restric
         const uint32_t sh = i0 / span, i = i0 - sh * span;
         if (i >= leader_count[sh]) continue;
         const uint32_t d = leader_list[(size_t)sh * shard_cap + i];
-        const uint64_t key0 = st[d].key;            // (smallest event key << 32) | d
-        t_cur[d] = key0;
-        if (!natural_start_fires(d, key0, st, fin, d_rec, W)) moved = true;
+        t_cur[d] = dart_key(d, d_rec[d], W);      // (smallest event key << 32) | d
+        if (!natural_start_fires(d, fin, nullptr, d_rec, W)) moved = true;
     }
     if (moved) ctr->resolve_needed = 1u;
 }
 
 // leaders get their natural start (their own key: the smallest event on the cycle); every other slot is "never"
-__global__ void k_resolve_init(const JumpState* __restrict__ st, const FinState* __restrict__ fin, uint32_t n_darts, uint64_t* __restrict__ t_cur,
+__global__ void k_resolve_init(const FinState* __restrict__ fin, const uint64_t* __restrict__ d_rec, int W, uint32_t n_darts, uint64_t* __restrict__ t_cur,
                                uint64_t* __restrict__ t_next, const DeviceCounters* __restrict__ ctr, const uint32_t* __restrict__ n_live) {
     if (!ctr->resolve_needed) return;
     if (n_live) n_darts = min(n_darts, *n_live);
     for (uint32_t d = blockIdx.x * blockDim.x + threadIdx.x; d < n_darts; d += gridDim.x * blockDim.x) {
         const FinState fs = fin[d];
         const bool natural = fs.leader == d && (fs.w & kFinEvent) != 0u;
-        t_cur[d] = natural ? st[d].key : kInf64;   // (a leader's local key is its own: final)
+        t_cur[d] = natural ? dart_key(d, d_rec[d], W) : kInf64;   // (a leader's key is its own)
         t_next[d] = kInf64;
     }
 }
@@ -1397,7 +1485,7 @@ __global__ void k_resolve_commit(const FinState* __restrict__ fin, uint32_t n_da
 // leader is 0 hops from itself, and every reader of that field special-cases the leader -- so that k_scatter_points finds "does my
 // leader lead itself" and "where do its points go" in one 8-byte load per dart instead of two scattered ones (on noise-like frames,
 // 50 M darts, the scattered loads are the kernel).
-__global__ __launch_bounds__(256) void k_cycle_select(const JumpState* __restrict__ st, FinState* fin, const uint32_t* __restrict__ leader_list,
+__global__ __launch_bounds__(256) void k_cycle_select(FinState* fin, const uint32_t* __restrict__ leader_list,
                                                       const unsigned int* __restrict__ leader_count, const uint32_t* __restrict__ d_succ,
                                                       const uint64_t* __restrict__ t_cur, const uint32_t* __restrict__ frame_base,
                                                       uint32_t n_frames, uint32_t first_frame, uint32_t min_edge_length, double eps_factor,
@@ -1406,7 +1494,9 @@ __global__ __launch_bounds__(256) void k_cycle_select(const JumpState* __restric
                                                       DeviceCounters* __restrict__ ctr, uint32_t shard_cap, const uint64_t* __restrict__ d_rec,
                                                       int W /* > 0: no resolve kernel ran; borders start naturally, checked here */,
                                                       uint32_t* __restrict__ keep_tmp /* one word per leader-list slot */,
-                                                      int keep_all /* debug taps: materialise every traced border (a3_download_contours) */) {
+                                                      int keep_all /* debug taps: materialise every traced border (a3_download_contours) */,
+                                                      const EntryState* __restrict__ es /* nullptr: k_jump_finalize has run; else pending states are resolved here */) {
+    if (ctr->entry_overflow) return;   // (the batch is re-run; without k_jump_finalize the listed leaders' neighbours may name unwritten entries)
     __shared__ uint32_t s_wave[4], s_wave_t[4];
     __shared__ unsigned long long s_wave_p[4];
     __shared__ uint32_t s_cbase;
@@ -1427,12 +1517,12 @@ __global__ __launch_bounds__(256) void k_cycle_select(const JumpState* __restric
         e.valid = i < leader_count[sh];
         if (!e.valid) return e;
         e.d = leader_list[(size_t)sh * shard_cap + i];
-        e.t = W > 0 ? st[e.d].key : t_cur[e.d];   // listed leaders carry a start event: their natural start is their key
+        e.t = W > 0 ? dart_key(e.d, d_rec[e.d], W) : t_cur[e.d];   // listed leaders carry a start event: their natural start is their key
         e.traced = e.t != kInf64;
         if (!e.traced) return e;
         // the successor's window must have wrapped around to this leader, else this is a chain, not a cycle
         const uint32_t sl = d_succ[e.d];
-        const FinState fsl = fin[sl];
+        const FinState fsl = fin_final(fin[sl], sl, es);
         if (sl == e.d || fsl.leader != e.d) { e.broken = true; return e; }
         e.n = (fsl.w & kFinHops) + 1u;
         // Parity-safe pruning (src/aruco.rs:133-158):
@@ -1464,7 +1554,7 @@ __global__ __launch_bounds__(256) void k_cycle_select(const JumpState* __restric
         if (e.valid) { const uint32_t sh = i0 / span; keep_tmp[(size_t)sh * shard_cap + (i0 - sh * span)] = e.keep ? 1u : 0u; }
         // the k_resolve_fast test, folded in: if some border's smallest event does not fire the batch is re-run with the
         // fixpoint passes (what is selected below is then discarded)
-        if (W > 0 && e.valid && !natural_start_fires(e.d, e.t, st, fin, d_rec, W)) moved = true;
+        if (W > 0 && e.valid && !natural_start_fires(e.d, fin, es, d_rec, W)) moved = true;
     }
     if (moved) ctr->resolve_needed = 1u;
     if (broken) atomicOr(&ctr->err_flags, kErrBrokenEvent);
@@ -1507,7 +1597,8 @@ __global__ __launch_bounds__(256) void k_cycle_select(const JumpState* __restric
         {
             const uint32_t sh = i0 / span, i = i0 - sh * span;
             if (i >= leader_count[sh]) continue;
-            if (!keep_tmp[(size_t)sh * shard_cap + i]) { fin[leader_list[(size_t)sh * shard_cap + i]].w = kFinEvent | kFinHops; continue; }
+            // (whole states: a listed leader's may still be pending, and the leader word must name the leader itself from here on)
+            if (!keep_tmp[(size_t)sh * shard_cap + i]) { const uint32_t d = leader_list[(size_t)sh * shard_cap + i]; fin[d] = FinState{d, kFinEvent | kFinHops}; continue; }
         }
         const Eval e = eval(i0);
         if (!e.valid) continue;
@@ -1524,21 +1615,29 @@ __global__ __launch_bounds__(256) void k_cycle_select(const JumpState* __restric
                 r.point_base = (uint32_t)pb;
                 r.n = e.n;
                 contours[c] = r;
-                cyc_start_off[c] = (uint32_t)e.t == e.d ? 0u : fin[(uint32_t)e.t].w & kFinHops;   // (the leader's own hops field is about to hold its slot)
+                cyc_start_off[c] = (uint32_t)e.t == e.d ? 0u : fin_final(fin[(uint32_t)e.t], (uint32_t)e.t, es).w & kFinHops;   // (the leader's own hops field is about to hold its slot)
                 slot = c;
             }
             c++; pb += e.n;
         }
-        fin[e.d].w = kFinEvent | (slot == kNone ? kFinHops : slot);   // (listed leaders carry an event and are not dead)
+        fin[e.d] = FinState{e.d, kFinEvent | (slot == kNone ? kFinHops : slot)};   // (listed leaders carry an event and are not dead)
     }
 }
 
 __global__ __launch_bounds__(256) void k_scatter_points(const FinState* __restrict__ fin, uint32_t n_darts, const uint64_t* __restrict__ d_rec,
                                                         const ContourRec* __restrict__ contours,
                                                         const uint32_t* __restrict__ cyc_start_off, uint32_t* __restrict__ points,
-                                                        const uint32_t* __restrict__ n_live, const DeviceCounters* __restrict__ ctr) {
+                                                        const uint32_t* __restrict__ n_live, DeviceCounters* __restrict__ ctr,
+                                                        uint32_t max_contours, uint64_t max_points,
+                                                        const EntryState* __restrict__ es /* nullptr: k_jump_finalize has run */) {
     if (ctr->entry_overflow) return;
     if (n_live) n_darts = min(n_darts, *n_live);
+    // Every store is checked against the tables it indexes: a border slot below the number of borders selected, a rank inside the
+    // border, a point inside the pool.  In a converged run none of these can fail; a state that names garbage (a run that has not
+    // converged reaching this kernel, or a bug) raises kErrScatter -- an internal error unless the batch is re-run anyway -- instead
+    // of writing outside the pool.
+    const uint32_t n_contours = min(ctr->contours, max_contours);
+    bool bad = false;
     // B darts per lane at a time, three rounds of loads instead of five per dart: {state, record} -> {leader's key, border
     // slot of the leader} -> {border record, start offset}.  Unconditional loads from clamped indices, see k_jump_finalize.
     constexpr int B = A3_SCAT_B;
@@ -1553,7 +1652,7 @@ __global__ __launch_bounds__(256) void k_scatter_points(const FinState* __restri
 #pragma unroll
         for (int u = 0; u < B; u++) {
             const uint32_t d = min(d0 + (uint32_t)u * stride, n_darts - 1u);
-            s[u] = fin[d];
+            s[u] = fin_final(fin[d], d, es);   // (one more round of loads, for pending states only)
         }
 #pragma unroll
         for (int u = 0; u < B; u++) {
@@ -1570,7 +1669,9 @@ __global__ __launch_bounds__(256) void k_scatter_points(const FinState* __restri
         for (int u = 0; u < B; u++) {
             // a leader that does not hold its own key: an open chain, or states of a run that has not converged (the batch is
             // then re-run) -- its slot was never written this batch
-            live[u] = live[u] && ls[u].leader == s[u].leader && c[u] != kFinHops;
+            const bool named = live[u] && ls[u].leader == s[u].leader && c[u] != kFinHops;
+            live[u] = named && c[u] < n_contours;
+            bad |= named && !live[u];
             r[u] = contours[live[u] ? c[u] : 0u];
             so[u] = cyc_start_off[live[u] ? c[u] : 0u];
         }
@@ -1580,9 +1681,11 @@ __global__ __launch_bounds__(256) void k_scatter_points(const FinState* __restri
             // off = hops forward to the leader; position along the border counted from the start dart
             const uint32_t off = s[u].leader == d0 + (uint32_t)u * stride ? 0u : s[u].w & kFinHops;   // (the leader's own hops field holds its slot)
             const uint32_t rank = so[u] >= off ? so[u] - off : so[u] + r[u].n - off;
-            points[r[u].point_base + rank] = rec_xy(rec[u]);
+            if (rank < r[u].n && (uint64_t)r[u].point_base + rank < max_points) points[r[u].point_base + rank] = rec_xy(rec[u]);
+            else bad = true;
         }
     }
+    if (bad) atomicOr(&ctr->err_flags, kErrScatter);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1867,15 +1970,18 @@ hipError_t launch_dart_build(hipStream_t st, const uint64_t* bits, int W, int H,
 }
 
 size_t entry_state_bytes() { return sizeof(EntryState); }
+// launch_rank_cycles leaves pending states for the readers to resolve (no k_jump_finalize) on the clean-frame path when the natural starts
+// are checked inline (no fixpoint passes)
+bool finalize_inline(bool frame_entries, bool trust_natural) { return frame_entries && trust_natural; }
 size_t fin_state_bytes() { return sizeof(FinState); }
 size_t entry_slots(uint32_t n_darts) { return (size_t)entry_shard_cap(n_darts) * kEntryShards; }
 size_t leader_list_bytes(uint32_t n_darts) { return (size_t)leader_shard_cap(n_darts) * kLeaderShards * 4; }
 
-// leaders + ranks for every dart of the chunk.  loc/fin: JumpState[n_darts]; es_a/es_b: EntryState[n_darts] (upper bound);
+// leaders + ranks for every dart of the chunk.  fin: FinState[n_darts]; es_a/es_b: EntryState[entry_slots(n_darts)];
 // entry_count[16] and leader_count[16] arrive zeroed.
 hipError_t launch_rank_cycles(hipStream_t st, uint32_t n_darts, int W, const uint64_t* d_rec, const uint32_t* d_succ,
-                              JumpState* loc, uint32_t* entry_list,
-                              unsigned int* entry_count, void* es_a, void* es_b, void* fin /* FinState[n_darts] */, uint32_t* leader_list,
+                              uint32_t* entry_list,
+                              unsigned int* entry_count, void* es_a, void* es_b, void* fin8 /* FinState[n_darts] */, uint32_t* leader_list,
                               unsigned int* leader_count, int max_rounds, DeviceCounters* ctr, const uint32_t* n_live, int dbg,
                               const uint32_t* frame_base, uint32_t* frame_entries /*nullptr: global rounds*/, uint32_t n_frames,
                               int phase /* 0: everything, 1: k_local_contract only, 2: what follows it */,
@@ -1883,48 +1989,59 @@ hipError_t launch_rank_cycles(hipStream_t st, uint32_t n_darts, int W, const uin
                               int trust_natural /* no fixpoint passes follow: k_cycle_select checks the natural starts inline */) {
     // entry_count[16] and leader_count[16] arrive zeroed (the caller's per-batch / per-chunk memset)
     const uint32_t ecap = entry_shard_cap(n_darts);
+    FinState* fin = reinterpret_cast<FinState*>(fin8);
+    // Clean frames with the natural starts checked inline: no k_jump_finalize.  k_local_contract and k_entry_frame list the leaders, the
+    // readers resolve pending states themselves (fin_final); launch_select_scatter is handed the entry table (finalize_inline()).
+    const bool no_finalize = finalize_inline(frame_entries != nullptr, trust_natural != 0) && dbg == 0;
+    uint32_t* const ll = no_finalize ? leader_list : nullptr;
+    const uint32_t lcap = leader_shard_cap(n_darts);
     if (phase != 2) {
         if (frame_entries && !dead_count)
-            hipLaunchKernelGGL((k_local_contract<kLTFrame, false>), dim3((n_darts + kLTFrame - 1) / kLTFrame), dim3(256), 0, st, n_darts, W, d_rec, d_succ, loc,
-                               entry_list, entry_count, ecap, frame_base, frame_entries, n_live, dbg, min_edge_length, dead_count, trust_natural);
+            hipLaunchKernelGGL((k_local_contract<kLTFrame, false>), dim3((n_darts + kLTFrame - 1) / kLTFrame), dim3(256), 0, st, n_darts, W, d_rec, d_succ, fin,
+                               entry_list, entry_count, ecap, frame_base, frame_entries, n_live, dbg, min_edge_length, dead_count, trust_natural,
+                               ll, leader_count, lcap);
         else if (frame_entries)   // (a dense graph's first batch, before its entries overflow k_entry_frame and the global rounds take over)
-            hipLaunchKernelGGL((k_local_contract<kLTFrame, true>), dim3((n_darts + kLTFrame - 1) / kLTFrame), dim3(256), 0, st, n_darts, W, d_rec, d_succ, loc,
-                               entry_list, entry_count, ecap, frame_base, frame_entries, n_live, dbg, min_edge_length, dead_count, trust_natural);
+            hipLaunchKernelGGL((k_local_contract<kLTFrame, true>), dim3((n_darts + kLTFrame - 1) / kLTFrame), dim3(256), 0, st, n_darts, W, d_rec, d_succ, fin,
+                               entry_list, entry_count, ecap, frame_base, frame_entries, n_live, dbg, min_edge_length, dead_count, trust_natural,
+                               ll, leader_count, lcap);
         else
-            hipLaunchKernelGGL((k_local_contract<kLT, true>), dim3((n_darts + kLT - 1) / kLT), dim3(256), 0, st, n_darts, W, d_rec, d_succ, loc,
-                               entry_list, entry_count, ecap, frame_base, frame_entries, n_live, dbg, min_edge_length, dead_count, trust_natural);
+            hipLaunchKernelGGL((k_local_contract<kLT, true>), dim3((n_darts + kLT - 1) / kLT), dim3(256), 0, st, n_darts, W, d_rec, d_succ, fin,
+                               entry_list, entry_count, ecap, frame_base, frame_entries, n_live, dbg, min_edge_length, dead_count, trust_natural,
+                               ll, leader_count, lcap);
     }
     if (dbg || phase == 1) return hipGetLastError();
     EntryState* a = reinterpret_cast<EntryState*>(es_a);
     EntryState* b = reinterpret_cast<EntryState*>(es_b);
     if (frame_entries) {   // clean frames: every frame's entry list fits LDS, one launch instead of ~9
-        hipLaunchKernelGGL(k_entry_frame, dim3(n_frames), dim3(256), 0, st, entry_list, frame_entries, frame_base, loc, a, ctr);
+        hipLaunchKernelGGL(k_entry_frame, dim3(n_frames), dim3(256), 0, st, entry_list, frame_entries, frame_base, fin, d_rec, W, a, ctr,
+                           ll, leader_count, lcap);
+        if (no_finalize) return hipGetLastError();
         const int fin_blocks = std::max(blocks_for(n_darts, 256, env_cap("A3_FIN_BLOCKS", 1536)), (int)(((uint64_t)n_darts + 256ull * 32 - 1) / (256ull * 32)));
-        hipLaunchKernelGGL(k_jump_finalize, dim3(fin_blocks), dim3(256), 0, st, n_darts, loc, a, reinterpret_cast<FinState*>(fin),
+        hipLaunchKernelGGL(k_jump_finalize, dim3(fin_blocks), dim3(256), 0, st, n_darts, a, fin,
                            leader_list, leader_count, leader_shard_cap(n_darts), n_live, ctr);
         return hipGetLastError();
     }
     const dim3 grid(blocks_for(n_darts / 16 + 1, 256, 1024)), block(256);   // entries are a few % of the darts on clean frames
-    hipLaunchKernelGGL(k_entry_init, grid, block, 0, st, entry_list, entry_count, loc, a, ecap);
+    hipLaunchKernelGGL(k_entry_init, grid, block, 0, st, entry_list, entry_count, fin, d_rec, W, a, ecap);
     for (int r = 0; r < max_rounds; r++) {
         hipLaunchKernelGGL(k_entry_jump, grid, block, 0, st, a, b, entry_count, ecap, r, ctr);
         EntryState* t = a; a = b; b = t;
     }
     const int fin_blocks = std::max(blocks_for(n_darts, 256, env_cap("A3_FIN_BLOCKS", 1536)), (int)(((uint64_t)n_darts + 256ull * 32 - 1) / (256ull * 32)));
-    hipLaunchKernelGGL(k_jump_finalize, dim3(fin_blocks), block, 0, st, n_darts, loc, a, reinterpret_cast<FinState*>(fin),
+    hipLaunchKernelGGL(k_jump_finalize, dim3(fin_blocks), block, 0, st, n_darts, a, fin,
                        leader_list, leader_count, leader_shard_cap(n_darts), n_live, ctr);
     return hipGetLastError();
 }
 
-hipError_t launch_resolve(hipStream_t st, const JumpState* loc, const void* fin8, uint32_t n_darts, int W, const uint64_t* d_rec, const uint32_t* leader_list,
+hipError_t launch_resolve(hipStream_t st, const void* fin8, uint32_t n_darts, int W, const uint64_t* d_rec, const uint32_t* leader_list,
                           const unsigned int* leader_count, uint64_t* t_cur, uint64_t* t_next, DeviceCounters* ctr, int max_iters,
                           const uint32_t* n_live) {
     const FinState* fin = reinterpret_cast<const FinState*>(fin8);
     if (max_iters <= 0) return hipSuccess;   // k_cycle_select checks the natural starts itself; the caller re-runs the batch if they do not hold
     const dim3 grid(blocks_for(n_darts, 256, 4096)), block(256);
-    hipLaunchKernelGGL(k_resolve_fast, dim3(blocks_for(n_darts / 16 + 1, 256, 1024)), block, 0, st, loc, fin, leader_list, leader_count,
+    hipLaunchKernelGGL(k_resolve_fast, dim3(blocks_for(n_darts / 16 + 1, 256, 1024)), block, 0, st, fin, leader_list, leader_count,
                        leader_shard_cap(n_darts), W, d_rec, t_cur, ctr);
-    hipLaunchKernelGGL(k_resolve_init, grid, block, 0, st, loc, fin, n_darts, t_cur, t_next, ctr, n_live);
+    hipLaunchKernelGGL(k_resolve_init, grid, block, 0, st, fin, d_rec, W, n_darts, t_cur, t_next, ctr, n_live);
     for (int it = 0; it < max_iters; it++) {
         hipLaunchKernelGGL(k_resolve_eval, grid, block, 0, st, fin, n_darts, W, d_rec, t_cur, t_next, it, ctr, n_live);
         hipLaunchKernelGGL(k_resolve_commit, grid, block, 0, st, fin, n_darts, t_cur, t_next, it, it == max_iters - 1 ? 1 : 0, ctr, n_live);
@@ -1932,19 +2049,22 @@ hipError_t launch_resolve(hipStream_t st, const JumpState* loc, const void* fin8
     return hipGetLastError();
 }
 
-hipError_t launch_select_scatter(hipStream_t st, const JumpState* loc, const void* fin8, uint32_t n_darts, const uint32_t* leader_list,
+hipError_t launch_select_scatter(hipStream_t st, const void* fin8, uint32_t n_darts, const uint32_t* leader_list,
                                  const unsigned int* leader_count, const uint32_t* d_succ, const uint64_t* t_cur,
                                  const uint32_t* frame_base, uint32_t n_frames, uint32_t first_frame, uint32_t min_edge_length,
                                  double eps_factor, double image_diag, ContourRec* contours, uint32_t* cyc_start_off,
                                  uint32_t max_contours, uint64_t max_points, DeviceCounters* ctr, const uint64_t* d_rec, uint32_t* points,
-                                 const uint32_t* n_live, int inline_resolve_W, uint32_t* keep_tmp, int keep_all) {
+                                 const uint32_t* n_live, int inline_resolve_W, uint32_t* keep_tmp, int keep_all,
+                                 const void* es8 /* the entry table when finalize_inline(): pending states are resolved by the readers */) {
+    const EntryState* es = reinterpret_cast<const EntryState*>(es8);
     // 8192 workgroups for the graphs of clean frames (6-8 M darts), more for the tens of millions of darts of noise-like ones
     const dim3 grid(blocks_for(n_darts, 256, env_cap("A3_SCATTER_BLOCKS", (int)std::min<uint32_t>(65536u, std::max<uint32_t>(8192u, n_darts / 1024u))))), block(256);
-    hipLaunchKernelGGL(k_cycle_select, dim3(blocks_for(n_darts / 64 + 1, 256, env_cap("A3_SELECT_BLOCKS", 1024))), block, 0, st, loc, reinterpret_cast<FinState*>(const_cast<void*>(fin8)), leader_list, leader_count, d_succ, t_cur,
+    hipLaunchKernelGGL(k_cycle_select, dim3(blocks_for(n_darts / 64 + 1, 256, env_cap("A3_SELECT_BLOCKS", 1024))), block, 0, st, reinterpret_cast<FinState*>(const_cast<void*>(fin8)), leader_list, leader_count, d_succ, t_cur,
                        frame_base, n_frames, first_frame, min_edge_length,
                        eps_factor, image_diag, contours, cyc_start_off, max_contours, max_points, ctr, leader_shard_cap(n_darts), d_rec,
-                       inline_resolve_W, keep_tmp, keep_all);
-    hipLaunchKernelGGL(k_scatter_points, grid, block, 0, st, reinterpret_cast<const FinState*>(fin8), n_darts, d_rec, contours, cyc_start_off, points, n_live, ctr);
+                       inline_resolve_W, keep_tmp, keep_all, es);
+    hipLaunchKernelGGL(k_scatter_points, grid, block, 0, st, reinterpret_cast<const FinState*>(fin8), n_darts, d_rec, contours, cyc_start_off, points, n_live, ctr,
+                       max_contours, max_points, es);
     return hipGetLastError();
 }
 
