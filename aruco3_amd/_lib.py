@@ -40,7 +40,7 @@ SYMBOLS = [
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
-INTERNAL_SYMBOLS = ["a3_debug_set_k1_stream", "a3_debug_set_overlap", "a3_debug_set_k1_waves", "a3_debug_set_partition", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_mark_threshold", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_stream_wait_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
+INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
 
 
 class A3Error(RuntimeError):
@@ -185,12 +185,6 @@ def load():
     if hasattr(L, "a3_debug_set_overlap"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack it)
         L.a3_debug_set_overlap.restype = C.c_int
         L.a3_debug_set_overlap.argtypes = [C.c_int]
-    if hasattr(L, "a3_debug_set_k1_stream"):
-        L.a3_debug_set_k1_stream.restype = C.c_int
-        L.a3_debug_set_k1_stream.argtypes = [C.c_int]
-    if hasattr(L, "a3_debug_set_k1_waves"):
-        L.a3_debug_set_k1_waves.restype = C.c_int
-        L.a3_debug_set_k1_waves.argtypes = [C.c_int]
     if hasattr(L, "a3_debug_launch_threshold"):
         L.a3_debug_launch_threshold.restype = C.c_int
         L.a3_debug_launch_threshold.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -200,20 +194,12 @@ def load():
     if hasattr(L, "a3_debug_set_jump_rounds"):
         L.a3_debug_set_jump_rounds.restype = C.c_int
         L.a3_debug_set_jump_rounds.argtypes = [C.c_int]
-    if hasattr(L, "a3_debug_set_mark_threshold"):
-        L.a3_debug_set_mark_threshold.restype = C.c_int
-        L.a3_debug_set_mark_threshold.argtypes = [C.c_int]
-        L.a3_debug_stream_wait_threshold.restype = C.c_int
-        L.a3_debug_stream_wait_threshold.argtypes = [vp, vp]
     if hasattr(L, "a3_debug_spin"):
         L.a3_debug_spin.restype = C.c_int
         L.a3_debug_spin.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "a3_debug_build_flags"):
         L.a3_debug_build_flags.restype = C.c_int
         L.a3_debug_build_flags.argtypes = []
-    if hasattr(L, "a3_debug_set_partition"):
-        L.a3_debug_set_partition.restype = C.c_int
-        L.a3_debug_set_partition.argtypes = [C.c_int, C.c_int]
     L.a3_debug_kernel_time.restype = C.c_int
     L.a3_debug_kernel_time.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.a3_get_stats.restype = C.c_int

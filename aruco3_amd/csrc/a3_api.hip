@@ -18,9 +18,7 @@
 namespace a3 {
 // k_threshold.hip
 hipError_t launch_grey_threshold(hipStream_t, const uint8_t*, int, size_t, size_t, int, int, uint32_t, uint32_t, uint8_t*, uint64_t*, uint16_t*);
-void set_k1_waves(int);
 bool threshold_writes_grey_plane(uint32_t radius, const uint8_t* pixels, size_t row_stride, size_t frame_stride, int W);
-void set_k1_cus(int);
 bool k1_build_is_default();
 // k_contours.hip
 hipError_t launch_dart_count(hipStream_t, const uint64_t*, int, int, uint32_t, uint32_t, unsigned long long*, uint32_t*, uint64_t, uint32_t*, uint32_t*, void*, size_t);
@@ -124,38 +122,34 @@ struct DevBuf {
 };
 
 struct Chunk { uint32_t first, count; uint64_t darts; uint32_t max_frame_darts; };
-// The second half of a batch (candidates -> markers -> read-back), kept aside when its enqueue is deferred: everything
-// enqueue_back needs besides the context's buffers.
-struct BackArgs {
-    uint32_t n = 0, W = 0, H = 0, S = 0, max_cand = 0, patch_cap = 0, marker_cap = 0, guess = 0;
-    float min_corner_separation = 0.0f;
-    PixelSrc src{};
-    size_t head_bytes = 0, pose_bytes = 0;
-    bool taps = false, want_pose = false, pose_has_intr = false;
+// One batch: the call and every setting it runs with, captured once when it starts (begin_batch) -- a setter called while the batch
+// is in flight applies to the next one -- and what its enqueue decided.  enqueue_front, enqueue_chain, enqueue_back (also when it is
+// deferred), finish_batch and the synchronous re-run read this record, never the context's live settings.
+struct Batch {
+    // the call (pixels: on the device)
+    const uint8_t* pixels = nullptr; int fmt = 0;
+    uint32_t W = 0, H = 0, n = 0;
+    size_t row_stride = 0, frame_stride = 0, out_cap = 0;
+    // settings
+    bool want_pose = false, pose_has_intr = false;   // a3_detect_batch_pose*: poses of every marker, solved on the device
     float pose_size_mm = 0.0f;
     a3_intrinsics pose_intr{};
-    int profiling = 0;
-    a3_refine_config refine{};   // the batch's corner refinement (method NONE: none)
+    size_t pose_bytes = 0;       // 2 poses per marker with poses, else 0
+    a3_refine_config refine{};   // corner refinement (method NONE: none)
     size_t refine_bytes = 0;     // 32 (8 floats per marker) with refinement, else 0
-    bool board = false;          // a pose batch with a board: k_board_pose runs behind k_pose
-};
-
-// what finish_batch needs to know about the batch enqueue_batch put on the stream
-struct Pending {
+    bool board = false;          // a pose batch with a board set: k_board_pose runs behind k_pose
+    bool taps = false;           // debug taps: grey plane, patches, contours and the per-frame candidate counts are kept
+    int profiling = 0, profile_every = 1;   // a3_set_profiling in force
+    // enqueue_front
+    int prof = 0;                // the profiling level of this enqueue (the sampled threshold-only mode times one batch in profile_every)
+    bool need_grey = false;      // the threshold kernel writes the grey plane (taps, or a window above 15)
+    uint32_t max_cand = 0, patch_cap = 0, marker_cap = 0, guess = 0;
+    // enqueue_chain
     bool active = false, device_plan = false;
-    size_t n_chunks = 0, ctr_bytes = 0, head_pad = 0, pose_bytes = 0;
+    size_t n_chunks = 0, ctr_bytes = 0, head_bytes = 0;
     uint64_t chunk0_darts = 0;
-    uint32_t marker_cap = 0, guess = 0, n = 0, W = 0, H = 0;
-    int rounds_max = 0, profiling = 0;
-    bool taps = false;   // debug taps were on: the per-frame candidate counts came back with the results
-    // the submitted call, for the synchronous re-run when the device asks for one
-    const uint8_t* pixels = nullptr; int fmt = 0; size_t row_stride = 0, frame_stride = 0;
-    bool want_pose = false;   // a3_detect_batch_pose_submit: the re-run must solve the poses again
-    // corner refinement in force for this batch, captured when it was submitted (a3_set_corner_refinement affects later batches;
-    // a held chain and a re-run use this copy)
-    a3_refine_config refine{};
-    size_t refine_bytes = 0;
-    bool board = false;   // a pose batch submitted with a board set (the board's device tables were brought up to date at submit)
+    int rounds_max = 0;
+    PixelSrc src{};              // what the decode stage samples: the caller's frames or the grey plane
 };
 
 }  // namespace
@@ -167,11 +161,10 @@ struct a3_ctx {
     // compute stream waits for the copy through ev_in: with two contexts in flight (submit / collect) the H2D of batch i+1 runs
     // under the kernels of batch i
     hipEvent_t ev_in = nullptr;
-    // Deferred decode (submit / collect with more than one context, see enqueue_batch): the decode stage of a submitted batch
+    // Deferred decode (submit / collect with more than one context, see enqueue_chain): the decode stage of a submitted batch
     // runs on the device's decode stream, released from inside the launch sequence of the NEXT submitted batch, so that it shares
     // the GPU with that batch's contour stage (both are latency-bound and leave the chip mostly idle) instead of standing in line.
-    hipEvent_t ev_contours = nullptr, ev_k1 = nullptr, ev_k1_ready = nullptr, ev_k1_done = nullptr, ev_gate = nullptr;
-    bool k1_marked = false;          // ev_k1_done was recorded behind the threshold kernel of the batch in flight
+    hipEvent_t ev_contours = nullptr, ev_k1 = nullptr, ev_k1_done = nullptr, ev_gate = nullptr;
     // Bursts (a3_order_after): a context that declared gates since its last submit is a member of a burst that is not the last
     // one: its submit enqueues the threshold kernel only and HOLDS the rest (contour stage ... read-back) until the burst's last
     // member -- the first submit without gates on the device -- has enqueued its threshold kernel; the held chains are then
@@ -179,8 +172,6 @@ struct a3_ctx {
     bool gates_declared = false;     // a3_order_after was called since the last submit
     bool rest_held = false;          // guarded by g_defer_mu: the chain of the submitted batch has not been enqueued yet
     int held_rc = 0;                 // guarded by g_defer_mu: what enqueueing the held chain returned, whoever did it
-    int front_prof = 0;              // profiling level in force for the batch whose front half has been enqueued
-    size_t held_out_cap = 0;
     bool back_deferred = false;      // guarded by g_defer_mu
     int back_rc = 0;                 // a failed launch of the deferred half, whoever enqueued it (guarded by g_defer_mu): collect reports it
     bool allow_defer = false;        // set by the submit entry points for the batch being enqueued
@@ -188,7 +179,6 @@ struct a3_ctx {
     std::atomic<uint32_t> stepping{0};   // A3_STEP_* of the batch in flight / last finished (a3_stats.stepping); another thread's submit may release this context's held chain
     uint32_t released_others = 0;    // held chains of other contexts this batch's submit released (the burst's last member)
     uint32_t reruns = 0;             // synchronous re-runs the device asked for while the last call's batch was produced (pool growth, more passes, host plan)
-    BackArgs back;
     a3_config cfg{};
     uint8_t num_bits = 0, tau = 0;
     uint32_t n_codes = 0, mark_size = 0;
@@ -200,15 +190,15 @@ struct a3_ctx {
     // launch-count hints (every pass past convergence is an empty launch of ~5 us): start low, retry the batch with the
     // maximum if a pass count turns out too small
     int jump_rounds_hint = 10, resolve_iters_hint = 4;
-    uint32_t dbg_nd = 0, dbg_frames = 0, dbg_chunks = 0;
+    uint32_t dbg_nd = 0, dbg_frames = 0, dbg_chunks = 0;   // a3_debug_kernel_time: shape of the last batch's contour graph
     PixelSrc dbg_src{};
     // a3_debug_inject_candidates (tests only): quads that replace frame 0's candidate list of the next batch, between the contour
     // stage and k_frame_candidates (quirk Q4: a degenerate quad cannot come out of a convex hull)
     std::vector<CandRec> inject;
     bool inject_armed = false;
     uint32_t inject_count = 0;
-    Pending pending;
-    bool pending_trivial = false;   // a submitted batch with no frames / empty images   // a3_debug_kernel_time: shape of the last batch's contour graph
+    Batch batch;                    // the batch in flight (or the last one)
+    bool pending_trivial = false;   // a submitted batch with no frames / empty images
     int resolve_full_ttl = 0;
     int entry_global_ttl = 0;   // > 0: a recent batch had a frame whose entry list did not fit LDS: use the global doubling rounds
     // device-side planning: the previous batch of this shape fitted one chunk with plan_darts darts, so this one is enqueued
@@ -216,13 +206,7 @@ struct a3_ctx {
     bool plan_valid = false, force_host_plan = false;
     uint32_t plan_n = 0, plan_W = 0, plan_H = 0;
     uint64_t plan_darts = 0;   // > 0: launch the fixpoint passes over all darts too (a recent batch needed them); else only k_resolve_fast
-    // a3_detect_batch_pose: poses of every marker are computed on the device right after detection
-    bool want_pose = false;
-    float pose_size_mm = 0.0f;
-    bool pose_has_intr = false;
-    a3_intrinsics pose_intr{};
-    a3_pose* pose_out = nullptr;
-    bool debug_taps = false;
+    bool debug_taps = false;   // a3_set_debug_taps: the setting the next batch captures
     uint32_t patch_cap = 0;    // patches the tap of the last tapped batch could hold
     bool grey_valid = false;   // the last batch wrote the grey plane
     // a3_download_contours: the last batch ran with debug taps in one chunk, so its contour table and point pool are whole
@@ -231,7 +215,9 @@ struct a3_ctx {
     // a3_pack_detections: the marker list of the last finished batch is still on the device
     bool markers_valid = false;
     uint32_t last_n = 0, last_max_per_frame = 0;
-    int profiling = 0;   // 0 off, 1 threshold stage only, 2 every stage (an event record between kernels costs ~6 us of device time)
+    // a3_set_profiling, the setting the next batch captures: 0 off, 1 threshold stage only, 2 every stage (an event record between
+    // kernels costs ~6 us of device time)
+    int profiling = 0;
     int profile_every = 1;   // threshold-only mode: time every k-th batch (A3_PROFILE_THRESHOLD_SAMPLED: 4)
     uint32_t batch_seq = 0;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -370,50 +356,21 @@ int ensure_dart_pool(a3_ctx* ctx, uint64_t darts) {
 // batch's line -- measured: a second set of contexts, each with three streams of its own, lost 10 % where the first set gained
 // 7 %.  So streams are few: ONE decode stream and ONE copy stream per device, shared by all contexts (their work never wants to
 // overlap with itself), created on first use; a context's own stream exists only if the caller never passed one (a3_set_stream).
-struct DeviceStreams { hipStream_t decode = nullptr, copy = nullptr, k1 = nullptr; };
+struct DeviceStreams { hipStream_t decode = nullptr, copy = nullptr; };
 std::mutex g_streams_mu;
 DeviceStreams g_dev_streams[64];
-bool g_decode_low_prio = false;   // (see a3_debug_set_overlap)
-// CU partition (a3_internal.h: a3_debug_set_partition): the threshold kernel of every batch on a device-wide stream restricted to
-// g_part_k1_cus compute units, everything else on streams restricted to the others.  0 = off.
-int g_part_k1_cus = 0, g_part_pattern = 0;
-// a3_debug_set_k1_stream (measurement aid): 0 off; 1 / 2: the threshold kernel of every batch on a device-wide stream of the LOWEST /
-// HIGHEST priority (no CU mask), ordered against the context's stream by two events
-int g_k1_stream_prio = 0;
 bool g_hold_rests = true;        // a3_debug_set_hold: bursts hold their chains back (see submit_common); 0 for A/B
 std::atomic<int> g_jump_rounds_cap{0};   // a3_debug_set_jump_rounds: at most this many global doubling rounds (0: no cap)
-bool g_mark_threshold = false;   // a3_debug_set_mark_threshold: record an event behind every threshold kernel (costs ~2 % of a step: tools/spin_probe.py)
-enum { kStreamCopy = 0, kStreamDecode = 1, kStreamK1 = 2 };
+enum { kStreamCopy = 0, kStreamDecode = 1 };
 
-// CU masks of the partition: 256 bits, bit i = compute unit i as the runtime numbers them
-void partition_masks(uint32_t k1[8], uint32_t rest[8]) {
-    for (int i = 0; i < 8; i++) { k1[i] = 0u; rest[i] = 0u; }
-    for (int cu = 0; cu < 256; cu++) {
-        bool to_k1;
-        if (g_part_pattern == 0) to_k1 = cu < g_part_k1_cus;                                   // the first k
-        else to_k1 = ((cu % 16) * g_part_k1_cus) / 256 != (((cu % 16) + 1) * g_part_k1_cus) / 256;   // k/256 of every group of 16
-        (to_k1 ? k1 : rest)[cu >> 5] |= 1u << (cu & 31);
-    }
-}
-
-hipError_t create_stream(hipStream_t* st, int role /* 0 rest, 1 k1 */, int priority) {
-    if (g_part_k1_cus > 0) {
-        uint32_t k1[8], rest[8];
-        partition_masks(k1, rest);
-        return hipExtStreamCreateWithCUMask(st, 8, role ? k1 : rest);
-    }
-    return hipStreamCreateWithPriority(st, hipStreamNonBlocking, priority);
-}
+hipError_t create_stream(hipStream_t* st) { return hipStreamCreateWithPriority(st, hipStreamNonBlocking, 0); }
 
 hipError_t device_stream(int device, int kind, hipStream_t* out) {
     std::lock_guard<std::mutex> lk(g_streams_mu);
     DeviceStreams& ds = g_dev_streams[device & 63];
-    hipStream_t& st = kind == kStreamDecode ? ds.decode : (kind == kStreamK1 ? ds.k1 : ds.copy);
+    hipStream_t& st = kind == kStreamDecode ? ds.decode : ds.copy;
     if (!st) {
-        int lo = 0, hi = 0;
-        hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-        const int prio = kind == kStreamDecode && g_decode_low_prio ? lo : (kind == kStreamK1 && g_k1_stream_prio == 1 ? lo : (kind == kStreamK1 && g_k1_stream_prio == 2 ? hi : 0));
-        if (e == hipSuccess) e = create_stream(&st, kind == kStreamK1 ? 1 : 0, prio);
+        const hipError_t e = create_stream(&st);
         if (e != hipSuccess) { st = nullptr; return e; }
     }
     *out = st;
@@ -472,7 +429,9 @@ const void* refine_params_for(a3_ctx* ctx, const a3_refine_config& cfg) {
 }
 
 // candidates -> markers -> read-back of one batch, on stream `st` (the context's stream, or its decode stream when deferred)
-int enqueue_back(a3_ctx* ctx, hipStream_t st, const BackArgs& b) {
+int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
+    const uint32_t S = ctx->cfg.homography_sample_size;
+    const float min_corner_separation = (float)std::min(b.W, b.H) * ctx->cfg.min_corner_separation_factor;   // src/aruco.rs:56
     unsigned int* d_work_count = ctx->scratch_u32 + 0;
     unsigned int* d_marker_total = ctx->scratch_u32 + 1;
     unsigned int* d_err = ctx->scratch_u32 + 4;
@@ -483,15 +442,15 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const BackArgs& b) {
         ctx->inject_count = cnt;
         A3_HIP(hipMemcpyAsync(ctx->cand_count, &ctx->inject_count, 4, hipMemcpyHostToDevice, st));
     }
-    A3_HIP(launch_frame_candidates(st, ctx->cands.as<CandRec>(), ctx->cand_count, b.n, b.max_cand, b.min_corner_separation,
+    A3_HIP(launch_frame_candidates(st, ctx->cands.as<CandRec>(), ctx->cand_count, b.n, b.max_cand, min_corner_separation,
                                    ctx->pre_xy.as<uint16_t>(), ctx->fin_xy.as<uint16_t>(), ctx->fin_count.as<uint32_t>(),
-                                   ctx->work.as<uint32_t>(), d_work_count, b.S, ctx->proj.p, ctx->cand_big.as<float>()));
+                                   ctx->work.as<uint32_t>(), d_work_count, S, ctx->proj.p, ctx->cand_big.as<float>()));
     // few frames (small batches): all four waves of a workgroup run the stages behind the sampling.  (Round 5 tried folding the marker
     // gather into k_decode for one-frame calls -- its last workgroup, found by a ticket -- to save a launch: the call got 5 us SLOWER,
     // 166 against 161 us in alternating runs, a fence + ticket per workgroup and a serial tail costing more than the launch; removed.)
     const int few = b.n <= 64u ? 1 : 0;
     A3_HIP(launch_decode(st, b.src, (int)b.W, (int)b.H, 0, ctx->fin_xy.as<uint16_t>(), ctx->work.as<uint32_t>(), d_work_count,
-                         b.max_cand, b.S, ctx->mark_size, b.S, ctx->dict.as<uint64_t>(), ctx->n_codes, ctx->tau, ctx->cfg.filter_high_bit_errors,
+                         b.max_cand, S, ctx->mark_size, S, ctx->dict.as<uint64_t>(), ctx->n_codes, ctx->tau, ctx->cfg.filter_high_bit_errors,
                          ctx->proj.p, ctx->wtab.as<float>(), ctx->outs.p, b.taps ? ctx->patches.as<uint8_t>() : nullptr, b.patch_cap, ctx->per_frame,
                          (int)std::min<uint32_t>(4096u, b.n * 128u) /* (grid-stride over the work list; 4096 workgroups that find nothing cost a one-frame call ~4 us) */, 0,
                          few));
@@ -514,7 +473,7 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const BackArgs& b) {
                                      ctx->per_frame, b.marker_cap, b.n, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p,
                                      b.pose_has_intr ? &in : nullptr, b.W, b.H, ctx->board_buf.as<a3_board_pose>()));
     }
-    if (b.profiling >= 2) A3_HIP(hipEventRecord(ctx->ev[3], st));
+    if (b.prof >= 2) A3_HIP(hipEventRecord(ctx->ev[3], st));
     // ---- results: one copy of [scratch | counters | per-frame counts | `guess` markers], then the poses and (taps) the counts ----
     uint8_t* hp = (uint8_t*)ctx->pinned;
     a3_pose* h_poses = reinterpret_cast<a3_pose*>(hp + b.head_bytes + (size_t)b.guess * sizeof(a3_marker));
@@ -551,7 +510,7 @@ int flush_deferred_impl(a3_ctx* ctx, hipEvent_t after) {
     A3_HIP(device_stream(ctx->device, kStreamDecode, &ds));
     A3_HIP(hipStreamWaitEvent(ds, ctx->ev_contours, 0));
     if (after) A3_HIP(hipStreamWaitEvent(ds, after, 0));
-    if (int rc = enqueue_back(ctx, ds, ctx->back)) return rc;
+    if (int rc = enqueue_back(ctx, ds, ctx->batch)) return rc;
     (void)hipStreamQuery(ds);   // hands what was just queued to the GPU now (the owner polls an event, not this stream)
     return A3_OK;
 }
@@ -560,7 +519,7 @@ int need_stream(a3_ctx* ctx) {
     if (ctx->stream) return A3_OK;
     if (!ctx->own_stream) {
         A3_HIP(hipSetDevice(ctx->device));
-        A3_HIP(create_stream(&ctx->own_stream, 0, 0));
+        A3_HIP(create_stream(&ctx->own_stream));
     }
     {   // (batch_mode_of reads every live context's stream under this lock, possibly from another thread's submit)
         std::lock_guard<std::mutex> lk(g_streams_mu);
@@ -571,8 +530,7 @@ int need_stream(a3_ctx* ctx) {
 
 // ---- bursts: contexts whose submitted batch has its threshold kernel enqueued and the rest held back (see a3_ctx::rest_held) ----
 std::vector<a3_ctx*> g_held;   // guarded by g_defer_mu, in submission order
-int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint32_t H, size_t row_stride, size_t frame_stride, uint32_t n,
-                  size_t out_cap, int phase, bool defer_locked = false);
+int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked);
 // Enqueue the held chain of `ctx`'s batch on its stream, behind `after` when given (the threshold kernel of the burst's last
 // member).  g_defer_mu is held; the owner may be another thread's context, so the verdict is kept for its collect.
 int flush_held_locked(a3_ctx* ctx, hipEvent_t after, bool by_last_member = false) {
@@ -581,13 +539,9 @@ int flush_held_locked(a3_ctx* ctx, hipEvent_t after, bool by_last_member = false
     ctx->stepping = by_last_member ? A3_STEP_HELD_RELEASED_BY_LAST : A3_STEP_HELD_RELEASED_EARLY;
     for (size_t i = 0; i < g_held.size(); i++)
         if (g_held[i] == ctx) { g_held.erase(g_held.begin() + (long)i); break; }
-    const Pending pd = ctx->pending;
-    const bool wp = ctx->want_pose;
-    ctx->want_pose = pd.want_pose;
     int rc = A3_OK;
     if (after && hipStreamWaitEvent(ctx->stream, after, 0) != hipSuccess) rc = fail(ctx, A3_ERR_HIP, "hipStreamWaitEvent (burst gate)");
-    if (rc == A3_OK) rc = enqueue_batch(ctx, pd.pixels, pd.fmt, pd.W, pd.H, pd.row_stride, pd.frame_stride, pd.n, ctx->held_out_cap, 2, /*defer_locked=*/true);
-    ctx->want_pose = wp;
+    if (rc == A3_OK) rc = enqueue_chain(ctx, ctx->batch, /*defer_locked=*/true);
     ctx->held_rc = rc;
     (void)hipStreamQuery(ctx->stream);   // hands what was just queued to the GPU now (the owner may be polling an event)
     return rc;
@@ -632,15 +586,31 @@ uint64_t pool_darts_of(const a3_ctx* ctx, uint64_t max_chunk_darts, size_t n_chu
     }
     return pool_darts;
 }
-// Every buffer the chain (contour stage ... read-back) of a DEVICE-PLANNED batch uses, allocated now: a chain that is held back for
-// a burst is enqueued later -- by whichever thread submits the burst's last member, under the process-wide lock -- and must then
-// find nothing left to allocate (hipMalloc / hipHostMalloc synchronise the device).  The same calls stand in enqueue_batch's chain
-// half, where they are no-ops afterwards (the buffers only grow).
-int ensure_chain_buffers(a3_ctx* ctx, hipStream_t st, uint32_t n, uint32_t W, uint32_t H, uint64_t cap_d, size_t out_cap) {
-    const size_t npx = (size_t)W * H;
-    const uint32_t marker_cap = marker_cap_of(ctx, n, out_cap);
-    const ZeroLayout z = zero_layout(1, n, n, marker_cap);
-    A3_HIP(ctx->tile_darts.ensure(tile_darts_bytes(W, H, n)));
+// The second half's buffers: poses, refined corners, board poses, pinned staging for the read-back head and `guess` markers (+ poses
+// ...; a longer list is fetched by finish_batch after growing it), pinned staging for the tap counts.
+int ensure_back_buffers(a3_ctx* ctx, const Batch& b, size_t head_bytes) {
+    const size_t board_bytes = b.board ? (size_t)b.n * sizeof(a3_board_pose) : 0;
+    if (b.want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)b.marker_cap * 2 * sizeof(a3_pose)));
+    if (b.refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)b.marker_cap * b.refine_bytes));
+    if (board_bytes) A3_HIP(ctx->board_buf.ensure(board_bytes));
+    if (int rc = ensure_pinned(ctx, head_bytes + (size_t)b.guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + b.refine_bytes) + board_bytes + (1 << 16))) return rc;
+    if (b.taps && ctx->pinned_counts_cap < (size_t)b.n * 8) {
+        if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
+        ctx->pinned_counts = nullptr; ctx->pinned_counts_cap = 0;
+        A3_HIP(hipHostMalloc(&ctx->pinned_counts, (size_t)b.n * 8, hipHostMallocDefault));
+        ctx->pinned_counts_cap = (size_t)b.n * 8;
+    }
+    return A3_OK;
+}
+// Every buffer the chain (contour stage ... read-back) of a DEVICE-PLANNED batch uses, with a dart capacity of cap_d, allocated
+// before anything of the chain is launched -- for a chain that is held back for a burst, at submit: it is enqueued later, by
+// whichever thread submits the burst's last member, under the process-wide lock, and must then find nothing left to allocate
+// (hipMalloc / hipHostMalloc synchronise the device).  The per-frame dart totals of the device plan live in frame_darts_dev, zeroed
+// once here and handed back zeroed by the plan workgroup.
+int ensure_chain_buffers(a3_ctx* ctx, hipStream_t st, const Batch& b, uint64_t cap_d) {
+    const uint32_t n = b.n;
+    const ZeroLayout z = zero_layout(1, n, n, b.marker_cap);
+    A3_HIP(ctx->tile_darts.ensure(tile_darts_bytes(b.W, b.H, n)));
     A3_HIP(ctx->zero_blk.ensure(z.total));
     if (ctx->frame_darts_dev.cap < (size_t)n * 8) {
         A3_HIP(ctx->frame_darts_dev.ensure((size_t)n * 8));
@@ -648,51 +618,32 @@ int ensure_chain_buffers(a3_ctx* ctx, hipStream_t st, uint32_t n, uint32_t W, ui
     }
     A3_HIP(ctx->frame_base.ensure((size_t)(n + 1) * 4));
     if (int rc = ensure_dart_pool(ctx, pool_darts_of(ctx, cap_d, 1))) return rc;
-    A3_HIP(ctx->pix_base.ensure((size_t)n * npx * 4));
+    A3_HIP(ctx->pix_base.ensure((size_t)n * b.W * b.H * 4));
     A3_HIP(ctx->contours.ensure((size_t)ctx->max_contours * sizeof(ContourRec)));
     A3_HIP(ctx->cyc_start_off.ensure((size_t)ctx->max_contours * 4));
     A3_HIP(ctx->points.ensure(ctx->max_points * 4));
-    if (ctx->want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)marker_cap * 2 * sizeof(a3_pose)));
-    const size_t refine_bytes = ctx->pending.refine.method != A3_REFINE_NONE ? 8 * sizeof(float) : 0;
-    if (refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)marker_cap * refine_bytes));
-    const size_t board_bytes = ctx->pending.board ? (size_t)n * sizeof(a3_board_pose) : 0;
-    if (board_bytes) A3_HIP(ctx->board_buf.ensure(board_bytes));
-    if (int rc = ensure_pinned(ctx, z.head_bytes + (size_t)marker_guess_of(ctx, marker_cap) * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + board_bytes + (1 << 16))) return rc;
-    if (ctx->debug_taps && ctx->pinned_counts_cap < (size_t)n * 8) {
-        if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
-        ctx->pinned_counts = nullptr; ctx->pinned_counts_cap = 0;
-        A3_HIP(hipHostMalloc(&ctx->pinned_counts, (size_t)n * 8, hipHostMallocDefault));
-        ctx->pinned_counts_cap = (size_t)n * 8;
-    }
-    return A3_OK;
+    return ensure_back_buffers(ctx, b, z.head_bytes);
 }
 
-// the whole pipeline for one batch; `pixels` is a device pointer here
-// One batch = enqueue_batch (every launch and the read-back copies, then an event) + finish_batch (wait for the event, check
-// the device's verdict, hand out the markers).  a3_detect_batch runs them back to back; a3_detect_batch_submit / _collect
-// let the caller enqueue the next batch (on another context) before collecting this one, so the GPU never waits for the host.
-// phase 0: the whole batch; 1: the front half only (buffers + threshold kernel + an event behind it); 2: everything after the
-// threshold kernel of a batch whose front half phase 1 enqueued (same arguments).  `defer_locked`: the caller holds g_defer_mu
-// (a held chain released by another context's submit, by a gate, by collect): nothing in here may take that lock again, so such a
-// batch neither releases other contexts' deferred decode stages nor defers its own -- and, planned on the device with every buffer
-// allocated by its phase 1 (ensure_chain_buffers), it neither allocates nor waits for the device.
-int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint32_t H, size_t row_stride, size_t frame_stride, uint32_t n,
-                  size_t out_cap, int phase, bool defer_locked) {
-    hipStream_t st = ctx->stream;
-    const int rel_mode = defer_locked ? 0 : release_mode();
-    const size_t npx = (size_t)W * H;
-    const uint32_t minwh = W < H ? W : H;
-    const uint32_t min_edge_length = (uint32_t)((float)minwh * ctx->cfg.min_side_length_factor);   // src/aruco.rs:55
-    const float min_corner_separation = (float)minwh * ctx->cfg.min_corner_separation_factor;       // src/aruco.rs:56
-    const uint32_t S = ctx->cfg.homography_sample_size;
-    const uint32_t kMaxCand = ctx->max_cand;
+// One batch = enqueue_front (buffers, threshold kernel) + enqueue_chain (plan, contour stage, then the second half -- candidates ->
+// markers -> read-back, ending in an event -- or its deferral) + finish_batch (wait for the event, check the device's verdict, hand
+// out the markers).  a3_detect_batch runs them back to back (enqueue_batch); a3_detect_batch_submit / _collect let the caller
+// enqueue the next batch (on another context) before collecting this one, so the GPU never waits for the host; a burst
+// (submit_common) enqueues a member's chain later than its front half.  `b.pixels` is a device pointer here.
 
+// `held`: the chain is held back (submit_common holds device-planned batches only): an event goes behind the threshold kernel, which
+// the burst's last member's own threshold kernel replaces for the chains it releases, and the chain's buffers are allocated now.
+int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
+    hipStream_t st = ctx->stream;
+    const uint32_t n = b.n, W = b.W, H = b.H;
+    const size_t npx = (size_t)W * H;
+    const uint32_t kMaxCand = ctx->max_cand;
     // the grey plane is materialised only for readers outside the fused path: Detection.grey (debug taps) and the generic
     // threshold kernels (windows above 15); the decode stage otherwise samples the caller's frames directly
-    const bool big_window = threshold_writes_grey_plane(ctx->cfg.threshold_window, pixels, row_stride, frame_stride, (int)W);
-    const bool need_grey = ctx->debug_taps || big_window;
-    if (need_grey) A3_HIP(ctx->grey.ensure(npx * n));
-    ctx->grey_valid = need_grey;
+    const bool big_window = threshold_writes_grey_plane(ctx->cfg.threshold_window, b.pixels, b.row_stride, b.frame_stride, (int)W);
+    b.need_grey = b.taps || big_window;
+    if (b.need_grey) A3_HIP(ctx->grey.ensure(npx * n));
+    ctx->grey_valid = b.need_grey;
     if (big_window) A3_HIP(ctx->hsum.ensure(npx * n * 2));
     const size_t bits_per_frame = (size_t)words_per_row(W) * 8 * H;   // packed thresholded image
     A3_HIP(ctx->bin.ensure(bits_per_frame * n));
@@ -705,40 +656,40 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
     if (kMaxCand > frame_cand_lds_slots()) A3_HIP(ctx->cand_big.ensure((size_t)n * kMaxCand * 4));   // keys / perimeters of k_frame_candidates' through-memory form
     A3_HIP(ctx->outs.ensure((size_t)n * kMaxCand * decode_out_bytes()));
     A3_HIP(ctx->proj.ensure((size_t)n * kMaxCand * proj_rec_bytes()));
-    const uint32_t marker_cap = marker_cap_of(ctx, n, out_cap);
-    const uint32_t patch_cap = (uint32_t)std::min<uint64_t>(kPatchCapMax, std::max<uint64_t>(kPatchCapMin, (uint64_t)n * kMaxCand));
-    if (ctx->debug_taps) { A3_HIP(ctx->patches.ensure((size_t)patch_cap * S * S)); ctx->patch_cap = patch_cap; }
-    int prof = ctx->front_prof;
-    if (phase != 2) {
+    b.max_cand = kMaxCand;
+    b.marker_cap = marker_cap_of(ctx, n, b.out_cap);
+    b.guess = marker_guess_of(ctx, b.marker_cap);
+    b.patch_cap = (uint32_t)std::min<uint64_t>(kPatchCapMax, std::max<uint64_t>(kPatchCapMin, (uint64_t)n * kMaxCand));
+    if (b.taps) { A3_HIP(ctx->patches.ensure((size_t)b.patch_cap * ctx->cfg.homography_sample_size * ctx->cfg.homography_sample_size)); ctx->patch_cap = b.patch_cap; }
     ctx->W = W; ctx->H = H; ctx->frames = n;
     ctx->stats = a3_stats{};
     ctx->contours_valid = false; ctx->markers_valid = false; ctx->poses_valid = false;
 
     // ---- K1 ----
-    // (level in force for THIS batch: the sampled threshold-only mode times one batch in profile_every)
-    prof = ctx->profiling == 1 && (ctx->batch_seq++ % (uint32_t)ctx->profile_every) != 0 ? 0 : ctx->profiling;
-    ctx->front_prof = prof;
-    hipStream_t k1st = st;
-    if (g_part_k1_cus > 0 || g_k1_stream_prio > 0) {   // CU partition / priority probe: the threshold kernel runs on the device's K1 stream, between two events
-        A3_HIP(device_stream(ctx->device, kStreamK1, &k1st));
-        A3_HIP(hipEventRecord(ctx->ev_k1_ready, st));
-        A3_HIP(hipStreamWaitEvent(k1st, ctx->ev_k1_ready, 0));
-    }
-    if (prof) A3_HIP(hipEventRecord(ctx->ev[0], k1st));
-    A3_HIP(launch_grey_threshold(k1st, pixels, fmt, row_stride, frame_stride, (int)W, (int)H, n, ctx->cfg.threshold_window,
-                                 need_grey ? ctx->grey.as<uint8_t>() : nullptr, ctx->bin.as<uint64_t>(), big_window ? ctx->hsum.as<uint16_t>() : nullptr));
-    if (prof) A3_HIP(hipEventRecord(ctx->ev[1], k1st));
-    if (k1st != st) {
-        A3_HIP(hipEventRecord(ctx->ev_k1_done, k1st));
-        A3_HIP(hipStreamWaitEvent(st, ctx->ev_k1_done, 0));
-    } else if (g_mark_threshold || phase == 1) A3_HIP(hipEventRecord(ctx->ev_k1_done, st));   // (held chains of a burst wait for the last member's)
-    ctx->k1_marked = g_mark_threshold || phase == 1 || k1st != st;
-    if (phase == 1) {   // the chain is held back: what it will need is allocated now (submit_common holds device-planned batches only)
-        const uint64_t cap1 = device_plan_capacity(ctx, n, W, H);
-        if (cap1 == 0) return fail(ctx, A3_ERR_INTERNAL, "a chain was held back for a batch that needs a host-side plan");
-        return ensure_chain_buffers(ctx, st, n, W, H, cap1, out_cap);
-    }
-    }
+    b.prof = b.profiling == 1 && (ctx->batch_seq++ % (uint32_t)b.profile_every) != 0 ? 0 : b.profiling;
+    if (b.prof) A3_HIP(hipEventRecord(ctx->ev[0], st));
+    A3_HIP(launch_grey_threshold(st, b.pixels, b.fmt, b.row_stride, b.frame_stride, (int)W, (int)H, n, ctx->cfg.threshold_window,
+                                 b.need_grey ? ctx->grey.as<uint8_t>() : nullptr, ctx->bin.as<uint64_t>(), big_window ? ctx->hsum.as<uint16_t>() : nullptr));
+    if (b.prof) A3_HIP(hipEventRecord(ctx->ev[1], st));
+    if (!held) return A3_OK;
+    A3_HIP(hipEventRecord(ctx->ev_k1_done, st));   // (held chains of a burst wait for the last member's)
+    const uint64_t cap_d = device_plan_capacity(ctx, n, W, H);
+    if (cap_d == 0) return fail(ctx, A3_ERR_INTERNAL, "a chain was held back for a batch that needs a host-side plan");
+    return ensure_chain_buffers(ctx, st, b, cap_d);
+}
+
+// Everything after the threshold kernel.  `defer_locked`: the caller holds g_defer_mu (a held chain released by another context's
+// submit, by a gate, by collect): nothing in here may take that lock again, so such a batch neither releases other contexts'
+// deferred decode stages nor defers its own -- and, planned on the device with every buffer allocated by its front half
+// (ensure_chain_buffers), it neither allocates nor waits for the device.
+int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
+    hipStream_t st = ctx->stream;
+    const uint32_t n = b.n, W = b.W, H = b.H;
+    const int rel_mode = defer_locked ? 0 : release_mode();
+    const size_t npx = (size_t)W * H;
+    const uint32_t minwh = W < H ? W : H;
+    const uint32_t min_edge_length = (uint32_t)((float)minwh * ctx->cfg.min_side_length_factor);   // src/aruco.rs:55
+    const uint32_t kMaxCand = b.max_cand;
     // batches of OTHER contexts (same device) that wait with their decode stage are released from inside this batch's launch
     // sequence (see release_mode()): `release_waiting()` records the event they wait for and enqueues them
     bool released = false;
@@ -767,7 +718,7 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
     size_t ctr_bytes = 0, head_bytes = 0, head_off = 0;
     void* zero_p = nullptr; size_t zero_bytes = 0;
     auto layout_zero_block = [&](size_t n_chunks, uint32_t chunk_frames, bool launch) -> hipError_t {
-        const ZeroLayout zl = zero_layout(n_chunks, chunk_frames, n, marker_cap);
+        const ZeroLayout zl = zero_layout(n_chunks, chunk_frames, n, b.marker_cap);
         ctr_bytes = zl.ctr_bytes; head_bytes = zl.head_bytes; head_off = zl.head_off;
         const hipError_t e = ctx->zero_blk.ensure(zl.total);
         if (e != hipSuccess) return e;
@@ -783,27 +734,24 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
     };
     std::vector<Chunk> chunks;
     std::vector<uint64_t> fd;
-    A3_HIP(ctx->tile_darts.ensure(tile_darts_bytes(W, H, n)));
     if (device_plan) {
+        if (int rc = ensure_chain_buffers(ctx, st, b, cap_d)) return rc;
         chunks.push_back(Chunk{0, n, cap_d, (uint32_t)std::min<uint64_t>(cap_d, 0xFFFFFFFFu)});
         // The plan workgroup (last of k_tile_scan's launch) zeroes the block before it writes the plan into it: nothing earlier
-        // touches it, and a launch of its own costs 4 us for a few KB.  The per-frame dart totals k_dart_count adds up live in a
-        // buffer of their own that the plan workgroup hands back zeroed.
+        // touches it, and a launch of its own costs 4 us for a few KB.
         A3_HIP(layout_zero_block(1, n, false));
-        if (ctx->frame_darts_dev.cap < (size_t)n * 8) {
-            A3_HIP(ctx->frame_darts_dev.ensure((size_t)n * 8));
-            A3_HIP(hipMemsetAsync(ctx->frame_darts_dev.p, 0, ctx->frame_darts_dev.cap, st));
-        }
         ctx->frame_darts_ptr = ctx->frame_darts_dev.as<unsigned long long>();
     } else {
+        A3_HIP(ctx->tile_darts.ensure(tile_darts_bytes(W, H, n)));
         ctx->frame_darts_ptr = ctx->frame_darts.as<unsigned long long>();
         A3_HIP(hipMemsetAsync(ctx->frame_darts.p, 0, (size_t)n * 8, st));
     }
     // device plan: frame bases and the dart total come out of the same launch sequence (scratch words 8..11, read back with the results)
-    if (device_plan) A3_HIP(ctx->frame_base.ensure((size_t)(n + 1) * 4));
     A3_HIP(launch_dart_count(st, ctx->bin.as<uint64_t>(), (int)W, (int)H, 0, n, ctx->frame_darts_ptr, ctx->tile_darts.as<uint32_t>(), cap_d,
                              device_plan ? ctx->frame_base.as<uint32_t>() : nullptr, device_plan ? ctx->scratch_u32 + 8 : nullptr,
                              device_plan ? zero_p : nullptr, device_plan ? zero_bytes : 0));
+    const uint32_t* n_live = device_plan ? ctx->scratch_u32 + 8 : nullptr;   // written by the plan workgroup of launch_dart_count
+    uint32_t max_chunk_frames = n;
     if (!device_plan) {
         if (int rc = ensure_pinned(ctx, std::max<size_t>((size_t)n * 8, 1 << 16))) return rc;
         A3_HIP(hipMemcpyAsync(ctx->pinned, ctx->frame_darts.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
@@ -819,27 +767,15 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
             c.count++; c.darts += fd[f]; c.max_frame_darts = (uint32_t)std::max<uint64_t>(c.max_frame_darts, fd[f]);
         }
         if (c.count) chunks.push_back(c);
-    }
-    uint32_t max_chunk_frames = 0; uint64_t max_chunk_darts = 0;
-    for (auto& c : chunks) { max_chunk_frames = std::max(max_chunk_frames, c.count); max_chunk_darts = std::max(max_chunk_darts, c.darts); }
-    ctx->stats.chunks = (uint32_t)chunks.size();
-    if (int rc = ensure_dart_pool(ctx, pool_darts_of(ctx, max_chunk_darts, chunks.size()))) return rc;
-    A3_HIP(ctx->pix_base.ensure((size_t)max_chunk_frames * npx * 4));
-    A3_HIP(ctx->frame_base.ensure((size_t)(max_chunk_frames + 1) * 4 * chunks.size()));
-    if (!device_plan) A3_HIP(layout_zero_block(chunks.size(), max_chunk_frames, true));
-    A3_HIP(ctx->contours.ensure((size_t)ctx->max_contours * sizeof(ContourRec)));
-    A3_HIP(ctx->cyc_start_off.ensure((size_t)ctx->max_contours * 4));
-    A3_HIP(ctx->points.ensure(ctx->max_points * 4));
-
-    unsigned int* d_err = ctx->scratch_u32 + 4;             // ([0] work count, [1] marker total: enqueue_back)
-    unsigned int* d_entry_count = ctx->scratch_u32 + 32;    // [32..47]
-    unsigned int* d_leader_count = ctx->scratch_u32 + 16;   // [16..31]
-    unsigned int* d_dead_count = ctx->scratch_u32 + 48;     // [48..63]: borders k_local_contract finished with (traced, never listed), 16 shards, all chunks
-
-    const uint32_t* n_live = nullptr;
-    if (device_plan) {
-        n_live = ctx->scratch_u32 + 8;   // written by the plan workgroup of launch_dart_count
-    } else {
+        max_chunk_frames = 0; uint64_t max_chunk_darts = 0;
+        for (auto& c : chunks) { max_chunk_frames = std::max(max_chunk_frames, c.count); max_chunk_darts = std::max(max_chunk_darts, c.darts); }
+        if (int rc = ensure_dart_pool(ctx, pool_darts_of(ctx, max_chunk_darts, chunks.size()))) return rc;
+        A3_HIP(ctx->pix_base.ensure((size_t)max_chunk_frames * npx * 4));
+        A3_HIP(ctx->frame_base.ensure((size_t)(max_chunk_frames + 1) * 4 * chunks.size()));
+        A3_HIP(layout_zero_block(chunks.size(), max_chunk_frames, true));
+        A3_HIP(ctx->contours.ensure((size_t)ctx->max_contours * sizeof(ContourRec)));
+        A3_HIP(ctx->cyc_start_off.ensure((size_t)ctx->max_contours * 4));
+        A3_HIP(ctx->points.ensure(ctx->max_points * 4));
         // frame bases of every chunk, uploaded once
         std::vector<uint32_t> bases;
         for (auto& c : chunks) {
@@ -855,10 +791,20 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
         memcpy(h_bases, bases.data(), bases.size() * 4);
         A3_HIP(hipMemcpyAsync(ctx->frame_base.p, h_bases, bases.size() * 4, hipMemcpyHostToDevice, st));
     }
+    ctx->stats.chunks = (uint32_t)chunks.size();
+
+    unsigned int* d_err = ctx->scratch_u32 + 4;             // ([0] work count, [1] marker total: enqueue_back)
+    unsigned int* d_entry_count = ctx->scratch_u32 + 32;    // [32..47]
+    unsigned int* d_leader_count = ctx->scratch_u32 + 16;   // [16..31]
+    unsigned int* d_dead_count = ctx->scratch_u32 + 48;     // [48..63]: borders k_local_contract finished with (traced, never listed), 16 shards, all chunks
 
     // ---- contour stage, chunk by chunk ----
     const uint64_t* d_bin = ctx->bin.as<uint64_t>();
     const double image_diag = std::sqrt((double)W * W + (double)H * H);
+    const double eps_factor = ctx->cfg.contour_simplification_epsilon;
+    const int resolve_iters = ctx->resolve_full_ttl > 0 ? ctx->resolve_iters_hint : 0;
+    const int inline_resolve_W = ctx->resolve_full_ttl > 0 ? 0 : (int)W;
+    const int keep_all = b.taps ? 1 : 0;
     int rounds_max = 0;
     for (size_t ci = 0; ci < chunks.size(); ci++) {
         const Chunk& c = chunks[ci];
@@ -882,118 +828,88 @@ int enqueue_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint3
         if (const int cap = g_jump_rounds_cap.load(std::memory_order_relaxed); cap > 0 && ctx->jump_rounds_hint < 32) rounds = std::min(rounds, cap);
         rounds_max = std::max(rounds_max, rounds);
         uint32_t* const frame_entries = ctx->entry_global_ttl > 0 ? nullptr : ctx->frame_cursor;   // per-frame entry counts
-        const double eps_factor = ctx->cfg.contour_simplification_epsilon;
-        const uint32_t max_contours = ctx->max_contours;
-        const uint64_t max_points = ctx->max_points;
-        const int resolve_iters = ctx->resolve_full_ttl > 0 ? ctx->resolve_iters_hint : 0;
-        const int inline_resolve_W = ctx->resolve_full_ttl > 0 ? 0 : (int)W;
-        const int keep_all = ctx->debug_taps ? 1 : 0;
         // Short borders are finished with inside k_local_contract (kDead) on DENSE graphs only -- noise-like frames, where nine borders
         // in ten die of their length: there it saves a sixth of the contour stage; on clean frames (a dart per hundred pixels, a few
         // dozen borders per frame) it would only cost its bookkeeping.  Results are the same either way.
         const bool dense_graph = (uint64_t)nd * 10u >= (uint64_t)c.count * npx;
         unsigned int* const dead_ctr = (keep_all || !dense_graph) ? nullptr : d_dead_count;
-        const Chunk cc = c;
         // first half: the doubling rounds inside LDS tiles
         A3_HIP(launch_rank_cycles(st, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(),
                                   ctx->entry_list.as<uint32_t>(), d_entry_count, ctx->es_a.p, ctx->es_b.p,
                                   ctx->fin.p, ctx->leader_list.as<uint32_t>(), d_leader_count, rounds, ctr, n_live, 0, fb,
-                                  frame_entries, cc.count, 1, min_edge_length, dead_ctr, inline_resolve_W > 0 ? 1 : 0));
+                                  frame_entries, c.count, 1, min_edge_length, dead_ctr, inline_resolve_W > 0 ? 1 : 0));
         if (rel_mode == 2) { if (int rc = release_waiting()) return rc; }   // waiting decode stages go out behind this k_local_contract
         ctx->dbg_nd = nd; ctx->dbg_frames = c.count; ctx->dbg_chunks = (uint32_t)chunks.size();
-        // second half: entry resolution, final states (+ border selection), point scatter, quads -- on `s2`
-        auto chunk_back = [=](hipStream_t s2) -> int {
-            A3_HIP(launch_rank_cycles(s2, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(),
-                                      ctx->entry_list.as<uint32_t>(), d_entry_count, ctx->es_a.p, ctx->es_b.p,
-                                      ctx->fin.p /* the 8-byte states */, ctx->leader_list.as<uint32_t>(), d_leader_count, rounds, ctr,
-                                      n_live, 0, fb, frame_entries, cc.count, 2, min_edge_length, dead_ctr, inline_resolve_W > 0 ? 1 : 0));
-            const void* fin = ctx->fin.p;
-            A3_HIP(launch_resolve(s2, fin, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->leader_list.as<uint32_t>(), d_leader_count,
-                                  ctx->t_cur.as<uint64_t>(), ctx->t_next.as<uint64_t>(), ctr, resolve_iters, n_live));
-            A3_HIP(launch_select_scatter(s2, fin, nd, ctx->leader_list.as<uint32_t>(), d_leader_count, ctx->d_succ.as<uint32_t>(), ctx->t_cur.as<uint64_t>(), fb,
-                                         cc.count, cc.first, min_edge_length, eps_factor, image_diag,
-                                         ctx->contours.as<ContourRec>(), ctx->cyc_start_off.as<uint32_t>(), max_contours, max_points, ctr,
-                                         ctx->d_xy.as<uint64_t>(), ctx->points.as<uint32_t>(), n_live, inline_resolve_W, ctx->leader_keep.as<uint32_t>(),
-                                         keep_all, finalize_inline(frame_entries != nullptr, inline_resolve_W > 0) ? ctx->es_a.p : nullptr));
-            A3_HIP(launch_contour_quads(s2, ctx->contours.as<ContourRec>(), ctr, max_contours, ctx->points.as<uint32_t>(),
-                                        eps_factor, min_edge_length, cc.first, kMaxCand,
-                                        ctx->cands.as<CandRec>() + (size_t)cc.first * kMaxCand, ctx->cand_count + cc.first, d_err,
-                                        W <= 16384u && H <= 16384u ? 1 : 0, nd));
-            return A3_OK;
-        };
-        if (int rc = chunk_back(st)) return rc;
+        // second half: entry resolution, final states (+ border selection), point scatter, quads
+        A3_HIP(launch_rank_cycles(st, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(),
+                                  ctx->entry_list.as<uint32_t>(), d_entry_count, ctx->es_a.p, ctx->es_b.p,
+                                  ctx->fin.p /* the 8-byte states */, ctx->leader_list.as<uint32_t>(), d_leader_count, rounds, ctr,
+                                  n_live, 0, fb, frame_entries, c.count, 2, min_edge_length, dead_ctr, inline_resolve_W > 0 ? 1 : 0));
+        const void* fin = ctx->fin.p;
+        A3_HIP(launch_resolve(st, fin, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->leader_list.as<uint32_t>(), d_leader_count,
+                              ctx->t_cur.as<uint64_t>(), ctx->t_next.as<uint64_t>(), ctr, resolve_iters, n_live));
+        A3_HIP(launch_select_scatter(st, fin, nd, ctx->leader_list.as<uint32_t>(), d_leader_count, ctx->d_succ.as<uint32_t>(), ctx->t_cur.as<uint64_t>(), fb,
+                                     c.count, c.first, min_edge_length, eps_factor, image_diag,
+                                     ctx->contours.as<ContourRec>(), ctx->cyc_start_off.as<uint32_t>(), ctx->max_contours, ctx->max_points, ctr,
+                                     ctx->d_xy.as<uint64_t>(), ctx->points.as<uint32_t>(), n_live, inline_resolve_W, ctx->leader_keep.as<uint32_t>(),
+                                     keep_all, finalize_inline(frame_entries != nullptr, inline_resolve_W > 0) ? ctx->es_a.p : nullptr));
+        A3_HIP(launch_contour_quads(st, ctx->contours.as<ContourRec>(), ctr, ctx->max_contours, ctx->points.as<uint32_t>(),
+                                    eps_factor, min_edge_length, c.first, kMaxCand,
+                                    ctx->cands.as<CandRec>() + (size_t)c.first * kMaxCand, ctx->cand_count + c.first, d_err,
+                                    W <= 16384u && H <= 16384u ? 1 : 0, nd));
     }
     if (rel_mode != 0) { if (int rc = release_waiting()) return rc; }   // (a batch without a contour graph releases here)
-    if (prof >= 2) A3_HIP(hipEventRecord(ctx->ev[2], st));
+    if (b.prof >= 2) A3_HIP(hipEventRecord(ctx->ev[2], st));
 
     // ---- candidates -> markers -> read-back: enqueued now, or deferred behind the next submitted batch's threshold kernel ----
-    const PixelSrc src = need_grey ? PixelSrc{ctx->grey.as<uint8_t>(), W, (unsigned long long)npx, kFmtGreyPlane}
-                                   : PixelSrc{pixels, row_stride, frame_stride, fmt};
-    ctx->dbg_src = src;
-    const size_t pose_bytes = ctx->want_pose ? 2 * sizeof(a3_pose) : 0;
-    const uint32_t guess = marker_guess_of(ctx, marker_cap);
-    const size_t head_pad = head_bytes;   // the markers follow the head directly, on the device and in the staging buffer
-    // every allocation of the second half happens here, at submit time: pose buffer, pinned staging for the head and `guess`
-    // markers (+ poses; a longer list is fetched by finish_batch after growing it), pinned staging for the tap counts
-    if (ctx->want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)marker_cap * 2 * sizeof(a3_pose)));
-    const size_t refine_bytes = ctx->pending.refine.method != A3_REFINE_NONE ? 8 * sizeof(float) : 0;   // (captured at submit)
-    if (refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)marker_cap * refine_bytes));
-    const bool board = ctx->pending.board;   // (captured at submit)
-    const size_t board_bytes = board ? (size_t)n * sizeof(a3_board_pose) : 0;
-    if (board_bytes) A3_HIP(ctx->board_buf.ensure(board_bytes));
-    if (int rc = ensure_pinned(ctx, head_pad + (size_t)guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + board_bytes + (1 << 16))) return rc;
+    b.src = b.need_grey ? PixelSrc{ctx->grey.as<uint8_t>(), W, (unsigned long long)npx, kFmtGreyPlane}
+                        : PixelSrc{b.pixels, b.row_stride, b.frame_stride, b.fmt};
+    ctx->dbg_src = b.src;
+    b.head_bytes = head_bytes;   // the markers follow the head directly, on the device and in the staging buffer
+    if (int rc = ensure_back_buffers(ctx, b, head_bytes)) return rc;   // (device plan: ensure_chain_buffers did, this is a no-op)
+    b.device_plan = device_plan; b.n_chunks = chunks.size(); b.chunk0_darts = chunks.empty() ? 0 : chunks[0].darts;
+    b.ctr_bytes = ctr_bytes; b.rounds_max = rounds_max;
     ctx->counts_valid = false;
-    if (ctx->debug_taps && ctx->pinned_counts_cap < (size_t)n * 8) {
-        if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
-        ctx->pinned_counts = nullptr; ctx->pinned_counts_cap = 0;
-        A3_HIP(hipHostMalloc(&ctx->pinned_counts, (size_t)n * 8, hipHostMallocDefault));
-        ctx->pinned_counts_cap = (size_t)n * 8;
-    }
-    BackArgs& bk = ctx->back;
-    bk.n = n; bk.W = W; bk.H = H; bk.S = S; bk.max_cand = kMaxCand; bk.patch_cap = patch_cap; bk.marker_cap = marker_cap; bk.guess = guess;
-    bk.min_corner_separation = min_corner_separation; bk.src = src; bk.head_bytes = head_bytes; bk.pose_bytes = pose_bytes;
-    bk.taps = ctx->debug_taps; bk.want_pose = ctx->want_pose; bk.pose_has_intr = ctx->pose_has_intr; bk.pose_size_mm = ctx->pose_size_mm;
-    bk.pose_intr = ctx->pose_intr; bk.profiling = prof;
-    bk.refine = ctx->pending.refine; bk.refine_bytes = refine_bytes; bk.board = board;
     // Deferral: only for submitted batches (somebody will submit again or collect), and not while every stage is being timed
     // (the stage times are those of stages that run alone).  The decode stage then waits on the context's decode stream until
     // (a) another context submits a batch -- it is released behind that batch's threshold kernel and shares the GPU with its
     // contour stage -- or (b) this batch is collected first.
-    if (phase == 0) ctx->stepping = A3_STEP_WHOLE;
-    if (ctx->allow_defer && !defer_locked && ctx->profiling < 2 && ctx->batch_mode != 0) {
+    if (ctx->allow_defer && !defer_locked && b.profiling < 2 && ctx->batch_mode != 0) {
         A3_HIP(hipEventRecord(ctx->ev_contours, st));
         std::lock_guard<std::mutex> lk(g_defer_mu);
         ctx->back_deferred = true;
         ctx->back_rc = 0;
         ctx->stepping = A3_STEP_DECODE_DEFERRED;
         g_deferred.push_back(ctx);
-    } else if (int rc = enqueue_back(ctx, st, bk)) return rc;
-    Pending& pd = ctx->pending;
-    pd.active = true; pd.n_chunks = chunks.size(); pd.chunk0_darts = chunks.empty() ? 0 : chunks[0].darts; pd.ctr_bytes = ctr_bytes;
-    pd.head_pad = head_pad; pd.marker_cap = marker_cap; pd.guess = guess; pd.pose_bytes = pose_bytes; pd.device_plan = device_plan;
-    pd.rounds_max = rounds_max; pd.n = n; pd.W = W; pd.H = H; pd.profiling = prof; pd.taps = ctx->debug_taps; pd.refine_bytes = refine_bytes;
+    } else if (int rc = enqueue_back(ctx, st, b)) return rc;
+    b.active = true;
     return A3_OK;
 }
 
-int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
-    Pending& pd = ctx->pending;
-    if (!pd.active) return fail(ctx, A3_ERR_INVALID, "no batch was submitted");
+// the whole batch at once (a3_detect_batch, a re-run, a submit that is neither held nor a burst's split last member)
+int enqueue_batch(a3_ctx* ctx) {
+    ctx->stepping = A3_STEP_WHOLE;
+    if (int rc = enqueue_front(ctx, ctx->batch, false)) return rc;
+    return enqueue_chain(ctx, ctx->batch, false);
+}
+
+// `poses`: where a pose batch's poses go (null: not wanted); `out_cap`: the capacity of the caller's `out` (and `poses`)
+int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
+    Batch& b = ctx->batch;
+    if (!b.active) return fail(ctx, A3_ERR_INVALID, "no batch was submitted");
     {   // a chain still held back (no later member of its burst was submitted): it goes out now
         std::lock_guard<std::mutex> lk(g_defer_mu);
         (void)flush_held_locked(ctx, nullptr);
-        if (const int rc = ctx->held_rc) { ctx->held_rc = 0; pd.active = false; return rc; }
+        if (const int rc = ctx->held_rc) { ctx->held_rc = 0; b.active = false; return rc; }
     }
-    pd.active = false;
+    b.active = false;
     hipStream_t st = ctx->stream;
-    const size_t ctr_bytes = pd.ctr_bytes, head_pad = pd.head_pad, pose_bytes = pd.pose_bytes, n_chunks = pd.n_chunks, refine_bytes = pd.refine_bytes;
-    const uint32_t marker_cap = pd.marker_cap, guess = pd.guess, n = pd.n, W = pd.W, H = pd.H;
-    const bool device_plan = pd.device_plan;
-    const int rounds_max = pd.rounds_max;
+    const size_t ctr_bytes = b.ctr_bytes, head_bytes = b.head_bytes, pose_bytes = b.pose_bytes, n_chunks = b.n_chunks, refine_bytes = b.refine_bytes;
+    const uint32_t guess = b.guess, n = b.n;
     uint8_t* hp = (uint8_t*)ctx->pinned;
-    a3_marker* h_markers = reinterpret_cast<a3_marker*>(hp + head_pad);
-    a3_pose* h_poses = reinterpret_cast<a3_pose*>(hp + head_pad + (size_t)guess * sizeof(a3_marker));
-    const float* h_refined = reinterpret_cast<const float*>(hp + head_pad + (size_t)guess * (sizeof(a3_marker) + pose_bytes));
-    (void)marker_cap;
+    a3_marker* h_markers = reinterpret_cast<a3_marker*>(hp + head_bytes);
+    a3_pose* h_poses = reinterpret_cast<a3_pose*>(hp + head_bytes + (size_t)guess * sizeof(a3_marker));
+    const float* h_refined = reinterpret_cast<const float*>(hp + head_bytes + (size_t)guess * (sizeof(a3_marker) + pose_bytes));
     {   // nobody submitted behind this batch: its decode stage goes out now
         std::lock_guard<std::mutex> lk(g_defer_mu);
         if (int rc = flush_deferred_locked(ctx, nullptr)) return rc;
@@ -1002,15 +918,15 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
     A3_HIP(wait_event(ctx->ev[4], st));
     const unsigned int* hs = reinterpret_cast<const unsigned int*>(hp);
     const DeviceCounters* hc = reinterpret_cast<const DeviceCounters*>(hp + 256);
-    if (device_plan) {
+    if (b.device_plan) {
         if (hs[9]) { ctx->force_host_plan = true; return 1; }   // the graph outgrew the hint: plan on the host this once
         ctx->stats.darts = hs[8];
         ctx->dbg_nd = hs[8];
         ctx->plan_darts = hs[8];
     } else {
         ctx->plan_valid = n_chunks == 1;
-        ctx->plan_n = n; ctx->plan_W = W; ctx->plan_H = H;
-        ctx->plan_darts = n_chunks == 1 ? pd.chunk0_darts : 0;
+        ctx->plan_n = n; ctx->plan_W = b.W; ctx->plan_H = b.H;
+        ctx->plan_darts = n_chunks == 1 ? b.chunk0_darts : 0;
     }
     unsigned int flags = hs[4];
     for (int sh = 0; sh < 16; sh++) ctx->stats.contours_traced += hs[48 + sh];   // borders finished inside k_local_contract (kDead)
@@ -1031,7 +947,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
         uint32_t it = hc[ci].resolve_needed ? 1 : 0;  // 0: k_resolve_fast confirmed the natural starts; pass k+1 ran iff pass k moved something
         for (int r = 0; r < kResolveItersMax - 1; r++) if (hc[ci].resolve_changed[r]) it = r + 2;
         ctx->stats.resolve_iterations = std::max(ctx->stats.resolve_iterations, it);
-        if (rounds_max > 0 && rounds_max < 32 && hc[ci].jump_changed[rounds_max - 1] != 0) jump_short = true;
+        if (b.rounds_max > 0 && b.rounds_max < 32 && hc[ci].jump_changed[b.rounds_max - 1] != 0) jump_short = true;
     }
     if (entry_overflow) { ctx->entry_global_ttl = 64; ctx->jump_rounds_hint = std::max(ctx->jump_rounds_hint, 12); return 1; }     // a frame's entry list outgrew LDS: re-run with the global rounds
     if (ctx->entry_global_ttl > 0) ctx->entry_global_ttl--;
@@ -1080,8 +996,8 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
     uint32_t max_per_frame = 0;   // (read now: the staging buffer may be re-allocated below)
     for (uint32_t f = 0; f < n; f++) max_per_frame = std::max(max_per_frame, hpf[f]);
     const uint32_t n_work = hs[0], n_pre = hs[2];
-    if (pd.board) {   // (read now: the staging buffer may be re-allocated below)
-        const a3_board_pose* hb = reinterpret_cast<const a3_board_pose*>(hp + head_pad + (size_t)guess * (sizeof(a3_marker) + pose_bytes + refine_bytes));
+    if (b.board) {   // (read now: the staging buffer may be re-allocated below)
+        const a3_board_pose* hb = reinterpret_cast<const a3_board_pose*>(hp + head_bytes + (size_t)guess * (sizeof(a3_marker) + pose_bytes + refine_bytes));
         ctx->h_board.assign(hb, hb + n);
     }
     const uint32_t tap_contours = n_chunks ? hc[0].contours : 0u; const uint64_t tap_points = n_chunks ? hc[0].points : 0ull;
@@ -1097,12 +1013,12 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
     }
     if (total) {
         memcpy(out, h_markers, (size_t)total * sizeof(a3_marker));
-        if (pose_bytes && ctx->pose_out) memcpy(ctx->pose_out, h_poses, (size_t)total * pose_bytes);
+        if (pose_bytes && poses) memcpy(poses, h_poses, (size_t)total * pose_bytes);
     }
     if (refine_bytes) ctx->h_refined.assign(h_refined, h_refined + (size_t)total * 8);
     ctx->refined_valid = refine_bytes != 0;
-    ctx->board_valid = pd.board;
-    if (pd.taps) {
+    ctx->board_valid = b.board;
+    if (b.taps) {
         const uint32_t* hc32 = reinterpret_cast<const uint32_t*>(ctx->pinned_counts);
         ctx->h_cand_pre.assign(hc32, hc32 + n);
         ctx->h_cand_fin.assign(hc32 + n, hc32 + 2 * (size_t)n);
@@ -1116,12 +1032,12 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
     ctx->stats.candidates_pre = n_pre;   // quads after contours_to_candidates (k_compact_markers sums the per-frame counts)
     ctx->markers_valid = true; ctx->last_n = n; ctx->last_max_per_frame = max_per_frame;
     ctx->poses_valid = pose_bytes != 0;
-    ctx->contours_valid = ctx->debug_taps && n_chunks == 1;
+    ctx->contours_valid = b.taps && n_chunks == 1;
     if (ctx->contours_valid) { ctx->tap_contours = tap_contours; ctx->tap_points = tap_points; }
-    if (pd.profiling >= 1) {   // the level in force when the batch was enqueued
+    if (b.prof >= 1) {   // the level in force when the batch was enqueued
         float ms;
         A3_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); ctx->prof_ms[A3_STAGE_THRESHOLD] += ms; ctx->prof_n[A3_STAGE_THRESHOLD]++;
-        if (pd.profiling >= 2) {
+        if (b.prof >= 2) {
             A3_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2])); ctx->prof_ms[A3_STAGE_CONTOUR] += ms; ctx->prof_n[A3_STAGE_CONTOUR]++;
             A3_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3])); ctx->prof_ms[A3_STAGE_DECODE] += ms; ctx->prof_n[A3_STAGE_DECODE]++;
         }
@@ -1129,10 +1045,9 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_fram
     return A3_OK;
 }
 
-int run_batch(a3_ctx* ctx, const uint8_t* pixels, int fmt, uint32_t W, uint32_t H, size_t row_stride, size_t frame_stride, uint32_t n,
-              a3_marker* out, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
-    if (int rc = enqueue_batch(ctx, pixels, fmt, W, H, row_stride, frame_stride, n, out_cap, 0)) return rc;
-    return finish_batch(ctx, out, out_cap, per_frame_count, out_n);
+int run_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
+    if (int rc = enqueue_batch(ctx)) return rc;
+    return finish_batch(ctx, out, poses, out_cap, per_frame_count, out_n);
 }
 
 }  // namespace
@@ -1201,7 +1116,6 @@ int a3_create(int device, const a3_config* cfg, const uint64_t* codes, size_t n_
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_contours, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_k1, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_gate, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_k1_ready, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_k1_done, hipEventDisableTiming);
     if (e != hipSuccess) { a3_destroy(c); ctx = nullptr; return fail(ctx, A3_ERR_HIP, "hipEventCreate", e); }
     for (auto& ev : c->ev) {
@@ -1251,7 +1165,6 @@ void a3_destroy(a3_ctx* ctx) {
         { std::lock_guard<std::mutex> lk(g_streams_mu); ds = g_dev_streams[ctx->device & 63]; }
         if (ds.decode) (void)hipStreamSynchronize(ds.decode);
         if (ds.copy) (void)hipStreamSynchronize(ds.copy);
-        if (ds.k1) (void)hipStreamSynchronize(ds.k1);
     }
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     DevBuf* bufs[] = {&ctx->dict, &ctx->in, &ctx->grey, &ctx->bin, &ctx->frame_darts, &ctx->frame_darts_dev, &ctx->frame_base, &ctx->pix_base,
@@ -1269,7 +1182,6 @@ void a3_destroy(a3_ctx* ctx) {
     if (ctx->ev_contours) (void)hipEventDestroy(ctx->ev_contours);
     if (ctx->ev_k1) (void)hipEventDestroy(ctx->ev_k1);
     if (ctx->ev_gate) (void)hipEventDestroy(ctx->ev_gate);
-    if (ctx->ev_k1_ready) (void)hipEventDestroy(ctx->ev_k1_ready);
     if (ctx->ev_k1_done) (void)hipEventDestroy(ctx->ev_k1_done);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -1330,16 +1242,6 @@ int a3_order_after(a3_ctx* ctx, a3_ctx* other) {
     A3_HIP(hipEventRecord(other->ev_gate, other->stream));
     A3_HIP(hipStreamWaitEvent(ctx->stream, other->ev_gate, 0));
     ctx->gates_declared = true;
-    return A3_OK;
-}
-
-// internal (a3_internal.h, tools/spin_probe.py): work enqueued on `hip_stream` after this call starts only once the threshold kernel
-// of ctx's batch in flight has finished; needs a3_debug_set_mark_threshold(1) before the submit
-int a3_debug_stream_wait_threshold(a3_ctx* ctx, void* hip_stream) {
-    if (!ctx) return A3_ERR_INVALID;
-    if (!ctx->pending.active || !ctx->k1_marked) return A3_OK;   // nothing in flight (or a synchronous call): nothing to wait for
-    A3_HIP(hipSetDevice(ctx->device));
-    A3_HIP(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(hip_stream), ctx->ev_k1_done, 0));
     return A3_OK;
 }
 
@@ -1421,55 +1323,74 @@ static int upload_board(a3_ctx* ctx) {
     return A3_OK;
 }
 
-static int run_batch_with_retries(a3_ctx* ctx, const uint8_t* d_pixels, int fmt, uint32_t width, uint32_t height, size_t row_stride,
-                                  size_t frame_stride, uint32_t n_frames, a3_marker* out, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
+// Starts a batch: its record (a3_ctx::batch) takes the call and every setting in force now, the frames are staged on the device, and
+// the board's tables are brought up to date (no batch of this context is in flight).  -> A3_OK, an error, or kNothingToDo.
+static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
+                       size_t frame_stride, uint32_t n_frames, size_t out_cap, bool want_pose, float size_mm, const a3_intrinsics* intr) {
+    Batch& b = ctx->batch;
+    b = Batch{};
+    b.fmt = fmt; b.W = width; b.H = height; b.n = n_frames; b.out_cap = out_cap;
+    b.want_pose = want_pose; b.pose_size_mm = size_mm; b.pose_has_intr = intr != nullptr;
+    if (intr) b.pose_intr = *intr;
+    b.pose_bytes = want_pose ? 2 * sizeof(a3_pose) : 0;
+    b.refine = ctx->refine;
+    b.refine_bytes = b.refine.method != A3_REFINE_NONE ? 8 * sizeof(float) : 0;
+    b.board = want_pose && !ctx->board_ids.empty();
+    b.taps = ctx->debug_taps;
+    b.profiling = ctx->profiling; b.profile_every = ctx->profile_every;
+    ctx->board_valid = false;
+    b.row_stride = row_stride; b.frame_stride = frame_stride;
+    const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &b.row_stride, &b.frame_stride, n_frames, &b.pixels);
+    if (rc != A3_OK) return rc;
+    if (b.board) { if (int urc = upload_board(ctx)) return urc; }
+    ctx->force_host_plan = false;
+    ctx->reruns = 0; ctx->released_others = 0;
+    return A3_OK;
+}
+
+// what a batch without frames (or with empty images) returns: no markers
+static void finish_trivial(a3_ctx* ctx, uint32_t* per_frame_count) {
+    const Batch& b = ctx->batch;
+    if (per_frame_count && b.n) memset(per_frame_count, 0, (size_t)b.n * 4);
+    ctx->h_refined.clear(); ctx->refined_valid = b.refine_bytes != 0;
+    ctx->h_board.assign(b.n, a3_board_pose{}); ctx->board_valid = b.board;
+}
+
+static int run_batch_with_retries(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
     for (int attempt = 0; attempt < 8; attempt++) {
-        const int rc = run_batch(ctx, d_pixels, fmt, width, height, row_stride, frame_stride, n_frames, out, out_cap, per_frame_count, out_n);
+        const int rc = run_batch(ctx, out, poses, out_cap, per_frame_count, out_n);
         if (rc != 1) return rc;
         ctx->reruns++;
     }
     return fail(ctx, A3_ERR_CAPACITY, "contour pools kept overflowing");
 }
 
+static int detect_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
+                         size_t frame_stride, uint32_t n_frames, bool want_pose, float size_mm, const a3_intrinsics* intr, a3_marker* out,
+                         a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
+    if (!out_n || (!out && out_cap)) return fail(ctx, A3_ERR_INVALID, "a3_detect_batch: null output");
+    *out_n = 0;
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");
+    const int rc = begin_batch(ctx, pixels, memory, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, want_pose, size_mm, intr);
+    if (rc == kNothingToDo) { finish_trivial(ctx, per_frame_count); return A3_OK; }
+    if (rc != A3_OK) return rc;
+    return run_batch_with_retries(ctx, out, poses, out_cap, per_frame_count, out_n);
+}
+
 int a3_detect_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
                     size_t frame_stride, uint32_t n_frames, a3_marker* out, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
     if (!ctx) return A3_ERR_INVALID;
-    if (!out_n || (!out && out_cap)) return fail(ctx, A3_ERR_INVALID, "a3_detect_batch: null output");
-    *out_n = 0;
-    if (ctx->pending.active) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");
-    ctx->pending.refine = ctx->refine;
-    ctx->pending.board = ctx->want_pose && !ctx->board_ids.empty();
-    ctx->board_valid = false;
-    const uint8_t* d_pixels = nullptr;
-    const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, n_frames, &d_pixels);
-    if (rc == kNothingToDo) {
-        if (per_frame_count && n_frames) memset(per_frame_count, 0, (size_t)n_frames * 4);
-        ctx->h_refined.clear(); ctx->refined_valid = ctx->refine.method != A3_REFINE_NONE;
-        ctx->h_board.assign(n_frames, a3_board_pose{}); ctx->board_valid = ctx->pending.board;
-        return A3_OK;
-    }
-    if (rc != A3_OK) return rc;
-    if (ctx->pending.board) { if (int urc = upload_board(ctx)) return urc; }
-    ctx->force_host_plan = false;
-    ctx->reruns = 0; ctx->released_others = 0;
-    return run_batch_with_retries(ctx, d_pixels, fmt, width, height, row_stride, frame_stride, n_frames, out, out_cap, per_frame_count, out_n);
+    return detect_common(ctx, pixels, memory, fmt, width, height, row_stride, frame_stride, n_frames, false, 0.0f, nullptr, out, nullptr,
+                         out_cap, per_frame_count, out_n);
 }
 
 static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
-                         size_t frame_stride, uint32_t n_frames, size_t out_cap, bool want_pose) {
-    if (ctx->pending.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");
-    ctx->pending.refine = ctx->refine;   // (the batch keeps the setting in force at its submit)
-    ctx->pending.board = want_pose && !ctx->board_ids.empty();   // (and the board)
-    ctx->board_valid = false;
-    const uint8_t* d_pixels = nullptr;
-    const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, n_frames, &d_pixels);
-    if (rc == kNothingToDo) { ctx->pending_trivial = true; ctx->pending.n = n_frames; return A3_OK; }
+                         size_t frame_stride, uint32_t n_frames, size_t out_cap, bool want_pose, float size_mm, const a3_intrinsics* intr) {
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");
+    const int rc = begin_batch(ctx, pixels, memory, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, want_pose, size_mm, intr);
+    if (rc == kNothingToDo) { ctx->pending_trivial = true; return A3_OK; }
     if (rc != A3_OK) return rc;
-    if (ctx->pending.board) { if (int urc = upload_board(ctx)) return urc; }
-    ctx->force_host_plan = false;
-    ctx->want_pose = want_pose;
-    Pending& pd = ctx->pending;
-    pd.pixels = d_pixels; pd.fmt = fmt; pd.row_stride = row_stride; pd.frame_stride = frame_stride; pd.want_pose = want_pose;
+    Batch& b = ctx->batch;
     // Bursts: a context that declared gates (a3_order_after) since its last submit holds its chain back behind its threshold
     // kernel; a submit without gates is the last member of its burst and releases every held chain of the device behind ITS
     // threshold kernel.  This is the library's behaviour behind the public header -- no switch selects it.  Exceptions, all of
@@ -1483,15 +1404,12 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
     const bool gated = ctx->gates_declared;
     ctx->gates_declared = false;
     ctx->batch_mode = batch_mode_of(ctx);
-    ctx->released_others = 0; ctx->reruns = 0;
-    const bool bursts = ctx->batch_mode == 0 && g_overlap_force.load(std::memory_order_relaxed) <= 0 && g_hold_rests && ctx->profiling < 2;
+    const bool bursts = ctx->batch_mode == 0 && g_overlap_force.load(std::memory_order_relaxed) <= 0 && g_hold_rests && b.profiling < 2;
     if (bursts && gated && device_plan_capacity(ctx, n_frames, width, height) != 0) {
-        pd.n = n_frames; pd.W = width; pd.H = height;
-        ctx->held_out_cap = out_cap;
-        if (int erc = enqueue_batch(ctx, d_pixels, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, 1)) return erc;
+        if (int erc = enqueue_front(ctx, b, true)) return erc;
         (void)hipStreamQuery(ctx->stream);
         std::lock_guard<std::mutex> lk(g_defer_mu);
-        pd.active = true;
+        b.active = true;
         ctx->rest_held = true; ctx->held_rc = 0;
         ctx->stepping = A3_STEP_HELD;   // (until the chain goes out: flush_held_locked says how)
         g_held.push_back(ctx);
@@ -1503,10 +1421,10 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
         for (a3_ctx* o : g_held) any_held |= (o != ctx && o->device == ctx->device);
     }
     if (any_held) {   // the last member: threshold kernel, then the held chains of the others behind it, then this batch's own
-        // A last member that needs a host-side plan cannot be split (phase 1 refuses it): the others are then released ungated,
-        // ahead of its whole batch.
+        // A last member that needs a host-side plan cannot be split (enqueue_front refuses to hold it): the others are then released
+        // ungated, ahead of its whole batch.
         const bool planned = device_plan_capacity(ctx, n_frames, width, height) != 0;
-        if (planned) { if (int erc = enqueue_batch(ctx, d_pixels, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, 1)) return erc; }
+        if (planned) { if (int erc = enqueue_front(ctx, b, true)) return erc; }
         uint32_t released = 0;
         {
             std::lock_guard<std::mutex> lk(g_defer_mu);
@@ -1514,12 +1432,12 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
             for (a3_ctx* o : list)
                 if (o != ctx && o->device == ctx->device) { (void)flush_held_locked(o, planned ? ctx->ev_k1_done : nullptr, true); released++; }   // (a failure is o's: its collect reports it)
         }
-        const int erc = enqueue_batch(ctx, d_pixels, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, planned ? 2 : 0);
+        const int erc = planned ? enqueue_chain(ctx, b, false) : enqueue_batch(ctx);
         ctx->stepping = A3_STEP_BURST_LAST; ctx->released_others = released;
         return erc;
     }
     ctx->allow_defer = true;    // (a synchronous call, or a re-run, enqueues both halves at once)
-    const int erc = enqueue_batch(ctx, d_pixels, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, 0);
+    const int erc = enqueue_batch(ctx);
     ctx->allow_defer = false;
     return erc;
 }
@@ -1528,30 +1446,23 @@ static int collect_common(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t ou
     *out_n = 0;
     if (ctx->pending_trivial) {
         ctx->pending_trivial = false;
-        if (per_frame_count && ctx->pending.n) memset(per_frame_count, 0, (size_t)ctx->pending.n * 4);
-        ctx->h_refined.clear(); ctx->refined_valid = ctx->pending.refine.method != A3_REFINE_NONE;
-        ctx->h_board.assign(ctx->pending.n, a3_board_pose{}); ctx->board_valid = ctx->pending.board;
+        finish_trivial(ctx, per_frame_count);
         return A3_OK;
     }
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
-    const Pending pd = ctx->pending;   // finish_batch clears .active
-    ctx->want_pose = pd.want_pose;     // (the other half of the pair may have been a different kind of call on this context)
-    ctx->pose_out = pd.want_pose ? poses : nullptr;
-    int rc = finish_batch(ctx, out, out_cap, per_frame_count, out_n);
+    int rc = finish_batch(ctx, out, poses, out_cap, per_frame_count, out_n);
     const uint32_t stepping = ctx->stepping;   // how the SUBMITTED batch was stepped (a re-run below is a synchronous call of its own)
-    // the device asked for a re-run (pool growth, more passes, host-side plan): do it synchronously
-    if (rc == 1) { ctx->reruns++; rc = run_batch_with_retries(ctx, pd.pixels, pd.fmt, pd.W, pd.H, pd.row_stride, pd.frame_stride, pd.n, out, out_cap, per_frame_count, out_n); }
+    // the device asked for a re-run (pool growth, more passes, host-side plan): do it synchronously, into the collect's buffers
+    if (rc == 1) { ctx->reruns++; ctx->batch.out_cap = out_cap; rc = run_batch_with_retries(ctx, out, poses, out_cap, per_frame_count, out_n); }
     ctx->stepping = stepping;
-    ctx->want_pose = false;
-    ctx->pose_out = nullptr;
     return rc;
 }
 
 int a3_detect_batch_submit(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
                            size_t frame_stride, uint32_t n_frames, size_t out_cap) {
     if (!ctx) return A3_ERR_INVALID;
-    return submit_common(ctx, pixels, memory, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, false);
+    return submit_common(ctx, pixels, memory, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, false, 0.0f, nullptr);
 }
 
 int a3_detect_batch_collect(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
@@ -1564,19 +1475,13 @@ int a3_detect_batch_collect(a3_ctx* ctx, a3_marker* out, size_t out_cap, uint32_
 int a3_detect_batch_pose_submit(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
                                 size_t frame_stride, uint32_t n_frames, float marker_size_mm, const a3_intrinsics* intr, size_t out_cap) {
     if (!ctx) return A3_ERR_INVALID;
-    if (ctx->pending.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");
-    ctx->pose_size_mm = marker_size_mm;
-    ctx->pose_has_intr = intr != nullptr;
-    if (intr) ctx->pose_intr = *intr;
-    const int rc = submit_common(ctx, pixels, memory, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, true);
-    ctx->want_pose = false;   // (enqueue_batch has read it; a plain call in between must not inherit it)
-    return rc;
+    return submit_common(ctx, pixels, memory, fmt, width, height, row_stride, frame_stride, n_frames, out_cap, true, marker_size_mm, intr);
 }
 
 int a3_detect_batch_pose_collect(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
     if (!ctx) return A3_ERR_INVALID;
     if (!out_n || (!out && out_cap) || (!poses && out_cap)) return fail(ctx, A3_ERR_INVALID, "a3_detect_batch_pose_collect: null output");
-    if (!ctx->pending_trivial && ctx->pending.active && !ctx->pending.want_pose)
+    if (!ctx->pending_trivial && ctx->batch.active && !ctx->batch.want_pose)
         return fail(ctx, A3_ERR_INVALID, "a3_detect_batch_pose_collect: the submitted batch was not an a3_detect_batch_pose_submit call");
     return collect_common(ctx, out, poses, out_cap, per_frame_count, out_n);
 }
@@ -1585,15 +1490,8 @@ int a3_detect_batch_pose(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
                          size_t frame_stride, uint32_t n_frames, float marker_size_mm, const a3_intrinsics* intr, a3_marker* out,
                          a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
     if (!ctx || !poses) return A3_ERR_INVALID;
-    ctx->want_pose = true;
-    ctx->pose_size_mm = marker_size_mm;
-    ctx->pose_has_intr = intr != nullptr;
-    if (intr) ctx->pose_intr = *intr;
-    ctx->pose_out = poses;
-    const int rc = a3_detect_batch(ctx, pixels, memory, fmt, width, height, row_stride, frame_stride, n_frames, out, out_cap, per_frame_count, out_n);
-    ctx->want_pose = false;
-    ctx->pose_out = nullptr;
-    return rc;
+    return detect_common(ctx, pixels, memory, fmt, width, height, row_stride, frame_stride, n_frames, true, marker_size_mm, intr, out, poses,
+                         out_cap, per_frame_count, out_n);
 }
 
 // Re-runs one contour kernel on the buffers of the last batch (single-chunk batches only) and returns its average device
@@ -1658,12 +1556,11 @@ int a3_debug_kernel_time(a3_ctx* ctx, int kernel, int dbg, int reps, float* avg_
 
 // internal (a3_internal.h): where a submitted batch's decode stage is released (0 not deferred, 1 behind the next batch's
 // threshold kernel, 2 behind its k_local_contract); process-wide, for A/B measurements
-int a3_debug_set_overlap(int mode) {   // -1: the library decides per batch (default); bits 0-7: forced mode; bit 8: a decode stream created from now on gets the LOWEST priority
-    if (mode != -1 && (mode < 0 || (mode & 0xFF) > 2)) return A3_ERR_INVALID;
+int a3_debug_set_overlap(int mode) {   // -1: the library decides per batch (default); 0, 1, 2: forced mode
+    if (mode < -1 || mode > 2) return A3_ERR_INVALID;
     std::lock_guard<std::mutex> lk(g_defer_mu);
     if (!g_held.empty() || !g_deferred.empty()) return A3_ERR_INVALID;   // batches in flight were submitted under the old mode: collect them first
-    g_overlap_force.store(mode == -1 ? -1 : (mode & 0xFF), std::memory_order_relaxed);
-    { std::lock_guard<std::mutex> lk2(g_streams_mu); g_decode_low_prio = mode != -1 && (mode & 0x100) != 0; }
+    g_overlap_force.store(mode, std::memory_order_relaxed);
     return A3_OK;
 }
 
@@ -1693,14 +1590,6 @@ int a3_debug_build_flags(void) {
     return f;
 }
 
-int a3_debug_set_partition(int k1_cus, int pattern) {   // before the first context of the process is used
-    if (k1_cus < 0 || k1_cus > 248) return A3_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(g_streams_mu);
-    g_part_k1_cus = k1_cus; g_part_pattern = pattern;
-    set_k1_cus(k1_cus > 0 ? k1_cus : 256);
-    return A3_OK;
-}
-
 // the threshold kernel alone on the context's stream, asynchronously (buffers of a preceding batch of the same shape are re-used)
 int a3_debug_launch_threshold(a3_ctx* ctx, const void* pixels_device, int fmt, uint32_t width, uint32_t height, uint32_t n_frames) {
     if (!ctx || !pixels_device || n_frames == 0) return A3_ERR_INVALID;
@@ -1715,21 +1604,12 @@ int a3_debug_launch_threshold(a3_ctx* ctx, const void* pixels_device, int fmt, u
     return A3_OK;
 }
 
-int a3_debug_set_mark_threshold(int on) { g_mark_threshold = on != 0; return A3_OK; }
-int a3_debug_set_k1_stream(int mode) {   // before the first context of the process is used (the device-wide stream is created once)
-    if (mode < 0 || mode > 2) return A3_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(g_streams_mu);
-    g_k1_stream_prio = mode;
-    return A3_OK;
-}
 int a3_debug_set_hold(int on) {
     std::lock_guard<std::mutex> lk(g_defer_mu);
     if (!g_held.empty()) return A3_ERR_INVALID;   // (chains held under the old setting: collect them first)
     g_hold_rests = on != 0;
     return A3_OK;
 }
-
-int a3_debug_set_k1_waves(int waves_per_simd) { set_k1_waves(waves_per_simd); return A3_OK; }
 
 int a3_debug_set_jump_rounds(int rounds) {
     if (rounds < 0 || rounds > 32) return A3_ERR_INVALID;
@@ -1840,7 +1720,7 @@ int a3_download_homographies(a3_ctx* ctx, uint32_t frame, uint8_t* dst, uint8_t*
     if (b > cap) return fail(ctx, A3_ERR_CAPACITY, "cap too small");
     if (sizeof(DecodeOutHost) != decode_out_bytes()) return fail(ctx, A3_ERR_INTERNAL, "DecodeOut layout mismatch");
     if (dst && !ctx->debug_taps) return fail(ctx, A3_ERR_INVALID, "patches are only kept after a3_set_debug_taps(ctx, 1)");
-    if (ctx->pending.active) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");   // (its staging buffer is in use)
+    if (ctx->batch.active) return fail(ctx, A3_ERR_INVALID, "a submitted batch has not been collected");   // (its staging buffer is in use)
     if (b == 0) return A3_OK;
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
@@ -2021,7 +1901,7 @@ int a3_debug_discard_too_near(a3_ctx* ctx, const uint32_t* quads_xy, size_t n, f
 
 int a3_debug_inject_candidates(a3_ctx* ctx, const uint32_t* quads_xy, size_t n) {
     if (!ctx || (!quads_xy && n)) return A3_ERR_INVALID;
-    if (ctx->pending.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_debug_inject_candidates: a submitted batch has not been collected");
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_debug_inject_candidates: a submitted batch has not been collected");
     if (n > kMaxCandDefault) return fail(ctx, A3_ERR_CAPACITY, "a3_debug_inject_candidates: at most 1024 quads");
     ctx->inject.resize(n);
     for (size_t i = 0; i < n; i++) {
@@ -2076,7 +1956,7 @@ int a3_refine_corners(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint
                       const float* cell_px, size_t n) {
     if (!ctx) return A3_ERR_INVALID;
     if (!corners_xy && n) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: null corners");
-    if (ctx->pending.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: a submitted batch has not been collected");
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: a submitted batch has not been collected");
     if (n == 0) return A3_OK;
     if (width == 0 || height == 0) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: empty image");
     if (n > (1u << 30)) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: more than 2^30 corners in one call");
@@ -2155,7 +2035,7 @@ int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corner
                            uint32_t image_width, uint32_t image_height, a3_board_pose* out) {
     if (!ctx) return A3_ERR_INVALID;
     if (!out || (n_markers && (!ids || !corners_xy))) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: null argument");
-    if (ctx->pending.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: a submitted batch has not been collected");
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: a submitted batch has not been collected");
     if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: no board is set (a3_set_board)");
     if (!intr && (image_width == 0 || image_height == 0)) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: empty image");
     if (n_markers > (1u << 20)) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: more than 2^20 markers in one call");

@@ -19,29 +19,15 @@ int  a3_debug_kernel_time(a3_ctx *ctx, int kernel, int dbg, int reps, float *avg
 
 /* Where the decode stage of a SUBMITTED batch is released when another context submits behind it (see a3_api.hip,
  * "deferred decode"): 0 = never deferred (both halves of a batch enqueued at once, as a3_detect_batch always does), 1 = behind
- * the next batch's threshold kernel, 2 = behind its k_local_contract (the default); | 0x100: contexts created from now on get a
- * decode stream of the lowest priority instead of the default one.  Process-wide; results are identical in every mode -- tools/ use it for A/B timing inside one process, since two boxes of the pool differ by more than the effect. */
+ * the next batch's threshold kernel, 2 = behind its k_local_contract (the default); -1 = the library decides per batch (its default).
+ * Process-wide; results are identical in every mode -- tools/ use it for A/B timing inside one process, since two boxes of the pool
+ * differ by more than the effect. */
 int  a3_debug_set_overlap(int mode);
-
-/* K1 waves per SIMD the threshold kernel's strip model sizes its launches for (2: the whole chip in one round; 1: one wave per
- * SIMD, twice as tall strips).  Process-wide; results are identical. */
-int  a3_debug_set_k1_waves(int waves_per_simd);
 
 /* A stand-in for a collective's channel kernels, for a box with one GPU: `workgroups` workgroups of `threads` threads stay
  * resident on `hip_stream` for `usec` microseconds (48 live registers per lane, a read and a short sleep per turn).
  * tools/spin_probe.py measures what such company does to the threshold kernel and to a step. */
 int  a3_debug_spin(void *hip_stream, int workgroups, int threads, int usec);
-
-/* Release point of a caller's side work (a collective's kernels), measured and NOT adopted (tools/spin_probe.py,
- * profiles/r04_spin_probe.txt): with a3_debug_set_mark_threshold(1) an event is recorded behind the threshold kernel of every
- * batch -- which alone costs ~2 % of a step -- and a3_debug_stream_wait_threshold makes work enqueued on `hip_stream` afterwards
- * wait for the threshold kernel of ctx's batch in flight.  Company released there costs a step as much as company released at once. */
-int  a3_debug_set_mark_threshold(int on);
-/* priority probe (measured, not adopted: profiles/r05_k1_priority.txt): 1 / 2 = the threshold kernel of every batch on one device-wide
- * stream of the lowest / highest priority, ordered against the context's stream by two events; 0 = on the context's stream (the
- * product).  Call before any context is used. */
-int  a3_debug_set_k1_stream(int mode);
-int  a3_debug_stream_wait_threshold(a3_ctx *ctx, void *hip_stream);
 
 /* 0: contexts that declared burst gates (a3_order_after) enqueue their whole batch at submit, as round 3's library did; 1 (default):
  * they hold the chain behind their threshold kernel until the burst's last member has enqueued its own (a3_api.hip, submit_common).
@@ -60,11 +46,6 @@ int  a3_debug_launch_threshold(a3_ctx *ctx, const void *pixels_device, int fmt, 
 /* which build this is: bit 0 = -DA3_TUNING (the library reads tuning knobs from the environment), bit 1 = a non-default kernel
  * build option (A3_T_LPX, A3_T_WAVES ...).  0 for the product library; bench.py and the GPU tests report it. */
 int  a3_debug_build_flags(void);
-
-/* CU partition (measurement aid): the threshold kernel of every batch on a device-wide stream restricted to k1_cus compute units
- * (hipExtStreamCreateWithCUMask), every other stream the library creates restricted to the remaining ones.  pattern 0: the first
- * k1_cus units as the runtime numbers them, 1: the same share of every group of 16.  0 = off.  Call before any context is used. */
-int  a3_debug_set_partition(int k1_cus, int pattern);
 
 /* numerics self-check used by the GPU tests: evaluates the IEEE operations the kernels rely on (f64 sqrt/div, f32 sqrt/div)
  * for n inputs so that the host can compare them bit for bit */

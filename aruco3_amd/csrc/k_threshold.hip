@@ -159,13 +159,7 @@ __global__ __launch_bounds__(64) void k_vsum_threshold_generic(const uint8_t* __
 }
 
 // ---- host launcher -------------------------------------------------------------------------
-// K1 waves per SIMD the strip model sizes a launch for (a3_internal.h: a3_debug_set_k1_waves).  2 = the whole chip in one
-// round (every register of every SIMD); 1 = one wave per SIMD, strips twice as tall: half of every SIMD's registers and wave
-// slots stay free for the kernels of another batch's contour / decode stage.
-int g_k1_waves = A3_T_WAVES;
-void set_k1_waves(int w) { g_k1_waves = w < 1 ? 1 : (w > A3_T_WAVES ? A3_T_WAVES : w); }
 bool k1_build_is_default() { return A3_T_LPX == 16 && A3_T_PF == 3 && A3_T_WAVES == 2 && A3_T_RECOMPUTE == 0 && A3_T_ADD32 == 1 && A3_T_LUMA_GROUPS == 1 && A3_T_COMPARE4 == 1; }
-int g_k1_cus = 256;   // compute units the kernel's stream may use (a3_debug_set_partition)
 #ifdef A3_TUNING
 // (tuning builds only) where the radius-7 kernel writes one record per wave: {begin, end (100 MHz), HW_ID, XCC_ID}; nullptr = off
 extern "C" __attribute__((visibility("default"))) int a3_debug_set_k1_stamps(void* device_buffer) {
@@ -173,7 +167,6 @@ extern "C" __attribute__((visibility("default"))) int a3_debug_set_k1_stamps(voi
     return hipMemcpyToSymbol(HIP_SYMBOL(g_k1_stamps), &p, sizeof(p)) == hipSuccess ? 0 : -5;
 }
 #endif
-void set_k1_cus(int c) { g_k1_cus = c < 8 ? 8 : (c > 256 ? 256 : c); }
 
 // radii 1..3 and 4..6: k_threshold_r1.hip, k_threshold_r2.hip
 hipError_t launch_k1_r1(uint32_t radius, hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H, uint32_t n,

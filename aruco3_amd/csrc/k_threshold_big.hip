@@ -259,7 +259,7 @@ hipError_t launch_ring(hipStream_t st, const uint8_t* pixels, int fmt, size_t ro
     const int NB = 2 * R + 1 - ring_reg_rows(R, fast, fmt), WPC = NB <= kRingLdsRows8 ? 8 : 4;
     // strips: K1's model (time ~ rounds x (rows per strip + 2R))
     const int strips_x = (W + OUT - 1) / OUT;
-    const long long slots = (long long)g_k1_cus * WPC, cols = (long long)strips_x * n;
+    const long long slots = 256LL * WPC, cols = (long long)strips_x * n;
     int best_sy = 1; double best_cost = 1e300;
     for (int sy = 1; sy <= std::max(1, H / 16); sy++) {
         const int rows = (H + sy - 1) / sy;

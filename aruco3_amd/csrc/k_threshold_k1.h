@@ -313,7 +313,7 @@ __device__ __forceinline__ void row_sums(const uint32_t g[T_NG], uint32_t Hp[T_N
 // (row % T_PF) of every row are then compile-time constants, and the row that leaves the window -- NR rows old -- sits in slot
 // (row - NR) % NRING (for the default radius NR = NRING = 15: the very slot the new row overwrites).
 template <int FMT, bool FAST, int T_PF = A3_T_PF, int R = T_R>
-__global__ __launch_bounds__(64, T_PF == A3_T_PF ? A3_T_WAVES : 1) void k_grey_threshold7(const uint8_t* __restrict__ pixels, size_t row_stride, size_t frame_stride,
+__global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_t* __restrict__ pixels, size_t row_stride, size_t frame_stride,
                                                         int W, int H, int rows_per_wave, int strips_y, int n_pairs,
                                                         uint8_t* __restrict__ grey,
                                                         uint8_t* __restrict__ bits, int aligned_in, int aligned_out, int map_by_frame,
@@ -580,9 +580,6 @@ __global__ __launch_bounds__(64, T_PF == A3_T_PF ? A3_T_WAVES : 1) void k_grey_t
 #endif
 }
 
-// launch geometry switches (k_threshold.hip; a3_internal.h: a3_debug_set_k1_waves, a3_debug_set_partition)
-extern int g_k1_waves, g_k1_cus;
-
 // the register-resident kernel for one radius R in 1..7 (the default, 7, is the one every figure of DESIGN.md is about)
 template <int R>
 hipError_t launch_k1(hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H, uint32_t n,
@@ -601,7 +598,7 @@ hipError_t launch_k1(hipStream_t st, const uint8_t* pixels, int fmt, size_t row_
     // strip count (at least 16 rows per strip).  256 frames of 1920x1080, R = 7: 2 column strips x 4 strips of 270 rows = 2048 waves
     // = exactly one round of two waves per SIMD.
     const int strips_x = (W + T_OUT - 1) / T_OUT;
-    const long long slots = (long long)g_k1_cus * 4 * g_k1_waves, cols = (long long)strips_x * n;
+    const long long slots = 256 * 4 * A3_T_WAVES, cols = (long long)strips_x * n;
     // (Strips of ONE row for a single small frame -- 480 waves of one 15-row block instead of 30 waves of two -- were tried in round 5:
     // 23.0 us against 16.8 for one 640x480 frame; a wave's fixed costs outweigh the block saved.  The model stays at >= 16 rows.)
     int best_sy = 1; double best_cost = 1e300;
@@ -632,15 +629,12 @@ hipError_t launch_k1(hipStream_t st, const uint8_t* pixels, int fmt, size_t row_
     const size_t lds_bytes = flush_rows > 0 ? (size_t)(flush_rows + UNROLL) * 64 * sizeof(out_bits_t) : 0;
     dim3 grid(map_by_frame ? 8 * (((int)n + 7) / 8) * strips_x * strips_y : 8 * ((n_pairs + 7) / 8) * strips_y), block(64);
     const bool fast = aligned_in && aligned_out;   // W % 16 == 0: a lane's 16 pixels are all inside or all outside
-#define A3_LAUNCH_K1(F, B, PF) hipLaunchKernelGGL((k_grey_threshold7<F, B, PF, R>), grid, block, lds_bytes, st, pixels, row_stride, frame_stride, W, H, \
+#define A3_LAUNCH_K1(F, B) hipLaunchKernelGGL((k_grey_threshold7<F, B, A3_T_PF, R>), grid, block, lds_bytes, st, pixels, row_stride, frame_stride, W, H, \
                                               rows_per_wave, strips_y, n_pairs, grey, bin, aligned_in, aligned_out, map_by_frame, flush_rows)
-    if (fmt == A3_FMT_RGB8) {
-        if constexpr (R == T_R && A3_T_WAVES != 1) { if (fast && g_k1_waves == 1) { A3_LAUNCH_K1(A3_FMT_RGB8, true, 5); return hipGetLastError(); } }
-        if (fast) A3_LAUNCH_K1(A3_FMT_RGB8, true, A3_T_PF); else A3_LAUNCH_K1(A3_FMT_RGB8, false, A3_T_PF);
-    }
-    else if (fmt == A3_FMT_RGBA8) { if (fast) A3_LAUNCH_K1(A3_FMT_RGBA8, true, A3_T_PF); else A3_LAUNCH_K1(A3_FMT_RGBA8, false, A3_T_PF); }
-    else if (fmt == A3_FMT_BGRA8) { if (fast) A3_LAUNCH_K1(A3_FMT_BGRA8, true, A3_T_PF); else A3_LAUNCH_K1(A3_FMT_BGRA8, false, A3_T_PF); }
-    else { if (fast) A3_LAUNCH_K1(A3_FMT_L8, true, A3_T_PF); else A3_LAUNCH_K1(A3_FMT_L8, false, A3_T_PF); }
+    if (fmt == A3_FMT_RGB8) { if (fast) A3_LAUNCH_K1(A3_FMT_RGB8, true); else A3_LAUNCH_K1(A3_FMT_RGB8, false); }
+    else if (fmt == A3_FMT_RGBA8) { if (fast) A3_LAUNCH_K1(A3_FMT_RGBA8, true); else A3_LAUNCH_K1(A3_FMT_RGBA8, false); }
+    else if (fmt == A3_FMT_BGRA8) { if (fast) A3_LAUNCH_K1(A3_FMT_BGRA8, true); else A3_LAUNCH_K1(A3_FMT_BGRA8, false); }
+    else { if (fast) A3_LAUNCH_K1(A3_FMT_L8, true); else A3_LAUNCH_K1(A3_FMT_L8, false); }
 #undef A3_LAUNCH_K1
     return hipGetLastError();
 }

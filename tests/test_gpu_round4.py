@@ -186,6 +186,45 @@ def test_held_chains_with_poses_and_host_threads(dicts):
         pass
 
 
+def test_taps_set_while_a_chain_is_held_apply_from_the_next_batch(dicts):
+    """A batch keeps the settings it was submitted with.  Two contexts step device-planned batches with burst gates: A's gated submit
+    is held, a3_set_debug_taps(A, 1) is called, then B -- the burst's last member -- submits and releases A's chain.  A's collect must
+    equal A's synchronous result for the same frames (its threshold kernel ran without taps: the released chain must not read a grey
+    plane that kernel never wrote), and the taps apply from A's next batch."""
+    import torch
+
+    from aruco3_amd import _lib, synth
+
+    fa, _ = synth.config_frames(1, 4)
+    fb, _ = synth.config_frames(1, 4, first=4)
+    da, db = torch.from_numpy(fa).cuda(), torch.from_numpy(fb).cuda()
+    aa, ab = _args(fa, _lib.MEM_DEVICE, da.data_ptr()), _args(fb, _lib.MEM_DEVICE, db.data_ptr())
+    ca, cb, tapped = [_detector(dicts, "ARUCO_DEFAULT")._context() for _ in range(3)]
+    want_a, want_b = ca.detect_batch(*aa, out_cap=256), cb.detect_batch(*ab, out_cap=256)
+    assert len(want_a[0]) > 0
+    ca.detect_batch(*aa, out_cap=256); cb.detect_batch(*ab, out_cap=256)   # (one chunk each: their next batches are planned on the device)
+    tapped.set_debug_taps(True)
+    want_tapped = tapped.detect_batch(*aa, out_cap=256)
+    h, w = fa.shape[1:3]
+    grey0 = tapped.download_grey(0, w, h)
+    same = lambda got, want: marker_tuples(got[0]) == marker_tuples(want[0]) and np.array_equal(got[1], want[1])
+    for step in range(2):
+        ca.order_after(cb)
+        ca.submit(*aa, out_cap=256)
+        assert ca.stats()["stepping"] == "held"
+        if step == 0:
+            ca.set_debug_taps(True)   # (for the next batches: not the one whose chain is held)
+        cb.submit(*ab, out_cap=256)
+        got_a, got_b = ca.collect(), cb.collect()
+        assert ca.stats()["stepping"] == "held_released_by_last"
+        assert same(got_a, want_tapped if step else want_a) and same(got_b, want_b), step
+        if step == 0:
+            with pytest.raises(_lib.A3Error):   # the batch ran without taps: no grey plane
+                ca.download_grey(0, w, h)
+        else:
+            assert np.array_equal(ca.download_grey(0, w, h), grey0)
+
+
 def test_bench_config5_two_ranks_gloo_with_poses_in_the_gather():
     """BASELINE config 5 through the bench's front door: `python bench.py --workload c5 --gpus 2 --backend gloo` (two fresh child
     ranks on the one leased GPU): detect + pose in submit / collect form on four contexts per rank, pose pairs inside the gather

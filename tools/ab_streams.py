@@ -3,7 +3,9 @@
 contexts in submit / collect.  An arrangement = (streams: shared | own, contexts, K1 waves per SIMD, overlap mode).  Arrangements
 are interleaved ROUNDS times; prints the median ms per step of each, the threshold kernel's duration in company (sampled events)
 and its duration alone in the same geometry.
-  python tools/ab_streams.py [frames] [steps] [rounds] [spec,spec,...]      spec = streams:contexts:k1waves:overlap[:group[:hold]]  (overlap -1: the library decides per batch, its default; 0/1/2: forced through the internal switch)  e.g. own:2:1:0, own:8:2:0:4 (two bursts of
+  python tools/ab_streams.py [frames] [steps] [rounds] [spec,spec,...]      spec = streams:contexts:k1waves:overlap[:group[:hold]]  (k1waves must be 2: the
+  library sizes K1 for two waves per SIMD -- the field stays so that recorded command lines parse; overlap -1: the library decides per
+  batch, its default; 0/1/2: forced through the internal switch)  e.g. own:2:2:0, own:8:2:0:4 (two bursts of
   four, submitted together), own:4:2:0:-1 (rotation with burst gates), own:4:2:0:-1:0 (the same, chains not held back);
   further fields KEY=VALUE are environment knobs of a -DA3_TUNING build (A3_HIP_LIB), set for that arrangement only"""
 import sys
@@ -16,7 +18,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 import os
 
-DEFAULT = "shared:2:2:2,own:2:2:0,own:2:1:0,own:3:1:0,own:3:2:0,shared:2:1:2"
+DEFAULT = "shared:2:2:2,own:2:2:0,own:3:2:0"
 
 
 def main():
@@ -30,6 +32,9 @@ def main():
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 40
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
     specs = (sys.argv[4] if len(sys.argv) > 4 else DEFAULT).split(",")
+    for s in specs:
+        if s.split(":")[2] != "2":
+            sys.exit(f"ab_streams.py: spec {s!r}: k1waves must be 2 (K1 is sized for two waves per SIMD; the one-wave geometry was removed)")
     d = ARDictionary.new_from_named_dict("ARUCO")
     spec, _ = synth.config_spec(2)
     max_ctx = max(int(s.split(":")[1]) for s in specs)
@@ -42,11 +47,6 @@ def main():
     same_batch = [False]
     arg = lambda k: args_of[0] if same_batch[0] else args_of[k % len(args_of)]
     L = _lib.load()
-    if os.environ.get("A3_K1_STREAM", "0") != "0":     # 1 / 2: the threshold kernels on one device-wide stream of the lowest / highest priority
-        assert L.a3_debug_set_k1_stream(int(os.environ["A3_K1_STREAM"])) == 0
-    if os.environ.get("A3_PARTITION", "0") != "0":     # "k1_cus[:pattern]": CU partition, set before any context exists
-        pp = os.environ["A3_PARTITION"].split(":")
-        assert L.a3_debug_set_partition(int(pp[0]), int(pp[1]) if len(pp) > 1 else 0) == 0
     stream = torch.cuda.Stream()
     pools = {"shared": [], "own": []}
     for kind in pools:
@@ -112,7 +112,7 @@ def main():
     k1a = {}
     for r in range(rounds):
         for s in specs:
-            kind, nc, kw, ov = s.split(":")[:4]
+            kind, nc, _, ov = s.split(":")[:4]
             group = int(s.split(":")[4]) if len(s.split(":")) > 4 else 1
             assert L.a3_debug_set_hold(int(s.split(":")[5]) if len(s.split(":")) > 5 else 1) == 0
             for kv in knobs_seen:                      # tuning builds read their knobs from the environment at every launch
@@ -126,7 +126,6 @@ def main():
                 os.environ[kname] = kval; knobs_seen.add(kname)
             ctxs = pools[kind][: int(nc)]
             assert L.a3_debug_set_overlap(int(ov)) == 0
-            assert L.a3_debug_set_k1_waves(int(kw)) == 0
             if s not in k1a:   # the threshold kernel alone in this geometry (synchronous calls, nothing else on the GPU)
                 cx = ctxs[0]
                 cx.set_profiling(_lib.PROFILE_THRESHOLD_ONLY)
@@ -158,7 +157,6 @@ def main():
         print(f"{s:16s} median {med:.4f} ms/step  ({n / med * 1e3:8.0f} frames/s)  K1 in company {k1c[s][0] / max(k1c[s][1], 1):.4f} ms, alone {k1a[s]:.4f} ms  "
               f"all {[round(x, 4) for x in res[s]]}  host us per submit by context {host.get(s)}  library stepping {seen.get(s)}", flush=True)
     L.a3_debug_set_overlap(-1)
-    L.a3_debug_set_k1_waves(2)
     L.a3_debug_set_hold(1)
 
 

@@ -13,9 +13,9 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
-CASES = [(0, 0, 0), (0, 0, -1), (8, 50, 0), (16, 50, 0), (16, 50, 1), (32, 50, 0), (32, 50, 1), (32, 200, 0), (32, 200, 1), (16, 600, 0), (16, 600, 1)]   # (W, T, mode): mode 0 = the
-# spinner is released at once (the product: no event behind the threshold kernel); 1 = it waits for the threshold kernel of the batch just submitted
-# (a3_debug_set_mark_threshold + a3_debug_stream_wait_threshold); -1 = no spinner, but the event is recorded behind every threshold kernel: its own cost
+# (W, T): the spinner is released at once.  (Releasing it behind the threshold kernel of the batch just submitted was measured and not
+# adopted: profiles/r04_spin_probe.txt; its library hooks are gone.)
+CASES = [(0, 0), (8, 50), (16, 50), (32, 50), (32, 200), (16, 600)]
 
 
 def main():
@@ -43,8 +43,7 @@ def main():
             ref = cx.detect_batch(*a, out_cap=n * 64)
     side = torch.cuda.Stream()
 
-    def run(k, wg, usec, profile, mode=0):
-        assert L.a3_debug_set_mark_threshold(0 if mode == 0 else 1) == 0
+    def run(k, wg, usec, profile):
         for cx in ctxs:
             cx.set_profiling(_lib.PROFILE_THRESHOLD_ONLY if profile else 0)
             cx.profile(_lib.STAGE_THRESHOLD, reset=True)
@@ -61,8 +60,6 @@ def main():
             if i + nc < k:
                 sub(i + nc)
             if wg:
-                if mode == 1 and i + nc < k:
-                    assert L.a3_debug_stream_wait_threshold(ctxs[i % nc].handle, side.cuda_stream) == 0
                 assert L.a3_debug_spin(side.cuda_stream, wg, 512, usec) == 0
         tot = [cx.profile(_lib.STAGE_THRESHOLD, reset=True) for cx in ctxs]
         return m, per, sum(t for t, _ in tot) / max(sum(b for _, b in tot), 1)
@@ -71,24 +68,23 @@ def main():
     k1 = {cs: [] for cs in CASES}
     for r in range(rounds):
         order = CASES[r % len(CASES):] + CASES[:r % len(CASES)]      # every case takes every position in turn: what runs before a case moves it by 1-2 %
-        run(2 * nc, 0, 0, False, 0)
-        for wg, usec, mode in order:
-            run(8, wg, usec, False, mode)
+        run(2 * nc, 0, 0, False)
+        for wg, usec in order:
+            run(8, wg, usec, False)
             torch.cuda.synchronize(); t0 = time.perf_counter()
-            m, per, _ = run(steps, wg, usec, False, mode)
-            torch.cuda.synchronize(); res[(wg, usec, mode)].append((time.perf_counter() - t0) / steps * 1e3)
+            m, per, _ = run(steps, wg, usec, False)
+            torch.cuda.synchronize(); res[(wg, usec)].append((time.perf_counter() - t0) / steps * 1e3)
             assert len(m) == len(ref[0]) and np.array_equal(per, ref[1])
-            _, _, k = run(16, wg, usec, True, mode)
+            _, _, k = run(16, wg, usec, True)
             torch.cuda.synchronize()
-            k1[(wg, usec, mode)].append(k)
-    L.a3_debug_set_mark_threshold(0)
-    base = sorted(res[(0, 0, 0)])[len(res[(0, 0, 0)]) // 2]
+            k1[(wg, usec)].append(k)
+    base = sorted(res[(0, 0)])[len(res[(0, 0)]) // 2]
     print(f"BASELINE config 2, {frames} frames per batch, {nc} contexts on their own streams with burst gates; spinner: W workgroups x 512 threads for T us per step, side stream")
-    for wg, usec, mode in CASES:
-        v = sorted(res[(wg, usec, mode)]); med = v[len(v) // 2]
-        kk = sorted(k1[(wg, usec, mode)]); kmed = kk[len(kk) // 2]
-        print(f"W {wg:3d}  T {usec:4d} us {('released behind the threshold kernel' if mode == 1 else ('event behind every threshold kernel' if mode < 0 else 'released at once')):38s}: {med:.4f} ms/step ({n / med * 1e3:8.0f} frames/s, {100 * (med / base - 1):+5.1f} %)   threshold kernel in company {kmed:.4f} ms   "
-              f"all {[round(x, 4) for x in res[(wg, usec, mode)]]}", flush=True)
+    for wg, usec in CASES:
+        v = sorted(res[(wg, usec)]); med = v[len(v) // 2]
+        kk = sorted(k1[(wg, usec)]); kmed = kk[len(kk) // 2]
+        print(f"W {wg:3d}  T {usec:4d} us: {med:.4f} ms/step ({n / med * 1e3:8.0f} frames/s, {100 * (med / base - 1):+5.1f} %)   threshold kernel in company {kmed:.4f} ms   "
+              f"all {[round(x, 4) for x in res[(wg, usec)]]}", flush=True)
 
 
 if __name__ == "__main__":
