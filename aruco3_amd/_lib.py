@@ -12,7 +12,7 @@ import numpy as np
 import os
 
 _HERE = Path(__file__).resolve().parent
-# A3_HIP_LIB: the sweep scripts under tools/ point this at a `make tuning` build (build/tuning/libaruco3_hip.so, -DA3_TUNING);
+# A3_HIP_LIB: the A/B scripts under tools/ (ab_libs.sh, r6_ab.sh) point this at another build of the library;
 # everything else loads the product library next to this file.
 LIB_PATH = Path(os.environ["A3_HIP_LIB"]).resolve() if os.environ.get("A3_HIP_LIB") else _HERE / "libaruco3_hip.so"
 

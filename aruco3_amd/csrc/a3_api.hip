@@ -19,7 +19,6 @@ namespace a3 {
 // k_threshold.hip
 hipError_t launch_grey_threshold(hipStream_t, const uint8_t*, int, size_t, size_t, int, int, uint32_t, uint32_t, uint8_t*, uint64_t*, uint16_t*);
 bool threshold_writes_grey_plane(uint32_t radius, const uint8_t* pixels, size_t row_stride, size_t frame_stride, int W);
-bool k1_build_is_default();
 // k_contours.hip
 hipError_t launch_dart_count(hipStream_t, const uint64_t*, int, int, uint32_t, uint32_t, unsigned long long*, uint32_t*, uint64_t, uint32_t*, uint32_t*, void*, size_t);
 size_t tile_darts_bytes(uint32_t W, uint32_t H, uint32_t n_frames);
@@ -386,7 +385,7 @@ std::vector<a3_ctx*> g_deferred;
 // 0: no deferral; 1: release a waiting decode stage behind the next batch's threshold kernel; 2 (default): behind the next batch's
 // k_local_contract -- the kernels that follow it (entry resolution, finalize, scatter, quads) are latency-bound like the decode
 // stage and share the chip with it, whereas the dart kernels before it are bound by VALU and LDS throughput and only get slower
-// in company.  Measured in one process (tools/attic/ab_overlap.py, BASELINE config 2, two contexts): 0.820 / 0.769 / 0.762 ms per step
+// in company.  Measured in one process (round 3, docs/HISTORY.md; BASELINE config 2, two contexts): 0.820 / 0.769 / 0.762 ms per step
 // for modes 0 / 1 / 2 (0.794 / 0.744 / 0.741 on another box); smaller decode grids (2048 ... 512 workgroups) only lose.  Deferring the second half of the contour stage as well (entry resolution ... quads, released with the
 // decode stage behind the next threshold kernel) was built and measured: 0.777 with two contexts, 0.821 with three -- dropped.
 // (a3_debug_set_overlap in a3_internal.h switches modes for the A/B measurements of tools/.)
@@ -930,9 +929,6 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     }
     unsigned int flags = hs[4];
     for (int sh = 0; sh < 16; sh++) ctx->stats.contours_traced += hs[48 + sh];   // borders finished inside k_local_contract (kDead)
-#ifdef A3_TUNING
-    if (tuning_knob("A3_PRINT_DEAD", 0)) { uint64_t dead = 0; for (int sh = 0; sh < 16; sh++) dead += hs[48 + sh]; fprintf(stderr, "[a3] borders finished in k_local_contract: %llu\n", (unsigned long long)dead); }
-#endif
     uint64_t need_points = 0; uint32_t need_contours = 0;
     bool jump_short = false, resolve_needed = false, entry_overflow = false;
     for (size_t ci = 0; ci < n_chunks; ci++) {
@@ -1580,15 +1576,8 @@ int a3_debug_spin(void* hip_stream, int workgroups, int threads, int usec) {
     return launch_spin(reinterpret_cast<hipStream_t>(hip_stream), workgroups, threads, usec, sink) == hipSuccess ? A3_OK : A3_ERR_HIP;
 }
 
-// bit 0: built with -DA3_TUNING (environment knobs are read), bit 1: any other non-default build flag of the kernels
-int a3_debug_build_flags(void) {
-    int f = 0;
-#ifdef A3_TUNING
-    f |= 1;
-#endif
-    f |= k1_build_is_default() ? 0 : 2;
-    return f;
-}
+// always 0: the library has a single build (see a3_internal.h)
+int a3_debug_build_flags(void) { return 0; }
 
 // the threshold kernel alone on the context's stream, asynchronously (buffers of a preceding batch of the same shape are re-used)
 int a3_debug_launch_threshold(a3_ctx* ctx, const void* pixels_device, int fmt, uint32_t width, uint32_t height, uint32_t n_frames) {

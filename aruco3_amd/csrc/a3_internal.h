@@ -43,8 +43,9 @@ int  a3_debug_set_jump_rounds(int rounds);
  * at once share the chip) */
 int  a3_debug_launch_threshold(a3_ctx *ctx, const void *pixels_device, int fmt, uint32_t width, uint32_t height, uint32_t n_frames);
 
-/* which build this is: bit 0 = -DA3_TUNING (the library reads tuning knobs from the environment), bit 1 = a non-default kernel
- * build option (A3_T_LPX, A3_T_WAVES ...).  0 for the product library; bench.py and the GPU tests report it. */
+/* which build this is: always 0 now that the library has no tuning build and no kernel build options (bit 0 was a build that read
+ * tuning knobs from the environment, bit 1 a non-default kernel build option).  Kept because bench.py and the GPU tests report it
+ * for whichever library A3_HIP_LIB names. */
 int  a3_debug_build_flags(void);
 
 /* numerics self-check used by the GPU tests: evaluates the IEEE operations the kernels rely on (f64 sqrt/div, f32 sqrt/div)

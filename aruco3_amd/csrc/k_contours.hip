@@ -36,22 +36,18 @@
 // atomic on one address costs ~11 ns and they serialise (12 k tiles = 140 us).  Counters that
 // remain are sharded 16 ways (entry and leader lists) or bumped once per workgroup.
 #include <algorithm>
-#include <cstdlib>
 
 #include "a3_common.h"
 
-// Darts per lane and trip in the per-dart sweeps (build knobs, swept on BASELINE config 2).  k_jump_finalize: 2 / 4 / 6 / 8 darts
+// Darts per lane and trip in the per-dart sweeps (swept on BASELINE config 2).  k_jump_finalize: 2 / 4 / 6 / 8 darts
 // -> 53 / 48 / 44.5 / 45 us with its three dependent loads of rounds 2-5; with two (round 6: the entry's slot comes with the state)
 // 4 / 6 / 8 / 10 -> 44.7 / 41.9 / 39.0 / 165 us (10 spills).  k_scatter_points: 1 / 2 / 3 / 4 -> 34.5 / 37 / 37.5 / 41 us
 // (on 8192 workgroups): its loads of one dart already come two and three at a time, and more threads beat more darts per thread.
-#ifndef A3_FIN_B
-#define A3_FIN_B 8
-#endif
-#ifndef A3_SCAT_B
-#define A3_SCAT_B 1
-#endif
 
 namespace a3 {
+
+constexpr int kFinB = 8;    // k_jump_finalize
+constexpr int kScatB = 1;   // k_scatter_points
 
 // ---------------------------------------------------------------------------------------
 // 64 pixels per lane: neighbour occupancy words in ring order W NW N NE E SE S SW
@@ -163,10 +159,7 @@ constexpr int kCountLanes = 60;   // words per wave and row: 15 whole tiles (lan
 // k_tile_scan adds them): with one wave per tile row pair the launch was 2304 waves on 1024 SIMDs, i.e. three on some SIMDs
 // and two on the others, and the kernel is bound by its bit arithmetic (VALU busy 70 %), so it took as long as three waves on
 // one SIMD.  1 / 2 / 4 parts: 36 / 31 / 27.6 us (each part re-reads two rows of its neighbours).
-#ifndef A3_COUNT_PARTS
-#define A3_COUNT_PARTS 4
-#endif
-constexpr int kCountHalves = A3_COUNT_PARTS;
+constexpr int kCountHalves = 4;
 template <int G>
 __global__ __launch_bounds__(64) void k_dart_count(const uint64_t* __restrict__ bits, int W, int H, uint32_t first_frame,
                                                    unsigned long long* __restrict__ frame_darts, uint32_t* __restrict__ tile_darts,
@@ -711,10 +704,7 @@ __global__ __launch_bounds__(256) void k_dart_link(int W, int H, uint32_t first_
 // costs the reference's noise recipe 19 %), 1024 with the per-frame entry resolution of clean frames, where the entries are
 // cheap and the smaller tile saves a doubling round and half of the LDS per workgroup (72 -> 60 us on BASELINE config 2;
 // 512: 68 us, 4096: 103 us).
-#ifndef A3_KLT
-#define A3_KLT 2048
-#endif
-constexpr int kLT = A3_KLT;                   // the larger of the two: sizes the entry slot space of the global rounds
+constexpr int kLT = 2048;   // the larger of the two: sizes the entry slot space of the global rounds
 constexpr int kLTFrame = 1024;
 // Entry slots are handed out from 16 counters (one same-address atomic costs ~11 ns and they serialise): tile t uses
 // shard t & 15, whose slots are [shard * cap, shard * cap + count[shard]); a tile holds at most kLT entries, so
@@ -1306,7 +1296,7 @@ __global__ __launch_bounds__(256) void k_jump_finalize(uint32_t n_darts,
     // window froze at -> that entry's state) issued for all of them before the first is used: the kernel is a chain of round trips
     // to memory.  Loads are unconditional from clamped indices (slot 0 for final states: a cached line); behind an `if` the
     // compiler would issue them one at a time again.
-    constexpr int B = A3_FIN_B;
+    constexpr int B = kFinB;
     int it = 0;
     for (uint32_t d0 = blockIdx.x * blockDim.x + threadIdx.x; d0 < n_darts; d0 += B * stride, it += B) {
         FinState s[B];
@@ -1640,7 +1630,7 @@ __global__ __launch_bounds__(256) void k_scatter_points(const FinState* __restri
     bool bad = false;
     // B darts per lane at a time, three rounds of loads instead of five per dart: {state, record} -> {leader's key, border
     // slot of the leader} -> {border record, start offset}.  Unconditional loads from clamped indices, see k_jump_finalize.
-    constexpr int B = A3_SCAT_B;
+    constexpr int B = kScatB;
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t d0 = blockIdx.x * blockDim.x + threadIdx.x; d0 < n_darts; d0 += B * stride) {
         FinState s[B];
@@ -1912,8 +1902,7 @@ __global__ void k_unpack_bits(const uint64_t* __restrict__ bits, int W, int H, u
 // ---------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------
-// grid caps of the per-dart sweeps, overridable for tuning (tools/attic/sweep_grids.sh)
-static inline int env_cap(const char* name, int dflt) { const int v = tuning_knob(name, dflt); return v > 0 ? v : dflt; }   // grid caps: constants unless -DA3_TUNING
+constexpr int kFinBlocks = 1536;   // grid cap of k_jump_finalize (raised where a lane would get more than 32 darts)
 static inline int blocks_for(uint64_t n, int per_block, int cap) {
     uint64_t b = (n + per_block - 1) / per_block;
     if (b < 1) b = 1;
@@ -1965,7 +1954,7 @@ hipError_t launch_dart_build(hipStream_t st, const uint64_t* bits, int W, int H,
     hipLaunchKernelGGL(k_dart_assign, dim3((tiles * n_frames + 7u) / 8u * 8u), dim3(256), 0, st, bits, W, H, first_frame, frame_base, tile_off,
                        pix_base, tile_darts, d_rec, d_succ, n_live, dbg, tile_mask, tiles, n_frames);
     if (dbg && dbg != 5) return hipGetLastError();   // 5 = everything (the probe's reference point), others leave d_succ alone
-    hipLaunchKernelGGL(k_dart_link, dim3(blocks_for(n_darts, 256, env_cap("A3_LINK_BLOCKS", 4096))), dim3(256), 0, st, W, H, first_frame, pix_base, bits, d_rec, d_succ, n_darts, n_live);
+    hipLaunchKernelGGL(k_dart_link, dim3(blocks_for(n_darts, 256, 4096)), dim3(256), 0, st, W, H, first_frame, pix_base, bits, d_rec, d_succ, n_darts, n_live);
     return hipGetLastError();
 }
 
@@ -2016,7 +2005,7 @@ hipError_t launch_rank_cycles(hipStream_t st, uint32_t n_darts, int W, const uin
         hipLaunchKernelGGL(k_entry_frame, dim3(n_frames), dim3(256), 0, st, entry_list, frame_entries, frame_base, fin, d_rec, W, a, ctr,
                            ll, leader_count, lcap);
         if (no_finalize) return hipGetLastError();
-        const int fin_blocks = std::max(blocks_for(n_darts, 256, env_cap("A3_FIN_BLOCKS", 1536)), (int)(((uint64_t)n_darts + 256ull * 32 - 1) / (256ull * 32)));
+        const int fin_blocks = std::max(blocks_for(n_darts, 256, kFinBlocks), (int)(((uint64_t)n_darts + 256ull * 32 - 1) / (256ull * 32)));
         hipLaunchKernelGGL(k_jump_finalize, dim3(fin_blocks), dim3(256), 0, st, n_darts, a, fin,
                            leader_list, leader_count, leader_shard_cap(n_darts), n_live, ctr);
         return hipGetLastError();
@@ -2027,7 +2016,7 @@ hipError_t launch_rank_cycles(hipStream_t st, uint32_t n_darts, int W, const uin
         hipLaunchKernelGGL(k_entry_jump, grid, block, 0, st, a, b, entry_count, ecap, r, ctr);
         EntryState* t = a; a = b; b = t;
     }
-    const int fin_blocks = std::max(blocks_for(n_darts, 256, env_cap("A3_FIN_BLOCKS", 1536)), (int)(((uint64_t)n_darts + 256ull * 32 - 1) / (256ull * 32)));
+    const int fin_blocks = std::max(blocks_for(n_darts, 256, kFinBlocks), (int)(((uint64_t)n_darts + 256ull * 32 - 1) / (256ull * 32)));
     hipLaunchKernelGGL(k_jump_finalize, dim3(fin_blocks), block, 0, st, n_darts, a, fin,
                        leader_list, leader_count, leader_shard_cap(n_darts), n_live, ctr);
     return hipGetLastError();
@@ -2058,8 +2047,8 @@ hipError_t launch_select_scatter(hipStream_t st, const void* fin8, uint32_t n_da
                                  const void* es8 /* the entry table when finalize_inline(): pending states are resolved by the readers */) {
     const EntryState* es = reinterpret_cast<const EntryState*>(es8);
     // 8192 workgroups for the graphs of clean frames (6-8 M darts), more for the tens of millions of darts of noise-like ones
-    const dim3 grid(blocks_for(n_darts, 256, env_cap("A3_SCATTER_BLOCKS", (int)std::min<uint32_t>(65536u, std::max<uint32_t>(8192u, n_darts / 1024u))))), block(256);
-    hipLaunchKernelGGL(k_cycle_select, dim3(blocks_for(n_darts / 64 + 1, 256, env_cap("A3_SELECT_BLOCKS", 1024))), block, 0, st, reinterpret_cast<FinState*>(const_cast<void*>(fin8)), leader_list, leader_count, d_succ, t_cur,
+    const dim3 grid(blocks_for(n_darts, 256, (int)std::min<uint32_t>(65536u, std::max<uint32_t>(8192u, n_darts / 1024u)))), block(256);
+    hipLaunchKernelGGL(k_cycle_select, dim3(blocks_for(n_darts / 64 + 1, 256, 1024)), block, 0, st, reinterpret_cast<FinState*>(const_cast<void*>(fin8)), leader_list, leader_count, d_succ, t_cur,
                        frame_base, n_frames, first_frame, min_edge_length,
                        eps_factor, image_diag, contours, cyc_start_off, max_contours, max_points, ctr, leader_shard_cap(n_darts), d_rec,
                        inline_resolve_W, keep_tmp, keep_all, es);
@@ -2073,8 +2062,8 @@ hipError_t launch_contour_quads(hipStream_t st, const ContourRec* contours, cons
                                 CandRec* cands, uint32_t* cand_count, unsigned int* err_flags, int coords14, uint32_t n_darts) {
     // 2560 + 4096 workgroups for the millions of darts of a batch (or of one noise frame); a graph of a few ten thousand darts -- one
     // clean frame per call -- gets a grid in proportion: dispatching 6656 workgroups that find nothing to do took 8 of that call's 13 us
-    const uint32_t b64 = std::min<uint32_t>((uint32_t)env_cap("A3_QUAD_BLOCKS64", 2560), std::max<uint32_t>(40u, n_darts / 2048u)),
-                   b16 = std::min<uint32_t>((uint32_t)env_cap("A3_QUAD_BLOCKS16", 4096), std::max<uint32_t>(64u, n_darts / 1024u));
+    const uint32_t b64 = std::min<uint32_t>(2560u, std::max<uint32_t>(40u, n_darts / 2048u)),
+                   b16 = std::min<uint32_t>(4096u, std::max<uint32_t>(64u, n_darts / 1024u));
     hipLaunchKernelGGL(k_contour_quads, dim3(b64 + b16), dim3(256), 0, st, b64, contours, ctr, max_contours, points, eps_factor, min_edge_length,
                        first_frame, max_cand, cands, cand_count, err_flags, coords14);
     return hipGetLastError();

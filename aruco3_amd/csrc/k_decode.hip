@@ -8,7 +8,6 @@
 // Floating point follows the reference operation by operation (f64 for the 8x8 solve and
 // Otsu, f32 elsewhere); the library is built with -ffp-contract=off so that no a*b+c is
 // fused, exactly like the Rust reference and the CPU oracle.
-#include <cstdlib>
 
 #include "a3_common.h"
 #include "a3_ippe.h"
@@ -41,11 +40,9 @@ __device__ bool solve_projection(const float* from, float S, float* inv_out);
 // in LDS (a byte per slot: 64 KB at the format's limit of 65 536 -- a3_marker.candidate_index is 16 bits).  Same walk, same order,
 // every LDS access of the small form a trip to the L2 instead: correct, not fast (0.1 s for 7 000 quads, all of them far apart).
 constexpr uint32_t kFrameCandLds = 6144;   // 21 bytes of LDS per slot in the small form: 129 KB of the CU's 160
-#ifndef A3_FC_WAVES
-#define A3_FC_WAVES 1
-#endif
+constexpr int kFcWaves = 1;   // occupancy bound of k_frame_candidates and k_projection (the 8x8 solve needs ~200 VGPRs)
 template <bool BIG>
-__global__ __launch_bounds__(64, A3_FC_WAVES) void k_frame_candidates(const CandRec* __restrict__ cands, const uint32_t* __restrict__ cand_count,
+__global__ __launch_bounds__(64, kFcWaves) void k_frame_candidates(const CandRec* __restrict__ cands, const uint32_t* __restrict__ cand_count,
                                                          uint32_t max_cand, float min_distance, uint16_t* pre_xy,
                                                          uint16_t* __restrict__ fin_xy, uint32_t* __restrict__ fin_count,
                                                          uint32_t* __restrict__ work, unsigned int* __restrict__ work_count,
@@ -428,7 +425,7 @@ __global__ void k_weight_table(uint32_t S, uint32_t n, uint32_t max_taps, float*
     const uint32_t left = resize_weights(S, n, threadIdx.x, row + 2, &cnt);
     row[0] = __uint_as_float(left); row[1] = __uint_as_float(cnt);
 }
-__global__ __launch_bounds__(64, A3_FC_WAVES) void k_projection(const uint16_t* __restrict__ fin_xy, const uint32_t* __restrict__ work,
+__global__ __launch_bounds__(64, kFcWaves) void k_projection(const uint16_t* __restrict__ fin_xy, const uint32_t* __restrict__ work,
                                                    const unsigned int* __restrict__ work_count, uint32_t S, ProjRec* __restrict__ proj) {
     const uint32_t n_work = *work_count;
     for (uint32_t wi = blockIdx.x * blockDim.x + threadIdx.x; wi < n_work; wi += gridDim.x * blockDim.x) {
@@ -454,21 +451,10 @@ __device__ __forceinline__ void rotated_source(uint32_t r, uint32_t n, uint32_t 
 
 // grid-stride over the work list; block = NT threads; dynamic LDS:
 //   patch S*S | tmp n*S f32 | wtab n*max_taps f32 | wleft n u32 | wcnt n u32 | bits n*n
-#ifndef A3_D_KU
-#define A3_D_KU 2
-#endif
-#ifndef A3_D_WAVES
-#define A3_D_WAVES 5
-#endif
-#ifndef A3_D_THREADS
-#define A3_D_THREADS 256   // threads that sample one candidate (large batches; small ones: 256 throughout)
-#endif
-#ifndef A3_D_WAVES256
-#define A3_D_WAVES256 5   // workgroups of 256 threads per CU-quarter (= waves per SIMD)
-#endif
-#ifndef A3_D_DB
-#define A3_D_DB 8     // dictionary codes per lane and trip in the nearest-code scan
-#endif
+constexpr int kDecodeKU = 2;        // samples per lane and trip whose row reads are in flight together
+constexpr int kDecodeThreads = 256;  // threads that sample one candidate
+constexpr int kDecodeWaves = 5;      // workgroups of 256 threads per CU-quarter (= waves per SIMD)
+constexpr int kDecodeDB = 8;         // dictionary codes per lane and trip in the nearest-code scan
 // Wave-wide scans and reductions by DPP row shifts (row_shr:1,2,4,8 inside rows of 16 lanes) and row broadcasts (row_bcast:15 into
 // rows 1 and 3, row_bcast:31 into rows 2 and 3): pure VALU, the result of a reduction ends up in lane 63.  The shuffle ladders
 // they replace are six ds_bpermute round trips each.  `OLD` is what a lane without a source combines with: the identity.
@@ -555,11 +541,11 @@ __device__ __forceinline__ void compact_frame_wave(uint32_t f, int lane, const D
 }
 
 // NT threads sample one candidate, PT of them (64, or all) run the stages after the sampling.  History of the shape, on the
-// 2.5 k candidates of BASELINE config 2 (tools/attic/tune_decode.sh): 256 threads throughout, 4 samples "in flight" per lane, row-major
+// 2.5 k candidates of BASELINE config 2 (round 2, docs/HISTORY.md): 256 threads throughout, 4 samples "in flight" per lane, row-major
 // sample order (round 1): 116 us; 64 threads, 8 x 8 blocked order: 98 us; 256 threads sampling, the first wave doing the rest:
 // 94 us -- and 7 us less than the 64-thread version inside the pipeline, where the frames are not in any cache.
 template <int NT, int PT>
-__global__ __launch_bounds__(NT, NT == 64 ? A3_D_WAVES : A3_D_WAVES256) void k_decode(PixelSrc src, int W, int H, uint32_t first_frame,
+__global__ __launch_bounds__(NT, kDecodeWaves) void k_decode(PixelSrc src, int W, int H, uint32_t first_frame,
                                                 const uint16_t* __restrict__ fin_xy, const uint32_t* __restrict__ work,
                                                 const unsigned int* __restrict__ work_count, uint32_t max_cand, uint32_t S, uint32_t n,
                                                 uint32_t max_taps, const uint64_t* __restrict__ dict, uint32_t n_codes, uint32_t tau,
@@ -623,14 +609,11 @@ __global__ __launch_bounds__(NT, NT == 64 ? A3_D_WAVES : A3_D_WAVES256) void k_d
                         t7 = s_inv[7], t8 = s_inv[8];
             // kU samples per lane per trip: all their row reads (one 12-byte load per row and sample: the two taps of a row
             // are adjacent) are in flight before the first is converted
-            constexpr int kU = A3_D_KU;
+            constexpr int kU = kDecodeKU;
             // Sample order: blocks of 8 x 8 output pixels, one block per wave instruction (lane = 8 * (y & 7) + (x & 7)).  Taps
             // of a block lie in a compact patch of the frame whatever the marker's rotation, so the 64 lanes of a load touch
             // a few dozen cache lines; a row-major order puts the 64 samples of an instruction on a slanted line that crosses
-            // a new image row -- a new cache line -- at almost every sample of a rotated marker (A3_D_BLOCKED=0: row-major).
-#ifndef A3_D_BLOCKED
-#define A3_D_BLOCKED 1
-#endif
+            // a new image row -- a new cache line -- at almost every sample of a rotated marker.
             const uint32_t bpp = (src.fmt == A3_FMT_RGB8) ? 3u : ((src.fmt == A3_FMT_RGBA8 || src.fmt == A3_FMT_BGRA8) ? 4u : 1u);
             // (a frame smaller than one wide read cannot hold a candidate; the weight table is merely something of 16 KB to read)
             const unsigned long long frame_bytes = (unsigned long long)(H - 1) * src.row_stride + (unsigned long long)W * bpp;
@@ -638,19 +621,14 @@ __global__ __launch_bounds__(NT, NT == 64 ? A3_D_WAVES : A3_D_WAVES256) void k_d
             const uintptr_t img_u = reinterpret_cast<uintptr_t>(img);
             const uint32_t mis = tiny ? 0u : (uint32_t)(img_u & 3u);
             const a3_gptr base4 = reinterpret_cast<a3_gptr>(tiny ? reinterpret_cast<uintptr_t>(wtab) : img_u - mis);
-            const uint32_t nbx = (S + 7u) / 8u, n_slots = A3_D_BLOCKED ? nbx * nbx * 64u : S * S;
-            // slot -> (x, y); i / S by a multiply-high in the row-major order (S is uniform but not a compile-time constant)
-            // blk / nbx as (blk * Mb) >> 16, Mb = 2^16 / nbx + 1: exact while blk * nbx < 2^16 (blk < nbx^2 <= 625, nbx <= 25), and full rate
-            const uint32_t M = S > 1 ? 0xFFFFFFFFu / S + 1u : 0u, Mb = 65536u / nbx + 1u;
+            const uint32_t nbx = (S + 7u) / 8u, n_slots = nbx * nbx * 64u;
+            // slot -> (x, y); blk / nbx as (blk * Mb) >> 16, Mb = 2^16 / nbx + 1: exact while blk * nbx < 2^16 (blk < nbx^2 <= 625,
+            // nbx <= 25), and full rate
+            const uint32_t Mb = 65536u / nbx + 1u;
             auto slot_xy = [&](uint32_t slot, uint32_t* x, uint32_t* y) -> bool {
-                if (A3_D_BLOCKED) {
-                    const uint32_t blk = slot >> 6, l = slot & 63u, by = __umul24(min(blk, 1023u), Mb) >> 16, bx = blk - __umul24(by, nbx);
-                    *x = bx * 8u + (l & 7u); *y = by * 8u + (l >> 3);
-                    return slot < n_slots && *x < S && *y < S;
-                }
-                const uint32_t row = S > 1 ? __umulhi(slot, M) : slot;
-                *x = slot - row * S; *y = row;
-                return slot < n_slots;
+                const uint32_t blk = slot >> 6, l = slot & 63u, by = __umul24(min(blk, 1023u), Mb) >> 16, bx = blk - __umul24(by, nbx);
+                *x = bx * 8u + (l & 7u); *y = by * 8u + (l >> 3);
+                return slot < n_slots && *x < S && *y < S;
             };
             for (uint32_t i0 = tid; i0 < n_slots; i0 += NT * kU) {
                 TapLoad tl[kU];
@@ -811,7 +789,7 @@ __global__ __launch_bounds__(NT, NT == 64 ? A3_D_WAVES : A3_D_WAVES256) void k_d
                 const uint64_t c0 = s_codes[0], c1 = s_codes[1], c2 = s_codes[2], c3 = s_codes[3];
                 // eight codes per lane and trip, their loads issued together (unconditional, clamped index): one code per trip is a
                 // chain of n_codes / 64 round trips to the table -- 16 for a 1024-code dictionary
-                constexpr int DB = A3_D_DB;
+                constexpr int DB = kDecodeDB;
                 for (uint32_t i0 = tid; i0 < n_codes; i0 += PT * DB) {
                     uint64_t cw[DB];
     #pragma unroll
@@ -1144,12 +1122,11 @@ hipError_t launch_decode(hipStream_t st, PixelSrc src, int W, int H, uint32_t fi
     // frames against 39), and on one wave -- no workgroup barriers -- when thousands of candidates are in flight and only the
     // throughput counts (BASELINE config 2: decode stage 0.123 ms against 0.130 with one wave per candidate throughout).
     const int d = dbg == -1000 ? 0 : (dbg < 0 ? -dbg : dbg);
-    few = tuning_knob("A3_DECODE_WIDE", few);   // (-DA3_TUNING builds only)
     if (few)
         hipLaunchKernelGGL((k_decode<256, 256>), dim3(grid_blocks), dim3(256), decode_lds_bytes(S, n, max_taps), st, src, W, H, first_frame, fin_xy, work, work_count,
                            max_cand, S, n, max_taps, dict, n_codes, tau, filter, recs, wtab, reinterpret_cast<DecodeOut*>(outs), patches, patch_cap, per_frame, d);
     else
-        hipLaunchKernelGGL((k_decode<A3_D_THREADS, 64>), dim3(grid_blocks), dim3(A3_D_THREADS), decode_lds_bytes(S, n, max_taps), st, src, W, H, first_frame, fin_xy, work,
+        hipLaunchKernelGGL((k_decode<kDecodeThreads, 64>), dim3(grid_blocks), dim3(kDecodeThreads), decode_lds_bytes(S, n, max_taps), st, src, W, H, first_frame, fin_xy, work,
                            work_count, max_cand, S, n, max_taps, dict, n_codes, tau, filter, recs, wtab, reinterpret_cast<DecodeOut*>(outs), patches, patch_cap,
                            per_frame, d);
     return hipGetLastError();

@@ -159,15 +159,6 @@ __global__ __launch_bounds__(64) void k_vsum_threshold_generic(const uint8_t* __
 }
 
 // ---- host launcher -------------------------------------------------------------------------
-bool k1_build_is_default() { return A3_T_LPX == 16 && A3_T_PF == 3 && A3_T_WAVES == 2 && A3_T_RECOMPUTE == 0 && A3_T_ADD32 == 1 && A3_T_LUMA_GROUPS == 1 && A3_T_COMPARE4 == 1; }
-#ifdef A3_TUNING
-// (tuning builds only) where the radius-7 kernel writes one record per wave: {begin, end (100 MHz), HW_ID, XCC_ID}; nullptr = off
-extern "C" __attribute__((visibility("default"))) int a3_debug_set_k1_stamps(void* device_buffer) {
-    unsigned long long* p = reinterpret_cast<unsigned long long*>(device_buffer);
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_k1_stamps), &p, sizeof(p)) == hipSuccess ? 0 : -5;
-}
-#endif
-
 // radii 1..3 and 4..6: k_threshold_r1.hip, k_threshold_r2.hip
 hipError_t launch_k1_r1(uint32_t radius, hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H, uint32_t n,
                         uint8_t* grey, uint64_t* bits);

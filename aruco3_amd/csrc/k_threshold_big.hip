@@ -82,7 +82,7 @@ __global__ __launch_bounds__(64, 2 * R + 1 - ring_reg_rows(R, FAST, FMT) <= kRin
                                                                 int rows_per_wave, int strips_y, int n_frames, uint8_t* __restrict__ grey,
                                                                 uint8_t* __restrict__ bits, int flush_rows, int aligned_in) {
     static_assert(R >= 8 && R <= 31, "radii 8..31: one (..15) or two neighbouring lanes' 16 columns cover the window's reach");
-    constexpr int RA = ring_reg_rows(R, FAST, FMT), NB = 2 * R + 1 - RA, PF = A3_T_PF;   // RA / NB: rows of the ring's first (registers) and second stage (LDS)
+    constexpr int RA = ring_reg_rows(R, FAST, FMT), NB = 2 * R + 1 - RA, PF = T_PF;   // RA / NB: rows of the ring's first (registers) and second stage (LDS)
     static_assert(RA >= R && NB >= 1, "the window's centre row (R iterations old) is still in registers");
     constexpr int HL = ring_halo_lanes(R), EB = 16 * HL, OUT = ring_out_cols(R);
     // LDS admits eight waves per CU; they must sit two on every SIMD.  Below 169 VGPRs a SIMD takes three, the eight are then
@@ -270,9 +270,9 @@ hipError_t launch_ring(hipStream_t st, const uint8_t* pixels, int fmt, size_t ro
     const int rows_per_wave = (H + best_sy - 1) / best_sy;
     const int strips_y = (H + rows_per_wave - 1) / rows_per_wave;
     const int per_wave = (160 * 1024) / WPC - 64;   // (the allocation granule)
-    const int flush_rows = std::max(1, std::min({128, rows_per_wave, (per_wave - NB * 1024) / 128 - A3_T_PF}));
-    const size_t lds_bytes = (size_t)NB * 1024 + (size_t)(flush_rows + A3_T_PF) * 128;
-    if ((per_wave - NB * 1024) / 128 - A3_T_PF < 1) return hipErrorInvalidValue;   // (cannot happen: 19 KB + 4 rows fit an eighth, 32 KB + 60 rows a quarter)
+    const int flush_rows = std::max(1, std::min({128, rows_per_wave, (per_wave - NB * 1024) / 128 - T_PF}));
+    const size_t lds_bytes = (size_t)NB * 1024 + (size_t)(flush_rows + T_PF) * 128;
+    if ((per_wave - NB * 1024) / 128 - T_PF < 1) return hipErrorInvalidValue;   // (cannot happen: 19 KB + 4 rows fit an eighth, 32 KB + 60 rows a quarter)
     dim3 grid(8 * (((int)n + 7) / 8) * strips_x * strips_y), block(64);
 #define A3_LAUNCH_RING(F)                                                                                                              \
     {                                                                                                                                  \

@@ -1,10 +1,8 @@
-// k_threshold_k1.h -- the register-resident threshold kernel (template on format, radius, load-queue depth) and its launcher
+// k_threshold_k1.h -- the register-resident threshold kernel (template on format, alignment, radius) and its launcher
 // template: shared by k_threshold.hip (radius 7, the default) and k_threshold_r1.hip / _r2.hip (radii 1..3 / 4..6), which exist
 // only so that the instantiations compile in parallel.  Everything about the kernel is described in k_threshold.hip's header.
 #pragma once
 #include <algorithm>
-#include <cstdlib>
-#include <type_traits>
 #include <utility>
 
 #include "a3_common.h"
@@ -12,98 +10,24 @@
 namespace a3 {
 
 constexpr int T_R = 7;               // fast path radius (threshold_window = 7)
-#ifdef A3_TUNING
-static __device__ unsigned long long* g_k1_stamps = nullptr;   // per translation unit; k_threshold.hip's copy (radius 7) is the one a3_debug_set_k1_stamps sets
-#endif
-#ifndef A3_T_LPX
-#define A3_T_LPX 16
-#endif
-#ifndef A3_T_PF
-#define A3_T_PF 3
-#endif
-#ifndef A3_T_RECOMPUTE
-#define A3_T_RECOMPUTE 0
-#endif
-#ifndef A3_T_WAVES
-#define A3_T_WAVES ((A3_T_LPX == 8 || A3_T_RECOMPUTE) ? 3 : 2)
-#endif
-// Pixels per lane and row.  16 (the default): 256 VGPRs (the ring of row sums alone is 120), two waves per SIMD.  8: every
-// per-lane array halves, 144 VGPRs, three waves per SIMD -- built to see whether occupancy was what kept the kernel (stores off)
-// 0.025 ms above the bare reads of tools/micro/readbench.hip.  It was not: 0.293 ms against 0.286 with stores off, 0.343 against
-// 0.324 with them (tools/attic/tune_k1.sh); the difference to the microbenchmark is the 5 % of halo rows and the feeder lanes.
-constexpr int T_LPX = A3_T_LPX;
-static_assert(T_LPX == 8 || T_LPX == 16, "a lane owns 8 or 16 consecutive pixels");
+// Pixels per lane and row: 256 VGPRs (the ring of row sums alone is 120), two waves per SIMD.  8 pixels per lane (144 VGPRs, three
+// waves per SIMD) was built to see whether occupancy was what kept the kernel (stores off) 0.025 ms above the bare reads of
+// tools/micro/readbench.hip.  It was not: 0.293 ms against 0.286 with stores off, 0.343 against 0.324 with them (docs/HISTORY.md
+// A.1); the difference to the microbenchmark is the 5 % of halo rows and the feeder lanes.
+constexpr int T_LPX = 16;
+constexpr int T_PF = 3;              // rows of loads in flight per lane
+constexpr int T_WAVES = 2;           // waves per SIMD (__launch_bounds__); every resident wave's LDS parking area must fit the CU
 constexpr int T_NG = T_LPX / 4;      // grey dwords per lane and row
 constexpr int T_NP = T_LPX / 2;      // packed pairs per lane and row: pixel j with pixel j + T_NP
 constexpr int T_OUT = 62 * T_LPX;    // output columns per wave (lanes 0 and 63 only feed their neighbours)
-typedef typename std::conditional<T_LPX == 16, uint16_t, uint8_t>::type out_bits_t;   // a lane's result bits of one row
+typedef uint16_t out_bits_t;         // a lane's result bits of one row
 
-
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u16x2 as_pk(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
-__device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
-// packed u16 pairs in one dword: v_pk_add_u16 / v_pk_sub_u16 / v_pk_mad_u16 / v_pk_sub_u16 clamp / v_pk_min_u16
-// Sums of pairs: both halves at once with the plain 32-bit add / subtract.  No half ever carries into or borrows from the other --
-// every partial result is a true window sum (0 .. 15 * 15 * 255 + 15 * 255 = 61 200 < 2^16), and the add comes before the subtract
-// -- and v_add_u32 / v_sub_u32 issue at the SIMD's full rate (2 cycles per wave64) where v_pk_add_u16 / v_pk_sub_u16 take 4
-// (tools/micro/valubench.hip).  -DA3_T_ADD32=0 restores the packed forms.
-#ifndef A3_T_ADD32
-#define A3_T_ADD32 1
-#endif
-// -DA3_T_WIDE_FLUSH=1 (round 5, measured): the parked result bits leave in 16-byte stores, eight rows per store
-// instruction (lanes 8j .. 8j+7 write row j's 124 bytes), instead of one 2-byte store per lane and row: 18 store instructions per
-// burst of 128 rows instead of 143.
-#ifndef A3_T_WIDE_FLUSH
-#define A3_T_WIDE_FLUSH 0
-#endif
-#ifndef A3_T_LUMA_GROUPS
-#define A3_T_LUMA_GROUPS 1
-#endif
-#ifndef A3_T_COMPARE4
-#define A3_T_COMPARE4 1
-#endif
-#ifndef A3_T_CMP_NOP
-#define A3_T_CMP_NOP "s_nop 0\n\t"
-#endif
-#if A3_T_ADD32
+// Sums of packed u16 pairs: both halves at once with the plain 32-bit add / subtract.  No half ever carries into or borrows from the
+// other -- every partial result is a true window sum (0 .. 15 * 15 * 255 + 15 * 255 = 61 200 < 2^16), and the add comes before the
+// subtract -- and v_add_u32 / v_sub_u32 issue at the SIMD's full rate (2 cycles per wave64) where v_pk_add_u16 / v_pk_sub_u16 take 4
+// (tools/micro/valubench.hip).
 __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) { return a + b; }
 __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) { return a - b; }
-#else
-__device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) { return as_u32(as_pk(a) + as_pk(b)); }
-__device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) { return as_u32(as_pk(a) - as_pk(b)); }
-#endif
-// The compare stage is written with these three as inline assembly: given the vector expressions the optimiser rewrites
-// min(sat(T - S), 1) into two scalar compares, two selects and a re-pack per pair (5x the instructions).
-__device__ __forceinline__ uint32_t pk_mad(uint32_t a, uint32_t b, uint32_t c) {   // a * b + c per half
-    uint32_t r;
-    asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_shift_in(uint32_t acc, uint32_t bit) {      // acc * 2 + bit per half
-    uint32_t r;
-    asm("v_pk_mad_u16 %0, %1, 2, %2 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(acc), "v"(bit));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_nonzero_diff(uint32_t t, uint32_t s) {      // min(saturating t - s, 1) per half: 1 iff s < t
-    uint32_t d;
-    asm("v_pk_sub_u16 %0, %1, %2 clamp\n\tv_pk_min_u16 %0, %0, 1 op_sel_hi:[1,0]" : "=v"(d) : "v"(t), "v"(s));
-    return d;
-}
-
-// (l * 13743896) >> 32 for l < 2^22: the upper half of floor(l / 10000) == (l * 13743896) >> 37, exact for every such l
-// (checked exhaustively; 429497 >> 32 is NOT exact): one full-rate v_mul_hi_u32_u24, the remaining >> 5 is done by the
-// instruction that puts the byte into place
-template <bool BGR, int BYTE_OFF>
-__device__ __forceinline__ uint32_t luma_hi(uint32_t px) {
-    // pixel in bytes BYTE_OFF .. BYTE_OFF+2 of px (the other byte has weight 0).  Byte-wise dot products with the split
-    // weights 2126 = 8*256+78, 7152 = 27*256+240, 722 = 2*256+210; the first byte is R (RGB/RGBA) or B (BGRA)
-    constexpr uint32_t wlo = (BGR ? 0x004EF0D2u : 0x00D2F04Eu) << (8 * BYTE_OFF), whi = (BGR ? 0x00081B02u : 0x00021B08u) << (8 * BYTE_OFF);
-    const uint32_t lo = __builtin_amdgcn_udot4(px, wlo, 0u, false);
-    const uint32_t hi = __builtin_amdgcn_udot4(px, whi, 0u, false);
-    const uint32_t l = lo + (hi << 8);   // <= 10000 * 255 < 2^22
-    __builtin_assume(l < (1u << 22));
-    return (uint32_t)(((uint64_t)l * 13743896ull) >> 32);   // both factors < 2^24: one v_mul_hi_u32_u24
-}
 
 template <int FMT> struct RawRow {
     static constexpr int BPP = FMT == A3_FMT_RGB8 ? 3 : (FMT == A3_FMT_L8 ? 1 : 4);
@@ -153,8 +77,11 @@ __device__ __forceinline__ void grey_row(const RawRow<FMT>& r, uint32_t g[T_NG])
 #pragma unroll
         for (int i = 0; i < T_NG; i++) g[i] = r.d[i];
     } else {
+        // l = 2126 R + 7152 G + 722 B from two byte-wise dot products with the split weights 2126 = 8*256+78, 7152 = 27*256+240,
+        // 722 = 2*256+210 (the first byte is R for RGB/RGBA, B for BGRA).  (l * 13743896) >> 32 for l < 2^22 is the upper half of
+        // floor(l / 10000) == (l * 13743896) >> 37, exact for every such l (checked exhaustively; 429497 >> 32 is NOT exact): one
+        // full-rate v_mul_hi_u32_u24, the remaining >> 5 is done by the instruction that puts the byte into place.
         uint32_t m[T_LPX];   // (l * 13743896) >> 32; grey = m >> 5
-#if A3_T_LUMA_GROUPS
         // Four pixels at a time, stage by stage: the eight dot products, then the four sums, then the four multiplies.  A v_dot4's
         // result is not forwarded to the next two instructions (the compiler pads a closer consumer with s_nop, which costs an issue
         // slot like any instruction: 24 of them per row when every pixel's chain dot -> add -> multiply was emitted on its own);
@@ -189,49 +116,19 @@ __device__ __forceinline__ void grey_row(const RawRow<FMT>& r, uint32_t g[T_NG])
             for (int j = 0; j < 4; j++) m[i0 + j] = (uint32_t)(((uint64_t)lo[j] * 13743896ull) >> 32);
             __builtin_amdgcn_sched_barrier(0);
         }
-#else
-#pragma unroll
-        for (int i = 0; i < T_LPX; i++) {
-            if constexpr (FMT == A3_FMT_RGBA8 || FMT == A3_FMT_BGRA8) m[i] = luma_hi<FMT == A3_FMT_BGRA8, 0>(r.d[i]);
-            else {
-                // RGB8: pixel i starts at byte 3 i.  Pixels 0 and 3 of every group of four lie inside one dword (byte offsets
-                // 0 and 1: the dot weights move instead of the data); pixels 1 and 2 straddle two dwords (one v_alignbit)
-                const int byte = 3 * i, k = byte >> 2, off = byte & 3;   // compile-time after unrolling
-                if (off == 0) m[i] = luma_hi<false, 0>(r.d[k]);
-                else if (off == 1) m[i] = luma_hi<false, 1>(r.d[k]);
-                else m[i] = luma_hi<false, 0>(__builtin_amdgcn_alignbit(r.d[k + 1], r.d[k], 8 * off));
-            }
-        }
-#endif
         // g[q].byte[j] = m[4 q + j] >> 5, the shift writing its byte in place (SDWA dst_sel).  One asm block so that the order
         // is fixed: gfx950 needs one instruction between a dst_sel write of a VGPR and the next read of it (the partial
         // write is not forwarded); consecutive writes of one g[q] are T_NG instructions apart here, and the s_nop covers
         // whatever the compiler schedules right behind the block.
-#define A3_SH(DST, SRC, B, U) "v_lshrrev_b32_sdwa " DST ", %" A3_STR(A3_SHAMT) ", " SRC " dst_sel:BYTE_" #B " dst_unused:UNUSED_" U " src0_sel:DWORD src1_sel:DWORD\n\t"
-        if constexpr (T_LPX == 16) {
-#define A3_SHAMT 4
-#define A3_STR_(x) #x
-#define A3_STR(x) A3_STR_(x)
-            asm(A3_SH("%0", "%5", 0, "PAD") A3_SH("%1", "%9", 0, "PAD") A3_SH("%2", "%13", 0, "PAD") A3_SH("%3", "%17", 0, "PAD")
-                A3_SH("%0", "%6", 1, "PRESERVE") A3_SH("%1", "%10", 1, "PRESERVE") A3_SH("%2", "%14", 1, "PRESERVE") A3_SH("%3", "%18", 1, "PRESERVE")
-                A3_SH("%0", "%7", 2, "PRESERVE") A3_SH("%1", "%11", 2, "PRESERVE") A3_SH("%2", "%15", 2, "PRESERVE") A3_SH("%3", "%19", 2, "PRESERVE")
-                A3_SH("%0", "%8", 3, "PRESERVE") A3_SH("%1", "%12", 3, "PRESERVE") A3_SH("%2", "%16", 3, "PRESERVE") A3_SH("%3", "%20", 3, "PRESERVE")
-                "s_nop 0"
-                : "=&v"(g[0]), "=&v"(g[1]), "=&v"(g[T_NG - 2]), "=&v"(g[T_NG - 1])
-                : "v"(5u), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]), "v"(m[6]), "v"(m[7]), "v"(m[T_LPX - 8]), "v"(m[T_LPX - 7]),
-                  "v"(m[T_LPX - 6]), "v"(m[T_LPX - 5]), "v"(m[T_LPX - 4]), "v"(m[T_LPX - 3]), "v"(m[T_LPX - 2]), "v"(m[T_LPX - 1]));
-#undef A3_SHAMT
-        } else {
-#define A3_SHAMT 2
-            asm(A3_SH("%0", "%3", 0, "PAD") A3_SH("%1", "%7", 0, "PAD")
-                A3_SH("%0", "%4", 1, "PRESERVE") A3_SH("%1", "%8", 1, "PRESERVE")
-                A3_SH("%0", "%5", 2, "PRESERVE") A3_SH("%1", "%9", 2, "PRESERVE")
-                A3_SH("%0", "%6", 3, "PRESERVE") A3_SH("%1", "%10", 3, "PRESERVE")
-                "s_nop 0"
-                : "=&v"(g[0]), "=&v"(g[1])
-                : "v"(5u), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]), "v"(m[6]), "v"(m[7]));
-#undef A3_SHAMT
-        }
+#define A3_SH(DST, SRC, B, U) "v_lshrrev_b32_sdwa " DST ", %4, " SRC " dst_sel:BYTE_" #B " dst_unused:UNUSED_" U " src0_sel:DWORD src1_sel:DWORD\n\t"
+        asm(A3_SH("%0", "%5", 0, "PAD") A3_SH("%1", "%9", 0, "PAD") A3_SH("%2", "%13", 0, "PAD") A3_SH("%3", "%17", 0, "PAD")
+            A3_SH("%0", "%6", 1, "PRESERVE") A3_SH("%1", "%10", 1, "PRESERVE") A3_SH("%2", "%14", 1, "PRESERVE") A3_SH("%3", "%18", 1, "PRESERVE")
+            A3_SH("%0", "%7", 2, "PRESERVE") A3_SH("%1", "%11", 2, "PRESERVE") A3_SH("%2", "%15", 2, "PRESERVE") A3_SH("%3", "%19", 2, "PRESERVE")
+            A3_SH("%0", "%8", 3, "PRESERVE") A3_SH("%1", "%12", 3, "PRESERVE") A3_SH("%2", "%16", 3, "PRESERVE") A3_SH("%3", "%20", 3, "PRESERVE")
+            "s_nop 0"
+            : "=&v"(g[0]), "=&v"(g[1]), "=&v"(g[2]), "=&v"(g[3])
+            : "v"(5u), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]), "v"(m[6]), "v"(m[7]), "v"(m[8]), "v"(m[9]),
+              "v"(m[10]), "v"(m[11]), "v"(m[12]), "v"(m[13]), "v"(m[14]), "v"(m[15]));
 #undef A3_SH
     }
 }
@@ -282,15 +179,9 @@ __device__ __forceinline__ void row_sums(const uint32_t g[T_NG], uint32_t Hp[T_N
     uint32_t ha, hb;
     if constexpr (R == 7) {
         // the two chains start at pixels 0 and T_NP: bytes p-7 .. p+7 = bytes 1..3 of D[(p + 1) >> 2] and the three dwords behind it
-        if constexpr (T_LPX == 16) {
-            const uint32_t mid = __builtin_amdgcn_sad_u8(D[3], 0u, 0u);                               // pixels 4..7, in both
-            ha = __builtin_amdgcn_sad_u8(D[2], 0u, __builtin_amdgcn_sad_u8(D[1], 0u, __builtin_amdgcn_sad_u8(D[0] & 0xFFFFFF00u, 0u, mid)));
-            hb = __builtin_amdgcn_sad_u8(D[5], 0u, __builtin_amdgcn_sad_u8(D[4], 0u, __builtin_amdgcn_sad_u8(D[2] & 0xFFFFFF00u, 0u, mid)));
-        } else {
-            const uint32_t mid = __builtin_amdgcn_sad_u8(D[3], 0u, __builtin_amdgcn_sad_u8(D[2], 0u, 0u));   // pixels 0..7, in both
-            ha = __builtin_amdgcn_sad_u8(D[1], 0u, __builtin_amdgcn_sad_u8(D[0] & 0xFFFFFF00u, 0u, mid));
-            hb = __builtin_amdgcn_sad_u8(D[4], 0u, __builtin_amdgcn_sad_u8(D[1] & 0xFFFFFF00u, 0u, mid));
-        }
+        const uint32_t mid = __builtin_amdgcn_sad_u8(D[3], 0u, 0u);                               // pixels 4..7, in both
+        ha = __builtin_amdgcn_sad_u8(D[2], 0u, __builtin_amdgcn_sad_u8(D[1], 0u, __builtin_amdgcn_sad_u8(D[0] & 0xFFFFFF00u, 0u, mid)));
+        hb = __builtin_amdgcn_sad_u8(D[5], 0u, __builtin_amdgcn_sad_u8(D[4], 0u, __builtin_amdgcn_sad_u8(D[2] & 0xFFFFFF00u, 0u, mid)));
     } else {   // pixel p is byte p + 8: chain a sums bytes 8-R .. 8+R, chain b bytes 8+T_NP-R .. 8+T_NP+R
         ha = sum_bytes<8 - R, 8 + R>(D, 0u);
         hb = sum_bytes<8 + T_NP - R, 8 + T_NP + R>(D, 0u);
@@ -312,8 +203,8 @@ __device__ __forceinline__ void row_sums(const uint32_t g[T_NG], uint32_t Hp[T_N
 // a multiple of the load queue's depth, and the row loop is unrolled NRING times: the ring slot (row % NRING) and the queue slot
 // (row % T_PF) of every row are then compile-time constants, and the row that leaves the window -- NR rows old -- sits in slot
 // (row - NR) % NRING (for the default radius NR = NRING = 15: the very slot the new row overwrites).
-template <int FMT, bool FAST, int T_PF = A3_T_PF, int R = T_R>
-__global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_t* __restrict__ pixels, size_t row_stride, size_t frame_stride,
+template <int FMT, bool FAST, int R = T_R>
+__global__ __launch_bounds__(64, T_WAVES) void k_grey_threshold7(const uint8_t* __restrict__ pixels, size_t row_stride, size_t frame_stride,
                                                         int W, int H, int rows_per_wave, int strips_y, int n_pairs,
                                                         uint8_t* __restrict__ grey,
                                                         uint8_t* __restrict__ bits, int aligned_in, int aligned_out, int map_by_frame,
@@ -339,9 +230,6 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
         sy = idx % strips_y;
     } else { pair = (k / strips_y) * 8 + xcd; sy = k % strips_y; }
     if (pair >= n_pairs) return;
-#ifdef A3_TUNING
-    const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();   // (tools/attic/k1_wave_times.py: when a launch's waves start and end)
-#endif
     const int sx = pair % strips_x;
     const uint32_t f = pair / strips_x;
     const uint8_t* frame = pixels + (size_t)f * frame_stride;
@@ -368,9 +256,8 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
     uint32_t ay_cur = 0;
     uint32_t gring[NRING][T_NG];  // grey rows; row `it` lives in slot it % NRING (static: the row loop is unrolled); a row is read
                                // again R iterations later, so only R + 1 of the slots are live at any time
-#if !A3_T_RECOMPUTE
-    uint32_t hring[NRING][T_NP];  // the last NRING rows of horizontal sums (pairs); the window's oldest is NR rows back
-#endif
+    uint32_t hring[NRING][T_NP];  // the last NRING rows of horizontal sums (pairs); the window's oldest is NR rows back.  Forming
+                                  // the oldest row's sums again from its grey bytes instead (round 4: 176 VGPRs) was slower.
     uint32_t S[T_NP];          // NR x NR window sums of the row R iterations old (pairs)
 #pragma unroll
     for (int i = 0; i < T_NP; i++) S[i] = 0u;
@@ -378,10 +265,8 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
     for (int q = 0; q < NRING; q++) {
 #pragma unroll
         for (int i = 0; i < T_NG; i++) gring[q][i] = 0u;
-#if !A3_T_RECOMPUTE
 #pragma unroll
         for (int i = 0; i < T_NP; i++) hring[q][i] = 0u;
-#endif
     }
 
     // Odd strips walk upwards.  Strip k (going down) and strip k+1 (going up) then both reach their common boundary --
@@ -390,27 +275,9 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
     // the XCD's L2 instead of fetching them again from HBM.  The box filter is symmetric, so direction only changes
     // the order rows enter and leave the window.
     const int dir = (sy & 1) ? -1 : 1;
-    // the parked rows [0, nb) (row q is image row yb0 + dir * q) leave for the packed image
+    // the parked rows [0, nb) (row q is image row yb0 + dir * q) leave for the packed image, one 2-byte store per lane and row
+    // (16-byte stores, eight rows per instruction, were bit-exact and 2-3 % slower in round 5)
     auto flush_parked = [&](int nb, int yb0) {
-#if A3_T_WIDE_FLUSH
-        if constexpr (sizeof(out_bits_t) == 2) {
-            // bytes of a row this strip owns: 2 per owner lane (lanes 1 .. 62 whose columns start inside the image)
-            const int first_x = sx * T_OUT, n_own = min(62, (W - first_x + T_LPX - 1) / T_LPX);
-            const int row_bytes = 2 * n_own, c = lane & 7, qo = lane >> 3;
-            typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-            uint8_t* const dst0 = bout + (first_x >> 3) + 16 * c;
-            const uint8_t* const src0 = reinterpret_cast<const uint8_t*>(s_out) + 16 * c;
-            for (int q0 = 0; q0 < nb; q0 += 8) {
-                const int q = q0 + qo;
-                if (q >= nb || 16 * c >= row_bytes) continue;
-                uint8_t* dst = dst0 + (size_t)(yb0 + dir * q) * bpr;
-                const uint8_t* src = src0 + (size_t)q * 128;
-                if (16 * c + 16 <= row_bytes) *reinterpret_cast<u32x4_a4*>(dst) = *reinterpret_cast<const u32x4_a4*>(src);
-                else for (int b = 0; 16 * c + b < row_bytes; b += 2) *reinterpret_cast<uint16_t*>(dst + b) = *reinterpret_cast<const uint16_t*>(src + b);
-            }
-            return;
-        }
-#endif
         if (owner)
             for (int q = 0; q < nb; q++)
                 *reinterpret_cast<out_bits_t*>(bout + (size_t)(yb0 + dir * q) * bpr + (x0 >> 3)) = s_out[q * 64 + lane];
@@ -455,8 +322,7 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
             if (write_grey && owner && r >= y_begin && r < y_end) {
                 uint8_t* dst = gout + (size_t)r * W + x0;
                 if (FAST || (aligned_out && x0 + T_LPX <= W)) {
-                    if constexpr (T_LPX == 16) *reinterpret_cast<uint4*>(dst) = make_uint4(g[0], g[1], g[T_NG - 2], g[T_NG - 1]);
-                    else *reinterpret_cast<uint2*>(dst) = make_uint2(g[0], g[1]);
+                    *reinterpret_cast<uint4*>(dst) = make_uint4(g[0], g[1], g[2], g[3]);
                 } else {
 #pragma unroll
                     for (int i = 0; i < T_LPX; i++) if (x0 + i < W) dst[i] = (uint8_t)(g[i >> 2] >> (8 * (i & 3)));
@@ -466,17 +332,8 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
             // entered 15 iterations ago (they never underflow: the add comes first and the true sum is >= 0)
             uint32_t Hn[T_NP];
             row_sums<R>(g, Hn);
-#if A3_T_RECOMPUTE
-            {   // the sums of the row that leaves the window are formed again from its grey bytes (slot k15 still holds that row)
-                uint32_t Ho[T_NP];
-                row_sums<R>(gring[kold], Ho);
-#pragma unroll
-                for (int j = 0; j < T_NP; j++) S[j] = pk_sub(pk_add(S[j], Hn[j]), Ho[j]);
-            }
-#else
 #pragma unroll
             for (int j = 0; j < T_NP; j++) { S[j] = pk_sub(pk_add(S[j], Hn[j]), hring[kold][j]); hring[k15][j] = Hn[j]; }
-#endif
 #pragma unroll
             for (int i = 0; i < T_NG; i++) gring[k15][i] = g[i];
             const uint32_t* centre = gring[(k15 + NRING - R) % NRING];   // the row R iterations old: the one being thresholded
@@ -491,18 +348,13 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
                     area[j] = mul24((axp[j >> 3] >> (4 * (j & 7))) & 15u, ay) | (mul24((axp[(j + T_NP) >> 3] >> (4 * ((j + T_NP) & 7))) & 15u, ay) << 16);
             }
             // white iff S < (L + 1) * area, two pixels per instruction: T = L * area + area, d = saturating T - S (non-zero
-            // iff S < T), bit = min(d, 1), shifted in from the last pair down to the first: acc = acc * 2 + bit
+            // iff S < T), bit = min(d, 1); bit j of each half of acc is pair j's
             uint32_t acc = 0u;
-#if defined(A3_TUNING) && defined(A3_K1_PROBE_SKIP_COMPARE)
-            // timing probe (wrong results): the compare stage's 40 instructions per row replaced by 8 that keep S and the centre row alive
-#pragma unroll
-            for (int j = 0; j < T_NP; j++) acc ^= S[j] + centre[j & (T_NG - 1)];
-#else
-#if A3_T_COMPARE4
-            // four pairs per asm block, stage by stage (4 x T = L * area + area, 4 x saturating T - S, 4 x min(.., 1), then the four
-            // bits of each half combined by a tree: b1 * 2 + b0, b3 * 2 + b2, then * 4 +): no instruction directly behind the one
-            // whose result it reads, and two asm blocks per row instead of twenty-four (the compiler pads an asm statement it cannot
-            // see into with s_nop, which costs an issue slot each)
+            // Inline assembly: given the vector expressions the optimiser rewrites min(sat(T - S), 1) into two scalar compares, two
+            // selects and a re-pack per pair (5x the instructions).  Four pairs per asm block, stage by stage (4 x T = L * area + area,
+            // 4 x saturating T - S, 4 x min(.., 1), then the four bits of each half combined by a tree: b1 * 2 + b0, b3 * 2 + b2, then
+            // * 4 +): no instruction directly behind the one whose result it reads, and two asm blocks per row instead of twenty-four
+            // (the compiler pads an asm statement it cannot see into with s_nop, which costs an issue slot each)
             {
                 uint32_t part[T_NP / 4];
 #pragma unroll
@@ -525,7 +377,7 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
                         "v_pk_min_u16 %3, %3, 1 op_sel_hi:[1,0]\n\t"
                         "v_pk_mad_u16 %1, %1, 2, %0 op_sel_hi:[1,0,1]\n\t"
                         "v_pk_mad_u16 %3, %3, 2, %2 op_sel_hi:[1,0,1]\n\t"
-                        A3_T_CMP_NOP
+                        "s_nop 0\n\t"
                         "v_pk_mad_u16 %4, %3, 4, %1 op_sel_hi:[1,0,1]"
                         : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(part[q])
                         : "v"(Lp[0]), "v"(Lp[1]), "v"(Lp[2]), "v"(Lp[3]), "v"(area[4 * q]), "v"(area[4 * q + 1]), "v"(area[4 * q + 2]), "v"(area[4 * q + 3]),
@@ -535,31 +387,13 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
 #pragma unroll
                 for (int q = 1; q < T_NP / 4; q++) acc |= part[q] << (4 * q);
             }
-#else
-#pragma unroll
-            for (int j = T_NP - 1; j >= 0; j--) {
-                const uint32_t Lp = byte_pair(j, centre[(j + T_NP) >> 2], centre[j >> 2]);
-                const uint32_t T = pk_mad(Lp, area[j], area[j]);
-                acc = pk_shift_in(acc, pk_nonzero_diff(T, S[j]));
-            }
-#endif
-#endif
             // the bits of pixels 0 .. T_NP-1 sit in the low half of acc, those of pixels T_NP .. in the high half
-            const uint32_t outb = T_LPX == 16 ? __builtin_amdgcn_perm(0u, acc, 0x0C0C0200u) : ((acc | (acc >> 12)) & 0xFFu);
+            const uint32_t outb = __builtin_amdgcn_perm(0u, acc, 0x0C0C0200u);
             if (flush_rows <= 0) {
-#ifdef A3_TUNING
-                if (owner && (flush_rows == 0 || outb == 0x12345u))   // (-1: timing probe, no stores)
-#else
-                if (owner)
-#endif
-                    *reinterpret_cast<out_bits_t*>(bout + (size_t)y * bpr + (x0 >> 3)) = (out_bits_t)outb;
+                if (owner) *reinterpret_cast<out_bits_t*>(bout + (size_t)y * bpr + (x0 >> 3)) = (out_bits_t)outb;
             } else {
                 if (n_buf == 0) y_buf0 = y;
-#if A3_T_WIDE_FLUSH
-                s_out[n_buf * 64 + (sizeof(out_bits_t) == 2 ? ((lane + 63) & 63) : lane)] = (out_bits_t)outb;   // owners 1..62 at slots 0..61: a row's bytes as they lie in memory
-#else
                 s_out[n_buf * 64 + lane] = (out_bits_t)outb;
-#endif
                 n_buf++;
             }
         }
@@ -570,21 +404,13 @@ __global__ __launch_bounds__(64, A3_T_WAVES) void k_grey_threshold7(const uint8_
         }
     }
     if (flush_rows > 0) flush_parked(n_buf, y_buf0);
-#ifdef A3_TUNING
-    if (g_k1_stamps && lane == 0) {   // 100 MHz timestamps of this wave's life + where it ran (HW_ID, XCC_ID)
-        unsigned long long* o = g_k1_stamps + (size_t)blockIdx.x * 4;
-        o[0] = t_begin; o[1] = __builtin_amdgcn_s_memrealtime();
-        o[2] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));    // HW_REG_HW_ID, 32 bits
-        o[3] = (unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));   // HW_REG_XCC_ID
-    }
-#endif
 }
 
 // the register-resident kernel for one radius R in 1..7 (the default, 7, is the one every figure of DESIGN.md is about)
 template <int R>
 hipError_t launch_k1(hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H, uint32_t n,
                             uint8_t* grey, uint64_t* bits) {
-    constexpr int NR = 2 * R + 1, UNROLL = ((NR + A3_T_PF - 1) / A3_T_PF) * A3_T_PF;   // (as in the kernel)
+    constexpr int NR = 2 * R + 1, UNROLL = ((NR + T_PF - 1) / T_PF) * T_PF;   // (as in the kernel)
     const int aligned_in = ((uintptr_t)pixels % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0);
     const int aligned_out = (W % 16 == 0) && ((uintptr_t)grey % 16 == 0);
     uint8_t* bin = reinterpret_cast<uint8_t*>(bits);
@@ -593,12 +419,12 @@ hipError_t launch_k1(hipStream_t st, const uint8_t* pixels, int fmt, size_t row_
         if (e != hipSuccess) return e;
     }
     // Rows per wave.  Every wave also reads and converts 2R rows outside its strip, so strips should be tall; but the
-    // chip holds 256 CUs x 4 SIMDs x A3_T_WAVES waves at once and a launch runs in whole rounds of that many, so the
+    // chip holds 256 CUs x 4 SIMDs x T_WAVES waves at once and a launch runs in whole rounds of that many, so the
     // number of strips should fill the last round.  Model: time ~ rounds x (rows per strip + 2R); take the best
     // strip count (at least 16 rows per strip).  256 frames of 1920x1080, R = 7: 2 column strips x 4 strips of 270 rows = 2048 waves
     // = exactly one round of two waves per SIMD.
     const int strips_x = (W + T_OUT - 1) / T_OUT;
-    const long long slots = 256 * 4 * A3_T_WAVES, cols = (long long)strips_x * n;
+    const long long slots = 256 * 4 * T_WAVES, cols = (long long)strips_x * n;
     // (Strips of ONE row for a single small frame -- 480 waves of one 15-row block instead of 30 waves of two -- were tried in round 5:
     // 23.0 us against 16.8 for one 640x480 frame; a wave's fixed costs outweigh the block saved.  The model stays at >= 16 rows.)
     int best_sy = 1; double best_cost = 1e300;
@@ -608,28 +434,23 @@ hipError_t launch_k1(hipStream_t st, const uint8_t* pixels, int fmt, size_t row_
         const double cost = (double)((waves + slots - 1) / slots) * (rows + 2 * R);
         if (cost < best_cost - 1e-9) { best_cost = cost; best_sy = sy; }
     }
-    int rows_per_wave = (H + best_sy - 1) / best_sy;
-    if (const int rv = tuning_knob("A3_ROWS_PER_WAVE", 0); rv > 0) rows_per_wave = rv;   // (-DA3_TUNING builds only)
+    const int rows_per_wave = (H + best_sy - 1) / best_sy;
     const int strips_y = (H + rows_per_wave - 1) / rows_per_wave;
     const int n_pairs = (int)n * strips_x;
     // every strip of a frame on one XCD (1) or every (frame, column strip) pair on its own XCD (0).  By frame is ~3 % faster:
     // the two column strips of a frame overlap by 32 columns and write the same lines of the packed image
-    const int map_by_frame = tuning_knob("A3_K1_MAP", 1);
-    // rows of results a wave parks in LDS before it writes them out (0: store row by row): 128 (+ UNROLL) rows x 64 lanes x 1 or 2
-    // bytes = 9 or 18 KB per wave; twelve resp. eight waves per CU fit the 160 KB
-    // (-1 = "no stores at all" is a timing probe that leaves the binary image stale: it exists in -DA3_TUNING builds only)
-    // (every resident wave's parking area must fit the CU's 160 KB: 4 x A3_T_WAVES waves)
-    constexpr int flush_cap = (160 * 1024 / (4 * A3_T_WAVES)) / (64 * (int)sizeof(out_bits_t)) - UNROLL;
-    const int fv = tuning_knob("A3_K1_FLUSH", flush_cap < 128 ? flush_cap : 128);
-#ifdef A3_TUNING
-    const int flush_rows = fv < 0 ? -1 : std::min(fv, rows_per_wave);
-#else
-    const int flush_rows = std::min(fv < 0 ? 128 : fv, rows_per_wave);
-#endif
+    const int map_by_frame = 1;
+    // rows of results a wave parks in LDS before it writes them out: 128 (+ UNROLL) rows x 64 lanes x 2 bytes = 18 KB per wave, and
+    // every resident wave's parking area must fit the CU's 160 KB (4 x T_WAVES waves)
+    constexpr int kFlushRows = 128;
+    static_assert((kFlushRows + UNROLL) * 64 * (int)sizeof(out_bits_t) * 4 * T_WAVES <= 160 * 1024, "the parked rows fit the LDS");
+    const int flush_rows = std::min(kFlushRows, rows_per_wave);
+    // (The kernel's map_by_frame == 0 branch and its row-by-row stores for flush_rows <= 0 are no longer launched.  Removing them
+    // changes K1's arguments and machine code, so it waits for a change that is timed on the GPU.)
     const size_t lds_bytes = flush_rows > 0 ? (size_t)(flush_rows + UNROLL) * 64 * sizeof(out_bits_t) : 0;
     dim3 grid(map_by_frame ? 8 * (((int)n + 7) / 8) * strips_x * strips_y : 8 * ((n_pairs + 7) / 8) * strips_y), block(64);
     const bool fast = aligned_in && aligned_out;   // W % 16 == 0: a lane's 16 pixels are all inside or all outside
-#define A3_LAUNCH_K1(F, B) hipLaunchKernelGGL((k_grey_threshold7<F, B, A3_T_PF, R>), grid, block, lds_bytes, st, pixels, row_stride, frame_stride, W, H, \
+#define A3_LAUNCH_K1(F, B) hipLaunchKernelGGL((k_grey_threshold7<F, B, R>), grid, block, lds_bytes, st, pixels, row_stride, frame_stride, W, H, \
                                               rows_per_wave, strips_y, n_pairs, grey, bin, aligned_in, aligned_out, map_by_frame, flush_rows)
     if (fmt == A3_FMT_RGB8) { if (fast) A3_LAUNCH_K1(A3_FMT_RGB8, true); else A3_LAUNCH_K1(A3_FMT_RGB8, false); }
     else if (fmt == A3_FMT_RGBA8) { if (fast) A3_LAUNCH_K1(A3_FMT_RGBA8, true); else A3_LAUNCH_K1(A3_FMT_RGBA8, false); }

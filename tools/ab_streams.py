@@ -7,7 +7,7 @@ and its duration alone in the same geometry.
   library sizes K1 for two waves per SIMD -- the field stays so that recorded command lines parse; overlap -1: the library decides per
   batch, its default; 0/1/2: forced through the internal switch)  e.g. own:2:2:0, own:8:2:0:4 (two bursts of
   four, submitted together), own:4:2:0:-1 (rotation with burst gates), own:4:2:0:-1:0 (the same, chains not held back);
-  further fields KEY=VALUE are environment knobs of a -DA3_TUNING build (A3_HIP_LIB), set for that arrangement only"""
+  a further field same=1 makes every context of that arrangement step one shared batch"""
 import sys
 import time
 from pathlib import Path
@@ -16,7 +16,6 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-import os
 
 DEFAULT = "shared:2:2:2,own:2:2:0,own:3:2:0"
 
@@ -35,6 +34,8 @@ def main():
     for s in specs:
         if s.split(":")[2] != "2":
             sys.exit(f"ab_streams.py: spec {s!r}: k1waves must be 2 (K1 is sized for two waves per SIMD; the one-wave geometry was removed)")
+        if any(kv.split("=")[0] != "same" for kv in s.split(":")[6:]):
+            sys.exit(f"ab_streams.py: spec {s!r}: the only field after hold is same=0|1 (the library reads no environment knobs)")
     d = ARDictionary.new_from_named_dict("ARUCO")
     spec, _ = synth.config_spec(2)
     max_ctx = max(int(s.split(":")[1]) for s in specs)
@@ -105,7 +106,6 @@ def main():
 
     host_us = []
     seen = {}
-    knobs_seen = set()
     res = {s: [] for s in specs}
     host = {}
     k1c = {s: [0.0, 0] for s in specs}
@@ -115,15 +115,7 @@ def main():
             kind, nc, _, ov = s.split(":")[:4]
             group = int(s.split(":")[4]) if len(s.split(":")) > 4 else 1
             assert L.a3_debug_set_hold(int(s.split(":")[5]) if len(s.split(":")) > 5 else 1) == 0
-            for kv in knobs_seen:                      # tuning builds read their knobs from the environment at every launch
-                os.environ.pop(kv, None)
-            same_batch[0] = False
-            for kv in s.split(":")[6:]:
-                kname, kval = kv.split("=")
-                if kname == "same":
-                    same_batch[0] = kval == "1"
-                    continue
-                os.environ[kname] = kval; knobs_seen.add(kname)
+            same_batch[0] = any(kv == "same=1" for kv in s.split(":")[6:])
             ctxs = pools[kind][: int(nc)]
             assert L.a3_debug_set_overlap(int(ov)) == 0
             if s not in k1a:   # the threshold kernel alone in this geometry (synchronous calls, nothing else on the GPU)
