@@ -1780,6 +1780,9 @@ __device__ __forceinline__ void contour_quads_body(uint32_t block, uint32_t n_bl
                                                        CandRec* __restrict__ cands, uint32_t* __restrict__ cand_count,
                                                        unsigned int* __restrict__ err_flags, bool coords14) {
     // coords14: every coordinate is below 2^14 (the image is at most 16384 x 16384): the distance numerators fit 32 bits
+    // A border that did not fit the point pool or the contour table still took its slot in ctr->contours, but k_cycle_select never
+    // wrote its record: nothing here may read those (a stale record names points anywhere).  The batch is re-run with larger pools.
+    if (ctr->err_flags & (kErrPointPool | kErrContourTable)) return;
     const uint32_t n_contours = min(ctr->contours, max_contours);
     const int lane = threadIdx.x & (G - 1);
     const uint32_t wave_global = (block * blockDim.x + threadIdx.x) / G, n_waves = (n_blocks * blockDim.x) / G;
