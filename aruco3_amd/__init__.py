@@ -14,7 +14,7 @@ def __getattr__(name):
         from . import aruco
 
         return getattr(aruco, name)
-    if name in ("CameraIntrinsics",):
+    if name in ("CameraIntrinsics", "Distortion", "undistort_points"):
         from . import pinhole
 
         return getattr(pinhole, name)

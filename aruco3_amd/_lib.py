@@ -26,6 +26,7 @@ STEP_WHOLE, STEP_DECODE_DEFERRED, STEP_HELD_RELEASED_BY_LAST, STEP_HELD_RELEASED
 REFINE_NONE, REFINE_SUBPIX = 0, 1
 BOARD_NONE, BOARD_OK = 0, 1
 BOARD_MAX_MARKERS = 1024
+DIST_NONE, DIST_RATIONAL = 0, 1
 STEP_NAMES = {0: "whole", 1: "decode_deferred", 2: "held_released_by_last", 3: "held_released_early", 4: "burst_last", 5: "held"}
 
 # every symbol include/aruco3_hip.h declares
@@ -38,6 +39,7 @@ SYMBOLS = [
     "a3_contour_count", "a3_download_contours", "a3_detection_record_bytes", "a3_pack_detections",
     "a3_default_refine_config", "a3_set_corner_refinement", "a3_get_refined_corners", "a3_refine_corners",
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
+    "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
 INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
@@ -96,6 +98,13 @@ class BoardPoseRec(C.Structure):
     """a3_board_pose: one board pose per frame (an extension beyond the reference; include/aruco3_hip.h states the solve)"""
     _fields_ = [("status", C.c_uint32), ("markers_used", C.c_uint32), ("markers_rejected", C.c_uint32), ("iterations", C.c_uint32),
                 ("rms_px", C.c_float), ("alt_rms_px", C.c_float), ("rotation", C.c_float * 9), ("translation", C.c_float * 3)]
+
+
+class DistortionRec(C.Structure):
+    """a3_distortion: lens distortion, OpenCV's rational model (an extension beyond the reference; include/aruco3_hip.h states it)"""
+    _fields_ = [("model", C.c_uint32), ("iterations", C.c_uint32), ("k1", C.c_float), ("k2", C.c_float), ("p1", C.c_float),
+                ("p2", C.c_float), ("k3", C.c_float), ("k4", C.c_float), ("k5", C.c_float), ("k6", C.c_float),
+                ("max_residual_px", C.c_float)]
 
 
 BOARD_POSE_DTYPE = np.dtype([("status", "<u4"), ("markers_used", "<u4"), ("markers_rejected", "<u4"), ("iterations", "<u4"),
@@ -258,6 +267,15 @@ def load():
         L.a3_get_board_poses.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.a3_estimate_board_pose.restype = C.c_int
         L.a3_estimate_board_pose.argtypes = [vp, u32p, f32p, C.c_size_t, C.POINTER(Intrinsics), C.c_uint32, C.c_uint32, C.POINTER(BoardPoseRec)]
+    if hasattr(L, "a3_set_distortion"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack lens distortion)
+        L.a3_default_distortion.restype = None
+        L.a3_default_distortion.argtypes = [C.POINTER(DistortionRec)]
+        L.a3_set_distortion.restype = C.c_int
+        L.a3_set_distortion.argtypes = [vp, C.POINTER(DistortionRec)]
+        L.a3_get_undistorted_corners.restype = C.c_int
+        L.a3_get_undistorted_corners.argtypes = [vp, f32p, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.a3_undistort_points.restype = C.c_int
+        L.a3_undistort_points.argtypes = [vp, f32p, C.c_size_t, C.POINTER(Intrinsics), C.POINTER(DistortionRec), f32p, f32p]
     L.a3_debug_discard_too_near.restype = C.c_int
     L.a3_debug_discard_too_near.argtypes = [vp, u32p, C.c_size_t, C.c_float, u32p, C.POINTER(C.c_size_t)]
     _lib = L
@@ -316,6 +334,12 @@ def default_refine_config() -> RefineConfig:
     cfg = RefineConfig()
     load().a3_default_refine_config(C.byref(cfg))
     return cfg
+
+
+def default_distortion() -> DistortionRec:
+    d = DistortionRec()
+    load().a3_default_distortion(C.byref(d))
+    return d
 
 
 def synth_render(device: int, frames: np.ndarray, markers: np.ndarray, width: int, height: int, paper: bool, black: float, white: float,
@@ -520,6 +544,33 @@ class Context:
         out = np.zeros(1, dtype=BOARD_POSE_DTYPE)
         C.memmove(out.ctypes.data, C.addressof(rec), C.sizeof(rec))
         return out[0]
+
+    # ---- lens distortion ----
+    def set_distortion(self, d: "DistortionRec" = None):
+        """a3_set_distortion: None (or model DIST_NONE) clears it; applies to pose batches submitted afterwards"""
+        check(load().a3_set_distortion(self.handle, C.byref(d) if d is not None else None), self.handle)
+
+    def undistorted_corners(self):
+        """a3_get_undistorted_corners: (float32 [n_markers, 4, 2] corners, float32 [n_markers, 4] residuals in px) of the last
+        collected batch, in marker order"""
+        n = C.c_size_t()
+        L = load()
+        rc = L.a3_get_undistorted_corners(self.handle, None, None, 0, C.byref(n))
+        if rc not in (OK, ERR_CAPACITY):
+            check(rc, self.handle)
+        out = np.zeros((max(n.value, 1), 4, 2), dtype=np.float32)
+        res = np.zeros((max(n.value, 1), 4), dtype=np.float32)
+        check(L.a3_get_undistorted_corners(self.handle, _p(out, C.c_float), _p(res, C.c_float), max(n.value, 1), C.byref(n)), self.handle)
+        return out[: n.value], res[: n.value]
+
+    def undistort_points(self, points: np.ndarray, intrinsics: "Intrinsics", d: "DistortionRec"):
+        """a3_undistort_points (stand-alone): points (..., 2) pixels -> (float32 (n, 2) undistorted pixels, float32 (n,) residuals)"""
+        xy = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 2))
+        out = np.zeros_like(xy)
+        res = np.zeros(xy.shape[0], dtype=np.float32)
+        check(load().a3_undistort_points(self.handle, _p(xy, C.c_float), xy.shape[0], C.byref(intrinsics), C.byref(d), _p(out, C.c_float),
+                                         _p(res, C.c_float)), self.handle)
+        return out, res
 
     # ---- Detection.grey / thresholded / candidates / homographies of the last batch ----
     def download_grey(self, frame: int, w: int, h: int, thresholded: bool = False) -> np.ndarray:

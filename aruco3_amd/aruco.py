@@ -48,12 +48,15 @@ class CornerRefinement:
 
 @dataclass
 class Marker:
-    """src/aruco.rs:8-13, plus the refined corners when the detector refines them (an extension; None otherwise)"""
+    """src/aruco.rs:8-13, plus the refined corners when the detector refines them and the undistorted corners (with their residuals in
+    pixels, +inf: not undistorted) when a pose call's intrinsics carry a lens distortion (extensions; None otherwise)"""
     id: int
     code: int
     corners: List[Tuple[int, int]]
     hamming_distance: int
     corners_refined: Optional[List[Tuple[float, float]]] = None
+    corners_undistorted: Optional[List[Tuple[float, float]]] = None
+    undistort_residual_px: Optional[List[float]] = None
 
 
 @dataclass
@@ -128,6 +131,12 @@ class Detector:
             self._board_applied = (ctx, b)
         return b is not None
 
+    def _apply_distortion(self, ctx: _lib.Context, intrinsics) -> bool:
+        """hands the lens distortion of a pose call's intrinsics to the context before the call -> whether it is on"""
+        d = getattr(intrinsics, "distortion", None) if intrinsics is not None else None
+        ctx.set_distortion(d._c() if d is not None else None)
+        return d is not None
+
     def _context(self) -> _lib.Context:
         key = (tuple(vars(self.config).items()), id(self.dictionary), self.device)
         if self._ctx is None or self._ctx_key != key:
@@ -181,19 +190,21 @@ class Detector:
             ctx.set_stream(stream)
         ctx.set_debug_taps(False)
         refine = self._apply_refinement(ctx)
+        dist = self._apply_distortion(ctx, intrinsics)
         intr = None
         if intrinsics is not None:
             ci = intrinsics
             intr = _lib.Intrinsics(ci.image_width, ci.image_height, ci.focal_x, ci.focal_y, ci.principal_x, ci.principal_y)
         markers, per, poses = ctx.detect_batch_pose(ptr, mem, fmt, w, h, rs, fs, n, marker_size_mm, intr, out_cap)
         refined = ctx.refined_corners() if refine else None
+        undist = ctx.undistorted_corners() if dist else None
         out = []
         pos = 0
         for f in range(n):
             det = Detection()
             pp = []
             for i in range(pos, pos + int(per[f])):
-                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None))
+                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i)))
                 pp.append(tuple(MarkerPose(float(q[0]), q[1:10].reshape(3, 3).copy(), q[10:13].copy()) for q in poses[i]))
             pos += int(per[f])
             out.append((det, pp))
@@ -213,6 +224,7 @@ class Detector:
             ctx.set_stream(stream)
         ctx.set_debug_taps(False)
         refine = self._apply_refinement(ctx)
+        dist = self._apply_distortion(ctx, intrinsics)
         self._apply_board(ctx)
         intr = None
         if intrinsics is not None:
@@ -220,8 +232,9 @@ class Detector:
             intr = _lib.Intrinsics(ci.image_width, ci.image_height, ci.focal_x, ci.focal_y, ci.principal_x, ci.principal_y)
         markers, per, _ = ctx.detect_batch_pose(ptr, mem, fmt, w, h, rs, fs, n, marker_size_mm, intr, out_cap)
         refined = ctx.refined_corners() if refine else None
+        undist = ctx.undistorted_corners() if dist else None
         boards = ctx.board_poses()
-        return [(d, BoardPose._from(boards[f])) for f, d in enumerate(_detections(markers, per, refined))]
+        return [(d, BoardPose._from(boards[f])) for f, d in enumerate(_detections(markers, per, refined, undist))]
 
     def detect_batch_raw(self, images, stream: int = None, out_cap: int = 0):
         """Batch entry without Python object construction: (structured marker array, per-frame counts)."""
@@ -233,18 +246,25 @@ class Detector:
         return ctx.detect_batch(ptr, mem, fmt, w, h, rs, fs, n, out_cap)
 
 
-def _marker(m, refined=None) -> Marker:
+def _marker(m, refined=None, undist=None) -> Marker:
     c = m["corners"]
     return Marker(int(m["id"]), int(m["code"]), [(int(c[2 * i]), int(c[2 * i + 1])) for i in range(4)], int(m["hamming_distance"]),
-                  None if refined is None else [(float(x), float(y)) for x, y in refined])
+                  None if refined is None else [(float(x), float(y)) for x, y in refined],
+                  None if undist is None else [(float(x), float(y)) for x, y in undist[0]],
+                  None if undist is None else [float(r) for r in undist[1]])
 
 
-def _detections(markers, per, refined=None) -> List[Detection]:
+def _undist_at(undist, i):
+    """marker i's (corners, residuals) of Context.undistorted_corners(), or None"""
+    return None if undist is None else (undist[0][i], undist[1][i])
+
+
+def _detections(markers, per, refined=None, undist=None) -> List[Detection]:
     out, pos = [], 0
     for f in range(len(per)):
         det = Detection()
         for i in range(pos, pos + int(per[f])):
-            det.markers.append(_marker(markers[i], refined[i] if refined is not None else None))
+            det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i)))
         pos += int(per[f])
         out.append(det)
     return out

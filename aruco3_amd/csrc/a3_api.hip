@@ -71,6 +71,8 @@ size_t board_slot_bytes();
 void board_slot_from(const float*, void*);
 hipError_t launch_board_pose(hipStream_t, const a3_marker*, const uint32_t*, const float*, const float*, const unsigned int*, const uint32_t*,
                              uint32_t, uint32_t, const uint16_t*, uint32_t, const void*, const a3_intrinsics*, uint32_t, uint32_t, a3_board_pose*);
+hipError_t launch_undistort_corners(hipStream_t, const a3_marker*, const float*, const unsigned int*, uint32_t, const a3_intrinsics&,
+                                    const a3_distortion&, float*, float*);
 hipError_t launch_calc_tau(hipStream_t, const uint64_t*, uint32_t, unsigned int*);
 hipError_t launch_synth_render(hipStream_t, const a3_synth_frame*, uint32_t, const a3_synth_marker*, uint32_t, uint32_t, int, float, float, int,
                                uint8_t*, size_t, size_t);
@@ -137,6 +139,8 @@ struct Batch {
     a3_refine_config refine{};   // corner refinement (method NONE: none)
     size_t refine_bytes = 0;     // 32 (8 floats per marker) with refinement, else 0
     bool board = false;          // a pose batch with a board set: k_board_pose runs behind k_pose
+    a3_distortion dist{};        // lens distortion (model NONE: none)
+    size_t undist_bytes = 0;     // 48 (8 corner floats + 4 residuals per marker) on a pose batch with distortion, else 0
     bool taps = false;           // debug taps: grey plane, patches, contours and the per-frame candidate counts are kept
     int profiling = 0, profile_every = 1;   // a3_set_profiling in force
     // enqueue_front
@@ -262,6 +266,12 @@ struct a3_ctx {
     DevBuf board_slot_of, board_slot_rec, board_buf;   // id -> slot (n_codes x u16), slot records, board poses of the last batch (per frame)
     std::vector<a3_board_pose> h_board;
     bool board_valid = false;   // the last collected batch was a pose batch with a board: h_board holds its poses
+    // a3_set_distortion: the setting later pose batches capture; undist_buf holds the undistorted corners of the last batch on the
+    // device: [marker_cap x 8 floats | marker_cap x 4 residuals]
+    a3_distortion dist{};
+    DevBuf undist_buf;
+    std::vector<float> h_undist, h_undist_res;
+    bool undist_valid = false;  // the last collected batch ran with distortion: h_undist / h_undist_res hold its corners
     void* pinned = nullptr;
     size_t pinned_cap = 0;
     // debug taps: per-frame candidate counts of the last batch (before / after discard_too_near), read back with the results so
@@ -458,17 +468,22 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     if (b.refine_bytes)   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
         A3_HIP(launch_refine_corners(st, b.src, b.W, b.H, ctx->markers_ptr, d_marker_total, nullptr, nullptr, b.marker_cap,
                                      refine_params_for(ctx, b.refine), ctx->refined_buf.as<float>()));
+    if (b.undist_bytes)   // undistorted pixel corners of the same markers (of their refined corners with refinement on)
+        A3_HIP(launch_undistort_corners(st, ctx->markers_ptr, b.refine_bytes ? ctx->refined_buf.as<float>() : nullptr, d_marker_total, b.marker_cap,
+                                        b.pose_intr, b.dist, ctx->undist_buf.as<float>(), ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
+    // the float corners the poses are solved from: undistorted, else refined, else none (the integer corners)
+    const float* fcorners = b.undist_bytes ? ctx->undist_buf.as<float>() : b.refine_bytes ? ctx->refined_buf.as<float>() : nullptr;
     if (b.want_pose) {   // IPPE on the device-resident marker list (src/pose.rs:52-81), no extra round trip
         const a3_intrinsics& in = b.pose_intr;
-        if (b.refine_bytes)   // from the refined float corners (k_pose modes 3 / 4)
-            A3_HIP(launch_pose(st, nullptr, 8u, ctx->refined_buf.as<float>(), b.marker_cap, d_marker_total, b.pose_has_intr ? 4 : 3, b.pose_size_mm,
+        if (fcorners)   // from float corners (k_pose modes 3 / 4)
+            A3_HIP(launch_pose(st, nullptr, 8u, fcorners, b.marker_cap, d_marker_total, b.pose_has_intr ? 4 : 3, b.pose_size_mm,
                                (float)b.W, (float)b.H, in.focal_x, in.focal_y, in.principal_x, in.principal_y, ctx->pose_buf.as<a3_pose>()));
         else
             A3_HIP(launch_pose(st, reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(ctx->markers_ptr) + offsetof(a3_marker, corners)),
                                (uint32_t)(sizeof(a3_marker) / 4), nullptr, b.marker_cap, d_marker_total, b.pose_has_intr ? 1 : 0, b.pose_size_mm,
                                (float)b.W, (float)b.H, in.focal_x, in.focal_y, in.principal_x, in.principal_y, ctx->pose_buf.as<a3_pose>()));
         if (b.board)   // one board pose per frame from the same device-resident markers (and refined corners), no extra round trip
-            A3_HIP(launch_board_pose(st, ctx->markers_ptr, nullptr, nullptr, b.refine_bytes ? ctx->refined_buf.as<float>() : nullptr, d_marker_total,
+            A3_HIP(launch_board_pose(st, ctx->markers_ptr, nullptr, nullptr, fcorners, d_marker_total,
                                      ctx->per_frame, b.marker_cap, b.n, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p,
                                      b.pose_has_intr ? &in : nullptr, b.W, b.H, ctx->board_buf.as<a3_board_pose>()));
     }
@@ -484,6 +499,12 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     if (b.board)   // (staged behind the refined corners; one record per frame, whatever the marker count)
         A3_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(h_poses) + (size_t)b.guess * (b.pose_bytes + b.refine_bytes), ctx->board_buf.p,
                               (size_t)b.n * sizeof(a3_board_pose), hipMemcpyDeviceToHost, st));
+    if (b.undist_bytes) {   // (staged behind the board poses: `guess` markers' corners, then their residuals)
+        uint8_t* hu = reinterpret_cast<uint8_t*>(h_poses) + (size_t)b.guess * (b.pose_bytes + b.refine_bytes) + (b.board ? (size_t)b.n * sizeof(a3_board_pose) : 0);
+        A3_HIP(hipMemcpyAsync(hu, ctx->undist_buf.p, (size_t)b.guess * 32, hipMemcpyDeviceToHost, st));
+        A3_HIP(hipMemcpyAsync(hu + (size_t)b.guess * 32, ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8, (size_t)b.guess * 16,
+                              hipMemcpyDeviceToHost, st));
+    }
     if (b.taps) {   // Detection.candidates / .homographies will be asked for frame by frame: their counts travel now
         A3_HIP(hipMemcpyAsync(ctx->pinned_counts, ctx->cand_count, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
         A3_HIP(hipMemcpyAsync((uint8_t*)ctx->pinned_counts + (size_t)b.n * 4, ctx->fin_count.p, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
@@ -585,14 +606,16 @@ uint64_t pool_darts_of(const a3_ctx* ctx, uint64_t max_chunk_darts, size_t n_chu
     }
     return pool_darts;
 }
-// The second half's buffers: poses, refined corners, board poses, pinned staging for the read-back head and `guess` markers (+ poses
+// The second half's buffers: poses, refined corners, board poses, undistorted corners, pinned staging for the read-back head and `guess` markers (+ poses
 // ...; a longer list is fetched by finish_batch after growing it), pinned staging for the tap counts.
 int ensure_back_buffers(a3_ctx* ctx, const Batch& b, size_t head_bytes) {
     const size_t board_bytes = b.board ? (size_t)b.n * sizeof(a3_board_pose) : 0;
     if (b.want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)b.marker_cap * 2 * sizeof(a3_pose)));
     if (b.refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)b.marker_cap * b.refine_bytes));
     if (board_bytes) A3_HIP(ctx->board_buf.ensure(board_bytes));
-    if (int rc = ensure_pinned(ctx, head_bytes + (size_t)b.guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + b.refine_bytes) + board_bytes + (1 << 16))) return rc;
+    if (b.undist_bytes) A3_HIP(ctx->undist_buf.ensure((size_t)b.marker_cap * b.undist_bytes));
+    if (int rc = ensure_pinned(ctx, head_bytes + (size_t)b.guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + b.refine_bytes + b.undist_bytes) + board_bytes +
+                                    (1 << 16))) return rc;
     if (b.taps && ctx->pinned_counts_cap < (size_t)b.n * 8) {
         if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
         ctx->pinned_counts = nullptr; ctx->pinned_counts_cap = 0;
@@ -904,11 +927,14 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     b.active = false;
     hipStream_t st = ctx->stream;
     const size_t ctr_bytes = b.ctr_bytes, head_bytes = b.head_bytes, pose_bytes = b.pose_bytes, n_chunks = b.n_chunks, refine_bytes = b.refine_bytes;
+    const size_t undist_bytes = b.undist_bytes, board_bytes = b.board ? (size_t)b.n * sizeof(a3_board_pose) : 0;
     const uint32_t guess = b.guess, n = b.n;
     uint8_t* hp = (uint8_t*)ctx->pinned;
     a3_marker* h_markers = reinterpret_cast<a3_marker*>(hp + head_bytes);
     a3_pose* h_poses = reinterpret_cast<a3_pose*>(hp + head_bytes + (size_t)guess * sizeof(a3_marker));
     const float* h_refined = reinterpret_cast<const float*>(hp + head_bytes + (size_t)guess * (sizeof(a3_marker) + pose_bytes));
+    const float* h_undist = reinterpret_cast<const float*>(hp + head_bytes + (size_t)guess * (sizeof(a3_marker) + pose_bytes + refine_bytes) + board_bytes);
+    const float* h_undist_res = h_undist + (size_t)guess * 8;
     {   // nobody submitted behind this batch: its decode stage goes out now
         std::lock_guard<std::mutex> lk(g_defer_mu);
         if (int rc = flush_deferred_locked(ctx, nullptr)) return rc;
@@ -998,13 +1024,20 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     }
     const uint32_t tap_contours = n_chunks ? hc[0].contours : 0u; const uint64_t tap_points = n_chunks ? hc[0].points : 0ull;
     if (total > guess) {   // the guess was short: the staging area grows (the head has been consumed) and the whole list is fetched
-        if (int rc = ensure_pinned(ctx, (size_t)total * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes) + (1 << 16))) return rc;
+        if (int rc = ensure_pinned(ctx, (size_t)total * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes + undist_bytes) + (1 << 16))) return rc;
         h_markers = reinterpret_cast<a3_marker*>(ctx->pinned);
         h_poses = reinterpret_cast<a3_pose*>((uint8_t*)ctx->pinned + (size_t)total * sizeof(a3_marker));
         h_refined = reinterpret_cast<const float*>((uint8_t*)ctx->pinned + (size_t)total * (sizeof(a3_marker) + pose_bytes));
         A3_HIP(hipMemcpyAsync(h_markers, ctx->markers_ptr, (size_t)total * sizeof(a3_marker), hipMemcpyDeviceToHost, st));
         if (pose_bytes) A3_HIP(hipMemcpyAsync(h_poses, ctx->pose_buf.p, (size_t)total * pose_bytes, hipMemcpyDeviceToHost, st));
         if (refine_bytes) A3_HIP(hipMemcpyAsync(const_cast<float*>(h_refined), ctx->refined_buf.p, (size_t)total * refine_bytes, hipMemcpyDeviceToHost, st));
+        if (undist_bytes) {
+            h_undist = reinterpret_cast<const float*>((uint8_t*)ctx->pinned + (size_t)total * (sizeof(a3_marker) + pose_bytes + refine_bytes));
+            h_undist_res = h_undist + (size_t)total * 8;
+            A3_HIP(hipMemcpyAsync(const_cast<float*>(h_undist), ctx->undist_buf.p, (size_t)total * 32, hipMemcpyDeviceToHost, st));
+            A3_HIP(hipMemcpyAsync(const_cast<float*>(h_undist_res), ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8, (size_t)total * 16,
+                                  hipMemcpyDeviceToHost, st));
+        }
         A3_HIP(hipStreamSynchronize(st));
     }
     if (total) {
@@ -1013,6 +1046,11 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     }
     if (refine_bytes) ctx->h_refined.assign(h_refined, h_refined + (size_t)total * 8);
     ctx->refined_valid = refine_bytes != 0;
+    if (undist_bytes) {
+        ctx->h_undist.assign(h_undist, h_undist + (size_t)total * 8);
+        ctx->h_undist_res.assign(h_undist_res, h_undist_res + (size_t)total * 4);
+    }
+    ctx->undist_valid = undist_bytes != 0;
     ctx->board_valid = b.board;
     if (b.taps) {
         const uint32_t* hc32 = reinterpret_cast<const uint32_t*>(ctx->pinned_counts);
@@ -1169,7 +1207,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->contours, &ctx->cyc_start_off, &ctx->points, &ctx->zero_blk, &ctx->cands,
                       &ctx->pre_xy, &ctx->fin_xy, &ctx->fin_count, &ctx->work, &ctx->outs, &ctx->proj, &ctx->patches, &ctx->cand_big,
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
-                      &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf};
+                      &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1332,9 +1370,15 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
     b.refine = ctx->refine;
     b.refine_bytes = b.refine.method != A3_REFINE_NONE ? 8 * sizeof(float) : 0;
     b.board = want_pose && !ctx->board_ids.empty();
+    if (want_pose && ctx->dist.model != A3_DIST_NONE) {
+        if (!intr) return fail(ctx, A3_ERR_INVALID, "a pose batch with lens distortion set needs intrinsics (the coefficients are in focal units)");
+        b.dist = ctx->dist;
+        b.undist_bytes = 12 * sizeof(float);
+    }
     b.taps = ctx->debug_taps;
     b.profiling = ctx->profiling; b.profile_every = ctx->profile_every;
     ctx->board_valid = false;
+    ctx->undist_valid = false;
     b.row_stride = row_stride; b.frame_stride = frame_stride;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &b.row_stride, &b.frame_stride, n_frames, &b.pixels);
     if (rc != A3_OK) return rc;
@@ -1350,6 +1394,7 @@ static void finish_trivial(a3_ctx* ctx, uint32_t* per_frame_count) {
     if (per_frame_count && b.n) memset(per_frame_count, 0, (size_t)b.n * 4);
     ctx->h_refined.clear(); ctx->refined_valid = b.refine_bytes != 0;
     ctx->h_board.assign(b.n, a3_board_pose{}); ctx->board_valid = b.board;
+    ctx->h_undist.clear(); ctx->h_undist_res.clear(); ctx->undist_valid = b.undist_bytes != 0;
 }
 
 static int run_batch_with_retries(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
@@ -2040,9 +2085,83 @@ int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corner
         A3_HIP(hipMemcpyAsync(d_ids, ids, n_markers * 4, hipMemcpyHostToDevice, ctx->stream));
         A3_HIP(hipMemcpyAsync(d_pts, corners_xy, pts_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
+    if (intr && ctx->dist.model != A3_DIST_NONE && n_markers) {   // undistorted pixel corners, as a pose batch solves from
+        A3_HIP(ctx->tmp_c.ensure(n_markers * 12 * sizeof(float)));
+        A3_HIP(launch_undistort_corners(ctx->stream, nullptr, d_pts, nullptr, (uint32_t)(n_markers * 4), *intr, ctx->dist, ctx->tmp_c.as<float>(),
+                                        ctx->tmp_c.as<float>() + n_markers * 8));
+        d_pts = ctx->tmp_c.as<float>();
+    }
     A3_HIP(launch_board_pose(ctx->stream, nullptr, d_ids, d_pts, nullptr, nullptr, nullptr, (uint32_t)n_markers, 1u, ctx->board_slot_of.as<uint16_t>(),
                              ctx->n_codes, ctx->board_slot_rec.p, intr, image_width, image_height, ctx->tmp_b.as<a3_board_pose>()));
     A3_HIP(hipMemcpyAsync(out, ctx->tmp_b.p, sizeof(a3_board_pose), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+// ---- lens distortion (an extension beyond the reference; contract in include/aruco3_hip.h) ----
+void a3_default_distortion(a3_distortion* d) {
+    if (!d) return;
+    *d = a3_distortion{};
+    d->model = A3_DIST_RATIONAL;
+    d->iterations = 20;
+    d->max_residual_px = 0.1f;
+}
+
+static int check_distortion(a3_ctx* ctx, const a3_distortion& d) {
+    if (d.model != A3_DIST_NONE && d.model != A3_DIST_RATIONAL) return fail(ctx, A3_ERR_INVALID, "a3_distortion.model: unknown model");
+    if (d.model == A3_DIST_NONE) return A3_OK;
+    if (d.iterations < 1 || d.iterations > 100) return fail(ctx, A3_ERR_INVALID, "a3_distortion.iterations must be in 1..100");
+    const float k[8] = {d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6};
+    for (float v : k)
+        if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_distortion: a coefficient is not finite");
+    if (!(d.max_residual_px >= 0.0f) || !std::isfinite(d.max_residual_px))
+        return fail(ctx, A3_ERR_INVALID, "a3_distortion.max_residual_px must be finite and >= 0");
+    return A3_OK;
+}
+
+int a3_set_distortion(a3_ctx* ctx, const a3_distortion* d) {
+    if (!ctx) return A3_ERR_INVALID;
+    a3_distortion c{};   // NULL: off
+    if (d) c = *d;
+    if (int rc = check_distortion(ctx, c)) return rc;
+    if (c.model == A3_DIST_NONE) c = a3_distortion{};
+    ctx->dist = c;
+    return A3_OK;
+}
+
+int a3_get_undistorted_corners(a3_ctx* ctx, float* dst_xy, float* residual_px, size_t cap_markers, size_t* n) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!n || (!dst_xy && cap_markers)) return fail(ctx, A3_ERR_INVALID, "a3_get_undistorted_corners: null argument");
+    if (!ctx->undist_valid) return fail(ctx, A3_ERR_INVALID, "a3_get_undistorted_corners: the last collected batch ran without lens distortion");
+    const size_t total = ctx->h_undist.size() / 8;
+    *n = total;
+    if (total > cap_markers) return fail(ctx, A3_ERR_CAPACITY, "a3_get_undistorted_corners: cap_markers is smaller than the number of markers");
+    if (total) {
+        memcpy(dst_xy, ctx->h_undist.data(), total * 8 * sizeof(float));
+        if (residual_px) memcpy(residual_px, ctx->h_undist_res.data(), total * 4 * sizeof(float));
+    }
+    return A3_OK;
+}
+
+int a3_undistort_points(a3_ctx* ctx, const float* xy, size_t n, const a3_intrinsics* intr, const a3_distortion* d, float* out_xy,
+                        float* residual_px) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!intr || !d || (n && (!xy || !out_xy))) return fail(ctx, A3_ERR_INVALID, "a3_undistort_points: null argument");
+    if (int rc = check_distortion(ctx, *d)) return rc;
+    if (d->model != A3_DIST_RATIONAL) return fail(ctx, A3_ERR_INVALID, "a3_undistort_points: no distortion model (A3_DIST_NONE)");
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_undistort_points: a submitted batch has not been collected");
+    if (n > (1u << 30)) return fail(ctx, A3_ERR_INVALID, "a3_undistort_points: more than 2^30 points in one call");
+    if (n == 0) return A3_OK;
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    const size_t xy_bytes = n * 2 * sizeof(float);
+    A3_HIP(ctx->tmp_a.ensure(xy_bytes));
+    A3_HIP(ctx->tmp_b.ensure(xy_bytes + n * sizeof(float)));
+    A3_HIP(hipMemcpyAsync(ctx->tmp_a.p, xy, xy_bytes, hipMemcpyHostToDevice, ctx->stream));
+    float* d_out = ctx->tmp_b.as<float>();
+    A3_HIP(launch_undistort_corners(ctx->stream, nullptr, ctx->tmp_a.as<float>(), nullptr, (uint32_t)n, *intr, *d, d_out, d_out + n * 2));
+    A3_HIP(hipMemcpyAsync(out_xy, d_out, xy_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (residual_px) A3_HIP(hipMemcpyAsync(residual_px, d_out + n * 2, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }

@@ -1,8 +1,54 @@
 """Host-side mirror of `CameraIntrinsics` (src/pinhole.rs:11-60): a plain parameter record.
-The one operation the pose path uses, `unproject` (src/pinhole.rs:88-93), runs inside the pose kernel."""
+The one operation the pose path uses, `unproject` (src/pinhole.rs:88-93), runs inside the pose kernel.
+
+`Distortion` is an extension (the reference assumes an ideal pinhole camera): OpenCV's rational lens model, whose inverse runs on the
+device (include/aruco3_hip.h, a3_set_distortion) before the poses are solved."""
 import math
 from dataclasses import dataclass
 from typing import Optional
+
+import numpy as np
+
+
+@dataclass
+class Distortion:
+    """OpenCV's 5- / 8-coefficient lens model (a3_distortion, model A3_DIST_RATIONAL): the coefficients of a calibration as
+    cv2.calibrateCamera returns them (k1 k2 p1 p2 k3 [k4 k5 k6]), the iteration count of the undistortion and the largest
+    reprojection residual, in pixels, at which an undistorted corner is accepted."""
+    k1: float = 0.0
+    k2: float = 0.0
+    p1: float = 0.0
+    p2: float = 0.0
+    k3: float = 0.0
+    k4: float = 0.0
+    k5: float = 0.0
+    k6: float = 0.0
+    iterations: int = 20
+    max_residual_px: float = 0.1
+
+    @classmethod
+    def from_opencv(cls, coeffs, **kw) -> "Distortion":
+        """from OpenCV's distCoeffs (4, 5 or 8 values: k1 k2 p1 p2 [k3 [k4 k5 k6]])"""
+        c = [float(v) for v in np.asarray(coeffs, dtype=np.float64).reshape(-1)]
+        if len(c) not in (4, 5, 8):
+            raise ValueError("distortion coefficients: 4, 5 or 8 values (k1 k2 p1 p2 [k3 [k4 k5 k6]])")
+        return cls(*(c + [0.0] * (8 - len(c))), **kw)
+
+    def distort_normalized(self, points) -> np.ndarray:
+        """the forward model on the host, in the normalised plane: ideal (x, y) (..., 2) -> distorted (xd, yd), float64"""
+        p = np.asarray(points, dtype=np.float64)
+        x, y = p[..., 0], p[..., 1]
+        r2 = x * x + y * y
+        radial = (1 + ((self.k3 * r2 + self.k2) * r2 + self.k1) * r2) / (1 + ((self.k6 * r2 + self.k5) * r2 + self.k4) * r2)
+        xd = x * radial + (2 * self.p1 * x * y + self.p2 * (r2 + 2 * x * x))
+        yd = y * radial + (self.p1 * (r2 + 2 * y * y) + 2 * self.p2 * x * y)
+        return np.stack([xd, yd], axis=-1)
+
+    def _c(self):
+        from . import _lib
+
+        return _lib.DistortionRec(_lib.DIST_RATIONAL, int(self.iterations), self.k1, self.k2, self.p1, self.p2, self.k3, self.k4, self.k5,
+                                  self.k6, self.max_residual_px)
 
 
 @dataclass
@@ -13,6 +59,7 @@ class CameraIntrinsics:
     focal_y: float
     principal_x: Optional[float] = None
     principal_y: Optional[float] = None
+    distortion: Optional[Distortion] = None   # (an extension: the lens model the pose calls undistort corners with)
 
     def __post_init__(self):  # src/pinhole.rs:26-35
         if self.principal_x is None:
@@ -32,3 +79,25 @@ class CameraIntrinsics:
         fx = (sensor_width_mm * 0.5) / math.tan(horizontal_fov_radians * 0.5)
         fy = (sensor_height_mm * 0.5) / math.tan(vfov * 0.5)
         return cls(resolution_x, resolution_y, fx, fy, resolution_x * 0.5, resolution_y * 0.5)
+
+    def _c(self):
+        from . import _lib
+
+        return _lib.Intrinsics(self.image_width, self.image_height, self.focal_x, self.focal_y, self.principal_x, self.principal_y)
+
+
+_undistort_ctx = None
+
+
+def undistort_points(points, intrinsics: CameraIntrinsics):
+    """a3_undistort_points: pixel points (..., 2) seen through `intrinsics.distortion` -> (float32 (n, 2) undistorted pixels -- where an
+    ideal camera with the same focal lengths and principal point would have seen them --, float32 (n,) residuals in pixels; +inf marks
+    a point the model could not invert, returned as it came).  Runs on the device, on the kernel the pose batches use."""
+    global _undistort_ctx
+    from . import _lib
+
+    if intrinsics.distortion is None:
+        raise ValueError("undistort_points needs CameraIntrinsics.distortion")
+    if _undistort_ctx is None:
+        _undistort_ctx = _lib.Context(_lib.default_config(), np.zeros(1, np.uint64), 64, 1)
+    return _undistort_ctx.undistort_points(points, intrinsics._c(), intrinsics.distortion._c())

@@ -356,9 +356,58 @@ int  a3_set_board(a3_ctx *ctx, const uint32_t *ids, const float *corners_xy, siz
  * a3_detect_batch_pose* batch, A3_ERR_CAPACITY when cap_frames is short (*n says how many there are). */
 int  a3_get_board_poses(a3_ctx *ctx, a3_board_pose *dst, size_t cap_frames, size_t *n);
 /* stand-alone, one frame: the board pose from n_markers caller-given markers (ids, 8 float corners each, in pixels), on the same
- * kernel; intr NULL normalises by image_width / image_height.  Needs a board; synchronous; not while a submitted batch is in flight. */
+ * kernel; intr NULL normalises by image_width / image_height.  With intr and a distortion set (a3_set_distortion) the corners are
+ * undistorted first, as in a batch.  Needs a board; synchronous; not while a submitted batch is in flight. */
 int  a3_estimate_board_pose(a3_ctx *ctx, const uint32_t *ids, const float *corners_xy, size_t n_markers, const a3_intrinsics *intr,
                             uint32_t image_width, uint32_t image_height, a3_board_pose *out);
+
+/* Lens distortion.  NOT in the reference (every pose it returns assumes an ideal pinhole camera, src/pose.rs:58): an opt-in extension,
+ * off by default; with it off no launch, buffer, copy or result of a batch changes.  The model is OpenCV's rational one (k1 k2 p1 p2 k3
+ * k4 k5 k6; a 5-coefficient calibration has k4 = k5 = k6 = 0), in the normalised plane of a3_intrinsics.  With distortion set, every
+ * a3_detect_batch_pose* batch undistorts the four corners of every accepted marker on the device (k_undistort_corners, after the
+ * refinement and before k_pose) -- the refined corners with refinement on (refinement runs on the raw, distorted frame), else the
+ * integer a3_marker corners -- and solves the per-marker poses (k_pose on float corners with intrinsics) and the board pose from the
+ * UNDISTORTED PIXEL corners: both pose contracts above stay as written, applied to undistorted pixels, so the board pose's
+ * largest-quad start and its rms_px / alt_rms_px are measured in undistorted pixels.  a3_get_refined_corners keeps returning the
+ * distorted refined corners.  Such a batch needs intrinsics (the coefficients are in focal units): a pose submit with distortion set
+ * and intr == NULL fails with A3_ERR_INVALID.  Detection-only batches are unaffected.
+ * The algorithm for one corner (u, v) in pixels, fixed to the bit -- tests/lens_oracle.c a3o_undistort restates it.  Arithmetic is
+ * f32; every expression is evaluated as C parses it (left to right), with no fused multiply-add; division and sqrtf correctly rounded:
+ *     x0 = (u - cx) / fx;  y0 = (v - cy) / fy;  x = x0;  y = y0;
+ *     repeat `iterations` times:
+ *         r2 = x*x + y*y
+ *         icdist = (1 + ((k6*r2 + k5)*r2 + k4)*r2) / (1 + ((k3*r2 + k2)*r2 + k1)*r2)
+ *         dx = 2*p1*x*y + p2*(r2 + 2*x*x);   dy = p1*(r2 + 2*y*y) + 2*p2*x*y
+ *         x = (x0 - dx)*icdist;  y = (y0 - dy)*icdist
+ *     check:  r2 = x*x + y*y;  radial = (1 + ((k3*r2 + k2)*r2 + k1)*r2) / (1 + ((k6*r2 + k5)*r2 + k4)*r2)
+ *             xd = x*radial + (2*p1*x*y + p2*(r2 + 2*x*x));  yd = y*radial + (p1*(r2 + 2*y*y) + 2*p2*x*y)
+ *             ex = (xd - x0)*fx;  ey = (yd - y0)*fy;  res = sqrtf(ex*ex + ey*ey)
+ *     ok  = x, y, res finite and res <= max_residual_px
+ *     out = ok ? (x*fx + cx, y*fy + cy) : (u, v);   residual = ok ? res : +INFINITY
+ * (fx, fy, cx, cy) = (focal_x, focal_y, principal_x, principal_y).  The output is the undistorted pixel corner: where an ideal camera
+ * with the same fx fy cx cy would have seen the point.  A corner whose iteration diverges or leaves the model's valid field keeps its
+ * input position and reports +INFINITY: it is reported, not dropped, and the poses solved from it stay finite.
+ * a3_pack_detections records keep their layout: they carry the integer corners only. */
+enum { A3_DIST_NONE = 0, A3_DIST_RATIONAL = 1 };
+typedef struct a3_distortion {
+    uint32_t model;            /* A3_DIST_NONE (default) */
+    uint32_t iterations;       /* 20, 1 .. 100 */
+    float    k1, k2, p1, p2, k3, k4, k5, k6;
+    float    max_residual_px;  /* 0.1; finite, >= 0 */
+} a3_distortion;
+/* model A3_DIST_RATIONAL, every coefficient 0, iterations 20, max_residual_px 0.1 */
+void a3_default_distortion(a3_distortion *d);
+/* applies to batches submitted after the call (and to a3_estimate_board_pose with intrinsics); NULL or model NONE clears it */
+int  a3_set_distortion(a3_ctx *ctx, const a3_distortion *d);
+/* undistorted corners of the last collected batch: 8 floats (dst_xy) and 4 residuals in pixels (residual_px, nullable) per marker, in
+ * the order of `out`, the corners in a3_marker order.  A3_ERR_INVALID when that batch ran without distortion, A3_ERR_CAPACITY when
+ * cap_markers is short (*n says how many there are). */
+int  a3_get_undistorted_corners(a3_ctx *ctx, float *dst_xy, float *residual_px, size_t cap_markers, size_t *n);
+/* stand-alone, on the same kernel: n points (x, y pairs in pixels) -> out_xy (2n floats) and residual_px (n floats, nullable).  Needs
+ * intrinsics and a distortion of model A3_DIST_RATIONAL (not the context's: `d`); synchronous; not while a submitted batch is in
+ * flight.  Compose with a3_estimate_pose_normalized ((x - cx) / fx, (y - cy) / fy of the output) for poses of caller-given corners. */
+int  a3_undistort_points(a3_ctx *ctx, const float *xy, size_t n, const a3_intrinsics *intr, const a3_distortion *d, float *out_xy,
+                         float *residual_px);
 
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);

@@ -71,6 +71,8 @@ pub const A3_REFINE_NONE: u32 = 0;
 pub const A3_REFINE_SUBPIX: u32 = 1;
 pub const A3_BOARD_NONE: u32 = 0;
 pub const A3_BOARD_OK: u32 = 1;
+pub const A3_DIST_NONE: u32 = 0;
+pub const A3_DIST_RATIONAL: u32 = 1;
 pub const A3_BOARD_MAX_MARKERS: usize = 1024;
 
 /// a3_config <-> DetectorConfig, src/aruco.rs:23-30
@@ -142,6 +144,23 @@ pub struct A3BoardPose {
     pub alt_rms_px: f32,
     pub rotation: [f32; 9],
     pub translation: [f32; 3],
+}
+
+/// a3_distortion: OpenCV's rational lens model (not in the reference; include/aruco3_hip.h states the undistortion)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3Distortion {
+    pub model: u32,
+    pub iterations: u32,
+    pub k1: f32,
+    pub k2: f32,
+    pub p1: f32,
+    pub p2: f32,
+    pub k3: f32,
+    pub k4: f32,
+    pub k5: f32,
+    pub k6: f32,
+    pub max_residual_px: f32,
 }
 
 /// a3_stats: per-batch stage counters (the reference prints its rejects in debug builds, src/aruco.rs:163-164)
@@ -254,6 +273,11 @@ extern "C" {
     pub fn a3_get_board_poses(ctx: *mut A3Ctx, dst: *mut A3BoardPose, cap_frames: usize, n: *mut usize) -> c_int;
     pub fn a3_estimate_board_pose(ctx: *mut A3Ctx, ids: *const u32, corners_xy: *const f32, n_markers: usize, intr: *const A3Intrinsics,
                                   image_width: u32, image_height: u32, out: *mut A3BoardPose) -> c_int;
+    pub fn a3_default_distortion(d: *mut A3Distortion);
+    pub fn a3_set_distortion(ctx: *mut A3Ctx, d: *const A3Distortion) -> c_int;
+    pub fn a3_get_undistorted_corners(ctx: *mut A3Ctx, dst_xy: *mut f32, residual_px: *mut f32, cap_markers: usize, n: *mut usize) -> c_int;
+    pub fn a3_undistort_points(ctx: *mut A3Ctx, xy: *const f32, n: usize, intr: *const A3Intrinsics, d: *const A3Distortion, out_xy: *mut f32,
+                               residual_px: *mut f32) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
@@ -574,7 +598,98 @@ impl RefineConfig {
     }
 }
 
+/// A calibrated lens for `Detector::detect_pose_distorted` (an extension: the reference assumes an ideal pinhole camera):
+/// OpenCV's distCoeffs k1 k2 p1 p2 k3 [k4 k5 k6] (a 5-coefficient calibration leaves k4..k6 at 0).  `Default` gives
+/// a3_default_distortion's values: no distortion, 20 iterations, 0.1 px accepted residual.
+#[derive(Clone, Copy, Debug)]
+pub struct Distortion {
+    pub k1: f32,
+    pub k2: f32,
+    pub p1: f32,
+    pub p2: f32,
+    pub k3: f32,
+    pub k4: f32,
+    pub k5: f32,
+    pub k6: f32,
+    pub iterations: u32,      // 1..100
+    pub max_residual_px: f32, // a corner whose undistortion reprojects farther than this is kept as detected (residual +inf)
+}
+impl Default for Distortion {
+    fn default() -> Self {
+        Distortion { k1: 0.0, k2: 0.0, p1: 0.0, p2: 0.0, k3: 0.0, k4: 0.0, k5: 0.0, k6: 0.0, iterations: 20, max_residual_px: 0.1 }
+    }
+}
+impl Distortion {
+    fn to_a3(&self) -> A3Distortion {
+        A3Distortion { model: A3_DIST_RATIONAL, iterations: self.iterations, k1: self.k1, k2: self.k2, p1: self.p1, p2: self.p2, k3: self.k3,
+                       k4: self.k4, k5: self.k5, k6: self.k6, max_residual_px: self.max_residual_px }
+    }
+}
+
+/// What `Detector::detect_pose_distorted` returns per marker, in the order of `Detection.markers`.
+#[derive(Clone, Debug)]
+pub struct UndistortedMarker {
+    pub poses: (MarkerPose, MarkerPose),       // lower error first, solved from the undistorted corners
+    pub corners: [(f32, f32); 4],              // undistorted pixel corners, `Marker.corners` order
+    pub residual_px: [f32; 4],                 // +inf: that corner could not be undistorted and kept its detected position
+}
+
 impl Detector {
+    /// New (additive): `detect` of one image plus the pose of every marker, solved from its corners undistorted on the device
+    /// through `dist` (the poses `estimate_pose` gives assume an ideal pinhole camera).  `Detector` itself gains no field: the
+    /// distortion is handed to the shared context for this call only, under its lock.
+    pub fn detect_pose_distorted(&self, image: DynamicImage, marker_size_mm: f32, intrinsics: &CameraIntrinsics, dist: &Distortion)
+                                 -> (Detection, Vec<UndistortedMarker>) {
+        let slot = slot_for(self);
+        let mut ctx = slot.lock().unwrap();
+        let images = std::slice::from_ref(&image);
+        let p = pack(images, &mut ctx.staging);
+        ctx.check(unsafe { a3_set_debug_taps(ctx.raw, 0) }, "a3_set_debug_taps");
+        let d = dist.to_a3();
+        ctx.check(unsafe { a3_set_distortion(ctx.raw, &d) }, "a3_set_distortion");
+        let intr = to_a3_intrinsics(intrinsics);
+        let mut cap = 64usize;
+        let mut markers = vec![A3Marker::default(); cap];
+        let mut poses = vec![A3Pose::default(); 2 * cap];
+        let mut per = vec![0u32; 1];
+        let mut found = 0usize;
+        let rc = loop {
+            let rc = unsafe {
+                a3_detect_batch_pose(ctx.raw, p.bytes as *const c_void, A3_MEM_HOST, p.fmt, p.width, p.height, p.width as usize * p.bpp,
+                                     p.width as usize * p.height as usize * p.bpp, 1, marker_size_mm, &intr, markers.as_mut_ptr(),
+                                     poses.as_mut_ptr(), cap, per.as_mut_ptr(), &mut found)
+            };
+            if rc == A3_ERR_CAPACITY && cap < MAX_MARKERS_PER_FRAME {
+                cap *= 4;
+                markers.resize(cap, A3Marker::default());
+                poses.resize(2 * cap, A3Pose::default());
+                continue;
+            }
+            break rc;
+        };
+        let mut xy = vec![0f32; 8 * found.max(1)];
+        let mut res = vec![0f32; 4 * found.max(1)];
+        let mut n = 0usize;
+        let rc2 = if rc == A3_OK {
+            unsafe { a3_get_undistorted_corners(ctx.raw, xy.as_mut_ptr(), res.as_mut_ptr(), found.max(1), &mut n) }
+        } else {
+            rc
+        };
+        unsafe { a3_set_distortion(ctx.raw, std::ptr::null()) }; // the shared context goes back to the ideal pinhole
+        ctx.check(rc, "a3_detect_batch_pose");
+        ctx.check(rc2, "a3_get_undistorted_corners");
+        let det = Detection { grey: None, candidates: vec![], homographies: vec![], markers: markers[..found].iter().map(marker_of).collect() };
+        let out = (0..n).map(|i| {
+            let q = &xy[8 * i..8 * i + 8];
+            UndistortedMarker {
+                poses: (to_marker_pose(&poses[2 * i]), to_marker_pose(&poses[2 * i + 1])),
+                corners: [(q[0], q[1]), (q[2], q[3]), (q[4], q[5]), (q[6], q[7])],
+                residual_px: [res[4 * i], res[4 * i + 1], res[4 * i + 2], res[4 * i + 3]],
+            }
+        }).collect();
+        (det, out)
+    }
+
     /// New (additive): `detect` plus the sub-pixel corners of every marker, in the order of `Detection.markers`, each
     /// in `Marker.corners` order.  The Detection is the one `detect` returns; `Detector` itself gains no field (the setting
     /// is handed to the shared context for this call only, under its lock).
