@@ -1,13 +1,21 @@
 #!/usr/bin/env python3
-"""bench.py -- frames/sec of the detection hot path on MI355X, with the roofline of the dominant
-HBM-bound kernel and a CPU baseline measured beside it.
+"""bench.py -- frames/sec of the detection hot path on MI355X; with --full also the roofline of the dominant
+HBM-bound kernel, a CPU baseline measured beside it and the other measurements listed below.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus N --steps K --warmup W --full
 
 A "step" is one pass of Detector::detect over one batch of synthetic frames that already sit in HBM:
 BASELINE.json config 2, a batch of 256 x 1920x1080 RGB frames with 4-8 ARUCO markers each (config 3 is the
 same batch per GPU on 8 GPUs: weak scaling, frames sharded by rank, dictionary broadcast once, detections
 all-gathered per batch over RCCL).  One JSON line is printed by rank 0.
+
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs and
+prints the line.  --full adds, outside the timed steps: the threshold kernel's roofline and the stage table from
+isolated launches, its launch time in a burst and in company, the stepping A/B block, the decode kernel's
+roofline, the id check of the last batches against the rendered layouts, the check of the gathered records
+(N > 1; --verify-gathers checks them without --full), the CPU baseline with parity against the oracle and the
+other BASELINE workloads.
 """
 import argparse
 import json
@@ -117,7 +125,10 @@ def main():
     ap.add_argument("--workload", choices=tuple(WORKLOADS), default="c2", help="c2 (default): BASELINE config 2, the configuration the metric is quoted "
                                                                                 "on; c5: BASELINE config 5 (3840x2160, 16 markers, detect + pose)")
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU per step (0 = the workload's: 256 for c2, 64 for c5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="beside the headline, run every other measurement and check of this file (rooflines, "
+                                                         "stage table, A/B block, id and gather checks, CPU baseline and parity, other "
+                                                         "workloads); off by default: a plain run sets up, warms up, times and prints")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
     ap.add_argument("--device-synth", action="store_true", help="render the frames on the GPU (a3_synth_render) instead of on the host: no "
                                                                   "host rendering, no H2D copy (same layouts and ids; pixels may differ by "
                                                                   "a grey level at cell edges)")
@@ -135,8 +146,8 @@ def main():
     ap.add_argument("--min-timed-s", type=float, default=3.0, help="with --repeats 0: seconds the timed regions add up to (the GPU is busy that long)")
     ap.add_argument("--force-dist", action="store_true", help="run the multi-rank code path (process group, dictionary broadcast, device-packed "
                                                                 "records, all-gather) even with one rank: lets a 1-GPU box exercise the RCCL branch")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the other_workloads block (reference bench recipe, configs 4 and 5) and the "
-                                                                       "shared-stream A/B")
+    ap.add_argument("--no-other-workloads", action="store_true", help="with --full: skip the other_workloads block (reference bench recipe, configs 4 "
+                                                                       "and 5) and the shared-stream A/B")
     ap.add_argument("--streams", choices=("own", "shared"), default="own",
                     help="own (default): every context on a stream of its own -- the threshold kernels of consecutive batches serialise (each "
                          "fills the chip's register file), the contour / decode chains of the batches in flight overlap one another; "
@@ -159,8 +170,9 @@ def main():
                                                                      "collective's queues (aruco3_amd/streams.py)")
     ap.add_argument("--no-gather-backpressure", action="store_true", help="test aid: packs do NOT wait for the collective that last read their record "
                                                                              "buffer (round 4's behaviour: with --gather-delay-us records are overwritten before they are sent)")
-    ap.add_argument("--isolated-launches", type=int, default=24, help="synchronous batches run one at a time, every stage between events, before the "
-                                                                      "timed steps: the threshold kernel's launch duration ALONE (roofline) and the stage table")
+    ap.add_argument("--isolated-launches", type=int, default=24, help="with --full: synchronous batches run one at a time, every stage between events, "
+                                                                      "before the timed steps: the threshold kernel's launch duration ALONE (roofline) "
+                                                                      "and the stage table")
     ap.add_argument("--max-markers", type=int, default=0, help="N > 1: markers per frame a gather record holds; 0 = calibrated on the first batch "
                                                                "(2 x the largest count on any rank, at least 8); a frame that holds more later is an error, never a clip")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="N > 1 started without a launcher: seconds the parent waits for its ranks")
@@ -303,7 +315,7 @@ def main():
         df, truths = synth.render_frames_device(spec, d.code_list, d.num_bits, seeds, device=local_rank)
         d_bufs.append(df); truth_ids.append([[t.id for t in tr] for tr in truths])
     t_gen += time.time() - t0
-    want_host = rank == 0 and not args.no_cpu_baseline and world == 1     # only the CPU baseline reads host copies
+    want_host = rank == 0 and args.full and not args.no_cpu_baseline and world == 1     # only the CPU baseline reads host copies
     frames_h = [frames0 if (j == 0 and frames0 is not None) else d_bufs[j].cpu().numpy() for j in range(n_bufs)] if want_host else None
     torch.cuda.synchronize()
     n, h, w, c = d_bufs[0].shape
@@ -481,23 +493,25 @@ def main():
         release_gathers()
         return res
 
-    # ---- isolated launches: one synchronous batch at a time, every stage between events, nothing else on the GPU ----
-    # The roofline figure of the threshold kernel is its launch duration ALONE; in the stepping below no kernel runs alone.
-    stage_ms, k1_ms, k1_n = {}, 0.0, 0
     for j in range(n_bufs):      # (the context meets every batch once before anything is timed: its pools grow to the largest)
         detect_sync(ctx, j)
-    ctx.set_profiling(True)
-    for st_id in (_lib.STAGE_THRESHOLD, _lib.STAGE_CONTOUR, _lib.STAGE_DECODE):
-        ctx.profile(st_id, reset=True)
-    torch.cuda.synchronize()
-    for it in range(max(1, args.isolated_launches)):
-        detect_sync(ctx, it % n_bufs)
-    for name, st_id in (("threshold", _lib.STAGE_THRESHOLD), ("contour", _lib.STAGE_CONTOUR), ("decode", _lib.STAGE_DECODE)):
-        a, b = ctx.profile(st_id, reset=True)
-        stage_ms[name] = round(a / b, 4) if b else None
-        if st_id == _lib.STAGE_THRESHOLD:
-            k1_ms, k1_n = a, b
-    ctx.set_profiling(0)
+
+    # ---- --full: isolated launches: one synchronous batch at a time, every stage between events, nothing else on the GPU ----
+    # The roofline figure of the threshold kernel is its launch duration ALONE; in the stepping below no kernel runs alone.
+    stage_ms, k1_ms, k1_n = {}, 0.0, 0
+    if args.full:
+        ctx.set_profiling(True)
+        for st_id in (_lib.STAGE_THRESHOLD, _lib.STAGE_CONTOUR, _lib.STAGE_DECODE):
+            ctx.profile(st_id, reset=True)
+        torch.cuda.synchronize()
+        for it in range(max(1, args.isolated_launches)):
+            detect_sync(ctx, it % n_bufs)
+        for name, st_id in (("threshold", _lib.STAGE_THRESHOLD), ("contour", _lib.STAGE_CONTOUR), ("decode", _lib.STAGE_DECODE)):
+            a, b = ctx.profile(st_id, reset=True)
+            stage_ms[name] = round(a / b, 4) if b else None
+            if st_id == _lib.STAGE_THRESHOLD:
+                k1_ms, k1_n = a, b
+        ctx.set_profiling(0)
 
     # The threshold kernel as the stepping runs it: ONE REAL ROTATION of the burst stepping (public calls only: the gates, the
     # submits, A3_PROFILE_THRESHOLD_ONLY = the library's own events around each threshold kernel on its context's stream), started
@@ -506,16 +520,22 @@ def main():
     # intervals is the span from the start of the first to the end of the last.  Launches in flight together refill each other's
     # retiring wave slots, which a lone launch -- sized to fill the chip in exactly one round -- cannot: the per-launch time here
     # is what the kernel costs inside a step, the isolated one above what it costs alone.
+    # The twelve rotations are set-up as well: the timed steps have always followed them, and without them the same free-running
+    # steps measured 0.95-1.0 ms per step instead of 0.67 ms (one MI355X, --steps 20 --warmup 5; 48 more free-running steps in
+    # their place did not make up for them).  So they run in every run; only the events around the threshold kernels and the
+    # figure they give are --full's.
     k1_burst_ms = None
     if own_streams and n_ctx > 1 and args.workload in WORKLOADS:
         spans = []
         use_gates[0] = True
-        for cx in ctxs:
-            cx.set_profiling(_lib.PROFILE_THRESHOLD_ONLY)
+        if args.full:
+            for cx in ctxs:
+                cx.set_profiling(_lib.PROFILE_THRESHOLD_ONLY)
         for rep in range(12):
             torch.cuda.synchronize()
-            for cx in ctxs:
-                cx.profile(_lib.STAGE_THRESHOLD, reset=True)
+            if args.full:
+                for cx in ctxs:
+                    cx.profile(_lib.STAGE_THRESHOLD, reset=True)
             s0 = torch.cuda.Event()
             with torch.cuda.stream(ctx_stream[id(ctxs[0])]):
                 torch.cuda._sleep(4_000_000)        # ~2 ms: the rotation's submits are enqueued while it runs
@@ -526,11 +546,13 @@ def main():
                 submit(cx)
             for cx in ctxs:
                 collect_raw(cx)
-            per_ctx = [cx.profile(_lib.STAGE_THRESHOLD, reset=True) for cx in ctxs]
-            if all(b == 1 for _, b in per_ctx):
-                spans.append(max(a for a, _ in per_ctx) / n_ctx)
-        for cx in ctxs:
-            cx.set_profiling(0)
+            if args.full:
+                per_ctx = [cx.profile(_lib.STAGE_THRESHOLD, reset=True) for cx in ctxs]
+                if all(b == 1 for _, b in per_ctx):
+                    spans.append(max(a for a, _ in per_ctx) / n_ctx)
+        if args.full:
+            for cx in ctxs:
+                cx.set_profiling(0)
         use_gates[0] = gated
         spans = sorted(spans[2:])
         k1_burst_ms = spans[len(spans) // 2] if spans else None
@@ -589,21 +611,22 @@ def main():
     elapsed = sorted(regions)[len(regions) // 2]
     outliers = [{"region": i, "ms_per_step": round(r / args.steps * 1e3, 4)} for i, r in enumerate(regions) if r > 1.5 * elapsed]
 
-    # sanity: what was rendered is what was read (ids per frame), on the last batch every context delivered
+    # --full: what was rendered is what was read (ids per frame), on the last batch every context delivered
+    check_gathers = use_dist and (args.full or args.verify_gathers)
     id_ok, id_total = 0, 0
     by_frame_of, per_of, poses_of = {}, {}, {}
-    for k, (r_k, j) in sorted(last_res.items()):
-        bf = split_by_frame(r_k[0], r_k[1])
-        by_frame_of[j], per_of[j] = bf, r_k[1]
-        poses_of[j] = r_k[2] if pose_mm else None
-        id_ok += sum(sorted(int(m["id"]) for m in bf[f]) == sorted(truth_ids[j][f]) for f in range(n))
-        id_total += n
-    markers, per = res[0], res[1]
+    if args.full or check_gathers:
+        for k, (r_k, j) in sorted(last_res.items()):
+            bf = split_by_frame(r_k[0], r_k[1])
+            by_frame_of[j], per_of[j] = bf, r_k[1]
+            poses_of[j] = r_k[2] if pose_mm else None
+            id_ok += sum(sorted(int(m["id"]) for m in bf[f]) == sorted(truth_ids[j][f]) for f in range(n))
+            id_total += n
 
-    # the threshold kernel's launch duration IN COMPANY (a few more steps with its launches between events, outside the timed
-    # regions): what the kernel trace of this run shows for it -- it waits for and shares the chip with the other batches
+    # --full: the threshold kernel's launch duration IN COMPANY (a few more steps with its launches between events, outside the
+    # timed regions): what the kernel trace of this run shows for it -- it waits for and shares the chip with the other batches
     k1_company = None
-    if not args.no_pipeline:
+    if args.full and not args.no_pipeline:
         for cx in ctxs:
             cx.set_profiling(_lib.PROFILE_THRESHOLD_ONLY); cx.profile(_lib.STAGE_THRESHOLD, reset=True)
         run_steps(max(8, 2 * n_ctx))
@@ -616,7 +639,7 @@ def main():
     # ==== everything above this line calls the public header only (tests/test_bench_public_abi.py greps for it).
     ab_shared, ab_r04_default, ab_gates = None, None, None
     internal_probes = []
-    if not use_dist and own_streams and not args.no_other_workloads:
+    if args.full and not use_dist and own_streams and not args.no_other_workloads:
         def timed(fn, k=20):
             fn(args.steps)
             sr = []
@@ -693,7 +716,7 @@ def main():
     # bounds it -- the L2's REQUEST rate for its scattered taps: tools/micro/scatterbench issues the same tap pattern with
     # everything else taken away, in this run, on this box.
     roofline_warp = None
-    if rank == 0 and not use_dist and not args.no_other_workloads and args.workload == "c2":
+    if args.full and rank == 0 and not use_dist and not args.no_other_workloads and args.workload == "c2":
         try:
             detect_sync(ctx, 0)
             n_cand = int(ctx.stats()["candidates"])
@@ -731,9 +754,9 @@ def main():
             roofline_warp = {"error": repr(e)}
 
     gathered = None
-    if use_dist:
+    if check_gathers:
         # what the collectives delivered, checked on rank 0: every rank's frames of the rotation, global indices as packed, ids as
-        # rendered.  Default: the last collective; --verify-gathers: every collective of the run (cloned on the side stream).
+        # rendered.  --full: the last collective; --verify-gathers: every collective of the run (cloned on the side stream).
         torch.cuda.synchronize()
         with_p = bool(pose_mm)
         truth_cache = {}
@@ -903,6 +926,9 @@ def main():
             "library_stepping_seen": stepping_seen,
             "frame_synthesis_s": round(t_gen, 1),
         }
+        if not args.full:   # measured by --full only (the line keeps its key order with it)
+            for k in ("roofline", "stage_ms_per_step", "frames_with_all_ids_correct"):
+                del out[k]
         if roofline_warp is not None:
             out["roofline_warp"] = roofline_warp
         if ab_shared is not None:
@@ -919,9 +945,9 @@ def main():
                            "hw_queues": hw_queues,
                            "pack_and_collective": "records packed by a kernel on the context's own stream right after collect(); one all-gather per rotation on a side stream, behind the packs' events",
                            "note": "an N > 1 RCCL number exists only where the driver's multi-GPU node produced one; a 1-GPU box can run world_size 1 (nccl) or rehearse ranks over gloo"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], out["parity_in_run"] = cpu_baseline(frames_h, d, by_frame_of, poses_of, per_of, pose_mm, (w, h))
-        if not args.no_other_workloads and world == 1 and args.workload == "c2":
+        if args.full and not args.no_other_workloads and world == 1 and args.workload == "c2":
             try:
                 out["other_workloads"] = other_workloads(local_rank, with_cpu=not args.no_cpu_baseline)
             except Exception as e:   # side measurements never take the line down
@@ -943,8 +969,8 @@ def _pick(d, keys, n=96):
 
 
 def compact_line(out, detail_path="bench_detail.json"):
-    """The driver-facing line: the contract's keys, `roofline`, `roofline_warp`, `cpu_baseline`, `parity_in_run`, one-word `stepping` /
-    `gates` and a few headline figures of the other BASELINE configurations -- everything else (per-region times, prose, A/B rows,
+    """The driver-facing line: the contract's keys, `roofline`, `roofline_warp`, `cpu_baseline`, `parity_in_run` (these four with --full), one-word
+    `stepping` / `gates` and a few headline figures of the other BASELINE configurations -- everything else (per-region times, prose, A/B rows,
     the other workloads' tables) stays in `out`, which goes to bench_detail.json.  Never longer than LINE_BUDGET bytes: optional
     keys are dropped, least important first, until it fits."""
     line = _pick(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "repeats", "timed_region_s_total",
@@ -954,10 +980,11 @@ def compact_line(out, detail_path="bench_detail.json"):
     cfg = out.get("config", {})
     line["config"] = dict(_pick(cfg, ("frames_per_gpu", "distinct_batches_in_flight", "resolution", "dictionary")),
                           workload=_short(cfg.get("workload", ""), 110), sharding=_short(cfg.get("sharding", ""), 60))
-    rf = out.get("roofline") or {}
-    line["roofline"] = _pick(rf, ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "bytes_per_pixel", "bytes_per_launch",
-                                  "avg_launch_ms", "launches_timed", "avg_launch_ms_in_company"), 100)
-    line["roofline"]["kernel"] = _short(rf.get("kernel", ""), 60)
+    rf = out.get("roofline")
+    if isinstance(rf, dict):      # (--full)
+        line["roofline"] = _pick(rf, ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "bytes_per_pixel", "bytes_per_launch",
+                                      "avg_launch_ms", "launches_timed", "avg_launch_ms_in_company"), 100)
+        line["roofline"]["kernel"] = _short(rf.get("kernel", ""), 60)
     rw = out.get("roofline_warp")
     if isinstance(rw, dict):
         if "error" in rw:
@@ -981,7 +1008,8 @@ def compact_line(out, detail_path="bench_detail.json"):
             line["cpu_baseline"]["all_cores"] = _pick(cb["all_cores"], ("value", "cores"))
     if out.get("parity_in_run"):
         line["parity_in_run"] = _pick(out["parity_in_run"], ("frames_compared", "frames_equal", "batches_covered", "pose_max_abs_diff", "against"), 60)
-    line["frames_with_all_ids_correct"] = out.get("frames_with_all_ids_correct")
+    if "frames_with_all_ids_correct" in out:
+        line["frames_with_all_ids_correct"] = out["frames_with_all_ids_correct"]
     if isinstance(out.get("library"), dict):
         line["library"] = _pick(out["library"], ("abi", "tuning_build", "internal_switches_used"))
     if isinstance(out.get("gathered"), dict):

@@ -89,6 +89,19 @@ def test_minimal_run_without_the_side_measurements():
     assert line["gathered"]["frames"] == 8192 and line["n_gpus"] == 8
 
 
+def test_plain_run_without_the_full_measurements():
+    """a run without --full: no roofline, stage table, id check or side measurement in `out` -- the line keeps the contract's keys"""
+    full = _round5_line()
+    for k in ("roofline", "roofline_warp", "stage_ms_per_step", "frames_with_all_ids_correct", "cpu_baseline", "parity_in_run", "other_workloads",
+              "ab_shared_stream", "ab_burst_gates", "ab_r04_library_default"):
+        full.pop(k, None)
+    line = bench.compact_line(full)
+    assert len(json.dumps(line).encode()) <= bench.LINE_BUDGET
+    for k in REQUIRED:
+        assert k in line or k == "roofline", k
+    assert "roofline" not in line and "frames_with_all_ids_correct" not in line and "stage_ms_per_step" not in line
+    assert (line["value"], line["ms_per_step"], line["dtype"]) == (full["value"], full["ms_per_step"], full["dtype"])
+
 def test_emit_prints_one_stdout_line_and_the_detail_elsewhere(tmp_path, monkeypatch):
     full = _round5_line()
     monkeypatch.setenv("A3_BENCH_DETAIL", str(tmp_path / "bench_detail.json"))

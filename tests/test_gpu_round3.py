@@ -43,7 +43,7 @@ def test_bench_front_door_starts_its_own_ranks():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--backend", "gloo", "--frames", "16", "--steps", "3", "--warmup", "1",
-           "--device-synth", "--repeats", "2", "--no-other-workloads", "--no-cpu-baseline", "--launch-timeout", "500"]
+           "--device-synth", "--repeats", "2", "--full", "--no-other-workloads", "--no-cpu-baseline", "--launch-timeout", "500"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     line, out = bench_output(p)                                                # ONE JSON line on stdout, within the driver's budget

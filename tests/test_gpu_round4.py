@@ -233,7 +233,7 @@ def test_bench_config5_two_ranks_gloo_with_poses_in_the_gather():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", "c5", "--gpus", "2", "--backend", "gloo", "--frames", "4", "--steps", "4", "--warmup", "1",
-           "--device-synth", "--repeats", "2", "--no-other-workloads", "--no-cpu-baseline", "--isolated-launches", "2", "--launch-timeout", "500"]
+           "--device-synth", "--repeats", "2", "--full", "--no-other-workloads", "--no-cpu-baseline", "--isolated-launches", "2", "--launch-timeout", "500"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     line, out = bench_output(p)
@@ -254,7 +254,7 @@ def test_bench_line_carries_parity_and_isolated_roofline():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--frames", "8", "--steps", "4", "--warmup", "1", "--repeats", "2", "--isolated-launches", "3",
-           "--synth-workers", "4"]
+           "--synth-workers", "4", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     line, out = bench_output(p)
@@ -282,3 +282,27 @@ def test_bench_line_carries_parity_and_isolated_roofline():
         if "skipped" not in ow[k]:
             pr = ow[k]["parity_in_run"]
             assert pr["frames_equal"] == pr["frames_compared"] > 0, (k, pr)
+
+
+def test_plain_bench_run_times_and_dumps_only(tmp_path):
+    """the same command without --full: set-up, warm-up, the timed steps, --dump-outputs and the line -- no roofline, no A/B, no CPU
+    baseline or parity, no other workloads, no internal probe"""
+    env = dict(os.environ, A3_BENCH_DETAIL=str(tmp_path / "bench_detail.json"))
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
+        env.pop(k, None)
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--frames", "8", "--steps", "4", "--warmup", "1", "--repeats", "2", "--synth-workers", "4",
+           "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-4000:]
+    line, out = bench_output(p)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "e2e_frac", "stepping", "gates"):
+        assert k in line, k
+    assert line["value"] == out["value"] > 0 and line["ms_per_step"] == out["ms_per_step"] > 0 and (line["steps"], line["warmup"]) == (4, 1)
+    for k in ("roofline", "roofline_warp", "stage_ms_per_step", "frames_with_all_ids_correct", "cpu_baseline", "parity_in_run", "other_workloads",
+              "ab_shared_stream", "ab_burst_gates", "ab_r04_library_default"):
+        assert k not in out and k not in line, k
+    assert out["library"]["internal_switches_used"] == [] and out["library"]["internal_probes_after_the_headline"] == []
+    assert out["library_stepping_seen"] == ["whole"] * 4 and out["repeats"] == 2
+    per = np.load(tmp_path / "out" / "per_frame_count.npy")
+    ids = np.load(tmp_path / "out" / "markers_id.npy")
+    assert per.shape == (8,) and int(per.sum()) == len(ids) > 0

@@ -124,7 +124,7 @@ def _front_door(extra, timeout=900):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "LOCAL_WORLD_SIZE", "A3_HIP_LIB"):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(_RANKS), "--backend", "gloo", "--frames", "8", "--steps", "2", "--warmup", "1",
-           "--device-synth", "--repeats", "2", "--isolated-launches", "2", "--no-other-workloads", "--no-cpu-baseline", "--launch-timeout", "600"] + extra
+           "--device-synth", "--repeats", "2", "--full", "--isolated-launches", "2", "--no-other-workloads", "--no-cpu-baseline", "--launch-timeout", "600"] + extra
     return subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
 
 

@@ -216,7 +216,7 @@ def test_two_rank_rehearsal_as_child_processes():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "16",
-           "--backend", "gloo", "--device-synth", "--repeats", "1", "--no-other-workloads"]
+           "--backend", "gloo", "--device-synth", "--repeats", "1", "--full", "--no-other-workloads"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     line, out = bench_output(p)

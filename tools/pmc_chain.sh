@@ -5,7 +5,7 @@
 # derived from (TCC_EA0_RDREQ, _32B, TCC_BUBBLE = 128-byte requests; TCC_EA0_WRREQ, _64B).  Four passes of at most four TCC counters, counters
 # only, on the isolated stepping (one synchronous batch at a time: every kernel alone).  Output: gpurun_out/pmc_chain/summary.txt + .json
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=$ROOT/gpurun_out/pmc_chain; rm -rf "$OUT"; mkdir -p "$OUT"; export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --device-synth --no-cpu-baseline --no-other-workloads --no-pipeline --repeats 1 --steps 3 --warmup 1 --isolated-launches 2 ${BENCH_ARGS:-}"
+ARGS="$ROOT/bench.py --full --device-synth --no-cpu-baseline --no-other-workloads --no-pipeline --repeats 1 --steps 3 --warmup 1 --isolated-launches 2 ${BENCH_ARGS:-}"
 cd /tmp
 PASSES=(
   "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_DRAM_32B_sum TCC_BUBBLE_sum"

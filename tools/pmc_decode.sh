@@ -14,7 +14,7 @@ echo "== scatterbench (tools/micro/scatterbench.hip) =="; timeout -k 5 120 ./too
 echo "== k_decode through a3_debug_kernel_time (dbg 0: projection + decode, -1: decode alone, -2: stop after sampling, -3: after Otsu, -4: after bits) =="
 timeout -k 5 200 python3 tools/kernel_probe.py 2>/dev/null | grep -E "^decode|^stats"
 } > "$OUT/summary.txt" 2>&1
-ARGS="$ROOT/bench.py --device-synth --no-cpu-baseline --no-other-workloads --no-pipeline --repeats 1 --steps 3 --warmup 1"
+ARGS="$ROOT/bench.py --full --device-synth --no-cpu-baseline --no-other-workloads --no-pipeline --repeats 1 --steps 3 --warmup 1"
 cd /tmp
 # Counter passes: each pass asks a hardware block for no more counters than it holds (round 3's second pass asked the L1 (TCP) for
 # five and aborted: "Request exceeds the capabilities of the hardware to collect" -- at most two TCP counters per pass now).  A pass

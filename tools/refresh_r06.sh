@@ -12,12 +12,12 @@ set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd); cd "$ROOT"; OUT=$ROOT/gpurun_out/refresh; mkdir -p "$OUT" "$ROOT/gpurun_out/pmc"; export TMPDIR=/tmp
 bench() {   # bench <name> <timeout> <args...>: stdout line -> $OUT/<name>.json.log, detail -> $OUT/<name>.detail.json
   local name=$1 to=$2; shift 2
-  A3_BENCH_DETAIL=$OUT/$name.detail.json timeout -k 10 "$to" python3 bench.py "$@" > "$OUT/$name.json.log" 2> "$OUT/$name.err" || { echo "$name FAILED"; tail -5 "$OUT/$name.err"; return 1; }
+  A3_BENCH_DETAIL=$OUT/$name.detail.json timeout -k 10 "$to" python3 bench.py --full "$@" > "$OUT/$name.json.log" 2> "$OUT/$name.err" || { echo "$name FAILED"; tail -5 "$OUT/$name.err"; return 1; }
   python3 tools/show_bench.py "$OUT/$name.json.log" | head -${SHOW:-3}
 }
 profiled() {   # profiled <name> <args...>: the same under rocprofv3 --kernel-trace --stats (the program itself after `--`, from /tmp)
   local name=$1; shift
-  (cd /tmp && A3_BENCH_DETAIL=$OUT/$name.detail.json timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o "$name" -- python3 "$ROOT/bench.py" "$@" > "$OUT/$name.log" 2>&1) || { tail -5 "$OUT/$name.log"; return 2; }
+  (cd /tmp && A3_BENCH_DETAIL=$OUT/$name.detail.json timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o "$name" -- python3 "$ROOT/bench.py" --full "$@" > "$OUT/$name.log" 2>&1) || { tail -5 "$OUT/$name.log"; return 2; }
   grep '^{' "$OUT/$name.log" | tail -1 > "$OUT/$name.json.log"; python3 tools/show_bench.py "$OUT/$name.json.log" | head -2
 }
 case ${1:-a} in

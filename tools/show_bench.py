@@ -16,9 +16,9 @@ else:
     d = json.loads(det.read_text()) if det.exists() else line
 if line is not None:
     print(f"line: {len(json.dumps(line))} bytes, detail {line.get('detail')}")
-r = d["roofline"]
+r = d.get("roofline") or {}     # (bench.py --full only)
 print(f"value {d['value']} {d['unit']}  ms/step {d['ms_per_step']}  n_gpus {d['n_gpus']}  contexts {d.get('contexts')}  gates {d.get('gates')}  ids {d.get('frames_with_all_ids_correct')}")
-print(f"roofline frac {r['frac']} in burst {(r.get('in_burst') or {}).get('frac')} (K1 alone {r['avg_launch_ms']} ms over {r['launches_timed']} launches, in company {r.get('avg_launch_ms_in_company')})  "
+print(f"roofline frac {r.get('frac')} in burst {(r.get('in_burst') or {}).get('frac')} (K1 alone {r.get('avg_launch_ms')} ms over {r.get('launches_timed')} launches, in company {r.get('avg_launch_ms_in_company')})  "
       f"e2e_frac {d.get('e2e_frac')}  stages {d.get('stage_ms_per_step')}  outliers {(d.get('outlier_regions') or {}).get('count')}")
 for k in ("roofline_warp", "ab_shared_stream", "ab_burst_gates", "ab_r04_library_default", "ab_fps", "cpu_baseline", "parity_in_run", "gathered", "dist", "library"):
     if k in d:
