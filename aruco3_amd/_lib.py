@@ -27,6 +27,8 @@ REFINE_NONE, REFINE_SUBPIX = 0, 1
 BOARD_NONE, BOARD_OK = 0, 1
 BOARD_MAX_MARKERS = 1024
 DIST_NONE, DIST_RATIONAL = 0, 1
+CHARUCO_MAX_CORNERS = 2048
+CHARUCO_NO_ADJ = 0xFFFFFFFF
 STEP_NAMES = {0: "whole", 1: "decode_deferred", 2: "held_released_by_last", 3: "held_released_early", 4: "burst_last", 5: "held"}
 
 # every symbol include/aruco3_hip.h declares
@@ -40,6 +42,7 @@ SYMBOLS = [
     "a3_default_refine_config", "a3_set_corner_refinement", "a3_get_refined_corners", "a3_refine_corners",
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
+    "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
 INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
@@ -107,6 +110,16 @@ class DistortionRec(C.Structure):
                 ("max_residual_px", C.c_float)]
 
 
+class CharucoConfig(C.Structure):
+    """a3_charuco_config: ChArUco corners (an extension beyond the reference; include/aruco3_hip.h states the algorithm)"""
+    _fields_ = [("min_markers", C.c_uint32), ("refine", C.c_uint32), ("win_half", C.c_uint32), ("relative_win", C.c_float),
+                ("max_iterations", C.c_uint32), ("min_shift", C.c_float)]
+
+
+CHARUCO_CORNER_DTYPE = np.dtype([("frame", "<u4"), ("id", "<u4"), ("x", "<f4"), ("y", "<f4"), ("interp_x", "<f4"), ("interp_y", "<f4"),
+                                 ("markers_used", "<u4"), ("window", "<u4")])
+CHARUCO_POSE_DTYPE = np.dtype([("status", "<u4"), ("corners_used", "<u4"), ("iterations", "<u4"), ("reserved", "<u4"), ("rms_px", "<f4"),
+                               ("alt_rms_px", "<f4"), ("rotation", "<f4", (9,)), ("translation", "<f4", (3,))])
 BOARD_POSE_DTYPE = np.dtype([("status", "<u4"), ("markers_used", "<u4"), ("markers_rejected", "<u4"), ("iterations", "<u4"),
                              ("rms_px", "<f4"), ("alt_rms_px", "<f4"), ("rotation", "<f4", (9,)), ("translation", "<f4", (3,))])
 
@@ -276,6 +289,18 @@ def load():
         L.a3_get_undistorted_corners.argtypes = [vp, f32p, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.a3_undistort_points.restype = C.c_int
         L.a3_undistort_points.argtypes = [vp, f32p, C.c_size_t, C.POINTER(Intrinsics), C.POINTER(DistortionRec), f32p, f32p]
+    if hasattr(L, "a3_set_charuco"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack ChArUco)
+        L.a3_default_charuco_config.restype = None
+        L.a3_default_charuco_config.argtypes = [C.POINTER(CharucoConfig)]
+        L.a3_set_charuco.restype = C.c_int
+        L.a3_set_charuco.argtypes = [vp, f32p, u32p, C.c_size_t, C.POINTER(CharucoConfig)]
+        L.a3_get_charuco_corners.restype = C.c_int
+        L.a3_get_charuco_corners.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.a3_get_charuco_poses.restype = C.c_int
+        L.a3_get_charuco_poses.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.a3_interpolate_charuco.restype = C.c_int
+        L.a3_interpolate_charuco.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, u32p, f32p, C.c_size_t, vp,
+                                             C.c_size_t, C.POINTER(C.c_size_t)]
     L.a3_debug_discard_too_near.restype = C.c_int
     L.a3_debug_discard_too_near.argtypes = [vp, u32p, C.c_size_t, C.c_float, u32p, C.POINTER(C.c_size_t)]
     _lib = L
@@ -340,6 +365,12 @@ def default_distortion() -> DistortionRec:
     d = DistortionRec()
     load().a3_default_distortion(C.byref(d))
     return d
+
+
+def default_charuco_config() -> CharucoConfig:
+    cfg = CharucoConfig()
+    load().a3_default_charuco_config(C.byref(cfg))
+    return cfg
 
 
 def synth_render(device: int, frames: np.ndarray, markers: np.ndarray, width: int, height: int, paper: bool, black: float, white: float,
@@ -546,6 +577,56 @@ class Context:
         return out[0]
 
     # ---- lens distortion ----
+    # ---- ChArUco ----
+    def set_charuco(self, corners=None, adjacent_ids=None, cfg: "CharucoConfig" = None):
+        """a3_set_charuco: chessboard corners (n, 2) in board units and adjacent marker ids (n, 4); None / empty clears it"""
+        if corners is None or len(corners) == 0:
+            check(load().a3_set_charuco(self.handle, None, None, 0, None), self.handle)
+            return
+        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 2))
+        a = np.ascontiguousarray(np.asarray(adjacent_ids, dtype=np.uint32).reshape(-1, 4))
+        if a.shape[0] != c.shape[0]:
+            raise ValueError("set_charuco needs four adjacent ids per corner")
+        check(load().a3_set_charuco(self.handle, _p(c, C.c_float), _p(a, C.c_uint32), c.shape[0], C.byref(cfg) if cfg else None), self.handle)
+
+    def charuco_corners(self) -> np.ndarray:
+        """a3_get_charuco_corners: CHARUCO_CORNER_DTYPE records of the last collected batch, ordered by (frame, id)"""
+        L = load()
+        n = C.c_size_t(0)
+        rc = L.a3_get_charuco_corners(self.handle, None, 0, C.byref(n))
+        if rc not in (0, ERR_CAPACITY):
+            check(rc, self.handle)
+        out = np.zeros(max(n.value, 1), dtype=CHARUCO_CORNER_DTYPE)
+        check(L.a3_get_charuco_corners(self.handle, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)), self.handle)
+        return out[:n.value]
+
+    def charuco_poses(self) -> np.ndarray:
+        """a3_get_charuco_poses: CHARUCO_POSE_DTYPE records of the last collected pose batch, one per frame"""
+        L = load()
+        n = C.c_size_t(0)
+        rc = L.a3_get_charuco_poses(self.handle, None, 0, C.byref(n))
+        if rc not in (0, ERR_CAPACITY):
+            check(rc, self.handle)
+        out = np.zeros(max(n.value, 1), dtype=CHARUCO_POSE_DTYPE)
+        check(L.a3_get_charuco_poses(self.handle, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)), self.handle)
+        return out[:n.value]
+
+    def interpolate_charuco(self, pixels_ptr: int, memory: int, fmt: int, width: int, height: int, row_stride: int, ids, corners) -> np.ndarray:
+        """a3_interpolate_charuco (stand-alone, one frame): marker ids (n,) and raw pixel corners (n, 4, 2) -> CHARUCO_CORNER_DTYPE records"""
+        L = load()
+        i = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 8))
+        if c.shape[0] != i.size:
+            raise ValueError("interpolate_charuco needs four corners per id")
+        n = C.c_size_t(0)
+        args = (self.handle, C.c_void_p(pixels_ptr), memory, fmt, width, height, row_stride, _p(i, C.c_uint32), _p(c, C.c_float), i.size)
+        rc = L.a3_interpolate_charuco(*args, None, 0, C.byref(n))
+        if rc not in (0, ERR_CAPACITY):
+            check(rc, self.handle)
+        out = np.zeros(max(n.value, 1), dtype=CHARUCO_CORNER_DTYPE)
+        check(L.a3_interpolate_charuco(*args, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)), self.handle)
+        return out[:n.value]
+
     def set_distortion(self, d: "DistortionRec" = None):
         """a3_set_distortion: None (or model DIST_NONE) clears it; applies to pose batches submitted afterwards"""
         check(load().a3_set_distortion(self.handle, C.byref(d) if d is not None else None), self.handle)

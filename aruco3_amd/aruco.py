@@ -67,6 +67,10 @@ class Detection:
     candidates: List[List[Tuple[int, int]]] = field(default_factory=list)
     homographies: List[np.ndarray] = field(default_factory=list)
     markers: List[Marker] = field(default_factory=list)
+    # with a CharucoBoard as the detector's board (an extension): the chessboard corners found, ids (n,) uint32 ascending and
+    # raw image pixels (n, 2) float32 -- refined, or interpolated with CharucoConfig.refine = 0; None otherwise
+    charuco_ids: Optional[np.ndarray] = None
+    charuco_corners: Optional[np.ndarray] = None
 
 
 def _as_frames(image):
@@ -107,12 +111,14 @@ class Detector:
     """`Detector { config, dictionary }` (src/aruco.rs:46-49)."""
 
     def __init__(self, config: DetectorConfig = None, dictionary: ARDictionary = None, device: int = 0,
-                 refinement: Optional[CornerRefinement] = None, board=None):
+                 refinement: Optional[CornerRefinement] = None, board=None, charuco_config: Optional[_lib.CharucoConfig] = None):
         self.config = config or DetectorConfig()
         self.dictionary = dictionary or ARDictionary.new_from_named_dict("ARUCO")
         self.device = device
         self.refinement = refinement
         self.board = board   # aruco3_amd.board.Board: detect_batch_with_board_pose solves one pose per frame from it
+        # with a board.CharucoBoard: every call also returns the chessboard corners (a3_charuco_config; None: the library's defaults)
+        self.charuco_config = charuco_config
         self._ctx = None
         self._ctx_key = None
 
@@ -123,13 +129,21 @@ class Detector:
         return r is not None
 
     def _apply_board(self, ctx: _lib.Context) -> bool:
-        """hands the detector's board to the context before a pose call -> whether one is set"""
-        b = self.board
+        """hands the detector's board (and, for a CharucoBoard, its chessboard) to the context before a call -> whether one is set"""
+        b, cfg = self.board, self.charuco_config
+        key = (b, None if cfg is None else bytes(cfg))
         applied = getattr(self, "_board_applied", None)
-        if applied is None or applied[0] is not ctx or applied[1] is not b:   # (a3_set_board re-uploads the tables: only on a change)
-            ctx.set_board(None if b is None else b.ids, None if b is None else b.corners)
-            self._board_applied = (ctx, b)
+        if applied is None or applied[0] is not ctx or applied[1] != key:   # (a3_set_board re-uploads the tables: only on a change)
+            _set_board(ctx, b, cfg)
+            self._board_applied = (ctx, key)
         return b is not None
+
+    def _charuco(self, ctx: _lib.Context) -> bool:
+        """a CharucoBoard as the board: hands it to the context (every call then reports its corners) -> whether it is one"""
+        if not _is_charuco(self.board):
+            return False
+        self._apply_board(ctx)
+        return True
 
     def _apply_distortion(self, ctx: _lib.Context, intrinsics) -> bool:
         """hands the lens distortion of a pose call's intrinsics to the context before the call -> whether it is on"""
@@ -162,6 +176,7 @@ class Detector:
             ctx.set_stream(stream)
         ctx.set_debug_taps(populate)
         refine = self._apply_refinement(ctx)
+        charuco = self._charuco(ctx)
         markers, per = ctx.detect_batch(ptr, mem, fmt, w, h, rs, fs, n, out_cap)
         refined = ctx.refined_corners() if refine else None
         out = []
@@ -177,6 +192,8 @@ class Detector:
                 patches, ok, _, _ = ctx.homographies(f)
                 det.homographies = [p if o else np.zeros((1, 1), np.uint8) for p, o in zip(patches, ok)]  # src/aruco.rs:256
             out.append(det)
+        if charuco:
+            _fill_charuco(out, ctx.charuco_corners())
         return out
 
     def detect_batch_with_pose(self, images, marker_size_mm: float, intrinsics=None, stream: int = None, out_cap: int = 0):
@@ -191,6 +208,7 @@ class Detector:
         ctx.set_debug_taps(False)
         refine = self._apply_refinement(ctx)
         dist = self._apply_distortion(ctx, intrinsics)
+        charuco = self._charuco(ctx)
         intr = None
         if intrinsics is not None:
             ci = intrinsics
@@ -208,6 +226,8 @@ class Detector:
                 pp.append(tuple(MarkerPose(float(q[0]), q[1:10].reshape(3, 3).copy(), q[10:13].copy()) for q in poses[i]))
             pos += int(per[f])
             out.append((det, pp))
+        if charuco:
+            _fill_charuco([d for d, _ in out], ctx.charuco_corners())
         return out
 
     def detect_batch_with_board_pose(self, images, intrinsics=None, marker_size_mm: float = 1.0, stream: int = None, out_cap: int = 0):
@@ -234,7 +254,51 @@ class Detector:
         refined = ctx.refined_corners() if refine else None
         undist = ctx.undistorted_corners() if dist else None
         boards = ctx.board_poses()
-        return [(d, BoardPose._from(boards[f])) for f, d in enumerate(_detections(markers, per, refined, undist))]
+        dets = _detections(markers, per, refined, undist)
+        if _is_charuco(self.board):
+            _fill_charuco(dets, ctx.charuco_corners())
+        return [(d, BoardPose._from(boards[f])) for f, d in enumerate(dets)]
+
+    def detect_batch_with_charuco_pose(self, images, intrinsics=None, marker_size_mm: float = 1.0, stream: int = None, out_cap: int = 0):
+        """detect + the ChArUco corners + one ChArUco pose per frame (the detector's `board`, a CharucoBoard), solved on the device from
+        the frame's chessboard corners (include/aruco3_hip.h states the solve).  -> [(Detection, CharucoPose)]"""
+        from .board import CharucoPose
+
+        if not _is_charuco(self.board):
+            raise ValueError("detect_batch_with_charuco_pose needs Detector(board=CharucoBoard(...))")
+        ctx = self._context()
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
+        if stream is not None:
+            ctx.set_stream(stream)
+        ctx.set_debug_taps(False)
+        refine = self._apply_refinement(ctx)
+        dist = self._apply_distortion(ctx, intrinsics)
+        self._apply_board(ctx)
+        intr = None
+        if intrinsics is not None:
+            ci = intrinsics
+            intr = _lib.Intrinsics(ci.image_width, ci.image_height, ci.focal_x, ci.focal_y, ci.principal_x, ci.principal_y)
+        markers, per, _ = ctx.detect_batch_pose(ptr, mem, fmt, w, h, rs, fs, n, marker_size_mm, intr, out_cap)
+        refined = ctx.refined_corners() if refine else None
+        undist = ctx.undistorted_corners() if dist else None
+        dets = _detections(markers, per, refined, undist)
+        _fill_charuco(dets, ctx.charuco_corners())
+        poses = ctx.charuco_poses()
+        return [(d, CharucoPose._from(poses[f])) for f, d in enumerate(dets)]
+
+    def interpolate_charuco(self, image, ids, corners):
+        """stand-alone, one frame (a3_interpolate_charuco): the chessboard corners of the detector's CharucoBoard from caller-given
+        markers -- ids (n,) and raw pixel corners (n, 4, 2) -- refined on `image` as a batch refines them.  -> (ids (m,) uint32,
+        corners (m, 2) float32)"""
+        if not _is_charuco(self.board):
+            raise ValueError("interpolate_charuco needs Detector(board=CharucoBoard(...))")
+        ctx = self._context()
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(image)
+        if n != 1:
+            raise ValueError("interpolate_charuco takes one frame")
+        self._apply_board(ctx)
+        rec = ctx.interpolate_charuco(ptr, mem, fmt, w, h, rs, ids, corners)
+        return rec["id"].copy(), np.stack([rec["x"], rec["y"]], axis=1).astype(np.float32)
 
     def detect_batch_raw(self, images, stream: int = None, out_cap: int = 0):
         """Batch entry without Python object construction: (structured marker array, per-frame counts)."""
@@ -244,6 +308,28 @@ class Detector:
             ctx.set_stream(stream)
         self._apply_refinement(ctx)   # (the refined corners are not returned here: Context.refined_corners() has them)
         return ctx.detect_batch(ptr, mem, fmt, w, h, rs, fs, n, out_cap)
+
+
+def _is_charuco(board) -> bool:
+    from .board import CharucoBoard
+
+    return isinstance(board, CharucoBoard)
+
+
+def _set_board(ctx: _lib.Context, board, charuco_config=None) -> None:
+    """a3_set_board (which clears the ChArUco setting), then a3_set_charuco for a CharucoBoard"""
+    ctx.set_board(None if board is None else board.ids, None if board is None else board.corners)
+    if _is_charuco(board):
+        ctx.set_charuco(board.chessboard_corners, board.adjacent_ids, charuco_config)
+
+
+def _fill_charuco(dets: List[Detection], recs: np.ndarray) -> None:
+    """Detection.charuco_ids / .charuco_corners of each frame from the (frame, id)-ordered records of Context.charuco_corners()"""
+    bounds = np.searchsorted(recs["frame"], np.arange(len(dets) + 1))
+    for f, d in enumerate(dets):
+        r = recs[bounds[f]:bounds[f + 1]]
+        d.charuco_ids = r["id"].copy()
+        d.charuco_corners = np.stack([r["x"], r["y"]], axis=1).astype(np.float32).reshape(-1, 2)
 
 
 def _marker(m, refined=None, undist=None) -> Marker:
@@ -287,6 +373,7 @@ class BatchQueue:
         d = detector.dictionary
         self._ctxs = [_lib.Context(detector.config._c(), d.code_list, d.num_bits, d._tau, detector.device) for _ in range(depth)]
         self._refinement = detector.refinement   # (the detector's setting when the queue was made; each batch keeps the one in force at its submit)
+        self._board, self._charuco_config = detector.board, detector.charuco_config   # (likewise)
         self._refine_on = [False] * depth
         self._keep = [None] * depth
         self._gates = gates
@@ -313,6 +400,8 @@ class BatchQueue:
         ctx.set_debug_taps(False)
         ctx.set_corner_refinement(self._refinement._c() if self._refinement is not None else None)
         self._refine_on[k] = self._refinement is not None
+        if self._submitted < depth and self._board is not None:   # (each context's first batch: the board stays set on it)
+            _set_board(ctx, self._board, self._charuco_config)
         ctx.submit(ptr, mem, fmt, w, h, rs, fs, n, out_cap=out_cap or n * 64)
         self._keep[k] = keep
         self._submitted += 1
@@ -330,7 +419,10 @@ class BatchQueue:
         finally:
             self._keep[k] = None
         self.last_stepping = ctx.stats()["stepping"]
-        return _detections(markers, per, ctx.refined_corners() if self._refine_on[k] else None)
+        dets = _detections(markers, per, ctx.refined_corners() if self._refine_on[k] else None)
+        if _is_charuco(self._board):
+            _fill_charuco(dets, ctx.charuco_corners())
+        return dets
 
     def close(self) -> None:
         while self._in_flight:

@@ -3,7 +3,8 @@
 Not part of the reference: an extension whose contract include/aruco3_hip.h states.  A board is a set of markers of known ids whose
 corners lie on the plane z = 0 of the board's frame (x to the right, y up, corner 0 the top-left, as the per-marker IPPE solver's
 square).  `Detector(board=...)` hands the board to the device, and `Detector.detect_batch_with_board_pose` returns one `BoardPose`
-per frame, solved on the GPU from every board marker of that frame."""
+per frame, solved on the GPU from every board marker of that frame.  A `CharucoBoard` also yields its chessboard corners in every
+frame (Detection.charuco_ids / .charuco_corners) and, from `Detector.detect_batch_with_charuco_pose`, one `CharucoPose` per frame."""
 from dataclasses import dataclass
 from typing import Sequence, Tuple
 
@@ -105,3 +106,76 @@ class BoardPose:
     def apply_inverse_transform_to_points(self, points: Sequence[Tuple[float, float, float]]):
         p = np.asarray(points, dtype=np.float32).reshape(-1, 3)
         return [tuple(map(float, (self.rotation.T @ (v - self.translation)).astype(np.float32))) for v in p]
+
+
+class CharucoBoard(Board):
+    """A ChArUco board: a squares_x x squares_y chessboard of side square_length with a marker of side marker_length centred in each
+    white square.  Origin at the board's top-left outer corner, x right, y up (points of the board have y <= 0), z = 0.  Square (row 0,
+    column 0) is black (OpenCV's current, non-legacy pattern); markers sit in the squares with row + column odd, id first_id + k numbered
+    row-major from the top-left.  The chessboard corners are the (squares_x - 1)(squares_y - 1) inner corners, id r * (squares_x - 1) + c
+    row-major from the top-left; each names the markers of the two white squares that touch it (`adjacent_ids`, 4 per corner, padded
+    with CHARUCO_NO_ADJ).
+
+    Detecting the markers of a ChArUco board needs a small DetectorConfig.min_corner_separation_factor: each white square is a hole of
+    the black chessboard component, and its border is a quad candidate with a larger perimeter than the marker inside it, whose corners
+    lie about m * sqrt(2) px from the marker's (m = (square_length - marker_length) / 2 in pixels).  discard_too_near keeps the larger of
+    two quads closer than min_corner_separation_factor * (short image side), so with the default factor (0.1) every marker is dropped:
+    the factor must stay below m * sqrt(2) / short side (0.005 with squares of 40 px or more at marker_length / square_length <= 0.75
+    in a 1080p frame)."""
+
+    def __init__(self, squares_x: int, squares_y: int, square_length: float, marker_length: float, first_id: int = 0):
+        if squares_x < 2 or squares_y < 2:
+            raise ValueError("a ChArUco board needs at least 2 squares along each side")
+        if not 0 < marker_length < square_length:
+            raise ValueError("a ChArUco board needs 0 < marker_length < square_length")
+        n_corners = (squares_x - 1) * (squares_y - 1)
+        if n_corners > _lib.CHARUCO_MAX_CORNERS:
+            raise ValueError(f"a ChArUco board has at most {_lib.CHARUCO_MAX_CORNERS} chessboard corners")
+        s, ml = float(square_length), float(marker_length)
+        m = (s - ml) / 2
+        ids, corners, marker_of = [], [], {}
+        for r in range(squares_y):
+            for c in range(squares_x):
+                if (r + c) % 2 == 1:
+                    marker_of[(r, c)] = first_id + len(ids)
+                    x0, y0 = c * s + m, -r * s - m
+                    ids.append(first_id + len(ids))
+                    corners.append([(x0, y0), (x0 + ml, y0), (x0 + ml, y0 - ml), (x0, y0 - ml)])
+        self.squares_x, self.squares_y = squares_x, squares_y
+        self.square_length, self.marker_length = s, ml
+        cxy = np.zeros((n_corners, 2), np.float32)
+        adj = np.full((n_corners, 4), _lib.CHARUCO_NO_ADJ, np.uint32)
+        for r in range(squares_y - 1):
+            for c in range(squares_x - 1):
+                k = r * (squares_x - 1) + c
+                cxy[k] = ((c + 1) * s, -(r + 1) * s)
+                near = [marker_of[q] for q in ((r, c), (r, c + 1), (r + 1, c), (r + 1, c + 1)) if q in marker_of]
+                adj[k, :len(near)] = near
+        self.chessboard_corners = cxy
+        self.adjacent_ids = adj
+        super().__init__(ids, corners)
+
+    @property
+    def n_corners(self) -> int:
+        return int(self.chessboard_corners.shape[0])
+
+
+@dataclass
+class CharucoPose:
+    """One frame's ChArUco pose (a3_charuco_pose), board -> camera.  status BOARD_NONE: fewer than 4 corners or no usable start."""
+    status: int
+    corners_used: int
+    iterations: int
+    rms_px: float
+    alt_rms_px: float
+    rotation: np.ndarray      # 3x3 float32
+    translation: np.ndarray   # 3 float32, board units
+
+    @property
+    def ok(self) -> bool:
+        return self.status == _lib.BOARD_OK
+
+    @classmethod
+    def _from(cls, rec) -> "CharucoPose":
+        return cls(int(rec["status"]), int(rec["corners_used"]), int(rec["iterations"]), float(rec["rms_px"]), float(rec["alt_rms_px"]),
+                   np.array(rec["rotation"], dtype=np.float32).reshape(3, 3), np.array(rec["translation"], dtype=np.float32))

@@ -73,6 +73,13 @@ hipError_t launch_board_pose(hipStream_t, const a3_marker*, const uint32_t*, con
                              uint32_t, uint32_t, const uint16_t*, uint32_t, const void*, const a3_intrinsics*, uint32_t, uint32_t, a3_board_pose*);
 hipError_t launch_undistort_corners(hipStream_t, const a3_marker*, const float*, const unsigned int*, uint32_t, const a3_intrinsics&,
                                     const a3_distortion&, float*, float*);
+hipError_t launch_charuco_corners(hipStream_t, PixelSrc, uint32_t, uint32_t, const a3_marker*, const uint32_t*, const float*, const float*,
+                                  const unsigned int*, const uint32_t*, uint32_t, uint32_t, const uint16_t*, uint32_t, const void*, const float*,
+                                  const uint32_t*, uint32_t, uint32_t, uint32_t, const void*, const a3_intrinsics*, const a3_distortion*,
+                                  a3_charuco_corner*, uint32_t*, a3_charuco_corner*, float*);
+hipError_t launch_charuco_pose(hipStream_t, const a3_marker*, const float*, const unsigned int*, const uint32_t*, uint32_t, uint32_t, const uint16_t*,
+                               uint32_t, const void*, const float*, uint32_t, const uint32_t*, const a3_charuco_corner*, const float*,
+                               const a3_intrinsics*, uint32_t, uint32_t, a3_charuco_pose*);
 hipError_t launch_calc_tau(hipStream_t, const uint64_t*, uint32_t, unsigned int*);
 hipError_t launch_synth_render(hipStream_t, const a3_synth_frame*, uint32_t, const a3_synth_marker*, uint32_t, uint32_t, int, float, float, int,
                                uint8_t*, size_t, size_t);
@@ -141,6 +148,9 @@ struct Batch {
     bool board = false;          // a pose batch with a board set: k_board_pose runs behind k_pose
     a3_distortion dist{};        // lens distortion (model NONE: none)
     size_t undist_bytes = 0;     // 48 (8 corner floats + 4 residuals per marker) on a pose batch with distortion, else 0
+    bool charuco = false;        // ChArUco set: the corner stage runs behind the refinement (and k_charuco_pose behind k_board_pose)
+    a3_charuco_config charuco_cfg{};
+    uint32_t charuco_nc = 0, charuco_guess = 0;   // chessboard corners; records in the speculative read-back
     bool taps = false;           // debug taps: grey plane, patches, contours and the per-frame candidate counts are kept
     int profiling = 0, profile_every = 1;   // a3_set_profiling in force
     // enqueue_front
@@ -272,6 +282,22 @@ struct a3_ctx {
     DevBuf undist_buf;
     std::vector<float> h_undist, h_undist_res;
     bool undist_valid = false;  // the last collected batch ran with distortion: h_undist / h_undist_res hold its corners
+    // a3_set_charuco: the chessboard later batches capture (charuco_tab_h: [2 floats per corner | 4 adjacent ids per corner]) and its
+    // device copy, brought up to date at the next submit as the board's; charuco_prm: the refinement parameters built for charuco_prm_cfg
+    a3_charuco_config charuco_cfg{};
+    std::vector<uint32_t> charuco_tab_h;
+    uint32_t charuco_nc = 0;
+    uint64_t charuco_version = 0, charuco_dev_version = 0;
+    std::vector<uint32_t> charuco_tab_up;
+    a3_charuco_config charuco_prm_cfg{};
+    std::vector<float> charuco_prm;
+    // the last batch on the device: per-frame slots [n x nc records | n + 1 counts], the records in (frame, id) order, their undistorted
+    // pixels (pose batches with distortion) and the poses
+    DevBuf charuco_tab, charuco_tmp, charuco_buf, charuco_und, charuco_pose_buf;
+    std::vector<a3_charuco_corner> h_charuco;
+    std::vector<a3_charuco_pose> h_charuco_pose;
+    bool charuco_valid = false, charuco_pose_valid = false;
+    uint32_t last_charuco_total = 0;   // sizes the speculative record read-back of the next batch
     void* pinned = nullptr;
     size_t pinned_cap = 0;
     // debug taps: per-frame candidate counts of the last batch (before / after discard_too_near), read back with the results so
@@ -437,6 +463,26 @@ const void* refine_params_for(a3_ctx* ctx, const a3_refine_config& cfg) {
     return ctx->refine_prm.data();
 }
 
+// ChArUco: the per-frame slot records of charuco_tmp (the counts follow them), and where the read-back stages the results
+size_t charuco_slot_bytes(const Batch& b) { return ((size_t)b.n * b.charuco_nc * sizeof(a3_charuco_corner) + 255) & ~(size_t)255; }
+size_t charuco_stage_off(const Batch& b) {
+    return b.head_bytes + (size_t)b.guess * (sizeof(a3_marker) + b.pose_bytes + b.refine_bytes + b.undist_bytes) +
+           (b.board ? (size_t)b.n * sizeof(a3_board_pose) : 0);
+}
+size_t charuco_stage_bytes(const Batch& b) {
+    return b.charuco ? 16 + (size_t)b.charuco_guess * sizeof(a3_charuco_corner) + (b.want_pose ? (size_t)b.n * sizeof(a3_charuco_pose) : 0) : 0;
+}
+// the refinement kernel's parameters for the ChArUco setting `cfg` (its window and iteration settings; built once per setting)
+const void* charuco_params_for(a3_ctx* ctx, const a3_charuco_config& cfg) {
+    if (ctx->charuco_prm.empty() || memcmp(&ctx->charuco_prm_cfg, &cfg, sizeof cfg) != 0) {
+        ctx->charuco_prm.assign((refine_params_bytes() + 3) / 4, 0.0f);
+        const a3_refine_config rc{A3_REFINE_SUBPIX, cfg.win_half, cfg.relative_win, cfg.max_iterations, cfg.min_shift};
+        refine_params(ctx->charuco_prm.data(), rc, 0);
+        ctx->charuco_prm_cfg = cfg;
+    }
+    return ctx->charuco_prm.data();
+}
+
 // candidates -> markers -> read-back of one batch, on stream `st` (the context's stream, or its decode stream when deferred)
 int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     const uint32_t S = ctx->cfg.homography_sample_size;
@@ -473,6 +519,15 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
                                         b.pose_intr, b.dist, ctx->undist_buf.as<float>(), ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
     // the float corners the poses are solved from: undistorted, else refined, else none (the integer corners)
     const float* fcorners = b.undist_bytes ? ctx->undist_buf.as<float>() : b.refine_bytes ? ctx->refined_buf.as<float>() : nullptr;
+    const uint32_t* charuco_counts = b.charuco ? reinterpret_cast<const uint32_t*>(ctx->charuco_tmp.as<uint8_t>() + charuco_slot_bytes(b)) : nullptr;
+    float* charuco_und = b.charuco && b.want_pose && b.undist_bytes ? ctx->charuco_und.as<float>() : nullptr;
+    if (b.charuco)   // the chessboard corners of the same markers (their raw refined or integer corners), sampled as the refinement samples
+        A3_HIP(launch_charuco_corners(st, b.src, b.W, b.H, ctx->markers_ptr, nullptr, nullptr, b.refine_bytes ? ctx->refined_buf.as<float>() : nullptr,
+                                      d_marker_total, ctx->per_frame, b.marker_cap, b.n, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes,
+                                      ctx->board_slot_rec.p, ctx->charuco_tab.as<float>(), ctx->charuco_tab.as<uint32_t>() + 2 * (size_t)b.charuco_nc,
+                                      b.charuco_nc, b.charuco_cfg.min_markers, b.charuco_cfg.refine, charuco_params_for(ctx, b.charuco_cfg),
+                                      &b.pose_intr, &b.dist, ctx->charuco_tmp.as<a3_charuco_corner>(), const_cast<uint32_t*>(charuco_counts),
+                                      ctx->charuco_buf.as<a3_charuco_corner>(), charuco_und));
     if (b.want_pose) {   // IPPE on the device-resident marker list (src/pose.rs:52-81), no extra round trip
         const a3_intrinsics& in = b.pose_intr;
         if (fcorners)   // from float corners (k_pose modes 3 / 4)
@@ -486,6 +541,11 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
             A3_HIP(launch_board_pose(st, ctx->markers_ptr, nullptr, nullptr, fcorners, d_marker_total,
                                      ctx->per_frame, b.marker_cap, b.n, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p,
                                      b.pose_has_intr ? &in : nullptr, b.W, b.H, ctx->board_buf.as<a3_board_pose>()));
+        if (b.charuco)   // one ChArUco pose per frame from the records just written, the starts as the board pose takes them
+            A3_HIP(launch_charuco_pose(st, ctx->markers_ptr, fcorners, d_marker_total, ctx->per_frame, b.marker_cap, b.n,
+                                       ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p, ctx->charuco_tab.as<float>(),
+                                       b.charuco_nc, charuco_counts, ctx->charuco_buf.as<a3_charuco_corner>(), charuco_und,
+                                       b.pose_has_intr ? &in : nullptr, b.W, b.H, ctx->charuco_pose_buf.as<a3_charuco_pose>()));
     }
     if (b.prof >= 2) A3_HIP(hipEventRecord(ctx->ev[3], st));
     // ---- results: one copy of [scratch | counters | per-frame counts | `guess` markers], then the poses and (taps) the counts ----
@@ -504,6 +564,14 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
         A3_HIP(hipMemcpyAsync(hu, ctx->undist_buf.p, (size_t)b.guess * 32, hipMemcpyDeviceToHost, st));
         A3_HIP(hipMemcpyAsync(hu + (size_t)b.guess * 32, ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8, (size_t)b.guess * 16,
                               hipMemcpyDeviceToHost, st));
+    }
+    if (b.charuco) {   // (staged behind the undistorted corners: the total, `charuco_guess` records, then the poses of a pose batch)
+        uint8_t* hc = hp + charuco_stage_off(b);
+        A3_HIP(hipMemcpyAsync(hc, charuco_counts + b.n, 4, hipMemcpyDeviceToHost, st));
+        A3_HIP(hipMemcpyAsync(hc + 16, ctx->charuco_buf.p, (size_t)b.charuco_guess * sizeof(a3_charuco_corner), hipMemcpyDeviceToHost, st));
+        if (b.want_pose)
+            A3_HIP(hipMemcpyAsync(hc + 16 + (size_t)b.charuco_guess * sizeof(a3_charuco_corner), ctx->charuco_pose_buf.p,
+                                  (size_t)b.n * sizeof(a3_charuco_pose), hipMemcpyDeviceToHost, st));
     }
     if (b.taps) {   // Detection.candidates / .homographies will be asked for frame by frame: their counts travel now
         A3_HIP(hipMemcpyAsync(ctx->pinned_counts, ctx->cand_count, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
@@ -614,8 +682,15 @@ int ensure_back_buffers(a3_ctx* ctx, const Batch& b, size_t head_bytes) {
     if (b.refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)b.marker_cap * b.refine_bytes));
     if (board_bytes) A3_HIP(ctx->board_buf.ensure(board_bytes));
     if (b.undist_bytes) A3_HIP(ctx->undist_buf.ensure((size_t)b.marker_cap * b.undist_bytes));
+    if (b.charuco) {
+        const size_t recs = (size_t)b.n * b.charuco_nc;
+        A3_HIP(ctx->charuco_tmp.ensure(charuco_slot_bytes(b) + ((size_t)b.n + 1) * 4));
+        A3_HIP(ctx->charuco_buf.ensure(std::max<size_t>(recs, 1) * sizeof(a3_charuco_corner)));
+        if (b.want_pose) A3_HIP(ctx->charuco_pose_buf.ensure((size_t)b.n * sizeof(a3_charuco_pose)));
+        if (b.want_pose && b.undist_bytes) A3_HIP(ctx->charuco_und.ensure(std::max<size_t>(recs, 1) * 8));
+    }
     if (int rc = ensure_pinned(ctx, head_bytes + (size_t)b.guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + b.refine_bytes + b.undist_bytes) + board_bytes +
-                                    (1 << 16))) return rc;
+                                    charuco_stage_bytes(b) + (1 << 16))) return rc;
     if (b.taps && ctx->pinned_counts_cap < (size_t)b.n * 8) {
         if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
         ctx->pinned_counts = nullptr; ctx->pinned_counts_cap = 0;
@@ -1022,6 +1097,24 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         const a3_board_pose* hb = reinterpret_cast<const a3_board_pose*>(hp + head_bytes + (size_t)guess * (sizeof(a3_marker) + pose_bytes + refine_bytes));
         ctx->h_board.assign(hb, hb + n);
     }
+    if (b.charuco) {   // (read now, as the board poses)
+        const uint8_t* hc = hp + charuco_stage_off(b);
+        uint32_t charuco_total = 0;
+        memcpy(&charuco_total, hc, 4);
+        ctx->h_charuco.resize(charuco_total);
+        const size_t staged = std::min<uint32_t>(charuco_total, b.charuco_guess);
+        if (staged) memcpy(ctx->h_charuco.data(), hc + 16, staged * sizeof(a3_charuco_corner));
+        if (b.want_pose) {
+            const a3_charuco_pose* hq = reinterpret_cast<const a3_charuco_pose*>(hc + 16 + (size_t)b.charuco_guess * sizeof(a3_charuco_corner));
+            ctx->h_charuco_pose.assign(hq, hq + n);
+        }
+        if (charuco_total > staged) {   // the guess was short: the rest of the records, straight from the device
+            A3_HIP(hipMemcpyAsync(ctx->h_charuco.data() + staged, ctx->charuco_buf.as<a3_charuco_corner>() + staged,
+                                  (charuco_total - staged) * sizeof(a3_charuco_corner), hipMemcpyDeviceToHost, st));
+            A3_HIP(hipStreamSynchronize(st));
+        }
+        ctx->last_charuco_total = charuco_total;
+    }
     const uint32_t tap_contours = n_chunks ? hc[0].contours : 0u; const uint64_t tap_points = n_chunks ? hc[0].points : 0ull;
     if (total > guess) {   // the guess was short: the staging area grows (the head has been consumed) and the whole list is fetched
         if (int rc = ensure_pinned(ctx, (size_t)total * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes + undist_bytes) + (1 << 16))) return rc;
@@ -1052,6 +1145,8 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     }
     ctx->undist_valid = undist_bytes != 0;
     ctx->board_valid = b.board;
+    ctx->charuco_valid = b.charuco;
+    ctx->charuco_pose_valid = b.charuco && b.want_pose;
     if (b.taps) {
         const uint32_t* hc32 = reinterpret_cast<const uint32_t*>(ctx->pinned_counts);
         ctx->h_cand_pre.assign(hc32, hc32 + n);
@@ -1207,7 +1302,8 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->contours, &ctx->cyc_start_off, &ctx->points, &ctx->zero_blk, &ctx->cands,
                       &ctx->pre_xy, &ctx->fin_xy, &ctx->fin_count, &ctx->work, &ctx->outs, &ctx->proj, &ctx->patches, &ctx->cand_big,
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
-                      &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf};
+                      &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
+                      &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1357,6 +1453,16 @@ static int upload_board(a3_ctx* ctx) {
     return A3_OK;
 }
 
+// the chessboard's device table for the ChArUco setting in force, when it is not current (as upload_board)
+static int upload_charuco(a3_ctx* ctx) {
+    if (ctx->charuco_dev_version == ctx->charuco_version) return A3_OK;
+    ctx->charuco_tab_up = ctx->charuco_tab_h;
+    A3_HIP(ctx->charuco_tab.ensure(ctx->charuco_tab_up.size() * 4));
+    A3_HIP(hipMemcpyAsync(ctx->charuco_tab.p, ctx->charuco_tab_up.data(), ctx->charuco_tab_up.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    ctx->charuco_dev_version = ctx->charuco_version;
+    return A3_OK;
+}
+
 // Starts a batch: its record (a3_ctx::batch) takes the call and every setting in force now, the frames are staged on the device, and
 // the board's tables are brought up to date (no batch of this context is in flight).  -> A3_OK, an error, or kNothingToDo.
 static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
@@ -1375,14 +1481,23 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
         b.dist = ctx->dist;
         b.undist_bytes = 12 * sizeof(float);
     }
+    b.charuco = ctx->charuco_nc != 0;
+    if (b.charuco) {
+        b.charuco_cfg = ctx->charuco_cfg;
+        b.charuco_nc = ctx->charuco_nc;
+        b.charuco_guess = (uint32_t)std::min<uint64_t>((uint64_t)n_frames * b.charuco_nc,
+                                                       (uint64_t)ctx->last_charuco_total + ctx->last_charuco_total / 4 + 64);
+    }
     b.taps = ctx->debug_taps;
     b.profiling = ctx->profiling; b.profile_every = ctx->profile_every;
     ctx->board_valid = false;
     ctx->undist_valid = false;
+    ctx->charuco_valid = false; ctx->charuco_pose_valid = false;
     b.row_stride = row_stride; b.frame_stride = frame_stride;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &b.row_stride, &b.frame_stride, n_frames, &b.pixels);
     if (rc != A3_OK) return rc;
-    if (b.board) { if (int urc = upload_board(ctx)) return urc; }
+    if (b.board || b.charuco) { if (int urc = upload_board(ctx)) return urc; }
+    if (b.charuco) { if (int urc = upload_charuco(ctx)) return urc; }
     ctx->force_host_plan = false;
     ctx->reruns = 0; ctx->released_others = 0;
     return A3_OK;
@@ -1395,6 +1510,8 @@ static void finish_trivial(a3_ctx* ctx, uint32_t* per_frame_count) {
     ctx->h_refined.clear(); ctx->refined_valid = b.refine_bytes != 0;
     ctx->h_board.assign(b.n, a3_board_pose{}); ctx->board_valid = b.board;
     ctx->h_undist.clear(); ctx->h_undist_res.clear(); ctx->undist_valid = b.undist_bytes != 0;
+    ctx->h_charuco.clear(); ctx->charuco_valid = b.charuco;
+    ctx->h_charuco_pose.assign(b.want_pose ? b.n : 0, a3_charuco_pose{}); ctx->charuco_pose_valid = b.charuco && b.want_pose;
 }
 
 static int run_batch_with_retries(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
@@ -2051,6 +2168,9 @@ int a3_set_board(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size
     ctx->board_ids.assign(ids, ids + n);
     ctx->board_slots.swap(slots);
     ctx->board_version++;
+    ctx->charuco_nc = 0;   // (a ChArUco setting names ids of the board it was checked against)
+    ctx->charuco_tab_h.clear();
+    ctx->charuco_version++;
     return A3_OK;
 }
 
@@ -2095,6 +2215,124 @@ int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corner
                              ctx->n_codes, ctx->board_slot_rec.p, intr, image_width, image_height, ctx->tmp_b.as<a3_board_pose>()));
     A3_HIP(hipMemcpyAsync(out, ctx->tmp_b.p, sizeof(a3_board_pose), hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+// ---- ChArUco boards (an extension beyond the reference; contract in include/aruco3_hip.h) ----
+void a3_default_charuco_config(a3_charuco_config* cfg) {
+    if (!cfg) return;
+    *cfg = a3_charuco_config{2, 1, 5, 0.5f, 30, 0.01f};
+}
+
+static int check_charuco_config(a3_ctx* ctx, const a3_charuco_config& c) {
+    if (c.min_markers < 1 || c.min_markers > 4) return fail(ctx, A3_ERR_INVALID, "a3_charuco_config.min_markers must be in 1..4");
+    if (c.refine > 1) return fail(ctx, A3_ERR_INVALID, "a3_charuco_config.refine must be 0 or 1");
+    if (c.win_half < 1 || c.win_half > 10) return fail(ctx, A3_ERR_INVALID, "a3_charuco_config.win_half must be in 1..10");
+    if (!(c.relative_win >= 0.0f) || !std::isfinite(c.relative_win)) return fail(ctx, A3_ERR_INVALID, "a3_charuco_config.relative_win must be finite and >= 0");
+    if (c.max_iterations > 100) return fail(ctx, A3_ERR_INVALID, "a3_charuco_config.max_iterations must be at most 100");
+    if (!(c.min_shift >= 0.0f) || !std::isfinite(c.min_shift)) return fail(ctx, A3_ERR_INVALID, "a3_charuco_config.min_shift must be finite and >= 0");
+    return A3_OK;
+}
+
+int a3_set_charuco(a3_ctx* ctx, const float* corners_xy, const uint32_t* adjacent_ids, size_t n_corners, const a3_charuco_config* cfg) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (n_corners == 0) {
+        ctx->charuco_nc = 0; ctx->charuco_tab_h.clear(); ctx->charuco_version++;
+        return A3_OK;
+    }
+    if (n_corners > A3_CHARUCO_MAX_CORNERS) return fail(ctx, A3_ERR_INVALID, "a3_set_charuco: more than A3_CHARUCO_MAX_CORNERS corners");
+    if (!corners_xy || !adjacent_ids) return fail(ctx, A3_ERR_INVALID, "a3_set_charuco: null corners or adjacent ids");
+    if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_set_charuco: no board is set (a3_set_board)");
+    a3_charuco_config c;
+    a3_default_charuco_config(&c);
+    if (cfg) c = *cfg;
+    if (int rc = check_charuco_config(ctx, c)) return rc;
+    std::vector<uint8_t> on_board(ctx->n_codes, 0);
+    for (uint32_t id : ctx->board_ids) on_board[id] = 1;
+    std::vector<uint32_t> tab(6 * n_corners);
+    for (size_t k = 0; k < n_corners; k++) {
+        if (!std::isfinite(corners_xy[2 * k]) || !std::isfinite(corners_xy[2 * k + 1]))
+            return fail(ctx, A3_ERR_INVALID, "a3_set_charuco: a corner is not finite");
+        for (int j = 0; j < 4; j++) {
+            const uint32_t id = adjacent_ids[4 * k + j];
+            if (id != 0xFFFFFFFFu && (id >= ctx->n_codes || !on_board[id]))
+                return fail(ctx, A3_ERR_INVALID, "a3_set_charuco: an adjacent id is not on the board (a3_set_board)");
+        }
+    }
+    memcpy(tab.data(), corners_xy, n_corners * 2 * sizeof(float));
+    memcpy(tab.data() + 2 * n_corners, adjacent_ids, n_corners * 4 * sizeof(uint32_t));
+    ctx->charuco_tab_h.swap(tab);
+    ctx->charuco_nc = (uint32_t)n_corners;
+    ctx->charuco_cfg = c;
+    ctx->charuco_version++;
+    return A3_OK;
+}
+
+int a3_get_charuco_corners(a3_ctx* ctx, a3_charuco_corner* dst, size_t cap, size_t* n) {
+    if (!ctx || !n || (!dst && cap)) return A3_ERR_INVALID;
+    *n = 0;
+    if (!ctx->charuco_valid) return fail(ctx, A3_ERR_INVALID, "a3_get_charuco_corners: the last collected batch ran without ChArUco");
+    *n = ctx->h_charuco.size();
+    if (*n > cap) return fail(ctx, A3_ERR_CAPACITY, "a3_get_charuco_corners: cap is smaller than the number of corners");
+    if (*n) memcpy(dst, ctx->h_charuco.data(), *n * sizeof(a3_charuco_corner));
+    return A3_OK;
+}
+
+int a3_get_charuco_poses(a3_ctx* ctx, a3_charuco_pose* dst, size_t cap_frames, size_t* n) {
+    if (!ctx || !n || (!dst && cap_frames)) return A3_ERR_INVALID;
+    *n = 0;
+    if (!ctx->charuco_pose_valid)
+        return fail(ctx, A3_ERR_INVALID, "a3_get_charuco_poses: the last collected batch was not a pose batch with ChArUco set");
+    *n = ctx->h_charuco_pose.size();
+    if (*n > cap_frames) return fail(ctx, A3_ERR_CAPACITY, "a3_get_charuco_poses: cap_frames is smaller than the number of frames");
+    if (*n) memcpy(dst, ctx->h_charuco_pose.data(), *n * sizeof(a3_charuco_pose));
+    return A3_OK;
+}
+
+int a3_interpolate_charuco(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
+                           const uint32_t* ids, const float* corners_xy, size_t n_markers, a3_charuco_corner* dst, size_t cap, size_t* n) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!n || (!dst && cap) || (n_markers && (!ids || !corners_xy))) return fail(ctx, A3_ERR_INVALID, "a3_interpolate_charuco: null argument");
+    *n = 0;
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_interpolate_charuco: a submitted batch has not been collected");
+    if (ctx->charuco_nc == 0) return fail(ctx, A3_ERR_INVALID, "a3_interpolate_charuco: ChArUco is not set (a3_set_charuco)");
+    if (width == 0 || height == 0) return fail(ctx, A3_ERR_INVALID, "a3_interpolate_charuco: empty image");
+    if (n_markers > (1u << 20)) return fail(ctx, A3_ERR_INVALID, "a3_interpolate_charuco: more than 2^20 markers in one call");
+    for (size_t k = 0; k < n_markers * 8; k++)
+        if (!std::isfinite(corners_xy[k])) return fail(ctx, A3_ERR_INVALID, "a3_interpolate_charuco: a marker corner is not finite");
+    size_t frame_stride = 0;
+    const uint8_t* d_pixels = nullptr;
+    const int src = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, 1, &d_pixels);
+    if (src != A3_OK) return src;
+    if (int urc = upload_board(ctx)) return urc;
+    if (int urc = upload_charuco(ctx)) return urc;
+    const uint32_t nc = ctx->charuco_nc;
+    const size_t id_bytes = (n_markers * 4 + 255) & ~(size_t)255, pts_bytes = n_markers * 8 * sizeof(float);
+    const size_t rec_bytes = ((size_t)nc * sizeof(a3_charuco_corner) + 255) & ~(size_t)255;
+    A3_HIP(ctx->tmp_a.ensure(std::max<size_t>(id_bytes + pts_bytes, 256)));
+    A3_HIP(ctx->tmp_c.ensure(2 * rec_bytes + 256));
+    uint32_t* d_ids = ctx->tmp_a.as<uint32_t>();
+    float* d_pts = reinterpret_cast<float*>(ctx->tmp_a.as<uint8_t>() + id_bytes);
+    a3_charuco_corner* d_slots = ctx->tmp_c.as<a3_charuco_corner>();
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(ctx->tmp_c.as<uint8_t>() + rec_bytes);
+    a3_charuco_corner* d_out = reinterpret_cast<a3_charuco_corner*>(ctx->tmp_c.as<uint8_t>() + rec_bytes + 256);
+    if (n_markers) {
+        A3_HIP(hipMemcpyAsync(d_ids, ids, n_markers * 4, hipMemcpyHostToDevice, ctx->stream));
+        A3_HIP(hipMemcpyAsync(d_pts, corners_xy, pts_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    A3_HIP(launch_charuco_corners(ctx->stream, PixelSrc{d_pixels, row_stride, frame_stride, fmt}, width, height, nullptr, d_ids, d_pts, nullptr, nullptr,
+                                  nullptr, (uint32_t)n_markers, 1u, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p,
+                                  ctx->charuco_tab.as<float>(), ctx->charuco_tab.as<uint32_t>() + 2 * (size_t)nc, nc, ctx->charuco_cfg.min_markers,
+                                  ctx->charuco_cfg.refine, charuco_params_for(ctx, ctx->charuco_cfg), nullptr, nullptr, d_slots, d_counts, d_out, nullptr));
+    uint32_t total = 0;
+    A3_HIP(hipMemcpyAsync(&total, d_counts + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    *n = total;
+    if (total > cap) return fail(ctx, A3_ERR_CAPACITY, "a3_interpolate_charuco: cap is smaller than the number of corners");
+    if (total) {
+        A3_HIP(hipMemcpyAsync(dst, d_out, (size_t)total * sizeof(a3_charuco_corner), hipMemcpyDeviceToHost, ctx->stream));
+        A3_HIP(hipStreamSynchronize(ctx->stream));
+    }
     return A3_OK;
 }
 

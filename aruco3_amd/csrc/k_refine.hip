@@ -2,55 +2,16 @@
 // keeps the integer contour corners: an extension stated in include/aruco3_hip.h, restated on the CPU by tests/refine_oracle.c
 // (a3o_refine_corners), which this kernel matches bit for bit.
 //
-// One wave64 per corner, four per workgroup (the four corners of one marker, or four consecutive caller corners).  The integer grey
-// levels any allowed estimate can touch are loaded into LDS once; every iteration after that is LDS and VALU only.  The estimate and
-// the five sums are wave-uniform (the xor butterfly leaves the same bits in every lane), so the iteration loop never diverges.
+// One wave64 per corner, four per workgroup (the four corners of one marker, or four consecutive caller corners).  The tile load and
+// the iteration below are a3_subpix.h's subpix_load_tile / subpix_iterate written out in place: called as functions they leave the
+// same arithmetic but a different schedule and register assignment in this kernel, whose code is kept as it was measured.
 #include <algorithm>
 #include <cmath>
 
 #include "a3_common.h"
+#include "a3_subpix.h"
 
 namespace a3 {
-
-constexpr int kRefineMaxWin = 10;
-// Estimates stay within w of the start q0 (the revert rule), samples lie within w + 1 of an estimate, and a bilinear sample reads
-// floor(x) and floor(x) + 1: 4w + 4 columns from floor(q0.x) - 2w - 1.  One guard column / row on each side absorbs the rounding
-// of c + i in float: 4w + 6, 46 at w = 10 (2116 bytes per wave).
-constexpr int kRefineTile = 4 * kRefineMaxWin + 6;
-
-struct RefineParams {
-    uint32_t win_half, max_iterations, cells;
-    float relative_win, min_shift;
-    float g[kRefineMaxWin + 1][2 * kRefineMaxWin + 1];   // g[w][i + w] = (float)exp(-(double)(i*i) / (double)(w*w)), host libm
-};
-
-// the contract's window: win_half, or min(win_half, max(2, floor(relative_win * cell_px))) (NaN -> 2)
-__device__ __forceinline__ int refine_window(const RefineParams& p, float cell_px) {
-    const int wh = (int)p.win_half;
-    if (!(p.relative_win > 0.0f)) return wh;
-    const float t = floorf(p.relative_win * cell_px);
-    const int v = t >= 2.0f ? (t >= (float)wh ? wh : (int)t) : 2;
-    return min(v, wh);
-}
-
-// into_luma8 grey level of pixel (x, y) of a frame (the grey plane K1 wrote, or the caller's pixel: same integers)
-__device__ __forceinline__ uint32_t refine_grey(const uint8_t* __restrict__ frame, unsigned long long row_stride, int fmt, uint32_t x, uint32_t y) {
-    const uint8_t* row = frame + (size_t)y * row_stride;
-    if (fmt == A3_FMT_L8 || fmt == kFmtGreyPlane) return row[x];
-    if (fmt == A3_FMT_RGB8) { const uint8_t* q = row + 3u * (size_t)x; return luma_of(q[0], q[1], q[2]); }
-    const uint8_t* q = row + 4u * (size_t)x;
-    return fmt == A3_FMT_BGRA8 ? luma_of(q[2], q[1], q[0]) : luma_of(q[0], q[1], q[2]);
-}
-
-// bilinear sample at (x, y) from the wave's tile (origin ox, oy; border replicate is baked into the tile), the contract's order
-__device__ __forceinline__ float refine_sample(const uint8_t* __restrict__ tile, int T, int ox, int oy, float x, float y) {
-    const float x0f = floorf(x), y0f = floorf(y);
-    const float fx = x - x0f, fy = y - y0f;
-    const int tx = min(max((int)x0f - ox, 0), T - 2), ty = min(max((int)y0f - oy, 0), T - 2);   // (a guard: never active, see kRefineTile)
-    const uint8_t* r = tile + ty * T + tx;
-    const float i00 = (float)r[0], i01 = (float)r[1], i10 = (float)r[T], i11 = (float)r[T + 1];
-    return (1.0f - fy) * ((1.0f - fx) * i00 + fx * i01) + fy * ((1.0f - fx) * i10 + fx * i11);
-}
 
 // markers != nullptr: the accepted markers of a batch (min(n, *n_dev) of them), 4 corners each, window from the quad's cell size.
 // markers == nullptr: n caller corners `pts` of frame 0, window from cell_px[k] (nullable).  out: x, y per corner, in corner order.

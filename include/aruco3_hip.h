@@ -409,6 +409,77 @@ int  a3_get_undistorted_corners(a3_ctx *ctx, float *dst_xy, float *residual_px, 
 int  a3_undistort_points(a3_ctx *ctx, const float *xy, size_t n, const a3_intrinsics *intr, const a3_distortion *d, float *out_xy,
                          float *residual_px);
 
+/* ChArUco boards.  NOT in the reference: an opt-in extension (OpenCV's interpolateCornersCharuco with local homographies, and the board
+ * pose from the interpolated corners), off by default; with it not set no launch, buffer, copy or result of a batch changes.  A ChArUco
+ * board is a chessboard with a marker in each white square; its n_corners inner chessboard corners (x, y in board units, z = 0, the
+ * board convention above) each name up to 4 adjacent markers (the markers of the white squares touching it; 0xFFFFFFFF = none).  The
+ * markers themselves are a board of a3_set_board, which must hold every adjacent id; a3_set_board clears the ChArUco setting.
+ * Caveat (discard_too_near): each white square is a hole of the black chessboard component, and its border is a quad candidate with a
+ * larger perimeter than the marker inside it, its corners about m * sqrt(2) px from the marker's (m = (square - marker) / 2 in px).
+ * discard_too_near keeps the larger of two candidates closer than min_corner_separation_factor * (short image side): with the default
+ * factor (0.1) every marker of a ChArUco board is dropped.  Detect ChArUco boards with a factor below m * sqrt(2) / short side.
+ * With ChArUco set, EVERY batch (detection-only batches included) reports the board's chessboard corners found in each frame, fixed as
+ * follows -- tests/charuco_oracle.c a3o_charuco_corners restates it:
+ *   1. correspondences: the frame's markers whose id is on the board; an id seen more than once in the frame is dropped in all its
+ *      instances.  Image corners are raw image pixels, never undistorted: the refined corners with a3_set_corner_refinement on, else the
+ *      integer a3_marker corners;
+ *   2. per used marker, a homography board -> image: imageproc's from_control_points exactly as the decode stage solves it (8 x 8 system
+ *      in f64 from `from` = the board marker's 4 corners, `to` = its 4 image corners, LU with partial pivoting, cast to f32, h8 = 1); a
+ *      singular system (a zero pivot, or |det| < 1e-10 of the f32 matrix, where from_control_points finds no inverse) leaves the marker
+ *      out.  A board point (X, Y) projects to  den = (h6*X + h7*Y) + 1;  x = ((h0*X + h1*Y) + h2) / den;  y = ((h3*X + h4*Y) + h5) / den;
+ *   3. per corner, the adjacent markers that are used and have a homography, in adjacency order; fewer than min_markers of them: the
+ *      corner is not reported.  interp = (sum of their projections, summed in adjacency order from 0) / (float)count.  A corner whose
+ *      interp is not finite or lies outside [0, W-1] x [0, H-1] is not reported;
+ *   4. refine = 1: the iteration of a3_refine_config above, verbatim (grey levels, sampling, weights, sums, revert and stop rules), from
+ *      q0 = interp with w = win_half, or (relative_win > 0) min(win_half, max(2, floorf(relative_win * d))), d = the smallest
+ *      sqrtf(dx*dx + dy*dy) from interp to the 4 image corners of each marker counted in 3 (markers in adjacency order, corners 0..3);
+ *   5. one a3_charuco_corner per reported corner, ordered by frame, then id.
+ * And every a3_detect_batch_pose* batch solves one a3_charuco_pose per frame (k_charuco_pose, behind k_board_pose): the board pose
+ * contract above (its LM, sums, butterfly, A3_BOARD_MAX_EVALS, A3_BOARD_REL_TOL, rms_px / alt_rms_px, choice of the kept start) with
+ *   - the two IPPE starts of the board contract, from the frame's board markers (undistorted corners with a distortion set);
+ *   - as correspondences the frame's reported corners in record order: (X, Y, 0) and the normalised image point of (x, y), first
+ *     undistorted by the a3_distortion routine when a distortion is set (a +inf residual keeps the position); the lane sums run over
+ *     the frame's records l, l + 64, ...;
+ *   - status A3_BOARD_NONE (zeros elsewhere, corners_used set) with fewer than 4 reported corners or no finite start.
+ * a3_pack_detections records keep their layout: ChArUco results are not gathered across ranks. */
+#define A3_CHARUCO_MAX_CORNERS 2048
+typedef struct a3_charuco_config {
+    uint32_t min_markers;     /* 2; 1 .. 4: adjacent markers a corner needs to be reported (OpenCV's minMarkers) */
+    uint32_t refine;          /* 1: cornerSubPix on the interpolated corner; 0: report the interpolation */
+    uint32_t win_half;        /* 5, 1 .. 10 */
+    float    relative_win;    /* 0.5; 0 = always win_half */
+    uint32_t max_iterations;  /* 30, at most 100 */
+    float    min_shift;       /* 0.01 px; finite, >= 0 */
+} a3_charuco_config;
+typedef struct a3_charuco_corner {   /* 32 bytes */
+    uint32_t frame, id;
+    float    x, y;                   /* reported corner: refined (or interpolated with refine = 0), raw image pixels */
+    float    interp_x, interp_y;     /* the interpolation the refinement started from */
+    uint32_t markers_used;           /* adjacent markers that took part */
+    uint32_t window;                 /* refinement half-width w used (0 with refine = 0) */
+} a3_charuco_corner;
+typedef struct a3_charuco_pose {     /* one per frame, board -> camera */
+    uint32_t status;                 /* A3_BOARD_NONE / A3_BOARD_OK */
+    uint32_t corners_used, iterations, reserved;
+    float    rms_px, alt_rms_px;
+    float    rotation[9];
+    float    translation[3];
+} a3_charuco_pose;
+/* min_markers 2, refine 1, win_half 5, relative_win 0.5, max_iterations 30, min_shift 0.01 */
+void a3_default_charuco_config(a3_charuco_config *cfg);
+/* applies to batches submitted after the call; needs a board (a3_set_board) holding every adjacent id; n_corners == 0 clears it.
+ * corners_xy: 2 floats per corner (board units, z = 0); adjacent_ids: 4 per corner, 0xFFFFFFFF = none; cfg NULL: the defaults */
+int  a3_set_charuco(a3_ctx *ctx, const float *corners_xy, const uint32_t *adjacent_ids, size_t n_corners, const a3_charuco_config *cfg);
+/* the last collected batch's corners, ordered by (frame, id).  A3_ERR_INVALID when that batch ran without ChArUco, A3_ERR_CAPACITY when
+ * cap is short (*n says how many there are). */
+int  a3_get_charuco_corners(a3_ctx *ctx, a3_charuco_corner *dst, size_t cap, size_t *n);
+/* the last collected a3_detect_batch_pose* batch's ChArUco poses, one per frame (A3_ERR_INVALID / A3_ERR_CAPACITY as above) */
+int  a3_get_charuco_poses(a3_ctx *ctx, a3_charuco_pose *dst, size_t cap_frames, size_t *n);
+/* stand-alone, one frame: the corners from n_markers caller-given markers (ids, 8 float corners each, raw pixels, batch order) on the
+ * same kernels, sampling `pixels` for the refinement.  Needs ChArUco set; synchronous; not while a submitted batch is in flight. */
+int  a3_interpolate_charuco(a3_ctx *ctx, const void *pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
+                            const uint32_t *ids, const float *corners_xy, size_t n_markers, a3_charuco_corner *dst, size_t cap, size_t *n);
+
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);
 int  a3_calculate_tau(int device, const uint64_t *codes, size_t n_codes, uint8_t *tau);

@@ -146,6 +146,46 @@ pub struct A3BoardPose {
     pub translation: [f32; 3],
 }
 
+/// a3_charuco_config: ChArUco chessboard corners (not in the reference; include/aruco3_hip.h states the interpolation and refinement)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3CharucoConfig {
+    pub min_markers: u32,
+    pub refine: u32,
+    pub win_half: u32,
+    pub relative_win: f32,
+    pub max_iterations: u32,
+    pub min_shift: f32,
+}
+
+/// a3_charuco_corner: one chessboard corner found in a frame, raw image pixels
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3CharucoCorner {
+    pub frame: u32,
+    pub id: u32,
+    pub x: f32,
+    pub y: f32,
+    pub interp_x: f32,
+    pub interp_y: f32,
+    pub markers_used: u32,
+    pub window: u32,
+}
+
+/// a3_charuco_pose: one pose per frame from its chessboard corners, board -> camera
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3CharucoPose {
+    pub status: u32,
+    pub corners_used: u32,
+    pub iterations: u32,
+    pub reserved: u32,
+    pub rms_px: f32,
+    pub alt_rms_px: f32,
+    pub rotation: [f32; 9],
+    pub translation: [f32; 3],
+}
+
 /// a3_distortion: OpenCV's rational lens model (not in the reference; include/aruco3_hip.h states the undistortion)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -278,6 +318,13 @@ extern "C" {
     pub fn a3_get_undistorted_corners(ctx: *mut A3Ctx, dst_xy: *mut f32, residual_px: *mut f32, cap_markers: usize, n: *mut usize) -> c_int;
     pub fn a3_undistort_points(ctx: *mut A3Ctx, xy: *const f32, n: usize, intr: *const A3Intrinsics, d: *const A3Distortion, out_xy: *mut f32,
                                residual_px: *mut f32) -> c_int;
+    pub fn a3_default_charuco_config(cfg: *mut A3CharucoConfig);
+    pub fn a3_set_charuco(ctx: *mut A3Ctx, corners_xy: *const f32, adjacent_ids: *const u32, n_corners: usize, cfg: *const A3CharucoConfig) -> c_int;
+    pub fn a3_get_charuco_corners(ctx: *mut A3Ctx, dst: *mut A3CharucoCorner, cap: usize, n: *mut usize) -> c_int;
+    pub fn a3_get_charuco_poses(ctx: *mut A3Ctx, dst: *mut A3CharucoPose, cap_frames: usize, n: *mut usize) -> c_int;
+    pub fn a3_interpolate_charuco(ctx: *mut A3Ctx, pixels: *const c_void, memory: c_int, fmt: c_int, width: u32, height: u32, row_stride: usize,
+                                  ids: *const u32, corners_xy: *const f32, n_markers: usize, dst: *mut A3CharucoCorner, cap: usize,
+                                  n: *mut usize) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;

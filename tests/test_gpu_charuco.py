@@ -1,0 +1,394 @@
+"""ChArUco boards on the MI355X (k_charuco_interp / k_charuco_refine / k_charuco_pose; a3_set_charuco, a3_get_charuco_corners,
+a3_get_charuco_poses, a3_interpolate_charuco): records bit-equal to the CPU restatement (tests/charuco_oracle.c) in every frame format
+and layout and through every scheduling path, poses equal to it within the board tolerances, the stand-alone call equal to the batch,
+nothing else changed by the setting, the ABI's checks, a read-back larger than its guess, and the accuracy on rendered boards."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import board_util as bu
+from tests import charuco_oracle as co
+from tests import charuco_util as cu
+from tests.test_gpu_corner_refine import _layouts, _lib_luma
+from tests.util import marker_tuples
+
+pytestmark = pytest.mark.gpu
+
+W, H = bu.W1080, bu.H1080
+INTR = (1400.0, 1400.0, 960.0, 540.0)
+LENS = (-0.05, 0.01, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+
+def _torch():
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("needs the MI355X")
+    return torch
+
+
+def _dict():
+    from aruco3_amd import ARDictionary
+
+    return ARDictionary.new_from_named_dict("ARUCO_DEFAULT")
+
+
+def _board(sx=5, sy=7):
+    from aruco3_amd.board import CharucoBoard
+
+    return CharucoBoard(sx, sy, 40.0, 28.0, first_id=5)
+
+
+def _ctx(d, board, refine=False, cfg=None, charuco=True):
+    from aruco3_amd import _lib
+
+    ctx = _lib.Context(cu.config(), d.code_list, d.num_bits, d._tau)
+    if refine:
+        ctx.set_corner_refinement(_lib.default_refine_config())
+    ctx.set_board(board.ids, board.corners)
+    if charuco:
+        ctx.set_charuco(board.chessboard_corners, board.adjacent_ids, cfg)
+    return ctx
+
+
+def _ocfg(cfg):
+    from aruco3_amd import _lib
+
+    c = cfg or _lib.default_charuco_config()
+    return co.Config(c.min_markers, c.refine, c.win_half, c.relative_win, c.max_iterations, c.min_shift)
+
+
+_SCENES = {}
+
+
+def _frames(n=4, seed=11):
+    """n rendered 1080p frames of the 5 x 7 board (tilted 15 .. 50 degrees; frame 1 without two markers, frame 2 with a duplicate)
+    -> (device tensor, host array, scenes)"""
+    torch = _torch()
+    key = (n, seed)
+    if key not in _SCENES:
+        b = _board()
+        scenes = []
+        for k, (R, t) in enumerate(cu.tilted_poses(b, n, seed=seed, tilt=(15.0, 35.0), distance=800.0)):
+            drop = (3, 8) if k % 4 == 1 else ()
+            extra = ()
+            if k % 4 == 2:   # a second instance of the board's id of slot 6, away from the board
+                extra = ((bu.square_quad(150.0, 150.0, 60.0), int(b.ids[6])),)
+            scenes.append(cu.Scene(b, R, t, drop=drop, extra=extra))
+        dev = cu.render(scenes, _dict())
+        torch.cuda.synchronize()
+        _SCENES[key] = (dev, dev.cpu().numpy(), scenes)
+    return _SCENES[key]
+
+
+def _expect(board, frames_host, markers, per, refined=None, cfg=None):
+    """the oracle's records of a batch: every frame's markers (batch order; refined corners when given, else the integer ones)"""
+    out, pos = [], 0
+    for f in range(len(per)):
+        cnt = int(per[f])
+        m = markers[pos: pos + cnt]
+        px = refined[pos: pos + cnt] if refined is not None else m["corners"].reshape(-1, 4, 2).astype(np.float32)
+        grey = _lib_luma(np.asarray(frames_host[f]))
+        out.append(co.corners(board, m["id"], px, grey=grey, config=_ocfg(cfg), frame=f))
+        pos += cnt
+    return np.concatenate(out) if out else np.zeros(0, co.CORNER_DTYPE)
+
+
+def _same(got, want):
+    got = np.ascontiguousarray(got)
+    want = np.ascontiguousarray(want, dtype=got.dtype)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    bad = np.nonzero(got.view(np.uint32).reshape(len(got), -1) != want.view(np.uint32).reshape(len(want), -1))[0] if len(got) else []
+    assert len(bad) == 0, (got[bad[:3]], want[bad[:3]])
+
+
+@pytest.mark.parametrize("refine_markers", [False, True])
+@pytest.mark.parametrize("refine", [0, 1])
+@pytest.mark.parametrize("taps", [False, True])
+def test_records_equal_oracle(refine_markers, refine, taps):
+    from aruco3_amd import _lib
+
+    dev, host, scenes = _frames()
+    b = _board()
+    cfg = _lib.default_charuco_config()
+    cfg.refine = refine
+    ctx = _ctx(_dict(), b, refine_markers, cfg)
+    ctx.set_debug_taps(taps)
+    m, per = ctx.detect_batch(dev.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, W * H * 3, len(scenes))
+    got = ctx.charuco_corners()
+    want = _expect(b, host, m, per, ctx.refined_corners() if refine_markers else None, cfg)
+    _same(got, want)
+    assert np.all(np.diff(got["frame"].astype(np.int64) * 4096 + got["id"]) > 0)
+    assert len(got) >= 24
+    if refine:
+        assert np.all((got["window"] >= 2) & (got["window"] <= 5))
+    else:
+        assert np.array_equal(got["x"], got["interp_x"]) and np.all(got["window"] == 0)
+
+
+@pytest.mark.parametrize("fmt_name", ["rgb", "rgba", "bgra", "l8"])
+def test_formats_layouts_and_memory(fmt_name):
+    from aruco3_amd import _lib
+
+    torch = _torch()
+    dev, host, scenes = _frames()
+    host = host[:2]
+    b = _board()
+    base = None
+    for fmt, buf, off, rs, fs, px in _layouts(host, fmt_name):
+        for memory in (_lib.MEM_HOST, _lib.MEM_DEVICE):
+            ctx = _ctx(_dict(), b, refine=True)
+            if memory == _lib.MEM_HOST:
+                ptr, keep = buf.ctypes.data + off, buf
+            else:
+                keep = torch.from_numpy(buf).cuda()
+                torch.cuda.synchronize()
+                ptr = keep.data_ptr() + off
+            m, per = ctx.detect_batch(ptr, memory, fmt, W, H, rs, fs, 2)
+            got = ctx.charuco_corners()
+            if base is None:
+                base = got.copy()
+                _same(got, _expect(b, host, m, per, ctx.refined_corners()))
+                assert len(got) >= 12
+            _same(got, base)
+            del keep
+
+
+@pytest.mark.parametrize("use_intr, lens", [(False, False), (True, False), (True, True)])
+def test_poses_equal_oracle(use_intr, lens):
+    from aruco3_amd import _lib
+
+    dev, host, scenes = _frames()
+    b = _board()
+    ctx = _ctx(_dict(), b, refine=True)
+    if lens:
+        d = _lib.default_distortion()
+        d.k1, d.k2 = LENS[0], LENS[1]
+        ctx.set_distortion(d)
+    intr = _lib.Intrinsics(W, H, *INTR) if use_intr else None
+    m, per, _ = ctx.detect_batch_pose(dev.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, W * H * 3, len(scenes), 28.0, intr)
+    recs = ctx.charuco_corners()
+    poses = ctx.charuco_poses()
+    px_all = ctx.undistorted_corners()[0] if lens else ctx.refined_corners()
+    dist = None if not lens else tuple(LENS) + (20.0, 0.1)
+    assert len(poses) == len(scenes)
+    pos = solved = 0
+    errs = []
+    for f in range(len(scenes)):
+        cnt = int(per[f])
+        r = recs[recs["frame"] == f]
+        want = co.pose(b, m["id"][pos: pos + cnt], px_all[pos: pos + cnt], r, (W, H), INTR if use_intr else None, dist)
+        got = poses[f]
+        pos += cnt
+        assert got["status"] == want["status"] and got["corners_used"] == want["corners_used"] == len(r)
+        if not got["status"]:
+            continue
+        solved += 1
+        assert np.abs(got["rotation"] - want["rotation"]).max() < 1e-4
+        assert np.linalg.norm(got["translation"] - want["translation"]) <= 1e-4 * np.linalg.norm(want["translation"])
+        assert abs(float(got["rms_px"]) - float(want["rms_px"])) < 1e-3
+        if use_intr and not lens:
+            errs.append(bu.rotation_error_deg(got["rotation"].reshape(3, 3), scenes[f].R))
+    assert solved >= 2
+    if errs:   # (against the truth: a frame showing few corners may be off by degrees, the median is not)
+        assert np.median(errs) < 0.5
+
+
+def test_standalone_equals_batch():
+    from aruco3_amd import _lib
+
+    dev, host, scenes = _frames()
+    b = _board()
+    ctx = _ctx(_dict(), b, refine=True)
+    m, per = ctx.detect_batch(dev.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, W * H * 3, len(scenes))
+    recs = ctx.charuco_corners()
+    refined = ctx.refined_corners()
+    pos = 0
+    for f in range(len(scenes)):
+        cnt = int(per[f])
+        for memory, ptr, keep in ((_lib.MEM_DEVICE, dev[f].data_ptr(), None), (_lib.MEM_HOST, host[f].ctypes.data, host[f])):
+            got = ctx.interpolate_charuco(ptr, memory, _lib.FMT_RGB8, W, H, W * 3, m["id"][pos: pos + cnt], refined[pos: pos + cnt])
+            want = recs[recs["frame"] == f].copy()
+            want["frame"] = 0
+            _same(got, want)
+        pos += cnt
+
+
+def test_setting_charuco_changes_nothing_else():
+    from aruco3_amd import _lib
+
+    dev, host, scenes = _frames()
+    b = _board()
+    intr = _lib.Intrinsics(W, H, *INTR)
+    out = []
+    for charuco in (False, True):
+        ctx = _ctx(_dict(), b, refine=True, charuco=charuco)
+        d = _lib.default_distortion()
+        d.k1 = LENS[0]
+        ctx.set_distortion(d)
+        m, per, poses = ctx.detect_batch_pose(dev.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, W * H * 3, len(scenes), 28.0, intr)
+        und, res = ctx.undistorted_corners()
+        out.append((marker_tuples(m), per.copy(), poses.copy(), ctx.refined_corners().copy(), und.copy(), res.copy(), ctx.board_poses().copy()))
+    a, c = out
+    assert a[0] == c[0] and np.array_equal(a[1], c[1])
+    for x, y in zip(a[2:], c[2:]):
+        assert np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8))
+
+
+def test_abi_checks():
+    from aruco3_amd import _lib
+
+    L = _lib.load()
+    dev, host, scenes = _frames()
+    b = _board()
+    d = _dict()
+    ctx = _lib.Context(cu.config(), d.code_list, d.num_bits, d._tau)
+    with pytest.raises(_lib.A3Error, match="no board"):
+        ctx.set_charuco(b.chessboard_corners, b.adjacent_ids)
+    ctx.set_board(b.ids[:-1], b.corners[:-1])   # the last marker is missing from the board
+    with pytest.raises(_lib.A3Error, match="not on the board"):
+        ctx.set_charuco(b.chessboard_corners, b.adjacent_ids)
+    ctx.set_board(b.ids, b.corners)
+    many = np.zeros((_lib.CHARUCO_MAX_CORNERS + 1, 2), np.float32)
+    with pytest.raises(_lib.A3Error, match="A3_CHARUCO_MAX_CORNERS"):
+        ctx.set_charuco(many, np.full((len(many), 4), _lib.CHARUCO_NO_ADJ, np.uint32))
+    bad = _lib.default_charuco_config()
+    bad.min_markers = 5
+    with pytest.raises(_lib.A3Error, match="min_markers"):
+        ctx.set_charuco(b.chessboard_corners, b.adjacent_ids, bad)
+    run = lambda: ctx.detect_batch(dev.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, W * H * 3, 2)   # noqa: E731
+    run()
+    for getter in (ctx.charuco_corners, ctx.charuco_poses):   # a batch without ChArUco
+        with pytest.raises(_lib.A3Error, match="without ChArUco|ChArUco set"):
+            getter()
+    ctx.set_charuco(b.chessboard_corners, b.adjacent_ids)
+    run()
+    recs = ctx.charuco_corners()
+    assert len(recs) > 1
+    with pytest.raises(_lib.A3Error, match="ChArUco set"):   # a detection-only batch has no poses
+        ctx.charuco_poses()
+    n = C.c_size_t(0)
+    one = np.zeros(1, _lib.CHARUCO_CORNER_DTYPE)
+    assert L.a3_get_charuco_corners(ctx.handle, one.ctypes.data_as(C.c_void_p), 1, C.byref(n)) == _lib.ERR_CAPACITY and n.value == len(recs)
+    ctx.set_board(b.ids, b.corners)   # clears the ChArUco setting
+    run()
+    with pytest.raises(_lib.A3Error, match="without ChArUco"):
+        ctx.charuco_corners()
+    with pytest.raises(_lib.A3Error, match="not set"):
+        ctx.interpolate_charuco(dev.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, [], np.zeros((0, 4, 2), np.float32))
+
+
+def test_records_beyond_the_read_back_guess():
+    """a 20 x 20 board (361 corners, 200 markers) seen whole in all 256 frames: 92 416 records, far beyond the first batch's guess"""
+    from aruco3_amd import _lib
+    from aruco3_amd.board import CharucoBoard
+
+    torch = _torch()
+    b = CharucoBoard(20, 20, 50.0, 35.0)
+    R, t = bu.board_pose_facing(b, 0.0, 0.0, 0.0, 1400.0)   # 50 px squares, frontal
+    sc = cu.Scene(b, R, t)
+    one = cu.render([sc], _dict())
+    frames = one.expand(256, -1, -1, -1).contiguous()
+    torch.cuda.synchronize()
+    ctx = _ctx(_dict(), b, refine=False)
+    expect = None
+    for _ in range(2):   # the first batch re-reads the records, the second fits the guess the first one left
+        m, per = ctx.detect_batch(frames.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, W * H * 3, 256, out_cap=256 * 256)
+        assert np.all(per == 200)
+        recs = ctx.charuco_corners()
+        assert len(recs) == 256 * 361
+        if expect is None:
+            expect = _expect(b, one.cpu().numpy(), m[:200], per[:1])
+            assert len(expect) == 361
+        for f in (0, 1, 100, 255):
+            r = recs[f * 361:(f + 1) * 361].copy()
+            assert np.all(r["frame"] == f)
+            r["frame"] = 0
+            _same(r, expect)
+
+
+def test_submit_collect_deferred_and_gates():
+    from aruco3_amd import _lib
+    from aruco3_amd.aruco import BatchQueue, Detector, DetectorConfig
+
+    torch = _torch()
+    dev, host, scenes = _frames()
+    b = _board()
+    n = len(scenes)
+    args = (dev.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, W * H * 3, n)
+    ref = _ctx(_dict(), b, refine=True)
+    m0, per0 = ref.detect_batch(*args)
+    want = ref.charuco_corners()
+    _same(want, _expect(b, host, m0, per0, ref.refined_corners()))
+    # submit / collect on one context
+    c1 = _ctx(_dict(), b, refine=True)
+    c1.submit(*args)
+    c1.collect()
+    _same(c1.charuco_corners(), want)
+    # two contexts on one stream: the first batch's decode stage is deferred behind the second's contour stage
+    s = torch.cuda.Stream()
+    ca, cb = _ctx(_dict(), b, refine=True), _ctx(_dict(), b, refine=True)
+    for c in (ca, cb, ca, cb):   # (each context's first batches of this shape)
+        c.detect_batch(*args)
+    ca.set_stream(s.cuda_stream)
+    cb.set_stream(s.cuda_stream)
+    ca.submit(*args)
+    cb.submit(*args)
+    ca.collect()
+    cb.collect()
+    assert ca.stats()["stepping"] == "decode_deferred"
+    _same(ca.charuco_corners(), want)
+    _same(cb.charuco_corners(), want)
+    # BatchQueue over several contexts, free-running and with a3_order_after gates, against the detector's own call
+    from aruco3_amd.aruco import CornerRefinement
+
+    cfg = DetectorConfig.default()
+    cfg.min_corner_separation_factor = bu.MIN_CORNER_SEPARATION_FACTOR
+    det = Detector(cfg, _dict(), refinement=CornerRefinement(), board=b)
+    sync = det.detect_batch(dev)
+    for f, dt in enumerate(sync):
+        r = want[want["frame"] == f]
+        assert np.array_equal(dt.charuco_ids, r["id"]) and np.array_equal(dt.charuco_corners[:, 0], r["x"])
+    for gates in (False, True):
+        q = BatchQueue(det, depth=3, gates=gates)
+        got = []
+        for _ in range(6):
+            if q.full:
+                got.append(q.collect())
+            q.submit(dev)
+        while len(q):
+            got.append(q.collect())
+        q.close()
+        assert len(got) == 6
+        for dets in got:
+            for a, c in zip(dets, sync):
+                assert np.array_equal(a.charuco_ids, c.charuco_ids)
+                assert np.array_equal(a.charuco_corners.view(np.uint32), c.charuco_corners.view(np.uint32))
+
+
+def test_accuracy_on_rendered_boards():
+    """1080p, tilted 15 .. 50 degrees: the ChArUco pose against the marker board pose on the same frames (both from refined corners)"""
+    from aruco3_amd import _lib
+
+    torch = _torch()
+    b = _board()
+    poses = cu.tilted_poses(b, 32, seed=5)
+    scenes = [cu.Scene(b, R, t) for R, t in poses]
+    dev = cu.render(scenes, _dict())
+    torch.cuda.synchronize()
+    ctx = _ctx(_dict(), b, refine=True)
+    intr = _lib.Intrinsics(W, H, *INTR)
+    ctx.detect_batch_pose(dev.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, W * H * 3, len(scenes), 28.0, intr)
+    cp, bp, recs = ctx.charuco_poses(), ctx.board_poses(), ctx.charuco_corners()
+    ec = [bu.rotation_error_deg(cp[f]["rotation"].reshape(3, 3), sc.R) for f, sc in enumerate(scenes) if cp[f]["status"]]
+    eb = [bu.rotation_error_deg(bp[f]["rotation"].reshape(3, 3), sc.R) for f, sc in enumerate(scenes) if bp[f]["status"]]
+    truth = np.concatenate([cu.true_corners(b, sc.R, sc.t)[recs["id"][recs["frame"] == f]] for f, sc in enumerate(scenes)])
+    err = np.hypot(recs["x"] - truth[:, 0], recs["y"] - truth[:, 1])
+    print(f"charuco corners: {len(recs)} median {np.median(err):.4f} px; rotation median charuco {np.median(ec):.4f} deg, "
+          f"marker board {np.median(eb):.4f} deg over {len(ec)} / {len(eb)} frames")
+    # first measured run: 538 corners, median 0.056 px; rotation median 0.031 deg (ChArUco) against 0.217 deg (marker board),
+    # 31 / 32 frames solved (one frame showed fewer than 4 corners)
+    assert len(ec) >= 0.9 * len(scenes) and len(eb) == len(scenes)
+    assert np.median(err) < 0.15
+    assert np.median(ec) < 0.5 * np.median(eb)
