@@ -26,6 +26,10 @@ def __getattr__(name):
         from . import board
 
         return getattr(board, name)
+    if name in ("Calibration", "calibrate_camera", "calibrate_cameras", "calibrate_camera_board", "calibrate_camera_charuco"):
+        from . import calibration
+
+        return getattr(calibration, name)
     if name == "pose":
         import importlib
 

@@ -29,6 +29,11 @@ BOARD_MAX_MARKERS = 1024
 DIST_NONE, DIST_RATIONAL = 0, 1
 CHARUCO_MAX_CORNERS = 2048
 CHARUCO_NO_ADJ = 0xFFFFFFFF
+# a3_calibrate_cameras (include/aruco3_hip.h A3_CALIB_*)
+CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST, CALIB_FIX_K3, CALIB_RATIONAL_MODEL, CALIB_USE_INTRINSIC_GUESS = 1, 2, 4, 8, 16
+CALIB_OK, CALIB_TOO_FEW, CALIB_NO_INIT, CALIB_NOT_FINITE = 1, 2, 3, 4
+CALIB_VIEW_USED, CALIB_VIEW_TOO_FEW_POINTS, CALIB_VIEW_DEGENERATE = 1, 2, 3
+CALIB_MAX_POINTS, CALIB_MAX_VIEWS, CALIB_MAX_CAMERAS, CALIB_MAX_CALL_VIEWS = 4096, 4096, 1024, 65536
 STEP_NAMES = {0: "whole", 1: "decode_deferred", 2: "held_released_by_last", 3: "held_released_early", 4: "burst_last", 5: "held"}
 
 # every symbol include/aruco3_hip.h declares
@@ -43,6 +48,7 @@ SYMBOLS = [
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
+    "a3_calibrate_cameras",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
 INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
@@ -122,6 +128,23 @@ CHARUCO_POSE_DTYPE = np.dtype([("status", "<u4"), ("corners_used", "<u4"), ("ite
                                ("alt_rms_px", "<f4"), ("rotation", "<f4", (9,)), ("translation", "<f4", (3,))])
 BOARD_POSE_DTYPE = np.dtype([("status", "<u4"), ("markers_used", "<u4"), ("markers_rejected", "<u4"), ("iterations", "<u4"),
                              ("rms_px", "<f4"), ("alt_rms_px", "<f4"), ("rotation", "<f4", (9,)), ("translation", "<f4", (3,))])
+
+
+class CalibCamera(C.Structure):
+    """a3_calib_camera: one calibration problem (an extension beyond the reference; include/aruco3_hip.h states the algorithm)"""
+    _fields_ = [("image_width", C.c_uint32), ("image_height", C.c_uint32), ("first_view", C.c_uint32), ("n_views", C.c_uint32),
+                ("flags", C.c_uint32), ("max_iterations", C.c_uint32), ("guess", Intrinsics), ("guess_distortion", DistortionRec)]
+
+
+class CalibResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("views_used", C.c_uint32), ("points_used", C.c_uint32), ("iterations", C.c_uint32),
+                ("converged", C.c_uint32), ("reserved", C.c_uint32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("dist", C.c_double * 8), ("std_dev", C.c_double * 12), ("rms_px", C.c_double),
+                ("intrinsics", Intrinsics), ("distortion", DistortionRec), ("reserved2", C.c_uint32)]
+
+
+class CalibView(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("points", C.c_uint32), ("rms_px", C.c_float), ("rotation", C.c_float * 9), ("translation", C.c_float * 3)]
 
 
 class Stats(C.Structure):
@@ -301,6 +324,10 @@ def load():
         L.a3_interpolate_charuco.restype = C.c_int
         L.a3_interpolate_charuco.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, u32p, f32p, C.c_size_t, vp,
                                              C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "a3_calibrate_cameras"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack calibration)
+        L.a3_calibrate_cameras.restype = C.c_int
+        L.a3_calibrate_cameras.argtypes = [vp, C.POINTER(CalibCamera), C.c_size_t, u32p, C.c_size_t, f32p, f32p, C.POINTER(CalibResult),
+                                           C.POINTER(CalibView)]
     L.a3_debug_discard_too_near.restype = C.c_int
     L.a3_debug_discard_too_near.argtypes = [vp, u32p, C.c_size_t, C.c_float, u32p, C.POINTER(C.c_size_t)]
     _lib = L
@@ -652,6 +679,20 @@ class Context:
         check(load().a3_undistort_points(self.handle, _p(xy, C.c_float), xy.shape[0], C.byref(intrinsics), C.byref(d), _p(out, C.c_float),
                                          _p(res, C.c_float)), self.handle)
         return out, res
+
+    # ---- camera calibration ----
+    def calibrate_cameras(self, cams, view_offsets, object_xy, image_xy, with_views: bool = True):
+        """a3_calibrate_cameras: cams (a CalibCamera array), view_offsets (n_views + 1), object / image points (n, 2) ->
+        (CalibResult array, CalibView array or None)"""
+        off = np.ascontiguousarray(np.asarray(view_offsets, dtype=np.uint32).reshape(-1))
+        obj = np.ascontiguousarray(np.asarray(object_xy, dtype=np.float32).reshape(-1, 2))
+        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 2))
+        n_views = max(off.size - 1, 0)
+        res = (CalibResult * max(len(cams), 1))()
+        views = (CalibView * max(n_views, 1))() if with_views else None
+        check(load().a3_calibrate_cameras(self.handle, cams, len(cams), _p(off, C.c_uint32), n_views, _p(obj, C.c_float), _p(img, C.c_float), res,
+                                          views), self.handle)
+        return res, views
 
     # ---- Detection.grey / thresholded / candidates / homographies of the last batch ----
     def download_grey(self, frame: int, w: int, h: int, thresholded: bool = False) -> np.ndarray:

@@ -1,0 +1,212 @@
+"""Camera calibration on the device (a3_calibrate_cameras): intrinsics and OpenCV's lens model from views of a planar target.
+
+Not part of the reference: an extension whose algorithm include/aruco3_hip.h fixes to the bit (Zhang's initialisation, then a
+Levenberg-Marquardt bundle over intrinsics, lens model and per-view poses, in f64, one workgroup per camera).  The result's
+`intrinsics` is a `CameraIntrinsics` whose `distortion` is set, ready for `Detector.detect_batch_with_pose` and the board / ChArUco pose
+calls.  Views are lists of correspondences: board points (x, y) in board units on z = 0, image points in pixels."""
+import threading
+from dataclasses import dataclass, field
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+from .pinhole import CameraIntrinsics, Distortion
+
+PARAM_NAMES = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")
+
+
+@dataclass
+class ViewResult:
+    """one view (a3_calib_view): status CALIB_VIEW_USED / _TOO_FEW_POINTS (< 4) / _DEGENERATE; the pose board -> camera"""
+    status: int
+    points: int
+    rms_px: float
+    rotation: np.ndarray      # 3x3 float32
+    translation: np.ndarray   # 3 float32, board units
+
+    @property
+    def used(self) -> bool:
+        return self.status == _lib.CALIB_VIEW_USED
+
+
+@dataclass
+class Calibration:
+    """one camera (a3_calib_result).  status CALIB_OK, or CALIB_TOO_FEW / _NO_INIT / _NOT_FINITE with zeros elsewhere."""
+    status: int
+    intrinsics: Optional[CameraIntrinsics]
+    params: np.ndarray        # float64 (12,): fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6
+    std_devs: np.ndarray      # float64 (12,), same order; 0 for fixed parameters, +inf where the problem is not observable
+    rms_px: float
+    iterations: int
+    converged: bool
+    views_used: int
+    points_used: int
+    views: List[ViewResult] = field(default_factory=list)
+    inliers: Optional[List[np.ndarray]] = None   # with outlier_passes: per view, the points the last solve used (bool)
+
+    @property
+    def ok(self) -> bool:
+        return self.status == _lib.CALIB_OK
+
+    @property
+    def distortion_coeffs(self) -> np.ndarray:
+        """OpenCV's distCoeffs order: k1 k2 p1 p2 k3 k4 k5 k6"""
+        return self.params[4:].copy()
+
+    @classmethod
+    def _from(cls, r, views) -> "Calibration":
+        p = np.array([r.fx, r.fy, r.cx, r.cy] + list(r.dist), np.float64)
+        intr = None
+        if r.status == _lib.CALIB_OK:
+            d = r.distortion
+            intr = CameraIntrinsics(r.intrinsics.image_width, r.intrinsics.image_height, r.intrinsics.focal_x, r.intrinsics.focal_y,
+                                    r.intrinsics.principal_x, r.intrinsics.principal_y,
+                                    distortion=Distortion(d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6, int(d.iterations), d.max_residual_px))
+        vr = [ViewResult(int(v.status), int(v.points), float(v.rms_px), np.array(v.rotation, np.float32).reshape(3, 3),
+                         np.array(v.translation, np.float32)) for v in views]
+        return cls(int(r.status), intr, p, np.array(r.std_dev, np.float64), float(r.rms_px), int(r.iterations), bool(r.converged),
+                   int(r.views_used), int(r.points_used), vr)
+
+
+def _flags(fix_principal_point=False, zero_tangent=False, fix_k3=False, rational=False, guess=None) -> int:
+    return ((_lib.CALIB_FIX_PRINCIPAL_POINT if fix_principal_point else 0) | (_lib.CALIB_ZERO_TANGENT_DIST if zero_tangent else 0) |
+            (_lib.CALIB_FIX_K3 if fix_k3 else 0) | (_lib.CALIB_RATIONAL_MODEL if rational else 0) |
+            (_lib.CALIB_USE_INTRINSIC_GUESS if guess is not None else 0))
+
+
+def _views(object_points, image_points):
+    if len(object_points) != len(image_points):
+        raise ValueError("one list of object points per list of image points")
+    obj, img = [], []
+    for o, i in zip(object_points, image_points):
+        o = np.asarray(o, np.float64).reshape(-1, np.asarray(o).shape[-1] if np.asarray(o).size else 2)
+        if o.shape[1] == 3:
+            if np.any(o[:, 2] != 0):
+                raise ValueError("object points must lie on the plane z = 0")
+            o = o[:, :2]
+        i = np.asarray(i, np.float32).reshape(-1, 2)
+        if o.shape[0] != i.shape[0]:
+            raise ValueError("a view has different numbers of object and image points")
+        obj.append(o.astype(np.float32))
+        img.append(i)
+    return obj, img
+
+
+_ctx = None
+_ctx_lock = threading.Lock()   # one context (one stream, one set of buffers) serves every thread: calls take turns
+
+
+def _calibrate(cams, offsets, obj, img):
+    global _ctx
+    with _ctx_lock:
+        if _ctx is None:
+            _ctx = _lib.Context(_lib.default_config(), np.zeros(1, np.uint64), 64, 1)
+        return _ctx.calibrate_cameras(cams, offsets, obj, img)
+
+
+def reproject(params, rotation, translation, object_points) -> np.ndarray:
+    """board points (n, 2) through the camera `params` (fx fy cx cy k1 .. k6) at pose (rotation, translation) -> pixels (n, 2), float64:
+    the forward model of the calibration, evaluated on the host"""
+    a = np.asarray(params, np.float64)
+    o = np.asarray(object_points, np.float64).reshape(-1, 2)
+    P = o @ np.asarray(rotation, np.float64).reshape(3, 3)[:, :2].T + np.asarray(translation, np.float64).reshape(3)
+    xd = Distortion(*[float(v) for v in a[4:12]]).distort_normalized(P[:, :2] / P[:, 2:3])
+    return xd * a[[0, 1]] + a[[2, 3]]
+
+
+def calibrate_cameras(problems: Sequence[dict]) -> List[Calibration]:
+    """Several cameras in one launch.  Each problem is a dict of calibrate_camera's arguments: object_points, image_points,
+    image_size and optionally fix_principal_point, zero_tangent, fix_k3, rational, guess (a CameraIntrinsics, its distortion the
+    starting lens), max_iterations."""
+    specs, obj, img = [], [], []
+    for pr in problems:
+        o, i = _views(pr["object_points"], pr["image_points"])
+        specs.append((pr, len(obj), len(o)))
+        obj += o
+        img += i
+    cams = (_lib.CalibCamera * max(len(specs), 1))()
+    for c, (pr, first, n) in zip(cams, specs):
+        w, h = pr["image_size"]
+        c.image_width, c.image_height, c.first_view, c.n_views = int(w), int(h), first, n
+        guess = pr.get("guess")
+        c.flags = _flags(pr.get("fix_principal_point", False), pr.get("zero_tangent", False), pr.get("fix_k3", False), pr.get("rational", False),
+                         guess)
+        c.max_iterations = int(pr.get("max_iterations") or 0)
+        if guess is not None:
+            c.guess = guess._c()
+            c.guess_distortion = (guess.distortion or Distortion())._c()
+    offsets = np.concatenate([[0], np.cumsum([len(o) for o in obj])]).astype(np.uint32)
+    res, views = _calibrate(cams, offsets, np.concatenate(obj) if obj else np.zeros((0, 2), np.float32),
+                            np.concatenate(img) if img else np.zeros((0, 2), np.float32))
+    return [Calibration._from(res[k], [views[first + j] for j in range(n)]) for k, (_, first, n) in enumerate(specs)]
+
+
+def calibrate_camera(object_points, image_points, image_size, *, fix_principal_point=False, zero_tangent=False, fix_k3=False, rational=False,
+                     guess: Optional[CameraIntrinsics] = None, max_iterations: Optional[int] = None, outlier_passes: int = 0) -> Calibration:
+    """cv::calibrateCamera for a planar target: object_points / image_points are per-view arrays ((n, 2) or (n, 3) with z = 0, and (n, 2)
+    pixels); image_size (width, height).  Views with fewer than 4 points are kept (status CALIB_VIEW_TOO_FEW_POINTS) so that view
+    indices match the caller's frames.
+
+    The solve is plain least squares: a correspondence that is wrong by pixels pulls every parameter.  outlier_passes = k solves k more
+    times, each time without the correspondences of a solved view that reproject farther than max(1 px, 3 x that view's median) from the
+    previous solution; `Calibration.inliers` then says which points of each view the last solve used."""
+    kw = dict(image_size=image_size, fix_principal_point=fix_principal_point, zero_tangent=zero_tangent, fix_k3=fix_k3, rational=rational,
+              guess=guess, max_iterations=max_iterations)
+    obj, img = _views(object_points, image_points)
+    keep = [np.ones(len(o), bool) for o in obj]
+    cal = calibrate_cameras([dict(object_points=obj, image_points=img, **kw)])[0]
+    for _ in range(int(outlier_passes)):
+        if not cal.ok:
+            break
+        k_obj, k_img = [o[k] for o, k in zip(obj, keep)], [i[k] for i, k in zip(img, keep)]
+        for j, v in enumerate(cal.views):
+            if not v.used:
+                continue
+            e = np.linalg.norm(reproject(cal.params, v.rotation, v.translation, k_obj[j]) - k_img[j], axis=1)
+            idx = np.nonzero(keep[j])[0]
+            keep[j][idx[~(e < max(1.0, 3.0 * float(np.median(e))))]] = False
+        cal = calibrate_cameras([dict(object_points=[o[k] for o, k in zip(obj, keep)], image_points=[i[k] for i, k in zip(img, keep)],
+                                      **kw)])[0]
+    if outlier_passes:
+        cal.inliers = keep
+    return cal
+
+
+def board_correspondences(board, detection):
+    """aruco's calibrateCameraAruco per frame: the corners of the detection's board markers (refined when present), in detection order; an
+    id seen more than once in the frame is left out in all its instances (the board pose's rule) -> (object (n, 2), image (n, 2))"""
+    ids = [m.id for m in detection.markers]
+    slot = {int(i): k for k, i in enumerate(board.ids)}
+    obj, img = [], []
+    for m in detection.markers:
+        k = slot.get(int(m.id))
+        if k is None or ids.count(m.id) > 1:
+            continue
+        obj.append(board.corners[k])
+        img.append(np.asarray(m.corners_refined if m.corners_refined is not None else m.corners, np.float32))
+    if not obj:
+        return np.zeros((0, 2), np.float32), np.zeros((0, 2), np.float32)
+    return np.concatenate(obj).astype(np.float32), np.concatenate(img).astype(np.float32)
+
+
+def calibrate_camera_board(board, detections, image_size, **kw) -> Calibration:
+    """calibrateCameraAruco: one view per Detection, from the marker corners of `board` (a Board / GridBoard); keywords as
+    calibrate_camera.  Detected marker corners carry outliers (a corner whose refinement fell back to the integer quad corner is a few
+    pixels off; now and then a marker is misread), which pull a plain solve by several pixels: pass outlier_passes=2 to solve again
+    without them."""
+    pairs = [board_correspondences(board, d) for d in detections]
+    return calibrate_camera([o for o, _ in pairs], [i for _, i in pairs], image_size, **kw)
+
+
+def calibrate_camera_charuco(board, views, image_size, **kw) -> Calibration:
+    """calibrateCameraCharuco: one view per Detection (its charuco_ids / charuco_corners; None when the frame showed no corner) or
+    (ids, corners) pair of a CharucoBoard; keywords as calibrate_camera"""
+    obj, img = [], []
+    for v in views:
+        ids, corners = (v.charuco_ids, v.charuco_corners) if hasattr(v, "charuco_ids") else v
+        ids = np.zeros(0, np.uint32) if ids is None else np.asarray(ids, np.int64).reshape(-1)
+        corners = np.zeros((0, 2), np.float32) if corners is None else np.asarray(corners, np.float32).reshape(-1, 2)
+        obj.append(board.chessboard_corners[ids].astype(np.float32))
+        img.append(corners)
+    return calibrate_camera(obj, img, image_size, **kw)

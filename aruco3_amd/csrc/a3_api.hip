@@ -81,6 +81,9 @@ hipError_t launch_charuco_pose(hipStream_t, const a3_marker*, const float*, cons
                                uint32_t, const void*, const float*, uint32_t, const uint32_t*, const a3_charuco_corner*, const float*,
                                const a3_intrinsics*, uint32_t, uint32_t, a3_charuco_pose*);
 hipError_t launch_calc_tau(hipStream_t, const uint64_t*, uint32_t, unsigned int*);
+size_t calib_view_bytes();
+hipError_t launch_calibrate(hipStream_t, const a3_calib_camera*, uint32_t, const uint32_t*, const float*, const float*, double*, a3_calib_result*,
+                            a3_calib_view*);
 hipError_t launch_synth_render(hipStream_t, const a3_synth_frame*, uint32_t, const a3_synth_marker*, uint32_t, uint32_t, int, float, float, int,
                                uint8_t*, size_t, size_t);
 hipError_t launch_spin(hipStream_t, int, int, int, uint32_t*);
@@ -297,6 +300,8 @@ struct a3_ctx {
     std::vector<a3_charuco_corner> h_charuco;
     std::vector<a3_charuco_pose> h_charuco_pose;
     bool charuco_valid = false, charuco_pose_valid = false;
+    // a3_calibrate_cameras: [cameras | view offsets | object points | image points], the per-view scratch, [results | views]
+    DevBuf calib_in, calib_scratch, calib_out;
     uint32_t last_charuco_total = 0;   // sizes the speculative record read-back of the next batch
     void* pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1303,7 +1308,8 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->pre_xy, &ctx->fin_xy, &ctx->fin_count, &ctx->work, &ctx->outs, &ctx->proj, &ctx->patches, &ctx->cand_big,
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
-                      &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf};
+                      &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->calib_in,
+                      &ctx->calib_scratch, &ctx->calib_out};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -2400,6 +2406,73 @@ int a3_undistort_points(a3_ctx* ctx, const float* xy, size_t n, const a3_intrins
     A3_HIP(launch_undistort_corners(ctx->stream, nullptr, ctx->tmp_a.as<float>(), nullptr, (uint32_t)n, *intr, *d, d_out, d_out + n * 2));
     A3_HIP(hipMemcpyAsync(out_xy, d_out, xy_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (residual_px) A3_HIP(hipMemcpyAsync(residual_px, d_out + n * 2, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+int a3_calibrate_cameras(a3_ctx* ctx, const a3_calib_camera* cams, size_t n_cams, const uint32_t* view_offsets, size_t n_views,
+                         const float* object_xy, const float* image_xy, a3_calib_result* results, a3_calib_view* views) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!cams || !view_offsets || !results) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: null argument");
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a submitted batch has not been collected");
+    if (n_cams == 0 || n_cams > A3_CALIB_MAX_CAMERAS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: n_cams must be in 1..A3_CALIB_MAX_CAMERAS");
+    if (n_views == 0 || n_views > A3_CALIB_MAX_CALL_VIEWS)
+        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: n_views must be in 1..A3_CALIB_MAX_CALL_VIEWS");
+    if (view_offsets[0] != 0) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: view_offsets[0] must be 0");
+    for (size_t i = 0; i < n_views; i++) {
+        if (view_offsets[i + 1] < view_offsets[i]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: view_offsets must not decrease");
+        if (view_offsets[i + 1] - view_offsets[i] > A3_CALIB_MAX_POINTS)
+            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a view has more than A3_CALIB_MAX_POINTS points");
+    }
+    const size_t n_pts = view_offsets[n_views];
+    if (n_pts && (!object_xy || !image_xy)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: null point array");
+    for (size_t i = 0; i < 2 * n_pts; i++)
+        if (!std::isfinite(object_xy[i]) || !std::isfinite(image_xy[i])) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a point is not finite");
+    std::vector<uint8_t> owned(n_views, 0);
+    for (size_t c = 0; c < n_cams; c++) {
+        const a3_calib_camera& cam = cams[c];
+        if (cam.flags & ~31u) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: unknown flags");
+        if (cam.image_width == 0 || cam.image_height == 0 || cam.image_width > 65535 || cam.image_height > 65535)
+            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: image size must be in 1..65535");
+        if (cam.max_iterations > A3_CALIB_MAX_ITERATIONS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: max_iterations above A3_CALIB_MAX_ITERATIONS");
+        if (cam.n_views == 0 || cam.n_views > A3_CALIB_MAX_VIEWS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a camera's n_views must be in 1..A3_CALIB_MAX_VIEWS");
+        if ((uint64_t)cam.first_view + cam.n_views > n_views) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a camera's views lie past n_views");
+        for (uint32_t v = cam.first_view; v < cam.first_view + cam.n_views; v++) {
+            if (owned[v]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: two cameras share a view");
+            owned[v] = 1;
+        }
+        if (cam.flags & A3_CALIB_USE_INTRINSIC_GUESS) {
+            const a3_intrinsics& g = cam.guess;
+            const a3_distortion& d = cam.guess_distortion;
+            const float v[12] = {g.focal_x, g.focal_y, g.principal_x, g.principal_y, d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6};
+            for (float x : v)
+                if (!std::isfinite(x)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: the guess is not finite");
+            if (!(g.focal_x > 0.0f) || !(g.focal_y > 0.0f)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: the guess's focal lengths must be > 0");
+        }
+    }
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_cams = up(n_cams * sizeof(a3_calib_camera)), b_off = up((n_views + 1) * sizeof(uint32_t)), b_pts = up(n_pts * 2 * sizeof(float));
+    const size_t b_res = up(n_cams * sizeof(a3_calib_result)), b_views = n_views * sizeof(a3_calib_view);
+    A3_HIP(ctx->calib_in.ensure(b_cams + b_off + 2 * b_pts));
+    A3_HIP(ctx->calib_scratch.ensure(n_views * calib_view_bytes()));
+    A3_HIP(ctx->calib_out.ensure(b_res + b_views));
+    uint8_t* din = ctx->calib_in.as<uint8_t>();
+    uint8_t* dout = ctx->calib_out.as<uint8_t>();
+    A3_HIP(hipMemcpyAsync(din, cams, n_cams * sizeof(a3_calib_camera), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(din + b_cams, view_offsets, (n_views + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (n_pts) {
+        A3_HIP(hipMemcpyAsync(din + b_cams + b_off, object_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        A3_HIP(hipMemcpyAsync(din + b_cams + b_off + b_pts, image_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    // a view no camera owns is not written by the kernel: it comes back zero, not as what an earlier call left in the buffer
+    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_views, ctx->stream));
+    A3_HIP(launch_calibrate(ctx->stream, reinterpret_cast<const a3_calib_camera*>(din), (uint32_t)n_cams, reinterpret_cast<const uint32_t*>(din + b_cams),
+                            reinterpret_cast<const float*>(din + b_cams + b_off), reinterpret_cast<const float*>(din + b_cams + b_off + b_pts),
+                            ctx->calib_scratch.as<double>(), reinterpret_cast<a3_calib_result*>(dout), reinterpret_cast<a3_calib_view*>(dout + b_res)));
+    A3_HIP(hipMemcpyAsync(results, dout, n_cams * sizeof(a3_calib_result), hipMemcpyDeviceToHost, ctx->stream));
+    if (views) A3_HIP(hipMemcpyAsync(views, dout + b_res, b_views, hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }

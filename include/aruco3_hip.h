@@ -480,6 +480,92 @@ int  a3_get_charuco_poses(a3_ctx *ctx, a3_charuco_pose *dst, size_t cap_frames, 
 int  a3_interpolate_charuco(a3_ctx *ctx, const void *pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
                             const uint32_t *ids, const float *corners_xy, size_t n_markers, a3_charuco_corner *dst, size_t cap, size_t *n);
 
+/* Camera calibration.  NOT in the reference: an opt-in extension (OpenCV's calibrateCamera for planar targets: Zhang's initialisation,
+ * then a Levenberg-Marquardt bundle over intrinsics, lens model and per-view poses), stand-alone: no batch, setting or launch of the
+ * detection path changes.  A call solves n_cams independent cameras (one workgroup each, k_calibrate); camera c owns the views
+ * first_view .. first_view + n_views - 1 of the call (ranges non-empty and disjoint), view i the points view_offsets[i] ..
+ * view_offsets[i + 1] - 1 (view_offsets[0] = 0, non-decreasing) of object_xy (board units, z = 0) and image_xy (pixels, pixel centres at
+ * integer coordinates).  The result plugs into the pose calls (`intrinsics`) and a3_set_distortion (`distortion`).  Fixed to the bit as
+ * follows -- tests/calib_oracle.c a3o_calibrate restates it.  Arithmetic is f64 (inputs converted exactly), every expression evaluated
+ * as C parses it, no fused multiply-add, division and sqrt correctly rounded, no other math function but fabs.  "s += x" means
+ * s = s + x; every sum over a view's points runs in point order from +0.0, every sum over views in view order over the USED views.
+ *   model (the forward model of a3_set_distortion, in f64): intrinsics a = (fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6), pose (R, t) board ->
+ *     camera.  q = (R0 X + R1 Y, R3 X + R4 Y, R6 X + R7 Y), P = q + t, ia = 1 / Pz, x = Px ia, y = Py ia, r2 = x x + y y,
+ *     num = 1 + ((k3 r2 + k2) r2 + k1) r2, den = 1 + ((k6 r2 + k5) r2 + k4) r2, iden = 1 / den, radial = num iden, xy2 = 2 x y,
+ *     xd = x radial + (p1 xy2 + p2 (r2 + 2 x x)), yd = y radial + (p1 (r2 + 2 y y) + p2 xy2), residual (fx xd + cx - u, fy yd + cy - v).
+ *     One point gives two augmented rows of 19 (18 Jacobian columns: the 12 intrinsics, then (w, t) of R <- cay(w) R, t <- t + dt, with
+ *     the board pose's Cayley map in f64; column 18 the residual); tests/calib_oracle.c calib_row lists the expressions.  A view's
+ *     block is the upper triangle, row by row, of the 19 x 19 sum of a_u a_u^T + a_v a_v^T over its points (190 entries: J^T J, J^T r,
+ *     r.r = the view's cost), entry by entry s += au_i au_k; s += av_i av_k.  Columns of fixed parameters are computed, never read.
+ *   1. per view with >= 4 points: homography board -> pixels by normalised DLT.  Hartley normalisation of each point set (the mean,
+ *      then the scale 1.4142135623730951 / (sum of distances to the mean / n)); rows (X, Y, 1, 0, 0, 0, -U X, -U Y | U) and (0, 0, 0,
+ *      X, Y, 1, -V X, -V Y | V), summed as above into 8 x 8 normal equations; LU with partial pivoting (the first largest |pivot|); a
+ *      pivot with |p| <= 1e-10 * the largest |diagonal| of the matrix, or not finite, marks the view DEGENERATE.  h8 = 1, denormalised,
+ *      divided by H22 (a non-finite entry: DEGENERATE).  Fewer than 4 points: TOO_FEW_POINTS.  The other views are USED.
+ *   2. no USED view, or 2 N - n_free - 6 views_used <= 0 (N: points of the USED views): status TOO_FEW.  Without USE_INTRINSIC_GUESS:
+ *      cx = (W - 1) * 0.5, cy = (H - 1) * 0.5, distortion 0, and (fx, fy) by OpenCV's initIntrinsicParams2D: per USED view, H with
+ *      rows 0 / 1 less cx / cy times row 2, its columns h, v and d1 = (h + v) * 0.5, d2 = (h - v) * 0.5, each times 1 / sqrt(its sum
+ *      of squares); the rows (h0 v0, h1 v1 | -(h2 v2)) and (d1_0 d2_0, d1_1 d2_1 | -(d1_2 d2_2)) into 2 x 2 normal equations, solved
+ *      by Cramer's rule; fx = sqrt(1 / |s0|), fy = sqrt(1 / |s1|); det <= 1e-9 A00 A11 (views all near fronto-parallel: the equations
+ *      do not fix both focal lengths), or fx / fy not finite or not > 0: status NO_INIT.  With USE_INTRINSIC_GUESS
+ *      everything starts from guess / guess_distortion; the flags then zero p1 p2 (ZERO_TANGENT_DIST) and k4 k5 k6 (no RATIONAL_MODEL).
+ *   3. per USED view: m_c = ((H0c - cx H2c) / fx, (H1c - cy H2c) / fy, H2c); r0 = m0 / |m0|, r1 = m1 - (r0 . m1) r0 normalised,
+ *      r2 = r0 x r1 (the columns of R); t = (2 m2) / (|m0| + |m1|).  Then the board pose's Levenberg-Marquardt (lambda 1e-3, x10 / /10,
+ *      a bad LDL^T pivot counts as a rejected evaluation, stop at A3_CALIB_POSE_EVALS evaluations, cost 0, or an accepted relative
+ *      decrease below A3_CALIB_REL_TOL) on the view's pose columns, intrinsics fixed.
+ *   4. joint LM over the free intrinsics and every USED view's pose, lambda 1e-3.  An iteration: V_j + lambda diag(V_j) by LDL^T (a
+ *      bad pivot in any view is a rejected step), S = U + lambda diag(U) - sum_j W_j V_j^-1 W_j^T with U = sum_j U_j (entry (c, k) of
+ *      a view's term: sum over m of W_j[k][m] y_c[m], y_c = V_j^-1 W_j[c]), rhs = -g_a + sum_j W_j V_j^-1 g_j, LDL^T of S (bad pivot:
+ *      rejected), per view d_j = V_j^-1 (-g_j - W_j^T d_a), R <- cay(w) R, t <- t + dt, a <- a + d_a; a lower candidate cost (the sum
+ *      of the views' costs) is accepted (lambda /= 10; converged when (cost - cost') / cost < A3_CALIB_REL_TOL), anything else
+ *      rejected (lambda *= 10; the blocks are not rebuilt).  Stop at max_iterations iterations or cost 0.
+ *   5. rms_px = sqrt(cost / N), per view sqrt(cost_j / n_j) (float).  std_dev: sqrt(sigma2 * diag(S0^-1)), S0 the undamped Schur
+ *      complement at the final state, sigma2 = cost / (2 N - n_free - 6 views_used); +inf for every free parameter where S0 (or a V_j)
+ *      is not positive definite; 0 for fixed ones.  A non-finite cost at the start of step 4: status NOT_FINITE.
+ * A camera that is not solved reports its status, views_used and points_used and zeros elsewhere, its views their status and points;
+ * a view that no camera's range holds comes back all zero.
+ * Input errors (A3_ERR_INVALID): null pointers, n_cams or n_views 0, unknown flags, image sizes of 0 or above 65535, max_iterations
+ * above A3_CALIB_MAX_ITERATIONS, empty or overlapping ranges, counts above the limits, non-finite coordinates, a non-finite guess or
+ * one with focal lengths <= 0 under USE_INTRINSIC_GUESS.  Synchronous; not while a submitted batch is in flight. */
+#define A3_CALIB_MAX_POINTS         4096    /* per view (4 * A3_BOARD_MAX_MARKERS) */
+#define A3_CALIB_MAX_VIEWS          4096    /* per camera */
+#define A3_CALIB_MAX_CAMERAS        1024    /* per call */
+#define A3_CALIB_MAX_CALL_VIEWS     65536   /* per call, all cameras */
+#define A3_CALIB_MAX_ITERATIONS     1000
+#define A3_CALIB_DEFAULT_ITERATIONS 50
+#define A3_CALIB_POSE_EVALS         20
+#define A3_CALIB_REL_TOL            1e-10
+enum { A3_CALIB_FIX_PRINCIPAL_POINT = 1, A3_CALIB_ZERO_TANGENT_DIST = 2, A3_CALIB_FIX_K3 = 4, A3_CALIB_RATIONAL_MODEL = 8,
+       A3_CALIB_USE_INTRINSIC_GUESS = 16 };
+enum { A3_CALIB_OK = 1, A3_CALIB_TOO_FEW = 2, A3_CALIB_NO_INIT = 3, A3_CALIB_NOT_FINITE = 4 };
+enum { A3_CALIB_VIEW_USED = 1, A3_CALIB_VIEW_TOO_FEW_POINTS = 2, A3_CALIB_VIEW_DEGENERATE = 3 };
+typedef struct a3_calib_camera {       /* one problem */
+    uint32_t image_width, image_height;
+    uint32_t first_view, n_views;      /* a contiguous, disjoint range of the call's views */
+    uint32_t flags;                    /* A3_CALIB_* */
+    uint32_t max_iterations;           /* joint LM iterations; 0 = A3_CALIB_DEFAULT_ITERATIONS */
+    a3_intrinsics guess;               /* read with USE_INTRINSIC_GUESS (image_width / image_height ignored) */
+    a3_distortion guess_distortion;    /* read with USE_INTRINSIC_GUESS (model, iterations, max_residual_px ignored) */
+} a3_calib_camera;
+typedef struct a3_calib_result {
+    uint32_t status;                   /* A3_CALIB_OK / _TOO_FEW / _NO_INIT / _NOT_FINITE */
+    uint32_t views_used, points_used, iterations, converged, reserved;
+    double   fx, fy, cx, cy, dist[8];  /* dist: k1 k2 p1 p2 k3 k4 k5 k6 */
+    double   std_dev[12];              /* fx fy cx cy then dist's order; 0 for fixed parameters */
+    double   rms_px;                   /* sqrt(cost / points_used), as cv::calibrateCamera returns it */
+    a3_intrinsics intrinsics;          /* the same values in float, for the pose calls ... */
+    a3_distortion distortion;          /* ... and a3_set_distortion (model RATIONAL, iterations and max_residual_px at their defaults) */
+    uint32_t reserved2;                /* 0 (the record has no padding bytes) */
+} a3_calib_result;
+typedef struct a3_calib_view {
+    uint32_t status, points;           /* A3_CALIB_VIEW_* */
+    float    rms_px;
+    float    rotation[9], translation[3];   /* board -> camera, the a3_pose convention */
+} a3_calib_view;
+/* view_offsets: n_views + 1 entries; results: n_cams; views: n_views records (nullable) */
+int  a3_calibrate_cameras(a3_ctx *ctx, const a3_calib_camera *cams, size_t n_cams, const uint32_t *view_offsets, size_t n_views,
+                          const float *object_xy, const float *image_xy, a3_calib_result *results, a3_calib_view *views);
+
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);
 int  a3_calculate_tau(int device, const uint64_t *codes, size_t n_codes, uint8_t *tau);

@@ -74,6 +74,13 @@ pub const A3_BOARD_OK: u32 = 1;
 pub const A3_DIST_NONE: u32 = 0;
 pub const A3_DIST_RATIONAL: u32 = 1;
 pub const A3_BOARD_MAX_MARKERS: usize = 1024;
+pub const A3_CALIB_FIX_PRINCIPAL_POINT: u32 = 1;
+pub const A3_CALIB_ZERO_TANGENT_DIST: u32 = 2;
+pub const A3_CALIB_FIX_K3: u32 = 4;
+pub const A3_CALIB_RATIONAL_MODEL: u32 = 8;
+pub const A3_CALIB_USE_INTRINSIC_GUESS: u32 = 16;
+pub const A3_CALIB_OK: u32 = 1;
+pub const A3_CALIB_VIEW_USED: u32 = 1;
 
 /// a3_config <-> DetectorConfig, src/aruco.rs:23-30
 #[repr(C)]
@@ -203,6 +210,53 @@ pub struct A3Distortion {
     pub max_residual_px: f32,
 }
 
+/// a3_calib_camera: one calibration problem (not in the reference; include/aruco3_hip.h states the algorithm)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct A3CalibCamera {
+    pub image_width: u32,
+    pub image_height: u32,
+    pub first_view: u32,
+    pub n_views: u32,
+    pub flags: u32,
+    pub max_iterations: u32,
+    pub guess: A3Intrinsics,
+    pub guess_distortion: A3Distortion,
+}
+
+/// a3_calib_result: one camera's intrinsics, lens model, deviations and fit
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct A3CalibResult {
+    pub status: u32,
+    pub views_used: u32,
+    pub points_used: u32,
+    pub iterations: u32,
+    pub converged: u32,
+    pub reserved: u32,
+    pub fx: f64,
+    pub fy: f64,
+    pub cx: f64,
+    pub cy: f64,
+    pub dist: [f64; 8],
+    pub std_dev: [f64; 12],
+    pub rms_px: f64,
+    pub intrinsics: A3Intrinsics,
+    pub distortion: A3Distortion,
+    pub reserved2: u32,
+}
+
+/// a3_calib_view: one view's status and pose, board -> camera
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3CalibView {
+    pub status: u32,
+    pub points: u32,
+    pub rms_px: f32,
+    pub rotation: [f32; 9],
+    pub translation: [f32; 3],
+}
+
 /// a3_stats: per-batch stage counters (the reference prints its rejects in debug builds, src/aruco.rs:163-164)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -325,6 +379,8 @@ extern "C" {
     pub fn a3_interpolate_charuco(ctx: *mut A3Ctx, pixels: *const c_void, memory: c_int, fmt: c_int, width: u32, height: u32, row_stride: usize,
                                   ids: *const u32, corners_xy: *const f32, n_markers: usize, dst: *mut A3CharucoCorner, cap: usize,
                                   n: *mut usize) -> c_int;
+    pub fn a3_calibrate_cameras(ctx: *mut A3Ctx, cams: *const A3CalibCamera, n_cams: usize, view_offsets: *const u32, n_views: usize,
+                                object_xy: *const f32, image_xy: *const f32, results: *mut A3CalibResult, views: *mut A3CalibView) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
@@ -1134,6 +1190,33 @@ pub fn find_nearest_batch(d: &Detector, bits: &[u64]) -> Vec<(usize, u8)> {
     let mut dist = vec![0u8; bits.len().max(1)];
     ctx.check(unsafe { a3_find_nearest(ctx.raw, bits.as_ptr(), bits.len(), idx.as_mut_ptr(), dist.as_mut_ptr()) }, "a3_find_nearest");
     (0..bits.len()).map(|i| (idx[i] as usize, dist[i])).collect()
+}
+
+/// New (additive): one camera calibrated on the device from views of a planar target (`a3_calibrate_cameras`; not in the
+/// reference).  `views[i]` holds (board (x, y), pixel (u, v)) pairs; `flags` are A3_CALIB_* (without A3_CALIB_USE_INTRINSIC_GUESS).
+/// Returns the camera's record and one record per view; the intrinsics go to `estimate_pose`, the lens to `Distortion`.
+pub fn calibrate_camera(d: &Detector, views: &[Vec<((f32, f32), (f32, f32))>], image_size: (u32, u32), flags: u32)
+                        -> (A3CalibResult, Vec<A3CalibView>) {
+    let slot = slot_for(d);
+    let ctx = slot.lock().unwrap();
+    let mut offsets = vec![0u32];
+    let (mut obj, mut img) = (Vec::new(), Vec::new());
+    for v in views {
+        for &((x, y), (u, w)) in v {
+            obj.extend_from_slice(&[x, y]);
+            img.extend_from_slice(&[u, w]);
+        }
+        offsets.push((obj.len() / 2) as u32);
+    }
+    let guess = A3Intrinsics { image_width: 0, image_height: 0, focal_x: 0.0, focal_y: 0.0, principal_x: 0.0, principal_y: 0.0 };
+    let cam = A3CalibCamera { image_width: image_size.0, image_height: image_size.1, first_view: 0, n_views: views.len() as u32,
+                              flags: flags & !A3_CALIB_USE_INTRINSIC_GUESS, max_iterations: 0, guess, guess_distortion: A3Distortion::default() };
+    let mut res: A3CalibResult = unsafe { std::mem::zeroed() };   // (plain numbers: all-zero is a valid record)
+    let mut out = vec![A3CalibView::default(); views.len()];
+    ctx.check(unsafe {
+        a3_calibrate_cameras(ctx.raw, &cam, 1, offsets.as_ptr(), views.len(), obj.as_ptr(), img.as_ptr(), &mut res, out.as_mut_ptr())
+    }, "a3_calibrate_cameras");
+    (res, out)
 }
 
 /// per-batch stage counters of the detector's last call
