@@ -30,6 +30,11 @@ def __getattr__(name):
         from . import calibration
 
         return getattr(calibration, name)
+    if name in ("RigCalibration", "calibrate_rig", "calibrate_rigs", "calibrate_rig_board", "calibrate_rig_charuco", "stereo_calibrate",
+                "rig_board_poses"):
+        from . import rig
+
+        return getattr(rig, name)
     if name == "pose":
         import importlib
 

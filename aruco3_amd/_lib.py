@@ -34,6 +34,12 @@ CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST, CALIB_FIX_K3, CALIB_RATIONAL
 CALIB_OK, CALIB_TOO_FEW, CALIB_NO_INIT, CALIB_NOT_FINITE = 1, 2, 3, 4
 CALIB_VIEW_USED, CALIB_VIEW_TOO_FEW_POINTS, CALIB_VIEW_DEGENERATE = 1, 2, 3
 CALIB_MAX_POINTS, CALIB_MAX_VIEWS, CALIB_MAX_CAMERAS, CALIB_MAX_CALL_VIEWS = 4096, 4096, 1024, 65536
+# a3_calibrate_rigs (include/aruco3_hip.h A3_RIG_*)
+RIG_USE_EXTRINSIC_GUESS, RIG_FIX_EXTRINSICS = 1, 2
+RIG_OK, RIG_NOT_CONNECTED, RIG_NOT_FINITE = 1, 2, 3
+RIG_OBS_USED, RIG_OBS_TOO_FEW_POINTS, RIG_OBS_DEGENERATE = 1, 2, 3
+RIG_FRAME_USED, RIG_FRAME_UNUSED = 1, 2
+RIG_MAX_CAMERAS, RIG_MAX_FRAMES, RIG_MAX_RIGS, RIG_MAX_CALL_FRAMES, RIG_MAX_CALL_OBSERVATIONS = 8, 4096, 1024, 65536, 262144
 STEP_NAMES = {0: "whole", 1: "decode_deferred", 2: "held_released_by_last", 3: "held_released_early", 4: "burst_last", 5: "held"}
 
 # every symbol include/aruco3_hip.h declares
@@ -48,7 +54,7 @@ SYMBOLS = [
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
-    "a3_calibrate_cameras",
+    "a3_calibrate_cameras", "a3_calibrate_rigs",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
 INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
@@ -145,6 +151,39 @@ class CalibResult(C.Structure):
 
 class CalibView(C.Structure):
     _fields_ = [("status", C.c_uint32), ("points", C.c_uint32), ("rms_px", C.c_float), ("rotation", C.c_float * 9), ("translation", C.c_float * 3)]
+
+
+class Rig(C.Structure):
+    """a3_rig: one rig calibration problem (an extension beyond the reference; include/aruco3_hip.h states the algorithm)"""
+    _fields_ = [("first_camera", C.c_uint32), ("n_cameras", C.c_uint32), ("first_frame", C.c_uint32), ("n_frames", C.c_uint32),
+                ("first_obs", C.c_uint32), ("n_obs", C.c_uint32), ("flags", C.c_uint32), ("max_iterations", C.c_uint32)]
+
+
+class RigCamera(C.Structure):
+    _fields_ = [("a", C.c_double * 12), ("guess_rotation", C.c_double * 9), ("guess_translation", C.c_double * 3)]
+
+
+class RigObservation(C.Structure):
+    _fields_ = [("camera", C.c_uint32), ("frame", C.c_uint32), ("first_point", C.c_uint32), ("n_points", C.c_uint32)]
+
+
+class RigResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("frames_used", C.c_uint32), ("obs_used", C.c_uint32), ("points_used", C.c_uint32),
+                ("iterations", C.c_uint32), ("converged", C.c_uint32), ("rms_px", C.c_double)]
+
+
+class RigCameraResult(C.Structure):
+    _fields_ = [("rotation", C.c_double * 9), ("translation", C.c_double * 3), ("std_dev", C.c_double * 6), ("rms_px", C.c_double),
+                ("rotation_f", C.c_float * 9), ("translation_f", C.c_float * 3), ("obs_used", C.c_uint32), ("points_used", C.c_uint32)]
+
+
+class RigFrame(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("obs_used", C.c_uint32), ("points_used", C.c_uint32), ("rms_px", C.c_float),
+                ("rotation", C.c_double * 9), ("translation", C.c_double * 3), ("rotation_f", C.c_float * 9), ("translation_f", C.c_float * 3)]
+
+
+class RigObservationResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("points", C.c_uint32), ("rms_px", C.c_float), ("reserved", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -324,6 +363,11 @@ def load():
         L.a3_interpolate_charuco.restype = C.c_int
         L.a3_interpolate_charuco.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, u32p, f32p, C.c_size_t, vp,
                                              C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "a3_calibrate_rigs"):
+        L.a3_calibrate_rigs.restype = C.c_int
+        L.a3_calibrate_rigs.argtypes = [vp, C.POINTER(Rig), C.c_size_t, C.POINTER(RigCamera), C.c_size_t, C.POINTER(RigObservation), C.c_size_t,
+                                        f32p, f32p, C.POINTER(RigResult), C.POINTER(RigCameraResult), C.POINTER(RigFrame),
+                                        C.POINTER(RigObservationResult)]
     if hasattr(L, "a3_calibrate_cameras"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack calibration)
         L.a3_calibrate_cameras.restype = C.c_int
         L.a3_calibrate_cameras.argtypes = [vp, C.POINTER(CalibCamera), C.c_size_t, u32p, C.c_size_t, f32p, f32p, C.POINTER(CalibResult),
@@ -693,6 +737,21 @@ class Context:
         check(load().a3_calibrate_cameras(self.handle, cams, len(cams), _p(off, C.c_uint32), n_views, _p(obj, C.c_float), _p(img, C.c_float), res,
                                           views), self.handle)
         return res, views
+
+    # ---- camera rig calibration ----
+    def calibrate_rigs(self, rigs, cameras, obs, object_xy, image_xy):
+        """a3_calibrate_rigs: rigs (a Rig array), cameras (RigCamera array), obs (RigObservation array), object / image points (n, 2) ->
+        (RigResult array, RigCameraResult array, RigFrame array, RigObservationResult array)"""
+        obj = np.ascontiguousarray(np.asarray(object_xy, dtype=np.float32).reshape(-1, 2))
+        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 2))
+        n_frames = max([int(r.first_frame) + int(r.n_frames) for r in rigs], default=0)
+        res = (RigResult * max(len(rigs), 1))()
+        cres = (RigCameraResult * max(len(cameras), 1))()
+        frames = (RigFrame * max(n_frames, 1))()
+        ores = (RigObservationResult * max(len(obs), 1))()
+        check(load().a3_calibrate_rigs(self.handle, rigs, len(rigs), cameras, len(cameras), obs, len(obs), _p(obj, C.c_float), _p(img, C.c_float),
+                                       res, cres, frames, ores), self.handle)
+        return res, cres, frames, ores
 
     # ---- Detection.grey / thresholded / candidates / homographies of the last batch ----
     def download_grey(self, frame: int, w: int, h: int, thresholded: bool = False) -> np.ndarray:

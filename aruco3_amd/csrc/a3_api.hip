@@ -81,6 +81,11 @@ hipError_t launch_charuco_pose(hipStream_t, const a3_marker*, const float*, cons
                                uint32_t, const void*, const float*, uint32_t, const uint32_t*, const a3_charuco_corner*, const float*,
                                const a3_intrinsics*, uint32_t, uint32_t, a3_charuco_pose*);
 hipError_t launch_calc_tau(hipStream_t, const uint64_t*, uint32_t, unsigned int*);
+size_t rig_obs_bytes();
+size_t rig_frame_bytes();
+size_t rig_table_bytes();
+hipError_t launch_rig(hipStream_t, const a3_rig*, uint32_t, const a3_rig_camera*, const a3_rig_observation*, const float*, const float*, uint32_t*,
+                      double*, double*, a3_rig_result*, a3_rig_camera_result*, a3_rig_frame*, a3_rig_observation_result*);
 size_t calib_view_bytes();
 hipError_t launch_calibrate(hipStream_t, const a3_calib_camera*, uint32_t, const uint32_t*, const float*, const float*, double*, a3_calib_result*,
                             a3_calib_view*);
@@ -302,6 +307,9 @@ struct a3_ctx {
     bool charuco_valid = false, charuco_pose_valid = false;
     // a3_calibrate_cameras: [cameras | view offsets | object points | image points], the per-view scratch, [results | views]
     DevBuf calib_in, calib_scratch, calib_out;
+    // a3_calibrate_rigs: [rigs | cameras | observations | object points | image points], [table | per-observation | per-frame scratch],
+    // [results | camera results | frames | observation results]
+    DevBuf rig_in, rig_scratch, rig_out;
     uint32_t last_charuco_total = 0;   // sizes the speculative record read-back of the next batch
     void* pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1309,7 +1317,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
                       &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->calib_in,
-                      &ctx->calib_scratch, &ctx->calib_out};
+                      &ctx->calib_scratch, &ctx->calib_out, &ctx->rig_in, &ctx->rig_scratch, &ctx->rig_out};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -2473,6 +2481,108 @@ int a3_calibrate_cameras(a3_ctx* ctx, const a3_calib_camera* cams, size_t n_cams
                             ctx->calib_scratch.as<double>(), reinterpret_cast<a3_calib_result*>(dout), reinterpret_cast<a3_calib_view*>(dout + b_res)));
     A3_HIP(hipMemcpyAsync(results, dout, n_cams * sizeof(a3_calib_result), hipMemcpyDeviceToHost, ctx->stream));
     if (views) A3_HIP(hipMemcpyAsync(views, dout + b_res, b_views, hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+int a3_calibrate_rigs(a3_ctx* ctx, const a3_rig* rigs, size_t n_rigs, const a3_rig_camera* cameras, size_t n_cameras, const a3_rig_observation* obs,
+                      size_t n_obs, const float* object_xy, const float* image_xy, a3_rig_result* results, a3_rig_camera_result* camera_results,
+                      a3_rig_frame* frames, a3_rig_observation_result* obs_results) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!rigs || !cameras || !obs || !object_xy || !image_xy || !results || !camera_results)
+        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: null argument");
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a submitted batch has not been collected");
+    if (n_rigs == 0 || n_rigs > A3_RIG_MAX_RIGS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: n_rigs must be in 1..A3_RIG_MAX_RIGS");
+    if (n_cameras == 0 || n_cameras > (size_t)A3_RIG_MAX_RIGS * A3_RIG_MAX_CAMERAS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: n_cameras out of range");
+    if (n_obs == 0 || n_obs > A3_RIG_MAX_CALL_OBSERVATIONS)
+        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: n_obs must be in 1..A3_RIG_MAX_CALL_OBSERVATIONS");
+    size_t n_frames = 0;
+    for (size_t r = 0; r < n_rigs; r++) {
+        const a3_rig& R = rigs[r];
+        if (R.flags & ~3u) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: unknown flags");
+        if (R.n_cameras < 2 || R.n_cameras > A3_RIG_MAX_CAMERAS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's n_cameras must be in 2..A3_RIG_MAX_CAMERAS");
+        if (R.max_iterations > A3_CALIB_MAX_ITERATIONS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: max_iterations above A3_CALIB_MAX_ITERATIONS");
+        if (R.n_frames == 0 || R.n_frames > A3_RIG_MAX_FRAMES) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's n_frames must be in 1..A3_RIG_MAX_FRAMES");
+        if (R.n_obs == 0) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig has no observations");
+        if ((uint64_t)R.first_camera + R.n_cameras > n_cameras) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's cameras lie past n_cameras");
+        if ((uint64_t)R.first_obs + R.n_obs > n_obs) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's observations lie past n_obs");
+        if ((uint64_t)R.first_frame + R.n_frames > A3_RIG_MAX_CALL_FRAMES)
+            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's frames lie past A3_RIG_MAX_CALL_FRAMES");
+        n_frames = std::max(n_frames, (size_t)R.first_frame + R.n_frames);
+    }
+    std::vector<uint8_t> cam_owned(n_cameras, 0), frame_owned(n_frames, 0), obs_owned(n_obs, 0), seen(n_frames * A3_RIG_MAX_CAMERAS, 0);
+    size_t n_pts = 0;
+    for (size_t r = 0; r < n_rigs; r++) {
+        const a3_rig& R = rigs[r];
+        for (uint32_t c = R.first_camera; c < R.first_camera + R.n_cameras; c++) {
+            if (cam_owned[c]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: two rigs share a camera");
+            cam_owned[c] = 1;
+            for (double v : cameras[c].a)
+                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a camera's intrinsics are not finite");
+            if (!(cameras[c].a[0] > 0.0) || !(cameras[c].a[1] > 0.0)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: focal lengths must be > 0");
+            if (R.flags && c > R.first_camera) {
+                for (double v : cameras[c].guess_rotation)
+                    if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: the extrinsic guess is not finite");
+                for (double v : cameras[c].guess_translation)
+                    if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: the extrinsic guess is not finite");
+            }
+        }
+        for (uint32_t f = R.first_frame; f < R.first_frame + R.n_frames; f++) {
+            if (frame_owned[f]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: two rigs share a frame");
+            frame_owned[f] = 1;
+        }
+        for (uint32_t o = R.first_obs; o < R.first_obs + R.n_obs; o++) {
+            if (obs_owned[o]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: two rigs share an observation");
+            obs_owned[o] = 1;
+            const a3_rig_observation& ob = obs[o];
+            if (ob.camera < R.first_camera || ob.camera - R.first_camera >= R.n_cameras)
+                return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: an observation's camera lies outside its rig");
+            if (ob.frame < R.first_frame || ob.frame - R.first_frame >= R.n_frames)
+                return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: an observation's frame lies outside its rig");
+            if (ob.n_points > A3_CALIB_MAX_POINTS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: an observation has more than A3_CALIB_MAX_POINTS points");
+            if ((uint64_t)ob.first_point + ob.n_points > 0xffffffffull) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: an observation's points lie past 2^32");
+            uint8_t& dup = seen[(size_t)ob.frame * A3_RIG_MAX_CAMERAS + (ob.camera - R.first_camera)];
+            if (dup) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: two observations of one (camera, frame)");
+            dup = 1;
+            for (size_t i = 2 * (size_t)ob.first_point; i < 2 * ((size_t)ob.first_point + ob.n_points); i++)
+                if (!std::isfinite(object_xy[i]) || !std::isfinite(image_xy[i])) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a point is not finite");
+            n_pts = std::max(n_pts, (size_t)ob.first_point + ob.n_points);
+        }
+    }
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_rigs = up(n_rigs * sizeof(a3_rig)), b_cams = up(n_cameras * sizeof(a3_rig_camera)), b_obs = up(n_obs * sizeof(a3_rig_observation));
+    const size_t b_pts = up(std::max<size_t>(n_pts, 1) * 2 * sizeof(float));
+    const size_t b_res = up(n_rigs * sizeof(a3_rig_result)), b_cres = up(n_cameras * sizeof(a3_rig_camera_result));
+    const size_t b_frames = up(n_frames * sizeof(a3_rig_frame)), b_ores = up(n_obs * sizeof(a3_rig_observation_result));
+    const size_t b_tab = up(n_frames * rig_table_bytes()), b_oscr = up(n_obs * rig_obs_bytes()), b_fscr = up(n_frames * rig_frame_bytes());
+    A3_HIP(ctx->rig_in.ensure(b_rigs + b_cams + b_obs + 2 * b_pts));
+    A3_HIP(ctx->rig_scratch.ensure(b_tab + b_oscr + b_fscr));
+    A3_HIP(ctx->rig_out.ensure(b_res + b_cres + b_frames + b_ores));
+    uint8_t* din = ctx->rig_in.as<uint8_t>();
+    uint8_t* dscr = ctx->rig_scratch.as<uint8_t>();
+    uint8_t* dout = ctx->rig_out.as<uint8_t>();
+    A3_HIP(hipMemcpyAsync(din, rigs, n_rigs * sizeof(a3_rig), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(din + b_rigs, cameras, n_cameras * sizeof(a3_rig_camera), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(din + b_rigs + b_cams, obs, n_obs * sizeof(a3_rig_observation), hipMemcpyHostToDevice, ctx->stream));
+    if (n_pts) {
+        A3_HIP(hipMemcpyAsync(din + b_rigs + b_cams + b_obs, object_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        A3_HIP(hipMemcpyAsync(din + b_rigs + b_cams + b_obs + b_pts, image_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    // a camera, frame or observation that no rig owns is not written by the kernel: it comes back zero
+    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_cres + b_frames + b_ores, ctx->stream));
+    A3_HIP(launch_rig(ctx->stream, reinterpret_cast<const a3_rig*>(din), (uint32_t)n_rigs, reinterpret_cast<const a3_rig_camera*>(din + b_rigs),
+                      reinterpret_cast<const a3_rig_observation*>(din + b_rigs + b_cams), reinterpret_cast<const float*>(din + b_rigs + b_cams + b_obs),
+                      reinterpret_cast<const float*>(din + b_rigs + b_cams + b_obs + b_pts), reinterpret_cast<uint32_t*>(dscr),
+                      reinterpret_cast<double*>(dscr + b_tab), reinterpret_cast<double*>(dscr + b_tab + b_oscr), reinterpret_cast<a3_rig_result*>(dout),
+                      reinterpret_cast<a3_rig_camera_result*>(dout + b_res), reinterpret_cast<a3_rig_frame*>(dout + b_res + b_cres),
+                      reinterpret_cast<a3_rig_observation_result*>(dout + b_res + b_cres + b_frames)));
+    A3_HIP(hipMemcpyAsync(results, dout, n_rigs * sizeof(a3_rig_result), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipMemcpyAsync(camera_results, dout + b_res, n_cameras * sizeof(a3_rig_camera_result), hipMemcpyDeviceToHost, ctx->stream));
+    if (frames) A3_HIP(hipMemcpyAsync(frames, dout + b_res + b_cres, n_frames * sizeof(a3_rig_frame), hipMemcpyDeviceToHost, ctx->stream));
+    if (obs_results)
+        A3_HIP(hipMemcpyAsync(obs_results, dout + b_res + b_cres + b_frames, n_obs * sizeof(a3_rig_observation_result), hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }

@@ -1,6 +1,6 @@
 // a3_calib.h -- the per-point and per-view pieces of the camera calibration of include/aruco3_hip.h (a3_calibrate_cameras): the
-// projection with its 18 Jacobian columns, the homography rows, the 6 x 6 LDL^T and the Cayley update, all in f64.  k_calibrate
-// (k_calib.hip) is the only user.  Every expression is written in the contract's order and tests/calib_oracle.c restates each one
+// projection with its 18 Jacobian columns, the homography rows and the wave-level homography, the 6 x 6 and n x n LDL^T and the Cayley
+// update, all in f64.  k_calibrate (k_calib.hip) and k_rig (k_rig.hip, a3_calibrate_rigs) use them.  Every expression is written in the contract's order and tests/calib_oracle.c restates each one
 // in the same order; the library is built with -ffp-contract=off, so nothing is fused.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -82,14 +82,15 @@ __device__ __forceinline__ void hom_row(double X, double Y, double U, double V, 
     av[0] = 0.0; av[1] = 0.0; av[2] = 0.0; av[3] = X;   av[4] = Y;   av[5] = 1.0; av[6] = -(V * X); av[7] = -(V * Y); av[8] = V;
 }
 
-// LDL^T of V + lambda diag(V), V the 6 x 6 pose block of a view's 190 entries: L below the diagonal, D; false on a pivot that is not
-// positive and finite
-__device__ __forceinline__ bool ldl6(const double* blk, double lambda, double L[6][6], double D[6]) {
+// LDL^T of V + lambda diag(V), V the 6 x 6 block at columns OFF .. OFF + 5 of the upper triangle of an AUG x AUG sum: L below the
+// diagonal, D; false on a pivot that is not positive and finite
+template <int OFF, int AUG>
+__device__ __forceinline__ bool ldl6_at(const double* blk, double lambda, double L[6][6], double D[6]) {
     double A[6][6];
 #pragma unroll
     for (int r = 0; r < 6; r++)
 #pragma unroll
-        for (int c = r; c < 6; c++) { const double v = blk[tri_index(12 + r, 12 + c, kCalAug)]; A[r][c] = v; A[c][r] = v; }
+        for (int c = r; c < 6; c++) { const double v = blk[tri_index(OFF + r, OFF + c, AUG)]; A[r][c] = v; A[c][r] = v; }
 #pragma unroll
     for (int r = 0; r < 6; r++) A[r][r] = A[r][r] + lambda * A[r][r];
     bool ok = true;
@@ -109,6 +110,9 @@ __device__ __forceinline__ bool ldl6(const double* blk, double lambda, double L[
     }
     return ok;
 }
+
+// the pose block of a view's 190 entries
+__device__ __forceinline__ bool ldl6(const double* blk, double lambda, double L[6][6], double D[6]) { return ldl6_at<12, kCalAug>(blk, lambda, L, D); }
 
 __device__ __forceinline__ void ldl6_solve(const double L[6][6], const double D[6], const double b[6], double x[6]) {
     double y[6];
@@ -145,6 +149,149 @@ __device__ __forceinline__ void cayley_d(const double w[3], const double R[9], d
     for (int r = 0; r < 3; r++)
 #pragma unroll
         for (int c = 0; c < 3; c++) Rn[3 * r + c] = (C[3 * r] * R[c] + C[3 * r + 1] * R[3 + c]) + C[3 * r + 2] * R[6 + c];
+}
+
+__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+
+// step 1 for one view with >= 4 points (wave-level): -> whether the homography (row-major, H22 = 1) was written to H
+__device__ inline bool view_homography(const float* __restrict__ obj, const float* __restrict__ img, uint32_t p0, uint32_t np, double* rows, double* wv,
+                                int lane, double* H) {
+    if (lane == 0) {
+        double sx = 0.0, sy = 0.0, su = 0.0, sv = 0.0;
+        for (uint32_t j = 0; j < np; j++) {
+            const size_t p = (size_t)p0 + j;
+            sx = sx + (double)obj[2 * p];
+            sy = sy + (double)obj[2 * p + 1];
+            su = su + (double)img[2 * p];
+            sv = sv + (double)img[2 * p + 1];
+        }
+        const double n = (double)np;
+        const double mx = sx / n, my = sy / n, mu = su / n, mv = sv / n;
+        double dob = 0.0, dim = 0.0;
+        for (uint32_t j = 0; j < np; j++) {
+            const size_t p = (size_t)p0 + j;
+            const double ox = (double)obj[2 * p] - mx, oy = (double)obj[2 * p + 1] - my;
+            const double ix = (double)img[2 * p] - mu, iy = (double)img[2 * p + 1] - mv;
+            dob = dob + sqrt(ox * ox + oy * oy);
+            dim = dim + sqrt(ix * ix + iy * iy);
+        }
+        wv[0] = mx; wv[1] = my; wv[2] = 1.4142135623730951 / (dob / n);
+        wv[3] = mu; wv[4] = mv; wv[5] = 1.4142135623730951 / (dim / n);
+    }
+    wave_sync();
+    const double mx = wv[0], my = wv[1], so = wv[2], mu = wv[3], mv = wv[4], si = wv[5];
+    int ei = 0, ek = 0;
+    if (lane < kHomEntries) tri_ik(lane, kHomAug, &ei, &ek);
+    double acc = 0.0;
+    for (uint32_t c0 = 0; c0 < np; c0 += 64) {
+        const uint32_t cnt = min(64u, np - c0);
+        if ((uint32_t)lane < cnt) {
+            const size_t p = (size_t)p0 + c0 + (uint32_t)lane;
+            hom_row(((double)obj[2 * p] - mx) * so, ((double)obj[2 * p + 1] - my) * so, ((double)img[2 * p] - mu) * si,
+                    ((double)img[2 * p + 1] - mv) * si, rows + lane * 2 * kHomAug, rows + lane * 2 * kHomAug + kHomAug);
+        }
+        wave_sync();
+        for (uint32_t j = 0; j < cnt; j++) {
+            const double* u = rows + j * 2 * kHomAug;
+            const double* v = u + kHomAug;
+            acc = acc + u[ei] * u[ek];
+            acc = acc + v[ei] * v[ek];
+        }
+        wave_sync();
+    }
+    if (lane < kHomEntries) rows[lane] = acc;
+    wave_sync();
+    if (lane == 0) {
+        double* A = rows + 64;   // 8 x 8, then b (8), then h (8)
+        double* b = A + 64;
+        double* h = b + 8;
+        for (int i = 0; i < 8; i++) {
+            for (int k = 0; k < 8; k++) A[i * 8 + k] = rows[i <= k ? tri_index(i, k, kHomAug) : tri_index(k, i, kHomAug)];
+            b[i] = rows[tri_index(i, 8, kHomAug)];
+        }
+        double amax = 0.0;
+        for (int i = 0; i < 8; i++) {
+            const double d = fabs(A[i * 9]);
+            if (d > amax) amax = d;
+        }
+        const double thr = 1e-10 * amax;
+        bool ok = true;
+        for (int c = 0; c < 8 && ok; c++) {
+            int piv = c;
+            double best = fabs(A[c * 9]);
+            for (int r = c + 1; r < 8; r++) {
+                const double v = fabs(A[r * 8 + c]);
+                if (v > best) { best = v; piv = r; }
+            }
+            if (!(best > thr) || !fin(best)) { ok = false; break; }
+            if (piv != c) {
+                for (int k = 0; k < 8; k++) { const double s = A[piv * 8 + k]; A[piv * 8 + k] = A[c * 8 + k]; A[c * 8 + k] = s; }
+                const double s = b[piv]; b[piv] = b[c]; b[c] = s;
+            }
+            for (int r = c + 1; r < 8; r++) {
+                const double f = A[r * 8 + c] / A[c * 9];
+                for (int k = c + 1; k < 8; k++) A[r * 8 + k] = A[r * 8 + k] - f * A[c * 8 + k];
+                b[r] = b[r] - f * b[c];
+            }
+        }
+        if (ok) {
+            for (int r = 7; r >= 0; r--) {
+                double s = b[r];
+                for (int k = r + 1; k < 8; k++) s = s - A[r * 8 + k] * h[k];
+                h[r] = s / A[r * 9];
+            }
+            const double Hn[9] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], 1.0};
+            double M[9], G[9];
+            for (int r = 0; r < 3; r++) {
+                M[3 * r] = Hn[3 * r] * so;
+                M[3 * r + 1] = Hn[3 * r + 1] * so;
+                M[3 * r + 2] = Hn[3 * r + 2] - (M[3 * r] * mx + M[3 * r + 1] * my);
+            }
+            for (int c = 0; c < 3; c++) {
+                G[c] = M[c] / si + mu * M[6 + c];
+                G[3 + c] = M[3 + c] / si + mv * M[6 + c];
+                G[6 + c] = M[6 + c];
+            }
+            const double h22 = G[8];
+            for (int i = 0; i < 9; i++) {
+                const double v = G[i] / h22;
+                ok = ok && fin(v);
+                H[i] = v;
+            }
+        }
+        wv[6] = ok ? 1.0 : 0.0;
+    }
+    wave_sync();
+    return wv[6] != 0.0;
+}
+
+// LDL^T of the n x n matrix in A (row stride S, lower triangle read), L written below the diagonal; false on a bad pivot
+template <int S>
+__device__ inline bool ldl_n(double* A, int n, double* D) {
+    for (int j = 0; j < n; j++)
+        for (int i = j; i < n; i++) {
+            double s = A[i * S + j];
+            for (int k = 0; k < j; k++) s = s - A[i * S + k] * A[j * S + k] * D[k];
+            if (i == j) {
+                if (!(s > 0.0) || !fin(s)) return false;
+                D[j] = s;
+            } else A[i * S + j] = s / D[j];
+        }
+    return true;
+}
+
+template <int S>
+__device__ inline void ldl_n_solve(const double* A, int n, const double* D, const double* b, double* x) {
+    for (int i = 0; i < n; i++) {
+        double s = b[i];
+        for (int k = 0; k < i; k++) s = s - A[i * S + k] * x[k];
+        x[i] = s;
+    }
+    for (int i = n - 1; i >= 0; i--) {
+        double s = x[i] / D[i];
+        for (int k = i + 1; k < n; k++) s = s - A[k * S + i] * x[k];
+        x[i] = s;
+    }
 }
 
 }  // namespace a3

@@ -31,8 +31,6 @@ struct CalibArgs {
     a3_calib_view* views;
 };
 
-__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-
 __device__ __forceinline__ bool cal_free(uint32_t flags, int i) {
     if (i == 2 || i == 3) return !(flags & A3_CALIB_FIX_PRINCIPAL_POINT);
     if (i == 6 || i == 7) return !(flags & A3_CALIB_ZERO_TANGENT_DIST);
@@ -76,118 +74,6 @@ __device__ __forceinline__ void view_block(const double a[12], const double R[9]
     for (int q = 0; q < 3; q++)
         if (lane + 64 * q < kCalEntries) out[lane + 64 * q] = acc[q];
     wave_sync();
-}
-
-// step 1 for one view with >= 4 points (wave-level): -> whether the homography (row-major, H22 = 1) was written to H
-__device__ bool view_homography(const float* __restrict__ obj, const float* __restrict__ img, uint32_t p0, uint32_t np, double* rows, double* wv,
-                                int lane, double* H) {
-    if (lane == 0) {
-        double sx = 0.0, sy = 0.0, su = 0.0, sv = 0.0;
-        for (uint32_t j = 0; j < np; j++) {
-            const size_t p = (size_t)p0 + j;
-            sx = sx + (double)obj[2 * p];
-            sy = sy + (double)obj[2 * p + 1];
-            su = su + (double)img[2 * p];
-            sv = sv + (double)img[2 * p + 1];
-        }
-        const double n = (double)np;
-        const double mx = sx / n, my = sy / n, mu = su / n, mv = sv / n;
-        double dob = 0.0, dim = 0.0;
-        for (uint32_t j = 0; j < np; j++) {
-            const size_t p = (size_t)p0 + j;
-            const double ox = (double)obj[2 * p] - mx, oy = (double)obj[2 * p + 1] - my;
-            const double ix = (double)img[2 * p] - mu, iy = (double)img[2 * p + 1] - mv;
-            dob = dob + sqrt(ox * ox + oy * oy);
-            dim = dim + sqrt(ix * ix + iy * iy);
-        }
-        wv[0] = mx; wv[1] = my; wv[2] = 1.4142135623730951 / (dob / n);
-        wv[3] = mu; wv[4] = mv; wv[5] = 1.4142135623730951 / (dim / n);
-    }
-    wave_sync();
-    const double mx = wv[0], my = wv[1], so = wv[2], mu = wv[3], mv = wv[4], si = wv[5];
-    int ei = 0, ek = 0;
-    if (lane < kHomEntries) tri_ik(lane, kHomAug, &ei, &ek);
-    double acc = 0.0;
-    for (uint32_t c0 = 0; c0 < np; c0 += 64) {
-        const uint32_t cnt = min(64u, np - c0);
-        if ((uint32_t)lane < cnt) {
-            const size_t p = (size_t)p0 + c0 + (uint32_t)lane;
-            hom_row(((double)obj[2 * p] - mx) * so, ((double)obj[2 * p + 1] - my) * so, ((double)img[2 * p] - mu) * si,
-                    ((double)img[2 * p + 1] - mv) * si, rows + lane * 2 * kHomAug, rows + lane * 2 * kHomAug + kHomAug);
-        }
-        wave_sync();
-        for (uint32_t j = 0; j < cnt; j++) {
-            const double* u = rows + j * 2 * kHomAug;
-            const double* v = u + kHomAug;
-            acc = acc + u[ei] * u[ek];
-            acc = acc + v[ei] * v[ek];
-        }
-        wave_sync();
-    }
-    if (lane < kHomEntries) rows[lane] = acc;
-    wave_sync();
-    if (lane == 0) {
-        double* A = rows + 64;   // 8 x 8, then b (8), then h (8)
-        double* b = A + 64;
-        double* h = b + 8;
-        for (int i = 0; i < 8; i++) {
-            for (int k = 0; k < 8; k++) A[i * 8 + k] = rows[i <= k ? tri_index(i, k, kHomAug) : tri_index(k, i, kHomAug)];
-            b[i] = rows[tri_index(i, 8, kHomAug)];
-        }
-        double amax = 0.0;
-        for (int i = 0; i < 8; i++) {
-            const double d = fabs(A[i * 9]);
-            if (d > amax) amax = d;
-        }
-        const double thr = 1e-10 * amax;
-        bool ok = true;
-        for (int c = 0; c < 8 && ok; c++) {
-            int piv = c;
-            double best = fabs(A[c * 9]);
-            for (int r = c + 1; r < 8; r++) {
-                const double v = fabs(A[r * 8 + c]);
-                if (v > best) { best = v; piv = r; }
-            }
-            if (!(best > thr) || !fin(best)) { ok = false; break; }
-            if (piv != c) {
-                for (int k = 0; k < 8; k++) { const double s = A[piv * 8 + k]; A[piv * 8 + k] = A[c * 8 + k]; A[c * 8 + k] = s; }
-                const double s = b[piv]; b[piv] = b[c]; b[c] = s;
-            }
-            for (int r = c + 1; r < 8; r++) {
-                const double f = A[r * 8 + c] / A[c * 9];
-                for (int k = c + 1; k < 8; k++) A[r * 8 + k] = A[r * 8 + k] - f * A[c * 8 + k];
-                b[r] = b[r] - f * b[c];
-            }
-        }
-        if (ok) {
-            for (int r = 7; r >= 0; r--) {
-                double s = b[r];
-                for (int k = r + 1; k < 8; k++) s = s - A[r * 8 + k] * h[k];
-                h[r] = s / A[r * 9];
-            }
-            const double Hn[9] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], 1.0};
-            double M[9], G[9];
-            for (int r = 0; r < 3; r++) {
-                M[3 * r] = Hn[3 * r] * so;
-                M[3 * r + 1] = Hn[3 * r + 1] * so;
-                M[3 * r + 2] = Hn[3 * r + 2] - (M[3 * r] * mx + M[3 * r + 1] * my);
-            }
-            for (int c = 0; c < 3; c++) {
-                G[c] = M[c] / si + mu * M[6 + c];
-                G[3 + c] = M[3 + c] / si + mv * M[6 + c];
-                G[6 + c] = M[6 + c];
-            }
-            const double h22 = G[8];
-            for (int i = 0; i < 9; i++) {
-                const double v = G[i] / h22;
-                ok = ok && fin(v);
-                H[i] = v;
-            }
-        }
-        wv[6] = ok ? 1.0 : 0.0;
-    }
-    wave_sync();
-    return wv[6] != 0.0;
 }
 
 // step 4's per-view Schur terms at `lambda` from block slot `slot` (wave-level, every USED view of the wave); a bad pivot sets *bad
@@ -258,33 +144,6 @@ __device__ void camera_sums(const CalibArgs& g, uint32_t v0, uint32_t nv, int sl
             s = s + g.scratch[(size_t)v * kCalViewDoubles + kOffBlk + slot * kCalEntries + idx];
         }
         s_U[e] = s;
-    }
-}
-
-// LDL^T of the n x n matrix in A (row stride 12, lower triangle read), L written below the diagonal; false on a bad pivot
-__device__ bool ldl_n(double* A, int n, double* D) {
-    for (int j = 0; j < n; j++)
-        for (int i = j; i < n; i++) {
-            double s = A[i * 12 + j];
-            for (int k = 0; k < j; k++) s = s - A[i * 12 + k] * A[j * 12 + k] * D[k];
-            if (i == j) {
-                if (!(s > 0.0) || !fin(s)) return false;
-                D[j] = s;
-            } else A[i * 12 + j] = s / D[j];
-        }
-    return true;
-}
-
-__device__ void ldl_n_solve(const double* A, int n, const double* D, const double* b, double* x) {
-    for (int i = 0; i < n; i++) {
-        double s = b[i];
-        for (int k = 0; k < i; k++) s = s - A[i * 12 + k] * x[k];
-        x[i] = s;
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double s = x[i] / D[i];
-        for (int k = i + 1; k < n; k++) s = s - A[k * 12 + i] * x[k];
-        x[i] = s;
     }
 }
 
@@ -476,9 +335,9 @@ __global__ __launch_bounds__(kCalThreads) void k_calibrate(CalibArgs g) {
             __syncthreads();
             if (tid == 0) {
                 bool bad = s_bad != 0;
-                if (!bad) bad = !ldl_n(s_S, nf, s_D);
+                if (!bad) bad = !ldl_n<12>(s_S, nf, s_D);
                 if (!bad) {
-                    ldl_n_solve(s_S, nf, s_D, s_rhs, s_da);
+                    ldl_n_solve<12>(s_S, nf, s_D, s_rhs, s_da);
                     for (int i = 0; i < 12; i++) s_an[i] = s_a[i];
                     for (int c = 0; c < nf; c++) s_an[s_free[c]] = s_a[s_free[c]] + s_da[c];
                 }
@@ -554,13 +413,13 @@ __global__ __launch_bounds__(kCalThreads) void k_calibrate(CalibArgs g) {
         if (wave == 0 && !s_bad) schur_matrix(g, v0, nv, nf, s_U, 0.0, lane, s_S, s_rhs);
         __syncthreads();
         if (tid == 0) {
-            const bool pd = !s_bad && ldl_n(s_S, nf, s_D);
+            const bool pd = !s_bad && ldl_n<12>(s_S, nf, s_D);
             const double sigma2 = s_cost / (double)(2ll * s_np - nf - 6ll * s_vu);
             for (int i = 0; i < nf; i++) {
                 double diag = __builtin_inf();
                 if (pd) {
                     for (int k = 0; k < nf; k++) s_b[k] = k == i ? 1.0 : 0.0;
-                    ldl_n_solve(s_S, nf, s_D, s_b, s_x);
+                    ldl_n_solve<12>(s_S, nf, s_D, s_b, s_x);
                     diag = sqrt(sigma2 * s_x[i]);
                 }
                 s_rhs[i] = diag;   // (s_rhs is free now: the deviations of the free parameters)

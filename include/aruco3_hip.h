@@ -566,6 +566,111 @@ typedef struct a3_calib_view {
 int  a3_calibrate_cameras(a3_ctx *ctx, const a3_calib_camera *cams, size_t n_cams, const uint32_t *view_offsets, size_t n_views,
                           const float *object_xy, const float *image_xy, a3_calib_result *results, a3_calib_view *views);
 
+/* Camera rig calibration.  NOT in the reference: an opt-in extension (OpenCV's stereoCalibrate with CALIB_FIX_INTRINSIC, for any number
+ * of cameras), stand-alone as a3_calibrate_cameras is.  A rig has C cameras (2 .. A3_RIG_MAX_CAMERAS) with KNOWN intrinsics and lens
+ * (a3_rig_camera.a: fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6, what an a3_calib_result carries) and F frames (time instants at which every
+ * camera looked at the same board).  An observation is what one camera saw of the board in one frame: the points first_point ..
+ * first_point + n_points - 1 of object_xy / image_xy (the point format of a3_calibrate_cameras).  Unknowns: E_c = (R_c, t_c), rig ->
+ * camera c, for every camera but the rig's first (E_0 is the identity: the rig frame is camera 0's), and T_f = (R_f, t_f), board ->
+ * rig, for every frame.  A call solves n_rigs independent rigs (one workgroup each, k_rig); a rig owns contiguous, disjoint ranges of
+ * the call's cameras, frames and observations, and an observation names its camera and frame by their index in the call.
+ * Fixed to the bit as follows -- tests/rig_oracle.c a3o_calibrate_rigs restates it; arithmetic and notation as for a3_calibrate_cameras.
+ *   poses: A . B = (R_A R_B, R_A t_B + t_A) with R[3r+c] = (A[3r] B[c] + A[3r+1] B[3+c]) + A[3r+2] B[6+c] and
+ *     t[r] = ((A[3r] tB[0] + A[3r+1] tB[1]) + A[3r+2] tB[2]) + tA[r]; A^-1 = (R^T, t'), t'[r] = -((R[r] t[0] + R[3+r] t[1]) + R[6+r] t[2]).
+ *   row: for camera c (intrinsics a, E = (Rc, tc)), frame pose T = (Rf, tf) and G = E . T (board -> camera): the calibration's model and
+ *     its translation columns at (a, G) give the residual and u = d residual_u / dP, v likewise (its columns 15-17).  With
+ *     qf = (Rf0 X + Rf1 Y, Rf3 X + Rf4 Y, Rf6 X + Rf7 Y), y = qf + tf, qc[r] = (Rc[3r] y0 + Rc[3r+1] y1) + Rc[3r+2] y2 and
+ *     ur[j] = (u0 Rc[j] + u1 Rc[3+j]) + u2 Rc[6+j], a row of 13 is: columns 0-2 (w of R_c <- cay(w) R_c) u x-crossed with 2 qc exactly
+ *     as the calibration's columns 12-14 with q = qc, 3-5 (t_c) u, 6-8 (w of R_f) the same form with ur and 2 qf, 9-11 (t_f) ur, 12 the
+ *     residual.  An observation's block is the upper triangle of the 13 x 13 sum over its points (91 entries, summed as a view's
+ *     block).  For the rig's first camera columns 0-5 are computed, never read.
+ *   1. per observation with >= 4 points: step 1 of the calibration contract (homography; fewer than 4 points: TOO_FEW_POINTS, a bad
+ *      pivot: DEGENERATE, else USED), then its step 3 with the camera's a: the pose start from the homography and the pose's LM, run on
+ *      columns 6-12 of the block with E the exact identity and G = T -> P_cf = board -> camera c, and cost_cf.
+ *   2. start.  best(c, b) for cameras c != b: over the frames in which both have a USED observation, in frame order, the first with
+ *      the lowest cost_cf / n_cf + cost_bf / n_bf.  reached = {0}; repeat: over the unreached cameras c in index order and for each the
+ *      reached cameras b in index order, the first pair with a best(c, b): E_c = P_cf . (P_bf^-1 . E_b), c is reached, start over;
+ *      until no pair is found.  With USE_EXTRINSIC_GUESS E_c is the camera's guess instead (E_0 stays the identity), with
+ *      FIX_EXTRINSICS (which implies the guess) the walk decides nothing; otherwise a camera never reached gives the rig status
+ *      NOT_CONNECTED.  A frame with a USED observation is USED: T_f = E_c^-1 . P_cf from the observation with the lowest
+ *      cost_cf / n_cf (the first in camera order).  The other frames are UNUSED and take no part.
+ *   3. joint LM over x = (w, t) of E_1 .. E_{C-1} (6 (C - 1) unknowns, camera order) and every USED frame's pose, lambda 1e-3.  Sums
+ *      over a frame's observations run in camera order over the USED ones, sums over frames in frame order over the USED ones.
+ *      V_f, g_f, cost_f: the sums of columns 6-12 of the frame's blocks (28 entries); U_c, g_c: the sums of columns 0-5 and (0-5, 12) of
+ *      camera c's blocks over the frames; W_cf: entries (0-5, 6-11) of the block of (c, f).  An iteration: V_f + lambda diag(V_f)
+ *      by LDL^T (a bad pivot in any frame is a rejected step); y_i = V_f^-1 W_cf[i] for every extrinsic unknown i whose camera c sees
+ *      f, y_g = V_f^-1 g_f; S = U + lambda diag(U) - sum_f (term (i, k), i <= k, both cameras seeing f: sum over m of W_f[i][m] y_k[m]
+ *      from +0.0, subtracted), rhs_k = -g_k + sum_f (sum over m of W_f[k][m] y_g[m]); LDL^T of S (bad pivot: rejected), d_e;
+ *      per frame b_q = -g_f[q] - (sum over the unknowns k of the cameras seeing f, in order, of W_f[k][q] d_e[k]), d_f = V_f^-1 b;
+ *      R <- cay(w) R, t <- t + dt for the extrinsics and the frames; acceptance, lambda x10 / /10, convergence, max_iterations and
+ *      the stop at cost 0 exactly as step 4 of the calibration contract (the cost is the sum of the frames' costs).
+ *      With FIX_EXTRINSICS there is no camera-level block and every USED frame solves alone: the same loop per frame with
+ *      d_f = V_f^-1 (-g_f), the frame's own lambda, cost, iteration count and convergence; the rig reports the largest iteration count
+ *      and converged when every frame has.
+ *   4. rms_px = sqrt(cost / N) (N: points of the USED observations; 0 when N = 0), per camera, frame and observation the same over
+ *      their own blocks (a camera's cost: its observations' in frame order).  std_dev of camera c >= 1: sqrt(sigma2 diag(S0^-1)), S0 the
+ *      undamped Schur complement at the final state, sigma2 = cost / (2 N - 6 (C - 1) - 6 frames_used); +inf where S0 (or a V_f) is
+ *      not positive definite; 0 for the first camera and under FIX_EXTRINSICS.  A non-finite cost at the start of step 3: NOT_FINITE.
+ * A rig that is not solved reports its status and counts, its observations and frames their status and counts, zeros elsewhere.
+ * Input errors (A3_ERR_INVALID): null pointers, zero counts, unknown flags, C outside 2 .. A3_RIG_MAX_CAMERAS, max_iterations above
+ * A3_CALIB_MAX_ITERATIONS, empty, overlapping or out-of-range ranges, counts above the limits, an observation whose camera or frame lies
+ * outside its rig's ranges, two observations of one (camera, frame), more than A3_CALIB_MAX_POINTS points,
+ * non-finite coordinates or intrinsics, focal lengths <= 0, a non-finite guess under USE_EXTRINSIC_GUESS / FIX_EXTRINSICS.
+ * Synchronous; not while a submitted batch is in flight. */
+#define A3_RIG_MAX_CAMERAS           8       /* per rig */
+#define A3_RIG_MAX_FRAMES            4096    /* per rig */
+#define A3_RIG_MAX_RIGS              1024    /* per call */
+#define A3_RIG_MAX_CALL_FRAMES       65536   /* per call, all rigs */
+#define A3_RIG_MAX_CALL_OBSERVATIONS 262144  /* per call, all rigs */
+enum { A3_RIG_USE_EXTRINSIC_GUESS = 1, A3_RIG_FIX_EXTRINSICS = 2 };
+enum { A3_RIG_OK = 1, A3_RIG_NOT_CONNECTED = 2, A3_RIG_NOT_FINITE = 3 };
+enum { A3_RIG_OBS_USED = 1, A3_RIG_OBS_TOO_FEW_POINTS = 2, A3_RIG_OBS_DEGENERATE = 3 };
+enum { A3_RIG_FRAME_USED = 1, A3_RIG_FRAME_UNUSED = 2 };
+typedef struct a3_rig {                /* one problem */
+    uint32_t first_camera, n_cameras;  /* contiguous, disjoint ranges of the call's cameras, ... */
+    uint32_t first_frame, n_frames;    /* ... frames ... */
+    uint32_t first_obs, n_obs;         /* ... and observations */
+    uint32_t flags;                    /* A3_RIG_* */
+    uint32_t max_iterations;           /* LM iterations; 0 = A3_CALIB_DEFAULT_ITERATIONS */
+} a3_rig;
+typedef struct a3_rig_camera {
+    double   a[12];                    /* fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 */
+    double   guess_rotation[9], guess_translation[3];   /* rig -> camera; read with USE_EXTRINSIC_GUESS / FIX_EXTRINSICS, not for the first */
+} a3_rig_camera;
+typedef struct a3_rig_observation {
+    uint32_t camera, frame;            /* indices in the call, inside the rig's ranges */
+    uint32_t first_point, n_points;
+} a3_rig_observation;
+typedef struct a3_rig_result {
+    uint32_t status;                   /* A3_RIG_OK / _NOT_CONNECTED / _NOT_FINITE */
+    uint32_t frames_used, obs_used, points_used, iterations, converged;
+    double   rms_px;
+} a3_rig_result;
+typedef struct a3_rig_camera_result {
+    double   rotation[9], translation[3];       /* rig -> camera */
+    double   std_dev[6];                        /* of (w, t): w the Cayley increment at the solution */
+    double   rms_px;
+    float    rotation_f[9], translation_f[3];   /* the same in float, the a3_pose convention */
+    uint32_t obs_used, points_used;
+} a3_rig_camera_result;
+typedef struct a3_rig_frame {
+    uint32_t status, obs_used, points_used;     /* A3_RIG_FRAME_* */
+    float    rms_px;
+    double   rotation[9], translation[3];       /* board -> rig */
+    float    rotation_f[9], translation_f[3];
+} a3_rig_frame;
+typedef struct a3_rig_observation_result {
+    uint32_t status, points;                    /* A3_RIG_OBS_* */
+    float    rms_px;
+    uint32_t reserved;
+} a3_rig_observation_result;
+/* results: n_rigs; camera_results: n_cameras; frames: one record per frame of the call (the largest first_frame + n_frames of the
+ * rigs) and obs_results: n_obs records (both nullable); the point arrays hold the largest first_point + n_points of the observations */
+int  a3_calibrate_rigs(a3_ctx *ctx, const a3_rig *rigs, size_t n_rigs, const a3_rig_camera *cameras, size_t n_cameras,
+                       const a3_rig_observation *obs, size_t n_obs, const float *object_xy, const float *image_xy,
+                       a3_rig_result *results, a3_rig_camera_result *camera_results, a3_rig_frame *frames,
+                       a3_rig_observation_result *obs_results);
+
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);
 int  a3_calculate_tau(int device, const uint64_t *codes, size_t n_codes, uint8_t *tau);

@@ -257,6 +257,90 @@ pub struct A3CalibView {
     pub translation: [f32; 3],
 }
 
+/// a3_rig: one rig calibration problem (not in the reference; include/aruco3_hip.h states the algorithm)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3Rig {
+    pub first_camera: u32,
+    pub n_cameras: u32,
+    pub first_frame: u32,
+    pub n_frames: u32,
+    pub first_obs: u32,
+    pub n_obs: u32,
+    pub flags: u32,
+    pub max_iterations: u32,
+}
+
+/// a3_rig_camera: a rig camera's known intrinsics and lens (fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6) and its extrinsic guess
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct A3RigCamera {
+    pub a: [f64; 12],
+    pub guess_rotation: [f64; 9],
+    pub guess_translation: [f64; 3],
+}
+
+/// a3_rig_observation: what one camera saw of the board at one instant
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3RigObservation {
+    pub camera: u32,
+    pub frame: u32,
+    pub first_point: u32,
+    pub n_points: u32,
+}
+
+/// a3_rig_result: one rig's status and fit
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3RigResult {
+    pub status: u32,
+    pub frames_used: u32,
+    pub obs_used: u32,
+    pub points_used: u32,
+    pub iterations: u32,
+    pub converged: u32,
+    pub rms_px: f64,
+}
+
+/// a3_rig_camera_result: rig -> camera, its deviations and fit
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3RigCameraResult {
+    pub rotation: [f64; 9],
+    pub translation: [f64; 3],
+    pub std_dev: [f64; 6],
+    pub rms_px: f64,
+    pub rotation_f: [f32; 9],
+    pub translation_f: [f32; 3],
+    pub obs_used: u32,
+    pub points_used: u32,
+}
+
+/// a3_rig_frame: one instant's status and pose, board -> rig
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3RigFrame {
+    pub status: u32,
+    pub obs_used: u32,
+    pub points_used: u32,
+    pub rms_px: f32,
+    pub rotation: [f64; 9],
+    pub translation: [f64; 3],
+    pub rotation_f: [f32; 9],
+    pub translation_f: [f32; 3],
+}
+
+/// a3_rig_observation_result: one observation's status and fit
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3RigObservationResult {
+    pub status: u32,
+    pub points: u32,
+    pub rms_px: f32,
+    pub reserved: u32,
+}
+
 /// a3_stats: per-batch stage counters (the reference prints its rejects in debug builds, src/aruco.rs:163-164)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -381,6 +465,10 @@ extern "C" {
                                   n: *mut usize) -> c_int;
     pub fn a3_calibrate_cameras(ctx: *mut A3Ctx, cams: *const A3CalibCamera, n_cams: usize, view_offsets: *const u32, n_views: usize,
                                 object_xy: *const f32, image_xy: *const f32, results: *mut A3CalibResult, views: *mut A3CalibView) -> c_int;
+    pub fn a3_calibrate_rigs(ctx: *mut A3Ctx, rigs: *const A3Rig, n_rigs: usize, cameras: *const A3RigCamera, n_cameras: usize,
+                             obs: *const A3RigObservation, n_obs: usize, object_xy: *const f32, image_xy: *const f32,
+                             results: *mut A3RigResult, camera_results: *mut A3RigCameraResult, frames: *mut A3RigFrame,
+                             obs_results: *mut A3RigObservationResult) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
@@ -1217,6 +1305,37 @@ pub fn calibrate_camera(d: &Detector, views: &[Vec<((f32, f32), (f32, f32))>], i
         a3_calibrate_cameras(ctx.raw, &cam, 1, offsets.as_ptr(), views.len(), obj.as_ptr(), img.as_ptr(), &mut res, out.as_mut_ptr())
     }, "a3_calibrate_cameras");
     (res, out)
+}
+
+/// New (additive): the extrinsics of one camera rig solved on the device (`a3_calibrate_rigs`; not in the reference).  `cameras[c]`
+/// holds camera c's known intrinsics and lens (fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6, what `calibrate_camera` returns);
+/// `observations[i]` is (camera, frame, (board (x, y), pixel (u, v)) pairs): what that camera saw at that instant.  `flags` is 0
+/// here (the extrinsic guess and A3_RIG_FIX_EXTRINSICS go through the raw call).  Returns the rig's record, one record per camera
+/// (rig -> camera; the rig frame is camera 0's) and one per frame (board -> rig).
+pub fn calibrate_rig(d: &Detector, cameras: &[[f64; 12]], n_frames: u32, observations: &[(u32, u32, Vec<((f32, f32), (f32, f32))>)])
+                     -> (A3RigResult, Vec<A3RigCameraResult>, Vec<A3RigFrame>) {
+    let slot = slot_for(d);
+    let ctx = slot.lock().unwrap();
+    let (mut obj, mut img, mut obs) = (Vec::new(), Vec::new(), Vec::new());
+    for (camera, frame, pts) in observations {
+        obs.push(A3RigObservation { camera: *camera, frame: *frame, first_point: (obj.len() / 2) as u32, n_points: pts.len() as u32 });
+        for &((x, y), (u, w)) in pts {
+            obj.extend_from_slice(&[x, y]);
+            img.extend_from_slice(&[u, w]);
+        }
+    }
+    let eye = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0];
+    let cams: Vec<A3RigCamera> = cameras.iter().map(|a| A3RigCamera { a: *a, guess_rotation: eye, guess_translation: [0.0; 3] }).collect();
+    let rig = A3Rig { first_camera: 0, n_cameras: cams.len() as u32, first_frame: 0, n_frames, first_obs: 0, n_obs: obs.len() as u32,
+                      flags: 0, max_iterations: 0 };
+    let mut res = A3RigResult::default();
+    let mut cres = vec![A3RigCameraResult::default(); cams.len()];
+    let mut frames = vec![A3RigFrame::default(); n_frames as usize];
+    ctx.check(unsafe {
+        a3_calibrate_rigs(ctx.raw, &rig, 1, cams.as_ptr(), cams.len(), obs.as_ptr(), obs.len(), obj.as_ptr(), img.as_ptr(), &mut res,
+                          cres.as_mut_ptr(), frames.as_mut_ptr(), std::ptr::null_mut())
+    }, "a3_calibrate_rigs");
+    (res, cres, frames)
 }
 
 /// per-batch stage counters of the detector's last call

@@ -1,0 +1,65 @@
+"""ctypes binding of tests/rig_oracle.c: the CPU restatement of the camera rig calibration (a3_calibrate_rigs, include/aruco3_hip.h) that
+the device kernel k_rig is held to, and the C compiler's view of the structs.  TEST INFRASTRUCTURE ONLY -- the tests and
+tools/rig_bench.py load it; aruco3_amd never does.
+
+The library is compiled on first use into a temporary directory of its own (gcc / cc, the flags of tests/calib_oracle.py), so the
+repository tree is not written to."""
+import atexit
+import ctypes as C
+import os
+import shutil
+import subprocess
+import tempfile
+from pathlib import Path
+
+import numpy as np
+
+from aruco3_amd import _lib as A
+
+_SRC = Path(__file__).resolve().parent / "rig_oracle.c"
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
+        if cc is None:
+            raise RuntimeError("tests/rig_oracle.c needs a C compiler (gcc or cc)")
+        d = tempfile.mkdtemp(prefix="a3_rig_oracle_")
+        atexit.register(shutil.rmtree, d, True)
+        so = Path(d) / "librig_oracle.so"
+        subprocess.check_call([cc, "-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-fno-fast-math",
+                               "-fno-unsafe-math-optimizations", "-shared", "-o", str(so), str(_SRC), "-lm"])
+        L = C.CDLL(str(so))
+        f32p = C.POINTER(C.c_float)
+        L.a3o_calibrate_rigs.restype = C.c_int
+        L.a3o_calibrate_rigs.argtypes = [C.POINTER(A.Rig), C.c_size_t, C.POINTER(A.RigCamera), C.c_size_t, C.POINTER(A.RigObservation),
+                                         C.c_size_t, f32p, f32p, C.POINTER(A.RigResult), C.POINTER(A.RigCameraResult), C.POINTER(A.RigFrame),
+                                         C.c_size_t, C.POINTER(A.RigObservationResult)]
+        L.a3o_rig_layout.restype = None
+        L.a3o_rig_layout.argtypes = [C.POINTER(C.c_size_t)]
+        _lib = L
+    return _lib
+
+
+def calibrate_rigs(rigs, cameras, obs, object_xy, image_xy):
+    """a3o_calibrate_rigs: the arguments and the result of Context.calibrate_rigs"""
+    obj = np.ascontiguousarray(np.asarray(object_xy, dtype=np.float32).reshape(-1, 2))
+    img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 2))
+    n_frames = max([int(r.first_frame) + int(r.n_frames) for r in rigs], default=0)
+    res = (A.RigResult * max(len(rigs), 1))()
+    cres = (A.RigCameraResult * max(len(cameras), 1))()
+    frames = (A.RigFrame * max(n_frames, 1))()
+    ores = (A.RigObservationResult * max(len(obs), 1))()
+    rc = lib().a3o_calibrate_rigs(rigs, len(rigs), cameras, len(cameras), obs, len(obs), obj.ctypes.data_as(C.POINTER(C.c_float)),
+                                  img.ctypes.data_as(C.POINTER(C.c_float)), res, cres, frames, n_frames, ores)
+    assert rc == 0
+    return res, cres, frames, ores
+
+
+def layout():
+    """sizes and offsets of the a3_rig* structs as gcc lays out include/aruco3_hip.h (a3o_rig_layout's order)"""
+    out = (C.c_size_t * 20)()
+    lib().a3o_rig_layout(out)
+    return list(out)

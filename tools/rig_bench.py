@@ -1,0 +1,70 @@
+"""Camera rig calibration cost (a3_calibrate_rigs / k_rig): end-to-end call time per shape on the MI355X against the CPU oracle
+(tests/rig_oracle.c, one thread).  Kernel times come from running this under
+`rocprofv3 --kernel-trace --stats -- python tools/rig_bench.py` (k_rig's rows of the kernel trace, in launch order: the warm-up
+and `--reps` calls of every shape).
+
+    python tools/rig_bench.py [--reps 3] [--shapes 1x2x25x24,1x4x100x140,1x8x500x140,16x2x25x24] [--fix]
+
+A shape is rigs x cameras x frames x points per observation (24: the inner corners of a 5 x 7 ChArUco board, 140: the marker corners of
+a 5 x 7 GridBoard).  One JSON line per shape: device ms per call (median), oracle ms, iterations, the worst extrinsic error against
+the truth and the rms of the solve.  The observations are synthetic: board points projected through known cameras at known extrinsics
+by the contract's own model, with 0.2 px of Gaussian noise, every camera seeing every frame.  --fix runs the same shapes with the
+true extrinsics fixed (one fused board pose per frame).  Accuracy on rendered and detected frames is measured by
+tests/test_gpu_rig.py, which prints it; DESIGN.md section 4.10 reports it."""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+from aruco3_amd import _lib  # noqa: E402
+from tests import rig_oracle as ro  # noqa: E402
+from tests import rig_util as ru  # noqa: E402
+
+SHAPES = "1x2x25x24,1x4x100x140,1x8x500x140,16x2x25x24"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--shapes", default=SHAPES)
+    ap.add_argument("--fix", action="store_true")
+    ap.add_argument("--no-oracle", action="store_true")
+    args = ap.parse_args()
+    import torch
+
+    if not torch.cuda.is_available():
+        sys.exit("rig_bench needs the MI355X")
+    ctx = _lib.Context(_lib.default_config(), np.zeros(1, np.uint64), 64, 1)
+    if not args.no_oracle:
+        ro.lib()                                        # (compiled on first use: not part of the first shape's oracle time)
+    for shape in args.shapes.split(","):
+        n_rigs, n_cams, n_frames, n_pts = (int(v) for v in shape.split("x"))
+        ps = [ru.make_rig(n_cams, n_frames, seed=k, kind="charuco" if n_pts == 24 else "grid", noise=0.2, subsets=False) for k in range(n_rigs)]
+        packed = ru.pack(ps, flags=_lib.RIG_FIX_EXTRINSICS if args.fix else 0, guess=[p["E"] for p in ps])
+        ctx.calibrate_rigs(*packed)                     # warm-up: code object load, scratch growth
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            res, cres, frames, ores = ctx.calibrate_rigs(*packed)
+            times.append((time.perf_counter() - t0) * 1e3)
+        errs = [ru.extrinsic_errors(cres, p["E"], c0=n_cams * k) for k, p in enumerate(ps)]
+        line = dict(rigs=n_rigs, cameras=n_cams, frames=n_frames, points=n_pts, fix=bool(args.fix), device_ms=float(np.median(times)),
+                    device_ms_all=[round(t, 3) for t in times], iterations=[int(r.iterations) for r in res][:4],
+                    status=sorted({int(r.status) for r in res}), rotation_err_deg_max=max(e[0] for e in errs),
+                    translation_rel_err_max=max(e[1] for e in errs), rms_px=float(res[0].rms_px))
+        if not args.no_oracle:
+            t0 = time.perf_counter()
+            ora = ro.calibrate_rigs(*packed)
+            line["oracle_ms"] = (time.perf_counter() - t0) * 1e3
+            line["bit_equal"] = all(bytes(a) == bytes(b) for a, b in zip(res, ora[0])) and all(bytes(a) == bytes(b) for a, b in zip(cres, ora[1]))
+        print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
