@@ -1238,6 +1238,8 @@ int a3_create(int device, const a3_config* cfg, const uint64_t* codes, size_t n_
     a3_ctx* ctx = nullptr;
     if (!cfg || !out || (!codes && n_codes)) return fail(ctx, A3_ERR_INVALID, "a3_create: null argument");
     if (cfg->threshold_window == 0) return fail(ctx, A3_ERR_INVALID, "threshold_window must be > 0 (imageproc asserts block_radius > 0)");
+    if (cfg->threshold_window > 0x7FFFFFFFu)
+        return fail(ctx, A3_ERR_INVALID, "threshold_window must be at most 2^31 - 1 (the threshold kernels take the radius as a signed 32-bit int)");
     if (!(cfg->contour_simplification_epsilon > 0.0)) return fail(ctx, A3_ERR_INVALID, "contour_simplification_epsilon must be > 0");
     if (cfg->homography_sample_size == 0 || cfg->homography_sample_size > 200)
         return fail(ctx, A3_ERR_INVALID, "homography_sample_size must be in 1..200");

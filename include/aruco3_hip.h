@@ -49,9 +49,12 @@ enum { A3_MEM_HOST = 0, A3_MEM_DEVICE = 1 };
 
 /* DetectorConfig, src/aruco.rs:23-43 (same fields, same defaults via a3_default_config) */
 typedef struct a3_config {
-    uint32_t threshold_window;               /* 7.  The block radius of adaptive_threshold (src/aruco.rs:61): the window is 2r+1 wide.  Every value
-                                                * >= 1 gives the reference's result; 1..31 run fused one-pass kernels (1..7 at about the speed of 7,
-                                                * 8..26 at 1.1-1.35 x, 27..31 at 2.3-2.5 x), larger windows a separable three-pass path (8-9 x) */
+    uint32_t threshold_window;               /* 7.  The block radius of adaptive_threshold (src/aruco.rs:61): the window is 2r+1 wide.  Accepted:
+                                                * 1 .. 2^31 - 1 (0 and anything above: A3_ERR_INVALID from a3_create; the kernels take the radius as
+                                                * a signed int, and a window that covers the frame is reached long before).  Every accepted value
+                                                * gives the reference's result; 1..31 run fused one-pass kernels (1..7 at about the speed of 7,
+                                                * 8..26 at 1.1-1.35 x, 27..31 at 2.3-2.5 x), 32..128 a separable three-pass path (8-9 x), larger
+                                                * windows a brute-force kernel whose work grows with the clipped window's area */
     double   contour_simplification_epsilon; /* 0.05 */
     float    min_side_length_factor;         /* 0.2 */
     float    min_corner_separation_factor;   /* 0.1 */
