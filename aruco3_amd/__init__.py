@@ -35,6 +35,10 @@ def __getattr__(name):
         from . import rig
 
         return getattr(rig, name)
+    if name in ("MarkerMap", "build_marker_map", "build_marker_maps", "locate_in_map"):
+        from . import markermap
+
+        return getattr(markermap, name)
     if name == "pose":
         import importlib
 

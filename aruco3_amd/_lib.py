@@ -40,6 +40,13 @@ RIG_OK, RIG_NOT_CONNECTED, RIG_NOT_FINITE = 1, 2, 3
 RIG_OBS_USED, RIG_OBS_TOO_FEW_POINTS, RIG_OBS_DEGENERATE = 1, 2, 3
 RIG_FRAME_USED, RIG_FRAME_UNUSED = 1, 2
 RIG_MAX_CAMERAS, RIG_MAX_FRAMES, RIG_MAX_RIGS, RIG_MAX_CALL_FRAMES, RIG_MAX_CALL_OBSERVATIONS = 8, 4096, 1024, 65536, 262144
+# a3_build_marker_maps (include/aruco3_hip.h A3_MAP_*)
+MAP_USE_GUESS, MAP_FIX_MAP = 1, 2
+MAP_OK, MAP_NOT_CONNECTED, MAP_NOT_FINITE = 1, 2, 3
+MAP_MARKER_USED, MAP_MARKER_UNSEEN, MAP_MARKER_UNREACHED = 1, 2, 3
+MAP_FRAME_USED, MAP_FRAME_UNUSED = 1, 2
+MAP_OBS_USED, MAP_OBS_DEGENERATE, MAP_OBS_UNREACHED = 1, 2, 3
+MAP_MAX_MARKERS, MAP_MAX_FRAMES, MAP_MAX_MAPS, MAP_MAX_CALL_FRAMES, MAP_MAX_CALL_OBSERVATIONS, MAP_START_OBSERVATIONS = 128, 4096, 1024, 65536, 262144, 8
 STEP_NAMES = {0: "whole", 1: "decode_deferred", 2: "held_released_by_last", 3: "held_released_early", 4: "burst_last", 5: "held"}
 
 # every symbol include/aruco3_hip.h declares
@@ -54,7 +61,7 @@ SYMBOLS = [
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
-    "a3_calibrate_cameras", "a3_calibrate_rigs",
+    "a3_calibrate_cameras", "a3_calibrate_rigs", "a3_build_marker_maps",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
 INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
@@ -184,6 +191,41 @@ class RigFrame(C.Structure):
 
 class RigObservationResult(C.Structure):
     _fields_ = [("status", C.c_uint32), ("points", C.c_uint32), ("rms_px", C.c_float), ("reserved", C.c_uint32)]
+
+
+class Map(C.Structure):
+    """a3_map: one marker map problem (an extension beyond the reference; include/aruco3_hip.h states the algorithm)"""
+    _fields_ = [("first_marker", C.c_uint32), ("n_markers", C.c_uint32), ("first_frame", C.c_uint32), ("n_frames", C.c_uint32),
+                ("first_obs", C.c_uint32), ("n_obs", C.c_uint32), ("flags", C.c_uint32), ("max_iterations", C.c_uint32),
+                ("a", C.c_double * 12), ("marker_length", C.c_float), ("reserved", C.c_uint32)]
+
+
+class MapMarker(C.Structure):
+    _fields_ = [("guess_rotation", C.c_double * 9), ("guess_translation", C.c_double * 3)]
+
+
+class MapObservation(C.Structure):
+    _fields_ = [("marker", C.c_uint32), ("frame", C.c_uint32)]
+
+
+class MapResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("markers_used", C.c_uint32), ("frames_used", C.c_uint32), ("obs_used", C.c_uint32),
+                ("iterations", C.c_uint32), ("converged", C.c_uint32), ("rms_px", C.c_double)]
+
+
+class MapMarkerResult(C.Structure):
+    _fields_ = [("rotation", C.c_double * 9), ("translation", C.c_double * 3), ("std_dev", C.c_double * 6), ("rms_px", C.c_double),
+                ("corners", C.c_double * 12), ("rotation_f", C.c_float * 9), ("translation_f", C.c_float * 3), ("status", C.c_uint32),
+                ("obs_used", C.c_uint32)]
+
+
+class MapFrame(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("obs_used", C.c_uint32), ("rms_px", C.c_float), ("reserved", C.c_uint32),
+                ("rotation", C.c_double * 9), ("translation", C.c_double * 3), ("rotation_f", C.c_float * 9), ("translation_f", C.c_float * 3)]
+
+
+class MapObservationResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("rms_px", C.c_float), ("start_rms_px", C.c_float * 2)]
 
 
 class Stats(C.Structure):
@@ -368,6 +410,11 @@ def load():
         L.a3_calibrate_rigs.argtypes = [vp, C.POINTER(Rig), C.c_size_t, C.POINTER(RigCamera), C.c_size_t, C.POINTER(RigObservation), C.c_size_t,
                                         f32p, f32p, C.POINTER(RigResult), C.POINTER(RigCameraResult), C.POINTER(RigFrame),
                                         C.POINTER(RigObservationResult)]
+    if hasattr(L, "a3_build_marker_maps"):
+        L.a3_build_marker_maps.restype = C.c_int
+        L.a3_build_marker_maps.argtypes = [vp, C.POINTER(Map), C.c_size_t, C.POINTER(MapMarker), C.c_size_t, C.POINTER(MapObservation),
+                                           C.c_size_t, f32p, C.POINTER(MapResult), C.POINTER(MapMarkerResult), C.POINTER(MapFrame),
+                                           C.POINTER(MapObservationResult)]
     if hasattr(L, "a3_calibrate_cameras"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack calibration)
         L.a3_calibrate_cameras.restype = C.c_int
         L.a3_calibrate_cameras.argtypes = [vp, C.POINTER(CalibCamera), C.c_size_t, u32p, C.c_size_t, f32p, f32p, C.POINTER(CalibResult),
@@ -752,6 +799,22 @@ class Context:
         check(load().a3_calibrate_rigs(self.handle, rigs, len(rigs), cameras, len(cameras), obs, len(obs), _p(obj, C.c_float), _p(img, C.c_float),
                                        res, cres, frames, ores), self.handle)
         return res, cres, frames, ores
+
+    # ---- marker maps ----
+    def build_marker_maps(self, maps, markers, obs, image_xy):
+        """a3_build_marker_maps: maps (a Map array), markers (MapMarker array), obs (MapObservation array), image corners (n_obs, 8) ->
+        (MapResult array, MapMarkerResult array, MapFrame array, MapObservationResult array)"""
+        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 8))
+        n_frames = max([int(r.first_frame) + int(r.n_frames) for r in maps], default=0)
+        res = (MapResult * max(len(maps), 1))()
+        mres = (MapMarkerResult * max(len(markers), 1))()
+        frames = (MapFrame * max(n_frames, 1))()
+        ores = (MapObservationResult * max(len(obs), 1))()
+        fn = getattr(load(), "a3_build_marker_maps", None)
+        if fn is None:
+            raise A3Error(-1, "this libaruco3_hip.so has no a3_build_marker_maps")
+        check(fn(self.handle, maps, len(maps), markers, len(markers), obs, len(obs), _p(img, C.c_float), res, mres, frames, ores), self.handle)
+        return res, mres, frames, ores
 
     # ---- Detection.grey / thresholded / candidates / homographies of the last batch ----
     def download_grey(self, frame: int, w: int, h: int, thresholded: bool = False) -> np.ndarray:

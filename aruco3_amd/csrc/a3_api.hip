@@ -81,6 +81,11 @@ hipError_t launch_charuco_pose(hipStream_t, const a3_marker*, const float*, cons
                                uint32_t, const void*, const float*, uint32_t, const uint32_t*, const a3_charuco_corner*, const float*,
                                const a3_intrinsics*, uint32_t, uint32_t, a3_charuco_pose*);
 hipError_t launch_calc_tau(hipStream_t, const uint64_t*, uint32_t, unsigned int*);
+size_t map_obs_bytes();
+size_t map_frame_bytes();
+size_t map_marker_bytes();
+hipError_t launch_map(hipStream_t, const a3_map*, uint32_t, const a3_map_marker*, const a3_map_observation*, const float*, const uint64_t*, uint32_t*,
+                      uint32_t*, double*, double*, double*, double*, a3_map_result*, a3_map_marker_result*, a3_map_frame*, a3_map_observation_result*);
 size_t rig_obs_bytes();
 size_t rig_frame_bytes();
 size_t rig_table_bytes();
@@ -310,6 +315,9 @@ struct a3_ctx {
     // a3_calibrate_rigs: [rigs | cameras | observations | object points | image points], [table | per-observation | per-frame scratch],
     // [results | camera results | frames | observation results]
     DevBuf rig_in, rig_scratch, rig_out;
+    // a3_build_marker_maps: [maps | markers | observations | image corners | matrix offsets], [tables | per-observation | per-frame |
+    // per-marker scratch], the reduced systems (two n x n per map), [results | marker results | frames | observation results]
+    DevBuf map_in, map_scratch, map_big, map_out;
     uint32_t last_charuco_total = 0;   // sizes the speculative record read-back of the next batch
     void* pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1319,7 +1327,8 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
                       &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->calib_in,
-                      &ctx->calib_scratch, &ctx->calib_out, &ctx->rig_in, &ctx->rig_scratch, &ctx->rig_out};
+                      &ctx->calib_scratch, &ctx->calib_out, &ctx->rig_in, &ctx->rig_scratch, &ctx->rig_out,
+                      &ctx->map_in, &ctx->map_scratch, &ctx->map_big, &ctx->map_out};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -2585,6 +2594,113 @@ int a3_calibrate_rigs(a3_ctx* ctx, const a3_rig* rigs, size_t n_rigs, const a3_r
     if (frames) A3_HIP(hipMemcpyAsync(frames, dout + b_res + b_cres, n_frames * sizeof(a3_rig_frame), hipMemcpyDeviceToHost, ctx->stream));
     if (obs_results)
         A3_HIP(hipMemcpyAsync(obs_results, dout + b_res + b_cres + b_frames, n_obs * sizeof(a3_rig_observation_result), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+int a3_build_marker_maps(a3_ctx* ctx, const a3_map* maps, size_t n_maps, const a3_map_marker* markers, size_t n_markers, const a3_map_observation* obs,
+                         size_t n_obs, const float* image_xy, a3_map_result* results, a3_map_marker_result* marker_results, a3_map_frame* frames,
+                         a3_map_observation_result* obs_results) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!maps || !markers || !obs || !image_xy || !results || !marker_results) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: null argument");
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a submitted batch has not been collected");
+    if (n_maps == 0 || n_maps > A3_MAP_MAX_MAPS) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: n_maps must be in 1..A3_MAP_MAX_MAPS");
+    if (n_markers == 0 || n_markers > (size_t)A3_MAP_MAX_MAPS * A3_MAP_MAX_MARKERS) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: n_markers out of range");
+    if (n_obs == 0 || n_obs > A3_MAP_MAX_CALL_OBSERVATIONS)
+        return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: n_obs must be in 1..A3_MAP_MAX_CALL_OBSERVATIONS");
+    size_t n_frames = 0;
+    for (size_t r = 0; r < n_maps; r++) {
+        const a3_map& R = maps[r];
+        if (R.flags & ~3u) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: unknown flags");
+        if (R.n_markers < 1 || R.n_markers > A3_MAP_MAX_MARKERS) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's n_markers must be in 1..A3_MAP_MAX_MARKERS");
+        if (R.max_iterations > A3_CALIB_MAX_ITERATIONS) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: max_iterations above A3_CALIB_MAX_ITERATIONS");
+        if (R.n_frames == 0 || R.n_frames > A3_MAP_MAX_FRAMES) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's n_frames must be in 1..A3_MAP_MAX_FRAMES");
+        if (R.n_obs == 0) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map has no observations");
+        if ((uint64_t)R.first_marker + R.n_markers > n_markers) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's markers lie past n_markers");
+        if ((uint64_t)R.first_obs + R.n_obs > n_obs) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's observations lie past n_obs");
+        if ((uint64_t)R.first_frame + R.n_frames > A3_MAP_MAX_CALL_FRAMES)
+            return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's frames lie past A3_MAP_MAX_CALL_FRAMES");
+        for (double v : R.a)
+            if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: the camera's intrinsics are not finite");
+        if (!(R.a[0] > 0.0) || !(R.a[1] > 0.0)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: focal lengths must be > 0");
+        if (!std::isfinite(R.marker_length) || !(R.marker_length > 0.0f)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: marker_length must be finite and > 0");
+        n_frames = std::max(n_frames, (size_t)R.first_frame + R.n_frames);
+    }
+    std::vector<uint8_t> marker_owned(n_markers, 0), frame_owned(n_frames, 0), obs_owned(n_obs, 0);
+    std::vector<uint64_t> big_off(n_maps, 0);
+    uint64_t big_doubles = 0;
+    for (size_t r = 0; r < n_maps; r++) {
+        const a3_map& R = maps[r];
+        for (uint32_t m = R.first_marker; m < R.first_marker + R.n_markers; m++) {
+            if (marker_owned[m]) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: two maps share a marker");
+            marker_owned[m] = 1;
+            if (R.flags && m > R.first_marker) {
+                for (double v : markers[m].guess_rotation)
+                    if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: the marker guess is not finite");
+                for (double v : markers[m].guess_translation)
+                    if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: the marker guess is not finite");
+            }
+        }
+        for (uint32_t f = R.first_frame; f < R.first_frame + R.n_frames; f++) {
+            if (frame_owned[f]) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: two maps share a frame");
+            frame_owned[f] = 1;
+        }
+        for (uint32_t o = R.first_obs; o < R.first_obs + R.n_obs; o++) {
+            if (obs_owned[o]) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: two maps share an observation");
+            obs_owned[o] = 1;
+            const a3_map_observation& ob = obs[o];
+            if (ob.marker < R.first_marker || ob.marker - R.first_marker >= R.n_markers)
+                return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: an observation's marker lies outside its map");
+            if (ob.frame < R.first_frame || ob.frame - R.first_frame >= R.n_frames)
+                return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: an observation's frame lies outside its map");
+            if (o > R.first_obs) {
+                const a3_map_observation& pv = obs[o - 1];
+                if (pv.frame == ob.frame && pv.marker == ob.marker) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: two observations of one (marker, frame)");
+                if (pv.frame > ob.frame || (pv.frame == ob.frame && pv.marker > ob.marker))
+                    return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's observations must be listed by frame, then by marker");
+            }
+            for (size_t i = 8 * (size_t)o; i < 8 * ((size_t)o + 1); i++)
+                if (!std::isfinite(image_xy[i])) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a corner is not finite");
+        }
+        const uint64_t nmax = (R.flags & A3_MAP_FIX_MAP) ? 0 : 6ull * (R.n_markers - 1);
+        big_off[r] = big_doubles;
+        big_doubles += 2 * nmax * nmax;
+    }
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_maps = up(n_maps * sizeof(a3_map)), b_mk = up(n_markers * sizeof(a3_map_marker)), b_obs = up(n_obs * sizeof(a3_map_observation));
+    const size_t b_img = up(n_obs * 8 * sizeof(float)), b_off = up(n_maps * sizeof(uint64_t));
+    const size_t b_res = up(n_maps * sizeof(a3_map_result)), b_mres = up(n_markers * sizeof(a3_map_marker_result));
+    const size_t b_frames = up(n_frames * sizeof(a3_map_frame)), b_ores = up(n_obs * sizeof(a3_map_observation_result));
+    const size_t b_fo = up(n_frames * sizeof(uint32_t)), b_ml = up(n_obs * sizeof(uint32_t));
+    const size_t b_oscr = up(n_obs * map_obs_bytes()), b_fscr = up(n_frames * map_frame_bytes()), b_mscr = up(n_markers * map_marker_bytes());
+    A3_HIP(ctx->map_in.ensure(b_maps + b_mk + b_obs + b_img + b_off));
+    A3_HIP(ctx->map_scratch.ensure(b_fo + b_ml + b_oscr + b_fscr + b_mscr));
+    A3_HIP(ctx->map_big.ensure(std::max<size_t>(big_doubles, 1) * sizeof(double)));
+    A3_HIP(ctx->map_out.ensure(b_res + b_mres + b_frames + b_ores));
+    uint8_t* din = ctx->map_in.as<uint8_t>();
+    uint8_t* dscr = ctx->map_scratch.as<uint8_t>();
+    uint8_t* dout = ctx->map_out.as<uint8_t>();
+    A3_HIP(hipMemcpyAsync(din, maps, n_maps * sizeof(a3_map), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(din + b_maps, markers, n_markers * sizeof(a3_map_marker), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(din + b_maps + b_mk, obs, n_obs * sizeof(a3_map_observation), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(din + b_maps + b_mk + b_obs, image_xy, n_obs * 8 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(din + b_maps + b_mk + b_obs + b_img, big_off.data(), n_maps * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    // a marker, frame or observation that no map owns is not written by the kernel: it comes back zero
+    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_mres + b_frames + b_ores, ctx->stream));
+    A3_HIP(launch_map(ctx->stream, reinterpret_cast<const a3_map*>(din), (uint32_t)n_maps, reinterpret_cast<const a3_map_marker*>(din + b_maps),
+                      reinterpret_cast<const a3_map_observation*>(din + b_maps + b_mk), reinterpret_cast<const float*>(din + b_maps + b_mk + b_obs),
+                      reinterpret_cast<const uint64_t*>(din + b_maps + b_mk + b_obs + b_img), reinterpret_cast<uint32_t*>(dscr),
+                      reinterpret_cast<uint32_t*>(dscr + b_fo), reinterpret_cast<double*>(dscr + b_fo + b_ml),
+                      reinterpret_cast<double*>(dscr + b_fo + b_ml + b_oscr), reinterpret_cast<double*>(dscr + b_fo + b_ml + b_oscr + b_fscr),
+                      ctx->map_big.as<double>(), reinterpret_cast<a3_map_result*>(dout), reinterpret_cast<a3_map_marker_result*>(dout + b_res),
+                      reinterpret_cast<a3_map_frame*>(dout + b_res + b_mres), reinterpret_cast<a3_map_observation_result*>(dout + b_res + b_mres + b_frames)));
+    A3_HIP(hipMemcpyAsync(results, dout, n_maps * sizeof(a3_map_result), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipMemcpyAsync(marker_results, dout + b_res, n_markers * sizeof(a3_map_marker_result), hipMemcpyDeviceToHost, ctx->stream));
+    if (frames) A3_HIP(hipMemcpyAsync(frames, dout + b_res + b_mres, n_frames * sizeof(a3_map_frame), hipMemcpyDeviceToHost, ctx->stream));
+    if (obs_results)
+        A3_HIP(hipMemcpyAsync(obs_results, dout + b_res + b_mres + b_frames, n_obs * sizeof(a3_map_observation_result), hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }

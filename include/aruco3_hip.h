@@ -674,6 +674,132 @@ int  a3_calibrate_rigs(a3_ctx *ctx, const a3_rig *rigs, size_t n_rigs, const a3_
                        a3_rig_result *results, a3_rig_camera_result *camera_results, a3_rig_frame *frames,
                        a3_rig_observation_result *obs_results);
 
+/* Marker maps.  NOT in the reference: an opt-in extension (what the ArUco library ships as MarkerMap / marker mapper), stand-alone as
+ * a3_calibrate_rigs is.  A map has M square markers (1 .. A3_MAP_MAX_MARKERS) of one side length marker_length, taped anywhere in a
+ * room, one camera with KNOWN intrinsics and lens (a3_map.a, the order of a3_rig_camera.a) and F frames of that camera.  An
+ * observation is one marker seen in one frame: observation i's four corners are image_xy[8 i .. 8 i + 7] (raw pixels, a3_marker
+ * corner order); its object points are the square (-h, h), (h, h), (h, -h), (-h, -h), h = marker_length * 0.5f (float, then converted),
+ * on the plane z = 0 of the marker's own frame.  Unknowns: M_m = marker m -> world for every marker but the map's first (M_0 is the
+ * exact identity: the world frame is marker 0's), and T_f = world -> camera for every frame.  A call solves n_maps independent maps
+ * (one workgroup each, k_map); a map owns contiguous, disjoint ranges of the call's markers, frames and observations, an observation
+ * names its marker and frame by their index in the call, and a map's observations are listed frame by frame, inside a frame by
+ * ascending marker (so one (marker, frame) appears once).  A marker may have no observation.
+ * Fixed to the bit as follows -- tests/map_oracle.c a3o_build_marker_maps restates it; arithmetic, notation, poses and the row of 13
+ * as for a3_calibrate_rigs with E := T_f and T := M_m, G = T_f . M_m: columns 0-5 are (w, t) of the frame, 6-11 (w, t) of the marker, 12
+ * the residual; an observation's block is the 91-entry triangle over its four points in corner order.
+ *   cost(G, o): the sum over observation o's corners, in order, of s += ru ru; s += rv rv, (ru, rv) the model's residual at (a, G).  A
+ *     cost that is not finite counts as +inf.  "lowest" below means the first, in the stated order, that no other undercuts.
+ *   1. per observation: step 1 of the calibration contract on its four points (a bad pivot: DEGENERATE, else USED), then the pose
+ *      start and pose LM of step 1 of the rig contract -> candidate P_o[0] = marker -> camera and c_o[0].  The second planar
+ *      candidate starts from the mirrored pose: with (R, t) = P_o[0], n = sqrt((t0 t0 + t1 t1) + t2 t2), v = t / n, for each column
+ *      c of R: d = (v0 R[c] + v1 R[3+c]) + v2 R[6+c], x_r = R[3r+c] - (2 d) v_r; columns 0 and 1 become x, column 2 becomes -x, t stays;
+ *      the same pose LM -> P_o[1], c_o[1].  Both are kept (start_rms_px).
+ *   2. start, in rounds over the co-visibility graph.  No single observation's lower-cost candidate is trusted: every choice is made
+ *      by a cost over all observations that bear on it, and a frame keeps two candidate poses until other markers decide between
+ *      them.  reached = {0} (with FIX_MAP: every marker).  A round:
+ *      a. every frame whose count of USED observations of reached markers is not 0 and differs from the count it was last located
+ *         with is located (again): over those observations o (marker m, in order) and c = 0, 1 the hypothesis T = P_o[c] . M_m^-1; its
+ *         cost k_o[c]: the sum over those same observations o' (marker m'), in order, of cost(T . M_m', o').  The best (o, c) starts
+ *         as the first observation's c = 0; in order, (o, 0) replaces it when k_o[0] is lower, then (o, 1) when k_o[1] is lower.  The
+ *         frame's candidates: T_f[0] the best hypothesis, T_f[1] the other candidate of the same observation, P_o[1 - c] . M_m^-1,
+ *         with K_f[0], K_f[1] their costs.
+ *      b. every marker not yet reached that has a USED observation in a located frame is reached: over the first
+ *         A3_MAP_START_OBSERVATIONS such observations o (frame f, in order) and h = 0 .. 3 the hypothesis M = T_f[h / 2]^-1 . P_o[h mod 2];
+ *         its cost: the sum over all such observations o' (frame f'), in order, of the lower of K_f'[0] + cost(T_f'[0] . M, o') and
+ *         K_f'[1] + cost(T_f'[1] . M, o') (the first unless the second is lower): a frame's candidate counts with what it costs the
+ *         markers it was located from.  M_m is the first hypothesis of lowest cost.  With USE_GUESS (or FIX_MAP, which implies it)
+ *         M_m is the marker's guess instead and only the reaching is decided.
+ *      Rounds repeat (a sees the markers reached before the round, b the frames as a left them) until one changes nothing; T_f[0] of
+ *      the last location, made with every reached marker the frame sees, is the frame's start.
+ *      A marker with no USED observation is UNSEEN, one never reached UNREACHED; a USED observation of an UNREACHED marker becomes
+ *      UNREACHED.  The map takes part without them; a map in which nothing but marker 0 is reached (or marker 0 is not seen) is
+ *      NOT_CONNECTED unless FIX_MAP is set.  A frame that was located is USED, the others UNUSED.
+ *   3. joint LM over x = (w, t) of the reached markers but the first, in marker order (n = 6 per marker), and every USED frame's
+ *      pose, lambda 1e-3.  Sums over a frame's observations run in observation order, sums over a marker's observations and over
+ *      frames in frame order, over the USED ones.  V_f, g_f, cost_f: the sums of entries (0-5, 12) x (0-5, 12) of the frame's blocks;
+ *      U_m, g_m: the sums of (6-11) x (6-11) and (6-11, 12) of the marker's blocks; W_o[k][q] = entry (q, 6 + k) of the block.  An
+ *      iteration: V_f + lambda diag(V_f) by LDL^T (a bad pivot in any frame is a rejected step); y_o,k = V_f^-1 W_o[k] for every
+ *      observation of a marker other than the first, y_g = V_f^-1 g_f; the reduced system S = U + lambda diag(U) - sum_f (term (i, k),
+ *      i <= k, for a frame that sees both markers: sum over q of W_oi[i mod 6][q] y_ok,k mod 6[q] from +0.0, subtracted), rhs_i = -g_i
+ *      + sum_f (sum over q of W_oi[i mod 6][q] y_g[q]); each entry sums over the frames in frame order.  LDL^T of S, column by column:
+ *      s = S[i][j]; s -= L[i][k] L[j][k] D[k] for k = 0 .. j - 1 in order; D[j] = s on the diagonal (not positive or not finite:
+ *      rejected), L[i][j] = s / D[j] below.  Solve: forward y[i] = b[i], y[i] -= L[i][k] y[k] for k = 0 .. i - 1 ascending;
+ *      backward x[i] = y[i] / D[i], x[i] -= L[k][i] x[k] for k = n - 1 .. i + 1 DEscending.  d_m = the solution's six entries of a
+ *      marker; per frame b_q = -g_f[q] - (sum over its observations of markers other than the first, in order, k = 0 .. 5, of
+ *      W_o[k][q] d_m[k]), d_f = V_f^-1 b; R <- cay(w) R, t <- t + dt for markers and frames; acceptance, lambda x10 / /10,
+ *      A3_CALIB_REL_TOL, max_iterations and the stop at cost 0 exactly as step 3 of the rig contract.  With FIX_MAP there is no
+ *      marker-level block and every USED frame solves alone, as under A3_RIG_FIX_EXTRINSICS: a frame's record depends on nothing but
+ *      the map and its own observations, so it equals a one-frame call bit for bit.
+ *   4. rms_px = sqrt(cost / N) (N = 4 obs_used), per marker, frame and observation over their own blocks.  std_dev of a reached
+ *      marker but the first: sqrt(sigma2 diag(S0^-1)), S0 the undamped reduced system at the final state, each diagonal entry from
+ *      the solve above on a unit vector, sigma2 = cost / (2 N - n - 6 frames_used); +inf where that count is not positive or S0 (or a
+ *      V_f) is not positive definite; 0 for the first marker and under FIX_MAP.  corners: R (X, Y, 0) + t of the four object points,
+ *      c[r] = (R[3r] X + R[3r+1] Y) + t[r].  A non-finite cost at the start of step 3: NOT_FINITE.
+ * A map that is not solved reports its status and counts, its markers, observations and frames their status and counts, zeros
+ * elsewhere.  Input errors (A3_ERR_INVALID): null pointers, zero counts, unknown flags, M outside 1 .. A3_MAP_MAX_MARKERS,
+ * max_iterations above A3_CALIB_MAX_ITERATIONS, empty, overlapping or out-of-range ranges, counts above the limits, an observation
+ * whose marker or frame lies outside its map's ranges, observations out of (frame, marker) order or two of one (marker, frame),
+ * non-finite coordinates or intrinsics, focal lengths <= 0, a marker_length that is not finite and > 0, a non-finite guess under
+ * USE_GUESS / FIX_MAP.  Synchronous; not while a submitted batch is in flight.  A context that never makes the call allocates nothing.
+ * Out of scope: markers that are not square, more than one camera per map, any change to a3_pack_detections. */
+#define A3_MAP_MAX_MARKERS           128     /* per map */
+#define A3_MAP_MAX_FRAMES            4096    /* per map */
+#define A3_MAP_MAX_MAPS              1024    /* per call */
+#define A3_MAP_MAX_CALL_FRAMES       65536   /* per call, all maps */
+#define A3_MAP_MAX_CALL_OBSERVATIONS 262144  /* per call, all maps */
+#define A3_MAP_START_OBSERVATIONS    8       /* step 2b: observations of a marker that give hypotheses */
+enum { A3_MAP_USE_GUESS = 1, A3_MAP_FIX_MAP = 2 };
+enum { A3_MAP_OK = 1, A3_MAP_NOT_CONNECTED = 2, A3_MAP_NOT_FINITE = 3 };
+enum { A3_MAP_MARKER_USED = 1, A3_MAP_MARKER_UNSEEN = 2, A3_MAP_MARKER_UNREACHED = 3 };
+enum { A3_MAP_FRAME_USED = 1, A3_MAP_FRAME_UNUSED = 2 };
+enum { A3_MAP_OBS_USED = 1, A3_MAP_OBS_DEGENERATE = 2, A3_MAP_OBS_UNREACHED = 3 };
+typedef struct a3_map {                /* one problem */
+    uint32_t first_marker, n_markers;  /* contiguous, disjoint ranges of the call's markers, ... */
+    uint32_t first_frame, n_frames;    /* ... frames ... */
+    uint32_t first_obs, n_obs;         /* ... and observations */
+    uint32_t flags;                    /* A3_MAP_* */
+    uint32_t max_iterations;           /* LM iterations; 0 = A3_CALIB_DEFAULT_ITERATIONS */
+    double   a[12];                    /* the camera: fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 */
+    float    marker_length;            /* side of every marker, world units */
+    uint32_t reserved;                 /* 0 */
+} a3_map;
+typedef struct a3_map_marker {
+    double   guess_rotation[9], guess_translation[3];   /* marker -> world; read with USE_GUESS / FIX_MAP, not for the first */
+} a3_map_marker;
+typedef struct a3_map_observation {
+    uint32_t marker, frame;            /* indices in the call, inside the map's ranges */
+} a3_map_observation;
+typedef struct a3_map_result {
+    uint32_t status;                   /* A3_MAP_OK / _NOT_CONNECTED / _NOT_FINITE */
+    uint32_t markers_used, frames_used, obs_used, iterations, converged;
+    double   rms_px;
+} a3_map_result;
+typedef struct a3_map_marker_result {
+    double   rotation[9], translation[3];       /* marker -> world */
+    double   std_dev[6];                        /* of (w, t): w the Cayley increment at the solution */
+    double   rms_px;
+    double   corners[12];                       /* the four corners in world units, (x, y, z) each, a3_marker order */
+    float    rotation_f[9], translation_f[3];   /* the same in float, the a3_pose convention */
+    uint32_t status, obs_used;                  /* A3_MAP_MARKER_* */
+} a3_map_marker_result;
+typedef struct a3_map_frame {
+    uint32_t status, obs_used;                  /* A3_MAP_FRAME_* */
+    float    rms_px;
+    uint32_t reserved;
+    double   rotation[9], translation[3];       /* world -> camera */
+    float    rotation_f[9], translation_f[3];
+} a3_map_frame;
+typedef struct a3_map_observation_result {
+    uint32_t status;                            /* A3_MAP_OBS_* */
+    float    rms_px;
+    float    start_rms_px[2];                   /* step 1: sqrt(c_o[0] / 4), sqrt(c_o[1] / 4) */
+} a3_map_observation_result;
+/* results: n_maps; marker_results: n_markers; frames: one record per frame of the call (the largest first_frame + n_frames of the
+ * maps) and obs_results: n_obs records (both nullable); image_xy holds 8 floats per observation */
+int  a3_build_marker_maps(a3_ctx *ctx, const a3_map *maps, size_t n_maps, const a3_map_marker *markers, size_t n_markers,
+                          const a3_map_observation *obs, size_t n_obs, const float *image_xy, a3_map_result *results,
+                          a3_map_marker_result *marker_results, a3_map_frame *frames, a3_map_observation_result *obs_results);
+
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);
 int  a3_calculate_tau(int device, const uint64_t *codes, size_t n_codes, uint8_t *tau);

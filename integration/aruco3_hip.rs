@@ -341,6 +341,90 @@ pub struct A3RigObservationResult {
     pub reserved: u32,
 }
 
+/// a3_map: one marker map problem (not in the reference; include/aruco3_hip.h states the algorithm)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3Map {
+    pub first_marker: u32,
+    pub n_markers: u32,
+    pub first_frame: u32,
+    pub n_frames: u32,
+    pub first_obs: u32,
+    pub n_obs: u32,
+    pub flags: u32,
+    pub max_iterations: u32,
+    pub a: [f64; 12],
+    pub marker_length: f32,
+    pub reserved: u32,
+}
+
+/// a3_map_marker: a marker's guess, marker -> world
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct A3MapMarker {
+    pub guess_rotation: [f64; 9],
+    pub guess_translation: [f64; 3],
+}
+
+/// a3_map_observation: one marker seen in one frame (its four corners are 8 floats of image_xy)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3MapObservation {
+    pub marker: u32,
+    pub frame: u32,
+}
+
+/// a3_map_result: one map's status and fit
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3MapResult {
+    pub status: u32,
+    pub markers_used: u32,
+    pub frames_used: u32,
+    pub obs_used: u32,
+    pub iterations: u32,
+    pub converged: u32,
+    pub rms_px: f64,
+}
+
+/// a3_map_marker_result: marker -> world, its deviations, fit and corners in world units
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3MapMarkerResult {
+    pub rotation: [f64; 9],
+    pub translation: [f64; 3],
+    pub std_dev: [f64; 6],
+    pub rms_px: f64,
+    pub corners: [f64; 12],
+    pub rotation_f: [f32; 9],
+    pub translation_f: [f32; 3],
+    pub status: u32,
+    pub obs_used: u32,
+}
+
+/// a3_map_frame: one frame's status and pose, world -> camera
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3MapFrame {
+    pub status: u32,
+    pub obs_used: u32,
+    pub rms_px: f32,
+    pub reserved: u32,
+    pub rotation: [f64; 9],
+    pub translation: [f64; 3],
+    pub rotation_f: [f32; 9],
+    pub translation_f: [f32; 3],
+}
+
+/// a3_map_observation_result: one observation's status, fit and the fit of step 1's two planar candidates
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3MapObservationResult {
+    pub status: u32,
+    pub rms_px: f32,
+    pub start_rms_px: [f32; 2],
+}
+
 /// a3_stats: per-batch stage counters (the reference prints its rejects in debug builds, src/aruco.rs:163-164)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -469,6 +553,10 @@ extern "C" {
                              obs: *const A3RigObservation, n_obs: usize, object_xy: *const f32, image_xy: *const f32,
                              results: *mut A3RigResult, camera_results: *mut A3RigCameraResult, frames: *mut A3RigFrame,
                              obs_results: *mut A3RigObservationResult) -> c_int;
+    pub fn a3_build_marker_maps(ctx: *mut A3Ctx, maps: *const A3Map, n_maps: usize, markers: *const A3MapMarker, n_markers: usize,
+                                obs: *const A3MapObservation, n_obs: usize, image_xy: *const f32, results: *mut A3MapResult,
+                                marker_results: *mut A3MapMarkerResult, frames: *mut A3MapFrame,
+                                obs_results: *mut A3MapObservationResult) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
