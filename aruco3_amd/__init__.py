@@ -39,6 +39,10 @@ def __getattr__(name):
         from . import markermap
 
         return getattr(markermap, name)
+    if name == "rectify_frames":
+        from . import rectify
+
+        return rectify.rectify_frames
     if name == "pose":
         import importlib
 

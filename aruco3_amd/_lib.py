@@ -62,6 +62,7 @@ SYMBOLS = [
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
     "a3_calibrate_cameras", "a3_calibrate_rigs", "a3_build_marker_maps",
+    "a3_default_rectify", "a3_rectify_frames",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
 INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
@@ -226,6 +227,16 @@ class MapFrame(C.Structure):
 
 class MapObservationResult(C.Structure):
     _fields_ = [("status", C.c_uint32), ("rms_px", C.c_float), ("start_rms_px", C.c_float * 2)]
+
+
+class RectifyRec(C.Structure):
+    """a3_rectify: one rectification (an extension beyond the reference; include/aruco3_hip.h states the map and the blend)"""
+    _fields_ = [("src", Intrinsics), ("distortion", DistortionRec), ("dst", Intrinsics), ("rotation", C.c_float * 9), ("fill", C.c_uint8),
+                ("reserved", C.c_uint8 * 3)]
+
+
+class RectifyInfo(C.Structure):
+    _fields_ = [("tiles", C.c_uint32), ("path_tiles", C.c_uint32 * 4), ("reserved", C.c_uint32 * 3)]
 
 
 class Stats(C.Structure):
@@ -419,6 +430,12 @@ def load():
         L.a3_calibrate_cameras.restype = C.c_int
         L.a3_calibrate_cameras.argtypes = [vp, C.POINTER(CalibCamera), C.c_size_t, u32p, C.c_size_t, f32p, f32p, C.POINTER(CalibResult),
                                            C.POINTER(CalibView)]
+    if hasattr(L, "a3_rectify_frames"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack rectification)
+        L.a3_default_rectify.restype = None
+        L.a3_default_rectify.argtypes = [C.POINTER(RectifyRec), C.POINTER(Intrinsics), C.POINTER(DistortionRec)]
+        L.a3_rectify_frames.restype = C.c_int
+        L.a3_rectify_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(RectifyRec), vp, C.c_int,
+                                        C.c_size_t, C.c_size_t, C.POINTER(RectifyInfo)]
     L.a3_debug_discard_too_near.restype = C.c_int
     L.a3_debug_discard_too_near.argtypes = [vp, u32p, C.c_size_t, C.c_float, u32p, C.POINTER(C.c_size_t)]
     _lib = L
@@ -483,6 +500,12 @@ def default_distortion() -> DistortionRec:
     d = DistortionRec()
     load().a3_default_distortion(C.byref(d))
     return d
+
+
+def default_rectify(src: Intrinsics, d: DistortionRec = None) -> RectifyRec:
+    r = RectifyRec()
+    load().a3_default_rectify(C.byref(r), C.byref(src), C.byref(d) if d is not None else None)
+    return r
 
 
 def default_charuco_config() -> CharucoConfig:
@@ -770,6 +793,17 @@ class Context:
         check(load().a3_undistort_points(self.handle, _p(xy, C.c_float), xy.shape[0], C.byref(intrinsics), C.byref(d), _p(out, C.c_float),
                                          _p(res, C.c_float)), self.handle)
         return out, res
+
+    # ---- frame rectification ----
+    def rectify_frames(self, src_ptr: int, src_memory: int, fmt: int, src_row_stride: int, src_frame_stride: int, n_frames: int,
+                       r: "RectifyRec", dst_ptr: int, dst_memory: int, dst_row_stride: int, dst_frame_stride: int) -> "RectifyInfo":
+        """a3_rectify_frames: n_frames frames at src_ptr (r.src's size) -> rectified frames at dst_ptr (r.dst's size, same format);
+        synchronous -> the launch's a3_rectify_info"""
+        info = RectifyInfo()
+        check(load().a3_rectify_frames(self.handle, C.c_void_p(src_ptr), src_memory, fmt, src_row_stride, src_frame_stride, n_frames,
+                                       C.byref(r), C.c_void_p(dst_ptr), dst_memory, dst_row_stride, dst_frame_stride, C.byref(info)),
+              self.handle)
+        return info
 
     # ---- camera calibration ----
     def calibrate_cameras(self, cams, view_offsets, object_xy, image_xy, with_views: bool = True):

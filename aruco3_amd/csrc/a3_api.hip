@@ -94,6 +94,8 @@ hipError_t launch_rig(hipStream_t, const a3_rig*, uint32_t, const a3_rig_camera*
 size_t calib_view_bytes();
 hipError_t launch_calibrate(hipStream_t, const a3_calib_camera*, uint32_t, const uint32_t*, const float*, const float*, double*, a3_calib_result*,
                             a3_calib_view*);
+void rectify_grid(uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*);
+hipError_t launch_rectify(hipStream_t, const uint8_t*, size_t, size_t, uint32_t, int, const a3_rectify&, uint8_t*, size_t, size_t);
 hipError_t launch_synth_render(hipStream_t, const a3_synth_frame*, uint32_t, const a3_synth_marker*, uint32_t, uint32_t, int, float, float, int,
                                uint8_t*, size_t, size_t);
 hipError_t launch_spin(hipStream_t, int, int, int, uint32_t*);
@@ -318,6 +320,8 @@ struct a3_ctx {
     // a3_build_marker_maps: [maps | markers | observations | image corners | matrix offsets], [tables | per-observation | per-frame |
     // per-marker scratch], the reduced systems (two n x n per map), [results | marker results | frames | observation results]
     DevBuf map_in, map_scratch, map_big, map_out;
+    // a3_rectify_frames: host-side source frames and host-side output staged on the device
+    DevBuf rect_in, rect_out;
     uint32_t last_charuco_total = 0;   // sizes the speculative record read-back of the next batch
     void* pinned = nullptr;
     size_t pinned_cap = 0;
@@ -1328,7 +1332,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
                       &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->calib_in,
                       &ctx->calib_scratch, &ctx->calib_out, &ctx->rig_in, &ctx->rig_scratch, &ctx->rig_out,
-                      &ctx->map_in, &ctx->map_scratch, &ctx->map_big, &ctx->map_out};
+                      &ctx->map_in, &ctx->map_scratch, &ctx->map_big, &ctx->map_out, &ctx->rect_in, &ctx->rect_out};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -2702,6 +2706,91 @@ int a3_build_marker_maps(a3_ctx* ctx, const a3_map* maps, size_t n_maps, const a
     if (obs_results)
         A3_HIP(hipMemcpyAsync(obs_results, dout + b_res + b_mres + b_frames, n_obs * sizeof(a3_map_observation_result), hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+// ---- frame rectification (an extension beyond the reference; contract in include/aruco3_hip.h) ----
+void a3_default_rectify(a3_rectify* r, const a3_intrinsics* src, const a3_distortion* d) {
+    if (!r) return;
+    *r = a3_rectify{};
+    if (src) r->src = r->dst = *src;
+    if (d) r->distortion = *d;
+    r->rotation[0] = r->rotation[4] = r->rotation[8] = 1.0f;
+}
+
+static int check_rectify_image(a3_ctx* ctx, const a3_intrinsics& k, size_t bpp, size_t row_stride, size_t frame_stride) {
+    if (k.image_width == 0 || k.image_height == 0 || k.image_width > 65535 || k.image_height > 65535 ||
+        (uint64_t)k.image_width * k.image_height >= (1ull << 30))
+        return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: an image size of 0, above 65535 or of 2^30 pixels and more");
+    if (row_stride < (size_t)k.image_width * bpp) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: row stride smaller than a row");
+    if (frame_stride / k.image_height < row_stride) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: frame stride smaller than a frame");
+    const float v[4] = {k.focal_x, k.focal_y, k.principal_x, k.principal_y};
+    for (float x : v)
+        if (!std::isfinite(x)) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: an intrinsic is not finite");
+    if (!(k.focal_x > 0.0f) || !(k.focal_y > 0.0f)) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: focal lengths must be > 0");
+    return A3_OK;
+}
+
+int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, size_t src_row_stride, size_t src_frame_stride, uint32_t n_frames,
+                      const a3_rectify* r, void* dst, int dst_memory, size_t dst_row_stride, size_t dst_frame_stride, a3_rectify_info* info) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!src || !r || !dst) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: null argument");
+    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: a submitted batch has not been collected");
+    if (n_frames == 0 || n_frames > 65535) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: n_frames must be in 1..65535");
+    if (fmt != A3_FMT_RGB8 && fmt != A3_FMT_RGBA8 && fmt != A3_FMT_L8 && fmt != A3_FMT_BGRA8)
+        return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: unknown pixel format");
+    if ((src_memory != A3_MEM_HOST && src_memory != A3_MEM_DEVICE) || (dst_memory != A3_MEM_HOST && dst_memory != A3_MEM_DEVICE))
+        return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: memory must be A3_MEM_HOST or A3_MEM_DEVICE");
+    const size_t bpp = fmt == A3_FMT_RGB8 ? 3 : (fmt == A3_FMT_L8 ? 1 : 4);
+    if (int rc = check_rectify_image(ctx, r->src, bpp, src_row_stride, src_frame_stride)) return rc;
+    if (int rc = check_rectify_image(ctx, r->dst, bpp, dst_row_stride, dst_frame_stride)) return rc;
+    if (r->reserved[0] || r->reserved[1] || r->reserved[2]) return fail(ctx, A3_ERR_INVALID, "a3_rectify.reserved must be 0");
+    const a3_distortion& d = r->distortion;
+    if (d.model != A3_DIST_NONE && d.model != A3_DIST_RATIONAL) return fail(ctx, A3_ERR_INVALID, "a3_rectify.distortion.model: unknown model");
+    if (d.model == A3_DIST_RATIONAL) {
+        const float k[8] = {d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6};
+        for (float v : k)
+            if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_rectify.distortion: a coefficient is not finite");
+    }
+    for (float v : r->rotation)
+        if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_rectify.rotation: an entry is not finite");
+
+    const uint32_t sw = r->src.image_width, sh = r->src.image_height, dw = r->dst.image_width, dh = r->dst.image_height;
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    const uint8_t* d_src = reinterpret_cast<const uint8_t*>(src);
+    if (src_memory == A3_MEM_HOST) {   // the caller's span, padding included, in one copy
+        const size_t bytes = src_frame_stride * (n_frames - 1) + src_row_stride * (sh - 1) + (size_t)sw * bpp;
+        A3_HIP(ctx->rect_in.ensure(bytes));
+        A3_HIP(hipMemcpyAsync(ctx->rect_in.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        d_src = ctx->rect_in.as<uint8_t>();
+    }
+    uint8_t* d_dst = reinterpret_cast<uint8_t*>(dst);
+    size_t d_row = dst_row_stride, d_frame = dst_frame_stride;
+    if (dst_memory == A3_MEM_HOST) {   // packed rows on the device; the copy back writes the rows' pixels only
+        d_row = (size_t)dw * bpp;
+        d_frame = d_row * dh;
+        A3_HIP(ctx->rect_out.ensure(d_frame * n_frames));
+        d_dst = ctx->rect_out.as<uint8_t>();
+    }
+    A3_HIP(launch_rectify(ctx->stream, d_src, src_row_stride, src_frame_stride, n_frames, (int)bpp, *r, d_dst, d_row, d_frame));
+    if (dst_memory == A3_MEM_HOST) {
+        if (dst_frame_stride == dst_row_stride * dh) {
+            A3_HIP(hipMemcpy2DAsync(dst, dst_row_stride, d_dst, d_row, d_row, (size_t)dh * n_frames, hipMemcpyDeviceToHost, ctx->stream));
+        } else {
+            for (uint32_t f = 0; f < n_frames; f++)
+                A3_HIP(hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(dst) + f * dst_frame_stride, dst_row_stride, d_dst + f * d_frame, d_row, d_row, dh,
+                                        hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    if (info) {
+        *info = a3_rectify_info{};
+        uint32_t tx, ty, tz;
+        rectify_grid(dw, dh, n_frames, &tx, &ty, &tz);
+        info->tiles = tx * ty;
+        info->path_tiles[0] = info->tiles;   // one launch path: the direct one
+    }
     return A3_OK;
 }
 

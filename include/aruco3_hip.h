@@ -800,6 +800,57 @@ int  a3_build_marker_maps(a3_ctx *ctx, const a3_map *maps, size_t n_maps, const 
                           const a3_map_observation *obs, size_t n_obs, const float *image_xy, a3_map_result *results,
                           a3_map_marker_result *marker_results, a3_map_frame *frames, a3_map_observation_result *obs_results);
 
+/* Frame rectification.  NOT in the reference: an opt-in extension (OpenCV's initUndistortRectifyMap + remap with bilinear
+ * interpolation, the map never written to memory), stand-alone: no batch, setting or launch of the detection path changes.  A call
+ * maps n_frames frames seen by the camera (`src` intrinsics, `distortion`) to the frames an ideal pinhole camera `dst`, rotated by
+ * `rotation` against the real one, would have seen; the output is device-resident when asked for and feeds a3_detect_batch as it is.
+ * Fixed to the bit as follows -- tests/rectify_oracle.c a3o_rectify restates it.  Output pixel (j, i) is column j, row i of the dst
+ * size, pixel centres at integer coordinates, the same for every frame of the call.  Arithmetic is f32, every expression evaluated as C
+ * parses it, no fused multiply-add, division correctly rounded.  d* are dst's focal lengths and principal point, s* src's, (sw, sh)
+ * src's image size, R = rotation, k* / p* the distortion's coefficients (all 0 with model A3_DIST_NONE):
+ *     a = ((float)j - dcx) / dfx;   b = ((float)i - dcy) / dfy
+ *     X = (R[0]*a + R[3]*b) + R[6];  Y = (R[1]*a + R[4]*b) + R[7];  Wz = (R[2]*a + R[5]*b) + R[8]     (R^T applied to (a, b, 1))
+ *     x = X / Wz;  y = Y / Wz;  r2 = x*x + y*y
+ *     radial = (1 + ((k3*r2 + k2)*r2 + k1)*r2) / (1 + ((k6*r2 + k5)*r2 + k4)*r2)
+ *     xd = x*radial + (2*p1*x*y + p2*(r2 + 2*x*x));   yd = y*radial + (p1*(r2 + 2*y*y) + 2*p2*x*y)
+ *     u = xd*sfx + scx;   v = yd*sfy + scy
+ *     inside = Wz > 0 and u, v finite and 0 <= u <= sw - 1 and 0 <= v <= sh - 1
+ *     not inside: every byte of the pixel = fill
+ *     inside: x0 = floorf(u), y0 = floorf(v), ax = u - x0, ay = v - y0, x1 = min(x0 + 1, sw - 1), y1 = min(y0 + 1, sh - 1); per byte c
+ *         of the pixel  val = (1-ay)*((1-ax)*I[y0][x0][c] + ax*I[y0][x1][c]) + ay*((1-ax)*I[y1][x0][c] + ax*I[y1][x1][c])
+ *         out = (uint8_t) min(floorf(val + 0.5f), 255.0f)
+ * The model is the forward model of the a3_set_distortion contract's check step, the blend that of the corner refinement.  The
+ * output format equals the input format (1, 3 or 4 bytes per pixel); every byte is interpolated alike, so RGBA and BGRA are the same
+ * work.  Bytes of dst between the end of a row's pixels and the next row are not written.  src and dst must not overlap.  Outside the
+ * field where the rational model is monotone a ray can fold back into the image, as with OpenCV: documented, not guarded.
+ * info (nullable): tiles = output tiles per frame, path_tiles[p] = how many of them launch path p of the kernel took (path 0 the
+ * general one, unused entries 0); the choice depends on the parameters only, never on pixel values.
+ * Input errors (A3_ERR_INVALID, decided on the host before anything is enqueued): null pointers, n_frames 0 or above 65535, a size
+ * of 0 or above 65535 or width x height >= 2^30 for either image, a row stride below width x bytes per pixel or a frame stride below
+ * height x row stride, an unknown format, memory kind or model, non-zero reserved, a non-finite coefficient, rotation entry or
+ * intrinsic, a focal length <= 0.  Synchronous; not while a submitted batch is in flight.  Host-side src or dst is staged through
+ * device buffers with plain copies.
+ * Out of scope: rectifying rotations from a rig (stereoRectify), the choice of an optimal new camera matrix, a submit / collect form. */
+typedef struct a3_rectify {
+    a3_intrinsics src;         /* the camera; image_width / image_height = size of the source frames */
+    a3_distortion distortion;  /* model A3_DIST_RATIONAL, or A3_DIST_NONE (coefficients taken as 0); iterations, max_residual_px ignored */
+    a3_intrinsics dst;         /* the rectified view; image_width / image_height = size of the output frames */
+    float    rotation[9];      /* R row-major, camera -> rectified view (cv::initUndistortRectifyMap's R); identity = plain undistortion.
+                                  Its TRANSPOSE is used as its inverse; orthonormality is the caller's business */
+    uint8_t  fill;             /* every byte of an output pixel that sees nothing */
+    uint8_t  reserved[3];      /* 0 */
+} a3_rectify;
+typedef struct a3_rectify_info {
+    uint32_t tiles;
+    uint32_t path_tiles[4];
+    uint32_t reserved[3];
+} a3_rectify_info;
+/* dst = src, R = the identity, fill 0; d NULL: model A3_DIST_NONE */
+void a3_default_rectify(a3_rectify *r, const a3_intrinsics *src, const a3_distortion *d);
+int  a3_rectify_frames(a3_ctx *ctx, const void *src, int src_memory, int fmt, size_t src_row_stride, size_t src_frame_stride,
+                       uint32_t n_frames, const a3_rectify *r, void *dst, int dst_memory, size_t dst_row_stride,
+                       size_t dst_frame_stride, a3_rectify_info *info);
+
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);
 int  a3_calculate_tau(int device, const uint64_t *codes, size_t n_codes, uint8_t *tau);

@@ -425,6 +425,27 @@ pub struct A3MapObservationResult {
     pub start_rms_px: [f32; 2],
 }
 
+/// a3_rectify: one frame rectification (not in the reference; include/aruco3_hip.h states the map and the blend)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct A3Rectify {
+    pub src: A3Intrinsics,
+    pub distortion: A3Distortion,
+    pub dst: A3Intrinsics,
+    pub rotation: [f32; 9],
+    pub fill: u8,
+    pub reserved: [u8; 3],
+}
+
+/// a3_rectify_info: output tiles per frame and how many of them each launch path of the kernel took
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3RectifyInfo {
+    pub tiles: u32,
+    pub path_tiles: [u32; 4],
+    pub reserved: [u32; 3],
+}
+
 /// a3_stats: per-batch stage counters (the reference prints its rejects in debug builds, src/aruco.rs:163-164)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -557,6 +578,10 @@ extern "C" {
                                 obs: *const A3MapObservation, n_obs: usize, image_xy: *const f32, results: *mut A3MapResult,
                                 marker_results: *mut A3MapMarkerResult, frames: *mut A3MapFrame,
                                 obs_results: *mut A3MapObservationResult) -> c_int;
+    pub fn a3_default_rectify(r: *mut A3Rectify, src: *const A3Intrinsics, d: *const A3Distortion);
+    pub fn a3_rectify_frames(ctx: *mut A3Ctx, src: *const c_void, src_memory: c_int, fmt: c_int, src_row_stride: usize, src_frame_stride: usize,
+                             n_frames: u32, r: *const A3Rectify, dst: *mut c_void, dst_memory: c_int, dst_row_stride: usize,
+                             dst_frame_stride: usize, info: *mut A3RectifyInfo) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
