@@ -27,6 +27,7 @@ REFINE_NONE, REFINE_SUBPIX = 0, 1
 BOARD_NONE, BOARD_OK = 0, 1
 BOARD_MAX_MARKERS = 1024
 DIST_NONE, DIST_RATIONAL = 0, 1
+DIST_FISHEYE = 3   # (2 is unassigned)
 CHARUCO_MAX_CORNERS = 2048
 CHARUCO_NO_ADJ = 0xFFFFFFFF
 # a3_calibrate_cameras (include/aruco3_hip.h A3_CALIB_*)

@@ -134,6 +134,8 @@ def calibrate_cameras(problems: Sequence[dict]) -> List[Calibration]:
                          guess)
         c.max_iterations = int(pr.get("max_iterations") or 0)
         if guess is not None:
+            if guess.distortion is not None:
+                guess.distortion.rational_coefficients("a calibration guess")   # (a fisheye lens is refused)
             c.guess = guess._c()
             c.guess_distortion = (guess.distortion or Distortion())._c()
     offsets = np.concatenate([[0], np.cumsum([len(o) for o in obj])]).astype(np.uint32)

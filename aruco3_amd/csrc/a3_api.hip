@@ -2374,13 +2374,23 @@ void a3_default_distortion(a3_distortion* d) {
     d->max_residual_px = 0.1f;
 }
 
-static int check_distortion(a3_ctx* ctx, const a3_distortion& d) {
-    if (d.model != A3_DIST_NONE && d.model != A3_DIST_RATIONAL) return fail(ctx, A3_ERR_INVALID, "a3_distortion.model: unknown model");
-    if (d.model == A3_DIST_NONE) return A3_OK;
-    if (d.iterations < 1 || d.iterations > 100) return fail(ctx, A3_ERR_INVALID, "a3_distortion.iterations must be in 1..100");
+// the coefficients of a model that has some: all finite, and with the fisheye model (which reads k1 k2 k3 k4) the other four exactly 0
+static int check_distortion_coefficients(a3_ctx* ctx, const a3_distortion& d, const char* not_finite, const char* not_fisheye) {
     const float k[8] = {d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6};
     for (float v : k)
-        if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_distortion: a coefficient is not finite");
+        if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, not_finite);
+    if (d.model == A3_DIST_FISHEYE && (d.p1 != 0.0f || d.p2 != 0.0f || d.k5 != 0.0f || d.k6 != 0.0f)) return fail(ctx, A3_ERR_INVALID, not_fisheye);
+    return A3_OK;
+}
+
+static int check_distortion(a3_ctx* ctx, const a3_distortion& d) {
+    if (d.model != A3_DIST_NONE && d.model != A3_DIST_RATIONAL && d.model != A3_DIST_FISHEYE)
+        return fail(ctx, A3_ERR_INVALID, "a3_distortion.model: unknown model");
+    if (d.model == A3_DIST_NONE) return A3_OK;
+    if (d.iterations < 1 || d.iterations > 100) return fail(ctx, A3_ERR_INVALID, "a3_distortion.iterations must be in 1..100");
+    if (int rc = check_distortion_coefficients(ctx, d, "a3_distortion: a coefficient is not finite",
+                                               "a3_distortion: model A3_DIST_FISHEYE reads k1 k2 k3 k4; p1 p2 k5 k6 must be 0"))
+        return rc;
     if (!(d.max_residual_px >= 0.0f) || !std::isfinite(d.max_residual_px))
         return fail(ctx, A3_ERR_INVALID, "a3_distortion.max_residual_px must be finite and >= 0");
     return A3_OK;
@@ -2415,7 +2425,7 @@ int a3_undistort_points(a3_ctx* ctx, const float* xy, size_t n, const a3_intrins
     if (!ctx) return A3_ERR_INVALID;
     if (!intr || !d || (n && (!xy || !out_xy))) return fail(ctx, A3_ERR_INVALID, "a3_undistort_points: null argument");
     if (int rc = check_distortion(ctx, *d)) return rc;
-    if (d->model != A3_DIST_RATIONAL) return fail(ctx, A3_ERR_INVALID, "a3_undistort_points: no distortion model (A3_DIST_NONE)");
+    if (d->model == A3_DIST_NONE) return fail(ctx, A3_ERR_INVALID, "a3_undistort_points: no distortion model (A3_DIST_NONE)");
     if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_undistort_points: a submitted batch has not been collected");
     if (n > (1u << 30)) return fail(ctx, A3_ERR_INVALID, "a3_undistort_points: more than 2^30 points in one call");
     if (n == 0) return A3_OK;
@@ -2746,11 +2756,12 @@ int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, siz
     if (int rc = check_rectify_image(ctx, r->dst, bpp, dst_row_stride, dst_frame_stride)) return rc;
     if (r->reserved[0] || r->reserved[1] || r->reserved[2]) return fail(ctx, A3_ERR_INVALID, "a3_rectify.reserved must be 0");
     const a3_distortion& d = r->distortion;
-    if (d.model != A3_DIST_NONE && d.model != A3_DIST_RATIONAL) return fail(ctx, A3_ERR_INVALID, "a3_rectify.distortion.model: unknown model");
-    if (d.model == A3_DIST_RATIONAL) {
-        const float k[8] = {d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6};
-        for (float v : k)
-            if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_rectify.distortion: a coefficient is not finite");
+    if (d.model != A3_DIST_NONE && d.model != A3_DIST_RATIONAL && d.model != A3_DIST_FISHEYE)
+        return fail(ctx, A3_ERR_INVALID, "a3_rectify.distortion.model: unknown model");
+    if (d.model != A3_DIST_NONE) {
+        if (int rc = check_distortion_coefficients(ctx, d, "a3_rectify.distortion: a coefficient is not finite",
+                                                   "a3_rectify.distortion: model A3_DIST_FISHEYE reads k1 k2 k3 k4; p1 p2 k5 k6 must be 0"))
+            return rc;
     }
     for (float v : r->rotation)
         if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_rectify.rotation: an entry is not finite");
@@ -2789,7 +2800,7 @@ int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, siz
         uint32_t tx, ty, tz;
         rectify_grid(dw, dh, n_frames, &tx, &ty, &tz);
         info->tiles = tx * ty;
-        info->path_tiles[0] = info->tiles;   // one launch path: the direct one
+        info->path_tiles[d.model == A3_DIST_FISHEYE ? 1 : 0] = info->tiles;   // path 0: the rational map (and no lens), path 1: the fisheye map
     }
     return A3_OK;
 }

@@ -380,7 +380,7 @@ hipError_t launch_charuco_corners(hipStream_t st, PixelSrc src, uint32_t W, uint
     if (und && intr && dist) {
         c.und = und;
         c.up = UndistortParams{intr->focal_x, intr->focal_y, intr->principal_x, intr->principal_y, dist->k1, dist->k2, dist->p1, dist->p2,
-                               dist->k3, dist->k4, dist->k5, dist->k6, dist->max_residual_px, dist->iterations};
+                               dist->k3, dist->k4, dist->k5, dist->k6, dist->max_residual_px, dist->iterations, dist->model};
     }
     const RefineParams& p = *reinterpret_cast<const RefineParams*>(params);
     hipLaunchKernelGGL(k_charuco_interp, dim3(n_frames), dim3(256), 0, st, a, c, p);

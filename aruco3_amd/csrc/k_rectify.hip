@@ -1,6 +1,7 @@
 // k_rectify.hip -- frame rectification (a3_rectify_frames): whole frames seen through a lens -> the frames of an ideal pinhole view.
 // Not part of the reference: an extension stated in include/aruco3_hip.h, restated on the CPU by tests/rectify_oracle.c (a3o_rectify),
-// which this kernel matches byte for byte.
+// which this kernel matches byte for byte; with the fisheye lens model (k_rectify<BPP, A3_DIST_FISHEYE>) tests/fisheye_oracle.c
+// (a3o_fisheye_rectify).  The two models differ in rectify_map's forward model only.
 //
 // The map output pixel -> source position is the same for every frame of a call and is never written to memory: a lane computes it
 // once for the kRun consecutive output pixels of one row that it owns, keeps per pixel the byte offset of the top-left tap, the two
@@ -17,6 +18,7 @@
 #include <cstring>
 
 #include "a3_common.h"
+#include "a3_undistort.h"
 
 namespace a3 {
 
@@ -35,13 +37,22 @@ struct RectifyParams {
 
 constexpr uint32_t kTapSecond = 1u, kTapNextRow = 2u, kTapInside = 4u;
 
-// the contract's map for output pixel (j, i) -> whether it sees the source, and where
+// the contract's map for output pixel (j, i) -> whether it sees the source, and where.  MODEL: A3_DIST_RATIONAL (which serves
+// A3_DIST_NONE with every coefficient 0) or A3_DIST_FISHEYE; the two differ in the forward model only.
+template <int MODEL>
 __device__ inline bool rectify_map(const RectifyParams& p, uint32_t j, uint32_t i, float* u_out, float* v_out) {
     const float a = ((float)j - p.dcx) / p.dfx, b = ((float)i - p.dcy) / p.dfy;
     const float X = (p.R[0]*a + p.R[3]*b) + p.R[6], Y = (p.R[1]*a + p.R[4]*b) + p.R[7], Wz = (p.R[2]*a + p.R[5]*b) + p.R[8];
-    const float x = X / Wz, y = Y / Wz, r2 = x*x + y*y;
-    const float radial = (1.0f + ((p.k3*r2 + p.k2)*r2 + p.k1)*r2) / (1.0f + ((p.k6*r2 + p.k5)*r2 + p.k4)*r2);
-    const float xd = x*radial + (2.0f*p.p1*x*y + p.p2*(r2 + 2.0f*x*x)), yd = y*radial + (p.p1*(r2 + 2.0f*y*y) + 2.0f*p.p2*x*y);
+    const float x = X / Wz, y = Y / Wz;
+    float xd, yd;
+    if constexpr (MODEL == A3_DIST_FISHEYE) {
+        fisheye_forward(p.k1, p.k2, p.k3, p.k4, x, y, &xd, &yd);
+    } else {
+        const float r2 = x*x + y*y;
+        const float radial = (1.0f + ((p.k3*r2 + p.k2)*r2 + p.k1)*r2) / (1.0f + ((p.k6*r2 + p.k5)*r2 + p.k4)*r2);
+        xd = x*radial + (2.0f*p.p1*x*y + p.p2*(r2 + 2.0f*x*x));
+        yd = y*radial + (p.p1*(r2 + 2.0f*y*y) + 2.0f*p.p2*x*y);
+    }
     const float u = xd*p.sfx + p.scx, v = yd*p.sfy + p.scy;
     *u_out = u;
     *v_out = v;
@@ -78,7 +89,7 @@ template <int BPP> __device__ inline uint64_t load_single(const uint8_t* q) {
     return t | (t << (8 * BPP));
 }
 
-template <int BPP>
+template <int BPP, int MODEL>
 __global__ __launch_bounds__(256) void k_rectify(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const RectifyParams p) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t i = blockIdx.y * kTileH + wave, j0 = blockIdx.x * kTileW + lane * kRun;
@@ -94,7 +105,7 @@ __global__ __launch_bounds__(256) void k_rectify(const uint8_t* __restrict__ src
     for (int q = 0; q < kRun; q++) {
         off[q] = 0; ax[q] = 0.0f; ay[q] = 0.0f; flags[q] = 0;
         float u, v;
-        if ((uint32_t)q < run && rectify_map(p, j0 + q, i, &u, &v)) {
+        if ((uint32_t)q < run && rectify_map<MODEL>(p, j0 + q, i, &u, &v)) {
             const float fx0 = floorf(u), fy0 = floorf(v);
             const uint32_t x0 = (uint32_t)fx0, y0 = (uint32_t)fy0;   // (0 <= u <= sw - 1, 0 <= v <= sh - 1)
             const uint32_t xb = single ? 0u : min(x0, p.sw - 2u);
@@ -161,7 +172,7 @@ void rectify_grid(uint32_t dw, uint32_t dh, uint32_t n_frames, uint32_t* tiles_x
 // src / dst: device memory; bpp 1, 3 or 4.  The caller has checked every size and stride (a3_rectify_frames).
 hipError_t launch_rectify(hipStream_t st, const uint8_t* src, size_t src_row, size_t src_frame, uint32_t n_frames, int bpp, const a3_rectify& r,
                           uint8_t* dst, size_t dst_row, size_t dst_frame) {
-    const bool lens = r.distortion.model == A3_DIST_RATIONAL;
+    const bool fisheye = r.distortion.model == A3_DIST_FISHEYE, lens = fisheye || r.distortion.model == A3_DIST_RATIONAL;
     const a3_distortion& k = r.distortion;
     RectifyParams p{};
     p.dfx = r.dst.focal_x; p.dfy = r.dst.focal_y; p.dcx = r.dst.principal_x; p.dcy = r.dst.principal_y;
@@ -175,9 +186,15 @@ hipError_t launch_rectify(hipStream_t st, const uint8_t* src, size_t src_row, si
     uint32_t tx, ty, tz;
     rectify_grid(p.dw, p.dh, n_frames, &tx, &ty, &tz);
     const dim3 grid(tx, ty, tz), block(WAVE * kTileH);
-    if (bpp == 1) hipLaunchKernelGGL(k_rectify<1>, grid, block, 0, st, src, dst, p);
-    else if (bpp == 3) hipLaunchKernelGGL(k_rectify<3>, grid, block, 0, st, src, dst, p);
-    else hipLaunchKernelGGL(k_rectify<4>, grid, block, 0, st, src, dst, p);
+    if (fisheye) {   // (p1 p2 k5 k6 are 0 there: a3_rectify_frames checked)
+        if (bpp == 1) hipLaunchKernelGGL((k_rectify<1, A3_DIST_FISHEYE>), grid, block, 0, st, src, dst, p);
+        else if (bpp == 3) hipLaunchKernelGGL((k_rectify<3, A3_DIST_FISHEYE>), grid, block, 0, st, src, dst, p);
+        else hipLaunchKernelGGL((k_rectify<4, A3_DIST_FISHEYE>), grid, block, 0, st, src, dst, p);
+    } else {
+        if (bpp == 1) hipLaunchKernelGGL((k_rectify<1, A3_DIST_RATIONAL>), grid, block, 0, st, src, dst, p);
+        else if (bpp == 3) hipLaunchKernelGGL((k_rectify<3, A3_DIST_RATIONAL>), grid, block, 0, st, src, dst, p);
+        else hipLaunchKernelGGL((k_rectify<4, A3_DIST_RATIONAL>), grid, block, 0, st, src, dst, p);
+    }
     return hipGetLastError();
 }
 

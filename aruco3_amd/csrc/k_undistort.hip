@@ -1,6 +1,6 @@
 // k_undistort.hip -- lens undistortion of marker corners (a3_set_distortion / a3_undistort_points).  Not part of the reference, whose
 // poses assume an ideal pinhole camera: an extension stated in include/aruco3_hip.h, restated on the CPU by tests/lens_oracle.c
-// (a3o_undistort), which this kernel matches bit for bit.
+// (a3o_undistort) and, for the fisheye model, by tests/fisheye_oracle.c (a3o_fisheye_undistort), which this kernel matches bit for bit.
 //
 // One lane per corner.  A batch's corners are those of the device-resident marker list (min(marker_cap, *n_dev) markers), read as
 // the refined floats (8 per marker) when refinement ran, else as the integer a3_marker corners; the stand-alone call passes n points.
@@ -37,7 +37,7 @@ hipError_t launch_undistort_corners(hipStream_t st, const a3_marker* markers, co
     const uint64_t corners = n_dev ? (uint64_t)n * 4u : n;
     if (corners == 0) return hipSuccess;
     const UndistortParams p{in.focal_x, in.focal_y, in.principal_x, in.principal_y, d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6,
-                            d.max_residual_px, d.iterations};
+                            d.max_residual_px, d.iterations, d.model};
     // (grid-stride: a batch's marker_cap is an upper bound -- the blocks past the real count find nothing and leave at once)
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((corners + 255) / 256, 1024);
     hipLaunchKernelGGL(k_undistort_corners, dim3(blocks), dim3(256), 0, st, markers, pts, n_dev, n, p, out_xy, out_res);

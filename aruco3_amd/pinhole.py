@@ -1,8 +1,8 @@
 """Host-side mirror of `CameraIntrinsics` (src/pinhole.rs:11-60): a plain parameter record.
 The one operation the pose path uses, `unproject` (src/pinhole.rs:88-93), runs inside the pose kernel.
 
-`Distortion` is an extension (the reference assumes an ideal pinhole camera): OpenCV's rational lens model, whose inverse runs on the
-device (include/aruco3_hip.h, a3_set_distortion) before the poses are solved."""
+`Distortion` is an extension (the reference assumes an ideal pinhole camera): OpenCV's rational lens model or its fisheye one
+(cv::fisheye, Kannala-Brandt), whose inverse runs on the device (include/aruco3_hip.h, a3_set_distortion) before the poses are solved."""
 import math
 from dataclasses import dataclass
 from typing import Optional
@@ -14,7 +14,9 @@ import numpy as np
 class Distortion:
     """OpenCV's 5- / 8-coefficient lens model (a3_distortion, model A3_DIST_RATIONAL): the coefficients of a calibration as
     cv2.calibrateCamera returns them (k1 k2 p1 p2 k3 [k4 k5 k6]), the iteration count of the undistortion and the largest
-    reprojection residual, in pixels, at which an undistorted corner is accepted."""
+    reprojection residual, in pixels, at which an undistorted corner is accepted.
+    With model "fisheye" (a3_distortion model A3_DIST_FISHEYE) k1 k2 k3 k4 are cv::fisheye's D -- theta_d = theta (1 + k1 theta^2 +
+    k2 theta^4 + k3 theta^6 + k4 theta^8) -- and p1 p2 k5 k6 must be 0: build it with `Distortion.fisheye` / `from_opencv_fisheye`."""
     k1: float = 0.0
     k2: float = 0.0
     p1: float = 0.0
@@ -25,6 +27,36 @@ class Distortion:
     k6: float = 0.0
     iterations: int = 20
     max_residual_px: float = 0.1
+    model: str = "rational"
+
+    def __post_init__(self):
+        if self.model not in ("rational", "fisheye"):
+            raise ValueError(f"Distortion.model: 'rational' or 'fisheye', not {self.model!r}")
+        self._check_fisheye()
+
+    def _check_fisheye(self):
+        if self.model == "fisheye" and any(float(v) != 0.0 for v in (self.p1, self.p2, self.k5, self.k6)):
+            raise ValueError("a fisheye Distortion reads k1 k2 k3 k4 (cv::fisheye's D); p1, p2, k5 and k6 must be 0")
+
+    @classmethod
+    def fisheye(cls, k1=0.0, k2=0.0, k3=0.0, k4=0.0, **kw) -> "Distortion":
+        """the fisheye model from cv::fisheye's four coefficients"""
+        return cls(k1=float(k1), k2=float(k2), k3=float(k3), k4=float(k4), model="fisheye", **kw)
+
+    @classmethod
+    def from_opencv_fisheye(cls, D, **kw) -> "Distortion":
+        """from cv::fisheye's D (exactly 4 values: k1 k2 k3 k4)"""
+        c = [float(v) for v in np.asarray(D, dtype=np.float64).reshape(-1)]
+        if len(c) != 4:
+            raise ValueError("fisheye distortion coefficients: exactly 4 values (k1 k2 k3 k4)")
+        return cls.fisheye(*c, **kw)
+
+    def rational_coefficients(self, what: str):
+        """k1 k2 p1 p2 k3 k4 k5 k6 for a consumer that knows the rational model only (`what` names it in the error)"""
+        if self.model != "rational":
+            raise ValueError(f"{what} takes rational lens coefficients only, not a fisheye Distortion: rectify the frames first "
+                             "(rectify_frames), then use the rectified view's plain intrinsics")
+        return [self.k1, self.k2, self.p1, self.p2, self.k3, self.k4, self.k5, self.k6]
 
     @classmethod
     def from_opencv(cls, coeffs, **kw) -> "Distortion":
@@ -38,6 +70,14 @@ class Distortion:
         """the forward model on the host, in the normalised plane: ideal (x, y) (..., 2) -> distorted (xd, yd), float64"""
         p = np.asarray(points, dtype=np.float64)
         x, y = p[..., 0], p[..., 1]
+        if self.model == "fisheye":
+            self._check_fisheye()
+            r = np.sqrt(x * x + y * y)
+            th = np.arctan(r)
+            t2 = th * th
+            thd = th * (1 + (((self.k4 * t2 + self.k3) * t2 + self.k2) * t2 + self.k1) * t2)
+            s = np.divide(thd, r, out=np.ones_like(r), where=r > 0)
+            return np.stack([x * s, y * s], axis=-1)
         r2 = x * x + y * y
         radial = (1 + ((self.k3 * r2 + self.k2) * r2 + self.k1) * r2) / (1 + ((self.k6 * r2 + self.k5) * r2 + self.k4) * r2)
         xd = x * radial + (2 * self.p1 * x * y + self.p2 * (r2 + 2 * x * x))
@@ -47,8 +87,10 @@ class Distortion:
     def _c(self):
         from . import _lib
 
-        return _lib.DistortionRec(_lib.DIST_RATIONAL, int(self.iterations), self.k1, self.k2, self.p1, self.p2, self.k3, self.k4, self.k5,
-                                  self.k6, self.max_residual_px)
+        self._check_fisheye()
+        model = _lib.DIST_FISHEYE if self.model == "fisheye" else _lib.DIST_RATIONAL
+        return _lib.DistortionRec(model, int(self.iterations), self.k1, self.k2, self.p1, self.p2, self.k3, self.k4, self.k5, self.k6,
+                                  self.max_residual_px)
 
 
 @dataclass

@@ -84,7 +84,7 @@ def camera_params(camera) -> np.ndarray:
         return np.asarray(camera.params, np.float64).reshape(12)
     if hasattr(camera, "focal_x"):
         d = camera.distortion
-        lens = [d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6] if d is not None else [0.0] * 8
+        lens = d.rational_coefficients("a rig or map solve") if d is not None else [0.0] * 8
         return np.array([camera.focal_x, camera.focal_y, camera.principal_x, camera.principal_y] + lens, np.float64)
     return np.asarray(camera, np.float64).reshape(12)
 

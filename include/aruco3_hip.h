@@ -366,7 +366,8 @@ int  a3_estimate_board_pose(a3_ctx *ctx, const uint32_t *ids, const float *corne
 
 /* Lens distortion.  NOT in the reference (every pose it returns assumes an ideal pinhole camera, src/pose.rs:58): an opt-in extension,
  * off by default; with it off no launch, buffer, copy or result of a batch changes.  The model is OpenCV's rational one (k1 k2 p1 p2 k3
- * k4 k5 k6; a 5-coefficient calibration has k4 = k5 = k6 = 0), in the normalised plane of a3_intrinsics.  With distortion set, every
+ * k4 k5 k6; a 5-coefficient calibration has k4 = k5 = k6 = 0) or its fisheye one (A3_DIST_FISHEYE, stated after the rational
+ * algorithm below), in the normalised plane of a3_intrinsics.  With distortion set, every
  * a3_detect_batch_pose* batch undistorts the four corners of every accepted marker on the device (k_undistort_corners, after the
  * refinement and before k_pose) -- the refined corners with refinement on (refinement runs on the raw, distorted frame), else the
  * integer a3_marker corners -- and solves the per-marker poses (k_pose on float corners with intrinsics) and the board pose from the
@@ -374,7 +375,8 @@ int  a3_estimate_board_pose(a3_ctx *ctx, const uint32_t *ids, const float *corne
  * largest-quad start and its rms_px / alt_rms_px are measured in undistorted pixels.  a3_get_refined_corners keeps returning the
  * distorted refined corners.  Such a batch needs intrinsics (the coefficients are in focal units): a pose submit with distortion set
  * and intr == NULL fails with A3_ERR_INVALID.  Detection-only batches are unaffected.
- * The algorithm for one corner (u, v) in pixels, fixed to the bit -- tests/lens_oracle.c a3o_undistort restates it.  Arithmetic is
+ * The algorithm of model A3_DIST_RATIONAL for one corner (u, v) in pixels, fixed to the bit -- tests/lens_oracle.c a3o_undistort
+ * restates it.  Arithmetic is
  * f32; every expression is evaluated as C parses it (left to right), with no fused multiply-add; division and sqrtf correctly rounded:
  *     x0 = (u - cx) / fx;  y0 = (v - cy) / fy;  x = x0;  y = y0;
  *     repeat `iterations` times:
@@ -390,12 +392,42 @@ int  a3_estimate_board_pose(a3_ctx *ctx, const uint32_t *ids, const float *corne
  * (fx, fy, cx, cy) = (focal_x, focal_y, principal_x, principal_y).  The output is the undistorted pixel corner: where an ideal camera
  * with the same fx fy cx cy would have seen the point.  A corner whose iteration diverges or leaves the model's valid field keeps its
  * input position and reports +INFINITY: it is reported, not dropped, and the poses solved from it stay finite.
- * a3_pack_detections records keep their layout: they carry the integer corners only. */
-enum { A3_DIST_NONE = 0, A3_DIST_RATIONAL = 1 };
+ * a3_pack_detections records keep their layout: they carry the integer corners only.
+ *
+ * Model A3_DIST_FISHEYE is OpenCV's cv::fisheye (Kannala-Brandt): theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 +
+ * k4 theta^8) with theta the angle between the ray and the optical axis.  It reads the fields k1 k2 k3 k4 (cv::fisheye's D); p1 p2
+ * k5 k6 must be exactly 0, else A3_ERR_INVALID (a rational coefficient set passed under the wrong model).  Everything said above
+ * holds for it, with this algorithm -- tests/fisheye_oracle.c restates it.  Arithmetic is f32, every expression evaluated as C parses
+ * it, no fused multiply-add, division and sqrtf correctly rounded, and NO OTHER MATH FUNCTION: the arctangent is A below (Cephes'
+ * atanf, written out; within 1.5e-7 rad, 2.8 ulp of pi/2, of the true arctangent on [0, 1e6] and monotone there), never a
+ * library's atanf -- the host's and the device's do not agree with each other.
+ *     A(t):   if      t > 2.414213562373095f  { y0 = 1.5707963267948966f; z = -(1.0f / t); }
+ *             else if t > 0.4142135623730950f { y0 = 0.7853981633974483f; z = (t - 1.0f) / (t + 1.0f); }
+ *             else                            { y0 = 0.0f;                z = t; }
+ *             w = z*z
+ *             A = y0 + ((((8.05374449538e-2f*w - 1.38776856032e-1f)*w + 1.99777106478e-1f)*w - 3.33329491539e-1f)*w*z + z)
+ *             (evaluated as written for any input, negative or non-finite included: the check step judges the outcome)
+ *     forward F(x, y):  r = sqrtf(x*x + y*y);  th = A(r);  t2 = th*th
+ *             thd = th*(1 + (((k4*t2 + k3)*t2 + k2)*t2 + k1)*t2)
+ *             s = r > 0 ? thd / r : 1;   xd = x*s;  yd = y*s
+ *     one corner (u, v):
+ *             x0 = (u - cx) / fx;  y0 = (v - cy) / fy;  rd = sqrtf(x0*x0 + y0*y0);  r = rd
+ *             repeat `iterations` times (Newton on r = tan(theta), so no tangent is needed):
+ *                 th = A(r);  t2 = th*th
+ *                 g  = th*(1 + (((k4*t2 + k3)*t2 + k2)*t2 + k1)*t2)
+ *                 dg = 1 + (((9*k4*t2 + 7*k3)*t2 + 5*k2)*t2 + 3*k1)*t2
+ *                 r  = r - (g - rd)*(1 + r*r)/dg
+ *             s = rd > 0 ? r / rd : 1;   x = x0*s;  y = y0*s
+ *             check:  (xd, yd) = F(x, y);  ex = (xd - x0)*fx;  ey = (yd - y0)*fy;  res = sqrtf(ex*ex + ey*ey)
+ *             ok, out, residual: as above
+ * A distorted point farther from the principal point than the largest theta_d the coefficients reach on theta < pi/2 has no
+ * preimage: it keeps its position and reports +INFINITY, like a point outside the rational model's field.
+ * a3_calibrate_cameras produces rational results only. */
+enum { A3_DIST_NONE = 0, A3_DIST_RATIONAL = 1, A3_DIST_FISHEYE = 3 };   /* 2 stays unassigned: it is refused like any unknown model */
 typedef struct a3_distortion {
     uint32_t model;            /* A3_DIST_NONE (default) */
     uint32_t iterations;       /* 20, 1 .. 100 */
-    float    k1, k2, p1, p2, k3, k4, k5, k6;
+    float    k1, k2, p1, p2, k3, k4, k5, k6;   /* A3_DIST_FISHEYE: k1 k2 k3 k4 = cv::fisheye's D, the other four 0 */
     float    max_residual_px;  /* 0.1; finite, >= 0 */
 } a3_distortion;
 /* model A3_DIST_RATIONAL, every coefficient 0, iterations 20, max_residual_px 0.1 */
@@ -407,7 +439,7 @@ int  a3_set_distortion(a3_ctx *ctx, const a3_distortion *d);
  * cap_markers is short (*n says how many there are). */
 int  a3_get_undistorted_corners(a3_ctx *ctx, float *dst_xy, float *residual_px, size_t cap_markers, size_t *n);
 /* stand-alone, on the same kernel: n points (x, y pairs in pixels) -> out_xy (2n floats) and residual_px (n floats, nullable).  Needs
- * intrinsics and a distortion of model A3_DIST_RATIONAL (not the context's: `d`); synchronous; not while a submitted batch is in
+ * intrinsics and a distortion of model A3_DIST_RATIONAL or A3_DIST_FISHEYE (not the context's: `d`); synchronous; not while a submitted batch is in
  * flight.  Compose with a3_estimate_pose_normalized ((x - cx) / fx, (y - cy) / fy of the output) for poses of caller-given corners. */
 int  a3_undistort_points(a3_ctx *ctx, const float *xy, size_t n, const a3_intrinsics *intr, const a3_distortion *d, float *out_xy,
                          float *residual_px);
@@ -819,21 +851,27 @@ int  a3_build_marker_maps(a3_ctx *ctx, const a3_map *maps, size_t n_maps, const 
  *     inside: x0 = floorf(u), y0 = floorf(v), ax = u - x0, ay = v - y0, x1 = min(x0 + 1, sw - 1), y1 = min(y0 + 1, sh - 1); per byte c
  *         of the pixel  val = (1-ay)*((1-ax)*I[y0][x0][c] + ax*I[y0][x1][c]) + ay*((1-ax)*I[y1][x0][c] + ax*I[y1][x1][c])
  *         out = (uint8_t) min(floorf(val + 0.5f), 255.0f)
+ * With model A3_DIST_FISHEYE the radial and tangential lines (r2, radial, xd, yd) are replaced by (xd, yd) = F(x, y) of the
+ * a3_set_distortion contract's fisheye model, k1 k2 k3 k4 read as there and p1 p2 k5 k6 required to be 0; every other line stays as
+ * written -- tests/fisheye_oracle.c a3o_fisheye_rectify restates it.  A ray at 90 degrees and more from the axis (Wz <= 0) sees
+ * nothing, as in the rational model: the output is a pinhole view.
  * The model is the forward model of the a3_set_distortion contract's check step, the blend that of the corner refinement.  The
  * output format equals the input format (1, 3 or 4 bytes per pixel); every byte is interpolated alike, so RGBA and BGRA are the same
  * work.  Bytes of dst between the end of a row's pixels and the next row are not written.  src and dst must not overlap.  Outside the
  * field where the rational model is monotone a ray can fold back into the image, as with OpenCV: documented, not guarded.
  * info (nullable): tiles = output tiles per frame, path_tiles[p] = how many of them launch path p of the kernel took (path 0 the
- * general one, unused entries 0); the choice depends on the parameters only, never on pixel values.
+ * rational map, which also serves A3_DIST_NONE, path 1 the fisheye map, unused entries 0); the choice depends on the parameters
+ * only, never on pixel values.
  * Input errors (A3_ERR_INVALID, decided on the host before anything is enqueued): null pointers, n_frames 0 or above 65535, a size
  * of 0 or above 65535 or width x height >= 2^30 for either image, a row stride below width x bytes per pixel or a frame stride below
  * height x row stride, an unknown format, memory kind or model, non-zero reserved, a non-finite coefficient, rotation entry or
- * intrinsic, a focal length <= 0.  Synchronous; not while a submitted batch is in flight.  Host-side src or dst is staged through
+ * intrinsic, a non-zero p1 p2 k5 k6 with the fisheye model, a focal length <= 0.  Synchronous; not while a submitted batch is in flight.  Host-side src or dst is staged through
  * device buffers with plain copies.
  * Out of scope: rectifying rotations from a rig (stereoRectify), the choice of an optimal new camera matrix, a submit / collect form. */
 typedef struct a3_rectify {
     a3_intrinsics src;         /* the camera; image_width / image_height = size of the source frames */
-    a3_distortion distortion;  /* model A3_DIST_RATIONAL, or A3_DIST_NONE (coefficients taken as 0); iterations, max_residual_px ignored */
+    a3_distortion distortion;  /* model A3_DIST_RATIONAL or A3_DIST_FISHEYE, or A3_DIST_NONE (coefficients taken as 0); iterations,
+                                  max_residual_px ignored */
     a3_intrinsics dst;         /* the rectified view; image_width / image_height = size of the output frames */
     float    rotation[9];      /* R row-major, camera -> rectified view (cv::initUndistortRectifyMap's R); identity = plain undistortion.
                                   Its TRANSPOSE is used as its inverse; orthonormality is the caller's business */

@@ -73,6 +73,7 @@ pub const A3_BOARD_NONE: u32 = 0;
 pub const A3_BOARD_OK: u32 = 1;
 pub const A3_DIST_NONE: u32 = 0;
 pub const A3_DIST_RATIONAL: u32 = 1;
+pub const A3_DIST_FISHEYE: u32 = 3; // (2 is unassigned and refused)
 pub const A3_BOARD_MAX_MARKERS: usize = 1024;
 pub const A3_CALIB_FIX_PRINCIPAL_POINT: u32 = 1;
 pub const A3_CALIB_ZERO_TANGENT_DIST: u32 = 2;
@@ -193,7 +194,8 @@ pub struct A3CharucoPose {
     pub translation: [f32; 3],
 }
 
-/// a3_distortion: OpenCV's rational lens model (not in the reference; include/aruco3_hip.h states the undistortion)
+/// a3_distortion: OpenCV's rational lens model or, with model A3_DIST_FISHEYE, its cv::fisheye one (not in the reference;
+/// include/aruco3_hip.h states the undistortion)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct A3Distortion {
@@ -904,9 +906,11 @@ impl RefineConfig {
 
 /// A calibrated lens for `Detector::detect_pose_distorted` (an extension: the reference assumes an ideal pinhole camera):
 /// OpenCV's distCoeffs k1 k2 p1 p2 k3 [k4 k5 k6] (a 5-coefficient calibration leaves k4..k6 at 0).  `Default` gives
-/// a3_default_distortion's values: no distortion, 20 iterations, 0.1 px accepted residual.
+/// a3_default_distortion's values: no distortion, 20 iterations, 0.1 px accepted residual.  `model` A3_DIST_FISHEYE
+/// (`Distortion::fisheye`) reads k1 k2 k3 k4 as cv::fisheye's D; p1 p2 k5 k6 must then be 0.
 #[derive(Clone, Copy, Debug)]
 pub struct Distortion {
+    pub model: u32,           // A3_DIST_RATIONAL or A3_DIST_FISHEYE
     pub k1: f32,
     pub k2: f32,
     pub p1: f32,
@@ -920,12 +924,16 @@ pub struct Distortion {
 }
 impl Default for Distortion {
     fn default() -> Self {
-        Distortion { k1: 0.0, k2: 0.0, p1: 0.0, p2: 0.0, k3: 0.0, k4: 0.0, k5: 0.0, k6: 0.0, iterations: 20, max_residual_px: 0.1 }
+        Distortion { model: A3_DIST_RATIONAL, k1: 0.0, k2: 0.0, p1: 0.0, p2: 0.0, k3: 0.0, k4: 0.0, k5: 0.0, k6: 0.0, iterations: 20, max_residual_px: 0.1 }
     }
 }
 impl Distortion {
+    /// cv::fisheye's four coefficients (Kannala-Brandt: theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8))
+    pub fn fisheye(k1: f32, k2: f32, k3: f32, k4: f32) -> Self {
+        Distortion { model: A3_DIST_FISHEYE, k1, k2, k3, k4, ..Default::default() }
+    }
     fn to_a3(&self) -> A3Distortion {
-        A3Distortion { model: A3_DIST_RATIONAL, iterations: self.iterations, k1: self.k1, k2: self.k2, p1: self.p1, p2: self.p2, k3: self.k3,
+        A3Distortion { model: self.model, iterations: self.iterations, k1: self.k1, k2: self.k2, p1: self.p1, p2: self.p2, k3: self.k3,
                        k4: self.k4, k5: self.k5, k6: self.k6, max_residual_px: self.max_residual_px }
     }
 }

@@ -4,7 +4,7 @@ on two contexts of their own, a one-frame call the same way, and the stand-alone
 time comes from a trace: run it under `rocprofv3 --kernel-trace --stats -- python tools/lens_bench.py` and read k_undistort_corners
 (one launch per pose batch with distortion).  Accuracy is measured by tests/test_gpu_distortion.py::test_accuracy_through_a_lens.
 
-    python tools/lens_bench.py [--device 0] [--regions 6] [--steps 10] [--out lens.json]
+    python tools/lens_bench.py [--model rational|fisheye] [--device 0] [--regions 6] [--steps 10] [--out lens.json]
 
 Prints one JSON object (DESIGN.md section 4.7 quotes it)."""
 import argparse
@@ -20,6 +20,7 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 WEBCAM = (-0.28, 0.09, 1e-3, -5e-4, 0.0, 0.0, 0.0, 0.0)
+FISHEYE = (-0.02, 0.005, 0.0, 0.0, -0.003, 0.0005, 0.0, 0.0)   # cv::fisheye's k1 k2 k3 k4 in a3_distortion's slots (--model fisheye)
 
 
 def _time(fn, steps):
@@ -30,7 +31,7 @@ def _time(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def lens_bench(device=0, regions=6, steps=10):
+def lens_bench(device=0, regions=6, steps=10, model="rational"):
     import torch
 
     from aruco3_amd import _lib, synth
@@ -43,6 +44,8 @@ def lens_bench(device=0, regions=6, steps=10):
     w, h = spec.width, spec.height
     intr = _lib.Intrinsics(w, h, 1400.0, 1400.0, w / 2, h / 2)
     dist = _lib.DistortionRec(_lib.DIST_RATIONAL, 20, *WEBCAM, 0.1)
+    if model == "fisheye":
+        dist = _lib.DistortionRec(_lib.DIST_FISHEYE, 20, *FISHEYE, 0.1)
     ctxs = {}
     for on in (False, True):
         c = _lib.Context(_lib.default_config(), d.code_list, d.num_bits, d._tau, device)
@@ -60,7 +63,7 @@ def lens_bench(device=0, regions=6, steps=10):
     stand_ms = _time(lambda: ctxs[True].undistort_points(pts, intr, dist), steps)
     med = lambda v: float(np.median(v))
     res = {
-        "config": 2, "frames": 256, "markers_per_batch": int(markers),
+        "model": model, "config": 2, "frames": 256, "markers_per_batch": int(markers),
         "batch_ms_off": med(out["batch_ms"][False]), "batch_ms_on": med(out["batch_ms"][True]),
         "frame_ms_off": med(out["frame_ms"][False]), "frame_ms_on": med(out["frame_ms"][True]),
         "undistort_points_1e5_ms": stand_ms,
@@ -75,9 +78,10 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--regions", type=int, default=6)
     ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--model", choices=("rational", "fisheye"), default="rational")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = lens_bench(a.device, a.regions, a.steps)
+    res = lens_bench(a.device, a.regions, a.steps, a.model)
     line = json.dumps(res)
     print(line)
     if a.out:
