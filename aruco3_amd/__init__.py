@@ -26,7 +26,8 @@ def __getattr__(name):
         from . import board
 
         return getattr(board, name)
-    if name in ("Calibration", "calibrate_camera", "calibrate_cameras", "calibrate_camera_board", "calibrate_camera_charuco"):
+    if name in ("Calibration", "calibrate_camera", "calibrate_cameras", "calibrate_camera_board", "calibrate_camera_charuco",
+                "calibrate_camera_fisheye", "calibrate_cameras_fisheye"):
         from . import calibration
 
         return getattr(calibration, name)

@@ -35,6 +35,9 @@ CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST, CALIB_FIX_K3, CALIB_RATIONAL
 CALIB_OK, CALIB_TOO_FEW, CALIB_NO_INIT, CALIB_NOT_FINITE = 1, 2, 3, 4
 CALIB_VIEW_USED, CALIB_VIEW_TOO_FEW_POINTS, CALIB_VIEW_DEGENERATE = 1, 2, 3
 CALIB_MAX_POINTS, CALIB_MAX_VIEWS, CALIB_MAX_CAMERAS, CALIB_MAX_CALL_VIEWS = 4096, 4096, 1024, 65536
+# a3_calibrate_fisheye_cameras (include/aruco3_hip.h A3_FISHEYE_*): the flags of its a3_calib_camera records
+FISHEYE_FIX_PRINCIPAL_POINT, FISHEYE_FIX_K1, FISHEYE_FIX_K2, FISHEYE_FIX_K3, FISHEYE_FIX_K4, FISHEYE_USE_INTRINSIC_GUESS = 1, 2, 4, 8, 16, 32
+FISHEYE_START_MAX_R = 4.0
 # a3_calibrate_rigs (include/aruco3_hip.h A3_RIG_*)
 RIG_USE_EXTRINSIC_GUESS, RIG_FIX_EXTRINSICS = 1, 2
 RIG_OK, RIG_NOT_CONNECTED, RIG_NOT_FINITE = 1, 2, 3
@@ -62,7 +65,7 @@ SYMBOLS = [
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
-    "a3_calibrate_cameras", "a3_calibrate_rigs", "a3_build_marker_maps",
+    "a3_calibrate_cameras", "a3_calibrate_fisheye_cameras", "a3_calibrate_rigs", "a3_build_marker_maps",
     "a3_default_rectify", "a3_rectify_frames",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
@@ -431,6 +434,10 @@ def load():
         L.a3_calibrate_cameras.restype = C.c_int
         L.a3_calibrate_cameras.argtypes = [vp, C.POINTER(CalibCamera), C.c_size_t, u32p, C.c_size_t, f32p, f32p, C.POINTER(CalibResult),
                                            C.POINTER(CalibView)]
+    if hasattr(L, "a3_calibrate_fisheye_cameras"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack it)
+        L.a3_calibrate_fisheye_cameras.restype = C.c_int
+        L.a3_calibrate_fisheye_cameras.argtypes = [vp, C.POINTER(CalibCamera), C.c_size_t, u32p, C.c_size_t, f32p, f32p, C.POINTER(CalibResult),
+                                                   C.POINTER(CalibView)]
     if hasattr(L, "a3_rectify_frames"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack rectification)
         L.a3_default_rectify.restype = None
         L.a3_default_rectify.argtypes = [C.POINTER(RectifyRec), C.POINTER(Intrinsics), C.POINTER(DistortionRec)]
@@ -818,6 +825,19 @@ class Context:
         views = (CalibView * max(n_views, 1))() if with_views else None
         check(load().a3_calibrate_cameras(self.handle, cams, len(cams), _p(off, C.c_uint32), n_views, _p(obj, C.c_float), _p(img, C.c_float), res,
                                           views), self.handle)
+        return res, views
+
+    def calibrate_fisheye_cameras(self, cams, view_offsets, object_xy, image_xy, with_views: bool = True):
+        """a3_calibrate_fisheye_cameras: the arguments of calibrate_cameras, the cameras' flags read as FISHEYE_* ->
+        (CalibResult array, CalibView array or None)"""
+        off = np.ascontiguousarray(np.asarray(view_offsets, dtype=np.uint32).reshape(-1))
+        obj = np.ascontiguousarray(np.asarray(object_xy, dtype=np.float32).reshape(-1, 2))
+        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 2))
+        n_views = max(off.size - 1, 0)
+        res = (CalibResult * max(len(cams), 1))()
+        views = (CalibView * max(n_views, 1))() if with_views else None
+        check(load().a3_calibrate_fisheye_cameras(self.handle, cams, len(cams), _p(off, C.c_uint32), n_views, _p(obj, C.c_float),
+                                                  _p(img, C.c_float), res, views), self.handle)
         return res, views
 
     # ---- camera rig calibration ----

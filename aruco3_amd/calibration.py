@@ -1,9 +1,14 @@
-"""Camera calibration on the device (a3_calibrate_cameras): intrinsics and OpenCV's lens model from views of a planar target.
+"""Camera calibration on the device (a3_calibrate_cameras, a3_calibrate_fisheye_cameras): intrinsics and OpenCV's lens model -- the
+rational one or cv::fisheye's -- from views of a planar target.
 
 Not part of the reference: an extension whose algorithm include/aruco3_hip.h fixes to the bit (Zhang's initialisation, then a
 Levenberg-Marquardt bundle over intrinsics, lens model and per-view poses, in f64, one workgroup per camera).  The result's
 `intrinsics` is a `CameraIntrinsics` whose `distortion` is set, ready for `Detector.detect_batch_with_pose` and the board / ChArUco pose
-calls.  Views are lists of correspondences: board points (x, y) in board units on z = 0, image points in pixels."""
+calls.  Views are lists of correspondences: board points (x, y) in board units on z = 0, image points in pixels.
+
+The fisheye solve (`calibrate_camera_fisheye`, or model="fisheye" on the board helpers) is cv::fisheye::calibrate for planar targets:
+fx fy cx cy and D = (k1 k2 k3 k4), a kernel and a bit-exact contract of its own; its result's `intrinsics.distortion` is a fisheye
+`Distortion`, ready for `rectify_frames`, `undistort_points` and the pose calls."""
 import threading
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
@@ -14,6 +19,7 @@ from . import _lib
 from .pinhole import CameraIntrinsics, Distortion
 
 PARAM_NAMES = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")
+FISHEYE_PARAM_INDEX = (0, 1, 2, 3, 4, 5, 8, 9)   # where a fisheye solve's fx fy cx cy k1 k2 k3 k4 sit in `params` / `std_devs`
 
 
 @dataclass
@@ -32,7 +38,8 @@ class ViewResult:
 
 @dataclass
 class Calibration:
-    """one camera (a3_calib_result).  status CALIB_OK, or CALIB_TOO_FEW / _NO_INIT / _NOT_FINITE with zeros elsewhere."""
+    """one camera (a3_calib_result).  status CALIB_OK, or CALIB_TOO_FEW / _NO_INIT / _NOT_FINITE with zeros elsewhere.  `model` says
+    which solve made it; a fisheye result keeps a3_distortion's field order in `params` and `std_devs` (k1 k2 0 0 k3 k4 0 0)."""
     status: int
     intrinsics: Optional[CameraIntrinsics]
     params: np.ndarray        # float64 (12,): fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6
@@ -44,6 +51,7 @@ class Calibration:
     points_used: int
     views: List[ViewResult] = field(default_factory=list)
     inliers: Optional[List[np.ndarray]] = None   # with outlier_passes: per view, the points the last solve used (bool)
+    model: str = "rational"                      # or "fisheye"
 
     @property
     def ok(self) -> bool:
@@ -51,22 +59,25 @@ class Calibration:
 
     @property
     def distortion_coeffs(self) -> np.ndarray:
-        """OpenCV's distCoeffs order: k1 k2 p1 p2 k3 k4 k5 k6"""
+        """OpenCV's distCoeffs order: k1 k2 p1 p2 k3 k4 k5 k6; for a fisheye result cv::fisheye's D = (k1 k2 k3 k4)"""
+        if self.model == "fisheye":
+            return self.params[[4, 5, 8, 9]].copy()
         return self.params[4:].copy()
 
     @classmethod
-    def _from(cls, r, views) -> "Calibration":
+    def _from(cls, r, views, model: str = "rational") -> "Calibration":
         p = np.array([r.fx, r.fy, r.cx, r.cy] + list(r.dist), np.float64)
         intr = None
         if r.status == _lib.CALIB_OK:
             d = r.distortion
             intr = CameraIntrinsics(r.intrinsics.image_width, r.intrinsics.image_height, r.intrinsics.focal_x, r.intrinsics.focal_y,
                                     r.intrinsics.principal_x, r.intrinsics.principal_y,
-                                    distortion=Distortion(d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6, int(d.iterations), d.max_residual_px))
+                                    distortion=Distortion(d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6, int(d.iterations), d.max_residual_px,
+                                                          model=model))
         vr = [ViewResult(int(v.status), int(v.points), float(v.rms_px), np.array(v.rotation, np.float32).reshape(3, 3),
                          np.array(v.translation, np.float32)) for v in views]
         return cls(int(r.status), intr, p, np.array(r.std_dev, np.float64), float(r.rms_px), int(r.iterations), bool(r.converged),
-                   int(r.views_used), int(r.points_used), vr)
+                   int(r.views_used), int(r.points_used), vr, model=model)
 
 
 def _flags(fix_principal_point=False, zero_tangent=False, fix_k3=False, rational=False, guess=None) -> int:
@@ -97,21 +108,21 @@ _ctx = None
 _ctx_lock = threading.Lock()   # one context (one stream, one set of buffers) serves every thread: calls take turns
 
 
-def _calibrate(cams, offsets, obj, img):
+def _calibrate(cams, offsets, obj, img, fisheye: bool = False):
     global _ctx
     with _ctx_lock:
         if _ctx is None:
             _ctx = _lib.Context(_lib.default_config(), np.zeros(1, np.uint64), 64, 1)
-        return _ctx.calibrate_cameras(cams, offsets, obj, img)
+        return (_ctx.calibrate_fisheye_cameras if fisheye else _ctx.calibrate_cameras)(cams, offsets, obj, img)
 
 
-def reproject(params, rotation, translation, object_points) -> np.ndarray:
-    """board points (n, 2) through the camera `params` (fx fy cx cy k1 .. k6) at pose (rotation, translation) -> pixels (n, 2), float64:
-    the forward model of the calibration, evaluated on the host"""
+def reproject(params, rotation, translation, object_points, model: str = "rational") -> np.ndarray:
+    """board points (n, 2) through the camera `params` (fx fy cx cy k1 .. k6, a Calibration's) at pose (rotation, translation) -> pixels
+    (n, 2), float64: the forward model of the calibration (`model`: the rational lens or the fisheye one), evaluated on the host"""
     a = np.asarray(params, np.float64)
     o = np.asarray(object_points, np.float64).reshape(-1, 2)
     P = o @ np.asarray(rotation, np.float64).reshape(3, 3)[:, :2].T + np.asarray(translation, np.float64).reshape(3)
-    xd = Distortion(*[float(v) for v in a[4:12]]).distort_normalized(P[:, :2] / P[:, 2:3])
+    xd = Distortion(*[float(v) for v in a[4:12]], model=model).distort_normalized(P[:, :2] / P[:, 2:3])
     return xd * a[[0, 1]] + a[[2, 3]]
 
 
@@ -155,9 +166,15 @@ def calibrate_camera(object_points, image_points, image_size, *, fix_principal_p
     previous solution; `Calibration.inliers` then says which points of each view the last solve used."""
     kw = dict(image_size=image_size, fix_principal_point=fix_principal_point, zero_tangent=zero_tangent, fix_k3=fix_k3, rational=rational,
               guess=guess, max_iterations=max_iterations)
+    return _solve_with_outlier_passes(calibrate_cameras, object_points, image_points, kw, outlier_passes)
+
+
+def _solve_with_outlier_passes(solve, object_points, image_points, kw, outlier_passes) -> Calibration:
+    """one camera by `solve` (calibrate_cameras or calibrate_cameras_fisheye), then the outlier passes of calibrate_camera: the
+    reprojection runs through the forward model of the solve's own lens"""
     obj, img = _views(object_points, image_points)
     keep = [np.ones(len(o), bool) for o in obj]
-    cal = calibrate_cameras([dict(object_points=obj, image_points=img, **kw)])[0]
+    cal = solve([dict(object_points=obj, image_points=img, **kw)])[0]
     for _ in range(int(outlier_passes)):
         if not cal.ok:
             break
@@ -165,14 +182,67 @@ def calibrate_camera(object_points, image_points, image_size, *, fix_principal_p
         for j, v in enumerate(cal.views):
             if not v.used:
                 continue
-            e = np.linalg.norm(reproject(cal.params, v.rotation, v.translation, k_obj[j]) - k_img[j], axis=1)
+            e = np.linalg.norm(reproject(cal.params, v.rotation, v.translation, k_obj[j], cal.model) - k_img[j], axis=1)
             idx = np.nonzero(keep[j])[0]
             keep[j][idx[~(e < max(1.0, 3.0 * float(np.median(e))))]] = False
-        cal = calibrate_cameras([dict(object_points=[o[k] for o, k in zip(obj, keep)], image_points=[i[k] for i, k in zip(img, keep)],
-                                      **kw)])[0]
+        cal = solve([dict(object_points=[o[k] for o, k in zip(obj, keep)], image_points=[i[k] for i, k in zip(img, keep)], **kw)])[0]
     if outlier_passes:
         cal.inliers = keep
     return cal
+
+
+def _fisheye_flags(fix_principal_point=False, fix_k1=False, fix_k2=False, fix_k3=False, fix_k4=False, guess=None) -> int:
+    return ((_lib.FISHEYE_FIX_PRINCIPAL_POINT if fix_principal_point else 0) | (_lib.FISHEYE_FIX_K1 if fix_k1 else 0) |
+            (_lib.FISHEYE_FIX_K2 if fix_k2 else 0) | (_lib.FISHEYE_FIX_K3 if fix_k3 else 0) | (_lib.FISHEYE_FIX_K4 if fix_k4 else 0) |
+            (_lib.FISHEYE_USE_INTRINSIC_GUESS if guess is not None else 0))
+
+
+def calibrate_cameras_fisheye(problems: Sequence[dict]) -> List[Calibration]:
+    """Several fisheye cameras in one launch (a3_calibrate_fisheye_cameras).  Each problem is a dict of calibrate_camera_fisheye's
+    arguments: object_points, image_points, image_size and optionally fix_principal_point, fix_k1 .. fix_k4, guess (a CameraIntrinsics
+    without a lens or with a fisheye one), max_iterations."""
+    specs, obj, img = [], [], []
+    for pr in problems:
+        o, i = _views(pr["object_points"], pr["image_points"])
+        specs.append((pr, len(obj), len(o)))
+        obj += o
+        img += i
+    cams = (_lib.CalibCamera * max(len(specs), 1))()
+    for c, (pr, first, n) in zip(cams, specs):
+        w, h = pr["image_size"]
+        c.image_width, c.image_height, c.first_view, c.n_views = int(w), int(h), first, n
+        guess = pr.get("guess")
+        c.flags = _fisheye_flags(pr.get("fix_principal_point", False), pr.get("fix_k1", False), pr.get("fix_k2", False), pr.get("fix_k3", False),
+                                 pr.get("fix_k4", False), guess)
+        c.max_iterations = int(pr.get("max_iterations") or 0)
+        if guess is not None:
+            if guess.distortion is not None and guess.distortion.model != "fisheye":
+                raise ValueError("a fisheye calibration guess takes a fisheye Distortion (Distortion.fisheye) or none, not rational lens "
+                                 "coefficients")
+            c.guess = guess._c()
+            c.guess_distortion = (guess.distortion or Distortion.fisheye())._c()
+    offsets = np.concatenate([[0], np.cumsum([len(o) for o in obj])]).astype(np.uint32)
+    res, views = _calibrate(cams, offsets, np.concatenate(obj) if obj else np.zeros((0, 2), np.float32),
+                            np.concatenate(img) if img else np.zeros((0, 2), np.float32), fisheye=True)
+    return [Calibration._from(res[k], [views[first + j] for j in range(n)], "fisheye") for k, (_, first, n) in enumerate(specs)]
+
+
+def calibrate_camera_fisheye(object_points, image_points, image_size, *, fix_principal_point=False, fix_k1=False, fix_k2=False, fix_k3=False,
+                             fix_k4=False, guess: Optional[CameraIntrinsics] = None, max_iterations: Optional[int] = None,
+                             outlier_passes: int = 0) -> Calibration:
+    """cv::fisheye::calibrate for a planar target: fx fy cx cy and D = (k1 k2 k3 k4) of the Kannala-Brandt model; arguments as
+    calibrate_camera.  A fixed coefficient stays at the guess's value, or at 0 without a guess.  Without a guess the focal lengths
+    start at max(width, height) / pi.  k3 and k4 need points far off the axis (60 degrees and more) to be told apart: fix them for a
+    lens or a set of views that does not reach there.  outlier_passes as in calibrate_camera, reprojecting through the fisheye model."""
+    kw = dict(image_size=image_size, fix_principal_point=fix_principal_point, fix_k1=fix_k1, fix_k2=fix_k2, fix_k3=fix_k3, fix_k4=fix_k4,
+              guess=guess, max_iterations=max_iterations)
+    return _solve_with_outlier_passes(calibrate_cameras_fisheye, object_points, image_points, kw, outlier_passes)
+
+
+def _by_model(model: str):
+    if model not in ("rational", "fisheye"):
+        raise ValueError(f"model: 'rational' or 'fisheye', not {model!r}")
+    return calibrate_camera_fisheye if model == "fisheye" else calibrate_camera
 
 
 def board_correspondences(board, detection):
@@ -192,18 +262,18 @@ def board_correspondences(board, detection):
     return np.concatenate(obj).astype(np.float32), np.concatenate(img).astype(np.float32)
 
 
-def calibrate_camera_board(board, detections, image_size, **kw) -> Calibration:
+def calibrate_camera_board(board, detections, image_size, *, model: str = "rational", **kw) -> Calibration:
     """calibrateCameraAruco: one view per Detection, from the marker corners of `board` (a Board / GridBoard); keywords as
-    calibrate_camera.  Detected marker corners carry outliers (a corner whose refinement fell back to the integer quad corner is a few
-    pixels off; now and then a marker is misread), which pull a plain solve by several pixels: pass outlier_passes=2 to solve again
-    without them."""
+    calibrate_camera, or as calibrate_camera_fisheye with model="fisheye".  Detected marker corners carry outliers (a corner whose
+    refinement fell back to the integer quad corner is a few pixels off; now and then a marker is misread), which pull a plain solve
+    by several pixels: pass outlier_passes=2 to solve again without them."""
     pairs = [board_correspondences(board, d) for d in detections]
-    return calibrate_camera([o for o, _ in pairs], [i for _, i in pairs], image_size, **kw)
+    return _by_model(model)([o for o, _ in pairs], [i for _, i in pairs], image_size, **kw)
 
 
-def calibrate_camera_charuco(board, views, image_size, **kw) -> Calibration:
+def calibrate_camera_charuco(board, views, image_size, *, model: str = "rational", **kw) -> Calibration:
     """calibrateCameraCharuco: one view per Detection (its charuco_ids / charuco_corners; None when the frame showed no corner) or
-    (ids, corners) pair of a CharucoBoard; keywords as calibrate_camera"""
+    (ids, corners) pair of a CharucoBoard; keywords as calibrate_camera, or as calibrate_camera_fisheye with model="fisheye" """
     obj, img = [], []
     for v in views:
         ids, corners = (v.charuco_ids, v.charuco_corners) if hasattr(v, "charuco_ids") else v
@@ -211,4 +281,4 @@ def calibrate_camera_charuco(board, views, image_size, **kw) -> Calibration:
         corners = np.zeros((0, 2), np.float32) if corners is None else np.asarray(corners, np.float32).reshape(-1, 2)
         obj.append(board.chessboard_corners[ids].astype(np.float32))
         img.append(corners)
-    return calibrate_camera(obj, img, image_size, **kw)
+    return _by_model(model)(obj, img, image_size, **kw)

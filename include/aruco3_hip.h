@@ -422,7 +422,7 @@ int  a3_estimate_board_pose(a3_ctx *ctx, const uint32_t *ids, const float *corne
  *             ok, out, residual: as above
  * A distorted point farther from the principal point than the largest theta_d the coefficients reach on theta < pi/2 has no
  * preimage: it keeps its position and reports +INFINITY, like a point outside the rational model's field.
- * a3_calibrate_cameras produces rational results only. */
+ * a3_calibrate_cameras produces rational results only; a3_calibrate_fisheye_cameras solves this model's parameters. */
 enum { A3_DIST_NONE = 0, A3_DIST_RATIONAL = 1, A3_DIST_FISHEYE = 3 };   /* 2 stays unassigned: it is refused like any unknown model */
 typedef struct a3_distortion {
     uint32_t model;            /* A3_DIST_NONE (default) */
@@ -600,6 +600,57 @@ typedef struct a3_calib_view {
 /* view_offsets: n_views + 1 entries; results: n_cams; views: n_views records (nullable) */
 int  a3_calibrate_cameras(a3_ctx *ctx, const a3_calib_camera *cams, size_t n_cams, const uint32_t *view_offsets, size_t n_views,
                           const float *object_xy, const float *image_xy, a3_calib_result *results, a3_calib_view *views);
+
+/* Fisheye camera calibration.  NOT in the reference: an opt-in extension (OpenCV's cv::fisheye::calibrate for planar targets),
+ * stand-alone as a3_calibrate_cameras is, with that call's records, limits, statuses, argument rules and input errors; a kernel of its
+ * own (k_calibrate_fisheye, one workgroup per camera).  It solves fx fy cx cy k1 k2 k3 k4 of model A3_DIST_FISHEYE (k1 .. k4 are
+ * cv::fisheye's D; no skew).  `flags` is read as A3_FISHEYE_*, any other bit is A3_ERR_INVALID; a fixed coefficient stays at the guess's
+ * value under USE_INTRINSIC_GUESS and at 0 otherwise, a fixed principal point at the guess's or at the image centre.  guess_distortion
+ * is read only under USE_INTRINSIC_GUESS, and only its k1 k2 k3 k4; a non-zero p1 p2 k5 k6 there is A3_ERR_INVALID as in
+ * a3_set_distortion.  In the result dist[8] and std_dev[4 .. 11] keep a3_distortion's field order (k1 k2 0 0 k3 k4 0 0) and
+ * `distortion` has model A3_DIST_FISHEYE, iterations 20 and max_residual_px 0.1: it plugs into a3_set_distortion, a3_undistort_points
+ * and a3_rectify_frames as it is.  A3_CALIB_NO_INIT is never reported: the start cannot fail that way.
+ * Fixed to the bit as follows -- tests/fisheye_calib_oracle.c a3o_calibrate_fisheye restates it.  Arithmetic is f64 (inputs converted
+ * exactly), every expression evaluated as C parses it, no fused multiply-add, division and sqrt correctly rounded, no other math
+ * function but fabs; sums as in the calibration contract.  The arctangent is A64 (Cephes' double atan, written out; within 1 ulp of
+ * the true arctangent on [1e-8, 1e6] as measured), never a library's atan:
+ *     A64(t): if      t > 2.41421356237309504880 { y0 = 1.5707963267948966; z = -(1.0 / t);            m = MB; }
+ *             else if t <= 0.66                  { y0 = 0.0;                z = t;                     m = 0.0; }
+ *             else                               { y0 = 0.7853981633974483; z = (t - 1.0) / (t + 1.0); m = 0.5 * MB; }
+ *             MB = 6.123233995736765886130e-17;  w = z*z
+ *             p = (((P0*w + P1)*w + P2)*w + P3)*w + P4;   q = ((((w + Q0)*w + Q1)*w + Q2)*w + Q3)*w + Q4
+ *             A64 = y0 + ((z*(w*p/q) + z) + m)
+ *             P = -8.750608600031904122785e-1, -1.615753718733365076637e1, -7.500855792314704667340e1, -1.228866684490136173410e2,
+ *                 -6.485021904942025371773e1;  Q = 2.485846490142306297962e1, 1.650270098316988542046e2, 4.328810604912902668951e2,
+ *                 4.853903996359136964868e2, 1.945506571482613964425e2
+ *   model: a = (fx fy cx cy k1 k2 k3 k4); q, P, ia, x, y as in the calibration contract; r2 = x x + y y, r = sqrt(r2), th = A64(r),
+ *     t2 = th th, poly = 1 + (((k4 t2 + k3) t2 + k2) t2 + k1) t2, thd = th poly, s = r > 0 ? thd / r : 1, xd = x s, yd = y s, residual
+ *     (fx xd + cx - u, fy yd + cy - v).  One point gives two augmented rows of 15: columns 0-3 fx fy cx cy (xd 0 1 0 / 0 yd 0 1), 4-7
+ *     k1 .. k4 (g t2, g t4, g t6, g t8 with g = fx x e / fy y e, e = r > 0 ? th / r : 1, t4 = t2 t2, t6 = t4 t2, t8 = t6 t2), 8-10 w and
+ *     11-13 t as the calibration's columns 12-17 from xxd = s + x x c, xyd = x y c, yyd = s + y y c, c = r > 0 ? (dpoly / (1 + r2) - s)
+ *     / r2 : 0, dpoly = 1 + (((9 k4 t2 + 7 k3) t2 + 5 k2) t2 + 3 k1) t2; column 14 the residual.  tests/fisheye_calib_oracle.c
+ *     fisheye_row lists the expressions.  A view's block is the upper triangle of the 15 x 15 sum, 120 entries, summed as there.
+ *   1. the start: with USE_INTRINSIC_GUESS a = the guess (k1 k2 k3 k4 from guess_distortion); else fx = fy = max(W, H) /
+ *      3.141592653589793 (the equidistant image circle across the long side, OpenCV's start), cx = (W - 1) * 0.5, cy = (H - 1) * 0.5,
+ *      k = 0.
+ *   2. per view with >= 4 points (fewer: TOO_FEW_POINTS): every image point (u, v) is undistorted at the start a, the fisheye
+ *      algorithm of a3_set_distortion in f64: x0 = (u - cx) / fx, y0 = (v - cy) / fy, rd = sqrt(x0 x0 + y0 y0), r = rd, 20 times
+ *      { th = A64(r); t2 = th th; g = th poly; dg = dpoly; r = r - (g - rd) * (1 + r r) / dg }, sc = rd > 0 ? r / rd : 1, x = x0 sc,
+ *      y = y0 sc, (xd, yd) = the model's forward lens at (x, y), ex = (xd - x0) fx, ey = (yd - y0) fy, res = sqrt(ex ex + ey ey).  A
+ *      point is kept for the start when r is finite, r <= A3_FISHEYE_START_MAX_R and res <= 0.1; the others (near or past 90 degrees
+ *      at the start, where a pinhole homography breaks down) are left out of the start only and enter every later sum.  The kept
+ *      points, (x, y) rounded to float, compacted in point order with their board points, go through step 1 of the calibration
+ *      contract (board -> normalised plane).  Fewer than 4 kept points or a bad pivot: DEGENERATE.  Then step 3 of the calibration
+ *      contract with m_c = (H0c, H1c, H2c) (fx = fy = 1, cx = cy = 0) and its pose-only LM on the view's pose columns over ALL of the
+ *      view's points, intrinsics fixed at the start.
+ *   3-5. TOO_FEW when no view is USED or 2 N - n_free - 6 views_used <= 0; then steps 4 and 5 of the calibration contract with the
+ *      intrinsic columns 0-7, the pose columns 8-13, the residual's column 14 and S at most 8 x 8. */
+#define A3_FISHEYE_START_MAX_R 4.0   /* tan(theta) of the widest point a view's start uses (about 76 degrees) */
+enum { A3_FISHEYE_FIX_PRINCIPAL_POINT = 1, A3_FISHEYE_FIX_K1 = 2, A3_FISHEYE_FIX_K2 = 4, A3_FISHEYE_FIX_K3 = 8,
+       A3_FISHEYE_FIX_K4 = 16, A3_FISHEYE_USE_INTRINSIC_GUESS = 32 };
+int  a3_calibrate_fisheye_cameras(a3_ctx *ctx, const a3_calib_camera *cams, size_t n_cams, const uint32_t *view_offsets,
+                                  size_t n_views, const float *object_xy, const float *image_xy, a3_calib_result *results,
+                                  a3_calib_view *views);
 
 /* Camera rig calibration.  NOT in the reference: an opt-in extension (OpenCV's stereoCalibrate with CALIB_FIX_INTRINSIC, for any number
  * of cameras), stand-alone as a3_calibrate_cameras is.  A rig has C cameras (2 .. A3_RIG_MAX_CAMERAS) with KNOWN intrinsics and lens

@@ -82,6 +82,14 @@ pub const A3_CALIB_RATIONAL_MODEL: u32 = 8;
 pub const A3_CALIB_USE_INTRINSIC_GUESS: u32 = 16;
 pub const A3_CALIB_OK: u32 = 1;
 pub const A3_CALIB_VIEW_USED: u32 = 1;
+// a3_calibrate_fisheye_cameras reads a3_calib_camera.flags as these
+pub const A3_FISHEYE_FIX_PRINCIPAL_POINT: u32 = 1;
+pub const A3_FISHEYE_FIX_K1: u32 = 2;
+pub const A3_FISHEYE_FIX_K2: u32 = 4;
+pub const A3_FISHEYE_FIX_K3: u32 = 8;
+pub const A3_FISHEYE_FIX_K4: u32 = 16;
+pub const A3_FISHEYE_USE_INTRINSIC_GUESS: u32 = 32;
+pub const A3_FISHEYE_START_MAX_R: f64 = 4.0;
 
 /// a3_config <-> DetectorConfig, src/aruco.rs:23-30
 #[repr(C)]
@@ -572,6 +580,8 @@ extern "C" {
                                   n: *mut usize) -> c_int;
     pub fn a3_calibrate_cameras(ctx: *mut A3Ctx, cams: *const A3CalibCamera, n_cams: usize, view_offsets: *const u32, n_views: usize,
                                 object_xy: *const f32, image_xy: *const f32, results: *mut A3CalibResult, views: *mut A3CalibView) -> c_int;
+    pub fn a3_calibrate_fisheye_cameras(ctx: *mut A3Ctx, cams: *const A3CalibCamera, n_cams: usize, view_offsets: *const u32, n_views: usize,
+                                        object_xy: *const f32, image_xy: *const f32, results: *mut A3CalibResult, views: *mut A3CalibView) -> c_int;
     pub fn a3_calibrate_rigs(ctx: *mut A3Ctx, rigs: *const A3Rig, n_rigs: usize, cameras: *const A3RigCamera, n_cameras: usize,
                              obs: *const A3RigObservation, n_obs: usize, object_xy: *const f32, image_xy: *const f32,
                              results: *mut A3RigResult, camera_results: *mut A3RigCameraResult, frames: *mut A3RigFrame,
