@@ -36,6 +36,10 @@ def __getattr__(name):
         from . import rig
 
         return getattr(rig, name)
+    if name in ("HandEyeCalibration", "calibrate_hand_eye", "calibrate_hand_eyes", "calibrate_hand_eye_board", "calibrate_hand_eye_charuco"):
+        from . import handeye
+
+        return getattr(handeye, name)
     if name in ("MarkerMap", "build_marker_map", "build_marker_maps", "locate_in_map"):
         from . import markermap
 

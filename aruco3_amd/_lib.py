@@ -44,6 +44,12 @@ RIG_OK, RIG_NOT_CONNECTED, RIG_NOT_FINITE = 1, 2, 3
 RIG_OBS_USED, RIG_OBS_TOO_FEW_POINTS, RIG_OBS_DEGENERATE = 1, 2, 3
 RIG_FRAME_USED, RIG_FRAME_UNUSED = 1, 2
 RIG_MAX_CAMERAS, RIG_MAX_FRAMES, RIG_MAX_RIGS, RIG_MAX_CALL_FRAMES, RIG_MAX_CALL_OBSERVATIONS = 8, 4096, 1024, 65536, 262144
+# a3_calibrate_hand_eyes (include/aruco3_hip.h A3_HANDEYE_*)
+HANDEYE_USE_GUESS, HANDEYE_FIX_X = 1, 2
+HANDEYE_OK, HANDEYE_TOO_FEW_FRAMES, HANDEYE_NO_MOTION, HANDEYE_NOT_FINITE = 1, 2, 3, 4
+HANDEYE_FRAME_USED, HANDEYE_FRAME_TOO_FEW_POINTS, HANDEYE_FRAME_DEGENERATE = 1, 2, 3
+HANDEYE_MAX_FRAMES, HANDEYE_MAX_PROBLEMS, HANDEYE_MAX_CALL_FRAMES = 256, 1024, 65536
+HANDEYE_MIN_PIVOT_RATIO = 1e-4
 # a3_build_marker_maps (include/aruco3_hip.h A3_MAP_*)
 MAP_USE_GUESS, MAP_FIX_MAP = 1, 2
 MAP_OK, MAP_NOT_CONNECTED, MAP_NOT_FINITE = 1, 2, 3
@@ -65,7 +71,7 @@ SYMBOLS = [
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
-    "a3_calibrate_cameras", "a3_calibrate_fisheye_cameras", "a3_calibrate_rigs", "a3_build_marker_maps",
+    "a3_calibrate_cameras", "a3_calibrate_fisheye_cameras", "a3_calibrate_rigs", "a3_calibrate_hand_eyes", "a3_build_marker_maps",
     "a3_default_rectify", "a3_rectify_frames",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
@@ -196,6 +202,31 @@ class RigFrame(C.Structure):
 
 class RigObservationResult(C.Structure):
     _fields_ = [("status", C.c_uint32), ("points", C.c_uint32), ("rms_px", C.c_float), ("reserved", C.c_uint32)]
+
+
+class HandEyeProblem(C.Structure):
+    """a3_handeye_problem: one hand-eye calibration problem (an extension beyond the reference; include/aruco3_hip.h states the algorithm)"""
+    _fields_ = [("first_frame", C.c_uint32), ("n_frames", C.c_uint32), ("flags", C.c_uint32), ("max_iterations", C.c_uint32),
+                ("a", C.c_double * 12), ("guess_x_rotation", C.c_double * 9), ("guess_x_translation", C.c_double * 3),
+                ("guess_y_rotation", C.c_double * 9), ("guess_y_translation", C.c_double * 3)]
+
+
+class HandEyeFrame(C.Structure):
+    _fields_ = [("rotation", C.c_double * 9), ("translation", C.c_double * 3), ("first_point", C.c_uint32), ("n_points", C.c_uint32)]
+
+
+class HandEyeResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("frames_used", C.c_uint32), ("points_used", C.c_uint32), ("pairs_used", C.c_uint32),
+                ("iterations", C.c_uint32), ("converged", C.c_uint32), ("rms_px", C.c_double),
+                ("x_rotation", C.c_double * 9), ("x_translation", C.c_double * 3), ("y_rotation", C.c_double * 9),
+                ("y_translation", C.c_double * 3), ("std_dev", C.c_double * 12),
+                ("x_rotation_f", C.c_float * 9), ("x_translation_f", C.c_float * 3), ("y_rotation_f", C.c_float * 9),
+                ("y_translation_f", C.c_float * 3)]
+
+
+class HandEyeFrameResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("points", C.c_uint32), ("rms_px", C.c_float), ("reserved", C.c_uint32),
+                ("rotation", C.c_double * 9), ("translation", C.c_double * 3), ("rotation_f", C.c_float * 9), ("translation_f", C.c_float * 3)]
 
 
 class Map(C.Structure):
@@ -425,6 +456,10 @@ def load():
         L.a3_calibrate_rigs.argtypes = [vp, C.POINTER(Rig), C.c_size_t, C.POINTER(RigCamera), C.c_size_t, C.POINTER(RigObservation), C.c_size_t,
                                         f32p, f32p, C.POINTER(RigResult), C.POINTER(RigCameraResult), C.POINTER(RigFrame),
                                         C.POINTER(RigObservationResult)]
+    if hasattr(L, "a3_calibrate_hand_eyes"):
+        L.a3_calibrate_hand_eyes.restype = C.c_int
+        L.a3_calibrate_hand_eyes.argtypes = [vp, C.POINTER(HandEyeProblem), C.c_size_t, C.POINTER(HandEyeFrame), C.c_size_t, f32p, f32p,
+                                             C.POINTER(HandEyeResult), C.POINTER(HandEyeFrameResult)]
     if hasattr(L, "a3_build_marker_maps"):
         L.a3_build_marker_maps.restype = C.c_int
         L.a3_build_marker_maps.argtypes = [vp, C.POINTER(Map), C.c_size_t, C.POINTER(MapMarker), C.c_size_t, C.POINTER(MapObservation),
@@ -854,6 +889,20 @@ class Context:
         check(load().a3_calibrate_rigs(self.handle, rigs, len(rigs), cameras, len(cameras), obs, len(obs), _p(obj, C.c_float), _p(img, C.c_float),
                                        res, cres, frames, ores), self.handle)
         return res, cres, frames, ores
+
+    # ---- hand-eye calibration ----
+    def calibrate_hand_eyes(self, problems, frames, object_xy, image_xy):
+        """a3_calibrate_hand_eyes: problems (a HandEyeProblem array), frames (HandEyeFrame array), object / image points (n, 2) ->
+        (HandEyeResult array, HandEyeFrameResult array)"""
+        obj = np.ascontiguousarray(np.asarray(object_xy, dtype=np.float32).reshape(-1, 2))
+        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 2))
+        res = (HandEyeResult * max(len(problems), 1))()
+        fres = (HandEyeFrameResult * max(len(frames), 1))()
+        fn = getattr(load(), "a3_calibrate_hand_eyes", None)
+        if fn is None:
+            raise A3Error(-1, "this libaruco3_hip.so has no a3_calibrate_hand_eyes")
+        check(fn(self.handle, problems, len(problems), frames, len(frames), _p(obj, C.c_float), _p(img, C.c_float), res, fres), self.handle)
+        return res, fres
 
     # ---- marker maps ----
     def build_marker_maps(self, maps, markers, obs, image_xy):

@@ -91,6 +91,9 @@ size_t rig_frame_bytes();
 size_t rig_table_bytes();
 hipError_t launch_rig(hipStream_t, const a3_rig*, uint32_t, const a3_rig_camera*, const a3_rig_observation*, const float*, const float*, uint32_t*,
                       double*, double*, a3_rig_result*, a3_rig_camera_result*, a3_rig_frame*, a3_rig_observation_result*);
+size_t handeye_frame_bytes();
+hipError_t launch_handeye(hipStream_t, const a3_handeye_problem*, uint32_t, const a3_handeye_frame*, const float*, const float*, double*,
+                          a3_handeye_result*, a3_handeye_frame_result*);
 size_t calib_view_bytes();
 hipError_t launch_calibrate(hipStream_t, const a3_calib_camera*, uint32_t, const uint32_t*, const float*, const float*, double*, a3_calib_result*,
                             a3_calib_view*);
@@ -320,6 +323,8 @@ struct a3_ctx {
     // a3_calibrate_rigs: [rigs | cameras | observations | object points | image points], [table | per-observation | per-frame scratch],
     // [results | camera results | frames | observation results]
     DevBuf rig_in, rig_scratch, rig_out;
+    // a3_calibrate_hand_eyes: [problems | frames | object points | image points], the per-frame scratch, [results | frame results]
+    DevBuf handeye_in, handeye_scratch, handeye_out;
     // a3_build_marker_maps: [maps | markers | observations | image corners | matrix offsets], [tables | per-observation | per-frame |
     // per-marker scratch], the reduced systems (two n x n per map), [results | marker results | frames | observation results]
     DevBuf map_in, map_scratch, map_big, map_out;
@@ -1335,6 +1340,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
                       &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->calib_in,
                       &ctx->calib_scratch, &ctx->calib_out, &ctx->rig_in, &ctx->rig_scratch, &ctx->rig_out,
+                      &ctx->handeye_in, &ctx->handeye_scratch, &ctx->handeye_out,
                       &ctx->map_in, &ctx->map_scratch, &ctx->map_big, &ctx->map_out, &ctx->rect_in, &ctx->rect_out};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -2691,6 +2697,86 @@ int a3_calibrate_rigs(a3_ctx* ctx, const a3_rig* rigs, size_t n_rigs, const a3_r
     if (frames) A3_HIP(hipMemcpyAsync(frames, dout + b_res + b_cres, n_frames * sizeof(a3_rig_frame), hipMemcpyDeviceToHost, ctx->stream));
     if (obs_results)
         A3_HIP(hipMemcpyAsync(obs_results, dout + b_res + b_cres + b_frames, n_obs * sizeof(a3_rig_observation_result), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+int a3_calibrate_hand_eyes(a3_ctx* ctx, const a3_handeye_problem* problems, size_t n_problems, const a3_handeye_frame* frames, size_t n_frames,
+                           const float* object_xy, const float* image_xy, a3_handeye_result* results, a3_handeye_frame_result* frame_results) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!problems || !frames || !object_xy || !image_xy || !results) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: null argument");
+    if (ctx->batch.active || ctx->pending_trivial)
+        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a submitted batch has not been collected");
+    if (n_problems == 0 || n_problems > A3_HANDEYE_MAX_PROBLEMS)
+        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: n_problems must be in 1..A3_HANDEYE_MAX_PROBLEMS");
+    if (n_frames == 0 || n_frames > A3_HANDEYE_MAX_CALL_FRAMES)
+        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: n_frames must be in 1..A3_HANDEYE_MAX_CALL_FRAMES");
+    std::vector<uint8_t> frame_owned(n_frames, 0);
+    size_t n_pts = 0;
+    for (size_t r = 0; r < n_problems; r++) {
+        const a3_handeye_problem& R = problems[r];
+        if (R.flags & ~3u) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: unknown flags");
+        if (R.max_iterations > A3_CALIB_MAX_ITERATIONS)
+            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: max_iterations above A3_CALIB_MAX_ITERATIONS");
+        if (R.n_frames == 0 || R.n_frames > A3_HANDEYE_MAX_FRAMES)
+            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a problem's n_frames must be in 1..A3_HANDEYE_MAX_FRAMES");
+        if ((uint64_t)R.first_frame + R.n_frames > n_frames) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a problem's frames lie past n_frames");
+        for (double v : R.a)
+            if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the camera's intrinsics are not finite");
+        if (!(R.a[0] > 0.0) || !(R.a[1] > 0.0)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: focal lengths must be > 0");
+        if (R.flags) {
+            for (double v : R.guess_x_rotation)
+                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the guess is not finite");
+            for (double v : R.guess_x_translation)
+                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the guess is not finite");
+        }
+        if (R.flags & A3_HANDEYE_USE_GUESS) {
+            for (double v : R.guess_y_rotation)
+                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the guess is not finite");
+            for (double v : R.guess_y_translation)
+                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the guess is not finite");
+        }
+        for (uint32_t f = R.first_frame; f < R.first_frame + R.n_frames; f++) {
+            if (frame_owned[f]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: two problems share a frame");
+            frame_owned[f] = 1;
+            const a3_handeye_frame& fr = frames[f];
+            for (double v : fr.rotation)
+                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a frame's robot pose is not finite");
+            for (double v : fr.translation)
+                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a frame's robot pose is not finite");
+            if (fr.n_points > A3_CALIB_MAX_POINTS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a frame has more than A3_CALIB_MAX_POINTS points");
+            if ((uint64_t)fr.first_point + fr.n_points > 0xffffffffull) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a frame's points lie past 2^32");
+            for (size_t i = 2 * (size_t)fr.first_point; i < 2 * ((size_t)fr.first_point + fr.n_points); i++)
+                if (!std::isfinite(object_xy[i]) || !std::isfinite(image_xy[i])) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a point is not finite");
+            n_pts = std::max(n_pts, (size_t)fr.first_point + fr.n_points);
+        }
+    }
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_probs = up(n_problems * sizeof(a3_handeye_problem)), b_frames = up(n_frames * sizeof(a3_handeye_frame));
+    const size_t b_pts = up(std::max<size_t>(n_pts, 1) * 2 * sizeof(float));
+    const size_t b_res = up(n_problems * sizeof(a3_handeye_result)), b_fres = up(n_frames * sizeof(a3_handeye_frame_result));
+    A3_HIP(ctx->handeye_in.ensure(b_probs + b_frames + 2 * b_pts));
+    A3_HIP(ctx->handeye_scratch.ensure(up(n_frames * handeye_frame_bytes())));
+    A3_HIP(ctx->handeye_out.ensure(b_res + b_fres));
+    uint8_t* din = ctx->handeye_in.as<uint8_t>();
+    uint8_t* dout = ctx->handeye_out.as<uint8_t>();
+    A3_HIP(hipMemcpyAsync(din, problems, n_problems * sizeof(a3_handeye_problem), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(din + b_probs, frames, n_frames * sizeof(a3_handeye_frame), hipMemcpyHostToDevice, ctx->stream));
+    if (n_pts) {
+        A3_HIP(hipMemcpyAsync(din + b_probs + b_frames, object_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        A3_HIP(hipMemcpyAsync(din + b_probs + b_frames + b_pts, image_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    // a frame that no problem owns is not written by the kernel: it comes back zero
+    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_fres, ctx->stream));
+    A3_HIP(launch_handeye(ctx->stream, reinterpret_cast<const a3_handeye_problem*>(din), (uint32_t)n_problems,
+                          reinterpret_cast<const a3_handeye_frame*>(din + b_probs), reinterpret_cast<const float*>(din + b_probs + b_frames),
+                          reinterpret_cast<const float*>(din + b_probs + b_frames + b_pts), ctx->handeye_scratch.as<double>(),
+                          reinterpret_cast<a3_handeye_result*>(dout), reinterpret_cast<a3_handeye_frame_result*>(dout + b_res)));
+    A3_HIP(hipMemcpyAsync(results, dout, n_problems * sizeof(a3_handeye_result), hipMemcpyDeviceToHost, ctx->stream));
+    if (frame_results)
+        A3_HIP(hipMemcpyAsync(frame_results, dout + b_res, n_frames * sizeof(a3_handeye_frame_result), hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }

@@ -757,6 +757,117 @@ int  a3_calibrate_rigs(a3_ctx *ctx, const a3_rig *rigs, size_t n_rigs, const a3_
                        a3_rig_result *results, a3_rig_camera_result *camera_results, a3_rig_frame *frames,
                        a3_rig_observation_result *obs_results);
 
+/* Hand-eye calibration by reprojection error.  NOT in the reference: an opt-in extension (OpenCV's calibrateHandEye /
+ * calibrateRobotWorldHandEye, minimising pixels), stand-alone as a3_calibrate_rigs is.  For every frame f the chain board -> camera is
+ *     G_f = X . M_f . Y
+ * with M_f a KNOWN rigid transform per frame (the robot's forward kinematics; its translation in the units of object_xy) and X, Y the
+ * two unknown rigid transforms.  Eye-in-hand (camera on the flange, board fixed): M_f = (gripper -> base)_f^-1, X = gripper -> camera,
+ * Y = board -> base.  Eye-to-hand (camera fixed, board on the flange): M_f = (gripper -> base)_f, X = base -> camera, Y = board ->
+ * gripper.  The camera has KNOWN intrinsics and lens (a3_handeye_problem.a, the order of a3_rig_camera.a); a frame's points are
+ * first_point .. first_point + n_points - 1 of object_xy / image_xy (the point format of a3_calibrate_cameras).  The cost is the
+ * reprojection error over all points of all USED frames; the 12 unknowns are (w, t) of X and (w, t) of Y.  A call solves n_problems
+ * independent problems (one workgroup each, k_handeye); a problem owns a contiguous, disjoint range of the call's frames.  M_f is used as
+ * given: a rotation that is not orthonormal is the caller's business.
+ * Fixed to the bit as follows -- tests/handeye_oracle.c a3o_calibrate_hand_eyes restates it; arithmetic, notation and poses as for
+ * a3_calibrate_rigs (f64, every expression as C parses it, no fused multiply-add, sqrt and division correctly rounded).
+ *   row: with E' = X . M_f and G = E' . Y: the calibration's model and its translation columns at (a, G) give the residual and u, v as
+ *     in the rig contract.  qf = (RY0 X + RY1 Y, RY3 X + RY4 Y, RY6 X + RY7 Y), y = qf + tY, m[r] = ((RM[3r] y0 + RM[3r+1] y1) +
+ *     RM[3r+2] y2) + tM[r], qc[r] = (RX[3r] m0 + RX[3r+1] m1) + RX[3r+2] m2.  The row of 13 is the rig contract's with Rc = R_E', this qc
+ *     and this qf: columns 0-5 (w, t) of X, 6-11 (w, t) of Y, 12 the residual.  A frame's block is the upper triangle of the 13 x 13 sum
+ *     over its points (91 entries, summed as a view's block).
+ *   1. per frame with >= 4 points: step 1 of the rig contract at the camera's a -> status (TOO_FEW_POINTS / DEGENERATE / USED), P_f =
+ *      board -> camera and cost_f.  Fewer than 3 USED frames: status TOO_FEW_FRAMES.
+ *   2. the start.  Under FIX_X, or USE_GUESS, X is the caller's guess and no pair is formed (pairs_used = 0).  Otherwise, for every
+ *      pair i < j of USED frames: A = P_i . P_j^-1, B = M_i . M_j^-1 (so that A . X = X . B), and the quaternions q_A, q_B = quat(R):
+ *        tr = (R0 + R4) + R8;
+ *        if tr >= R0, R4, R8:   s = sqrt(tr + 1.0) * 2.0;                (w, x, y, z) = (0.25 s, (R7 - R5) / s, (R2 - R6) / s, (R3 - R1) / s)
+ *        else if R0 >= R4, R8:  s = sqrt(((1.0 + R0) - R4) - R8) * 2.0;  ((R7 - R5) / s, 0.25 s, (R1 + R3) / s, (R2 + R6) / s)
+ *        else if R4 >= R8:      s = sqrt(((1.0 + R4) - R0) - R8) * 2.0;  ((R2 - R6) / s, (R1 + R3) / s, 0.25 s, (R5 + R7) / s)
+ *        else:                  s = sqrt(((1.0 + R8) - R0) - R4) * 2.0;  ((R3 - R1) / s, (R2 + R6) / s, (R5 + R7) / s, 0.25 s)
+ *        then all four negated when w < 0.
+ *      A pair counts (pairs_used) when A3_HANDEYE_COS_HALF_MAX_PAIR_ANGLE <= q_B.w <= A3_HANDEYE_COS_HALF_MIN_PAIR_ANGLE: the cosines
+ *      of half of 170 and of half of 2 degrees, design constants (below 2 degrees a pair says nothing about rotation, near 180 the sign
+ *      of q is decided by noise).  With d = wA - wB, dl = vA - vB, sg = vA + vB the pair's 4 x 4 matrix K is
+ *        [ d, -dl0, -dl1, -dl2 ], [ dl0, d, -sg2, sg1 ], [ dl1, sg2, d, -sg0 ], [ dl2, -sg1, sg0, d ]     (K q_X = q_A q_X - q_X q_B)
+ *      and its term of N (upper triangle, 10 entries, row by row) is, entry (a, b): t = +0.0; t += K[r][a] K[r][b] for r = 0 .. 3.
+ *      Pair sums: for every frame i in frame order a partial sum from +0.0 over its counted pairs (i, j), j ascending (s += t), then
+ *      N = the partials added in i order from +0.0 (a frame without pairs adds +0.0).  No counted pair: status NO_MOTION.
+ *      solve3(S, b) is the LDL^T of a symmetric 3 x 3 S: mx = the largest diagonal entry (S00, then S11, S22 compared with >), thr =
+ *      A3_HANDEYE_MIN_PIVOT_RATIO * mx; d0 = S00; l10 = S01 / d0; l20 = S02 / d0; d1 = S11 - l10 l10 d0; l21 = (S12 - l20 l10 d0) /
+ *      d1; d2 = (S22 - l20 l20 d0) - l21 l21 d1; a pivot d that is not finite or not > thr makes the system DEGENERATE (tested in the
+ *      order d0, d1, d2, each before it is divided by); y0 = b0; y1 = b1 - l10 y0; y2 = (b2 - l20 y0) - l21 y1; x2 = y2 / d2;
+ *      x1 = y1 / d1 - l21 x2; x0 = (y0 / d0 - l10 x1) - l20 x2.
+ *      Rotation: for chart k = 0 .. 3, q_k = 1 and the other three (ascending index r) from solve3(N[r][r'], -N[r][k]); n2_k =
+ *      ((q0 q0 + q1 q1) + q2 q2) + q3 q3.  The chart with the smallest n2 among those not degenerate wins, the lowest k on ties (its
+ *      pinned component is the largest of the normalised quaternion, so no orientation of the mount is singular); all four
+ *      degenerate: NO_MOTION.  q <- q / sqrt(n2), R_X = [1 - 2 (yy + zz), 2 (xy - wz), 2 (xz + wy); 2 (xy + wz), 1 - 2 (xx + zz),
+ *      2 (yz - wx); 2 (xz - wy), 2 (yz + wx), 1 - 2 (xx + yy)] with (w, x, y, z) = q, each product as written.
+ *      Translation: over the same pairs, D = R_A - I, c = R_X t_B - t_A (c[r] = ((RX[3r] tB0 + RX[3r+1] tB1) + RX[3r+2] tB2) - tA[r]);
+ *      the pair's terms: entry (a, b), a <= b, of D^T D: t = +0.0; t += D[3r+a] D[3r+b] for r = 0 .. 2, and entry a of D^T c likewise
+ *      with c[r]; summed as N.  t_X = solve3(sum D^T D, sum D^T c); degenerate: NO_MOTION (pure translations and rotations about
+ *      parallel axes end here or at the charts).  A3_HANDEYE_MIN_PIVOT_RATIO is a design constant: axes within about a degree of
+ *      parallel.
+ *      Y: under USE_GUESS the caller's guess; otherwise Y = M_f^-1 . (X^-1 . P_f) from the USED frame with the lowest cost_f / n_f, the
+ *      first on ties.
+ *   3. joint LM, lambda 1e-3.  S = the sum of the USED frames' blocks at (X, Y), entry by entry in frame order from +0.0; cost = S[12][12].
+ *      A non-finite cost at the start: NOT_FINITE.  The free unknowns are columns 0-11, under FIX_X columns 6-11 (n = 12 / 6).  An
+ *      iteration: A = the free part of S with A_ii <- A_ii + lambda A_ii, LDL^T as the calibration's S (a bad pivot: a rejected step),
+ *      d = A^-1 (-S[free][12]); X <- (cay(w) R_X, t_X + dt) from d's first six (not under FIX_X), Y likewise from its last six;
+ *      every USED frame's block at the candidate; acceptance, lambda x10 / /10, convergence, max_iterations and the stop at cost 0
+ *      exactly as step 4 of the calibration contract.
+ *   4. rms_px = sqrt(cost / N) (N: points of the USED frames), per frame (float) sqrt(cost_f / n_f) from its block at the solution.
+ *      std_dev: sqrt(sigma2 diag(A0^-1)), A0 the undamped free part of S at the solution, sigma2 = cost / (2 N - n); +inf for every free
+ *      unknown where A0 is not positive definite; 0 for X under FIX_X.
+ * A problem that is not solved reports its status and counts and zeros elsewhere; its frames report status, points and, where USED,
+ * P_f (with rms_px 0).  A frame that is not USED has a zero pose.
+ * Input errors (A3_ERR_INVALID): null pointers, zero counts, unknown flags, max_iterations above A3_CALIB_MAX_ITERATIONS, empty,
+ * overlapping or out-of-range frame ranges, counts above the limits, more than A3_CALIB_MAX_POINTS points in a frame, non-finite
+ * coordinates, intrinsics or M_f, focal lengths <= 0, a non-finite guess where one is read (X under USE_GUESS / FIX_X, Y under
+ * USE_GUESS).  Synchronous; not while a submitted batch is in flight. */
+#define A3_HANDEYE_MAX_FRAMES        256     /* per problem */
+#define A3_HANDEYE_MAX_PROBLEMS      1024    /* per call */
+#define A3_HANDEYE_MAX_CALL_FRAMES   65536   /* per call, all problems */
+#define A3_HANDEYE_MAX_PAIR_ANGLE    170.0   /* degrees: the widest relative robot rotation a pair of frames may have in the start ... */
+#define A3_HANDEYE_MIN_PAIR_ANGLE    2.0     /* ... and the narrowest */
+#define A3_HANDEYE_COS_HALF_MAX_PAIR_ANGLE 0.08715574274765817   /* cos(85 degrees) */
+#define A3_HANDEYE_COS_HALF_MIN_PAIR_ANGLE 0.9998476951563913    /* cos(1 degree) */
+#define A3_HANDEYE_MIN_PIVOT_RATIO   1e-4
+enum { A3_HANDEYE_USE_GUESS = 1, A3_HANDEYE_FIX_X = 2 };
+enum { A3_HANDEYE_OK = 1, A3_HANDEYE_TOO_FEW_FRAMES = 2, A3_HANDEYE_NO_MOTION = 3, A3_HANDEYE_NOT_FINITE = 4 };
+enum { A3_HANDEYE_FRAME_USED = 1, A3_HANDEYE_FRAME_TOO_FEW_POINTS = 2, A3_HANDEYE_FRAME_DEGENERATE = 3 };
+typedef struct a3_handeye_problem {
+    uint32_t first_frame, n_frames;    /* a contiguous, disjoint range of the call's frames */
+    uint32_t flags;                    /* A3_HANDEYE_* */
+    uint32_t max_iterations;           /* LM iterations; 0 = A3_CALIB_DEFAULT_ITERATIONS */
+    double   a[12];                    /* fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 */
+    double   guess_x_rotation[9], guess_x_translation[3];   /* read with USE_GUESS / FIX_X */
+    double   guess_y_rotation[9], guess_y_translation[3];   /* read with USE_GUESS */
+} a3_handeye_problem;
+typedef struct a3_handeye_frame {
+    double   rotation[9], translation[3];   /* M_f */
+    uint32_t first_point, n_points;
+} a3_handeye_frame;
+typedef struct a3_handeye_result {
+    uint32_t status;                   /* A3_HANDEYE_OK / _TOO_FEW_FRAMES / _NO_MOTION / _NOT_FINITE */
+    uint32_t frames_used, points_used, pairs_used, iterations, converged;
+    double   rms_px;
+    double   x_rotation[9], x_translation[3];   /* X */
+    double   y_rotation[9], y_translation[3];   /* Y */
+    double   std_dev[12];                       /* of (w, t) of X, then of Y: w the Cayley increment at the solution */
+    float    x_rotation_f[9], x_translation_f[3], y_rotation_f[9], y_translation_f[3];   /* the same in float, the a3_pose convention */
+} a3_handeye_result;
+typedef struct a3_handeye_frame_result {
+    uint32_t status, points;           /* A3_HANDEYE_FRAME_* */
+    float    rms_px;
+    uint32_t reserved;
+    double   rotation[9], translation[3];   /* P_f: the frame's own board -> camera pose from step 1 */
+    float    rotation_f[9], translation_f[3];
+} a3_handeye_frame_result;
+/* results: n_problems; frame_results: n_frames records (nullable); the point arrays hold the largest first_point + n_points */
+int  a3_calibrate_hand_eyes(a3_ctx *ctx, const a3_handeye_problem *problems, size_t n_problems, const a3_handeye_frame *frames,
+                            size_t n_frames, const float *object_xy, const float *image_xy, a3_handeye_result *results,
+                            a3_handeye_frame_result *frame_results);
+
 /* Marker maps.  NOT in the reference: an opt-in extension (what the ArUco library ships as MarkerMap / marker mapper), stand-alone as
  * a3_calibrate_rigs is.  A map has M square markers (1 .. A3_MAP_MAX_MARKERS) of one side length marker_length, taped anywhere in a
  * room, one camera with KNOWN intrinsics and lens (a3_map.a, the order of a3_rig_camera.a) and F frames of that camera.  An

@@ -351,6 +351,81 @@ pub struct A3RigObservationResult {
     pub reserved: u32,
 }
 
+/// a3_handeye_problem: one hand-eye calibration problem, board -> camera G_f = X . M_f . Y (not in the reference; include/aruco3_hip.h
+/// states the algorithm)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3HandEyeProblem {
+    pub first_frame: u32,
+    pub n_frames: u32,
+    pub flags: u32,
+    pub max_iterations: u32,
+    pub a: [f64; 12],
+    pub guess_x_rotation: [f64; 9],
+    pub guess_x_translation: [f64; 3],
+    pub guess_y_rotation: [f64; 9],
+    pub guess_y_translation: [f64; 3],
+}
+
+/// a3_handeye_frame: the known transform M_f of one frame and its points
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3HandEyeFrame {
+    pub rotation: [f64; 9],
+    pub translation: [f64; 3],
+    pub first_point: u32,
+    pub n_points: u32,
+}
+
+/// a3_handeye_result: one problem's status, X, Y, their deviations and the fit
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3HandEyeResult {
+    pub status: u32,
+    pub frames_used: u32,
+    pub points_used: u32,
+    pub pairs_used: u32,
+    pub iterations: u32,
+    pub converged: u32,
+    pub rms_px: f64,
+    pub x_rotation: [f64; 9],
+    pub x_translation: [f64; 3],
+    pub y_rotation: [f64; 9],
+    pub y_translation: [f64; 3],
+    pub std_dev: [f64; 12],
+    pub x_rotation_f: [f32; 9],
+    pub x_translation_f: [f32; 3],
+    pub y_rotation_f: [f32; 9],
+    pub y_translation_f: [f32; 3],
+}
+
+/// a3_handeye_frame_result: one frame's status, fit and own pose board -> camera
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3HandEyeFrameResult {
+    pub status: u32,
+    pub points: u32,
+    pub rms_px: f32,
+    pub reserved: u32,
+    pub rotation: [f64; 9],
+    pub translation: [f64; 3],
+    pub rotation_f: [f32; 9],
+    pub translation_f: [f32; 3],
+}
+
+pub const A3_HANDEYE_USE_GUESS: u32 = 1;
+pub const A3_HANDEYE_FIX_X: u32 = 2;
+pub const A3_HANDEYE_OK: u32 = 1;
+pub const A3_HANDEYE_TOO_FEW_FRAMES: u32 = 2;
+pub const A3_HANDEYE_NO_MOTION: u32 = 3;
+pub const A3_HANDEYE_NOT_FINITE: u32 = 4;
+pub const A3_HANDEYE_FRAME_USED: u32 = 1;
+pub const A3_HANDEYE_FRAME_TOO_FEW_POINTS: u32 = 2;
+pub const A3_HANDEYE_FRAME_DEGENERATE: u32 = 3;
+pub const A3_HANDEYE_MAX_FRAMES: usize = 256;
+pub const A3_HANDEYE_MAX_PROBLEMS: usize = 1024;
+pub const A3_HANDEYE_MAX_CALL_FRAMES: usize = 65536;
+
 /// a3_map: one marker map problem (not in the reference; include/aruco3_hip.h states the algorithm)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -586,6 +661,9 @@ extern "C" {
                              obs: *const A3RigObservation, n_obs: usize, object_xy: *const f32, image_xy: *const f32,
                              results: *mut A3RigResult, camera_results: *mut A3RigCameraResult, frames: *mut A3RigFrame,
                              obs_results: *mut A3RigObservationResult) -> c_int;
+    pub fn a3_calibrate_hand_eyes(ctx: *mut A3Ctx, problems: *const A3HandEyeProblem, n_problems: usize, frames: *const A3HandEyeFrame,
+                                  n_frames: usize, object_xy: *const f32, image_xy: *const f32, results: *mut A3HandEyeResult,
+                                  frame_results: *mut A3HandEyeFrameResult) -> c_int;
     pub fn a3_build_marker_maps(ctx: *mut A3Ctx, maps: *const A3Map, n_maps: usize, markers: *const A3MapMarker, n_markers: usize,
                                 obs: *const A3MapObservation, n_obs: usize, image_xy: *const f32, results: *mut A3MapResult,
                                 marker_results: *mut A3MapMarkerResult, frames: *mut A3MapFrame,
@@ -1467,6 +1545,32 @@ pub fn calibrate_rig(d: &Detector, cameras: &[[f64; 12]], n_frames: u32, observa
                           cres.as_mut_ptr(), frames.as_mut_ptr(), std::ptr::null_mut())
     }, "a3_calibrate_rigs");
     (res, cres, frames)
+}
+
+/// New (additive): hand-eye calibration solved on the device (`a3_calibrate_hand_eyes`; not in the reference).  `camera` holds the
+/// known intrinsics and lens (fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6); `frames[f]` is (M_f as (rotation, translation), (board (x, y),
+/// pixel (u, v)) pairs), with M_f = (gripper -> base)^-1 for a camera on the flange and gripper -> base for a fixed camera looking at
+/// a board on the flange.  `flags` is 0 here (guesses and A3_HANDEYE_FIX_X go through the raw call).  Returns the problem's record
+/// (X = gripper -> camera / base -> camera, Y = board -> base / board -> gripper) and one record per frame.
+pub fn calibrate_hand_eye(d: &Detector, camera: &[f64; 12], frames: &[(([f64; 9], [f64; 3]), Vec<((f32, f32), (f32, f32))>)])
+                          -> (A3HandEyeResult, Vec<A3HandEyeFrameResult>) {
+    let slot = slot_for(d);
+    let ctx = slot.lock().unwrap();
+    let (mut obj, mut img, mut recs) = (Vec::new(), Vec::new(), Vec::new());
+    for ((rotation, translation), pts) in frames {
+        recs.push(A3HandEyeFrame { rotation: *rotation, translation: *translation, first_point: (obj.len() / 2) as u32, n_points: pts.len() as u32 });
+        for &((x, y), (u, w)) in pts {
+            obj.extend_from_slice(&[x, y]);
+            img.extend_from_slice(&[u, w]);
+        }
+    }
+    let problem = A3HandEyeProblem { first_frame: 0, n_frames: recs.len() as u32, a: *camera, ..Default::default() };
+    let mut res = A3HandEyeResult::default();
+    let mut fres = vec![A3HandEyeFrameResult::default(); recs.len()];
+    ctx.check(unsafe {
+        a3_calibrate_hand_eyes(ctx.raw, &problem, 1, recs.as_ptr(), recs.len(), obj.as_ptr(), img.as_ptr(), &mut res, fres.as_mut_ptr())
+    }, "a3_calibrate_hand_eyes");
+    (res, fres)
 }
 
 /// per-batch stage counters of the detector's last call
