@@ -75,7 +75,7 @@ SYMBOLS = [
     "a3_default_rectify", "a3_rectify_frames",
 ]
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
-INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates"]
+INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates", "a3_debug_sample_frames"]
 
 
 class A3Error(RuntimeError):
@@ -414,6 +414,9 @@ def load():
     L.a3_debug_rotate_bits.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, u8p]
     L.a3_debug_inject_candidates.restype = C.c_int
     L.a3_debug_inject_candidates.argtypes = [vp, u32p, C.c_size_t]
+    if hasattr(L, "a3_debug_sample_frames"):    # (older builds loaded through A3_HIP_LIB for A/B runs lack it)
+        L.a3_debug_sample_frames.restype = C.c_int
+        L.a3_debug_sample_frames.argtypes = [vp, C.c_int]
     if hasattr(L, "a3_refine_corners"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack corner refinement)
         L.a3_default_refine_config.restype = None
         L.a3_default_refine_config.argtypes = [C.POINTER(RefineConfig)]
@@ -985,6 +988,10 @@ class Context:
         """the next one-frame batch decodes THESE quads (n x 4 x 2, in this order) instead of what its contour stage finds"""
         q = np.ascontiguousarray(quads, dtype=np.uint32).reshape(-1, 8)
         check(load().a3_debug_inject_candidates(self.handle, _p(q, C.c_uint32), q.shape[0]), self)
+
+    def debug_sample_frames(self, on: bool):
+        """while set, a batch with debug taps on keeps sampling the caller's frames (as one without taps does) and not the grey plane"""
+        check(load().a3_debug_sample_frames(self.handle, int(on)), self.handle)
 
     def debug_discard_too_near(self, quads: np.ndarray, min_distance: float) -> np.ndarray:
         q = np.ascontiguousarray(quads, dtype=np.uint32).reshape(-1, 8)

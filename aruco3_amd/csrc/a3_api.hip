@@ -173,10 +173,12 @@ struct Batch {
     a3_charuco_config charuco_cfg{};
     uint32_t charuco_nc = 0, charuco_guess = 0;   // chessboard corners; records in the speculative read-back
     bool taps = false;           // debug taps: grey plane, patches, contours and the per-frame candidate counts are kept
+    bool sample_frames = false;  // a3_debug_sample_frames: a tapped batch still samples the caller's frames wherever an untapped one would
     int profiling = 0, profile_every = 1;   // a3_set_profiling in force
     // enqueue_front
     int prof = 0;                // the profiling level of this enqueue (the sampled threshold-only mode times one batch in profile_every)
     bool need_grey = false;      // the threshold kernel writes the grey plane (taps, or a window above 15)
+    bool grey_src = false;       // ... and the decode stage samples it (always, unless a3_debug_sample_frames keeps a tapped batch on the frames)
     uint32_t max_cand = 0, patch_cap = 0, marker_cap = 0, guess = 0;
     // enqueue_chain
     bool active = false, device_plan = false;
@@ -241,6 +243,7 @@ struct a3_ctx {
     uint32_t plan_n = 0, plan_W = 0, plan_H = 0;
     uint64_t plan_darts = 0;   // > 0: launch the fixpoint passes over all darts too (a recent batch needed them); else only k_resolve_fast
     bool debug_taps = false;   // a3_set_debug_taps: the setting the next batch captures
+    bool debug_sample_frames = false;   // a3_debug_sample_frames (tests only): likewise
     uint32_t patch_cap = 0;    // patches the tap of the last tapped batch could hold
     bool grey_valid = false;   // the last batch wrote the grey plane
     // a3_download_contours: the last batch ran with debug taps in one chunk, so its contour table and point pool are whole
@@ -772,6 +775,7 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     // threshold kernels (windows above 15); the decode stage otherwise samples the caller's frames directly
     const bool big_window = threshold_writes_grey_plane(ctx->cfg.threshold_window, b.pixels, b.row_stride, b.frame_stride, (int)W);
     b.need_grey = b.taps || big_window;
+    b.grey_src = big_window || (b.taps && !b.sample_frames);
     if (b.need_grey) A3_HIP(ctx->grey.ensure(npx * n));
     ctx->grey_valid = b.need_grey;
     if (big_window) A3_HIP(ctx->hsum.ensure(npx * n * 2));
@@ -992,7 +996,7 @@ int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
     if (b.prof >= 2) A3_HIP(hipEventRecord(ctx->ev[2], st));
 
     // ---- candidates -> markers -> read-back: enqueued now, or deferred behind the next submitted batch's threshold kernel ----
-    b.src = b.need_grey ? PixelSrc{ctx->grey.as<uint8_t>(), W, (unsigned long long)npx, kFmtGreyPlane}
+    b.src = b.grey_src ? PixelSrc{ctx->grey.as<uint8_t>(), W, (unsigned long long)npx, kFmtGreyPlane}
                         : PixelSrc{b.pixels, b.row_stride, b.frame_stride, b.fmt};
     ctx->dbg_src = b.src;
     b.head_bytes = head_bytes;   // the markers follow the head directly, on the device and in the staging buffer
@@ -1527,6 +1531,7 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
                                                        (uint64_t)ctx->last_charuco_total + ctx->last_charuco_total / 4 + 64);
     }
     b.taps = ctx->debug_taps;
+    b.sample_frames = ctx->debug_sample_frames;
     b.profiling = ctx->profiling; b.profile_every = ctx->profile_every;
     ctx->board_valid = false;
     ctx->undist_valid = false;
@@ -2101,6 +2106,12 @@ int a3_debug_inject_candidates(a3_ctx* ctx, const uint32_t* quads_xy, size_t n) 
         }
     }
     ctx->inject_armed = true;
+    return A3_OK;
+}
+
+int a3_debug_sample_frames(a3_ctx* ctx, int enabled) {
+    if (!ctx) return A3_ERR_INVALID;
+    ctx->debug_sample_frames = enabled != 0;
     return A3_OK;
 }
 

@@ -67,6 +67,11 @@ int  a3_debug_rotate_bits(a3_ctx *ctx, const uint8_t *bits, uint32_t n, uint32_t
  * the only way to lead one through discard_too_near, the solve, k_decode's 1 x 1 stand-in and the accept test on the device.
  * One shot: the batch after that runs unchanged. */
 int  a3_debug_inject_candidates(a3_ctx *ctx, const uint32_t *quads_xy, size_t n);
+/* Debug taps switch the decode stage's source to the packed grey plane, so a tapped batch's patches say nothing about the sampler
+ * an untapped batch runs on the caller's pixel format, strides and alignment.  While this is set, a tapped batch still gets its
+ * grey plane (for the grey tap) but its decode stage samples what an untapped batch would: the caller's frames, or the grey plane
+ * only where the threshold window itself needs it.  A host-side selection; applies to batches started afterwards. */
+int  a3_debug_sample_frames(a3_ctx *ctx, int enabled);
 int  a3_debug_discard_too_near(a3_ctx *ctx, const uint32_t *quads_xy, size_t n, float min_distance, uint32_t *out_xy, size_t *n_out);
 
 #ifdef __cplusplus

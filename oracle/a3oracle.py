@@ -173,6 +173,15 @@ def _u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
+def _u8_rows(a):
+    """uint8 with packed pixels inside a row; the rows themselves may lie apart (strides[0] is handed to the C side as it is)"""
+    a = np.asarray(a)
+    packed = (1,) if a.ndim == 2 else (a.shape[2], 1) if a.ndim == 3 else None
+    if a.dtype == np.uint8 and a.strides[1:] == packed and a.strides[0] >= a.shape[1] * a.strides[1]:
+        return a
+    return _u8(a)
+
+
 # ---- numpy-level helpers used by the tests -------------------------------------------
 
 def hamming_distance(a: int, b: int) -> int:
@@ -317,7 +326,7 @@ def detect(img: np.ndarray, codes: np.ndarray, num_bits: int, tau: int, config: 
     """Run the whole restated Detector::detect and return every stage as numpy data.  `quads` (test aid, n x 4 x 2): the candidate
     list handed to discard_too_near / extract_homographies INSTEAD of what the contour stage found (quirk Q4's degenerate quads)."""
     cfg = config or Config.default()
-    img = _u8(img)
+    img = _u8_rows(img)
     h, w = img.shape[:2]
     codes = np.ascontiguousarray(codes, dtype=np.uint64)
     d = Detection()

@@ -7,7 +7,9 @@ implementations and definitions that were NOT written from the same reading of t
   * adaptive_threshold (A2) against a direct window loop;
   * find_contours (A3) against the topology scipy.ndimage.label reports: one outer border per 8-connected foreground component, one
     hole border per 4-connected background component that does not reach the frame, and the union of all border points = the foreground
-    pixels with a background 4-neighbour (images whose foreground keeps off columns 0 and W - 1, where A3's guards do not bite)."""
+    pixels with a background 4-neighbour (images whose foreground keeps off columns 0 and W - 1, where A3's guards do not bite);
+  * warp_into (imageproc, A7) against the plain bilinear sample in float64 of the same f32 inverse map, without the three truncations;
+  * into_luma8 (A1) against the integers of its definition for every RGB triple."""
 import numpy as np
 import pytest
 from scipy import ndimage
@@ -187,3 +189,75 @@ def test_control_point_solve_is_insensitive_to_the_solver(oracle):
     if patch_px:
         assert patch_diff <= patch_px * 0.01, (patch_diff, patch_px)
     print(f"solver sensitivity: {diff_entries}/{entries} f32 entries differ (by {worst_ulp} ulp at most); {patch_diff}/{patch_px} patch pixels differ on a noise image")
+
+
+def _bilinear_f64(img, inv, S):
+    """(values f64 [S, S], inside bool [S, S]): the f32 matrix `inv` applied to the output pixels in f64, imageproc's inside test, and the
+    bilinear sample with nothing truncated"""
+    h, w = img.shape
+    m = np.asarray(inv, dtype=np.float32).astype(np.float64)
+    xs, ys = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64))
+    den = m[6] * xs + m[7] * ys + m[8]
+    px, py = (m[0] * xs + m[1] * ys + m[2]) / den, (m[3] * xs + m[4] * ys + m[5]) / den
+    left, top = np.floor(px), np.floor(py)
+    inside = (left >= 0) & (left + 1 < w) & (top >= 0) & (top + 1 < h)
+    l, t = np.where(inside, left, 0).astype(np.int64), np.where(inside, top, 0).astype(np.int64)
+    rw, bw = px - left, py - top
+    f = img.astype(np.float64)
+    r, b = np.minimum(l + 1, w - 1), np.minimum(t + 1, h - 1)
+    v = (1 - bw) * ((1 - rw) * f[t, l] + rw * f[t, r]) + bw * ((1 - rw) * f[b, l] + rw * f[b, r])
+    return v, inside
+
+
+def test_warp_into_against_a_float64_bilinear_sample(oracle):
+    """imageproc truncates to u8 three times per sample (the two horizontal lerps, then the vertical one): each costs less than a level
+    (row values in (T - 1, T] and (B - 1, B] blend to (V - 1, V], the last truncation gives (V - 2, V]), so the oracle's patch lies within
+    2.0 grey levels of the untruncated value wherever both call the sample inside.  The two can disagree about inside / outside only where
+    the f32 and the f64 evaluation of the map fall on different sides of an edge of the frame: a few pixels in a million at most (none
+    of these 960 400); the cap of 1e-4 is a condition on the inputs, far above that.  The oracle's verdict is read off its patch: 0 is
+    outside, and a sample whose untruncated value is below 2 may be 0 either way."""
+    r = _rng(21)
+    S, w, h = 49, 160, 120
+    noise = r.integers(0, 256, (h, w), dtype=np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    smooth = np.clip(127.5 + 80 * np.sin(xx / 9.0) * np.cos(yy / 13.0) + 40 * np.sin((xx + yy) / 23.0), 0, 255).astype(np.uint8)
+    to = np.array([0, 0, S, 0, S, S, 0, S], np.float32)
+    pixels = disagree = 0
+    worst = 0.0
+    for case in range(400):
+        img = noise if case % 2 == 0 else smooth
+        c = r.uniform([20, 20], [w - 20, h - 20]); side = r.uniform(8, 110); ang = r.uniform(0, 2 * np.pi)
+        base = np.array([[-1, -1], [1, -1], [1, 1], [-1, 1]], float) * side / 2
+        rot = np.array([[np.cos(ang), -np.sin(ang)], [np.sin(ang), np.cos(ang)]])
+        quad = np.clip(np.rint(base @ rot.T * r.uniform(0.6, 1.4, (4, 1)) + c), 0, 65535).astype(np.float32).reshape(8)   # some reach past the frame
+        ok, _, inv = oracle.from_control_points(quad, to)
+        if not ok:
+            continue
+        got = oracle.warp_into(img, inv, S, S).astype(np.float64)
+        ref, inside = _bilinear_f64(img, inv, S)
+        got_inside = got != 0        # (an inside sample of value 0 counts as agreeing with either verdict below)
+        both = inside & got_inside
+        disagree += int((got_inside & ~inside).sum()) + int((inside & ~got_inside & (ref >= 2.0)).sum())
+        pixels += S * S
+        if both.any():
+            worst = max(worst, float(np.abs(got - ref)[both].max()))
+    print(f"warp_into vs float64 bilinear: worst {worst:.3f} levels over {pixels} pixels, inside / outside disagreement {disagree}")
+    assert pixels == 400 * S * S
+    assert worst <= 2.0, worst
+    assert disagree <= pixels * 1e-4, (disagree, pixels)
+
+
+def test_to_luma8_is_the_integer_definition_for_every_rgb_triple(oracle):
+    """L = (2126 R + 7152 G + 722 B) / 10000, truncating, for all 2^24 triples; the same with an alpha byte that must not matter"""
+    g, b = np.meshgrid(np.arange(256, dtype=np.uint32), np.arange(256, dtype=np.uint32), indexing="ij")
+    rng = _rng(5)
+    for r0 in range(0, 256, 16):
+        rgb = np.empty((16 * 256, 256, 3), dtype=np.uint8)
+        rr = np.repeat(np.arange(r0, r0 + 16, dtype=np.uint32), 256)[:, None]
+        rgb[..., 0] = rr
+        rgb[..., 1] = np.tile(g, (16, 1))
+        rgb[..., 2] = np.tile(b, (16, 1))
+        want = ((2126 * rgb[..., 0].astype(np.uint64) + 7152 * rgb[..., 1].astype(np.uint64) + 722 * rgb[..., 2].astype(np.uint64)) // 10000).astype(np.uint8)
+        assert np.array_equal(oracle.to_luma8(rgb), want), r0
+        rgba = np.concatenate([rgb, rng.integers(0, 256, rgb.shape[:2] + (1,), dtype=np.uint8)], axis=2)
+        assert np.array_equal(oracle.to_luma8(rgba), want), r0
