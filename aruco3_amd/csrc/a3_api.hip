@@ -1216,6 +1216,89 @@ int run_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint3
     return finish_batch(ctx, out, poses, out_cap, per_frame_count, out_n);
 }
 
+// a3_calibrate_cameras and a3_calibrate_fisheye_cameras: the same validation and staging.  The fisheye model also checks the guess's
+// coefficients it does not read, and keeps the start's compacted points behind the per-view scratch.  Each message is two whole
+// literals, one per entry point, so the library's read-only data holds every message as it reads.
+int calibrate_impl(a3_ctx* ctx, uint32_t flag_mask, uint32_t guess_flag, bool fisheye, const a3_calib_camera* cams, size_t n_cams,
+                   const uint32_t* view_offsets, size_t n_views, const float* object_xy, const float* image_xy, a3_calib_result* results,
+                   a3_calib_view* views) {
+#define A3_CALIB_FAIL(tail) fail(ctx, A3_ERR_INVALID, fisheye ? "a3_calibrate_fisheye_cameras" tail : "a3_calibrate_cameras" tail)
+    if (!ctx) return A3_ERR_INVALID;
+    if (!cams || !view_offsets || !results) return A3_CALIB_FAIL(": null argument");
+    if (ctx->batch.active || ctx->pending_trivial) return A3_CALIB_FAIL(": a submitted batch has not been collected");
+    if (n_cams == 0 || n_cams > A3_CALIB_MAX_CAMERAS) return A3_CALIB_FAIL(": n_cams must be in 1..A3_CALIB_MAX_CAMERAS");
+    if (n_views == 0 || n_views > A3_CALIB_MAX_CALL_VIEWS) return A3_CALIB_FAIL(": n_views must be in 1..A3_CALIB_MAX_CALL_VIEWS");
+    if (view_offsets[0] != 0) return A3_CALIB_FAIL(": view_offsets[0] must be 0");
+    for (size_t i = 0; i < n_views; i++) {
+        if (view_offsets[i + 1] < view_offsets[i]) return A3_CALIB_FAIL(": view_offsets must not decrease");
+        if (view_offsets[i + 1] - view_offsets[i] > A3_CALIB_MAX_POINTS) return A3_CALIB_FAIL(": a view has more than A3_CALIB_MAX_POINTS points");
+    }
+    const size_t n_pts = view_offsets[n_views];
+    if (n_pts && (!object_xy || !image_xy)) return A3_CALIB_FAIL(": null point array");
+    for (size_t i = 0; i < 2 * n_pts; i++)
+        if (!std::isfinite(object_xy[i]) || !std::isfinite(image_xy[i])) return A3_CALIB_FAIL(": a point is not finite");
+    std::vector<uint8_t> owned(n_views, 0);
+    for (size_t c = 0; c < n_cams; c++) {
+        const a3_calib_camera& cam = cams[c];
+        if (cam.flags & flag_mask) return A3_CALIB_FAIL(": unknown flags");
+        if (cam.image_width == 0 || cam.image_height == 0 || cam.image_width > 65535 || cam.image_height > 65535)
+            return A3_CALIB_FAIL(": image size must be in 1..65535");
+        if (cam.max_iterations > A3_CALIB_MAX_ITERATIONS) return A3_CALIB_FAIL(": max_iterations above A3_CALIB_MAX_ITERATIONS");
+        if (cam.n_views == 0 || cam.n_views > A3_CALIB_MAX_VIEWS) return A3_CALIB_FAIL(": a camera's n_views must be in 1..A3_CALIB_MAX_VIEWS");
+        if ((uint64_t)cam.first_view + cam.n_views > n_views) return A3_CALIB_FAIL(": a camera's views lie past n_views");
+        for (uint32_t v = cam.first_view; v < cam.first_view + cam.n_views; v++) {
+            if (owned[v]) return A3_CALIB_FAIL(": two cameras share a view");
+            owned[v] = 1;
+        }
+        if (cam.flags & guess_flag) {
+            const a3_intrinsics& g = cam.guess;
+            const a3_distortion& d = cam.guess_distortion;
+            const float v[12] = {g.focal_x, g.focal_y, g.principal_x, g.principal_y, d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6};
+            for (float x : v)
+                if (!std::isfinite(x)) return A3_CALIB_FAIL(": the guess is not finite");
+            if (!(g.focal_x > 0.0f) || !(g.focal_y > 0.0f)) return A3_CALIB_FAIL(": the guess's focal lengths must be > 0");
+            if (fisheye && (d.p1 != 0.0f || d.p2 != 0.0f || d.k5 != 0.0f || d.k6 != 0.0f))
+                return A3_CALIB_FAIL(": the guess's lens reads k1 k2 k3 k4; p1, p2, k5 and k6 must be 0");
+        }
+    }
+#undef A3_CALIB_FAIL
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_cams = up(n_cams * sizeof(a3_calib_camera)), b_off = up((n_views + 1) * sizeof(uint32_t)), b_pts = up(n_pts * 2 * sizeof(float));
+    const size_t b_res = up(n_cams * sizeof(a3_calib_result)), b_views = n_views * sizeof(a3_calib_view);
+    const size_t b_blocks = up(n_views * (fisheye ? fisheye_calib_view_bytes() : calib_view_bytes()));
+    A3_HIP(ctx->calib_in.ensure(b_cams + b_off + 2 * b_pts));
+    A3_HIP(ctx->calib_scratch.ensure(b_blocks + (fisheye ? 2 * b_pts : 0)));   // the per-view scratch, then the fisheye start's compacted points
+    A3_HIP(ctx->calib_out.ensure(b_res + b_views));
+    uint8_t* din = ctx->calib_in.as<uint8_t>();
+    uint8_t* dscr = ctx->calib_scratch.as<uint8_t>();
+    uint8_t* dout = ctx->calib_out.as<uint8_t>();
+    A3_HIP(hipMemcpyAsync(din, cams, n_cams * sizeof(a3_calib_camera), hipMemcpyHostToDevice, ctx->stream));
+    A3_HIP(hipMemcpyAsync(din + b_cams, view_offsets, (n_views + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (n_pts) {
+        A3_HIP(hipMemcpyAsync(din + b_cams + b_off, object_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        A3_HIP(hipMemcpyAsync(din + b_cams + b_off + b_pts, image_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    // a view no camera owns is not written by the kernel: it comes back zero, not as what an earlier call left in the buffer
+    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_views, ctx->stream));
+    const a3_calib_camera* dcams = reinterpret_cast<const a3_calib_camera*>(din);
+    const uint32_t* doff = reinterpret_cast<const uint32_t*>(din + b_cams);
+    const float* dobj = reinterpret_cast<const float*>(din + b_cams + b_off);
+    const float* dimg = reinterpret_cast<const float*>(din + b_cams + b_off + b_pts);
+    a3_calib_result* dres = reinterpret_cast<a3_calib_result*>(dout);
+    a3_calib_view* dviews = reinterpret_cast<a3_calib_view*>(dout + b_res);
+    if (fisheye)
+        A3_HIP(launch_calibrate_fisheye(ctx->stream, dcams, (uint32_t)n_cams, doff, dobj, dimg, reinterpret_cast<double*>(dscr),
+                                        reinterpret_cast<float*>(dscr + b_blocks), reinterpret_cast<float*>(dscr + b_blocks + b_pts), dres, dviews));
+    else
+        A3_HIP(launch_calibrate(ctx->stream, dcams, (uint32_t)n_cams, doff, dobj, dimg, reinterpret_cast<double*>(dscr), dres, dviews));
+    A3_HIP(hipMemcpyAsync(results, dout, n_cams * sizeof(a3_calib_result), hipMemcpyDeviceToHost, ctx->stream));
+    if (views) A3_HIP(hipMemcpyAsync(views, dout + b_res, b_views, hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -2465,149 +2548,12 @@ int a3_undistort_points(a3_ctx* ctx, const float* xy, size_t n, const a3_intrins
 
 int a3_calibrate_cameras(a3_ctx* ctx, const a3_calib_camera* cams, size_t n_cams, const uint32_t* view_offsets, size_t n_views,
                          const float* object_xy, const float* image_xy, a3_calib_result* results, a3_calib_view* views) {
-    if (!ctx) return A3_ERR_INVALID;
-    if (!cams || !view_offsets || !results) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: null argument");
-    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a submitted batch has not been collected");
-    if (n_cams == 0 || n_cams > A3_CALIB_MAX_CAMERAS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: n_cams must be in 1..A3_CALIB_MAX_CAMERAS");
-    if (n_views == 0 || n_views > A3_CALIB_MAX_CALL_VIEWS)
-        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: n_views must be in 1..A3_CALIB_MAX_CALL_VIEWS");
-    if (view_offsets[0] != 0) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: view_offsets[0] must be 0");
-    for (size_t i = 0; i < n_views; i++) {
-        if (view_offsets[i + 1] < view_offsets[i]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: view_offsets must not decrease");
-        if (view_offsets[i + 1] - view_offsets[i] > A3_CALIB_MAX_POINTS)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a view has more than A3_CALIB_MAX_POINTS points");
-    }
-    const size_t n_pts = view_offsets[n_views];
-    if (n_pts && (!object_xy || !image_xy)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: null point array");
-    for (size_t i = 0; i < 2 * n_pts; i++)
-        if (!std::isfinite(object_xy[i]) || !std::isfinite(image_xy[i])) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a point is not finite");
-    std::vector<uint8_t> owned(n_views, 0);
-    for (size_t c = 0; c < n_cams; c++) {
-        const a3_calib_camera& cam = cams[c];
-        if (cam.flags & ~31u) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: unknown flags");
-        if (cam.image_width == 0 || cam.image_height == 0 || cam.image_width > 65535 || cam.image_height > 65535)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: image size must be in 1..65535");
-        if (cam.max_iterations > A3_CALIB_MAX_ITERATIONS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: max_iterations above A3_CALIB_MAX_ITERATIONS");
-        if (cam.n_views == 0 || cam.n_views > A3_CALIB_MAX_VIEWS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a camera's n_views must be in 1..A3_CALIB_MAX_VIEWS");
-        if ((uint64_t)cam.first_view + cam.n_views > n_views) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: a camera's views lie past n_views");
-        for (uint32_t v = cam.first_view; v < cam.first_view + cam.n_views; v++) {
-            if (owned[v]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: two cameras share a view");
-            owned[v] = 1;
-        }
-        if (cam.flags & A3_CALIB_USE_INTRINSIC_GUESS) {
-            const a3_intrinsics& g = cam.guess;
-            const a3_distortion& d = cam.guess_distortion;
-            const float v[12] = {g.focal_x, g.focal_y, g.principal_x, g.principal_y, d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6};
-            for (float x : v)
-                if (!std::isfinite(x)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: the guess is not finite");
-            if (!(g.focal_x > 0.0f) || !(g.focal_y > 0.0f)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_cameras: the guess's focal lengths must be > 0");
-        }
-    }
-    A3_HIP(hipSetDevice(ctx->device));
-    if (int rcs_ = need_stream(ctx)) return rcs_;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_cams = up(n_cams * sizeof(a3_calib_camera)), b_off = up((n_views + 1) * sizeof(uint32_t)), b_pts = up(n_pts * 2 * sizeof(float));
-    const size_t b_res = up(n_cams * sizeof(a3_calib_result)), b_views = n_views * sizeof(a3_calib_view);
-    A3_HIP(ctx->calib_in.ensure(b_cams + b_off + 2 * b_pts));
-    A3_HIP(ctx->calib_scratch.ensure(n_views * calib_view_bytes()));
-    A3_HIP(ctx->calib_out.ensure(b_res + b_views));
-    uint8_t* din = ctx->calib_in.as<uint8_t>();
-    uint8_t* dout = ctx->calib_out.as<uint8_t>();
-    A3_HIP(hipMemcpyAsync(din, cams, n_cams * sizeof(a3_calib_camera), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_cams, view_offsets, (n_views + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (n_pts) {
-        A3_HIP(hipMemcpyAsync(din + b_cams + b_off, object_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        A3_HIP(hipMemcpyAsync(din + b_cams + b_off + b_pts, image_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    // a view no camera owns is not written by the kernel: it comes back zero, not as what an earlier call left in the buffer
-    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_views, ctx->stream));
-    A3_HIP(launch_calibrate(ctx->stream, reinterpret_cast<const a3_calib_camera*>(din), (uint32_t)n_cams, reinterpret_cast<const uint32_t*>(din + b_cams),
-                            reinterpret_cast<const float*>(din + b_cams + b_off), reinterpret_cast<const float*>(din + b_cams + b_off + b_pts),
-                            ctx->calib_scratch.as<double>(), reinterpret_cast<a3_calib_result*>(dout), reinterpret_cast<a3_calib_view*>(dout + b_res)));
-    A3_HIP(hipMemcpyAsync(results, dout, n_cams * sizeof(a3_calib_result), hipMemcpyDeviceToHost, ctx->stream));
-    if (views) A3_HIP(hipMemcpyAsync(views, dout + b_res, b_views, hipMemcpyDeviceToHost, ctx->stream));
-    A3_HIP(hipStreamSynchronize(ctx->stream));
-    return A3_OK;
+    return calibrate_impl(ctx, ~31u, A3_CALIB_USE_INTRINSIC_GUESS, false, cams, n_cams, view_offsets, n_views, object_xy, image_xy, results, views);
 }
 
 int a3_calibrate_fisheye_cameras(a3_ctx* ctx, const a3_calib_camera* cams, size_t n_cams, const uint32_t* view_offsets, size_t n_views,
                                  const float* object_xy, const float* image_xy, a3_calib_result* results, a3_calib_view* views) {
-    if (!ctx) return A3_ERR_INVALID;
-    if (!cams || !view_offsets || !results) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: null argument");
-    if (ctx->batch.active || ctx->pending_trivial)
-        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: a submitted batch has not been collected");
-    if (n_cams == 0 || n_cams > A3_CALIB_MAX_CAMERAS)
-        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: n_cams must be in 1..A3_CALIB_MAX_CAMERAS");
-    if (n_views == 0 || n_views > A3_CALIB_MAX_CALL_VIEWS)
-        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: n_views must be in 1..A3_CALIB_MAX_CALL_VIEWS");
-    if (view_offsets[0] != 0) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: view_offsets[0] must be 0");
-    for (size_t i = 0; i < n_views; i++) {
-        if (view_offsets[i + 1] < view_offsets[i]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: view_offsets must not decrease");
-        if (view_offsets[i + 1] - view_offsets[i] > A3_CALIB_MAX_POINTS)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: a view has more than A3_CALIB_MAX_POINTS points");
-    }
-    const size_t n_pts = view_offsets[n_views];
-    if (n_pts && (!object_xy || !image_xy)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: null point array");
-    for (size_t i = 0; i < 2 * n_pts; i++)
-        if (!std::isfinite(object_xy[i]) || !std::isfinite(image_xy[i]))
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: a point is not finite");
-    std::vector<uint8_t> owned(n_views, 0);
-    for (size_t c = 0; c < n_cams; c++) {
-        const a3_calib_camera& cam = cams[c];
-        if (cam.flags & ~63u) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: unknown flags");
-        if (cam.image_width == 0 || cam.image_height == 0 || cam.image_width > 65535 || cam.image_height > 65535)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: image size must be in 1..65535");
-        if (cam.max_iterations > A3_CALIB_MAX_ITERATIONS)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: max_iterations above A3_CALIB_MAX_ITERATIONS");
-        if (cam.n_views == 0 || cam.n_views > A3_CALIB_MAX_VIEWS)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: a camera's n_views must be in 1..A3_CALIB_MAX_VIEWS");
-        if ((uint64_t)cam.first_view + cam.n_views > n_views)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: a camera's views lie past n_views");
-        for (uint32_t v = cam.first_view; v < cam.first_view + cam.n_views; v++) {
-            if (owned[v]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: two cameras share a view");
-            owned[v] = 1;
-        }
-        if (cam.flags & A3_FISHEYE_USE_INTRINSIC_GUESS) {
-            const a3_intrinsics& g = cam.guess;
-            const a3_distortion& d = cam.guess_distortion;
-            const float v[12] = {g.focal_x, g.focal_y, g.principal_x, g.principal_y, d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6};
-            for (float x : v)
-                if (!std::isfinite(x)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: the guess is not finite");
-            if (!(g.focal_x > 0.0f) || !(g.focal_y > 0.0f))
-                return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: the guess's focal lengths must be > 0");
-            if (d.p1 != 0.0f || d.p2 != 0.0f || d.k5 != 0.0f || d.k6 != 0.0f)
-                return fail(ctx, A3_ERR_INVALID, "a3_calibrate_fisheye_cameras: the guess's lens reads k1 k2 k3 k4; p1, p2, k5 and k6 must be 0");
-        }
-    }
-    A3_HIP(hipSetDevice(ctx->device));
-    if (int rcs_ = need_stream(ctx)) return rcs_;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_cams = up(n_cams * sizeof(a3_calib_camera)), b_off = up((n_views + 1) * sizeof(uint32_t)), b_pts = up(n_pts * 2 * sizeof(float));
-    const size_t b_res = up(n_cams * sizeof(a3_calib_result)), b_views = n_views * sizeof(a3_calib_view);
-    const size_t b_blocks = up(n_views * fisheye_calib_view_bytes());
-    A3_HIP(ctx->calib_in.ensure(b_cams + b_off + 2 * b_pts));
-    A3_HIP(ctx->calib_scratch.ensure(b_blocks + 2 * b_pts));   // the per-view scratch, then the start's compacted points
-    A3_HIP(ctx->calib_out.ensure(b_res + b_views));
-    uint8_t* din = ctx->calib_in.as<uint8_t>();
-    uint8_t* dscr = ctx->calib_scratch.as<uint8_t>();
-    uint8_t* dout = ctx->calib_out.as<uint8_t>();
-    A3_HIP(hipMemcpyAsync(din, cams, n_cams * sizeof(a3_calib_camera), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_cams, view_offsets, (n_views + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (n_pts) {
-        A3_HIP(hipMemcpyAsync(din + b_cams + b_off, object_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        A3_HIP(hipMemcpyAsync(din + b_cams + b_off + b_pts, image_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
-    // a view no camera owns is not written by the kernel: it comes back zero, not as what an earlier call left in the buffer
-    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_views, ctx->stream));
-    A3_HIP(launch_calibrate_fisheye(ctx->stream, reinterpret_cast<const a3_calib_camera*>(din), (uint32_t)n_cams,
-                                    reinterpret_cast<const uint32_t*>(din + b_cams), reinterpret_cast<const float*>(din + b_cams + b_off),
-                                    reinterpret_cast<const float*>(din + b_cams + b_off + b_pts), reinterpret_cast<double*>(dscr),
-                                    reinterpret_cast<float*>(dscr + b_blocks), reinterpret_cast<float*>(dscr + b_blocks + b_pts),
-                                    reinterpret_cast<a3_calib_result*>(dout), reinterpret_cast<a3_calib_view*>(dout + b_res)));
-    A3_HIP(hipMemcpyAsync(results, dout, n_cams * sizeof(a3_calib_result), hipMemcpyDeviceToHost, ctx->stream));
-    if (views) A3_HIP(hipMemcpyAsync(views, dout + b_res, b_views, hipMemcpyDeviceToHost, ctx->stream));
-    A3_HIP(hipStreamSynchronize(ctx->stream));
-    return A3_OK;
+    return calibrate_impl(ctx, ~63u, A3_FISHEYE_USE_INTRINSIC_GUESS, true, cams, n_cams, view_offsets, n_views, object_xy, image_xy, results, views);
 }
 
 int a3_calibrate_rigs(a3_ctx* ctx, const a3_rig* rigs, size_t n_rigs, const a3_rig_camera* cameras, size_t n_cameras, const a3_rig_observation* obs,

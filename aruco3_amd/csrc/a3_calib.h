@@ -1,10 +1,10 @@
 // a3_calib.h -- the per-point and per-view pieces of the camera calibration of include/aruco3_hip.h (a3_calibrate_cameras): the
-// projection with its 18 Jacobian columns, the homography rows and the wave-level homography, the 6 x 6 and n x n LDL^T and the Cayley
-// update, all in f64.  k_calibrate (k_calib.hip) and k_rig (k_rig.hip, a3_calibrate_rigs) use them.  Every expression is written in the contract's order and tests/calib_oracle.c restates each one
-// in the same order; the library is built with -ffp-contract=off, so nothing is fused.
+// projection with its 18 Jacobian columns, the homography rows and the wave-level homography, all in f64, on top of
+// the shared solver pieces of a3_solve.h.  k_calibrate (k_calib.hip) uses them, and through a3_rig.h k_rig, k_map and k_handeye.  Every
+// expression is written in the contract's order and tests/calib_oracle.c restates each one in the same order; the library is built
+// with -ffp-contract=off, so nothing is fused.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cstdint>
+#include "a3_solve.h"
 
 namespace a3 {
 
@@ -12,19 +12,6 @@ constexpr int kCalAug = 19;        // 18 Jacobian columns (12 intrinsics, then w
 constexpr int kCalEntries = 190;   // upper triangle of the 19 x 19 augmented sum
 constexpr int kHomAug = 9;         // 8 homography columns + the right-hand side
 constexpr int kHomEntries = 45;
-
-// index of (i, k), i <= k, in the row-by-row upper triangle of an n x n matrix
-__device__ __forceinline__ int tri_index(int i, int k, int n) { return i * n - (i * (i - 1)) / 2 + (k - i); }
-
-// (i, k) of entry e of that triangle
-__device__ __forceinline__ void tri_ik(int e, int n, int* i, int* k) {
-    int r = 0;
-    while (e >= n - r) { e -= n - r; r++; }
-    *i = r;
-    *k = r + e;
-}
-
-__device__ __forceinline__ bool fin(double v) { return v - v == 0.0; }
 
 // the two augmented rows of one point: intrinsics a (fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6), pose (R, t), board point (X, Y, 0) seen at
 // (ou, ov).  au / av: 19 values each (columns 0-11 intrinsics, 12-14 w, 15-17 t, 18 the residual).
@@ -81,77 +68,6 @@ __device__ __forceinline__ void hom_row(double X, double Y, double U, double V, 
     au[0] = X;   au[1] = Y;   au[2] = 1.0; au[3] = 0.0; au[4] = 0.0; au[5] = 0.0; au[6] = -(U * X); au[7] = -(U * Y); au[8] = U;
     av[0] = 0.0; av[1] = 0.0; av[2] = 0.0; av[3] = X;   av[4] = Y;   av[5] = 1.0; av[6] = -(V * X); av[7] = -(V * Y); av[8] = V;
 }
-
-// LDL^T of V + lambda diag(V), V the 6 x 6 block at columns OFF .. OFF + 5 of the upper triangle of an AUG x AUG sum: L below the
-// diagonal, D; false on a pivot that is not positive and finite
-template <int OFF, int AUG>
-__device__ __forceinline__ bool ldl6_at(const double* blk, double lambda, double L[6][6], double D[6]) {
-    double A[6][6];
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-        for (int c = r; c < 6; c++) { const double v = blk[tri_index(OFF + r, OFF + c, AUG)]; A[r][c] = v; A[c][r] = v; }
-#pragma unroll
-    for (int r = 0; r < 6; r++) A[r][r] = A[r][r] + lambda * A[r][r];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-#pragma unroll
-        for (int i = j; i < 6; i++) {
-            double s = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s = s - L[i][k] * L[j][k] * D[k];
-            if (i == j) {
-                ok = ok && s > 0.0 && fin(s);
-                D[j] = s;
-                L[j][j] = 1.0;
-            } else L[i][j] = s / D[j];
-        }
-    }
-    return ok;
-}
-
-// the pose block of a view's 190 entries
-__device__ __forceinline__ bool ldl6(const double* blk, double lambda, double L[6][6], double D[6]) { return ldl6_at<12, kCalAug>(blk, lambda, L, D); }
-
-__device__ __forceinline__ void ldl6_solve(const double L[6][6], const double D[6], const double b[6], double x[6]) {
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double s = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s = s - L[i][k] * y[k];
-        y[i] = s;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double s = y[i] / D[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) s = s - L[k][i] * x[k];
-        x[i] = s;
-    }
-}
-
-// R <- cay(w) R, the board pose's update in f64
-__device__ __forceinline__ void cayley_d(const double w[3], const double R[9], double Rn[9]) {
-    const double n2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-    const double k = 2.0 / (1.0 + n2);
-    const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-    double C[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const double w2 = w[r] * w[c] - (r == c ? n2 : 0.0);
-            C[3 * r + c] = (r == c ? 1.0 : 0.0) + k * (W[3 * r + c] + w2);
-        }
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) Rn[3 * r + c] = (C[3 * r] * R[c] + C[3 * r + 1] * R[3 + c]) + C[3 * r + 2] * R[6 + c];
-}
-
-__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
 // step 1 for one view with >= 4 points (wave-level): -> whether the homography (row-major, H22 = 1) was written to H
 __device__ inline bool view_homography(const float* __restrict__ obj, const float* __restrict__ img, uint32_t p0, uint32_t np, double* rows, double* wv,
@@ -263,35 +179,6 @@ __device__ inline bool view_homography(const float* __restrict__ obj, const floa
     }
     wave_sync();
     return wv[6] != 0.0;
-}
-
-// LDL^T of the n x n matrix in A (row stride S, lower triangle read), L written below the diagonal; false on a bad pivot
-template <int S>
-__device__ inline bool ldl_n(double* A, int n, double* D) {
-    for (int j = 0; j < n; j++)
-        for (int i = j; i < n; i++) {
-            double s = A[i * S + j];
-            for (int k = 0; k < j; k++) s = s - A[i * S + k] * A[j * S + k] * D[k];
-            if (i == j) {
-                if (!(s > 0.0) || !fin(s)) return false;
-                D[j] = s;
-            } else A[i * S + j] = s / D[j];
-        }
-    return true;
-}
-
-template <int S>
-__device__ inline void ldl_n_solve(const double* A, int n, const double* D, const double* b, double* x) {
-    for (int i = 0; i < n; i++) {
-        double s = b[i];
-        for (int k = 0; k < i; k++) s = s - A[i * S + k] * x[k];
-        x[i] = s;
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double s = x[i] / D[i];
-        for (int k = i + 1; k < n; k++) s = s - A[k * S + i] * x[k];
-        x[i] = s;
-    }
 }
 
 }  // namespace a3

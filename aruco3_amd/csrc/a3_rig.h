@@ -11,7 +11,7 @@ constexpr int kRigAug = 13;       // (w, t) of the extrinsics, (w, t) of the fra
 constexpr int kRigEntries = 91;   // upper triangle of the 13 x 13 augmented sum
 constexpr int kRigFrameTri = 63;  // its rows 6 .. 12 are the 7-triangle (V_f, g_f, cost) of the frame columns: entries 63 .. 90
 
-// poses are 12 doubles: R (9, row-major), t (3).  O = A . B
+// poses are 12 doubles: R (9, row-major), t (3); pose_update is in a3_solve.h.  O = A . B
 __device__ __forceinline__ void pose_mul(const double* A, const double* B, double* O) {
 #pragma unroll
     for (int r = 0; r < 3; r++) {
@@ -28,13 +28,6 @@ __device__ __forceinline__ void pose_inv(const double* A, double* O) {
         for (int c = 0; c < 3; c++) O[3 * r + c] = A[3 * c + r];
         O[9 + r] = -((A[r] * A[9] + A[3 + r] * A[10]) + A[6 + r] * A[11]);
     }
-}
-
-// R <- cay(w) R, t <- t + dt
-__device__ __forceinline__ void pose_update(const double* T, const double d[6], double* Tn) {
-    cayley_d(d, T, Tn);
-#pragma unroll
-    for (int q = 0; q < 3; q++) Tn[9 + q] = T[9 + q] + d[3 + q];
 }
 
 __device__ __forceinline__ void rig_cols(const double u[3], const double* Rc, const double qc[3], const double qf[3], double res, double* o) {

@@ -6,7 +6,8 @@
 // ...).  A view's sums run in point order: the lanes write the augmented rows of up to 64 points into the wave's LDS, then each lane owns
 // up to three of the 190 block entries and adds the rows in order -- deterministic sums with three accumulators per lane instead of 190.
 // Camera-level sums run over the views in view order, one lane of wave 0 per entry; the <= 12 x 12 Schur system is solved by one lane.
-// Per-view blocks, poses and Schur terms live in a device scratch buffer of kCalViewDoubles per view.
+// Per-view blocks, poses and Schur terms live in a device scratch buffer of kCalViewDoubles per view.  The block accumulator
+// (aug_block), the pose start (pose_from_h) and the small solves are a3_solve.h's, shared with the other solver kernels.
 #include <cmath>
 
 #include "a3_common.h"
@@ -39,41 +40,11 @@ __device__ __forceinline__ bool cal_free(uint32_t flags, int i) {
     return true;
 }
 
-// one view's 190 block entries at (a, R, t) -> out (wave-level).  Inlined: a, R and t stay in registers (a call would pass them
-// through scratch memory).
+// one view's 190 block entries at (a, R, t) -> out (wave-level): aug_block (a3_solve.h) over calib_row
 __device__ __forceinline__ void view_block(const double a[12], const double R[9], const double t[3], const float* __restrict__ obj, const float* __restrict__ img,
                            uint32_t p0, uint32_t np, double* rows, int lane, double* out) {
-    int ei[3], ek[3];
-    double acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        ei[q] = 0;
-        ek[q] = 0;
-        if (lane + 64 * q < kCalEntries) tri_ik(lane + 64 * q, kCalAug, &ei[q], &ek[q]);
-    }
-    for (uint32_t c0 = 0; c0 < np; c0 += 64) {
-        const uint32_t cnt = min(64u, np - c0);
-        if ((uint32_t)lane < cnt) {
-            const size_t p = (size_t)p0 + c0 + (uint32_t)lane;
-            calib_row(a, R, t, (double)obj[2 * p], (double)obj[2 * p + 1], (double)img[2 * p], (double)img[2 * p + 1], rows + lane * kRowStride,
-                      rows + lane * kRowStride + kCalAug);
-        }
-        wave_sync();
-        for (uint32_t j = 0; j < cnt; j++) {
-            const double* u = rows + j * kRowStride;
-            const double* v = u + kCalAug;
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                acc[q] = acc[q] + u[ei[q]] * u[ek[q]];
-                acc[q] = acc[q] + v[ei[q]] * v[ek[q]];
-            }
-        }
-        wave_sync();
-    }
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-        if (lane + 64 * q < kCalEntries) out[lane + 64 * q] = acc[q];
-    wave_sync();
+    aug_block<kCalAug>([&](double X, double Y, double ou, double ov, double* au, double* av) { calib_row(a, R, t, X, Y, ou, ov, au, av); }, obj, img, p0,
+                       np, rows, lane, out);
 }
 
 // step 4's per-view Schur terms at `lambda` from block slot `slot` (wave-level, every USED view of the wave); a bad pivot sets *bad
@@ -86,7 +57,7 @@ __device__ void schur_terms(const CalibArgs& g, uint32_t v0, uint32_t nv, int sl
         double* sv = g.scratch + (size_t)v * kCalViewDoubles;
         const double* blk = sv + kOffBlk + slot * kCalEntries;
         double L[6][6], D[6];
-        if (!ldl6(blk, lambda, L, D)) {
+        if (!ldl6_at<12, kCalAug>(blk, lambda, L, D)) {
             if (lane == 0) *bad = 1;
             continue;
         }
@@ -247,22 +218,14 @@ __global__ __launch_bounds__(kCalThreads) void k_calibrate(CalibArgs g) {
             const uint32_t p0 = g.view_off[v], np = g.view_off[v + 1] - p0;
             double* sv = g.scratch + (size_t)v * kCalViewDoubles;
             const double* H = sv + kOffH;
-            double m[3][3];
+            double m[3][3], R[9], t[3];
             for (int c = 0; c < 3; c++) {
                 m[c][0] = (H[c] - a[2] * H[6 + c]) / a[0];
                 m[c][1] = (H[3 + c] - a[3] * H[6 + c]) / a[1];
                 m[c][2] = H[6 + c];
             }
-            const double n0 = sqrt((m[0][0] * m[0][0] + m[0][1] * m[0][1]) + m[0][2] * m[0][2]);
-            const double r00 = m[0][0] / n0, r01 = m[0][1] / n0, r02 = m[0][2] / n0;
-            const double dd = (r00 * m[1][0] + r01 * m[1][1]) + r02 * m[1][2];
-            const double e0 = m[1][0] - dd * r00, e1 = m[1][1] - dd * r01, e2 = m[1][2] - dd * r02;
-            const double ne = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-            const double r10 = e0 / ne, r11 = e1 / ne, r12 = e2 / ne;
-            const double n1 = sqrt((m[1][0] * m[1][0] + m[1][1] * m[1][1]) + m[1][2] * m[1][2]);
-            const double den = n0 + n1;
-            double R[9] = {r00, r10, r01 * r12 - r02 * r11, r01, r11, r02 * r10 - r00 * r12, r02, r12, r00 * r11 - r01 * r10};
-            double t[3] = {(2.0 * m[2][0]) / den, (2.0 * m[2][1]) / den, (2.0 * m[2][2]) / den};
+            pose_from_h(m, R, t);
+            // (the pose-only LM loop stays this kernel's own: behind a shared function it compiles to other code)
             double* cur = sv + kOffBlk;
             double* oth = cur + kCalEntries;
             view_block(a, R, t, g.obj, g.img, p0, np, rows, lane, cur);
@@ -271,7 +234,7 @@ __global__ __launch_bounds__(kCalThreads) void k_calibrate(CalibArgs g) {
             double lambda = 1e-3;
             while (evals < A3_CALIB_POSE_EVALS && cost > 0.0) {
                 double L[6][6], D[6];
-                if (!ldl6(cur, lambda, L, D)) { lambda = lambda * 10.0; evals++; continue; }
+                if (!ldl6_at<12, kCalAug>(cur, lambda, L, D)) { lambda = lambda * 10.0; evals++; continue; }
                 double b[6], d[6];
 #pragma unroll
                 for (int q = 0; q < 6; q++) b[q] = -cur[tri_index(12 + q, 18, kCalAug)];
@@ -361,7 +324,7 @@ __global__ __launch_bounds__(kCalThreads) void k_calibrate(CalibArgs g) {
                 double* sv = g.scratch + (size_t)v * kCalViewDoubles;
                 const double* blk = sv + kOffBlk + cur * kCalEntries;
                 double L[6][6], D[6];
-                ldl6(blk, lambda, L, D);
+                ldl6_at<12, kCalAug>(blk, lambda, L, D);
                 double b[6], d[6];
 #pragma unroll
                 for (int q = 0; q < 6; q++) {

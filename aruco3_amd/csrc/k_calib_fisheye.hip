@@ -8,7 +8,8 @@
 // a view's image points a lane each and compacts the kept ones in point order (a ballot and a prefix count) into a device scratch of 4
 // floats per point, which view_homography (a3_calib.h) reads as it reads the caller's arrays.  Camera-level sums run over the views in
 // view order, one lane of wave 0 per entry; the <= 8 x 8 Schur system is solved by one lane.  Per-view blocks, poses and Schur terms
-// live in a device scratch buffer of kFeViewDoubles per view.
+// live in a device scratch buffer of kFeViewDoubles per view.  The block accumulator (aug_block), the pose start (pose_from_h) and the
+// small solves are a3_solve.h's, shared with the other solver kernels.
 #include <cmath>
 
 #include "a3_common.h"
@@ -49,41 +50,11 @@ __device__ __forceinline__ bool fe_ldl6(const double* blk, double lambda, double
     return ldl6_at<kFePose, kFeAug>(blk, lambda, L, D);
 }
 
-// one view's 120 block entries at (a, R, t) -> out (wave-level).  Inlined: a, R and t stay in registers (a call would pass them
-// through scratch memory).
+// one view's 120 block entries at (a, R, t) -> out (wave-level): aug_block (a3_solve.h) over fisheye_row
 __device__ __forceinline__ void fe_view_block(const double a[8], const double R[9], const double t[3], const float* __restrict__ obj,
                                               const float* __restrict__ img, uint32_t p0, uint32_t np, double* rows, int lane, double* out) {
-    int ei[2], ek[2];
-    double acc[2] = {0.0, 0.0};
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        ei[q] = 0;
-        ek[q] = 0;
-        if (lane + 64 * q < kFeEntries) tri_ik(lane + 64 * q, kFeAug, &ei[q], &ek[q]);
-    }
-    for (uint32_t c0 = 0; c0 < np; c0 += 64) {
-        const uint32_t cnt = min(64u, np - c0);
-        if ((uint32_t)lane < cnt) {
-            const size_t p = (size_t)p0 + c0 + (uint32_t)lane;
-            fisheye_row(a, R, t, (double)obj[2 * p], (double)obj[2 * p + 1], (double)img[2 * p], (double)img[2 * p + 1], rows + lane * kFeRowStride,
-                        rows + lane * kFeRowStride + kFeAug);
-        }
-        wave_sync();
-        for (uint32_t j = 0; j < cnt; j++) {
-            const double* u = rows + j * kFeRowStride;
-            const double* v = u + kFeAug;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                acc[q] = acc[q] + u[ei[q]] * u[ek[q]];
-                acc[q] = acc[q] + v[ei[q]] * v[ek[q]];
-            }
-        }
-        wave_sync();
-    }
-#pragma unroll
-    for (int q = 0; q < 2; q++)
-        if (lane + 64 * q < kFeEntries) out[lane + 64 * q] = acc[q];
-    wave_sync();
+    aug_block<kFeAug>([&](double X, double Y, double ou, double ov, double* au, double* av) { fisheye_row(a, R, t, X, Y, ou, ov, au, av); }, obj, img,
+                      p0, np, rows, lane, out);
 }
 
 // step 2's kept points of one view, compacted in point order into start_obj / start_img at the view's own offset (wave-level) -> how many
@@ -261,19 +232,11 @@ __global__ __launch_bounds__(kFeThreads) void k_calibrate_fisheye(FisheyeCalibAr
             if (g.views[v].status != A3_CALIB_VIEW_USED) continue;
             const uint32_t p0 = g.view_off[v], np = g.view_off[v + 1] - p0;
             double* sv = g.scratch + (size_t)v * kFeViewDoubles;
-            const double* H = sv + kFeOffH;
-            double m[3][3];
+            const double* H = sv + kFeOffH;   // board -> normalised plane, taken as it is
+            double m[3][3], R[9], t[3];
             for (int c = 0; c < 3; c++) { m[c][0] = H[c]; m[c][1] = H[3 + c]; m[c][2] = H[6 + c]; }
-            const double n0 = sqrt((m[0][0] * m[0][0] + m[0][1] * m[0][1]) + m[0][2] * m[0][2]);
-            const double r00 = m[0][0] / n0, r01 = m[0][1] / n0, r02 = m[0][2] / n0;
-            const double dd = (r00 * m[1][0] + r01 * m[1][1]) + r02 * m[1][2];
-            const double e0 = m[1][0] - dd * r00, e1 = m[1][1] - dd * r01, e2 = m[1][2] - dd * r02;
-            const double ne = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-            const double r10 = e0 / ne, r11 = e1 / ne, r12 = e2 / ne;
-            const double n1 = sqrt((m[1][0] * m[1][0] + m[1][1] * m[1][1]) + m[1][2] * m[1][2]);
-            const double den = n0 + n1;
-            double R[9] = {r00, r10, r01 * r12 - r02 * r11, r01, r11, r02 * r10 - r00 * r12, r02, r12, r00 * r11 - r01 * r10};
-            double t[3] = {(2.0 * m[2][0]) / den, (2.0 * m[2][1]) / den, (2.0 * m[2][2]) / den};
+            pose_from_h(m, R, t);
+            // (the pose-only LM loop stays this kernel's own: behind a shared function it compiles to other code)
             double* cur = sv + kFeOffBlk;
             double* oth = cur + kFeEntries;
             fe_view_block(a, R, t, g.obj, g.img, p0, np, rows, lane, cur);

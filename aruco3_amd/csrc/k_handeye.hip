@@ -5,7 +5,7 @@
 // One workgroup of four waves per problem, on the structure of k_rig; every phase runs inside the one launch, separated by barriers.
 // Per-frame work (step 1's homography and pose LM, every evaluation of a frame's 91-entry block) goes to one wave (frames w, w + 4,
 // ...): the lanes write the rows of up to 64 points into the wave's LDS, then each lane owns up to two of the 91 entries and adds the
-// rows in point order.  The start's pair sums take one thread per frame i (the partial over j > i in order), thread 0 adds the
+// rows in point order (aug_block, a3_solve.h; step 1's pose start is its pose_from_h).  The start's pair sums take one thread per frame i (the partial over j > i in order), thread 0 adds the
 // partials in i order and solves the charts and the translation.  The 91 sums over the frames take one thread each, in frame order;
 // the damped 12 x 12 system, its LDL^T and the covariance are thread 0's.  Blocks, step 1's poses and the pair partials live in device
 // scratch, kHeFrameDoubles per frame.  A shared flag is read into a register and a barrier passed before thread 0 may change it, so
@@ -36,43 +36,6 @@ struct HeArgs {
     a3_handeye_frame_result* fres;
 };
 
-// the 91 block entries of one frame's points -> out (wave-level); row(X, Y, u, v, au, av) writes a point's two rows of 13
-template <class Row>
-__device__ __forceinline__ void he_block(Row row, const float* __restrict__ obj, const float* __restrict__ img, uint32_t p0, uint32_t np, double* rows,
-                                         int lane, double* out) {
-    int ei[2], ek[2];
-    double acc[2] = {0.0, 0.0};
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        ei[q] = 0;
-        ek[q] = 0;
-        if (lane + 64 * q < kRigEntries) tri_ik(lane + 64 * q, kRigAug, &ei[q], &ek[q]);
-    }
-    for (uint32_t c0 = 0; c0 < np; c0 += 64) {
-        const uint32_t cnt = min(64u, np - c0);
-        if ((uint32_t)lane < cnt) {
-            const size_t p = (size_t)p0 + c0 + (uint32_t)lane;
-            row((double)obj[2 * p], (double)obj[2 * p + 1], (double)img[2 * p], (double)img[2 * p + 1], rows + lane * kHeRowStride,
-                rows + lane * kHeRowStride + kRigAug);
-        }
-        wave_sync();
-        for (uint32_t j = 0; j < cnt; j++) {
-            const double* u = rows + j * kHeRowStride;
-            const double* v = u + kRigAug;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                acc[q] = acc[q] + u[ei[q]] * u[ek[q]];
-                acc[q] = acc[q] + v[ei[q]] * v[ek[q]];
-            }
-        }
-        wave_sync();
-    }
-#pragma unroll
-    for (int q = 0; q < 2; q++)
-        if (lane + 64 * q < kRigEntries) out[lane + 64 * q] = acc[q];
-    wave_sync();
-}
-
 __device__ __forceinline__ void frame_pose(const a3_handeye_frame* fr, double* M) {
 #pragma unroll
     for (int q = 0; q < 9; q++) M[q] = fr->rotation[q];
@@ -92,7 +55,7 @@ __device__ __forceinline__ void frames_eval(const HeArgs& g, uint32_t f0, uint32
         frame_pose(&g.frames[f], M);
         pose_mul(X, M, Ep);
         pose_mul(Ep, Y, G);
-        he_block([&](double Xc, double Yc, double ou, double ov, double* au, double* av) { he_row(a, X, M, Y, Ep, G, Xc, Yc, ou, ov, au, av); }, g.obj,
+        aug_block<kRigAug>([&](double Xc, double Yc, double ou, double ov, double* au, double* av) { he_row(a, X, M, Y, Ep, G, Xc, Yc, ou, ov, au, av); }, g.obj,
                  g.img, g.frames[f].first_point, g.frames[f].n_points, rows, lane, g.fscr + (size_t)f * kHeFrameDoubles + kHeBlk + slot * kRigEntries);
     }
 }
@@ -156,28 +119,20 @@ __global__ __launch_bounds__(kHeThreads) void k_handeye(HeArgs g) {
 #pragma unroll
         for (int q = 0; q < 12; q++) a[q] = s_a[q];
         const double* H = os + kHeP;
-        double m[3][3];
+        double m[3][3], T[12];
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             m[c][0] = (H[c] - a[2] * H[6 + c]) / a[0];
             m[c][1] = (H[3 + c] - a[3] * H[6 + c]) / a[1];
             m[c][2] = H[6 + c];
         }
-        const double n0 = sqrt((m[0][0] * m[0][0] + m[0][1] * m[0][1]) + m[0][2] * m[0][2]);
-        const double r00 = m[0][0] / n0, r01 = m[0][1] / n0, r02 = m[0][2] / n0;
-        const double dd = (r00 * m[1][0] + r01 * m[1][1]) + r02 * m[1][2];
-        const double e0 = m[1][0] - dd * r00, e1 = m[1][1] - dd * r01, e2 = m[1][2] - dd * r02;
-        const double ne = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-        const double r10 = e0 / ne, r11 = e1 / ne, r12 = e2 / ne;
-        const double n1 = sqrt((m[1][0] * m[1][0] + m[1][1] * m[1][1]) + m[1][2] * m[1][2]);
-        const double den = n0 + n1;
-        double T[12] = {r00, r10, r01 * r12 - r02 * r11, r01, r11, r02 * r10 - r00 * r12, r02, r12, r00 * r11 - r01 * r10,
-                        (2.0 * m[2][0]) / den, (2.0 * m[2][1]) / den, (2.0 * m[2][2]) / den};
+        pose_from_h(m, T, T + 9);
         const double ID[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
         wave_sync();   // (every lane has read H before the blocks and P go over this scratch)
+        // (the pose-only LM loop stays this kernel's own: behind a shared function it compiles to other code)
         double* cur = os + kHeBlk;
         double* oth = cur + kRigEntries;
-        he_block([&](double Xc, double Yc, double ou, double ov, double* au, double* av) { rig_row(a, ID, T, T, Xc, Yc, ou, ov, au, av); }, g.obj, g.img,
+        aug_block<kRigAug>([&](double Xc, double Yc, double ou, double ov, double* au, double* av) { rig_row(a, ID, T, T, Xc, Yc, ou, ov, au, av); }, g.obj, g.img,
                  p0, np, rows, lane, cur);
         double cost = cur[kRigEntries - 1];
         int evals = 1;
@@ -190,7 +145,7 @@ __global__ __launch_bounds__(kHeThreads) void k_handeye(HeArgs g) {
             for (int q = 0; q < 6; q++) b[q] = -cur[tri_index(6 + q, 12, kRigAug)];
             ldl6_solve(L, D, b, d);
             pose_update(T, d, Tn);
-            he_block([&](double Xc, double Yc, double ou, double ov, double* au, double* av) { rig_row(a, ID, Tn, Tn, Xc, Yc, ou, ov, au, av); }, g.obj,
+            aug_block<kRigAug>([&](double Xc, double Yc, double ou, double ov, double* au, double* av) { rig_row(a, ID, Tn, Tn, Xc, Yc, ou, ov, au, av); }, g.obj,
                      g.img, p0, np, rows, lane, oth);
             evals++;
             const double c2 = oth[kRigEntries - 1];

@@ -10,7 +10,8 @@
 // barrier, which is the contract's order (ascending forward, descending backward); the covariance's unit-vector solves take one
 // thread each on a second n x n scratch.  Blocks, candidates, poses and the frames' vectors live in device scratch: kMapObsDoubles
 // per observation, kMapFrameDoubles per frame, kMapMarkerDoubles per marker, and two tables (a frame's first observation, a marker's
-// observations in order).  No atomics on shared addresses but the rig's iteration maximum: every result is reproducible.
+// observations in order).  No atomics on shared addresses but the rig's iteration maximum: every result is reproducible.  Step 1's
+// pose start is pose_from_h (a3_solve.h).
 #include <cmath>
 
 #include "a3_common.h"
@@ -53,35 +54,13 @@ struct MapArgs {
     a3_map_observation_result* ores;
 };
 
-// one observation's 91 block entries at (a, E, T), G = E . T -> out (wave-level); the four object points from sq
+// one observation's 91 block entries at (a, E, T), G = E . T -> out (wave-level): one chunk of aug_block (a3_solve.h) over rig_row, the
+// four object points from sq.  aug_block takes its points __restrict__: sq is the map's s_sq in LDS, which is written before a barrier
+// and never while a block is evaluated.
 __device__ __forceinline__ void map_block(const double a[12], const double* E, const double* T, const double* G, const float* sq,
                                           const float* __restrict__ img, double* rows, int lane, double* out) {
-    int ei[2], ek[2];
-    double acc[2] = {0.0, 0.0};
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        ei[q] = 0;
-        ek[q] = 0;
-        if (lane + 64 * q < kRigEntries) tri_ik(lane + 64 * q, kRigAug, &ei[q], &ek[q]);
-    }
-    if (lane < 4)
-        rig_row(a, E, T, G, (double)sq[2 * lane], (double)sq[2 * lane + 1], (double)img[2 * lane], (double)img[2 * lane + 1], rows + lane * 2 * kRigAug,
-                rows + lane * 2 * kRigAug + kRigAug);
-    wave_sync();
-    for (int j = 0; j < 4; j++) {
-        const double* u = rows + j * 2 * kRigAug;
-        const double* v = u + kRigAug;
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            acc[q] = acc[q] + u[ei[q]] * u[ek[q]];
-            acc[q] = acc[q] + v[ei[q]] * v[ek[q]];
-        }
-    }
-    wave_sync();
-#pragma unroll
-    for (int q = 0; q < 2; q++)
-        if (lane + 64 * q < kRigEntries) out[lane + 64 * q] = acc[q];
-    wave_sync();
+    aug_block<kRigAug>([&](double X, double Y, double ou, double ov, double* au, double* av) { rig_row(a, E, T, G, X, Y, ou, ov, au, av); }, sq, img, 0, 4,
+                       rows, lane, out);
 }
 
 // the pose LM of step 1 on columns 6-12 with E the identity (wave-level): T in / out -> the cost; the blocks go over blk[2][91]
@@ -303,23 +282,14 @@ __global__ __launch_bounds__(kMapThreads) void k_map(MapArgs g) {
 #pragma unroll
             for (int q = 0; q < 12; q++) a[q] = s_a[q];
             const double* H = os + kMoP;
-            double m[3][3];
+            double m[3][3], T[12];
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 m[c][0] = (H[c] - a[2] * H[6 + c]) / a[0];
                 m[c][1] = (H[3 + c] - a[3] * H[6 + c]) / a[1];
                 m[c][2] = H[6 + c];
             }
-            const double n0 = sqrt((m[0][0] * m[0][0] + m[0][1] * m[0][1]) + m[0][2] * m[0][2]);
-            const double r00 = m[0][0] / n0, r01 = m[0][1] / n0, r02 = m[0][2] / n0;
-            const double dd = (r00 * m[1][0] + r01 * m[1][1]) + r02 * m[1][2];
-            const double e0 = m[1][0] - dd * r00, e1 = m[1][1] - dd * r01, e2 = m[1][2] - dd * r02;
-            const double ne = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-            const double r10 = e0 / ne, r11 = e1 / ne, r12 = e2 / ne;
-            const double n1 = sqrt((m[1][0] * m[1][0] + m[1][1] * m[1][1]) + m[1][2] * m[1][2]);
-            const double den = n0 + n1;
-            double T[12] = {r00, r10, r01 * r12 - r02 * r11, r01, r11, r02 * r10 - r00 * r12, r02, r12, r00 * r11 - r01 * r10,
-                            (2.0 * m[2][0]) / den, (2.0 * m[2][1]) / den, (2.0 * m[2][2]) / den};
+            pose_from_h(m, T, T + 9);
             wave_sync();   // (every lane has read H before the candidates go over this scratch)
             c0 = map_pose_lm(a, s_sq, im, T, os + kMoBlk, rows, lane);
             double Q[12];

@@ -4,7 +4,7 @@
 // One workgroup of four waves per rig; every phase runs inside the one launch, separated by barriers.  Per-observation work (step 1) goes
 // to one wave (observations w, w + 4, ...), per-frame work to one wave (frame f to wave f mod 4).  An observation's sums run in point
 // order: the lanes write the rows of up to 64 points into the wave's LDS, then each lane owns up to two of the 91 block entries and adds
-// the rows in order (the view_block scheme of k_calib.hip).  The Schur complement over the extrinsics (order 6 (C - 1) <= 42) has one
+// the rows in order (aug_block of a3_solve.h, where the pose start, pose_from_h, lives too).  The Schur complement over the extrinsics (order 6 (C - 1) <= 42) has one
 // thread per entry, each summing over the frames in frame order; its LDL^T runs column by column on wave 0, one lane per row, every
 // entry in the contract's order; the covariance's unit-vector solves take one lane each.  Blocks, poses and the frames' Schur
 // vectors live in device scratch: kRigObsDoubles per observation, kRigFrameDoubles per frame, and a table [frame][8] of the USED
@@ -45,40 +45,11 @@ struct RigArgs {
     a3_rig_observation_result* ores;
 };
 
-// one observation's 91 block entries at (a, E, T), G = E . T -> out (wave-level).  Inlined: the poses stay in registers.
+// one observation's 91 block entries at (a, E, T), G = E . T -> out (wave-level): aug_block (a3_solve.h) over rig_row
 __device__ __forceinline__ void obs_block(const double a[12], const double* E, const double* T, const double* G, const float* __restrict__ obj,
                                           const float* __restrict__ img, uint32_t p0, uint32_t np, double* rows, int lane, double* out) {
-    int ei[2], ek[2];
-    double acc[2] = {0.0, 0.0};
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        ei[q] = 0;
-        ek[q] = 0;
-        if (lane + 64 * q < kRigEntries) tri_ik(lane + 64 * q, kRigAug, &ei[q], &ek[q]);
-    }
-    for (uint32_t c0 = 0; c0 < np; c0 += 64) {
-        const uint32_t cnt = min(64u, np - c0);
-        if ((uint32_t)lane < cnt) {
-            const size_t p = (size_t)p0 + c0 + (uint32_t)lane;
-            rig_row(a, E, T, G, (double)obj[2 * p], (double)obj[2 * p + 1], (double)img[2 * p], (double)img[2 * p + 1], rows + lane * kRigRowStride,
-                    rows + lane * kRigRowStride + kRigAug);
-        }
-        wave_sync();
-        for (uint32_t j = 0; j < cnt; j++) {
-            const double* u = rows + j * kRigRowStride;
-            const double* v = u + kRigAug;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                acc[q] = acc[q] + u[ei[q]] * u[ek[q]];
-                acc[q] = acc[q] + v[ei[q]] * v[ek[q]];
-            }
-        }
-        wave_sync();
-    }
-#pragma unroll
-    for (int q = 0; q < 2; q++)
-        if (lane + 64 * q < kRigEntries) out[lane + 64 * q] = acc[q];
-    wave_sync();
+    aug_block<kRigAug>([&](double X, double Y, double ou, double ov, double* au, double* av) { rig_row(a, E, T, G, X, Y, ou, ov, au, av); }, obj, img, p0,
+                       np, rows, lane, out);
 }
 
 // the blocks of frame f (call index) at (s_E, T) into `slot`, then the frame's sums (wave-level)
@@ -179,25 +150,17 @@ __global__ __launch_bounds__(kRigThreads) void k_rig(RigArgs g) {
 #pragma unroll
         for (int q = 0; q < 12; q++) a[q] = s_a[(ob.camera - c0) * 12 + q];
         const double* H = os + kObsP;
-        double m[3][3];
+        double m[3][3], T[12];
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             m[c][0] = (H[c] - a[2] * H[6 + c]) / a[0];
             m[c][1] = (H[3 + c] - a[3] * H[6 + c]) / a[1];
             m[c][2] = H[6 + c];
         }
-        const double n0 = sqrt((m[0][0] * m[0][0] + m[0][1] * m[0][1]) + m[0][2] * m[0][2]);
-        const double r00 = m[0][0] / n0, r01 = m[0][1] / n0, r02 = m[0][2] / n0;
-        const double dd = (r00 * m[1][0] + r01 * m[1][1]) + r02 * m[1][2];
-        const double e0 = m[1][0] - dd * r00, e1 = m[1][1] - dd * r01, e2 = m[1][2] - dd * r02;
-        const double ne = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-        const double r10 = e0 / ne, r11 = e1 / ne, r12 = e2 / ne;
-        const double n1 = sqrt((m[1][0] * m[1][0] + m[1][1] * m[1][1]) + m[1][2] * m[1][2]);
-        const double den = n0 + n1;
-        double T[12] = {r00, r10, r01 * r12 - r02 * r11, r01, r11, r02 * r10 - r00 * r12, r02, r12, r00 * r11 - r01 * r10,
-                        (2.0 * m[2][0]) / den, (2.0 * m[2][1]) / den, (2.0 * m[2][2]) / den};
+        pose_from_h(m, T, T + 9);
         const double ID[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
         wave_sync();   // (every lane has read H before the blocks and P go over this scratch)
+        // (the pose-only LM loop stays this kernel's own: behind a shared function it compiles to other code)
         double* cur = os + kObsBlk;
         double* oth = cur + kRigEntries;
         obs_block(a, ID, T, T, g.obj, g.img, p0, np, rows, lane, cur);
