@@ -74,8 +74,10 @@ SYMBOLS = [
     "a3_calibrate_cameras", "a3_calibrate_fisheye_cameras", "a3_calibrate_rigs", "a3_calibrate_hand_eyes", "a3_build_marker_maps",
     "a3_default_rectify", "a3_rectify_frames",
 ]
+CAND_DTYPE = np.dtype([("start_key", "<u4"), ("xy", "<u2", (8,))])      # a3_debug_cand (a3_internal.h)
+PROJ_DTYPE = np.dtype([("inv", "<f4", (9,)), ("ok", "<i4")])            # A3_DEBUG_PROJ_BYTES
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
-INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates", "a3_debug_sample_frames"]
+INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates", "a3_debug_sample_frames", "a3_debug_frame_candidates"]
 
 
 class A3Error(RuntimeError):
@@ -484,6 +486,10 @@ def load():
                                         C.c_size_t, C.c_size_t, C.POINTER(RectifyInfo)]
     L.a3_debug_discard_too_near.restype = C.c_int
     L.a3_debug_discard_too_near.argtypes = [vp, u32p, C.c_size_t, C.c_float, u32p, C.POINTER(C.c_size_t)]
+    if hasattr(L, "a3_debug_frame_candidates"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack it)
+        L.a3_debug_frame_candidates.restype = C.c_int
+        L.a3_debug_frame_candidates.argtypes = [vp, C.c_uint32, C.c_uint32, u32p, vp, C.c_float, C.c_uint32, C.POINTER(C.c_uint16),
+                                                C.POINTER(C.c_uint16), u32p, u32p, u32p, vp]
     _lib = L
     return L
 
@@ -1000,6 +1006,28 @@ class Context:
         check(load().a3_debug_discard_too_near(self.handle, _p(q, C.c_uint32), q.shape[0], min_distance, _p(out, C.c_uint32), C.byref(n)),
               self.handle)
         return out[: n.value].reshape(-1, 4, 2)
+
+    def debug_frame_candidates(self, cand_count, records: np.ndarray, max_cand: int, min_distance: float, S: int = 0) -> dict:
+        """a3_debug_frame_candidates: one launch of k_frame_candidates, as the pipeline makes it, on hand-made candidate tables.
+        cand_count: per frame (may exceed max_cand); records: CAND_DTYPE, frame after frame, min(count, max_cand) each, in table order.
+        Returns whole tables -- what the kernel did not write is 0xFF bytes: pre_xy, fin_xy (frames x max_cand x 8 u16), fin_count,
+        work (frames * max_cand u32), work_count, and with S != 0 proj (PROJ_DTYPE, frames * max_cand, indexed like work)."""
+        cnt = np.ascontiguousarray(cand_count, dtype=np.uint32).reshape(-1)
+        rec = np.ascontiguousarray(records, dtype=CAND_DTYPE).reshape(-1)
+        n = cnt.shape[0]
+        if max_cand >= 1 and rec.shape[0] != int(np.minimum(cnt, max_cand).sum()):
+            raise ValueError("records must hold min(cand_count, max_cand) entries per frame")
+        slots = n * max_cand if 1 <= max_cand <= 65536 else 0      # (out of range: the library refuses before it writes)
+        pre = np.empty((n, slots // max(n, 1), 8), dtype=np.uint16)
+        fin = np.empty_like(pre)
+        fin_count = np.empty(n, dtype=np.uint32)
+        work = np.empty(slots, dtype=np.uint32)
+        work_count = np.zeros(1, dtype=np.uint32)
+        proj = np.empty(slots if S else 0, dtype=PROJ_DTYPE)
+        check(load().a3_debug_frame_candidates(self.handle, n, max_cand, _p(cnt, C.c_uint32), rec.ctypes.data if rec.size else None, min_distance, S,
+                                               _p(pre, C.c_uint16), _p(fin, C.c_uint16), _p(fin_count, C.c_uint32), _p(work, C.c_uint32),
+                                               _p(work_count, C.c_uint32), proj.ctypes.data if S else None), self.handle)
+        return {"pre_xy": pre, "fin_xy": fin, "fin_count": fin_count, "work": work, "work_count": int(work_count[0]), "proj": proj if S else None}
 
     # ---- pose ----
     def estimate_pose(self, corners: np.ndarray, marker_size_mm: float, image_size=None, intrinsics: Intrinsics = None) -> np.ndarray:

@@ -2176,6 +2176,71 @@ int a3_debug_discard_too_near(a3_ctx* ctx, const uint32_t* quads_xy, size_t n, f
     return A3_OK;
 }
 
+// k_frame_candidates as the pipeline launches it -- any frame count, any table size, keys as given -- on buffers of its own (freed on
+// return: nothing of the context's changes size, so a batch afterwards runs what it would have run).  Every device buffer is filled
+// with 0xFF first, so what the kernel left alone comes back as 0xFF.
+int a3_debug_frame_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t max_cand, const uint32_t* cand_count, const a3_debug_cand* records,
+                              float min_distance, uint32_t S, uint16_t* pre_xy, uint16_t* fin_xy, uint32_t* fin_count, uint32_t* work,
+                              uint32_t* work_count, void* proj) {
+    static_assert(sizeof(a3_debug_cand) == sizeof(CandRec) && sizeof(CandRec) == 20, "a3_debug_cand is a CandRec");
+    if (!ctx) return A3_ERR_INVALID;
+    if (n_frames == 0) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: n_frames must be at least 1");
+    if (max_cand == 0 || max_cand > kMaxCandLimit) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: max_cand must be in 1..65536");
+    if (!cand_count || !pre_xy || !fin_xy || !fin_count || !work || !work_count || (S && !proj))
+        return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: a NULL argument");
+    if (proj_rec_bytes() != A3_DEBUG_PROJ_BYTES) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: ProjRec is not A3_DEBUG_PROJ_BYTES long");
+    const size_t slots = (size_t)n_frames * max_cand;
+    if (slots > ((size_t)1 << 26)) return fail(ctx, A3_ERR_LIMIT, "a3_debug_frame_candidates: more than 2^26 slots");
+    std::vector<CandRec> h(slots);
+    memset(h.data(), 0xFF, slots * sizeof(CandRec));
+    size_t given = 0;
+    std::vector<uint32_t> keys;
+    for (uint32_t f = 0; f < n_frames; f++) {
+        const uint32_t c = std::min(cand_count[f], max_cand);
+        if (c && !records) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: a NULL argument");
+        keys.resize(c);
+        for (uint32_t i = 0; i < c; i++) {
+            memcpy(&h[(size_t)f * max_cand + i], &records[given + i], sizeof(CandRec));
+            keys[i] = records[given + i].start_key;
+        }
+        std::sort(keys.begin(), keys.end());
+        if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
+            return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: a frame's start keys must be unique");
+        given += c;
+    }
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    struct Own : DevBuf { ~Own() { release(); } } d_cands, d_cnt, d_pre, d_fin, d_work, d_proj, d_big;
+    const bool big = max_cand > frame_cand_lds_slots();
+    const size_t proj_bytes = S ? slots * proj_rec_bytes() : 0;
+    A3_HIP(d_cands.ensure(slots * sizeof(CandRec)));
+    A3_HIP(d_cnt.ensure(((size_t)2 * n_frames + 1) * 4));   // cand_count | fin_count | work_count
+    A3_HIP(d_pre.ensure(slots * 16)); A3_HIP(d_fin.ensure(slots * 16)); A3_HIP(d_work.ensure(slots * 4));
+    if (S) A3_HIP(d_proj.ensure(proj_bytes));
+    if (big) A3_HIP(d_big.ensure(slots * 4));
+    uint32_t* cnt = d_cnt.as<uint32_t>();
+    hipStream_t st = ctx->stream;
+    A3_HIP(hipMemcpyAsync(d_cands.p, h.data(), slots * sizeof(CandRec), hipMemcpyHostToDevice, st));
+    A3_HIP(hipMemcpyAsync(cnt, cand_count, (size_t)n_frames * 4, hipMemcpyHostToDevice, st));
+    A3_HIP(hipMemsetAsync(cnt + n_frames, 0xFF, (size_t)n_frames * 4, st));
+    A3_HIP(hipMemsetAsync(cnt + 2 * (size_t)n_frames, 0, 4, st));
+    A3_HIP(hipMemsetAsync(d_pre.p, 0xFF, slots * 16, st)); A3_HIP(hipMemsetAsync(d_fin.p, 0xFF, slots * 16, st));
+    A3_HIP(hipMemsetAsync(d_work.p, 0xFF, slots * 4, st));
+    if (S) A3_HIP(hipMemsetAsync(d_proj.p, 0xFF, proj_bytes, st));
+    if (big) A3_HIP(hipMemsetAsync(d_big.p, 0xFF, slots * 4, st));
+    A3_HIP(launch_frame_candidates(st, d_cands.as<CandRec>(), cnt, n_frames, max_cand, min_distance, d_pre.as<uint16_t>(), d_fin.as<uint16_t>(),
+                                   cnt + n_frames, d_work.as<uint32_t>(), cnt + 2 * (size_t)n_frames, S, S ? d_proj.p : nullptr,
+                                   big ? d_big.as<float>() : nullptr));
+    A3_HIP(hipMemcpyAsync(pre_xy, d_pre.p, slots * 16, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(fin_xy, d_fin.p, slots * 16, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(fin_count, cnt + n_frames, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(work, d_work.p, slots * 4, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(work_count, cnt + 2 * (size_t)n_frames, 4, hipMemcpyDeviceToHost, st));
+    if (S) A3_HIP(hipMemcpyAsync(proj, d_proj.p, proj_bytes, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipStreamSynchronize(st));
+    return A3_OK;
+}
+
 int a3_debug_inject_candidates(a3_ctx* ctx, const uint32_t* quads_xy, size_t n) {
     if (!ctx || (!quads_xy && n)) return A3_ERR_INVALID;
     if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_debug_inject_candidates: a submitted batch has not been collected");

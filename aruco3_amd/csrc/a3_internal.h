@@ -74,6 +74,23 @@ int  a3_debug_inject_candidates(a3_ctx *ctx, const uint32_t *quads_xy, size_t n)
 int  a3_debug_sample_frames(a3_ctx *ctx, int enabled);
 int  a3_debug_discard_too_near(a3_ctx *ctx, const uint32_t *quads_xy, size_t n, float min_distance, uint32_t *out_xy, size_t *n_out);
 
+/* k_frame_candidates (candidate order by start key, discard_too_near, compaction, the work list, the projections) launched exactly
+ * as the pipeline launches it -- ONE call of launch_frame_candidates, so the table size picks the kernel's form: all in LDS up to
+ * 6144 slots per frame, through memory above -- on hand-made candidate tables.  The product never calls it; tests/ do, because the
+ * contour stage cannot be made to produce a chosen candidate list and the two hooks above stop at one frame of 1024 quads whose
+ * keys are 0..n-1.
+ *   n_frames >= 1, max_cand in 1..65536 (slots per frame), cand_count[n_frames] (may exceed max_cand: an overflowed frame),
+ *   records: frame after frame, min(cand_count[f], max_cand) records each, in the order of the frame's table (keys unique per frame),
+ *   S: homography_sample_size, 0 = no projections (proj may then be NULL).
+ * Out, each for n_frames * max_cand slots and filled with 0xFF bytes wherever the kernel did not write: pre_xy and fin_xy (8 x u16 per
+ * slot), work (u32 per slot), proj (A3_DEBUG_PROJ_BYTES per slot, indexed like work: 9 x f32 inverse, i32 ok); fin_count[n_frames];
+ * *work_count.  Runs on buffers of its own and frees them: the context's buffers and settings are what they were. */
+typedef struct { uint32_t start_key; uint16_t xy[8]; } a3_debug_cand;
+#define A3_DEBUG_PROJ_BYTES 40
+int  a3_debug_frame_candidates(a3_ctx *ctx, uint32_t n_frames, uint32_t max_cand, const uint32_t *cand_count, const a3_debug_cand *records,
+                               float min_distance, uint32_t S, uint16_t *pre_xy, uint16_t *fin_xy, uint32_t *fin_count, uint32_t *work,
+                               uint32_t *work_count, void *proj);
+
 #ifdef __cplusplus
 }
 #endif
