@@ -531,6 +531,19 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _f32(a, cols: int) -> np.ndarray:
+    """a contiguous float32 (n, cols) view or copy of `a`"""
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, cols))
+
+
+def _symbol(name: str):
+    """an entry point that a library built before it was added does not have"""
+    fn = getattr(load(), name, None)
+    if fn is None:
+        raise A3Error(-1, f"this libaruco3_hip.so has no {name}")
+    return fn
+
+
 def check(rc, ctx=None):
     if rc != OK:
         raise A3Error(rc, load().a3_last_error(ctx).decode("utf-8", "replace"))
@@ -724,7 +737,7 @@ class Context:
     def refine_corners(self, pixels_ptr: int, memory: int, fmt: int, width: int, height: int, row_stride: int, corners: np.ndarray,
                        cell_px: np.ndarray = None) -> np.ndarray:
         """a3_refine_corners (stand-alone, one frame): corners (..., 2) -> refined float32 (n, 2)"""
-        xy = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 2)).copy()
+        xy = _f32(corners, 2).copy()
         cp = None if cell_px is None else np.ascontiguousarray(np.asarray(cell_px, dtype=np.float32).reshape(-1))
         if cp is not None and cp.size != xy.shape[0]:
             raise ValueError("cell_px needs one value per corner")
@@ -739,7 +752,7 @@ class Context:
             check(load().a3_set_board(self.handle, None, None, 0), self.handle)
             return
         i = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
-        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 8))
+        c = _f32(corners, 8)
         if c.shape[0] != i.size:
             raise ValueError("set_board needs four corners per id")
         check(load().a3_set_board(self.handle, _p(i, C.c_uint32), _p(c, C.c_float), i.size), self.handle)
@@ -758,7 +771,7 @@ class Context:
     def estimate_board_pose(self, ids, corners, image_size=None, intrinsics: "Intrinsics" = None) -> np.ndarray:
         """a3_estimate_board_pose (stand-alone, one frame): ids (n,), image corners (n, 4, 2) in pixels -> one BOARD_POSE_DTYPE record"""
         i = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
-        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 8))
+        c = _f32(corners, 8)
         if c.shape[0] != i.size:
             raise ValueError("estimate_board_pose needs four corners per id")
         iw, ih = image_size if image_size else (0, 0)
@@ -776,7 +789,7 @@ class Context:
         if corners is None or len(corners) == 0:
             check(load().a3_set_charuco(self.handle, None, None, 0, None), self.handle)
             return
-        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 2))
+        c = _f32(corners, 2)
         a = np.ascontiguousarray(np.asarray(adjacent_ids, dtype=np.uint32).reshape(-1, 4))
         if a.shape[0] != c.shape[0]:
             raise ValueError("set_charuco needs four adjacent ids per corner")
@@ -808,7 +821,7 @@ class Context:
         """a3_interpolate_charuco (stand-alone, one frame): marker ids (n,) and raw pixel corners (n, 4, 2) -> CHARUCO_CORNER_DTYPE records"""
         L = load()
         i = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
-        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 8))
+        c = _f32(corners, 8)
         if c.shape[0] != i.size:
             raise ValueError("interpolate_charuco needs four corners per id")
         n = C.c_size_t(0)
@@ -839,7 +852,7 @@ class Context:
 
     def undistort_points(self, points: np.ndarray, intrinsics: "Intrinsics", d: "DistortionRec"):
         """a3_undistort_points (stand-alone): points (..., 2) pixels -> (float32 (n, 2) undistorted pixels, float32 (n,) residuals)"""
-        xy = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 2))
+        xy = _f32(points, 2)
         out = np.zeros_like(xy)
         res = np.zeros(xy.shape[0], dtype=np.float32)
         check(load().a3_undistort_points(self.handle, _p(xy, C.c_float), xy.shape[0], C.byref(intrinsics), C.byref(d), _p(out, C.c_float),
@@ -858,38 +871,31 @@ class Context:
         return info
 
     # ---- camera calibration ----
-    def calibrate_cameras(self, cams, view_offsets, object_xy, image_xy, with_views: bool = True):
-        """a3_calibrate_cameras: cams (a CalibCamera array), view_offsets (n_views + 1), object / image points (n, 2) ->
-        (CalibResult array, CalibView array or None)"""
+    def _calibrate(self, symbol, cams, view_offsets, object_xy, image_xy, with_views):
         off = np.ascontiguousarray(np.asarray(view_offsets, dtype=np.uint32).reshape(-1))
-        obj = np.ascontiguousarray(np.asarray(object_xy, dtype=np.float32).reshape(-1, 2))
-        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 2))
+        obj, img = _f32(object_xy, 2), _f32(image_xy, 2)
         n_views = max(off.size - 1, 0)
         res = (CalibResult * max(len(cams), 1))()
         views = (CalibView * max(n_views, 1))() if with_views else None
-        check(load().a3_calibrate_cameras(self.handle, cams, len(cams), _p(off, C.c_uint32), n_views, _p(obj, C.c_float), _p(img, C.c_float), res,
-                                          views), self.handle)
+        check(getattr(load(), symbol)(self.handle, cams, len(cams), _p(off, C.c_uint32), n_views, _p(obj, C.c_float), _p(img, C.c_float), res,
+                                      views), self.handle)
         return res, views
+
+    def calibrate_cameras(self, cams, view_offsets, object_xy, image_xy, with_views: bool = True):
+        """a3_calibrate_cameras: cams (a CalibCamera array), view_offsets (n_views + 1), object / image points (n, 2) ->
+        (CalibResult array, CalibView array or None)"""
+        return self._calibrate("a3_calibrate_cameras", cams, view_offsets, object_xy, image_xy, with_views)
 
     def calibrate_fisheye_cameras(self, cams, view_offsets, object_xy, image_xy, with_views: bool = True):
         """a3_calibrate_fisheye_cameras: the arguments of calibrate_cameras, the cameras' flags read as FISHEYE_* ->
         (CalibResult array, CalibView array or None)"""
-        off = np.ascontiguousarray(np.asarray(view_offsets, dtype=np.uint32).reshape(-1))
-        obj = np.ascontiguousarray(np.asarray(object_xy, dtype=np.float32).reshape(-1, 2))
-        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 2))
-        n_views = max(off.size - 1, 0)
-        res = (CalibResult * max(len(cams), 1))()
-        views = (CalibView * max(n_views, 1))() if with_views else None
-        check(load().a3_calibrate_fisheye_cameras(self.handle, cams, len(cams), _p(off, C.c_uint32), n_views, _p(obj, C.c_float),
-                                                  _p(img, C.c_float), res, views), self.handle)
-        return res, views
+        return self._calibrate("a3_calibrate_fisheye_cameras", cams, view_offsets, object_xy, image_xy, with_views)
 
     # ---- camera rig calibration ----
     def calibrate_rigs(self, rigs, cameras, obs, object_xy, image_xy):
         """a3_calibrate_rigs: rigs (a Rig array), cameras (RigCamera array), obs (RigObservation array), object / image points (n, 2) ->
         (RigResult array, RigCameraResult array, RigFrame array, RigObservationResult array)"""
-        obj = np.ascontiguousarray(np.asarray(object_xy, dtype=np.float32).reshape(-1, 2))
-        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 2))
+        obj, img = _f32(object_xy, 2), _f32(image_xy, 2)
         n_frames = max([int(r.first_frame) + int(r.n_frames) for r in rigs], default=0)
         res = (RigResult * max(len(rigs), 1))()
         cres = (RigCameraResult * max(len(cameras), 1))()
@@ -903,30 +909,25 @@ class Context:
     def calibrate_hand_eyes(self, problems, frames, object_xy, image_xy):
         """a3_calibrate_hand_eyes: problems (a HandEyeProblem array), frames (HandEyeFrame array), object / image points (n, 2) ->
         (HandEyeResult array, HandEyeFrameResult array)"""
-        obj = np.ascontiguousarray(np.asarray(object_xy, dtype=np.float32).reshape(-1, 2))
-        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 2))
+        obj, img = _f32(object_xy, 2), _f32(image_xy, 2)
         res = (HandEyeResult * max(len(problems), 1))()
         fres = (HandEyeFrameResult * max(len(frames), 1))()
-        fn = getattr(load(), "a3_calibrate_hand_eyes", None)
-        if fn is None:
-            raise A3Error(-1, "this libaruco3_hip.so has no a3_calibrate_hand_eyes")
-        check(fn(self.handle, problems, len(problems), frames, len(frames), _p(obj, C.c_float), _p(img, C.c_float), res, fres), self.handle)
+        check(_symbol("a3_calibrate_hand_eyes")(self.handle, problems, len(problems), frames, len(frames), _p(obj, C.c_float), _p(img, C.c_float),
+                                                res, fres), self.handle)
         return res, fres
 
     # ---- marker maps ----
     def build_marker_maps(self, maps, markers, obs, image_xy):
         """a3_build_marker_maps: maps (a Map array), markers (MapMarker array), obs (MapObservation array), image corners (n_obs, 8) ->
         (MapResult array, MapMarkerResult array, MapFrame array, MapObservationResult array)"""
-        img = np.ascontiguousarray(np.asarray(image_xy, dtype=np.float32).reshape(-1, 8))
+        img = _f32(image_xy, 8)
         n_frames = max([int(r.first_frame) + int(r.n_frames) for r in maps], default=0)
         res = (MapResult * max(len(maps), 1))()
         mres = (MapMarkerResult * max(len(markers), 1))()
         frames = (MapFrame * max(n_frames, 1))()
         ores = (MapObservationResult * max(len(obs), 1))()
-        fn = getattr(load(), "a3_build_marker_maps", None)
-        if fn is None:
-            raise A3Error(-1, "this libaruco3_hip.so has no a3_build_marker_maps")
-        check(fn(self.handle, maps, len(maps), markers, len(markers), obs, len(obs), _p(img, C.c_float), res, mres, frames, ores), self.handle)
+        check(_symbol("a3_build_marker_maps")(self.handle, maps, len(maps), markers, len(markers), obs, len(obs), _p(img, C.c_float), res, mres,
+                                              frames, ores), self.handle)
         return res, mres, frames, ores
 
     # ---- Detection.grey / thresholded / candidates / homographies of the last batch ----

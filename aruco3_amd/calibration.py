@@ -9,13 +9,12 @@ calls.  Views are lists of correspondences: board points (x, y) in board units o
 The fisheye solve (`calibrate_camera_fisheye`, or model="fisheye" on the board helpers) is cv::fisheye::calibrate for planar targets:
 fx fy cx cy and D = (k1 k2 k3 k4), a kernel and a bit-exact contract of its own; its result's `intrinsics.distortion` is a fisheye
 `Distortion`, ready for `rectify_frames`, `undistort_points` and the pose calls."""
-import threading
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _solver
 from .pinhole import CameraIntrinsics, Distortion
 
 PARAM_NAMES = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")
@@ -80,10 +79,25 @@ class Calibration:
                    int(r.views_used), int(r.points_used), vr, model=model)
 
 
-def _flags(fix_principal_point=False, zero_tangent=False, fix_k3=False, rational=False, guess=None) -> int:
-    return ((_lib.CALIB_FIX_PRINCIPAL_POINT if fix_principal_point else 0) | (_lib.CALIB_ZERO_TANGENT_DIST if zero_tangent else 0) |
-            (_lib.CALIB_FIX_K3 if fix_k3 else 0) | (_lib.CALIB_RATIONAL_MODEL if rational else 0) |
-            (_lib.CALIB_USE_INTRINSIC_GUESS if guess is not None else 0))
+def _flags(pr) -> int:
+    return ((_lib.CALIB_FIX_PRINCIPAL_POINT if pr.get("fix_principal_point") else 0) | (_lib.CALIB_ZERO_TANGENT_DIST if pr.get("zero_tangent") else 0) |
+            (_lib.CALIB_FIX_K3 if pr.get("fix_k3") else 0) | (_lib.CALIB_RATIONAL_MODEL if pr.get("rational") else 0) |
+            (_lib.CALIB_USE_INTRINSIC_GUESS if pr.get("guess") is not None else 0))
+
+
+def _fisheye_flags(pr) -> int:
+    return ((_lib.FISHEYE_FIX_PRINCIPAL_POINT if pr.get("fix_principal_point") else 0) | (_lib.FISHEYE_FIX_K1 if pr.get("fix_k1") else 0) |
+            (_lib.FISHEYE_FIX_K2 if pr.get("fix_k2") else 0) | (_lib.FISHEYE_FIX_K3 if pr.get("fix_k3") else 0) |
+            (_lib.FISHEYE_FIX_K4 if pr.get("fix_k4") else 0) | (_lib.FISHEYE_USE_INTRINSIC_GUESS if pr.get("guess") is not None else 0))
+
+
+def _rational_lens(d: Distortion) -> None:
+    d.rational_coefficients("a calibration guess")   # (a fisheye lens is refused)
+
+
+def _fisheye_lens(d: Distortion) -> None:
+    if d.model != "fisheye":
+        raise ValueError("a fisheye calibration guess takes a fisheye Distortion (Distortion.fisheye) or none, not rational lens coefficients")
 
 
 def _views(object_points, image_points):
@@ -104,16 +118,8 @@ def _views(object_points, image_points):
     return obj, img
 
 
-_ctx = None
-_ctx_lock = threading.Lock()   # one context (one stream, one set of buffers) serves every thread: calls take turns
-
-
 def _calibrate(cams, offsets, obj, img, fisheye: bool = False):
-    global _ctx
-    with _ctx_lock:
-        if _ctx is None:
-            _ctx = _lib.Context(_lib.default_config(), np.zeros(1, np.uint64), 64, 1)
-        return (_ctx.calibrate_fisheye_cameras if fisheye else _ctx.calibrate_cameras)(cams, offsets, obj, img)
+    return _solver.call("calibrate_fisheye_cameras" if fisheye else "calibrate_cameras", cams, offsets, obj, img)
 
 
 def reproject(params, rotation, translation, object_points, model: str = "rational") -> np.ndarray:
@@ -126,10 +132,9 @@ def reproject(params, rotation, translation, object_points, model: str = "ration
     return xd * a[[0, 1]] + a[[2, 3]]
 
 
-def calibrate_cameras(problems: Sequence[dict]) -> List[Calibration]:
-    """Several cameras in one launch.  Each problem is a dict of calibrate_camera's arguments: object_points, image_points,
-    image_size and optionally fix_principal_point, zero_tangent, fix_k3, rational, guess (a CameraIntrinsics, its distortion the
-    starting lens), max_iterations."""
+def _calibrate_cameras(problems, model, flags, check_lens, default_lens) -> List[Calibration]:
+    """calibrate_cameras for either lens model: `flags` reads a problem's, `check_lens` refuses a guess's lens of the other model and
+    `default_lens` stands in for a guess without one"""
     specs, obj, img = [], [], []
     for pr in problems:
         o, i = _views(pr["object_points"], pr["image_points"])
@@ -140,19 +145,24 @@ def calibrate_cameras(problems: Sequence[dict]) -> List[Calibration]:
     for c, (pr, first, n) in zip(cams, specs):
         w, h = pr["image_size"]
         c.image_width, c.image_height, c.first_view, c.n_views = int(w), int(h), first, n
-        guess = pr.get("guess")
-        c.flags = _flags(pr.get("fix_principal_point", False), pr.get("zero_tangent", False), pr.get("fix_k3", False), pr.get("rational", False),
-                         guess)
+        c.flags = flags(pr)
         c.max_iterations = int(pr.get("max_iterations") or 0)
+        guess = pr.get("guess")
         if guess is not None:
             if guess.distortion is not None:
-                guess.distortion.rational_coefficients("a calibration guess")   # (a fisheye lens is refused)
+                check_lens(guess.distortion)
             c.guess = guess._c()
-            c.guess_distortion = (guess.distortion or Distortion())._c()
+            c.guess_distortion = (guess.distortion or default_lens())._c()
     offsets = np.concatenate([[0], np.cumsum([len(o) for o in obj])]).astype(np.uint32)
-    res, views = _calibrate(cams, offsets, np.concatenate(obj) if obj else np.zeros((0, 2), np.float32),
-                            np.concatenate(img) if img else np.zeros((0, 2), np.float32))
-    return [Calibration._from(res[k], [views[first + j] for j in range(n)]) for k, (_, first, n) in enumerate(specs)]
+    res, views = _calibrate(cams, offsets, _solver.cat_points(obj), _solver.cat_points(img), model == "fisheye")
+    return [Calibration._from(res[k], [views[first + j] for j in range(n)], model) for k, (_, first, n) in enumerate(specs)]
+
+
+def calibrate_cameras(problems: Sequence[dict]) -> List[Calibration]:
+    """Several cameras in one launch.  Each problem is a dict of calibrate_camera's arguments: object_points, image_points,
+    image_size and optionally fix_principal_point, zero_tangent, fix_k3, rational, guess (a CameraIntrinsics, its distortion the
+    starting lens), max_iterations."""
+    return _calibrate_cameras(problems, "rational", _flags, _rational_lens, Distortion)
 
 
 def calibrate_camera(object_points, image_points, image_size, *, fix_principal_point=False, zero_tangent=False, fix_k3=False, rational=False,
@@ -173,58 +183,21 @@ def _solve_with_outlier_passes(solve, object_points, image_points, kw, outlier_p
     """one camera by `solve` (calibrate_cameras or calibrate_cameras_fisheye), then the outlier passes of calibrate_camera: the
     reprojection runs through the forward model of the solve's own lens"""
     obj, img = _views(object_points, image_points)
-    keep = [np.ones(len(o), bool) for o in obj]
-    cal = solve([dict(object_points=obj, image_points=img, **kw)])[0]
-    for _ in range(int(outlier_passes)):
-        if not cal.ok:
-            break
-        k_obj, k_img = [o[k] for o, k in zip(obj, keep)], [i[k] for i, k in zip(img, keep)]
-        for j, v in enumerate(cal.views):
-            if not v.used:
-                continue
-            e = np.linalg.norm(reproject(cal.params, v.rotation, v.translation, k_obj[j], cal.model) - k_img[j], axis=1)
-            idx = np.nonzero(keep[j])[0]
-            keep[j][idx[~(e < max(1.0, 3.0 * float(np.median(e))))]] = False
-        cal = solve([dict(object_points=[o[k] for o, k in zip(obj, keep)], image_points=[i[k] for i, k in zip(img, keep)], **kw)])[0]
-    if outlier_passes:
-        cal.inliers = keep
-    return cal
 
+    def residuals(cal, j, k):
+        v = cal.views[j]
+        return np.linalg.norm(reproject(cal.params, v.rotation, v.translation, obj[j][k], cal.model) - img[j][k], axis=1) if v.used else None
 
-def _fisheye_flags(fix_principal_point=False, fix_k1=False, fix_k2=False, fix_k3=False, fix_k4=False, guess=None) -> int:
-    return ((_lib.FISHEYE_FIX_PRINCIPAL_POINT if fix_principal_point else 0) | (_lib.FISHEYE_FIX_K1 if fix_k1 else 0) |
-            (_lib.FISHEYE_FIX_K2 if fix_k2 else 0) | (_lib.FISHEYE_FIX_K3 if fix_k3 else 0) | (_lib.FISHEYE_FIX_K4 if fix_k4 else 0) |
-            (_lib.FISHEYE_USE_INTRINSIC_GUESS if guess is not None else 0))
+    return _solver.solve_with_outlier_passes(
+        [len(o) for o in obj], lambda keep: solve([dict(object_points=[o[k] for o, k in zip(obj, keep)],
+                                                        image_points=[i[k] for i, k in zip(img, keep)], **kw)])[0], residuals, outlier_passes)
 
 
 def calibrate_cameras_fisheye(problems: Sequence[dict]) -> List[Calibration]:
     """Several fisheye cameras in one launch (a3_calibrate_fisheye_cameras).  Each problem is a dict of calibrate_camera_fisheye's
     arguments: object_points, image_points, image_size and optionally fix_principal_point, fix_k1 .. fix_k4, guess (a CameraIntrinsics
     without a lens or with a fisheye one), max_iterations."""
-    specs, obj, img = [], [], []
-    for pr in problems:
-        o, i = _views(pr["object_points"], pr["image_points"])
-        specs.append((pr, len(obj), len(o)))
-        obj += o
-        img += i
-    cams = (_lib.CalibCamera * max(len(specs), 1))()
-    for c, (pr, first, n) in zip(cams, specs):
-        w, h = pr["image_size"]
-        c.image_width, c.image_height, c.first_view, c.n_views = int(w), int(h), first, n
-        guess = pr.get("guess")
-        c.flags = _fisheye_flags(pr.get("fix_principal_point", False), pr.get("fix_k1", False), pr.get("fix_k2", False), pr.get("fix_k3", False),
-                                 pr.get("fix_k4", False), guess)
-        c.max_iterations = int(pr.get("max_iterations") or 0)
-        if guess is not None:
-            if guess.distortion is not None and guess.distortion.model != "fisheye":
-                raise ValueError("a fisheye calibration guess takes a fisheye Distortion (Distortion.fisheye) or none, not rational lens "
-                                 "coefficients")
-            c.guess = guess._c()
-            c.guess_distortion = (guess.distortion or Distortion.fisheye())._c()
-    offsets = np.concatenate([[0], np.cumsum([len(o) for o in obj])]).astype(np.uint32)
-    res, views = _calibrate(cams, offsets, np.concatenate(obj) if obj else np.zeros((0, 2), np.float32),
-                            np.concatenate(img) if img else np.zeros((0, 2), np.float32), fisheye=True)
-    return [Calibration._from(res[k], [views[first + j] for j in range(n)], "fisheye") for k, (_, first, n) in enumerate(specs)]
+    return _calibrate_cameras(problems, "fisheye", _fisheye_flags, _fisheye_lens, Distortion.fisheye)
 
 
 def calibrate_camera_fisheye(object_points, image_points, image_size, *, fix_principal_point=False, fix_k1=False, fix_k2=False, fix_k3=False,
@@ -274,11 +247,5 @@ def calibrate_camera_board(board, detections, image_size, *, model: str = "ratio
 def calibrate_camera_charuco(board, views, image_size, *, model: str = "rational", **kw) -> Calibration:
     """calibrateCameraCharuco: one view per Detection (its charuco_ids / charuco_corners; None when the frame showed no corner) or
     (ids, corners) pair of a CharucoBoard; keywords as calibrate_camera, or as calibrate_camera_fisheye with model="fisheye" """
-    obj, img = [], []
-    for v in views:
-        ids, corners = (v.charuco_ids, v.charuco_corners) if hasattr(v, "charuco_ids") else v
-        ids = np.zeros(0, np.uint32) if ids is None else np.asarray(ids, np.int64).reshape(-1)
-        corners = np.zeros((0, 2), np.float32) if corners is None else np.asarray(corners, np.float32).reshape(-1, 2)
-        obj.append(board.chessboard_corners[ids].astype(np.float32))
-        img.append(corners)
-    return _by_model(model)(obj, img, image_size, **kw)
+    pairs = [_solver.charuco_view(board, v) for v in views]
+    return _by_model(model)([o for o, _ in pairs], [i for _, i in pairs], image_size, **kw)

@@ -14,6 +14,7 @@
 
 #include "a3_common.h"
 #include "a3_internal.h"
+#include "a3_solve_check.h"
 
 namespace a3 {
 // k_threshold.hip
@@ -150,6 +151,30 @@ struct DevBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// Consecutive 256-byte-aligned segments of one DevBuf, for the solver entry points: each segment is declared once (add: n elements
+// of T, or n records of `elem` bytes seen as T) and then addressed by the handle that add returned, so no offset sum is written twice.
+// The copies and the memset go to the layout's stream.
+template <typename T> struct Seg { size_t off, n; };
+struct Layout {
+    DevBuf& buf;
+    hipStream_t stream;
+    size_t end = 0;
+    template <typename T> Seg<T> add(size_t n, size_t elem = sizeof(T)) {
+        const size_t off = (end + 255) & ~(size_t)255;
+        end = off + n * elem;
+        return {off, n};
+    }
+    hipError_t ensure() { return buf.ensure((end + 255) & ~(size_t)255); }   // (the last segment padded like the others)
+    template <typename T> T* at(Seg<T> s) const { return reinterpret_cast<T*>(buf.as<uint8_t>() + s.off); }
+    template <typename T> hipError_t upload(Seg<T> s, const T* src, size_t n) const {   // n: what the caller has, may be 0
+        return n ? hipMemcpyAsync(at(s), src, n * sizeof(T), hipMemcpyHostToDevice, stream) : hipSuccess;
+    }
+    template <typename T> hipError_t download(Seg<T> s, T* dst) const {   // dst: nullable
+        return dst ? hipMemcpyAsync(dst, at(s), s.n * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess;
+    }
+    template <typename T> hipError_t zero_from(Seg<T> s) const { return hipMemsetAsync(at(s), 0, end - s.off, stream); }   // s and all behind it
+};
+
 struct Chunk { uint32_t first, count; uint64_t darts; uint32_t max_frame_darts; };
 // One batch: the call and every setting it runs with, captured once when it starts (begin_batch) -- a setter called while the batch
 // is in flight applies to the next one -- and what its enqueue decided.  enqueue_front, enqueue_chain, enqueue_back (also when it is
@@ -235,6 +260,7 @@ struct a3_ctx {
     uint32_t inject_count = 0;
     Batch batch;                    // the batch in flight (or the last one)
     bool pending_trivial = false;   // a submitted batch with no frames / empty images
+    bool busy() const { return batch.active || pending_trivial; }   // a submitted batch has not been collected
     int resolve_full_ttl = 0;
     int entry_global_ttl = 0;   // > 0: a recent batch had a frame whose entry list did not fit LDS: use the global doubling rounds
     // device-side planning: the previous batch of this shape fitted one chunk with plan_darts darts, so this one is enqueued
@@ -321,16 +347,10 @@ struct a3_ctx {
     std::vector<a3_charuco_corner> h_charuco;
     std::vector<a3_charuco_pose> h_charuco_pose;
     bool charuco_valid = false, charuco_pose_valid = false;
-    // a3_calibrate_cameras: [cameras | view offsets | object points | image points], the per-view scratch, [results | views]
-    DevBuf calib_in, calib_scratch, calib_out;
-    // a3_calibrate_rigs: [rigs | cameras | observations | object points | image points], [table | per-observation | per-frame scratch],
-    // [results | camera results | frames | observation results]
-    DevBuf rig_in, rig_scratch, rig_out;
-    // a3_calibrate_hand_eyes: [problems | frames | object points | image points], the per-frame scratch, [results | frame results]
-    DevBuf handeye_in, handeye_scratch, handeye_out;
-    // a3_build_marker_maps: [maps | markers | observations | image corners | matrix offsets], [tables | per-observation | per-frame |
-    // per-marker scratch], the reduced systems (two n x n per map), [results | marker results | frames | observation results]
-    DevBuf map_in, map_scratch, map_big, map_out;
+    // The solver entry points (a3_calibrate_cameras ... a3_build_marker_maps): the call's staged input, the kernel's scratch, the
+    // maps' reduced systems (two n x n per map: sized very differently from the rest) and the results.  One set serves them all: each
+    // of these calls refuses to start while a batch is in flight and waits for its own work before it returns.
+    DevBuf solve_in, solve_scratch, solve_big, solve_out;
     // a3_rectify_frames: host-side source frames and host-side output staged on the device
     DevBuf rect_in, rect_out;
     uint32_t last_charuco_total = 0;   // sizes the speculative record read-back of the next batch
@@ -1148,7 +1168,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         if (charuco_total > staged) {   // the guess was short: the rest of the records, straight from the device
             A3_HIP(hipMemcpyAsync(ctx->h_charuco.data() + staged, ctx->charuco_buf.as<a3_charuco_corner>() + staged,
                                   (charuco_total - staged) * sizeof(a3_charuco_corner), hipMemcpyDeviceToHost, st));
-            A3_HIP(hipStreamSynchronize(st));
+            A3_HIP(hipStreamSynchronize(ctx->stream));
         }
         ctx->last_charuco_total = charuco_total;
     }
@@ -1168,7 +1188,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
             A3_HIP(hipMemcpyAsync(const_cast<float*>(h_undist_res), ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8, (size_t)total * 16,
                                   hipMemcpyDeviceToHost, st));
         }
-        A3_HIP(hipStreamSynchronize(st));
+        A3_HIP(hipStreamSynchronize(ctx->stream));
     }
     if (total) {
         memcpy(out, h_markers, (size_t)total * sizeof(a3_marker));
@@ -1216,85 +1236,38 @@ int run_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint3
     return finish_batch(ctx, out, poses, out_cap, per_frame_count, out_n);
 }
 
-// a3_calibrate_cameras and a3_calibrate_fisheye_cameras: the same validation and staging.  The fisheye model also checks the guess's
-// coefficients it does not read, and keeps the start's compacted points behind the per-view scratch.  Each message is two whole
-// literals, one per entry point, so the library's read-only data holds every message as it reads.
-int calibrate_impl(a3_ctx* ctx, uint32_t flag_mask, uint32_t guess_flag, bool fisheye, const a3_calib_camera* cams, size_t n_cams,
-                   const uint32_t* view_offsets, size_t n_views, const float* object_xy, const float* image_xy, a3_calib_result* results,
-                   a3_calib_view* views) {
-#define A3_CALIB_FAIL(tail) fail(ctx, A3_ERR_INVALID, fisheye ? "a3_calibrate_fisheye_cameras" tail : "a3_calibrate_cameras" tail)
+// a3_calibrate_cameras and a3_calibrate_fisheye_cameras: the same checks and staging.  The fisheye model keeps the start's compacted
+// points behind the per-view scratch.
+int calibrate_impl(a3_ctx* ctx, bool fisheye, const a3_calib_camera* cams, size_t n_cams, const uint32_t* view_offsets, size_t n_views,
+                   const float* object_xy, const float* image_xy, a3_calib_result* results, a3_calib_view* views) {
     if (!ctx) return A3_ERR_INVALID;
-    if (!cams || !view_offsets || !results) return A3_CALIB_FAIL(": null argument");
-    if (ctx->batch.active || ctx->pending_trivial) return A3_CALIB_FAIL(": a submitted batch has not been collected");
-    if (n_cams == 0 || n_cams > A3_CALIB_MAX_CAMERAS) return A3_CALIB_FAIL(": n_cams must be in 1..A3_CALIB_MAX_CAMERAS");
-    if (n_views == 0 || n_views > A3_CALIB_MAX_CALL_VIEWS) return A3_CALIB_FAIL(": n_views must be in 1..A3_CALIB_MAX_CALL_VIEWS");
-    if (view_offsets[0] != 0) return A3_CALIB_FAIL(": view_offsets[0] must be 0");
-    for (size_t i = 0; i < n_views; i++) {
-        if (view_offsets[i + 1] < view_offsets[i]) return A3_CALIB_FAIL(": view_offsets must not decrease");
-        if (view_offsets[i + 1] - view_offsets[i] > A3_CALIB_MAX_POINTS) return A3_CALIB_FAIL(": a view has more than A3_CALIB_MAX_POINTS points");
-    }
-    const size_t n_pts = view_offsets[n_views];
-    if (n_pts && (!object_xy || !image_xy)) return A3_CALIB_FAIL(": null point array");
-    for (size_t i = 0; i < 2 * n_pts; i++)
-        if (!std::isfinite(object_xy[i]) || !std::isfinite(image_xy[i])) return A3_CALIB_FAIL(": a point is not finite");
-    std::vector<uint8_t> owned(n_views, 0);
-    for (size_t c = 0; c < n_cams; c++) {
-        const a3_calib_camera& cam = cams[c];
-        if (cam.flags & flag_mask) return A3_CALIB_FAIL(": unknown flags");
-        if (cam.image_width == 0 || cam.image_height == 0 || cam.image_width > 65535 || cam.image_height > 65535)
-            return A3_CALIB_FAIL(": image size must be in 1..65535");
-        if (cam.max_iterations > A3_CALIB_MAX_ITERATIONS) return A3_CALIB_FAIL(": max_iterations above A3_CALIB_MAX_ITERATIONS");
-        if (cam.n_views == 0 || cam.n_views > A3_CALIB_MAX_VIEWS) return A3_CALIB_FAIL(": a camera's n_views must be in 1..A3_CALIB_MAX_VIEWS");
-        if ((uint64_t)cam.first_view + cam.n_views > n_views) return A3_CALIB_FAIL(": a camera's views lie past n_views");
-        for (uint32_t v = cam.first_view; v < cam.first_view + cam.n_views; v++) {
-            if (owned[v]) return A3_CALIB_FAIL(": two cameras share a view");
-            owned[v] = 1;
-        }
-        if (cam.flags & guess_flag) {
-            const a3_intrinsics& g = cam.guess;
-            const a3_distortion& d = cam.guess_distortion;
-            const float v[12] = {g.focal_x, g.focal_y, g.principal_x, g.principal_y, d.k1, d.k2, d.p1, d.p2, d.k3, d.k4, d.k5, d.k6};
-            for (float x : v)
-                if (!std::isfinite(x)) return A3_CALIB_FAIL(": the guess is not finite");
-            if (!(g.focal_x > 0.0f) || !(g.focal_y > 0.0f)) return A3_CALIB_FAIL(": the guess's focal lengths must be > 0");
-            if (fisheye && (d.p1 != 0.0f || d.p2 != 0.0f || d.k5 != 0.0f || d.k6 != 0.0f))
-                return A3_CALIB_FAIL(": the guess's lens reads k1 k2 k3 k4; p1, p2, k5 and k6 must be 0");
-        }
-    }
-#undef A3_CALIB_FAIL
+    size_t n_pts = 0;
+    if (const char* m = check_cameras(fisheye, ctx->busy(), cams, n_cams, view_offsets, n_views, object_xy, image_xy, results, n_pts))
+        return fail(ctx, A3_ERR_INVALID, m);
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_cams = up(n_cams * sizeof(a3_calib_camera)), b_off = up((n_views + 1) * sizeof(uint32_t)), b_pts = up(n_pts * 2 * sizeof(float));
-    const size_t b_res = up(n_cams * sizeof(a3_calib_result)), b_views = n_views * sizeof(a3_calib_view);
-    const size_t b_blocks = up(n_views * (fisheye ? fisheye_calib_view_bytes() : calib_view_bytes()));
-    A3_HIP(ctx->calib_in.ensure(b_cams + b_off + 2 * b_pts));
-    A3_HIP(ctx->calib_scratch.ensure(b_blocks + (fisheye ? 2 * b_pts : 0)));   // the per-view scratch, then the fisheye start's compacted points
-    A3_HIP(ctx->calib_out.ensure(b_res + b_views));
-    uint8_t* din = ctx->calib_in.as<uint8_t>();
-    uint8_t* dscr = ctx->calib_scratch.as<uint8_t>();
-    uint8_t* dout = ctx->calib_out.as<uint8_t>();
-    A3_HIP(hipMemcpyAsync(din, cams, n_cams * sizeof(a3_calib_camera), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_cams, view_offsets, (n_views + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (n_pts) {
-        A3_HIP(hipMemcpyAsync(din + b_cams + b_off, object_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        A3_HIP(hipMemcpyAsync(din + b_cams + b_off + b_pts, image_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
+    Layout in{ctx->solve_in, ctx->stream}, scr{ctx->solve_scratch, ctx->stream}, out{ctx->solve_out, ctx->stream};
+    const auto s_cams = in.add<a3_calib_camera>(n_cams);
+    const auto s_off = in.add<uint32_t>(n_views + 1);
+    const auto s_obj = in.add<float>(2 * n_pts), s_img = in.add<float>(2 * n_pts);
+    const auto s_blocks = scr.add<double>(n_views, fisheye ? fisheye_calib_view_bytes() : calib_view_bytes());
+    const auto s_start_obj = scr.add<float>(fisheye ? 2 * n_pts : 0), s_start_img = scr.add<float>(fisheye ? 2 * n_pts : 0);
+    const auto s_res = out.add<a3_calib_result>(n_cams);
+    const auto s_views = out.add<a3_calib_view>(n_views);
+    A3_HIP(in.ensure()); A3_HIP(scr.ensure()); A3_HIP(out.ensure());
+    A3_HIP(in.upload(s_cams, cams, n_cams));
+    A3_HIP(in.upload(s_off, view_offsets, n_views + 1));
+    A3_HIP(in.upload(s_obj, object_xy, 2 * n_pts)); A3_HIP(in.upload(s_img, image_xy, 2 * n_pts));
     // a view no camera owns is not written by the kernel: it comes back zero, not as what an earlier call left in the buffer
-    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_views, ctx->stream));
-    const a3_calib_camera* dcams = reinterpret_cast<const a3_calib_camera*>(din);
-    const uint32_t* doff = reinterpret_cast<const uint32_t*>(din + b_cams);
-    const float* dobj = reinterpret_cast<const float*>(din + b_cams + b_off);
-    const float* dimg = reinterpret_cast<const float*>(din + b_cams + b_off + b_pts);
-    a3_calib_result* dres = reinterpret_cast<a3_calib_result*>(dout);
-    a3_calib_view* dviews = reinterpret_cast<a3_calib_view*>(dout + b_res);
+    A3_HIP(out.zero_from(s_views));
     if (fisheye)
-        A3_HIP(launch_calibrate_fisheye(ctx->stream, dcams, (uint32_t)n_cams, doff, dobj, dimg, reinterpret_cast<double*>(dscr),
-                                        reinterpret_cast<float*>(dscr + b_blocks), reinterpret_cast<float*>(dscr + b_blocks + b_pts), dres, dviews));
+        A3_HIP(launch_calibrate_fisheye(ctx->stream, in.at(s_cams), (uint32_t)n_cams, in.at(s_off), in.at(s_obj), in.at(s_img), scr.at(s_blocks),
+                                        scr.at(s_start_obj), scr.at(s_start_img), out.at(s_res), out.at(s_views)));
     else
-        A3_HIP(launch_calibrate(ctx->stream, dcams, (uint32_t)n_cams, doff, dobj, dimg, reinterpret_cast<double*>(dscr), dres, dviews));
-    A3_HIP(hipMemcpyAsync(results, dout, n_cams * sizeof(a3_calib_result), hipMemcpyDeviceToHost, ctx->stream));
-    if (views) A3_HIP(hipMemcpyAsync(views, dout + b_res, b_views, hipMemcpyDeviceToHost, ctx->stream));
+        A3_HIP(launch_calibrate(ctx->stream, in.at(s_cams), (uint32_t)n_cams, in.at(s_off), in.at(s_obj), in.at(s_img), scr.at(s_blocks), out.at(s_res),
+                                out.at(s_views)));
+    A3_HIP(out.download(s_res, results));
+    A3_HIP(out.download(s_views, views));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }
@@ -1425,10 +1398,8 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->pre_xy, &ctx->fin_xy, &ctx->fin_count, &ctx->work, &ctx->outs, &ctx->proj, &ctx->patches, &ctx->cand_big,
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
-                      &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->calib_in,
-                      &ctx->calib_scratch, &ctx->calib_out, &ctx->rig_in, &ctx->rig_scratch, &ctx->rig_out,
-                      &ctx->handeye_in, &ctx->handeye_scratch, &ctx->handeye_out,
-                      &ctx->map_in, &ctx->map_scratch, &ctx->map_big, &ctx->map_out, &ctx->rect_in, &ctx->rect_out};
+                      &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->solve_in,
+                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1829,7 +1800,7 @@ int a3_debug_kernel_time(a3_ctx* ctx, int kernel, int dbg, int reps, float* avg_
                                  dbg == 0 ? -1000 : dbg, ctx->frames <= 64u ? 1 : 0));   // 0: k_projection + k_decode, < 0: k_decode alone (variant -dbg)
         } else return fail(ctx, A3_ERR_INVALID, "kernel: 0 dart_count, 1 dart_assign, 2 local_contract, 3 decode, 4 decode on cold frames");
         A3_HIP(hipEventRecord(e1, st));
-        A3_HIP(hipStreamSynchronize(st));
+        A3_HIP(hipStreamSynchronize(ctx->stream));
         float ms = 0;
         A3_HIP(hipEventElapsedTime(&ms, e0, e1));
         total += ms;
@@ -2237,7 +2208,7 @@ int a3_debug_frame_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t max_cand,
     A3_HIP(hipMemcpyAsync(work, d_work.p, slots * 4, hipMemcpyDeviceToHost, st));
     A3_HIP(hipMemcpyAsync(work_count, cnt + 2 * (size_t)n_frames, 4, hipMemcpyDeviceToHost, st));
     if (S) A3_HIP(hipMemcpyAsync(proj, d_proj.p, proj_bytes, hipMemcpyDeviceToHost, st));
-    A3_HIP(hipStreamSynchronize(st));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }
 
@@ -2613,112 +2584,47 @@ int a3_undistort_points(a3_ctx* ctx, const float* xy, size_t n, const a3_intrins
 
 int a3_calibrate_cameras(a3_ctx* ctx, const a3_calib_camera* cams, size_t n_cams, const uint32_t* view_offsets, size_t n_views,
                          const float* object_xy, const float* image_xy, a3_calib_result* results, a3_calib_view* views) {
-    return calibrate_impl(ctx, ~31u, A3_CALIB_USE_INTRINSIC_GUESS, false, cams, n_cams, view_offsets, n_views, object_xy, image_xy, results, views);
+    return calibrate_impl(ctx, false, cams, n_cams, view_offsets, n_views, object_xy, image_xy, results, views);
 }
 
 int a3_calibrate_fisheye_cameras(a3_ctx* ctx, const a3_calib_camera* cams, size_t n_cams, const uint32_t* view_offsets, size_t n_views,
                                  const float* object_xy, const float* image_xy, a3_calib_result* results, a3_calib_view* views) {
-    return calibrate_impl(ctx, ~63u, A3_FISHEYE_USE_INTRINSIC_GUESS, true, cams, n_cams, view_offsets, n_views, object_xy, image_xy, results, views);
+    return calibrate_impl(ctx, true, cams, n_cams, view_offsets, n_views, object_xy, image_xy, results, views);
 }
 
 int a3_calibrate_rigs(a3_ctx* ctx, const a3_rig* rigs, size_t n_rigs, const a3_rig_camera* cameras, size_t n_cameras, const a3_rig_observation* obs,
                       size_t n_obs, const float* object_xy, const float* image_xy, a3_rig_result* results, a3_rig_camera_result* camera_results,
                       a3_rig_frame* frames, a3_rig_observation_result* obs_results) {
     if (!ctx) return A3_ERR_INVALID;
-    if (!rigs || !cameras || !obs || !object_xy || !image_xy || !results || !camera_results)
-        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: null argument");
-    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a submitted batch has not been collected");
-    if (n_rigs == 0 || n_rigs > A3_RIG_MAX_RIGS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: n_rigs must be in 1..A3_RIG_MAX_RIGS");
-    if (n_cameras == 0 || n_cameras > (size_t)A3_RIG_MAX_RIGS * A3_RIG_MAX_CAMERAS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: n_cameras out of range");
-    if (n_obs == 0 || n_obs > A3_RIG_MAX_CALL_OBSERVATIONS)
-        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: n_obs must be in 1..A3_RIG_MAX_CALL_OBSERVATIONS");
-    size_t n_frames = 0;
-    for (size_t r = 0; r < n_rigs; r++) {
-        const a3_rig& R = rigs[r];
-        if (R.flags & ~3u) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: unknown flags");
-        if (R.n_cameras < 2 || R.n_cameras > A3_RIG_MAX_CAMERAS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's n_cameras must be in 2..A3_RIG_MAX_CAMERAS");
-        if (R.max_iterations > A3_CALIB_MAX_ITERATIONS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: max_iterations above A3_CALIB_MAX_ITERATIONS");
-        if (R.n_frames == 0 || R.n_frames > A3_RIG_MAX_FRAMES) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's n_frames must be in 1..A3_RIG_MAX_FRAMES");
-        if (R.n_obs == 0) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig has no observations");
-        if ((uint64_t)R.first_camera + R.n_cameras > n_cameras) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's cameras lie past n_cameras");
-        if ((uint64_t)R.first_obs + R.n_obs > n_obs) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's observations lie past n_obs");
-        if ((uint64_t)R.first_frame + R.n_frames > A3_RIG_MAX_CALL_FRAMES)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a rig's frames lie past A3_RIG_MAX_CALL_FRAMES");
-        n_frames = std::max(n_frames, (size_t)R.first_frame + R.n_frames);
-    }
-    std::vector<uint8_t> cam_owned(n_cameras, 0), frame_owned(n_frames, 0), obs_owned(n_obs, 0), seen(n_frames * A3_RIG_MAX_CAMERAS, 0);
-    size_t n_pts = 0;
-    for (size_t r = 0; r < n_rigs; r++) {
-        const a3_rig& R = rigs[r];
-        for (uint32_t c = R.first_camera; c < R.first_camera + R.n_cameras; c++) {
-            if (cam_owned[c]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: two rigs share a camera");
-            cam_owned[c] = 1;
-            for (double v : cameras[c].a)
-                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a camera's intrinsics are not finite");
-            if (!(cameras[c].a[0] > 0.0) || !(cameras[c].a[1] > 0.0)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: focal lengths must be > 0");
-            if (R.flags && c > R.first_camera) {
-                for (double v : cameras[c].guess_rotation)
-                    if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: the extrinsic guess is not finite");
-                for (double v : cameras[c].guess_translation)
-                    if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: the extrinsic guess is not finite");
-            }
-        }
-        for (uint32_t f = R.first_frame; f < R.first_frame + R.n_frames; f++) {
-            if (frame_owned[f]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: two rigs share a frame");
-            frame_owned[f] = 1;
-        }
-        for (uint32_t o = R.first_obs; o < R.first_obs + R.n_obs; o++) {
-            if (obs_owned[o]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: two rigs share an observation");
-            obs_owned[o] = 1;
-            const a3_rig_observation& ob = obs[o];
-            if (ob.camera < R.first_camera || ob.camera - R.first_camera >= R.n_cameras)
-                return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: an observation's camera lies outside its rig");
-            if (ob.frame < R.first_frame || ob.frame - R.first_frame >= R.n_frames)
-                return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: an observation's frame lies outside its rig");
-            if (ob.n_points > A3_CALIB_MAX_POINTS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: an observation has more than A3_CALIB_MAX_POINTS points");
-            if ((uint64_t)ob.first_point + ob.n_points > 0xffffffffull) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: an observation's points lie past 2^32");
-            uint8_t& dup = seen[(size_t)ob.frame * A3_RIG_MAX_CAMERAS + (ob.camera - R.first_camera)];
-            if (dup) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: two observations of one (camera, frame)");
-            dup = 1;
-            for (size_t i = 2 * (size_t)ob.first_point; i < 2 * ((size_t)ob.first_point + ob.n_points); i++)
-                if (!std::isfinite(object_xy[i]) || !std::isfinite(image_xy[i])) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_rigs: a point is not finite");
-            n_pts = std::max(n_pts, (size_t)ob.first_point + ob.n_points);
-        }
-    }
+    size_t n_frames = 0, n_pts = 0;
+    if (const char* m = check_rigs(ctx->busy(), rigs, n_rigs, cameras, n_cameras, obs, n_obs, object_xy, image_xy, results, camera_results, n_frames, n_pts))
+        return fail(ctx, A3_ERR_INVALID, m);
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_rigs = up(n_rigs * sizeof(a3_rig)), b_cams = up(n_cameras * sizeof(a3_rig_camera)), b_obs = up(n_obs * sizeof(a3_rig_observation));
-    const size_t b_pts = up(std::max<size_t>(n_pts, 1) * 2 * sizeof(float));
-    const size_t b_res = up(n_rigs * sizeof(a3_rig_result)), b_cres = up(n_cameras * sizeof(a3_rig_camera_result));
-    const size_t b_frames = up(n_frames * sizeof(a3_rig_frame)), b_ores = up(n_obs * sizeof(a3_rig_observation_result));
-    const size_t b_tab = up(n_frames * rig_table_bytes()), b_oscr = up(n_obs * rig_obs_bytes()), b_fscr = up(n_frames * rig_frame_bytes());
-    A3_HIP(ctx->rig_in.ensure(b_rigs + b_cams + b_obs + 2 * b_pts));
-    A3_HIP(ctx->rig_scratch.ensure(b_tab + b_oscr + b_fscr));
-    A3_HIP(ctx->rig_out.ensure(b_res + b_cres + b_frames + b_ores));
-    uint8_t* din = ctx->rig_in.as<uint8_t>();
-    uint8_t* dscr = ctx->rig_scratch.as<uint8_t>();
-    uint8_t* dout = ctx->rig_out.as<uint8_t>();
-    A3_HIP(hipMemcpyAsync(din, rigs, n_rigs * sizeof(a3_rig), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_rigs, cameras, n_cameras * sizeof(a3_rig_camera), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_rigs + b_cams, obs, n_obs * sizeof(a3_rig_observation), hipMemcpyHostToDevice, ctx->stream));
-    if (n_pts) {
-        A3_HIP(hipMemcpyAsync(din + b_rigs + b_cams + b_obs, object_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        A3_HIP(hipMemcpyAsync(din + b_rigs + b_cams + b_obs + b_pts, image_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
+    Layout in{ctx->solve_in, ctx->stream}, scr{ctx->solve_scratch, ctx->stream}, out{ctx->solve_out, ctx->stream};
+    const auto s_rigs = in.add<a3_rig>(n_rigs);
+    const auto s_cams = in.add<a3_rig_camera>(n_cameras);
+    const auto s_obs = in.add<a3_rig_observation>(n_obs);
+    const auto s_obj = in.add<float>(2 * std::max<size_t>(n_pts, 1)), s_img = in.add<float>(2 * std::max<size_t>(n_pts, 1));
+    const auto s_tab = scr.add<uint32_t>(n_frames, rig_table_bytes());
+    const auto s_oscr = scr.add<double>(n_obs, rig_obs_bytes()), s_fscr = scr.add<double>(n_frames, rig_frame_bytes());
+    const auto s_res = out.add<a3_rig_result>(n_rigs);
+    const auto s_cres = out.add<a3_rig_camera_result>(n_cameras);
+    const auto s_frames = out.add<a3_rig_frame>(n_frames);
+    const auto s_ores = out.add<a3_rig_observation_result>(n_obs);
+    A3_HIP(in.ensure()); A3_HIP(scr.ensure()); A3_HIP(out.ensure());
+    A3_HIP(in.upload(s_rigs, rigs, n_rigs));
+    A3_HIP(in.upload(s_cams, cameras, n_cameras));
+    A3_HIP(in.upload(s_obs, obs, n_obs));
+    A3_HIP(in.upload(s_obj, object_xy, 2 * n_pts)); A3_HIP(in.upload(s_img, image_xy, 2 * n_pts));
     // a camera, frame or observation that no rig owns is not written by the kernel: it comes back zero
-    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_cres + b_frames + b_ores, ctx->stream));
-    A3_HIP(launch_rig(ctx->stream, reinterpret_cast<const a3_rig*>(din), (uint32_t)n_rigs, reinterpret_cast<const a3_rig_camera*>(din + b_rigs),
-                      reinterpret_cast<const a3_rig_observation*>(din + b_rigs + b_cams), reinterpret_cast<const float*>(din + b_rigs + b_cams + b_obs),
-                      reinterpret_cast<const float*>(din + b_rigs + b_cams + b_obs + b_pts), reinterpret_cast<uint32_t*>(dscr),
-                      reinterpret_cast<double*>(dscr + b_tab), reinterpret_cast<double*>(dscr + b_tab + b_oscr), reinterpret_cast<a3_rig_result*>(dout),
-                      reinterpret_cast<a3_rig_camera_result*>(dout + b_res), reinterpret_cast<a3_rig_frame*>(dout + b_res + b_cres),
-                      reinterpret_cast<a3_rig_observation_result*>(dout + b_res + b_cres + b_frames)));
-    A3_HIP(hipMemcpyAsync(results, dout, n_rigs * sizeof(a3_rig_result), hipMemcpyDeviceToHost, ctx->stream));
-    A3_HIP(hipMemcpyAsync(camera_results, dout + b_res, n_cameras * sizeof(a3_rig_camera_result), hipMemcpyDeviceToHost, ctx->stream));
-    if (frames) A3_HIP(hipMemcpyAsync(frames, dout + b_res + b_cres, n_frames * sizeof(a3_rig_frame), hipMemcpyDeviceToHost, ctx->stream));
-    if (obs_results)
-        A3_HIP(hipMemcpyAsync(obs_results, dout + b_res + b_cres + b_frames, n_obs * sizeof(a3_rig_observation_result), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(out.zero_from(s_cres));
+    A3_HIP(launch_rig(ctx->stream, in.at(s_rigs), (uint32_t)n_rigs, in.at(s_cams), in.at(s_obs), in.at(s_obj), in.at(s_img), scr.at(s_tab), scr.at(s_oscr),
+                      scr.at(s_fscr), out.at(s_res), out.at(s_cres), out.at(s_frames), out.at(s_ores)));
+    A3_HIP(out.download(s_res, results));
+    A3_HIP(out.download(s_cres, camera_results));
+    A3_HIP(out.download(s_frames, frames));
+    A3_HIP(out.download(s_ores, obs_results));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }
@@ -2726,79 +2632,28 @@ int a3_calibrate_rigs(a3_ctx* ctx, const a3_rig* rigs, size_t n_rigs, const a3_r
 int a3_calibrate_hand_eyes(a3_ctx* ctx, const a3_handeye_problem* problems, size_t n_problems, const a3_handeye_frame* frames, size_t n_frames,
                            const float* object_xy, const float* image_xy, a3_handeye_result* results, a3_handeye_frame_result* frame_results) {
     if (!ctx) return A3_ERR_INVALID;
-    if (!problems || !frames || !object_xy || !image_xy || !results) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: null argument");
-    if (ctx->batch.active || ctx->pending_trivial)
-        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a submitted batch has not been collected");
-    if (n_problems == 0 || n_problems > A3_HANDEYE_MAX_PROBLEMS)
-        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: n_problems must be in 1..A3_HANDEYE_MAX_PROBLEMS");
-    if (n_frames == 0 || n_frames > A3_HANDEYE_MAX_CALL_FRAMES)
-        return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: n_frames must be in 1..A3_HANDEYE_MAX_CALL_FRAMES");
-    std::vector<uint8_t> frame_owned(n_frames, 0);
     size_t n_pts = 0;
-    for (size_t r = 0; r < n_problems; r++) {
-        const a3_handeye_problem& R = problems[r];
-        if (R.flags & ~3u) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: unknown flags");
-        if (R.max_iterations > A3_CALIB_MAX_ITERATIONS)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: max_iterations above A3_CALIB_MAX_ITERATIONS");
-        if (R.n_frames == 0 || R.n_frames > A3_HANDEYE_MAX_FRAMES)
-            return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a problem's n_frames must be in 1..A3_HANDEYE_MAX_FRAMES");
-        if ((uint64_t)R.first_frame + R.n_frames > n_frames) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a problem's frames lie past n_frames");
-        for (double v : R.a)
-            if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the camera's intrinsics are not finite");
-        if (!(R.a[0] > 0.0) || !(R.a[1] > 0.0)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: focal lengths must be > 0");
-        if (R.flags) {
-            for (double v : R.guess_x_rotation)
-                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the guess is not finite");
-            for (double v : R.guess_x_translation)
-                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the guess is not finite");
-        }
-        if (R.flags & A3_HANDEYE_USE_GUESS) {
-            for (double v : R.guess_y_rotation)
-                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the guess is not finite");
-            for (double v : R.guess_y_translation)
-                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: the guess is not finite");
-        }
-        for (uint32_t f = R.first_frame; f < R.first_frame + R.n_frames; f++) {
-            if (frame_owned[f]) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: two problems share a frame");
-            frame_owned[f] = 1;
-            const a3_handeye_frame& fr = frames[f];
-            for (double v : fr.rotation)
-                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a frame's robot pose is not finite");
-            for (double v : fr.translation)
-                if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a frame's robot pose is not finite");
-            if (fr.n_points > A3_CALIB_MAX_POINTS) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a frame has more than A3_CALIB_MAX_POINTS points");
-            if ((uint64_t)fr.first_point + fr.n_points > 0xffffffffull) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a frame's points lie past 2^32");
-            for (size_t i = 2 * (size_t)fr.first_point; i < 2 * ((size_t)fr.first_point + fr.n_points); i++)
-                if (!std::isfinite(object_xy[i]) || !std::isfinite(image_xy[i])) return fail(ctx, A3_ERR_INVALID, "a3_calibrate_hand_eyes: a point is not finite");
-            n_pts = std::max(n_pts, (size_t)fr.first_point + fr.n_points);
-        }
-    }
+    if (const char* m = check_hand_eyes(ctx->busy(), problems, n_problems, frames, n_frames, object_xy, image_xy, results, n_pts))
+        return fail(ctx, A3_ERR_INVALID, m);
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_probs = up(n_problems * sizeof(a3_handeye_problem)), b_frames = up(n_frames * sizeof(a3_handeye_frame));
-    const size_t b_pts = up(std::max<size_t>(n_pts, 1) * 2 * sizeof(float));
-    const size_t b_res = up(n_problems * sizeof(a3_handeye_result)), b_fres = up(n_frames * sizeof(a3_handeye_frame_result));
-    A3_HIP(ctx->handeye_in.ensure(b_probs + b_frames + 2 * b_pts));
-    A3_HIP(ctx->handeye_scratch.ensure(up(n_frames * handeye_frame_bytes())));
-    A3_HIP(ctx->handeye_out.ensure(b_res + b_fres));
-    uint8_t* din = ctx->handeye_in.as<uint8_t>();
-    uint8_t* dout = ctx->handeye_out.as<uint8_t>();
-    A3_HIP(hipMemcpyAsync(din, problems, n_problems * sizeof(a3_handeye_problem), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_probs, frames, n_frames * sizeof(a3_handeye_frame), hipMemcpyHostToDevice, ctx->stream));
-    if (n_pts) {
-        A3_HIP(hipMemcpyAsync(din + b_probs + b_frames, object_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        A3_HIP(hipMemcpyAsync(din + b_probs + b_frames + b_pts, image_xy, n_pts * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
+    Layout in{ctx->solve_in, ctx->stream}, scr{ctx->solve_scratch, ctx->stream}, out{ctx->solve_out, ctx->stream};
+    const auto s_probs = in.add<a3_handeye_problem>(n_problems);
+    const auto s_frames = in.add<a3_handeye_frame>(n_frames);
+    const auto s_obj = in.add<float>(2 * std::max<size_t>(n_pts, 1)), s_img = in.add<float>(2 * std::max<size_t>(n_pts, 1));
+    const auto s_fscr = scr.add<double>(n_frames, handeye_frame_bytes());
+    const auto s_res = out.add<a3_handeye_result>(n_problems);
+    const auto s_fres = out.add<a3_handeye_frame_result>(n_frames);
+    A3_HIP(in.ensure()); A3_HIP(scr.ensure()); A3_HIP(out.ensure());
+    A3_HIP(in.upload(s_probs, problems, n_problems));
+    A3_HIP(in.upload(s_frames, frames, n_frames));
+    A3_HIP(in.upload(s_obj, object_xy, 2 * n_pts)); A3_HIP(in.upload(s_img, image_xy, 2 * n_pts));
     // a frame that no problem owns is not written by the kernel: it comes back zero
-    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_fres, ctx->stream));
-    A3_HIP(launch_handeye(ctx->stream, reinterpret_cast<const a3_handeye_problem*>(din), (uint32_t)n_problems,
-                          reinterpret_cast<const a3_handeye_frame*>(din + b_probs), reinterpret_cast<const float*>(din + b_probs + b_frames),
-                          reinterpret_cast<const float*>(din + b_probs + b_frames + b_pts), ctx->handeye_scratch.as<double>(),
-                          reinterpret_cast<a3_handeye_result*>(dout), reinterpret_cast<a3_handeye_frame_result*>(dout + b_res)));
-    A3_HIP(hipMemcpyAsync(results, dout, n_problems * sizeof(a3_handeye_result), hipMemcpyDeviceToHost, ctx->stream));
-    if (frame_results)
-        A3_HIP(hipMemcpyAsync(frame_results, dout + b_res, n_frames * sizeof(a3_handeye_frame_result), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(out.zero_from(s_fres));
+    A3_HIP(launch_handeye(ctx->stream, in.at(s_probs), (uint32_t)n_problems, in.at(s_frames), in.at(s_obj), in.at(s_img), scr.at(s_fscr), out.at(s_res),
+                          out.at(s_fres)));
+    A3_HIP(out.download(s_res, results));
+    A3_HIP(out.download(s_fres, frame_results));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }
@@ -2807,105 +2662,43 @@ int a3_build_marker_maps(a3_ctx* ctx, const a3_map* maps, size_t n_maps, const a
                          size_t n_obs, const float* image_xy, a3_map_result* results, a3_map_marker_result* marker_results, a3_map_frame* frames,
                          a3_map_observation_result* obs_results) {
     if (!ctx) return A3_ERR_INVALID;
-    if (!maps || !markers || !obs || !image_xy || !results || !marker_results) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: null argument");
-    if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a submitted batch has not been collected");
-    if (n_maps == 0 || n_maps > A3_MAP_MAX_MAPS) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: n_maps must be in 1..A3_MAP_MAX_MAPS");
-    if (n_markers == 0 || n_markers > (size_t)A3_MAP_MAX_MAPS * A3_MAP_MAX_MARKERS) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: n_markers out of range");
-    if (n_obs == 0 || n_obs > A3_MAP_MAX_CALL_OBSERVATIONS)
-        return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: n_obs must be in 1..A3_MAP_MAX_CALL_OBSERVATIONS");
     size_t n_frames = 0;
-    for (size_t r = 0; r < n_maps; r++) {
-        const a3_map& R = maps[r];
-        if (R.flags & ~3u) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: unknown flags");
-        if (R.n_markers < 1 || R.n_markers > A3_MAP_MAX_MARKERS) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's n_markers must be in 1..A3_MAP_MAX_MARKERS");
-        if (R.max_iterations > A3_CALIB_MAX_ITERATIONS) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: max_iterations above A3_CALIB_MAX_ITERATIONS");
-        if (R.n_frames == 0 || R.n_frames > A3_MAP_MAX_FRAMES) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's n_frames must be in 1..A3_MAP_MAX_FRAMES");
-        if (R.n_obs == 0) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map has no observations");
-        if ((uint64_t)R.first_marker + R.n_markers > n_markers) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's markers lie past n_markers");
-        if ((uint64_t)R.first_obs + R.n_obs > n_obs) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's observations lie past n_obs");
-        if ((uint64_t)R.first_frame + R.n_frames > A3_MAP_MAX_CALL_FRAMES)
-            return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's frames lie past A3_MAP_MAX_CALL_FRAMES");
-        for (double v : R.a)
-            if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: the camera's intrinsics are not finite");
-        if (!(R.a[0] > 0.0) || !(R.a[1] > 0.0)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: focal lengths must be > 0");
-        if (!std::isfinite(R.marker_length) || !(R.marker_length > 0.0f)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: marker_length must be finite and > 0");
-        n_frames = std::max(n_frames, (size_t)R.first_frame + R.n_frames);
-    }
-    std::vector<uint8_t> marker_owned(n_markers, 0), frame_owned(n_frames, 0), obs_owned(n_obs, 0);
-    std::vector<uint64_t> big_off(n_maps, 0);
+    std::vector<uint64_t> big_off;
     uint64_t big_doubles = 0;
-    for (size_t r = 0; r < n_maps; r++) {
-        const a3_map& R = maps[r];
-        for (uint32_t m = R.first_marker; m < R.first_marker + R.n_markers; m++) {
-            if (marker_owned[m]) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: two maps share a marker");
-            marker_owned[m] = 1;
-            if (R.flags && m > R.first_marker) {
-                for (double v : markers[m].guess_rotation)
-                    if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: the marker guess is not finite");
-                for (double v : markers[m].guess_translation)
-                    if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: the marker guess is not finite");
-            }
-        }
-        for (uint32_t f = R.first_frame; f < R.first_frame + R.n_frames; f++) {
-            if (frame_owned[f]) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: two maps share a frame");
-            frame_owned[f] = 1;
-        }
-        for (uint32_t o = R.first_obs; o < R.first_obs + R.n_obs; o++) {
-            if (obs_owned[o]) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: two maps share an observation");
-            obs_owned[o] = 1;
-            const a3_map_observation& ob = obs[o];
-            if (ob.marker < R.first_marker || ob.marker - R.first_marker >= R.n_markers)
-                return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: an observation's marker lies outside its map");
-            if (ob.frame < R.first_frame || ob.frame - R.first_frame >= R.n_frames)
-                return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: an observation's frame lies outside its map");
-            if (o > R.first_obs) {
-                const a3_map_observation& pv = obs[o - 1];
-                if (pv.frame == ob.frame && pv.marker == ob.marker) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: two observations of one (marker, frame)");
-                if (pv.frame > ob.frame || (pv.frame == ob.frame && pv.marker > ob.marker))
-                    return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a map's observations must be listed by frame, then by marker");
-            }
-            for (size_t i = 8 * (size_t)o; i < 8 * ((size_t)o + 1); i++)
-                if (!std::isfinite(image_xy[i])) return fail(ctx, A3_ERR_INVALID, "a3_build_marker_maps: a corner is not finite");
-        }
-        const uint64_t nmax = (R.flags & A3_MAP_FIX_MAP) ? 0 : 6ull * (R.n_markers - 1);
-        big_off[r] = big_doubles;
-        big_doubles += 2 * nmax * nmax;
-    }
+    if (const char* m = check_marker_maps(ctx->busy(), maps, n_maps, markers, n_markers, obs, n_obs, image_xy, results, marker_results, n_frames, big_off,
+                                          big_doubles))
+        return fail(ctx, A3_ERR_INVALID, m);
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_maps = up(n_maps * sizeof(a3_map)), b_mk = up(n_markers * sizeof(a3_map_marker)), b_obs = up(n_obs * sizeof(a3_map_observation));
-    const size_t b_img = up(n_obs * 8 * sizeof(float)), b_off = up(n_maps * sizeof(uint64_t));
-    const size_t b_res = up(n_maps * sizeof(a3_map_result)), b_mres = up(n_markers * sizeof(a3_map_marker_result));
-    const size_t b_frames = up(n_frames * sizeof(a3_map_frame)), b_ores = up(n_obs * sizeof(a3_map_observation_result));
-    const size_t b_fo = up(n_frames * sizeof(uint32_t)), b_ml = up(n_obs * sizeof(uint32_t));
-    const size_t b_oscr = up(n_obs * map_obs_bytes()), b_fscr = up(n_frames * map_frame_bytes()), b_mscr = up(n_markers * map_marker_bytes());
-    A3_HIP(ctx->map_in.ensure(b_maps + b_mk + b_obs + b_img + b_off));
-    A3_HIP(ctx->map_scratch.ensure(b_fo + b_ml + b_oscr + b_fscr + b_mscr));
-    A3_HIP(ctx->map_big.ensure(std::max<size_t>(big_doubles, 1) * sizeof(double)));
-    A3_HIP(ctx->map_out.ensure(b_res + b_mres + b_frames + b_ores));
-    uint8_t* din = ctx->map_in.as<uint8_t>();
-    uint8_t* dscr = ctx->map_scratch.as<uint8_t>();
-    uint8_t* dout = ctx->map_out.as<uint8_t>();
-    A3_HIP(hipMemcpyAsync(din, maps, n_maps * sizeof(a3_map), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_maps, markers, n_markers * sizeof(a3_map_marker), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_maps + b_mk, obs, n_obs * sizeof(a3_map_observation), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_maps + b_mk + b_obs, image_xy, n_obs * 8 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(hipMemcpyAsync(din + b_maps + b_mk + b_obs + b_img, big_off.data(), n_maps * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    Layout in{ctx->solve_in, ctx->stream}, scr{ctx->solve_scratch, ctx->stream}, out{ctx->solve_out, ctx->stream};
+    const auto s_maps = in.add<a3_map>(n_maps);
+    const auto s_mk = in.add<a3_map_marker>(n_markers);
+    const auto s_obs = in.add<a3_map_observation>(n_obs);
+    const auto s_img = in.add<float>(8 * n_obs);
+    const auto s_off = in.add<uint64_t>(n_maps);
+    const auto s_fo = scr.add<uint32_t>(n_frames), s_ml = scr.add<uint32_t>(n_obs);
+    const auto s_oscr = scr.add<double>(n_obs, map_obs_bytes()), s_fscr = scr.add<double>(n_frames, map_frame_bytes());
+    const auto s_mscr = scr.add<double>(n_markers, map_marker_bytes());
+    const auto s_res = out.add<a3_map_result>(n_maps);
+    const auto s_mres = out.add<a3_map_marker_result>(n_markers);
+    const auto s_frames = out.add<a3_map_frame>(n_frames);
+    const auto s_ores = out.add<a3_map_observation_result>(n_obs);
+    A3_HIP(in.ensure()); A3_HIP(scr.ensure()); A3_HIP(out.ensure());
+    A3_HIP(ctx->solve_big.ensure(std::max<size_t>(big_doubles, 1) * sizeof(double)));
+    A3_HIP(in.upload(s_maps, maps, n_maps));
+    A3_HIP(in.upload(s_mk, markers, n_markers));
+    A3_HIP(in.upload(s_obs, obs, n_obs));
+    A3_HIP(in.upload(s_img, image_xy, 8 * n_obs));
+    A3_HIP(in.upload(s_off, big_off.data(), n_maps));
     // a marker, frame or observation that no map owns is not written by the kernel: it comes back zero
-    A3_HIP(hipMemsetAsync(dout + b_res, 0, b_mres + b_frames + b_ores, ctx->stream));
-    A3_HIP(launch_map(ctx->stream, reinterpret_cast<const a3_map*>(din), (uint32_t)n_maps, reinterpret_cast<const a3_map_marker*>(din + b_maps),
-                      reinterpret_cast<const a3_map_observation*>(din + b_maps + b_mk), reinterpret_cast<const float*>(din + b_maps + b_mk + b_obs),
-                      reinterpret_cast<const uint64_t*>(din + b_maps + b_mk + b_obs + b_img), reinterpret_cast<uint32_t*>(dscr),
-                      reinterpret_cast<uint32_t*>(dscr + b_fo), reinterpret_cast<double*>(dscr + b_fo + b_ml),
-                      reinterpret_cast<double*>(dscr + b_fo + b_ml + b_oscr), reinterpret_cast<double*>(dscr + b_fo + b_ml + b_oscr + b_fscr),
-                      ctx->map_big.as<double>(), reinterpret_cast<a3_map_result*>(dout), reinterpret_cast<a3_map_marker_result*>(dout + b_res),
-                      reinterpret_cast<a3_map_frame*>(dout + b_res + b_mres), reinterpret_cast<a3_map_observation_result*>(dout + b_res + b_mres + b_frames)));
-    A3_HIP(hipMemcpyAsync(results, dout, n_maps * sizeof(a3_map_result), hipMemcpyDeviceToHost, ctx->stream));
-    A3_HIP(hipMemcpyAsync(marker_results, dout + b_res, n_markers * sizeof(a3_map_marker_result), hipMemcpyDeviceToHost, ctx->stream));
-    if (frames) A3_HIP(hipMemcpyAsync(frames, dout + b_res + b_mres, n_frames * sizeof(a3_map_frame), hipMemcpyDeviceToHost, ctx->stream));
-    if (obs_results)
-        A3_HIP(hipMemcpyAsync(obs_results, dout + b_res + b_mres + b_frames, n_obs * sizeof(a3_map_observation_result), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(out.zero_from(s_mres));
+    A3_HIP(launch_map(ctx->stream, in.at(s_maps), (uint32_t)n_maps, in.at(s_mk), in.at(s_obs), in.at(s_img), in.at(s_off), scr.at(s_fo), scr.at(s_ml),
+                      scr.at(s_oscr), scr.at(s_fscr), scr.at(s_mscr), ctx->solve_big.as<double>(), out.at(s_res), out.at(s_mres), out.at(s_frames),
+                      out.at(s_ores)));
+    A3_HIP(out.download(s_res, results));
+    A3_HIP(out.download(s_mres, marker_results));
+    A3_HIP(out.download(s_frames, frames));
+    A3_HIP(out.download(s_ores, obs_results));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _solver
 from . import calibration as _cal
 from .rig import camera_params
 
@@ -131,10 +131,7 @@ def _robot_to_M(pose, setup):
 
 
 def _solve(*args):
-    with _cal._ctx_lock:
-        if _cal._ctx is None:
-            _cal._ctx = _lib.Context(_lib.default_config(), np.zeros(1, np.uint64), 64, 1)
-        return _cal._ctx.calibrate_hand_eyes(*args)
+    return _solver.call("calibrate_hand_eyes", *args)
 
 
 def calibrate_hand_eyes(problems: Sequence[dict]) -> List[HandEyeCalibration]:
@@ -184,31 +181,23 @@ def calibrate_hand_eyes(problems: Sequence[dict]) -> List[HandEyeCalibration]:
         P = probs[r]
         P.first_frame, P.n_frames, P.flags, P.max_iterations = f0, F, flags, int(pr.get("max_iterations") or 0)
         P.a[:] = [float(v) for v in a]
-        P.guess_x_rotation[:] = [float(v) for v in gx[0].reshape(9)]
-        P.guess_x_translation[:] = [float(v) for v in gx[1].reshape(3)]
-        P.guess_y_rotation[:] = [float(v) for v in gy[0].reshape(9)]
-        P.guess_y_translation[:] = [float(v) for v in gy[1].reshape(3)]
+        _solver.set_pose(P, gx, "guess_x_")
+        _solver.set_pose(P, gy, "guess_y_")
         for j, pose in enumerate(poses):
-            M = _robot_to_M(pose, setup)
             fr = frames[f0 + j]
-            fr.rotation[:] = [float(v) for v in M[0].reshape(9)]
-            fr.translation[:] = [float(v) for v in M[1].reshape(3)]
+            _solver.set_pose(fr, _robot_to_M(pose, setup))
             fr.first_point, fr.n_points = p0, len(o[j])
             p0 += len(o[j])
         obj += o
         img += i
         spans.append((f0, F, setup, a))
         f0 += F
-    cat = lambda v: np.concatenate(v) if v else np.zeros((0, 2), np.float32)   # noqa: E731
-    res, fres = _solve(probs, frames, cat(obj), cat(img))
+    res, fres = _solve(probs, frames, _solver.cat_points(obj), _solver.cat_points(img))
     out = []
     for r, (ff, F, setup, a) in enumerate(spans):
         q = res[r]
-        fr = [HandEyeFrameResult(int(f.status), int(f.points), float(f.rms_px), np.array(f.rotation, np.float64).reshape(3, 3),
-                                 np.array(f.translation, np.float64)) for f in (fres[ff + j] for j in range(F))]
-        out.append(HandEyeCalibration(int(q.status), setup, a, (np.array(q.x_rotation, np.float64).reshape(3, 3), np.array(q.x_translation, np.float64)),
-                                      (np.array(q.y_rotation, np.float64).reshape(3, 3), np.array(q.y_translation, np.float64)),
-                                      np.array(q.std_dev, np.float64), float(q.rms_px), int(q.iterations), bool(q.converged), int(q.frames_used),
+        fr = [HandEyeFrameResult(int(f.status), int(f.points), float(f.rms_px), *_solver.get_pose(f)) for f in (fres[ff + j] for j in range(F))]
+        out.append(HandEyeCalibration(int(q.status), setup, a, _solver.get_pose(q, "x_"), _solver.get_pose(q, "y_"), np.array(q.std_dev, np.float64), float(q.rms_px), int(q.iterations), bool(q.converged), int(q.frames_used),
                                       int(q.points_used), int(q.pairs_used), fr))
     return out
 
@@ -228,23 +217,16 @@ def calibrate_hand_eye(camera, robot_poses, observations, *, setup: str = "eye_i
     points of each frame the last solve used."""
     kw = dict(camera=camera, robot_poses=robot_poses, setup=setup, guess=guess, fix_mount=fix_mount, max_iterations=max_iterations)
     obj, img = _cal._views([ob[0] for ob in observations], [ob[1] for ob in observations])
-    keep = [np.ones(len(o), bool) for o in obj]
-    solve = lambda: calibrate_hand_eyes([dict(observations=[(o[k], i[k]) for o, i, k in zip(obj, img, keep)], **kw)])[0]   # noqa: E731
-    he = solve()
-    for _ in range(int(outlier_passes)):
-        if not he.ok:
-            break
-        for j, f in enumerate(he.frames):
-            if not f.used:
-                continue
-            R, t = he.board_pose_in_camera(robot_poses[j])
-            e = np.linalg.norm(_cal.reproject(he.camera, R, t, obj[j][keep[j]]) - img[j][keep[j]], axis=1)
-            idx = np.nonzero(keep[j])[0]
-            keep[j][idx[~(e < max(1.0, 3.0 * float(np.median(e))))]] = False
-        he = solve()
-    if outlier_passes:
-        he.inliers = keep
-    return he
+
+    def residuals(he, j, k):
+        if not he.frames[j].used:
+            return None
+        R, t = he.board_pose_in_camera(robot_poses[j])
+        return np.linalg.norm(_cal.reproject(he.camera, R, t, obj[j][k]) - img[j][k], axis=1)
+
+    return _solver.solve_with_outlier_passes(
+        [len(o) for o in obj], lambda keep: calibrate_hand_eyes([dict(observations=[(o[k], i[k]) for o, i, k in zip(obj, img, keep)], **kw)])[0],
+        residuals, outlier_passes)
 
 
 def calibrate_hand_eye_board(board, detections, robot_poses, calibration, **kw) -> HandEyeCalibration:
@@ -257,10 +239,4 @@ def calibrate_hand_eye_board(board, detections, robot_poses, calibration, **kw) 
 def calibrate_hand_eye_charuco(board, views, robot_poses, calibration, **kw) -> HandEyeCalibration:
     """One view per robot pose: Detections (charuco_ids / charuco_corners) or (ids, corners) pairs of a CharucoBoard; keywords as
     calibrate_hand_eye"""
-    obs = []
-    for v in views:
-        ids, corners = (v.charuco_ids, v.charuco_corners) if hasattr(v, "charuco_ids") else v
-        ids = np.zeros(0, np.int64) if ids is None else np.asarray(ids, np.int64).reshape(-1)
-        corners = np.zeros((0, 2), np.float32) if corners is None else np.asarray(corners, np.float32).reshape(-1, 2)
-        obs.append((board.chessboard_corners[ids].astype(np.float32), corners))
-    return calibrate_hand_eye(calibration, robot_poses, obs, **kw)
+    return calibrate_hand_eye(calibration, robot_poses, [_solver.charuco_view(board, v) for v in views], **kw)

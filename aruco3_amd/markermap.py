@@ -12,8 +12,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
-from . import calibration as _cal
+from . import _lib, _solver
 from .rig import camera_params
 
 
@@ -114,10 +113,7 @@ class MarkerMap:
 
 
 def _solve(*args):
-    with _cal._ctx_lock:
-        if _cal._ctx is None:
-            _cal._ctx = _lib.Context(_lib.default_config(), np.zeros(1, np.uint64), 64, 1)
-        return _cal._ctx.build_marker_maps(*args)
+    return _solver.call("build_marker_maps", *args)
 
 
 def frame_observations(detection) -> Dict[int, np.ndarray]:
@@ -172,11 +168,10 @@ def build_marker_maps(problems: Sequence[dict]) -> List[MarkerMap]:
         maps[r].a[:] = [float(v) for v in camera_params(pr["camera"])]
         maps[r].marker_length = float(pr["marker_length"])
         for k, i in enumerate(ids):
-            R, t = (np.eye(3), np.zeros(3))
+            pose = (np.eye(3), np.zeros(3))
             if guess is not None and k >= 1:
-                R, t = guess.pose(i) if isinstance(guess, MarkerMap) else guess[i]
-            markers[m0 + k].guess_rotation[:] = [float(v) for v in np.asarray(R, np.float64).reshape(9)]
-            markers[m0 + k].guess_translation[:] = [float(v) for v in np.asarray(t, np.float64).reshape(3)]
+                pose = guess.pose(i) if isinstance(guess, MarkerMap) else guess[i]
+            _solver.set_pose(markers[m0 + k], pose, "guess_")
         for j, (m, f, uv) in enumerate(obs):
             obs_arr[o0 + j] = _lib.MapObservation(m0 + m, f0 + f)
             img.append(np.asarray(uv, np.float32).reshape(8))
@@ -195,8 +190,7 @@ def build_marker_maps(problems: Sequence[dict]) -> List[MarkerMap]:
                        int(res[r].iterations), bool(res[r].converged), int(res[r].frames_used), int(res[r].obs_used))
         for f in range(len(frames)):
             x = fres[R.first_frame + f]
-            mm.frames.append(MapFramePose(int(x.status), int(x.obs_used), float(x.rms_px), np.array(x.rotation).reshape(3, 3),
-                                          np.array(x.translation)))
+            mm.frames.append(MapFramePose(int(x.status), int(x.obs_used), float(x.rms_px), *_solver.get_pose(x)))
         for j, (m, f, _) in enumerate(obs):
             x = ores[R.first_obs + j]
             mm.observations.append(MapObservationResult(ids[m], f, int(x.status), float(x.rms_px), tuple(x.start_rms_px)))
@@ -223,7 +217,7 @@ def build_marker_map(detections, camera, marker_length: float, *, reference_id: 
         if not mm.ok:
             break
         used = [o for o in mm.observations if o.used]
-        limit = max(1.0, 3.0 * float(np.median([o.rms_px for o in used])))
+        limit = _solver.outlier_limit([o.rms_px for o in used])
         bad = [(o.frame, o.marker_id) for o in used if not o.rms_px < limit]
         if not bad:
             break

@@ -128,18 +128,12 @@ class CameraIntrinsics:
         return _lib.Intrinsics(self.image_width, self.image_height, self.focal_x, self.focal_y, self.principal_x, self.principal_y)
 
 
-_undistort_ctx = None
-
-
 def undistort_points(points, intrinsics: CameraIntrinsics):
     """a3_undistort_points: pixel points (..., 2) seen through `intrinsics.distortion` -> (float32 (n, 2) undistorted pixels -- where an
     ideal camera with the same focal lengths and principal point would have seen them --, float32 (n,) residuals in pixels; +inf marks
     a point the model could not invert, returned as it came).  Runs on the device, on the kernel the pose batches use."""
-    global _undistort_ctx
-    from . import _lib
+    from . import _solver
 
     if intrinsics.distortion is None:
         raise ValueError("undistort_points needs CameraIntrinsics.distortion")
-    if _undistort_ctx is None:
-        _undistort_ctx = _lib.Context(_lib.default_config(), np.zeros(1, np.uint64), 64, 1)
-    return _undistort_ctx.undistort_points(points, intrinsics._c(), intrinsics.distortion._c())
+    return _solver.call("undistort_points", points, intrinsics._c(), intrinsics.distortion._c())

@@ -10,7 +10,7 @@ from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _solver
 from . import calibration as _cal
 
 
@@ -90,10 +90,7 @@ def camera_params(camera) -> np.ndarray:
 
 
 def _solve(*args):
-    with _cal._ctx_lock:
-        if _cal._ctx is None:
-            _cal._ctx = _lib.Context(_lib.default_config(), np.zeros(1, np.uint64), 64, 1)
-        return _cal._ctx.calibrate_rigs(*args)
+    return _solver.call("calibrate_rigs", *args)
 
 
 def calibrate_rigs(problems: Sequence[dict]) -> List[RigCalibration]:
@@ -125,9 +122,7 @@ def calibrate_rigs(problems: Sequence[dict]) -> List[RigCalibration]:
         rigs[r] = _lib.Rig(c0, len(a), f0, F, o0, len(o), flags, int(pr.get("max_iterations") or 0))
         for c in range(len(a)):
             cams[c0 + c].a[:] = [float(v) for v in a[c]]
-            R, t = guess[c] if guess is not None else (np.eye(3), np.zeros(3))
-            cams[c0 + c].guess_rotation[:] = [float(v) for v in np.asarray(R, np.float64).reshape(9)]
-            cams[c0 + c].guess_translation[:] = [float(v) for v in np.asarray(t, np.float64).reshape(3)]
+            _solver.set_pose(cams[c0 + c], guess[c] if guess is not None else (np.eye(3), np.zeros(3)), "guess_")
         for j, ob in enumerate(pr["observations"]):
             obs[o0 + j] = _lib.RigObservation(c0 + int(ob[0]), f0 + int(ob[1]), p0, len(o[j]))
             p0 += len(o[j])
@@ -135,13 +130,12 @@ def calibrate_rigs(problems: Sequence[dict]) -> List[RigCalibration]:
         img += i
         spans.append((c0, len(a), f0, F, o0, len(o)))
         c0, f0, o0 = c0 + len(a), f0 + F, o0 + len(o)
-    cat = lambda v: np.concatenate(v) if v else np.zeros((0, 2), np.float32)   # noqa: E731
-    res, cres, frames, ores = _solve(rigs, cams, obs, cat(obj), cat(img))
+    res, cres, frames, ores = _solve(rigs, cams, obs, _solver.cat_points(obj), _solver.cat_points(img))
     out = []
     for r, (cc, C_, ff, F, oo, NO) in enumerate(spans):
         cr = [cres[cc + c] for c in range(C_)]
-        fr = [RigFrameResult(int(f.status), int(f.obs_used), int(f.points_used), float(f.rms_px), np.array(f.rotation, np.float64).reshape(3, 3),
-                             np.array(f.translation, np.float64)) for f in (frames[ff + j] for j in range(F))]
+        fr = [RigFrameResult(int(f.status), int(f.obs_used), int(f.points_used), float(f.rms_px), *_solver.get_pose(f))
+              for f in (frames[ff + j] for j in range(F))]
         ob = [RigObservationResult(int(obs[oo + j].camera) - cc, int(obs[oo + j].frame) - ff, int(ores[oo + j].status), int(ores[oo + j].points),
                                    float(ores[oo + j].rms_px)) for j in range(NO)]
         out.append(RigCalibration(int(res[r].status), params[r], np.array([list(c.rotation) for c in cr], np.float64).reshape(C_, 3, 3),
@@ -166,23 +160,17 @@ def calibrate_rig(cameras, observations, *, guess=None, fix_extrinsics=False, ma
     obj, img = _cal._views([ob[2] for ob in observations], [ob[3] for ob in observations])
     if n_frames is None:
         kw["n_frames"] = max([f for _, f in head], default=0) + 1
-    keep = [np.ones(len(o), bool) for o in obj]
-    solve = lambda: calibrate_rigs([dict(observations=[(c, f, o[k], i[k]) for (c, f), o, i, k in zip(head, obj, img, keep)], **kw)])[0]   # noqa: E731
-    rig = solve()
-    for _ in range(int(outlier_passes)):
-        if not rig.ok:
-            break
-        for j, r in enumerate(rig.observations):
-            if not r.used:
-                continue
-            R, t = rig.camera_pose(r.camera, r.frame)
-            e = np.linalg.norm(_cal.reproject(rig.cameras[r.camera], R, t, obj[j][keep[j]]) - img[j][keep[j]], axis=1)
-            idx = np.nonzero(keep[j])[0]
-            keep[j][idx[~(e < max(1.0, 3.0 * float(np.median(e))))]] = False
-        rig = solve()
-    if outlier_passes:
-        rig.inliers = keep
-    return rig
+
+    def residuals(rig, j, k):
+        r = rig.observations[j]
+        if not r.used:
+            return None
+        R, t = rig.camera_pose(r.camera, r.frame)
+        return np.linalg.norm(_cal.reproject(rig.cameras[r.camera], R, t, obj[j][k]) - img[j][k], axis=1)
+
+    return _solver.solve_with_outlier_passes(
+        [len(o) for o in obj], lambda keep: calibrate_rigs([dict(observations=[(c, f, o[k], i[k]) for (c, f), o, i, k in zip(head, obj, img, keep)],
+                                                                 **kw)])[0], residuals, outlier_passes)
 
 
 def _board_observations(board, detections_per_camera):
@@ -203,13 +191,7 @@ def calibrate_rig_board(board, detections_per_camera, calibrations, **kw) -> Rig
 def calibrate_rig_charuco(board, views_per_camera, calibrations, **kw) -> RigCalibration:
     """One list of views per camera (entry k the same instant): Detections (charuco_ids / charuco_corners) or (ids, corners) pairs of a
     CharucoBoard; keywords as calibrate_rig"""
-    obs = []
-    for c, views in enumerate(views_per_camera):
-        for f, v in enumerate(views):
-            ids, corners = (v.charuco_ids, v.charuco_corners) if hasattr(v, "charuco_ids") else v
-            ids = np.zeros(0, np.int64) if ids is None else np.asarray(ids, np.int64).reshape(-1)
-            corners = np.zeros((0, 2), np.float32) if corners is None else np.asarray(corners, np.float32).reshape(-1, 2)
-            obs.append((c, f, board.chessboard_corners[ids].astype(np.float32), corners))
+    obs = [(c, f, *_solver.charuco_view(board, v)) for c, views in enumerate(views_per_camera) for f, v in enumerate(views)]
     return calibrate_rig(calibrations, obs, n_frames=len(views_per_camera[0]), **kw)
 
 
