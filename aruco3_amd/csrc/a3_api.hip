@@ -14,6 +14,7 @@
 
 #include "a3_common.h"
 #include "a3_internal.h"
+#include "a3_readback.h"
 #include "a3_solve_check.h"
 
 namespace a3 {
@@ -188,12 +189,11 @@ struct Batch {
     bool want_pose = false, pose_has_intr = false;   // a3_detect_batch_pose*: poses of every marker, solved on the device
     float pose_size_mm = 0.0f;
     a3_intrinsics pose_intr{};
-    size_t pose_bytes = 0;       // 2 poses per marker with poses, else 0
     a3_refine_config refine{};   // corner refinement (method NONE: none)
-    size_t refine_bytes = 0;     // 32 (8 floats per marker) with refinement, else 0
+    bool refined = false;        // ... is on: 8 floats per marker
     bool board = false;          // a pose batch with a board set: k_board_pose runs behind k_pose
     a3_distortion dist{};        // lens distortion (model NONE: none)
-    size_t undist_bytes = 0;     // 48 (8 corner floats + 4 residuals per marker) on a pose batch with distortion, else 0
+    bool undist = false;         // ... is on, on a pose batch: 8 corner floats + 4 residuals per marker
     bool charuco = false;        // ChArUco set: the corner stage runs behind the refinement (and k_charuco_pose behind k_board_pose)
     a3_charuco_config charuco_cfg{};
     uint32_t charuco_nc = 0, charuco_guess = 0;   // chessboard corners; records in the speculative read-back
@@ -207,7 +207,8 @@ struct Batch {
     uint32_t max_cand = 0, patch_cap = 0, marker_cap = 0, guess = 0;
     // enqueue_chain
     bool active = false, device_plan = false;
-    size_t n_chunks = 0, ctr_bytes = 0, head_bytes = 0;
+    size_t n_chunks = 0, ctr_bytes = 0;
+    Readback rb;                 // where the results lie in the pinned staging buffer (ensure_back_buffers)
     uint64_t chunk0_darts = 0;
     int rounds_max = 0;
     PixelSrc src{};              // what the decode stage samples: the caller's frames or the grey plane
@@ -519,15 +520,10 @@ const void* refine_params_for(a3_ctx* ctx, const a3_refine_config& cfg) {
     return ctx->refine_prm.data();
 }
 
-// ChArUco: the per-frame slot records of charuco_tmp (the counts follow them), and where the read-back stages the results
+// ChArUco: the per-frame slot records of charuco_tmp (the counts follow them)
 size_t charuco_slot_bytes(const Batch& b) { return ((size_t)b.n * b.charuco_nc * sizeof(a3_charuco_corner) + 255) & ~(size_t)255; }
-size_t charuco_stage_off(const Batch& b) {
-    return b.head_bytes + (size_t)b.guess * (sizeof(a3_marker) + b.pose_bytes + b.refine_bytes + b.undist_bytes) +
-           (b.board ? (size_t)b.n * sizeof(a3_board_pose) : 0);
-}
-size_t charuco_stage_bytes(const Batch& b) {
-    return b.charuco ? 16 + (size_t)b.charuco_guess * sizeof(a3_charuco_corner) + (b.want_pose ? (size_t)b.n * sizeof(a3_charuco_pose) : 0) : 0;
-}
+// what a3_readback.h lays a batch's staging out from
+ReadbackShape readback_shape(const Batch& b, size_t head_bytes) { return {b.n, b.guess, b.charuco_guess, head_bytes, b.want_pose, b.refined, b.undist, b.board, b.charuco}; }
 // the refinement kernel's parameters for the ChArUco setting `cfg` (its window and iteration settings; built once per setting)
 const void* charuco_params_for(a3_ctx* ctx, const a3_charuco_config& cfg) {
     if (ctx->charuco_prm.empty() || memcmp(&ctx->charuco_prm_cfg, &cfg, sizeof cfg) != 0) {
@@ -567,18 +563,18 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
                          few));
     A3_HIP(launch_compact_markers(st, ctx->outs.p, ctx->fin_xy.as<uint16_t>(), ctx->fin_count.as<uint32_t>(), b.n, 0, b.max_cand,
                                   ctx->markers_ptr, b.marker_cap, ctx->per_frame, d_marker_total, d_err, ctx->cand_count, ctx->scratch_u32 + 2));
-    if (b.refine_bytes)   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
+    if (b.refined)   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
         A3_HIP(launch_refine_corners(st, b.src, b.W, b.H, ctx->markers_ptr, d_marker_total, nullptr, nullptr, b.marker_cap,
                                      refine_params_for(ctx, b.refine), ctx->refined_buf.as<float>()));
-    if (b.undist_bytes)   // undistorted pixel corners of the same markers (of their refined corners with refinement on)
-        A3_HIP(launch_undistort_corners(st, ctx->markers_ptr, b.refine_bytes ? ctx->refined_buf.as<float>() : nullptr, d_marker_total, b.marker_cap,
+    if (b.undist)   // undistorted pixel corners of the same markers (of their refined corners with refinement on)
+        A3_HIP(launch_undistort_corners(st, ctx->markers_ptr, b.refined ? ctx->refined_buf.as<float>() : nullptr, d_marker_total, b.marker_cap,
                                         b.pose_intr, b.dist, ctx->undist_buf.as<float>(), ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
     // the float corners the poses are solved from: undistorted, else refined, else none (the integer corners)
-    const float* fcorners = b.undist_bytes ? ctx->undist_buf.as<float>() : b.refine_bytes ? ctx->refined_buf.as<float>() : nullptr;
+    const float* fcorners = b.undist ? ctx->undist_buf.as<float>() : b.refined ? ctx->refined_buf.as<float>() : nullptr;
     const uint32_t* charuco_counts = b.charuco ? reinterpret_cast<const uint32_t*>(ctx->charuco_tmp.as<uint8_t>() + charuco_slot_bytes(b)) : nullptr;
-    float* charuco_und = b.charuco && b.want_pose && b.undist_bytes ? ctx->charuco_und.as<float>() : nullptr;
+    float* charuco_und = b.charuco && b.want_pose && b.undist ? ctx->charuco_und.as<float>() : nullptr;
     if (b.charuco)   // the chessboard corners of the same markers (their raw refined or integer corners), sampled as the refinement samples
-        A3_HIP(launch_charuco_corners(st, b.src, b.W, b.H, ctx->markers_ptr, nullptr, nullptr, b.refine_bytes ? ctx->refined_buf.as<float>() : nullptr,
+        A3_HIP(launch_charuco_corners(st, b.src, b.W, b.H, ctx->markers_ptr, nullptr, nullptr, b.refined ? ctx->refined_buf.as<float>() : nullptr,
                                       d_marker_total, ctx->per_frame, b.marker_cap, b.n, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes,
                                       ctx->board_slot_rec.p, ctx->charuco_tab.as<float>(), ctx->charuco_tab.as<uint32_t>() + 2 * (size_t)b.charuco_nc,
                                       b.charuco_nc, b.charuco_cfg.min_markers, b.charuco_cfg.refine, charuco_params_for(ctx, b.charuco_cfg),
@@ -605,29 +601,21 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     }
     if (b.prof >= 2) A3_HIP(hipEventRecord(ctx->ev[3], st));
     // ---- results: one copy of [scratch | counters | per-frame counts | `guess` markers], then the poses and (taps) the counts ----
-    uint8_t* hp = (uint8_t*)ctx->pinned;
-    a3_pose* h_poses = reinterpret_cast<a3_pose*>(hp + b.head_bytes + (size_t)b.guess * sizeof(a3_marker));
-    A3_HIP(hipMemcpyAsync(hp, ctx->scratch_u32, b.head_bytes + (size_t)b.guess * sizeof(a3_marker), hipMemcpyDeviceToHost, st));
-    if (b.pose_bytes) A3_HIP(hipMemcpyAsync(h_poses, ctx->pose_buf.p, (size_t)b.guess * b.pose_bytes, hipMemcpyDeviceToHost, st));
-    if (b.refine_bytes)   // (staged behind the poses)
-        A3_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(h_poses) + (size_t)b.guess * b.pose_bytes, ctx->refined_buf.p, (size_t)b.guess * b.refine_bytes,
-                              hipMemcpyDeviceToHost, st));
-    if (b.board)   // (staged behind the refined corners; one record per frame, whatever the marker count)
-        A3_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(h_poses) + (size_t)b.guess * (b.pose_bytes + b.refine_bytes), ctx->board_buf.p,
-                              (size_t)b.n * sizeof(a3_board_pose), hipMemcpyDeviceToHost, st));
-    if (b.undist_bytes) {   // (staged behind the board poses: `guess` markers' corners, then their residuals)
-        uint8_t* hu = reinterpret_cast<uint8_t*>(h_poses) + (size_t)b.guess * (b.pose_bytes + b.refine_bytes) + (b.board ? (size_t)b.n * sizeof(a3_board_pose) : 0);
-        A3_HIP(hipMemcpyAsync(hu, ctx->undist_buf.p, (size_t)b.guess * 32, hipMemcpyDeviceToHost, st));
-        A3_HIP(hipMemcpyAsync(hu + (size_t)b.guess * 32, ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8, (size_t)b.guess * 16,
-                              hipMemcpyDeviceToHost, st));
+    // (every destination from the batch's layout, a3_readback.h; the board and ChArUco poses: one record per frame, whatever the marker count)
+    const Readback& rb = b.rb;
+    auto stage = [&](const Span& to, const void* from) { return hipMemcpyAsync(at<uint8_t>(ctx->pinned, to), from, to.bytes, hipMemcpyDeviceToHost, st); };
+    A3_HIP(hipMemcpyAsync(ctx->pinned, ctx->scratch_u32, rb.head.bytes + rb.markers.bytes, hipMemcpyDeviceToHost, st));
+    if (b.want_pose) A3_HIP(stage(rb.poses, ctx->pose_buf.p));
+    if (b.refined) A3_HIP(stage(rb.refined, ctx->refined_buf.p));
+    if (b.board) A3_HIP(stage(rb.board, ctx->board_buf.p));
+    if (b.undist) {
+        A3_HIP(stage(rb.undist, ctx->undist_buf.p));
+        A3_HIP(stage(rb.undist_res, ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
     }
-    if (b.charuco) {   // (staged behind the undistorted corners: the total, `charuco_guess` records, then the poses of a pose batch)
-        uint8_t* hc = hp + charuco_stage_off(b);
-        A3_HIP(hipMemcpyAsync(hc, charuco_counts + b.n, 4, hipMemcpyDeviceToHost, st));
-        A3_HIP(hipMemcpyAsync(hc + 16, ctx->charuco_buf.p, (size_t)b.charuco_guess * sizeof(a3_charuco_corner), hipMemcpyDeviceToHost, st));
-        if (b.want_pose)
-            A3_HIP(hipMemcpyAsync(hc + 16 + (size_t)b.charuco_guess * sizeof(a3_charuco_corner), ctx->charuco_pose_buf.p,
-                                  (size_t)b.n * sizeof(a3_charuco_pose), hipMemcpyDeviceToHost, st));
+    if (b.charuco) {
+        A3_HIP(hipMemcpyAsync(at<uint8_t>(ctx->pinned, rb.charuco_total), charuco_counts + b.n, 4, hipMemcpyDeviceToHost, st));
+        A3_HIP(stage(rb.charuco, ctx->charuco_buf.p));
+        if (b.want_pose) A3_HIP(stage(rb.charuco_poses, ctx->charuco_pose_buf.p));
     }
     if (b.taps) {   // Detection.candidates / .homographies will be asked for frame by frame: their counts travel now
         A3_HIP(hipMemcpyAsync(ctx->pinned_counts, ctx->cand_count, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
@@ -732,21 +720,20 @@ uint64_t pool_darts_of(const a3_ctx* ctx, uint64_t max_chunk_darts, size_t n_chu
 }
 // The second half's buffers: poses, refined corners, board poses, undistorted corners, pinned staging for the read-back head and `guess` markers (+ poses
 // ...; a longer list is fetched by finish_batch after growing it), pinned staging for the tap counts.
-int ensure_back_buffers(a3_ctx* ctx, const Batch& b, size_t head_bytes) {
-    const size_t board_bytes = b.board ? (size_t)b.n * sizeof(a3_board_pose) : 0;
+int ensure_back_buffers(a3_ctx* ctx, Batch& b, size_t head_bytes) {
+    b.rb = readback_layout(readback_shape(b, head_bytes));   // (guess and charuco_guess are fixed; the head's size is known now)
     if (b.want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)b.marker_cap * 2 * sizeof(a3_pose)));
-    if (b.refine_bytes) A3_HIP(ctx->refined_buf.ensure((size_t)b.marker_cap * b.refine_bytes));
-    if (board_bytes) A3_HIP(ctx->board_buf.ensure(board_bytes));
-    if (b.undist_bytes) A3_HIP(ctx->undist_buf.ensure((size_t)b.marker_cap * b.undist_bytes));
+    if (b.refined) A3_HIP(ctx->refined_buf.ensure((size_t)b.marker_cap * 8 * sizeof(float)));
+    if (b.board) A3_HIP(ctx->board_buf.ensure((size_t)b.n * sizeof(a3_board_pose)));
+    if (b.undist) A3_HIP(ctx->undist_buf.ensure((size_t)b.marker_cap * 12 * sizeof(float)));
     if (b.charuco) {
         const size_t recs = (size_t)b.n * b.charuco_nc;
         A3_HIP(ctx->charuco_tmp.ensure(charuco_slot_bytes(b) + ((size_t)b.n + 1) * 4));
         A3_HIP(ctx->charuco_buf.ensure(std::max<size_t>(recs, 1) * sizeof(a3_charuco_corner)));
         if (b.want_pose) A3_HIP(ctx->charuco_pose_buf.ensure((size_t)b.n * sizeof(a3_charuco_pose)));
-        if (b.want_pose && b.undist_bytes) A3_HIP(ctx->charuco_und.ensure(std::max<size_t>(recs, 1) * 8));
+        if (b.want_pose && b.undist) A3_HIP(ctx->charuco_und.ensure(std::max<size_t>(recs, 1) * 8));
     }
-    if (int rc = ensure_pinned(ctx, head_bytes + (size_t)b.guess * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + b.refine_bytes + b.undist_bytes) + board_bytes +
-                                    charuco_stage_bytes(b) + (1 << 16))) return rc;
+    if (int rc = ensure_pinned(ctx, pinned_bytes(b.rb))) return rc;
     if (b.taps && ctx->pinned_counts_cap < (size_t)b.n * 8) {
         if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
         ctx->pinned_counts = nullptr; ctx->pinned_counts_cap = 0;
@@ -760,7 +747,7 @@ int ensure_back_buffers(a3_ctx* ctx, const Batch& b, size_t head_bytes) {
 // whichever thread submits the burst's last member, under the process-wide lock, and must then find nothing left to allocate
 // (hipMalloc / hipHostMalloc synchronise the device).  The per-frame dart totals of the device plan live in frame_darts_dev, zeroed
 // once here and handed back zeroed by the plan workgroup.
-int ensure_chain_buffers(a3_ctx* ctx, hipStream_t st, const Batch& b, uint64_t cap_d) {
+int ensure_chain_buffers(a3_ctx* ctx, hipStream_t st, Batch& b, uint64_t cap_d) {
     const uint32_t n = b.n;
     const ZeroLayout z = zero_layout(1, n, n, b.marker_cap);
     A3_HIP(ctx->tile_darts.ensure(tile_darts_bytes(b.W, b.H, n)));
@@ -1019,7 +1006,6 @@ int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
     b.src = b.grey_src ? PixelSrc{ctx->grey.as<uint8_t>(), W, (unsigned long long)npx, kFmtGreyPlane}
                         : PixelSrc{b.pixels, b.row_stride, b.frame_stride, b.fmt};
     ctx->dbg_src = b.src;
-    b.head_bytes = head_bytes;   // the markers follow the head directly, on the device and in the staging buffer
     if (int rc = ensure_back_buffers(ctx, b, head_bytes)) return rc;   // (device plan: ensure_chain_buffers did, this is a no-op)
     b.device_plan = device_plan; b.n_chunks = chunks.size(); b.chunk0_darts = chunks.empty() ? 0 : chunks[0].darts;
     b.ctr_bytes = ctr_bytes; b.rounds_max = rounds_max;
@@ -1058,15 +1044,10 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     }
     b.active = false;
     hipStream_t st = ctx->stream;
-    const size_t ctr_bytes = b.ctr_bytes, head_bytes = b.head_bytes, pose_bytes = b.pose_bytes, n_chunks = b.n_chunks, refine_bytes = b.refine_bytes;
-    const size_t undist_bytes = b.undist_bytes, board_bytes = b.board ? (size_t)b.n * sizeof(a3_board_pose) : 0;
+    const size_t ctr_bytes = b.ctr_bytes, n_chunks = b.n_chunks;
     const uint32_t guess = b.guess, n = b.n;
     uint8_t* hp = (uint8_t*)ctx->pinned;
-    a3_marker* h_markers = reinterpret_cast<a3_marker*>(hp + head_bytes);
-    a3_pose* h_poses = reinterpret_cast<a3_pose*>(hp + head_bytes + (size_t)guess * sizeof(a3_marker));
-    const float* h_refined = reinterpret_cast<const float*>(hp + head_bytes + (size_t)guess * (sizeof(a3_marker) + pose_bytes));
-    const float* h_undist = reinterpret_cast<const float*>(hp + head_bytes + (size_t)guess * (sizeof(a3_marker) + pose_bytes + refine_bytes) + board_bytes);
-    const float* h_undist_res = h_undist + (size_t)guess * 8;
+    Readback rb = b.rb;   // where the results lie behind hp (a3_readback.h)
     {   // nobody submitted behind this batch: its decode stage goes out now
         std::lock_guard<std::mutex> lk(g_defer_mu);
         if (int rc = flush_deferred_locked(ctx, nullptr)) return rc;
@@ -1151,18 +1132,17 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     for (uint32_t f = 0; f < n; f++) max_per_frame = std::max(max_per_frame, hpf[f]);
     const uint32_t n_work = hs[0], n_pre = hs[2];
     if (b.board) {   // (read now: the staging buffer may be re-allocated below)
-        const a3_board_pose* hb = reinterpret_cast<const a3_board_pose*>(hp + head_bytes + (size_t)guess * (sizeof(a3_marker) + pose_bytes + refine_bytes));
+        const a3_board_pose* hb = at<a3_board_pose>(hp, rb.board);
         ctx->h_board.assign(hb, hb + n);
     }
     if (b.charuco) {   // (read now, as the board poses)
-        const uint8_t* hc = hp + charuco_stage_off(b);
         uint32_t charuco_total = 0;
-        memcpy(&charuco_total, hc, 4);
+        memcpy(&charuco_total, at<uint8_t>(hp, rb.charuco_total), 4);
         ctx->h_charuco.resize(charuco_total);
         const size_t staged = std::min<uint32_t>(charuco_total, b.charuco_guess);
-        if (staged) memcpy(ctx->h_charuco.data(), hc + 16, staged * sizeof(a3_charuco_corner));
+        if (staged) memcpy(ctx->h_charuco.data(), at<uint8_t>(hp, rb.charuco), staged * sizeof(a3_charuco_corner));
         if (b.want_pose) {
-            const a3_charuco_pose* hq = reinterpret_cast<const a3_charuco_pose*>(hc + 16 + (size_t)b.charuco_guess * sizeof(a3_charuco_corner));
+            const a3_charuco_pose* hq = at<a3_charuco_pose>(hp, rb.charuco_poses);
             ctx->h_charuco_pose.assign(hq, hq + n);
         }
         if (charuco_total > staged) {   // the guess was short: the rest of the records, straight from the device
@@ -1174,33 +1154,31 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     }
     const uint32_t tap_contours = n_chunks ? hc[0].contours : 0u; const uint64_t tap_points = n_chunks ? hc[0].points : 0ull;
     if (total > guess) {   // the guess was short: the staging area grows (the head has been consumed) and the whole list is fetched
-        if (int rc = ensure_pinned(ctx, (size_t)total * (sizeof(a3_marker) + 2 * sizeof(a3_pose) + refine_bytes + undist_bytes) + (1 << 16))) return rc;
-        h_markers = reinterpret_cast<a3_marker*>(ctx->pinned);
-        h_poses = reinterpret_cast<a3_pose*>((uint8_t*)ctx->pinned + (size_t)total * sizeof(a3_marker));
-        h_refined = reinterpret_cast<const float*>((uint8_t*)ctx->pinned + (size_t)total * (sizeof(a3_marker) + pose_bytes));
-        A3_HIP(hipMemcpyAsync(h_markers, ctx->markers_ptr, (size_t)total * sizeof(a3_marker), hipMemcpyDeviceToHost, st));
-        if (pose_bytes) A3_HIP(hipMemcpyAsync(h_poses, ctx->pose_buf.p, (size_t)total * pose_bytes, hipMemcpyDeviceToHost, st));
-        if (refine_bytes) A3_HIP(hipMemcpyAsync(const_cast<float*>(h_refined), ctx->refined_buf.p, (size_t)total * refine_bytes, hipMemcpyDeviceToHost, st));
-        if (undist_bytes) {
-            h_undist = reinterpret_cast<const float*>((uint8_t*)ctx->pinned + (size_t)total * (sizeof(a3_marker) + pose_bytes + refine_bytes));
-            h_undist_res = h_undist + (size_t)total * 8;
-            A3_HIP(hipMemcpyAsync(const_cast<float*>(h_undist), ctx->undist_buf.p, (size_t)total * 32, hipMemcpyDeviceToHost, st));
-            A3_HIP(hipMemcpyAsync(const_cast<float*>(h_undist_res), ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8, (size_t)total * 16,
-                                  hipMemcpyDeviceToHost, st));
+        rb = refetch_layout(readback_shape(b, 0), total);
+        if (int rc = ensure_pinned(ctx, pinned_bytes(rb))) return rc;
+        hp = (uint8_t*)ctx->pinned;
+        auto fetch = [&](const Span& to, const void* from) { return hipMemcpyAsync(at<uint8_t>(hp, to), from, to.bytes, hipMemcpyDeviceToHost, st); };
+        A3_HIP(fetch(rb.markers, ctx->markers_ptr));
+        if (b.want_pose) A3_HIP(fetch(rb.poses, ctx->pose_buf.p));
+        if (b.refined) A3_HIP(fetch(rb.refined, ctx->refined_buf.p));
+        if (b.undist) {
+            A3_HIP(fetch(rb.undist, ctx->undist_buf.p));
+            A3_HIP(fetch(rb.undist_res, ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
         }
         A3_HIP(hipStreamSynchronize(ctx->stream));
     }
     if (total) {
-        memcpy(out, h_markers, (size_t)total * sizeof(a3_marker));
-        if (pose_bytes && poses) memcpy(poses, h_poses, (size_t)total * pose_bytes);
+        memcpy(out, at<a3_marker>(hp, rb.markers), (size_t)total * sizeof(a3_marker));
+        if (b.want_pose && poses) memcpy(poses, at<a3_pose>(hp, rb.poses), (size_t)total * 2 * sizeof(a3_pose));
     }
-    if (refine_bytes) ctx->h_refined.assign(h_refined, h_refined + (size_t)total * 8);
-    ctx->refined_valid = refine_bytes != 0;
-    if (undist_bytes) {
+    const float* h_refined = at<float>(hp, rb.refined), * h_undist = at<float>(hp, rb.undist), * h_undist_res = at<float>(hp, rb.undist_res);
+    if (b.refined) ctx->h_refined.assign(h_refined, h_refined + (size_t)total * 8);
+    ctx->refined_valid = b.refined;
+    if (b.undist) {
         ctx->h_undist.assign(h_undist, h_undist + (size_t)total * 8);
         ctx->h_undist_res.assign(h_undist_res, h_undist_res + (size_t)total * 4);
     }
-    ctx->undist_valid = undist_bytes != 0;
+    ctx->undist_valid = b.undist;
     ctx->board_valid = b.board;
     ctx->charuco_valid = b.charuco;
     ctx->charuco_pose_valid = b.charuco && b.want_pose;
@@ -1217,7 +1195,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     ctx->stats.candidates = n_work;      // work items = quads that survived discard_too_near
     ctx->stats.candidates_pre = n_pre;   // quads after contours_to_candidates (k_compact_markers sums the per-frame counts)
     ctx->markers_valid = true; ctx->last_n = n; ctx->last_max_per_frame = max_per_frame;
-    ctx->poses_valid = pose_bytes != 0;
+    ctx->poses_valid = b.want_pose;
     ctx->contours_valid = b.taps && n_chunks == 1;
     if (ctx->contours_valid) { ctx->tap_contours = tap_contours; ctx->tap_points = tap_points; }
     if (b.prof >= 1) {   // the level in force when the batch was enqueued
@@ -1234,6 +1212,17 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
 int run_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
     if (int rc = enqueue_batch(ctx)) return rc;
     return finish_batch(ctx, out, poses, out_cap, per_frame_count, out_n);
+}
+
+// The getters of the last collected batch's results, their pointers checked: the records (`per` elements each) of the host copy `v` that
+// finish_batch kept, refused with `without` when that batch ran without the feature and with `small` when dst holds fewer.
+template <typename T>
+int get_last(a3_ctx* ctx, bool valid, const std::vector<T>& v, size_t per, T* dst, size_t cap, size_t* n, const char* without, const char* small) {
+    if (!valid) return fail(ctx, A3_ERR_INVALID, without);
+    *n = v.size() / per;
+    if (*n > cap) return fail(ctx, A3_ERR_CAPACITY, small);
+    if (*n) memcpy(dst, v.data(), v.size() * sizeof(T));
+    return A3_OK;
 }
 
 // a3_calibrate_cameras and a3_calibrate_fisheye_cameras: the same checks and staging.  The fisheye model keeps the start's compacted
@@ -1568,14 +1557,13 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
     b.fmt = fmt; b.W = width; b.H = height; b.n = n_frames; b.out_cap = out_cap;
     b.want_pose = want_pose; b.pose_size_mm = size_mm; b.pose_has_intr = intr != nullptr;
     if (intr) b.pose_intr = *intr;
-    b.pose_bytes = want_pose ? 2 * sizeof(a3_pose) : 0;
     b.refine = ctx->refine;
-    b.refine_bytes = b.refine.method != A3_REFINE_NONE ? 8 * sizeof(float) : 0;
+    b.refined = b.refine.method != A3_REFINE_NONE;
     b.board = want_pose && !ctx->board_ids.empty();
     if (want_pose && ctx->dist.model != A3_DIST_NONE) {
         if (!intr) return fail(ctx, A3_ERR_INVALID, "a pose batch with lens distortion set needs intrinsics (the coefficients are in focal units)");
         b.dist = ctx->dist;
-        b.undist_bytes = 12 * sizeof(float);
+        b.undist = true;
     }
     b.charuco = ctx->charuco_nc != 0;
     if (b.charuco) {
@@ -1604,9 +1592,9 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
 static void finish_trivial(a3_ctx* ctx, uint32_t* per_frame_count) {
     const Batch& b = ctx->batch;
     if (per_frame_count && b.n) memset(per_frame_count, 0, (size_t)b.n * 4);
-    ctx->h_refined.clear(); ctx->refined_valid = b.refine_bytes != 0;
+    ctx->h_refined.clear(); ctx->refined_valid = b.refined;
     ctx->h_board.assign(b.n, a3_board_pose{}); ctx->board_valid = b.board;
-    ctx->h_undist.clear(); ctx->h_undist_res.clear(); ctx->undist_valid = b.undist_bytes != 0;
+    ctx->h_undist.clear(); ctx->h_undist_res.clear(); ctx->undist_valid = b.undist;
     ctx->h_charuco.clear(); ctx->charuco_valid = b.charuco;
     ctx->h_charuco_pose.assign(b.want_pose ? b.n : 0, a3_charuco_pose{}); ctx->charuco_pose_valid = b.charuco && b.want_pose;
 }
@@ -2263,12 +2251,8 @@ int a3_set_corner_refinement(a3_ctx* ctx, const a3_refine_config* cfg) {
 int a3_get_refined_corners(a3_ctx* ctx, float* dst_xy, size_t cap_markers, size_t* n) {
     if (!ctx || !n || (!dst_xy && cap_markers)) return A3_ERR_INVALID;
     *n = 0;
-    if (!ctx->refined_valid) return fail(ctx, A3_ERR_INVALID, "a3_get_refined_corners: the last collected batch ran without corner refinement");
-    const size_t total = ctx->h_refined.size() / 8;
-    *n = total;
-    if (total > cap_markers) return fail(ctx, A3_ERR_CAPACITY, "a3_get_refined_corners: cap_markers is smaller than the number of markers");
-    if (total) memcpy(dst_xy, ctx->h_refined.data(), total * 8 * sizeof(float));
-    return A3_OK;
+    return get_last(ctx, ctx->refined_valid, ctx->h_refined, 8, dst_xy, cap_markers, n, "a3_get_refined_corners: the last collected batch ran without corner refinement",
+                    "a3_get_refined_corners: cap_markers is smaller than the number of markers");
 }
 
 int a3_refine_corners(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride, float* corners_xy,
@@ -2290,16 +2274,14 @@ int a3_refine_corners(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint
     const uint8_t* d_pixels = nullptr;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, 1, &d_pixels);
     if (rc != A3_OK) return rc == kNothingToDo ? A3_OK : rc;
-    const size_t pts_bytes = n * 2 * sizeof(float), cell_off = (pts_bytes + 255) & ~(size_t)255;
-    A3_HIP(ctx->tmp_a.ensure(cell_off + (cell_px ? n * sizeof(float) : 0)));
-    A3_HIP(ctx->tmp_b.ensure(pts_bytes));
-    float* d_pts = ctx->tmp_a.as<float>();
-    float* d_cell = cell_px ? reinterpret_cast<float*>(ctx->tmp_a.as<uint8_t>() + cell_off) : nullptr;
-    A3_HIP(hipMemcpyAsync(d_pts, corners_xy, pts_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (cell_px) A3_HIP(hipMemcpyAsync(d_cell, cell_px, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    A3_HIP(launch_refine_corners(ctx->stream, PixelSrc{d_pixels, row_stride, frame_stride, fmt}, width, height, nullptr, nullptr, d_pts, d_cell, (uint32_t)n,
-                                 refine_params_for(ctx, cfg), ctx->tmp_b.as<float>()));
-    A3_HIP(hipMemcpyAsync(corners_xy, ctx->tmp_b.p, pts_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    Layout in{ctx->tmp_a, ctx->stream}, out{ctx->tmp_b, ctx->stream};
+    const auto s_pts = in.add<float>(2 * n), s_cell = in.add<float>(cell_px ? n : 0), s_out = out.add<float>(2 * n);
+    A3_HIP(in.ensure()); A3_HIP(out.ensure());
+    A3_HIP(in.upload(s_pts, corners_xy, 2 * n));
+    if (cell_px) A3_HIP(in.upload(s_cell, cell_px, n));
+    A3_HIP(launch_refine_corners(ctx->stream, PixelSrc{d_pixels, row_stride, frame_stride, fmt}, width, height, nullptr, nullptr, in.at(s_pts),
+                                 cell_px ? in.at(s_cell) : nullptr, (uint32_t)n, refine_params_for(ctx, cfg), out.at(s_out)));
+    A3_HIP(out.download(s_out, corners_xy));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }
@@ -2345,12 +2327,8 @@ int a3_set_board(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size
 int a3_get_board_poses(a3_ctx* ctx, a3_board_pose* dst, size_t cap_frames, size_t* n) {
     if (!ctx || !n || (!dst && cap_frames)) return A3_ERR_INVALID;
     *n = 0;
-    if (!ctx->board_valid)
-        return fail(ctx, A3_ERR_INVALID, "a3_get_board_poses: the last collected batch was not a pose batch with a board set");
-    *n = ctx->h_board.size();
-    if (*n > cap_frames) return fail(ctx, A3_ERR_CAPACITY, "a3_get_board_poses: cap_frames is smaller than the number of frames");
-    if (*n) memcpy(dst, ctx->h_board.data(), *n * sizeof(a3_board_pose));
-    return A3_OK;
+    return get_last(ctx, ctx->board_valid, ctx->h_board, 1, dst, cap_frames, n, "a3_get_board_poses: the last collected batch was not a pose batch with a board set",
+                    "a3_get_board_poses: cap_frames is smaller than the number of frames");
 }
 
 int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size_t n_markers, const a3_intrinsics* intr,
@@ -2364,24 +2342,22 @@ int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corner
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
     if (int urc = upload_board(ctx)) return urc;
-    const size_t id_bytes = (n_markers * 4 + 255) & ~(size_t)255, pts_bytes = n_markers * 8 * sizeof(float);
-    A3_HIP(ctx->tmp_a.ensure(std::max<size_t>(id_bytes + pts_bytes, 256)));
-    A3_HIP(ctx->tmp_b.ensure(sizeof(a3_board_pose)));
-    uint32_t* d_ids = ctx->tmp_a.as<uint32_t>();
-    float* d_pts = reinterpret_cast<float*>(ctx->tmp_a.as<uint8_t>() + id_bytes);
-    if (n_markers) {
-        A3_HIP(hipMemcpyAsync(d_ids, ids, n_markers * 4, hipMemcpyHostToDevice, ctx->stream));
-        A3_HIP(hipMemcpyAsync(d_pts, corners_xy, pts_bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
+    Layout in{ctx->tmp_a, ctx->stream}, res{ctx->tmp_b, ctx->stream}, und{ctx->tmp_c, ctx->stream};
+    const auto s_ids = in.add<uint32_t>(std::max<size_t>(n_markers, 1));   // (never an empty buffer)
+    const auto s_pts = in.add<float>(8 * n_markers);
+    const auto s_out = res.add<a3_board_pose>(1);
+    A3_HIP(in.ensure()); A3_HIP(res.ensure());
+    A3_HIP(in.upload(s_ids, ids, n_markers)); A3_HIP(in.upload(s_pts, corners_xy, 8 * n_markers));
+    float* d_pts = in.at(s_pts);
     if (intr && ctx->dist.model != A3_DIST_NONE && n_markers) {   // undistorted pixel corners, as a pose batch solves from
-        A3_HIP(ctx->tmp_c.ensure(n_markers * 12 * sizeof(float)));
-        A3_HIP(launch_undistort_corners(ctx->stream, nullptr, d_pts, nullptr, (uint32_t)(n_markers * 4), *intr, ctx->dist, ctx->tmp_c.as<float>(),
-                                        ctx->tmp_c.as<float>() + n_markers * 8));
-        d_pts = ctx->tmp_c.as<float>();
+        const auto s_und = und.add<float>(8 * n_markers), s_und_res = und.add<float>(4 * n_markers);
+        A3_HIP(und.ensure());
+        A3_HIP(launch_undistort_corners(ctx->stream, nullptr, d_pts, nullptr, (uint32_t)(n_markers * 4), *intr, ctx->dist, und.at(s_und), und.at(s_und_res)));
+        d_pts = und.at(s_und);
     }
-    A3_HIP(launch_board_pose(ctx->stream, nullptr, d_ids, d_pts, nullptr, nullptr, nullptr, (uint32_t)n_markers, 1u, ctx->board_slot_of.as<uint16_t>(),
-                             ctx->n_codes, ctx->board_slot_rec.p, intr, image_width, image_height, ctx->tmp_b.as<a3_board_pose>()));
-    A3_HIP(hipMemcpyAsync(out, ctx->tmp_b.p, sizeof(a3_board_pose), hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(launch_board_pose(ctx->stream, nullptr, in.at(s_ids), d_pts, nullptr, nullptr, nullptr, (uint32_t)n_markers, 1u, ctx->board_slot_of.as<uint16_t>(),
+                             ctx->n_codes, ctx->board_slot_rec.p, intr, image_width, image_height, res.at(s_out)));
+    A3_HIP(res.download(s_out, out));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }
@@ -2439,22 +2415,15 @@ int a3_set_charuco(a3_ctx* ctx, const float* corners_xy, const uint32_t* adjacen
 int a3_get_charuco_corners(a3_ctx* ctx, a3_charuco_corner* dst, size_t cap, size_t* n) {
     if (!ctx || !n || (!dst && cap)) return A3_ERR_INVALID;
     *n = 0;
-    if (!ctx->charuco_valid) return fail(ctx, A3_ERR_INVALID, "a3_get_charuco_corners: the last collected batch ran without ChArUco");
-    *n = ctx->h_charuco.size();
-    if (*n > cap) return fail(ctx, A3_ERR_CAPACITY, "a3_get_charuco_corners: cap is smaller than the number of corners");
-    if (*n) memcpy(dst, ctx->h_charuco.data(), *n * sizeof(a3_charuco_corner));
-    return A3_OK;
+    return get_last(ctx, ctx->charuco_valid, ctx->h_charuco, 1, dst, cap, n, "a3_get_charuco_corners: the last collected batch ran without ChArUco",
+                    "a3_get_charuco_corners: cap is smaller than the number of corners");
 }
 
 int a3_get_charuco_poses(a3_ctx* ctx, a3_charuco_pose* dst, size_t cap_frames, size_t* n) {
     if (!ctx || !n || (!dst && cap_frames)) return A3_ERR_INVALID;
     *n = 0;
-    if (!ctx->charuco_pose_valid)
-        return fail(ctx, A3_ERR_INVALID, "a3_get_charuco_poses: the last collected batch was not a pose batch with ChArUco set");
-    *n = ctx->h_charuco_pose.size();
-    if (*n > cap_frames) return fail(ctx, A3_ERR_CAPACITY, "a3_get_charuco_poses: cap_frames is smaller than the number of frames");
-    if (*n) memcpy(dst, ctx->h_charuco_pose.data(), *n * sizeof(a3_charuco_pose));
-    return A3_OK;
+    return get_last(ctx, ctx->charuco_pose_valid, ctx->h_charuco_pose, 1, dst, cap_frames, n,
+                    "a3_get_charuco_poses: the last collected batch was not a pose batch with ChArUco set", "a3_get_charuco_poses: cap_frames is smaller than the number of frames");
 }
 
 int a3_interpolate_charuco(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
@@ -2475,30 +2444,24 @@ int a3_interpolate_charuco(a3_ctx* ctx, const void* pixels, int memory, int fmt,
     if (int urc = upload_board(ctx)) return urc;
     if (int urc = upload_charuco(ctx)) return urc;
     const uint32_t nc = ctx->charuco_nc;
-    const size_t id_bytes = (n_markers * 4 + 255) & ~(size_t)255, pts_bytes = n_markers * 8 * sizeof(float);
-    const size_t rec_bytes = ((size_t)nc * sizeof(a3_charuco_corner) + 255) & ~(size_t)255;
-    A3_HIP(ctx->tmp_a.ensure(std::max<size_t>(id_bytes + pts_bytes, 256)));
-    A3_HIP(ctx->tmp_c.ensure(2 * rec_bytes + 256));
-    uint32_t* d_ids = ctx->tmp_a.as<uint32_t>();
-    float* d_pts = reinterpret_cast<float*>(ctx->tmp_a.as<uint8_t>() + id_bytes);
-    a3_charuco_corner* d_slots = ctx->tmp_c.as<a3_charuco_corner>();
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(ctx->tmp_c.as<uint8_t>() + rec_bytes);
-    a3_charuco_corner* d_out = reinterpret_cast<a3_charuco_corner*>(ctx->tmp_c.as<uint8_t>() + rec_bytes + 256);
-    if (n_markers) {
-        A3_HIP(hipMemcpyAsync(d_ids, ids, n_markers * 4, hipMemcpyHostToDevice, ctx->stream));
-        A3_HIP(hipMemcpyAsync(d_pts, corners_xy, pts_bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    A3_HIP(launch_charuco_corners(ctx->stream, PixelSrc{d_pixels, row_stride, frame_stride, fmt}, width, height, nullptr, d_ids, d_pts, nullptr, nullptr,
+    Layout in{ctx->tmp_a, ctx->stream}, res{ctx->tmp_c, ctx->stream};
+    const auto s_ids = in.add<uint32_t>(std::max<size_t>(n_markers, 1));   // (never an empty buffer)
+    const auto s_pts = in.add<float>(8 * n_markers);
+    // the frame's slot records, its two counts (the second: the total), the records in id order
+    const auto s_slots = res.add<a3_charuco_corner>(nc); const auto s_counts = res.add<uint32_t>(2); const auto s_out = res.add<a3_charuco_corner>(nc);
+    A3_HIP(in.ensure()); A3_HIP(res.ensure());
+    A3_HIP(in.upload(s_ids, ids, n_markers)); A3_HIP(in.upload(s_pts, corners_xy, 8 * n_markers));
+    A3_HIP(launch_charuco_corners(ctx->stream, PixelSrc{d_pixels, row_stride, frame_stride, fmt}, width, height, nullptr, in.at(s_ids), in.at(s_pts), nullptr, nullptr,
                                   nullptr, (uint32_t)n_markers, 1u, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p,
                                   ctx->charuco_tab.as<float>(), ctx->charuco_tab.as<uint32_t>() + 2 * (size_t)nc, nc, ctx->charuco_cfg.min_markers,
-                                  ctx->charuco_cfg.refine, charuco_params_for(ctx, ctx->charuco_cfg), nullptr, nullptr, d_slots, d_counts, d_out, nullptr));
+                                  ctx->charuco_cfg.refine, charuco_params_for(ctx, ctx->charuco_cfg), nullptr, nullptr, res.at(s_slots), res.at(s_counts), res.at(s_out), nullptr));
     uint32_t total = 0;
-    A3_HIP(hipMemcpyAsync(&total, d_counts + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+    A3_HIP(hipMemcpyAsync(&total, res.at(s_counts) + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     *n = total;
     if (total > cap) return fail(ctx, A3_ERR_CAPACITY, "a3_interpolate_charuco: cap is smaller than the number of corners");
     if (total) {
-        A3_HIP(hipMemcpyAsync(dst, d_out, (size_t)total * sizeof(a3_charuco_corner), hipMemcpyDeviceToHost, ctx->stream));
+        A3_HIP(hipMemcpyAsync(dst, res.at(s_out), (size_t)total * sizeof(a3_charuco_corner), hipMemcpyDeviceToHost, ctx->stream));
         A3_HIP(hipStreamSynchronize(ctx->stream));
     }
     return A3_OK;
@@ -2548,15 +2511,10 @@ int a3_set_distortion(a3_ctx* ctx, const a3_distortion* d) {
 int a3_get_undistorted_corners(a3_ctx* ctx, float* dst_xy, float* residual_px, size_t cap_markers, size_t* n) {
     if (!ctx) return A3_ERR_INVALID;
     if (!n || (!dst_xy && cap_markers)) return fail(ctx, A3_ERR_INVALID, "a3_get_undistorted_corners: null argument");
-    if (!ctx->undist_valid) return fail(ctx, A3_ERR_INVALID, "a3_get_undistorted_corners: the last collected batch ran without lens distortion");
-    const size_t total = ctx->h_undist.size() / 8;
-    *n = total;
-    if (total > cap_markers) return fail(ctx, A3_ERR_CAPACITY, "a3_get_undistorted_corners: cap_markers is smaller than the number of markers");
-    if (total) {
-        memcpy(dst_xy, ctx->h_undist.data(), total * 8 * sizeof(float));
-        if (residual_px) memcpy(residual_px, ctx->h_undist_res.data(), total * 4 * sizeof(float));
-    }
-    return A3_OK;
+    const int rc = get_last(ctx, ctx->undist_valid, ctx->h_undist, 8, dst_xy, cap_markers, n, "a3_get_undistorted_corners: the last collected batch ran without lens distortion",
+                            "a3_get_undistorted_corners: cap_markers is smaller than the number of markers");   // (*n: untouched by the first refusal)
+    if (rc == A3_OK && *n && residual_px) memcpy(residual_px, ctx->h_undist_res.data(), *n * 4 * sizeof(float));
+    return rc;
 }
 
 int a3_undistort_points(a3_ctx* ctx, const float* xy, size_t n, const a3_intrinsics* intr, const a3_distortion* d, float* out_xy,
@@ -2570,14 +2528,12 @@ int a3_undistort_points(a3_ctx* ctx, const float* xy, size_t n, const a3_intrins
     if (n == 0) return A3_OK;
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
-    const size_t xy_bytes = n * 2 * sizeof(float);
-    A3_HIP(ctx->tmp_a.ensure(xy_bytes));
-    A3_HIP(ctx->tmp_b.ensure(xy_bytes + n * sizeof(float)));
-    A3_HIP(hipMemcpyAsync(ctx->tmp_a.p, xy, xy_bytes, hipMemcpyHostToDevice, ctx->stream));
-    float* d_out = ctx->tmp_b.as<float>();
-    A3_HIP(launch_undistort_corners(ctx->stream, nullptr, ctx->tmp_a.as<float>(), nullptr, (uint32_t)n, *intr, *d, d_out, d_out + n * 2));
-    A3_HIP(hipMemcpyAsync(out_xy, d_out, xy_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (residual_px) A3_HIP(hipMemcpyAsync(residual_px, d_out + n * 2, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    Layout in{ctx->tmp_a, ctx->stream}, out{ctx->tmp_b, ctx->stream};
+    const auto s_xy = in.add<float>(2 * n), s_out = out.add<float>(2 * n), s_res = out.add<float>(n);
+    A3_HIP(in.ensure()); A3_HIP(out.ensure());
+    A3_HIP(in.upload(s_xy, xy, 2 * n));
+    A3_HIP(launch_undistort_corners(ctx->stream, nullptr, in.at(s_xy), nullptr, (uint32_t)n, *intr, *d, out.at(s_out), out.at(s_res)));
+    A3_HIP(out.download(s_out, out_xy)); A3_HIP(out.download(s_res, residual_px));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
 }
