@@ -14,101 +14,9 @@
 
 #include "a3_common.h"
 #include "a3_internal.h"
+#include "a3_launch.h"
 #include "a3_readback.h"
 #include "a3_solve_check.h"
-
-namespace a3 {
-// k_threshold.hip
-hipError_t launch_grey_threshold(hipStream_t, const uint8_t*, int, size_t, size_t, int, int, uint32_t, uint32_t, uint8_t*, uint64_t*, uint16_t*);
-bool threshold_writes_grey_plane(uint32_t radius, const uint8_t* pixels, size_t row_stride, size_t frame_stride, int W);
-// k_contours.hip
-hipError_t launch_dart_count(hipStream_t, const uint64_t*, int, int, uint32_t, uint32_t, unsigned long long*, uint32_t*, uint64_t, uint32_t*, uint32_t*, void*, size_t);
-size_t tile_darts_bytes(uint32_t W, uint32_t H, uint32_t n_frames);
-size_t tile_off_offset(uint32_t W, uint32_t H, uint32_t n_frames);
-size_t tile_mask_offset_bytes(uint32_t W, uint32_t H, uint32_t n_frames);
-hipError_t launch_dart_build(hipStream_t, const uint64_t*, int, int, uint32_t, uint32_t, const uint32_t*, const uint32_t*, uint32_t*, const uint32_t*,
-                             uint64_t*, uint32_t*, uint32_t, const uint32_t*, int, const unsigned long long*);
-hipError_t launch_zero(hipStream_t, void*, size_t);
-size_t entry_state_bytes();
-bool finalize_inline(bool frame_entries, bool trust_natural);
-size_t fin_state_bytes();
-size_t entry_slots(uint32_t);
-size_t leader_list_bytes(uint32_t);
-hipError_t launch_rank_cycles(hipStream_t, uint32_t, int, const uint64_t*, const uint32_t*,
-                              uint32_t*, unsigned int*, void*, void*, void*, uint32_t*, unsigned int*, int, DeviceCounters*, const uint32_t*, int,
-                              const uint32_t*, uint32_t*, uint32_t, int, uint32_t, unsigned int*, int);
-hipError_t launch_resolve(hipStream_t, const void*, uint32_t, int, const uint64_t*, const uint32_t*, const unsigned int*, uint64_t*, uint64_t*,
-                          DeviceCounters*, int, const uint32_t*);
-hipError_t launch_select_scatter(hipStream_t, const void*, uint32_t, const uint32_t*, const unsigned int*, const uint32_t*, const uint64_t*,
-                                 const uint32_t*, uint32_t, uint32_t,
-                                 uint32_t, double, double, ContourRec*, uint32_t*, uint32_t, uint64_t, DeviceCounters*,
-                                 const uint64_t*, uint32_t*, const uint32_t*, int, uint32_t*, int, const void*);
-hipError_t launch_debug_clockwise(hipStream_t, const int32_t*, uint32_t, int32_t*);
-hipError_t launch_unpack_bits(hipStream_t, const uint64_t*, int, int, uint8_t*);
-hipError_t launch_contour_quads(hipStream_t, const ContourRec*, const DeviceCounters*, uint32_t, const uint32_t*, double, uint32_t, uint32_t,
-                                uint32_t, CandRec*, uint32_t*, unsigned int*, int, uint32_t);
-// k_decode.hip
-size_t decode_out_bytes();
-hipError_t launch_frame_candidates(hipStream_t, const CandRec*, const uint32_t*, uint32_t, uint32_t, float, uint16_t*, uint16_t*, uint32_t*,
-                                   uint32_t*, unsigned int*, uint32_t, void*, float*);
-uint32_t frame_cand_lds_slots();
-size_t proj_rec_bytes();
-size_t weight_table_bytes();
-hipError_t launch_weight_table(hipStream_t, uint32_t, uint32_t, uint32_t, float*);
-hipError_t launch_decode(hipStream_t, PixelSrc, int, int, uint32_t, const uint16_t*, const uint32_t*, const unsigned int*, uint32_t,
-                         uint32_t, uint32_t, uint32_t, const uint64_t*, uint32_t, uint32_t, int, void*, const float*, void*, uint8_t*, uint32_t, uint32_t*, int, int, int);
-hipError_t launch_compact_markers(hipStream_t, const void*, const uint16_t*, const uint32_t*, uint32_t, uint32_t, uint32_t, a3_marker*,
-                                  uint32_t, uint32_t*, unsigned int*, unsigned int*, const uint32_t*, unsigned int*);
-hipError_t launch_pack_detections(hipStream_t, const a3_marker*, const a3_pose*, const uint32_t*, uint32_t, uint32_t, uint32_t, void*, unsigned int*);
-hipError_t launch_debug_rotate_bits(hipStream_t, const uint8_t*, uint32_t, uint32_t, uint8_t*);
-hipError_t launch_gather_patches(hipStream_t, const void*, uint32_t, const uint8_t*, uint32_t, uint32_t, uint8_t*, unsigned int*);
-hipError_t launch_pose(hipStream_t, const uint32_t*, uint32_t, const float*, uint32_t, const unsigned int*, int, float, float, float, float,
-                       float, float, float, a3_pose*);
-hipError_t launch_find_nearest(hipStream_t, const uint64_t*, uint32_t, const uint64_t*, uint32_t, uint32_t*, uint8_t*);
-size_t refine_params_bytes();
-void refine_params(void*, const a3_refine_config&, uint32_t);
-hipError_t launch_refine_corners(hipStream_t, PixelSrc, uint32_t, uint32_t, const a3_marker*, const unsigned int*, const float*, const float*, uint32_t,
-                                 const void*, float*);
-size_t board_slot_bytes();
-void board_slot_from(const float*, void*);
-hipError_t launch_board_pose(hipStream_t, const a3_marker*, const uint32_t*, const float*, const float*, const unsigned int*, const uint32_t*,
-                             uint32_t, uint32_t, const uint16_t*, uint32_t, const void*, const a3_intrinsics*, uint32_t, uint32_t, a3_board_pose*);
-hipError_t launch_undistort_corners(hipStream_t, const a3_marker*, const float*, const unsigned int*, uint32_t, const a3_intrinsics&,
-                                    const a3_distortion&, float*, float*);
-hipError_t launch_charuco_corners(hipStream_t, PixelSrc, uint32_t, uint32_t, const a3_marker*, const uint32_t*, const float*, const float*,
-                                  const unsigned int*, const uint32_t*, uint32_t, uint32_t, const uint16_t*, uint32_t, const void*, const float*,
-                                  const uint32_t*, uint32_t, uint32_t, uint32_t, const void*, const a3_intrinsics*, const a3_distortion*,
-                                  a3_charuco_corner*, uint32_t*, a3_charuco_corner*, float*);
-hipError_t launch_charuco_pose(hipStream_t, const a3_marker*, const float*, const unsigned int*, const uint32_t*, uint32_t, uint32_t, const uint16_t*,
-                               uint32_t, const void*, const float*, uint32_t, const uint32_t*, const a3_charuco_corner*, const float*,
-                               const a3_intrinsics*, uint32_t, uint32_t, a3_charuco_pose*);
-hipError_t launch_calc_tau(hipStream_t, const uint64_t*, uint32_t, unsigned int*);
-size_t map_obs_bytes();
-size_t map_frame_bytes();
-size_t map_marker_bytes();
-hipError_t launch_map(hipStream_t, const a3_map*, uint32_t, const a3_map_marker*, const a3_map_observation*, const float*, const uint64_t*, uint32_t*,
-                      uint32_t*, double*, double*, double*, double*, a3_map_result*, a3_map_marker_result*, a3_map_frame*, a3_map_observation_result*);
-size_t rig_obs_bytes();
-size_t rig_frame_bytes();
-size_t rig_table_bytes();
-hipError_t launch_rig(hipStream_t, const a3_rig*, uint32_t, const a3_rig_camera*, const a3_rig_observation*, const float*, const float*, uint32_t*,
-                      double*, double*, a3_rig_result*, a3_rig_camera_result*, a3_rig_frame*, a3_rig_observation_result*);
-size_t handeye_frame_bytes();
-hipError_t launch_handeye(hipStream_t, const a3_handeye_problem*, uint32_t, const a3_handeye_frame*, const float*, const float*, double*,
-                          a3_handeye_result*, a3_handeye_frame_result*);
-size_t calib_view_bytes();
-hipError_t launch_calibrate(hipStream_t, const a3_calib_camera*, uint32_t, const uint32_t*, const float*, const float*, double*, a3_calib_result*,
-                            a3_calib_view*);
-size_t fisheye_calib_view_bytes();
-hipError_t launch_calibrate_fisheye(hipStream_t, const a3_calib_camera*, uint32_t, const uint32_t*, const float*, const float*, double*, float*,
-                                    float*, a3_calib_result*, a3_calib_view*);
-void rectify_grid(uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*);
-hipError_t launch_rectify(hipStream_t, const uint8_t*, size_t, size_t, uint32_t, int, const a3_rectify&, uint8_t*, size_t, size_t);
-hipError_t launch_synth_render(hipStream_t, const a3_synth_frame*, uint32_t, const a3_synth_marker*, uint32_t, uint32_t, int, float, float, int,
-                               uint8_t*, size_t, size_t);
-hipError_t launch_spin(hipStream_t, int, int, int, uint32_t*);
-hipError_t launch_selftest(hipStream_t, const double*, const double*, uint32_t, double*, double*, float*, float*);
-}  // namespace a3
 
 using namespace a3;
 
@@ -535,13 +443,28 @@ const void* charuco_params_for(a3_ctx* ctx, const a3_charuco_config& cfg) {
     return ctx->charuco_prm.data();
 }
 
+// the board's and the ChArUco setting's device tables (upload_board, upload_charuco); nc: the chessboard corners of the setting in force
+BoardTables board_tables(const a3_ctx* ctx, uint32_t nc) {
+    return {.slot_of = ctx->board_slot_of.as<uint16_t>(), .n_codes = ctx->n_codes, .slots = ctx->board_slot_rec.p, .cxy = ctx->charuco_tab.as<float>(),
+            .adj = ctx->charuco_tab.as<uint32_t>() + 2 * (size_t)nc, .nc = nc};
+}
+// The decode stage on the context's buffers as the last enqueue_front / layout_zero_block left them: what the product path
+// (enqueue_back) and the probe (a3_debug_kernel_time) share.  The frames, the table size, the grid and the taps are the caller's.
+DecodeStage decode_stage(const a3_ctx* ctx) {
+    const uint32_t S = ctx->cfg.homography_sample_size;
+    DecodeStage d;
+    d.cands = ctx->cands.as<CandRec>(); d.cand_count = ctx->cand_count; d.pre_xy = ctx->pre_xy.as<uint16_t>(); d.fin_xy = ctx->fin_xy.as<uint16_t>();
+    d.fin_count = ctx->fin_count.as<uint32_t>(); d.work = ctx->work.as<uint32_t>(); d.S = S; d.proj = ctx->proj.p; d.big_scratch = ctx->cand_big.as<float>();
+    d.n = ctx->mark_size; d.max_taps = S; d.dict = ctx->dict.as<uint64_t>(); d.n_codes = ctx->n_codes; d.tau = ctx->tau;
+    d.filter = ctx->cfg.filter_high_bit_errors; d.wtab = ctx->wtab.as<float>(); d.outs = ctx->outs.p; d.per_frame = ctx->per_frame; d.markers = ctx->markers_ptr;
+    d.work_count = ctx->scratch_u32 + 0; d.marker_total = ctx->scratch_u32 + 1; d.cand_pre_total = ctx->scratch_u32 + 2; d.err_flags = ctx->scratch_u32 + 4;
+    return d;
+}
+
 // candidates -> markers -> read-back of one batch, on stream `st` (the context's stream, or its decode stream when deferred)
 int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
-    const uint32_t S = ctx->cfg.homography_sample_size;
     const float min_corner_separation = (float)std::min(b.W, b.H) * ctx->cfg.min_corner_separation_factor;   // src/aruco.rs:56
-    unsigned int* d_work_count = ctx->scratch_u32 + 0;
     unsigned int* d_marker_total = ctx->scratch_u32 + 1;
-    unsigned int* d_err = ctx->scratch_u32 + 4;
     if (ctx->inject_armed) {   // (test hook; never set by a caller of the public header)
         ctx->inject_armed = false;
         const uint32_t cnt = (uint32_t)ctx->inject.size();
@@ -549,55 +472,56 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
         ctx->inject_count = cnt;
         A3_HIP(hipMemcpyAsync(ctx->cand_count, &ctx->inject_count, 4, hipMemcpyHostToDevice, st));
     }
-    A3_HIP(launch_frame_candidates(st, ctx->cands.as<CandRec>(), ctx->cand_count, b.n, b.max_cand, min_corner_separation,
-                                   ctx->pre_xy.as<uint16_t>(), ctx->fin_xy.as<uint16_t>(), ctx->fin_count.as<uint32_t>(),
-                                   ctx->work.as<uint32_t>(), d_work_count, S, ctx->proj.p, ctx->cand_big.as<float>()));
     // few frames (small batches): all four waves of a workgroup run the stages behind the sampling.  (Round 5 tried folding the marker
     // gather into k_decode for one-frame calls -- its last workgroup, found by a ticket -- to save a launch: the call got 5 us SLOWER,
     // 166 against 161 us in alternating runs, a fence + ticket per workgroup and a serial tail costing more than the launch; removed.)
-    const int few = b.n <= 64u ? 1 : 0;
-    A3_HIP(launch_decode(st, b.src, (int)b.W, (int)b.H, 0, ctx->fin_xy.as<uint16_t>(), ctx->work.as<uint32_t>(), d_work_count,
-                         b.max_cand, S, ctx->mark_size, S, ctx->dict.as<uint64_t>(), ctx->n_codes, ctx->tau, ctx->cfg.filter_high_bit_errors,
-                         ctx->proj.p, ctx->wtab.as<float>(), ctx->outs.p, b.taps ? ctx->patches.as<uint8_t>() : nullptr, b.patch_cap, ctx->per_frame,
-                         (int)std::min<uint32_t>(4096u, b.n * 128u) /* (grid-stride over the work list; 4096 workgroups that find nothing cost a one-frame call ~4 us) */, 0,
-                         few));
-    A3_HIP(launch_compact_markers(st, ctx->outs.p, ctx->fin_xy.as<uint16_t>(), ctx->fin_count.as<uint32_t>(), b.n, 0, b.max_cand,
-                                  ctx->markers_ptr, b.marker_cap, ctx->per_frame, d_marker_total, d_err, ctx->cand_count, ctx->scratch_u32 + 2));
+    DecodeStage dec = decode_stage(ctx);
+    dec.n_frames = b.n; dec.max_cand = b.max_cand; dec.min_distance = min_corner_separation; dec.marker_cap = b.marker_cap;
+    dec.src = b.src; dec.W = (int)b.W; dec.H = (int)b.H; dec.few = b.n <= 64u;
+    if (b.taps) dec.patches = ctx->patches.as<uint8_t>();
+    dec.patch_cap = b.patch_cap;
+    dec.grid_blocks = (int)std::min<uint32_t>(4096u, b.n * 128u);   // (grid-stride over the work list; 4096 workgroups that find nothing cost a one-frame call ~4 us)
+    A3_HIP(launch_frame_candidates(st, dec));
+    A3_HIP(launch_decode(st, dec));
+    A3_HIP(launch_compact_markers(st, dec));
+    float* const refined = b.refined ? ctx->refined_buf.as<float>() : nullptr;
     if (b.refined)   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
-        A3_HIP(launch_refine_corners(st, b.src, b.W, b.H, ctx->markers_ptr, d_marker_total, nullptr, nullptr, b.marker_cap,
-                                     refine_params_for(ctx, b.refine), ctx->refined_buf.as<float>()));
+        A3_HIP(launch_refine_corners(st, {.src = b.src, .W = b.W, .H = b.H, .markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap,
+                                          .params = refine_params_for(ctx, b.refine), .out = refined}));
     if (b.undist)   // undistorted pixel corners of the same markers (of their refined corners with refinement on)
-        A3_HIP(launch_undistort_corners(st, ctx->markers_ptr, b.refined ? ctx->refined_buf.as<float>() : nullptr, d_marker_total, b.marker_cap,
-                                        b.pose_intr, b.dist, ctx->undist_buf.as<float>(), ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
-    // the float corners the poses are solved from: undistorted, else refined, else none (the integer corners)
-    const float* fcorners = b.undist ? ctx->undist_buf.as<float>() : b.refined ? ctx->refined_buf.as<float>() : nullptr;
+        A3_HIP(launch_undistort_corners(st, ctx->markers_ptr, refined, d_marker_total, b.marker_cap, b.pose_intr, b.dist, ctx->undist_buf.as<float>(),
+                                        ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
+    // the batch's marker list with the float corners the poses are solved from: undistorted, else refined, else none (the integer corners)
+    MarkerSrc m{.markers = ctx->markers_ptr, .n_dev = d_marker_total, .per_frame = ctx->per_frame, .corners = b.undist ? ctx->undist_buf.as<float>() : refined,
+                .n = b.marker_cap, .n_frames = b.n};
+    const BoardTables board = board_tables(ctx, b.charuco_nc);
+    const a3_intrinsics* const intr = b.pose_has_intr ? &b.pose_intr : nullptr;
     const uint32_t* charuco_counts = b.charuco ? reinterpret_cast<const uint32_t*>(ctx->charuco_tmp.as<uint8_t>() + charuco_slot_bytes(b)) : nullptr;
     float* charuco_und = b.charuco && b.want_pose && b.undist ? ctx->charuco_und.as<float>() : nullptr;
-    if (b.charuco)   // the chessboard corners of the same markers (their raw refined or integer corners), sampled as the refinement samples
-        A3_HIP(launch_charuco_corners(st, b.src, b.W, b.H, ctx->markers_ptr, nullptr, nullptr, b.refined ? ctx->refined_buf.as<float>() : nullptr,
-                                      d_marker_total, ctx->per_frame, b.marker_cap, b.n, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes,
-                                      ctx->board_slot_rec.p, ctx->charuco_tab.as<float>(), ctx->charuco_tab.as<uint32_t>() + 2 * (size_t)b.charuco_nc,
-                                      b.charuco_nc, b.charuco_cfg.min_markers, b.charuco_cfg.refine, charuco_params_for(ctx, b.charuco_cfg),
-                                      &b.pose_intr, &b.dist, ctx->charuco_tmp.as<a3_charuco_corner>(), const_cast<uint32_t*>(charuco_counts),
-                                      ctx->charuco_buf.as<a3_charuco_corner>(), charuco_und));
+    if (b.charuco) {   // the chessboard corners of the same markers (their raw refined or integer corners), sampled as the refinement samples
+        MarkerSrc raw = m;
+        raw.corners = refined;
+        A3_HIP(launch_charuco_corners(st, {.src = b.src, .W = b.W, .H = b.H, .m = raw, .board = board, .min_markers = b.charuco_cfg.min_markers,
+                                           .refine = b.charuco_cfg.refine, .params = charuco_params_for(ctx, b.charuco_cfg), .intr = &b.pose_intr, .dist = &b.dist,
+                                           .slots_tmp = ctx->charuco_tmp.as<a3_charuco_corner>(), .counts = const_cast<uint32_t*>(charuco_counts),
+                                           .out = ctx->charuco_buf.as<a3_charuco_corner>(), .und = charuco_und}));
+    }
     if (b.want_pose) {   // IPPE on the device-resident marker list (src/pose.rs:52-81), no extra round trip
         const a3_intrinsics& in = b.pose_intr;
-        if (fcorners)   // from float corners (k_pose modes 3 / 4)
-            A3_HIP(launch_pose(st, nullptr, 8u, fcorners, b.marker_cap, d_marker_total, b.pose_has_intr ? 4 : 3, b.pose_size_mm,
-                               (float)b.W, (float)b.H, in.focal_x, in.focal_y, in.principal_x, in.principal_y, ctx->pose_buf.as<a3_pose>()));
-        else
-            A3_HIP(launch_pose(st, reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(ctx->markers_ptr) + offsetof(a3_marker, corners)),
-                               (uint32_t)(sizeof(a3_marker) / 4), nullptr, b.marker_cap, d_marker_total, b.pose_has_intr ? 1 : 0, b.pose_size_mm,
-                               (float)b.W, (float)b.H, in.focal_x, in.focal_y, in.principal_x, in.principal_y, ctx->pose_buf.as<a3_pose>()));
+        PoseLaunch pose{.n = b.marker_cap, .n_dev = d_marker_total, .marker_size_mm = b.pose_size_mm, .iw = (float)b.W, .ih = (float)b.H, .fx = in.focal_x,
+                        .fy = in.focal_y, .cx = in.principal_x, .cy = in.principal_y, .out = ctx->pose_buf.as<a3_pose>()};
+        if (m.corners) {   // from float corners (k_pose modes 3 / 4)
+            pose.corner_stride = 8u; pose.norm_pts = m.corners; pose.mode = b.pose_has_intr ? 4 : 3;
+        } else {
+            pose.corners = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(ctx->markers_ptr) + offsetof(a3_marker, corners));
+            pose.corner_stride = (uint32_t)(sizeof(a3_marker) / 4); pose.mode = b.pose_has_intr ? 1 : 0;
+        }
+        A3_HIP(launch_pose(st, pose));
         if (b.board)   // one board pose per frame from the same device-resident markers (and refined corners), no extra round trip
-            A3_HIP(launch_board_pose(st, ctx->markers_ptr, nullptr, nullptr, fcorners, d_marker_total,
-                                     ctx->per_frame, b.marker_cap, b.n, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p,
-                                     b.pose_has_intr ? &in : nullptr, b.W, b.H, ctx->board_buf.as<a3_board_pose>()));
+            A3_HIP(launch_board_pose(st, {.m = m, .board = board, .intr = intr, .W = b.W, .H = b.H, .out = ctx->board_buf.as<a3_board_pose>()}));
         if (b.charuco)   // one ChArUco pose per frame from the records just written, the starts as the board pose takes them
-            A3_HIP(launch_charuco_pose(st, ctx->markers_ptr, fcorners, d_marker_total, ctx->per_frame, b.marker_cap, b.n,
-                                       ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p, ctx->charuco_tab.as<float>(),
-                                       b.charuco_nc, charuco_counts, ctx->charuco_buf.as<a3_charuco_corner>(), charuco_und,
-                                       b.pose_has_intr ? &in : nullptr, b.W, b.H, ctx->charuco_pose_buf.as<a3_charuco_pose>()));
+            A3_HIP(launch_charuco_pose(st, {.m = m, .board = board, .counts = charuco_counts, .recs = ctx->charuco_buf.as<a3_charuco_corner>(), .und = charuco_und,
+                                            .intr = intr, .W = b.W, .H = b.H, .out = ctx->charuco_pose_buf.as<a3_charuco_pose>()}));
     }
     if (b.prof >= 2) A3_HIP(hipEventRecord(ctx->ev[3], st));
     // ---- results: one copy of [scratch | counters | per-frame counts | `guess` markers], then the poses and (taps) the counts ----
@@ -780,7 +704,7 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     const uint32_t kMaxCand = ctx->max_cand;
     // the grey plane is materialised only for readers outside the fused path: Detection.grey (debug taps) and the generic
     // threshold kernels (windows above 15); the decode stage otherwise samples the caller's frames directly
-    const bool big_window = threshold_writes_grey_plane(ctx->cfg.threshold_window, b.pixels, b.row_stride, b.frame_stride, (int)W);
+    const bool big_window = threshold_writes_grey_plane(ctx->cfg.threshold_window);
     b.need_grey = b.taps || big_window;
     b.grey_src = big_window || (b.taps && !b.sample_frames);
     if (b.need_grey) A3_HIP(ctx->grey.ensure(npx * n));
@@ -809,14 +733,33 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     // ---- K1 ----
     b.prof = b.profiling == 1 && (ctx->batch_seq++ % (uint32_t)b.profile_every) != 0 ? 0 : b.profiling;
     if (b.prof) A3_HIP(hipEventRecord(ctx->ev[0], st));
-    A3_HIP(launch_grey_threshold(st, b.pixels, b.fmt, b.row_stride, b.frame_stride, (int)W, (int)H, n, ctx->cfg.threshold_window,
-                                 b.need_grey ? ctx->grey.as<uint8_t>() : nullptr, ctx->bin.as<uint64_t>(), big_window ? ctx->hsum.as<uint16_t>() : nullptr));
+    A3_HIP(launch_grey_threshold(st, {.pixels = b.pixels, .fmt = b.fmt, .row_stride = b.row_stride, .frame_stride = b.frame_stride, .W = (int)W, .H = (int)H,
+                                      .n = n, .radius = ctx->cfg.threshold_window, .grey = b.need_grey ? ctx->grey.as<uint8_t>() : nullptr,
+                                      .bits = ctx->bin.as<uint64_t>(), .hsum_tmp = big_window ? ctx->hsum.as<uint16_t>() : nullptr}));
     if (b.prof) A3_HIP(hipEventRecord(ctx->ev[1], st));
     if (!held) return A3_OK;
     A3_HIP(hipEventRecord(ctx->ev_k1_done, st));   // (held chains of a burst wait for the last member's)
     const uint64_t cap_d = device_plan_capacity(ctx, n, W, H);
     if (cap_d == 0) return fail(ctx, A3_ERR_INTERNAL, "a chain was held back for a batch that needs a host-side plan");
     return ensure_chain_buffers(ctx, st, b, cap_d);
+}
+
+// The contour stage's buffers as the last enqueue_front / layout_zero_block left them, for a chunk of the context's batch: what the
+// chunk loop (enqueue_chain) and the probe (a3_debug_kernel_time) share.  The chunk, the settings and n_live are the caller's.
+ContourChunk contour_chunk(const a3_ctx* ctx) {
+    ContourChunk c;
+    c.W = (int)ctx->W; c.H = (int)ctx->H; c.batch_frames = ctx->frames;
+    c.bits = ctx->bin.as<uint64_t>(); c.tile_darts = ctx->tile_darts.as<uint32_t>(); c.pix_base = ctx->pix_base.as<uint32_t>();
+    c.d_rec = ctx->d_xy.as<uint64_t>(); c.d_succ = ctx->d_succ.as<uint32_t>();
+    c.entry_list = ctx->entry_list.as<uint32_t>(); c.es_a = ctx->es_a.p; c.es_b = ctx->es_b.p; c.fin = ctx->fin.p;
+    c.leader_count = ctx->scratch_u32 + 16; c.entry_count = ctx->scratch_u32 + 32;   // [16..31], [32..47]
+    c.leader_list = ctx->leader_list.as<uint32_t>(); c.leader_keep = ctx->leader_keep.as<uint32_t>();
+    c.t_cur = ctx->t_cur.as<uint64_t>(); c.t_next = ctx->t_next.as<uint64_t>();
+    c.contours = ctx->contours.as<ContourRec>(); c.cyc_start_off = ctx->cyc_start_off.as<uint32_t>(); c.points = ctx->points.as<uint32_t>();
+    c.max_contours = ctx->max_contours; c.max_points = ctx->max_points;
+    c.cands = ctx->cands.as<CandRec>(); c.cand_count = ctx->cand_count;
+    c.err_flags = ctx->scratch_u32 + 4;   // ([0] work count, [1] marker total: enqueue_back)
+    return c;
 }
 
 // Everything after the threshold kernel.  `defer_locked`: the caller holds g_defer_mu (a held chain released by another context's
@@ -888,9 +831,10 @@ int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
         A3_HIP(hipMemsetAsync(ctx->frame_darts.p, 0, (size_t)n * 8, st));
     }
     // device plan: frame bases and the dart total come out of the same launch sequence (scratch words 8..11, read back with the results)
-    A3_HIP(launch_dart_count(st, ctx->bin.as<uint64_t>(), (int)W, (int)H, 0, n, ctx->frame_darts_ptr, ctx->tile_darts.as<uint32_t>(), cap_d,
-                             device_plan ? ctx->frame_base.as<uint32_t>() : nullptr, device_plan ? ctx->scratch_u32 + 8 : nullptr,
-                             device_plan ? zero_p : nullptr, device_plan ? zero_bytes : 0));
+    DartCountLaunch count{.bits = ctx->bin.as<uint64_t>(), .W = (int)W, .H = (int)H, .n_frames = n, .frame_darts = ctx->frame_darts_ptr,
+                          .tile_darts = ctx->tile_darts.as<uint32_t>(), .plan_cap = cap_d};
+    if (device_plan) { count.frame_base = ctx->frame_base.as<uint32_t>(); count.plan = ctx->scratch_u32 + 8; count.zero_p = zero_p; count.zero_bytes = zero_bytes; }
+    A3_HIP(launch_dart_count(st, count));
     const uint32_t* n_live = device_plan ? ctx->scratch_u32 + 8 : nullptr;   // written by the plan workgroup of launch_dart_count
     uint32_t max_chunk_frames = n;
     if (!device_plan) {
@@ -934,33 +878,28 @@ int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
     }
     ctx->stats.chunks = (uint32_t)chunks.size();
 
-    unsigned int* d_err = ctx->scratch_u32 + 4;             // ([0] work count, [1] marker total: enqueue_back)
-    unsigned int* d_entry_count = ctx->scratch_u32 + 32;    // [32..47]
-    unsigned int* d_leader_count = ctx->scratch_u32 + 16;   // [16..31]
-    unsigned int* d_dead_count = ctx->scratch_u32 + 48;     // [48..63]: borders k_local_contract finished with (traced, never listed), 16 shards, all chunks
-
     // ---- contour stage, chunk by chunk ----
-    const uint64_t* d_bin = ctx->bin.as<uint64_t>();
-    const double image_diag = std::sqrt((double)W * W + (double)H * H);
-    const double eps_factor = ctx->cfg.contour_simplification_epsilon;
-    const int resolve_iters = ctx->resolve_full_ttl > 0 ? ctx->resolve_iters_hint : 0;
-    const int inline_resolve_W = ctx->resolve_full_ttl > 0 ? 0 : (int)W;
-    const int keep_all = b.taps ? 1 : 0;
+    ContourChunk cc = contour_chunk(ctx);
+    cc.n_live = n_live;
+    cc.resolve_iters = ctx->resolve_full_ttl > 0 ? ctx->resolve_iters_hint : 0;
+    cc.inline_resolve_W = ctx->resolve_full_ttl > 0 ? 0 : (int)W;
+    cc.min_edge_length = min_edge_length;
+    cc.eps_factor = ctx->cfg.contour_simplification_epsilon;
+    cc.keep_all = b.taps;
+    cc.max_cand = kMaxCand;
     int rounds_max = 0;
     for (size_t ci = 0; ci < chunks.size(); ci++) {
         const Chunk& c = chunks[ci];
-        DeviceCounters* ctr = ctx->counters + ci;
-        const uint32_t* fb = ctx->frame_base.as<uint32_t>() + ci * (max_chunk_frames + 1);
         const uint32_t nd = (uint32_t)c.darts;
         if (nd == 0) continue;
         if (ci > 0) {   // the batch-wide memset covered chunk 0
-            A3_HIP(hipMemsetAsync(d_leader_count, 0, 4 * 32, st));   // leader + entry counters, adjacent
+            A3_HIP(hipMemsetAsync(cc.leader_count, 0, 4 * 32, st));   // leader + entry counters, adjacent
             A3_HIP(hipMemsetAsync(ctx->frame_cursor, 0, (size_t)c.count * 4, st));   // per-frame entry counts
         }
-        const uint32_t* tile_off = ctx->tile_darts.as<uint32_t>() + tile_off_offset(W, H, n);
-        A3_HIP(launch_dart_build(st, d_bin, (int)W, (int)H, c.first, c.count, fb, tile_off, ctx->pix_base.as<uint32_t>(),
-                                 ctx->tile_darts.as<uint32_t>(), ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(), nd, n_live, 0,
-                                 reinterpret_cast<const unsigned long long*>(ctx->tile_darts.as<uint8_t>() + tile_mask_offset_bytes(W, H, n))));
+        cc.first_frame = c.first; cc.n_frames = c.count; cc.n_darts = nd;
+        cc.frame_base = ctx->frame_base.as<uint32_t>() + ci * (max_chunk_frames + 1);
+        cc.ctr = ctx->counters + ci;
+        A3_HIP(launch_dart_build(st, cc));
         int rounds = 1;
         while ((1ull << rounds) < (uint64_t)c.max_frame_darts && rounds < 31) rounds++;
         rounds += 1;  // the round that observes "nothing moved"
@@ -968,36 +907,22 @@ int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
         // a3_debug_set_jump_rounds: too few rounds on purpose (not for the re-run with all rounds that a short launch asks for)
         if (const int cap = g_jump_rounds_cap.load(std::memory_order_relaxed); cap > 0 && ctx->jump_rounds_hint < 32) rounds = std::min(rounds, cap);
         rounds_max = std::max(rounds_max, rounds);
-        uint32_t* const frame_entries = ctx->entry_global_ttl > 0 ? nullptr : ctx->frame_cursor;   // per-frame entry counts
+        cc.max_rounds = rounds;
+        cc.frame_entries = ctx->entry_global_ttl > 0 ? nullptr : ctx->frame_cursor;   // per-frame entry counts
         // Short borders are finished with inside k_local_contract (kDead) on DENSE graphs only -- noise-like frames, where nine borders
         // in ten die of their length: there it saves a sixth of the contour stage; on clean frames (a dart per hundred pixels, a few
         // dozen borders per frame) it would only cost its bookkeeping.  Results are the same either way.
         const bool dense_graph = (uint64_t)nd * 10u >= (uint64_t)c.count * npx;
-        unsigned int* const dead_ctr = (keep_all || !dense_graph) ? nullptr : d_dead_count;
-        // first half: the doubling rounds inside LDS tiles
-        A3_HIP(launch_rank_cycles(st, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(),
-                                  ctx->entry_list.as<uint32_t>(), d_entry_count, ctx->es_a.p, ctx->es_b.p,
-                                  ctx->fin.p, ctx->leader_list.as<uint32_t>(), d_leader_count, rounds, ctr, n_live, 0, fb,
-                                  frame_entries, c.count, 1, min_edge_length, dead_ctr, inline_resolve_W > 0 ? 1 : 0));
+        cc.dead_count = (b.taps || !dense_graph) ? nullptr : ctx->scratch_u32 + 48;   // [48..63]: borders k_local_contract finished with (traced, never listed), 16 shards, all chunks
+        cc.phase = 1;   // first half: the doubling rounds inside LDS tiles
+        A3_HIP(launch_rank_cycles(st, cc));
         if (rel_mode == 2) { if (int rc = release_waiting()) return rc; }   // waiting decode stages go out behind this k_local_contract
         ctx->dbg_nd = nd; ctx->dbg_frames = c.count; ctx->dbg_chunks = (uint32_t)chunks.size();
-        // second half: entry resolution, final states (+ border selection), point scatter, quads
-        A3_HIP(launch_rank_cycles(st, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(),
-                                  ctx->entry_list.as<uint32_t>(), d_entry_count, ctx->es_a.p, ctx->es_b.p,
-                                  ctx->fin.p /* the 8-byte states */, ctx->leader_list.as<uint32_t>(), d_leader_count, rounds, ctr,
-                                  n_live, 0, fb, frame_entries, c.count, 2, min_edge_length, dead_ctr, inline_resolve_W > 0 ? 1 : 0));
-        const void* fin = ctx->fin.p;
-        A3_HIP(launch_resolve(st, fin, nd, (int)W, ctx->d_xy.as<uint64_t>(), ctx->leader_list.as<uint32_t>(), d_leader_count,
-                              ctx->t_cur.as<uint64_t>(), ctx->t_next.as<uint64_t>(), ctr, resolve_iters, n_live));
-        A3_HIP(launch_select_scatter(st, fin, nd, ctx->leader_list.as<uint32_t>(), d_leader_count, ctx->d_succ.as<uint32_t>(), ctx->t_cur.as<uint64_t>(), fb,
-                                     c.count, c.first, min_edge_length, eps_factor, image_diag,
-                                     ctx->contours.as<ContourRec>(), ctx->cyc_start_off.as<uint32_t>(), ctx->max_contours, ctx->max_points, ctr,
-                                     ctx->d_xy.as<uint64_t>(), ctx->points.as<uint32_t>(), n_live, inline_resolve_W, ctx->leader_keep.as<uint32_t>(),
-                                     keep_all, finalize_inline(frame_entries != nullptr, inline_resolve_W > 0) ? ctx->es_a.p : nullptr));
-        A3_HIP(launch_contour_quads(st, ctx->contours.as<ContourRec>(), ctr, ctx->max_contours, ctx->points.as<uint32_t>(),
-                                    eps_factor, min_edge_length, c.first, kMaxCand,
-                                    ctx->cands.as<CandRec>() + (size_t)c.first * kMaxCand, ctx->cand_count + c.first, d_err,
-                                    W <= 16384u && H <= 16384u ? 1 : 0, nd));
+        cc.phase = 2;   // second half: entry resolution, final states (+ border selection), point scatter, quads
+        A3_HIP(launch_rank_cycles(st, cc));
+        A3_HIP(launch_resolve(st, cc));
+        A3_HIP(launch_select_scatter(st, cc));
+        A3_HIP(launch_contour_quads(st, cc));
     }
     if (rel_mode != 0) { if (int rc = release_waiting()) return rc; }   // (a batch without a contour graph releases here)
     if (b.prof >= 2) A3_HIP(hipEventRecord(ctx->ev[2], st));
@@ -1249,12 +1174,10 @@ int calibrate_impl(a3_ctx* ctx, bool fisheye, const a3_calib_camera* cams, size_
     A3_HIP(in.upload(s_obj, object_xy, 2 * n_pts)); A3_HIP(in.upload(s_img, image_xy, 2 * n_pts));
     // a view no camera owns is not written by the kernel: it comes back zero, not as what an earlier call left in the buffer
     A3_HIP(out.zero_from(s_views));
-    if (fisheye)
-        A3_HIP(launch_calibrate_fisheye(ctx->stream, in.at(s_cams), (uint32_t)n_cams, in.at(s_off), in.at(s_obj), in.at(s_img), scr.at(s_blocks),
-                                        scr.at(s_start_obj), scr.at(s_start_img), out.at(s_res), out.at(s_views)));
-    else
-        A3_HIP(launch_calibrate(ctx->stream, in.at(s_cams), (uint32_t)n_cams, in.at(s_off), in.at(s_obj), in.at(s_img), scr.at(s_blocks), out.at(s_res),
-                                out.at(s_views)));
+    const CalibLaunch cal{.cams = in.at(s_cams), .n_cams = (uint32_t)n_cams, .view_off = in.at(s_off), .obj = in.at(s_obj), .img = in.at(s_img),
+                          .scratch = scr.at(s_blocks), .start_obj = scr.at(s_start_obj), .start_img = scr.at(s_start_img), .res = out.at(s_res),
+                          .views = out.at(s_views)};
+    A3_HIP(fisheye ? launch_calibrate_fisheye(ctx->stream, cal) : launch_calibrate(ctx->stream, cal));
     A3_HIP(out.download(s_res, results));
     A3_HIP(out.download(s_views, views));
     A3_HIP(hipStreamSynchronize(ctx->stream));
@@ -1754,38 +1677,35 @@ int a3_debug_kernel_time(a3_ctx* ctx, int kernel, int dbg, int reps, float* avg_
     A3_HIP(hipEventCreate(&evp.e0)); A3_HIP(hipEventCreate(&evp.e1));
     const hipEvent_t e0 = evp.e0, e1 = evp.e1;
     double total = 0.0;
-    unsigned int* d_entry_count = ctx->scratch_u32 + 32;
-    unsigned int* d_leader_count = ctx->scratch_u32 + 16;
+    // the product path's launches (contour_chunk, decode_stage) on the whole last batch as one chunk; only what the probe sets differs
+    ContourChunk cc = contour_chunk(ctx);
+    cc.n_frames = ctx->dbg_frames; cc.n_darts = ctx->dbg_nd; cc.frame_base = ctx->frame_base.as<uint32_t>(); cc.ctr = ctx->counters;
     for (int r = 0; r < reps; r++) {
-        A3_HIP(hipMemsetAsync(d_leader_count, 0, 4 * 32, st));
+        A3_HIP(hipMemsetAsync(cc.leader_count, 0, 4 * 32, st));
         A3_HIP(hipEventRecord(e0, st));
         if (kernel == 0) {
             A3_HIP(hipMemsetAsync(ctx->frame_darts.p, 0, (size_t)ctx->frames * 8, st));
-            A3_HIP(launch_dart_count(st, ctx->bin.as<uint64_t>(), (int)ctx->W, (int)ctx->H, 0, ctx->frames, ctx->frame_darts.as<unsigned long long>(),
-                                     ctx->tile_darts.as<uint32_t>(), 0, nullptr, nullptr, nullptr, 0));
+            A3_HIP(launch_dart_count(st, {.bits = cc.bits, .W = cc.W, .H = cc.H, .n_frames = ctx->frames, .frame_darts = ctx->frame_darts.as<unsigned long long>(),
+                                          .tile_darts = ctx->tile_darts.as<uint32_t>()}));
         } else if (kernel == 1) {
-            A3_HIP(launch_dart_build(st, ctx->bin.as<uint64_t>(), (int)ctx->W, (int)ctx->H, 0, ctx->dbg_frames, ctx->frame_base.as<uint32_t>(),
-                                     ctx->tile_darts.as<uint32_t>() + tile_off_offset(ctx->W, ctx->H, ctx->frames), ctx->pix_base.as<uint32_t>(),
-                                     ctx->tile_darts.as<uint32_t>(), ctx->d_xy.as<uint64_t>(),
-                                     ctx->d_succ.as<uint32_t>(), ctx->dbg_nd, nullptr, dbg ? dbg : 5,
-                                     reinterpret_cast<const unsigned long long*>(ctx->tile_darts.as<uint8_t>() + tile_mask_offset_bytes(ctx->W, ctx->H, ctx->frames))));
+            cc.dbg = dbg ? dbg : 5;
+            A3_HIP(launch_dart_build(st, cc));
         } else if (kernel == 2) {
-            A3_HIP(launch_rank_cycles(st, ctx->dbg_nd, (int)ctx->W, ctx->d_xy.as<uint64_t>(), ctx->d_succ.as<uint32_t>(),
-                                      ctx->entry_list.as<uint32_t>(),
-                                      d_entry_count, ctx->es_a.p, ctx->es_b.p, ctx->fin.p,
-                                      ctx->leader_list.as<uint32_t>(), d_leader_count, 0, ctx->counters, nullptr, dbg ? dbg : 11, ctx->frame_base.as<uint32_t>(), nullptr, ctx->dbg_frames, 0,
-                                      0u, nullptr, 0));
-        } else if (kernel == 3 || kernel == 4) {   // dbg < 0: k_decode alone (variant -dbg; -5: the whole kernel), dbg >= 0: k_projection + k_decode
+            cc.dbg = dbg ? dbg : 11;
+            A3_HIP(launch_rank_cycles(st, cc));
+        } else if (kernel == 3 || kernel == 4) {
             if (kernel == 4) {   // COLD frames, as the pipeline meets them (1.6 GB went through the threshold kernel, the contour stage's buffers since):
                                  // half a gigabyte of the pixel-base plane is overwritten first (garbage after a batch anyway), outside the timed span
                 const size_t sweep = std::min<size_t>(ctx->pix_base.cap & ~(size_t)15, (size_t)512 << 20);
                 if (sweep) A3_HIP(launch_zero(st, ctx->pix_base.p, sweep));
                 A3_HIP(hipEventRecord(e0, st));
             }
-            A3_HIP(launch_decode(st, ctx->dbg_src, (int)ctx->W, (int)ctx->H, 0, ctx->fin_xy.as<uint16_t>(), ctx->work.as<uint32_t>(), ctx->scratch_u32,
-                                 ctx->max_cand, ctx->cfg.homography_sample_size, ctx->mark_size, ctx->cfg.homography_sample_size, ctx->dict.as<uint64_t>(),
-                                 ctx->n_codes, ctx->tau, ctx->cfg.filter_high_bit_errors, ctx->proj.p, ctx->wtab.as<float>(), ctx->outs.p, nullptr, 0u, nullptr, 4096,
-                                 dbg == 0 ? -1000 : dbg, ctx->frames <= 64u ? 1 : 0));   // 0: k_projection + k_decode, < 0: k_decode alone (variant -dbg)
+            // dbg >= 0: k_projection + k_decode, dbg < 0: k_decode alone; |dbg| 1..5 selects the truncated variant (5 and 0: the whole kernel)
+            DecodeStage dec = decode_stage(ctx);
+            dec.src = ctx->dbg_src; dec.W = cc.W; dec.H = cc.H; dec.max_cand = ctx->max_cand; dec.few = ctx->frames <= 64u; dec.grid_blocks = 4096;
+            dec.per_frame = nullptr;
+            dec.projection = dbg >= 0; dec.variant = dbg < 0 ? -dbg : dbg;
+            A3_HIP(launch_decode(st, dec));
         } else return fail(ctx, A3_ERR_INVALID, "kernel: 0 dart_count, 1 dart_assign, 2 local_contract, 3 decode, 4 decode on cold frames");
         A3_HIP(hipEventRecord(e1, st));
         A3_HIP(hipStreamSynchronize(ctx->stream));
@@ -1832,11 +1752,12 @@ int a3_debug_launch_threshold(a3_ctx* ctx, const void* pixels_device, int fmt, u
     A3_HIP(hipSetDevice(ctx->device));
     if (int rc = need_stream(ctx)) return rc;
     const size_t bpp = fmt == A3_FMT_RGB8 ? 3 : (fmt == A3_FMT_L8 ? 1 : 4);
-    if (threshold_writes_grey_plane(ctx->cfg.threshold_window, reinterpret_cast<const uint8_t*>(pixels_device), (size_t)width * bpp, (size_t)width * bpp * height, (int)width))
+    if (threshold_writes_grey_plane(ctx->cfg.threshold_window))
         return fail(ctx, A3_ERR_INVALID, "a3_debug_launch_threshold: this threshold_window / frame layout takes the separable path, which needs a grey plane");
     A3_HIP(ctx->bin.ensure((size_t)words_per_row(width) * 8 * height * n_frames));
-    A3_HIP(launch_grey_threshold(ctx->stream, reinterpret_cast<const uint8_t*>(pixels_device), fmt, (size_t)width * bpp, (size_t)width * bpp * height,
-                                 (int)width, (int)height, n_frames, ctx->cfg.threshold_window, nullptr, ctx->bin.as<uint64_t>(), nullptr));
+    A3_HIP(launch_grey_threshold(ctx->stream, {.pixels = reinterpret_cast<const uint8_t*>(pixels_device), .fmt = fmt, .row_stride = (size_t)width * bpp,
+                                               .frame_stride = (size_t)width * bpp * height, .W = (int)width, .H = (int)height, .n = n_frames,
+                                               .radius = ctx->cfg.threshold_window, .bits = ctx->bin.as<uint64_t>()}));
     return A3_OK;
 }
 
@@ -1873,8 +1794,9 @@ int a3_synth_render(int device, void* hip_stream, const a3_synth_frame* frames, 
     if (e == hipSuccess && n_markers) e = hipMalloc(&d_markers, sizeof(a3_synth_marker) * n_markers);
     if (e == hipSuccess) e = hipMemcpyAsync(d_frames, frames, sizeof(a3_synth_frame) * n_frames, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && n_markers) e = hipMemcpyAsync(d_markers, markers, sizeof(a3_synth_marker) * n_markers, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_synth_render(st, d_frames, n_frames, d_markers, width, height, paper, black, white, supersample,
-                                                 reinterpret_cast<uint8_t*>(out_rgb_device), row_stride, frame_stride);
+    if (e == hipSuccess) e = launch_synth_render(st, {.frames = d_frames, .n_frames = n_frames, .markers = d_markers, .W = width, .H = height, .paper = paper,
+                                                      .black = black, .white = white, .supersample = supersample,
+                                                      .out = reinterpret_cast<uint8_t*>(out_rgb_device), .row_stride = row_stride, .frame_stride = frame_stride});
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (d_frames) (void)hipFree(d_frames);
     if (d_markers) (void)hipFree(d_markers);
@@ -2123,8 +2045,9 @@ int a3_debug_discard_too_near(a3_ctx* ctx, const uint32_t* quads_xy, size_t n, f
     A3_HIP(hipMemcpyAsync(ctx->tmp_a.p, h.data(), n * sizeof(CandRec), hipMemcpyHostToDevice, ctx->stream));
     A3_HIP(hipMemcpyAsync(small, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
     uint16_t* pre = ctx->tmp_b.as<uint16_t>(); uint16_t* fin = pre + kMaxCand * 8;
-    A3_HIP(launch_frame_candidates(ctx->stream, ctx->tmp_a.as<CandRec>(), small, 1, kMaxCand, min_distance, pre, fin, small + 1,
-                                   ctx->tmp_c.as<uint32_t>(), small + 2, 0u, nullptr, nullptr));
+    A3_HIP(launch_frame_candidates(ctx->stream, {.n_frames = 1, .max_cand = kMaxCand, .cands = ctx->tmp_a.as<CandRec>(), .cand_count = small,
+                                                 .min_distance = min_distance, .pre_xy = pre, .fin_xy = fin, .fin_count = small + 1,
+                                                 .work = ctx->tmp_c.as<uint32_t>(), .work_count = small + 2}));
     uint32_t cnt = 0;
     A3_HIP(hipMemcpyAsync(&cnt, small + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
@@ -2187,9 +2110,10 @@ int a3_debug_frame_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t max_cand,
     A3_HIP(hipMemsetAsync(d_work.p, 0xFF, slots * 4, st));
     if (S) A3_HIP(hipMemsetAsync(d_proj.p, 0xFF, proj_bytes, st));
     if (big) A3_HIP(hipMemsetAsync(d_big.p, 0xFF, slots * 4, st));
-    A3_HIP(launch_frame_candidates(st, d_cands.as<CandRec>(), cnt, n_frames, max_cand, min_distance, d_pre.as<uint16_t>(), d_fin.as<uint16_t>(),
-                                   cnt + n_frames, d_work.as<uint32_t>(), cnt + 2 * (size_t)n_frames, S, S ? d_proj.p : nullptr,
-                                   big ? d_big.as<float>() : nullptr));
+    A3_HIP(launch_frame_candidates(st, {.n_frames = n_frames, .max_cand = max_cand, .cands = d_cands.as<CandRec>(), .cand_count = cnt, .min_distance = min_distance,
+                                        .pre_xy = d_pre.as<uint16_t>(), .fin_xy = d_fin.as<uint16_t>(), .fin_count = cnt + n_frames, .work = d_work.as<uint32_t>(),
+                                        .work_count = cnt + 2 * (size_t)n_frames, .S = S, .proj = S ? d_proj.p : nullptr,
+                                        .big_scratch = big ? d_big.as<float>() : nullptr}));
     A3_HIP(hipMemcpyAsync(pre_xy, d_pre.p, slots * 16, hipMemcpyDeviceToHost, st));
     A3_HIP(hipMemcpyAsync(fin_xy, d_fin.p, slots * 16, hipMemcpyDeviceToHost, st));
     A3_HIP(hipMemcpyAsync(fin_count, cnt + n_frames, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
@@ -2279,8 +2203,9 @@ int a3_refine_corners(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint
     A3_HIP(in.ensure()); A3_HIP(out.ensure());
     A3_HIP(in.upload(s_pts, corners_xy, 2 * n));
     if (cell_px) A3_HIP(in.upload(s_cell, cell_px, n));
-    A3_HIP(launch_refine_corners(ctx->stream, PixelSrc{d_pixels, row_stride, frame_stride, fmt}, width, height, nullptr, nullptr, in.at(s_pts),
-                                 cell_px ? in.at(s_cell) : nullptr, (uint32_t)n, refine_params_for(ctx, cfg), out.at(s_out)));
+    A3_HIP(launch_refine_corners(ctx->stream, {.src = {d_pixels, row_stride, frame_stride, fmt}, .W = width, .H = height, .pts = in.at(s_pts),
+                                               .cell_px = cell_px ? in.at(s_cell) : nullptr, .n = (uint32_t)n, .params = refine_params_for(ctx, cfg),
+                                               .out = out.at(s_out)}));
     A3_HIP(out.download(s_out, corners_xy));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
@@ -2355,8 +2280,8 @@ int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corner
         A3_HIP(launch_undistort_corners(ctx->stream, nullptr, d_pts, nullptr, (uint32_t)(n_markers * 4), *intr, ctx->dist, und.at(s_und), und.at(s_und_res)));
         d_pts = und.at(s_und);
     }
-    A3_HIP(launch_board_pose(ctx->stream, nullptr, in.at(s_ids), d_pts, nullptr, nullptr, nullptr, (uint32_t)n_markers, 1u, ctx->board_slot_of.as<uint16_t>(),
-                             ctx->n_codes, ctx->board_slot_rec.p, intr, image_width, image_height, res.at(s_out)));
+    A3_HIP(launch_board_pose(ctx->stream, {.m = {.ids = in.at(s_ids), .pts = d_pts, .n = (uint32_t)n_markers, .n_frames = 1u}, .board = board_tables(ctx, 0),
+                                           .intr = intr, .W = image_width, .H = image_height, .out = res.at(s_out)}));
     A3_HIP(res.download(s_out, out));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
@@ -2451,10 +2376,11 @@ int a3_interpolate_charuco(a3_ctx* ctx, const void* pixels, int memory, int fmt,
     const auto s_slots = res.add<a3_charuco_corner>(nc); const auto s_counts = res.add<uint32_t>(2); const auto s_out = res.add<a3_charuco_corner>(nc);
     A3_HIP(in.ensure()); A3_HIP(res.ensure());
     A3_HIP(in.upload(s_ids, ids, n_markers)); A3_HIP(in.upload(s_pts, corners_xy, 8 * n_markers));
-    A3_HIP(launch_charuco_corners(ctx->stream, PixelSrc{d_pixels, row_stride, frame_stride, fmt}, width, height, nullptr, in.at(s_ids), in.at(s_pts), nullptr, nullptr,
-                                  nullptr, (uint32_t)n_markers, 1u, ctx->board_slot_of.as<uint16_t>(), ctx->n_codes, ctx->board_slot_rec.p,
-                                  ctx->charuco_tab.as<float>(), ctx->charuco_tab.as<uint32_t>() + 2 * (size_t)nc, nc, ctx->charuco_cfg.min_markers,
-                                  ctx->charuco_cfg.refine, charuco_params_for(ctx, ctx->charuco_cfg), nullptr, nullptr, res.at(s_slots), res.at(s_counts), res.at(s_out), nullptr));
+    A3_HIP(launch_charuco_corners(ctx->stream, {.src = {d_pixels, row_stride, frame_stride, fmt}, .W = width, .H = height,
+                                                .m = {.ids = in.at(s_ids), .pts = in.at(s_pts), .n = (uint32_t)n_markers, .n_frames = 1u},
+                                                .board = board_tables(ctx, nc), .min_markers = ctx->charuco_cfg.min_markers, .refine = ctx->charuco_cfg.refine,
+                                                .params = charuco_params_for(ctx, ctx->charuco_cfg), .slots_tmp = res.at(s_slots), .counts = res.at(s_counts),
+                                                .out = res.at(s_out)}));
     uint32_t total = 0;
     A3_HIP(hipMemcpyAsync(&total, res.at(s_counts) + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
@@ -2575,8 +2501,9 @@ int a3_calibrate_rigs(a3_ctx* ctx, const a3_rig* rigs, size_t n_rigs, const a3_r
     A3_HIP(in.upload(s_obj, object_xy, 2 * n_pts)); A3_HIP(in.upload(s_img, image_xy, 2 * n_pts));
     // a camera, frame or observation that no rig owns is not written by the kernel: it comes back zero
     A3_HIP(out.zero_from(s_cres));
-    A3_HIP(launch_rig(ctx->stream, in.at(s_rigs), (uint32_t)n_rigs, in.at(s_cams), in.at(s_obs), in.at(s_obj), in.at(s_img), scr.at(s_tab), scr.at(s_oscr),
-                      scr.at(s_fscr), out.at(s_res), out.at(s_cres), out.at(s_frames), out.at(s_ores)));
+    A3_HIP(launch_rig(ctx->stream, {.rigs = in.at(s_rigs), .n_rigs = (uint32_t)n_rigs, .cams = in.at(s_cams), .obs = in.at(s_obs), .obj = in.at(s_obj),
+                                    .img = in.at(s_img), .tab = scr.at(s_tab), .oscr = scr.at(s_oscr), .fscr = scr.at(s_fscr), .res = out.at(s_res),
+                                    .cres = out.at(s_cres), .frames = out.at(s_frames), .ores = out.at(s_ores)}));
     A3_HIP(out.download(s_res, results));
     A3_HIP(out.download(s_cres, camera_results));
     A3_HIP(out.download(s_frames, frames));
@@ -2648,9 +2575,10 @@ int a3_build_marker_maps(a3_ctx* ctx, const a3_map* maps, size_t n_maps, const a
     A3_HIP(in.upload(s_off, big_off.data(), n_maps));
     // a marker, frame or observation that no map owns is not written by the kernel: it comes back zero
     A3_HIP(out.zero_from(s_mres));
-    A3_HIP(launch_map(ctx->stream, in.at(s_maps), (uint32_t)n_maps, in.at(s_mk), in.at(s_obs), in.at(s_img), in.at(s_off), scr.at(s_fo), scr.at(s_ml),
-                      scr.at(s_oscr), scr.at(s_fscr), scr.at(s_mscr), ctx->solve_big.as<double>(), out.at(s_res), out.at(s_mres), out.at(s_frames),
-                      out.at(s_ores)));
+    A3_HIP(launch_map(ctx->stream, {.maps = in.at(s_maps), .n_maps = (uint32_t)n_maps, .markers = in.at(s_mk), .obs = in.at(s_obs), .img = in.at(s_img),
+                                    .big_off = in.at(s_off), .fo = scr.at(s_fo), .ml = scr.at(s_ml), .oscr = scr.at(s_oscr), .fscr = scr.at(s_fscr),
+                                    .mscr = scr.at(s_mscr), .big = ctx->solve_big.as<double>(), .res = out.at(s_res), .mres = out.at(s_mres),
+                                    .frames = out.at(s_frames), .ores = out.at(s_ores)}));
     A3_HIP(out.download(s_res, results));
     A3_HIP(out.download(s_mres, marker_results));
     A3_HIP(out.download(s_frames, frames));
@@ -2724,7 +2652,8 @@ int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, siz
         A3_HIP(ctx->rect_out.ensure(d_frame * n_frames));
         d_dst = ctx->rect_out.as<uint8_t>();
     }
-    A3_HIP(launch_rectify(ctx->stream, d_src, src_row_stride, src_frame_stride, n_frames, (int)bpp, *r, d_dst, d_row, d_frame));
+    A3_HIP(launch_rectify(ctx->stream, {.src = d_src, .src_row = src_row_stride, .src_frame = src_frame_stride, .n_frames = n_frames, .bpp = (int)bpp, .r = r,
+                                        .dst = d_dst, .dst_row = d_row, .dst_frame = d_frame}));
     if (dst_memory == A3_MEM_HOST) {
         if (dst_frame_stride == dst_row_stride * dh) {
             A3_HIP(hipMemcpy2DAsync(dst, dst_row_stride, d_dst, d_row, d_row, (size_t)dh * n_frames, hipMemcpyDeviceToHost, ctx->stream));
@@ -2757,8 +2686,9 @@ static int pose_common(a3_ctx* ctx, const uint32_t* corners, const float* norm, 
     A3_HIP(hipMemcpyAsync(ctx->tmp_a.p, corners ? (const void*)corners : (const void*)norm, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     float fx = 1, fy = 1, cx = 0, cy = 0;
     if (intr) { fx = intr->focal_x; fy = intr->focal_y; cx = intr->principal_x; cy = intr->principal_y; }
-    A3_HIP(launch_pose(ctx->stream, corners ? ctx->tmp_a.as<uint32_t>() : nullptr, 8u, norm ? ctx->tmp_a.as<float>() : nullptr, (uint32_t)n, nullptr, mode,
-                       size_mm, (float)iw, (float)ih, fx, fy, cx, cy, ctx->tmp_b.as<a3_pose>()));
+    A3_HIP(launch_pose(ctx->stream, {.corners = corners ? ctx->tmp_a.as<uint32_t>() : nullptr, .corner_stride = 8u, .norm_pts = norm ? ctx->tmp_a.as<float>() : nullptr,
+                                     .n = (uint32_t)n, .mode = mode, .marker_size_mm = size_mm, .iw = (float)iw, .ih = (float)ih, .fx = fx, .fy = fy, .cx = cx,
+                                     .cy = cy, .out = ctx->tmp_b.as<a3_pose>()}));
     A3_HIP(hipMemcpyAsync(out, ctx->tmp_b.p, n * 2 * sizeof(a3_pose), hipMemcpyDeviceToHost, ctx->stream));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;

@@ -6,6 +6,7 @@
 
 #include "a3_common.h"
 #include "a3_ippe.h"
+#include "a3_launch.h"
 
 namespace a3 {
 
@@ -33,6 +34,16 @@ struct BoardArgs {
     float iw, ih, fx, fy, cx, cy;
     a3_board_pose* out;
 };
+
+// the kernels' view of a marker source and the board's tables (a3_launch.h); intr == nullptr: normalised by the image size
+inline BoardArgs board_args(const MarkerSrc& m, const BoardTables& t, const a3_intrinsics* intr, uint32_t W, uint32_t H) {
+    BoardArgs a{};
+    a.markers = m.markers; a.ids = m.ids; a.pts = m.pts; a.refined = m.corners; a.n_dev = m.n_dev; a.per_frame = m.per_frame;
+    a.n = m.n; a.n_frames = m.n_frames; a.slot_of = t.slot_of; a.n_codes = t.n_codes; a.slots = reinterpret_cast<const BoardSlot*>(t.slots);
+    a.has_intr = intr ? 1 : 0; a.iw = (float)W; a.ih = (float)H;
+    if (intr) { a.fx = intr->focal_x; a.fy = intr->focal_y; a.cx = intr->principal_x; a.cy = intr->principal_y; }
+    return a;
+}
 
 struct BoardAcc {
     float h[21], g[6], cost, pix;

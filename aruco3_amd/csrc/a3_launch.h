@@ -1,0 +1,247 @@
+// a3_launch.h -- every function one translation unit of the library defines and another calls: the kernel files' launchers and
+// size accessors, declared once, with the contract of each (what may be null, how capacities relate to counts, which buffers arrive
+// zeroed).  A launcher with more than eight parameters besides the stream takes (hipStream_t, const X&): X is a plain aggregate
+// whose members all default to null / 0, built at the call site with designated initialisers, so an optional input is a member the
+// caller leaves out.  Groups that travel together to several launchers are one struct, built once and passed on (ContourChunk,
+// DecodeStage, MarkerSrc, BoardTables).  The records the kernels keep to themselves (EntryState, FinState, ProjRec, DecodeOut, BoardSlot,
+// RefineParams, the solvers' scratch) stay opaque here: the host sees their sizes and void pointers.
+#pragma once
+
+#include "a3_common.h"
+
+namespace a3 {
+
+// ---- k_threshold.hip (+ _r1, _r2, _big): grey + adaptive threshold ----------------------------------------------------------
+// n frames of W x H pixels -> the packed image `bits`.  grey (nullable): the grey plane is written too; the separable path (see
+// threshold_writes_grey_plane) needs it and hsum_tmp (one u16 per pixel), the fused kernels need neither.
+struct ThresholdLaunch {
+    const uint8_t* pixels = nullptr; int fmt = 0; size_t row_stride = 0, frame_stride = 0; int W = 0, H = 0; uint32_t n = 0, radius = 0;
+    uint8_t* grey = nullptr; uint64_t* bits = nullptr; uint16_t* hsum_tmp = nullptr;
+};
+hipError_t launch_grey_threshold(hipStream_t st, const ThresholdLaunch& t);
+// this window takes the separable path, which reads a grey plane and a plane of row sums: radius 0 and radii above 31
+bool threshold_writes_grey_plane(uint32_t radius);
+hipError_t launch_k1_r1(hipStream_t st, const ThresholdLaunch& t);   // radii 1..3
+hipError_t launch_k1_r2(hipStream_t st, const ThresholdLaunch& t);   // radii 4..6
+bool ring_kernel_applies(uint32_t radius);                           // radii 8..31, any frame layout
+hipError_t launch_ring_threshold(hipStream_t st, const ThresholdLaunch& t);
+
+// ---- k_contours.hip: the contour stage ----------------------------------------------------------------------------------------
+// the tile tables of a batch: tile_darts[frames * tiles] | tile_off[frames * tiles] | second-half counts of k_dart_count[frames *
+// tiles], followed (8-byte aligned) by the word masks; launch_dart_count writes them, launch_dart_build reads them
+size_t tile_darts_bytes(uint32_t W, uint32_t H, uint32_t n_frames);
+// The darts of every frame and tile.  plan != nullptr: the launch of k_tile_scan also plans the batch on the device
+// (frame_base[0..n_frames], plan[0..3] against plan_cap) and zeroes [zero_p, zero_p + zero_bytes), the counter block, a multiple of
+// 16 bytes; frame_darts arrives zeroed.
+struct DartCountLaunch {
+    const uint64_t* bits = nullptr; int W = 0, H = 0; uint32_t first_frame = 0, n_frames = 0; unsigned long long* frame_darts = nullptr;
+    uint32_t* tile_darts = nullptr; uint64_t plan_cap = 0; uint32_t* frame_base = nullptr; uint32_t* plan = nullptr; void* zero_p = nullptr;
+    size_t zero_bytes = 0;
+};
+hipError_t launch_dart_count(hipStream_t st, const DartCountLaunch& d);
+hipError_t launch_zero(hipStream_t st, void* p, size_t bytes);   // bytes: a multiple of 16, p 16-byte aligned
+
+size_t entry_state_bytes();
+size_t fin_state_bytes();
+size_t entry_slots(uint32_t n_darts);
+size_t leader_list_bytes(uint32_t n_darts);
+
+// One chunk of a batch's contour graph, as launch_dart_build, launch_rank_cycles, launch_resolve, launch_select_scatter and
+// launch_contour_quads take it, in that order: the buffers and settings are the batch's, the first block below is the chunk's.
+struct ContourChunk {
+    // the chunk: frames [first_frame, first_frame + n_frames) of the batch, n_darts darts, frame_base[0..n_frames] into them
+    uint32_t first_frame = 0, n_frames = 0, n_darts = 0; const uint32_t* frame_base = nullptr; DeviceCounters* ctr = nullptr;
+    int max_rounds = 0;                  // doubling rounds of the global form (frame_entries == nullptr)
+    uint32_t* frame_entries = nullptr;   // per-frame entry counts, zeroed; nullptr: the global rounds
+    unsigned int* dead_count = nullptr;  // [16]; nullptr: no border is dropped early (debug taps, sparse graphs)
+    // the batch
+    int W = 0, H = 0;
+    uint32_t batch_frames = 0;           // the frames launch_dart_count laid the tile tables out for
+    const uint64_t* bits = nullptr; const uint32_t* tile_darts = nullptr;
+    const uint32_t* n_live = nullptr;    // the dart total on the device (a device-planned batch: n_darts is its capacity); nullable
+    uint32_t* pix_base = nullptr; uint64_t* d_rec = nullptr; uint32_t* d_succ = nullptr; uint32_t* entry_list = nullptr;
+    unsigned int* entry_count = nullptr, * leader_count = nullptr;   // [16] each, zeroed per chunk
+    void* es_a = nullptr, * es_b = nullptr;   // EntryState[entry_slots(n_darts)]
+    void* fin = nullptr;                      // FinState[n_darts]
+    uint32_t* leader_list = nullptr, * leader_keep = nullptr; uint64_t* t_cur = nullptr, * t_next = nullptr;
+    int resolve_iters = 0;               // fixpoint passes of launch_resolve; 0: none, k_cycle_select checks the natural starts inline
+    int inline_resolve_W = 0;            // ... against this row width (W); 0 with fixpoint passes
+    uint32_t min_edge_length = 0; double eps_factor = 0.0; ContourRec* contours = nullptr; uint32_t* cyc_start_off = nullptr;
+    uint32_t* points = nullptr; uint32_t max_contours = 0; uint64_t max_points = 0;
+    bool keep_all = false;               // debug taps: every border is kept
+    CandRec* cands = nullptr;            // batch_frames x max_cand, and cand_count[batch_frames]: the launcher moves to first_frame
+    uint32_t* cand_count = nullptr; uint32_t max_cand = 0; unsigned int* err_flags = nullptr;
+    // a3_debug_kernel_time only (0 in the product path).  phase: 0 everything, 1 k_local_contract only, 2 what follows it.  dbg:
+    // launch_dart_build 1..4 stop k_dart_assign early and leave d_succ alone, 5 = everything; launch_rank_cycles n > 0 runs n doubling
+    // rounds of k_local_contract instead of 11, -1 none, and nothing behind it
+    int phase = 0, dbg = 0;
+};
+hipError_t launch_dart_build(hipStream_t st, const ContourChunk& c);
+// leaders + ranks for every dart of the chunk
+hipError_t launch_rank_cycles(hipStream_t st, const ContourChunk& c);
+hipError_t launch_resolve(hipStream_t st, const ContourChunk& c);
+hipError_t launch_select_scatter(hipStream_t st, const ContourChunk& c);
+hipError_t launch_contour_quads(hipStream_t st, const ContourChunk& c);
+hipError_t launch_debug_clockwise(hipStream_t st, const int32_t* in, uint32_t n, int32_t* out);
+hipError_t launch_unpack_bits(hipStream_t st, const uint64_t* bits, int W, int H, uint8_t* out);
+
+// ---- k_decode.hip: candidates -> markers -> poses -------------------------------------------------------------------------------
+size_t decode_out_bytes();
+size_t proj_rec_bytes();
+size_t weight_table_bytes();
+uint32_t frame_cand_lds_slots();
+// The decode stage of n_frames frames with max_cand candidate slots each, as launch_frame_candidates, launch_decode and
+// launch_compact_markers take it, in that order; a caller of one of them fills what that one reads.
+struct DecodeStage {
+    uint32_t n_frames = 0, first_frame = 0, max_cand = 0;
+    // launch_frame_candidates.  Per frame: the quads in start-key order (pre_xy), discard_too_near's survivors (fin_xy, fin_count), their
+    // work items and, with S > 0, their projections (proj).  work_count arrives zeroed; big_scratch: n_frames x max_cand floats, needed
+    // when max_cand > frame_cand_lds_slots().
+    const CandRec* cands = nullptr; const uint32_t* cand_count = nullptr; float min_distance = 0.0f;
+    uint16_t* pre_xy = nullptr, * fin_xy = nullptr; uint32_t* fin_count = nullptr, * work = nullptr; unsigned int* work_count = nullptr;
+    uint32_t S = 0; void* proj = nullptr; float* big_scratch = nullptr;
+    // launch_decode: k_decode over the work list.  n: cells per side; patches (nullable, debug taps): patch_cap warped patches are kept;
+    // per_frame: nullable; few (at most 64 frames): all four waves of a workgroup run the stages behind the sampling.
+    PixelSrc src{}; int W = 0, H = 0; uint32_t n = 0, max_taps = 0; const uint64_t* dict = nullptr; uint32_t n_codes = 0, tau = 0; int filter = 0;
+    const float* wtab = nullptr; void* outs = nullptr; uint8_t* patches = nullptr; uint32_t patch_cap = 0; uint32_t* per_frame = nullptr;
+    int grid_blocks = 0; bool few = false;
+    // ... a3_debug_kernel_time only: k_projection runs first (the product's projections come from k_frame_candidates); k_decode stops
+    // early: 1 = no sampling, 2 / 3 / 4 = after sampling / Otsu / bits, 0 and 5 = the whole kernel
+    bool projection = false; int variant = 0;
+    // launch_compact_markers: the marker list (capacity marker_cap), its total and the sum of cand_count (cand_pre_total)
+    a3_marker* markers = nullptr; uint32_t marker_cap = 0; unsigned int* marker_total = nullptr, * err_flags = nullptr, * cand_pre_total = nullptr;
+};
+hipError_t launch_frame_candidates(hipStream_t st, const DecodeStage& d);
+hipError_t launch_decode(hipStream_t st, const DecodeStage& d);
+hipError_t launch_compact_markers(hipStream_t st, const DecodeStage& d);
+hipError_t launch_weight_table(hipStream_t st, uint32_t S, uint32_t n, uint32_t max_taps, float* wtab);
+hipError_t launch_pack_detections(hipStream_t st, const a3_marker* markers, const a3_pose* poses, const uint32_t* per_frame, uint32_t n_frames,
+                                  uint32_t first_frame_global, uint32_t maxm, void* dst, unsigned int* overflow);
+hipError_t launch_debug_rotate_bits(hipStream_t st, const uint8_t* in, uint32_t n, uint32_t r, uint8_t* out);
+hipError_t launch_gather_patches(hipStream_t st, const void* outs_frame, uint32_t n_cand, const uint8_t* patches, uint32_t patch_cap, uint32_t S2,
+                                 uint8_t* dst, unsigned int* missing);
+// IPPE, one lane per marker.  mode 0: pts = corners / (iw, ih); 1: unprojected through the intrinsics; 2: norm_pts are normalised
+// already; 3 / 4: as 0 / 1 from the float corners in norm_pts (8 per marker).  corner_stride: u32 words between the corner lists of
+// consecutive markers (8 for a packed list, 14 inside a3_marker[]); n_dev (nullable): the marker count on the device, n its capacity.
+struct PoseLaunch {
+    const uint32_t* corners = nullptr; uint32_t corner_stride = 0; const float* norm_pts = nullptr; uint32_t n = 0;
+    const unsigned int* n_dev = nullptr; int mode = 0; float marker_size_mm = 0.0f, iw = 0.0f, ih = 0.0f, fx = 0.0f, fy = 0.0f, cx = 0.0f, cy = 0.0f;
+    a3_pose* out = nullptr;
+};
+hipError_t launch_pose(hipStream_t st, const PoseLaunch& p);
+hipError_t launch_find_nearest(hipStream_t st, const uint64_t* dict, uint32_t n_codes, const uint64_t* bits, uint32_t n, uint32_t* idx, uint8_t* dist);
+hipError_t launch_calc_tau(hipStream_t st, const uint64_t* dict, uint32_t n_codes, unsigned int* tau);
+hipError_t launch_selftest(hipStream_t st, const double* a, const double* b, uint32_t n, double* sq, double* dv, float* sqf, float* dvf);
+
+// ---- markers as the board, ChArUco, refinement and undistortion kernels take them ---------------------------------------------------
+// Either a batch's marker list on the device -- markers (capacity n), their count n_dev, per_frame[n_frames], optionally their float
+// corners (8 per marker: undistorted or refined) -- or one frame (n_frames = 1) of n caller markers: ids and pts (8 floats each).
+// markers != nullptr selects the first form.
+struct MarkerSrc {
+    const a3_marker* markers = nullptr; const unsigned int* n_dev = nullptr; const uint32_t* per_frame = nullptr; const float* corners = nullptr;
+    const uint32_t* ids = nullptr; const float* pts = nullptr; uint32_t n = 0, n_frames = 0;
+};
+// the board's device tables (a3_set_board: id -> slot, n_codes entries; BoardSlot records) and the ChArUco table (a3_set_charuco: nc
+// chessboard corners cxy, their adjacent ids adj), nc = 0 without one
+struct BoardTables {
+    const uint16_t* slot_of = nullptr; uint32_t n_codes = 0; const void* slots = nullptr; const float* cxy = nullptr; const uint32_t* adj = nullptr;
+    uint32_t nc = 0;
+};
+
+// ---- k_refine.hip -------------------------------------------------------------------------------------------------------------------
+size_t refine_params_bytes();
+void refine_params(void* out, const a3_refine_config& cfg, uint32_t cells);
+// markers != nullptr: the corners of a batch's marker list (capacity n, count n_dev) -> 8 floats per marker; else n stand-alone corners
+// pts (2 floats each) with their cell sizes cell_px (nullable).  (One workgroup per marker up to 1024, then a workgroup-stride loop.)
+struct RefineLaunch {
+    PixelSrc src{}; uint32_t W = 0, H = 0; const a3_marker* markers = nullptr; const unsigned int* n_dev = nullptr;
+    const float* pts = nullptr, * cell_px = nullptr; uint32_t n = 0;
+    const void* params = nullptr;   // refine_params()
+    float* out = nullptr;
+};
+hipError_t launch_refine_corners(hipStream_t st, const RefineLaunch& r);
+
+// ---- k_undistort.hip ----------------------------------------------------------------------------------------------------------------
+// markers / pts: the corners' source (pts wins when both are given); n_dev: the device-side marker count of a batch (n = its marker
+// capacity), or nullptr for n stand-alone points.  out_xy: 2 floats per corner, out_res: 1.
+hipError_t launch_undistort_corners(hipStream_t st, const a3_marker* markers, const float* pts, const unsigned int* n_dev, uint32_t n,
+                                    const a3_intrinsics& in, const a3_distortion& d, float* out_xy, float* out_res);
+
+// ---- k_board.hip --------------------------------------------------------------------------------------------------------------------
+size_t board_slot_bytes();
+void board_slot_from(const float xy[8], void* out);   // one slot record from a checked marker's corners
+// one a3_board_pose per frame of m.  intr == nullptr: normalised by the image size (W, H).
+struct BoardPoseLaunch {
+    MarkerSrc m; BoardTables board; const a3_intrinsics* intr = nullptr; uint32_t W = 0, H = 0; a3_board_pose* out = nullptr;
+};
+hipError_t launch_board_pose(hipStream_t st, const BoardPoseLaunch& b);
+
+// ---- k_charuco.hip ------------------------------------------------------------------------------------------------------------------
+// The corner stage of m's frames (m.corners: the batch's refined corners or nullptr).  slots_tmp: n_frames x nc records; counts:
+// n_frames + 1; out: n_frames x nc records; und (nullable, with intr and dist): 2 floats per record.
+struct CharucoCornersLaunch {
+    PixelSrc src{}; uint32_t W = 0, H = 0; MarkerSrc m; BoardTables board; uint32_t min_markers = 0, refine = 0;
+    const void* params = nullptr;   // refine_params()
+    const a3_intrinsics* intr = nullptr; const a3_distortion* dist = nullptr; a3_charuco_corner* slots_tmp = nullptr; uint32_t* counts = nullptr;
+    a3_charuco_corner* out = nullptr; float* und = nullptr;
+};
+hipError_t launch_charuco_corners(hipStream_t st, const CharucoCornersLaunch& c);
+// one a3_charuco_pose per frame of a batch from the records launch_charuco_corners wrote (the same counts / recs / und); m.corners: the
+// markers' float corners (undistorted, else refined, else nullptr) as k_board_pose reads them
+struct CharucoPoseLaunch {
+    MarkerSrc m; BoardTables board; const uint32_t* counts = nullptr; const a3_charuco_corner* recs = nullptr; const float* und = nullptr;
+    const a3_intrinsics* intr = nullptr; uint32_t W = 0, H = 0; a3_charuco_pose* out = nullptr;
+};
+hipError_t launch_charuco_pose(hipStream_t st, const CharucoPoseLaunch& c);
+
+// ---- the solvers (k_calib, k_calib_fisheye, k_rig, k_handeye, k_map): one workgroup per problem; the scratch segments hold *_bytes()
+// per record; every pointer is device memory the caller has checked and staged (a3_solve_check.h) ------------------------------------
+size_t calib_view_bytes();
+size_t fisheye_calib_view_bytes();
+// start_obj, start_img: the fisheye model only (2 floats per point each)
+struct CalibLaunch {
+    const a3_calib_camera* cams = nullptr; uint32_t n_cams = 0; const uint32_t* view_off = nullptr; const float* obj = nullptr, * img = nullptr;
+    double* scratch = nullptr; float* start_obj = nullptr, * start_img = nullptr; a3_calib_result* res = nullptr; a3_calib_view* views = nullptr;
+};
+hipError_t launch_calibrate(hipStream_t st, const CalibLaunch& c);
+hipError_t launch_calibrate_fisheye(hipStream_t st, const CalibLaunch& c);
+size_t rig_obs_bytes();
+size_t rig_frame_bytes();
+size_t rig_table_bytes();
+struct RigLaunch {
+    const a3_rig* rigs = nullptr; uint32_t n_rigs = 0; const a3_rig_camera* cams = nullptr; const a3_rig_observation* obs = nullptr;
+    const float* obj = nullptr, * img = nullptr; uint32_t* tab = nullptr; double* oscr = nullptr, * fscr = nullptr; a3_rig_result* res = nullptr;
+    a3_rig_camera_result* cres = nullptr; a3_rig_frame* frames = nullptr; a3_rig_observation_result* ores = nullptr;
+};
+hipError_t launch_rig(hipStream_t st, const RigLaunch& r);
+size_t handeye_frame_bytes();
+hipError_t launch_handeye(hipStream_t st, const a3_handeye_problem* probs, uint32_t n_probs, const a3_handeye_frame* frames, const float* obj,
+                          const float* img, double* fscr, a3_handeye_result* res, a3_handeye_frame_result* fres);
+size_t map_obs_bytes();
+size_t map_frame_bytes();
+size_t map_marker_bytes();
+struct MapLaunch {
+    const a3_map* maps = nullptr; uint32_t n_maps = 0; const a3_map_marker* markers = nullptr; const a3_map_observation* obs = nullptr;
+    const float* img = nullptr; const uint64_t* big_off = nullptr; uint32_t* fo = nullptr, * ml = nullptr;
+    double* oscr = nullptr, * fscr = nullptr, * mscr = nullptr, * big = nullptr; a3_map_result* res = nullptr; a3_map_marker_result* mres = nullptr;
+    a3_map_frame* frames = nullptr; a3_map_observation_result* ores = nullptr;
+};
+hipError_t launch_map(hipStream_t st, const MapLaunch& m);
+
+// ---- k_rectify.hip, k_synth.hip ---------------------------------------------------------------------------------------------------------
+void rectify_grid(uint32_t dw, uint32_t dh, uint32_t n_frames, uint32_t* tiles_x, uint32_t* tiles_y, uint32_t* chunks);
+// src / dst: device memory; bpp 1, 3 or 4.  The caller has checked every size and stride (a3_rectify_frames).
+struct RectifyLaunch {
+    const uint8_t* src = nullptr; size_t src_row = 0, src_frame = 0; uint32_t n_frames = 0; int bpp = 0; const a3_rectify* r = nullptr;
+    uint8_t* dst = nullptr; size_t dst_row = 0, dst_frame = 0;
+};
+hipError_t launch_rectify(hipStream_t st, const RectifyLaunch& r);
+struct SynthLaunch {
+    const a3_synth_frame* frames = nullptr; uint32_t n_frames = 0; const a3_synth_marker* markers = nullptr; uint32_t W = 0, H = 0; int paper = 0;
+    float black = 0.0f, white = 0.0f; int supersample = 0; uint8_t* out = nullptr; size_t row_stride = 0, frame_stride = 0;
+};
+hipError_t launch_synth_render(hipStream_t st, const SynthLaunch& s);
+// `workgroups` x `threads` that stay resident for `usec` microseconds (a3_debug_spin)
+hipError_t launch_spin(hipStream_t st, int workgroups, int threads, int usec, uint32_t* sink);
+
+}  // namespace a3

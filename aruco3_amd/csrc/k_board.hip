@@ -13,6 +13,7 @@
 
 #include "a3_board.h"
 #include "a3_common.h"
+#include "a3_launch.h"
 
 namespace a3 {
 
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(128) void k_board_pose(BoardArgs a) {
 
 size_t board_slot_bytes() { return sizeof(BoardSlot); }
 
-// one slot record from a checked marker's corners (the contract's float arithmetic; tests/board_oracle.c a3o_board_slot)
+// (the contract's float arithmetic; tests/board_oracle.c a3o_board_slot)
 void board_slot_from(const float xy[8], void* out) {
     BoardSlot s{};
     for (int k = 0; k < 4; k++) { s.x[k] = xy[2 * k]; s.y[k] = xy[2 * k + 1]; }
@@ -168,18 +169,11 @@ void board_slot_from(const float xy[8], void* out) {
     *reinterpret_cast<BoardSlot*>(out) = s;
 }
 
-// markers != nullptr: a batch of n_frames frames (marker capacity n, counts on the device); else one frame of n caller markers
-hipError_t launch_board_pose(hipStream_t st, const a3_marker* markers, const uint32_t* ids, const float* pts, const float* refined,
-                             const unsigned int* n_dev, const uint32_t* per_frame, uint32_t n, uint32_t n_frames, const uint16_t* slot_of,
-                             uint32_t n_codes, const void* slots, const a3_intrinsics* intr, uint32_t W, uint32_t H, a3_board_pose* out) {
-    if (n_frames == 0) return hipSuccess;
-    BoardArgs a{};
-    a.markers = markers; a.ids = ids; a.pts = pts; a.refined = refined; a.n_dev = n_dev; a.per_frame = per_frame;
-    a.n = n; a.n_frames = n_frames; a.slot_of = slot_of; a.n_codes = n_codes; a.slots = reinterpret_cast<const BoardSlot*>(slots);
-    a.has_intr = intr ? 1 : 0; a.iw = (float)W; a.ih = (float)H;
-    if (intr) { a.fx = intr->focal_x; a.fy = intr->focal_y; a.cx = intr->principal_x; a.cy = intr->principal_y; }
-    a.out = out;
-    hipLaunchKernelGGL(k_board_pose, dim3(n_frames), dim3(128), 0, st, a);
+hipError_t launch_board_pose(hipStream_t st, const BoardPoseLaunch& b) {
+    if (b.m.n_frames == 0) return hipSuccess;
+    BoardArgs a = board_args(b.m, b.board, b.intr, b.W, b.H);
+    a.out = b.out;
+    hipLaunchKernelGGL(k_board_pose, dim3(b.m.n_frames), dim3(128), 0, st, a);
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_calib.h"
 
 namespace a3 {
@@ -434,11 +435,10 @@ __global__ __launch_bounds__(kCalThreads) void k_calibrate(CalibArgs g) {
 
 size_t calib_view_bytes() { return kCalViewDoubles * sizeof(double); }
 
-hipError_t launch_calibrate(hipStream_t st, const a3_calib_camera* cams, uint32_t n_cams, const uint32_t* view_off, const float* obj,
-                            const float* img, double* scratch, a3_calib_result* res, a3_calib_view* views) {
-    if (n_cams == 0) return hipSuccess;
-    const CalibArgs g{cams, view_off, obj, img, scratch, res, views};
-    hipLaunchKernelGGL(k_calibrate, dim3(n_cams), dim3(kCalThreads), 0, st, g);
+hipError_t launch_calibrate(hipStream_t st, const CalibLaunch& c) {
+    if (c.n_cams == 0) return hipSuccess;
+    const CalibArgs g{c.cams, c.view_off, c.obj, c.img, c.scratch, c.res, c.views};
+    hipLaunchKernelGGL(k_calibrate, dim3(c.n_cams), dim3(kCalThreads), 0, st, g);
     return hipGetLastError();
 }
 

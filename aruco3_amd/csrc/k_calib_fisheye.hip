@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_fisheye_calib.h"
 
 namespace a3 {
@@ -446,12 +447,10 @@ __global__ __launch_bounds__(kFeThreads) void k_calibrate_fisheye(FisheyeCalibAr
 
 size_t fisheye_calib_view_bytes() { return kFeViewDoubles * sizeof(double); }
 
-hipError_t launch_calibrate_fisheye(hipStream_t st, const a3_calib_camera* cams, uint32_t n_cams, const uint32_t* view_off, const float* obj,
-                                    const float* img, double* scratch, float* start_obj, float* start_img, a3_calib_result* res,
-                                    a3_calib_view* views) {
-    if (n_cams == 0) return hipSuccess;
-    const FisheyeCalibArgs g{cams, view_off, obj, img, scratch, start_obj, start_img, res, views};
-    hipLaunchKernelGGL(k_calibrate_fisheye, dim3(n_cams), dim3(kFeThreads), 0, st, g);
+hipError_t launch_calibrate_fisheye(hipStream_t st, const CalibLaunch& c) {
+    if (c.n_cams == 0) return hipSuccess;
+    const FisheyeCalibArgs g{c.cams, c.view_off, c.obj, c.img, c.scratch, c.start_obj, c.start_img, c.res, c.views};
+    hipLaunchKernelGGL(k_calibrate_fisheye, dim3(c.n_cams), dim3(kFeThreads), 0, st, g);
     return hipGetLastError();
 }
 

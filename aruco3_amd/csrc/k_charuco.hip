@@ -19,6 +19,7 @@
 
 #include "a3_board.h"
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_subpix.h"
 #include "a3_undistort.h"
 
@@ -353,54 +354,31 @@ __global__ __launch_bounds__(128) void k_charuco_pose(BoardArgs a, CharucoArgs c
     }
 }
 
-namespace {
-BoardArgs charuco_board_args(const a3_marker* markers, const uint32_t* ids, const float* pts, const float* corners, const unsigned int* n_dev,
-                             const uint32_t* per_frame, uint32_t n, uint32_t n_frames, const uint16_t* slot_of, uint32_t n_codes, const void* slots) {
-    BoardArgs a{};
-    a.markers = markers; a.ids = ids; a.pts = pts; a.refined = corners; a.n_dev = n_dev; a.per_frame = per_frame;
-    a.n = n; a.n_frames = n_frames; a.slot_of = slot_of; a.n_codes = n_codes; a.slots = reinterpret_cast<const BoardSlot*>(slots);
-    return a;
-}
-}  // namespace
-
-// The corner stage of n_frames frames.  markers != nullptr: a batch's marker list (capacity n, counts on the device; `refined`: its
-// refined corners or nullptr); else one frame of n caller markers (ids, pts).  slots_tmp: n_frames x nc records; counts: n_frames + 1;
-// out: n_frames x nc records; und (nullable, with up): 2 floats per record.
-hipError_t launch_charuco_corners(hipStream_t st, PixelSrc src, uint32_t W, uint32_t H, const a3_marker* markers, const uint32_t* ids,
-                                  const float* pts, const float* refined, const unsigned int* n_dev, const uint32_t* per_frame, uint32_t n,
-                                  uint32_t n_frames, const uint16_t* slot_of, uint32_t n_codes, const void* slots, const float* cxy,
-                                  const uint32_t* adj, uint32_t nc, uint32_t min_markers, uint32_t refine, const void* params,
-                                  const a3_intrinsics* intr, const a3_distortion* dist, a3_charuco_corner* slots_tmp, uint32_t* counts,
-                                  a3_charuco_corner* out, float* und) {
+hipError_t launch_charuco_corners(hipStream_t st, const CharucoCornersLaunch& l) {
+    const uint32_t n_frames = l.m.n_frames, nc = l.board.nc;
+    const a3_intrinsics* const intr = l.intr; const a3_distortion* const dist = l.dist;
     if (n_frames == 0 || nc == 0) return hipSuccess;
-    const BoardArgs a = charuco_board_args(markers, ids, pts, refined, n_dev, per_frame, n, n_frames, slot_of, n_codes, slots);
+    const BoardArgs a = board_args(l.m, l.board, nullptr, 0, 0);
     CharucoArgs c{};
-    c.cxy = cxy; c.adj = adj; c.nc = nc; c.W = W; c.H = H; c.min_markers = min_markers; c.refine = refine; c.src = src;
-    c.slots = slots_tmp; c.counts = counts; c.out = out;
-    if (und && intr && dist) {
-        c.und = und;
+    c.cxy = l.board.cxy; c.adj = l.board.adj; c.nc = nc; c.W = l.W; c.H = l.H; c.min_markers = l.min_markers; c.refine = l.refine; c.src = l.src;
+    c.slots = l.slots_tmp; c.counts = l.counts; c.out = l.out;
+    if (l.und && intr && dist) {
+        c.und = l.und;
         c.up = UndistortParams{intr->focal_x, intr->focal_y, intr->principal_x, intr->principal_y, dist->k1, dist->k2, dist->p1, dist->p2,
                                dist->k3, dist->k4, dist->k5, dist->k6, dist->max_residual_px, dist->iterations, dist->model};
     }
-    const RefineParams& p = *reinterpret_cast<const RefineParams*>(params);
+    const RefineParams& p = *reinterpret_cast<const RefineParams*>(l.params);
     hipLaunchKernelGGL(k_charuco_interp, dim3(n_frames), dim3(256), 0, st, a, c, p);
     hipLaunchKernelGGL(k_charuco_refine, dim3((nc + 3) / 4, n_frames), dim3(256), 0, st, c, p, n_frames);
     return hipGetLastError();
 }
 
-// one a3_charuco_pose per frame of a batch from the records launch_charuco_corners wrote (same counts / out / und); the markers' float
-// corners (`corners`: undistorted, else refined, else nullptr) as k_board_pose reads them
-hipError_t launch_charuco_pose(hipStream_t st, const a3_marker* markers, const float* corners, const unsigned int* n_dev, const uint32_t* per_frame,
-                               uint32_t n, uint32_t n_frames, const uint16_t* slot_of, uint32_t n_codes, const void* slots, const float* cxy,
-                               uint32_t nc, const uint32_t* counts, const a3_charuco_corner* recs, const float* und, const a3_intrinsics* intr,
-                               uint32_t W, uint32_t H, a3_charuco_pose* out) {
-    if (n_frames == 0) return hipSuccess;
-    BoardArgs a = charuco_board_args(markers, nullptr, nullptr, corners, n_dev, per_frame, n, n_frames, slot_of, n_codes, slots);
-    a.has_intr = intr ? 1 : 0; a.iw = (float)W; a.ih = (float)H;
-    if (intr) { a.fx = intr->focal_x; a.fy = intr->focal_y; a.cx = intr->principal_x; a.cy = intr->principal_y; }
+hipError_t launch_charuco_pose(hipStream_t st, const CharucoPoseLaunch& l) {
+    if (l.m.n_frames == 0) return hipSuccess;
+    const BoardArgs a = board_args(l.m, l.board, l.intr, l.W, l.H);
     CharucoArgs c{};
-    c.cxy = cxy; c.nc = nc; c.counts = const_cast<uint32_t*>(counts); c.out = const_cast<a3_charuco_corner*>(recs); c.und = const_cast<float*>(und);
-    hipLaunchKernelGGL(k_charuco_pose, dim3(n_frames), dim3(128), 0, st, a, c, out);
+    c.cxy = l.board.cxy; c.nc = l.board.nc; c.counts = const_cast<uint32_t*>(l.counts); c.out = const_cast<a3_charuco_corner*>(l.recs); c.und = const_cast<float*>(l.und);
+    hipLaunchKernelGGL(k_charuco_pose, dim3(l.m.n_frames), dim3(128), 0, st, a, c, l.out);
     return hipGetLastError();
 }
 

@@ -36,8 +36,10 @@
 // atomic on one address costs ~11 ns and they serialise (12 k tiles = 140 us).  Counters that
 // remain are sharded 16 ways (entry and leader lists) or bumped once per workgroup.
 #include <algorithm>
+#include <cmath>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 
 // Darts per lane and trip in the per-dart sweeps (swept on BASELINE config 2).  k_jump_finalize: 2 / 4 / 6 / 8 darts
 // -> 53 / 48 / 44.5 / 45 us with its three dependent loads of rounds 2-5; with two (round 6: the entry's slot comes with the state)
@@ -1917,24 +1919,20 @@ static inline int blocks_for(uint64_t n, int per_block, int cap) {
 __global__ __launch_bounds__(256) void k_zero(uint4* __restrict__ p, uint32_t n16) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += gridDim.x * blockDim.x) p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
-hipError_t launch_zero(hipStream_t st, void* p, size_t bytes /* multiple of 16, p 16-byte aligned */) {
+hipError_t launch_zero(hipStream_t st, void* p, size_t bytes) {
     const uint32_t n16 = (uint32_t)(bytes / 16);
     hipLaunchKernelGGL(k_zero, dim3(blocks_for(n16, 256, 256)), dim3(256), 0, st, reinterpret_cast<uint4*>(p), n16);
     return hipGetLastError();
 }
 
-// tile_darts[frames * tiles] followed by tile_off[frames * tiles]
-// tile_darts[frames * tiles] | tile_off[frames * tiles] | second-half counts of k_dart_count[frames * tiles]
-size_t tile_mask_offset_bytes(uint32_t W, uint32_t H, uint32_t n_frames);
+// the tile tables (a3_launch.h): where tile_off (in u32 words) and the word masks (in bytes; kCountHalves 64-bit words per tile) begin
+static size_t tile_off_offset(uint32_t W, uint32_t H, uint32_t n_frames) { return (size_t)dart_tiles(W, H) * n_frames; }
+static size_t tile_mask_offset_bytes(uint32_t W, uint32_t H, uint32_t n_frames) { return ((size_t)dart_tiles(W, H) * n_frames * 4 * (1 + kCountHalves) + 7) & ~(size_t)7; }
 size_t tile_darts_bytes(uint32_t W, uint32_t H, uint32_t n_frames) { return tile_mask_offset_bytes(W, H, n_frames) + (size_t)dart_tiles(W, H) * n_frames * kCountHalves * 8; }
-size_t tile_off_offset(uint32_t W, uint32_t H, uint32_t n_frames) { return (size_t)dart_tiles(W, H) * n_frames; }
-// ... followed (8-byte aligned) by the word masks, kCountHalves 64-bit words per tile
-size_t tile_mask_offset_bytes(uint32_t W, uint32_t H, uint32_t n_frames) { return ((size_t)dart_tiles(W, H) * n_frames * 4 * (1 + kCountHalves) + 7) & ~(size_t)7; }
 
-// plan != nullptr: the launch of k_tile_scan also plans the batch on the device (frame_base[0..n_frames], plan[0..3])
-hipError_t launch_dart_count(hipStream_t st, const uint64_t* bits, int W, int H, uint32_t first_frame, uint32_t n_frames,
-                             unsigned long long* frame_darts, uint32_t* tile_darts, uint64_t plan_cap, uint32_t* frame_base, uint32_t* plan,
-                             void* zero_p, size_t zero_bytes /* with plan: the counter block to zero, a multiple of 16 bytes */) {
+hipError_t launch_dart_count(hipStream_t st, const DartCountLaunch& d) {
+    const uint64_t* const bits = d.bits; const int W = d.W, H = d.H; const uint32_t first_frame = d.first_frame, n_frames = d.n_frames;
+    unsigned long long* const frame_darts = d.frame_darts; uint32_t* const tile_darts = d.tile_darts, * const plan = d.plan;
     const uint32_t tiles_x = dart_tiles_x((uint32_t)W), tiles_y = ((uint32_t)H + kTileRows - 1) / kTileRows;
     const uint32_t wpr = words_per_row((uint32_t)W);
     uint32_t* h1 = tile_darts + (size_t)tiles_x * tiles_y * n_frames * 2;
@@ -1945,43 +1943,41 @@ hipError_t launch_dart_count(hipStream_t st, const uint64_t* bits, int W, int H,
         hipLaunchKernelGGL(k_dart_count<64>, dim3(((wpr + kCountLanes - 1) / kCountLanes) * tiles_y, n_frames, kCountHalves), dim3(64), 0, st, bits, W, H, first_frame,
                            frame_darts, tile_darts, h1, tmask);
     hipLaunchKernelGGL(k_tile_scan, dim3(n_frames + (plan ? 1u : 0u)), dim3(256), 0, st, tile_darts, h1, tiles_x * tiles_y, first_frame,
-                       tile_darts + (size_t)tiles_x * tiles_y * n_frames, n_frames, frame_darts, (unsigned long long)plan_cap, frame_base, plan,
-                       reinterpret_cast<uint4*>(zero_p), (uint32_t)(zero_bytes / 16));
+                       tile_darts + (size_t)tiles_x * tiles_y * n_frames, n_frames, frame_darts, (unsigned long long)d.plan_cap, d.frame_base, plan,
+                       reinterpret_cast<uint4*>(d.zero_p), (uint32_t)(d.zero_bytes / 16));
     return hipGetLastError();
 }
 
-hipError_t launch_dart_build(hipStream_t st, const uint64_t* bits, int W, int H, uint32_t first_frame, uint32_t n_frames,
-                             const uint32_t* frame_base, const uint32_t* tile_off, uint32_t* pix_base, const uint32_t* tile_darts, uint64_t* d_rec,
-                             uint32_t* d_succ, uint32_t n_darts, const uint32_t* n_live, int dbg, const unsigned long long* tile_mask) {
-    const uint32_t tiles = dart_tiles((uint32_t)W, (uint32_t)H);
-    hipLaunchKernelGGL(k_dart_assign, dim3((tiles * n_frames + 7u) / 8u * 8u), dim3(256), 0, st, bits, W, H, first_frame, frame_base, tile_off,
-                       pix_base, tile_darts, d_rec, d_succ, n_live, dbg, tile_mask, tiles, n_frames);
-    if (dbg && dbg != 5) return hipGetLastError();   // 5 = everything (the probe's reference point), others leave d_succ alone
-    hipLaunchKernelGGL(k_dart_link, dim3(blocks_for(n_darts, 256, 4096)), dim3(256), 0, st, W, H, first_frame, pix_base, bits, d_rec, d_succ, n_darts, n_live);
+hipError_t launch_dart_build(hipStream_t st, const ContourChunk& c) {
+    const uint32_t tiles = dart_tiles((uint32_t)c.W, (uint32_t)c.H);
+    const uint32_t* const tile_off = c.tile_darts + tile_off_offset((uint32_t)c.W, (uint32_t)c.H, c.batch_frames);
+    const unsigned long long* const tile_mask = reinterpret_cast<const unsigned long long*>(
+        reinterpret_cast<const uint8_t*>(c.tile_darts) + tile_mask_offset_bytes((uint32_t)c.W, (uint32_t)c.H, c.batch_frames));
+    hipLaunchKernelGGL(k_dart_assign, dim3((tiles * c.n_frames + 7u) / 8u * 8u), dim3(256), 0, st, c.bits, c.W, c.H, c.first_frame, c.frame_base, tile_off,
+                       c.pix_base, c.tile_darts, c.d_rec, c.d_succ, c.n_live, c.dbg, tile_mask, tiles, c.n_frames);
+    if (c.dbg && c.dbg != 5) return hipGetLastError();   // 5 = everything (the probe's reference point), others leave d_succ alone
+    hipLaunchKernelGGL(k_dart_link, dim3(blocks_for(c.n_darts, 256, 4096)), dim3(256), 0, st, c.W, c.H, c.first_frame, c.pix_base, c.bits, c.d_rec, c.d_succ,
+                       c.n_darts, c.n_live);
     return hipGetLastError();
 }
 
 size_t entry_state_bytes() { return sizeof(EntryState); }
 // launch_rank_cycles leaves pending states for the readers to resolve (no k_jump_finalize) on the clean-frame path when the natural starts
 // are checked inline (no fixpoint passes)
-bool finalize_inline(bool frame_entries, bool trust_natural) { return frame_entries && trust_natural; }
+static bool finalize_inline(bool frame_entries, bool trust_natural) { return frame_entries && trust_natural; }
 size_t fin_state_bytes() { return sizeof(FinState); }
 size_t entry_slots(uint32_t n_darts) { return (size_t)entry_shard_cap(n_darts) * kEntryShards; }
 size_t leader_list_bytes(uint32_t n_darts) { return (size_t)leader_shard_cap(n_darts) * kLeaderShards * 4; }
 
-// leaders + ranks for every dart of the chunk.  fin: FinState[n_darts]; es_a/es_b: EntryState[entry_slots(n_darts)];
-// entry_count[16] and leader_count[16] arrive zeroed.
-hipError_t launch_rank_cycles(hipStream_t st, uint32_t n_darts, int W, const uint64_t* d_rec, const uint32_t* d_succ,
-                              uint32_t* entry_list,
-                              unsigned int* entry_count, void* es_a, void* es_b, void* fin8 /* FinState[n_darts] */, uint32_t* leader_list,
-                              unsigned int* leader_count, int max_rounds, DeviceCounters* ctr, const uint32_t* n_live, int dbg,
-                              const uint32_t* frame_base, uint32_t* frame_entries /*nullptr: global rounds*/, uint32_t n_frames,
-                              int phase /* 0: everything, 1: k_local_contract only, 2: what follows it */,
-                              uint32_t min_edge_length, unsigned int* dead_count /* [16], nullptr: no border is dropped early (debug taps) */,
-                              int trust_natural /* no fixpoint passes follow: k_cycle_select checks the natural starts inline */) {
-    // entry_count[16] and leader_count[16] arrive zeroed (the caller's per-batch / per-chunk memset)
+hipError_t launch_rank_cycles(hipStream_t st, const ContourChunk& c) {
+    const uint32_t n_darts = c.n_darts, n_frames = c.n_frames, min_edge_length = c.min_edge_length; const int W = c.W, dbg = c.dbg, phase = c.phase;
+    const uint64_t* const d_rec = c.d_rec; const uint32_t* const d_succ = c.d_succ, * const n_live = c.n_live, * const frame_base = c.frame_base;
+    uint32_t* const entry_list = c.entry_list, * const leader_list = c.leader_list, * const frame_entries = c.frame_entries;
+    unsigned int* const entry_count = c.entry_count, * const leader_count = c.leader_count, * const dead_count = c.dead_count;
+    DeviceCounters* const ctr = c.ctr;
+    const int trust_natural = c.inline_resolve_W > 0 ? 1 : 0;   // no fixpoint passes follow: k_cycle_select checks the natural starts inline
     const uint32_t ecap = entry_shard_cap(n_darts);
-    FinState* fin = reinterpret_cast<FinState*>(fin8);
+    FinState* fin = reinterpret_cast<FinState*>(c.fin);
     // Clean frames with the natural starts checked inline: no k_jump_finalize.  k_local_contract and k_entry_frame list the leaders, the
     // readers resolve pending states themselves (fin_final); launch_select_scatter is handed the entry table (finalize_inline()).
     const bool no_finalize = finalize_inline(frame_entries != nullptr, trust_natural != 0) && dbg == 0;
@@ -2002,8 +1998,8 @@ hipError_t launch_rank_cycles(hipStream_t st, uint32_t n_darts, int W, const uin
                                ll, leader_count, lcap);
     }
     if (dbg || phase == 1) return hipGetLastError();
-    EntryState* a = reinterpret_cast<EntryState*>(es_a);
-    EntryState* b = reinterpret_cast<EntryState*>(es_b);
+    EntryState* a = reinterpret_cast<EntryState*>(c.es_a);
+    EntryState* b = reinterpret_cast<EntryState*>(c.es_b);
     if (frame_entries) {   // clean frames: every frame's entry list fits LDS, one launch instead of ~9
         hipLaunchKernelGGL(k_entry_frame, dim3(n_frames), dim3(256), 0, st, entry_list, frame_entries, frame_base, fin, d_rec, W, a, ctr,
                            ll, leader_count, lcap);
@@ -2015,7 +2011,7 @@ hipError_t launch_rank_cycles(hipStream_t st, uint32_t n_darts, int W, const uin
     }
     const dim3 grid(blocks_for(n_darts / 16 + 1, 256, 1024)), block(256);   // entries are a few % of the darts on clean frames
     hipLaunchKernelGGL(k_entry_init, grid, block, 0, st, entry_list, entry_count, fin, d_rec, W, a, ecap);
-    for (int r = 0; r < max_rounds; r++) {
+    for (int r = 0; r < c.max_rounds; r++) {
         hipLaunchKernelGGL(k_entry_jump, grid, block, 0, st, a, b, entry_count, ecap, r, ctr);
         EntryState* t = a; a = b; b = t;
     }
@@ -2025,10 +2021,12 @@ hipError_t launch_rank_cycles(hipStream_t st, uint32_t n_darts, int W, const uin
     return hipGetLastError();
 }
 
-hipError_t launch_resolve(hipStream_t st, const void* fin8, uint32_t n_darts, int W, const uint64_t* d_rec, const uint32_t* leader_list,
-                          const unsigned int* leader_count, uint64_t* t_cur, uint64_t* t_next, DeviceCounters* ctr, int max_iters,
-                          const uint32_t* n_live) {
-    const FinState* fin = reinterpret_cast<const FinState*>(fin8);
+hipError_t launch_resolve(hipStream_t st, const ContourChunk& c) {
+    const uint32_t n_darts = c.n_darts; const int W = c.W, max_iters = c.resolve_iters;
+    const uint64_t* const d_rec = c.d_rec; uint64_t* const t_cur = c.t_cur, * const t_next = c.t_next;
+    const uint32_t* const leader_list = c.leader_list, * const n_live = c.n_live; const unsigned int* const leader_count = c.leader_count;
+    DeviceCounters* const ctr = c.ctr;
+    const FinState* fin = reinterpret_cast<const FinState*>(c.fin);
     if (max_iters <= 0) return hipSuccess;   // k_cycle_select checks the natural starts itself; the caller re-runs the batch if they do not hold
     const dim3 grid(blocks_for(n_darts, 256, 4096)), block(256);
     hipLaunchKernelGGL(k_resolve_fast, dim3(blocks_for(n_darts / 16 + 1, 256, 1024)), block, 0, st, fin, leader_list, leader_count,
@@ -2041,34 +2039,32 @@ hipError_t launch_resolve(hipStream_t st, const void* fin8, uint32_t n_darts, in
     return hipGetLastError();
 }
 
-hipError_t launch_select_scatter(hipStream_t st, const void* fin8, uint32_t n_darts, const uint32_t* leader_list,
-                                 const unsigned int* leader_count, const uint32_t* d_succ, const uint64_t* t_cur,
-                                 const uint32_t* frame_base, uint32_t n_frames, uint32_t first_frame, uint32_t min_edge_length,
-                                 double eps_factor, double image_diag, ContourRec* contours, uint32_t* cyc_start_off,
-                                 uint32_t max_contours, uint64_t max_points, DeviceCounters* ctr, const uint64_t* d_rec, uint32_t* points,
-                                 const uint32_t* n_live, int inline_resolve_W, uint32_t* keep_tmp, int keep_all,
-                                 const void* es8 /* the entry table when finalize_inline(): pending states are resolved by the readers */) {
-    const EntryState* es = reinterpret_cast<const EntryState*>(es8);
+hipError_t launch_select_scatter(hipStream_t st, const ContourChunk& c) {
+    const uint32_t n_darts = c.n_darts;
+    const double image_diag = std::sqrt((double)c.W * c.W + (double)c.H * c.H);
+    // the entry table when finalize_inline(): pending states are resolved by the readers
+    const EntryState* es = finalize_inline(c.frame_entries != nullptr, c.inline_resolve_W > 0) ? reinterpret_cast<const EntryState*>(c.es_a) : nullptr;
     // 8192 workgroups for the graphs of clean frames (6-8 M darts), more for the tens of millions of darts of noise-like ones
     const dim3 grid(blocks_for(n_darts, 256, (int)std::min<uint32_t>(65536u, std::max<uint32_t>(8192u, n_darts / 1024u)))), block(256);
-    hipLaunchKernelGGL(k_cycle_select, dim3(blocks_for(n_darts / 64 + 1, 256, 1024)), block, 0, st, reinterpret_cast<FinState*>(const_cast<void*>(fin8)), leader_list, leader_count, d_succ, t_cur,
-                       frame_base, n_frames, first_frame, min_edge_length,
-                       eps_factor, image_diag, contours, cyc_start_off, max_contours, max_points, ctr, leader_shard_cap(n_darts), d_rec,
-                       inline_resolve_W, keep_tmp, keep_all, es);
-    hipLaunchKernelGGL(k_scatter_points, grid, block, 0, st, reinterpret_cast<const FinState*>(fin8), n_darts, d_rec, contours, cyc_start_off, points, n_live, ctr,
-                       max_contours, max_points, es);
+    hipLaunchKernelGGL(k_cycle_select, dim3(blocks_for(n_darts / 64 + 1, 256, 1024)), block, 0, st, reinterpret_cast<FinState*>(c.fin), c.leader_list, c.leader_count,
+                       c.d_succ, c.t_cur, c.frame_base, c.n_frames, c.first_frame, c.min_edge_length,
+                       c.eps_factor, image_diag, c.contours, c.cyc_start_off, c.max_contours, c.max_points, c.ctr, leader_shard_cap(n_darts), c.d_rec,
+                       c.inline_resolve_W, c.leader_keep, c.keep_all ? 1 : 0, es);
+    hipLaunchKernelGGL(k_scatter_points, grid, block, 0, st, reinterpret_cast<const FinState*>(c.fin), n_darts, c.d_rec, c.contours, c.cyc_start_off, c.points, c.n_live,
+                       c.ctr, c.max_contours, c.max_points, es);
     return hipGetLastError();
 }
 
-hipError_t launch_contour_quads(hipStream_t st, const ContourRec* contours, const DeviceCounters* ctr, uint32_t max_contours,
-                                const uint32_t* points, double eps_factor, uint32_t min_edge_length, uint32_t first_frame, uint32_t max_cand,
-                                CandRec* cands, uint32_t* cand_count, unsigned int* err_flags, int coords14, uint32_t n_darts) {
+hipError_t launch_contour_quads(hipStream_t st, const ContourChunk& c) {
+    const uint32_t n_darts = c.n_darts;
+    const int coords14 = c.W <= 16384 && c.H <= 16384 ? 1 : 0;
     // 2560 + 4096 workgroups for the millions of darts of a batch (or of one noise frame); a graph of a few ten thousand darts -- one
     // clean frame per call -- gets a grid in proportion: dispatching 6656 workgroups that find nothing to do took 8 of that call's 13 us
     const uint32_t b64 = std::min<uint32_t>(2560u, std::max<uint32_t>(40u, n_darts / 2048u)),
                    b16 = std::min<uint32_t>(4096u, std::max<uint32_t>(64u, n_darts / 1024u));
-    hipLaunchKernelGGL(k_contour_quads, dim3(b64 + b16), dim3(256), 0, st, b64, contours, ctr, max_contours, points, eps_factor, min_edge_length,
-                       first_frame, max_cand, cands, cand_count, err_flags, coords14);
+    hipLaunchKernelGGL(k_contour_quads, dim3(b64 + b16), dim3(256), 0, st, b64, c.contours, c.ctr,
+                       c.max_contours, c.points, c.eps_factor, c.min_edge_length, c.first_frame, c.max_cand,
+                       c.cands + (size_t)c.first_frame * c.max_cand, c.cand_count + c.first_frame, c.err_flags, coords14);
     return hipGetLastError();
 }
 

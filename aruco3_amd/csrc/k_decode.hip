@@ -10,6 +10,7 @@
 // fused, exactly like the Rust reference and the CPU oracle.
 
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_ippe.h"
 
 namespace a3 {
@@ -1082,11 +1083,10 @@ size_t decode_lds_bytes(uint32_t S, uint32_t n, uint32_t max_taps) {
     return (o + 15) & ~(size_t)15;
 }
 
-hipError_t launch_frame_candidates(hipStream_t st, const CandRec* cands, const uint32_t* cand_count, uint32_t n_frames, uint32_t max_cand,
-                                   float min_distance, uint16_t* pre_xy, uint16_t* fin_xy, uint32_t* fin_count, uint32_t* work,
-                                   unsigned int* work_count, uint32_t S, void* proj, float* big_scratch /* max_cand > frame_cand_lds_slots(): frames x max_cand floats */) {
+hipError_t launch_frame_candidates(hipStream_t st, const DecodeStage& f) {
+    const uint32_t max_cand = f.max_cand;
     const bool big = max_cand > kFrameCandLds;
-    if (big && !big_scratch) return hipErrorInvalidValue;
+    if (big && !f.big_scratch) return hipErrorInvalidValue;
     const size_t lds = big ? (size_t)max_cand + 16 : (size_t)max_cand * 21 + 16;
     if (lds > 48 * 1024) {   // tables grown past the default
         const hipError_t e = hipFuncSetAttribute(big ? reinterpret_cast<const void*>(k_frame_candidates<true>) : reinterpret_cast<const void*>(k_frame_candidates<false>),
@@ -1094,11 +1094,11 @@ hipError_t launch_frame_candidates(hipStream_t st, const CandRec* cands, const u
         if (e != hipSuccess) return e;
     }
     if (big)
-        hipLaunchKernelGGL(k_frame_candidates<true>, dim3(n_frames), dim3(64), lds, st, cands, cand_count, max_cand, min_distance, pre_xy, fin_xy,
-                           fin_count, work, work_count, S, reinterpret_cast<ProjRec*>(proj), big_scratch);
+        hipLaunchKernelGGL(k_frame_candidates<true>, dim3(f.n_frames), dim3(64), lds, st, f.cands, f.cand_count, max_cand, f.min_distance, f.pre_xy, f.fin_xy,
+                           f.fin_count, f.work, f.work_count, f.S, reinterpret_cast<ProjRec*>(f.proj), f.big_scratch);
     else
-        hipLaunchKernelGGL(k_frame_candidates<false>, dim3(n_frames), dim3(64), lds, st, cands, cand_count, max_cand, min_distance, pre_xy, fin_xy,
-                           fin_count, work, work_count, S, reinterpret_cast<ProjRec*>(proj), nullptr);
+        hipLaunchKernelGGL(k_frame_candidates<false>, dim3(f.n_frames), dim3(64), lds, st, f.cands, f.cand_count, max_cand, f.min_distance, f.pre_xy, f.fin_xy,
+                           f.fin_count, f.work, f.work_count, f.S, reinterpret_cast<ProjRec*>(f.proj), nullptr);
     return hipGetLastError();
 }
 uint32_t frame_cand_lds_slots() { return kFrameCandLds; }
@@ -1111,38 +1111,36 @@ hipError_t launch_weight_table(hipStream_t st, uint32_t S, uint32_t n, uint32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_decode(hipStream_t st, PixelSrc src, int W, int H, uint32_t first_frame, const uint16_t* fin_xy, const uint32_t* work,
-                         const unsigned int* work_count, uint32_t max_cand, uint32_t S, uint32_t n, uint32_t max_taps, const uint64_t* dict,
-                         uint32_t n_codes, uint32_t tau, int filter, void* proj, const float* wtab, void* outs, uint8_t* patches, uint32_t patch_cap, uint32_t* per_frame, int grid_blocks, int dbg, int few) {
-    ProjRec* recs = reinterpret_cast<ProjRec*>(proj);
-    if (dbg > 0 || dbg == -1000) hipLaunchKernelGGL(k_projection, dim3(256), dim3(64), 0, st, fin_xy, work, work_count, S, recs);
+hipError_t launch_decode(hipStream_t st, const DecodeStage& d) {
+    ProjRec* recs = reinterpret_cast<ProjRec*>(d.proj);
+    if (d.projection) hipLaunchKernelGGL(k_projection, dim3(256), dim3(64), 0, st, d.fin_xy, d.work, d.work_count, d.S, recs);
     // Four waves sample a candidate: a candidate is a chain of round trips to the frame (19 of them for one wave: 65 us for a lone
     // candidate however idle the chip is, 33 us with four waves).  What follows the sampling runs on all four waves when the
     // batch is small and every microsecond of that chain shows (`few`: at most 64 frames; 36 us for the 337 candidates of 32
     // frames against 39), and on one wave -- no workgroup barriers -- when thousands of candidates are in flight and only the
     // throughput counts (BASELINE config 2: decode stage 0.123 ms against 0.130 with one wave per candidate throughout).
-    const int d = dbg == -1000 ? 0 : (dbg < 0 ? -dbg : dbg);
-    if (few)
-        hipLaunchKernelGGL((k_decode<256, 256>), dim3(grid_blocks), dim3(256), decode_lds_bytes(S, n, max_taps), st, src, W, H, first_frame, fin_xy, work, work_count,
-                           max_cand, S, n, max_taps, dict, n_codes, tau, filter, recs, wtab, reinterpret_cast<DecodeOut*>(outs), patches, patch_cap, per_frame, d);
+    const size_t lds = decode_lds_bytes(d.S, d.n, d.max_taps);
+    if (d.few)
+        hipLaunchKernelGGL((k_decode<256, 256>), dim3(d.grid_blocks), dim3(256), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy, d.work, d.work_count,
+                           d.max_cand, d.S, d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab, reinterpret_cast<DecodeOut*>(d.outs), d.patches,
+                           d.patch_cap, d.per_frame, d.variant);
     else
-        hipLaunchKernelGGL((k_decode<kDecodeThreads, 64>), dim3(grid_blocks), dim3(kDecodeThreads), decode_lds_bytes(S, n, max_taps), st, src, W, H, first_frame, fin_xy, work,
-                           work_count, max_cand, S, n, max_taps, dict, n_codes, tau, filter, recs, wtab, reinterpret_cast<DecodeOut*>(outs), patches, patch_cap,
-                           per_frame, d);
+        hipLaunchKernelGGL((k_decode<kDecodeThreads, 64>), dim3(d.grid_blocks), dim3(kDecodeThreads), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy, d.work,
+                           d.work_count, d.max_cand, d.S, d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab, reinterpret_cast<DecodeOut*>(d.outs),
+                           d.patches, d.patch_cap, d.per_frame, d.variant);
     return hipGetLastError();
 }
 
 size_t decode_out_bytes() { return sizeof(DecodeOut); }
 
-hipError_t launch_compact_markers(hipStream_t st, const void* outs, const uint16_t* fin_xy, const uint32_t* fin_count, uint32_t n_frames,
-                                  uint32_t first_frame, uint32_t max_cand, a3_marker* markers, uint32_t marker_cap, uint32_t* per_frame,
-                                  unsigned int* marker_total, unsigned int* err_flags, const uint32_t* cand_count, unsigned int* cand_pre_total) {
-    if (first_frame == 0 && n_frames <= kCompactParMax)
-        hipLaunchKernelGGL(k_compact_markers_par, dim3((n_frames + 3) / 4), dim3(256), 0, st, reinterpret_cast<const DecodeOut*>(outs), fin_xy, fin_count,
-                           n_frames, max_cand, markers, marker_cap, per_frame, marker_total, err_flags, cand_count, cand_pre_total);
+hipError_t launch_compact_markers(hipStream_t st, const DecodeStage& c) {
+    const DecodeOut* outs = reinterpret_cast<const DecodeOut*>(c.outs);
+    if (c.first_frame == 0 && c.n_frames <= kCompactParMax)
+        hipLaunchKernelGGL(k_compact_markers_par, dim3((c.n_frames + 3) / 4), dim3(256), 0, st, outs, c.fin_xy, c.fin_count, c.n_frames, c.max_cand, c.markers,
+                           c.marker_cap, c.per_frame, c.marker_total, c.err_flags, c.cand_count, c.cand_pre_total);
     else
-        hipLaunchKernelGGL(k_compact_markers, dim3(1), dim3(256), 0, st, reinterpret_cast<const DecodeOut*>(outs), fin_xy, fin_count, n_frames,
-                           first_frame, max_cand, markers, marker_cap, per_frame, marker_total, err_flags, cand_count, cand_pre_total);
+        hipLaunchKernelGGL(k_compact_markers, dim3(1), dim3(256), 0, st, outs, c.fin_xy, c.fin_count, c.n_frames, c.first_frame, c.max_cand, c.markers,
+                           c.marker_cap, c.per_frame, c.marker_total, c.err_flags, c.cand_count, c.cand_pre_total);
     return hipGetLastError();
 }
 
@@ -1158,11 +1156,9 @@ hipError_t launch_debug_rotate_bits(hipStream_t st, const uint8_t* in, uint32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_pose(hipStream_t st, const uint32_t* corners, uint32_t corner_stride, const float* norm_pts, uint32_t n,
-                       const unsigned int* n_dev, int mode, float marker_size_mm, float iw, float ih, float fx, float fy, float cx, float cy,
-                       a3_pose* out) {
-    hipLaunchKernelGGL(k_pose, dim3((n + 63) / 64), dim3(64), 0, st, corners, corner_stride, norm_pts, n, n_dev, mode, marker_size_mm, iw, ih,
-                       fx, fy, cx, cy, out);
+hipError_t launch_pose(hipStream_t st, const PoseLaunch& p) {
+    hipLaunchKernelGGL(k_pose, dim3((p.n + 63) / 64), dim3(64), 0, st, p.corners, p.corner_stride, p.norm_pts, p.n, p.n_dev, p.mode, p.marker_size_mm, p.iw, p.ih,
+                       p.fx, p.fy, p.cx, p.cy, p.out);
     return hipGetLastError();
 }
 

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_handeye.h"
 
 namespace a3 {

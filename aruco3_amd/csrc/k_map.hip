@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_map.h"
 
 namespace a3 {
@@ -831,12 +832,10 @@ size_t map_obs_bytes() { return kMapObsDoubles * sizeof(double); }
 size_t map_frame_bytes() { return kMapFrameDoubles * sizeof(double); }
 size_t map_marker_bytes() { return kMapMarkerDoubles * sizeof(double); }
 
-hipError_t launch_map(hipStream_t st, const a3_map* maps, uint32_t n_maps, const a3_map_marker* markers, const a3_map_observation* obs, const float* img,
-                      const uint64_t* big_off, uint32_t* fo, uint32_t* ml, double* oscr, double* fscr, double* mscr, double* big, a3_map_result* res,
-                      a3_map_marker_result* mres, a3_map_frame* frames, a3_map_observation_result* ores) {
-    if (n_maps == 0) return hipSuccess;
-    const MapArgs g{maps, markers, obs, img, big_off, fo, ml, oscr, fscr, mscr, big, res, mres, frames, ores};
-    hipLaunchKernelGGL(k_map, dim3(n_maps), dim3(kMapThreads), 0, st, g);
+hipError_t launch_map(hipStream_t st, const MapLaunch& m) {
+    if (m.n_maps == 0) return hipSuccess;
+    const MapArgs g{m.maps, m.markers, m.obs, m.img, m.big_off, m.fo, m.ml, m.oscr, m.fscr, m.mscr, m.big, m.res, m.mres, m.frames, m.ores};
+    hipLaunchKernelGGL(k_map, dim3(m.n_maps), dim3(kMapThreads), 0, st, g);
     return hipGetLastError();
 }
 

@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_undistort.h"
 
 namespace a3 {
@@ -169,9 +170,9 @@ void rectify_grid(uint32_t dw, uint32_t dh, uint32_t n_frames, uint32_t* tiles_x
     *chunks = (n_frames + kChunk - 1) / kChunk;
 }
 
-// src / dst: device memory; bpp 1, 3 or 4.  The caller has checked every size and stride (a3_rectify_frames).
-hipError_t launch_rectify(hipStream_t st, const uint8_t* src, size_t src_row, size_t src_frame, uint32_t n_frames, int bpp, const a3_rectify& r,
-                          uint8_t* dst, size_t dst_row, size_t dst_frame) {
+hipError_t launch_rectify(hipStream_t st, const RectifyLaunch& l) {
+    const a3_rectify& r = *l.r;
+    const uint8_t* const src = l.src; uint8_t* const dst = l.dst; const uint32_t n_frames = l.n_frames; const int bpp = l.bpp;
     const bool fisheye = r.distortion.model == A3_DIST_FISHEYE, lens = fisheye || r.distortion.model == A3_DIST_RATIONAL;
     const a3_distortion& k = r.distortion;
     RectifyParams p{};
@@ -182,7 +183,7 @@ hipError_t launch_rectify(hipStream_t st, const uint8_t* src, size_t src_row, si
     p.k3 = lens ? k.k3 : 0.0f; p.k4 = lens ? k.k4 : 0.0f; p.k5 = lens ? k.k5 : 0.0f; p.k6 = lens ? k.k6 : 0.0f;
     p.sw = r.src.image_width; p.sh = r.src.image_height; p.dw = r.dst.image_width; p.dh = r.dst.image_height;
     p.n_frames = n_frames; p.fill = r.fill;
-    p.src_row = src_row; p.src_frame = src_frame; p.dst_row = dst_row; p.dst_frame = dst_frame;
+    p.src_row = l.src_row; p.src_frame = l.src_frame; p.dst_row = l.dst_row; p.dst_frame = l.dst_frame;
     uint32_t tx, ty, tz;
     rectify_grid(p.dw, p.dh, n_frames, &tx, &ty, &tz);
     const dim3 grid(tx, ty, tz), block(WAVE * kTileH);

@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_subpix.h"
 
 namespace a3 {
@@ -109,13 +110,11 @@ void refine_params(void* out, const a3_refine_config& cfg, uint32_t cells) {
 
 size_t refine_params_bytes() { return sizeof(RefineParams); }
 
-// (grid: one workgroup per marker up to 1024, then a workgroup-stride loop; the marker count is read on the device)
-hipError_t launch_refine_corners(hipStream_t st, PixelSrc src, uint32_t W, uint32_t H, const a3_marker* markers, const unsigned int* n_dev,
-                                 const float* pts, const float* cell_px, uint32_t n, const void* params, float* out) {
-    const uint32_t units = markers ? n : (n + 3u) / 4u;
+hipError_t launch_refine_corners(hipStream_t st, const RefineLaunch& r) {
+    const uint32_t units = r.markers ? r.n : (r.n + 3u) / 4u;
     if (units == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_refine_corners, dim3(std::min<uint32_t>(units, 1024u)), dim3(256), 0, st, src, W, H, markers, n_dev, pts, cell_px, n,
-                       *reinterpret_cast<const RefineParams*>(params), out);
+    hipLaunchKernelGGL(k_refine_corners, dim3(std::min<uint32_t>(units, 1024u)), dim3(256), 0, st, r.src, r.W, r.H, r.markers, r.n_dev, r.pts, r.cell_px, r.n,
+                       *reinterpret_cast<const RefineParams*>(r.params), r.out);
     return hipGetLastError();
 }
 

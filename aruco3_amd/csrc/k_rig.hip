@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_rig.h"
 
 namespace a3 {
@@ -596,12 +597,10 @@ size_t rig_obs_bytes() { return kRigObsDoubles * sizeof(double); }
 size_t rig_frame_bytes() { return kRigFrameDoubles * sizeof(double); }
 size_t rig_table_bytes() { return kRigMaxC * sizeof(uint32_t); }
 
-hipError_t launch_rig(hipStream_t st, const a3_rig* rigs, uint32_t n_rigs, const a3_rig_camera* cams, const a3_rig_observation* obs, const float* obj,
-                      const float* img, uint32_t* tab, double* oscr, double* fscr, a3_rig_result* res, a3_rig_camera_result* cres,
-                      a3_rig_frame* frames, a3_rig_observation_result* ores) {
-    if (n_rigs == 0) return hipSuccess;
-    const RigArgs g{rigs, cams, obs, obj, img, tab, oscr, fscr, res, cres, frames, ores};
-    hipLaunchKernelGGL(k_rig, dim3(n_rigs), dim3(kRigThreads), 0, st, g);
+hipError_t launch_rig(hipStream_t st, const RigLaunch& r) {
+    if (r.n_rigs == 0) return hipSuccess;
+    const RigArgs g{r.rigs, r.cams, r.obs, r.obj, r.img, r.tab, r.oscr, r.fscr, r.res, r.cres, r.frames, r.ores};
+    hipLaunchKernelGGL(k_rig, dim3(r.n_rigs), dim3(kRigThreads), 0, st, g);
     return hipGetLastError();
 }
 

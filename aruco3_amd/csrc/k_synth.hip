@@ -6,6 +6,7 @@
 // one thread per pixel paints the background gradient, then every marker whose bounding box covers the pixel through the
 // inverse homography with ss x ss supersampling, then the channel tint and optional Gaussian noise.
 #include "a3_common.h"
+#include "a3_launch.h"
 
 namespace a3 {
 
@@ -59,10 +60,9 @@ __global__ __launch_bounds__(256) void k_synth_render(const a3_synth_frame* __re
     for (int c = 0; c < 3; c++) dst[c] = (uint8_t)rintf(fminf(fmaxf(rgb[c], 0.0f), 255.0f));
 }
 
-hipError_t launch_synth_render(hipStream_t st, const a3_synth_frame* frames, uint32_t n_frames, const a3_synth_marker* markers, uint32_t W,
-                               uint32_t H, int paper, float black, float white, int ss, uint8_t* out, size_t row_stride, size_t frame_stride) {
-    hipLaunchKernelGGL(k_synth_render, dim3((W + 255) / 256, H, n_frames), dim3(256), 0, st, frames, markers, W, H, paper, black, white, ss, out,
-                       row_stride, frame_stride);
+hipError_t launch_synth_render(hipStream_t st, const SynthLaunch& s) {
+    hipLaunchKernelGGL(k_synth_render, dim3((s.W + 255) / 256, s.H, s.n_frames), dim3(256), 0, st, s.frames, s.markers, s.W, s.H, s.paper, s.black, s.white,
+                       s.supersample, s.out, s.row_stride, s.frame_stride);
     return hipGetLastError();
 }
 

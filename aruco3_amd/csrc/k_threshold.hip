@@ -159,34 +159,24 @@ __global__ __launch_bounds__(64) void k_vsum_threshold_generic(const uint8_t* __
 }
 
 // ---- host launcher -------------------------------------------------------------------------
-// radii 1..3 and 4..6: k_threshold_r1.hip, k_threshold_r2.hip
-hipError_t launch_k1_r1(uint32_t radius, hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H, uint32_t n,
-                        uint8_t* grey, uint64_t* bits);
-hipError_t launch_k1_r2(uint32_t radius, hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H, uint32_t n,
-                        uint8_t* grey, uint64_t* bits);
-
 // threshold windows the register-resident kernel covers: radii 1..kFusedMaxRadius.  Beyond 7 the packed 16-bit arithmetic ends --
 // (2R+1)^2 * 256 no longer fits a u16 from R = 8 on (289 * 256 = 73 984), so window sums and the compare would need 32-bit lanes and a ring
 // of 2R+1 rows no register file holds.
 // Radii 8..31 have a fused kernel of their own (k_threshold_big.hip: the grey ring in registers + LDS, 32-bit sums); what is left for
 // the separable path -- which needs a grey plane and a plane of row sums -- is radius 0 and radii above 31.
 constexpr uint32_t kFusedMaxRadius = 7;
-bool ring_kernel_applies(uint32_t radius, const uint8_t* pixels, size_t row_stride, size_t frame_stride, int W);
-hipError_t launch_ring_threshold(uint32_t radius, hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H,
-                                 uint32_t n, uint8_t* grey, uint64_t* bits);
-bool threshold_writes_grey_plane(uint32_t radius, const uint8_t* pixels, size_t row_stride, size_t frame_stride, int W) {
-    return (radius == 0 || radius > kFusedMaxRadius) && !ring_kernel_applies(radius, pixels, row_stride, frame_stride, W);
-}
+bool threshold_writes_grey_plane(uint32_t radius) { return (radius == 0 || radius > kFusedMaxRadius) && !ring_kernel_applies(radius); }
 
-hipError_t launch_grey_threshold(hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H,
-                                 uint32_t n, uint32_t radius, uint8_t* grey, uint64_t* bits, uint16_t* hsum_tmp) {
-    switch (radius) {
-        case 1: case 2: case 3: return launch_k1_r1(radius, st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 4: case 5: case 6: return launch_k1_r2(radius, st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 7: return launch_k1<7>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
+hipError_t launch_grey_threshold(hipStream_t st, const ThresholdLaunch& t) {
+    switch (t.radius) {
+        case 1: case 2: case 3: return launch_k1_r1(st, t);
+        case 4: case 5: case 6: return launch_k1_r2(st, t);
+        case 7: return launch_k1<7>(st, t);
         default: break;
     }
-    if (ring_kernel_applies(radius, pixels, row_stride, frame_stride, W)) return launch_ring_threshold(radius, st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
+    if (ring_kernel_applies(t.radius)) return launch_ring_threshold(st, t);
+    const uint8_t* const pixels = t.pixels; uint8_t* const grey = t.grey; uint64_t* const bits = t.bits; uint16_t* const hsum_tmp = t.hsum_tmp;
+    const int fmt = t.fmt, W = t.W, H = t.H; const size_t row_stride = t.row_stride, frame_stride = t.frame_stride; const uint32_t n = t.n, radius = t.radius;
     dim3 block(64), gridg((W + 255) / 256, H, n), grid1(words_per_row((uint32_t)W), H, n);
     if (fmt == A3_FMT_RGB8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_RGB8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
     else if (fmt == A3_FMT_RGBA8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_RGBA8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);

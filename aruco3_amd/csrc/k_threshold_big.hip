@@ -245,8 +245,9 @@ __global__ __launch_bounds__(64, 2 * R + 1 - ring_reg_rows(R, FAST, FMT) <= kRin
 }
 
 template <int R>
-hipError_t launch_ring(hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H, uint32_t n, uint8_t* grey,
-                       uint64_t* bits) {
+hipError_t launch_ring(hipStream_t st, const ThresholdLaunch& t) {
+    const uint8_t* const pixels = t.pixels; uint8_t* const grey = t.grey; uint64_t* const bits = t.bits;
+    const int fmt = t.fmt, W = t.W, H = t.H; const size_t row_stride = t.row_stride, frame_stride = t.frame_stride; const uint32_t n = t.n;
     constexpr int OUT = ring_out_cols(R);
     uint8_t* bin = reinterpret_cast<uint8_t*>(bits);
     if (W % 64 != 0) {  // packed rows end in padding bits that no strip writes
@@ -289,36 +290,34 @@ hipError_t launch_ring(hipStream_t st, const uint8_t* pixels, int fmt, size_t ro
     return hipGetLastError();
 }
 
-// the radii this file covers (any frame layout)
-bool ring_kernel_applies(uint32_t radius, const uint8_t*, size_t, size_t, int) { return radius >= 8 && radius <= 31; }
+bool ring_kernel_applies(uint32_t radius) { return radius >= 8 && radius <= 31; }
 
-hipError_t launch_ring_threshold(uint32_t radius, hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H,
-                                 uint32_t n, uint8_t* grey, uint64_t* bits) {
-    switch (radius) {
-        case 8: return launch_ring<8>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 9: return launch_ring<9>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 10: return launch_ring<10>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 11: return launch_ring<11>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 12: return launch_ring<12>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 13: return launch_ring<13>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 14: return launch_ring<14>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 15: return launch_ring<15>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 16: return launch_ring<16>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 17: return launch_ring<17>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 18: return launch_ring<18>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 19: return launch_ring<19>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 20: return launch_ring<20>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 21: return launch_ring<21>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 22: return launch_ring<22>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 23: return launch_ring<23>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 24: return launch_ring<24>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 25: return launch_ring<25>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 26: return launch_ring<26>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 27: return launch_ring<27>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 28: return launch_ring<28>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 29: return launch_ring<29>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 30: return launch_ring<30>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 31: return launch_ring<31>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
+hipError_t launch_ring_threshold(hipStream_t st, const ThresholdLaunch& t) {
+    switch (t.radius) {
+        case 8: return launch_ring<8>(st, t);
+        case 9: return launch_ring<9>(st, t);
+        case 10: return launch_ring<10>(st, t);
+        case 11: return launch_ring<11>(st, t);
+        case 12: return launch_ring<12>(st, t);
+        case 13: return launch_ring<13>(st, t);
+        case 14: return launch_ring<14>(st, t);
+        case 15: return launch_ring<15>(st, t);
+        case 16: return launch_ring<16>(st, t);
+        case 17: return launch_ring<17>(st, t);
+        case 18: return launch_ring<18>(st, t);
+        case 19: return launch_ring<19>(st, t);
+        case 20: return launch_ring<20>(st, t);
+        case 21: return launch_ring<21>(st, t);
+        case 22: return launch_ring<22>(st, t);
+        case 23: return launch_ring<23>(st, t);
+        case 24: return launch_ring<24>(st, t);
+        case 25: return launch_ring<25>(st, t);
+        case 26: return launch_ring<26>(st, t);
+        case 27: return launch_ring<27>(st, t);
+        case 28: return launch_ring<28>(st, t);
+        case 29: return launch_ring<29>(st, t);
+        case 30: return launch_ring<30>(st, t);
+        case 31: return launch_ring<31>(st, t);
         default: return hipErrorInvalidValue;
     }
 }

@@ -6,6 +6,7 @@
 #include <utility>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 
 namespace a3 {
 
@@ -408,8 +409,9 @@ __global__ __launch_bounds__(64, T_WAVES) void k_grey_threshold7(const uint8_t* 
 
 // the register-resident kernel for one radius R in 1..7 (the default, 7, is the one every figure of DESIGN.md is about)
 template <int R>
-hipError_t launch_k1(hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H, uint32_t n,
-                            uint8_t* grey, uint64_t* bits) {
+hipError_t launch_k1(hipStream_t st, const ThresholdLaunch& t) {
+    const uint8_t* const pixels = t.pixels; uint8_t* const grey = t.grey; uint64_t* const bits = t.bits;
+    const int fmt = t.fmt, W = t.W, H = t.H; const size_t row_stride = t.row_stride, frame_stride = t.frame_stride; const uint32_t n = t.n;
     constexpr int NR = 2 * R + 1, UNROLL = ((NR + T_PF - 1) / T_PF) * T_PF;   // (as in the kernel)
     const int aligned_in = ((uintptr_t)pixels % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0);
     const int aligned_out = (W % 16 == 0) && ((uintptr_t)grey % 16 == 0);

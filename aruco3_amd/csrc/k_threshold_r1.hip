@@ -3,12 +3,11 @@
 
 namespace a3 {
 
-hipError_t launch_k1_r1(uint32_t radius, hipStream_t st, const uint8_t* pixels, int fmt, size_t row_stride, size_t frame_stride, int W, int H, uint32_t n,
-                        uint8_t* grey, uint64_t* bits) {
-    switch (radius) {
-        case 1: return launch_k1<1>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 2: return launch_k1<2>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
-        case 3: return launch_k1<3>(st, pixels, fmt, row_stride, frame_stride, W, H, n, grey, bits);
+hipError_t launch_k1_r1(hipStream_t st, const ThresholdLaunch& t) {
+    switch (t.radius) {
+        case 1: return launch_k1<1>(st, t);
+        case 2: return launch_k1<2>(st, t);
+        case 3: return launch_k1<3>(st, t);
         default: return hipErrorInvalidValue;
     }
 }

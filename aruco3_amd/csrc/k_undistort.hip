@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "a3_common.h"
+#include "a3_launch.h"
 #include "a3_undistort.h"
 
 namespace a3 {
@@ -30,8 +31,6 @@ __global__ __launch_bounds__(256) void k_undistort_corners(const a3_marker* __re
     }
 }
 
-// markers / pts: the corners' source (pts wins when both are given); n_dev: the device-side marker count of a batch (n = marker_cap),
-// or nullptr for n stand-alone points
 hipError_t launch_undistort_corners(hipStream_t st, const a3_marker* markers, const float* pts, const unsigned int* n_dev, uint32_t n,
                                     const a3_intrinsics& in, const a3_distortion& d, float* out_xy, float* out_res) {
     const uint64_t corners = n_dev ? (uint64_t)n * 4u : n;
