@@ -10,7 +10,7 @@ from .dictionaries import ARDictionary  # noqa: F401
 
 def __getattr__(name):
     # GPU-backed names are imported lazily so that table handling works without the .so
-    if name in ("Detector", "DetectorConfig", "Detection", "Marker"):
+    if name in ("Detector", "DetectorConfig", "Detection", "Marker", "Rectification"):
         from . import aruco
 
         return getattr(aruco, name)

@@ -72,7 +72,7 @@ SYMBOLS = [
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
     "a3_calibrate_cameras", "a3_calibrate_fisheye_cameras", "a3_calibrate_rigs", "a3_calibrate_hand_eyes", "a3_build_marker_maps",
-    "a3_default_rectify", "a3_rectify_frames",
+    "a3_default_rectify", "a3_rectify_frames", "a3_set_rectification", "a3_get_rectification",
 ]
 CAND_DTYPE = np.dtype([("start_key", "<u4"), ("xy", "<u2", (8,))])      # a3_debug_cand (a3_internal.h)
 PROJ_DTYPE = np.dtype([("inv", "<f4", (9,)), ("ok", "<i4")])            # A3_DEBUG_PROJ_BYTES
@@ -484,6 +484,11 @@ def load():
         L.a3_rectify_frames.restype = C.c_int
         L.a3_rectify_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(RectifyRec), vp, C.c_int,
                                         C.c_size_t, C.c_size_t, C.POINTER(RectifyInfo)]
+    if hasattr(L, "a3_set_rectification"):   # (likewise rectification inside the detect calls)
+        L.a3_set_rectification.restype = C.c_int
+        L.a3_set_rectification.argtypes = [vp, C.POINTER(RectifyRec)]
+        L.a3_get_rectification.restype = C.c_int
+        L.a3_get_rectification.argtypes = [vp, C.POINTER(RectifyRec), C.POINTER(C.c_int)]
     L.a3_debug_discard_too_near.restype = C.c_int
     L.a3_debug_discard_too_near.argtypes = [vp, u32p, C.c_size_t, C.c_float, u32p, C.POINTER(C.c_size_t)]
     if hasattr(L, "a3_debug_frame_candidates"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack it)
@@ -860,6 +865,17 @@ class Context:
         return out, res
 
     # ---- frame rectification ----
+    def set_rectification(self, r: "RectifyRec" = None):
+        """a3_set_rectification: every later detect call of this context sees its frames through r (they have r.src's size, the results
+        are pixels of r.dst's view); None turns it off.  Refused while a submitted batch is in flight."""
+        check(load().a3_set_rectification(self.handle, C.byref(r) if r is not None else None), self.handle)
+
+    def rectification(self):
+        """a3_get_rectification -> the RectifyRec in force, or None"""
+        r, on = RectifyRec(), C.c_int(0)
+        check(load().a3_get_rectification(self.handle, C.byref(r), C.byref(on)), self.handle)
+        return r if on.value else None
+
     def rectify_frames(self, src_ptr: int, src_memory: int, fmt: int, src_row_stride: int, src_frame_stride: int, n_frames: int,
                        r: "RectifyRec", dst_ptr: int, dst_memory: int, dst_row_stride: int, dst_frame_stride: int) -> "RectifyInfo":
         """a3_rectify_frames: n_frames frames at src_ptr (r.src's size) -> rectified frames at dst_ptr (r.dst's size, same format);

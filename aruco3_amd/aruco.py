@@ -47,6 +47,38 @@ class CornerRefinement:
 
 
 @dataclass
+class Rectification:
+    """Frame rectification inside the detect calls (a3_set_rectification; not in the reference).  The arguments mean what they mean in
+    `rectify_frames`: `intrinsics` is the camera the frames come from (with its `distortion`), `new_intrinsics` the rectified view and its
+    size (default: the camera without its lens), `rotation` 3 x 3 camera -> view, `fill` the grey level of a pixel that sees nothing.
+    Passing one to `Detector(rectification=...)` makes every detect call take frames of `intrinsics`' size and return, to the bit, what
+    `rectify_frames` followed by the same call would: corners are pixels of the view, and pose calls take the view's plain intrinsics."""
+    intrinsics: object
+    new_intrinsics: object = None
+    rotation: object = None
+    fill: int = 0
+
+    def _c(self) -> _lib.RectifyRec:
+        from .rectify import rectify_rec
+
+        return rectify_rec(self.intrinsics, self.new_intrinsics, self.rotation, self.fill)
+
+    @property
+    def view_size(self) -> Tuple[int, int]:
+        """(width, height) of the rectified view"""
+        v = self.new_intrinsics if self.new_intrinsics is not None else self.intrinsics
+        return int(v.image_width), int(v.image_height)
+
+
+def _apply_rectification(ctx: _lib.Context, rectification: Optional[Rectification]) -> None:
+    """hands a rectification setting to a context that has no batch in flight (the setter is refused otherwise): only on a change"""
+    key = None if rectification is None else bytes(rectification._c())
+    if getattr(ctx, "_rectification_key", None) != key:
+        ctx.set_rectification(None if rectification is None else rectification._c())
+        ctx._rectification_key = key
+
+
+@dataclass
 class Marker:
     """src/aruco.rs:8-13, plus the refined corners when the detector refines them and the undistorted corners (with their residuals in
     pixels, +inf: not undistorted) when a pose call's intrinsics carry a lens distortion (extensions; None otherwise)"""
@@ -111,7 +143,8 @@ class Detector:
     """`Detector { config, dictionary }` (src/aruco.rs:46-49)."""
 
     def __init__(self, config: DetectorConfig = None, dictionary: ARDictionary = None, device: int = 0,
-                 refinement: Optional[CornerRefinement] = None, board=None, charuco_config: Optional[_lib.CharucoConfig] = None):
+                 refinement: Optional[CornerRefinement] = None, board=None, charuco_config: Optional[_lib.CharucoConfig] = None,
+                 rectification: Optional[Rectification] = None):
         self.config = config or DetectorConfig()
         self.dictionary = dictionary or ARDictionary.new_from_named_dict("ARUCO")
         self.device = device
@@ -119,6 +152,8 @@ class Detector:
         self.board = board   # aruco3_amd.board.Board: detect_batch_with_board_pose solves one pose per frame from it
         # with a board.CharucoBoard: every call also returns the chessboard corners (a3_charuco_config; None: the library's defaults)
         self.charuco_config = charuco_config
+        # every call sees its frames through this rectification (frames of its camera's size in, pixels of its view out)
+        self.rectification = rectification
         self._ctx = None
         self._ctx_key = None
 
@@ -151,12 +186,18 @@ class Detector:
         ctx.set_distortion(d._c() if d is not None else None)
         return d is not None
 
+    def _check_pose_intrinsics(self, intrinsics) -> None:
+        """a detector that rectifies its frames returns pixels of an ideal pinhole view: a lens on the pose call would undistort twice"""
+        if self.rectification is not None and getattr(intrinsics, "distortion", None) is not None:
+            raise ValueError("the detector rectifies its frames: pass the view's plain intrinsics (no `distortion`) to the pose calls")
+
     def _context(self) -> _lib.Context:
         key = (tuple(vars(self.config).items()), id(self.dictionary), self.device)
         if self._ctx is None or self._ctx_key != key:
             d = self.dictionary
             self._ctx = _lib.Context(self.config._c(), d.code_list, d.num_bits, d._tau, self.device)
             self._ctx_key = key
+        _apply_rectification(self._ctx, self.rectification)
         return self._ctx
 
     # src/aruco.rs:52-121
@@ -187,7 +228,7 @@ class Detector:
                 det.markers.append(_marker(markers[i], refined[i] if refined is not None else None))
             pos += int(per[f])
             if populate:
-                det.grey = ctx.download_grey(f, w, h)
+                det.grey = ctx.download_grey(f, *(self.rectification.view_size if self.rectification is not None else (w, h)))
                 det.candidates = [[(int(x), int(y)) for x, y in q] for q in ctx.candidates(f)]
                 patches, ok, _, _ = ctx.homographies(f)
                 det.homographies = [p if o else np.zeros((1, 1), np.uint8) for p, o in zip(patches, ok)]  # src/aruco.rs:256
@@ -201,6 +242,7 @@ class Detector:
         device pass, the way examples/webcam_kamera.rs:56-71 chains them.  -> [(Detection, [(MarkerPose, MarkerPose), ...])]"""
         from .pose import MarkerPose
 
+        self._check_pose_intrinsics(intrinsics)
         ctx = self._context()
         ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
         if stream is not None:
@@ -238,6 +280,7 @@ class Detector:
 
         if self.board is None:
             raise ValueError("detect_batch_with_board_pose needs Detector(board=...)")
+        self._check_pose_intrinsics(intrinsics)
         ctx = self._context()
         ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
         if stream is not None:
@@ -266,6 +309,7 @@ class Detector:
 
         if not _is_charuco(self.board):
             raise ValueError("detect_batch_with_charuco_pose needs Detector(board=CharucoBoard(...))")
+        self._check_pose_intrinsics(intrinsics)
         ctx = self._context()
         ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
         if stream is not None:
@@ -374,6 +418,7 @@ class BatchQueue:
         self._ctxs = [_lib.Context(detector.config._c(), d.code_list, d.num_bits, d._tau, detector.device) for _ in range(depth)]
         self._refinement = detector.refinement   # (the detector's setting when the queue was made; each batch keeps the one in force at its submit)
         self._board, self._charuco_config = detector.board, detector.charuco_config   # (likewise)
+        self._rectification = detector.rectification   # (likewise)
         self._refine_on = [False] * depth
         self._keep = [None] * depth
         self._gates = gates
@@ -398,6 +443,7 @@ class BatchQueue:
                 ctx.order_after(self._ctxs[m])
         ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
         ctx.set_debug_taps(False)
+        _apply_rectification(ctx, self._rectification)   # (this context's last batch has been collected: the queue is not full)
         ctx.set_corner_refinement(self._refinement._c() if self._refinement is not None else None)
         self._refine_on[k] = self._refinement is not None
         if self._submitted < depth and self._board is not None:   # (each context's first batch: the board stays set on it)

@@ -16,6 +16,7 @@
 #include "a3_internal.h"
 #include "a3_launch.h"
 #include "a3_readback.h"
+#include "a3_rectify_check.h"
 #include "a3_solve_check.h"
 
 using namespace a3;
@@ -105,6 +106,12 @@ struct Batch {
     bool charuco = false;        // ChArUco set: the corner stage runs behind the refinement (and k_charuco_pose behind k_board_pose)
     a3_charuco_config charuco_cfg{};
     uint32_t charuco_nc = 0, charuco_guess = 0;   // chessboard corners; records in the speculative read-back
+    // a3_set_rectification in force: the call's frames (rect_src, in rect_fmt, with strides rect_row and rect_frame) are the SOURCE, seen
+    // through rect_r.  pixels, fmt, W, H, row_stride and frame_stride above then describe the rectified grey plane (A3_FMT_L8, r.dst's size),
+    // which k_rectify's grey form writes ahead of the threshold kernel; everything behind that launch sees nothing else
+    bool rect = false;
+    a3_rectify rect_r{};
+    const uint8_t* rect_src = nullptr; int rect_fmt = 0; size_t rect_row = 0, rect_frame = 0;
     bool taps = false;           // debug taps: grey plane, patches, contours and the per-frame candidate counts are kept
     bool sample_frames = false;  // a3_debug_sample_frames: a tapped batch still samples the caller's frames wherever an untapped one would
     int profiling = 0, profile_every = 1;   // a3_set_profiling in force
@@ -262,6 +269,11 @@ struct a3_ctx {
     DevBuf solve_in, solve_scratch, solve_big, solve_out;
     // a3_rectify_frames: host-side source frames and host-side output staged on the device
     DevBuf rect_in, rect_out;
+    // a3_set_rectification: the setting later batches capture, and the rectified grey plane of the batch in flight (n x dw x dh bytes,
+    // tightly packed): written ahead of the threshold kernel, sampled by the decode stage, the refinement and ChArUco until collect
+    a3_rectify rect{};
+    bool rect_on = false;
+    DevBuf rect_plane;
     uint32_t last_charuco_total = 0;   // sizes the speculative record read-back of the next batch
     void* pinned = nullptr;
     size_t pinned_cap = 0;
@@ -732,6 +744,9 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
 
     // ---- K1 ----
     b.prof = b.profiling == 1 && (ctx->batch_seq++ % (uint32_t)b.profile_every) != 0 ? 0 : b.profiling;
+    if (b.rect)   // the frames' rectified grey plane, immediately ahead of its reader on the same stream: whatever orders that orders this
+        A3_HIP(launch_rectify_grey(st, {.src = b.rect_src, .src_row = b.rect_row, .src_frame = b.rect_frame, .n_frames = n, .fmt = b.rect_fmt, .r = &b.rect_r,
+                                        .grey = ctx->rect_plane.as<uint8_t>()}));
     if (b.prof) A3_HIP(hipEventRecord(ctx->ev[0], st));
     A3_HIP(launch_grey_threshold(st, {.pixels = b.pixels, .fmt = b.fmt, .row_stride = b.row_stride, .frame_stride = b.frame_stride, .W = (int)W, .H = (int)H,
                                       .n = n, .radius = ctx->cfg.threshold_window, .grey = b.need_grey ? ctx->grey.as<uint8_t>() : nullptr,
@@ -1311,7 +1326,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
                       &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->solve_in,
-                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out};
+                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out, &ctx->rect_plane};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1477,6 +1492,8 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
                        size_t frame_stride, uint32_t n_frames, size_t out_cap, bool want_pose, float size_mm, const a3_intrinsics* intr) {
     Batch& b = ctx->batch;
     b = Batch{};
+    if (ctx->rect_on && (width != ctx->rect.src.image_width || height != ctx->rect.src.image_height))
+        return fail(ctx, A3_ERR_INVALID, "a3_detect_batch: with a rectification set the frames must have the size of its src (a3_set_rectification)");
     b.fmt = fmt; b.W = width; b.H = height; b.n = n_frames; b.out_cap = out_cap;
     b.want_pose = want_pose; b.pose_size_mm = size_mm; b.pose_has_intr = intr != nullptr;
     if (intr) b.pose_intr = *intr;
@@ -1504,6 +1521,14 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
     b.row_stride = row_stride; b.frame_stride = frame_stride;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &b.row_stride, &b.frame_stride, n_frames, &b.pixels);
     if (rc != A3_OK) return rc;
+    if (ctx->rect_on) {   // from here on the batch is an A3_FMT_L8 device batch of the view's size whose frames are the plane
+        b.rect = true; b.rect_r = ctx->rect;
+        b.rect_src = b.pixels; b.rect_fmt = fmt; b.rect_row = b.row_stride; b.rect_frame = b.frame_stride;
+        const size_t dw = b.rect_r.dst.image_width, dh = b.rect_r.dst.image_height;
+        A3_HIP(ctx->rect_plane.ensure(dw * dh * n_frames));
+        b.pixels = ctx->rect_plane.as<uint8_t>(); b.fmt = A3_FMT_L8; b.W = (uint32_t)dw; b.H = (uint32_t)dh;
+        b.row_stride = dw; b.frame_stride = dw * dh;
+    }
     if (b.board || b.charuco) { if (int urc = upload_board(ctx)) return urc; }
     if (b.charuco) { if (int urc = upload_charuco(ctx)) return urc; }
     ctx->force_host_plan = false;
@@ -1571,7 +1596,8 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
     ctx->gates_declared = false;
     ctx->batch_mode = batch_mode_of(ctx);
     const bool bursts = ctx->batch_mode == 0 && g_overlap_force.load(std::memory_order_relaxed) <= 0 && g_hold_rests && b.profiling < 2;
-    if (bursts && gated && device_plan_capacity(ctx, n_frames, width, height) != 0) {
+    // (the plan is the BATCH's: with a rectification set its frames have the view's size b.W x b.H, not the call's width x height)
+    if (bursts && gated && device_plan_capacity(ctx, b.n, b.W, b.H) != 0) {
         if (int erc = enqueue_front(ctx, b, true)) return erc;
         (void)hipStreamQuery(ctx->stream);
         std::lock_guard<std::mutex> lk(g_defer_mu);
@@ -1589,7 +1615,7 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
     if (any_held) {   // the last member: threshold kernel, then the held chains of the others behind it, then this batch's own
         // A last member that needs a host-side plan cannot be split (enqueue_front refuses to hold it): the others are then released
         // ungated, ahead of its whole batch.
-        const bool planned = device_plan_capacity(ctx, n_frames, width, height) != 0;
+        const bool planned = device_plan_capacity(ctx, b.n, b.W, b.H) != 0;
         if (planned) { if (int erc = enqueue_front(ctx, b, true)) return erc; }
         uint32_t released = 0;
         {
@@ -2596,19 +2622,6 @@ void a3_default_rectify(a3_rectify* r, const a3_intrinsics* src, const a3_distor
     r->rotation[0] = r->rotation[4] = r->rotation[8] = 1.0f;
 }
 
-static int check_rectify_image(a3_ctx* ctx, const a3_intrinsics& k, size_t bpp, size_t row_stride, size_t frame_stride) {
-    if (k.image_width == 0 || k.image_height == 0 || k.image_width > 65535 || k.image_height > 65535 ||
-        (uint64_t)k.image_width * k.image_height >= (1ull << 30))
-        return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: an image size of 0, above 65535 or of 2^30 pixels and more");
-    if (row_stride < (size_t)k.image_width * bpp) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: row stride smaller than a row");
-    if (frame_stride / k.image_height < row_stride) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: frame stride smaller than a frame");
-    const float v[4] = {k.focal_x, k.focal_y, k.principal_x, k.principal_y};
-    for (float x : v)
-        if (!std::isfinite(x)) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: an intrinsic is not finite");
-    if (!(k.focal_x > 0.0f) || !(k.focal_y > 0.0f)) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: focal lengths must be > 0");
-    return A3_OK;
-}
-
 int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, size_t src_row_stride, size_t src_frame_stride, uint32_t n_frames,
                       const a3_rectify* r, void* dst, int dst_memory, size_t dst_row_stride, size_t dst_frame_stride, a3_rectify_info* info) {
     if (!ctx) return A3_ERR_INVALID;
@@ -2620,19 +2633,8 @@ int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, siz
     if ((src_memory != A3_MEM_HOST && src_memory != A3_MEM_DEVICE) || (dst_memory != A3_MEM_HOST && dst_memory != A3_MEM_DEVICE))
         return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: memory must be A3_MEM_HOST or A3_MEM_DEVICE");
     const size_t bpp = fmt == A3_FMT_RGB8 ? 3 : (fmt == A3_FMT_L8 ? 1 : 4);
-    if (int rc = check_rectify_image(ctx, r->src, bpp, src_row_stride, src_frame_stride)) return rc;
-    if (int rc = check_rectify_image(ctx, r->dst, bpp, dst_row_stride, dst_frame_stride)) return rc;
-    if (r->reserved[0] || r->reserved[1] || r->reserved[2]) return fail(ctx, A3_ERR_INVALID, "a3_rectify.reserved must be 0");
+    if (const char* m = check_rectify(false, *r, bpp, src_row_stride, src_frame_stride, dst_row_stride, dst_frame_stride)) return fail(ctx, A3_ERR_INVALID, m);
     const a3_distortion& d = r->distortion;
-    if (d.model != A3_DIST_NONE && d.model != A3_DIST_RATIONAL && d.model != A3_DIST_FISHEYE)
-        return fail(ctx, A3_ERR_INVALID, "a3_rectify.distortion.model: unknown model");
-    if (d.model != A3_DIST_NONE) {
-        if (int rc = check_distortion_coefficients(ctx, d, "a3_rectify.distortion: a coefficient is not finite",
-                                                   "a3_rectify.distortion: model A3_DIST_FISHEYE reads k1 k2 k3 k4; p1 p2 k5 k6 must be 0"))
-            return rc;
-    }
-    for (float v : r->rotation)
-        if (!std::isfinite(v)) return fail(ctx, A3_ERR_INVALID, "a3_rectify.rotation: an entry is not finite");
 
     const uint32_t sw = r->src.image_width, sh = r->src.image_height, dw = r->dst.image_width, dh = r->dst.image_height;
     A3_HIP(hipSetDevice(ctx->device));
@@ -2671,6 +2673,24 @@ int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, siz
         info->tiles = tx * ty;
         info->path_tiles[d.model == A3_DIST_FISHEYE ? 1 : 0] = info->tiles;   // path 0: the rational map (and no lens), path 1: the fisheye map
     }
+    return A3_OK;
+}
+
+int a3_set_rectification(a3_ctx* ctx, const a3_rectify* r) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (ctx->busy()) return fail(ctx, A3_ERR_INVALID, "a3_set_rectification: a submitted batch has not been collected");
+    if (!r) { ctx->rect_on = false; ctx->rect = a3_rectify{}; return A3_OK; }   // NULL: off
+    const size_t sw = r->src.image_width, sh = r->src.image_height, dw = r->dst.image_width, dh = r->dst.image_height;
+    if (const char* m = check_rectify(true, *r, 1, sw, sw * sh, dw, dw * dh)) return fail(ctx, A3_ERR_INVALID, m);
+    ctx->rect = *r;
+    ctx->rect_on = true;
+    return A3_OK;
+}
+
+int a3_get_rectification(const a3_ctx* ctx, a3_rectify* r, int* enabled) {
+    if (!ctx || !r || !enabled) return A3_ERR_INVALID;
+    *r = ctx->rect;
+    *enabled = ctx->rect_on ? 1 : 0;
     return A3_OK;
 }
 

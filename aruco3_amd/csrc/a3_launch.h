@@ -236,6 +236,16 @@ struct RectifyLaunch {
     uint8_t* dst = nullptr; size_t dst_row = 0, dst_frame = 0;
 };
 hipError_t launch_rectify(hipStream_t st, const RectifyLaunch& r);
+// The grey form (a3_set_rectification): the same map, taps and blend, then one byte per pixel -- luma_of the rectified pixel's rounded
+// bytes in fmt's channel order (A3_FMT_L8: the byte), which is what every sampler of the tree makes of the rectified colour frame.
+// src: device memory, n_frames frames of r->src's size in format fmt (an A3_FMT_*); grey: device memory, n_frames planes of r->dst's
+// size, tightly packed (row stride = r->dst.image_width), every byte of which is written and nothing else.  The caller has checked
+// r (a3_rectify_check.h) and every size and stride.
+struct RectifyGreyLaunch {
+    const uint8_t* src = nullptr; size_t src_row = 0, src_frame = 0; uint32_t n_frames = 0; int fmt = 0; const a3_rectify* r = nullptr;
+    uint8_t* grey = nullptr;
+};
+hipError_t launch_rectify_grey(hipStream_t st, const RectifyGreyLaunch& r);
 struct SynthLaunch {
     const a3_synth_frame* frames = nullptr; uint32_t n_frames = 0; const a3_synth_marker* markers = nullptr; uint32_t W = 0, H = 0; int paper = 0;
     float black = 0.0f, white = 0.0f; int supersample = 0; uint8_t* out = nullptr; size_t row_stride = 0, frame_stride = 0;

@@ -14,6 +14,10 @@
 // starts at column min(x0, sw - 2): in the last column x1 = x0 and the pair's second pixel serves both taps.  A one-column source is
 // read pixel by pixel.  Pixels that see nothing read the pair at (0, 0) and select `fill`; a wave none of whose pixels sees anything
 // loads nothing.
+// The grey form (a3_set_rectification, launch_rectify_grey) is the same kernel with another last step: per pixel the blended bytes go
+// through luma_of in the source format's channel order and ONE byte is kept, so a lane's kRun pixels are one dword, a wave's row
+// piece 256 contiguous bytes, and the two store rules above hold unchanged.  RGBA8 and BGRA8 are the same work in the pixel form and
+// different work here, so the grey form is instantiated per format; the pixel-form instantiations compile as before.
 #include <algorithm>
 #include <cstring>
 
@@ -90,8 +94,16 @@ template <int BPP> __device__ inline uint64_t load_single(const uint8_t* q) {
     return t | (t << (8 * BPP));
 }
 
-template <int BPP, int MODEL>
+// GREY: kPixelForm -- the output pixel in the input's format -- or the A3_FMT_* of the source, the grey form: the same map, taps and
+// blend, then one byte per pixel, luma_of the pixel's rounded output bytes in that format's channel order (L8: the byte; alpha is never
+// blended).  dst is then a plane of dst_row = dw, and a lane's kRun pixels are one dword.
+constexpr int kPixelForm = -1;
+
+template <int BPP, int MODEL, int GREY = kPixelForm>
 __global__ __launch_bounds__(256) void k_rectify(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const RectifyParams p) {
+    constexpr bool grey = GREY != kPixelForm;
+    constexpr int OBPP = grey ? 1 : BPP;   // bytes of an output pixel
+    static_assert(!grey || BPP == (GREY == A3_FMT_RGB8 ? 3 : (GREY == A3_FMT_L8 ? 1 : 4)), "the grey form's BPP is its format's");
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t i = blockIdx.y * kTileH + wave, j0 = blockIdx.x * kTileW + lane * kRun;
     if (i >= p.dh || j0 >= p.dw) return;
@@ -122,8 +134,8 @@ __global__ __launch_bounds__(256) void k_rectify(const uint8_t* __restrict__ src
     const uint32_t f0 = blockIdx.z * kChunk, f1 = min(f0 + (uint32_t)kChunk, p.n_frames);
     for (uint32_t f = f0; f < f1; f++) {
         const uint8_t* s = src + (unsigned long long)f * p.src_frame;
-        uint8_t* d = dst + (unsigned long long)f * p.dst_frame + (unsigned long long)i * p.dst_row + (unsigned long long)j0 * BPP;
-        uint32_t w[BPP] = {};   // the lane's kRun * BPP output bytes
+        uint8_t* d = dst + (unsigned long long)f * p.dst_frame + (unsigned long long)i * p.dst_row + (unsigned long long)j0 * OBPP;
+        uint32_t w[OBPP] = {};   // the lane's kRun * OBPP output bytes
         if (wave_sees) {
             uint64_t top[kRun], bot[kRun];
 #pragma unroll
@@ -137,29 +149,36 @@ __global__ __launch_bounds__(256) void k_rectify(const uint8_t* __restrict__ src
             for (int q = 0; q < kRun; q++) {
                 const int sh0 = (flags[q] & kTapSecond) ? 8 * BPP : 0;
                 const float bx = 1.0f - ax[q], by = 1.0f - ay[q];
+                uint32_t ch[3] = {};   // (the grey form: the pixel's colour bytes)
 #pragma unroll
-                for (int c = 0; c < BPP; c++) {
+                for (int c = 0; c < (grey && BPP == 4 ? 3 : BPP); c++) {
                     const float i00 = (float)((uint32_t)(top[q] >> (sh0 + 8 * c)) & 0xFFu), i01 = (float)((uint32_t)(top[q] >> (8 * (BPP + c))) & 0xFFu);
                     const float i10 = (float)((uint32_t)(bot[q] >> (sh0 + 8 * c)) & 0xFFu), i11 = (float)((uint32_t)(bot[q] >> (8 * (BPP + c))) & 0xFFu);
                     const float val = by*(bx*i00 + ax[q]*i01) + ay[q]*(bx*i10 + ax[q]*i11);
                     const uint32_t out = (flags[q] & kTapInside) ? (uint32_t)fminf(floorf(val + 0.5f), 255.0f) : p.fill;
-                    const int byte = q * BPP + c;
-                    w[byte >> 2] |= out << (8 * (byte & 3));
+                    if constexpr (grey) {
+                        ch[c] = out;
+                    } else {
+                        const int byte = q * BPP + c;
+                        w[byte >> 2] |= out << (8 * (byte & 3));
+                    }
                 }
+                if constexpr (grey)
+                    w[0] |= (BPP == 1 ? ch[0] : (GREY == A3_FMT_BGRA8 ? luma_of(ch[2], ch[1], ch[0]) : luma_of(ch[0], ch[1], ch[2]))) << (8 * q);
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < BPP; k++) w[k] = p.fill * 0x01010101u;
+            for (int k = 0; k < OBPP; k++) w[k] = (grey && BPP != 1 ? luma_of(p.fill, p.fill, p.fill) : p.fill) * 0x01010101u;
         }
         if (run == (uint32_t)kRun && (reinterpret_cast<uintptr_t>(d) & 3u) == 0) {
-            Words<BPP> o;
+            Words<OBPP> o;
 #pragma unroll
-            for (int k = 0; k < BPP; k++) o.v[k] = w[k];
-            *reinterpret_cast<Words<BPP>*>(d) = o;   // one 4- / 12- / 16-byte store
+            for (int k = 0; k < OBPP; k++) o.v[k] = w[k];
+            *reinterpret_cast<Words<OBPP>*>(d) = o;   // one 4- / 12- / 16-byte store
         } else {   // the end of a row, or a destination row that is not dword-aligned
 #pragma unroll
-            for (int byte = 0; byte < kRun * BPP; byte++)
-                if ((uint32_t)byte < run * BPP) d[byte] = (uint8_t)(w[byte >> 2] >> (8 * (byte & 3)));
+            for (int byte = 0; byte < kRun * OBPP; byte++)
+                if ((uint32_t)byte < run * OBPP) d[byte] = (uint8_t)(w[byte >> 2] >> (8 * (byte & 3)));
         }
     }
 }
@@ -170,10 +189,9 @@ void rectify_grid(uint32_t dw, uint32_t dh, uint32_t n_frames, uint32_t* tiles_x
     *chunks = (n_frames + kChunk - 1) / kChunk;
 }
 
-hipError_t launch_rectify(hipStream_t st, const RectifyLaunch& l) {
-    const a3_rectify& r = *l.r;
-    const uint8_t* const src = l.src; uint8_t* const dst = l.dst; const uint32_t n_frames = l.n_frames; const int bpp = l.bpp;
-    const bool fisheye = r.distortion.model == A3_DIST_FISHEYE, lens = fisheye || r.distortion.model == A3_DIST_RATIONAL;
+// the kernel's parameters for r on frames of these strides (lens coefficients taken as 0 with A3_DIST_NONE)
+static RectifyParams rectify_params(const a3_rectify& r, uint32_t n_frames, size_t src_row, size_t src_frame, size_t dst_row, size_t dst_frame) {
+    const bool lens = r.distortion.model == A3_DIST_FISHEYE || r.distortion.model == A3_DIST_RATIONAL;
     const a3_distortion& k = r.distortion;
     RectifyParams p{};
     p.dfx = r.dst.focal_x; p.dfy = r.dst.focal_y; p.dcx = r.dst.principal_x; p.dcy = r.dst.principal_y;
@@ -183,9 +201,17 @@ hipError_t launch_rectify(hipStream_t st, const RectifyLaunch& l) {
     p.k3 = lens ? k.k3 : 0.0f; p.k4 = lens ? k.k4 : 0.0f; p.k5 = lens ? k.k5 : 0.0f; p.k6 = lens ? k.k6 : 0.0f;
     p.sw = r.src.image_width; p.sh = r.src.image_height; p.dw = r.dst.image_width; p.dh = r.dst.image_height;
     p.n_frames = n_frames; p.fill = r.fill;
-    p.src_row = l.src_row; p.src_frame = l.src_frame; p.dst_row = l.dst_row; p.dst_frame = l.dst_frame;
+    p.src_row = src_row; p.src_frame = src_frame; p.dst_row = dst_row; p.dst_frame = dst_frame;
+    return p;
+}
+
+hipError_t launch_rectify(hipStream_t st, const RectifyLaunch& l) {
+    const a3_rectify& r = *l.r;
+    const uint8_t* const src = l.src; uint8_t* const dst = l.dst; const int bpp = l.bpp;
+    const bool fisheye = r.distortion.model == A3_DIST_FISHEYE;
+    const RectifyParams p = rectify_params(r, l.n_frames, l.src_row, l.src_frame, l.dst_row, l.dst_frame);
     uint32_t tx, ty, tz;
-    rectify_grid(p.dw, p.dh, n_frames, &tx, &ty, &tz);
+    rectify_grid(p.dw, p.dh, l.n_frames, &tx, &ty, &tz);
     const dim3 grid(tx, ty, tz), block(WAVE * kTileH);
     if (fisheye) {   // (p1 p2 k5 k6 are 0 there: a3_rectify_frames checked)
         if (bpp == 1) hipLaunchKernelGGL((k_rectify<1, A3_DIST_FISHEYE>), grid, block, 0, st, src, dst, p);
@@ -196,6 +222,25 @@ hipError_t launch_rectify(hipStream_t st, const RectifyLaunch& l) {
         else if (bpp == 3) hipLaunchKernelGGL((k_rectify<3, A3_DIST_RATIONAL>), grid, block, 0, st, src, dst, p);
         else hipLaunchKernelGGL((k_rectify<4, A3_DIST_RATIONAL>), grid, block, 0, st, src, dst, p);
     }
+    return hipGetLastError();
+}
+
+template <int MODEL> static void launch_grey_form(hipStream_t st, dim3 grid, dim3 block, int fmt, const uint8_t* src, uint8_t* grey, const RectifyParams& p) {
+    if (fmt == A3_FMT_L8) hipLaunchKernelGGL((k_rectify<1, MODEL, A3_FMT_L8>), grid, block, 0, st, src, grey, p);
+    else if (fmt == A3_FMT_RGB8) hipLaunchKernelGGL((k_rectify<3, MODEL, A3_FMT_RGB8>), grid, block, 0, st, src, grey, p);
+    else if (fmt == A3_FMT_RGBA8) hipLaunchKernelGGL((k_rectify<4, MODEL, A3_FMT_RGBA8>), grid, block, 0, st, src, grey, p);
+    else hipLaunchKernelGGL((k_rectify<4, MODEL, A3_FMT_BGRA8>), grid, block, 0, st, src, grey, p);
+}
+
+hipError_t launch_rectify_grey(hipStream_t st, const RectifyGreyLaunch& l) {
+    const a3_rectify& r = *l.r;
+    const size_t dw = r.dst.image_width, dh = r.dst.image_height;
+    const RectifyParams p = rectify_params(r, l.n_frames, l.src_row, l.src_frame, dw, dw * dh);
+    uint32_t tx, ty, tz;
+    rectify_grid(p.dw, p.dh, l.n_frames, &tx, &ty, &tz);
+    const dim3 grid(tx, ty, tz), block(WAVE * kTileH);
+    if (r.distortion.model == A3_DIST_FISHEYE) launch_grey_form<A3_DIST_FISHEYE>(st, grid, block, l.fmt, l.src, l.grey, p);
+    else launch_grey_form<A3_DIST_RATIONAL>(st, grid, block, l.fmt, l.src, l.grey, p);
     return hipGetLastError();
 }
 

@@ -16,15 +16,8 @@ _ctxs = {}   # one context per device
 _ctx_lock = threading.Lock()
 
 
-def rectify_frames(frames, intrinsics: CameraIntrinsics, new_intrinsics: CameraIntrinsics = None, rotation=None, fill: int = 0):
-    """frames: H x W, H x W x C or N x H x W x C uint8 (C 1, 3 or 4), a numpy array or a torch tensor, of `intrinsics`' size.
-    intrinsics: the camera (its `distortion` may be None); new_intrinsics: the rectified view and the output size (default: the same
-    focal lengths, principal point and size, no lens); rotation: 3 x 3, camera -> rectified view (default: the identity); fill: the
-    value of every byte of a pixel that sees nothing.
-    -> N x H' x W' x C uint8: a CUDA tensor for a CUDA tensor (no host copy), else a numpy array."""
-    ptr, mem, fmt, w, h, row, frame, n, keep = _as_frames(frames)
-    if (w, h) != (int(intrinsics.image_width), int(intrinsics.image_height)):
-        raise ValueError(f"frames are {w} x {h}, the intrinsics say {intrinsics.image_width} x {intrinsics.image_height}")
+def rectify_rec(intrinsics: CameraIntrinsics, new_intrinsics: CameraIntrinsics = None, rotation=None, fill: int = 0) -> "_lib.RectifyRec":
+    """the a3_rectify of these arguments (rectify_frames states them): what a3_rectify_frames and a3_set_rectification take"""
     new = new_intrinsics if new_intrinsics is not None else intrinsics
     r = _lib.RectifyRec()
     r.src = intrinsics._c()
@@ -36,6 +29,20 @@ def rectify_frames(frames, intrinsics: CameraIntrinsics, new_intrinsics: CameraI
     if not 0 <= int(fill) <= 255:
         raise ValueError("fill must be in 0..255")
     r.fill = int(fill)
+    return r
+
+
+def rectify_frames(frames, intrinsics: CameraIntrinsics, new_intrinsics: CameraIntrinsics = None, rotation=None, fill: int = 0):
+    """frames: H x W, H x W x C or N x H x W x C uint8 (C 1, 3 or 4), a numpy array or a torch tensor, of `intrinsics`' size.
+    intrinsics: the camera (its `distortion` may be None); new_intrinsics: the rectified view and the output size (default: the same
+    focal lengths, principal point and size, no lens); rotation: 3 x 3, camera -> rectified view (default: the identity); fill: the
+    value of every byte of a pixel that sees nothing.
+    -> N x H' x W' x C uint8: a CUDA tensor for a CUDA tensor (no host copy), else a numpy array."""
+    ptr, mem, fmt, w, h, row, frame, n, keep = _as_frames(frames)
+    if (w, h) != (int(intrinsics.image_width), int(intrinsics.image_height)):
+        raise ValueError(f"frames are {w} x {h}, the intrinsics say {intrinsics.image_width} x {intrinsics.image_height}")
+    new = new_intrinsics if new_intrinsics is not None else intrinsics
+    r = rectify_rec(intrinsics, new_intrinsics, rotation, fill)
     c = row // w
     ow, oh = int(new.image_width), int(new.image_height)
     device = keep.device.index or 0 if mem == _lib.MEM_DEVICE else 0

@@ -1050,6 +1050,31 @@ void a3_default_rectify(a3_rectify *r, const a3_intrinsics *src, const a3_distor
 int  a3_rectify_frames(a3_ctx *ctx, const void *src, int src_memory, int fmt, size_t src_row_stride, size_t src_frame_stride,
                        uint32_t n_frames, const a3_rectify *r, void *dst, int dst_memory, size_t dst_row_stride,
                        size_t dst_frame_stride, a3_rectify_info *info);
+/* Rectification inside the detect calls: a context setting, off by default; a context that never sets it launches exactly what it
+ * launched before.  r != NULL: every later a3_detect_batch* / *_submit of this context sees its frames through r; NULL: off.
+ * With it set, a detect call returns, to the bit, what the caller would get by (1) a3_rectify_frames with r on the call's frames, in
+ * their own format, to a tightly packed output and (2) the same call without the setting on those rectified frames: every marker,
+ * corner, code and order, the refined corners, the ChArUco corners, and the marker, board and ChArUco poses.  The rectified colour
+ * frames are never written: k_rectify's grey form writes one byte per pixel into a plane the context owns, and the whole pipeline
+ * runs on that plane.  Consequences:
+ *   - width, height, fmt, the strides and the memory kind of the call describe the SOURCE frames; a width / height that is not
+ *     r->src.image_width / image_height is A3_ERR_INVALID.  Host-resident frames cross the link once, nothing but results comes back.
+ *   - everything the detector derives from the image size uses r->dst's: the minimum edge length, the minimum corner separation, the
+ *     corner range, and the (w, h) a pose call without intrinsics normalises by.
+ *   - corners are pixels of the rectified view; pose calls take the view's plain intrinsics (r->dst).
+ *   - independent of a3_set_distortion: with both set the corners of a pose batch are undistorted twice.
+ *   - the grey plane detection works on is luma_of (into_luma8's integers) of the rectified pixel's ROUNDED OUTPUT BYTES, in the format's
+ *     channel order (A3_FMT_L8: the byte itself) -- what every sampler (threshold, decode, refinement, ChArUco) makes of the rectified
+ *     colour frame, which is why (1) + (2) above holds; a detector run on that plane as A3_FMT_L8 equals one run on the colour frames.
+ *   - a3_download_grey and the other debug taps report the rectified view, sized r->dst.
+ *   - the setter's argument errors (A3_ERR_INVALID) are those a3_rectify_frames makes for an a3_rectify: sizes, non-finite values, focal
+ *     lengths, reserved, model, the fisheye model's unused coefficients; a3_last_error names a3_set_rectification.
+ *   - the setter is refused (A3_ERR_INVALID) while a submitted batch of the context is in flight; a batch keeps the setting it was
+ *     submitted with, so contexts in rotation (submit / collect) each carry their own, and each owns its plane until its collect.
+ * a3_get_rectification: the setting in force (*enabled 0: none, *r zeroed).  a3_rectify_frames, a3_refine_corners,
+ * a3_interpolate_charuco and the solvers never look at the setting. */
+int  a3_set_rectification(a3_ctx *ctx, const a3_rectify *r);
+int  a3_get_rectification(const a3_ctx *ctx, a3_rectify *r, int *enabled);
 
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);

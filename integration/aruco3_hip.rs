@@ -672,6 +672,8 @@ extern "C" {
     pub fn a3_rectify_frames(ctx: *mut A3Ctx, src: *const c_void, src_memory: c_int, fmt: c_int, src_row_stride: usize, src_frame_stride: usize,
                              n_frames: u32, r: *const A3Rectify, dst: *mut c_void, dst_memory: c_int, dst_row_stride: usize,
                              dst_frame_stride: usize, info: *mut A3RectifyInfo) -> c_int;
+    pub fn a3_set_rectification(ctx: *mut A3Ctx, r: *const A3Rectify) -> c_int;
+    pub fn a3_get_rectification(ctx: *const A3Ctx, r: *mut A3Rectify, enabled: *mut c_int) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
@@ -1132,6 +1134,43 @@ impl Detector {
             [(q[0], q[1]), (q[2], q[3]), (q[4], q[5]), (q[6], q[7])]
         }).collect();
         (det, refined)
+    }
+
+    /// New (additive): `detect` of an image seen through a lens, rectified inside the call (a3_set_rectification): `image` has the
+    /// size of `rect.src`, the Detection is the one `detect` returns for the image a3_rectify_frames makes of it -- corners are pixels
+    /// of `rect.dst`'s view, and the pose solvers take that view's plain intrinsics.  The Python twin is
+    /// `Detector(rectification=...)`; here `Detector` itself gains no field (the setting is handed to the shared context for this call
+    /// only, under its lock, as `detect_refined` hands over its refinement).
+    pub fn detect_rectified(&self, image: DynamicImage, rect: &A3Rectify) -> Detection {
+        let populate = POPULATE.load(Ordering::Relaxed);
+        let slot = slot_for(self);
+        let mut ctx = slot.lock().unwrap();
+        let images = std::slice::from_ref(&image);
+        let p = pack(images, &mut ctx.staging);
+        ctx.check(unsafe { a3_set_debug_taps(ctx.raw, populate as c_int) }, "a3_set_debug_taps");
+        ctx.check(unsafe { a3_set_rectification(ctx.raw, rect) }, "a3_set_rectification");
+        let mut markers = vec![A3Marker::default(); 64];
+        let mut per = vec![0u32; 1];
+        let mut found = 0usize;
+        let rc = loop {
+            let rc = unsafe {
+                a3_detect_batch(ctx.raw, p.bytes as *const c_void, A3_MEM_HOST, p.fmt, p.width, p.height, p.width as usize * p.bpp,
+                                p.width as usize * p.height as usize * p.bpp, 1, markers.as_mut_ptr(), markers.len(), per.as_mut_ptr(),
+                                &mut found)
+            };
+            if rc == A3_ERR_CAPACITY && markers.len() < MAX_MARKERS_PER_FRAME {
+                markers.resize(markers.len() * 4, A3Marker::default());
+                continue;
+            }
+            break rc;
+        };
+        unsafe { a3_set_rectification(ctx.raw, std::ptr::null()) }; // the shared context goes back to the plain detect
+        ctx.check(rc, "a3_detect_batch");
+        let mut det = Detection { grey: None, candidates: vec![], homographies: vec![], markers: markers[..found].iter().map(marker_of).collect() };
+        if populate {   // (the taps report the rectified view)
+            fill_debug_outputs(&ctx, 0, rect.dst.image_width, rect.dst.image_height, self.config.homography_sample_size as u32, &mut det);
+        }
+        det
     }
 
     /// New (additive): `detect` of one image plus the pose of a planar board (OpenCV's estimatePoseBoard), solved on the device
