@@ -27,20 +27,7 @@ namespace {
 // created concurrently from different threads
 thread_local std::string g_create_error;
 
-// Quad candidates kept per frame.  The reference is unbounded (src/aruco.rs:124-166 pushes into a Vec); here the tables start at
-// kMaxCandDefault per frame and a batch that overflows them is re-run with tables twice the size (1024, 2048, 4096, 6144 -- as far as the
-// per-frame ordering + discard_too_near kernel keeps a frame's candidates in LDS, 21 bytes each -- then 12 288 ... through memory), up
-// to kMaxCandLimit = 65 536, where a3_marker.candidate_index (16 bits) ends; beyond that: A3_ERR_LIMIT.
-constexpr uint32_t kMaxCandDefault = 1024, kMaxCandLimit = A3_MAX_CANDIDATES_PER_FRAME;
-static_assert(kMaxCandLimit == 65536, "a3_marker.candidate_index is a uint16_t");
-constexpr uint32_t kMaxContoursDefault = 1u << 20;
-constexpr uint64_t kMaxDartsDefault = 48ull << 20;
-constexpr uint64_t kMaxPointsDefault = 64ull << 20;
-// dart indices and entry slots (at most 32 k above the darts) stay below 2^30: a pending FinState holds a 30-bit slot beside its
-// marker bit (k_contours.hip)
-constexpr uint64_t kHardMaxDarts = (1ull << 30) - (1ull << 16);
-constexpr uint64_t kHardMaxPoints = 3ull << 30;
-constexpr int kResolveItersMax = 16;        // == DeviceCounters::resolve_changed slots
+// (The pool and table limits, the hints a context carries between batches and the device's verdict on a batch: a3_batch_head.h.)
 // debug taps: warped patches kept per batch (one per candidate that reaches the decode stage).  The tap holds a patch for every
 // candidate the batch can have (frames x kMaxCand) up to kPatchCapMax patches (2.4 GB at 49 x 49); a binding that populates
 // Detection.homographies for more than 1024 frames per call splits the call (integration/aruco3_hip.rs does).
@@ -85,7 +72,6 @@ struct Layout {
     template <typename T> hipError_t zero_from(Seg<T> s) const { return hipMemsetAsync(at(s), 0, end - s.off, stream); }   // s and all behind it
 };
 
-struct Chunk { uint32_t first, count; uint64_t darts; uint32_t max_frame_darts; };
 // One batch: the call and every setting it runs with, captured once when it starts (begin_batch) -- a setter called while the batch
 // is in flight applies to the next one -- and what its enqueue decided.  enqueue_front, enqueue_chain, enqueue_back (also when it is
 // deferred), finish_batch and the synchronous re-run read this record, never the context's live settings.
@@ -122,7 +108,7 @@ struct Batch {
     uint32_t max_cand = 0, patch_cap = 0, marker_cap = 0, guess = 0;
     // enqueue_chain
     bool active = false, device_plan = false;
-    size_t n_chunks = 0, ctr_bytes = 0;
+    size_t n_chunks = 0;
     Readback rb;                 // where the results lie in the pinned staging buffer (ensure_back_buffers)
     uint64_t chunk0_darts = 0;
     int rounds_max = 0;
@@ -161,12 +147,8 @@ struct a3_ctx {
     uint32_t n_codes = 0, mark_size = 0;
     std::string err;
 
-    uint64_t max_darts = kMaxDartsDefault, max_points = kMaxPointsDefault;
-    uint32_t max_contours = kMaxContoursDefault;
-    uint32_t max_cand = kMaxCandDefault;   // candidate slots per frame (grows on overflow, see kMaxCandLimit)
-    // launch-count hints (every pass past convergence is an empty launch of ~5 us): start low, retry the batch with the
-    // maximum if a pass count turns out too small
-    int jump_rounds_hint = 10, resolve_iters_hint = 4;
+    uint64_t max_darts = kMaxDartsDefault;
+    BatchHints hints;   // launch-count hints, the device plan, the pools and tables that grow: what batch_verdict moves (a3_batch_head.h)
     uint32_t dbg_nd = 0, dbg_frames = 0, dbg_chunks = 0;   // a3_debug_kernel_time: shape of the last batch's contour graph
     PixelSrc dbg_src{};
     // a3_debug_inject_candidates (tests only): quads that replace frame 0's candidate list of the next batch, between the contour
@@ -177,13 +159,6 @@ struct a3_ctx {
     Batch batch;                    // the batch in flight (or the last one)
     bool pending_trivial = false;   // a submitted batch with no frames / empty images
     bool busy() const { return batch.active || pending_trivial; }   // a submitted batch has not been collected
-    int resolve_full_ttl = 0;
-    int entry_global_ttl = 0;   // > 0: a recent batch had a frame whose entry list did not fit LDS: use the global doubling rounds
-    // device-side planning: the previous batch of this shape fitted one chunk with plan_darts darts, so this one is enqueued
-    // without reading the dart counts back first (k_plan); an overflow falls back to the host plan once (force_host_plan)
-    bool plan_valid = false, force_host_plan = false;
-    uint32_t plan_n = 0, plan_W = 0, plan_H = 0;
-    uint64_t plan_darts = 0;   // > 0: launch the fixpoint passes over all darts too (a recent batch needed them); else only k_resolve_fast
     bool debug_taps = false;   // a3_set_debug_taps: the setting the next batch captures
     bool debug_sample_frames = false;   // a3_debug_sample_frames (tests only): likewise
     uint32_t patch_cap = 0;    // patches the tap of the last tapped batch could hold
@@ -212,11 +187,11 @@ struct a3_ctx {
     DevBuf leader_list, leader_keep, entry_list, es_a, es_b;
     DevBuf contours, cyc_start_off, points;
     DevBuf cands, pre_xy, fin_xy, fin_count, work, outs, proj, patches, cand_big;
-    // one allocation zeroed by one memset per batch and read back with one copy: [scratch 256 B | counters | per_frame | frame_cursor | cand_count]
+    // one allocation zeroed by one memset per batch, its head read back with one copy (zero_layout, a3_batch_head.h)
     DevBuf zero_blk;
     a3_marker* markers_ptr = nullptr;                // the compacted marker list, right behind the read-back head in the zero block
     unsigned long long* frame_darts_ptr = nullptr;   // frame_darts_dev (device plan: kept zero by its reader) or the frame_darts buffer (host plan)
-    unsigned int* scratch_u32 = nullptr; DeviceCounters* counters = nullptr; uint32_t* per_frame = nullptr; uint32_t* frame_cursor = nullptr; uint32_t* cand_count = nullptr;
+    BatchScratch* head = nullptr; DeviceCounters* counters = nullptr; uint32_t* per_frame = nullptr; uint32_t* frame_cursor = nullptr; uint32_t* cand_count = nullptr;
     uint32_t last_marker_total = 0;   // sizes the speculative marker read-back of the next batch
     DevBuf tmp_a, tmp_b, tmp_c, tmp_d;
     DevBuf hsum;                // row sums of the grey plane (u16): the separable threshold path only (windows above 15)
@@ -469,14 +444,15 @@ DecodeStage decode_stage(const a3_ctx* ctx) {
     d.fin_count = ctx->fin_count.as<uint32_t>(); d.work = ctx->work.as<uint32_t>(); d.S = S; d.proj = ctx->proj.p; d.big_scratch = ctx->cand_big.as<float>();
     d.n = ctx->mark_size; d.max_taps = S; d.dict = ctx->dict.as<uint64_t>(); d.n_codes = ctx->n_codes; d.tau = ctx->tau;
     d.filter = ctx->cfg.filter_high_bit_errors; d.wtab = ctx->wtab.as<float>(); d.outs = ctx->outs.p; d.per_frame = ctx->per_frame; d.markers = ctx->markers_ptr;
-    d.work_count = ctx->scratch_u32 + 0; d.marker_total = ctx->scratch_u32 + 1; d.cand_pre_total = ctx->scratch_u32 + 2; d.err_flags = ctx->scratch_u32 + 4;
+    BatchScratch* const head = ctx->head;
+    d.work_count = &head->work_count; d.marker_total = &head->marker_total; d.cand_pre_total = &head->cand_pre_total; d.err_flags = &head->err_flags;
     return d;
 }
 
 // candidates -> markers -> read-back of one batch, on stream `st` (the context's stream, or its decode stream when deferred)
 int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     const float min_corner_separation = (float)std::min(b.W, b.H) * ctx->cfg.min_corner_separation_factor;   // src/aruco.rs:56
-    unsigned int* d_marker_total = ctx->scratch_u32 + 1;
+    unsigned int* d_marker_total = &ctx->head->marker_total;
     if (ctx->inject_armed) {   // (test hook; never set by a caller of the public header)
         ctx->inject_armed = false;
         const uint32_t cnt = (uint32_t)ctx->inject.size();
@@ -536,11 +512,11 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
                                             .intr = intr, .W = b.W, .H = b.H, .out = ctx->charuco_pose_buf.as<a3_charuco_pose>()}));
     }
     if (b.prof >= 2) A3_HIP(hipEventRecord(ctx->ev[3], st));
-    // ---- results: one copy of [scratch | counters | per-frame counts | `guess` markers], then the poses and (taps) the counts ----
+    // ---- results: one copy of [head | `guess` markers], then the poses and (taps) the counts ----
     // (every destination from the batch's layout, a3_readback.h; the board and ChArUco poses: one record per frame, whatever the marker count)
     const Readback& rb = b.rb;
     auto stage = [&](const Span& to, const void* from) { return hipMemcpyAsync(at<uint8_t>(ctx->pinned, to), from, to.bytes, hipMemcpyDeviceToHost, st); };
-    A3_HIP(hipMemcpyAsync(ctx->pinned, ctx->scratch_u32, rb.head.bytes + rb.markers.bytes, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(ctx->pinned, ctx->head, rb.head.bytes + rb.markers.bytes, hipMemcpyDeviceToHost, st));
     if (b.want_pose) A3_HIP(stage(rb.poses, ctx->pose_buf.p));
     if (b.refined) A3_HIP(stage(rb.refined, ctx->refined_buf.p));
     if (b.board) A3_HIP(stage(rb.board, ctx->board_buf.p));
@@ -616,44 +592,7 @@ int flush_held_locked(a3_ctx* ctx, hipEvent_t after, bool by_last_member = false
 }
 
 // ---- what a batch's chain needs before it can be enqueued without allocating ----
-// A batch shaped like the previous one, which fitted one chunk, is planned on the device (no read-back of the dart counts before
-// the contour stage).  -> the dart capacity such a batch is launched with; 0: this batch must be planned by the host.
-uint64_t device_plan_capacity(const a3_ctx* ctx, uint32_t n, uint32_t W, uint32_t H) {
-    if (!(ctx->plan_valid && !ctx->force_host_plan && ctx->plan_n == n && ctx->plan_W == W && ctx->plan_H == H && n <= kMaxChunkFrames)) return 0;
-    const uint64_t cap_d = ctx->plan_darts + ctx->plan_darts / 4 + 65536;
-    return cap_d > ctx->max_darts ? 0 : cap_d;
-}
-// One allocation for everything small: [frame_cursor | cand_count | (device plan: frame_darts) | HEAD | markers], HEAD =
-// [scratch 256 B | counters | per_frame]: what the host reads back ahead of the markers.
-struct ZeroLayout { size_t ctr_bytes, head_bytes, head_off, total; };
-ZeroLayout zero_layout(size_t n_chunks, uint32_t chunk_frames, uint32_t n, uint32_t marker_cap) {
-    ZeroLayout z;
-    z.ctr_bytes = sizeof(DeviceCounters) * n_chunks;
-    z.head_bytes = (256 + z.ctr_bytes + (size_t)n * 4 + 7) & ~(size_t)7;
-    const size_t fd_off = ((size_t)chunk_frames * 4 + (size_t)n * 4 + 15) & ~(size_t)15;
-    z.head_off = (fd_off + 255) & ~(size_t)255;
-    z.total = z.head_off + z.head_bytes + (size_t)marker_cap * sizeof(a3_marker);
-    return z;
-}
-uint32_t marker_cap_of(const a3_ctx* ctx, uint32_t n, size_t out_cap) {
-    return (uint32_t)std::min<size_t>(std::max<size_t>(out_cap, 1), (size_t)n * ctx->max_cand);
-}
-uint32_t marker_guess_of(const a3_ctx* ctx, uint32_t marker_cap) {
-    return (uint32_t)std::min<size_t>(marker_cap, (size_t)ctx->last_marker_total + ctx->last_marker_total / 4 + 64);
-}
-// a single-chunk batch is followed by device-planned ones sized darts * 1.25 + 64k: the pool is allocated for that at once
-uint64_t pool_darts_of(const a3_ctx* ctx, uint64_t max_chunk_darts, size_t n_chunks) {
-    uint64_t pool_darts = std::max<uint64_t>(max_chunk_darts, 1);
-    if (n_chunks == 1) {
-        pool_darts = std::min<uint64_t>(std::max<uint64_t>(ctx->max_darts, pool_darts), pool_darts + pool_darts / 2 + 131072);
-        // in steps of an eighth of an octave: a stream of batches whose graphs differ by a percent or two (consecutive batches of one
-        // camera) must not re-allocate the pool -- a dozen hipFree + hipMalloc in the middle of a batch, ~2 ms -- at every new maximum
-        uint64_t step = 1ull << 17;
-        while (step * 16 < pool_darts) step <<= 1;
-        pool_darts = std::min<uint64_t>((pool_darts + step - 1) / step * step, std::max<uint64_t>(kHardMaxDarts, pool_darts));
-    }
-    return pool_darts;
-}
+// (device_plan_capacity, zero_layout, marker_cap_of, marker_guess_of, pool_darts_of: a3_batch_head.h)
 // The second half's buffers: poses, refined corners, board poses, undistorted corners, pinned staging for the read-back head and `guess` markers (+ poses
 // ...; a longer list is fetched by finish_batch after growing it), pinned staging for the tap counts.
 int ensure_back_buffers(a3_ctx* ctx, Batch& b, size_t head_bytes) {
@@ -693,11 +632,11 @@ int ensure_chain_buffers(a3_ctx* ctx, hipStream_t st, Batch& b, uint64_t cap_d) 
         A3_HIP(hipMemsetAsync(ctx->frame_darts_dev.p, 0, ctx->frame_darts_dev.cap, st));
     }
     A3_HIP(ctx->frame_base.ensure((size_t)(n + 1) * 4));
-    if (int rc = ensure_dart_pool(ctx, pool_darts_of(ctx, cap_d, 1))) return rc;
+    if (int rc = ensure_dart_pool(ctx, pool_darts_of(ctx->max_darts, cap_d, 1))) return rc;
     A3_HIP(ctx->pix_base.ensure((size_t)n * b.W * b.H * 4));
-    A3_HIP(ctx->contours.ensure((size_t)ctx->max_contours * sizeof(ContourRec)));
-    A3_HIP(ctx->cyc_start_off.ensure((size_t)ctx->max_contours * 4));
-    A3_HIP(ctx->points.ensure(ctx->max_points * 4));
+    A3_HIP(ctx->contours.ensure((size_t)ctx->hints.max_contours * sizeof(ContourRec)));
+    A3_HIP(ctx->cyc_start_off.ensure((size_t)ctx->hints.max_contours * 4));
+    A3_HIP(ctx->points.ensure(ctx->hints.max_points * 4));
     return ensure_back_buffers(ctx, b, z.head_bytes);
 }
 
@@ -713,7 +652,7 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     hipStream_t st = ctx->stream;
     const uint32_t n = b.n, W = b.W, H = b.H;
     const size_t npx = (size_t)W * H;
-    const uint32_t kMaxCand = ctx->max_cand;
+    const uint32_t kMaxCand = ctx->hints.max_cand;
     // the grey plane is materialised only for readers outside the fused path: Detection.grey (debug taps) and the generic
     // threshold kernels (windows above 15); the decode stage otherwise samples the caller's frames directly
     const bool big_window = threshold_writes_grey_plane(ctx->cfg.threshold_window);
@@ -734,8 +673,8 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     A3_HIP(ctx->outs.ensure((size_t)n * kMaxCand * decode_out_bytes()));
     A3_HIP(ctx->proj.ensure((size_t)n * kMaxCand * proj_rec_bytes()));
     b.max_cand = kMaxCand;
-    b.marker_cap = marker_cap_of(ctx, n, b.out_cap);
-    b.guess = marker_guess_of(ctx, b.marker_cap);
+    b.marker_cap = marker_cap_of(kMaxCand, n, b.out_cap);
+    b.guess = marker_guess_of(ctx->last_marker_total, b.marker_cap);
     b.patch_cap = (uint32_t)std::min<uint64_t>(kPatchCapMax, std::max<uint64_t>(kPatchCapMin, (uint64_t)n * kMaxCand));
     if (b.taps) { A3_HIP(ctx->patches.ensure((size_t)b.patch_cap * ctx->cfg.homography_sample_size * ctx->cfg.homography_sample_size)); ctx->patch_cap = b.patch_cap; }
     ctx->W = W; ctx->H = H; ctx->frames = n;
@@ -754,7 +693,7 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     if (b.prof) A3_HIP(hipEventRecord(ctx->ev[1], st));
     if (!held) return A3_OK;
     A3_HIP(hipEventRecord(ctx->ev_k1_done, st));   // (held chains of a burst wait for the last member's)
-    const uint64_t cap_d = device_plan_capacity(ctx, n, W, H);
+    const uint64_t cap_d = device_plan_capacity(ctx->hints, ctx->max_darts, n, W, H);
     if (cap_d == 0) return fail(ctx, A3_ERR_INTERNAL, "a chain was held back for a batch that needs a host-side plan");
     return ensure_chain_buffers(ctx, st, b, cap_d);
 }
@@ -767,13 +706,13 @@ ContourChunk contour_chunk(const a3_ctx* ctx) {
     c.bits = ctx->bin.as<uint64_t>(); c.tile_darts = ctx->tile_darts.as<uint32_t>(); c.pix_base = ctx->pix_base.as<uint32_t>();
     c.d_rec = ctx->d_xy.as<uint64_t>(); c.d_succ = ctx->d_succ.as<uint32_t>();
     c.entry_list = ctx->entry_list.as<uint32_t>(); c.es_a = ctx->es_a.p; c.es_b = ctx->es_b.p; c.fin = ctx->fin.p;
-    c.leader_count = ctx->scratch_u32 + 16; c.entry_count = ctx->scratch_u32 + 32;   // [16..31], [32..47]
+    c.leader_count = ctx->head->leader_count; c.entry_count = ctx->head->entry_count;
     c.leader_list = ctx->leader_list.as<uint32_t>(); c.leader_keep = ctx->leader_keep.as<uint32_t>();
     c.t_cur = ctx->t_cur.as<uint64_t>(); c.t_next = ctx->t_next.as<uint64_t>();
     c.contours = ctx->contours.as<ContourRec>(); c.cyc_start_off = ctx->cyc_start_off.as<uint32_t>(); c.points = ctx->points.as<uint32_t>();
-    c.max_contours = ctx->max_contours; c.max_points = ctx->max_points;
+    c.max_contours = ctx->hints.max_contours; c.max_points = ctx->hints.max_points;
     c.cands = ctx->cands.as<CandRec>(); c.cand_count = ctx->cand_count;
-    c.err_flags = ctx->scratch_u32 + 4;   // ([0] work count, [1] marker total: enqueue_back)
+    c.err_flags = &ctx->head->err_flags;
     return c;
 }
 
@@ -810,23 +749,23 @@ int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
 
     // ---- contour graph size per frame -> chunk plan ----
     // A batch shaped like the previous one is planned on the device: no read-back, no idle GPU while the host thinks.
-    const uint64_t cap_d = device_plan_capacity(ctx, n, W, H);
+    const uint64_t cap_d = device_plan_capacity(ctx->hints, ctx->max_darts, n, W, H);
     const bool device_plan = cap_d != 0;
     // The zero block (zero_layout): one memset zeroes it up to the end of HEAD; HEAD and the marker list that follows it come back
     // to the host in one copy.
-    size_t ctr_bytes = 0, head_bytes = 0, head_off = 0;
+    size_t head_bytes = 0, head_off = 0;
     void* zero_p = nullptr; size_t zero_bytes = 0;
     auto layout_zero_block = [&](size_t n_chunks, uint32_t chunk_frames, bool launch) -> hipError_t {
         const ZeroLayout zl = zero_layout(n_chunks, chunk_frames, n, b.marker_cap);
-        ctr_bytes = zl.ctr_bytes; head_bytes = zl.head_bytes; head_off = zl.head_off;
+        head_bytes = zl.head_bytes; head_off = zl.head_off;
         const hipError_t e = ctx->zero_blk.ensure(zl.total);
         if (e != hipSuccess) return e;
         uint8_t* z = ctx->zero_blk.as<uint8_t>();
         ctx->frame_cursor = reinterpret_cast<uint32_t*>(z);
         ctx->cand_count = ctx->frame_cursor + chunk_frames;
-        ctx->scratch_u32 = reinterpret_cast<unsigned int*>(z + head_off);
-        ctx->counters = reinterpret_cast<DeviceCounters*>(z + head_off + 256);
-        ctx->per_frame = reinterpret_cast<uint32_t*>(z + head_off + 256 + ctr_bytes);
+        ctx->head = reinterpret_cast<BatchScratch*>(z + head_off);
+        ctx->counters = reinterpret_cast<DeviceCounters*>(ctx->head + 1);
+        ctx->per_frame = reinterpret_cast<uint32_t*>(ctx->counters + n_chunks);
         ctx->markers_ptr = reinterpret_cast<a3_marker*>(z + head_off + head_bytes);
         zero_p = z; zero_bytes = (head_off + head_bytes + 15) & ~(size_t)15;   // (may run a few bytes into the marker area: not yet written)
         return launch ? launch_zero(st, zero_p, zero_bytes) : hipSuccess;
@@ -845,59 +784,46 @@ int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
         ctx->frame_darts_ptr = ctx->frame_darts.as<unsigned long long>();
         A3_HIP(hipMemsetAsync(ctx->frame_darts.p, 0, (size_t)n * 8, st));
     }
-    // device plan: frame bases and the dart total come out of the same launch sequence (scratch words 8..11, read back with the results)
+    // device plan: frame bases and the dart total come out of the same launch sequence (BatchScratch::plan, read back with the results)
     DartCountLaunch count{.bits = ctx->bin.as<uint64_t>(), .W = (int)W, .H = (int)H, .n_frames = n, .frame_darts = ctx->frame_darts_ptr,
                           .tile_darts = ctx->tile_darts.as<uint32_t>(), .plan_cap = cap_d};
-    if (device_plan) { count.frame_base = ctx->frame_base.as<uint32_t>(); count.plan = ctx->scratch_u32 + 8; count.zero_p = zero_p; count.zero_bytes = zero_bytes; }
+    if (device_plan) { count.frame_base = ctx->frame_base.as<uint32_t>(); count.plan = &ctx->head->plan; count.zero_p = zero_p; count.zero_bytes = zero_bytes; }
     A3_HIP(launch_dart_count(st, count));
-    const uint32_t* n_live = device_plan ? ctx->scratch_u32 + 8 : nullptr;   // written by the plan workgroup of launch_dart_count
+    const uint32_t* n_live = device_plan ? &ctx->head->plan.darts : nullptr;   // written by the plan workgroup of launch_dart_count
     uint32_t max_chunk_frames = n;
     if (!device_plan) {
         if (int rc = ensure_pinned(ctx, std::max<size_t>((size_t)n * 8, 1 << 16))) return rc;
         A3_HIP(hipMemcpyAsync(ctx->pinned, ctx->frame_darts.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
         A3_HIP(wait_stream(st));
         fd.assign((uint64_t*)ctx->pinned, (uint64_t*)ctx->pinned + n);
-        uint64_t biggest = 0;
-        for (uint64_t v : fd) { biggest = std::max(biggest, v); ctx->stats.darts += v; }
-        if (biggest > kHardMaxDarts) return fail(ctx, A3_ERR_LIMIT, "a frame needs more contour-graph nodes than 32-bit indices allow");
-        if (biggest > ctx->max_darts) ctx->max_darts = biggest;  // one frame must fit; grow the pool
-        Chunk c{0, 0, 0, 0};
-        for (uint32_t f = 0; f < n; f++) {
-            if (c.count && (c.darts + fd[f] > ctx->max_darts || c.count >= kMaxChunkFrames)) { chunks.push_back(c); c = Chunk{f, 0, 0, 0}; }
-            c.count++; c.darts += fd[f]; c.max_frame_darts = (uint32_t)std::max<uint64_t>(c.max_frame_darts, fd[f]);
-        }
-        if (c.count) chunks.push_back(c);
-        max_chunk_frames = 0; uint64_t max_chunk_darts = 0;
-        for (auto& c : chunks) { max_chunk_frames = std::max(max_chunk_frames, c.count); max_chunk_darts = std::max(max_chunk_darts, c.darts); }
-        if (int rc = ensure_dart_pool(ctx, pool_darts_of(ctx, max_chunk_darts, chunks.size()))) return rc;
+        chunks.resize(n);
+        const ChunkSplit split = split_chunks(fd.data(), n, ctx->max_darts, kMaxChunkFrames, chunks.data());
+        ctx->stats.darts += split.total_darts;
+        if (split.refused) return fail(ctx, A3_ERR_LIMIT, "a frame needs more contour-graph nodes than 32-bit indices allow");
+        ctx->max_darts = split.max_darts;   // one frame must fit; grow the pool
+        chunks.resize(split.n_chunks);
+        max_chunk_frames = split.max_chunk_frames;
+        if (int rc = ensure_dart_pool(ctx, pool_darts_of(ctx->max_darts, split.max_chunk_darts, chunks.size()))) return rc;
         A3_HIP(ctx->pix_base.ensure((size_t)max_chunk_frames * npx * 4));
         A3_HIP(ctx->frame_base.ensure((size_t)(max_chunk_frames + 1) * 4 * chunks.size()));
         A3_HIP(layout_zero_block(chunks.size(), max_chunk_frames, true));
-        A3_HIP(ctx->contours.ensure((size_t)ctx->max_contours * sizeof(ContourRec)));
-        A3_HIP(ctx->cyc_start_off.ensure((size_t)ctx->max_contours * 4));
-        A3_HIP(ctx->points.ensure(ctx->max_points * 4));
-        // frame bases of every chunk, uploaded once
-        std::vector<uint32_t> bases;
-        for (auto& c : chunks) {
-            uint32_t acc = 0;
-            for (uint32_t i = 0; i < max_chunk_frames + 1; i++) {
-                bases.push_back(acc);
-                if (i < c.count) acc += (uint32_t)fd[c.first + i];
-            }
-        }
-        // the pinned buffer still holds fd; stage the bases behind it
-        if (int rc = ensure_pinned(ctx, (size_t)n * 8 + bases.size() * 4 + (1 << 16))) return rc;
+        A3_HIP(ctx->contours.ensure((size_t)ctx->hints.max_contours * sizeof(ContourRec)));
+        A3_HIP(ctx->cyc_start_off.ensure((size_t)ctx->hints.max_contours * 4));
+        A3_HIP(ctx->points.ensure(ctx->hints.max_points * 4));
+        // frame bases of every chunk, uploaded once, staged behind fd's place in the pinned buffer
+        const size_t stride = max_chunk_frames + 1, n_bases = stride * chunks.size();
+        if (int rc = ensure_pinned(ctx, (size_t)n * 8 + n_bases * 4 + (1 << 16))) return rc;
         uint32_t* h_bases = reinterpret_cast<uint32_t*>((uint8_t*)ctx->pinned + (size_t)n * 8);
-        memcpy(h_bases, bases.data(), bases.size() * 4);
-        A3_HIP(hipMemcpyAsync(ctx->frame_base.p, h_bases, bases.size() * 4, hipMemcpyHostToDevice, st));
+        for (size_t ci = 0; ci < chunks.size(); ci++) chunk_frame_bases(fd.data(), chunks[ci], (uint32_t)stride, h_bases + ci * stride);
+        A3_HIP(hipMemcpyAsync(ctx->frame_base.p, h_bases, n_bases * 4, hipMemcpyHostToDevice, st));
     }
     ctx->stats.chunks = (uint32_t)chunks.size();
 
     // ---- contour stage, chunk by chunk ----
     ContourChunk cc = contour_chunk(ctx);
     cc.n_live = n_live;
-    cc.resolve_iters = ctx->resolve_full_ttl > 0 ? ctx->resolve_iters_hint : 0;
-    cc.inline_resolve_W = ctx->resolve_full_ttl > 0 ? 0 : (int)W;
+    cc.resolve_iters = ctx->hints.resolve_full_ttl > 0 ? ctx->hints.resolve_iters_hint : 0;
+    cc.inline_resolve_W = ctx->hints.resolve_full_ttl > 0 ? 0 : (int)W;
     cc.min_edge_length = min_edge_length;
     cc.eps_factor = ctx->cfg.contour_simplification_epsilon;
     cc.keep_all = b.taps;
@@ -908,27 +834,22 @@ int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
         const uint32_t nd = (uint32_t)c.darts;
         if (nd == 0) continue;
         if (ci > 0) {   // the batch-wide memset covered chunk 0
-            A3_HIP(hipMemsetAsync(cc.leader_count, 0, 4 * 32, st));   // leader + entry counters, adjacent
+            A3_HIP(hipMemsetAsync(cc.leader_count, 0, sizeof(BatchScratch::leader_count) + sizeof(BatchScratch::entry_count), st));
             A3_HIP(hipMemsetAsync(ctx->frame_cursor, 0, (size_t)c.count * 4, st));   // per-frame entry counts
         }
         cc.first_frame = c.first; cc.n_frames = c.count; cc.n_darts = nd;
         cc.frame_base = ctx->frame_base.as<uint32_t>() + ci * (max_chunk_frames + 1);
         cc.ctr = ctx->counters + ci;
         A3_HIP(launch_dart_build(st, cc));
-        int rounds = 1;
-        while ((1ull << rounds) < (uint64_t)c.max_frame_darts && rounds < 31) rounds++;
-        rounds += 1;  // the round that observes "nothing moved"
-        rounds = std::min(rounds, ctx->jump_rounds_hint);
-        // a3_debug_set_jump_rounds: too few rounds on purpose (not for the re-run with all rounds that a short launch asks for)
-        if (const int cap = g_jump_rounds_cap.load(std::memory_order_relaxed); cap > 0 && ctx->jump_rounds_hint < 32) rounds = std::min(rounds, cap);
+        const int rounds = chunk_rounds(c.max_frame_darts, ctx->hints.jump_rounds_hint, g_jump_rounds_cap.load(std::memory_order_relaxed));
         rounds_max = std::max(rounds_max, rounds);
         cc.max_rounds = rounds;
-        cc.frame_entries = ctx->entry_global_ttl > 0 ? nullptr : ctx->frame_cursor;   // per-frame entry counts
+        cc.frame_entries = ctx->hints.entry_global_ttl > 0 ? nullptr : ctx->frame_cursor;   // per-frame entry counts
         // Short borders are finished with inside k_local_contract (kDead) on DENSE graphs only -- noise-like frames, where nine borders
         // in ten die of their length: there it saves a sixth of the contour stage; on clean frames (a dart per hundred pixels, a few
         // dozen borders per frame) it would only cost its bookkeeping.  Results are the same either way.
         const bool dense_graph = (uint64_t)nd * 10u >= (uint64_t)c.count * npx;
-        cc.dead_count = (b.taps || !dense_graph) ? nullptr : ctx->scratch_u32 + 48;   // [48..63]: borders k_local_contract finished with (traced, never listed), 16 shards, all chunks
+        cc.dead_count = (b.taps || !dense_graph) ? nullptr : ctx->head->dead_count;
         cc.phase = 1;   // first half: the doubling rounds inside LDS tiles
         A3_HIP(launch_rank_cycles(st, cc));
         if (rel_mode == 2) { if (int rc = release_waiting()) return rc; }   // waiting decode stages go out behind this k_local_contract
@@ -948,7 +869,7 @@ int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
     ctx->dbg_src = b.src;
     if (int rc = ensure_back_buffers(ctx, b, head_bytes)) return rc;   // (device plan: ensure_chain_buffers did, this is a no-op)
     b.device_plan = device_plan; b.n_chunks = chunks.size(); b.chunk0_darts = chunks.empty() ? 0 : chunks[0].darts;
-    b.ctr_bytes = ctr_bytes; b.rounds_max = rounds_max;
+    b.rounds_max = rounds_max;
     ctx->counts_valid = false;
     // Deferral: only for submitted batches (somebody will submit again or collect), and not while every stage is being timed
     // (the stage times are those of stages that run alone).  The decode stage then waits on the context's decode stream until
@@ -984,7 +905,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     }
     b.active = false;
     hipStream_t st = ctx->stream;
-    const size_t ctr_bytes = b.ctr_bytes, n_chunks = b.n_chunks;
+    const size_t n_chunks = b.n_chunks;
     const uint32_t guess = b.guess, n = b.n;
     uint8_t* hp = (uint8_t*)ctx->pinned;
     Readback rb = b.rb;   // where the results lie behind hp (a3_readback.h)
@@ -994,83 +915,33 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         if (const int rc = ctx->back_rc) { ctx->back_rc = 0; return rc; }   // (released by another context's submit, and that failed)
     }
     A3_HIP(wait_event(ctx->ev[4], st));
-    const unsigned int* hs = reinterpret_cast<const unsigned int*>(hp);
-    const DeviceCounters* hc = reinterpret_cast<const DeviceCounters*>(hp + 256);
-    if (b.device_plan) {
-        if (hs[9]) { ctx->force_host_plan = true; return 1; }   // the graph outgrew the hint: plan on the host this once
-        ctx->stats.darts = hs[8];
-        ctx->dbg_nd = hs[8];
-        ctx->plan_darts = hs[8];
-    } else {
-        ctx->plan_valid = n_chunks == 1;
-        ctx->plan_n = n; ctx->plan_W = b.W; ctx->plan_H = b.H;
-        ctx->plan_darts = n_chunks == 1 ? b.chunk0_darts : 0;
+    // the device's verdict on the batch (a3_batch_head.h): deliver, re-run with the hints it moved, or fail
+    const BatchScratch& hs = *reinterpret_cast<const BatchScratch*>(hp);
+    const DeviceCounters* hc = reinterpret_cast<const DeviceCounters*>(&hs + 1);
+    const size_t slot_bytes = sizeof(CandRec) + 16 + 16 + 4 + decode_out_bytes() + proj_rec_bytes();   // cands, pre_xy, fin_xy, work, outs, proj
+    const Verdict v = batch_verdict(hs, hc, {.n = n, .W = b.W, .H = b.H, .device_plan = b.device_plan, .n_chunks = n_chunks, .chunk0_darts = b.chunk0_darts,
+                                             .rounds_max = b.rounds_max, .out_cap = out_cap, .lds_slots = frame_cand_lds_slots(), .slot_bytes = slot_bytes},
+                                    ctx->hints);
+    if (b.device_plan && !hs.plan.overflow) ctx->stats.darts = ctx->dbg_nd = v.darts;
+    ctx->stats.contours_traced = v.contours_traced; ctx->stats.contours_materialised = v.contours_materialised;
+    ctx->stats.jump_rounds = v.jump_rounds; ctx->stats.resolve_iterations = v.resolve_iterations;
+    if (v.action == Verdict::Fail) return fail(ctx, v.code, v.message);
+    if (v.action == Verdict::GrowCands) {
+        // Every frame of the batch gets the table of the fullest one: what that costs is known before anything is allocated, and a
+        // batch whose tables cannot fit is a limit of this implementation (fewer frames per call cure it), not a HIP failure.
+        const size_t had = ctx->cands.cap + ctx->pre_xy.cap + ctx->fin_xy.cap + ctx->work.cap + ctx->cand_big.cap + ctx->outs.cap + ctx->proj.cap;
+        const size_t want = (size_t)n * v.next_cand * v.slot_bytes;
+        size_t free_b = 0, total_b = 0;
+        if (want > had && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want - had > free_b)
+            return fail(ctx, A3_ERR_LIMIT, "candidate tables of this batch do not fit the device (every frame gets the fullest frame's table): fewer frames per call");
+        ctx->hints.max_cand = v.next_cand;
     }
-    unsigned int flags = hs[4];
-    for (int sh = 0; sh < 16; sh++) ctx->stats.contours_traced += hs[48 + sh];   // borders finished inside k_local_contract (kDead)
-    uint64_t need_points = 0; uint32_t need_contours = 0;
-    bool jump_short = false, resolve_needed = false, entry_overflow = false;
-    for (size_t ci = 0; ci < n_chunks; ci++) {
-        flags |= hc[ci].err_flags;
-        resolve_needed |= hc[ci].resolve_needed != 0;
-        entry_overflow |= hc[ci].entry_overflow != 0;
-        need_points = std::max<uint64_t>(need_points, hc[ci].points);
-        need_contours = std::max(need_contours, hc[ci].contours);
-        ctx->stats.contours_traced += hc[ci].traced;
-        ctx->stats.contours_materialised += hc[ci].contours;
-        for (int r = 0; r < 32; r++) if (hc[ci].jump_changed[r]) ctx->stats.jump_rounds = std::max<uint32_t>(ctx->stats.jump_rounds, r + 1);
-        uint32_t it = hc[ci].resolve_needed ? 1 : 0;  // 0: k_resolve_fast confirmed the natural starts; pass k+1 ran iff pass k moved something
-        for (int r = 0; r < kResolveItersMax - 1; r++) if (hc[ci].resolve_changed[r]) it = r + 2;
-        ctx->stats.resolve_iterations = std::max(ctx->stats.resolve_iterations, it);
-        if (b.rounds_max > 0 && b.rounds_max < 32 && hc[ci].jump_changed[b.rounds_max - 1] != 0) jump_short = true;
-    }
-    if (entry_overflow) { ctx->entry_global_ttl = 64; ctx->jump_rounds_hint = std::max(ctx->jump_rounds_hint, 12); return 1; }     // a frame's entry list outgrew LDS: re-run with the global rounds
-    if (ctx->entry_global_ttl > 0) ctx->entry_global_ttl--;
-    if (jump_short && ctx->jump_rounds_hint < 32) { ctx->jump_rounds_hint = 32; return 1; }             // re-run with all rounds
-    if (resolve_needed) {
-        const bool ran = ctx->resolve_full_ttl > 0;
-        ctx->resolve_full_ttl = 64;        // keep the full passes in the launch sequence for the next batches
-        if (!ran) return 1;                // they were not launched this time: re-run
-    } else if (ctx->resolve_full_ttl > 0) ctx->resolve_full_ttl--;
-    if ((flags & kErrResolve) && ctx->resolve_iters_hint < kResolveItersMax) { ctx->resolve_iters_hint = kResolveItersMax; return 1; }
-    ctx->jump_rounds_hint = std::max(4, std::min(32, (int)ctx->stats.jump_rounds + 2));   // follow the workload, both ways (one round of slack: a short launch costs a re-run)
-    if (flags & (kErrPointPool | kErrContourTable)) {
-        // grow and let the caller loop re-run the batch
-        if (need_points > ctx->max_points) ctx->max_points = std::min<uint64_t>(kHardMaxPoints, std::max(need_points, ctx->max_points * 2));
-        if (need_contours > ctx->max_contours) ctx->max_contours = std::max(need_contours, ctx->max_contours * 2);
-        return 1;  // retry
-    }
-    if (flags & kErrBrokenEvent) return fail(ctx, A3_ERR_INTERNAL, "contour graph: a start event lies on an open chain");
-    if (flags & kErrScatter) return fail(ctx, A3_ERR_INTERNAL, "contour points: a border slot, rank or point index out of range");
-    if (flags & kErrResolve) return fail(ctx, A3_ERR_INTERNAL, "contour start resolution did not converge");
-    if (flags & kErrCandTable) {   // a frame has more quad candidates than its table: twice the table and again
-        // straight to the table that holds the fullest frame (hs[5], from the marker gather): 2048, 4096, 6144 (the last that
-        // k_frame_candidates works in LDS), 12 288, 24 576, 49 152, 65 536
-        const uint32_t lds_slots = frame_cand_lds_slots(), need = std::max(hs[5], ctx->max_cand + 1u);
-        if (need > kMaxCandLimit) return fail(ctx, A3_ERR_LIMIT, "a frame holds more than 65536 quad candidates (A3_MAX_CANDIDATES_PER_FRAME)");
-        uint32_t next = ctx->max_cand;
-        while (next < need) next = next < lds_slots ? std::min(lds_slots, next * 2) : std::min(kMaxCandLimit, next * 2);
-        if ((uint64_t)n * next > 0xFFFFFFFFull) return fail(ctx, A3_ERR_LIMIT, "frames x candidate slots per frame exceeds 2^32: fewer frames per call");
-        {   // Every frame of the batch gets the table of the fullest one: what that costs is known before anything is allocated, and a
-            // batch whose tables cannot fit is a limit of this implementation (fewer frames per call cure it), not a HIP failure.
-            const size_t per_slot = sizeof(CandRec) + 16 + 16 + 4 + (next > lds_slots ? 4 : 0) + decode_out_bytes() + proj_rec_bytes();
-            const size_t had = ctx->cands.cap + ctx->pre_xy.cap + ctx->fin_xy.cap + ctx->work.cap + ctx->cand_big.cap + ctx->outs.cap + ctx->proj.cap;
-            const size_t want = (size_t)n * next * per_slot;
-            size_t free_b = 0, total_b = 0;
-            if (want > had && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want - had > free_b)
-                return fail(ctx, A3_ERR_LIMIT, "candidate tables of this batch do not fit the device (every frame gets the fullest frame's table): fewer frames per call");
-        }
-        ctx->max_cand = next;
-        return 1;
-    }
-    if (flags & kErrMarkerCap) return fail(ctx, A3_ERR_CAPACITY, "out_cap is smaller than the number of markers found");
-    const uint32_t total = hs[1];
-    if (total > out_cap) return fail(ctx, A3_ERR_CAPACITY, "out_cap is smaller than the number of markers found");
-    const uint32_t* hpf = reinterpret_cast<const uint32_t*>(hp + 256 + ctr_bytes);
+    if (v.action != Verdict::Deliver) return 1;   // the caller's loop re-runs the batch
+    const uint32_t total = v.total, n_work = v.n_work, n_pre = v.n_pre;
+    const uint32_t* hpf = reinterpret_cast<const uint32_t*>(hc + n_chunks);
     if (per_frame_count) memcpy(per_frame_count, hpf, (size_t)n * 4);
     uint32_t max_per_frame = 0;   // (read now: the staging buffer may be re-allocated below)
     for (uint32_t f = 0; f < n; f++) max_per_frame = std::max(max_per_frame, hpf[f]);
-    const uint32_t n_work = hs[0], n_pre = hs[2];
     if (b.board) {   // (read now: the staging buffer may be re-allocated below)
         const a3_board_pose* hb = at<a3_board_pose>(hp, rb.board);
         ctx->h_board.assign(hb, hb + n);
@@ -1092,7 +963,6 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         }
         ctx->last_charuco_total = charuco_total;
     }
-    const uint32_t tap_contours = n_chunks ? hc[0].contours : 0u; const uint64_t tap_points = n_chunks ? hc[0].points : 0ull;
     if (total > guess) {   // the guess was short: the staging area grows (the head has been consumed) and the whole list is fetched
         rb = refetch_layout(readback_shape(b, 0), total);
         if (int rc = ensure_pinned(ctx, pinned_bytes(rb))) return rc;
@@ -1126,7 +996,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         const uint32_t* hc32 = reinterpret_cast<const uint32_t*>(ctx->pinned_counts);
         ctx->h_cand_pre.assign(hc32, hc32 + n);
         ctx->h_cand_fin.assign(hc32 + n, hc32 + 2 * (size_t)n);
-        for (auto& v : ctx->h_cand_pre) v = std::min(v, ctx->max_cand);
+        for (auto& v : ctx->h_cand_pre) v = std::min(v, ctx->hints.max_cand);
         ctx->counts_valid = true;
     }
     ctx->last_marker_total = total;
@@ -1137,7 +1007,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     ctx->markers_valid = true; ctx->last_n = n; ctx->last_max_per_frame = max_per_frame;
     ctx->poses_valid = b.want_pose;
     ctx->contours_valid = b.taps && n_chunks == 1;
-    if (ctx->contours_valid) { ctx->tap_contours = tap_contours; ctx->tap_points = tap_points; }
+    if (ctx->contours_valid) { ctx->tap_contours = v.tap_contours; ctx->tap_points = v.tap_points; }
     if (b.prof >= 1) {   // the level in force when the batch was enqueued
         float ms;
         A3_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1])); ctx->prof_ms[A3_STAGE_THRESHOLD] += ms; ctx->prof_n[A3_STAGE_THRESHOLD]++;
@@ -1408,7 +1278,7 @@ int a3_get_stream(const a3_ctx* ctx, void** hip_stream) {
 int a3_set_pool_limits(a3_ctx* ctx, uint64_t max_darts, uint64_t max_points) {
     if (!ctx) return A3_ERR_INVALID;
     if (max_darts) ctx->max_darts = std::min<uint64_t>(max_darts, kHardMaxDarts);
-    if (max_points) ctx->max_points = std::min<uint64_t>(max_points, kHardMaxPoints);
+    if (max_points) ctx->hints.max_points = std::min<uint64_t>(max_points, kHardMaxPoints);
     return A3_OK;
 }
 
@@ -1531,7 +1401,7 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
     }
     if (b.board || b.charuco) { if (int urc = upload_board(ctx)) return urc; }
     if (b.charuco) { if (int urc = upload_charuco(ctx)) return urc; }
-    ctx->force_host_plan = false;
+    ctx->hints.force_host_plan = false;
     ctx->reruns = 0; ctx->released_others = 0;
     return A3_OK;
 }
@@ -1597,7 +1467,7 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
     ctx->batch_mode = batch_mode_of(ctx);
     const bool bursts = ctx->batch_mode == 0 && g_overlap_force.load(std::memory_order_relaxed) <= 0 && g_hold_rests && b.profiling < 2;
     // (the plan is the BATCH's: with a rectification set its frames have the view's size b.W x b.H, not the call's width x height)
-    if (bursts && gated && device_plan_capacity(ctx, b.n, b.W, b.H) != 0) {
+    if (bursts && gated && device_plan_capacity(ctx->hints, ctx->max_darts, b.n, b.W, b.H) != 0) {
         if (int erc = enqueue_front(ctx, b, true)) return erc;
         (void)hipStreamQuery(ctx->stream);
         std::lock_guard<std::mutex> lk(g_defer_mu);
@@ -1615,7 +1485,7 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
     if (any_held) {   // the last member: threshold kernel, then the held chains of the others behind it, then this batch's own
         // A last member that needs a host-side plan cannot be split (enqueue_front refuses to hold it): the others are then released
         // ungated, ahead of its whole batch.
-        const bool planned = device_plan_capacity(ctx, b.n, b.W, b.H) != 0;
+        const bool planned = device_plan_capacity(ctx->hints, ctx->max_darts, b.n, b.W, b.H) != 0;
         if (planned) { if (int erc = enqueue_front(ctx, b, true)) return erc; }
         uint32_t released = 0;
         {
@@ -1707,7 +1577,7 @@ int a3_debug_kernel_time(a3_ctx* ctx, int kernel, int dbg, int reps, float* avg_
     ContourChunk cc = contour_chunk(ctx);
     cc.n_frames = ctx->dbg_frames; cc.n_darts = ctx->dbg_nd; cc.frame_base = ctx->frame_base.as<uint32_t>(); cc.ctr = ctx->counters;
     for (int r = 0; r < reps; r++) {
-        A3_HIP(hipMemsetAsync(cc.leader_count, 0, 4 * 32, st));
+        A3_HIP(hipMemsetAsync(cc.leader_count, 0, sizeof(BatchScratch::leader_count) + sizeof(BatchScratch::entry_count), st));
         A3_HIP(hipEventRecord(e0, st));
         if (kernel == 0) {
             A3_HIP(hipMemsetAsync(ctx->frame_darts.p, 0, (size_t)ctx->frames * 8, st));
@@ -1728,7 +1598,7 @@ int a3_debug_kernel_time(a3_ctx* ctx, int kernel, int dbg, int reps, float* avg_
             }
             // dbg >= 0: k_projection + k_decode, dbg < 0: k_decode alone; |dbg| 1..5 selects the truncated variant (5 and 0: the whole kernel)
             DecodeStage dec = decode_stage(ctx);
-            dec.src = ctx->dbg_src; dec.W = cc.W; dec.H = cc.H; dec.max_cand = ctx->max_cand; dec.few = ctx->frames <= 64u; dec.grid_blocks = 4096;
+            dec.src = ctx->dbg_src; dec.W = cc.W; dec.H = cc.H; dec.max_cand = ctx->hints.max_cand; dec.few = ctx->frames <= 64u; dec.grid_blocks = 4096;
             dec.per_frame = nullptr;
             dec.projection = dbg >= 0; dec.variant = dbg < 0 ? -dbg : dbg;
             A3_HIP(launch_decode(st, dec));
@@ -1877,7 +1747,7 @@ int a3_candidate_count(a3_ctx* ctx, uint32_t frame, uint32_t* n_pre, uint32_t* n
     uint32_t a = 0, b = 0;
     A3_HIP(hipMemcpy(&a, ctx->cand_count + frame, 4, hipMemcpyDeviceToHost));
     A3_HIP(hipMemcpy(&b, ctx->fin_count.as<uint32_t>() + frame, 4, hipMemcpyDeviceToHost));
-    if (n_pre) *n_pre = std::min(a, ctx->max_cand);
+    if (n_pre) *n_pre = std::min(a, ctx->hints.max_cand);
     if (n_final) *n_final = b;
     return A3_OK;
 }
@@ -1890,7 +1760,7 @@ int a3_download_candidates(a3_ctx* ctx, uint32_t frame, int before_discard, uint
     if (cnt > cap_quads) return fail(ctx, A3_ERR_CAPACITY, "cap_quads too small");
     std::vector<uint16_t> tmp((size_t)cnt * 8);
     const DevBuf& src = before_discard ? ctx->pre_xy : ctx->fin_xy;
-    if (cnt) A3_HIP(hipMemcpy(tmp.data(), src.as<uint16_t>() + (size_t)frame * ctx->max_cand * 8, tmp.size() * 2, hipMemcpyDeviceToHost));
+    if (cnt) A3_HIP(hipMemcpy(tmp.data(), src.as<uint16_t>() + (size_t)frame * ctx->hints.max_cand * 8, tmp.size() * 2, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < tmp.size(); i++) dst_xy[i] = tmp[i];
     return A3_OK;
 }
@@ -1910,7 +1780,7 @@ int a3_download_homographies(a3_ctx* ctx, uint32_t frame, uint8_t* dst, uint8_t*
     if (int rcs_ = need_stream(ctx)) return rcs_;
     const uint32_t S = ctx->cfg.homography_sample_size;
     const size_t S2 = (size_t)S * S, rec_bytes = (size_t)b * sizeof(DecodeOutHost);
-    const uint8_t* d_outs = (const uint8_t*)ctx->outs.p + (size_t)frame * ctx->max_cand * sizeof(DecodeOutHost);
+    const uint8_t* d_outs = (const uint8_t*)ctx->outs.p + (size_t)frame * ctx->hints.max_cand * sizeof(DecodeOutHost);
     // One trip: the frame's decode records, and its patches gathered by a kernel into one dense array, land in pinned memory
     // through two copies on the stream and one wait (it was a blocking copy per candidate).
     const size_t flag_off = (rec_bytes + 15) & ~(size_t)15, patch_off = flag_off + 16;
@@ -1963,9 +1833,9 @@ int a3_pack_detections(a3_ctx* ctx, uint32_t first_frame_global, uint32_t max_ma
     }
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
-    // scratch word 3 is the kernel's overflow flag (cannot fire after the host check; kept as the device-side guard)
+    // pack_overflow is the kernel's overflow flag (cannot fire after the host check; kept as the device-side guard)
     A3_HIP(launch_pack_detections(ctx->stream, ctx->markers_ptr, with_poses ? ctx->pose_buf.as<a3_pose>() : nullptr, ctx->per_frame, ctx->last_n,
-                                  first_frame_global, max_markers_per_frame, dst_device, ctx->scratch_u32 + 3));
+                                  first_frame_global, max_markers_per_frame, dst_device, &ctx->head->pack_overflow));
     return A3_OK;
 }
 

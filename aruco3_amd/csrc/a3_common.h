@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/aruco3_hip.h"
+#include "a3_batch_head.h"   // DeviceCounters, the kErr* flags, the scratch words of a batch, kMaxChunkFrames, the shard counts
 
 namespace a3 {
 
@@ -27,8 +28,7 @@ constexpr uint8_t kInfoE = 1u << 4;
 constexpr uint8_t kInfoBroken = 1u << 5;
 
 // per-dart record, one u64: bits 0-15 x, 16-31 y, 32-39 foreground-neighbour mask F of the pixel, 40-47 info byte,
-// 48-63 frame index inside the chunk (chunks hold at most 65536 frames)
-constexpr uint32_t kMaxChunkFrames = 65536u;
+// 48-63 frame index inside the chunk (chunks hold at most kMaxChunkFrames = 65536 frames)
 __host__ __device__ inline uint64_t dart_rec(uint32_t xy, uint32_t F, uint32_t info, uint32_t frame) {
     return (uint64_t)xy | ((uint64_t)(F & 0xFFu) << 32) | ((uint64_t)(info & 0xFFu) << 40) | ((uint64_t)(frame & 0xFFFFu) << 48);
 }
@@ -75,22 +75,5 @@ struct CandRec {
     uint32_t start_key;
     uint16_t xy[8];
 };
-
-struct DeviceCounters {
-    unsigned long long darts;       // per chunk: next free dart
-    unsigned long long points;      // next free point
-    unsigned int contours;          // next free ContourRec
-    unsigned int traced;            // cycles with a start event (stat)
-    unsigned int err_flags;         // bit 0: event dart on a broken chain, bit 1: point pool overflow,
-                                    // bit 2: contour table overflow, bit 3: candidate table overflow
-    unsigned int resolve_needed;    // set by k_resolve_fast: some border's first start event does not fire -> run the fixpoint passes
-    unsigned int jump_changed[32];     // per doubling round: darts whose key changed
-    unsigned int resolve_changed[16];  // per start-resolution pass: cycles whose start moved
-    unsigned int entry_overflow;    // k_entry_frame: a frame has more entries than fit in LDS -> re-run with the global doubling rounds
-    unsigned int pad[1];
-};
-
-constexpr unsigned kErrBrokenEvent = 1u, kErrPointPool = 2u, kErrContourTable = 4u, kErrCandTable = 8u, kErrResolve = 16u, kErrMarkerCap = 32u,
-                   kErrScatter = 64u;   // k_scatter_points / k_cycle_select: a store's index failed its bounds check (nothing was stored)
 
 }  // namespace a3

@@ -31,11 +31,11 @@ hipError_t launch_ring_threshold(hipStream_t st, const ThresholdLaunch& t);
 // tiles], followed (8-byte aligned) by the word masks; launch_dart_count writes them, launch_dart_build reads them
 size_t tile_darts_bytes(uint32_t W, uint32_t H, uint32_t n_frames);
 // The darts of every frame and tile.  plan != nullptr: the launch of k_tile_scan also plans the batch on the device
-// (frame_base[0..n_frames], plan[0..3] against plan_cap) and zeroes [zero_p, zero_p + zero_bytes), the counter block, a multiple of
+// (frame_base[0..n_frames], *plan -- BatchScratch::plan -- against plan_cap) and zeroes [zero_p, zero_p + zero_bytes), the counter block, a multiple of
 // 16 bytes; frame_darts arrives zeroed.
 struct DartCountLaunch {
     const uint64_t* bits = nullptr; int W = 0, H = 0; uint32_t first_frame = 0, n_frames = 0; unsigned long long* frame_darts = nullptr;
-    uint32_t* tile_darts = nullptr; uint64_t plan_cap = 0; uint32_t* frame_base = nullptr; uint32_t* plan = nullptr; void* zero_p = nullptr;
+    uint32_t* tile_darts = nullptr; uint64_t plan_cap = 0; uint32_t* frame_base = nullptr; PlanWords* plan = nullptr; void* zero_p = nullptr;
     size_t zero_bytes = 0;
 };
 hipError_t launch_dart_count(hipStream_t st, const DartCountLaunch& d);
@@ -53,14 +53,14 @@ struct ContourChunk {
     uint32_t first_frame = 0, n_frames = 0, n_darts = 0; const uint32_t* frame_base = nullptr; DeviceCounters* ctr = nullptr;
     int max_rounds = 0;                  // doubling rounds of the global form (frame_entries == nullptr)
     uint32_t* frame_entries = nullptr;   // per-frame entry counts, zeroed; nullptr: the global rounds
-    unsigned int* dead_count = nullptr;  // [16]; nullptr: no border is dropped early (debug taps, sparse graphs)
+    unsigned int* dead_count = nullptr;  // BatchScratch::dead_count; nullptr: no border is dropped early (debug taps, sparse graphs)
     // the batch
     int W = 0, H = 0;
     uint32_t batch_frames = 0;           // the frames launch_dart_count laid the tile tables out for
     const uint64_t* bits = nullptr; const uint32_t* tile_darts = nullptr;
     const uint32_t* n_live = nullptr;    // the dart total on the device (a device-planned batch: n_darts is its capacity); nullable
     uint32_t* pix_base = nullptr; uint64_t* d_rec = nullptr; uint32_t* d_succ = nullptr; uint32_t* entry_list = nullptr;
-    unsigned int* entry_count = nullptr, * leader_count = nullptr;   // [16] each, zeroed per chunk
+    unsigned int* entry_count = nullptr, * leader_count = nullptr;   // BatchScratch's, zeroed per chunk
     void* es_a = nullptr, * es_b = nullptr;   // EntryState[entry_slots(n_darts)]
     void* fin = nullptr;                      // FinState[n_darts]
     uint32_t* leader_list = nullptr, * leader_keep = nullptr; uint64_t* t_cur = nullptr, * t_next = nullptr;
@@ -108,7 +108,8 @@ struct DecodeStage {
     // ... a3_debug_kernel_time only: k_projection runs first (the product's projections come from k_frame_candidates); k_decode stops
     // early: 1 = no sampling, 2 / 3 / 4 = after sampling / Otsu / bits, 0 and 5 = the whole kernel
     bool projection = false; int variant = 0;
-    // launch_compact_markers: the marker list (capacity marker_cap), its total and the sum of cand_count (cand_pre_total)
+    // launch_compact_markers: the marker list (capacity marker_cap), its total and the sum of cand_count (cand_pre_total: BatchScratch's, with
+    // cand_most kCandMostFromPre words behind it)
     a3_marker* markers = nullptr; uint32_t marker_cap = 0; unsigned int* marker_total = nullptr, * err_flags = nullptr, * cand_pre_total = nullptr;
 };
 hipError_t launch_frame_candidates(hipStream_t st, const DecodeStage& d);

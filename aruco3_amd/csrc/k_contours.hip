@@ -306,11 +306,11 @@ __global__ __launch_bounds__(64) void k_dart_count(const uint64_t* __restrict__ 
 }
 
 // Device-side plan for a batch whose contour graph is expected to fit one chunk (the host learnt its size from the previous
-// batch): exclusive prefix sums of the per-frame dart counts -> frame_base[0..n], total -> plan[0] (0 and plan[1] = 1 when
+// batch): exclusive prefix sums of the per-frame dart counts -> frame_base[0..n], total -> plan->darts (0 and plan->overflow = 1 when
 // the total exceeds `cap`, which makes every later kernel a no-op; the host then re-plans with a read-back), largest
-// frame -> plan[2].  One workgroup of 256 threads (the last one of k_tile_scan's launch); n_frames is small.
+// frame -> plan->max_frame_darts (PlanWords, a3_batch_head.h).  One workgroup of 256 threads (the last one of k_tile_scan's launch); n_frames is small.
 __device__ void plan_frames(unsigned long long* __restrict__ frame_darts, uint32_t n_frames, unsigned long long cap,
-                            uint32_t* __restrict__ frame_base, uint32_t* __restrict__ plan) {
+                            uint32_t* __restrict__ frame_base, PlanWords* __restrict__ plan) {
     __shared__ unsigned long long s_pw[4];
     __shared__ unsigned long long s_run;
     __shared__ unsigned int s_max;
@@ -338,10 +338,10 @@ __device__ void plan_frames(unsigned long long* __restrict__ frame_darts, uint32
         const unsigned long long total = s_run;
         const bool fits = total <= cap;
         frame_base[n_frames] = fits ? (uint32_t)total : 0u;
-        plan[0] = fits ? (uint32_t)total : 0u;
-        plan[1] = fits ? 0u : 1u;
-        plan[2] = s_max;
-        plan[3] = (uint32_t)min(total, 0xFFFFFFFFull);
+        plan->darts = fits ? (uint32_t)total : 0u;
+        plan->overflow = fits ? 0u : 1u;
+        plan->max_frame_darts = s_max;
+        plan->total_clamped = (uint32_t)min(total, 0xFFFFFFFFull);
     }
 }
 
@@ -352,7 +352,7 @@ __device__ void plan_frames(unsigned long long* __restrict__ frame_darts, uint32
 __global__ __launch_bounds__(256) void k_tile_scan(uint32_t* __restrict__ tile_darts, const uint32_t* __restrict__ tile_darts_h1, uint32_t tiles, uint32_t first_frame,
                                                    uint32_t* __restrict__ tile_off, uint32_t n_frames,
                                                    unsigned long long* __restrict__ frame_darts, unsigned long long cap,
-                                                   uint32_t* __restrict__ frame_base, uint32_t* __restrict__ plan,
+                                                   uint32_t* __restrict__ frame_base, PlanWords* __restrict__ plan,
                                                    uint4* __restrict__ zero_p, uint32_t zero_n16) {
     if (blockIdx.x == n_frames) {
         // the batch's block of counters (a3_api's zero block, which also holds `plan`): zeroed here, ahead of its first use
@@ -710,12 +710,10 @@ constexpr int kLT = 2048;   // the larger of the two: sizes the entry slot space
 constexpr int kLTFrame = 1024;
 // Entry slots are handed out from 16 counters (one same-address atomic costs ~11 ns and they serialise): tile t uses
 // shard t & 15, whose slots are [shard * cap, shard * cap + count[shard]); a tile holds at most kLT entries, so
-// cap = ceil(tiles / 16) * kLT can never overflow.
-constexpr uint32_t kEntryShards = 16;
+// cap = ceil(tiles / 16) * kLT can never overflow.  (kEntryShards, kLeaderShards: a3_batch_head.h, beside the counters.)
 // The leaders of cycles that carry a start event are listed in 16 shards of leader_shard_cap slots each (one atomic per workgroup and
 // shard).  k_jump_finalize: the darts handled by the blocks of one shard, n/16 plus at most one 256-dart slice per block of the shard and
 // iteration; k_local_contract + k_entry_frame: leaders of the shard's 1024-dart tiles, at most n/16 + 1024.
-constexpr uint32_t kLeaderShards = 16;
 __host__ __device__ inline uint32_t leader_shard_cap(uint32_t n_darts) { return n_darts / kLeaderShards + n_darts / 64u + 262144u; }
 __host__ __device__ inline uint32_t entry_shard_cap(uint32_t n_darts) {
     const uint32_t tiles = (n_darts + kLT - 1) / kLT;
@@ -844,7 +842,7 @@ __global__ __launch_bounds__(256, (LT >= 2048 || DEAD) ? 4 : 8) void k_local_con
                                                         unsigned int* __restrict__ entry_count, uint32_t ecap,
                                                         const uint32_t* __restrict__ frame_base, uint32_t* __restrict__ frame_entries,
                                                         const uint32_t* __restrict__ n_live, int dbg,
-                                                        uint32_t min_edge_length, unsigned int* __restrict__ dead_count /*[16]; nullptr: mark nothing dead*/,
+                                                        uint32_t min_edge_length, unsigned int* __restrict__ dead_count /*[kDeadShards]; nullptr: mark nothing dead*/,
                                                         int trust_natural /* the launch sequence ends in k_cycle_select's inline check (no fixpoint passes): see the epilogue */,
                                                         uint32_t* __restrict__ leader_list /* nullptr: k_jump_finalize lists the leaders */,
                                                         unsigned int* __restrict__ leader_count /*[kLeaderShards]*/, uint32_t leader_cap) {
@@ -1066,7 +1064,7 @@ __global__ __launch_bounds__(256, (LT >= 2048 || DEAD) ? 4 : 8) void k_local_con
         }
         if (my_dead) atomicAdd(&s_dead_n, my_dead);
         lds_barrier();
-        if (threadIdx.x == 0 && s_dead_n) atomicAdd(&dead_count[blockIdx.x & 15u], s_dead_n);
+        if (threadIdx.x == 0 && s_dead_n) atomicAdd(&dead_count[blockIdx.x & (kDeadShards - 1)], s_dead_n);
     }
     // Entries get their slots; the slot of dart i's successor is left in LDS under i (the windows are not needed any more), where
     // the windows that froze on i find it: a frozen window's state carries the SLOT of the entry it ends on.  (Until round 5 it
@@ -1932,7 +1930,7 @@ size_t tile_darts_bytes(uint32_t W, uint32_t H, uint32_t n_frames) { return tile
 
 hipError_t launch_dart_count(hipStream_t st, const DartCountLaunch& d) {
     const uint64_t* const bits = d.bits; const int W = d.W, H = d.H; const uint32_t first_frame = d.first_frame, n_frames = d.n_frames;
-    unsigned long long* const frame_darts = d.frame_darts; uint32_t* const tile_darts = d.tile_darts, * const plan = d.plan;
+    unsigned long long* const frame_darts = d.frame_darts; uint32_t* const tile_darts = d.tile_darts; PlanWords* const plan = d.plan;
     const uint32_t tiles_x = dart_tiles_x((uint32_t)W), tiles_y = ((uint32_t)H + kTileRows - 1) / kTileRows;
     const uint32_t wpr = words_per_row((uint32_t)W);
     uint32_t* h1 = tile_darts + (size_t)tiles_x * tiles_y * n_frames * 2;

@@ -505,10 +505,10 @@ __device__ __forceinline__ void compact_frame_wave(uint32_t f, int lane, const D
     for (int o = 32; o > 0; o >>= 1) base += __shfl_xor(base, o);
     if (f + 1 == n_frames && lane == 0) *marker_total = base + per_frame[f];
     if (f + 1 == n_frames) {   // a3_stats.candidates_pre: quads after contours_to_candidates, summed over the batch
-        uint32_t pre = 0, most = 0;   // cand_pre_total[3]: the largest number of quads any frame produced (beyond its table's slots: what the host grows the tables to)
+        uint32_t pre = 0, most = 0;   // BatchScratch::cand_most: the largest number of quads any frame produced (beyond its table's slots: what the host grows the tables to)
         for (uint32_t g = lane; g < n_frames; g += 64) { pre += min(cand_count[g], max_cand); most = max(most, cand_count[g]); }
         for (int o = 32; o > 0; o >>= 1) { pre += __shfl_xor(pre, o); most = max(most, (uint32_t)__shfl_xor(most, o)); }
-        if (lane == 0) { *cand_pre_total = pre; cand_pre_total[3] = most; }
+        if (lane == 0) { *cand_pre_total = pre; cand_pre_total[kCandMostFromPre] = most; }
     }
     const uint32_t c = fin_count[f];
     uint32_t pos = base;
@@ -880,7 +880,7 @@ __global__ __launch_bounds__(256) void k_compact_markers(const DecodeOut* __rest
         uint32_t pre = 0, most = 0;
         for (uint32_t g = tid; g < n_frames; g += 256) { pre += min(cand_count[g], max_cand); most = max(most, cand_count[g]); }
         if (pre) atomicAdd(cand_pre_total, pre);
-        if (most) atomicMax(cand_pre_total + 3, most);
+        if (most) atomicMax(cand_pre_total + kCandMostFromPre, most);
     }
     __syncthreads();
     for (uint32_t f0 = 0; f0 < n_frames; f0 += 256) {
