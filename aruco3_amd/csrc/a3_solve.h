@@ -5,6 +5,7 @@
 // pose-only Levenberg-Marquardt loop is not here: moved behind a function it compiles to other code in every one of the kernels, so
 // each keeps its loop and stays instruction for instruction what it was.  Every expression is written in the contract's order and the tests' oracles (tests/*_oracle.c)
 // restate each one in the same order; the library is built with -ffp-contract=off, so nothing is fused.
+// The CPU counterpart of this header, which those oracles share, is tests/solve_oracle.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -8,16 +8,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#define A3O_MAX_EVALS 30
-#define A3O_REL_TOL 1e-6f
-#define A3O_MAX_MARKERS 1024
-
-typedef struct a3o_pose { float error; float rotation[9]; float translation[3]; } a3o_pose;
-typedef struct a3o_board_rec {   /* the layout of a3_board_pose */
-    uint32_t status, markers_used, markers_rejected, iterations;
-    float rms_px, alt_rms_px, rotation[9], translation[3];
-} a3o_board_rec;
-typedef struct a3o_slot { float x[4], y[4], side, cs, sn, cx, cy; } a3o_slot;
+#include "board_oracle.h"
 
 /* ---------------- IPPE (host copy of a3_ippe.h) ---------------- */
 static void find_rotation_to_z(const float v[3], float rot[9]) {  // src/pose.rs:238-267
@@ -170,7 +161,7 @@ int a3o_check_marker(const float c[8]) {
     return 0;
 }
 
-static void slot_from(const float xy[8], a3o_slot* s) {
+void a3o_slot_from(const float xy[8], a3o_slot* s) {
     for (int k = 0; k < 4; k++) { s->x[k] = xy[2 * k]; s->y[k] = xy[2 * k + 1]; }
     const float ex = s->x[1] - s->x[0], ey = s->y[1] - s->y[0];
     s->side = sqrtf(ex * ex + ey * ey);
@@ -180,22 +171,13 @@ static void slot_from(const float xy[8], a3o_slot* s) {
 }
 
 /* ---------------- one frame ---------------- */
-typedef struct {
-    const uint32_t* ids; const float* px; uint32_t cnt;   /* the frame's markers, batch order; pixel corners */
-    const uint32_t* board_ids; a3o_slot* slots; uint32_t n_slots;
-    const uint8_t* dup;
-    int has_intr; float iw, ih, fx, fy, cx, cy, sx, sy;
-} frame_t;
-
-typedef struct { float h[21], g[6], cost, pix; } acc_t;
-
 static uint32_t slot_of(const frame_t* F, uint32_t id) {
     for (uint32_t s = 0; s < F->n_slots; s++)
         if (F->board_ids[s] == id) return s;
     return 0xFFFFu;
 }
 
-static void normalise(const frame_t* F, float x, float y, float* u, float* v) {
+void a3o_normalise(const frame_t* F, float x, float y, float* u, float* v) {
     if (F->has_intr) { *u = (x - F->cx) / F->fx; *v = (y - F->cy) / F->fy; }
     else { *u = x / F->iw; *v = y / F->ih; }
 }
@@ -205,11 +187,11 @@ static int corner(const frame_t* F, uint32_t c, float* bx, float* by, float* mx,
     const uint32_t slot = slot_of(F, F->ids[m]);
     if (slot == 0xFFFFu || F->dup[slot]) return 0;
     *bx = F->slots[slot].x[k]; *by = F->slots[slot].y[k];
-    normalise(F, F->px[8 * m + 2 * k], F->px[8 * m + 2 * k + 1], mx, my);
+    a3o_normalise(F, F->px[8 * m + 2 * k], F->px[8 * m + 2 * k + 1], mx, my);
     return 1;
 }
 
-static void accum(acc_t* s, const float R[9], const float t[3], float bx, float by, float mx, float my, float sx, float sy) {
+void a3o_accum(acc_t* s, const float R[9], const float t[3], float bx, float by, float mx, float my, float sx, float sy) {
     const float qx = R[0] * bx + R[1] * by, qy = R[3] * bx + R[4] * by, qz = R[6] * bx + R[7] * by;
     const float px = qx + t[0], py = qy + t[1], pz = qz + t[2];
     const float zz = pz > 1e-5f ? pz : 1e-5f;
@@ -228,15 +210,9 @@ static void accum(acc_t* s, const float R[9], const float t[3], float bx, float 
     s->pix += eu * eu + ev * ev;
 }
 
-/* 64 lanes, corners l, l + 64, ... in order, then the xor butterfly 32 .. 1 (lane 0's bits = every lane's) */
-static void evaluate(const frame_t* F, const float R[9], const float t[3], acc_t* out) {
-    static acc_t lanes[64], nxt[64];
-    memset(lanes, 0, sizeof lanes);
-    for (int l = 0; l < 64; l++)
-        for (uint32_t c = (uint32_t)l; c < 4 * F->cnt; c += 64) {
-            float bx, by, mx, my;
-            if (corner(F, c, &bx, &by, &mx, &my)) accum(&lanes[l], R, t, bx, by, mx, my, F->sx, F->sy);
-        }
+/* lane 0 after the xor butterfly 32 .. 1 over 64 lanes (lane 0's bits = every lane's); lanes is overwritten */
+void a3o_reduce64(acc_t lanes[64], acc_t* out) {
+    acc_t nxt[64];
     for (int o = 32; o >= 1; o >>= 1) {
         for (int l = 0; l < 64; l++) {
             const acc_t* a = &lanes[l]; const acc_t* b = &lanes[l ^ o];
@@ -245,9 +221,22 @@ static void evaluate(const frame_t* F, const float R[9], const float t[3], acc_t
             nxt[l].cost = a->cost + b->cost;
             nxt[l].pix = a->pix + b->pix;
         }
-        memcpy(lanes, nxt, sizeof lanes);
+        memcpy(lanes, nxt, sizeof nxt);
     }
     *out = lanes[0];
+}
+
+/* 64 lanes, corners l, l + 64, ... in order, then the butterfly */
+static void evaluate(const void* ctx, const float R[9], const float t[3], acc_t* out) {
+    const frame_t* F = (const frame_t*)ctx;
+    acc_t lanes[64];
+    memset(lanes, 0, sizeof lanes);
+    for (int l = 0; l < 64; l++)
+        for (uint32_t c = (uint32_t)l; c < 4 * F->cnt; c += 64) {
+            float bx, by, mx, my;
+            if (corner(F, c, &bx, &by, &mx, &my)) a3o_accum(&lanes[l], R, t, bx, by, mx, my, F->sx, F->sy);
+        }
+    a3o_reduce64(lanes, out);
 }
 
 static int solve6(const float h[21], const float g[6], float lambda, float d[6]) {
@@ -298,9 +287,9 @@ void a3o_cayley(const float w[3], const float R[9], float Rn[9]) {
 }
 
 /* LM from one start (R, t in the board frame, updated in place) -> evaluations; *cost / *pix of the final state */
-static uint32_t refine(const frame_t* F, float R[9], float t[3], float* cost, float* pix) {
+uint32_t a3o_lm(a3o_eval_fn eval, const void* ctx, float R[9], float t[3], float* cost, float* pix) {
     acc_t s;
-    evaluate(F, R, t, &s);
+    eval(ctx, R, t, &s);
     uint32_t evals = 1;
     float lambda = 1e-3f;
     while (evals < A3O_MAX_EVALS && s.cost > 0.0f) {
@@ -310,7 +299,7 @@ static uint32_t refine(const frame_t* F, float R[9], float t[3], float* cost, fl
         a3o_cayley(d, R, Rn);
         for (int r = 0; r < 3; r++) tn[r] = t[r] + d[3 + r];
         acc_t s2;
-        evaluate(F, Rn, tn, &s2);
+        eval(ctx, Rn, tn, &s2);
         evals++;
         if (s2.cost < s.cost) {
             const float rel = (s.cost - s2.cost) / s.cost;
@@ -329,11 +318,11 @@ uint32_t a3o_refine_from(const uint32_t* board_ids, const float* board_xy, uint3
                          const float* intr /* fx, fy, cx, cy or NULL */, uint32_t w, uint32_t h, float R[9], float t[3], float* cost_pix2) {
     static a3o_slot slots[A3O_MAX_MARKERS];
     static uint8_t dup[A3O_MAX_MARKERS];
-    for (uint32_t s = 0; s < n_board; s++) { slot_from(board_xy + 8 * s, &slots[s]); dup[s] = 0; }
+    for (uint32_t s = 0; s < n_board; s++) { a3o_slot_from(board_xy + 8 * s, &slots[s]); dup[s] = 0; }
     frame_t F = {ids, px, cnt, board_ids, slots, n_board, dup, intr != NULL, (float)w, (float)h, 0, 0, 0, 0, 0, 0};
     if (intr) { F.fx = intr[0]; F.fy = intr[1]; F.cx = intr[2]; F.cy = intr[3]; }
     F.sx = intr ? F.fx : F.iw; F.sy = intr ? F.fy : F.ih;
-    return refine(&F, R, t, &cost_pix2[0], &cost_pix2[1]);
+    return a3o_lm(evaluate, &F, R, t, &cost_pix2[0], &cost_pix2[1]);
 }
 
 /* the board pose of one frame: cnt markers (ids, 8 pixel corners each, batch order); start_out (nullable, 2 x 12 floats): both
@@ -343,7 +332,7 @@ int a3o_board_pose(const uint32_t* board_ids, const float* board_xy, uint32_t n_
     static a3o_slot slots[A3O_MAX_MARKERS];
     static uint8_t seen[A3O_MAX_MARKERS], dup[A3O_MAX_MARKERS];
     if (n_board > A3O_MAX_MARKERS) return -1;
-    for (uint32_t s = 0; s < n_board; s++) { slot_from(board_xy + 8 * s, &slots[s]); seen[s] = dup[s] = 0; }
+    for (uint32_t s = 0; s < n_board; s++) { a3o_slot_from(board_xy + 8 * s, &slots[s]); seen[s] = dup[s] = 0; }
     frame_t F = {ids, px, cnt, board_ids, slots, n_board, dup, intr != NULL, (float)w, (float)h, 0, 0, 0, 0, 0, 0};
     if (intr) { F.fx = intr[0]; F.fy = intr[1]; F.cx = intr[2]; F.cy = intr[3]; }
     F.sx = intr ? F.fx : F.iw; F.sy = intr ? F.fy : F.ih;
@@ -368,7 +357,7 @@ int a3o_board_pose(const uint32_t* board_ids, const float* board_xy, uint32_t n_
         if (area > best_area || (area == best_area && slot < best_slot)) {
             float q[8];
             a3o_pose p2[2];
-            for (int k = 0; k < 4; k++) normalise(&F, x[2 * k], x[2 * k + 1], &q[2 * k], &q[2 * k + 1]);
+            for (int k = 0; k < 4; k++) a3o_normalise(&F, x[2 * k], x[2 * k + 1], &q[2 * k], &q[2 * k + 1]);
             solve_normalized(q, slots[slot].side, &p2[0], &p2[1]);
             if (pose_finite(&p2[0]) && pose_finite(&p2[1])) { best_area = area; best_i = i; best_slot = slot; }
         }
@@ -379,7 +368,7 @@ int a3o_board_pose(const uint32_t* board_ids, const float* board_xy, uint32_t n_
     out->status = 1u;
     const a3o_slot* bs = &slots[best_slot];
     float pts[8];
-    for (int k = 0; k < 4; k++) normalise(&F, px[8 * best_i + 2 * k], px[8 * best_i + 2 * k + 1], &pts[2 * k], &pts[2 * k + 1]);
+    for (int k = 0; k < 4; k++) a3o_normalise(&F, px[8 * best_i + 2 * k], px[8 * best_i + 2 * k + 1], &pts[2 * k], &pts[2 * k + 1]);
     a3o_pose p[2];
     solve_normalized(pts, bs->side, &p[0], &p[1]);
     float R[2][9], t[2][3], cost[2], pix[2];
@@ -393,7 +382,7 @@ int a3o_board_pose(const uint32_t* board_ids, const float* board_xy, uint32_t n_
         }
         for (int r = 0; r < 3; r++) t[st][r] = p[st].translation[r] - (R[st][3 * r] * bs->cx + R[st][3 * r + 1] * bs->cy);
         if (start_out) { memcpy(start_out + 12 * st, R[st], 36); memcpy(start_out + 12 * st + 9, t[st], 12); }
-        ev[st] = refine(&F, R[st], t[st], &cost[st], &pix[st]);
+        ev[st] = a3o_lm(evaluate, &F, R[st], t[st], &cost[st], &pix[st]);
     }
     const int keep = cost[1] < cost[0] ? 1 : 0;
     const float nc = (float)(4u * used);

@@ -3,17 +3,12 @@ kernel k_board_pose is held to.  TEST INFRASTRUCTURE ONLY -- the tests and tools
 
 The library is compiled on first use into a temporary directory of its own (gcc / cc, -ffp-contract=off as the kernels), so the
 repository tree is not written to."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-_SRC = Path(__file__).resolve().parent / "board_oracle.c"
+from tests.oracle_build import build
+
 _lib = None
 
 REC_DTYPE = np.dtype([("status", "<u4"), ("markers_used", "<u4"), ("markers_rejected", "<u4"), ("iterations", "<u4"),
@@ -24,15 +19,7 @@ CHECK_ERRORS = {0: None, 1: "no size", 2: "sides differ", 3: "not right angles",
 def lib():
     global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        if cc is None:
-            raise RuntimeError("tests/board_oracle.c needs a C compiler (gcc or cc)")
-        d = tempfile.mkdtemp(prefix="a3_board_oracle_")
-        atexit.register(shutil.rmtree, d, True)
-        so = Path(d) / "libboard_oracle.so"
-        subprocess.check_call([cc, "-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-fno-fast-math",
-                               "-fno-unsafe-math-optimizations", "-shared", "-o", str(so), str(_SRC), "-lm"])
-        L = C.CDLL(str(so))
+        L = build("board_oracle")
         u32p, f32p, vp = C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_void_p
         L.a3o_check_marker.restype = C.c_int
         L.a3o_check_marker.argtypes = [f32p]

@@ -3,10 +3,14 @@
  * with refine_oracle.c (the cornerSubPix iteration), lens_oracle.c (undistortion) and oracle/a3_oracle.c (from_control_points).
  * TEST INFRASTRUCTURE ONLY.
  *
- * The board pose's IPPE start, residual sums, LDL^T step and Cayley update are board_oracle.c's, included here. */
-#include "board_oracle.c"
-
+ * The board pose's IPPE start, residual sums, 64-lane reduction and LM loop are board_oracle.c's, compiled beside this file and
+ * reached through board_oracle.h. */
+#include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
+#include <string.h>
+
+#include "board_oracle.h"
 
 int a3o_from_control_points(const float from[8], const float to[8], float transform[9], float inverse[9]);
 void a3o_undistort(const float *xy, size_t n, const float *intr, const float *k, uint32_t iterations, float max_residual_px, float *out_xy,
@@ -116,48 +120,19 @@ uint32_t a3o_charuco_corners(const uint32_t *board_ids, const float *board_xy, u
 }
 
 /* the frame's records as correspondences: lanes l of 64 sum the records l, l + 64, ..., then the xor butterfly */
-static void charuco_evaluate(const frame_t *F, const float *bxy, const float *mxy, uint32_t n, const float R[9], const float t[3], acc_t *out) {
+typedef struct {
+    const frame_t *F;
+    const float *bxy, *mxy;
+    uint32_t n;
+} records_t;
+
+static void charuco_evaluate(const void *ctx, const float R[9], const float t[3], acc_t *out) {
+    const records_t *g = (const records_t *)ctx;
     acc_t lane[64];
     memset(lane, 0, sizeof lane);
-    for (uint32_t c = 0; c < n; c++) accum(&lane[c & 63], R, t, bxy[2 * c], bxy[2 * c + 1], mxy[2 * c], mxy[2 * c + 1], F->sx, F->sy);
-    for (int o = 32; o >= 1; o >>= 1) {
-        acc_t nx[64];
-        for (int l = 0; l < 64; l++) {
-            const acc_t *a = &lane[l], *b = &lane[l ^ o];
-            for (int q = 0; q < 21; q++) nx[l].h[q] = a->h[q] + b->h[q];
-            for (int q = 0; q < 6; q++) nx[l].g[q] = a->g[q] + b->g[q];
-            nx[l].cost = a->cost + b->cost;
-            nx[l].pix = a->pix + b->pix;
-        }
-        memcpy(lane, nx, sizeof lane);
-    }
-    *out = lane[0];
-}
-
-static uint32_t charuco_lm(const frame_t *F, const float *bxy, const float *mxy, uint32_t n, float R[9], float t[3], float *cost, float *pix) {
-    acc_t s;
-    charuco_evaluate(F, bxy, mxy, n, R, t, &s);
-    uint32_t evals = 1;
-    float lambda = 1e-3f;
-    while (evals < A3O_MAX_EVALS && s.cost > 0.0f) {
-        float d[6];
-        if (!solve6(s.h, s.g, lambda, d)) { lambda = lambda * 10.0f; evals++; continue; }
-        float Rn[9], tn[3];
-        a3o_cayley(d, R, Rn);
-        for (int r = 0; r < 3; r++) tn[r] = t[r] + d[3 + r];
-        acc_t s2;
-        charuco_evaluate(F, bxy, mxy, n, Rn, tn, &s2);
-        evals++;
-        if (s2.cost < s.cost) {
-            const float rel = (s.cost - s2.cost) / s.cost;
-            memcpy(R, Rn, sizeof Rn); memcpy(t, tn, sizeof tn);
-            s = s2;
-            lambda = lambda / 10.0f;
-            if (rel < A3O_REL_TOL) break;
-        } else lambda = lambda * 10.0f;
-    }
-    *cost = s.cost; *pix = s.pix;
-    return evals;
+    for (uint32_t c = 0; c < g->n; c++)
+        a3o_accum(&lane[c & 63], R, t, g->bxy[2 * c], g->bxy[2 * c + 1], g->mxy[2 * c], g->mxy[2 * c + 1], g->F->sx, g->F->sy);
+    a3o_reduce64(lane, out);
 }
 
 /* The ChArUco pose of one frame: cnt markers (ids; px: the corners the board pose reads -- undistorted with a distortion set), the
@@ -173,7 +148,7 @@ int a3o_charuco_pose(const uint32_t *board_ids, const float *board_xy, uint32_t 
     if (br.status == 0 || n < 4) return 0;
     static a3o_slot slots[A3O_MAX_MARKERS];
     static uint8_t nodup[A3O_MAX_MARKERS];
-    for (uint32_t s = 0; s < n_board; s++) { slot_from(board_xy + 8 * s, &slots[s]); nodup[s] = 0; }
+    for (uint32_t s = 0; s < n_board; s++) { a3o_slot_from(board_xy + 8 * s, &slots[s]); nodup[s] = 0; }
     frame_t F = {ids, px, cnt, board_ids, slots, n_board, nodup, intr != NULL, (float)w, (float)h, 0, 0, 0, 0, 0, 0};
     if (intr) { F.fx = intr[0]; F.fy = intr[1]; F.cx = intr[2]; F.cy = intr[3]; }
     F.sx = intr ? F.fx : F.iw; F.sy = intr ? F.fy : F.ih;
@@ -186,13 +161,14 @@ int a3o_charuco_pose(const uint32_t *board_ids, const float *board_xy, uint32_t 
             xy[0] = u[0]; xy[1] = u[1];
         }
         bxy[2 * c] = cxy[2 * rec[c].id]; bxy[2 * c + 1] = cxy[2 * rec[c].id + 1];
-        normalise(&F, xy[0], xy[1], &mxy[2 * c], &mxy[2 * c + 1]);
+        a3o_normalise(&F, xy[0], xy[1], &mxy[2 * c], &mxy[2 * c + 1]);
     }
+    const records_t g = {&F, bxy, mxy, n};
     float R[2][9], t[2][3], cost[2], pix[2];
     uint32_t ev[2];
     for (int st = 0; st < 2; st++) {
         memcpy(R[st], starts + 12 * st, 36); memcpy(t[st], starts + 12 * st + 9, 12);
-        ev[st] = charuco_lm(&F, bxy, mxy, n, R[st], t[st], &cost[st], &pix[st]);
+        ev[st] = a3o_lm(charuco_evaluate, &g, R[st], t[st], &cost[st], &pix[st]);
     }
     free(bxy); free(mxy);
     const int keep = cost[1] < cost[0] ? 1 : 0;

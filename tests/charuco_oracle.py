@@ -2,17 +2,14 @@
 that the device kernels of k_charuco.hip are held to.  TEST INFRASTRUCTURE ONLY -- the tests and tools/charuco_bench.py load it;
 aruco3_amd never does.
 
-Compiled on first use into a temporary directory of its own, with refine_oracle.c, lens_oracle.c and oracle/a3_oracle.c (gcc / cc,
+Compiled on first use into a temporary directory of its own, with board_oracle.c, refine_oracle.c, lens_oracle.c and oracle/a3_oracle.c (gcc / cc,
 -ffp-contract=off as the kernels), so the repository tree is not written to."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
+
+from tests.oracle_build import build
 
 _HERE = Path(__file__).resolve().parent
 _lib = None
@@ -39,16 +36,9 @@ class Config(C.Structure):
 def lib():
     global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        if cc is None:
-            raise RuntimeError("tests/charuco_oracle.c needs a C compiler (gcc or cc)")
-        d = tempfile.mkdtemp(prefix="a3_charuco_oracle_")
-        atexit.register(shutil.rmtree, d, True)
-        so = Path(d) / "libcharuco_oracle.so"
-        srcs = [_HERE / "charuco_oracle.c", _HERE / "refine_oracle.c", _HERE / "lens_oracle.c", _HERE.parent / "oracle" / "a3_oracle.c"]
-        subprocess.check_call([cc, "-O2", "-std=c11", "-fPIC", "-Wall", "-Wno-unused-function", "-ffp-contract=off", "-fno-fast-math",
-                               "-fno-unsafe-math-optimizations", "-shared", "-o", str(so), *map(str, srcs), "-lm"])
-        L = C.CDLL(str(so))
+        srcs = [_HERE / "charuco_oracle.c", _HERE / "board_oracle.c", _HERE / "refine_oracle.c", _HERE / "lens_oracle.c",
+                _HERE.parent / "oracle" / "a3_oracle.c"]
+        L = build("charuco_oracle", srcs)
         u8p, u32p, f32p, vp = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_void_p
         L.a3o_charuco_corners.restype = C.c_uint32
         L.a3o_charuco_corners.argtypes = [u32p, f32p, C.c_uint32, f32p, u32p, C.c_uint32, C.POINTER(Config), u32p, f32p, C.c_uint32, u8p,

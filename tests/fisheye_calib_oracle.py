@@ -5,34 +5,20 @@ compiler's view of the structs.  TEST INFRASTRUCTURE ONLY -- the tests and tools
 
 The library is compiled on first use into a temporary directory of its own (gcc / cc, -ffp-contract=off as the kernels), so the
 repository tree is not written to."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
 from aruco3_amd import _lib as A
+from tests.oracle_build import build
 
-_SRC = Path(__file__).resolve().parent / "fisheye_calib_oracle.c"
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        if cc is None:
-            raise RuntimeError("tests/fisheye_calib_oracle.c needs a C compiler (gcc or cc)")
-        d = tempfile.mkdtemp(prefix="a3_fisheye_calib_oracle_")
-        atexit.register(shutil.rmtree, d, True)
-        so = Path(d) / "libfisheye_calib_oracle.so"
-        subprocess.check_call([cc, "-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-fno-fast-math",
-                               "-fno-unsafe-math-optimizations", "-shared", "-o", str(so), str(_SRC), "-lm"])
-        L = C.CDLL(str(so))
+        L = build("fisheye_calib_oracle")
         f32p, f64p, u32p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32)
         L.a3o_calibrate_fisheye.restype = C.c_int
         L.a3o_calibrate_fisheye.argtypes = [C.POINTER(A.CalibCamera), C.c_size_t, u32p, C.c_size_t, f32p, f32p, C.POINTER(A.CalibResult),

@@ -5,19 +5,13 @@ load it; aruco3_amd never does.
 
 The library is compiled on first use into a temporary directory of its own (gcc / cc, -ffp-contract=off as the kernels), so the
 repository tree is not written to."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
 from tests import rectify_oracle
+from tests.oracle_build import build
 
-_SRC = Path(__file__).resolve().parent / "fisheye_oracle.c"
 _lib = None
 
 # coefficient sets the tests sweep: (k1, k2, k3, k4), cv::fisheye's D
@@ -43,15 +37,7 @@ rot_y = rectify_oracle.rot_y
 def lib():
     global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        if cc is None:
-            raise RuntimeError("tests/fisheye_oracle.c needs a C compiler (gcc or cc)")
-        d = tempfile.mkdtemp(prefix="a3_fisheye_oracle_")
-        atexit.register(shutil.rmtree, d, True)
-        so = Path(d) / "libfisheye_oracle.so"
-        subprocess.check_call([cc, "-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-fno-fast-math",
-                               "-fno-unsafe-math-optimizations", "-shared", "-o", str(so), str(_SRC), "-lm"])
-        L = C.CDLL(str(so))
+        L = build("fisheye_oracle")
         f32p, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
         L.a3o_fisheye_atan.restype = None
         L.a3o_fisheye_atan.argtypes = [f32p, C.c_size_t, f32p]

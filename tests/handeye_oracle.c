@@ -1,10 +1,10 @@
 /* handeye_oracle.c -- the CPU restatement of the hand-eye calibration of include/aruco3_hip.h (a3_calibrate_hand_eyes) that the device
- * kernel k_handeye is held to bit for bit.  One problem at a time, in the contract's order of operations.  The model, the homography,
- * the LDL^T pieces, the Cayley update, pose composition and the rig's columns are the calibration's and the rig's, so this file
- * includes rig_oracle.c and uses its static functions; what is the hand-eye solve's own (the quaternion conversion, the pairs' K rows,
- * the four charts, the row of 13 through X . M_f . Y, the 12 x 12 system) is written out here.  Compiled with -ffp-contract=off
- * (tests/handeye_oracle.py).  TEST INFRASTRUCTURE ONLY. */
-#include "rig_oracle.c"
+ * kernel k_handeye is held to bit for bit.  One problem at a time, in the contract's order of operations.  The homography, the LDL^T
+ * pieces, the Cayley update and the pose LM are solve_oracle.h's, the lens model calib_model.h's, pose composition, the rig's columns
+ * and a frame's pose rig_model.h's; what is written out here is the hand-eye solve's own: the quaternion conversion, the pairs' K
+ * rows, the four charts, the row of 13 through X . M_f . Y and the 12 x 12 system.  Compiled with -ffp-contract=off
+ * (tests/oracle_build.py).  TEST INFRASTRUCTURE ONLY. */
+#include "rig_model.h"
 
 static void he_quat(const double *R, double q[4]) {
     const double tr = (R[0] + R[4]) + R[8];
@@ -130,35 +130,32 @@ static int he_charts(const double *N, double q[4], double *ratio) {
 }
 
 /* the two augmented rows of one point through G = (X . M) . Y; Ep = X . M */
-static void he_row(const double a[12], const double *X, const double *M, const double *Y, const double *Ep, const double *G, double Xc, double Yc,
-                   double ou, double ov, double *au, double *av) {
+typedef struct HeAt {
+    const double *a, *X, *M, *Y, *Ep, *G;
+} HeAt;
+
+static void he_row(const void *ctx, double Xc, double Yc, double ou, double ov, double *au, double *av) {
+    const HeAt *g = (const HeAt *)ctx;
+    const double *X = g->X, *M = g->M, *Y = g->Y;
     double cu[AUG], cv[AUG];
-    calib_row(a, G, G + 9, Xc, Yc, ou, ov, cu, cv);
+    calib_row(g->a, g->G, g->G + 9, Xc, Yc, ou, ov, cu, cv);
     const double qf[3] = {Y[0] * Xc + Y[1] * Yc, Y[3] * Xc + Y[4] * Yc, Y[6] * Xc + Y[7] * Yc};
     const double y[3] = {qf[0] + Y[9], qf[1] + Y[10], qf[2] + Y[11]};
     double m[3], qc[3];
     for (int r = 0; r < 3; r++) m[r] = ((M[3 * r] * y[0] + M[3 * r + 1] * y[1]) + M[3 * r + 2] * y[2]) + M[9 + r];
     for (int r = 0; r < 3; r++) qc[r] = (X[3 * r] * m[0] + X[3 * r + 1] * m[1]) + X[3 * r + 2] * m[2];
-    rig_cols(cu + 15, Ep, qc, qf, cu[18], au);
-    rig_cols(cv + 15, Ep, qc, qf, cv[18], av);
+    rig_cols(cu + 15, g->Ep, qc, qf, cu[18], au);
+    rig_cols(cv + 15, g->Ep, qc, qf, cv[18], av);
 }
 
 static void he_block(const double a[12], const double *X, const double *M, const double *Y, const float *obj, const float *img, uint32_t p0,
                      uint32_t np, double out[RENT]) {
-    double au[RAUG], av[RAUG], Ep[12], G[12];
+    double Ep[12], G[12];
     pose_mul(X, M, Ep);
     pose_mul(Ep, Y, G);
-    for (int e = 0; e < RENT; e++) out[e] = 0.0;
-    for (uint32_t j = 0; j < np; j++) {
-        const size_t p = (size_t)p0 + j;
-        he_row(a, X, M, Y, Ep, G, (double)obj[2 * p], (double)obj[2 * p + 1], (double)img[2 * p], (double)img[2 * p + 1], au, av);
-        for (int e = 0; e < RENT; e++) {
-            int i, k;
-            tri_ik(e, RAUG, &i, &k);
-            out[e] = out[e] + au[i] * au[k];
-            out[e] = out[e] + av[i] * av[k];
-        }
-    }
+    const HeAt g = {a, X, M, Y, Ep, G};
+    const Points P = {obj, img, p0, np};
+    aug_block(he_row, &g, RAUG, &P, out);
 }
 
 typedef struct HeFrame {
@@ -188,7 +185,7 @@ static int he_system(const double *S, int n, int off, double lambda, double A[12
     for (int i = 0; i < n; i++)
         for (int k = i; k < n; k++) { const double v = S[tri_index(off + i, off + k, RAUG)]; A[i][k] = v; A[k][i] = v; }
     for (int i = 0; i < n; i++) A[i][i] = A[i][i] + lambda * A[i][i];
-    return ldl_n(A, n, D);
+    return ldl_n(&A[0][0], 12, n, D);
 }
 
 static void handeye_one(const a3_handeye_problem *R, const a3_handeye_frame *frames, const float *obj, const float *img, HeFrame *fs,
@@ -196,7 +193,6 @@ static void handeye_one(const a3_handeye_problem *R, const a3_handeye_frame *fra
     const uint32_t f0 = R->first_frame, F = R->n_frames;
     const int fixx = (R->flags & A3_HANDEYE_FIX_X) != 0, guess = (R->flags & A3_HANDEYE_USE_GUESS) != 0;
     const double *a = R->a;
-    static const double ID[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
     uint32_t fu = 0, N = 0, pairs = 0;
     /* 1 */
     for (uint32_t j = 0; j < F; j++) {
@@ -209,55 +205,17 @@ static void handeye_one(const a3_handeye_problem *R, const a3_handeye_frame *fra
         if (rec->status != A3_HANDEYE_FRAME_USED) continue;
         fu++;
         N += np;
-        double m[3][3];
-        for (int c = 0; c < 3; c++) {
-            m[c][0] = (H[c] - a[2] * H[6 + c]) / a[0];
-            m[c][1] = (H[3 + c] - a[3] * H[6 + c]) / a[1];
-            m[c][2] = H[6 + c];
-        }
-        const double n0 = sqrt((m[0][0] * m[0][0] + m[0][1] * m[0][1]) + m[0][2] * m[0][2]);
-        const double r00 = m[0][0] / n0, r01 = m[0][1] / n0, r02 = m[0][2] / n0;
-        const double dd = (r00 * m[1][0] + r01 * m[1][1]) + r02 * m[1][2];
-        const double e0 = m[1][0] - dd * r00, e1 = m[1][1] - dd * r01, e2 = m[1][2] - dd * r02;
-        const double ne = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-        const double r10 = e0 / ne, r11 = e1 / ne, r12 = e2 / ne;
-        const double n1 = sqrt((m[1][0] * m[1][0] + m[1][1] * m[1][1]) + m[1][2] * m[1][2]);
-        const double den = n0 + n1;
-        double T[12] = {r00, r10, r01 * r12 - r02 * r11, r01, r11, r02 * r10 - r00 * r12, r02, r12, r00 * r11 - r01 * r10,
-                        (2.0 * m[2][0]) / den, (2.0 * m[2][1]) / den, (2.0 * m[2][2]) / den};
-        double *pc = fs[f].blk[0], *po = fs[f].blk[1];
-        obs_block(a, ID, T, T, obj, img, p0, np, pc);
-        double c1 = pc[RENT - 1], lam = 1e-3;
-        int evals = 1;
-        while (evals < A3_CALIB_POSE_EVALS && c1 > 0.0) {
-            double L[6][6], D[6];
-            if (!ldl6_at(pc, 6, RAUG, lam, L, D)) { lam = lam * 10.0; evals++; continue; }
-            double b[6], d[6], Tn[12];
-            for (int q = 0; q < 6; q++) b[q] = -pc[tri_index(6 + q, 12, RAUG)];
-            ldl6_solve(L, D, b, d);
-            pose_update(T, d, Tn);
-            obs_block(a, ID, Tn, Tn, obj, img, p0, np, po);
-            evals++;
-            const double c2 = po[RENT - 1];
-            if (c2 < c1) {
-                const double rel = (c1 - c2) / c1;
-                memcpy(T, Tn, sizeof T);
-                double *s = pc; pc = po; po = s;
-                c1 = c2;
-                lam = lam / 10.0;
-                if (rel < A3_CALIB_REL_TOL) break;
-            } else lam = lam * 10.0;
-        }
-        memcpy(fs[f].P, T, sizeof T);
-        fs[f].cost = c1;
+        double *T = fs[f].P;
+        obs_pose_start(a, H, T);
+        fs[f].cost = obs_pose_lm(a, obj, img, p0, np, T);
         for (int q = 0; q < 9; q++) { rec->rotation[q] = T[q]; rec->rotation_f[q] = (float)T[q]; }
         for (int q = 0; q < 3; q++) { rec->translation[q] = T[9 + q]; rec->translation_f[q] = (float)T[9 + q]; }
     }
     int status = fu < 3 ? A3_HANDEYE_TOO_FEW_FRAMES : A3_HANDEYE_OK;
     /* 2 */
     double X[2][12], Y[2][12];
-    memcpy(X[0], ID, sizeof ID);
-    memcpy(Y[0], ID, sizeof ID);
+    memcpy(X[0], POSE_ID, sizeof POSE_ID);
+    memcpy(Y[0], POSE_ID, sizeof POSE_ID);
     if (status == A3_HANDEYE_OK && (fixx || guess)) {
         memcpy(X[0], R->guess_x_rotation, 9 * sizeof(double));
         memcpy(X[0] + 9, R->guess_x_translation, 3 * sizeof(double));
@@ -355,7 +313,7 @@ static void handeye_one(const a3_handeye_problem *R, const a3_handeye_frame *fra
                 continue;
             }
             for (int i = 0; i < n; i++) b[i] = -S[cur][tri_index(off + i, 12, RAUG)];
-            ldl_n_solve(A, n, D, b, d);
+            ldl_n_solve(&A[0][0], 12, n, D, b, d, 0);
             if (fixx) memcpy(X[1 - cur], X[cur], sizeof X[0]);
             else pose_update(X[cur], d, X[1 - cur]);
             pose_update(Y[cur], d + (n - 6), Y[1 - cur]);
@@ -386,7 +344,7 @@ static void handeye_one(const a3_handeye_problem *R, const a3_handeye_frame *fra
             if (!bad) {
                 double e[12], x[12];
                 for (int k = 0; k < n; k++) e[k] = k == i ? 1.0 : 0.0;
-                ldl_n_solve(A, n, D, e, x);
+                ldl_n_solve(&A[0][0], 12, n, D, e, x, 0);
                 dv = sqrt(sigma2 * x[i]);
             }
             std[off + i] = dv;

@@ -4,17 +4,12 @@ load it; aruco3_amd never does.
 
 The library is compiled on first use into a temporary directory of its own (gcc / cc, -ffp-contract=off as the kernels), so the
 repository tree is not written to."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-_SRC = Path(__file__).resolve().parent / "lens_oracle.c"
+from tests.oracle_build import build
+
 _lib = None
 
 # coefficient sets the tests sweep: (k1, k2, p1, p2, k3, k4, k5, k6)
@@ -30,15 +25,7 @@ COEFFS = {
 def lib():
     global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        if cc is None:
-            raise RuntimeError("tests/lens_oracle.c needs a C compiler (gcc or cc)")
-        d = tempfile.mkdtemp(prefix="a3_lens_oracle_")
-        atexit.register(shutil.rmtree, d, True)
-        so = Path(d) / "liblens_oracle.so"
-        subprocess.check_call([cc, "-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-fno-fast-math",
-                               "-fno-unsafe-math-optimizations", "-shared", "-o", str(so), str(_SRC), "-lm"])
-        L = C.CDLL(str(so))
+        L = build("lens_oracle")
         f32p = C.POINTER(C.c_float)
         L.a3o_undistort.restype = None
         L.a3o_undistort.argtypes = [f32p, C.c_size_t, f32p, f32p, C.c_uint32, C.c_float, f32p, f32p]

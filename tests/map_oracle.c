@@ -1,10 +1,9 @@
 /* map_oracle.c -- the CPU restatement of the marker map solve of include/aruco3_hip.h (a3_build_marker_maps) that the device kernel
- * k_map is held to bit for bit.  One map at a time, in the contract's order of operations.  The model, the homography, the 6 x 6
- * LDL^T, the Cayley update, pose composition and the row of 13 are the calibration's and the rig's, so this file includes
- * rig_oracle.c and uses its static functions; what is the map's own (the two planar candidates, the start in rounds, the reduced
- * system over the markers with its LDL^T and solve) is written out here.  Compiled with -ffp-contract=off (tests/map_oracle.py).
- * TEST INFRASTRUCTURE ONLY. */
-#include "rig_oracle.c"
+ * k_map is held to bit for bit.  One map at a time, in the contract's order of operations.  The homography, the LDL^T pieces, the
+ * Cayley update and the pose LM are solve_oracle.h's, the lens model calib_model.h's, pose composition, the row of 13 and an
+ * observation's pose rig_model.h's; what is written out here is the map's own: the two planar candidates, the start in rounds and
+ * the reduced system over the markers.  Compiled with -ffp-contract=off (tests/oracle_build.py).  TEST INFRASTRUCTURE ONLY. */
+#include "rig_model.h"
 
 #define MM A3_MAP_MAX_MARKERS
 
@@ -49,82 +48,6 @@ static void pose_flip(const double *P, double *Q) {
     for (int q = 9; q < 12; q++) Q[q] = P[q];
 }
 
-/* the pose LM of step 1 on columns 6-12, E the identity: T in / out -> the cost */
-static double pose_lm(const double a[12], const float *sq, const float *img, double T[12]) {
-    static const double ID[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
-    double b0[RENT], b1[RENT], *pc = b0, *po = b1;
-    obs_block(a, ID, T, T, sq, img, 0, 4, pc);
-    double c1 = pc[RENT - 1], lam = 1e-3;
-    int evals = 1;
-    while (evals < A3_CALIB_POSE_EVALS && c1 > 0.0) {
-        double L[6][6], D[6];
-        if (!ldl6_at(pc, 6, RAUG, lam, L, D)) { lam = lam * 10.0; evals++; continue; }
-        double b[6], d[6], Tn[12];
-        for (int q = 0; q < 6; q++) b[q] = -pc[tri_index(6 + q, 12, RAUG)];
-        ldl6_solve(L, D, b, d);
-        pose_update(T, d, Tn);
-        obs_block(a, ID, Tn, Tn, sq, img, 0, 4, po);
-        evals++;
-        const double c2 = po[RENT - 1];
-        if (c2 < c1) {
-            const double rel = (c1 - c2) / c1;
-            memcpy(T, Tn, 12 * sizeof(double));
-            double *s = pc; pc = po; po = s;
-            c1 = c2;
-            lam = lam / 10.0;
-            if (rel < A3_CALIB_REL_TOL) break;
-        } else lam = lam * 10.0;
-    }
-    return c1;
-}
-
-/* the pose start of step 1 from the homography */
-static void map_start(const double a[12], const double H[9], double *P) {
-    double m[3][3];
-    for (int c = 0; c < 3; c++) {
-        m[c][0] = (H[c] - a[2] * H[6 + c]) / a[0];
-        m[c][1] = (H[3 + c] - a[3] * H[6 + c]) / a[1];
-        m[c][2] = H[6 + c];
-    }
-    const double n0 = sqrt((m[0][0] * m[0][0] + m[0][1] * m[0][1]) + m[0][2] * m[0][2]);
-    const double r00 = m[0][0] / n0, r01 = m[0][1] / n0, r02 = m[0][2] / n0;
-    const double dd = (r00 * m[1][0] + r01 * m[1][1]) + r02 * m[1][2];
-    const double e0 = m[1][0] - dd * r00, e1 = m[1][1] - dd * r01, e2 = m[1][2] - dd * r02;
-    const double ne = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-    const double r10 = e0 / ne, r11 = e1 / ne, r12 = e2 / ne;
-    const double n1 = sqrt((m[1][0] * m[1][0] + m[1][1] * m[1][1]) + m[1][2] * m[1][2]);
-    const double den = n0 + n1;
-    const double T[12] = {r00, r10, r01 * r12 - r02 * r11, r01, r11, r02 * r10 - r00 * r12, r02, r12, r00 * r11 - r01 * r10,
-                          (2.0 * m[2][0]) / den, (2.0 * m[2][1]) / den, (2.0 * m[2][2]) / den};
-    memcpy(P, T, sizeof T);
-}
-
-static int ldl_big(double *A, int n, double *D) {   /* row-major, stride n, lower triangle */
-    for (int j = 0; j < n; j++)
-        for (int i = j; i < n; i++) {
-            double s = A[(size_t)i * n + j];
-            for (int k = 0; k < j; k++) s = s - A[(size_t)i * n + k] * A[(size_t)j * n + k] * D[k];
-            if (i == j) {
-                if (!(s > 0.0) || !fin(s)) return 0;
-                D[j] = s;
-            } else A[(size_t)i * n + j] = s / D[j];
-        }
-    return 1;
-}
-
-static void ldl_big_solve(const double *A, int n, const double *D, const double *b, double *x) {
-    for (int i = 0; i < n; i++) {
-        double s = b[i];
-        for (int k = 0; k < i; k++) s = s - A[(size_t)i * n + k] * x[k];
-        x[i] = s;
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double s = x[i] / D[i];
-        for (int k = n - 1; k > i; k--) s = s - A[(size_t)k * n + i] * x[k];
-        x[i] = s;
-    }
-}
-
 typedef struct Map {
     const a3_map *R;
     const a3_map_observation *obs;
@@ -153,7 +76,6 @@ static void map_one(const a3_map *R, const a3_map_marker *markers, const a3_map_
     const uint32_t M = R->n_markers, m0 = R->first_marker, f0 = R->first_frame, F = R->n_frames, o0 = R->first_obs, NO = R->n_obs;
     const int fix = (R->flags & A3_MAP_FIX_MAP) != 0, guess = fix || (R->flags & A3_MAP_USE_GUESS);
     const double *a = R->a;
-    static const double ID[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
     Map g = {R, obs, img, {0}, os, fs, fo};
     const float h = R->marker_length * 0.5f;
     const float sq[8] = {-h, h, h, h, h, -h, -h, -h};
@@ -190,10 +112,10 @@ static void map_one(const a3_map *R, const a3_map_marker *markers, const a3_map_
         double H[9];
         rec->status = view_homography(sq, im, 0, 4, H) ? A3_MAP_OBS_USED : A3_MAP_OBS_DEGENERATE;
         if (rec->status != A3_MAP_OBS_USED) continue;
-        map_start(a, H, os[o].P[0]);
-        os[o].c[0] = pose_lm(a, sq, im, os[o].P[0]);
+        obs_pose_start(a, H, os[o].P[0]);
+        os[o].c[0] = obs_pose_lm(a, sq, im, 0, 4, os[o].P[0]);
         pose_flip(os[o].P[0], os[o].P[1]);
-        os[o].c[1] = pose_lm(a, sq, im, os[o].P[1]);
+        os[o].c[1] = obs_pose_lm(a, sq, im, 0, 4, os[o].P[1]);
         rec->start_rms_px[0] = (float)sqrt(os[o].c[0] / 4.0);
         rec->start_rms_px[1] = (float)sqrt(os[o].c[1] / 4.0);
     }
@@ -201,8 +123,8 @@ static void map_one(const a3_map *R, const a3_map_marker *markers, const a3_map_
     double Mp[2][MM][12];
     int reached[MM];
     for (uint32_t m = 0; m < M; m++) {
-        memcpy(Mp[0][m], ID, sizeof ID);
-        memcpy(Mp[1][m], ID, sizeof ID);
+        memcpy(Mp[0][m], POSE_ID, sizeof POSE_ID);
+        memcpy(Mp[1][m], POSE_ID, sizeof POSE_ID);
         if (guess && m >= 1) {
             memcpy(Mp[0][m], markers[m0 + m].guess_rotation, 9 * sizeof(double));
             memcpy(Mp[0][m] + 9, markers[m0 + m].guess_translation, 3 * sizeof(double));
@@ -434,7 +356,7 @@ static void map_one(const a3_map *R, const a3_map_marker *markers, const a3_map_
                         if (k < n) { S[(size_t)i * n + k] = s; S[(size_t)k * n + i] = s; }
                         else rhs[i] = s;
                     }
-                bad = !ldl_big(S, n, Dg);
+                bad = !ldl_n(S, n, n, Dg);
             }
             if (covariance) {
                 const long long dof = 2ll * N - n - 6ll * fu;
@@ -443,7 +365,7 @@ static void map_one(const a3_map *R, const a3_map_marker *markers, const a3_map_
                     double dv = INFINITY;
                     if (!bad && dof > 0) {
                         for (int k = 0; k < n; k++) ev[k] = k == i ? 1.0 : 0.0;
-                        ldl_big_solve(S, n, Dg, ev, ev);
+                        ldl_n_solve(S, n, n, Dg, ev, ev, 1);
                         dv = sqrt(sigma2 * ev[i]);
                     }
                     std[i] = dv;
@@ -456,8 +378,8 @@ static void map_one(const a3_map *R, const a3_map_marker *markers, const a3_map_
                 if (iter >= maxit) stop = 1;
                 continue;
             }
-            ldl_big_solve(S, n, Dg, rhs, de);
-            for (uint32_t m = 0; m < M; m++) memcpy(Mp[1 - cur][m], Mp[cur][m], sizeof ID);
+            ldl_n_solve(S, n, n, Dg, rhs, de, 1);
+            for (uint32_t m = 0; m < M; m++) memcpy(Mp[1 - cur][m], Mp[cur][m], sizeof POSE_ID);
             for (int u = 0; u < nu; u++) pose_update(Mp[cur][ua[u]], de + 6 * u, Mp[1 - cur][ua[u]]);
             for (uint32_t j = 0; j < F; j++) {
                 const uint32_t f = f0 + j;
@@ -539,10 +461,10 @@ int a3o_map_candidates(const double *a, float marker_length, const float *img, d
     const float sq[8] = {-h, h, h, h, h, -h, -h, -h};
     double H[9];
     if (!view_homography(sq, img, 0, 4, H)) return 0;
-    map_start(a, H, P);
-    c[0] = pose_lm(a, sq, img, P);
+    obs_pose_start(a, H, P);
+    c[0] = obs_pose_lm(a, sq, img, 0, 4, P);
     pose_flip(P, P + 12);
-    c[1] = pose_lm(a, sq, img, P + 12);
+    c[1] = obs_pose_lm(a, sq, img, 0, 4, P + 12);
     return 1;
 }
 

@@ -2,36 +2,22 @@
 the device kernel k_map is held to, and the C compiler's view of the structs.  TEST INFRASTRUCTURE ONLY -- the tests and
 tools/map_bench.py load it; aruco3_amd never does.
 
-The library is compiled on first use into a temporary directory of its own (gcc / cc, the flags of tests/calib_oracle.py), so the
+The library is compiled on first use into a temporary directory of its own (gcc / cc, the flags of tests/oracle_build.py), so the
 repository tree is not written to."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
 from aruco3_amd import _lib as A
+from tests.oracle_build import build
 
-_SRC = Path(__file__).resolve().parent / "map_oracle.c"
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        if cc is None:
-            raise RuntimeError("tests/map_oracle.c needs a C compiler (gcc or cc)")
-        d = tempfile.mkdtemp(prefix="a3_map_oracle_")
-        atexit.register(shutil.rmtree, d, True)
-        so = Path(d) / "libmap_oracle.so"
-        subprocess.check_call([cc, "-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-fno-fast-math",
-                               "-fno-unsafe-math-optimizations", "-shared", "-o", str(so), str(_SRC), "-lm"])
-        L = C.CDLL(str(so))
+        L = build("map_oracle")
         L.a3o_build_marker_maps.restype = C.c_int
         L.a3o_build_marker_maps.argtypes = [C.POINTER(A.Map), C.c_size_t, C.POINTER(A.MapMarker), C.c_size_t, C.POINTER(A.MapObservation),
                                             C.c_size_t, C.POINTER(C.c_float), C.POINTER(A.MapResult), C.POINTER(A.MapMarkerResult),

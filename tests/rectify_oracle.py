@@ -3,17 +3,12 @@ that the device kernel k_rectify is held to.  TEST INFRASTRUCTURE ONLY -- the te
 
 The library is compiled on first use into a temporary directory of its own (gcc / cc, -ffp-contract=off as the kernels), so the
 repository tree is not written to."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-_SRC = Path(__file__).resolve().parent / "rectify_oracle.c"
+from tests.oracle_build import build
+
 _lib = None
 
 # the source camera and the five views the tests sweep: (K of the view, (width, height), rotation about y in degrees)
@@ -37,15 +32,7 @@ def rot_y(deg):
 def lib():
     global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        if cc is None:
-            raise RuntimeError("tests/rectify_oracle.c needs a C compiler (gcc or cc)")
-        d = tempfile.mkdtemp(prefix="a3_rectify_oracle_")
-        atexit.register(shutil.rmtree, d, True)
-        so = Path(d) / "librectify_oracle.so"
-        subprocess.check_call([cc, "-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-fno-fast-math",
-                               "-fno-unsafe-math-optimizations", "-shared", "-o", str(so), str(_SRC), "-lm"])
-        L = C.CDLL(str(so))
+        L = build("rectify_oracle")
         f32p, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
         L.a3o_rectify.restype = None
         L.a3o_rectify.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, f32p, f32p, f32p, f32p, C.c_uint8,

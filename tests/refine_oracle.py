@@ -3,17 +3,12 @@ kernel is held to bit for bit.  TEST INFRASTRUCTURE ONLY -- the tests and tools/
 
 The library is compiled on first use into a temporary directory of its own (gcc / cc, -ffp-contract=off as the kernels), so the
 repository tree is not written to."""
-import atexit
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-_SRC = Path(__file__).resolve().parent / "refine_oracle.c"
+from tests.oracle_build import build
+
 _lib = None
 
 
@@ -30,15 +25,7 @@ class RefineConfig(C.Structure):
 def lib():
     global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("gcc") or shutil.which("cc")
-        if cc is None:
-            raise RuntimeError("tests/refine_oracle.c needs a C compiler (gcc or cc)")
-        d = tempfile.mkdtemp(prefix="a3_refine_oracle_")
-        atexit.register(shutil.rmtree, d, True)
-        so = Path(d) / "librefine_oracle.so"
-        subprocess.check_call([cc, "-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-ffp-contract=off", "-fno-fast-math",
-                               "-fno-unsafe-math-optimizations", "-shared", "-o", str(so), str(_SRC), "-lm"])
-        L = C.CDLL(str(so))
+        L = build("refine_oracle")
         u8p, u32p, f32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_float)
         L.a3o_quad_cell_px.restype = C.c_float
         L.a3o_quad_cell_px.argtypes = [u32p, C.c_uint32]

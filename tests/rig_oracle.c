@@ -1,116 +1,13 @@
 /* rig_oracle.c -- the CPU restatement of the camera rig calibration of include/aruco3_hip.h (a3_calibrate_rigs) that the device kernel
- * k_rig is held to bit for bit.  One rig at a time, in the contract's order of operations.  The model, the homography, the 6 x 6 LDL^T
- * and the Cayley update are the calibration contract's, so this file includes calib_oracle.c and uses its static functions; what is
- * the rig's own (pose composition, the row of 13, the start over the co-visibility graph, the Schur system over the extrinsics) is
- * written out here.  Compiled with -ffp-contract=off (tests/rig_oracle.py).  TEST INFRASTRUCTURE ONLY. */
-#include "calib_oracle.c"
+ * k_rig is held to bit for bit.  One rig at a time, in the contract's order of operations.  The homography, the LDL^T pieces, the
+ * Cayley update and the pose LM are solve_oracle.h's, the lens model calib_model.h's, pose composition and the row of 13 rig_model.h's;
+ * what is written out here is the rig's own: the start over the co-visibility graph and the Schur system over the extrinsics.
+ * Compiled with -ffp-contract=off (tests/oracle_build.py).  TEST INFRASTRUCTURE ONLY. */
+#include "rig_model.h"
 
-#define RAUG 13
-#define RENT 91
 #define NONE 0xffffffffu
 #define MAXC A3_RIG_MAX_CAMERAS
 #define MAXN (6 * (A3_RIG_MAX_CAMERAS - 1))
-
-static void pose_mul(const double *A, const double *B, double *O) {   /* poses as R (9), t (3) */
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) O[3 * r + c] = (A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c]) + A[3 * r + 2] * B[6 + c];
-        O[9 + r] = ((A[3 * r] * B[9] + A[3 * r + 1] * B[10]) + A[3 * r + 2] * B[11]) + A[9 + r];
-    }
-}
-
-static void pose_inv(const double *A, double *O) {
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) O[3 * r + c] = A[3 * c + r];
-        O[9 + r] = -((A[r] * A[9] + A[3 + r] * A[10]) + A[6 + r] * A[11]);
-    }
-}
-
-static void rig_cols(const double u[3], const double Rc[9], const double qc[3], const double qf[3], double res, double *o) {
-    const double cx = 2.0 * qc[0], cy = 2.0 * qc[1], cz = 2.0 * qc[2];
-    o[0] = u[2] * cy - u[1] * cz; o[1] = u[0] * cz - u[2] * cx; o[2] = u[1] * cx - u[0] * cy;
-    o[3] = u[0]; o[4] = u[1]; o[5] = u[2];
-    double ur[3];
-    for (int j = 0; j < 3; j++) ur[j] = (u[0] * Rc[j] + u[1] * Rc[3 + j]) + u[2] * Rc[6 + j];
-    const double fx = 2.0 * qf[0], fy = 2.0 * qf[1], fz = 2.0 * qf[2];
-    o[6] = ur[2] * fy - ur[1] * fz; o[7] = ur[0] * fz - ur[2] * fx; o[8] = ur[1] * fx - ur[0] * fy;
-    o[9] = ur[0]; o[10] = ur[1]; o[11] = ur[2];
-    o[12] = res;
-}
-
-/* E = (Rc, .) rig -> camera, T board -> rig, G = E . T */
-static void rig_row(const double a[12], const double *E, const double *T, const double *G, double X, double Y, double ou, double ov, double *au,
-                    double *av) {
-    double cu[AUG], cv[AUG];
-    calib_row(a, G, G + 9, X, Y, ou, ov, cu, cv);
-    const double qf[3] = {T[0] * X + T[1] * Y, T[3] * X + T[4] * Y, T[6] * X + T[7] * Y};
-    const double y[3] = {qf[0] + T[9], qf[1] + T[10], qf[2] + T[11]};
-    double qc[3];
-    for (int r = 0; r < 3; r++) qc[r] = (E[3 * r] * y[0] + E[3 * r + 1] * y[1]) + E[3 * r + 2] * y[2];
-    rig_cols(cu + 15, E, qc, qf, cu[18], au);
-    rig_cols(cv + 15, E, qc, qf, cv[18], av);
-}
-
-static void obs_block(const double a[12], const double *E, const double *T, const double *G, const float *obj, const float *img, uint32_t p0,
-                      uint32_t np, double out[RENT]) {
-    double au[RAUG], av[RAUG];
-    for (int e = 0; e < RENT; e++) out[e] = 0.0;
-    for (uint32_t j = 0; j < np; j++) {
-        const size_t p = (size_t)p0 + j;
-        rig_row(a, E, T, G, (double)obj[2 * p], (double)obj[2 * p + 1], (double)img[2 * p], (double)img[2 * p + 1], au, av);
-        for (int e = 0; e < RENT; e++) {
-            int i, k;
-            tri_ik(e, RAUG, &i, &k);
-            out[e] = out[e] + au[i] * au[k];
-            out[e] = out[e] + av[i] * av[k];
-        }
-    }
-}
-
-/* LDL^T of V + lambda diag(V), V the 6 x 6 block at columns off .. off + 5 of an aug-triangle */
-static int ldl6_at(const double *blk, int off, int aug, double lambda, double L[6][6], double D[6]) {
-    double A[6][6];
-    for (int r = 0; r < 6; r++)
-        for (int c = r; c < 6; c++) { const double v = blk[tri_index(off + r, off + c, aug)]; A[r][c] = v; A[c][r] = v; }
-    for (int r = 0; r < 6; r++) A[r][r] = A[r][r] + lambda * A[r][r];
-    int ok = 1;
-    for (int j = 0; j < 6; j++)
-        for (int i = j; i < 6; i++) {
-            double s = A[i][j];
-            for (int k = 0; k < j; k++) s = s - L[i][k] * L[j][k] * D[k];
-            if (i == j) {
-                ok = ok && s > 0.0 && fin(s);
-                D[j] = s;
-                L[j][j] = 1.0;
-            } else L[i][j] = s / D[j];
-        }
-    return ok;
-}
-
-static int ldl_m(double A[MAXN][MAXN], int n, double D[MAXN]) {
-    for (int j = 0; j < n; j++)
-        for (int i = j; i < n; i++) {
-            double s = A[i][j];
-            for (int k = 0; k < j; k++) s = s - A[i][k] * A[j][k] * D[k];
-            if (i == j) {
-                if (!(s > 0.0) || !fin(s)) return 0;
-                D[j] = s;
-            } else A[i][j] = s / D[j];
-        }
-    return 1;
-}
-
-static void ldl_m_solve(double A[MAXN][MAXN], int n, const double D[MAXN], const double *b, double *x) {
-    for (int i = 0; i < n; i++) {
-        double s = b[i];
-        for (int k = 0; k < i; k++) s = s - A[i][k] * x[k];
-        x[i] = s;
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double s = x[i] / D[i];
-        for (int k = i + 1; k < n; k++) s = s - A[k][i] * x[k];
-        x[i] = s;
-    }
-}
 
 typedef struct Obs {
     double blk[2][RENT];
@@ -124,11 +21,6 @@ typedef struct Frame {
     double Y[MAXN + 1][6];
     int cur;
 } Frame;
-
-static void pose_update(const double *T, const double d[6], double *Tn) {
-    cayley_d(d, T, Tn);
-    for (int q = 0; q < 3; q++) Tn[9 + q] = T[9 + q] + d[3 + q];
-}
 
 typedef struct Rig {
     const a3_rig *R;
@@ -161,7 +53,6 @@ static void rig_one(const a3_rig *R, const a3_rig_camera *cams, const a3_rig_obs
     const uint32_t C = R->n_cameras, c0 = R->first_camera, f0 = R->first_frame, F = R->n_frames, o0 = R->first_obs, NO = R->n_obs;
     const Rig g = {R, cams, obs, obj, img, os, fs, tab};
     const int fix = (R->flags & A3_RIG_FIX_EXTRINSICS) != 0, guess = fix || (R->flags & A3_RIG_USE_EXTRINSIC_GUESS);
-    static const double ID[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
     for (uint32_t j = 0; j < F; j++)
         for (uint32_t c = 0; c < MAXC; c++) tab[(size_t)(f0 + j) * MAXC + c] = NONE;
     /* 1 */
@@ -175,47 +66,8 @@ static void rig_one(const a3_rig *R, const a3_rig_camera *cams, const a3_rig_obs
         rec->status = np < 4 ? A3_RIG_OBS_TOO_FEW_POINTS : view_homography(obj, img, p0, np, H) ? A3_RIG_OBS_USED : A3_RIG_OBS_DEGENERATE;
         if (rec->status != A3_RIG_OBS_USED) continue;
         tab[(size_t)obs[o].frame * MAXC + (obs[o].camera - c0)] = o;
-        double m[3][3];
-        for (int c = 0; c < 3; c++) {
-            m[c][0] = (H[c] - a[2] * H[6 + c]) / a[0];
-            m[c][1] = (H[3 + c] - a[3] * H[6 + c]) / a[1];
-            m[c][2] = H[6 + c];
-        }
-        const double n0 = sqrt((m[0][0] * m[0][0] + m[0][1] * m[0][1]) + m[0][2] * m[0][2]);
-        const double r00 = m[0][0] / n0, r01 = m[0][1] / n0, r02 = m[0][2] / n0;
-        const double dd = (r00 * m[1][0] + r01 * m[1][1]) + r02 * m[1][2];
-        const double e0 = m[1][0] - dd * r00, e1 = m[1][1] - dd * r01, e2 = m[1][2] - dd * r02;
-        const double ne = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
-        const double r10 = e0 / ne, r11 = e1 / ne, r12 = e2 / ne;
-        const double n1 = sqrt((m[1][0] * m[1][0] + m[1][1] * m[1][1]) + m[1][2] * m[1][2]);
-        const double den = n0 + n1;
-        double T[12] = {r00, r10, r01 * r12 - r02 * r11, r01, r11, r02 * r10 - r00 * r12, r02, r12, r00 * r11 - r01 * r10,
-                        (2.0 * m[2][0]) / den, (2.0 * m[2][1]) / den, (2.0 * m[2][2]) / den};
-        double *pc = os[o].blk[0], *po = os[o].blk[1];
-        obs_block(a, ID, T, T, obj, img, p0, np, pc);
-        double c1 = pc[RENT - 1], lam = 1e-3;
-        int evals = 1;
-        while (evals < A3_CALIB_POSE_EVALS && c1 > 0.0) {
-            double L[6][6], D[6];
-            if (!ldl6_at(pc, 6, RAUG, lam, L, D)) { lam = lam * 10.0; evals++; continue; }
-            double b[6], d[6], Tn[12];
-            for (int q = 0; q < 6; q++) b[q] = -pc[tri_index(6 + q, 12, RAUG)];
-            ldl6_solve(L, D, b, d);
-            pose_update(T, d, Tn);
-            obs_block(a, ID, Tn, Tn, obj, img, p0, np, po);
-            evals++;
-            const double c2 = po[RENT - 1];
-            if (c2 < c1) {
-                const double rel = (c1 - c2) / c1;
-                memcpy(T, Tn, sizeof T);
-                double *s = pc; pc = po; po = s;
-                c1 = c2;
-                lam = lam / 10.0;
-                if (rel < A3_CALIB_REL_TOL) break;
-            } else lam = lam * 10.0;
-        }
-        memcpy(os[o].P, T, sizeof T);
-        os[o].cost = c1;
+        obs_pose_start(a, H, os[o].P);
+        os[o].cost = obs_pose_lm(a, obj, img, p0, np, os[o].P);
     }
     /* counts */
     uint32_t fu = 0, ou = 0, N = 0;
@@ -252,9 +104,9 @@ static void rig_one(const a3_rig *R, const a3_rig_camera *cams, const a3_rig_obs
                 if (best[c][b] < 0 || s < bs) { best[c][b] = (int32_t)j; bs = s; }
             }
         }
-    memcpy(E[0][0], ID, sizeof ID);
+    memcpy(E[0][0], POSE_ID, sizeof POSE_ID);
     for (uint32_t c = 1; c < C; c++) {
-        memcpy(E[0][c], ID, sizeof ID);
+        memcpy(E[0][c], POSE_ID, sizeof POSE_ID);
         if (guess) {
             memcpy(E[0][c], cams[c0 + c].guess_rotation, 9 * sizeof(double));
             memcpy(E[0][c] + 9, cams[c0 + c].guess_translation, 3 * sizeof(double));
@@ -415,7 +267,7 @@ static void rig_one(const a3_rig *R, const a3_rig_camera *cams, const a3_rig_obs
                         if (k < n) { S[i][k] = s; S[k][i] = s; }
                         else rhs[i] = s;
                     }
-                bad = !ldl_m(S, n, Dg);
+                bad = !ldl_n(&S[0][0], MAXN, n, Dg);
             }
             if (covariance) {
                 const double sigma2 = cost / (double)(2ll * N - n - 6ll * fu);
@@ -424,7 +276,7 @@ static void rig_one(const a3_rig *R, const a3_rig_camera *cams, const a3_rig_obs
                     if (!bad) {
                         double e[MAXN], x[MAXN];
                         for (int k = 0; k < n; k++) e[k] = k == i ? 1.0 : 0.0;
-                        ldl_m_solve(S, n, Dg, e, x);
+                        ldl_n_solve(&S[0][0], MAXN, n, Dg, e, x, 0);
                         dv = sqrt(sigma2 * x[i]);
                     }
                     std[i] = dv;
@@ -437,8 +289,8 @@ static void rig_one(const a3_rig *R, const a3_rig_camera *cams, const a3_rig_obs
                 if (iter >= maxit) stop = 1;
                 continue;
             }
-            ldl_m_solve(S, n, Dg, rhs, de);
-            memcpy(E[1 - cur][0], ID, sizeof ID);
+            ldl_n_solve(&S[0][0], MAXN, n, Dg, rhs, de, 0);
+            memcpy(E[1 - cur][0], POSE_ID, sizeof POSE_ID);
             for (uint32_t c = 1; c < C; c++) pose_update(E[cur][c], de + 6 * (c - 1), E[1 - cur][c]);
             for (uint32_t j = 0; j < F; j++) {
                 const uint32_t f = f0 + j;
