@@ -69,6 +69,7 @@ SYMBOLS = [
     "a3_contour_count", "a3_download_contours", "a3_detection_record_bytes", "a3_pack_detections",
     "a3_default_refine_config", "a3_set_corner_refinement", "a3_get_refined_corners", "a3_refine_corners",
     "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
+    "a3_default_recover_config", "a3_set_board_recovery", "a3_get_board_recovery", "a3_get_recovered_counts", "a3_recover_markers",
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
     "a3_calibrate_cameras", "a3_calibrate_fisheye_cameras", "a3_calibrate_rigs", "a3_calibrate_hand_eyes", "a3_build_marker_maps",
@@ -133,6 +134,15 @@ class BoardPoseRec(C.Structure):
     """a3_board_pose: one board pose per frame (an extension beyond the reference; include/aruco3_hip.h states the solve)"""
     _fields_ = [("status", C.c_uint32), ("markers_used", C.c_uint32), ("markers_rejected", C.c_uint32), ("iterations", C.c_uint32),
                 ("rms_px", C.c_float), ("alt_rms_px", C.c_float), ("rotation", C.c_float * 9), ("translation", C.c_float * 3)]
+
+
+class RecoverConfig(C.Structure):
+    """a3_recover_config: board-aided recovery of rejected markers (an extension beyond the reference; include/aruco3_hip.h states it)"""
+    _fields_ = [("mode", C.c_uint32), ("min_markers", C.c_uint32), ("max_distance_px", C.c_float), ("max_hamming", C.c_uint8),
+                ("reserved", C.c_uint8 * 3)]
+
+
+RECOVER_NO_BITS = 255   # a3_recover_config.max_hamming: bits are not compared
 
 
 class DistortionRec(C.Structure):
@@ -435,6 +445,19 @@ def load():
         L.a3_get_board_poses.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.a3_estimate_board_pose.restype = C.c_int
         L.a3_estimate_board_pose.argtypes = [vp, u32p, f32p, C.c_size_t, C.POINTER(Intrinsics), C.c_uint32, C.c_uint32, C.POINTER(BoardPoseRec)]
+    if hasattr(L, "a3_set_board_recovery"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack board recovery)
+        u64p, u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+        L.a3_default_recover_config.restype = C.c_int
+        L.a3_default_recover_config.argtypes = [vp, C.POINTER(RecoverConfig)]
+        L.a3_set_board_recovery.restype = C.c_int
+        L.a3_set_board_recovery.argtypes = [vp, C.POINTER(RecoverConfig)]
+        L.a3_get_board_recovery.restype = C.c_int
+        L.a3_get_board_recovery.argtypes = [vp, C.POINTER(RecoverConfig)]
+        L.a3_get_recovered_counts.restype = C.c_int
+        L.a3_get_recovered_counts.argtypes = [vp, u32p, C.c_size_t]
+        L.a3_recover_markers.restype = C.c_int
+        L.a3_recover_markers.argtypes = [vp, u32p, u32p, C.c_size_t, u32p, u64p, u8p, C.c_size_t, C.POINTER(RecoverConfig), vp, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]
     if hasattr(L, "a3_set_distortion"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack lens distortion)
         L.a3_default_distortion.restype = None
         L.a3_default_distortion.argtypes = [C.POINTER(DistortionRec)]
@@ -786,6 +809,48 @@ class Context:
         out = np.zeros(1, dtype=BOARD_POSE_DTYPE)
         C.memmove(out.ctypes.data, C.addressof(rec), C.sizeof(rec))
         return out[0]
+
+    # ---- board-aided recovery ----
+    def default_recover_config(self) -> "RecoverConfig":
+        """a3_default_recover_config: on, min_markers 2, max_distance_px 10, max_hamming derived from the dictionary's bit count"""
+        cfg = RecoverConfig()
+        check(load().a3_default_recover_config(self.handle, C.byref(cfg)), self.handle)
+        return cfg
+
+    def set_board_recovery(self, cfg: "RecoverConfig" = None):
+        """a3_set_board_recovery: None (or mode 0) clears it; applies to batches submitted afterwards"""
+        check(load().a3_set_board_recovery(self.handle, C.byref(cfg) if cfg is not None else None), self.handle)
+
+    def board_recovery(self):
+        """a3_get_board_recovery -> the RecoverConfig in force, or None"""
+        cfg = RecoverConfig()
+        check(load().a3_get_board_recovery(self.handle, C.byref(cfg)), self.handle)
+        return cfg if cfg.mode else None
+
+    def recovered_counts(self, n_frames: int) -> np.ndarray:
+        """a3_get_recovered_counts: how many markers at the tail of each frame's segment of the last collected batch are recovered ones"""
+        out = np.zeros(max(n_frames, 1), dtype=np.uint32)
+        check(load().a3_get_recovered_counts(self.handle, _p(out, C.c_uint32), n_frames), self.handle)
+        return out[:n_frames]
+
+    def recover_markers(self, detected_ids, detected_corners, candidate_corners, codes4, has_codes, cfg: "RecoverConfig", out_cap: int = None) -> np.ndarray:
+        """a3_recover_markers (stand-alone, one frame): detected ids (n,) and integer corners (n, 4, 2); rejected candidates' integer
+        corners (m, 4, 2), their four rotated codes (m, 4) and has-codes flags (m,) -> MARKER_DTYPE records, in candidate order"""
+        i = np.ascontiguousarray(np.asarray(detected_ids, dtype=np.uint32).reshape(-1))
+        d = np.ascontiguousarray(np.asarray(detected_corners, dtype=np.uint32).reshape(-1, 8))
+        q = np.ascontiguousarray(np.asarray(candidate_corners, dtype=np.uint32).reshape(-1, 8))
+        k = np.ascontiguousarray(np.asarray(codes4, dtype=np.uint64).reshape(-1, 4))
+        h = np.ascontiguousarray(np.asarray(has_codes, dtype=np.uint8).reshape(-1))
+        if d.shape[0] != i.size:
+            raise ValueError("recover_markers needs four corners per detected id")
+        if k.shape[0] != q.shape[0] or h.size != q.shape[0]:
+            raise ValueError("recover_markers needs four codes and one flag per candidate")
+        cap = q.shape[0] if out_cap is None else int(out_cap)
+        out = np.zeros(max(cap, 1), dtype=MARKER_DTYPE)
+        n = C.c_size_t()
+        check(load().a3_recover_markers(self.handle, _p(i, C.c_uint32), _p(d, C.c_uint32), i.size, _p(q, C.c_uint32), _p(k, C.c_uint64), _p(h, C.c_uint8),
+                                        q.shape[0], C.byref(cfg), out.ctypes.data_as(C.c_void_p), cap, C.byref(n)), self.handle)
+        return out[: n.value]
 
     # ---- lens distortion ----
     # ---- ChArUco ----

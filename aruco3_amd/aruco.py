@@ -80,7 +80,7 @@ def _apply_rectification(ctx: _lib.Context, rectification: Optional[Rectificatio
 
 @dataclass
 class Marker:
-    """src/aruco.rs:8-13, plus the refined corners when the detector refines them and the undistorted corners (with their residuals in
+    """src/aruco.rs:8-13, plus whether the marker was recovered through the board (an extension), the refined corners when the detector refines them and the undistorted corners (with their residuals in
     pixels, +inf: not undistorted) when a pose call's intrinsics carry a lens distortion (extensions; None otherwise)"""
     id: int
     code: int
@@ -89,6 +89,7 @@ class Marker:
     corners_refined: Optional[List[Tuple[float, float]]] = None
     corners_undistorted: Optional[List[Tuple[float, float]]] = None
     undistort_residual_px: Optional[List[float]] = None
+    recovered: bool = False   # with Detector(recovery=...): the decoder rejected this quad, the board placed it (hamming_distance 255: bits not compared)
 
 
 @dataclass
@@ -144,7 +145,9 @@ class Detector:
 
     def __init__(self, config: DetectorConfig = None, dictionary: ARDictionary = None, device: int = 0,
                  refinement: Optional[CornerRefinement] = None, board=None, charuco_config: Optional[_lib.CharucoConfig] = None,
-                 rectification: Optional[Rectification] = None):
+                 rectification: Optional[Rectification] = None, recovery=None):
+        if recovery is not None and board is None:
+            raise ValueError("Detector(recovery=...) needs a board: recovery places rejected quads where the board says its markers are")
         self.config = config or DetectorConfig()
         self.dictionary = dictionary or ARDictionary.new_from_named_dict("ARUCO")
         self.device = device
@@ -154,6 +157,8 @@ class Detector:
         self.charuco_config = charuco_config
         # every call sees its frames through this rectification (frames of its camera's size in, pixels of its view out)
         self.rectification = rectification
+        # aruco3_amd.board.BoardRecovery: board markers the decoder rejected are recovered on the device (Marker.recovered)
+        self.recovery = recovery
         self._ctx = None
         self._ctx_key = None
 
@@ -172,6 +177,10 @@ class Detector:
             _set_board(ctx, b, cfg)
             self._board_applied = (ctx, key)
         return b is not None
+
+    def _apply_recovery(self, ctx: _lib.Context) -> bool:
+        """hands the detector's recovery setting (and the board it needs) to the context before a call -> whether it is on"""
+        return _apply_recovery(ctx, self.recovery, lambda: self._apply_board(ctx))
 
     def _charuco(self, ctx: _lib.Context) -> bool:
         """a CharucoBoard as the board: hands it to the context (every call then reports its corners) -> whether it is one"""
@@ -218,14 +227,16 @@ class Detector:
         ctx.set_debug_taps(populate)
         refine = self._apply_refinement(ctx)
         charuco = self._charuco(ctx)
+        recover = self._apply_recovery(ctx)
         markers, per = ctx.detect_batch(ptr, mem, fmt, w, h, rs, fs, n, out_cap)
         refined = ctx.refined_corners() if refine else None
+        rec = ctx.recovered_counts(n) if recover else None
         out = []
         pos = 0
         for f in range(n):
             det = Detection()
             for i in range(pos, pos + int(per[f])):
-                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None))
+                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, recovered=_is_tail(rec, f, i - pos, per)))
             pos += int(per[f])
             if populate:
                 det.grey = ctx.download_grey(f, *(self.rectification.view_size if self.rectification is not None else (w, h)))
@@ -251,6 +262,7 @@ class Detector:
         refine = self._apply_refinement(ctx)
         dist = self._apply_distortion(ctx, intrinsics)
         charuco = self._charuco(ctx)
+        recover = self._apply_recovery(ctx)
         intr = None
         if intrinsics is not None:
             ci = intrinsics
@@ -258,13 +270,14 @@ class Detector:
         markers, per, poses = ctx.detect_batch_pose(ptr, mem, fmt, w, h, rs, fs, n, marker_size_mm, intr, out_cap)
         refined = ctx.refined_corners() if refine else None
         undist = ctx.undistorted_corners() if dist else None
+        rec = ctx.recovered_counts(n) if recover else None
         out = []
         pos = 0
         for f in range(n):
             det = Detection()
             pp = []
             for i in range(pos, pos + int(per[f])):
-                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i)))
+                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i), _is_tail(rec, f, i - pos, per)))
                 pp.append(tuple(MarkerPose(float(q[0]), q[1:10].reshape(3, 3).copy(), q[10:13].copy()) for q in poses[i]))
             pos += int(per[f])
             out.append((det, pp))
@@ -289,6 +302,7 @@ class Detector:
         refine = self._apply_refinement(ctx)
         dist = self._apply_distortion(ctx, intrinsics)
         self._apply_board(ctx)
+        recover = self._apply_recovery(ctx)
         intr = None
         if intrinsics is not None:
             ci = intrinsics
@@ -297,7 +311,7 @@ class Detector:
         refined = ctx.refined_corners() if refine else None
         undist = ctx.undistorted_corners() if dist else None
         boards = ctx.board_poses()
-        dets = _detections(markers, per, refined, undist)
+        dets = _detections(markers, per, refined, undist, ctx.recovered_counts(n) if recover else None)
         if _is_charuco(self.board):
             _fill_charuco(dets, ctx.charuco_corners())
         return [(d, BoardPose._from(boards[f])) for f, d in enumerate(dets)]
@@ -318,6 +332,7 @@ class Detector:
         refine = self._apply_refinement(ctx)
         dist = self._apply_distortion(ctx, intrinsics)
         self._apply_board(ctx)
+        recover = self._apply_recovery(ctx)
         intr = None
         if intrinsics is not None:
             ci = intrinsics
@@ -325,7 +340,7 @@ class Detector:
         markers, per, _ = ctx.detect_batch_pose(ptr, mem, fmt, w, h, rs, fs, n, marker_size_mm, intr, out_cap)
         refined = ctx.refined_corners() if refine else None
         undist = ctx.undistorted_corners() if dist else None
-        dets = _detections(markers, per, refined, undist)
+        dets = _detections(markers, per, refined, undist, ctx.recovered_counts(n) if recover else None)
         _fill_charuco(dets, ctx.charuco_corners())
         poses = ctx.charuco_poses()
         return [(d, CharucoPose._from(poses[f])) for f, d in enumerate(dets)]
@@ -351,6 +366,7 @@ class Detector:
         if stream is not None:
             ctx.set_stream(stream)
         self._apply_refinement(ctx)   # (the refined corners are not returned here: Context.refined_corners() has them)
+        self._apply_recovery(ctx)     # (likewise the recovered counts: Context.recovered_counts())
         return ctx.detect_batch(ptr, mem, fmt, w, h, rs, fs, n, out_cap)
 
 
@@ -367,6 +383,26 @@ def _set_board(ctx: _lib.Context, board, charuco_config=None) -> None:
         ctx.set_charuco(board.chessboard_corners, board.adjacent_ids, charuco_config)
 
 
+def _apply_recovery(ctx: _lib.Context, recovery, apply_board) -> bool:
+    """hands a BoardRecovery (or None) to a context that has no batch in flight; apply_board() sets the board it needs first"""
+    if recovery is None:
+        if getattr(ctx, "_recovery_key", None) is not None:
+            ctx.set_board_recovery(None)
+            ctx._recovery_key = None
+        return False
+    apply_board()
+    cfg = recovery._c(ctx)
+    if getattr(ctx, "_recovery_key", None) != bytes(cfg):
+        ctx.set_board_recovery(cfg)
+        ctx._recovery_key = bytes(cfg)
+    return True
+
+
+def _is_tail(rec, f: int, k: int, per) -> bool:
+    """marker k of frame f's segment is one of the frame's rec[f] recovered markers (they are the segment's tail)"""
+    return rec is not None and k >= int(per[f]) - int(rec[f])
+
+
 def _fill_charuco(dets: List[Detection], recs: np.ndarray) -> None:
     """Detection.charuco_ids / .charuco_corners of each frame from the (frame, id)-ordered records of Context.charuco_corners()"""
     bounds = np.searchsorted(recs["frame"], np.arange(len(dets) + 1))
@@ -376,12 +412,12 @@ def _fill_charuco(dets: List[Detection], recs: np.ndarray) -> None:
         d.charuco_corners = np.stack([r["x"], r["y"]], axis=1).astype(np.float32).reshape(-1, 2)
 
 
-def _marker(m, refined=None, undist=None) -> Marker:
+def _marker(m, refined=None, undist=None, recovered: bool = False) -> Marker:
     c = m["corners"]
     return Marker(int(m["id"]), int(m["code"]), [(int(c[2 * i]), int(c[2 * i + 1])) for i in range(4)], int(m["hamming_distance"]),
                   None if refined is None else [(float(x), float(y)) for x, y in refined],
                   None if undist is None else [(float(x), float(y)) for x, y in undist[0]],
-                  None if undist is None else [float(r) for r in undist[1]])
+                  None if undist is None else [float(r) for r in undist[1]], recovered)
 
 
 def _undist_at(undist, i):
@@ -389,12 +425,12 @@ def _undist_at(undist, i):
     return None if undist is None else (undist[0][i], undist[1][i])
 
 
-def _detections(markers, per, refined=None, undist=None) -> List[Detection]:
+def _detections(markers, per, refined=None, undist=None, rec=None) -> List[Detection]:
     out, pos = [], 0
     for f in range(len(per)):
         det = Detection()
         for i in range(pos, pos + int(per[f])):
-            det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i)))
+            det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i), _is_tail(rec, f, i - pos, per)))
         pos += int(per[f])
         out.append(det)
     return out
@@ -419,6 +455,7 @@ class BatchQueue:
         self._refinement = detector.refinement   # (the detector's setting when the queue was made; each batch keeps the one in force at its submit)
         self._board, self._charuco_config = detector.board, detector.charuco_config   # (likewise)
         self._rectification = detector.rectification   # (likewise)
+        self._recovery = detector.recovery   # (likewise)
         self._refine_on = [False] * depth
         self._keep = [None] * depth
         self._gates = gates
@@ -448,6 +485,7 @@ class BatchQueue:
         self._refine_on[k] = self._refinement is not None
         if self._submitted < depth and self._board is not None:   # (each context's first batch: the board stays set on it)
             _set_board(ctx, self._board, self._charuco_config)
+        _apply_recovery(ctx, self._recovery, lambda: None)   # (the board is set: Detector refuses a recovery without one)
         ctx.submit(ptr, mem, fmt, w, h, rs, fs, n, out_cap=out_cap or n * 64)
         self._keep[k] = keep
         self._submitted += 1
@@ -465,7 +503,8 @@ class BatchQueue:
         finally:
             self._keep[k] = None
         self.last_stepping = ctx.stats()["stepping"]
-        dets = _detections(markers, per, ctx.refined_corners() if self._refine_on[k] else None)
+        dets = _detections(markers, per, ctx.refined_corners() if self._refine_on[k] else None,
+                           rec=ctx.recovered_counts(len(per)) if self._recovery is not None else None)
         if _is_charuco(self._board):
             _fill_charuco(dets, ctx.charuco_corners())
         return dets

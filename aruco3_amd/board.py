@@ -8,6 +8,9 @@ frame (Detection.charuco_ids / .charuco_corners) and, from `Detector.detect_batc
 from dataclasses import dataclass
 from typing import Sequence, Tuple
 
+import math
+from typing import Optional
+
 import numpy as np
 
 from . import _lib
@@ -179,3 +182,50 @@ class CharucoPose:
     def _from(cls, rec) -> "CharucoPose":
         return cls(int(rec["status"]), int(rec["corners_used"]), int(rec["iterations"]), float(rec["rms_px"]), float(rec["alt_rms_px"]),
                    np.array(rec["rotation"], dtype=np.float32).reshape(3, 3), np.array(rec["translation"], dtype=np.float32))
+
+
+@dataclass
+class BoardRecovery:
+    """Board-aided recovery of markers the decoder rejected (a3_recover_config; not in the reference -- include/aruco3_hip.h states the
+    algorithm; OpenCV's refineDetectedMarkers).  Passing one to `Detector(board=..., recovery=...)` makes every detect call look, in each
+    frame that shows at least `min_markers` board markers, for the board's other markers among the quads the decoder rejected: a quad
+    within `max_distance_px` of where the board's homography puts a marker, whose bits lie within `max_hamming` of that marker's code,
+    comes back as a `Marker` with `recovered=True`.  max_hamming None: the default derived from the dictionary's bit count (a random
+    code passes with probability below 1e-3); 255: bits are not compared, and quads without a readable code are eligible too."""
+    max_distance_px: float = 10.0
+    max_hamming: Optional[int] = None
+    min_markers: int = 2
+
+    def __post_init__(self):
+        d = float(self.max_distance_px)
+        if not math.isfinite(d) or not d > 0:
+            raise ValueError("BoardRecovery.max_distance_px must be finite and > 0")
+        if int(self.min_markers) != self.min_markers or self.min_markers < 1:
+            raise ValueError("BoardRecovery.min_markers must be an integer >= 1")
+        if self.max_hamming is not None and (int(self.max_hamming) != self.max_hamming or not 0 <= self.max_hamming <= 255):
+            raise ValueError("BoardRecovery.max_hamming must be None or an integer in 0..255")
+
+    def _c(self, ctx: "_lib.Context") -> "_lib.RecoverConfig":
+        cfg = ctx.default_recover_config()
+        cfg.min_markers = int(self.min_markers)
+        cfg.max_distance_px = float(self.max_distance_px)
+        if self.max_hamming is not None:
+            cfg.max_hamming = int(self.max_hamming)
+        return cfg
+
+
+def recover_markers(board: Board, dictionary, detected_ids, detected_corners, candidate_corners, codes4, has_codes,
+                    recovery: Optional[BoardRecovery] = None, device: int = 0) -> np.ndarray:
+    """stand-alone, one frame (a3_recover_markers): the markers of `board` that `detected_ids` lacks, looked for among caller-given
+    rejected quads -- what a refineDetectedMarkers user calls.  detected_corners (n, 4, 2) and candidate_corners (m, 4, 2) are integer
+    pixels, codes4 (m, 4) each quad's code read at the four rotations, has_codes (m,) whether it has any.  -> _lib.MARKER_DTYPE records
+    in candidate order (candidate_index: the quad's position, rotation: the shift that aligns it with the board)."""
+    from .aruco import DetectorConfig
+
+    ctx = _lib.Context(DetectorConfig()._c(), dictionary.code_list, dictionary.num_bits, dictionary._tau, device)
+    try:
+        ctx.set_board(board.ids, board.corners)
+        cfg = (recovery or BoardRecovery())._c(ctx)
+        return ctx.recover_markers(detected_ids, detected_corners, candidate_corners, codes4, has_codes, cfg).copy()
+    finally:
+        ctx.close()

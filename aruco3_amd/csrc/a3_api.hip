@@ -92,6 +92,11 @@ struct Batch {
     bool charuco = false;        // ChArUco set: the corner stage runs behind the refinement (and k_charuco_pose behind k_board_pose)
     a3_charuco_config charuco_cfg{};
     uint32_t charuco_nc = 0, charuco_guess = 0;   // chessboard corners; records in the speculative read-back
+    // a3_set_board_recovery in force: the marker gather writes to a side list and k_recover_frames / k_recover_merge leave the merged
+    // list where every later stage and the read-back expect the batch's markers
+    bool recover = false;
+    a3_recover_config recover_cfg{};
+    uint32_t recover_slots = 0, recover_cap = 0;   // board markers; records a frame's recovery can hold (ensure_back_buffers)
     // a3_set_rectification in force: the call's frames (rect_src, in rect_fmt, with strides rect_row and rect_frame) are the SOURCE, seen
     // through rect_r.  pixels, fmt, W, H, row_stride and frame_stride above then describe the rectified grey plane (A3_FMT_L8, r.dst's size),
     // which k_rectify's grey form writes ahead of the threshold kernel; everything behind that launch sees nothing else
@@ -217,6 +222,15 @@ struct a3_ctx {
     DevBuf board_slot_of, board_slot_rec, board_buf;   // id -> slot (n_codes x u16), slot records, board poses of the last batch (per frame)
     std::vector<a3_board_pose> h_board;
     bool board_valid = false;   // the last collected batch was a pose batch with a board: h_board holds its poses
+    // a3_set_board_recovery: the setting later batches capture; the board's ids in slot order on the device (brought up to date with the
+    // board's tables); the side list the marker gather writes ([total, padded to 16 bytes | per-frame counts | recovered per frame] in
+    // recover_counts, the markers in recover_det), the per-frame records of k_recover_frames; the last collected batch's counts
+    a3_recover_config recover{};
+    uint64_t recover_ids_version = 0;
+    std::vector<uint32_t> recover_ids_up;
+    DevBuf recover_ids, recover_counts, recover_det, recover_tmp;
+    std::vector<uint32_t> h_recovered;
+    bool recovered_valid = false;
     // a3_set_distortion: the setting later pose batches capture; undist_buf holds the undistorted corners of the last batch on the
     // device: [marker_cap x 8 floats | marker_cap x 4 residuals]
     a3_distortion dist{};
@@ -418,7 +432,7 @@ const void* refine_params_for(a3_ctx* ctx, const a3_refine_config& cfg) {
 // ChArUco: the per-frame slot records of charuco_tmp (the counts follow them)
 size_t charuco_slot_bytes(const Batch& b) { return ((size_t)b.n * b.charuco_nc * sizeof(a3_charuco_corner) + 255) & ~(size_t)255; }
 // what a3_readback.h lays a batch's staging out from
-ReadbackShape readback_shape(const Batch& b, size_t head_bytes) { return {b.n, b.guess, b.charuco_guess, head_bytes, b.want_pose, b.refined, b.undist, b.board, b.charuco}; }
+ReadbackShape readback_shape(const Batch& b, size_t head_bytes) { return {b.n, b.guess, b.charuco_guess, head_bytes, b.want_pose, b.refined, b.undist, b.board, b.charuco, b.recover}; }
 // the refinement kernel's parameters for the ChArUco setting `cfg` (its window and iteration settings; built once per setting)
 const void* charuco_params_for(a3_ctx* ctx, const a3_charuco_config& cfg) {
     if (ctx->charuco_prm.empty() || memcmp(&ctx->charuco_prm_cfg, &cfg, sizeof cfg) != 0) {
@@ -469,9 +483,25 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     if (b.taps) dec.patches = ctx->patches.as<uint8_t>();
     dec.patch_cap = b.patch_cap;
     dec.grid_blocks = (int)std::min<uint32_t>(4096u, b.n * 128u);   // (grid-stride over the work list; 4096 workgroups that find nothing cost a one-frame call ~4 us)
+    uint32_t* side_total = nullptr, * side_per_frame = nullptr, * recovered = nullptr;   // recover_counts: [total, padded | per frame | recovered per frame]
+    if (b.recover) {
+        side_total = ctx->recover_counts.as<uint32_t>(); side_per_frame = side_total + 4; recovered = side_per_frame + b.n;   // the gather's list, counts and total go to the side buffers; the batch's own are written by k_recover_merge
+        A3_HIP(hipMemsetAsync(side_total, 0, 16 + (size_t)b.n * 4, st));
+        dec.markers = ctx->recover_det.as<a3_marker>(); dec.per_frame = side_per_frame; dec.marker_total = side_total;
+    }
     A3_HIP(launch_frame_candidates(st, dec));
     A3_HIP(launch_decode(st, dec));
     A3_HIP(launch_compact_markers(st, dec));
+    if (b.recover) {
+        A3_HIP(launch_recover_frames(st, {.markers = dec.markers, .n_dev = side_total, .per_frame = side_per_frame, .n = b.marker_cap, .n_frames = b.n,
+                                          .outs = dec.outs, .fin_xy = dec.fin_xy, .fin_count = dec.fin_count, .max_cand = b.max_cand,
+                                          .board = board_tables(ctx, b.charuco_nc), .slot_ids = ctx->recover_ids.as<uint32_t>(), .n_slots = b.recover_slots,
+                                          .dict = ctx->dict.as<uint64_t>(), .cfg = b.recover_cfg, .rec = ctx->recover_tmp.as<a3_marker>(),
+                                          .rec_cap = b.recover_cap, .rec_count = recovered}));
+        A3_HIP(launch_recover_merge(st, {.det = dec.markers, .det_cap = b.marker_cap, .det_per_frame = side_per_frame, .rec = ctx->recover_tmp.as<a3_marker>(),
+                                         .rec_cap = b.recover_cap, .rec_count = recovered, .n_frames = b.n, .out = ctx->markers_ptr, .out_cap = b.marker_cap,
+                                         .per_frame = ctx->per_frame, .marker_total = d_marker_total, .err_flags = &ctx->head->err_flags}));
+    }
     float* const refined = b.refined ? ctx->refined_buf.as<float>() : nullptr;
     if (b.refined)   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
         A3_HIP(launch_refine_corners(st, {.src = b.src, .W = b.W, .H = b.H, .markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap,
@@ -529,6 +559,7 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
         A3_HIP(stage(rb.charuco, ctx->charuco_buf.p));
         if (b.want_pose) A3_HIP(stage(rb.charuco_poses, ctx->charuco_pose_buf.p));
     }
+    if (b.recover) A3_HIP(stage(rb.recovered, recovered));
     if (b.taps) {   // Detection.candidates / .homographies will be asked for frame by frame: their counts travel now
         A3_HIP(hipMemcpyAsync(ctx->pinned_counts, ctx->cand_count, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
         A3_HIP(hipMemcpyAsync((uint8_t*)ctx->pinned_counts + (size_t)b.n * 4, ctx->fin_count.p, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
@@ -607,6 +638,12 @@ int ensure_back_buffers(a3_ctx* ctx, Batch& b, size_t head_bytes) {
         A3_HIP(ctx->charuco_buf.ensure(std::max<size_t>(recs, 1) * sizeof(a3_charuco_corner)));
         if (b.want_pose) A3_HIP(ctx->charuco_pose_buf.ensure((size_t)b.n * sizeof(a3_charuco_pose)));
         if (b.want_pose && b.undist) A3_HIP(ctx->charuco_und.ensure(std::max<size_t>(recs, 1) * 8));
+    }
+    if (b.recover) {
+        b.recover_cap = std::min(b.recover_slots, b.max_cand);
+        A3_HIP(ctx->recover_counts.ensure(16 + (size_t)b.n * 8));
+        A3_HIP(ctx->recover_det.ensure((size_t)b.marker_cap * sizeof(a3_marker)));
+        A3_HIP(ctx->recover_tmp.ensure((size_t)b.n * b.recover_cap * sizeof(a3_marker)));
     }
     if (int rc = ensure_pinned(ctx, pinned_bytes(b.rb))) return rc;
     if (b.taps && ctx->pinned_counts_cap < (size_t)b.n * 8) {
@@ -946,6 +983,10 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         const a3_board_pose* hb = at<a3_board_pose>(hp, rb.board);
         ctx->h_board.assign(hb, hb + n);
     }
+    if (b.recover) {   // (read now, as the board poses)
+        const uint32_t* hr = at<uint32_t>(hp, rb.recovered);
+        ctx->h_recovered.assign(hr, hr + n);
+    }
     if (b.charuco) {   // (read now, as the board poses)
         uint32_t charuco_total = 0;
         memcpy(&charuco_total, at<uint8_t>(hp, rb.charuco_total), 4);
@@ -990,6 +1031,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     }
     ctx->undist_valid = b.undist;
     ctx->board_valid = b.board;
+    ctx->recovered_valid = b.recover;
     ctx->charuco_valid = b.charuco;
     ctx->charuco_pose_valid = b.charuco && b.want_pose;
     if (b.taps) {
@@ -1346,6 +1388,16 @@ static int upload_board(a3_ctx* ctx) {
     return A3_OK;
 }
 
+// the board's ids in slot order, for the recovery stage, when they are not current (as upload_board)
+static int upload_recover_ids(a3_ctx* ctx) {
+    if (ctx->recover_ids_version == ctx->board_version) return A3_OK;
+    ctx->recover_ids_up = ctx->board_ids;
+    A3_HIP(ctx->recover_ids.ensure(std::max<size_t>(ctx->recover_ids_up.size(), 1) * 4));
+    A3_HIP(hipMemcpyAsync(ctx->recover_ids.p, ctx->recover_ids_up.data(), ctx->recover_ids_up.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    ctx->recover_ids_version = ctx->board_version;
+    return A3_OK;
+}
+
 // the chessboard's device table for the ChArUco setting in force, when it is not current (as upload_board)
 static int upload_charuco(a3_ctx* ctx) {
     if (ctx->charuco_dev_version == ctx->charuco_version) return A3_OK;
@@ -1382,10 +1434,13 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
         b.charuco_guess = (uint32_t)std::min<uint64_t>((uint64_t)n_frames * b.charuco_nc,
                                                        (uint64_t)ctx->last_charuco_total + ctx->last_charuco_total / 4 + 64);
     }
+    b.recover = ctx->recover.mode != 0 && !ctx->board_ids.empty();
+    if (b.recover) { b.recover_cfg = ctx->recover; b.recover_slots = (uint32_t)ctx->board_ids.size(); }
     b.taps = ctx->debug_taps;
     b.sample_frames = ctx->debug_sample_frames;
     b.profiling = ctx->profiling; b.profile_every = ctx->profile_every;
     ctx->board_valid = false;
+    ctx->recovered_valid = false;
     ctx->undist_valid = false;
     ctx->charuco_valid = false; ctx->charuco_pose_valid = false;
     b.row_stride = row_stride; b.frame_stride = frame_stride;
@@ -1399,7 +1454,8 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
         b.pixels = ctx->rect_plane.as<uint8_t>(); b.fmt = A3_FMT_L8; b.W = (uint32_t)dw; b.H = (uint32_t)dh;
         b.row_stride = dw; b.frame_stride = dw * dh;
     }
-    if (b.board || b.charuco) { if (int urc = upload_board(ctx)) return urc; }
+    if (b.board || b.charuco || b.recover) { if (int urc = upload_board(ctx)) return urc; }
+    if (b.recover) { if (int urc = upload_recover_ids(ctx)) return urc; }
     if (b.charuco) { if (int urc = upload_charuco(ctx)) return urc; }
     ctx->hints.force_host_plan = false;
     ctx->reruns = 0; ctx->released_others = 0;
@@ -1412,6 +1468,7 @@ static void finish_trivial(a3_ctx* ctx, uint32_t* per_frame_count) {
     if (per_frame_count && b.n) memset(per_frame_count, 0, (size_t)b.n * 4);
     ctx->h_refined.clear(); ctx->refined_valid = b.refined;
     ctx->h_board.assign(b.n, a3_board_pose{}); ctx->board_valid = b.board;
+    ctx->h_recovered.assign(b.n, 0u); ctx->recovered_valid = b.recover;
     ctx->h_undist.clear(); ctx->h_undist_res.clear(); ctx->undist_valid = b.undist;
     ctx->h_charuco.clear(); ctx->charuco_valid = b.charuco;
     ctx->h_charuco_pose.assign(b.want_pose ? b.n : 0, a3_charuco_pose{}); ctx->charuco_pose_valid = b.charuco && b.want_pose;
@@ -2139,6 +2196,7 @@ int a3_set_board(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size
     ctx->board_ids.assign(ids, ids + n);
     ctx->board_slots.swap(slots);
     ctx->board_version++;
+    if (n == 0) ctx->recover = a3_recover_config{};   // (recovery needs a board)
     ctx->charuco_nc = 0;   // (a ChArUco setting names ids of the board it was checked against)
     ctx->charuco_tab_h.clear();
     ctx->charuco_version++;
@@ -2180,6 +2238,112 @@ int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corner
                                            .intr = intr, .W = image_width, .H = image_height, .out = res.at(s_out)}));
     A3_HIP(res.download(s_out, out));
     A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+// ---- board-aided recovery (an extension beyond the reference; contract in include/aruco3_hip.h) ----
+// the largest h with sum over k <= h of C(bits, k) * 1000 < 2^bits, in integers; 0 when no h does
+static uint8_t recover_default_hamming(uint32_t bits) {
+    if (bits == 0 || bits > 64) return 0;
+    const unsigned __int128 space = (unsigned __int128)1 << bits;
+    unsigned __int128 sum = 0, term = 1;   // C(bits, k)
+    uint8_t h = 0;
+    for (uint32_t k = 0; k <= bits; k++) {
+        sum += term;
+        if (sum * 1000 >= space) break;
+        h = (uint8_t)k;
+        term = term * (bits - k) / (k + 1);
+    }
+    return h;
+}
+
+int a3_default_recover_config(const a3_ctx* ctx, a3_recover_config* cfg) {
+    if (!ctx || !cfg) return A3_ERR_INVALID;
+    *cfg = a3_recover_config{};
+    cfg->mode = 1; cfg->min_markers = 2; cfg->max_distance_px = 10.0f;
+    cfg->max_hamming = recover_default_hamming(ctx->num_bits);
+    return A3_OK;
+}
+
+static int check_recover_config(a3_ctx* ctx, const a3_recover_config& c, const char* who) {
+    const char* what = nullptr;
+    if (c.mode > 1) what = "mode must be 0 or 1";
+    else if (c.min_markers == 0) what = "min_markers must be at least 1";
+    else if (!std::isfinite(c.max_distance_px) || !(c.max_distance_px > 0.0f)) what = "max_distance_px must be finite and > 0";
+    else if (c.reserved[0] || c.reserved[1] || c.reserved[2]) what = "reserved bytes must be 0";
+    if (!what) return A3_OK;
+    return fail(ctx, A3_ERR_INVALID, (std::string(who) + ": a3_recover_config." + what).c_str());
+}
+
+int a3_set_board_recovery(a3_ctx* ctx, const a3_recover_config* cfg) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (ctx->busy()) return fail(ctx, A3_ERR_INVALID, "a3_set_board_recovery: a submitted batch has not been collected");
+    if (!cfg || cfg->mode == 0) { ctx->recover = a3_recover_config{}; return A3_OK; }
+    if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_set_board_recovery: no board is set (a3_set_board)");
+    if (int rc = check_recover_config(ctx, *cfg, "a3_set_board_recovery")) return rc;
+    ctx->recover = *cfg;
+    return A3_OK;
+}
+
+int a3_get_board_recovery(const a3_ctx* ctx, a3_recover_config* cfg) {
+    if (!ctx || !cfg) return A3_ERR_INVALID;
+    *cfg = ctx->recover;
+    return A3_OK;
+}
+
+int a3_get_recovered_counts(a3_ctx* ctx, uint32_t* per_frame_recovered, size_t n_frames) {
+    if (!ctx || (!per_frame_recovered && n_frames)) return A3_ERR_INVALID;
+    size_t n = 0;
+    return get_last(ctx, ctx->recovered_valid, ctx->h_recovered, 1, per_frame_recovered, n_frames, &n,
+                    "a3_get_recovered_counts: the last collected batch ran without board recovery",
+                    "a3_get_recovered_counts: n_frames is smaller than the number of frames");
+}
+
+int a3_recover_markers(a3_ctx* ctx, const uint32_t* detected_ids, const uint32_t* detected_corners_xy, size_t n_detected,
+                       const uint32_t* candidate_corners_xy, const uint64_t* codes4, const uint8_t* has_codes, size_t n_candidates,
+                       const a3_recover_config* cfg, a3_marker* out, size_t out_cap, size_t* out_n) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!cfg || !out_n || (!out && out_cap) || (n_detected && (!detected_ids || !detected_corners_xy)) ||
+        (n_candidates && (!candidate_corners_xy || !codes4 || !has_codes)))
+        return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: null argument");
+    *out_n = 0;
+    if (ctx->busy()) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: a submitted batch has not been collected");
+    if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: no board is set (a3_set_board)");
+    if (cfg->mode != 1) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: a3_recover_config.mode must be 1");
+    if (int rc = check_recover_config(ctx, *cfg, "a3_recover_markers")) return rc;
+    if (n_detected > (1u << 20)) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: more than 2^20 detected markers in one call");
+    if (n_candidates > kMaxCandLimit) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: more than A3_MAX_CANDIDATES_PER_FRAME candidates");
+    for (size_t i = 0; i < 8 * n_candidates; i++)
+        if (candidate_corners_xy[i] > 0xFFFFu) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: a candidate corner is above 65535");
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    if (int urc = upload_board(ctx)) return urc;
+    if (int urc = upload_recover_ids(ctx)) return urc;
+    const uint32_t slots = (uint32_t)ctx->board_ids.size(), rec_cap = (uint32_t)std::min<size_t>(slots, std::max<size_t>(n_candidates, 1));
+    Layout in{ctx->tmp_a, ctx->stream}, res{ctx->tmp_b, ctx->stream};
+    const auto s_ids = in.add<uint32_t>(std::max<size_t>(n_detected, 1));   // (never an empty buffer)
+    const auto s_det = in.add<uint32_t>(8 * n_detected), s_cand = in.add<uint32_t>(8 * n_candidates);
+    const auto s_codes = in.add<uint64_t>(4 * n_candidates);
+    const auto s_has = in.add<uint8_t>(n_candidates);
+    const auto s_count = res.add<uint32_t>(1);
+    const auto s_rec = res.add<a3_marker>(rec_cap);
+    A3_HIP(in.ensure()); A3_HIP(res.ensure());
+    A3_HIP(in.upload(s_ids, detected_ids, n_detected)); A3_HIP(in.upload(s_det, detected_corners_xy, 8 * n_detected));
+    A3_HIP(in.upload(s_cand, candidate_corners_xy, 8 * n_candidates)); A3_HIP(in.upload(s_codes, codes4, 4 * n_candidates));
+    A3_HIP(in.upload(s_has, has_codes, n_candidates));
+    A3_HIP(launch_recover_frames(ctx->stream, {.ids = in.at(s_ids), .corners = in.at(s_det), .n = (uint32_t)n_detected, .n_frames = 1u,
+                                               .cand_xy = in.at(s_cand), .codes4 = in.at(s_codes), .has_codes = in.at(s_has), .n_cand = (uint32_t)n_candidates,
+                                               .board = board_tables(ctx, 0), .slot_ids = ctx->recover_ids.as<uint32_t>(), .n_slots = slots,
+                                               .dict = ctx->dict.as<uint64_t>(), .cfg = *cfg, .rec = res.at(s_rec), .rec_cap = rec_cap, .rec_count = res.at(s_count)}));
+    uint32_t count = 0;
+    A3_HIP(res.download(s_count, &count));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    *out_n = count;
+    if (count > out_cap) return fail(ctx, A3_ERR_CAPACITY, "a3_recover_markers: out_cap is smaller than the number of recovered markers");
+    if (count) {
+        A3_HIP(hipMemcpyAsync(out, res.at(s_rec), (size_t)count * sizeof(a3_marker), hipMemcpyDeviceToHost, ctx->stream));
+        A3_HIP(hipStreamSynchronize(ctx->stream));
+    }
     return A3_OK;
 }
 

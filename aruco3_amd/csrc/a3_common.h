@@ -76,4 +76,14 @@ struct CandRec {
     uint16_t xy[8];
 };
 
+// what k_decode leaves per final candidate slot (k_decode.hip writes it; the marker gather and k_recover.hip read it)
+struct DecodeOut {
+    uint64_t code;
+    uint64_t codes[4];
+    uint32_t id;
+    uint8_t valid, rotation, hamming, hom_ok;
+    int32_t decode_ok;
+    uint32_t patch;   // debug taps: index of this candidate's warped patch in the patch buffer, kNone if it was not kept
+};
+
 }  // namespace a3

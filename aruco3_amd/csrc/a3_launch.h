@@ -177,6 +177,34 @@ struct BoardPoseLaunch {
 };
 hipError_t launch_board_pose(hipStream_t st, const BoardPoseLaunch& b);
 
+// ---- k_recover.hip ------------------------------------------------------------------------------------------------------------------
+// Board-aided recovery (a3_set_board_recovery).  Stage 1, one workgroup per frame: the board markers no marker of the frame carries,
+// matched to the frame's rejected candidates; frame f's records go to rec[f * rec_cap ...] in candidate order, their number to
+// rec_count[f].  Detected markers: a batch's list (markers != nullptr: capacity n, count n_dev, per_frame[n_frames]) or one frame of n
+// caller markers (ids, corners: 8 u32 each).  Candidates: a batch's (outs != nullptr: DecodeOut and fin_xy records, max_cand slots per
+// frame, fin_count[n_frames]; those with valid == 0 are eligible) or one frame of n_cand caller quads (cand_xy: 8 u32 each, codes4: 4 each,
+// has_codes: 1 each; all eligible).  slot_ids: the board's ids in slot order (n_slots <= A3_BOARD_MAX_MARKERS); rec_cap >= min(n_slots,
+// candidates per frame).
+struct RecoverLaunch {
+    const a3_marker* markers = nullptr; const unsigned int* n_dev = nullptr; const uint32_t* per_frame = nullptr; const uint32_t* ids = nullptr;
+    const uint32_t* corners = nullptr; uint32_t n = 0, n_frames = 0;
+    const void* outs = nullptr; const uint16_t* fin_xy = nullptr; const uint32_t* fin_count = nullptr; uint32_t max_cand = 0;
+    const uint32_t* cand_xy = nullptr; const uint64_t* codes4 = nullptr; const uint8_t* has_codes = nullptr; uint32_t n_cand = 0;
+    BoardTables board; const uint32_t* slot_ids = nullptr; uint32_t n_slots = 0; const uint64_t* dict = nullptr;
+    a3_recover_config cfg{};
+    a3_marker* rec = nullptr; uint32_t rec_cap = 0; uint32_t* rec_count = nullptr;
+};
+hipError_t launch_recover_frames(hipStream_t st, const RecoverLaunch& r);
+// Stage 2, one workgroup per frame: the merged list -- per frame the detected markers (det: capacity det_cap, det_per_frame[n_frames]) in
+// their order, then stage 1's records -- into out (capacity out_cap), its counts into per_frame and its total into *marker_total;
+// a total above out_cap raises kErrMarkerCap in *err_flags and nothing is stored past the capacity.
+struct RecoverMergeLaunch {
+    const a3_marker* det = nullptr; uint32_t det_cap = 0; const uint32_t* det_per_frame = nullptr; const a3_marker* rec = nullptr; uint32_t rec_cap = 0;
+    const uint32_t* rec_count = nullptr; uint32_t n_frames = 0; a3_marker* out = nullptr; uint32_t out_cap = 0; uint32_t* per_frame = nullptr;
+    unsigned int* marker_total = nullptr, * err_flags = nullptr;
+};
+hipError_t launch_recover_merge(hipStream_t st, const RecoverMergeLaunch& m);
+
 // ---- k_charuco.hip ------------------------------------------------------------------------------------------------------------------
 // The corner stage of m's frames (m.corners: the batch's refined corners or nullptr).  slots_tmp: n_frames x nc records; counts:
 // n_frames + 1; out: n_frames x nc records; und (nullable, with intr and dist): 2 floats per record.

@@ -10,9 +10,10 @@
 namespace a3 {
 
 // what the batch record knows: frames, markers and ChArUco records read back speculatively, the bytes of the head, what is switched on
-struct ReadbackShape { uint32_t n, guess, charuco_guess; size_t head_bytes; bool pose, refine, undist, board, charuco; };
+// (recover: the batch ran board-aided recovery -- one count per frame travels behind everything else)
+struct ReadbackShape { uint32_t n, guess, charuco_guess; size_t head_bytes; bool pose, refine, undist, board, charuco; bool recover = false; };
 struct Span { size_t off = 0, bytes = 0; };
-struct Readback { Span head, markers, poses, refined, board, undist, undist_res, charuco_total, charuco, charuco_poses; size_t end = 0; };
+struct Readback { Span head, markers, poses, refined, board, undist, undist_res, charuco_total, charuco, charuco_poses; size_t end = 0; Span recovered; };
 template <typename T> inline T* at(void* base, const Span& s) { return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + s.off); }
 
 // The spans follow each other in this order without padding; the span of a feature that is off is empty.
@@ -29,12 +30,13 @@ inline Readback readback_layout(const ReadbackShape& s) {
     put(r.charuco_total, s.charuco, 1, 16);   // the record count in the first 4 bytes of a 16-byte slot
     put(r.charuco, s.charuco, s.charuco_guess, sizeof(a3_charuco_corner));
     put(r.charuco_poses, s.charuco && s.pose, s.n, sizeof(a3_charuco_pose));   // one per frame
+    put(r.recovered, s.recover, s.n, sizeof(uint32_t));   // recovered markers per frame (last: every span before it lies where it lay)
     return r;
 }
-// The marker guess was short: head, board poses and ChArUco results have been consumed, and the whole list of `total` markers is
+// The marker guess was short: head, board poses, ChArUco results and recovered counts have been consumed, and the whole list of `total` markers is
 // fetched to the start of the buffer: markers, poses, refined corners, undistorted corners, residuals.
 inline Readback refetch_layout(ReadbackShape s, uint32_t total) {
-    s.head_bytes = 0; s.guess = total; s.board = s.charuco = false;
+    s.head_bytes = 0; s.guess = total; s.board = s.charuco = s.recover = false;
     return readback_layout(s);
 }
 // what is asked of the pinned allocation for a layout: 64 KB of slack behind its end

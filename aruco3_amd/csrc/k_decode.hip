@@ -186,14 +186,7 @@ __global__ __launch_bounds__(64, kFcWaves) void k_frame_candidates(const CandRec
 // ---------------------------------------------------------------------------------------
 // decode one candidate per workgroup
 // ---------------------------------------------------------------------------------------
-struct DecodeOut {      // one per final candidate slot
-    uint64_t code;
-    uint64_t codes[4];
-    uint32_t id;
-    uint8_t valid, rotation, hamming, hom_ok;
-    int32_t decode_ok;
-    uint32_t patch;   // debug taps: index of this candidate's warped patch in the patch buffer, kNone if it was not kept
-};
+// (DecodeOut, one per final candidate slot: a3_common.h -- k_recover.hip reads the records too)
 
 // imageproc Projection::from_control_points: 8x8 system in f64, LU with partial pivoting (nalgebra order of
 // operations), cast to f32, adjugate inverse normalised by its last element.  Single lane.

@@ -364,6 +364,73 @@ int  a3_get_board_poses(a3_ctx *ctx, a3_board_pose *dst, size_t cap_frames, size
 int  a3_estimate_board_pose(a3_ctx *ctx, const uint32_t *ids, const float *corners_xy, size_t n_markers, const a3_intrinsics *intr,
                             uint32_t image_width, uint32_t image_height, a3_board_pose *out);
 
+/* Board-aided recovery of markers the decoder rejected.  NOT in the reference: an opt-in extension (OpenCV's refineDetectedMarkers),
+ * off by default; with it off no launch, buffer, copy or result of a batch changes.  With a board set (a3_set_board, with or without
+ * a3_set_charuco) and recovery on, every a3_detect_batch* batch runs one more stage on the device, right behind the marker gather and
+ * ahead of everything that reads the marker list (k_recover_frames, one workgroup per frame; k_recover_merge).  Per frame, fixed to
+ * the bit as follows -- tests/recover_oracle.c a3o_recover_markers restates it.  Arithmetic is f64 (inputs converted exactly), every
+ * expression evaluated as C parses it, no fused multiply-add, division and sqrt correctly rounded.
+ *   1. frame homography.  The frame's detected markers whose id is on the board, in list order; an id seen more than once in the
+ *      frame is excluded in all its instances, as the board pose excludes it.  k of them are left; k < min_markers: nothing is
+ *      recovered.  Their 4 k correspondences, marker after marker, corner 0..3: board corner (x, y) of the marker's slot (the floats
+ *      a3_set_board was given) -> the marker's integer pixel corner, both converted to float.  H (board plane -> pixels, row-major,
+ *      H22 = 1) is step 1 of the calibration contract below (normalised DLT, a3_calibrate_cameras); a DEGENERATE verdict there:
+ *      nothing is recovered.
+ *   2. expected corners.  A board marker is MISSING when no marker of the frame carries its id.  For each, in slot order, and each
+ *      of its corners j = 0..3 at (X, Y): u = (H0 X + H1 Y) + H2, v = (H3 X + H4 Y) + H5, w = (H6 X + H7 Y) + H8; e_j = (u / w, v / w).
+ *      A marker with some w <= 0, or a w, u / w or v / w that is not finite, is skipped.
+ *   3. feasible pairs.  The candidates are the frame's final candidates (Detection.candidates: after discard_too_near, index c in
+ *      that list) that did not become a marker.  For a missing marker m, a candidate c with corners q_0..q_3 and a cyclic shift
+ *      r = 0..3: d2(m, c, r) = the largest over j of dx dx + dy dy, dx = e_j.x - q_((j + r) mod 4).x, dy likewise -- the corner
+ *      convention of a3_marker.corners after rotate_left(r).  The pair is feasible when d2 <= (double)max_distance_px *
+ *      (double)max_distance_px and the bit test passes: the candidate has codes (its projection was solved and its border was
+ *      black all round: the ok and decode_ok of a3_download_homographies) and popcount(codes4[r] ^ dictionary[id_m]) <= max_hamming.
+ *      max_hamming == 255: bits are not compared, and candidates without codes are eligible too.
+ *   4. assignment, one pass.  Each missing marker takes its feasible (c, r) of smallest d2 (ties: the lowest c, then the lowest r).
+ *      A candidate taken by several markers goes to the one with the smallest d2 (ties: the lowest board slot); the others
+ *      recover nothing.
+ *   5. record.  An a3_marker: frame, id = id_m, code = codes4[r] (0 for a candidate without codes), corners[i] = q_((i + r) mod 4),
+ *      rotation = r, candidate_index = c, hamming_distance = the popcount (255 when bits were not compared).
+ *   6. delivery.  The batch's marker list is the merged one: per frame the detected markers in their order, then the recovered
+ *      ones in candidate order.  out, per_frame_count and out_n of every detect, pose, submit and collect call describe it (out_cap
+ *      below the merged total: A3_ERR_CAPACITY), and so does everything computed from the list: refined and undistorted corners,
+ *      marker, board and ChArUco poses, ChArUco corners, a3_pack_detections.  a3_get_recovered_counts says how many markers at
+ *      the tail of each frame's segment are recovered ones.
+ * The expected positions come from a plain homography: under strong lens distortion set a3_set_rectification or raise
+ * max_distance_px.  Cost: missing markers x rejected candidates x 4 shifts per frame, a few thousand pair tests for an ordinary frame
+ * (one wave per missing marker, its lanes over the candidates); the assignment compares the missing markers pairwise.  It stays
+ * correct, and gets slow, up to A3_BOARD_MAX_MARKERS missing markers and A3_MAX_CANDIDATES_PER_FRAME candidates.
+ * a3_default_recover_config: mode 1, min_markers 2, max_distance_px 10, and max_hamming = the largest h for which a uniformly random
+ * num_bits-bit code lies within h of one fixed code with probability below 1e-3, that is sum over k <= h of C(num_bits, k) * 1000 <
+ * 2^num_bits in integers (0 when no h does) -- a derivation, not a tuned number; the geometry fixes the rotation, so one comparison
+ * per pair is made.  For the named dictionaries: 16 bits (APRILTAG_16H5, ARUCO_MIP_16H3) 1; 25 bits (ARUCO, ARUCO_DEFAULT,
+ * ARUCO_MIP_25H7, APRILTAG_25H7, APRILTAG_25H9) 4; 36 bits (ARUCO_MIP_36H12, APRILTAG_36H9 / 36H10 / 36H11, ARTAG, ARTOOLKITPLUS,
+ * ARTOOLKITPLUSBCH) 8; 64 bits (CHILITAGS) 19. */
+typedef struct a3_recover_config {
+    uint32_t mode;             /* 0 off, 1 on */
+    uint32_t min_markers;      /* detected board markers a frame needs, >= 1 */
+    float    max_distance_px;  /* finite, > 0 */
+    uint8_t  max_hamming;      /* 255: bits are not compared */
+    uint8_t  reserved[3];      /* 0 */
+} a3_recover_config;
+int  a3_default_recover_config(const a3_ctx *ctx, a3_recover_config *cfg);
+/* applies to batches submitted after the call; cfg NULL or mode 0 clears it (a3_set_board with n == 0 clears it too).
+ * A3_ERR_INVALID: a submitted batch of the context is in flight (a batch keeps the setting it was submitted with, as with
+ * a3_set_rectification), no board is set, mode above 1, min_markers 0, max_distance_px not finite or not > 0, a reserved byte set. */
+int  a3_set_board_recovery(a3_ctx *ctx, const a3_recover_config *cfg);
+int  a3_get_board_recovery(const a3_ctx *ctx, a3_recover_config *cfg);   /* mode 0 and zeros: none */
+/* the recovered markers of each frame of the last collected batch (the tail of the frame's segment of the list).  A3_ERR_INVALID
+ * when that batch ran without recovery, A3_ERR_CAPACITY when n_frames is smaller than its frame count. */
+int  a3_get_recovered_counts(a3_ctx *ctx, uint32_t *per_frame_recovered, size_t n_frames);
+/* stand-alone, one frame of caller-given lists, on the same kernel and arithmetic: n_detected markers (ids, 8 integer pixel corners
+ * each) and n_candidates rejected quads (8 integer pixel corners each, below 65536; codes4: their four rotated codes, 4 per
+ * candidate; has_codes: 1 per candidate, 0 = none); every candidate given is eligible, index c is its position.  out: room for
+ * out_cap records (frame 0), *out_n their number (at most min(board markers, n_candidates); a smaller out_cap: A3_ERR_CAPACITY).
+ * cfg as the setter takes it (mode must be 1).  Needs a board; synchronous; not while a submitted batch is in flight. */
+int  a3_recover_markers(a3_ctx *ctx, const uint32_t *detected_ids, const uint32_t *detected_corners_xy, size_t n_detected,
+                        const uint32_t *candidate_corners_xy, const uint64_t *codes4, const uint8_t *has_codes, size_t n_candidates,
+                        const a3_recover_config *cfg, a3_marker *out, size_t out_cap, size_t *out_n);
+
 /* Lens distortion.  NOT in the reference (every pose it returns assumes an ideal pinhole camera, src/pose.rs:58): an opt-in extension,
  * off by default; with it off no launch, buffer, copy or result of a batch changes.  The model is OpenCV's rational one (k1 k2 p1 p2 k3
  * k4 k5 k6; a 5-coefficient calibration has k4 = k5 = k6 = 0) or its fisheye one (A3_DIST_FISHEYE, stated after the rational

@@ -510,6 +510,18 @@ pub struct A3MapObservationResult {
     pub start_rms_px: [f32; 2],
 }
 
+/// a3_recover_config: board-aided recovery of markers the decoder rejected (not in the reference; include/aruco3_hip.h states the
+/// algorithm; OpenCV's refineDetectedMarkers).  Fill it with a3_default_recover_config: max_hamming is derived from the dictionary.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3RecoverConfig {
+    pub mode: u32,
+    pub min_markers: u32,
+    pub max_distance_px: f32,
+    pub max_hamming: u8,
+    pub reserved: [u8; 3],
+}
+
 /// a3_rectify: one frame rectification (not in the reference; include/aruco3_hip.h states the map and the blend)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -641,6 +653,13 @@ extern "C" {
     pub fn a3_get_board_poses(ctx: *mut A3Ctx, dst: *mut A3BoardPose, cap_frames: usize, n: *mut usize) -> c_int;
     pub fn a3_estimate_board_pose(ctx: *mut A3Ctx, ids: *const u32, corners_xy: *const f32, n_markers: usize, intr: *const A3Intrinsics,
                                   image_width: u32, image_height: u32, out: *mut A3BoardPose) -> c_int;
+    pub fn a3_default_recover_config(ctx: *const A3Ctx, cfg: *mut A3RecoverConfig) -> c_int;
+    pub fn a3_set_board_recovery(ctx: *mut A3Ctx, cfg: *const A3RecoverConfig) -> c_int;
+    pub fn a3_get_board_recovery(ctx: *const A3Ctx, cfg: *mut A3RecoverConfig) -> c_int;
+    pub fn a3_get_recovered_counts(ctx: *mut A3Ctx, per_frame_recovered: *mut u32, n_frames: usize) -> c_int;
+    pub fn a3_recover_markers(ctx: *mut A3Ctx, detected_ids: *const u32, detected_corners_xy: *const u32, n_detected: usize,
+                              candidate_corners_xy: *const u32, codes4: *const u64, has_codes: *const u8, n_candidates: usize,
+                              cfg: *const A3RecoverConfig, out: *mut A3Marker, out_cap: usize, out_n: *mut usize) -> c_int;
     pub fn a3_default_distortion(d: *mut A3Distortion);
     pub fn a3_set_distortion(ctx: *mut A3Ctx, d: *const A3Distortion) -> c_int;
     pub fn a3_get_undistorted_corners(ctx: *mut A3Ctx, dst_xy: *mut f32, residual_px: *mut f32, cap_markers: usize, n: *mut usize) -> c_int;
