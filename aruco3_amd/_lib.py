@@ -77,8 +77,9 @@ SYMBOLS = [
 ]
 CAND_DTYPE = np.dtype([("start_key", "<u4"), ("xy", "<u2", (8,))])      # a3_debug_cand (a3_internal.h)
 PROJ_DTYPE = np.dtype([("inv", "<f4", (9,)), ("ok", "<i4")])            # A3_DEBUG_PROJ_BYTES
+CONTOUR_DTYPE = np.dtype([("frame", "<u4"), ("start_key", "<u4"), ("point_base", "<u4"), ("n", "<u4")])   # a3_debug_contour
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
-INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates", "a3_debug_sample_frames", "a3_debug_frame_candidates"]
+INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates", "a3_debug_sample_frames", "a3_debug_frame_candidates", "a3_debug_contour_quads"]
 
 
 class A3Error(RuntimeError):
@@ -518,6 +519,10 @@ def load():
         L.a3_debug_frame_candidates.restype = C.c_int
         L.a3_debug_frame_candidates.argtypes = [vp, C.c_uint32, C.c_uint32, u32p, vp, C.c_float, C.c_uint32, C.POINTER(C.c_uint16),
                                                 C.POINTER(C.c_uint16), u32p, u32p, u32p, vp]
+    if hasattr(L, "a3_debug_contour_quads"):         # (likewise)
+        L.a3_debug_contour_quads.restype = C.c_int
+        L.a3_debug_contour_quads.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_size_t, u32p, vp, u32p]
     _lib = L
     return L
 
@@ -1110,6 +1115,26 @@ class Context:
                                                _p(pre, C.c_uint16), _p(fin, C.c_uint16), _p(fin_count, C.c_uint32), _p(work, C.c_uint32),
                                                _p(work_count, C.c_uint32), proj.ctypes.data if S else None), self.handle)
         return {"pre_xy": pre, "fin_xy": fin, "fin_count": fin_count, "work": work, "work_count": int(work_count[0]), "proj": proj if S else None}
+
+    def debug_contour_quads(self, width: int, height: int, records: np.ndarray, points: np.ndarray, *, eps_factor: float = 0.05,
+                            min_edge_length: int = 0, n_darts: int = 0, first_frame: int = 0, n_frames: int = 1, max_cand: int = 1024,
+                            max_contours: int = None, ctr_contours: int = None, ctr_err_flags: int = 0) -> dict:
+        """a3_debug_contour_quads: one launch of k_contour_quads, as the pipeline makes it, on a hand-made contour table.
+        records: CONTOUR_DTYPE in table order; points: the pool, x | y << 16; max_contours and ctr_contours default to the record count.
+        Returns whole tables -- what the kernel did not write is 0xFF bytes: cand_count (first_frame + n_frames u32), cands (CAND_DTYPE,
+        first_frame + n_frames x max_cand) and the kernel's err_flags word."""
+        rec = np.ascontiguousarray(records, dtype=CONTOUR_DTYPE).reshape(-1)
+        pts = np.ascontiguousarray(points, dtype=np.uint32).reshape(-1)
+        frames = first_frame + n_frames
+        ok = 1 <= max_cand <= 65536 and 1 <= n_frames <= 65536 and 0 <= first_frame <= 65536 and frames * max_cand <= 1 << 24
+        cnt = np.empty(frames if ok else 1, dtype=np.uint32)      # (out of range: the library refuses before it writes)
+        cands = np.empty((frames, max_cand) if ok else (1, 1), dtype=CAND_DTYPE)
+        err = np.zeros(1, dtype=np.uint32)
+        check(load().a3_debug_contour_quads(self.handle, width, height, n_darts, eps_factor, min_edge_length, first_frame, n_frames, max_cand,
+                                            len(rec) if max_contours is None else max_contours, len(rec) if ctr_contours is None else ctr_contours,
+                                            ctr_err_flags, rec.ctypes.data if rec.size else None, len(rec), pts.ctypes.data if pts.size else None,
+                                            pts.size, _p(cnt, C.c_uint32), cands.ctypes.data, _p(err, C.c_uint32)), self.handle)
+        return {"cand_count": cnt, "cands": cands, "err_flags": int(err[0])}
 
     # ---- pose ----
     def estimate_pose(self, corners: np.ndarray, marker_size_mm: float, image_size=None, intrinsics: Intrinsics = None) -> np.ndarray:

@@ -2077,6 +2077,79 @@ int a3_debug_frame_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t max_cand,
     return A3_OK;
 }
 
+// k_contour_quads as the pipeline launches it -- ONE call of launch_contour_quads with a ContourChunk filled from the arguments -- on a
+// hand-made contour table and point pool, on buffers of its own (freed on return: nothing of the context's changes).  Whatever the
+// pipeline could never hand the kernel is refused here, because the kernel trusts its tables: it checks no index.
+int a3_debug_contour_quads(a3_ctx* ctx, uint32_t width, uint32_t height, uint32_t n_darts, double eps_factor, uint32_t min_edge_length,
+                           uint32_t first_frame, uint32_t n_frames, uint32_t max_cand, uint32_t max_contours, uint32_t ctr_contours,
+                           uint32_t ctr_err_flags, const a3_debug_contour* records, uint32_t n_records, const uint32_t* points, size_t n_points,
+                           uint32_t* cand_count, a3_debug_cand* cands, uint32_t* err_flags) {
+    static_assert(sizeof(a3_debug_contour) == sizeof(ContourRec) && sizeof(ContourRec) == 16, "a3_debug_contour is a ContourRec");
+    static_assert(sizeof(a3_debug_cand) == sizeof(CandRec), "a3_debug_cand is a CandRec");
+    if (!ctx) return A3_ERR_INVALID;
+    if (!cand_count || !cands || !err_flags || (n_records && (!records || !points)))
+        return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: a NULL argument");
+    if (width == 0 || width > 65536u || height == 0 || height > 65536u)
+        return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: width and height must be in 1..65536");
+    if (n_frames == 0 || n_frames > kMaxChunkFrames || first_frame > kMaxChunkFrames)
+        return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: n_frames must be in 1..65536 and first_frame at most 65536");
+    if (max_cand == 0 || max_cand > kMaxCandLimit) return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: max_cand must be in 1..65536");
+    if (!std::isfinite(eps_factor) || eps_factor < 0.0) return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: eps_factor must be finite and >= 0");
+    const size_t frames = (size_t)first_frame + n_frames, slots = frames * max_cand;
+    if (slots > ((size_t)1 << 24)) return fail(ctx, A3_ERR_LIMIT, "a3_debug_contour_quads: more than 2^24 slots");
+    if (n_points >= ((size_t)1 << 30)) return fail(ctx, A3_ERR_LIMIT, "a3_debug_contour_quads: the point pool must hold fewer than 2^30 points");
+    // every record the kernel may read exists -- unless the counters carry the flags on which it reads none
+    const bool stale = (ctr_err_flags & (kErrPointPool | kErrContourTable)) != 0;
+    if (!stale && std::min(ctr_contours, max_contours) > n_records)
+        return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: min(ctr_contours, max_contours) records must be given");
+    std::vector<uint64_t> keys(n_records);
+    for (uint32_t i = 0; i < n_records; i++) {
+        const a3_debug_contour& r = records[i];
+        if (r.n == 0) return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: a record with n == 0");
+        if ((uint64_t)r.point_base + r.n > n_points) return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: a record's points lie beyond the pool");
+        if (r.frame < first_frame || r.frame - first_frame >= n_frames)
+            return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: a record's frame lies outside [first_frame, first_frame + n_frames)");
+        keys[i] = ((uint64_t)r.frame << 32) | r.start_key;
+    }
+    std::sort(keys.begin(), keys.end());
+    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
+        return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: a frame's start keys must be unique");
+    for (size_t i = 0; i < n_points; i++)
+        if ((points[i] & 0xFFFFu) >= width || (points[i] >> 16) >= height)
+            return fail(ctx, A3_ERR_INVALID, "a3_debug_contour_quads: a coordinate lies outside width x height");
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    struct Own : DevBuf { ~Own() { release(); } } d_rec, d_pts, d_ctr, d_cands, d_cnt;
+    A3_HIP(d_rec.ensure(std::max<size_t>(n_records, 1) * sizeof(ContourRec)));
+    A3_HIP(d_pts.ensure(std::max<size_t>(n_points, 1) * 4));
+    A3_HIP(d_ctr.ensure(sizeof(DeviceCounters)));
+    A3_HIP(d_cands.ensure(slots * sizeof(CandRec)));
+    A3_HIP(d_cnt.ensure((frames + 1) * 4));   // cand_count | err_flags
+    DeviceCounters hc;
+    memset(&hc, 0, sizeof hc);
+    hc.contours = ctr_contours; hc.err_flags = ctr_err_flags;
+    uint32_t* cnt = d_cnt.as<uint32_t>();
+    hipStream_t st = ctx->stream;
+    if (n_records) A3_HIP(hipMemcpyAsync(d_rec.p, records, (size_t)n_records * sizeof(ContourRec), hipMemcpyHostToDevice, st));
+    if (n_points) A3_HIP(hipMemcpyAsync(d_pts.p, points, n_points * 4, hipMemcpyHostToDevice, st));
+    A3_HIP(hipMemcpyAsync(d_ctr.p, &hc, sizeof hc, hipMemcpyHostToDevice, st));
+    A3_HIP(hipMemsetAsync(d_cands.p, 0xFF, slots * sizeof(CandRec), st));
+    if (first_frame) A3_HIP(hipMemsetAsync(cnt, 0xFF, (size_t)first_frame * 4, st));
+    A3_HIP(hipMemsetAsync(cnt + first_frame, 0, ((size_t)n_frames + 1) * 4, st));   // the chunk's counts arrive zeroed, and so does the flag word
+    ContourChunk cc;
+    cc.first_frame = first_frame; cc.n_frames = n_frames; cc.n_darts = n_darts; cc.ctr = d_ctr.as<DeviceCounters>();
+    cc.W = (int)width; cc.H = (int)height; cc.batch_frames = (uint32_t)frames;
+    cc.min_edge_length = min_edge_length; cc.eps_factor = eps_factor; cc.contours = d_rec.as<ContourRec>(); cc.points = d_pts.as<uint32_t>();
+    cc.max_contours = max_contours; cc.max_points = n_points;
+    cc.cands = d_cands.as<CandRec>(); cc.cand_count = cnt; cc.max_cand = max_cand; cc.err_flags = cnt + frames;
+    A3_HIP(launch_contour_quads(st, cc));
+    A3_HIP(hipMemcpyAsync(cand_count, cnt, frames * 4, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(err_flags, cnt + frames, 4, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(cands, d_cands.p, slots * sizeof(CandRec), hipMemcpyDeviceToHost, st));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
 int a3_debug_inject_candidates(a3_ctx* ctx, const uint32_t* quads_xy, size_t n) {
     if (!ctx || (!quads_xy && n)) return A3_ERR_INVALID;
     if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_debug_inject_candidates: a submitted batch has not been collected");

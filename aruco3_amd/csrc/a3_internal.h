@@ -91,6 +91,30 @@ int  a3_debug_frame_candidates(a3_ctx *ctx, uint32_t n_frames, uint32_t max_cand
                                float min_distance, uint32_t S, uint16_t *pre_xy, uint16_t *fin_xy, uint32_t *fin_count, uint32_t *work,
                                uint32_t *work_count, void *proj);
 
+/* k_contour_quads (per traced border: Douglas-Peucker with the arg-max over a group's lanes, the hull of the four kept points, the
+ * squared-edge filter of quirk Q1, the winding fix) launched exactly as the pipeline launches it -- ONE call of launch_contour_quads with
+ * a ContourChunk filled from the arguments, so width and height pick the 24-bit or the 64-bit numerators and n_darts sizes the grid (160
+ * wave groups and 1024 16-lane groups at the least, 10240 and 65536 from 2^23 darts on) -- on a hand-made contour table and point pool.
+ * The product never calls it; tests/ do, because whole images cannot be made to hand the kernel a chosen border.
+ *   width, height in 1..65536; first_frame + n_frames frames of max_cand (1..65536) slots, at most 2^24 slots in all;
+ *   records[n_records]: {frame, start_key, point_base, n} in the table's order; points[n_points]: x | y << 16;
+ *   max_contours: the table's capacity as the kernel is told it; ctr_contours, ctr_err_flags: DeviceCounters::contours and ::err_flags
+ *   as the kernel finds them.  The kernel reads the first min(ctr_contours, max_contours) records; that many must be given, unless
+ *   ctr_err_flags carries kErrPointPool (2) or kErrContourTable (4), on which it reads none.
+ * Refused with A3_ERR_INVALID, because the kernel checks none of it and the pipeline never produces it: a record with n == 0 or with
+ * points beyond the pool, a frame outside [first_frame, first_frame + n_frames), a coordinate >= width or height, two records of one
+ * frame with the same start key, NULL arguments.
+ * Out: cand_count[first_frame + n_frames], cands[(first_frame + n_frames) * max_cand] and *err_flags (the kErr* word the kernel raises
+ * kErrCandTable = 8 in).  The tables are filled with 0xFF bytes first and the chunk's counts and the flag word zeroed, as the pipeline has
+ * them: a slot the kernel did not write, and every count and slot of a frame below first_frame, comes back as 0xFF.  Slot order within a
+ * frame is the order of an atomic and not part of the contract.  Runs on buffers of its own and frees them: the context's buffers and
+ * settings are what they were. */
+typedef struct { uint32_t frame, start_key, point_base, n; } a3_debug_contour;
+int  a3_debug_contour_quads(a3_ctx *ctx, uint32_t width, uint32_t height, uint32_t n_darts, double eps_factor, uint32_t min_edge_length,
+                            uint32_t first_frame, uint32_t n_frames, uint32_t max_cand, uint32_t max_contours, uint32_t ctr_contours,
+                            uint32_t ctr_err_flags, const a3_debug_contour *records, uint32_t n_records, const uint32_t *points, size_t n_points,
+                            uint32_t *cand_count, a3_debug_cand *cands, uint32_t *err_flags);
+
 #ifdef __cplusplus
 }
 #endif
