@@ -10,7 +10,7 @@ from .dictionaries import ARDictionary  # noqa: F401
 
 def __getattr__(name):
     # GPU-backed names are imported lazily so that table handling works without the .so
-    if name in ("Detector", "DetectorConfig", "Detection", "Marker", "Rectification"):
+    if name in ("Detector", "DetectorConfig", "Detection", "Marker", "Rectification", "Reduction"):
         from . import aruco
 
         return getattr(aruco, name)
@@ -48,6 +48,10 @@ def __getattr__(name):
         from . import rectify
 
         return rectify.rectify_frames
+    if name == "reduce_frames":
+        from . import reduce
+
+        return reduce.reduce_frames
     if name == "pose":
         import importlib
 

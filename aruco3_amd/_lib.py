@@ -74,6 +74,7 @@ SYMBOLS = [
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
     "a3_calibrate_cameras", "a3_calibrate_fisheye_cameras", "a3_calibrate_rigs", "a3_calibrate_hand_eyes", "a3_build_marker_maps",
     "a3_default_rectify", "a3_rectify_frames", "a3_set_rectification", "a3_get_rectification",
+    "a3_reduce_frames", "a3_set_reduction", "a3_get_reduction",
 ]
 CAND_DTYPE = np.dtype([("start_key", "<u4"), ("xy", "<u2", (8,))])      # a3_debug_cand (a3_internal.h)
 PROJ_DTYPE = np.dtype([("inv", "<f4", (9,)), ("ok", "<i4")])            # A3_DEBUG_PROJ_BYTES
@@ -281,6 +282,11 @@ class RectifyRec(C.Structure):
     """a3_rectify: one rectification (an extension beyond the reference; include/aruco3_hip.h states the map and the blend)"""
     _fields_ = [("src", Intrinsics), ("distortion", DistortionRec), ("dst", Intrinsics), ("rotation", C.c_float * 9), ("fill", C.c_uint8),
                 ("reserved", C.c_uint8 * 3)]
+
+
+class ReductionRec(C.Structure):
+    """a3_reduction: detection on frames reduced by `factor` (an extension beyond the reference; include/aruco3_hip.h states the plane)"""
+    _fields_ = [("factor", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class RectifyInfo(C.Structure):
@@ -508,6 +514,14 @@ def load():
         L.a3_rectify_frames.restype = C.c_int
         L.a3_rectify_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(RectifyRec), vp, C.c_int,
                                         C.c_size_t, C.c_size_t, C.POINTER(RectifyInfo)]
+    if hasattr(L, "a3_reduce_frames"):       # (likewise detection on reduced frames)
+        L.a3_reduce_frames.restype = C.c_int
+        L.a3_reduce_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, vp, C.c_int,
+                                       C.c_size_t, C.c_size_t]
+        L.a3_set_reduction.restype = C.c_int
+        L.a3_set_reduction.argtypes = [vp, C.POINTER(ReductionRec)]
+        L.a3_get_reduction.restype = C.c_int
+        L.a3_get_reduction.argtypes = [vp, C.POINTER(ReductionRec), C.POINTER(C.c_int)]
     if hasattr(L, "a3_set_rectification"):   # (likewise rectification inside the detect calls)
         L.a3_set_rectification.restype = C.c_int
         L.a3_set_rectification.argtypes = [vp, C.POINTER(RectifyRec)]
@@ -955,6 +969,25 @@ class Context:
                                        C.byref(r), C.c_void_p(dst_ptr), dst_memory, dst_row_stride, dst_frame_stride, C.byref(info)),
               self.handle)
         return info
+
+    # ---- detection on reduced frames ----
+    def set_reduction(self, r: "ReductionRec" = None):
+        """a3_set_reduction: every later detect call of this context detects on its frames reduced by r.factor and returns full-size
+        corners; None turns it off.  Refused while a submitted batch is in flight, and on a context with a rectification."""
+        check(load().a3_set_reduction(self.handle, C.byref(r) if r is not None else None), self.handle)
+
+    def reduction(self):
+        """a3_get_reduction -> the ReductionRec in force, or None"""
+        r, on = ReductionRec(), C.c_int(0)
+        check(load().a3_get_reduction(self.handle, C.byref(r), C.byref(on)), self.handle)
+        return r if on.value else None
+
+    def reduce_frames(self, src_ptr: int, src_memory: int, fmt: int, width: int, height: int, src_row_stride: int, src_frame_stride: int,
+                      n_frames: int, factor: int, dst_ptr: int, dst_memory: int, dst_row_stride: int, dst_frame_stride: int) -> None:
+        """a3_reduce_frames: n_frames frames of width x height at src_ptr -> grey planes of (width // factor) x (height // factor) bytes at
+        dst_ptr; synchronous"""
+        check(load().a3_reduce_frames(self.handle, C.c_void_p(src_ptr), src_memory, fmt, width, height, src_row_stride, src_frame_stride, n_frames,
+                                      factor, C.c_void_p(dst_ptr), dst_memory, dst_row_stride, dst_frame_stride), self.handle)
 
     # ---- camera calibration ----
     def _calibrate(self, symbol, cams, view_offsets, object_xy, image_xy, with_views):

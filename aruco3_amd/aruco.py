@@ -79,6 +79,33 @@ def _apply_rectification(ctx: _lib.Context, rectification: Optional[Rectificatio
 
 
 @dataclass
+class Reduction:
+    """Detection on reduced frames (a3_set_reduction; not in the reference): `Detector(reduction=Reduction(2))` thresholds, traces and
+    decodes the frames box-filtered to 1 / `factor` (2, 3 or 4) of their size -- the plane `reduce_frames` returns -- maps the integer
+    corners back up (f x + f // 2) and refines them, interpolates ChArUco corners and solves poses on the full-size frames.  For markers
+    that are large in the frame; the refinement window has to cover a start that is up to about factor + 1 px off."""
+    factor: int
+
+    def _c(self) -> _lib.ReductionRec:
+        from .reduce import reduction_rec
+
+        return reduction_rec(self.factor)
+
+
+def _apply_reduction(ctx: _lib.Context, reduction: Optional[Reduction]) -> None:
+    """hands a reduction setting to a context that has no batch in flight (the setter is refused otherwise): only on a change"""
+    key = None if reduction is None else bytes(reduction._c())
+    if getattr(ctx, "_reduction_key", None) != key:
+        ctx.set_reduction(None if reduction is None else reduction._c())
+        ctx._reduction_key = key
+
+
+def _one_view(reduction, rectification) -> None:
+    if reduction is not None and rectification is not None:
+        raise ValueError("a detector takes a reduction or a rectification, not both (a3_set_reduction refuses the pair)")
+
+
+@dataclass
 class Marker:
     """src/aruco.rs:8-13, plus whether the marker was recovered through the board (an extension), the refined corners when the detector refines them and the undistorted corners (with their residuals in
     pixels, +inf: not undistorted) when a pose call's intrinsics carry a lens distortion (extensions; None otherwise)"""
@@ -145,7 +172,8 @@ class Detector:
 
     def __init__(self, config: DetectorConfig = None, dictionary: ARDictionary = None, device: int = 0,
                  refinement: Optional[CornerRefinement] = None, board=None, charuco_config: Optional[_lib.CharucoConfig] = None,
-                 rectification: Optional[Rectification] = None, recovery=None):
+                 rectification: Optional[Rectification] = None, recovery=None, reduction: Optional[Reduction] = None):
+        _one_view(reduction, rectification)
         if recovery is not None and board is None:
             raise ValueError("Detector(recovery=...) needs a board: recovery places rejected quads where the board says its markers are")
         self.config = config or DetectorConfig()
@@ -159,6 +187,8 @@ class Detector:
         self.rectification = rectification
         # aruco3_amd.board.BoardRecovery: board markers the decoder rejected are recovered on the device (Marker.recovered)
         self.recovery = recovery
+        # the front half of every call runs on the frames reduced by this factor; corners, refinement and poses are full-size
+        self.reduction = reduction
         self._ctx = None
         self._ctx_key = None
 
@@ -201,12 +231,16 @@ class Detector:
             raise ValueError("the detector rectifies its frames: pass the view's plain intrinsics (no `distortion`) to the pose calls")
 
     def _context(self) -> _lib.Context:
+        _one_view(self.reduction, self.rectification)
         key = (tuple(vars(self.config).items()), id(self.dictionary), self.device)
         if self._ctx is None or self._ctx_key != key:
             d = self.dictionary
             self._ctx = _lib.Context(self.config._c(), d.code_list, d.num_bits, d._tau, self.device)
             self._ctx_key = key
+        if self.reduction is None:   # (one of the two at a time: the one that goes is turned off first)
+            _apply_reduction(self._ctx, None)
         _apply_rectification(self._ctx, self.rectification)
+        _apply_reduction(self._ctx, self.reduction)
         return self._ctx
 
     # src/aruco.rs:52-121
@@ -239,7 +273,8 @@ class Detector:
                 det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, recovered=_is_tail(rec, f, i - pos, per)))
             pos += int(per[f])
             if populate:
-                det.grey = ctx.download_grey(f, *(self.rectification.view_size if self.rectification is not None else (w, h)))
+                view = (w // self.reduction.factor, h // self.reduction.factor) if self.reduction is not None else (w, h)
+                det.grey = ctx.download_grey(f, *(self.rectification.view_size if self.rectification is not None else view))
                 det.candidates = [[(int(x), int(y)) for x, y in q] for q in ctx.candidates(f)]
                 patches, ok, _, _ = ctx.homographies(f)
                 det.homographies = [p if o else np.zeros((1, 1), np.uint8) for p, o in zip(patches, ok)]  # src/aruco.rs:256
@@ -450,12 +485,14 @@ class BatchQueue:
     def __init__(self, detector: Detector, depth: int = 4, gates: bool = False):
         if not 1 <= depth <= 8:
             raise ValueError("depth must be in 1..8")
+        _one_view(detector.reduction, detector.rectification)
         d = detector.dictionary
         self._ctxs = [_lib.Context(detector.config._c(), d.code_list, d.num_bits, d._tau, detector.device) for _ in range(depth)]
         self._refinement = detector.refinement   # (the detector's setting when the queue was made; each batch keeps the one in force at its submit)
         self._board, self._charuco_config = detector.board, detector.charuco_config   # (likewise)
         self._rectification = detector.rectification   # (likewise)
         self._recovery = detector.recovery   # (likewise)
+        self._reduction = detector.reduction   # (likewise)
         self._refine_on = [False] * depth
         self._keep = [None] * depth
         self._gates = gates
@@ -481,6 +518,7 @@ class BatchQueue:
         ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
         ctx.set_debug_taps(False)
         _apply_rectification(ctx, self._rectification)   # (this context's last batch has been collected: the queue is not full)
+        _apply_reduction(ctx, self._reduction)
         ctx.set_corner_refinement(self._refinement._c() if self._refinement is not None else None)
         self._refine_on[k] = self._refinement is not None
         if self._submitted < depth and self._board is not None:   # (each context's first batch: the board stays set on it)

@@ -17,6 +17,7 @@
 #include "a3_launch.h"
 #include "a3_readback.h"
 #include "a3_rectify_check.h"
+#include "a3_reduce_check.h"
 #include "a3_solve_check.h"
 
 using namespace a3;
@@ -103,6 +104,13 @@ struct Batch {
     bool rect = false;
     a3_rectify rect_r{};
     const uint8_t* rect_src = nullptr; int rect_fmt = 0; size_t rect_row = 0, rect_frame = 0;
+    // a3_set_reduction in force (reduce_f != 0): the call's frames (full, of full_W x full_H pixels) are the SOURCE of the reduced grey
+    // plane.  pixels, fmt, W, H, row_stride and frame_stride above then describe that plane (A3_FMT_L8, full size / reduce_f), which
+    // k_reduce_frames writes ahead of the threshold kernel: the front half (threshold ... decode, recovery) sees nothing else, and the back
+    // half (refinement, ChArUco, poses) works on `full` from the corners k_scale_markers mapped back up
+    uint32_t reduce_f = 0;
+    PixelSrc full{};
+    uint32_t full_W = 0, full_H = 0;
     bool taps = false;           // debug taps: grey plane, patches, contours and the per-frame candidate counts are kept
     bool sample_frames = false;  // a3_debug_sample_frames: a tapped batch still samples the caller's frames wherever an untapped one would
     int profiling = 0, profile_every = 1;   // a3_set_profiling in force
@@ -263,6 +271,11 @@ struct a3_ctx {
     a3_rectify rect{};
     bool rect_on = false;
     DevBuf rect_plane;
+    // a3_set_reduction: the setting later batches capture (factor 0: off), and the reduced grey plane of the batch in flight (n x w x h
+    // bytes, tightly packed), owned like rect_plane; a3_reduce_frames stages host-side frames and output in rect_in / rect_out (both calls
+    // are synchronous)
+    a3_reduction reduction{};
+    DevBuf reduce_plane;
     uint32_t last_charuco_total = 0;   // sizes the speculative record read-back of the next batch
     void* pinned = nullptr;
     size_t pinned_cap = 0;
@@ -502,9 +515,14 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
                                          .rec_cap = b.recover_cap, .rec_count = recovered, .n_frames = b.n, .out = ctx->markers_ptr, .out_cap = b.marker_cap,
                                          .per_frame = ctx->per_frame, .marker_total = d_marker_total, .err_flags = &ctx->head->err_flags}));
     }
+    // what everything behind the marker list samples and measures by: the decode stage's source, or with a reduction the caller's
+    // full-size frames, on which the list's corners lie once k_scale_markers has mapped them up
+    const PixelSrc back_src = b.reduce_f ? b.full : b.src;
+    const uint32_t back_W = b.reduce_f ? b.full_W : b.W, back_H = b.reduce_f ? b.full_H : b.H;
+    if (b.reduce_f) A3_HIP(launch_scale_markers(st, {.markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap, .factor = b.reduce_f}));
     float* const refined = b.refined ? ctx->refined_buf.as<float>() : nullptr;
     if (b.refined)   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
-        A3_HIP(launch_refine_corners(st, {.src = b.src, .W = b.W, .H = b.H, .markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap,
+        A3_HIP(launch_refine_corners(st, {.src = back_src, .W = back_W, .H = back_H, .markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap,
                                           .params = refine_params_for(ctx, b.refine), .out = refined}));
     if (b.undist)   // undistorted pixel corners of the same markers (of their refined corners with refinement on)
         A3_HIP(launch_undistort_corners(st, ctx->markers_ptr, refined, d_marker_total, b.marker_cap, b.pose_intr, b.dist, ctx->undist_buf.as<float>(),
@@ -519,14 +537,14 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     if (b.charuco) {   // the chessboard corners of the same markers (their raw refined or integer corners), sampled as the refinement samples
         MarkerSrc raw = m;
         raw.corners = refined;
-        A3_HIP(launch_charuco_corners(st, {.src = b.src, .W = b.W, .H = b.H, .m = raw, .board = board, .min_markers = b.charuco_cfg.min_markers,
+        A3_HIP(launch_charuco_corners(st, {.src = back_src, .W = back_W, .H = back_H, .m = raw, .board = board, .min_markers = b.charuco_cfg.min_markers,
                                            .refine = b.charuco_cfg.refine, .params = charuco_params_for(ctx, b.charuco_cfg), .intr = &b.pose_intr, .dist = &b.dist,
                                            .slots_tmp = ctx->charuco_tmp.as<a3_charuco_corner>(), .counts = const_cast<uint32_t*>(charuco_counts),
                                            .out = ctx->charuco_buf.as<a3_charuco_corner>(), .und = charuco_und}));
     }
     if (b.want_pose) {   // IPPE on the device-resident marker list (src/pose.rs:52-81), no extra round trip
         const a3_intrinsics& in = b.pose_intr;
-        PoseLaunch pose{.n = b.marker_cap, .n_dev = d_marker_total, .marker_size_mm = b.pose_size_mm, .iw = (float)b.W, .ih = (float)b.H, .fx = in.focal_x,
+        PoseLaunch pose{.n = b.marker_cap, .n_dev = d_marker_total, .marker_size_mm = b.pose_size_mm, .iw = (float)back_W, .ih = (float)back_H, .fx = in.focal_x,
                         .fy = in.focal_y, .cx = in.principal_x, .cy = in.principal_y, .out = ctx->pose_buf.as<a3_pose>()};
         if (m.corners) {   // from float corners (k_pose modes 3 / 4)
             pose.corner_stride = 8u; pose.norm_pts = m.corners; pose.mode = b.pose_has_intr ? 4 : 3;
@@ -536,10 +554,10 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
         }
         A3_HIP(launch_pose(st, pose));
         if (b.board)   // one board pose per frame from the same device-resident markers (and refined corners), no extra round trip
-            A3_HIP(launch_board_pose(st, {.m = m, .board = board, .intr = intr, .W = b.W, .H = b.H, .out = ctx->board_buf.as<a3_board_pose>()}));
+            A3_HIP(launch_board_pose(st, {.m = m, .board = board, .intr = intr, .W = back_W, .H = back_H, .out = ctx->board_buf.as<a3_board_pose>()}));
         if (b.charuco)   // one ChArUco pose per frame from the records just written, the starts as the board pose takes them
             A3_HIP(launch_charuco_pose(st, {.m = m, .board = board, .counts = charuco_counts, .recs = ctx->charuco_buf.as<a3_charuco_corner>(), .und = charuco_und,
-                                            .intr = intr, .W = b.W, .H = b.H, .out = ctx->charuco_pose_buf.as<a3_charuco_pose>()}));
+                                            .intr = intr, .W = back_W, .H = back_H, .out = ctx->charuco_pose_buf.as<a3_charuco_pose>()}));
     }
     if (b.prof >= 2) A3_HIP(hipEventRecord(ctx->ev[3], st));
     // ---- results: one copy of [head | `guess` markers], then the poses and (taps) the counts ----
@@ -723,6 +741,10 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     if (b.rect)   // the frames' rectified grey plane, immediately ahead of its reader on the same stream: whatever orders that orders this
         A3_HIP(launch_rectify_grey(st, {.src = b.rect_src, .src_row = b.rect_row, .src_frame = b.rect_frame, .n_frames = n, .fmt = b.rect_fmt, .r = &b.rect_r,
                                         .grey = ctx->rect_plane.as<uint8_t>()}));
+    if (b.reduce_f)   // likewise the frames' reduced grey plane
+        A3_HIP(launch_reduce_frames(st, {.src = b.full.base, .src_row = (size_t)b.full.row_stride, .src_frame = (size_t)b.full.frame_stride, .n_frames = n,
+                                         .fmt = b.full.fmt, .W = b.full_W, .H = b.full_H, .factor = b.reduce_f, .dst = ctx->reduce_plane.as<uint8_t>(),
+                                         .dst_row = W, .dst_frame = npx}));
     if (b.prof) A3_HIP(hipEventRecord(ctx->ev[0], st));
     A3_HIP(launch_grey_threshold(st, {.pixels = b.pixels, .fmt = b.fmt, .row_stride = b.row_stride, .frame_stride = b.frame_stride, .W = (int)W, .H = (int)H,
                                       .n = n, .radius = ctx->cfg.threshold_window, .grey = b.need_grey ? ctx->grey.as<uint8_t>() : nullptr,
@@ -1238,7 +1260,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
                       &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->solve_in,
-                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out, &ctx->rect_plane};
+                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out, &ctx->rect_plane, &ctx->reduce_plane};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1416,6 +1438,8 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
     b = Batch{};
     if (ctx->rect_on && (width != ctx->rect.src.image_width || height != ctx->rect.src.image_height))
         return fail(ctx, A3_ERR_INVALID, "a3_detect_batch: with a rectification set the frames must have the size of its src (a3_set_rectification)");
+    if (ctx->reduction.factor && n_frames != 0 && pixels && width != 0 && height != 0)
+        if (const char* m = check_reduced_size(true, width, height, ctx->reduction.factor)) return fail(ctx, A3_ERR_INVALID, m);
     b.fmt = fmt; b.W = width; b.H = height; b.n = n_frames; b.out_cap = out_cap;
     b.want_pose = want_pose; b.pose_size_mm = size_mm; b.pose_has_intr = intr != nullptr;
     if (intr) b.pose_intr = *intr;
@@ -1453,6 +1477,15 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
         A3_HIP(ctx->rect_plane.ensure(dw * dh * n_frames));
         b.pixels = ctx->rect_plane.as<uint8_t>(); b.fmt = A3_FMT_L8; b.W = (uint32_t)dw; b.H = (uint32_t)dh;
         b.row_stride = dw; b.frame_stride = dw * dh;
+    }
+    if (ctx->reduction.factor) {   // from here on the front half's batch is an A3_FMT_L8 device batch of the reduced size whose frames are the plane
+        const uint32_t f = ctx->reduction.factor;
+        b.reduce_f = f;
+        b.full = PixelSrc{b.pixels, b.row_stride, b.frame_stride, fmt}; b.full_W = width; b.full_H = height;
+        const size_t w = width / f, h = height / f;
+        A3_HIP(ctx->reduce_plane.ensure(w * h * n_frames));
+        b.pixels = ctx->reduce_plane.as<uint8_t>(); b.fmt = A3_FMT_L8; b.W = (uint32_t)w; b.H = (uint32_t)h;
+        b.row_stride = w; b.frame_stride = w * h;
     }
     if (b.board || b.charuco || b.recover) { if (int urc = upload_board(ctx)) return urc; }
     if (b.recover) { if (int urc = upload_recover_ids(ctx)) return urc; }
@@ -2787,6 +2820,7 @@ int a3_set_rectification(a3_ctx* ctx, const a3_rectify* r) {
     if (!ctx) return A3_ERR_INVALID;
     if (ctx->busy()) return fail(ctx, A3_ERR_INVALID, "a3_set_rectification: a submitted batch has not been collected");
     if (!r) { ctx->rect_on = false; ctx->rect = a3_rectify{}; return A3_OK; }   // NULL: off
+    if (ctx->reduction.factor) return fail(ctx, A3_ERR_INVALID, "a3_set_rectification: a reduction is set (a3_set_reduction): set one or the other");
     const size_t sw = r->src.image_width, sh = r->src.image_height, dw = r->dst.image_width, dh = r->dst.image_height;
     if (const char* m = check_rectify(true, *r, 1, sw, sw * sh, dw, dw * dh)) return fail(ctx, A3_ERR_INVALID, m);
     ctx->rect = *r;
@@ -2798,6 +2832,66 @@ int a3_get_rectification(const a3_ctx* ctx, a3_rectify* r, int* enabled) {
     if (!ctx || !r || !enabled) return A3_ERR_INVALID;
     *r = ctx->rect;
     *enabled = ctx->rect_on ? 1 : 0;
+    return A3_OK;
+}
+
+// ---- detection on reduced frames (an extension beyond the reference; contract in include/aruco3_hip.h) ----
+int a3_reduce_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, uint32_t width, uint32_t height, size_t src_row_stride,
+                     size_t src_frame_stride, uint32_t n_frames, uint32_t factor, void* dst, int dst_memory, size_t dst_row_stride,
+                     size_t dst_frame_stride) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (!src || !dst) return fail(ctx, A3_ERR_INVALID, "a3_reduce_frames: null argument");
+    if (ctx->busy()) return fail(ctx, A3_ERR_INVALID, "a3_reduce_frames: a submitted batch has not been collected");
+    if (const char* m = check_reduce_frames(src, src_memory, fmt, width, height, src_row_stride, src_frame_stride, n_frames, factor, dst, dst_memory,
+                                            dst_row_stride, dst_frame_stride))
+        return fail(ctx, A3_ERR_INVALID, m);
+    const size_t bpp = reduce_bpp(fmt), w = width / factor, h = height / factor;
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    const uint8_t* d_src = reinterpret_cast<const uint8_t*>(src);
+    if (src_memory == A3_MEM_HOST) {   // the caller's span, padding included, in one copy
+        const size_t bytes = src_frame_stride * (n_frames - 1) + src_row_stride * (height - 1) + (size_t)width * bpp;
+        A3_HIP(ctx->rect_in.ensure(bytes));
+        A3_HIP(hipMemcpyAsync(ctx->rect_in.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        d_src = ctx->rect_in.as<uint8_t>();
+    }
+    uint8_t* d_dst = reinterpret_cast<uint8_t*>(dst);
+    size_t d_row = dst_row_stride, d_frame = dst_frame_stride;
+    if (dst_memory == A3_MEM_HOST) {   // packed rows on the device; the copy back writes the rows' pixels only
+        d_row = w;
+        d_frame = w * h;
+        A3_HIP(ctx->rect_out.ensure(d_frame * n_frames));
+        d_dst = ctx->rect_out.as<uint8_t>();
+    }
+    A3_HIP(launch_reduce_frames(ctx->stream, {.src = d_src, .src_row = src_row_stride, .src_frame = src_frame_stride, .n_frames = n_frames, .fmt = fmt,
+                                              .W = width, .H = height, .factor = factor, .dst = d_dst, .dst_row = d_row, .dst_frame = d_frame}));
+    if (dst_memory == A3_MEM_HOST) {
+        if (dst_frame_stride == dst_row_stride * h) {
+            A3_HIP(hipMemcpy2DAsync(dst, dst_row_stride, d_dst, d_row, d_row, h * n_frames, hipMemcpyDeviceToHost, ctx->stream));
+        } else {
+            for (uint32_t f = 0; f < n_frames; f++)
+                A3_HIP(hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(dst) + f * dst_frame_stride, dst_row_stride, d_dst + f * d_frame, d_row, d_row, h,
+                                        hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+int a3_set_reduction(a3_ctx* ctx, const a3_reduction* r) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (ctx->busy()) return fail(ctx, A3_ERR_INVALID, "a3_set_reduction: a submitted batch has not been collected");
+    if (!r) { ctx->reduction = a3_reduction{}; return A3_OK; }   // NULL: off
+    if (const char* m = check_reduction(*r)) return fail(ctx, A3_ERR_INVALID, m);
+    if (ctx->rect_on) return fail(ctx, A3_ERR_INVALID, "a3_set_reduction: a rectification is set (a3_set_rectification): set one or the other");
+    ctx->reduction = *r;
+    return A3_OK;
+}
+
+int a3_get_reduction(const a3_ctx* ctx, a3_reduction* r, int* enabled) {
+    if (!ctx || !r || !enabled) return A3_ERR_INVALID;
+    *r = ctx->reduction;
+    *enabled = ctx->reduction.factor ? 1 : 0;
     return A3_OK;
 }
 

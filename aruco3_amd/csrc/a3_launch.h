@@ -275,6 +275,21 @@ struct RectifyGreyLaunch {
     uint8_t* grey = nullptr;
 };
 hipError_t launch_rectify_grey(hipStream_t st, const RectifyGreyLaunch& r);
+// ---- k_reduce.hip ---------------------------------------------------------------------------------------------------------------------
+// The reduced grey plane (a3_reduce_frames, a3_set_reduction): n_frames frames of W x H pixels in format fmt (an A3_FMT_*) -> planes of
+// (W / factor) x (H / factor) bytes, byte (j, i) = (sum of luma_of over the factor x factor block at (factor j, factor i) + factor^2 / 2)
+// / factor^2.  src, dst: device memory; factor 2, 3 or 4.  Nothing past a row's W / factor bytes is written.  The caller has checked
+// every size and stride (a3_reduce_check.h).
+struct ReduceLaunch {
+    const uint8_t* src = nullptr; size_t src_row = 0, src_frame = 0; uint32_t n_frames = 0; int fmt = 0; uint32_t W = 0, H = 0, factor = 0;
+    uint8_t* dst = nullptr; size_t dst_row = 0, dst_frame = 0;
+};
+hipError_t launch_reduce_frames(hipStream_t st, const ReduceLaunch& r);
+// corners[8] of every marker of a device-resident list (capacity n, count n_dev) -> factor * c + factor / 2, in place
+struct ScaleMarkersLaunch {
+    a3_marker* markers = nullptr; const unsigned int* n_dev = nullptr; uint32_t n = 0, factor = 0;
+};
+hipError_t launch_scale_markers(hipStream_t st, const ScaleMarkersLaunch& s);
 struct SynthLaunch {
     const a3_synth_frame* frames = nullptr; uint32_t n_frames = 0; const a3_synth_marker* markers = nullptr; uint32_t W = 0, H = 0; int paper = 0;
     float black = 0.0f, white = 0.0f; int supersample = 0; uint8_t* out = nullptr; size_t row_stride = 0, frame_stride = 0;

@@ -1143,6 +1143,67 @@ int  a3_rectify_frames(a3_ctx *ctx, const void *src, int src_memory, int fmt, si
 int  a3_set_rectification(a3_ctx *ctx, const a3_rectify *r);
 int  a3_get_rectification(const a3_ctx *ctx, a3_rectify *r, int *enabled);
 
+/* Detection on reduced frames.  NOT in the reference: an opt-in extension (the ArUco 3 paper's image reduction, OpenCV's
+ * useAruco3Detection): when the markers are large, the front half of the detector -- threshold, contours, decode, recovery -- runs on a
+ * box-filtered grey plane 1/factor the size, and the back half -- refinement, ChArUco, undistortion, poses -- on the caller's full-size
+ * frames, from corners mapped back up.
+ *
+ * a3_reduce_frames: the reduced plane, fixed to the bit as follows -- tests/reduced_cases.py reduce restates it.  With f = factor
+ * (2, 3 or 4) and W x H = width x height of the source frames the reduced size is w = W / f, h = H / f in integer division; the
+ * trailing W mod f columns and H mod f rows are not read.  Output byte (j, i), column j of row i, is
+ *     (S + f*f/2) / (f*f)                               in integer division (f*f/2 = 2, 4, 8: the mean, rounded half up)
+ *     S = the sum over the f x f block of source pixels (f*j + a, f*i + b), 0 <= a, b < f, of luma_of of the pixel
+ * where luma_of gives into_luma8's integers, (2126 R + 7152 G + 722 B) / 10000 truncated, in the format's channel order; for
+ * A3_FMT_L8 it is the byte itself, and alpha is ignored.  The output is always ONE byte per pixel, whatever the input format, the same
+ * arithmetic for every frame of the call.  Bytes of dst between the end of a row's w bytes and the next row are not written.  src and
+ * dst must not overlap.  Synchronous; not while a submitted batch is in flight.  Host-side src or dst is staged through device buffers
+ * with plain copies.  The strides are in bytes and are taken as given (0 is no default here).
+ * Input errors (A3_ERR_INVALID, decided on the host before anything is enqueued): null pointers, n_frames 0 or above 65535, an unknown
+ * format or memory kind, a factor outside 2..4, a reduced width or height of 0 or one a3_detect_batch would refuse as a frame size
+ * (above 65535, or w x h >= 2^30), a row stride below a row or a frame stride below height x row stride on either side, overlapping
+ * src and dst.
+ *
+ * a3_set_reduction: a context setting, off by default; a context that never sets it launches exactly what it launched before.
+ * r != NULL: every later a3_detect_batch* / *_submit of this context detects on the reduced plane; NULL: off.  With it set, a detect
+ * call returns, to the bit, the result of these four steps:
+ *   1. a3_reduce_frames of the call's frames, with r->factor, to a tightly packed plane P.
+ *   2. the same detector, without the setting and with every extension off, run on P as A3_FMT_L8.  This fixes every marker's id, code,
+ *      rotation, hamming distance and candidate_index, the order of the markers and the per-frame counts -- and, where
+ *      a3_set_board_recovery is in force, a recovered marker's flag: recovery runs on the reduced list, and its max_distance_px counts
+ *      reduced pixels.
+ *   3. every integer corner (x, y) of every marker mapped to X = f*x + f/2, Y = f*y + f/2 (integer division: the block's centre,
+ *      rounded up).
+ *   4. everything behind the marker list computed exactly as a batch without the setting computes it from a marker list with those
+ *      integer corners on the caller's own full-size frames: the refined corners (the start q0 at the mapped corner, cell_px taken from
+ *      the mapped quad), the ChArUco corners, the undistorted corners, and the marker, board and ChArUco poses.  A pose call without
+ *      intrinsics normalises by the full W x H; intrinsics and lens coefficients are the full-size camera's.
+ * Consequences:
+ *   - the minimum edge length, the minimum corner separation and the corner range derive from the reduced size w x h.
+ *   - the debug taps (a3_download_grey, candidates, homographies, patches, contours) report the reduced view; a3_download_grey is P.
+ *   - a3_pack_detections carries the mapped corners.
+ *   - host-resident frames cross the link at full size, once; the reduced plane is written on the device into a buffer the context owns,
+ *     immediately ahead of the threshold kernel.  With a threshold window above 15 the decode stage samples the reduced grey plane,
+ *     while the refinement still samples the caller's frames.
+ *   - the setter is refused (A3_ERR_INVALID) while a submitted batch of the context is in flight; a batch keeps the setting it was
+ *     submitted with, so contexts in rotation (submit / collect) each carry their own.
+ *   - a reduction on a context that has a rectification set, or a rectification on one that has a reduction, is A3_ERR_INVALID: set
+ *     one or the other.  Frames smaller than one block (w or h = 0) are A3_ERR_INVALID at the detect call.
+ *   - the refinement's rule "a corner that moves farther than the window from q0 is q0" now applies to a start that is up to about
+ *     f + 1 px off the true corner where the reduced quad is good to a pixel (f times whatever the reduced detector's own corner error
+ *     is, where it is not): the refinement window (win_half, and what relative_win makes of it) has to cover that, or the refined
+ *     corner falls back to the mapped integer corner.
+ * Errors of the setter (A3_ERR_INVALID): a factor outside 2..4, non-zero reserved, a rectification set, a batch in flight.
+ * a3_get_reduction: the setting in force (*enabled 0: none, *r zeroed).  a3_reduce_frames, a3_rectify_frames, a3_refine_corners,
+ * a3_interpolate_charuco and the solvers never look at the setting.
+ * Out of scope: non-integer factors, a pyramid of more than one level, decoding or recovery at full resolution, choosing the factor
+ * from a minimum marker size, combining with rectification. */
+typedef struct a3_reduction { uint32_t factor; uint32_t reserved[3]; } a3_reduction;   /* factor 2, 3 or 4; reserved 0 */
+int  a3_reduce_frames(a3_ctx *ctx, const void *src, int src_memory, int fmt, uint32_t width, uint32_t height,
+                      size_t src_row_stride, size_t src_frame_stride, uint32_t n_frames, uint32_t factor,
+                      void *dst, int dst_memory, size_t dst_row_stride, size_t dst_frame_stride);
+int  a3_set_reduction(a3_ctx *ctx, const a3_reduction *r);          /* NULL: off */
+int  a3_get_reduction(const a3_ctx *ctx, a3_reduction *r, int *enabled);
+
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);
 int  a3_calculate_tau(int device, const uint64_t *codes, size_t n_codes, uint8_t *tau);

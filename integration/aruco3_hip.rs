@@ -543,6 +543,14 @@ pub struct A3RectifyInfo {
     pub reserved: [u32; 3],
 }
 
+/// a3_reduction: detection on frames reduced by `factor` (2, 3 or 4); reserved 0
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct A3Reduction {
+    pub factor: u32,
+    pub reserved: [u32; 3],
+}
+
 /// a3_stats: per-batch stage counters (the reference prints its rejects in debug builds, src/aruco.rs:163-164)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -693,6 +701,11 @@ extern "C" {
                              dst_frame_stride: usize, info: *mut A3RectifyInfo) -> c_int;
     pub fn a3_set_rectification(ctx: *mut A3Ctx, r: *const A3Rectify) -> c_int;
     pub fn a3_get_rectification(ctx: *const A3Ctx, r: *mut A3Rectify, enabled: *mut c_int) -> c_int;
+    pub fn a3_reduce_frames(ctx: *mut A3Ctx, src: *const c_void, src_memory: c_int, fmt: c_int, width: u32, height: u32,
+                            src_row_stride: usize, src_frame_stride: usize, n_frames: u32, factor: u32, dst: *mut c_void,
+                            dst_memory: c_int, dst_row_stride: usize, dst_frame_stride: usize) -> c_int;
+    pub fn a3_set_reduction(ctx: *mut A3Ctx, r: *const A3Reduction) -> c_int;
+    pub fn a3_get_reduction(ctx: *const A3Ctx, r: *mut A3Reduction, enabled: *mut c_int) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
@@ -1188,6 +1201,43 @@ impl Detector {
         let mut det = Detection { grey: None, candidates: vec![], homographies: vec![], markers: markers[..found].iter().map(marker_of).collect() };
         if populate {   // (the taps report the rectified view)
             fill_debug_outputs(&ctx, 0, rect.dst.image_width, rect.dst.image_height, self.config.homography_sample_size as u32, &mut det);
+        }
+        det
+    }
+
+    /// New (additive): `detect` on the image reduced by `factor` (2, 3 or 4; a3_set_reduction): threshold, contours and decode run on
+    /// the box-filtered grey plane a3_reduce_frames makes of it, and `Marker.corners` are full-size pixels (f x + f / 2).  For markers
+    /// that are large in the image.  The Python twin is `Detector(reduction=Reduction(factor))`; here `Detector` itself gains no field
+    /// (the setting is handed to the shared context for this call only, under its lock, as `detect_rectified` hands over its own).
+    pub fn detect_reduced(&self, image: DynamicImage, factor: u32) -> Detection {
+        let populate = POPULATE.load(Ordering::Relaxed);
+        let slot = slot_for(self);
+        let mut ctx = slot.lock().unwrap();
+        let images = std::slice::from_ref(&image);
+        let p = pack(images, &mut ctx.staging);
+        ctx.check(unsafe { a3_set_debug_taps(ctx.raw, populate as c_int) }, "a3_set_debug_taps");
+        let red = A3Reduction { factor, reserved: [0; 3] };
+        ctx.check(unsafe { a3_set_reduction(ctx.raw, &red) }, "a3_set_reduction");
+        let mut markers = vec![A3Marker::default(); 64];
+        let mut per = vec![0u32; 1];
+        let mut found = 0usize;
+        let rc = loop {
+            let rc = unsafe {
+                a3_detect_batch(ctx.raw, p.bytes as *const c_void, A3_MEM_HOST, p.fmt, p.width, p.height, p.width as usize * p.bpp,
+                                p.width as usize * p.height as usize * p.bpp, 1, markers.as_mut_ptr(), markers.len(), per.as_mut_ptr(),
+                                &mut found)
+            };
+            if rc == A3_ERR_CAPACITY && markers.len() < MAX_MARKERS_PER_FRAME {
+                markers.resize(markers.len() * 4, A3Marker::default());
+                continue;
+            }
+            break rc;
+        };
+        unsafe { a3_set_reduction(ctx.raw, std::ptr::null()) }; // the shared context goes back to the plain detect
+        ctx.check(rc, "a3_detect_batch");
+        let mut det = Detection { grey: None, candidates: vec![], homographies: vec![], markers: markers[..found].iter().map(marker_of).collect() };
+        if populate {   // (the taps report the reduced view)
+            fill_debug_outputs(&ctx, 0, p.width / factor, p.height / factor, self.config.homography_sample_size as u32, &mut det);
         }
         det
     }
