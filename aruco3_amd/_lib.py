@@ -18,6 +18,7 @@ LIB_PATH = Path(os.environ["A3_HIP_LIB"]).resolve() if os.environ.get("A3_HIP_LI
 
 OK, ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_INTERNAL, ERR_NO_DEVICE, ERR_LIMIT = 0, -1, -2, -3, -4, -5, -6
 FMT_RGB8, FMT_RGBA8, FMT_L8, FMT_BGRA8 = 0, 1, 2, 3
+FMT_YUYV8, FMT_UYVY8 = 5, 6   # packed 4:2:2, 2 bytes per pixel, the luma byte is the grey level (4 is unassigned and refused)
 MEM_HOST, MEM_DEVICE = 0, 1
 PROFILE_OFF, PROFILE_STAGES, PROFILE_THRESHOLD_ONLY, PROFILE_THRESHOLD_SAMPLED = 0, 1, 2, 3
 STAGE_THRESHOLD, STAGE_CONTOUR, STAGE_DECODE = 0, 1, 2
@@ -962,8 +963,8 @@ class Context:
 
     def rectify_frames(self, src_ptr: int, src_memory: int, fmt: int, src_row_stride: int, src_frame_stride: int, n_frames: int,
                        r: "RectifyRec", dst_ptr: int, dst_memory: int, dst_row_stride: int, dst_frame_stride: int) -> "RectifyInfo":
-        """a3_rectify_frames: n_frames frames at src_ptr (r.src's size) -> rectified frames at dst_ptr (r.dst's size, same format);
-        synchronous -> the launch's a3_rectify_info"""
+        """a3_rectify_frames: n_frames frames at src_ptr (r.src's size) -> rectified frames at dst_ptr (r.dst's size, same format; for
+        FMT_YUYV8 / FMT_UYVY8 the rectified luma view, one byte per pixel); synchronous -> the launch's a3_rectify_info"""
         info = RectifyInfo()
         check(load().a3_rectify_frames(self.handle, C.c_void_p(src_ptr), src_memory, fmt, src_row_stride, src_frame_stride, n_frames,
                                        C.byref(r), C.c_void_p(dst_ptr), dst_memory, dst_row_stride, dst_frame_stride, C.byref(info)),

@@ -133,38 +133,75 @@ class Detection:
     charuco_corners: Optional[np.ndarray] = None
 
 
-def _as_frames(image):
-    """-> (pointer, memory kind, fmt, w, h, row_stride, frame_stride, n, keepalive)"""
+PACKED_422 = {"yuyv": _lib.FMT_YUYV8, "uyvy": _lib.FMT_UYVY8}   # 2 bytes per pixel; the luma byte is the grey level as it stands
+PLANAR_LUMA_FIRST = ("nv12", "nv21", "i420", "yv12")               # H rows of luma, then H / 2 rows of chroma in some order
+
+
+def _as_frames(image, pixel_format: Optional[str] = None):
+    """The one place that understands frame layouts.  -> (pointer, memory kind, fmt, w, h, row_stride, frame_stride, n, keepalive)
+
+    pixel_format None: the format follows from the channel count -- (N,H,W,C), (H,W,C) or (H,W) uint8 with C 1 (L8), 3 (RGB8) or 4
+    (RGBA8); two channels are refused (YUYV or UYVY: the byte order is the caller's to say).
+    "bgra": 4 channels in webcam byte order B,G,R,A.
+    "yuyv" / "uyvy": packed 4:2:2, (N,H,W,2) or (H,W,2), W even; the luma byte of every pixel is its grey level, chroma is never read
+    into a result.
+    "nv12", "nv21", "i420", "yv12": the luma-first planar layouts, (N,3H/2,W) or (3H/2,W) -- the buffer as the decoder wrote it.  The
+    luma plane is read in place (FMT_L8, height H, row stride W, frame stride 3H/2 * W); the chroma rows are skipped by the strides.
+    numpy arrays and torch tensors, on the host or the device; nothing is copied beyond making the buffer contiguous."""
     try:
         import torch
     except ImportError:  # pragma: no cover
         torch = None
-    if torch is not None and isinstance(image, torch.Tensor):
-        t = image
-        if t.dtype != torch.uint8:
-            raise TypeError("frames must be uint8")
-        if t.dim() == 2:
-            t = t[None, :, :, None]
-        elif t.dim() == 3:
-            t = t[None] if t.shape[-1] in (1, 3, 4) else t[..., None]
-        if t.dim() != 4 or t.shape[-1] not in (1, 3, 4):
-            raise ValueError("expected (N,H,W,C) with C in 1,3,4")
-        t = t.contiguous()
-        n, h, w, c = t.shape
-        mem = _lib.MEM_DEVICE if t.is_cuda else _lib.MEM_HOST
-        return t.data_ptr(), mem, {1: _lib.FMT_L8, 3: _lib.FMT_RGB8, 4: _lib.FMT_RGBA8}[c], w, h, w * c, h * w * c, n, t
-    a = np.asarray(image)
-    if a.dtype != np.uint8:
+    fmt_name = None if pixel_format is None else str(pixel_format).lower()
+    if fmt_name is not None and fmt_name != "bgra" and fmt_name not in PACKED_422 and fmt_name not in PLANAR_LUMA_FIRST:
+        raise ValueError(f"unknown pixel_format {pixel_format!r}: None, 'bgra', 'yuyv', 'uyvy', 'nv12', 'nv21', 'i420' or 'yv12'")
+    is_tensor = torch is not None and isinstance(image, torch.Tensor)
+    a = image if is_tensor else np.asarray(image)
+    if a.dtype != (torch.uint8 if is_tensor else np.uint8):
         raise TypeError("frames must be uint8")
-    if a.ndim == 2:
-        a = a[None, :, :, None]
-    elif a.ndim == 3:
-        a = a[None] if a.shape[-1] in (1, 3, 4) else a[..., None]
-    if a.ndim != 4 or a.shape[-1] not in (1, 3, 4):
-        raise ValueError("expected (N,H,W,C) with C in 1,3,4")
+    nd = a.dim() if is_tensor else a.ndim
+    if fmt_name in PLANAR_LUMA_FIRST:
+        if nd == 2:
+            a = a[None]
+        if (a.dim() if is_tensor else a.ndim) != 3:
+            raise ValueError(f"pixel_format={fmt_name!r} expects (N,3H/2,W) or (3H/2,W)")
+        n, rows, w = (int(v) for v in a.shape)
+        if rows % 3 or (rows * 2 // 3) % 2:
+            raise ValueError(f"pixel_format={fmt_name!r}: {rows} rows are not 3H/2 for an even H")
+        if w % 2:
+            raise ValueError(f"pixel_format={fmt_name!r}: 4:2:0 frames have an even width")
+        c, h, fmt, row, frame = 1, rows * 2 // 3, _lib.FMT_L8, w, rows * w
+    else:
+        chans = (2,) if fmt_name in PACKED_422 else (4,) if fmt_name == "bgra" else (1, 3, 4)
+        if nd == 2 and 1 in chans:
+            a = a[None, :, :, None]
+        elif nd == 3:
+            a = a[None] if a.shape[-1] in chans else a[..., None]
+        if (a.dim() if is_tensor else a.ndim) != 4 or a.shape[-1] not in chans:
+            if fmt_name in PACKED_422:
+                raise ValueError(f"pixel_format={fmt_name!r} expects (N,H,W,2) or (H,W,2)")
+            if fmt_name == "bgra":
+                raise ValueError("bgra=True needs 4-channel frames")
+            if nd in (3, 4) and a.shape[-1] == 2:
+                raise ValueError("expected (N,H,W,C) with C in 1,3,4; 2-channel frames need pixel_format='yuyv' or 'uyvy'")
+            raise ValueError("expected (N,H,W,C) with C in 1,3,4")
+        n, h, w, c = (int(v) for v in a.shape)
+        if c == 2 and w % 2:
+            raise ValueError("4:2:2 frames have an even width")
+        fmt = PACKED_422[fmt_name] if c == 2 else _lib.FMT_BGRA8 if fmt_name == "bgra" else {1: _lib.FMT_L8, 3: _lib.FMT_RGB8, 4: _lib.FMT_RGBA8}[c]
+        row, frame = w * c, h * w * c
+    if is_tensor:
+        a = a.contiguous()
+        return a.data_ptr(), _lib.MEM_DEVICE if a.is_cuda else _lib.MEM_HOST, fmt, w, h, row, frame, n, a
     a = np.ascontiguousarray(a)
-    n, h, w, c = a.shape
-    return a.ctypes.data, _lib.MEM_HOST, {1: _lib.FMT_L8, 3: _lib.FMT_RGB8, 4: _lib.FMT_RGBA8}[c], w, h, w * c, h * w * c, n, a
+    return a.ctypes.data, _lib.MEM_HOST, fmt, w, h, row, frame, n, a
+
+
+def _pixel_format(pixel_format: Optional[str], bgra: bool) -> Optional[str]:
+    """the pixel_format of a call that also has the older `bgra` flag"""
+    if bgra and pixel_format not in (None, "bgra"):
+        raise ValueError("bgra=True and pixel_format disagree")
+    return "bgra" if bgra else pixel_format
 
 
 class Detector:
@@ -244,18 +281,18 @@ class Detector:
         return self._ctx
 
     # src/aruco.rs:52-121
-    def detect(self, image, populate: bool = False) -> Detection:
-        return self.detect_batch(image, populate=populate)[0]
+    def detect(self, image, populate: bool = False, pixel_format: Optional[str] = None) -> Detection:
+        return self.detect_batch(image, populate=populate, pixel_format=pixel_format)[0]
 
-    def detect_batch(self, images, populate: bool = False, stream: int = None, out_cap: int = 0, bgra: bool = False) -> List[Detection]:
-        """`bgra=True`: 4-channel frames are in webcam byte order B,G,R,A (examples/webcam_kamera.rs:38-52 re-orders them on
-        the CPU before `detect`; here the kernel reads them as they are)."""
+    def detect_batch(self, images, populate: bool = False, stream: int = None, out_cap: int = 0, bgra: bool = False,
+                     pixel_format: Optional[str] = None) -> List[Detection]:
+        """`bgra=True` (or pixel_format="bgra"): 4-channel frames are in webcam byte order B,G,R,A (examples/webcam_kamera.rs:38-52
+        re-orders them on the CPU before `detect`; here the kernel reads them as they are).
+        pixel_format (here and in every call that takes frames): "yuyv" / "uyvy" for packed 4:2:2 frames (N,H,W,2), "nv12" / "nv21" /
+        "i420" / "yv12" for planar buffers (N,3H/2,W) -- read in place, the luma byte is the grey level (`_as_frames` states the
+        layouts); the result is, to the bit, that of the luma plane as an L8 frame, and `populate=True` returns that plane as `grey`."""
         ctx = self._context()
-        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
-        if bgra:
-            if fmt != _lib.FMT_RGBA8:
-                raise ValueError("bgra=True needs 4-channel frames")
-            fmt = _lib.FMT_BGRA8
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images, _pixel_format(pixel_format, bgra))
         if stream is not None:
             ctx.set_stream(stream)
         ctx.set_debug_taps(populate)
@@ -283,14 +320,15 @@ class Detector:
             _fill_charuco(out, ctx.charuco_corners())
         return out
 
-    def detect_batch_with_pose(self, images, marker_size_mm: float, intrinsics=None, stream: int = None, out_cap: int = 0):
+    def detect_batch_with_pose(self, images, marker_size_mm: float, intrinsics=None, stream: int = None, out_cap: int = 0,
+                               pixel_format: Optional[str] = None):
         """detect + `pose::solve_with_undistorted_points` / `solve_with_intrinsics` of every marker (src/pose.rs:52-81) in one
         device pass, the way examples/webcam_kamera.rs:56-71 chains them.  -> [(Detection, [(MarkerPose, MarkerPose), ...])]"""
         from .pose import MarkerPose
 
         self._check_pose_intrinsics(intrinsics)
         ctx = self._context()
-        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images, pixel_format)
         if stream is not None:
             ctx.set_stream(stream)
         ctx.set_debug_taps(False)
@@ -320,7 +358,8 @@ class Detector:
             _fill_charuco([d for d, _ in out], ctx.charuco_corners())
         return out
 
-    def detect_batch_with_board_pose(self, images, intrinsics=None, marker_size_mm: float = 1.0, stream: int = None, out_cap: int = 0):
+    def detect_batch_with_board_pose(self, images, intrinsics=None, marker_size_mm: float = 1.0, stream: int = None, out_cap: int = 0,
+                                     pixel_format: Optional[str] = None):
         """detect + one board pose per frame (the detector's `board`), solved on the device from every board marker of the frame
         (include/aruco3_hip.h states the solve).  -> [(Detection, BoardPose)]; the per-marker poses of the same call are solved too
         (with `marker_size_mm`) and left out here -- detect_batch_with_pose returns them."""
@@ -330,7 +369,7 @@ class Detector:
             raise ValueError("detect_batch_with_board_pose needs Detector(board=...)")
         self._check_pose_intrinsics(intrinsics)
         ctx = self._context()
-        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images, pixel_format)
         if stream is not None:
             ctx.set_stream(stream)
         ctx.set_debug_taps(False)
@@ -351,7 +390,8 @@ class Detector:
             _fill_charuco(dets, ctx.charuco_corners())
         return [(d, BoardPose._from(boards[f])) for f, d in enumerate(dets)]
 
-    def detect_batch_with_charuco_pose(self, images, intrinsics=None, marker_size_mm: float = 1.0, stream: int = None, out_cap: int = 0):
+    def detect_batch_with_charuco_pose(self, images, intrinsics=None, marker_size_mm: float = 1.0, stream: int = None, out_cap: int = 0,
+                                       pixel_format: Optional[str] = None):
         """detect + the ChArUco corners + one ChArUco pose per frame (the detector's `board`, a CharucoBoard), solved on the device from
         the frame's chessboard corners (include/aruco3_hip.h states the solve).  -> [(Detection, CharucoPose)]"""
         from .board import CharucoPose
@@ -360,7 +400,7 @@ class Detector:
             raise ValueError("detect_batch_with_charuco_pose needs Detector(board=CharucoBoard(...))")
         self._check_pose_intrinsics(intrinsics)
         ctx = self._context()
-        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images, pixel_format)
         if stream is not None:
             ctx.set_stream(stream)
         ctx.set_debug_taps(False)
@@ -380,24 +420,34 @@ class Detector:
         poses = ctx.charuco_poses()
         return [(d, CharucoPose._from(poses[f])) for f, d in enumerate(dets)]
 
-    def interpolate_charuco(self, image, ids, corners):
+    def interpolate_charuco(self, image, ids, corners, pixel_format: Optional[str] = None):
         """stand-alone, one frame (a3_interpolate_charuco): the chessboard corners of the detector's CharucoBoard from caller-given
         markers -- ids (n,) and raw pixel corners (n, 4, 2) -- refined on `image` as a batch refines them.  -> (ids (m,) uint32,
         corners (m, 2) float32)"""
         if not _is_charuco(self.board):
             raise ValueError("interpolate_charuco needs Detector(board=CharucoBoard(...))")
         ctx = self._context()
-        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(image)
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(image, pixel_format)
         if n != 1:
             raise ValueError("interpolate_charuco takes one frame")
         self._apply_board(ctx)
         rec = ctx.interpolate_charuco(ptr, mem, fmt, w, h, rs, ids, corners)
         return rec["id"].copy(), np.stack([rec["x"], rec["y"]], axis=1).astype(np.float32)
 
-    def detect_batch_raw(self, images, stream: int = None, out_cap: int = 0):
+    def refine_corners(self, image, corners, cell_px=None, pixel_format: Optional[str] = None) -> np.ndarray:
+        """stand-alone, one frame (a3_refine_corners): corners (..., 2) -> refined float32 (n, 2) with the detector's `refinement` (the
+        library's defaults without one); cell_px: one marker cell size per corner for the relative window, or None"""
+        ctx = self._context()
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(image, pixel_format)
+        if n != 1:
+            raise ValueError("refine_corners takes one frame")
+        self._apply_refinement(ctx)
+        return ctx.refine_corners(ptr, mem, fmt, w, h, rs, corners, cell_px)
+
+    def detect_batch_raw(self, images, stream: int = None, out_cap: int = 0, pixel_format: Optional[str] = None):
         """Batch entry without Python object construction: (structured marker array, per-frame counts)."""
         ctx = self._context()
-        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images, pixel_format)
         if stream is not None:
             ctx.set_stream(stream)
         self._apply_refinement(ctx)   # (the refined corners are not returned here: Context.refined_corners() has them)
@@ -506,7 +556,7 @@ class BatchQueue:
     def full(self) -> bool:
         return self._in_flight == len(self._ctxs)
 
-    def submit(self, images, out_cap: int = 0) -> None:
+    def submit(self, images, out_cap: int = 0, pixel_format: Optional[str] = None) -> None:
         if self.full:
             raise RuntimeError("BatchQueue is full: collect() the oldest batch first")
         depth = len(self._ctxs)
@@ -515,7 +565,7 @@ class BatchQueue:
         if self._gates:
             for m in range(k + 1, depth):
                 ctx.order_after(self._ctxs[m])
-        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images)
+        ptr, mem, fmt, w, h, rs, fs, n, keep = _as_frames(images, pixel_format)
         ctx.set_debug_taps(False)
         _apply_rectification(ctx, self._rectification)   # (this context's last batch has been collected: the queue is not full)
         _apply_reduction(ctx, self._reduction)

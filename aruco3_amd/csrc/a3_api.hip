@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "a3_common.h"
+#include "a3_format.h"
 #include "a3_internal.h"
 #include "a3_launch.h"
 #include "a3_readback.h"
@@ -1365,21 +1366,21 @@ static int stage_input(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
                        size_t* frame_stride, uint32_t n_frames, const uint8_t** d_pixels) {
     if (n_frames == 0) return kNothingToDo;
     if (!pixels) return fail(ctx, A3_ERR_INVALID, "a3_detect_batch: null pixels");
-    if (fmt != A3_FMT_RGB8 && fmt != A3_FMT_RGBA8 && fmt != A3_FMT_L8 && fmt != A3_FMT_BGRA8) return fail(ctx, A3_ERR_INVALID, "unknown pixel format");
+    if (!format_valid(fmt)) return fail(ctx, A3_ERR_INVALID, "unknown pixel format");
     if (width == 0 || height == 0) return kNothingToDo;   // an empty image has no contours
     if (n_frames > 65535) return fail(ctx, A3_ERR_INVALID, "more than 65535 frames in one call (split the batch)");
     if (width > 65535 || height > 65535 || (uint64_t)width * height >= (1ull << 30))
         return fail(ctx, A3_ERR_INVALID, "image dimensions above 65535 (or 2^30 pixels) are not supported");
-    const size_t bpp = fmt == A3_FMT_RGB8 ? 3 : (fmt == A3_FMT_L8 ? 1 : 4);
-    if (*row_stride == 0) *row_stride = (size_t)width * bpp;
-    if (*row_stride < (size_t)width * bpp) return fail(ctx, A3_ERR_INVALID, "row_stride smaller than a row");
+    if (const char* m = format_width_error(fmt, width)) return fail(ctx, A3_ERR_INVALID, m);
+    if (*row_stride == 0) *row_stride = format_min_row_bytes(fmt, width);
+    if (*row_stride < format_min_row_bytes(fmt, width)) return fail(ctx, A3_ERR_INVALID, "row_stride smaller than a row");
     if (*frame_stride == 0) *frame_stride = *row_stride * height;
-    if (*frame_stride < *row_stride * (height - 1) + (size_t)width * bpp) return fail(ctx, A3_ERR_INVALID, "frame_stride smaller than a frame");
+    if (*frame_stride < format_min_frame_bytes(fmt, width, height, *row_stride)) return fail(ctx, A3_ERR_INVALID, "frame_stride smaller than a frame");
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
     *d_pixels = reinterpret_cast<const uint8_t*>(pixels);
     if (memory == A3_MEM_HOST) {
-        const size_t bytes = *frame_stride * (n_frames - 1) + *row_stride * (height - 1) + (size_t)width * bpp;
+        const size_t bytes = *frame_stride * (n_frames - 1) + format_min_frame_bytes(fmt, width, height, *row_stride);
         A3_HIP(ctx->in.ensure(bytes));
         // On the copy stream, not the compute stream: the kernels of another context's batch (submit / collect with two
         // contexts) keep running while these frames cross the link.  Pageable memory is staged by the runtime and the call
@@ -1737,7 +1738,8 @@ int a3_debug_launch_threshold(a3_ctx* ctx, const void* pixels_device, int fmt, u
     if (!ctx || !pixels_device || n_frames == 0) return A3_ERR_INVALID;
     A3_HIP(hipSetDevice(ctx->device));
     if (int rc = need_stream(ctx)) return rc;
-    const size_t bpp = fmt == A3_FMT_RGB8 ? 3 : (fmt == A3_FMT_L8 ? 1 : 4);
+    if (!format_valid(fmt) || format_width_error(fmt, width)) return A3_ERR_INVALID;
+    const size_t bpp = format_bpp(fmt);
     if (threshold_writes_grey_plane(ctx->cfg.threshold_window))
         return fail(ctx, A3_ERR_INVALID, "a3_debug_launch_threshold: this threshold_window / frame layout takes the separable path, which needs a grey plane");
     A3_HIP(ctx->bin.ensure((size_t)words_per_row(width) * 8 * height * n_frames));
@@ -2768,12 +2770,12 @@ int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, siz
     if (!src || !r || !dst) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: null argument");
     if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: a submitted batch has not been collected");
     if (n_frames == 0 || n_frames > 65535) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: n_frames must be in 1..65535");
-    if (fmt != A3_FMT_RGB8 && fmt != A3_FMT_RGBA8 && fmt != A3_FMT_L8 && fmt != A3_FMT_BGRA8)
-        return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: unknown pixel format");
+    if (!format_valid(fmt)) return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: unknown pixel format");
     if ((src_memory != A3_MEM_HOST && src_memory != A3_MEM_DEVICE) || (dst_memory != A3_MEM_HOST && dst_memory != A3_MEM_DEVICE))
         return fail(ctx, A3_ERR_INVALID, "a3_rectify_frames: memory must be A3_MEM_HOST or A3_MEM_DEVICE");
-    const size_t bpp = fmt == A3_FMT_RGB8 ? 3 : (fmt == A3_FMT_L8 ? 1 : 4);
-    if (const char* m = check_rectify(false, *r, bpp, src_row_stride, src_frame_stride, dst_row_stride, dst_frame_stride)) return fail(ctx, A3_ERR_INVALID, m);
+    // bpp: of the source; obpp: of what is written -- the same, but for a packed 4:2:2 source, whose rectified frames are the luma view
+    const size_t bpp = format_bpp(fmt), obpp = format_rectified_bpp(fmt);
+    if (const char* m = check_rectify_frames_fmt(*r, fmt, src_row_stride, src_frame_stride, dst_row_stride, dst_frame_stride)) return fail(ctx, A3_ERR_INVALID, m);
     const a3_distortion& d = r->distortion;
 
     const uint32_t sw = r->src.image_width, sh = r->src.image_height, dw = r->dst.image_width, dh = r->dst.image_height;
@@ -2789,13 +2791,17 @@ int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, siz
     uint8_t* d_dst = reinterpret_cast<uint8_t*>(dst);
     size_t d_row = dst_row_stride, d_frame = dst_frame_stride;
     if (dst_memory == A3_MEM_HOST) {   // packed rows on the device; the copy back writes the rows' pixels only
-        d_row = (size_t)dw * bpp;
+        d_row = (size_t)dw * obpp;
         d_frame = d_row * dh;
         A3_HIP(ctx->rect_out.ensure(d_frame * n_frames));
         d_dst = ctx->rect_out.as<uint8_t>();
     }
-    A3_HIP(launch_rectify(ctx->stream, {.src = d_src, .src_row = src_row_stride, .src_frame = src_frame_stride, .n_frames = n_frames, .bpp = (int)bpp, .r = r,
-                                        .dst = d_dst, .dst_row = d_row, .dst_frame = d_frame}));
+    if (format_is_422(fmt))   // the grey form: the luma byte alone, one byte per pixel out
+        A3_HIP(launch_rectify_grey(ctx->stream, {.src = d_src, .src_row = src_row_stride, .src_frame = src_frame_stride, .n_frames = n_frames, .fmt = fmt,
+                                                 .r = r, .grey = d_dst, .dst_row = d_row, .dst_frame = d_frame}));
+    else
+        A3_HIP(launch_rectify(ctx->stream, {.src = d_src, .src_row = src_row_stride, .src_frame = src_frame_stride, .n_frames = n_frames, .bpp = (int)bpp, .r = r,
+                                            .dst = d_dst, .dst_row = d_row, .dst_frame = d_frame}));
     if (dst_memory == A3_MEM_HOST) {
         if (dst_frame_stride == dst_row_stride * dh) {
             A3_HIP(hipMemcpy2DAsync(dst, dst_row_stride, d_dst, d_row, d_row, (size_t)dh * n_frames, hipMemcpyDeviceToHost, ctx->stream));

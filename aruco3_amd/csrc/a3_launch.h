@@ -13,7 +13,8 @@ namespace a3 {
 
 // ---- k_threshold.hip (+ _r1, _r2, _big): grey + adaptive threshold ----------------------------------------------------------
 // n frames of W x H pixels -> the packed image `bits`.  grey (nullable): the grey plane is written too; the separable path (see
-// threshold_writes_grey_plane) needs it and hsum_tmp (one u16 per pixel), the fused kernels need neither.
+// threshold_writes_grey_plane) needs it and hsum_tmp (one u16 per pixel), the fused kernels need neither.  fmt: any A3_FMT_*; for
+// A3_FMT_YUYV8 / A3_FMT_UYVY8 (2 bytes per pixel, W even) the grey level is the luma byte as it stands (a3_format.h).
 struct ThresholdLaunch {
     const uint8_t* pixels = nullptr; int fmt = 0; size_t row_stride = 0, frame_stride = 0; int W = 0, H = 0; uint32_t n = 0, radius = 0;
     uint8_t* grey = nullptr; uint64_t* bits = nullptr; uint16_t* hsum_tmp = nullptr;
@@ -270,15 +271,18 @@ hipError_t launch_rectify(hipStream_t st, const RectifyLaunch& r);
 // src: device memory, n_frames frames of r->src's size in format fmt (an A3_FMT_*); grey: device memory, n_frames planes of r->dst's
 // size, tightly packed (row stride = r->dst.image_width), every byte of which is written and nothing else.  The caller has checked
 // r (a3_rectify_check.h) and every size and stride.
+// fmt A3_FMT_YUYV8 / A3_FMT_UYVY8 (packed 4:2:2, 2 bytes per pixel in src's strides): the luma byte alone is blended and is the output
+// byte -- what fmt A3_FMT_L8 gives on a plane of those luma bytes.  These two formats have the grey form only, so a3_rectify_frames
+// comes here for them, with its caller's strides in dst_row / dst_frame (bytes; dst_row 0: tightly packed, as above).
 struct RectifyGreyLaunch {
     const uint8_t* src = nullptr; size_t src_row = 0, src_frame = 0; uint32_t n_frames = 0; int fmt = 0; const a3_rectify* r = nullptr;
-    uint8_t* grey = nullptr;
+    uint8_t* grey = nullptr; size_t dst_row = 0, dst_frame = 0;
 };
 hipError_t launch_rectify_grey(hipStream_t st, const RectifyGreyLaunch& r);
 // ---- k_reduce.hip ---------------------------------------------------------------------------------------------------------------------
 // The reduced grey plane (a3_reduce_frames, a3_set_reduction): n_frames frames of W x H pixels in format fmt (an A3_FMT_*) -> planes of
 // (W / factor) x (H / factor) bytes, byte (j, i) = (sum of luma_of over the factor x factor block at (factor j, factor i) + factor^2 / 2)
-// / factor^2.  src, dst: device memory; factor 2, 3 or 4.  Nothing past a row's W / factor bytes is written.  The caller has checked
+// / factor^2 (A3_FMT_YUYV8 / A3_FMT_UYVY8: the luma byte in luma_of's place).  src, dst: device memory; factor 2, 3 or 4.  Nothing past a row's W / factor bytes is written.  The caller has checked
 // every size and stride (a3_reduce_check.h).
 struct ReduceLaunch {
     const uint8_t* src = nullptr; size_t src_row = 0, src_frame = 0; uint32_t n_frames = 0; int fmt = 0; uint32_t W = 0, H = 0, factor = 0;

@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "../../include/aruco3_hip.h"
+#include "a3_format.h"
 
 namespace a3 {
 
@@ -31,10 +32,12 @@ inline const char* check_rectify_image(bool setter, const a3_intrinsics& k, size
 
 // setter: a3_set_rectification, which has no frames yet -- it passes bpp 1 and tightly packed strides, so the stride checks cannot
 // fail there; the detect call checks the strides of its own frames (stage_input)
-inline const char* check_rectify(bool setter, const a3_rectify& r, size_t bpp, size_t src_row_stride, size_t src_frame_stride, size_t dst_row_stride,
-                                 size_t dst_frame_stride) {
-    if (const char* m = check_rectify_image(setter, r.src, bpp, src_row_stride, src_frame_stride)) return m;
-    if (const char* m = check_rectify_image(setter, r.dst, bpp, dst_row_stride, dst_frame_stride)) return m;
+// src_bpp / dst_bpp: bytes per pixel of the source frames and of what the call writes -- the same but for a packed 4:2:2 source, whose
+// rectified frames are the luma view (a3_format.h: format_bpp, format_rectified_bpp)
+inline const char* check_rectify_as(bool setter, const a3_rectify& r, size_t src_bpp, size_t dst_bpp, size_t src_row_stride, size_t src_frame_stride,
+                                    size_t dst_row_stride, size_t dst_frame_stride) {
+    if (const char* m = check_rectify_image(setter, r.src, src_bpp, src_row_stride, src_frame_stride)) return m;
+    if (const char* m = check_rectify_image(setter, r.dst, dst_bpp, dst_row_stride, dst_frame_stride)) return m;
     if (r.reserved[0] || r.reserved[1] || r.reserved[2]) return A3_RECT_REC("a3_rectify.reserved must be 0");
     const a3_distortion& d = r.distortion;
     if (d.model != A3_DIST_NONE && d.model != A3_DIST_RATIONAL && d.model != A3_DIST_FISHEYE) return A3_RECT_REC("a3_rectify.distortion.model: unknown model");
@@ -48,6 +51,16 @@ inline const char* check_rectify(bool setter, const a3_rectify& r, size_t bpp, s
     for (float v : r.rotation)
         if (!std::isfinite(v)) return A3_RECT_REC("a3_rectify.rotation: an entry is not finite");
     return nullptr;
+}
+inline const char* check_rectify(bool setter, const a3_rectify& r, size_t bpp, size_t src_row_stride, size_t src_frame_stride, size_t dst_row_stride,
+                                 size_t dst_frame_stride) {
+    return check_rectify_as(setter, r, bpp, bpp, src_row_stride, src_frame_stride, dst_row_stride, dst_frame_stride);
+}
+// a3_rectify_frames on frames of format fmt (a valid one): the format's own rule first, then the record with the format's pixel sizes
+inline const char* check_rectify_frames_fmt(const a3_rectify& r, int fmt, size_t src_row_stride, size_t src_frame_stride, size_t dst_row_stride,
+                                            size_t dst_frame_stride) {
+    if (format_width_error(fmt, r.src.image_width)) return "a3_rectify_frames: 4:2:2 frames have an even width";
+    return check_rectify_as(false, r, format_bpp(fmt), format_rectified_bpp(fmt), src_row_stride, src_frame_stride, dst_row_stride, dst_frame_stride);
 }
 
 #undef A3_RECT_MSG

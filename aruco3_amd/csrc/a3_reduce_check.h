@@ -7,13 +7,12 @@
 #include <cstdint>
 
 #include "../../include/aruco3_hip.h"
+#include "a3_format.h"
 
 namespace a3 {
 
-// bytes per pixel of an A3_FMT_*, 0 for none
-inline size_t reduce_bpp(int fmt) {
-    return fmt == A3_FMT_RGB8 ? 3 : fmt == A3_FMT_L8 ? 1 : (fmt == A3_FMT_RGBA8 || fmt == A3_FMT_BGRA8) ? 4 : 0;
-}
+// bytes per pixel of an A3_FMT_*, 0 for none (a3_format.h)
+inline size_t reduce_bpp(int fmt) { return format_bpp(fmt); }
 
 // the record of a3_set_reduction
 inline const char* check_reduction(const a3_reduction& r) {
@@ -41,6 +40,7 @@ inline const char* check_reduce_frames(const void* src, int src_memory, int fmt,
     if (n_frames == 0 || n_frames > 65535) return "a3_reduce_frames: n_frames must be in 1..65535";
     const size_t bpp = reduce_bpp(fmt);
     if (bpp == 0) return "a3_reduce_frames: unknown pixel format";
+    if (format_width_error(fmt, width)) return "a3_reduce_frames: 4:2:2 frames have an even width";
     if ((src_memory != A3_MEM_HOST && src_memory != A3_MEM_DEVICE) || (dst_memory != A3_MEM_HOST && dst_memory != A3_MEM_DEVICE))
         return "a3_reduce_frames: memory must be A3_MEM_HOST or A3_MEM_DEVICE";
     if (factor < 2 || factor > 4) return "a3_reduce_frames: factor must be 2, 3 or 4";

@@ -34,6 +34,7 @@ __device__ __forceinline__ int refine_window(const RefineParams& p, float cell_p
 __device__ __forceinline__ uint32_t refine_grey(const uint8_t* __restrict__ frame, unsigned long long row_stride, int fmt, uint32_t x, uint32_t y) {
     const uint8_t* row = frame + (size_t)y * row_stride;
     if (fmt == A3_FMT_L8 || fmt == kFmtGreyPlane) return row[x];
+    if (fmt == A3_FMT_YUYV8 || fmt == A3_FMT_UYVY8) return row[2u * (size_t)x + (fmt == A3_FMT_UYVY8 ? 1u : 0u)];   // packed 4:2:2: the luma byte as it stands
     if (fmt == A3_FMT_RGB8) { const uint8_t* q = row + 3u * (size_t)x; return luma_of(q[0], q[1], q[2]); }
     const uint8_t* q = row + 4u * (size_t)x;
     return fmt == A3_FMT_BGRA8 ? luma_of(q[2], q[1], q[0]) : luma_of(q[0], q[1], q[2]);

@@ -284,8 +284,13 @@ __device__ __forceinline__ uint8_t clamp_u8(float x) {
     return (uint8_t)(x != x ? 255u : r);
 }
 
-// grey level of pixel x in a frame row: the plane K1 wrote, or into_luma8 of the caller's pixel (same integers)
+// grey level of pixel x in a frame row: the plane K1 wrote, or into_luma8 of the caller's pixel (same integers).
+// Y422: the frames are packed 4:2:2 (A3_FMT_YUYV8 / A3_FMT_UYVY8) -- the luma byte as it stands.  A template parameter of the sampler
+// and of k_decode, not one more run-time case: the instantiations for the other formats then compile exactly as they did (one more
+// case in grey_tap alone cost k_decode two spilled VGPRs), and the 4:2:2 ones carry no luma arithmetic at all.
+template <bool Y422 = false>
 __device__ __forceinline__ float grey_tap(const uint8_t* __restrict__ row, uint32_t x, int fmt) {
+    if constexpr (Y422) return (float)row[2u * (size_t)x + (fmt == A3_FMT_UYVY8 ? 1u : 0u)];
     if (fmt == A3_FMT_L8 || fmt == kFmtGreyPlane) return (float)row[x];
     if (fmt == A3_FMT_RGB8) { const uint8_t* p = row + 3u * (size_t)x; return (float)luma_of(p[0], p[1], p[2]); }
     const uint8_t* p = row + 4u * (size_t)x;
@@ -355,8 +360,14 @@ __device__ __forceinline__ void sample_issue(TapLoad& tl, a3_gptr base4, uint32_
     tl.sh = ((uint32_t)(at & 3u) * 8u) | (((uint32_t)(ab & 3u) * 8u) << 8);
 }
 
+template <bool Y422 = false>
 __device__ __forceinline__ void pair_from(const uint32_t d[3], uint32_t sh, int fmt, uint32_t bpp, float* g0, float* g1) {
     const uint32_t w0 = __builtin_amdgcn_alignbit(d[1], d[0], sh), w1 = __builtin_amdgcn_alignbit(d[2], d[1], sh);   // bytes p .. p+7
+    if constexpr (Y422) {   // bpp 2: the two taps of a row are the luma bytes o and o + 2 of the window (o = 1 for UYVY)
+        const uint32_t y = fmt == A3_FMT_UYVY8 ? w0 >> 8 : w0;
+        *g0 = (float)(y & 0xFFu); *g1 = (float)((y >> 16) & 0xFFu);
+        return;
+    }
     if (bpp == 1u) { *g0 = (float)(w0 & 0xFFu); *g1 = (float)((w0 >> 8) & 0xFFu); return; }
     const bool bgr = fmt == A3_FMT_BGRA8;
     const uint32_t px1 = bpp == 3u ? ((w0 >> 24) | (w1 << 8)) : w1;   // the dot products ignore byte 3
@@ -364,14 +375,15 @@ __device__ __forceinline__ void pair_from(const uint32_t d[3], uint32_t sh, int 
     *g1 = (float)luma_px(px1, bgr);
 }
 
+template <bool Y422 = false>
 __device__ __forceinline__ uint8_t sample_finish(const TapLoad& tl, const uint8_t* __restrict__ img, size_t row_stride, int fmt, uint32_t bpp) {
     float a, b, c, d;
-    pair_from(tl.top, tl.sh & 0xFFu, fmt, bpp, &a, &b);
-    pair_from(tl.bot, tl.sh >> 8, fmt, bpp, &c, &d);
+    pair_from<Y422>(tl.top, tl.sh & 0xFFu, fmt, bpp, &a, &b);
+    pair_from<Y422>(tl.bot, tl.sh >> 8, fmt, bpp, &c, &d);
     if (tl.mode == 2) {   // the last few pixels of a frame: byte loads
         const uint8_t* rt = img + (size_t)tl.t * row_stride;
         const uint8_t* rb = rt + row_stride;
-        a = grey_tap(rt, tl.l, fmt); b = grey_tap(rt, tl.l + 1u, fmt); c = grey_tap(rb, tl.l, fmt); d = grey_tap(rb, tl.l + 1u, fmt);
+        a = grey_tap<Y422>(rt, tl.l, fmt); b = grey_tap<Y422>(rt, tl.l + 1u, fmt); c = grey_tap<Y422>(rb, tl.l, fmt); d = grey_tap<Y422>(rb, tl.l + 1u, fmt);
     }
     const uint8_t tv = clamp_u8((1.0f - tl.rw) * a + tl.rw * b);
     const uint8_t bv = clamp_u8((1.0f - tl.rw) * c + tl.rw * d);
@@ -538,7 +550,8 @@ __device__ __forceinline__ void compact_frame_wave(uint32_t f, int lane, const D
 // 2.5 k candidates of BASELINE config 2 (round 2, docs/HISTORY.md): 256 threads throughout, 4 samples "in flight" per lane, row-major
 // sample order (round 1): 116 us; 64 threads, 8 x 8 blocked order: 98 us; 256 threads sampling, the first wave doing the rest:
 // 94 us -- and 7 us less than the 64-thread version inside the pipeline, where the frames are not in any cache.
-template <int NT, int PT>
+// Y422: the frames are packed 4:2:2 (src.fmt A3_FMT_YUYV8 / A3_FMT_UYVY8; see grey_tap)
+template <int NT, int PT, bool Y422 = false>
 __global__ __launch_bounds__(NT, kDecodeWaves) void k_decode(PixelSrc src, int W, int H, uint32_t first_frame,
                                                 const uint16_t* __restrict__ fin_xy, const uint32_t* __restrict__ work,
                                                 const unsigned int* __restrict__ work_count, uint32_t max_cand, uint32_t S, uint32_t n,
@@ -608,7 +621,7 @@ __global__ __launch_bounds__(NT, kDecodeWaves) void k_decode(PixelSrc src, int W
             // of a block lie in a compact patch of the frame whatever the marker's rotation, so the 64 lanes of a load touch
             // a few dozen cache lines; a row-major order puts the 64 samples of an instruction on a slanted line that crosses
             // a new image row -- a new cache line -- at almost every sample of a rotated marker.
-            const uint32_t bpp = (src.fmt == A3_FMT_RGB8) ? 3u : ((src.fmt == A3_FMT_RGBA8 || src.fmt == A3_FMT_BGRA8) ? 4u : 1u);
+            const uint32_t bpp = Y422 ? 2u : ((src.fmt == A3_FMT_RGB8) ? 3u : ((src.fmt == A3_FMT_RGBA8 || src.fmt == A3_FMT_BGRA8) ? 4u : 1u));
             // (a frame smaller than one wide read cannot hold a candidate; the weight table is merely something of 16 KB to read)
             const unsigned long long frame_bytes = (unsigned long long)(H - 1) * src.row_stride + (unsigned long long)W * bpp;
             const bool tiny = frame_bytes < 16ull, off32 = frame_bytes < 0xFFFFFFE0ull && src.row_stride < (1ull << 24);
@@ -641,7 +654,7 @@ __global__ __launch_bounds__(NT, kDecodeWaves) void k_decode(PixelSrc src, int W
                 for (int u = 0; u < kU; u++) {
                     uint32_t x, y;
                     if (slot_xy(i0 + (uint32_t)NT * u, &x, &y)) {
-                        const uint8_t v = sample_finish(tl[u], img, (size_t)src.row_stride, src.fmt, bpp);
+                        const uint8_t v = sample_finish<Y422>(tl[u], img, (size_t)src.row_stride, src.fmt, bpp);
                         s_patch[__umul24(y, S) + x] = v;
                         atomicAdd(&s_hist[v], 1u);
                     }
@@ -1113,6 +1126,17 @@ hipError_t launch_decode(hipStream_t st, const DecodeStage& d) {
     // frames against 39), and on one wave -- no workgroup barriers -- when thousands of candidates are in flight and only the
     // throughput counts (BASELINE config 2: decode stage 0.123 ms against 0.130 with one wave per candidate throughout).
     const size_t lds = decode_lds_bytes(d.S, d.n, d.max_taps);
+    if (d.src.fmt == A3_FMT_YUYV8 || d.src.fmt == A3_FMT_UYVY8) {   // packed 4:2:2: the samplers' instantiation of their own (grey_tap)
+        if (d.few)
+            hipLaunchKernelGGL((k_decode<256, 256, true>), dim3(d.grid_blocks), dim3(256), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy, d.work,
+                               d.work_count, d.max_cand, d.S, d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab,
+                               reinterpret_cast<DecodeOut*>(d.outs), d.patches, d.patch_cap, d.per_frame, d.variant);
+        else
+            hipLaunchKernelGGL((k_decode<kDecodeThreads, 64, true>), dim3(d.grid_blocks), dim3(kDecodeThreads), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy,
+                               d.work, d.work_count, d.max_cand, d.S, d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab,
+                               reinterpret_cast<DecodeOut*>(d.outs), d.patches, d.patch_cap, d.per_frame, d.variant);
+        return hipGetLastError();
+    }
     if (d.few)
         hipLaunchKernelGGL((k_decode<256, 256>), dim3(d.grid_blocks), dim3(256), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy, d.work, d.work_count,
                            d.max_cand, d.S, d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab, reinterpret_cast<DecodeOut*>(d.outs), d.patches,

@@ -18,6 +18,8 @@
 // through luma_of in the source format's channel order and ONE byte is kept, so a lane's kRun pixels are one dword, a wave's row
 // piece 256 contiguous bytes, and the two store rules above hold unchanged.  RGBA8 and BGRA8 are the same work in the pixel form and
 // different work here, so the grey form is instantiated per format; the pixel-form instantiations compile as before.
+// Packed 4:2:2 (A3_FMT_YUYV8, A3_FMT_UYVY8) has the grey form only: the pair load is one dword (Y U Y V or U Y V Y), the luma byte is the
+// only one blended and is the output byte, so the result is the L8 form's on a plane of those luma bytes; a3_rectify_frames uses it too.
 #include <algorithm>
 #include <cstring>
 
@@ -73,6 +75,10 @@ template <int BPP> __device__ inline uint64_t load_pair(const uint8_t* q) {
         uint16_t t;
         memcpy(&t, q, 2);
         return t;
+    } else if constexpr (BPP == 2) {   // (packed 4:2:2: Y U Y V or U Y V Y, the pair's two luma bytes among them)
+        uint32_t t;
+        memcpy(&t, q, 4);
+        return t;
     } else if constexpr (BPP == 3) {
         uint32_t lo;
         uint16_t hi;
@@ -103,7 +109,12 @@ template <int BPP, int MODEL, int GREY = kPixelForm>
 __global__ __launch_bounds__(256) void k_rectify(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const RectifyParams p) {
     constexpr bool grey = GREY != kPixelForm;
     constexpr int OBPP = grey ? 1 : BPP;   // bytes of an output pixel
-    static_assert(!grey || BPP == (GREY == A3_FMT_RGB8 ? 3 : (GREY == A3_FMT_L8 ? 1 : 4)), "the grey form's BPP is its format's");
+    // packed 4:2:2 has the grey form only: of a pixel's two bytes the luma byte (C0) alone is blended, and it is the output byte as it
+    // stands -- what the L8 form makes of a plane of those luma bytes
+    constexpr bool yuv422 = GREY == A3_FMT_YUYV8 || GREY == A3_FMT_UYVY8;
+    static_assert(BPP != 2 || yuv422, "two bytes per pixel: packed 4:2:2, the grey form");
+    static_assert(!grey || BPP == (GREY == A3_FMT_RGB8 ? 3 : (GREY == A3_FMT_L8 ? 1 : (yuv422 ? 2 : 4))), "the grey form's BPP is its format's");
+    constexpr int C0 = GREY == A3_FMT_UYVY8 ? 1 : 0, C1 = yuv422 ? C0 + 1 : (grey && BPP == 4 ? 3 : BPP);   // the bytes of a pixel that are blended
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t i = blockIdx.y * kTileH + wave, j0 = blockIdx.x * kTileW + lane * kRun;
     if (i >= p.dh || j0 >= p.dw) return;
@@ -151,24 +162,24 @@ __global__ __launch_bounds__(256) void k_rectify(const uint8_t* __restrict__ src
                 const float bx = 1.0f - ax[q], by = 1.0f - ay[q];
                 uint32_t ch[3] = {};   // (the grey form: the pixel's colour bytes)
 #pragma unroll
-                for (int c = 0; c < (grey && BPP == 4 ? 3 : BPP); c++) {
+                for (int c = C0; c < C1; c++) {
                     const float i00 = (float)((uint32_t)(top[q] >> (sh0 + 8 * c)) & 0xFFu), i01 = (float)((uint32_t)(top[q] >> (8 * (BPP + c))) & 0xFFu);
                     const float i10 = (float)((uint32_t)(bot[q] >> (sh0 + 8 * c)) & 0xFFu), i11 = (float)((uint32_t)(bot[q] >> (8 * (BPP + c))) & 0xFFu);
                     const float val = by*(bx*i00 + ax[q]*i01) + ay[q]*(bx*i10 + ax[q]*i11);
                     const uint32_t out = (flags[q] & kTapInside) ? (uint32_t)fminf(floorf(val + 0.5f), 255.0f) : p.fill;
                     if constexpr (grey) {
-                        ch[c] = out;
+                        ch[c - C0] = out;
                     } else {
                         const int byte = q * BPP + c;
                         w[byte >> 2] |= out << (8 * (byte & 3));
                     }
                 }
                 if constexpr (grey)
-                    w[0] |= (BPP == 1 ? ch[0] : (GREY == A3_FMT_BGRA8 ? luma_of(ch[2], ch[1], ch[0]) : luma_of(ch[0], ch[1], ch[2]))) << (8 * q);
+                    w[0] |= (BPP == 1 || yuv422 ? ch[0] : (GREY == A3_FMT_BGRA8 ? luma_of(ch[2], ch[1], ch[0]) : luma_of(ch[0], ch[1], ch[2]))) << (8 * q);
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < OBPP; k++) w[k] = (grey && BPP != 1 ? luma_of(p.fill, p.fill, p.fill) : p.fill) * 0x01010101u;
+            for (int k = 0; k < OBPP; k++) w[k] = (grey && BPP != 1 && !yuv422 ? luma_of(p.fill, p.fill, p.fill) : p.fill) * 0x01010101u;
         }
         if (run == (uint32_t)kRun && (reinterpret_cast<uintptr_t>(d) & 3u) == 0) {
             Words<OBPP> o;
@@ -229,13 +240,15 @@ template <int MODEL> static void launch_grey_form(hipStream_t st, dim3 grid, dim
     if (fmt == A3_FMT_L8) hipLaunchKernelGGL((k_rectify<1, MODEL, A3_FMT_L8>), grid, block, 0, st, src, grey, p);
     else if (fmt == A3_FMT_RGB8) hipLaunchKernelGGL((k_rectify<3, MODEL, A3_FMT_RGB8>), grid, block, 0, st, src, grey, p);
     else if (fmt == A3_FMT_RGBA8) hipLaunchKernelGGL((k_rectify<4, MODEL, A3_FMT_RGBA8>), grid, block, 0, st, src, grey, p);
+    else if (fmt == A3_FMT_YUYV8) hipLaunchKernelGGL((k_rectify<2, MODEL, A3_FMT_YUYV8>), grid, block, 0, st, src, grey, p);
+    else if (fmt == A3_FMT_UYVY8) hipLaunchKernelGGL((k_rectify<2, MODEL, A3_FMT_UYVY8>), grid, block, 0, st, src, grey, p);
     else hipLaunchKernelGGL((k_rectify<4, MODEL, A3_FMT_BGRA8>), grid, block, 0, st, src, grey, p);
 }
 
 hipError_t launch_rectify_grey(hipStream_t st, const RectifyGreyLaunch& l) {
     const a3_rectify& r = *l.r;
     const size_t dw = r.dst.image_width, dh = r.dst.image_height;
-    const RectifyParams p = rectify_params(r, l.n_frames, l.src_row, l.src_frame, dw, dw * dh);
+    const RectifyParams p = rectify_params(r, l.n_frames, l.src_row, l.src_frame, l.dst_row ? l.dst_row : dw, l.dst_row ? l.dst_frame : dw * dh);
     uint32_t tx, ty, tz;
     rectify_grid(p.dw, p.dh, l.n_frames, &tx, &ty, &tz);
     const dim3 grid(tx, ty, tz), block(WAVE * kTileH);

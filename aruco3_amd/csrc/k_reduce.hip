@@ -165,6 +165,8 @@ hipError_t launch_reduce_frames(hipStream_t st, const ReduceLaunch& l) {
     if (l.fmt == A3_FMT_L8) launch_reduce_fmt<A3_FMT_L8>(st, l.factor, l.src, l.dst, p);
     else if (l.fmt == A3_FMT_RGB8) launch_reduce_fmt<A3_FMT_RGB8>(st, l.factor, l.src, l.dst, p);
     else if (l.fmt == A3_FMT_RGBA8) launch_reduce_fmt<A3_FMT_RGBA8>(st, l.factor, l.src, l.dst, p);
+    else if (l.fmt == A3_FMT_YUYV8) launch_reduce_fmt<A3_FMT_YUYV8>(st, l.factor, l.src, l.dst, p);   // (packed 4:2:2: grey_row keeps the luma bytes)
+    else if (l.fmt == A3_FMT_UYVY8) launch_reduce_fmt<A3_FMT_UYVY8>(st, l.factor, l.src, l.dst, p);
     else launch_reduce_fmt<A3_FMT_BGRA8>(st, l.factor, l.src, l.dst, p);
     return hipGetLastError();
 }

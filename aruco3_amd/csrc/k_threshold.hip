@@ -34,7 +34,8 @@ __global__ void k_grey_generic(const uint8_t* __restrict__ pixels, size_t row_st
     const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x), y = blockIdx.y;
     if (x >= W) return;
     const uint32_t f = blockIdx.z;
-    constexpr int BPP = FMT == A3_FMT_RGB8 ? 3 : (FMT == A3_FMT_L8 ? 1 : 4);
+    constexpr int BPP = RawRow<FMT>::BPP;
+    constexpr int LO = FMT == A3_FMT_UYVY8 ? 1 : 0;   // packed 4:2:2: the luma byte of a pixel's two (the grey level as it stands)
     const uint8_t* p = pixels + (size_t)f * frame_stride + (size_t)y * row_stride + (size_t)x * BPP;
     uint8_t* out = grey + (size_t)f * W * H + (size_t)y * W + x;
     auto luma = [](uint32_t b0, uint32_t b1, uint32_t b2) -> uint32_t { return FMT == A3_FMT_BGRA8 ? luma_of(b2, b1, b0) : luma_of(b0, b1, b2); };
@@ -47,6 +48,7 @@ __global__ void k_grey_generic(const uint8_t* __restrict__ pixels, size_t row_st
         for (int i = 0; i < 4; i++) {
             uint32_t v;
             if (BPP == 1) v = (d[0] >> (8 * i)) & 0xFFu;
+            else if (BPP == 2) v = (d[i >> 1] >> (8 * (2 * (i & 1) + LO))) & 0xFFu;
             else {
                 const int b = i * BPP;   // byte offset of pixel i inside d[]
                 auto byte = [&](int k) -> uint32_t { return (d[k >> 2] >> (8 * (k & 3))) & 0xFFu; };
@@ -59,7 +61,7 @@ __global__ void k_grey_generic(const uint8_t* __restrict__ pixels, size_t row_st
     }
     for (int i = 0; i < 4 && x + i < W; i++) {
         const uint8_t* q = p + (size_t)i * BPP;
-        out[i] = BPP == 1 ? q[0] : (uint8_t)luma(q[0], q[1], q[2]);
+        out[i] = BPP == 1 ? q[0] : (BPP == 2 ? q[LO] : (uint8_t)luma(q[0], q[1], q[2]));
     }
 }
 
@@ -181,6 +183,8 @@ hipError_t launch_grey_threshold(hipStream_t st, const ThresholdLaunch& t) {
     if (fmt == A3_FMT_RGB8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_RGB8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
     else if (fmt == A3_FMT_RGBA8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_RGBA8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
     else if (fmt == A3_FMT_BGRA8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_BGRA8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
+    else if (fmt == A3_FMT_YUYV8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_YUYV8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
+    else if (fmt == A3_FMT_UYVY8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_UYVY8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
     else hipLaunchKernelGGL(k_grey_generic<A3_FMT_L8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
     if (hsum_tmp && radius <= 128u) {   // separable: row sums (<= 257 * 255 fit a u16), then a running column sum with the compare
         hipLaunchKernelGGL(k_hsum_generic, dim3((W + kHsumCols - 1) / kHsumCols, H, n), dim3(256), kHsumCols + 2 * ((radius + 3) & ~3u) + 16, st, grey, W, H, (int)radius, hsum_tmp);

@@ -69,7 +69,8 @@ __device__ __forceinline__ void slide_chain(const uint32_t* E, uint32_t* S) {   
 // grows (1.26-1.45 x of window 7); the largest radii fall back to R | R + 1 and one wave per SIMD (2.4-2.6 x).
 constexpr int kRingLdsRows8 = 19;
 constexpr int ring_reg_rows(int R, bool fast, int fmt) {   // (the limits: the largest radius whose instantiation needs no scratch)
-    const int last8 = !fast ? 19 : (fmt == A3_FMT_L8 ? 28 : (fmt == A3_FMT_RGB8 ? 26 : 24));
+    const bool yuv422 = fmt == A3_FMT_YUYV8 || fmt == A3_FMT_UYVY8;   // 8 raw dwords per row in flight: between L8's 4 and RGB8's 12
+    const int last8 = !fast ? 19 : (fmt == A3_FMT_L8 ? 28 : (yuv422 ? 27 : (fmt == A3_FMT_RGB8 ? 26 : 24)));
     return R + 1 <= kRingLdsRows8 ? R : (R <= last8 ? 2 * R + 1 - kRingLdsRows8 : R);
 }
 // apron lanes on either side of a wave and the output columns left to it
@@ -285,6 +286,8 @@ hipError_t launch_ring(hipStream_t st, const ThresholdLaunch& t) {
     if (fmt == A3_FMT_RGB8) A3_LAUNCH_RING(A3_FMT_RGB8)
     else if (fmt == A3_FMT_RGBA8) A3_LAUNCH_RING(A3_FMT_RGBA8)
     else if (fmt == A3_FMT_BGRA8) A3_LAUNCH_RING(A3_FMT_BGRA8)
+    else if (fmt == A3_FMT_YUYV8) A3_LAUNCH_RING(A3_FMT_YUYV8)
+    else if (fmt == A3_FMT_UYVY8) A3_LAUNCH_RING(A3_FMT_UYVY8)
     else A3_LAUNCH_RING(A3_FMT_L8)
 #undef A3_LAUNCH_RING
     return hipGetLastError();

@@ -31,7 +31,7 @@ __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) { return a + 
 __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) { return a - b; }
 
 template <int FMT> struct RawRow {
-    static constexpr int BPP = FMT == A3_FMT_RGB8 ? 3 : (FMT == A3_FMT_L8 ? 1 : 4);
+    static constexpr int BPP = FMT == A3_FMT_RGB8 ? 3 : (FMT == A3_FMT_L8 ? 1 : ((FMT == A3_FMT_YUYV8 || FMT == A3_FMT_UYVY8) ? 2 : 4));
     static constexpr int NDW = T_LPX * BPP / 4;
     uint32_t d[NDW];
 };
@@ -77,6 +77,13 @@ __device__ __forceinline__ void grey_row(const RawRow<FMT>& r, uint32_t g[T_NG])
     if constexpr (FMT == A3_FMT_L8) {
 #pragma unroll
         for (int i = 0; i < T_NG; i++) g[i] = r.d[i];
+    } else if constexpr (FMT == A3_FMT_YUYV8 || FMT == A3_FMT_UYVY8) {
+        // packed 4:2:2: the luma byte is the grey level as it stands.  Pixels 4 i .. 4 i + 3 are the even (YUYV) or odd (UYVY) bytes of
+        // the dwords 2 i and 2 i + 1: one v_perm_b32 per grey dword, the two formats differ in its selector only.  No chroma byte
+        // survives this line.
+        constexpr uint32_t sel = FMT == A3_FMT_YUYV8 ? 0x06040200u : 0x07050301u;
+#pragma unroll
+        for (int i = 0; i < T_NG; i++) g[i] = __builtin_amdgcn_perm(r.d[2 * i + 1], r.d[2 * i], sel);
     } else {
         // l = 2126 R + 7152 G + 722 B from two byte-wise dot products with the split weights 2126 = 8*256+78, 7152 = 27*256+240,
         // 722 = 2*256+210 (the first byte is R for RGB/RGBA, B for BGRA).  (l * 13743896) >> 32 for l < 2^22 is the upper half of
@@ -457,6 +464,8 @@ hipError_t launch_k1(hipStream_t st, const ThresholdLaunch& t) {
     if (fmt == A3_FMT_RGB8) { if (fast) A3_LAUNCH_K1(A3_FMT_RGB8, true); else A3_LAUNCH_K1(A3_FMT_RGB8, false); }
     else if (fmt == A3_FMT_RGBA8) { if (fast) A3_LAUNCH_K1(A3_FMT_RGBA8, true); else A3_LAUNCH_K1(A3_FMT_RGBA8, false); }
     else if (fmt == A3_FMT_BGRA8) { if (fast) A3_LAUNCH_K1(A3_FMT_BGRA8, true); else A3_LAUNCH_K1(A3_FMT_BGRA8, false); }
+    else if (fmt == A3_FMT_YUYV8) { if (fast) A3_LAUNCH_K1(A3_FMT_YUYV8, true); else A3_LAUNCH_K1(A3_FMT_YUYV8, false); }
+    else if (fmt == A3_FMT_UYVY8) { if (fast) A3_LAUNCH_K1(A3_FMT_UYVY8, true); else A3_LAUNCH_K1(A3_FMT_UYVY8, false); }
     else { if (fast) A3_LAUNCH_K1(A3_FMT_L8, true); else A3_LAUNCH_K1(A3_FMT_L8, false); }
 #undef A3_LAUNCH_K1
     return hipGetLastError();

@@ -32,18 +32,20 @@ def rectify_rec(intrinsics: CameraIntrinsics, new_intrinsics: CameraIntrinsics =
     return r
 
 
-def rectify_frames(frames, intrinsics: CameraIntrinsics, new_intrinsics: CameraIntrinsics = None, rotation=None, fill: int = 0):
+def rectify_frames(frames, intrinsics: CameraIntrinsics, new_intrinsics: CameraIntrinsics = None, rotation=None, fill: int = 0,
+                   pixel_format=None):
     """frames: H x W, H x W x C or N x H x W x C uint8 (C 1, 3 or 4), a numpy array or a torch tensor, of `intrinsics`' size.
     intrinsics: the camera (its `distortion` may be None); new_intrinsics: the rectified view and the output size (default: the same
     focal lengths, principal point and size, no lens); rotation: 3 x 3, camera -> rectified view (default: the identity); fill: the
-    value of every byte of a pixel that sees nothing.
-    -> N x H' x W' x C uint8: a CUDA tensor for a CUDA tensor (no host copy), else a numpy array."""
-    ptr, mem, fmt, w, h, row, frame, n, keep = _as_frames(frames)
+    value of every byte of a pixel that sees nothing; pixel_format: as in `Detector.detect_batch`.
+    -> N x H' x W' x C uint8: a CUDA tensor for a CUDA tensor (no host copy), else a numpy array.  Packed 4:2:2 ("yuyv" / "uyvy") and
+    planar ("nv12" ...) frames give their rectified LUMA view, C = 1: the plane a rectifying detector detects on."""
+    ptr, mem, fmt, w, h, row, frame, n, keep = _as_frames(frames, pixel_format)
     if (w, h) != (int(intrinsics.image_width), int(intrinsics.image_height)):
         raise ValueError(f"frames are {w} x {h}, the intrinsics say {intrinsics.image_width} x {intrinsics.image_height}")
     new = new_intrinsics if new_intrinsics is not None else intrinsics
     r = rectify_rec(intrinsics, new_intrinsics, rotation, fill)
-    c = row // w
+    c = 1 if fmt in (_lib.FMT_YUYV8, _lib.FMT_UYVY8) else row // w
     ow, oh = int(new.image_width), int(new.image_height)
     device = keep.device.index or 0 if mem == _lib.MEM_DEVICE else 0
     with _ctx_lock:

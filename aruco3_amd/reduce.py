@@ -8,7 +8,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from .aruco import _as_frames
+from .aruco import _as_frames, _pixel_format
 
 _ctxs = {}   # one context per device
 _ctx_lock = threading.Lock()
@@ -23,16 +23,13 @@ def reduction_rec(factor: int) -> "_lib.ReductionRec":
     return r
 
 
-def reduce_frames(frames, factor: int, bgra: bool = False):
+def reduce_frames(frames, factor: int, bgra: bool = False, pixel_format=None):
     """frames: H x W, H x W x C or N x H x W x C uint8 (C 1, 3 or 4), a numpy array or a torch tensor; factor 2, 3 or 4; bgra: 4-channel
-    frames are in the byte order B, G, R, A.
+    frames are in the byte order B, G, R, A; pixel_format: as in `Detector.detect_batch` ("yuyv" / "uyvy": N x H x W x 2, "nv12" ...:
+    N x 3H/2 x W; their luma is what is reduced).
     -> N x (H // factor) x (W // factor) uint8: a CUDA tensor for a CUDA tensor (no host copy), else a numpy array."""
-    ptr, mem, fmt, w, h, row, frame, n, keep = _as_frames(frames)
-    if bgra:
-        if fmt != _lib.FMT_RGBA8:
-            raise ValueError("bgra=True needs 4-channel frames")
-        fmt = _lib.FMT_BGRA8
-    f = reduction_rec(factor).factor
+    ptr, mem, fmt, w, h, row, frame, n, keep = _as_frames(frames, _pixel_format(pixel_format, bgra))
+    f =reduction_rec(factor).factor
     ow, oh = w // f, h // f
     device = keep.device.index or 0 if mem == _lib.MEM_DEVICE else 0
     with _ctx_lock:

@@ -43,7 +43,23 @@ enum {
 
 /* pixel layouts accepted where the reference takes an image::DynamicImage (src/aruco.rs:52,60) */
 enum { A3_FMT_RGB8 = 0, A3_FMT_RGBA8 = 1, A3_FMT_L8 = 2,
-       A3_FMT_BGRA8 = 3 /* webcam byte order (examples/webcam_kamera.rs:38-52 swizzles it on the CPU first) */ };
+       A3_FMT_BGRA8 = 3 /* webcam byte order (examples/webcam_kamera.rs:38-52 swizzles it on the CPU first) */,
+       /* (4 is unassigned and refused) */
+       A3_FMT_YUYV8 = 5 /* Y0 U Y1 V: the luma of pixel x is byte 2x   of its row */,
+       A3_FMT_UYVY8 = 6 /* U Y0 V Y1: the luma of pixel x is byte 2x+1 of its row */ };
+/* Packed 4:2:2 (A3_FMT_YUYV8, also called YUY2, and A3_FMT_UYVY8: what UVC webcams, V4L2 capture cards and SDI / HDMI grabbers deliver;
+ * not in the reference, whose DynamicImage has no such variant).  The frames are read in place by every stage:
+ *   - the grey level of pixel (x, y) is its luma byte AS IT STANDS: no range expansion from 16..235, and no chroma byte is ever used in
+ *     a result;
+ *   - a pixel takes 2 bytes in all stride arithmetic: row_stride 0 means 2 * width, and row_stride must be at least 2 * width;
+ *   - an odd width is A3_ERR_INVALID ("4:2:2 frames have an even width").
+ * THE LUMA RULE: any entry point that takes frames returns, for a 4:2:2 buffer, bit for bit what it returns for an A3_FMT_L8 buffer of
+ * the same width and height that holds those luma bytes -- ids, codes, integer corners, rotations, candidates, patches, refined corners,
+ * ChArUco corners, poses, rms values, reduced planes, rectified planes and the grey tap; with every setting (a3_set_corner_refinement,
+ * a3_set_board, a3_set_charuco, a3_set_board_recovery, a3_set_distortion, a3_set_reduction, a3_set_rectification).  a3_rectify_frames
+ * writes, for a 4:2:2 source, the rectified LUMA VIEW, one byte per pixel (see there).
+ * The luma plane of a planar frame (NV12, NV21, I420, YV12: H rows of luma followed by H / 2 rows of chroma) is read in place as
+ * A3_FMT_L8 with row_stride = width and frame_stride = width * 3 * H / 2. */
 /* where `pixels` lives */
 enum { A3_MEM_HOST = 0, A3_MEM_DEVICE = 1 };
 
@@ -1086,7 +1102,11 @@ int  a3_build_marker_maps(a3_ctx *ctx, const a3_map *maps, size_t n_maps, const 
  * nothing, as in the rational model: the output is a pinhole view.
  * The model is the forward model of the a3_set_distortion contract's check step, the blend that of the corner refinement.  The
  * output format equals the input format (1, 3 or 4 bytes per pixel); every byte is interpolated alike, so RGBA and BGRA are the same
- * work.  Bytes of dst between the end of a row's pixels and the next row are not written.  src and dst must not overlap.  Outside the
+ * work.  The one exception: a packed 4:2:2 source (A3_FMT_YUYV8, A3_FMT_UYVY8: an even width, 2 bytes per pixel in src's strides) gives
+ * the rectified LUMA VIEW, ONE byte per pixel -- the map and the blend above on the luma byte alone, i.e. what the call writes for an
+ * A3_FMT_L8 source holding those luma bytes, and the plane a3_set_rectification detects on; dst's strides are checked with 1 byte per
+ * pixel.  Chroma is not rectified.
+ * Bytes of dst between the end of a row's pixels and the next row are not written.  src and dst must not overlap.  Outside the
  * field where the rational model is monotone a ray can fold back into the image, as with OpenCV: documented, not guarded.
  * info (nullable): tiles = output tiles per frame, path_tiles[p] = how many of them launch path p of the kernel took (path 0 the
  * rational map, which also serves A3_DIST_NONE, path 1 the fisheye map, unused entries 0); the choice depends on the parameters
@@ -1131,7 +1151,7 @@ int  a3_rectify_frames(a3_ctx *ctx, const void *src, int src_memory, int fmt, si
  *   - corners are pixels of the rectified view; pose calls take the view's plain intrinsics (r->dst).
  *   - independent of a3_set_distortion: with both set the corners of a pose batch are undistorted twice.
  *   - the grey plane detection works on is luma_of (into_luma8's integers) of the rectified pixel's ROUNDED OUTPUT BYTES, in the format's
- *     channel order (A3_FMT_L8: the byte itself) -- what every sampler (threshold, decode, refinement, ChArUco) makes of the rectified
+ *     channel order (A3_FMT_L8: the byte itself; A3_FMT_YUYV8 / A3_FMT_UYVY8: the rectified luma byte) -- what every sampler (threshold, decode, refinement, ChArUco) makes of the rectified
  *     colour frame, which is why (1) + (2) above holds; a detector run on that plane as A3_FMT_L8 equals one run on the colour frames.
  *   - a3_download_grey and the other debug taps report the rectified view, sized r->dst.
  *   - the setter's argument errors (A3_ERR_INVALID) are those a3_rectify_frames makes for an a3_rectify: sizes, non-finite values, focal
@@ -1154,7 +1174,8 @@ int  a3_get_rectification(const a3_ctx *ctx, a3_rectify *r, int *enabled);
  *     (S + f*f/2) / (f*f)                               in integer division (f*f/2 = 2, 4, 8: the mean, rounded half up)
  *     S = the sum over the f x f block of source pixels (f*j + a, f*i + b), 0 <= a, b < f, of luma_of of the pixel
  * where luma_of gives into_luma8's integers, (2126 R + 7152 G + 722 B) / 10000 truncated, in the format's channel order; for
- * A3_FMT_L8 it is the byte itself, and alpha is ignored.  The output is always ONE byte per pixel, whatever the input format, the same
+ * A3_FMT_L8 it is the byte itself, for A3_FMT_YUYV8 / A3_FMT_UYVY8 the pixel's luma byte (an even width, or A3_ERR_INVALID), and alpha
+ * is ignored.  The output is always ONE byte per pixel, whatever the input format, the same
  * arithmetic for every frame of the call.  Bytes of dst between the end of a row's w bytes and the next row are not written.  src and
  * dst must not overlap.  Synchronous; not while a submitted batch is in flight.  Host-side src or dst is staged through device buffers
  * with plain copies.  The strides are in bytes and are taken as given (0 is no default here).

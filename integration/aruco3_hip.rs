@@ -57,6 +57,11 @@ pub const A3_FMT_RGBA8: c_int = 1;
 pub const A3_FMT_L8: c_int = 2;
 /// webcam byte order: examples/webcam_kamera.rs:38-52 re-orders it on the CPU today; the kernel reads it as it is
 pub const A3_FMT_BGRA8: c_int = 3;
+/// packed 4:2:2 as UVC webcams and capture cards deliver it, 2 bytes per pixel, read in place: the luma byte is the grey level as it
+/// stands (Y0 U Y1 V: byte 2x of the row; U Y0 V Y1: byte 2x+1) and the result is, to the bit, that of the luma plane as A3_FMT_L8.
+/// (4 is unassigned and refused.)  `DynamicImage` has no such variant: `Detector::detect_raw` takes the bytes.
+pub const A3_FMT_YUYV8: c_int = 5;
+pub const A3_FMT_UYVY8: c_int = 6;
 pub const A3_MEM_HOST: c_int = 0;
 pub const A3_MEM_DEVICE: c_int = 1;
 
@@ -1337,6 +1342,48 @@ impl Detector {
             out.push(det);
         }
         out
+    }
+
+    /// New (additive): `detect` of one frame handed over as raw bytes in any layout the library takes (`fmt`: an A3_FMT_*), for the
+    /// layouts `DynamicImage` cannot hold -- A3_FMT_YUYV8 / A3_FMT_UYVY8 straight from a V4L2 buffer, A3_FMT_BGRA8, or the luma plane
+    /// of an NV12 / I420 buffer as A3_FMT_L8.  `row_stride` in bytes, 0 = tightly packed; `bytes` must hold `height` such rows (the last
+    /// one may end with its pixels).  The Detection is what `detect` returns for the frame's grey levels; `Detector` gains no field.
+    pub fn detect_raw(&self, bytes: &[u8], fmt: c_int, width: u32, height: u32, row_stride: usize) -> Detection {
+        let bpp: usize = match fmt {
+            A3_FMT_RGB8 => 3,
+            A3_FMT_RGBA8 | A3_FMT_BGRA8 => 4,
+            A3_FMT_YUYV8 | A3_FMT_UYVY8 => 2,
+            A3_FMT_L8 => 1,
+            _ => panic!("aruco3_hip: detect_raw: unknown pixel format {}", fmt),
+        };
+        let row = if row_stride == 0 { width as usize * bpp } else { row_stride };
+        assert!(row >= width as usize * bpp, "aruco3_hip: detect_raw: row_stride smaller than a row");
+        let need = if height == 0 { 0 } else { row * (height as usize - 1) + width as usize * bpp };
+        assert!(bytes.len() >= need, "aruco3_hip: detect_raw: {} bytes given, the frame spans {}", bytes.len(), need);
+        let populate = POPULATE.load(Ordering::Relaxed);
+        let slot = slot_for(self);
+        let ctx = slot.lock().unwrap();
+        ctx.check(unsafe { a3_set_debug_taps(ctx.raw, populate as c_int) }, "a3_set_debug_taps");
+        let mut markers = vec![A3Marker::default(); 64];
+        let mut per = vec![0u32; 1];
+        let mut found = 0usize;
+        loop {
+            let rc = unsafe {
+                a3_detect_batch(ctx.raw, bytes.as_ptr() as *const c_void, A3_MEM_HOST, fmt, width, height, row, row * height as usize, 1,
+                                markers.as_mut_ptr(), markers.len(), per.as_mut_ptr(), &mut found)
+            };
+            if rc == A3_ERR_CAPACITY && markers.len() < MAX_MARKERS_PER_FRAME {
+                markers.resize(markers.len() * 4, A3Marker::default());
+                continue;
+            }
+            ctx.check(rc, "a3_detect_batch");
+            break;
+        }
+        let mut det = Detection { grey: None, candidates: vec![], homographies: vec![], markers: markers[..found].iter().map(marker_of).collect() };
+        if populate && width != 0 && height != 0 {
+            fill_debug_outputs(&ctx, 0, width, height, self.config.homography_sample_size as u32, &mut det);
+        }
+        det
     }
 
     /// New (additive): detect + both IPPE poses of every marker in one device pass (callers always solve the pose right after
