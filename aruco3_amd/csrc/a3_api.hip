@@ -99,19 +99,19 @@ struct Batch {
     bool recover = false;
     a3_recover_config recover_cfg{};
     uint32_t recover_slots = 0, recover_cap = 0;   // board markers; records a frame's recovery can hold (ensure_back_buffers)
-    // a3_set_rectification in force: the call's frames (rect_src, in rect_fmt, with strides rect_row and rect_frame) are the SOURCE, seen
-    // through rect_r.  pixels, fmt, W, H, row_stride and frame_stride above then describe the rectified grey plane (A3_FMT_L8, r.dst's size),
-    // which k_rectify's grey form writes ahead of the threshold kernel; everything behind that launch sees nothing else
-    bool rect = false;
+    uint32_t sides = 0;          // the side results all of this turns on, one bit per SideKind (a3_readback.h)
+    bool has(int kind) const { return (sides >> kind & 1u) != 0; }
+    // The call's frames as staged on the device (frames, of frames_W x frames_H pixels).  With a3_set_rectification or a3_set_reduction in
+    // force (they exclude each other) they are the SOURCE of a derived grey plane, and pixels, fmt, W, H, row_stride and frame_stride above
+    // describe that plane (A3_FMT_L8, tightly packed), written ahead of the threshold kernel:
+    //   Rectified: the frames seen through rect_r, of rect_r.dst's size, by k_rectify's grey form; everything behind that launch sees nothing else
+    //   Reduced: frames_W / reduce_f x frames_H / reduce_f, by k_reduce_frames; the front half (threshold ... decode, recovery) sees nothing
+    //     else, and the back half (refinement, ChArUco, poses) works on `frames` from the corners k_scale_markers mapped back up
+    enum class Plane { None, Rectified, Reduced } plane = Plane::None;
+    PixelSrc frames{};
+    uint32_t frames_W = 0, frames_H = 0;
     a3_rectify rect_r{};
-    const uint8_t* rect_src = nullptr; int rect_fmt = 0; size_t rect_row = 0, rect_frame = 0;
-    // a3_set_reduction in force (reduce_f != 0): the call's frames (full, of full_W x full_H pixels) are the SOURCE of the reduced grey
-    // plane.  pixels, fmt, W, H, row_stride and frame_stride above then describe that plane (A3_FMT_L8, full size / reduce_f), which
-    // k_reduce_frames writes ahead of the threshold kernel: the front half (threshold ... decode, recovery) sees nothing else, and the back
-    // half (refinement, ChArUco, poses) works on `full` from the corners k_scale_markers mapped back up
     uint32_t reduce_f = 0;
-    PixelSrc full{};
-    uint32_t full_W = 0, full_H = 0;
     bool taps = false;           // debug taps: grey plane, patches, contours and the per-frame candidate counts are kept
     bool sample_frames = false;  // a3_debug_sample_frames: a tapped batch still samples the caller's frames wherever an untapped one would
     int profiling = 0, profile_every = 1;   // a3_set_profiling in force
@@ -211,15 +211,18 @@ struct a3_ctx {
     DevBuf hsum;                // row sums of the grey plane (u16): the separable threshold path only (windows above 15)
     DevBuf wtab;                // triangle-resize weights of a full patch (sample -> mark_size), written once at a3_create
     DevBuf pose_buf;            // a3_detect_batch_pose: both poses of every marker of the last batch (kept for a3_pack_detections)
-    bool poses_valid = false;
+    // The side results (kSides, a3_readback.h), by kind: where the batch in flight has them on the device (ensure_back_buffers), the copy
+    // finish_batch kept for the getters, and whether the last collected batch produced the kind.  (Poses have no kept copy: their flag
+    // says that pose_buf holds the last batch's, for a3_pack_detections.)
+    void* side_dev[kSideKinds] = {};
+    std::vector<uint8_t> side_h[kSideKinds];
+    bool side_valid[kSideKinds] = {};
     // a3_set_corner_refinement: the setting later batches capture; refine_prm holds the kernel parameters (weight tables) built for
     // refine_prm_cfg, rebuilt when a batch brings another setting
     a3_refine_config refine{};
     a3_refine_config refine_prm_cfg{};
     std::vector<float> refine_prm;
     DevBuf refined_buf;          // refined corners of the last batch on the device (8 floats per marker, marker order)
-    std::vector<float> h_refined;
-    bool refined_valid = false;  // the last collected batch ran with refinement: h_refined holds its corners
     // a3_set_board: the board later batches capture (board_ids; board_slots: one BoardSlot record per marker) and its device tables
     // (id -> slot, slot records), brought up to date at the next submit when board_version moved -- never while a batch of this
     // context is in flight, so a batch keeps the board it was submitted with
@@ -229,23 +232,17 @@ struct a3_ctx {
     std::vector<uint16_t> board_slot_up;   // (the sources of the last upload, untouched until the next one)
     std::vector<uint8_t> board_slots_up;
     DevBuf board_slot_of, board_slot_rec, board_buf;   // id -> slot (n_codes x u16), slot records, board poses of the last batch (per frame)
-    std::vector<a3_board_pose> h_board;
-    bool board_valid = false;   // the last collected batch was a pose batch with a board: h_board holds its poses
     // a3_set_board_recovery: the setting later batches capture; the board's ids in slot order on the device (brought up to date with the
     // board's tables); the side list the marker gather writes ([total, padded to 16 bytes | per-frame counts | recovered per frame] in
-    // recover_counts, the markers in recover_det), the per-frame records of k_recover_frames; the last collected batch's counts
+    // recover_counts, the markers in recover_det), the per-frame records of k_recover_frames
     a3_recover_config recover{};
     uint64_t recover_ids_version = 0;
     std::vector<uint32_t> recover_ids_up;
     DevBuf recover_ids, recover_counts, recover_det, recover_tmp;
-    std::vector<uint32_t> h_recovered;
-    bool recovered_valid = false;
     // a3_set_distortion: the setting later pose batches capture; undist_buf holds the undistorted corners of the last batch on the
     // device: [marker_cap x 8 floats | marker_cap x 4 residuals]
     a3_distortion dist{};
     DevBuf undist_buf;
-    std::vector<float> h_undist, h_undist_res;
-    bool undist_valid = false;  // the last collected batch ran with distortion: h_undist / h_undist_res hold its corners
     // a3_set_charuco: the chessboard later batches capture (charuco_tab_h: [2 floats per corner | 4 adjacent ids per corner]) and its
     // device copy, brought up to date at the next submit as the board's; charuco_prm: the refinement parameters built for charuco_prm_cfg
     a3_charuco_config charuco_cfg{};
@@ -258,25 +255,22 @@ struct a3_ctx {
     // the last batch on the device: per-frame slots [n x nc records | n + 1 counts], the records in (frame, id) order, their undistorted
     // pixels (pose batches with distortion) and the poses
     DevBuf charuco_tab, charuco_tmp, charuco_buf, charuco_und, charuco_pose_buf;
-    std::vector<a3_charuco_corner> h_charuco;
-    std::vector<a3_charuco_pose> h_charuco_pose;
-    bool charuco_valid = false, charuco_pose_valid = false;
+    std::vector<a3_charuco_corner> h_charuco;   // the last collected batch's corner records, and whether it ran with ChArUco
+    bool charuco_valid = false;
     // The solver entry points (a3_calibrate_cameras ... a3_build_marker_maps): the call's staged input, the kernel's scratch, the
     // maps' reduced systems (two n x n per map: sized very differently from the rest) and the results.  One set serves them all: each
     // of these calls refuses to start while a batch is in flight and waits for its own work before it returns.
     DevBuf solve_in, solve_scratch, solve_big, solve_out;
     // a3_rectify_frames: host-side source frames and host-side output staged on the device
     DevBuf rect_in, rect_out;
-    // a3_set_rectification: the setting later batches capture, and the rectified grey plane of the batch in flight (n x dw x dh bytes,
-    // tightly packed): written ahead of the threshold kernel, sampled by the decode stage, the refinement and ChArUco until collect
+    // a3_set_rectification and a3_set_reduction (factor 0: off): the settings later batches capture, one of them at the most, and the
+    // derived grey plane of the batch in flight (Batch::plane; n x w x h bytes, tightly packed): written ahead of the threshold kernel,
+    // sampled by the decode stage (rectified: also by the refinement and ChArUco) until collect.  a3_reduce_frames stages host-side
+    // frames and output in rect_in / rect_out as a3_rectify_frames does (both calls are synchronous)
     a3_rectify rect{};
     bool rect_on = false;
-    DevBuf rect_plane;
-    // a3_set_reduction: the setting later batches capture (factor 0: off), and the reduced grey plane of the batch in flight (n x w x h
-    // bytes, tightly packed), owned like rect_plane; a3_reduce_frames stages host-side frames and output in rect_in / rect_out (both calls
-    // are synchronous)
     a3_reduction reduction{};
-    DevBuf reduce_plane;
+    DevBuf plane;
     uint32_t last_charuco_total = 0;   // sizes the speculative record read-back of the next batch
     void* pinned = nullptr;
     size_t pinned_cap = 0;
@@ -499,7 +493,7 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     dec.grid_blocks = (int)std::min<uint32_t>(4096u, b.n * 128u);   // (grid-stride over the work list; 4096 workgroups that find nothing cost a one-frame call ~4 us)
     uint32_t* side_total = nullptr, * side_per_frame = nullptr, * recovered = nullptr;   // recover_counts: [total, padded | per frame | recovered per frame]
     if (b.recover) {
-        side_total = ctx->recover_counts.as<uint32_t>(); side_per_frame = side_total + 4; recovered = side_per_frame + b.n;   // the gather's list, counts and total go to the side buffers; the batch's own are written by k_recover_merge
+        side_total = ctx->recover_counts.as<uint32_t>(); side_per_frame = side_total + 4; recovered = static_cast<uint32_t*>(ctx->side_dev[kSideRecovered]);   // the gather's list, counts and total go to the side buffers; the batch's own are written by k_recover_merge
         A3_HIP(hipMemsetAsync(side_total, 0, 16 + (size_t)b.n * 4, st));
         dec.markers = ctx->recover_det.as<a3_marker>(); dec.per_frame = side_per_frame; dec.marker_total = side_total;
     }
@@ -518,16 +512,17 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     }
     // what everything behind the marker list samples and measures by: the decode stage's source, or with a reduction the caller's
     // full-size frames, on which the list's corners lie once k_scale_markers has mapped them up
-    const PixelSrc back_src = b.reduce_f ? b.full : b.src;
-    const uint32_t back_W = b.reduce_f ? b.full_W : b.W, back_H = b.reduce_f ? b.full_H : b.H;
-    if (b.reduce_f) A3_HIP(launch_scale_markers(st, {.markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap, .factor = b.reduce_f}));
+    const bool reduced = b.plane == Batch::Plane::Reduced;
+    const PixelSrc back_src = reduced ? b.frames : b.src;
+    const uint32_t back_W = reduced ? b.frames_W : b.W, back_H = reduced ? b.frames_H : b.H;
+    if (reduced) A3_HIP(launch_scale_markers(st, {.markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap, .factor = b.reduce_f}));
     float* const refined = b.refined ? ctx->refined_buf.as<float>() : nullptr;
     if (b.refined)   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
         A3_HIP(launch_refine_corners(st, {.src = back_src, .W = back_W, .H = back_H, .markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap,
                                           .params = refine_params_for(ctx, b.refine), .out = refined}));
     if (b.undist)   // undistorted pixel corners of the same markers (of their refined corners with refinement on)
         A3_HIP(launch_undistort_corners(st, ctx->markers_ptr, refined, d_marker_total, b.marker_cap, b.pose_intr, b.dist, ctx->undist_buf.as<float>(),
-                                        ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
+                                        static_cast<float*>(ctx->side_dev[kSideUndistRes])));
     // the batch's marker list with the float corners the poses are solved from: undistorted, else refined, else none (the integer corners)
     MarkerSrc m{.markers = ctx->markers_ptr, .n_dev = d_marker_total, .per_frame = ctx->per_frame, .corners = b.undist ? ctx->undist_buf.as<float>() : refined,
                 .n = b.marker_cap, .n_frames = b.n};
@@ -566,19 +561,12 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     const Readback& rb = b.rb;
     auto stage = [&](const Span& to, const void* from) { return hipMemcpyAsync(at<uint8_t>(ctx->pinned, to), from, to.bytes, hipMemcpyDeviceToHost, st); };
     A3_HIP(hipMemcpyAsync(ctx->pinned, ctx->head, rb.head.bytes + rb.markers.bytes, hipMemcpyDeviceToHost, st));
-    if (b.want_pose) A3_HIP(stage(rb.poses, ctx->pose_buf.p));
-    if (b.refined) A3_HIP(stage(rb.refined, ctx->refined_buf.p));
-    if (b.board) A3_HIP(stage(rb.board, ctx->board_buf.p));
-    if (b.undist) {
-        A3_HIP(stage(rb.undist, ctx->undist_buf.p));
-        A3_HIP(stage(rb.undist_res, ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
-    }
+    for (int k = 0; k < kSideKinds; k++)
+        if (b.has(k)) A3_HIP(stage(rb.side[k], ctx->side_dev[k]));
     if (b.charuco) {
         A3_HIP(hipMemcpyAsync(at<uint8_t>(ctx->pinned, rb.charuco_total), charuco_counts + b.n, 4, hipMemcpyDeviceToHost, st));
         A3_HIP(stage(rb.charuco, ctx->charuco_buf.p));
-        if (b.want_pose) A3_HIP(stage(rb.charuco_poses, ctx->charuco_pose_buf.p));
     }
-    if (b.recover) A3_HIP(stage(rb.recovered, recovered));
     if (b.taps) {   // Detection.candidates / .homographies will be asked for frame by frame: their counts travel now
         A3_HIP(hipMemcpyAsync(ctx->pinned_counts, ctx->cand_count, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
         A3_HIP(hipMemcpyAsync((uint8_t*)ctx->pinned_counts + (size_t)b.n * 4, ctx->fin_count.p, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
@@ -647,20 +635,25 @@ int flush_held_locked(a3_ctx* ctx, hipEvent_t after, bool by_last_member = false
 // ...; a longer list is fetched by finish_batch after growing it), pinned staging for the tap counts.
 int ensure_back_buffers(a3_ctx* ctx, Batch& b, size_t head_bytes) {
     b.rb = readback_layout(readback_shape(b, head_bytes));   // (guess and charuco_guess are fixed; the head's size is known now)
-    if (b.want_pose) A3_HIP(ctx->pose_buf.ensure((size_t)b.marker_cap * 2 * sizeof(a3_pose)));
-    if (b.refined) A3_HIP(ctx->refined_buf.ensure((size_t)b.marker_cap * 8 * sizeof(float)));
-    if (b.board) A3_HIP(ctx->board_buf.ensure((size_t)b.n * sizeof(a3_board_pose)));
-    if (b.undist) A3_HIP(ctx->undist_buf.ensure((size_t)b.marker_cap * 12 * sizeof(float)));
+    void** const side = ctx->side_dev;   // (where each side result of this batch is written: what the read-back copies from)
+    if (b.want_pose) { A3_HIP(ctx->pose_buf.ensure((size_t)b.marker_cap * 2 * sizeof(a3_pose))); side[kSidePoses] = ctx->pose_buf.p; }
+    if (b.refined) { A3_HIP(ctx->refined_buf.ensure((size_t)b.marker_cap * 8 * sizeof(float))); side[kSideRefined] = ctx->refined_buf.p; }
+    if (b.board) { A3_HIP(ctx->board_buf.ensure((size_t)b.n * sizeof(a3_board_pose))); side[kSideBoard] = ctx->board_buf.p; }
+    if (b.undist) {
+        A3_HIP(ctx->undist_buf.ensure((size_t)b.marker_cap * 12 * sizeof(float)));
+        side[kSideUndist] = ctx->undist_buf.p; side[kSideUndistRes] = ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8;
+    }
     if (b.charuco) {
         const size_t recs = (size_t)b.n * b.charuco_nc;
         A3_HIP(ctx->charuco_tmp.ensure(charuco_slot_bytes(b) + ((size_t)b.n + 1) * 4));
         A3_HIP(ctx->charuco_buf.ensure(std::max<size_t>(recs, 1) * sizeof(a3_charuco_corner)));
-        if (b.want_pose) A3_HIP(ctx->charuco_pose_buf.ensure((size_t)b.n * sizeof(a3_charuco_pose)));
+        if (b.want_pose) { A3_HIP(ctx->charuco_pose_buf.ensure((size_t)b.n * sizeof(a3_charuco_pose))); side[kSideCharucoPoses] = ctx->charuco_pose_buf.p; }
         if (b.want_pose && b.undist) A3_HIP(ctx->charuco_und.ensure(std::max<size_t>(recs, 1) * 8));
     }
     if (b.recover) {
         b.recover_cap = std::min(b.recover_slots, b.max_cand);
         A3_HIP(ctx->recover_counts.ensure(16 + (size_t)b.n * 8));
+        side[kSideRecovered] = ctx->recover_counts.as<uint32_t>() + 4 + b.n;   // [total, padded | per frame | recovered per frame]
         A3_HIP(ctx->recover_det.ensure((size_t)b.marker_cap * sizeof(a3_marker)));
         A3_HIP(ctx->recover_tmp.ensure((size_t)b.n * b.recover_cap * sizeof(a3_marker)));
     }
@@ -735,17 +728,19 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     if (b.taps) { A3_HIP(ctx->patches.ensure((size_t)b.patch_cap * ctx->cfg.homography_sample_size * ctx->cfg.homography_sample_size)); ctx->patch_cap = b.patch_cap; }
     ctx->W = W; ctx->H = H; ctx->frames = n;
     ctx->stats = a3_stats{};
-    ctx->contours_valid = false; ctx->markers_valid = false; ctx->poses_valid = false;
+    ctx->contours_valid = false; ctx->markers_valid = false; ctx->side_valid[kSidePoses] = false;
 
     // ---- K1 ----
     b.prof = b.profiling == 1 && (ctx->batch_seq++ % (uint32_t)b.profile_every) != 0 ? 0 : b.profiling;
-    if (b.rect)   // the frames' rectified grey plane, immediately ahead of its reader on the same stream: whatever orders that orders this
-        A3_HIP(launch_rectify_grey(st, {.src = b.rect_src, .src_row = b.rect_row, .src_frame = b.rect_frame, .n_frames = n, .fmt = b.rect_fmt, .r = &b.rect_r,
-                                        .grey = ctx->rect_plane.as<uint8_t>()}));
-    if (b.reduce_f)   // likewise the frames' reduced grey plane
-        A3_HIP(launch_reduce_frames(st, {.src = b.full.base, .src_row = (size_t)b.full.row_stride, .src_frame = (size_t)b.full.frame_stride, .n_frames = n,
-                                         .fmt = b.full.fmt, .W = b.full_W, .H = b.full_H, .factor = b.reduce_f, .dst = ctx->reduce_plane.as<uint8_t>(),
-                                         .dst_row = W, .dst_frame = npx}));
+    // the frames' derived grey plane, immediately ahead of its reader on the same stream: whatever orders that orders this
+    const PixelSrc& fr = b.frames;
+    if (b.plane == Batch::Plane::Rectified)
+        A3_HIP(launch_rectify_grey(st, {.src = fr.base, .src_row = (size_t)fr.row_stride, .src_frame = (size_t)fr.frame_stride, .n_frames = n, .fmt = fr.fmt,
+                                        .r = &b.rect_r, .grey = ctx->plane.as<uint8_t>()}));
+    if (b.plane == Batch::Plane::Reduced)
+        A3_HIP(launch_reduce_frames(st, {.src = fr.base, .src_row = (size_t)fr.row_stride, .src_frame = (size_t)fr.frame_stride, .n_frames = n, .fmt = fr.fmt,
+                                         .W = b.frames_W, .H = b.frames_H, .factor = b.reduce_f, .dst = ctx->plane.as<uint8_t>(), .dst_row = W,
+                                         .dst_frame = npx}));
     if (b.prof) A3_HIP(hipEventRecord(ctx->ev[0], st));
     A3_HIP(launch_grey_threshold(st, {.pixels = b.pixels, .fmt = b.fmt, .row_stride = b.row_stride, .frame_stride = b.frame_stride, .W = (int)W, .H = (int)H,
                                       .n = n, .radius = ctx->cfg.threshold_window, .grey = b.need_grey ? ctx->grey.as<uint8_t>() : nullptr,
@@ -1002,24 +997,14 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     if (per_frame_count) memcpy(per_frame_count, hpf, (size_t)n * 4);
     uint32_t max_per_frame = 0;   // (read now: the staging buffer may be re-allocated below)
     for (uint32_t f = 0; f < n; f++) max_per_frame = std::max(max_per_frame, hpf[f]);
-    if (b.board) {   // (read now: the staging buffer may be re-allocated below)
-        const a3_board_pose* hb = at<a3_board_pose>(hp, rb.board);
-        ctx->h_board.assign(hb, hb + n);
-    }
-    if (b.recover) {   // (read now, as the board poses)
-        const uint32_t* hr = at<uint32_t>(hp, rb.recovered);
-        ctx->h_recovered.assign(hr, hr + n);
-    }
-    if (b.charuco) {   // (read now, as the board poses)
+    for (int k = 0; k < kSideKinds; k++)   // the per-frame kinds (read now: the staging buffer may be re-allocated below)
+        if (b.has(k) && kSides[k].per_frame) ctx->side_h[k].assign(at<uint8_t>(hp, rb.side[k]), at<uint8_t>(hp, rb.side[k]) + rb.side[k].bytes);
+    if (b.charuco) {   // (read now, as the per-frame kinds)
         uint32_t charuco_total = 0;
         memcpy(&charuco_total, at<uint8_t>(hp, rb.charuco_total), 4);
         ctx->h_charuco.resize(charuco_total);
         const size_t staged = std::min<uint32_t>(charuco_total, b.charuco_guess);
         if (staged) memcpy(ctx->h_charuco.data(), at<uint8_t>(hp, rb.charuco), staged * sizeof(a3_charuco_corner));
-        if (b.want_pose) {
-            const a3_charuco_pose* hq = at<a3_charuco_pose>(hp, rb.charuco_poses);
-            ctx->h_charuco_pose.assign(hq, hq + n);
-        }
         if (charuco_total > staged) {   // the guess was short: the rest of the records, straight from the device
             A3_HIP(hipMemcpyAsync(ctx->h_charuco.data() + staged, ctx->charuco_buf.as<a3_charuco_corner>() + staged,
                                   (charuco_total - staged) * sizeof(a3_charuco_corner), hipMemcpyDeviceToHost, st));
@@ -1033,30 +1018,20 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         hp = (uint8_t*)ctx->pinned;
         auto fetch = [&](const Span& to, const void* from) { return hipMemcpyAsync(at<uint8_t>(hp, to), from, to.bytes, hipMemcpyDeviceToHost, st); };
         A3_HIP(fetch(rb.markers, ctx->markers_ptr));
-        if (b.want_pose) A3_HIP(fetch(rb.poses, ctx->pose_buf.p));
-        if (b.refined) A3_HIP(fetch(rb.refined, ctx->refined_buf.p));
-        if (b.undist) {
-            A3_HIP(fetch(rb.undist, ctx->undist_buf.p));
-            A3_HIP(fetch(rb.undist_res, ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8));
-        }
+        for (int k = 0; k < kSideKinds; k++)
+            if (b.has(k) && !kSides[k].per_frame) A3_HIP(fetch(rb.side[k], ctx->side_dev[k]));
         A3_HIP(hipStreamSynchronize(ctx->stream));
     }
     if (total) {
         memcpy(out, at<a3_marker>(hp, rb.markers), (size_t)total * sizeof(a3_marker));
-        if (b.want_pose && poses) memcpy(poses, at<a3_pose>(hp, rb.poses), (size_t)total * 2 * sizeof(a3_pose));
+        if (b.want_pose && poses) memcpy(poses, at<a3_pose>(hp, rb.side[kSidePoses]), (size_t)total * 2 * sizeof(a3_pose));
     }
-    const float* h_refined = at<float>(hp, rb.refined), * h_undist = at<float>(hp, rb.undist), * h_undist_res = at<float>(hp, rb.undist_res);
-    if (b.refined) ctx->h_refined.assign(h_refined, h_refined + (size_t)total * 8);
-    ctx->refined_valid = b.refined;
-    if (b.undist) {
-        ctx->h_undist.assign(h_undist, h_undist + (size_t)total * 8);
-        ctx->h_undist_res.assign(h_undist_res, h_undist_res + (size_t)total * 4);
+    for (int k = 0; k < kSideKinds; k++) {   // the per-marker kinds: `total` records each; from here on the getters answer for this batch
+        const uint8_t* const h = at<uint8_t>(hp, rb.side[k]);
+        if (b.has(k) && !kSides[k].per_frame && kSides[k].kept) ctx->side_h[k].assign(h, h + (size_t)total * kSides[k].rec);
+        ctx->side_valid[k] = b.has(k);
     }
-    ctx->undist_valid = b.undist;
-    ctx->board_valid = b.board;
-    ctx->recovered_valid = b.recover;
     ctx->charuco_valid = b.charuco;
-    ctx->charuco_pose_valid = b.charuco && b.want_pose;
     if (b.taps) {
         const uint32_t* hc32 = reinterpret_cast<const uint32_t*>(ctx->pinned_counts);
         ctx->h_cand_pre.assign(hc32, hc32 + n);
@@ -1070,7 +1045,6 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     ctx->stats.candidates = n_work;      // work items = quads that survived discard_too_near
     ctx->stats.candidates_pre = n_pre;   // quads after contours_to_candidates (k_compact_markers sums the per-frame counts)
     ctx->markers_valid = true; ctx->last_n = n; ctx->last_max_per_frame = max_per_frame;
-    ctx->poses_valid = b.want_pose;
     ctx->contours_valid = b.taps && n_chunks == 1;
     if (ctx->contours_valid) { ctx->tap_contours = v.tap_contours; ctx->tap_points = v.tap_points; }
     if (b.prof >= 1) {   // the level in force when the batch was enqueued
@@ -1089,15 +1063,17 @@ int run_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint3
     return finish_batch(ctx, out, poses, out_cap, per_frame_count, out_n);
 }
 
-// The getters of the last collected batch's results, their pointers checked: the records (`per` elements each) of the host copy `v` that
+// The getters of the last collected batch's results, their pointers checked: the records (`rec` bytes each) of the host copy that
 // finish_batch kept, refused with `without` when that batch ran without the feature and with `small` when dst holds fewer.
-template <typename T>
-int get_last(a3_ctx* ctx, bool valid, const std::vector<T>& v, size_t per, T* dst, size_t cap, size_t* n, const char* without, const char* small) {
+int get_last(a3_ctx* ctx, bool valid, const void* kept, size_t bytes, size_t rec, void* dst, size_t cap, size_t* n, const char* without, const char* small) {
     if (!valid) return fail(ctx, A3_ERR_INVALID, without);
-    *n = v.size() / per;
+    *n = bytes / rec;
     if (*n > cap) return fail(ctx, A3_ERR_CAPACITY, small);
-    if (*n) memcpy(dst, v.data(), v.size() * sizeof(T));
+    if (*n) memcpy(dst, kept, bytes);
     return A3_OK;
+}
+int get_side(a3_ctx* ctx, SideKind k, void* dst, size_t cap, size_t* n, const char* without, const char* small) {
+    return get_last(ctx, ctx->side_valid[k], ctx->side_h[k].data(), ctx->side_h[k].size(), kSides[k].rec, dst, cap, n, without, small);
 }
 
 // a3_calibrate_cameras and a3_calibrate_fisheye_cameras: the same checks and staging.  The fisheye model keeps the start's compacted
@@ -1261,7 +1237,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
                       &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->solve_in,
-                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out, &ctx->rect_plane, &ctx->reduce_plane};
+                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out, &ctx->plane};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1464,28 +1440,21 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
     b.taps = ctx->debug_taps;
     b.sample_frames = ctx->debug_sample_frames;
     b.profiling = ctx->profiling; b.profile_every = ctx->profile_every;
-    ctx->board_valid = false;
-    ctx->recovered_valid = false;
-    ctx->undist_valid = false;
-    ctx->charuco_valid = false; ctx->charuco_pose_valid = false;
+    b.sides = sides_on(readback_shape(b, 0));
+    for (int k = 0; k < kSideKinds; k++)
+        if (kSides[k].begin_clears) ctx->side_valid[k] = false;
+    ctx->charuco_valid = false;
     b.row_stride = row_stride; b.frame_stride = frame_stride;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &b.row_stride, &b.frame_stride, n_frames, &b.pixels);
     if (rc != A3_OK) return rc;
-    if (ctx->rect_on) {   // from here on the batch is an A3_FMT_L8 device batch of the view's size whose frames are the plane
-        b.rect = true; b.rect_r = ctx->rect;
-        b.rect_src = b.pixels; b.rect_fmt = fmt; b.rect_row = b.row_stride; b.rect_frame = b.frame_stride;
-        const size_t dw = b.rect_r.dst.image_width, dh = b.rect_r.dst.image_height;
-        A3_HIP(ctx->rect_plane.ensure(dw * dh * n_frames));
-        b.pixels = ctx->rect_plane.as<uint8_t>(); b.fmt = A3_FMT_L8; b.W = (uint32_t)dw; b.H = (uint32_t)dh;
-        b.row_stride = dw; b.frame_stride = dw * dh;
-    }
-    if (ctx->reduction.factor) {   // from here on the front half's batch is an A3_FMT_L8 device batch of the reduced size whose frames are the plane
-        const uint32_t f = ctx->reduction.factor;
-        b.reduce_f = f;
-        b.full = PixelSrc{b.pixels, b.row_stride, b.frame_stride, fmt}; b.full_W = width; b.full_H = height;
-        const size_t w = width / f, h = height / f;
-        A3_HIP(ctx->reduce_plane.ensure(w * h * n_frames));
-        b.pixels = ctx->reduce_plane.as<uint8_t>(); b.fmt = A3_FMT_L8; b.W = (uint32_t)w; b.H = (uint32_t)h;
+    b.frames = PixelSrc{b.pixels, b.row_stride, b.frame_stride, fmt}; b.frames_W = width; b.frames_H = height;
+    b.plane = ctx->rect_on ? Batch::Plane::Rectified : ctx->reduction.factor ? Batch::Plane::Reduced : Batch::Plane::None;
+    if (b.plane != Batch::Plane::None) {   // from here on the (front half's) batch is an A3_FMT_L8 device batch of the plane's size whose frames are the plane
+        size_t w, h;
+        if (b.plane == Batch::Plane::Rectified) { b.rect_r = ctx->rect; w = b.rect_r.dst.image_width; h = b.rect_r.dst.image_height; }
+        else { b.reduce_f = ctx->reduction.factor; w = width / b.reduce_f; h = height / b.reduce_f; }
+        A3_HIP(ctx->plane.ensure(w * h * n_frames));
+        b.pixels = ctx->plane.as<uint8_t>(); b.fmt = A3_FMT_L8; b.W = (uint32_t)w; b.H = (uint32_t)h;
         b.row_stride = w; b.frame_stride = w * h;
     }
     if (b.board || b.charuco || b.recover) { if (int urc = upload_board(ctx)) return urc; }
@@ -1500,12 +1469,12 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
 static void finish_trivial(a3_ctx* ctx, uint32_t* per_frame_count) {
     const Batch& b = ctx->batch;
     if (per_frame_count && b.n) memset(per_frame_count, 0, (size_t)b.n * 4);
-    ctx->h_refined.clear(); ctx->refined_valid = b.refined;
-    ctx->h_board.assign(b.n, a3_board_pose{}); ctx->board_valid = b.board;
-    ctx->h_recovered.assign(b.n, 0u); ctx->recovered_valid = b.recover;
-    ctx->h_undist.clear(); ctx->h_undist_res.clear(); ctx->undist_valid = b.undist;
+    for (int k = 0; k < kSideKinds; k++) {   // a zero record per frame, no record per marker (the poses' flag is the enqueued batch's)
+        if (!kSides[k].kept) continue;
+        ctx->side_h[k].assign(b.has(k) && kSides[k].per_frame ? b.n * kSides[k].rec : 0, 0);
+        ctx->side_valid[k] = b.has(k);
+    }
     ctx->h_charuco.clear(); ctx->charuco_valid = b.charuco;
-    ctx->h_charuco_pose.assign(b.want_pose ? b.n : 0, a3_charuco_pose{}); ctx->charuco_pose_valid = b.charuco && b.want_pose;
 }
 
 static int run_batch_with_retries(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
@@ -1912,7 +1881,7 @@ size_t a3_detection_record_bytes(uint32_t max_markers_per_frame, int with_poses)
 int a3_pack_detections(a3_ctx* ctx, uint32_t first_frame_global, uint32_t max_markers_per_frame, int with_poses, void* dst_device, size_t dst_bytes) {
     if (!ctx || !dst_device) return A3_ERR_INVALID;
     if (!ctx->markers_valid) return fail(ctx, A3_ERR_INVALID, "a3_pack_detections: no finished batch on this context");
-    if (with_poses && !ctx->poses_valid) return fail(ctx, A3_ERR_INVALID, "a3_pack_detections: the last batch was not an a3_detect_batch_pose call");
+    if (with_poses && !ctx->side_valid[kSidePoses]) return fail(ctx, A3_ERR_INVALID, "a3_pack_detections: the last batch was not an a3_detect_batch_pose call");
     if (max_markers_per_frame == 0) return fail(ctx, A3_ERR_INVALID, "a3_pack_detections: max_markers_per_frame must be > 0");
     const size_t need = a3_detection_record_bytes(max_markers_per_frame, with_poses) * ctx->last_n;
     if (dst_bytes < need) return fail(ctx, A3_ERR_CAPACITY, "a3_pack_detections: dst_bytes smaller than frames x record size");
@@ -2236,7 +2205,7 @@ int a3_set_corner_refinement(a3_ctx* ctx, const a3_refine_config* cfg) {
 int a3_get_refined_corners(a3_ctx* ctx, float* dst_xy, size_t cap_markers, size_t* n) {
     if (!ctx || !n || (!dst_xy && cap_markers)) return A3_ERR_INVALID;
     *n = 0;
-    return get_last(ctx, ctx->refined_valid, ctx->h_refined, 8, dst_xy, cap_markers, n, "a3_get_refined_corners: the last collected batch ran without corner refinement",
+    return get_side(ctx, kSideRefined, dst_xy, cap_markers, n, "a3_get_refined_corners: the last collected batch ran without corner refinement",
                     "a3_get_refined_corners: cap_markers is smaller than the number of markers");
 }
 
@@ -2314,7 +2283,7 @@ int a3_set_board(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size
 int a3_get_board_poses(a3_ctx* ctx, a3_board_pose* dst, size_t cap_frames, size_t* n) {
     if (!ctx || !n || (!dst && cap_frames)) return A3_ERR_INVALID;
     *n = 0;
-    return get_last(ctx, ctx->board_valid, ctx->h_board, 1, dst, cap_frames, n, "a3_get_board_poses: the last collected batch was not a pose batch with a board set",
+    return get_side(ctx, kSideBoard, dst, cap_frames, n, "a3_get_board_poses: the last collected batch was not a pose batch with a board set",
                     "a3_get_board_poses: cap_frames is smaller than the number of frames");
 }
 
@@ -2402,7 +2371,7 @@ int a3_get_board_recovery(const a3_ctx* ctx, a3_recover_config* cfg) {
 int a3_get_recovered_counts(a3_ctx* ctx, uint32_t* per_frame_recovered, size_t n_frames) {
     if (!ctx || (!per_frame_recovered && n_frames)) return A3_ERR_INVALID;
     size_t n = 0;
-    return get_last(ctx, ctx->recovered_valid, ctx->h_recovered, 1, per_frame_recovered, n_frames, &n,
+    return get_side(ctx, kSideRecovered, per_frame_recovered, n_frames, &n,
                     "a3_get_recovered_counts: the last collected batch ran without board recovery",
                     "a3_get_recovered_counts: n_frames is smaller than the number of frames");
 }
@@ -2508,14 +2477,15 @@ int a3_set_charuco(a3_ctx* ctx, const float* corners_xy, const uint32_t* adjacen
 int a3_get_charuco_corners(a3_ctx* ctx, a3_charuco_corner* dst, size_t cap, size_t* n) {
     if (!ctx || !n || (!dst && cap)) return A3_ERR_INVALID;
     *n = 0;
-    return get_last(ctx, ctx->charuco_valid, ctx->h_charuco, 1, dst, cap, n, "a3_get_charuco_corners: the last collected batch ran without ChArUco",
+    return get_last(ctx, ctx->charuco_valid, ctx->h_charuco.data(), ctx->h_charuco.size() * sizeof(a3_charuco_corner), sizeof(a3_charuco_corner), dst, cap, n,
+                    "a3_get_charuco_corners: the last collected batch ran without ChArUco",
                     "a3_get_charuco_corners: cap is smaller than the number of corners");
 }
 
 int a3_get_charuco_poses(a3_ctx* ctx, a3_charuco_pose* dst, size_t cap_frames, size_t* n) {
     if (!ctx || !n || (!dst && cap_frames)) return A3_ERR_INVALID;
     *n = 0;
-    return get_last(ctx, ctx->charuco_pose_valid, ctx->h_charuco_pose, 1, dst, cap_frames, n,
+    return get_side(ctx, kSideCharucoPoses, dst, cap_frames, n,
                     "a3_get_charuco_poses: the last collected batch was not a pose batch with ChArUco set", "a3_get_charuco_poses: cap_frames is smaller than the number of frames");
 }
 
@@ -2605,9 +2575,9 @@ int a3_set_distortion(a3_ctx* ctx, const a3_distortion* d) {
 int a3_get_undistorted_corners(a3_ctx* ctx, float* dst_xy, float* residual_px, size_t cap_markers, size_t* n) {
     if (!ctx) return A3_ERR_INVALID;
     if (!n || (!dst_xy && cap_markers)) return fail(ctx, A3_ERR_INVALID, "a3_get_undistorted_corners: null argument");
-    const int rc = get_last(ctx, ctx->undist_valid, ctx->h_undist, 8, dst_xy, cap_markers, n, "a3_get_undistorted_corners: the last collected batch ran without lens distortion",
+    const int rc = get_side(ctx, kSideUndist, dst_xy, cap_markers, n, "a3_get_undistorted_corners: the last collected batch ran without lens distortion",
                             "a3_get_undistorted_corners: cap_markers is smaller than the number of markers");   // (*n: untouched by the first refusal)
-    if (rc == A3_OK && *n && residual_px) memcpy(residual_px, ctx->h_undist_res.data(), *n * 4 * sizeof(float));
+    if (rc == A3_OK && *n && residual_px) memcpy(residual_px, ctx->side_h[kSideUndistRes].data(), *n * kSides[kSideUndistRes].rec);
     return rc;
 }
 
@@ -2764,6 +2734,42 @@ void a3_default_rectify(a3_rectify* r, const a3_intrinsics* src, const a3_distor
     r->rotation[0] = r->rotation[4] = r->rotation[8] = 1.0f;
 }
 
+// a3_rectify_frames and a3_reduce_frames, both synchronous.  A host-side source: the caller's span (`bytes`, padding included) goes to
+// rect_in in one copy.
+static int stage_frames_in(a3_ctx* ctx, const void* src, int memory, size_t bytes, const uint8_t** d_src) {
+    *d_src = reinterpret_cast<const uint8_t*>(src);
+    if (memory != A3_MEM_HOST) return A3_OK;
+    A3_HIP(ctx->rect_in.ensure(bytes));
+    A3_HIP(hipMemcpyAsync(ctx->rect_in.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *d_src = ctx->rect_in.as<uint8_t>();
+    return A3_OK;
+}
+// Where the kernel writes n_frames frames of `rows` rows of row_bytes: the caller's device frames, or for a host-side destination packed
+// rows in rect_out, which finish copies back -- the rows' pixels only -- before it waits for the stream.
+struct FramesOut {
+    uint8_t* d_dst = nullptr; size_t d_row = 0, d_frame = 0;
+    void* host = nullptr; size_t row_stride = 0, frame_stride = 0, rows = 0; uint32_t n_frames = 0;
+    int begin(a3_ctx* ctx, void* dst, int memory, size_t row_stride_, size_t frame_stride_, size_t row_bytes, size_t rows_, uint32_t n) {
+        d_dst = reinterpret_cast<uint8_t*>(dst); d_row = row_stride = row_stride_; d_frame = frame_stride = frame_stride_; rows = rows_; n_frames = n;
+        if (memory != A3_MEM_HOST) return A3_OK;
+        host = dst; d_row = row_bytes; d_frame = d_row * rows;
+        A3_HIP(ctx->rect_out.ensure(d_frame * n_frames));
+        d_dst = ctx->rect_out.as<uint8_t>();
+        return A3_OK;
+    }
+    int finish(a3_ctx* ctx) const {
+        if (host && frame_stride == row_stride * rows) {
+            A3_HIP(hipMemcpy2DAsync(host, row_stride, d_dst, d_row, d_row, rows * n_frames, hipMemcpyDeviceToHost, ctx->stream));
+        } else if (host) {
+            for (uint32_t f = 0; f < n_frames; f++)
+                A3_HIP(hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(host) + f * frame_stride, row_stride, d_dst + f * d_frame, d_row, d_row, rows,
+                                        hipMemcpyDeviceToHost, ctx->stream));
+        }
+        A3_HIP(hipStreamSynchronize(ctx->stream));
+        return A3_OK;
+    }
+};
+
 int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, size_t src_row_stride, size_t src_frame_stride, uint32_t n_frames,
                       const a3_rectify* r, void* dst, int dst_memory, size_t dst_row_stride, size_t dst_frame_stride, a3_rectify_info* info) {
     if (!ctx) return A3_ERR_INVALID;
@@ -2781,37 +2787,17 @@ int a3_rectify_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, siz
     const uint32_t sw = r->src.image_width, sh = r->src.image_height, dw = r->dst.image_width, dh = r->dst.image_height;
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
-    const uint8_t* d_src = reinterpret_cast<const uint8_t*>(src);
-    if (src_memory == A3_MEM_HOST) {   // the caller's span, padding included, in one copy
-        const size_t bytes = src_frame_stride * (n_frames - 1) + src_row_stride * (sh - 1) + (size_t)sw * bpp;
-        A3_HIP(ctx->rect_in.ensure(bytes));
-        A3_HIP(hipMemcpyAsync(ctx->rect_in.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_src = ctx->rect_in.as<uint8_t>();
-    }
-    uint8_t* d_dst = reinterpret_cast<uint8_t*>(dst);
-    size_t d_row = dst_row_stride, d_frame = dst_frame_stride;
-    if (dst_memory == A3_MEM_HOST) {   // packed rows on the device; the copy back writes the rows' pixels only
-        d_row = (size_t)dw * obpp;
-        d_frame = d_row * dh;
-        A3_HIP(ctx->rect_out.ensure(d_frame * n_frames));
-        d_dst = ctx->rect_out.as<uint8_t>();
-    }
+    const uint8_t* d_src = nullptr;
+    if (int rc = stage_frames_in(ctx, src, src_memory, src_frame_stride * (n_frames - 1) + src_row_stride * (sh - 1) + (size_t)sw * bpp, &d_src)) return rc;
+    FramesOut o;
+    if (int rc = o.begin(ctx, dst, dst_memory, dst_row_stride, dst_frame_stride, (size_t)dw * obpp, dh, n_frames)) return rc;
     if (format_is_422(fmt))   // the grey form: the luma byte alone, one byte per pixel out
         A3_HIP(launch_rectify_grey(ctx->stream, {.src = d_src, .src_row = src_row_stride, .src_frame = src_frame_stride, .n_frames = n_frames, .fmt = fmt,
-                                                 .r = r, .grey = d_dst, .dst_row = d_row, .dst_frame = d_frame}));
+                                                 .r = r, .grey = o.d_dst, .dst_row = o.d_row, .dst_frame = o.d_frame}));
     else
         A3_HIP(launch_rectify(ctx->stream, {.src = d_src, .src_row = src_row_stride, .src_frame = src_frame_stride, .n_frames = n_frames, .bpp = (int)bpp, .r = r,
-                                            .dst = d_dst, .dst_row = d_row, .dst_frame = d_frame}));
-    if (dst_memory == A3_MEM_HOST) {
-        if (dst_frame_stride == dst_row_stride * dh) {
-            A3_HIP(hipMemcpy2DAsync(dst, dst_row_stride, d_dst, d_row, d_row, (size_t)dh * n_frames, hipMemcpyDeviceToHost, ctx->stream));
-        } else {
-            for (uint32_t f = 0; f < n_frames; f++)
-                A3_HIP(hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(dst) + f * dst_frame_stride, dst_row_stride, d_dst + f * d_frame, d_row, d_row, dh,
-                                        hipMemcpyDeviceToHost, ctx->stream));
-        }
-    }
-    A3_HIP(hipStreamSynchronize(ctx->stream));
+                                            .dst = o.d_dst, .dst_row = o.d_row, .dst_frame = o.d_frame}));
+    if (int rc = o.finish(ctx)) return rc;
     if (info) {
         *info = a3_rectify_info{};
         uint32_t tx, ty, tz;
@@ -2854,34 +2840,13 @@ int a3_reduce_frames(a3_ctx* ctx, const void* src, int src_memory, int fmt, uint
     const size_t bpp = reduce_bpp(fmt), w = width / factor, h = height / factor;
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
-    const uint8_t* d_src = reinterpret_cast<const uint8_t*>(src);
-    if (src_memory == A3_MEM_HOST) {   // the caller's span, padding included, in one copy
-        const size_t bytes = src_frame_stride * (n_frames - 1) + src_row_stride * (height - 1) + (size_t)width * bpp;
-        A3_HIP(ctx->rect_in.ensure(bytes));
-        A3_HIP(hipMemcpyAsync(ctx->rect_in.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_src = ctx->rect_in.as<uint8_t>();
-    }
-    uint8_t* d_dst = reinterpret_cast<uint8_t*>(dst);
-    size_t d_row = dst_row_stride, d_frame = dst_frame_stride;
-    if (dst_memory == A3_MEM_HOST) {   // packed rows on the device; the copy back writes the rows' pixels only
-        d_row = w;
-        d_frame = w * h;
-        A3_HIP(ctx->rect_out.ensure(d_frame * n_frames));
-        d_dst = ctx->rect_out.as<uint8_t>();
-    }
+    const uint8_t* d_src = nullptr;
+    if (int rc = stage_frames_in(ctx, src, src_memory, src_frame_stride * (n_frames - 1) + src_row_stride * (height - 1) + (size_t)width * bpp, &d_src)) return rc;
+    FramesOut o;
+    if (int rc = o.begin(ctx, dst, dst_memory, dst_row_stride, dst_frame_stride, w, h, n_frames)) return rc;
     A3_HIP(launch_reduce_frames(ctx->stream, {.src = d_src, .src_row = src_row_stride, .src_frame = src_frame_stride, .n_frames = n_frames, .fmt = fmt,
-                                              .W = width, .H = height, .factor = factor, .dst = d_dst, .dst_row = d_row, .dst_frame = d_frame}));
-    if (dst_memory == A3_MEM_HOST) {
-        if (dst_frame_stride == dst_row_stride * h) {
-            A3_HIP(hipMemcpy2DAsync(dst, dst_row_stride, d_dst, d_row, d_row, h * n_frames, hipMemcpyDeviceToHost, ctx->stream));
-        } else {
-            for (uint32_t f = 0; f < n_frames; f++)
-                A3_HIP(hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(dst) + f * dst_frame_stride, dst_row_stride, d_dst + f * d_frame, d_row, d_row, h,
-                                        hipMemcpyDeviceToHost, ctx->stream));
-        }
-    }
-    A3_HIP(hipStreamSynchronize(ctx->stream));
-    return A3_OK;
+                                              .W = width, .H = height, .factor = factor, .dst = o.d_dst, .dst_row = o.d_row, .dst_frame = o.d_frame}));
+    return o.finish(ctx);
 }
 
 int a3_set_reduction(a3_ctx* ctx, const a3_reduction* r) {
