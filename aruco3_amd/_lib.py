@@ -24,7 +24,7 @@ PROFILE_OFF, PROFILE_STAGES, PROFILE_THRESHOLD_ONLY, PROFILE_THRESHOLD_SAMPLED =
 STAGE_THRESHOLD, STAGE_CONTOUR, STAGE_DECODE = 0, 1, 2
 # a3_stats.stepping & 0xFF (include/aruco3_hip.h A3_STEP_*)
 STEP_WHOLE, STEP_DECODE_DEFERRED, STEP_HELD_RELEASED_BY_LAST, STEP_HELD_RELEASED_EARLY, STEP_BURST_LAST, STEP_HELD = 0, 1, 2, 3, 4, 5
-REFINE_NONE, REFINE_SUBPIX = 0, 1
+REFINE_NONE, REFINE_SUBPIX, REFINE_EDGES = 0, 1, 2
 BOARD_NONE, BOARD_OK = 0, 1
 BOARD_MAX_MARKERS = 1024
 DIST_NONE, DIST_RATIONAL = 0, 1
@@ -784,7 +784,8 @@ class Context:
 
     def refine_corners(self, pixels_ptr: int, memory: int, fmt: int, width: int, height: int, row_stride: int, corners: np.ndarray,
                        cell_px: np.ndarray = None) -> np.ndarray:
-        """a3_refine_corners (stand-alone, one frame): corners (..., 2) -> refined float32 (n, 2)"""
+        """a3_refine_corners (stand-alone, one frame): corners (..., 2) -> refined float32 (n, 2).  With the context's method REFINE_EDGES
+        the corners are quads (a multiple of 4, a3_marker order) and cell_px is read at each quad's first corner."""
         xy = _f32(corners, 2).copy()
         cp = None if cell_px is None else np.ascontiguousarray(np.asarray(cell_px, dtype=np.float32).reshape(-1))
         if cp is not None and cp.size != xy.shape[0]:

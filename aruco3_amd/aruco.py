@@ -41,9 +41,20 @@ class CornerRefinement:
     relative_win: float = 0.4
     max_iterations: int = 30
     min_shift: float = 0.01
+    method: str = "subpix"   # "subpix": a cornerSubPix window around each corner; "edges": lines fitted to the sides, intersected
+
+    @classmethod
+    def edges(cls, win_half: int = 10, relative_win: float = 0.4, max_iterations: int = 30, min_shift: float = 0.01) -> "CornerRefinement":
+        """Edge-fit refinement (A3_REFINE_EDGES): each corner is where the lines fitted to its two sides cross.  `win_half` is the range
+        each side's edge is searched in; the default 10 is what corners mapped up from a reduced plane (`Reduction`) want.  The fit
+        assumes straight sides: on frames of an uncorrected lens use "subpix", or a `Rectification`."""
+        return cls(win_half, relative_win, max_iterations, min_shift, "edges")
 
     def _c(self) -> _lib.RefineConfig:
-        return _lib.RefineConfig(_lib.REFINE_SUBPIX, self.win_half, self.relative_win, self.max_iterations, self.min_shift)
+        methods = {"subpix": _lib.REFINE_SUBPIX, "edges": _lib.REFINE_EDGES}
+        if self.method not in methods:
+            raise ValueError(f"CornerRefinement.method must be one of {sorted(methods)}, not {self.method!r}")
+        return _lib.RefineConfig(methods[self.method], self.win_half, self.relative_win, self.max_iterations, self.min_shift)
 
 
 @dataclass

@@ -517,9 +517,11 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     const uint32_t back_W = reduced ? b.frames_W : b.W, back_H = reduced ? b.frames_H : b.H;
     if (reduced) A3_HIP(launch_scale_markers(st, {.markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap, .factor = b.reduce_f}));
     float* const refined = b.refined ? ctx->refined_buf.as<float>() : nullptr;
-    if (b.refined)   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
-        A3_HIP(launch_refine_corners(st, {.src = back_src, .W = back_W, .H = back_H, .markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap,
-                                          .params = refine_params_for(ctx, b.refine), .out = refined}));
+    if (b.refined) {   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
+        const RefineLaunch rl{.src = back_src, .W = back_W, .H = back_H, .markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap,
+                              .params = refine_params_for(ctx, b.refine), .out = refined};
+        A3_HIP(b.refine.method == A3_REFINE_EDGES ? launch_refine_edges(st, rl) : launch_refine_corners(st, rl));
+    }
     if (b.undist)   // undistorted pixel corners of the same markers (of their refined corners with refinement on)
         A3_HIP(launch_undistort_corners(st, ctx->markers_ptr, refined, d_marker_total, b.marker_cap, b.pose_intr, b.dist, ctx->undist_buf.as<float>(),
                                         static_cast<float*>(ctx->side_dev[kSideUndistRes])));
@@ -1662,7 +1664,16 @@ int a3_debug_kernel_time(a3_ctx* ctx, int kernel, int dbg, int reps, float* avg_
             dec.per_frame = nullptr;
             dec.projection = dbg >= 0; dec.variant = dbg < 0 ? -dbg : dbg;
             A3_HIP(launch_decode(st, dec));
-        } else return fail(ctx, A3_ERR_INVALID, "kernel: 0 dart_count, 1 dart_assign, 2 local_contract, 3 decode, 4 decode on cold frames");
+        } else if (kernel == 6) {   // the refinement kernel of method dbg (A3_REFINE_SUBPIX / A3_REFINE_EDGES) over the last batch's marker list
+            const Batch& b = ctx->batch;
+            if (!b.refined || b.plane == Batch::Plane::Reduced || (dbg != A3_REFINE_SUBPIX && dbg != A3_REFINE_EDGES))
+                return fail(ctx, A3_ERR_INVALID, "kernel 6: needs a preceding unreduced batch with corner refinement, and dbg = the method to time");
+            a3_refine_config rc = b.refine;
+            rc.method = (uint32_t)dbg;
+            const RefineLaunch rl{.src = ctx->dbg_src, .W = (uint32_t)cc.W, .H = (uint32_t)cc.H, .markers = ctx->markers_ptr, .n_dev = &ctx->head->marker_total,
+                                  .n = b.marker_cap, .params = refine_params_for(ctx, rc), .out = ctx->refined_buf.as<float>()};
+            A3_HIP(dbg == A3_REFINE_EDGES ? launch_refine_edges(st, rl) : launch_refine_corners(st, rl));
+        } else return fail(ctx, A3_ERR_INVALID, "kernel: 0 dart_count, 1 dart_assign, 2 local_contract, 3 decode, 4 decode on cold frames, 6 corner refinement");
         A3_HIP(hipEventRecord(e1, st));
         A3_HIP(hipStreamSynchronize(ctx->stream));
         float ms = 0;
@@ -2183,7 +2194,7 @@ void a3_default_refine_config(a3_refine_config* cfg) {
 }
 
 static int check_refine_config(a3_ctx* ctx, const a3_refine_config& c) {
-    if (c.method != A3_REFINE_NONE && c.method != A3_REFINE_SUBPIX) return fail(ctx, A3_ERR_INVALID, "a3_refine_config.method: unknown method");
+    if (c.method != A3_REFINE_NONE && c.method != A3_REFINE_SUBPIX && c.method != A3_REFINE_EDGES) return fail(ctx, A3_ERR_INVALID, "a3_refine_config.method: unknown method");
     if (c.method == A3_REFINE_NONE) return A3_OK;
     if (c.win_half < 1 || c.win_half > 10) return fail(ctx, A3_ERR_INVALID, "a3_refine_config.win_half must be in 1..10");
     if (!(c.relative_win >= 0.0f) || !std::isfinite(c.relative_win)) return fail(ctx, A3_ERR_INVALID, "a3_refine_config.relative_win must be finite and >= 0");
@@ -2224,6 +2235,8 @@ int a3_refine_corners(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint
     }
     a3_refine_config cfg = ctx->refine;
     if (cfg.method == A3_REFINE_NONE) a3_default_refine_config(&cfg);
+    const bool edges = cfg.method == A3_REFINE_EDGES;   // quads: four consecutive corners each, cell_px read at the first
+    if (edges && n % 4 != 0) return fail(ctx, A3_ERR_INVALID, "a3_refine_corners: method A3_REFINE_EDGES takes quads, n must be a multiple of 4");
     size_t frame_stride = 0;
     const uint8_t* d_pixels = nullptr;
     const int rc = stage_input(ctx, pixels, memory, fmt, width, height, &row_stride, &frame_stride, 1, &d_pixels);
@@ -2233,9 +2246,9 @@ int a3_refine_corners(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint
     A3_HIP(in.ensure()); A3_HIP(out.ensure());
     A3_HIP(in.upload(s_pts, corners_xy, 2 * n));
     if (cell_px) A3_HIP(in.upload(s_cell, cell_px, n));
-    A3_HIP(launch_refine_corners(ctx->stream, {.src = {d_pixels, row_stride, frame_stride, fmt}, .W = width, .H = height, .pts = in.at(s_pts),
-                                               .cell_px = cell_px ? in.at(s_cell) : nullptr, .n = (uint32_t)n, .params = refine_params_for(ctx, cfg),
-                                               .out = out.at(s_out)}));
+    const RefineLaunch rl{.src = {d_pixels, row_stride, frame_stride, fmt}, .W = width, .H = height, .pts = in.at(s_pts),
+                          .cell_px = cell_px ? in.at(s_cell) : nullptr, .n = (uint32_t)n, .params = refine_params_for(ctx, cfg), .out = out.at(s_out)};
+    A3_HIP(edges ? launch_refine_edges(ctx->stream, rl) : launch_refine_corners(ctx->stream, rl));
     A3_HIP(out.download(s_out, corners_xy));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;

@@ -163,6 +163,12 @@ struct RefineLaunch {
 };
 hipError_t launch_refine_corners(hipStream_t st, const RefineLaunch& r);
 
+// ---- k_edge_refine.hip --------------------------------------------------------------------------------------------------------------
+// method A3_REFINE_EDGES of the same launch: markers != nullptr as above; else the n / 4 stand-alone quads of pts (n corners, a multiple
+// of 4), cell_px (nullable) read at each quad's first corner.  params: refine_params() (the weight tables are not read).  (One wave
+// per marker, four per workgroup, up to 1024 workgroups, then a workgroup-stride loop.)
+hipError_t launch_refine_edges(hipStream_t st, const RefineLaunch& r);
+
 // ---- k_undistort.hip ----------------------------------------------------------------------------------------------------------------
 // markers / pts: the corners' source (pts wins when both are given); n_dev: the device-side marker count of a batch (n = its marker
 // capacity), or nullptr for n stand-alone points.  out_xy: 2 floats per corner, out_res: 1.

@@ -300,8 +300,40 @@ int  a3_estimate_pose_normalized(a3_ctx *ctx, const float *points_xy, size_t n, 
  *     det = a*c2 - b*b: 0 or not finite -> stop at c; else s = 1/det, c' = c + (c2*s*bb1 - b*s*bb2, -b*s*bb1 + a*s*bb2);
  *     c' farther than w from q0 in x or y (or not finite) -> the corner is q0, stop; else c = c' and stop once
  *     |c' - c|^2 <= min_shift^2 or after max_iterations.
- * Out of scope: a3_pack_detections records keep their layout and carry the integer corners only. */
-enum { A3_REFINE_NONE = 0, A3_REFINE_SUBPIX = 1 };
+ * Out of scope: a3_pack_detections records keep their layout and carry the integer corners only.
+ *
+ * Method A3_REFINE_EDGES (opt-in; AprilTag 3's refine_edges, OpenCV's CORNER_REFINE_CONTOUR): a corner is where the lines fitted to
+ * the two sides that meet in it cross.  It uses every edge pixel of the middle of a side, so it does not stall on the pixel grid as
+ * the window method does, and it does not care how far off the start corner is as long as the sides lie within the search range --
+ * the method for corners mapped up from a reduced plane (a3_set_reduction), with win_half 10.  It writes the same 8 floats per
+ * marker as SUBPIX, and everything behind them reads them alike.  Fixed to the bit -- tests/edge_refine_oracle.c a3o_refine_quads
+ * restates it.  All arithmetic is f32 without fused multiply-add and uses only +, -, *, /, sqrtf and floorf:
+ *   - one marker is a quad q0..q3 of float corners in a3_marker order (clockwise in image coordinates, y down; the marker is dark
+ *     inside); grey levels, pixel centres and the bilinear sample P(x, y) are those of the SUBPIX contract above;
+ *   - search range r: the window rule above applied to win_half, relative_win and the cell_px of the START quad;
+ *   - one pass from the current corners c0..c3 (c = q before the first).  Side e runs from a = c_e to b = c_(e+1 mod 4):
+ *     d = b - a, L = sqrtf(d.x*d.x + d.y*d.y), outward normal N = (d.y / L, -(d.x / L)); L >= 4 fails -> the marker reverts;
+ *     stations k = 0..15 at p_k = a + s_k*d, s_k = 0.125 + 0.75 * ((k + 0.5) / 16): the middle three quarters of the side, so that a
+ *     bad corner does not bend the line;
+ *     samples S_i = P(p_k.x + (i*0.5)*N.x, p_k.y + (i*0.5)*N.y) for i = -2r-2 .. 2r+2 (4r + 5 of them); for j = -2r .. 2r in
+ *     ascending order: o_j = j*0.5, g_j = S_(j+2) - S_(j-2) (the difference of the samples one pixel outside and one pixel inside
+ *     o_j), w_j = g_j*g_j where g_j > 0, else 0 (the polarity filter: edges of the inner cells and of a neighbouring marker, which
+ *     get darker outward, weigh nothing), sw += w_j, swo += w_j*o_j;
+ *     the station is live iff max_j g_j >= A3_REFINE_EDGES_LIVE_LEVEL grey levels, and then m_k = swo / sw;
+ *     over the side's 16 stations, a dead one contributing zeros, each summed by an xor butterfly 8, 4, 2, 1 over the stations:
+ *     n = sum 1, Ss = sum s_k, Sss = sum s_k*s_k, Sm = sum m_k, Ssm = sum s_k*m_k; n >= 12 fails -> the marker reverts;
+ *     det = n*Sss - Ss*Ss: 0 or not finite -> the marker reverts; alpha = (Sm*Sss - Ss*Ssm) / det, beta = (n*Ssm - Ss*Sm) / det
+ *     (the unweighted least-squares line m = alpha + beta*s); the side's line is O_e + u*D_e, O_e = a + alpha*N, D_e = d + beta*N;
+ *     new corner e: with (O_p, D_p) the line of side e-1 (mod 4) and (O_c, D_c) that of side e, w = O_c - O_p,
+ *     dd = D_p.x*D_c.y - D_p.y*D_c.x, v = (w.x*D_p.y - w.y*D_p.x) / dd, c'_e = O_c + v*D_c; dd == 0 -> the marker reverts;
+ *   - revert rule: when any case above fires, or any c'_e is farther than 2r from its start q_e in x or y (or not finite), all four
+ *     corners of the marker are the start corners q0..q3 -- a quad is never half refined;
+ *   - c = c'; stop after a pass in which no corner moved more than min_shift in x or y, or after max_iterations passes (0: the start).
+ * The fit assumes straight sides.  Through an uncorrected lens a side is curved, and the line fitted to its middle three quarters
+ * meets its neighbour off the true corner by about the side's sagitta: use SUBPIX there, or rectify (a3_set_rectification) -- on
+ * rectified frames the sides are straight again.  Out of scope: inverted (bright-inside) markers, and reverting single corners. */
+enum { A3_REFINE_NONE = 0, A3_REFINE_SUBPIX = 1, A3_REFINE_EDGES = 2 };
+#define A3_REFINE_EDGES_LIVE_LEVEL 20   /* grey levels: the least outward gradient of a live station (method A3_REFINE_EDGES) */
 typedef struct a3_refine_config {
     uint32_t method;          /* A3_REFINE_NONE (default) */
     uint32_t win_half;        /* 5, 1 .. 10 */
@@ -311,14 +343,17 @@ typedef struct a3_refine_config {
 } a3_refine_config;
 /* method A3_REFINE_SUBPIX, win_half 5, relative_win 0.4, max_iterations 30, min_shift 0.01 */
 void a3_default_refine_config(a3_refine_config *cfg);
-/* applies to batches submitted after the call; NULL or method NONE turns it off */
+/* applies to batches submitted after the call; NULL or method NONE turns it off.  A3_REFINE_SUBPIX and A3_REFINE_EDGES take the same
+ * fields under the same range checks (win_half: the window's half-width, or the edge search range r); another method is A3_ERR_INVALID */
 int  a3_set_corner_refinement(a3_ctx *ctx, const a3_refine_config *cfg);
 /* refined corners of the last collected batch: 8 floats per marker, in the order of `out`, the corners in a3_marker order.
  * A3_ERR_INVALID when that batch ran without refinement, A3_ERR_CAPACITY when cap_markers is short (*n says how many there are). */
 int  a3_get_refined_corners(a3_ctx *ctx, float *dst_xy, size_t cap_markers, size_t *n);
 /* stand-alone: refine n caller-given corners (x, y float pairs, in place, each within 64 px of the frame) of one frame -- a tracker's
  * corners, or tests; cell_px (nullable) per corner for relative_win, NULL = always win_half.  The window and iteration settings are
- * the context's (a3_set_corner_refinement) when refinement is on, a3_default_refine_config's otherwise.  Synchronous; not while a
+ * the context's (a3_set_corner_refinement) when refinement is on, a3_default_refine_config's otherwise.  When the context's method is
+ * A3_REFINE_EDGES the corners are quads: n must be a multiple of 4 (else A3_ERR_INVALID), each consecutive four corners are one quad in
+ * a3_marker order, and cell_px, when given, is read at the quad's first corner (NULL: r = win_half).  Synchronous; not while a
  * submitted batch is in flight. */
 int  a3_refine_corners(a3_ctx *ctx, const void *pixels, int memory, int fmt, uint32_t width, uint32_t height, size_t row_stride,
                        float *corners_xy, const float *cell_px, size_t n);
@@ -1151,7 +1186,7 @@ int  a3_rectify_frames(a3_ctx *ctx, const void *src, int src_memory, int fmt, si
  *   - corners are pixels of the rectified view; pose calls take the view's plain intrinsics (r->dst).
  *   - independent of a3_set_distortion: with both set the corners of a pose batch are undistorted twice.
  *   - the grey plane detection works on is luma_of (into_luma8's integers) of the rectified pixel's ROUNDED OUTPUT BYTES, in the format's
- *     channel order (A3_FMT_L8: the byte itself; A3_FMT_YUYV8 / A3_FMT_UYVY8: the rectified luma byte) -- what every sampler (threshold, decode, refinement, ChArUco) makes of the rectified
+ *     channel order (A3_FMT_L8: the byte itself; A3_FMT_YUYV8 / A3_FMT_UYVY8: the rectified luma byte) -- what every sampler (threshold, decode, refinement by either method, ChArUco) makes of the rectified
  *     colour frame, which is why (1) + (2) above holds; a detector run on that plane as A3_FMT_L8 equals one run on the colour frames.
  *   - a3_download_grey and the other debug taps report the rectified view, sized r->dst.
  *   - the setter's argument errors (A3_ERR_INVALID) are those a3_rectify_frames makes for an a3_rectify: sizes, non-finite values, focal
@@ -1195,8 +1230,8 @@ int  a3_get_rectification(const a3_ctx *ctx, a3_rectify *r, int *enabled);
  *   3. every integer corner (x, y) of every marker mapped to X = f*x + f/2, Y = f*y + f/2 (integer division: the block's centre,
  *      rounded up).
  *   4. everything behind the marker list computed exactly as a batch without the setting computes it from a marker list with those
- *      integer corners on the caller's own full-size frames: the refined corners (the start q0 at the mapped corner, cell_px taken from
- *      the mapped quad), the ChArUco corners, the undistorted corners, and the marker, board and ChArUco poses.  A pose call without
+ *      integer corners on the caller's own full-size frames: the refined corners (A3_REFINE_SUBPIX: the start q0 at the mapped corner;
+ *      A3_REFINE_EDGES: the start quad q0..q3 the mapped quad; cell_px taken from the mapped quad), the ChArUco corners, the undistorted corners, and the marker, board and ChArUco poses.  A pose call without
  *      intrinsics normalises by the full W x H; intrinsics and lens coefficients are the full-size camera's.
  * Consequences:
  *   - the minimum edge length, the minimum corner separation and the corner range derive from the reduced size w x h.
@@ -1212,7 +1247,8 @@ int  a3_get_rectification(const a3_ctx *ctx, a3_rectify *r, int *enabled);
  *   - the refinement's rule "a corner that moves farther than the window from q0 is q0" now applies to a start that is up to about
  *     f + 1 px off the true corner where the reduced quad is good to a pixel (f times whatever the reduced detector's own corner error
  *     is, where it is not): the refinement window (win_half, and what relative_win makes of it) has to cover that, or the refined
- *     corner falls back to the mapped integer corner.
+ *     corner falls back to the mapped integer corner.  A3_REFINE_EDGES searches each side's edge within r of the mapped side and
+ *     reverts a whole marker when a fitted corner lands more than 2r from its start: use win_half 10 with it on reduced frames.
  * Errors of the setter (A3_ERR_INVALID): a factor outside 2..4, non-zero reserved, a rectification set, a batch in flight.
  * a3_get_reduction: the setting in force (*enabled 0: none, *r zeroed).  a3_reduce_frames, a3_rectify_frames, a3_refine_corners,
  * a3_interpolate_charuco and the solvers never look at the setting.

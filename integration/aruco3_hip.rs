@@ -74,6 +74,7 @@ pub const A3_PROFILE_THRESHOLD_ONLY: c_int = 2;
 pub const A3_PROFILE_THRESHOLD_SAMPLED: c_int = 3;
 pub const A3_REFINE_NONE: u32 = 0;
 pub const A3_REFINE_SUBPIX: u32 = 1;
+pub const A3_REFINE_EDGES: u32 = 2;
 pub const A3_BOARD_NONE: u32 = 0;
 pub const A3_BOARD_OK: u32 = 1;
 pub const A3_DIST_NONE: u32 = 0;
@@ -1018,15 +1019,26 @@ pub struct RefineConfig {
     pub relative_win: f32,   // 0 = always win_half
     pub max_iterations: u32, // at most 100
     pub min_shift: f32,      // px
+    pub method: u32,         // A3_REFINE_SUBPIX (default) or A3_REFINE_EDGES
 }
 impl Default for RefineConfig {
     fn default() -> Self {
-        RefineConfig { win_half: 5, relative_win: 0.4, max_iterations: 30, min_shift: 0.01 }
+        RefineConfig { win_half: 5, relative_win: 0.4, max_iterations: 30, min_shift: 0.01, method: A3_REFINE_SUBPIX }
     }
 }
 impl RefineConfig {
+    /// Edge-fit refinement (A3_REFINE_EDGES): corners from lines fitted to the sides.  `win_half` 10 is the search range that corners
+    /// mapped up from a reduced plane want; the fit assumes straight sides (no uncorrected lens).
+    pub fn edges() -> Self {
+        RefineConfig { win_half: 10, method: A3_REFINE_EDGES, ..Default::default() }
+    }
+    /// the same settings with another method (A3_REFINE_SUBPIX or A3_REFINE_EDGES)
+    pub fn method(mut self, method: u32) -> Self {
+        self.method = method;
+        self
+    }
     fn to_a3(&self) -> A3RefineConfig {
-        A3RefineConfig { method: A3_REFINE_SUBPIX, win_half: self.win_half, relative_win: self.relative_win,
+        A3RefineConfig { method: self.method, win_half: self.win_half, relative_win: self.relative_win,
                          max_iterations: self.max_iterations, min_shift: self.min_shift }
     }
 }

@@ -1,0 +1,60 @@
+"""ctypes binding of tests/edge_refine_oracle.c: the CPU restatement of edge-fit corner refinement (a3_refine_config.method
+A3_REFINE_EDGES) that the device kernel is held to bit for bit.  TEST INFRASTRUCTURE ONLY -- the tests and tools/edge_refine_bench.py
+load it; aruco3_amd never does.  Compiled on first use through tests/oracle_build.build."""
+import ctypes as C
+
+import numpy as np
+
+from tests.oracle_build import build
+from tests.refine_oracle import RefineConfig, quad_cell_px
+
+EDGES = 2
+_lib = None
+
+
+def config(win_half=10, relative_win=0.4, max_iterations=30, min_shift=0.01) -> RefineConfig:
+    return RefineConfig(EDGES, win_half, relative_win, max_iterations, min_shift)
+
+
+def default() -> RefineConfig:
+    """a3_default_refine_config's fields with method EDGES"""
+    return config(win_half=5)
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        L = build("edge_refine_oracle")
+        L.a3o_refine_quads.restype = C.c_int
+        L.a3o_refine_quads.argtypes = [C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.POINTER(RefineConfig), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float), C.c_size_t]
+        _lib = L
+    return _lib
+
+
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+def refine_quads(grey: np.ndarray, quads, cfg: RefineConfig = None, cell_px=None) -> np.ndarray:
+    """one grey frame: quads (n, 4, 2) float (a3_marker order) -> refined float32 (n, 4, 2); cell_px: one value per quad or None"""
+    g = np.ascontiguousarray(grey, dtype=np.uint8)
+    h, w = g.shape
+    xy = np.ascontiguousarray(np.asarray(quads, dtype=np.float32).reshape(-1, 4, 2)).copy()
+    cp = None if cell_px is None else np.ascontiguousarray(np.asarray(cell_px, dtype=np.float32).reshape(-1))
+    assert cp is None or cp.size == xy.shape[0]
+    cfg = cfg or default()
+    rc = lib().a3o_refine_quads(_p(g, C.c_uint8), w, h, C.byref(cfg), _p(xy, C.c_float), None if cp is None else _p(cp, C.c_float), xy.shape[0])
+    if rc != 0:
+        raise ValueError("a3o_refine_quads: bad refinement config")
+    return xy
+
+
+def refine_markers(grey: np.ndarray, markers, cells: int, cfg: RefineConfig = None) -> np.ndarray:
+    """the refinement a detection batch applies with method EDGES: every marker's integer corners (a3_marker order), its search range
+    from the quad's cell size -> float32 (n_markers, 4, 2)"""
+    if len(markers) == 0:
+        return np.zeros((0, 4, 2), dtype=np.float32)
+    quads = np.array([np.asarray(q, dtype=np.uint32).reshape(8) for q in markers], dtype=np.uint32)
+    cell = np.array([quad_cell_px(q, cells) for q in quads], dtype=np.float32)
+    return refine_quads(grey, quads.reshape(-1, 4, 2).astype(np.float32), cfg, cell)
