@@ -33,6 +33,9 @@ def lib():
         L.a3o_refine_weights.argtypes = [C.c_uint32, f32p]
         L.a3o_refine_corners.restype = C.c_int
         L.a3o_refine_corners.argtypes = [u8p, C.c_uint32, C.c_uint32, C.POINTER(RefineConfig), f32p, f32p, C.c_size_t]
+        L.a3o_refine_corners_trace.restype = C.c_int
+        L.a3o_refine_corners_trace.argtypes = [u8p, C.c_uint32, C.c_uint32, C.POINTER(RefineConfig), f32p, f32p, C.c_size_t, C.c_int,
+                                               C.POINTER(C.c_int32), u32p, C.POINTER(C.c_int32), f32p]
         _lib = L
     return _lib
 
@@ -66,6 +69,28 @@ def refine_corners(grey: np.ndarray, corners, config: RefineConfig = None, cell_
     if rc != 0:
         raise ValueError("a3o_refine_corners: bad refinement config")
     return xy
+
+
+EXITS = ("det0", "nonfinite", "revert", "converged", "cap")   # a3o_refine_corners_trace's `how` (A3O_EXIT_*)
+VARIANTS = range(1, 10)   # the deliberately wrong restatements (tests/refine_oracle.c lists them); 0 is the contract
+
+
+def refine_corners_trace(grey: np.ndarray, corners, config: RefineConfig = None, cell_px=None, variant: int = 0) -> dict:
+    """refine_corners with a record per corner: {"xy" float32 (n, 2), "w" int32, "iters" uint32, "exit" int32 (an index into EXITS),
+    "excursion" float32 (the largest max(|cx - q0x|, |cy - q0y|) over the estimates kept)}.  variant 0 is the contract."""
+    g = np.ascontiguousarray(grey, dtype=np.uint8)
+    h, w = g.shape
+    xy = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 2)).copy()
+    n = xy.shape[0]
+    cp = None if cell_px is None else np.ascontiguousarray(np.asarray(cell_px, dtype=np.float32).reshape(-1))
+    assert cp is None or cp.size == n
+    cfg = config or RefineConfig.default()
+    win, iters, how, far = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+    rc = lib().a3o_refine_corners_trace(_p(g, C.c_uint8), w, h, C.byref(cfg), _p(xy, C.c_float), None if cp is None else _p(cp, C.c_float), n,
+                                        variant, _p(win, C.c_int32), _p(iters, C.c_uint32), _p(how, C.c_int32), _p(far, C.c_float))
+    if rc != 0:
+        raise ValueError("a3o_refine_corners_trace: bad refinement config or variant")
+    return {"xy": xy, "w": win, "iters": iters, "exit": how, "excursion": far}
 
 
 def refine_markers(grey: np.ndarray, markers, cells: int, config: RefineConfig = None) -> np.ndarray:

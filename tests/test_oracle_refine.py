@@ -14,6 +14,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from tests import refine_cases as rcs
 from tests import refine_oracle as refo
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -95,31 +96,29 @@ def test_flat_window_keeps_the_start():
     assert np.array_equal(refo.refine_corners(grey, start), start)
 
 
-def _square(h, w, x0, y0, x1, y1, lo=30, hi=220):
-    img = np.full((h, w), hi, np.uint8)
-    img[y0:y1, x0:x1] = lo
-    return img
-
-
 @pytest.mark.parametrize("d", [0, 1, 2])
 def test_corner_near_the_frame_border(d):
-    """border replicate: a corner 0-2 px from the frame edge refines without reading outside and stays in the window"""
-    img = _square(60, 80, d, d, 40, 40)
+    """border replicate: a corner 0-2 px from the frame edge refines without reading outside and stays in the window (the frame of
+    tests/refine_cases.py that the kernel runs as well: a dark rectangle of 20 x 14 from pixel (d, d))"""
+    img, _ = rcs.border_frames(d)["corners"]
+    assert img[d, d] == 30 and img[d + 13, d + 19] == 30 and img[d + 14, d + 19] == 220 and img[d + 13, d + 20] == 220
     cfg = refo.RefineConfig(1, 5, 0.0, 30, 0.01)
-    r = refo.refine_corners(img, [[float(d), float(d)], [39.0, 39.0]], cfg)
+    start = np.array([[d, d], [d + 19, d + 13]], np.float32)
+    r = refo.refine_corners(img, start, cfg)
     assert np.all(np.isfinite(r))
-    assert np.all(np.abs(r - np.array([[d, d], [39, 39]], np.float32)) <= 5.0)
-    assert np.linalg.norm(r[1] - np.array([39.5, 39.5])) < 0.3   # the free corner finds the edge crossing (between pixels 39 and 40)
+    assert np.all(np.abs(r - start) <= 5.0)
+    assert np.linalg.norm(r[1] - np.array([d + 19.5, d + 13.5])) < 0.3   # the free corner finds the edge crossing (between two pixels)
 
 
 def test_start_that_drifts_past_the_window_reverts():
-    """the corner of a dark square sits at (19.5, 19.5); started at (17, 17) with w = 2, the window's last column and row
-    (pixels 19) already see both edges (det != 0), the first step lands about 2.5 px away -- past w -- and the corner reverts to q0"""
-    img = np.full((60, 60), 220, np.uint8)
-    img[20:45, 20:45] = 30
-    start = np.array([[17.0, 17.0]], np.float32)
+    """the corner of a dark square sits at (29.5, 29.5) (tests/refine_cases.py, box_frame); started at (27, 27) with w = 2, the window's
+    last column and row (pixels 29) already see both edges (det != 0), the first step lands about 2.5 px away -- past w -- and the
+    corner reverts to q0"""
+    img = rcs.box_frame()
+    assert rcs.BOX[:2] == (29.5, 29.5)
+    start = np.array([[27.0, 27.0]], np.float32)
     free = refo.refine_corners(img, start, refo.RefineConfig(1, 5, 0.0, 30, 0.0))
-    assert np.linalg.norm(free[0] - np.array([19.5, 19.5])) < 0.1, free   # with room it finds the corner, 2.5 px away
+    assert np.linalg.norm(free[0] - np.array([29.5, 29.5])) < 0.1, free   # with room it finds the corner, 2.5 px away
     for it in (1, 30):
         assert np.array_equal(refo.refine_corners(img, start, refo.RefineConfig(1, 2, 0.0, it, 0.0)), start)
     moved = refo.refine_corners(img, start, refo.RefineConfig(1, 3, 0.0, 1, 0.0))   # w = 3 allows the same first step
