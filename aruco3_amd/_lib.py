@@ -58,6 +58,7 @@ MAP_MARKER_USED, MAP_MARKER_UNSEEN, MAP_MARKER_UNREACHED = 1, 2, 3
 MAP_FRAME_USED, MAP_FRAME_UNUSED = 1, 2
 MAP_OBS_USED, MAP_OBS_DEGENERATE, MAP_OBS_UNREACHED = 1, 2, 3
 MAP_MAX_MARKERS, MAP_MAX_FRAMES, MAP_MAX_MAPS, MAP_MAX_CALL_FRAMES, MAP_MAX_CALL_OBSERVATIONS, MAP_START_OBSERVATIONS = 128, 4096, 1024, 65536, 262144, 8
+MAX_THRESHOLD_WINDOWS = 4   # A3_MAX_THRESHOLD_WINDOWS
 STEP_NAMES = {0: "whole", 1: "decode_deferred", 2: "held_released_by_last", 3: "held_released_early", 4: "burst_last", 5: "held"}
 
 # every symbol include/aruco3_hip.h declares
@@ -76,12 +77,13 @@ SYMBOLS = [
     "a3_calibrate_cameras", "a3_calibrate_fisheye_cameras", "a3_calibrate_rigs", "a3_calibrate_hand_eyes", "a3_build_marker_maps",
     "a3_default_rectify", "a3_rectify_frames", "a3_set_rectification", "a3_get_rectification",
     "a3_reduce_frames", "a3_set_reduction", "a3_get_reduction",
+    "a3_set_threshold_windows", "a3_get_threshold_windows",
 ]
 CAND_DTYPE = np.dtype([("start_key", "<u4"), ("xy", "<u2", (8,))])      # a3_debug_cand (a3_internal.h)
 PROJ_DTYPE = np.dtype([("inv", "<f4", (9,)), ("ok", "<i4")])            # A3_DEBUG_PROJ_BYTES
 CONTOUR_DTYPE = np.dtype([("frame", "<u4"), ("start_key", "<u4"), ("point_base", "<u4"), ("n", "<u4")])   # a3_debug_contour
 # aruco3_amd/csrc/a3_internal.h: probes and single-stage hooks for this repository's tests and tools, not for bindings
-INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates", "a3_debug_sample_frames", "a3_debug_frame_candidates", "a3_debug_contour_quads"]
+INTERNAL_SYMBOLS = ["a3_debug_set_overlap", "a3_debug_build_flags", "a3_debug_spin", "a3_debug_set_hold", "a3_debug_set_jump_rounds", "a3_debug_launch_threshold", "a3_debug_kernel_time", "a3_selftest_ieee", "a3_debug_clockwise", "a3_debug_rotate_bits", "a3_debug_discard_too_near", "a3_debug_inject_candidates", "a3_debug_sample_frames", "a3_debug_frame_candidates", "a3_debug_contour_quads", "a3_debug_merge_candidates"]
 
 
 class A3Error(RuntimeError):
@@ -523,6 +525,11 @@ def load():
         L.a3_set_reduction.argtypes = [vp, C.POINTER(ReductionRec)]
         L.a3_get_reduction.restype = C.c_int
         L.a3_get_reduction.argtypes = [vp, C.POINTER(ReductionRec), C.POINTER(C.c_int)]
+    if hasattr(L, "a3_set_threshold_windows"):   # (likewise several threshold windows)
+        L.a3_set_threshold_windows.restype = C.c_int
+        L.a3_set_threshold_windows.argtypes = [vp, C.POINTER(C.c_uint32), C.c_size_t]
+        L.a3_get_threshold_windows.restype = C.c_int
+        L.a3_get_threshold_windows.argtypes = [vp, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
     if hasattr(L, "a3_set_rectification"):   # (likewise rectification inside the detect calls)
         L.a3_set_rectification.restype = C.c_int
         L.a3_set_rectification.argtypes = [vp, C.POINTER(RectifyRec)]
@@ -530,6 +537,10 @@ def load():
         L.a3_get_rectification.argtypes = [vp, C.POINTER(RectifyRec), C.POINTER(C.c_int)]
     L.a3_debug_discard_too_near.restype = C.c_int
     L.a3_debug_discard_too_near.argtypes = [vp, u32p, C.c_size_t, C.c_float, u32p, C.POINTER(C.c_size_t)]
+    if hasattr(L, "a3_debug_merge_candidates"):      # (likewise)
+        L.a3_debug_merge_candidates.restype = C.c_int
+        L.a3_debug_merge_candidates.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, u32p, vp, C.c_float, C.c_uint32, C.POINTER(C.c_uint16),
+                                                C.POINTER(C.c_uint16), u32p, u32p, u32p, vp, u32p, u32p]
     if hasattr(L, "a3_debug_frame_candidates"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack it)
         L.a3_debug_frame_candidates.restype = C.c_int
         L.a3_debug_frame_candidates.argtypes = [vp, C.c_uint32, C.c_uint32, u32p, vp, C.c_float, C.c_uint32, C.POINTER(C.c_uint16),
@@ -991,6 +1002,23 @@ class Context:
         check(load().a3_reduce_frames(self.handle, C.c_void_p(src_ptr), src_memory, fmt, width, height, src_row_stride, src_frame_stride, n_frames,
                                       factor, C.c_void_p(dst_ptr), dst_memory, dst_row_stride, dst_frame_stride), self.handle)
 
+    # ---- several threshold windows ----
+    def set_threshold_windows(self, radii=None):
+        """a3_set_threshold_windows: every later detect call of this context thresholds at each radius and merges the candidates on the
+        device (one radius: the single-window path with that radius); None or an empty sequence turns it off.  Refused while a
+        submitted batch is in flight."""
+        r = [int(v) for v in radii] if radii is not None else []
+        if any(v < 0 or v > 0xFFFFFFFF for v in r):
+            raise ValueError("a threshold window radius is a uint32")
+        arr = (C.c_uint32 * max(len(r), 1))(*r)
+        check(load().a3_set_threshold_windows(self.handle, arr if r else None, len(r)), self.handle)
+
+    def get_threshold_windows(self):
+        """a3_get_threshold_windows -> the radii in force as a tuple (empty: off)"""
+        arr, n = (C.c_uint32 * MAX_THRESHOLD_WINDOWS)(), C.c_size_t(0)
+        check(load().a3_get_threshold_windows(self.handle, arr, MAX_THRESHOLD_WINDOWS, C.byref(n)), self.handle)
+        return tuple(int(arr[i]) for i in range(n.value))
+
     # ---- camera calibration ----
     def _calibrate(self, symbol, cams, view_offsets, object_xy, image_xy, with_views):
         off = np.ascontiguousarray(np.asarray(view_offsets, dtype=np.uint32).reshape(-1))
@@ -1150,6 +1178,30 @@ class Context:
                                                _p(pre, C.c_uint16), _p(fin, C.c_uint16), _p(fin_count, C.c_uint32), _p(work, C.c_uint32),
                                                _p(work_count, C.c_uint32), proj.ctypes.data if S else None), self.handle)
         return {"pre_xy": pre, "fin_xy": fin, "fin_count": fin_count, "work": work, "work_count": int(work_count[0]), "proj": proj if S else None}
+
+    def debug_merge_candidates(self, n_frames: int, n_windows: int, plane_cand: int, cand_count, records, min_distance: float, S: int = 0) -> dict:
+        """a3_debug_merge_candidates: one launch of k_merge_candidates, as the pipeline makes it, on hand-made per-plane tables.
+        cand_count: n_windows * n_frames counts at plane index k * n_frames + f; records: CAND_DTYPE, plane after plane in that order.
+        Returns whole tables of M = min(n_windows * plane_cand, 65536) slots per frame -- 0xFF bytes where the kernel did not write."""
+        cnt = np.ascontiguousarray(cand_count, dtype=np.uint32).reshape(-1)
+        rec = np.ascontiguousarray(records, dtype=CAND_DTYPE).reshape(-1)
+        assert cnt.size == n_frames * n_windows
+        m = min(n_windows * plane_cand, 65536)
+        slots = n_frames * m
+        pre = np.empty((n_frames, m, 4, 2), dtype=np.uint16)
+        fin = np.empty((n_frames, m, 4, 2), dtype=np.uint16)
+        fin_count = np.empty(n_frames, dtype=np.uint32)
+        merged = np.empty(n_frames, dtype=np.uint32)
+        work = np.empty(slots, dtype=np.uint32)
+        work_count = np.zeros(1, dtype=np.uint32)
+        err = np.zeros(1, dtype=np.uint32)
+        proj = np.empty(slots if S else 0, dtype=PROJ_DTYPE)
+        check(load().a3_debug_merge_candidates(self.handle, n_frames, n_windows, plane_cand, _p(cnt, C.c_uint32), rec.ctypes.data if rec.size else None,
+                                               min_distance, S, _p(pre, C.c_uint16), _p(fin, C.c_uint16), _p(fin_count, C.c_uint32),
+                                               _p(work, C.c_uint32), _p(work_count, C.c_uint32), proj.ctypes.data if S else None,
+                                               _p(merged, C.c_uint32), _p(err, C.c_uint32)), self.handle)
+        return {"pre_xy": pre, "fin_xy": fin, "fin_count": fin_count, "merged_count": merged, "work": work, "work_count": int(work_count[0]),
+                "err_flags": int(err[0]), "proj": proj if S else None, "merged_cap": m}
 
     def debug_contour_quads(self, width: int, height: int, records: np.ndarray, points: np.ndarray, *, eps_factor: float = 0.05,
                             min_edge_length: int = 0, n_darts: int = 0, first_frame: int = 0, n_frames: int = 1, max_cand: int = 1024,

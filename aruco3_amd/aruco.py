@@ -111,6 +111,19 @@ def _apply_reduction(ctx: _lib.Context, reduction: Optional[Reduction]) -> None:
         ctx._reduction_key = key
 
 
+def _windows_key(threshold_windows) -> tuple:
+    """`threshold_windows` as the tuple of radii a3_set_threshold_windows takes (None or empty: off)"""
+    return () if threshold_windows is None else tuple(int(v) for v in threshold_windows)
+
+
+def _apply_threshold_windows(ctx: _lib.Context, threshold_windows) -> None:
+    """hands a threshold-window set to a context that has no batch in flight (the setter is refused otherwise): only on a change"""
+    key = _windows_key(threshold_windows)
+    if getattr(ctx, "_windows_key", ()) != key:
+        ctx.set_threshold_windows(key)
+        ctx._windows_key = key
+
+
 def _one_view(reduction, rectification) -> None:
     if reduction is not None and rectification is not None:
         raise ValueError("a detector takes a reduction or a rectification, not both (a3_set_reduction refuses the pair)")
@@ -220,7 +233,8 @@ class Detector:
 
     def __init__(self, config: DetectorConfig = None, dictionary: ARDictionary = None, device: int = 0,
                  refinement: Optional[CornerRefinement] = None, board=None, charuco_config: Optional[_lib.CharucoConfig] = None,
-                 rectification: Optional[Rectification] = None, recovery=None, reduction: Optional[Reduction] = None):
+                 rectification: Optional[Rectification] = None, recovery=None, reduction: Optional[Reduction] = None,
+                 threshold_windows=None):
         _one_view(reduction, rectification)
         if recovery is not None and board is None:
             raise ValueError("Detector(recovery=...) needs a board: recovery places rejected quads where the board says its markers are")
@@ -237,6 +251,9 @@ class Detector:
         self.recovery = recovery
         # the front half of every call runs on the frames reduced by this factor; corners, refinement and poses are full-size
         self.reduction = reduction
+        # several adaptive-threshold windows (a3_set_threshold_windows; not in the reference): e.g. (3, 7, 15) -- every frame is
+        # binarised at each radius and the candidates are merged on the device; one radius overrides config.threshold_window; None: off
+        self.threshold_windows = threshold_windows
         self._ctx = None
         self._ctx_key = None
 
@@ -289,6 +306,7 @@ class Detector:
             _apply_reduction(self._ctx, None)
         _apply_rectification(self._ctx, self.rectification)
         _apply_reduction(self._ctx, self.reduction)
+        _apply_threshold_windows(self._ctx, self.threshold_windows)
         return self._ctx
 
     # src/aruco.rs:52-121
@@ -554,6 +572,7 @@ class BatchQueue:
         self._rectification = detector.rectification   # (likewise)
         self._recovery = detector.recovery   # (likewise)
         self._reduction = detector.reduction   # (likewise)
+        self._threshold_windows = detector.threshold_windows   # (likewise)
         self._refine_on = [False] * depth
         self._keep = [None] * depth
         self._gates = gates
@@ -580,6 +599,7 @@ class BatchQueue:
         ctx.set_debug_taps(False)
         _apply_rectification(ctx, self._rectification)   # (this context's last batch has been collected: the queue is not full)
         _apply_reduction(ctx, self._reduction)
+        _apply_threshold_windows(ctx, self._threshold_windows)
         ctx.set_corner_refinement(self._refinement._c() if self._refinement is not None else None)
         self._refine_on[k] = self._refinement is not None
         if self._submitted < depth and self._board is not None:   # (each context's first batch: the board stays set on it)

@@ -20,6 +20,7 @@
 #include "a3_rectify_check.h"
 #include "a3_reduce_check.h"
 #include "a3_solve_check.h"
+#include "a3_windows_check.h"
 
 using namespace a3;
 
@@ -112,6 +113,10 @@ struct Batch {
     uint32_t frames_W = 0, frames_H = 0;
     a3_rectify rect_r{};
     uint32_t reduce_f = 0;
+    // a3_set_threshold_windows: the radius of the single-window path (the context's threshold_window, or the one radius set), or with
+    // K >= 2 the windows of a batch whose front half and contour stage run on planes = n * K planes (plane (k, f) at k * n + f,
+    // plane_cand candidate slots each) and whose candidates k_merge_candidates merges into n frames' lists of max_cand slots
+    uint32_t K = 1, win[A3_MAX_THRESHOLD_WINDOWS] = {}, radius = 0, planes = 0, plane_cand = 0;
     bool taps = false;           // debug taps: grey plane, patches, contours and the per-frame candidate counts are kept
     bool sample_frames = false;  // a3_debug_sample_frames: a tapped batch still samples the caller's frames wherever an untapped one would
     int profiling = 0, profile_every = 1;   // a3_set_profiling in force
@@ -193,14 +198,20 @@ struct a3_ctx {
     uint64_t prof_n[A3_STAGE_COUNT] = {0, 0, 0};
     a3_stats stats{};
 
-    // last batch geometry (for the debug downloads)
-    uint32_t W = 0, H = 0, frames = 0;
+    // last batch geometry (for the debug downloads): frames = the planes of the front half and the contour stage (the batch's frames
+    // times its threshold windows), frames_merged = the batch's frames, cand_stride = slots per frame of the tables behind the candidates,
+    // pre_count = the per-frame lengths of the lists before the discard on the device
+    uint32_t W = 0, H = 0, frames = 0, frames_merged = 0, cand_stride = 0;
+    const uint32_t* pre_count = nullptr;
+    // a3_set_threshold_windows: the setting later batches capture (0 windows: off)
+    uint32_t n_windows = 0, windows[A3_MAX_THRESHOLD_WINDOWS] = {};
 
     DevBuf dict, in, grey, bin, frame_darts, frame_darts_dev, frame_base, pix_base, tile_darts;
     DevBuf d_xy, d_succ, fin, t_cur, t_next;
     DevBuf leader_list, leader_keep, entry_list, es_a, es_b;
     DevBuf contours, cyc_start_off, points;
     DevBuf cands, pre_xy, fin_xy, fin_count, work, outs, proj, patches, cand_big;
+    DevBuf merged_count;   // several threshold windows: the per-frame lengths of the concatenated candidate lists (k_merge_candidates)
     // one allocation zeroed by one memset per batch, its head read back with one copy (zero_layout, a3_batch_head.h)
     DevBuf zero_blk;
     a3_marker* markers_ptr = nullptr;                // the compacted marker list, right behind the read-back head in the zero block
@@ -475,6 +486,7 @@ DecodeStage decode_stage(const a3_ctx* ctx) {
 int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     const float min_corner_separation = (float)std::min(b.W, b.H) * ctx->cfg.min_corner_separation_factor;   // src/aruco.rs:56
     unsigned int* d_marker_total = &ctx->head->marker_total;
+    ctx->pre_count = b.K > 1 ? ctx->merged_count.as<uint32_t>() : ctx->cand_count;
     if (ctx->inject_armed) {   // (test hook; never set by a caller of the public header)
         ctx->inject_armed = false;
         const uint32_t cnt = (uint32_t)ctx->inject.size();
@@ -497,7 +509,11 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
         A3_HIP(hipMemsetAsync(side_total, 0, 16 + (size_t)b.n * 4, st));
         dec.markers = ctx->recover_det.as<a3_marker>(); dec.per_frame = side_per_frame; dec.marker_total = side_total;
     }
-    A3_HIP(launch_frame_candidates(st, dec));
+    if (b.K > 1) {   // the K planes' tables merged into the frames' lists; from here on cand_count is the merged lists'
+        dec.windows = b.K; dec.plane_cand = b.plane_cand; dec.merged_count = ctx->merged_count.as<uint32_t>();
+        A3_HIP(launch_merge_candidates(st, dec));
+        dec.cand_count = dec.merged_count;
+    } else A3_HIP(launch_frame_candidates(st, dec));
     A3_HIP(launch_decode(st, dec));
     A3_HIP(launch_compact_markers(st, dec));
     if (b.recover) {
@@ -570,7 +586,7 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
         A3_HIP(stage(rb.charuco, ctx->charuco_buf.p));
     }
     if (b.taps) {   // Detection.candidates / .homographies will be asked for frame by frame: their counts travel now
-        A3_HIP(hipMemcpyAsync(ctx->pinned_counts, ctx->cand_count, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
+        A3_HIP(hipMemcpyAsync(ctx->pinned_counts, dec.cand_count, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
         A3_HIP(hipMemcpyAsync((uint8_t*)ctx->pinned_counts + (size_t)b.n * 4, ctx->fin_count.p, (size_t)b.n * 4, hipMemcpyDeviceToHost, st));
     }
     A3_HIP(hipEventRecord(ctx->ev[4], st));
@@ -674,7 +690,7 @@ int ensure_back_buffers(a3_ctx* ctx, Batch& b, size_t head_bytes) {
 // (hipMalloc / hipHostMalloc synchronise the device).  The per-frame dart totals of the device plan live in frame_darts_dev, zeroed
 // once here and handed back zeroed by the plan workgroup.
 int ensure_chain_buffers(a3_ctx* ctx, hipStream_t st, Batch& b, uint64_t cap_d) {
-    const uint32_t n = b.n;
+    const uint32_t n = b.planes;
     const ZeroLayout z = zero_layout(1, n, n, b.marker_cap);
     A3_HIP(ctx->tile_darts.ensure(tile_darts_bytes(b.W, b.H, n)));
     A3_HIP(ctx->zero_blk.ensure(z.total));
@@ -706,29 +722,32 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     const uint32_t kMaxCand = ctx->hints.max_cand;
     // the grey plane is materialised only for readers outside the fused path: Detection.grey (debug taps) and the generic
     // threshold kernels (windows above 15); the decode stage otherwise samples the caller's frames directly
-    const bool big_window = threshold_writes_grey_plane(ctx->cfg.threshold_window);
+    const bool big_window = b.K == 1 && threshold_writes_grey_plane(b.radius);   // (a set of two or more holds fused-kernel radii only)
+    const uint32_t np = b.planes;   // the planes of the front half: n, or n x K with several threshold windows
+    const uint32_t merged_cand = b.K > 1 ? merged_cand_capacity(b.K, kMaxCand) : kMaxCand;
     b.need_grey = b.taps || big_window;
     b.grey_src = big_window || (b.taps && !b.sample_frames);
     if (b.need_grey) A3_HIP(ctx->grey.ensure(npx * n));
     ctx->grey_valid = b.need_grey;
     if (big_window) A3_HIP(ctx->hsum.ensure(npx * n * 2));
     const size_t bits_per_frame = (size_t)words_per_row(W) * 8 * H;   // packed thresholded image
-    A3_HIP(ctx->bin.ensure(bits_per_frame * n));
-    A3_HIP(ctx->frame_darts.ensure((size_t)n * 8));
-    A3_HIP(ctx->cands.ensure((size_t)n * kMaxCand * sizeof(CandRec)));
-    A3_HIP(ctx->pre_xy.ensure((size_t)n * kMaxCand * 16));
-    A3_HIP(ctx->fin_xy.ensure((size_t)n * kMaxCand * 16));
+    A3_HIP(ctx->bin.ensure(bits_per_frame * np));
+    A3_HIP(ctx->frame_darts.ensure((size_t)np * 8));
+    A3_HIP(ctx->cands.ensure((size_t)np * kMaxCand * sizeof(CandRec)));
+    if (b.K > 1) A3_HIP(ctx->merged_count.ensure((size_t)n * 4));
+    A3_HIP(ctx->pre_xy.ensure((size_t)n * merged_cand * 16));
+    A3_HIP(ctx->fin_xy.ensure((size_t)n * merged_cand * 16));
     A3_HIP(ctx->fin_count.ensure((size_t)n * 4));
-    A3_HIP(ctx->work.ensure((size_t)n * kMaxCand * 4));
-    if (kMaxCand > frame_cand_lds_slots()) A3_HIP(ctx->cand_big.ensure((size_t)n * kMaxCand * 4));   // keys / perimeters of k_frame_candidates' through-memory form
-    A3_HIP(ctx->outs.ensure((size_t)n * kMaxCand * decode_out_bytes()));
-    A3_HIP(ctx->proj.ensure((size_t)n * kMaxCand * proj_rec_bytes()));
-    b.max_cand = kMaxCand;
-    b.marker_cap = marker_cap_of(kMaxCand, n, b.out_cap);
+    A3_HIP(ctx->work.ensure((size_t)n * merged_cand * 4));
+    if (merged_cand > frame_cand_lds_slots()) A3_HIP(ctx->cand_big.ensure((size_t)n * merged_cand * 4));   // keys / perimeters of k_frame_candidates' through-memory form
+    A3_HIP(ctx->outs.ensure((size_t)n * merged_cand * decode_out_bytes()));
+    A3_HIP(ctx->proj.ensure((size_t)n * merged_cand * proj_rec_bytes()));
+    b.max_cand = merged_cand; b.plane_cand = kMaxCand;
+    b.marker_cap = marker_cap_of(merged_cand, n, b.out_cap);
     b.guess = marker_guess_of(ctx->last_marker_total, b.marker_cap);
-    b.patch_cap = (uint32_t)std::min<uint64_t>(kPatchCapMax, std::max<uint64_t>(kPatchCapMin, (uint64_t)n * kMaxCand));
+    b.patch_cap = (uint32_t)std::min<uint64_t>(kPatchCapMax, std::max<uint64_t>(kPatchCapMin, (uint64_t)n * merged_cand));
     if (b.taps) { A3_HIP(ctx->patches.ensure((size_t)b.patch_cap * ctx->cfg.homography_sample_size * ctx->cfg.homography_sample_size)); ctx->patch_cap = b.patch_cap; }
-    ctx->W = W; ctx->H = H; ctx->frames = n;
+    ctx->W = W; ctx->H = H; ctx->frames = np; ctx->frames_merged = n; ctx->cand_stride = merged_cand;
     ctx->stats = a3_stats{};
     ctx->contours_valid = false; ctx->markers_valid = false; ctx->side_valid[kSidePoses] = false;
 
@@ -744,13 +763,16 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
                                          .W = b.frames_W, .H = b.frames_H, .factor = b.reduce_f, .dst = ctx->plane.as<uint8_t>(), .dst_row = W,
                                          .dst_frame = npx}));
     if (b.prof) A3_HIP(hipEventRecord(ctx->ev[0], st));
-    A3_HIP(launch_grey_threshold(st, {.pixels = b.pixels, .fmt = b.fmt, .row_stride = b.row_stride, .frame_stride = b.frame_stride, .W = (int)W, .H = (int)H,
-                                      .n = n, .radius = ctx->cfg.threshold_window, .grey = b.need_grey ? ctx->grey.as<uint8_t>() : nullptr,
-                                      .bits = ctx->bin.as<uint64_t>(), .hsum_tmp = big_window ? ctx->hsum.as<uint16_t>() : nullptr}));
+    // one launch per window, window k's bits in block k of the packed planes (the grey plane, where wanted, is the first launch's)
+    for (uint32_t k = 0; k < b.K; k++)
+        A3_HIP(launch_grey_threshold(st, {.pixels = b.pixels, .fmt = b.fmt, .row_stride = b.row_stride, .frame_stride = b.frame_stride, .W = (int)W, .H = (int)H,
+                                          .n = n, .radius = b.K > 1 ? b.win[k] : b.radius, .grey = b.need_grey && k == 0 ? ctx->grey.as<uint8_t>() : nullptr,
+                                          .bits = ctx->bin.as<uint64_t>() + bits_per_frame / 8 * window_plane(k, 0, n),
+                                          .hsum_tmp = big_window ? ctx->hsum.as<uint16_t>() : nullptr}));
     if (b.prof) A3_HIP(hipEventRecord(ctx->ev[1], st));
     if (!held) return A3_OK;
     A3_HIP(hipEventRecord(ctx->ev_k1_done, st));   // (held chains of a burst wait for the last member's)
-    const uint64_t cap_d = device_plan_capacity(ctx->hints, ctx->max_darts, n, W, H);
+    const uint64_t cap_d = device_plan_capacity(ctx->hints, ctx->max_darts, np, W, H);
     if (cap_d == 0) return fail(ctx, A3_ERR_INTERNAL, "a chain was held back for a batch that needs a host-side plan");
     return ensure_chain_buffers(ctx, st, b, cap_d);
 }
@@ -779,12 +801,12 @@ ContourChunk contour_chunk(const a3_ctx* ctx) {
 // (ensure_chain_buffers), it neither allocates nor waits for the device.
 int enqueue_chain(a3_ctx* ctx, Batch& b, bool defer_locked) {
     hipStream_t st = ctx->stream;
-    const uint32_t n = b.n, W = b.W, H = b.H;
+    const uint32_t n = b.planes, W = b.W, H = b.H;   // (the planes: this function is the contour stage's)
     const int rel_mode = defer_locked ? 0 : release_mode();
     const size_t npx = (size_t)W * H;
     const uint32_t minwh = W < H ? W : H;
     const uint32_t min_edge_length = (uint32_t)((float)minwh * ctx->cfg.min_side_length_factor);   // src/aruco.rs:55
-    const uint32_t kMaxCand = b.max_cand;
+    const uint32_t kMaxCand = b.plane_cand;
     // batches of OTHER contexts (same device) that wait with their decode stage are released from inside this batch's launch
     // sequence (see release_mode()): `release_waiting()` records the event they wait for and enqueues them
     bool released = false;
@@ -976,7 +998,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
     const BatchScratch& hs = *reinterpret_cast<const BatchScratch*>(hp);
     const DeviceCounters* hc = reinterpret_cast<const DeviceCounters*>(&hs + 1);
     const size_t slot_bytes = sizeof(CandRec) + 16 + 16 + 4 + decode_out_bytes() + proj_rec_bytes();   // cands, pre_xy, fin_xy, work, outs, proj
-    const Verdict v = batch_verdict(hs, hc, {.n = n, .W = b.W, .H = b.H, .device_plan = b.device_plan, .n_chunks = n_chunks, .chunk0_darts = b.chunk0_darts,
+    const Verdict v = batch_verdict(hs, hc, {.n = b.planes, .W = b.W, .H = b.H, .device_plan = b.device_plan, .n_chunks = n_chunks, .chunk0_darts = b.chunk0_darts,
                                              .rounds_max = b.rounds_max, .out_cap = out_cap, .lds_slots = frame_cand_lds_slots(), .slot_bytes = slot_bytes},
                                     ctx->hints);
     if (b.device_plan && !hs.plan.overflow) ctx->stats.darts = ctx->dbg_nd = v.darts;
@@ -987,7 +1009,10 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         // Every frame of the batch gets the table of the fullest one: what that costs is known before anything is allocated, and a
         // batch whose tables cannot fit is a limit of this implementation (fewer frames per call cure it), not a HIP failure.
         const size_t had = ctx->cands.cap + ctx->pre_xy.cap + ctx->fin_xy.cap + ctx->work.cap + ctx->cand_big.cap + ctx->outs.cap + ctx->proj.cap;
-        const size_t want = (size_t)n * v.next_cand * v.slot_bytes;
+        // (several windows: a plane's slot is a CandRec, a frame's merged tables hold what merged_cand_capacity makes of the planes')
+        const size_t want = b.K > 1 ? (size_t)b.planes * v.next_cand * sizeof(CandRec) +
+                                          (size_t)n * merged_cand_capacity(b.K, v.next_cand) * (v.slot_bytes - sizeof(CandRec))
+                                    : (size_t)n * v.next_cand * v.slot_bytes;
         size_t free_b = 0, total_b = 0;
         if (want > had && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want - had > free_b)
             return fail(ctx, A3_ERR_LIMIT, "candidate tables of this batch do not fit the device (every frame gets the fullest frame's table): fewer frames per call");
@@ -1038,7 +1063,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         const uint32_t* hc32 = reinterpret_cast<const uint32_t*>(ctx->pinned_counts);
         ctx->h_cand_pre.assign(hc32, hc32 + n);
         ctx->h_cand_fin.assign(hc32 + n, hc32 + 2 * (size_t)n);
-        for (auto& v : ctx->h_cand_pre) v = std::min(v, ctx->hints.max_cand);
+        for (auto& v : ctx->h_cand_pre) v = std::min(v, b.max_cand);
         ctx->counts_valid = true;
     }
     ctx->last_marker_total = total;
@@ -1239,7 +1264,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
                       &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->solve_in,
-                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out, &ctx->plane};
+                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out, &ctx->plane, &ctx->merged_count};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1439,6 +1464,11 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
     }
     b.recover = ctx->recover.mode != 0 && !ctx->board_ids.empty();
     if (b.recover) { b.recover_cfg = ctx->recover; b.recover_slots = (uint32_t)ctx->board_ids.size(); }
+    b.K = ctx->n_windows > 1 ? ctx->n_windows : 1;
+    b.radius = ctx->n_windows == 1 ? ctx->windows[0] : ctx->cfg.threshold_window;
+    for (uint32_t k = 0; k < b.K && b.K > 1; k++) b.win[k] = ctx->windows[k];
+    if (const char* m = check_window_planes(n_frames, b.K)) return fail(ctx, A3_ERR_INVALID, m);
+    b.planes = n_frames * b.K;
     b.taps = ctx->debug_taps;
     b.sample_frames = ctx->debug_sample_frames;
     b.profiling = ctx->profiling; b.profile_every = ctx->profile_every;
@@ -1529,7 +1559,7 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
     ctx->batch_mode = batch_mode_of(ctx);
     const bool bursts = ctx->batch_mode == 0 && g_overlap_force.load(std::memory_order_relaxed) <= 0 && g_hold_rests && b.profiling < 2;
     // (the plan is the BATCH's: with a rectification set its frames have the view's size b.W x b.H, not the call's width x height)
-    if (bursts && gated && device_plan_capacity(ctx->hints, ctx->max_darts, b.n, b.W, b.H) != 0) {
+    if (bursts && gated && device_plan_capacity(ctx->hints, ctx->max_darts, b.planes, b.W, b.H) != 0) {
         if (int erc = enqueue_front(ctx, b, true)) return erc;
         (void)hipStreamQuery(ctx->stream);
         std::lock_guard<std::mutex> lk(g_defer_mu);
@@ -1547,7 +1577,7 @@ static int submit_common(a3_ctx* ctx, const void* pixels, int memory, int fmt, u
     if (any_held) {   // the last member: threshold kernel, then the held chains of the others behind it, then this batch's own
         // A last member that needs a host-side plan cannot be split (enqueue_front refuses to hold it): the others are then released
         // ungated, ahead of its whole batch.
-        const bool planned = device_plan_capacity(ctx->hints, ctx->max_darts, b.n, b.W, b.H) != 0;
+        const bool planned = device_plan_capacity(ctx->hints, ctx->max_darts, b.planes, b.W, b.H) != 0;
         if (planned) { if (int erc = enqueue_front(ctx, b, true)) return erc; }
         uint32_t released = 0;
         {
@@ -1660,7 +1690,7 @@ int a3_debug_kernel_time(a3_ctx* ctx, int kernel, int dbg, int reps, float* avg_
             }
             // dbg >= 0: k_projection + k_decode, dbg < 0: k_decode alone; |dbg| 1..5 selects the truncated variant (5 and 0: the whole kernel)
             DecodeStage dec = decode_stage(ctx);
-            dec.src = ctx->dbg_src; dec.W = cc.W; dec.H = cc.H; dec.max_cand = ctx->hints.max_cand; dec.few = ctx->frames <= 64u; dec.grid_blocks = 4096;
+            dec.src = ctx->dbg_src; dec.W = cc.W; dec.H = cc.H; dec.max_cand = ctx->cand_stride; dec.few = ctx->frames_merged <= 64u; dec.grid_blocks = 4096;
             dec.per_frame = nullptr;
             dec.projection = dbg >= 0; dec.variant = dbg < 0 ? -dbg : dbg;
             A3_HIP(launch_decode(st, dec));
@@ -1780,7 +1810,7 @@ int a3_get_stats(const a3_ctx* ctx, a3_stats* stats) {
 
 static int download_plane(a3_ctx* ctx, const DevBuf& buf, uint32_t frame, uint8_t* dst) {
     if (!ctx || !dst) return A3_ERR_INVALID;
-    if (frame >= ctx->frames) return fail(ctx, A3_ERR_INVALID, "frame index outside the last batch");
+    if (frame >= ctx->frames_merged) return fail(ctx, A3_ERR_INVALID, "frame index outside the last batch");
     const size_t npx = (size_t)ctx->W * ctx->H;
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
@@ -1808,7 +1838,7 @@ int a3_download_thresholded(a3_ctx* ctx, uint32_t frame, uint8_t* dst) {
 
 int a3_candidate_count(a3_ctx* ctx, uint32_t frame, uint32_t* n_pre, uint32_t* n_final) {
     if (!ctx) return A3_ERR_INVALID;
-    if (frame >= ctx->frames) return fail(ctx, A3_ERR_INVALID, "frame index outside the last batch");
+    if (frame >= ctx->frames_merged) return fail(ctx, A3_ERR_INVALID, "frame index outside the last batch");
     if (ctx->counts_valid && frame < ctx->h_cand_fin.size()) {   // the tapped batch brought them along
         if (n_pre) *n_pre = ctx->h_cand_pre[frame];
         if (n_final) *n_final = ctx->h_cand_fin[frame];
@@ -1817,9 +1847,9 @@ int a3_candidate_count(a3_ctx* ctx, uint32_t frame, uint32_t* n_pre, uint32_t* n
     A3_HIP(hipSetDevice(ctx->device));
     if (int rcs_ = need_stream(ctx)) return rcs_;
     uint32_t a = 0, b = 0;
-    A3_HIP(hipMemcpy(&a, ctx->cand_count + frame, 4, hipMemcpyDeviceToHost));
+    A3_HIP(hipMemcpy(&a, ctx->pre_count + frame, 4, hipMemcpyDeviceToHost));
     A3_HIP(hipMemcpy(&b, ctx->fin_count.as<uint32_t>() + frame, 4, hipMemcpyDeviceToHost));
-    if (n_pre) *n_pre = std::min(a, ctx->hints.max_cand);
+    if (n_pre) *n_pre = std::min(a, ctx->cand_stride);
     if (n_final) *n_final = b;
     return A3_OK;
 }
@@ -1832,7 +1862,7 @@ int a3_download_candidates(a3_ctx* ctx, uint32_t frame, int before_discard, uint
     if (cnt > cap_quads) return fail(ctx, A3_ERR_CAPACITY, "cap_quads too small");
     std::vector<uint16_t> tmp((size_t)cnt * 8);
     const DevBuf& src = before_discard ? ctx->pre_xy : ctx->fin_xy;
-    if (cnt) A3_HIP(hipMemcpy(tmp.data(), src.as<uint16_t>() + (size_t)frame * ctx->hints.max_cand * 8, tmp.size() * 2, hipMemcpyDeviceToHost));
+    if (cnt) A3_HIP(hipMemcpy(tmp.data(), src.as<uint16_t>() + (size_t)frame * ctx->cand_stride * 8, tmp.size() * 2, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < tmp.size(); i++) dst_xy[i] = tmp[i];
     return A3_OK;
 }
@@ -1852,7 +1882,7 @@ int a3_download_homographies(a3_ctx* ctx, uint32_t frame, uint8_t* dst, uint8_t*
     if (int rcs_ = need_stream(ctx)) return rcs_;
     const uint32_t S = ctx->cfg.homography_sample_size;
     const size_t S2 = (size_t)S * S, rec_bytes = (size_t)b * sizeof(DecodeOutHost);
-    const uint8_t* d_outs = (const uint8_t*)ctx->outs.p + (size_t)frame * ctx->hints.max_cand * sizeof(DecodeOutHost);
+    const uint8_t* d_outs = (const uint8_t*)ctx->outs.p + (size_t)frame * ctx->cand_stride * sizeof(DecodeOutHost);
     // One trip: the frame's decode records, and its patches gathered by a kernel into one dense array, land in pinned memory
     // through two copies on the stream and one wait (it was a blocking copy per candidate).
     const size_t flag_off = (rec_bytes + 15) & ~(size_t)15, patch_off = flag_off + 16;
@@ -2087,6 +2117,76 @@ int a3_debug_frame_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t max_cand,
     A3_HIP(hipMemcpyAsync(fin_count, cnt + n_frames, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
     A3_HIP(hipMemcpyAsync(work, d_work.p, slots * 4, hipMemcpyDeviceToHost, st));
     A3_HIP(hipMemcpyAsync(work_count, cnt + 2 * (size_t)n_frames, 4, hipMemcpyDeviceToHost, st));
+    if (S) A3_HIP(hipMemcpyAsync(proj, d_proj.p, proj_bytes, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipStreamSynchronize(ctx->stream));
+    return A3_OK;
+}
+
+// k_merge_candidates as the pipeline launches it (a3_set_threshold_windows) -- one call of launch_merge_candidates on hand-made per-plane
+// tables, on buffers of its own (freed on return), every device buffer filled with 0xFF first, as a3_debug_frame_candidates.
+int a3_debug_merge_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t n_windows, uint32_t plane_cand, const uint32_t* cand_count,
+                              const a3_debug_cand* records, float min_distance, uint32_t S, uint16_t* pre_xy, uint16_t* fin_xy,
+                              uint32_t* fin_count, uint32_t* work, uint32_t* work_count, void* proj, uint32_t* merged_count, uint32_t* err_flags) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (n_frames == 0 || n_windows < 2 || n_windows > A3_MAX_THRESHOLD_WINDOWS) return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: n_frames >= 1 and 2..4 windows");
+    if (plane_cand == 0 || plane_cand > kMaxCandLimit) return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: plane_cand must be in 1..65536");
+    if (!cand_count || !pre_xy || !fin_xy || !fin_count || !work || !work_count || !merged_count || !err_flags || (S && !proj))
+        return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: a NULL argument");
+    const size_t planes = (size_t)n_frames * n_windows, plane_slots = planes * plane_cand;
+    const uint32_t merged = merged_cand_capacity(n_windows, plane_cand);
+    const size_t slots = (size_t)n_frames * merged;
+    if (plane_slots > ((size_t)1 << 26)) return fail(ctx, A3_ERR_LIMIT, "a3_debug_merge_candidates: more than 2^26 slots");
+    std::vector<CandRec> h(plane_slots);
+    memset(h.data(), 0xFF, plane_slots * sizeof(CandRec));
+    size_t given = 0;
+    std::vector<uint32_t> keys;
+    for (size_t p = 0; p < planes; p++) {
+        const uint32_t c = std::min(cand_count[p], plane_cand);
+        if (c && !records) return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: a NULL argument");
+        keys.resize(c);
+        for (uint32_t i = 0; i < c; i++) {
+            memcpy(&h[p * plane_cand + i], &records[given + i], sizeof(CandRec));
+            keys[i] = records[given + i].start_key;
+        }
+        std::sort(keys.begin(), keys.end());
+        if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
+            return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: a plane's start keys must be unique");
+        given += c;
+    }
+    A3_HIP(hipSetDevice(ctx->device));
+    if (int rcs_ = need_stream(ctx)) return rcs_;
+    struct Own : DevBuf { ~Own() { release(); } } d_cands, d_cnt, d_pre, d_fin, d_work, d_proj, d_big;
+    const bool big = merged > frame_cand_lds_slots();
+    const size_t proj_bytes = S ? slots * proj_rec_bytes() : 0;
+    A3_HIP(d_cands.ensure(plane_slots * sizeof(CandRec)));
+    A3_HIP(d_cnt.ensure((planes + (size_t)2 * n_frames + 2) * 4));   // cand_count | fin_count | merged_count | work_count | err_flags
+    A3_HIP(d_pre.ensure(slots * 16)); A3_HIP(d_fin.ensure(slots * 16)); A3_HIP(d_work.ensure(slots * 4));
+    if (S) A3_HIP(d_proj.ensure(proj_bytes));
+    if (big) A3_HIP(d_big.ensure(slots * 4));
+    uint32_t* cnt = d_cnt.as<uint32_t>();
+    uint32_t* d_fin_count = cnt + planes, * d_merged = d_fin_count + n_frames, * d_work_count = d_merged + n_frames, * d_err = d_work_count + 1;
+    hipStream_t st = ctx->stream;
+    A3_HIP(hipMemcpyAsync(d_cands.p, h.data(), plane_slots * sizeof(CandRec), hipMemcpyHostToDevice, st));
+    A3_HIP(hipMemcpyAsync(cnt, cand_count, planes * 4, hipMemcpyHostToDevice, st));
+    A3_HIP(hipMemsetAsync(d_fin_count, 0xFF, (size_t)2 * n_frames * 4, st));
+    A3_HIP(hipMemsetAsync(d_work_count, 0, 8, st));
+    A3_HIP(hipMemsetAsync(d_pre.p, 0xFF, slots * 16, st)); A3_HIP(hipMemsetAsync(d_fin.p, 0xFF, slots * 16, st));
+    A3_HIP(hipMemsetAsync(d_work.p, 0xFF, slots * 4, st));
+    if (S) A3_HIP(hipMemsetAsync(d_proj.p, 0xFF, proj_bytes, st));
+    if (big) A3_HIP(hipMemsetAsync(d_big.p, 0xFF, slots * 4, st));
+    DecodeStage dec;
+    dec.n_frames = n_frames; dec.max_cand = merged; dec.cands = d_cands.as<CandRec>(); dec.cand_count = cnt; dec.min_distance = min_distance;
+    dec.pre_xy = d_pre.as<uint16_t>(); dec.fin_xy = d_fin.as<uint16_t>(); dec.fin_count = d_fin_count; dec.work = d_work.as<uint32_t>();
+    dec.work_count = d_work_count; dec.S = S; dec.proj = S ? d_proj.p : nullptr; dec.big_scratch = big ? d_big.as<float>() : nullptr;
+    dec.windows = n_windows; dec.plane_cand = plane_cand; dec.merged_count = d_merged; dec.err_flags = d_err;
+    A3_HIP(launch_merge_candidates(st, dec));
+    A3_HIP(hipMemcpyAsync(pre_xy, d_pre.p, slots * 16, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(fin_xy, d_fin.p, slots * 16, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(fin_count, d_fin_count, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(merged_count, d_merged, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(work, d_work.p, slots * 4, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(work_count, d_work_count, 4, hipMemcpyDeviceToHost, st));
+    A3_HIP(hipMemcpyAsync(err_flags, d_err, 4, hipMemcpyDeviceToHost, st));
     if (S) A3_HIP(hipMemcpyAsync(proj, d_proj.p, proj_bytes, hipMemcpyDeviceToHost, st));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
@@ -2869,6 +2969,22 @@ int a3_set_reduction(a3_ctx* ctx, const a3_reduction* r) {
     if (const char* m = check_reduction(*r)) return fail(ctx, A3_ERR_INVALID, m);
     if (ctx->rect_on) return fail(ctx, A3_ERR_INVALID, "a3_set_reduction: a rectification is set (a3_set_rectification): set one or the other");
     ctx->reduction = *r;
+    return A3_OK;
+}
+
+int a3_set_threshold_windows(a3_ctx* ctx, const uint32_t* radii, size_t n) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (const char* m = check_threshold_windows(ctx->busy(), radii, n)) return fail(ctx, A3_ERR_INVALID, m);
+    ctx->n_windows = radii ? (uint32_t)n : 0;
+    for (uint32_t k = 0; k < A3_MAX_THRESHOLD_WINDOWS; k++) ctx->windows[k] = k < ctx->n_windows ? radii[k] : 0;
+    return A3_OK;
+}
+
+int a3_get_threshold_windows(const a3_ctx* ctx, uint32_t* radii, size_t cap, size_t* n) {
+    if (!ctx || !n || (!radii && cap)) return A3_ERR_INVALID;
+    *n = ctx->n_windows;
+    if (ctx->n_windows > cap) return fail(const_cast<a3_ctx*>(ctx), A3_ERR_CAPACITY, "a3_get_threshold_windows: cap is smaller than the number of windows set");
+    for (uint32_t k = 0; k < ctx->n_windows; k++) radii[k] = ctx->windows[k];
     return A3_OK;
 }
 

@@ -91,6 +91,21 @@ int  a3_debug_frame_candidates(a3_ctx *ctx, uint32_t n_frames, uint32_t max_cand
                                float min_distance, uint32_t S, uint16_t *pre_xy, uint16_t *fin_xy, uint32_t *fin_count, uint32_t *work,
                                uint32_t *work_count, void *proj);
 
+/* k_merge_candidates (a3_set_threshold_windows: the K planes' candidates of every frame ranked by (window, start key), the discard with
+ * the rotation across windows, compaction, the work list, the projections) launched exactly as the pipeline launches it -- ONE call of
+ * launch_merge_candidates, so the merged capacity M = min(n_windows * plane_cand, 65536) picks the kernel's form: all in LDS up to 6144
+ * merged slots per frame, through memory above -- on hand-made per-plane tables.  The product never calls it; tests/ do.
+ *   n_frames >= 1, n_windows in 2..4, plane_cand in 1..65536 (slots per plane), cand_count[n_windows * n_frames] at plane index
+ *   k * n_frames + f (may exceed plane_cand: an overflowed plane), records: plane after plane in that index order, min(cand_count[p],
+ *   plane_cand) records each (keys unique per plane), S: homography_sample_size, 0 = no projections (proj may then be NULL).
+ * Out, each for n_frames * M slots and filled with 0xFF bytes wherever the kernel did not write: pre_xy and fin_xy (8 x u16 per slot),
+ * work (u32 per slot), proj (A3_DEBUG_PROJ_BYTES per slot, indexed like work); fin_count[n_frames]; merged_count[n_frames]; *work_count;
+ * *err_flags (the kErr* word, zeroed first: kErrCandTable = 8 for a frame whose planes sum beyond M).  Runs on buffers of its own. */
+int  a3_debug_merge_candidates(a3_ctx *ctx, uint32_t n_frames, uint32_t n_windows, uint32_t plane_cand, const uint32_t *cand_count,
+                               const a3_debug_cand *records, float min_distance, uint32_t S, uint16_t *pre_xy, uint16_t *fin_xy,
+                               uint32_t *fin_count, uint32_t *work, uint32_t *work_count, void *proj, uint32_t *merged_count,
+                               uint32_t *err_flags);
+
 /* k_contour_quads (per traced border: Douglas-Peucker with the arg-max over a group's lanes, the hull of the four kept points, the
  * squared-edge filter of quirk Q1, the winding fix) launched exactly as the pipeline launches it -- ONE call of launch_contour_quads with
  * a ContourChunk filled from the arguments, so width and height pick the 24-bit or the 64-bit numerators and n_darts sizes the grid (160

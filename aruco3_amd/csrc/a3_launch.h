@@ -101,6 +101,11 @@ struct DecodeStage {
     const CandRec* cands = nullptr; const uint32_t* cand_count = nullptr; float min_distance = 0.0f;
     uint16_t* pre_xy = nullptr, * fin_xy = nullptr; uint32_t* fin_count = nullptr, * work = nullptr; unsigned int* work_count = nullptr;
     uint32_t S = 0; void* proj = nullptr; float* big_scratch = nullptr;
+    // launch_merge_candidates (a3_set_threshold_windows, windows = 2..4) in launch_frame_candidates' place: cands and cand_count are the
+    // n_frames x windows PLANES' (plane (k, f) at k * n_frames + f, plane_cand slots each), every other table is the frames' with
+    // max_cand = merged_cand_capacity(windows, plane_cand) slots; merged_count[n_frames]: the concatenated lists' lengths, which the
+    // caller then hands to launch_compact_markers as its cand_count.  big_scratch: needed when max_cand > frame_cand_lds_slots().
+    uint32_t windows = 0, plane_cand = 0; uint32_t* merged_count = nullptr;
     // launch_decode: k_decode over the work list.  n: cells per side; patches (nullable, debug taps): patch_cap warped patches are kept;
     // per_frame: nullable; few (at most 64 frames): all four waves of a workgroup run the stages behind the sampling.
     PixelSrc src{}; int W = 0, H = 0; uint32_t n = 0, max_taps = 0; const uint64_t* dict = nullptr; uint32_t n_codes = 0, tau = 0; int filter = 0;
@@ -114,6 +119,7 @@ struct DecodeStage {
     a3_marker* markers = nullptr; uint32_t marker_cap = 0; unsigned int* marker_total = nullptr, * err_flags = nullptr, * cand_pre_total = nullptr;
 };
 hipError_t launch_frame_candidates(hipStream_t st, const DecodeStage& d);
+hipError_t launch_merge_candidates(hipStream_t st, const DecodeStage& d);
 hipError_t launch_decode(hipStream_t st, const DecodeStage& d);
 hipError_t launch_compact_markers(hipStream_t st, const DecodeStage& d);
 hipError_t launch_weight_table(hipStream_t st, uint32_t S, uint32_t n, uint32_t max_taps, float* wtab);

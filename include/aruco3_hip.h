@@ -1261,6 +1261,51 @@ int  a3_reduce_frames(a3_ctx *ctx, const void *src, int src_memory, int fmt, uin
 int  a3_set_reduction(a3_ctx *ctx, const a3_reduction *r);          /* NULL: off */
 int  a3_get_reduction(const a3_ctx *ctx, a3_reduction *r, int *enabled);
 
+/* Detection with several threshold windows.  NOT in the reference: an opt-in extension (OpenCV's adaptiveThreshWinSizeMin / Max / Step):
+ * every frame is binarised once per window, quads are found in each binary image, and the candidates of all windows are merged into one
+ * list per frame on the device, ahead of the decode stage.
+ *
+ * a3_set_threshold_windows: a context setting, off by default; a context that never sets it (or set NULL / n = 0 last) launches exactly
+ * what it launched before.
+ *   n = 1, radius w in 1 .. 2^31 - 1: every later detect call returns, to the bit, what a context created with threshold_window = w
+ *     returns; it takes the ordinary single-window path.
+ *   2 <= n <= A3_MAX_THRESHOLD_WINDOWS: radii strictly ascending, each in 1..31 (the fused one-pass threshold kernels, which need no
+ *     grey plane).  With windows w_0 < ... < w_{K-1}, a batch of n frames and min_distance = min(W, H) * min_corner_separation_factor
+ *     (f32, as ever), a detect call returns, to the bit, the result of these steps:
+ *   1. plane (k, f), index k*n + f (window-major), is the reference's adaptive_threshold(grey_f, w_k); find_contours,
+ *      contours_to_candidates and enforce_clockwise_corners run on each plane as they do on a frame today.
+ *   2. frame f's candidate list before the discard is the concatenation, for k = 0 .. K-1, of plane (k, f)'s candidates in the
+ *      reference's order (ascending start key within a plane).
+ *   3. the discard is the reference's walk (src/aruco.rs:187-232) over that list with the same f32 operations: i ascending, j > i
+ *      ascending, dead ones skipped; a pair is close when distance / 4.0f < min_distance; then j dies if perimeter_i >= perimeter_j,
+ *      else i dies (and the rest of i's row is skipped).  For a pair from the SAME window, distance is the reference's: the sum over
+ *      p = 0..3 of |corner_p(i) - corner_p(j)|.  For a pair from DIFFERENT windows it is the minimum over r = 0..3 of that sum between
+ *      quad i and quad j with its corners rotated left by r (corner_p(j) replaced by corner_{(p+r) mod 4}(j)); the minimum is taken
+ *      as r = 0 first, then each later r replacing it when strictly smaller.  (The same marker traced in two binary images often
+ *      starts at a different corner; its unrotated distance is about a side length and both copies would survive.)
+ *   4. survivors keep their own corner order and their order in the list; decode, accept and everything behind them are unchanged and
+ *      read frame f.  a3_marker.candidate_index is the position in the merged final list.
+ * Consequences:
+ *   - A3_MAX_CANDIDATES_PER_FRAME applies to the merged list: a frame whose planes together hold more is A3_ERR_LIMIT.  The merged
+ *     tables hold K times a plane's table (up to that limit), so they never overflow on their own; a plane that outgrows its table
+ *     is re-run with larger tables as a frame is today.
+ *   - frames x K is at most 65535 per call (A3_ERR_INVALID at the detect call beyond: split the batch).
+ *   - with a3_set_reduction or a3_set_rectification the derived grey plane is the source of all K threshold launches; everything
+ *     behind the marker list (refinement, poses, boards, recovery, ChArUco) composes unchanged.
+ *   - debug taps: a3_download_thresholded, a3_contour_count and a3_download_contours take the plane index k*n + f;
+ *     a3_download_grey, a3_candidate_count, a3_download_candidates and a3_download_homographies take frame f and serve the merged
+ *     lists (before_discard = 1: the concatenated list of step 2).
+ *   - a3_stats.candidates_pre counts the concatenated lists.
+ *   - the frames are read K times by the threshold stage (K launches); the contour stage sees n*K frames.
+ * Errors of the setter (A3_ERR_INVALID, the setting stays as it was): n > A3_MAX_THRESHOLD_WINDOWS, a radius of 0, a radius above 31
+ * in a set of two or more (above 2^31 - 1 alone), radii not strictly ascending, a batch submitted and not yet collected.
+ * a3_get_threshold_windows: the radii in force (*n = 0: off); more than cap: A3_ERR_CAPACITY (*n is still set).
+ * Out of scope: a threshold kernel that reads the frames once for all windows, radii above 31 in a set, choosing windows
+ * automatically, reporting which window found a marker, a rotation-aware discard within one window. */
+#define A3_MAX_THRESHOLD_WINDOWS 4
+int  a3_set_threshold_windows(a3_ctx *ctx, const uint32_t *radii, size_t n);   /* NULL or n = 0: off */
+int  a3_get_threshold_windows(const a3_ctx *ctx, uint32_t *radii, size_t cap, size_t *n);
+
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);
 int  a3_calculate_tau(int device, const uint64_t *codes, size_t n_codes, uint8_t *tau);

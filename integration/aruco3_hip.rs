@@ -712,6 +712,8 @@ extern "C" {
                             dst_memory: c_int, dst_row_stride: usize, dst_frame_stride: usize) -> c_int;
     pub fn a3_set_reduction(ctx: *mut A3Ctx, r: *const A3Reduction) -> c_int;
     pub fn a3_get_reduction(ctx: *const A3Ctx, r: *mut A3Reduction, enabled: *mut c_int) -> c_int;
+    pub fn a3_set_threshold_windows(ctx: *mut A3Ctx, radii: *const u32, n: usize) -> c_int;
+    pub fn a3_get_threshold_windows(ctx: *const A3Ctx, radii: *mut u32, cap: usize, n: *mut usize) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
@@ -1255,6 +1257,43 @@ impl Detector {
         let mut det = Detection { grey: None, candidates: vec![], homographies: vec![], markers: markers[..found].iter().map(marker_of).collect() };
         if populate {   // (the taps report the reduced view)
             fill_debug_outputs(&ctx, 0, p.width / factor, p.height / factor, self.config.homography_sample_size as u32, &mut det);
+        }
+        det
+    }
+
+    /// New (additive): `detect` with several adaptive-threshold windows (a3_set_threshold_windows; OpenCV's adaptiveThreshWinSizeMin /
+    /// Max / Step): the image is binarised once per radius of `windows` (2 to 4 radii, strictly ascending, each in 1..31; one radius:
+    /// that radius in `config.threshold_window`'s place), quads are found in every binary image and merged into one candidate list on
+    /// the device, ahead of the decoder.  The Python twin is `Detector(threshold_windows=(3, 7, 15))`; here `Detector` itself gains no
+    /// field (the setting is handed to the shared context for this call only, under its lock, as `detect_reduced` hands over its own).
+    pub fn detect_windows(&self, image: DynamicImage, windows: &[u32]) -> Detection {
+        let populate = POPULATE.load(Ordering::Relaxed);
+        let slot = slot_for(self);
+        let mut ctx = slot.lock().unwrap();
+        let images = std::slice::from_ref(&image);
+        let p = pack(images, &mut ctx.staging);
+        ctx.check(unsafe { a3_set_debug_taps(ctx.raw, populate as c_int) }, "a3_set_debug_taps");
+        ctx.check(unsafe { a3_set_threshold_windows(ctx.raw, windows.as_ptr(), windows.len()) }, "a3_set_threshold_windows");
+        let mut markers = vec![A3Marker::default(); 64];
+        let mut per = vec![0u32; 1];
+        let mut found = 0usize;
+        let rc = loop {
+            let rc = unsafe {
+                a3_detect_batch(ctx.raw, p.bytes as *const c_void, A3_MEM_HOST, p.fmt, p.width, p.height, p.width as usize * p.bpp,
+                                p.width as usize * p.height as usize * p.bpp, 1, markers.as_mut_ptr(), markers.len(), per.as_mut_ptr(),
+                                &mut found)
+            };
+            if rc == A3_ERR_CAPACITY && markers.len() < MAX_MARKERS_PER_FRAME {
+                markers.resize(markers.len() * 4, A3Marker::default());
+                continue;
+            }
+            break rc;
+        };
+        unsafe { a3_set_threshold_windows(ctx.raw, std::ptr::null(), 0) }; // the shared context goes back to the plain detect
+        ctx.check(rc, "a3_detect_batch");
+        let mut det = Detection { grey: None, candidates: vec![], homographies: vec![], markers: markers[..found].iter().map(marker_of).collect() };
+        if populate {   // (the taps serve the merged lists)
+            fill_debug_outputs(&ctx, 0, p.width, p.height, self.config.homography_sample_size as u32, &mut det);
         }
         det
     }
