@@ -2056,93 +2056,26 @@ int a3_debug_discard_too_near(a3_ctx* ctx, const uint32_t* quads_xy, size_t n, f
     return A3_OK;
 }
 
-// k_frame_candidates as the pipeline launches it -- any frame count, any table size, keys as given -- on buffers of its own (freed on
-// return: nothing of the context's changes size, so a batch afterwards runs what it would have run).  Every device buffer is filled
-// with 0xFF first, so what the kernel left alone comes back as 0xFF.
-int a3_debug_frame_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t max_cand, const uint32_t* cand_count, const a3_debug_cand* records,
-                              float min_distance, uint32_t S, uint16_t* pre_xy, uint16_t* fin_xy, uint32_t* fin_count, uint32_t* work,
-                              uint32_t* work_count, void* proj) {
+// The host path of a3_debug_frame_candidates (K == 1: `plane` is "frame", no merged_count, no err_flags) and a3_debug_merge_candidates
+// (K = 2..4): one call of launch_frame_candidates or launch_merge_candidates, as the pipeline makes it, on hand-made tables of plane_cand
+// slots per plane -- any frame count, any table size, keys as given -- on buffers of its own (freed on return: nothing of the context's
+// changes size, so a batch afterwards runs what it would have run).  Every device buffer is filled with 0xFF first, so what the kernel
+// left alone comes back as 0xFF.  The callers have checked their arguments; `who` names the caller in what is refused here.
+static int debug_candidates(a3_ctx* ctx, const char* who, const char* plane, uint32_t n_frames, uint32_t K, uint32_t plane_cand,
+                            const uint32_t* cand_count, const a3_debug_cand* records, float min_distance, uint32_t S, uint16_t* pre_xy,
+                            uint16_t* fin_xy, uint32_t* fin_count, uint32_t* work, uint32_t* work_count, void* proj,
+                            uint32_t* merged_count /*nullable*/, uint32_t* err_flags /*nullable*/) {
     static_assert(sizeof(a3_debug_cand) == sizeof(CandRec) && sizeof(CandRec) == 20, "a3_debug_cand is a CandRec");
-    if (!ctx) return A3_ERR_INVALID;
-    if (n_frames == 0) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: n_frames must be at least 1");
-    if (max_cand == 0 || max_cand > kMaxCandLimit) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: max_cand must be in 1..65536");
-    if (!cand_count || !pre_xy || !fin_xy || !fin_count || !work || !work_count || (S && !proj))
-        return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: a NULL argument");
-    if (proj_rec_bytes() != A3_DEBUG_PROJ_BYTES) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: ProjRec is not A3_DEBUG_PROJ_BYTES long");
-    const size_t slots = (size_t)n_frames * max_cand;
-    if (slots > ((size_t)1 << 26)) return fail(ctx, A3_ERR_LIMIT, "a3_debug_frame_candidates: more than 2^26 slots");
-    std::vector<CandRec> h(slots);
-    memset(h.data(), 0xFF, slots * sizeof(CandRec));
-    size_t given = 0;
-    std::vector<uint32_t> keys;
-    for (uint32_t f = 0; f < n_frames; f++) {
-        const uint32_t c = std::min(cand_count[f], max_cand);
-        if (c && !records) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: a NULL argument");
-        keys.resize(c);
-        for (uint32_t i = 0; i < c; i++) {
-            memcpy(&h[(size_t)f * max_cand + i], &records[given + i], sizeof(CandRec));
-            keys[i] = records[given + i].start_key;
-        }
-        std::sort(keys.begin(), keys.end());
-        if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
-            return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: a frame's start keys must be unique");
-        given += c;
-    }
-    A3_HIP(hipSetDevice(ctx->device));
-    if (int rcs_ = need_stream(ctx)) return rcs_;
-    struct Own : DevBuf { ~Own() { release(); } } d_cands, d_cnt, d_pre, d_fin, d_work, d_proj, d_big;
-    const bool big = max_cand > frame_cand_lds_slots();
-    const size_t proj_bytes = S ? slots * proj_rec_bytes() : 0;
-    A3_HIP(d_cands.ensure(slots * sizeof(CandRec)));
-    A3_HIP(d_cnt.ensure(((size_t)2 * n_frames + 1) * 4));   // cand_count | fin_count | work_count
-    A3_HIP(d_pre.ensure(slots * 16)); A3_HIP(d_fin.ensure(slots * 16)); A3_HIP(d_work.ensure(slots * 4));
-    if (S) A3_HIP(d_proj.ensure(proj_bytes));
-    if (big) A3_HIP(d_big.ensure(slots * 4));
-    uint32_t* cnt = d_cnt.as<uint32_t>();
-    hipStream_t st = ctx->stream;
-    A3_HIP(hipMemcpyAsync(d_cands.p, h.data(), slots * sizeof(CandRec), hipMemcpyHostToDevice, st));
-    A3_HIP(hipMemcpyAsync(cnt, cand_count, (size_t)n_frames * 4, hipMemcpyHostToDevice, st));
-    A3_HIP(hipMemsetAsync(cnt + n_frames, 0xFF, (size_t)n_frames * 4, st));
-    A3_HIP(hipMemsetAsync(cnt + 2 * (size_t)n_frames, 0, 4, st));
-    A3_HIP(hipMemsetAsync(d_pre.p, 0xFF, slots * 16, st)); A3_HIP(hipMemsetAsync(d_fin.p, 0xFF, slots * 16, st));
-    A3_HIP(hipMemsetAsync(d_work.p, 0xFF, slots * 4, st));
-    if (S) A3_HIP(hipMemsetAsync(d_proj.p, 0xFF, proj_bytes, st));
-    if (big) A3_HIP(hipMemsetAsync(d_big.p, 0xFF, slots * 4, st));
-    A3_HIP(launch_frame_candidates(st, {.n_frames = n_frames, .max_cand = max_cand, .cands = d_cands.as<CandRec>(), .cand_count = cnt, .min_distance = min_distance,
-                                        .pre_xy = d_pre.as<uint16_t>(), .fin_xy = d_fin.as<uint16_t>(), .fin_count = cnt + n_frames, .work = d_work.as<uint32_t>(),
-                                        .work_count = cnt + 2 * (size_t)n_frames, .S = S, .proj = S ? d_proj.p : nullptr,
-                                        .big_scratch = big ? d_big.as<float>() : nullptr}));
-    A3_HIP(hipMemcpyAsync(pre_xy, d_pre.p, slots * 16, hipMemcpyDeviceToHost, st));
-    A3_HIP(hipMemcpyAsync(fin_xy, d_fin.p, slots * 16, hipMemcpyDeviceToHost, st));
-    A3_HIP(hipMemcpyAsync(fin_count, cnt + n_frames, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
-    A3_HIP(hipMemcpyAsync(work, d_work.p, slots * 4, hipMemcpyDeviceToHost, st));
-    A3_HIP(hipMemcpyAsync(work_count, cnt + 2 * (size_t)n_frames, 4, hipMemcpyDeviceToHost, st));
-    if (S) A3_HIP(hipMemcpyAsync(proj, d_proj.p, proj_bytes, hipMemcpyDeviceToHost, st));
-    A3_HIP(hipStreamSynchronize(ctx->stream));
-    return A3_OK;
-}
-
-// k_merge_candidates as the pipeline launches it (a3_set_threshold_windows) -- one call of launch_merge_candidates on hand-made per-plane
-// tables, on buffers of its own (freed on return), every device buffer filled with 0xFF first, as a3_debug_frame_candidates.
-int a3_debug_merge_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t n_windows, uint32_t plane_cand, const uint32_t* cand_count,
-                              const a3_debug_cand* records, float min_distance, uint32_t S, uint16_t* pre_xy, uint16_t* fin_xy,
-                              uint32_t* fin_count, uint32_t* work, uint32_t* work_count, void* proj, uint32_t* merged_count, uint32_t* err_flags) {
-    if (!ctx) return A3_ERR_INVALID;
-    if (n_frames == 0 || n_windows < 2 || n_windows > A3_MAX_THRESHOLD_WINDOWS) return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: n_frames >= 1 and 2..4 windows");
-    if (plane_cand == 0 || plane_cand > kMaxCandLimit) return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: plane_cand must be in 1..65536");
-    if (!cand_count || !pre_xy || !fin_xy || !fin_count || !work || !work_count || !merged_count || !err_flags || (S && !proj))
-        return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: a NULL argument");
-    const size_t planes = (size_t)n_frames * n_windows, plane_slots = planes * plane_cand;
-    const uint32_t merged = merged_cand_capacity(n_windows, plane_cand);
+    const size_t planes = (size_t)n_frames * K, plane_slots = planes * plane_cand;
+    const uint32_t merged = merged_cand_capacity(K, plane_cand);   // (K == 1: plane_cand)
     const size_t slots = (size_t)n_frames * merged;
-    if (plane_slots > ((size_t)1 << 26)) return fail(ctx, A3_ERR_LIMIT, "a3_debug_merge_candidates: more than 2^26 slots");
     std::vector<CandRec> h(plane_slots);
     memset(h.data(), 0xFF, plane_slots * sizeof(CandRec));
     size_t given = 0;
     std::vector<uint32_t> keys;
     for (size_t p = 0; p < planes; p++) {
         const uint32_t c = std::min(cand_count[p], plane_cand);
-        if (c && !records) return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: a NULL argument");
+        if (c && !records) return fail(ctx, A3_ERR_INVALID, (std::string(who) + ": a NULL argument").c_str());
         keys.resize(c);
         for (uint32_t i = 0; i < c; i++) {
             memcpy(&h[p * plane_cand + i], &records[given + i], sizeof(CandRec));
@@ -2150,7 +2083,7 @@ int a3_debug_merge_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t n_windows
         }
         std::sort(keys.begin(), keys.end());
         if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
-            return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: a plane's start keys must be unique");
+            return fail(ctx, A3_ERR_INVALID, (std::string(who) + ": a " + plane + "'s start keys must be unique").c_str());
         given += c;
     }
     A3_HIP(hipSetDevice(ctx->device));
@@ -2178,18 +2111,51 @@ int a3_debug_merge_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t n_windows
     dec.n_frames = n_frames; dec.max_cand = merged; dec.cands = d_cands.as<CandRec>(); dec.cand_count = cnt; dec.min_distance = min_distance;
     dec.pre_xy = d_pre.as<uint16_t>(); dec.fin_xy = d_fin.as<uint16_t>(); dec.fin_count = d_fin_count; dec.work = d_work.as<uint32_t>();
     dec.work_count = d_work_count; dec.S = S; dec.proj = S ? d_proj.p : nullptr; dec.big_scratch = big ? d_big.as<float>() : nullptr;
-    dec.windows = n_windows; dec.plane_cand = plane_cand; dec.merged_count = d_merged; dec.err_flags = d_err;
-    A3_HIP(launch_merge_candidates(st, dec));
+    if (K > 1) {
+        dec.windows = K; dec.plane_cand = plane_cand; dec.merged_count = d_merged; dec.err_flags = d_err;
+        A3_HIP(launch_merge_candidates(st, dec));
+    } else {
+        A3_HIP(launch_frame_candidates(st, dec));
+    }
     A3_HIP(hipMemcpyAsync(pre_xy, d_pre.p, slots * 16, hipMemcpyDeviceToHost, st));
     A3_HIP(hipMemcpyAsync(fin_xy, d_fin.p, slots * 16, hipMemcpyDeviceToHost, st));
     A3_HIP(hipMemcpyAsync(fin_count, d_fin_count, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
-    A3_HIP(hipMemcpyAsync(merged_count, d_merged, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
+    if (merged_count) A3_HIP(hipMemcpyAsync(merged_count, d_merged, (size_t)n_frames * 4, hipMemcpyDeviceToHost, st));
     A3_HIP(hipMemcpyAsync(work, d_work.p, slots * 4, hipMemcpyDeviceToHost, st));
     A3_HIP(hipMemcpyAsync(work_count, d_work_count, 4, hipMemcpyDeviceToHost, st));
-    A3_HIP(hipMemcpyAsync(err_flags, d_err, 4, hipMemcpyDeviceToHost, st));
+    if (err_flags) A3_HIP(hipMemcpyAsync(err_flags, d_err, 4, hipMemcpyDeviceToHost, st));
     if (S) A3_HIP(hipMemcpyAsync(proj, d_proj.p, proj_bytes, hipMemcpyDeviceToHost, st));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
+}
+
+// k_frame_candidates as the pipeline launches it: one call of launch_frame_candidates.
+int a3_debug_frame_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t max_cand, const uint32_t* cand_count, const a3_debug_cand* records,
+                              float min_distance, uint32_t S, uint16_t* pre_xy, uint16_t* fin_xy, uint32_t* fin_count, uint32_t* work,
+                              uint32_t* work_count, void* proj) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (n_frames == 0) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: n_frames must be at least 1");
+    if (max_cand == 0 || max_cand > kMaxCandLimit) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: max_cand must be in 1..65536");
+    if (!cand_count || !pre_xy || !fin_xy || !fin_count || !work || !work_count || (S && !proj))
+        return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: a NULL argument");
+    if (proj_rec_bytes() != A3_DEBUG_PROJ_BYTES) return fail(ctx, A3_ERR_INVALID, "a3_debug_frame_candidates: ProjRec is not A3_DEBUG_PROJ_BYTES long");
+    if ((size_t)n_frames * max_cand > ((size_t)1 << 26)) return fail(ctx, A3_ERR_LIMIT, "a3_debug_frame_candidates: more than 2^26 slots");
+    return debug_candidates(ctx, "a3_debug_frame_candidates", "frame", n_frames, 1, max_cand, cand_count, records, min_distance, S, pre_xy, fin_xy,
+                            fin_count, work, work_count, proj, nullptr, nullptr);
+}
+
+// k_merge_candidates as the pipeline launches it (a3_set_threshold_windows): one call of launch_merge_candidates on per-plane tables.
+int a3_debug_merge_candidates(a3_ctx* ctx, uint32_t n_frames, uint32_t n_windows, uint32_t plane_cand, const uint32_t* cand_count,
+                              const a3_debug_cand* records, float min_distance, uint32_t S, uint16_t* pre_xy, uint16_t* fin_xy,
+                              uint32_t* fin_count, uint32_t* work, uint32_t* work_count, void* proj, uint32_t* merged_count, uint32_t* err_flags) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (n_frames == 0 || n_windows < 2 || n_windows > A3_MAX_THRESHOLD_WINDOWS) return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: n_frames >= 1 and 2..4 windows");
+    if (plane_cand == 0 || plane_cand > kMaxCandLimit) return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: plane_cand must be in 1..65536");
+    if (!cand_count || !pre_xy || !fin_xy || !fin_count || !work || !work_count || !merged_count || !err_flags || (S && !proj))
+        return fail(ctx, A3_ERR_INVALID, "a3_debug_merge_candidates: a NULL argument");
+    if ((size_t)n_frames * n_windows * plane_cand > ((size_t)1 << 26)) return fail(ctx, A3_ERR_LIMIT, "a3_debug_merge_candidates: more than 2^26 slots");
+    return debug_candidates(ctx, "a3_debug_merge_candidates", "plane", n_frames, n_windows, plane_cand, cand_count, records, min_distance, S, pre_xy,
+                            fin_xy, fin_count, work, work_count, proj, merged_count, err_flags);
 }
 
 // k_contour_quads as the pipeline launches it -- ONE call of launch_contour_quads with a ContourChunk filled from the arguments -- on a

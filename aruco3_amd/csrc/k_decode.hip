@@ -33,45 +33,109 @@ __device__ __forceinline__ float perimeter4(const uint16_t* q) {  // src/aruco.r
 struct __attribute__((aligned(8))) ProjRec { float inv[9]; int ok; };
 __device__ bool solve_projection(const float* from, float S, float* inv_out);
 
-// one wave per frame.  cands: unordered CandRec[max_cand] per frame (as k_contour_quads appended them).
+// discard_too_near's distance between quad i and quad j: the reference's sum of the four corner distances (src/aruco.rs:187-232); across
+// threshold windows (include/aruco3_hip.h, a3_set_threshold_windows step 3) the minimum over the four rotations of j, r = 0 first, a
+// later r only when strictly smaller.  A constant cross == false leaves the r = 0 sum and nothing else.
+__device__ __forceinline__ float merge_distance(const float* xi, const float* xj, bool cross) {
+    float best = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        float distance = 0.0f;
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            const int q = (p + r) & 3;
+            const float dx = xi[2 * p] - xj[2 * q];
+            const float dy = xi[2 * p + 1] - xj[2 * q + 1];
+            distance += sqrtf((dx * dx) + (dy * dy));
+        }
+        if (r == 0) best = distance;
+        else if (cross && distance < best) best = distance;
+    }
+    return best;
+}
+
+// One wave per frame: the body of k_frame_candidates (MERGE == false: one table per frame, K == 1, plane_cand == max_cand) and of
+// k_merge_candidates (MERGE: K = 2..4 planes per frame, plane (k, f) at index k * n_frames + f with plane_cand slots).  Frame f's list
+// is the concatenation over k of plane (k, f)'s quads in start-key order: rank = (quads of the frame's earlier planes) + (keys of the
+// same plane below this one).  MERGE carries the window index with the quad (a byte per slot), which selects the distance, and writes
+// merged_count and kErrCandTable; nothing else differs.
 // proj != nullptr: the wave also solves the projection of every surviving candidate (one lane each: the 8x8 system needs
 // ~200 VGPRs, affordable in a one-wave workgroup) into proj[work index], which saves the separate k_projection launch.
 // BIG (tables beyond kFrameCandLds slots per frame -- a frame tiled with thousands of small squares; no camera frame gets there): the
 // sorted quads live where they end up anyway (pre_xy), keys and perimeters in a scratch plane of the caller's, and only the dead flags
-// in LDS (a byte per slot: 64 KB at the format's limit of 65 536 -- a3_marker.candidate_index is 16 bits).  Same walk, same order,
-// every LDS access of the small form a trip to the L2 instead: correct, not fast (0.1 s for 7 000 quads, all of them far apart).
-constexpr uint32_t kFrameCandLds = 6144;   // 21 bytes of LDS per slot in the small form: 129 KB of the CU's 160
+// (and window bytes) in LDS (a byte each per slot: 64 KB at the format's limit of 65 536 -- a3_marker.candidate_index is 16 bits).
+// Same walk, same order, every LDS access of the small form a trip to the L2 instead: correct, not fast (0.1 s for 7 000 quads, all
+// of them far apart).
+constexpr uint32_t kFrameCandLds = 6144;   // 21 bytes of LDS per slot in the small form (22 with the window byte): 129 KB of the CU's 160
 constexpr int kFcWaves = 1;   // occupancy bound of k_frame_candidates and k_projection (the 8x8 solve needs ~200 VGPRs)
-template <bool BIG>
-__global__ __launch_bounds__(64, kFcWaves) void k_frame_candidates(const CandRec* __restrict__ cands, const uint32_t* __restrict__ cand_count,
-                                                         uint32_t max_cand, float min_distance, uint16_t* pre_xy,
-                                                         uint16_t* __restrict__ fin_xy, uint32_t* __restrict__ fin_count,
-                                                         uint32_t* __restrict__ work, unsigned int* __restrict__ work_count,
-                                                         uint32_t S, ProjRec* __restrict__ proj, float* big_scratch /* BIG: frames x max_cand */) {
+template <bool BIG, bool MERGE>
+__device__ __forceinline__ void frame_candidates(const CandRec* __restrict__ cands, const uint32_t* __restrict__ cand_count,
+                                                 uint32_t n_frames, uint32_t K, uint32_t plane_cand, uint32_t max_cand,
+                                                 float min_distance, uint16_t* pre_xy, uint16_t* __restrict__ fin_xy,
+                                                 uint32_t* __restrict__ fin_count, uint32_t* __restrict__ work,
+                                                 unsigned int* __restrict__ work_count, uint32_t S, ProjRec* __restrict__ proj,
+                                                 float* big_scratch /* BIG: frames x max_cand */, uint32_t* __restrict__ merged_count,
+                                                 unsigned int* __restrict__ err_flags) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint16_t* s_xy = BIG ? pre_xy + (size_t)blockIdx.x * max_cand * 8 : reinterpret_cast<uint16_t*>(smem);                      // max_cand * 8
     float* s_per = BIG ? big_scratch + (size_t)blockIdx.x * max_cand : reinterpret_cast<float*>(smem + (size_t)max_cand * 16);   // max_cand
     uint8_t* s_dead = BIG ? smem : smem + (size_t)max_cand * 20;                                                                // max_cand
+    [[maybe_unused]] uint8_t* s_win = s_dead + max_cand;                                                                        // max_cand, MERGE only
     // (BIG: what one lane wrote to memory another reads after the barrier -- the fence makes the wave's stores visible and drops stale lines)
 #define FC_SYNC() do { if (BIG) __threadfence(); __syncthreads(); } while (0)
+    constexpr uint32_t kPlanes = MERGE ? 4 : 1;
     const uint32_t f = blockIdx.x;
     const int lane = threadIdx.x;
-    // a frame that overflowed its table: k_contour_quads has flagged it, the host re-runs the batch with larger tables and nothing of
-    // this pass is used -- no point in ordering the slots that did fit (seconds, at the large end of the through-memory form)
-    const uint32_t c = cand_count[f] > max_cand ? 0u : cand_count[f];
-    const CandRec* src = cands + (size_t)f * max_cand;
-    // rank sort by start key (keys are unique: one border starts per pixel visit).  The keys go to LDS first: ranking
+    uint32_t cnt[kPlanes], off[kPlanes];   // a plane's quads and where they start in the frame's list
+    uint32_t c;
+    if constexpr (MERGE) {
+        // merged_count[f]: the length of the concatenated list; for a frame with a plane beyond plane_cand (flagged by k_contour_quads:
+        // the batch is re-run) the fullest plane's count, and for a frame whose planes sum beyond max_cand (raised here) the sum --
+        // either way what the marker gather reports as the fullest count -- and the frame is left empty.
+        uint32_t sum = 0, most = 0;
+        bool plane_over = false;
+#pragma unroll
+        for (uint32_t k = 0; k < kPlanes; k++) {
+            const uint32_t ck = k < K ? cand_count[(size_t)k * n_frames + f] : 0u;
+            plane_over |= ck > plane_cand;
+            most = max(most, ck);
+            cnt[k] = ck; off[k] = sum;
+            sum += min(ck, plane_cand);   // (no wrap: at most 4 x 65536)
+        }
+        const bool merged_over = !plane_over && sum > max_cand;
+        c = plane_over || merged_over ? 0u : sum;
+        if (lane == 0) {
+            merged_count[f] = plane_over ? most : sum;
+            if (merged_over) atomicOr(err_flags, kErrCandTable);
+        }
+        if (!c) for (uint32_t k = 0; k < kPlanes; k++) cnt[k] = 0;
+    } else {
+        // a frame that overflowed its table: k_contour_quads has flagged it, the host re-runs the batch with larger tables and nothing
+        // of this pass is used -- no point in ordering the slots that did fit (seconds, at the large end of the through-memory form)
+        c = cand_count[f] > max_cand ? 0u : cand_count[f];
+        cnt[0] = c; off[0] = 0;
+    }
+    // rank sort by start key within a plane (keys are unique: one border starts per pixel visit).  The keys go to LDS first: ranking
     // straight from global memory was a chain of c dependent loads per lane (s_per doubles as the key buffer until the
     // perimeters are written).
     uint32_t* s_key = reinterpret_cast<uint32_t*>(s_per);
-    for (uint32_t i = lane; i < c; i += 64) s_key[i] = src[i].start_key;
+#pragma unroll
+    for (uint32_t k = 0; k < kPlanes; k++) {
+        const CandRec* src = cands + ((size_t)k * n_frames + f) * plane_cand;
+        for (uint32_t i = lane; i < cnt[k]; i += 64) s_key[off[k] + i] = src[i].start_key;
+    }
     FC_SYNC();
-    for (uint32_t i = lane; i < c; i += 64) {
-        const uint32_t key = s_key[i];
-        const CandRec r = src[i];   // in flight while the rank is counted
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < c; j++) rank += s_key[j] < key;
-        for (int k = 0; k < 8; k++) s_xy[rank * 8 + k] = r.xy[k];
+#pragma unroll
+    for (uint32_t k = 0; k < kPlanes; k++) {
+        const CandRec* src = cands + ((size_t)k * n_frames + f) * plane_cand;
+        for (uint32_t i = lane; i < cnt[k]; i += 64) {
+            const uint32_t key = s_key[off[k] + i];
+            const CandRec r = src[i];   // in flight while the rank is counted
+            uint32_t rank = off[k];
+            for (uint32_t j = 0; j < cnt[k]; j++) rank += s_key[off[k] + j] < key;
+            for (int q = 0; q < 8; q++) s_xy[rank * 8 + q] = r.xy[q];
+            if constexpr (MERGE) s_win[rank] = (uint8_t)k;
+        }
     }
     FC_SYNC();
     for (uint32_t i = lane; i < c; i += 64) {
@@ -83,15 +147,17 @@ __global__ __launch_bounds__(64, kFcWaves) void k_frame_candidates(const CandRec
     // discard_too_near, src/aruco.rs:187-232: i ascending; for j > i ascending, a close pair kills the smaller
     // perimeter; once i itself is dead the rest of its row is a no-op.
     if (c >= 2 && c <= 64) {
-        // The usual case (a frame holds a few dozen quads): the same walk with everything in registers -- lane j holds quad j,
-        // row i's quad comes through v_readlane (i is uniform), the dead set is a 64-bit mask every lane carries -- so a row is
-        // four square roots, a division and two ballots, without LDS traffic or a barrier.  (s_memtime stamps: the LDS version
+        // The usual case (a frame holds a few dozen quads): the same walk with everything in registers -- lane j holds quad j (and its
+        // window), row i's quad comes through v_readlane (i is uniform), the dead set is a 64-bit mask every lane carries -- so a row
+        // is four square roots, a division and two ballots, without LDS traffic or a barrier.  (s_memtime stamps: the LDS version
         // below spent 850 cycles per live row, half of the kernel's 20 us on BASELINE config 2.)
         const uint32_t j = min((uint32_t)lane, c - 1u);
         float xj[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) xj[k] = (float)s_xy[j * 8 + k];
         const float per_j = s_per[j];
+        int win_j = 0;
+        if constexpr (MERGE) win_j = (int)s_win[j];
         unsigned long long dead = 0;
         for (uint32_t i = 0; i + 1 < c; i++) {
             if ((dead >> i) & 1ull) continue;   // uniform
@@ -99,13 +165,9 @@ __global__ __launch_bounds__(64, kFcWaves) void k_frame_candidates(const CandRec
 #pragma unroll
             for (int k = 0; k < 8; k++) xi[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xj[k]), (int)i));
             const float per_i = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(per_j), (int)i));
-            float distance = 0.0f;
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                const float dx = xi[2 * p] - xj[2 * p];
-                const float dy = xi[2 * p + 1] - xj[2 * p + 1];
-                distance += sqrtf((dx * dx) + (dy * dy));
-            }
+            bool cross = false;
+            if constexpr (MERGE) cross = __builtin_amdgcn_readlane(win_j, (int)i) != win_j;
+            const float distance = merge_distance(xi, xj, cross);
             const bool cand = (uint32_t)lane > i && (uint32_t)lane < c && !((dead >> lane) & 1ull);
             const bool close_alive = cand && (distance / 4.0f) < min_distance;
             const bool bigger = close_alive && !(per_i >= per_j);
@@ -127,13 +189,12 @@ __global__ __launch_bounds__(64, kFcWaves) void k_frame_candidates(const CandRec
             const uint32_t j = j0 + lane;
             bool close_alive = false, bigger = false;
             if (j < c && !s_dead[j]) {
-                float distance = 0.0f;
+                float xi[8], xj[8];
 #pragma unroll
-                for (int p = 0; p < 4; p++) {
-                    const float dx = (float)s_xy[i * 8 + 2 * p] - (float)s_xy[j * 8 + 2 * p];
-                    const float dy = (float)s_xy[i * 8 + 2 * p + 1] - (float)s_xy[j * 8 + 2 * p + 1];
-                    distance += sqrtf((dx * dx) + (dy * dy));
-                }
+                for (int k = 0; k < 8; k++) { xi[k] = (float)s_xy[i * 8 + k]; xj[k] = (float)s_xy[j * 8 + k]; }
+                bool cross = false;
+                if constexpr (MERGE) cross = s_win[i] != s_win[j];
+                const float distance = merge_distance(xi, xj, cross);
                 close_alive = (distance / 4.0f) < min_distance;
                 bigger = close_alive && !(per_i >= s_per[j]);
             }
@@ -183,39 +244,20 @@ __global__ __launch_bounds__(64, kFcWaves) void k_frame_candidates(const CandRec
 #undef FC_SYNC
 }
 
-// ---------------------------------------------------------------------------------------
-// per frame, several threshold windows (a3_set_threshold_windows): merge the K planes' candidates, then the discard
-// ---------------------------------------------------------------------------------------
-// discard_too_near's distance between quad i and quad j (include/aruco3_hip.h, a3_set_threshold_windows step 3): the reference's sum for
-// a pair from one window; across windows the minimum over the four rotations of j, r = 0 first, a later r only when strictly smaller
-__device__ __forceinline__ float merge_distance(const float* xi, const float* xj, bool cross) {
-    float best = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        float distance = 0.0f;
-#pragma unroll
-        for (int p = 0; p < 4; p++) {
-            const int q = (p + r) & 3;
-            const float dx = xi[2 * p] - xj[2 * q];
-            const float dy = xi[2 * p + 1] - xj[2 * q + 1];
-            distance += sqrtf((dx * dx) + (dy * dy));
-        }
-        if (r == 0) best = distance;
-        else if (cross && distance < best) best = distance;
-    }
-    return best;
+// cands: unordered CandRec[max_cand] per frame (as k_contour_quads appended them), 21 bytes of LDS per slot (BIG: 1).
+template <bool BIG>
+__global__ __launch_bounds__(64, kFcWaves) void k_frame_candidates(const CandRec* __restrict__ cands, const uint32_t* __restrict__ cand_count,
+                                                         uint32_t max_cand, float min_distance, uint16_t* pre_xy,
+                                                         uint16_t* __restrict__ fin_xy, uint32_t* __restrict__ fin_count,
+                                                         uint32_t* __restrict__ work, unsigned int* __restrict__ work_count,
+                                                         uint32_t S, ProjRec* __restrict__ proj, float* big_scratch /* BIG: frames x max_cand */) {
+    frame_candidates<BIG, false>(cands, cand_count, 0u, 1u, max_cand, max_cand, min_distance, pre_xy, fin_xy, fin_count, work, work_count, S, proj,
+                                 big_scratch, nullptr, nullptr);
 }
 
-// One wave per frame, k_frame_candidates' counterpart for K = 2..4 windows.  cands: unordered CandRec[plane_cand] per PLANE, plane
-// (k, f) at index k * n_frames + f, with cand_count per plane.  Frame f's list is the concatenation over k of plane (k, f)'s quads in
-// start-key order: rank = (quads of the frame's earlier planes) + (keys of the same plane below this one).  The walk, the compaction,
-// the work items and the projections are k_frame_candidates'; the window index travels with the quad (a byte per slot) and selects the
-// distance.  All merged tables (pre_xy, fin_xy, work, proj) have merged_cap = merged_cand_capacity(K, plane_cand) slots per frame.
-// merged_count[f]: the length of the concatenated list; for a frame with a plane beyond plane_cand (flagged by k_contour_quads: the
-// batch is re-run) the fullest plane's count, and for a frame whose planes sum beyond merged_cap (raised here) the sum -- either way
-// what the marker gather reports as the fullest count -- and the frame is left empty.
-// BIG (merged_cap beyond kFrameCandLds): quads in pre_xy, keys / perimeters in big_scratch (n_frames x merged_cap), dead flags and
-// window bytes in LDS (2 bytes per slot: 128 KB at the format's limit).
+// Several threshold windows (a3_set_threshold_windows), K = 2..4: cands is CandRec[plane_cand] per PLANE with cand_count per plane, and
+// all merged tables (pre_xy, fin_xy, work, proj, big_scratch) have merged_cap = merged_cand_capacity(K, plane_cand) slots per frame;
+// 22 bytes of LDS per slot (BIG: 2).
 template <bool BIG>
 __global__ __launch_bounds__(64, kFcWaves) void k_merge_candidates(const CandRec* __restrict__ cands, const uint32_t* __restrict__ cand_count,
                                                          uint32_t n_frames, uint32_t K, uint32_t plane_cand, uint32_t merged_cap,
@@ -224,162 +266,8 @@ __global__ __launch_bounds__(64, kFcWaves) void k_merge_candidates(const CandRec
                                                          unsigned int* __restrict__ work_count, uint32_t S, ProjRec* __restrict__ proj,
                                                          float* big_scratch, uint32_t* __restrict__ merged_count,
                                                          unsigned int* __restrict__ err_flags) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t max_cand = merged_cap;
-    uint16_t* s_xy = BIG ? pre_xy + (size_t)blockIdx.x * max_cand * 8 : reinterpret_cast<uint16_t*>(smem);                      // max_cand * 8
-    float* s_per = BIG ? big_scratch + (size_t)blockIdx.x * max_cand : reinterpret_cast<float*>(smem + (size_t)max_cand * 16);   // max_cand
-    uint8_t* s_dead = BIG ? smem : smem + (size_t)max_cand * 20;                                                                // max_cand
-    uint8_t* s_win = s_dead + max_cand;                                                                                         // max_cand
-#define FC_SYNC() do { if (BIG) __threadfence(); __syncthreads(); } while (0)
-    const uint32_t f = blockIdx.x;
-    const int lane = threadIdx.x;
-    uint32_t cnt[4] = {0, 0, 0, 0}, off[4] = {0, 0, 0, 0};
-    uint32_t sum = 0, most = 0;
-    bool plane_over = false;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {
-        if (k < K) {
-            const uint32_t ck = cand_count[(size_t)k * n_frames + f];
-            plane_over |= ck > plane_cand;
-            most = max(most, ck);
-            cnt[k] = ck; off[k] = sum;
-            sum += min(ck, plane_cand);   // (no wrap: at most 4 x 65536)
-        }
-    }
-    const bool merged_over = !plane_over && sum > max_cand;
-    const uint32_t c = plane_over || merged_over ? 0u : sum;
-    if (lane == 0) {
-        merged_count[f] = plane_over ? most : sum;
-        if (merged_over) atomicOr(err_flags, kErrCandTable);
-    }
-    // keys to LDS plane by plane (s_per doubles as the key buffer until the perimeters are written), then each quad to its rank
-    uint32_t* s_key = reinterpret_cast<uint32_t*>(s_per);
-    if (c) {
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            if (k < K) {
-                const CandRec* src = cands + ((size_t)k * n_frames + f) * plane_cand;
-                for (uint32_t i = lane; i < cnt[k]; i += 64) s_key[off[k] + i] = src[i].start_key;
-            }
-        }
-    }
-    FC_SYNC();
-    if (c) {
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            if (k < K) {
-                const CandRec* src = cands + ((size_t)k * n_frames + f) * plane_cand;
-                for (uint32_t i = lane; i < cnt[k]; i += 64) {
-                    const uint32_t key = s_key[off[k] + i];
-                    const CandRec r = src[i];   // in flight while the rank is counted
-                    uint32_t rank = off[k];
-                    for (uint32_t j = 0; j < cnt[k]; j++) rank += s_key[off[k] + j] < key;
-                    for (int q = 0; q < 8; q++) s_xy[rank * 8 + q] = r.xy[q];
-                    s_win[rank] = (uint8_t)k;
-                }
-            }
-        }
-    }
-    FC_SYNC();
-    for (uint32_t i = lane; i < c; i += 64) {
-        s_per[i] = perimeter4(&s_xy[i * 8]);
-        s_dead[i] = 0;
-        if (!BIG) for (int k = 0; k < 8; k++) pre_xy[((size_t)f * max_cand + i) * 8 + k] = s_xy[i * 8 + k];
-    }
-    FC_SYNC();
-    if (c >= 2 && c <= 64) {
-        // everything in registers, as k_frame_candidates: lane j holds quad j and its window, row i's come through v_readlane
-        const uint32_t j = min((uint32_t)lane, c - 1u);
-        float xj[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) xj[k] = (float)s_xy[j * 8 + k];
-        const float per_j = s_per[j];
-        const int win_j = (int)s_win[j];
-        unsigned long long dead = 0;
-        for (uint32_t i = 0; i + 1 < c; i++) {
-            if ((dead >> i) & 1ull) continue;   // uniform
-            float xi[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) xi[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xj[k]), (int)i));
-            const float per_i = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(per_j), (int)i));
-            const int win_i = __builtin_amdgcn_readlane(win_j, (int)i);
-            const float distance = merge_distance(xi, xj, win_i != win_j);
-            const bool cand = (uint32_t)lane > i && (uint32_t)lane < c && !((dead >> lane) & 1ull);
-            const bool close_alive = cand && (distance / 4.0f) < min_distance;
-            const bool bigger = close_alive && !(per_i >= per_j);
-            const unsigned long long m_close = __ballot(close_alive), m_big = __ballot(bigger);
-            unsigned long long kill = m_close;
-            if (m_big) {
-                kill = m_close & ((1ull << (__ffsll((long long)m_big) - 1)) - 1ull);
-                dead |= 1ull << i;
-            }
-            dead |= kill;
-        }
-        if ((uint32_t)lane < c) s_dead[lane] = (uint8_t)((dead >> lane) & 1ull);
-    } else
-    for (uint32_t i = 0; i + 1 < c; i++) {
-        if (s_dead[i]) continue;  // uniform: LDS value
-        const float per_i = s_per[i];
-        const uint8_t win_i = s_win[i];
-        float xi[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) xi[k] = (float)s_xy[i * 8 + k];
-        bool i_dead = false;
-        for (uint32_t j0 = i + 1; j0 < c && !i_dead; j0 += 64) {
-            const uint32_t j = j0 + lane;
-            bool close_alive = false, bigger = false;
-            if (j < c && !s_dead[j]) {
-                float xj[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) xj[k] = (float)s_xy[j * 8 + k];
-                const float distance = merge_distance(xi, xj, win_i != s_win[j]);
-                close_alive = (distance / 4.0f) < min_distance;
-                bigger = close_alive && !(per_i >= s_per[j]);
-            }
-            const unsigned long long m_close = __ballot(close_alive), m_big = __ballot(bigger);
-            unsigned long long kill = m_close;
-            if (m_big) {
-                const int first = __ffsll((long long)m_big) - 1;
-                kill = m_close & ((1ull << first) - 1ull);
-                i_dead = true;
-            }
-            if ((kill >> lane) & 1ull) s_dead[j] = 1;
-        }
-        if (i_dead && lane == 0) s_dead[i] = 1;
-        __syncthreads();   // (only s_dead changes inside this loop, and s_dead lives in LDS in both forms)
-    }
-    FC_SYNC();
-    // survivors, order preserved: count them, take a range of the work list, then write quads, work items and projections
-    uint32_t total = 0;
-    for (uint32_t i0 = 0; i0 < c; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        total += (uint32_t)__popcll(__ballot(i < c && !s_dead[i]));
-    }
-    uint32_t w0 = 0;
-    if (lane == 0) {
-        fin_count[f] = total;
-        if (total) w0 = atomicAdd(work_count, total);
-    }
-    w0 = __shfl(w0, 0);
-    uint32_t base = 0;
-    for (uint32_t i0 = 0; i0 < c; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        const bool alive = i < c && !s_dead[i];
-        const unsigned long long m = __ballot(alive);
-        if (alive) {
-            const uint32_t pos = base + __popcll(m & ((1ull << lane) - 1ull));
-            float from[8];
-            for (int k = 0; k < 8; k++) { const uint16_t v = s_xy[i * 8 + k]; fin_xy[((size_t)f * max_cand + pos) * 8 + k] = v; from[k] = (float)v; }
-            work[w0 + pos] = f * max_cand + pos;
-            if (proj) {
-                ProjRec r;
-                r.ok = solve_projection(from, (float)S, r.inv) ? 1 : 0;
-                proj[w0 + pos] = r;
-            }
-        }
-        base += __popcll(m);
-    }
-#undef FC_SYNC
+    frame_candidates<BIG, true>(cands, cand_count, n_frames, K, plane_cand, merged_cap, min_distance, pre_xy, fin_xy, fin_count, work, work_count, S,
+                                proj, big_scratch, merged_count, err_flags);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1288,45 +1176,32 @@ size_t decode_lds_bytes(uint32_t S, uint32_t n, uint32_t max_taps) {
     return (o + 15) & ~(size_t)15;
 }
 
-hipError_t launch_frame_candidates(hipStream_t st, const DecodeStage& f) {
-    const uint32_t max_cand = f.max_cand;
-    const bool big = max_cand > kFrameCandLds;
+// k_frame_candidates or k_merge_candidates, one wave per frame: the BIG choice, the LDS bytes (20 per slot for quads and perimeters in
+// the small form, flag_bytes per slot in both), the dynamic-LDS attribute and the launch
+template <typename... P, typename... A>
+static hipError_t launch_candidates(hipStream_t st, const DecodeStage& f, void (*small)(P...), void (*through_memory)(P...), uint32_t flag_bytes, A... args) {
+    const bool big = f.max_cand > kFrameCandLds;
     if (big && !f.big_scratch) return hipErrorInvalidValue;
-    const size_t lds = big ? (size_t)max_cand + 16 : (size_t)max_cand * 21 + 16;
+    void (*const kernel)(P...) = big ? through_memory : small;
+    const size_t lds = (size_t)f.max_cand * (flag_bytes + (big ? 0u : 20u)) + 16;
     if (lds > 48 * 1024) {   // tables grown past the default
-        const hipError_t e = hipFuncSetAttribute(big ? reinterpret_cast<const void*>(k_frame_candidates<true>) : reinterpret_cast<const void*>(k_frame_candidates<false>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    if (big)
-        hipLaunchKernelGGL(k_frame_candidates<true>, dim3(f.n_frames), dim3(64), lds, st, f.cands, f.cand_count, max_cand, f.min_distance, f.pre_xy, f.fin_xy,
-                           f.fin_count, f.work, f.work_count, f.S, reinterpret_cast<ProjRec*>(f.proj), f.big_scratch);
-    else
-        hipLaunchKernelGGL(k_frame_candidates<false>, dim3(f.n_frames), dim3(64), lds, st, f.cands, f.cand_count, max_cand, f.min_distance, f.pre_xy, f.fin_xy,
-                           f.fin_count, f.work, f.work_count, f.S, reinterpret_cast<ProjRec*>(f.proj), nullptr);
+    hipLaunchKernelGGL(kernel, dim3(f.n_frames), dim3(64), lds, st, args...);
     return hipGetLastError();
 }
+hipError_t launch_frame_candidates(hipStream_t st, const DecodeStage& f) {
+    return launch_candidates(st, f, k_frame_candidates<false>, k_frame_candidates<true>, 1, f.cands, f.cand_count, f.max_cand, f.min_distance, f.pre_xy,
+                             f.fin_xy, f.fin_count, f.work, f.work_count, f.S, reinterpret_cast<ProjRec*>(f.proj), f.big_scratch);
+}
 hipError_t launch_merge_candidates(hipStream_t st, const DecodeStage& f) {
-    const uint32_t max_cand = f.max_cand;
-    const bool big = max_cand > kFrameCandLds;
-    if (f.windows < 2 || f.windows > 4 || !f.merged_count || f.plane_cand == 0 || max_cand > kMaxCandLimit ||
-        (uint64_t)f.windows * f.plane_cand < max_cand || (big && !f.big_scratch))
+    if (f.windows < 2 || f.windows > 4 || !f.merged_count || f.plane_cand == 0 || f.max_cand > kMaxCandLimit ||
+        (uint64_t)f.windows * f.plane_cand < f.max_cand)
         return hipErrorInvalidValue;
-    const size_t lds = big ? (size_t)max_cand * 2 + 16 : (size_t)max_cand * 22 + 16;
-    if (lds > 48 * 1024) {   // tables grown past the default
-        const hipError_t e = hipFuncSetAttribute(big ? reinterpret_cast<const void*>(k_merge_candidates<true>) : reinterpret_cast<const void*>(k_merge_candidates<false>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    if (big)
-        hipLaunchKernelGGL(k_merge_candidates<true>, dim3(f.n_frames), dim3(64), lds, st, f.cands, f.cand_count, f.n_frames, f.windows, f.plane_cand, max_cand,
-                           f.min_distance, f.pre_xy, f.fin_xy, f.fin_count, f.work, f.work_count, f.S, reinterpret_cast<ProjRec*>(f.proj), f.big_scratch,
-                           f.merged_count, f.err_flags);
-    else
-        hipLaunchKernelGGL(k_merge_candidates<false>, dim3(f.n_frames), dim3(64), lds, st, f.cands, f.cand_count, f.n_frames, f.windows, f.plane_cand, max_cand,
-                           f.min_distance, f.pre_xy, f.fin_xy, f.fin_count, f.work, f.work_count, f.S, reinterpret_cast<ProjRec*>(f.proj), nullptr,
-                           f.merged_count, f.err_flags);
-    return hipGetLastError();
+    return launch_candidates(st, f, k_merge_candidates<false>, k_merge_candidates<true>, 2, f.cands, f.cand_count, f.n_frames, f.windows, f.plane_cand,
+                             f.max_cand, f.min_distance, f.pre_xy, f.fin_xy, f.fin_count, f.work, f.work_count, f.S, reinterpret_cast<ProjRec*>(f.proj),
+                             f.big_scratch, f.merged_count, f.err_flags);
 }
 uint32_t frame_cand_lds_slots() { return kFrameCandLds; }
 

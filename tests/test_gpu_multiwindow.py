@@ -273,6 +273,75 @@ def test_kernel_flags_planes_and_sums_beyond_their_tables(dicts):
     assert out["merged_cap"] == 65536 and out["merged_count"].tolist() == [65540] and out["err_flags"] == 8 and out["fin_count"][0] == 0
 
 
+_ONE_PLANE = (("reg_2_kill_j", 2, 1024), ("reg_2_i_dies", 2, 1024), ("reg_64", 64, 1024), ("lds_65", 65, 1024), ("big_65", 65, 3073))
+
+
+def _one_plane_quads(name, c):
+    """c quads of candidates_util.clusters in walk order.  Two quads make one row, which either kills j or lets i die: both orders of
+    one close pair, the bigger quad first (j is killed) and second (i dies)."""
+    from tests import candidates_util as cu
+
+    rng = np.random.default_rng(4200 + c)
+    if c > 2:
+        return cu.clusters(c, rng, n_clusters=4), rng
+    q = cu.clusters(2, rng, n_clusters=1)
+    per = cu.perimeters(q.reshape(2, 8).astype(np.float32))
+    assert per[0] != per[1]
+    bigger_first = per[0] > per[1]
+    return (q if bigger_first == name.endswith("kill_j") else q[::-1]), rng
+
+
+@pytest.mark.parametrize("name,c,plane_cand", _ONE_PLANE, ids=[p[0] for p in _ONE_PLANE])
+def test_one_filled_plane_is_the_single_table_walk(dicts, oracle, name, c, plane_cand):
+    """k_merge_candidates and k_frame_candidates run one body: with K = 2 and every count of plane 1 at zero, every output of the
+    merge is what candidates_util.model expects of plane 0's table alone (projections: oracle.from_control_points), and equals
+    a3_debug_frame_candidates' on that table slot for slot, the 0xFF remainder included.  One frame of c quads and an empty one:
+    c = 2 and 64 take the register walk, 65 the LDS walk, 65 in planes of 3073 (merged capacity 6146, beyond kFrameCandLds) the
+    through-memory one."""
+    from tests import candidates_util as cu
+
+    md, S, n = 25.0, 49, 2
+    quads, rng = _one_plane_quads(name, c)
+    fr = cu.frame(name, quads, rng, plane_cand)
+    order, kept, census = cu.model(fr.records["xy"].reshape(-1, 4, 2), fr.records["start_key"], md)
+    srt = fr.records["xy"][order]
+    assert np.array_equal(srt.reshape(-1, 4, 2), quads)
+    kills_j = c - len(kept) - census["i_dies"]          # a dead quad was killed as some row's j, or died as a row's i
+    if c == 2:
+        assert (kills_j, census["i_dies"]) == ((1, 0) if name.endswith("kill_j") else (0, 1)), census
+    else:
+        assert kills_j >= 1 and census["i_dies"] >= 1 and len(kept) >= 2, census
+    ctx = _detector(dicts.new_from_named_dict("ARUCO_DEFAULT"))._context()
+    got = ctx.debug_merge_candidates(n, 2, plane_cand, [c, 0, 0, 0], fr.records, md, S=S)
+    m, total = got["merged_cap"], len(kept)
+    assert m == 2 * plane_cand and (m > LDS_SLOTS) == name.startswith("big") and got["err_flags"] == 0
+    assert got["merged_count"].tolist() == [c, 0] and got["fin_count"].tolist() == [total, 0] and got["work_count"] == total
+    pre, fin = got["pre_xy"].reshape(n, m, 8), got["fin_xy"].reshape(n, m, 8)
+    assert np.array_equal(pre[0, :c], srt) and (pre[0, c:] == 0xFFFF).all() and (pre[1] == 0xFFFF).all()
+    assert np.array_equal(fin[0, :total], srt[kept]) and (fin[0, total:] == 0xFFFF).all() and (fin[1] == 0xFFFF).all()
+    assert got["work"][:total].tolist() == list(range(total)) and (got["work"][total:] == 0xFFFFFFFF).all()
+    proj = got["proj"]
+    assert (proj[total:].view(np.uint8) == 0xFF).all()
+    to = np.array([0, 0, S, 0, S, S, 0, S], dtype=np.float32)
+    solved = 0
+    for pos, quad in enumerate(srt[kept]):
+        ok, _, inv = oracle.from_control_points(quad.astype(np.float32), to)
+        assert int(proj[pos]["ok"]) == int(ok), (pos, quad)
+        if ok:
+            assert np.array_equal(proj[pos]["inv"].view(np.uint32), inv.view(np.uint32)), (pos, quad)
+            solved += 1
+    assert solved >= 1
+    # the single-table kernel on plane 0's records, in tables of the merged size
+    one = ctx.debug_frame_candidates([c, 0], fr.records, m, md, S)
+    for key in ("pre_xy", "fin_xy"):
+        assert np.array_equal(got[key].reshape(n, m, 8), one[key]), key
+    assert np.array_equal(got["fin_count"], one["fin_count"]) and np.array_equal(got["work"], one["work"]) and one["work_count"] == total
+    assert np.array_equal(proj["ok"], one["proj"]["ok"])
+    solved_at = proj["ok"] == 1                         # (a failed solve leaves no defined inverse behind)
+    assert np.array_equal(proj["inv"][solved_at].view(np.uint32), one["proj"]["inv"][solved_at].view(np.uint32))
+    assert np.array_equal(proj[total:].view(np.uint8), one["proj"][total:].view(np.uint8))
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # 5. composition
 # ------------------------------------------------------------------------------------------------------------------
