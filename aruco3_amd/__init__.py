@@ -22,7 +22,7 @@ def __getattr__(name):
         from . import pose
 
         return getattr(pose, name)
-    if name in ("Board", "GridBoard", "BoardPose", "CharucoBoard", "CharucoPose", "BoardRecovery", "recover_markers"):
+    if name in ("Board", "GridBoard", "Board3D", "BoardPose", "CharucoBoard", "CharucoPose", "BoardRecovery", "recover_markers"):
         from . import board
 
         return getattr(board, name)

@@ -70,7 +70,7 @@ SYMBOLS = [
     "a3_find_nearest", "a3_calculate_tau", "a3_set_profiling", "a3_get_profile",
     "a3_contour_count", "a3_download_contours", "a3_detection_record_bytes", "a3_pack_detections",
     "a3_default_refine_config", "a3_set_corner_refinement", "a3_get_refined_corners", "a3_refine_corners",
-    "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose",
+    "a3_set_board", "a3_get_board_poses", "a3_estimate_board_pose", "a3_set_board3d",
     "a3_default_recover_config", "a3_set_board_recovery", "a3_get_board_recovery", "a3_get_recovered_counts", "a3_recover_markers",
     "a3_default_distortion", "a3_set_distortion", "a3_get_undistorted_corners", "a3_undistort_points",
     "a3_default_charuco_config", "a3_set_charuco", "a3_get_charuco_corners", "a3_get_charuco_poses", "a3_interpolate_charuco",
@@ -455,6 +455,9 @@ def load():
         L.a3_get_board_poses.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.a3_estimate_board_pose.restype = C.c_int
         L.a3_estimate_board_pose.argtypes = [vp, u32p, f32p, C.c_size_t, C.POINTER(Intrinsics), C.c_uint32, C.c_uint32, C.POINTER(BoardPoseRec)]
+    if hasattr(L, "a3_set_board3d"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack 3-D boards)
+        L.a3_set_board3d.restype = C.c_int
+        L.a3_set_board3d.argtypes = [vp, u32p, f32p, C.c_size_t]
     if hasattr(L, "a3_set_board_recovery"):      # (older builds loaded through A3_HIP_LIB for A/B runs lack board recovery)
         u64p, u8p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
         L.a3_default_recover_config.restype = C.c_int
@@ -816,6 +819,18 @@ class Context:
         if c.shape[0] != i.size:
             raise ValueError("set_board needs four corners per id")
         check(load().a3_set_board(self.handle, _p(i, C.c_uint32), _p(c, C.c_float), i.size), self.handle)
+
+    def set_board3d(self, ids=None, corners=None):
+        """a3_set_board3d: ids (n,), corners (n, 4, 3) float in board units; None / empty clears the board; applies to batches submitted
+        afterwards"""
+        if ids is None or len(ids) == 0:
+            check(load().a3_set_board3d(self.handle, None, None, 0), self.handle)
+            return
+        i = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+        c = _f32(corners, 12)
+        if c.shape[0] != i.size:
+            raise ValueError("set_board3d needs four corners per id")
+        check(load().a3_set_board3d(self.handle, _p(i, C.c_uint32), _p(c, C.c_float), i.size), self.handle)
 
     def board_poses(self) -> np.ndarray:
         """a3_get_board_poses: BOARD_POSE_DTYPE records of the last collected batch, one per frame"""

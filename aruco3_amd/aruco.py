@@ -238,6 +238,8 @@ class Detector:
         _one_view(reduction, rectification)
         if recovery is not None and board is None:
             raise ValueError("Detector(recovery=...) needs a board: recovery places rejected quads where the board says its markers are")
+        if recovery is not None and _is_board3d(board):
+            raise ValueError("Detector(recovery=...) needs a planar board: a homography places the missing markers, and a Board3D has none")
         self.config = config or DetectorConfig()
         self.dictionary = dictionary or ARDictionary.new_from_named_dict("ARUCO")
         self.device = device
@@ -490,8 +492,17 @@ def _is_charuco(board) -> bool:
     return isinstance(board, CharucoBoard)
 
 
+def _is_board3d(board) -> bool:
+    from .board import Board3D
+
+    return isinstance(board, Board3D)
+
+
 def _set_board(ctx: _lib.Context, board, charuco_config=None) -> None:
-    """a3_set_board (which clears the ChArUco setting), then a3_set_charuco for a CharucoBoard"""
+    """a3_set_board (which clears the ChArUco setting), then a3_set_charuco for a CharucoBoard; a3_set_board3d for a Board3D"""
+    if _is_board3d(board):
+        ctx.set_board3d(board.ids, board.corners)
+        return
     ctx.set_board(None if board is None else board.ids, None if board is None else board.corners)
     if _is_charuco(board):
         ctx.set_charuco(board.chessboard_corners, board.adjacent_ids, charuco_config)
@@ -575,6 +586,7 @@ class BatchQueue:
         self._threshold_windows = detector.threshold_windows   # (likewise)
         self._refine_on = [False] * depth
         self._keep = [None] * depth
+        self._pose_batch = [False] * depth
         self._gates = gates
         self._head = self._in_flight = self._submitted = 0
         self.last_stepping = None
@@ -586,7 +598,28 @@ class BatchQueue:
     def full(self) -> bool:
         return self._in_flight == len(self._ctxs)
 
-    def submit(self, images, out_cap: int = 0, pixel_format: Optional[str] = None) -> None:
+    def submit_with_board_pose(self, images, intrinsics=None, marker_size_mm: float = 1.0, out_cap: int = 0,
+                               pixel_format: Optional[str] = None) -> None:
+        """submit as a pose batch (a3_detect_batch_pose_submit): `collect_with_board_pose` returns what
+        Detector.detect_batch_with_board_pose would.  Needs the detector's board (planar or Board3D); no lens distortion is applied."""
+        if self._board is None:
+            raise ValueError("submit_with_board_pose needs Detector(board=...)")
+        intr = None
+        if intrinsics is not None:
+            ci = intrinsics
+            intr = _lib.Intrinsics(ci.image_width, ci.image_height, ci.focal_x, ci.focal_y, ci.principal_x, ci.principal_y)
+        self.submit(images, out_cap, pixel_format, _pose=(float(marker_size_mm), intr))
+
+    def collect_with_board_pose(self):
+        """the oldest batch in flight, which submit_with_board_pose handed over -> [(Detection, BoardPose)]"""
+        from .board import BoardPose
+
+        ctx = self._ctxs[self._head]
+        dets = self.collect()
+        boards = ctx.board_poses()
+        return [(d, BoardPose._from(boards[f])) for f, d in enumerate(dets)]
+
+    def submit(self, images, out_cap: int = 0, pixel_format: Optional[str] = None, _pose=None) -> None:
         if self.full:
             raise RuntimeError("BatchQueue is full: collect() the oldest batch first")
         depth = len(self._ctxs)
@@ -605,7 +638,11 @@ class BatchQueue:
         if self._submitted < depth and self._board is not None:   # (each context's first batch: the board stays set on it)
             _set_board(ctx, self._board, self._charuco_config)
         _apply_recovery(ctx, self._recovery, lambda: None)   # (the board is set: Detector refuses a recovery without one)
-        ctx.submit(ptr, mem, fmt, w, h, rs, fs, n, out_cap=out_cap or n * 64)
+        if _pose is not None:
+            ctx.submit_pose(ptr, mem, fmt, w, h, rs, fs, n, _pose[0], _pose[1], out_cap=out_cap or n * 64)
+        else:
+            ctx.submit(ptr, mem, fmt, w, h, rs, fs, n, out_cap=out_cap or n * 64)
+        self._pose_batch[k] = _pose is not None
         self._keep[k] = keep
         self._submitted += 1
         self._in_flight += 1
@@ -618,7 +655,7 @@ class BatchQueue:
         self._head = (self._head + 1) % len(self._ctxs)
         self._in_flight -= 1
         try:
-            markers, per = ctx.collect()
+            markers, per = ctx.collect_pose()[:2] if self._pose_batch[k] else ctx.collect()
         finally:
             self._keep[k] = None
         self.last_stepping = ctx.stats()["stepping"]

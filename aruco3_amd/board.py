@@ -4,7 +4,11 @@ Not part of the reference: an extension whose contract include/aruco3_hip.h stat
 corners lie on the plane z = 0 of the board's frame (x to the right, y up, corner 0 the top-left, as the per-marker IPPE solver's
 square).  `Detector(board=...)` hands the board to the device, and `Detector.detect_batch_with_board_pose` returns one `BoardPose`
 per frame, solved on the GPU from every board marker of that frame.  A `CharucoBoard` also yields its chessboard corners in every
-frame (Detection.charuco_ids / .charuco_corners) and, from `Detector.detect_batch_with_charuco_pose`, one `CharucoPose` per frame."""
+frame (Detection.charuco_ids / .charuco_corners) and, from `Detector.detect_batch_with_charuco_pose`, one `CharucoPose` per frame.
+
+A `Board3D` (a3_set_board3d) is a board whose markers are not coplanar -- a cube with a marker on each face, two grid boards at a right
+angle, the markers of a `MarkerMap`: `Detector(board=Board3D...)` returns its pose from `detect_batch_with_board_pose` as a planar
+board's, solved on the device from every marker of the frame whichever face it lies on."""
 from dataclasses import dataclass
 from typing import Sequence, Tuple
 
@@ -79,6 +83,110 @@ class GridBoard(Board):
         self.markers_x, self.markers_y = markers_x, markers_y
         self.marker_length, self.marker_separation = marker_length, marker_separation
         super().__init__(ids, corners)
+
+
+def check_marker_corners_3d(corners) -> None:
+    """raises ValueError unless the four (x, y, z) corners form a planar square (the test a3_set_board3d applies, in its wording).  The
+    order top-left, top-right, bottom-right, bottom-left is as seen from the side the marker is printed on: it defines that side."""
+    c = np.asarray(corners, dtype=np.float32).reshape(4, 3).astype(np.float64)
+    if not np.all(np.isfinite(c)):
+        raise ValueError("a corner is not finite")
+    e = np.roll(c, -1, axis=0) - c
+    dot = lambda a, b: (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+    s = math.sqrt(dot(e[0], e[0]))
+    if not s > 0:
+        raise ValueError("a marker has no size")
+    for k in range(4):
+        k1 = (k + 1) % 4
+        if abs(math.sqrt(dot(e[k], e[k])) - s) > SQUARE_TOL * s:
+            raise ValueError("a marker's sides differ (its corners must form a square)")
+        if abs(dot(e[k], e[k1])) > SQUARE_TOL * s * s:
+            raise ValueError("a marker's corners are not at right angles (they must form a square)")
+    g = c[2] - ((c[1] + c[3]) - c[0])
+    if math.sqrt(dot(g, g)) > SQUARE_TOL * s:
+        raise ValueError("a marker's corners do not lie in one plane (they must form a square)")
+
+
+class Board3D:
+    """`n` markers that need not be coplanar: ids (unique dictionary indices) and corners (n, 4, 3) in board units.  A marker's corners
+    are top-left, top-right, bottom-right, bottom-left as seen from the side it is printed on; that order defines the side, and its
+    outward normal is (c1 - c0) x (c0 - c3) normalised.  (a3_set_board3d; the ChArUco and recovery settings need a planar board.)"""
+
+    def __init__(self, ids: Sequence[int], corners):
+        self.ids = np.asarray(ids, dtype=np.uint32).reshape(-1)
+        self.corners = np.asarray(corners, dtype=np.float32).reshape(-1, 4, 3)
+        if self.corners.shape[0] != self.ids.size:
+            raise ValueError("a board needs four corners per id")
+        if not 1 <= self.ids.size <= _lib.BOARD_MAX_MARKERS:
+            raise ValueError(f"a board has 1 .. {_lib.BOARD_MAX_MARKERS} markers")
+        if np.unique(self.ids).size != self.ids.size:
+            raise ValueError("an id appears twice on the board")
+        for c in self.corners:
+            check_marker_corners_3d(c)
+
+    def __len__(self) -> int:
+        return int(self.ids.size)
+
+    def object_points(self, id_: int) -> np.ndarray:
+        """the (4, 3) board-frame corners of marker `id_`"""
+        k = int(np.nonzero(self.ids == id_)[0][0])
+        return self.corners[k].astype(np.float64)
+
+    def normals(self) -> np.ndarray:
+        """(n, 3) unit normals out of each marker's printed face"""
+        c = self.corners.astype(np.float64)
+        n = np.cross(c[:, 1] - c[:, 0], c[:, 0] - c[:, 3])
+        return n / np.linalg.norm(n, axis=1, keepdims=True)
+
+    # the cube's faces in id order: (outward normal, the face's "up")
+    CUBE_FACES = (((1, 0, 0), (0, 0, 1)), ((-1, 0, 0), (0, 0, 1)), ((0, 1, 0), (0, 0, 1)), ((0, -1, 0), (0, 0, 1)),
+                  ((0, 0, 1), (0, 1, 0)), ((0, 0, -1), (0, 1, 0)))
+
+    @classmethod
+    def cube(cls, side: float, marker_length: float, first_id: int = 0) -> "Board3D":
+        """A cube of edge `side` with its centre at the origin and one marker of side `marker_length` centred on each face: ids
+        first_id .. first_id + 5 on the faces +x, -x, +y, -y, +z, -z.  Seen from outside, a marker's up (corner 3 -> corner 0) is +z on
+        the four faces +x, -x, +y, -y and +y on the faces +z and -z; its right (corner 0 -> corner 1) is up x normal: +y, -y, -x, +x on
+        the first four faces, +x on +z, -x on -z."""
+        if not 0 < marker_length <= side:
+            raise ValueError("a cube board needs 0 < marker_length <= side")
+        h = marker_length / 2.0
+        corners = []
+        for n, u in cls.CUBE_FACES:
+            n, u = np.array(n, np.float64), np.array(u, np.float64)
+            r = np.cross(u, n)
+            c = n * (side / 2.0)
+            corners.append([c - h * r + h * u, c + h * r + h * u, c + h * r - h * u, c - h * r - h * u])
+        return cls([first_id + k for k in range(6)], corners)
+
+    @classmethod
+    def from_board(cls, board: "Board", R=None, t=None) -> "Board3D":
+        """a planar Board / GridBoard lifted into 3-D at the pose (R, t): corner (x, y) -> R (x, y, 0) + t.  R: a rotation (3, 3), None:
+        the identity; t: (3,), None: zero"""
+        R = np.eye(3) if R is None else np.asarray(R, dtype=np.float64).reshape(3, 3)
+        t = np.zeros(3) if t is None else np.asarray(t, dtype=np.float64).reshape(3)
+        if not (np.all(np.isfinite(R)) and np.all(np.isfinite(t))):
+            raise ValueError("from_board needs a finite R and t")
+        if not (np.abs(R @ R.T - np.eye(3)).max() <= 1e-6 and np.linalg.det(R) > 0):
+            raise ValueError("from_board needs a rotation matrix R (a reflection would turn the markers' printed sides over)")
+        c = board.corners.astype(np.float64).reshape(-1, 2)
+        X = np.concatenate([c, np.zeros((c.shape[0], 1))], axis=1) @ R.T + t
+        return cls(board.ids, X.reshape(-1, 4, 3))
+
+    @classmethod
+    def join(cls, boards: Sequence["Board3D"]) -> "Board3D":
+        """several Board3D, given in one common frame, as one board; their ids must be distinct"""
+        boards = list(boards)
+        if not boards:
+            raise ValueError("join needs at least one board")
+        return cls(np.concatenate([b.ids for b in boards]), np.concatenate([b.corners for b in boards], axis=0))
+
+    @classmethod
+    def from_marker_map(cls, marker_map) -> "Board3D":
+        """the markers of a MarkerMap (its ids and their corners_3d) as a board: detect_batch_with_board_pose then returns world -> camera
+        of every frame inside the detect call"""
+        ids = np.asarray(marker_map.ids).reshape(-1)
+        return cls(ids, np.stack([np.asarray(marker_map.corners_3d(int(i)), dtype=np.float64) for i in ids]))
 
 
 @dataclass

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "a3_board3d_check.h"
 #include "a3_common.h"
 #include "a3_format.h"
 #include "a3_internal.h"
@@ -237,8 +238,11 @@ struct a3_ctx {
     // a3_set_board: the board later batches capture (board_ids; board_slots: one BoardSlot record per marker) and its device tables
     // (id -> slot, slot records), brought up to date at the next submit when board_version moved -- never while a batch of this
     // context is in flight, so a batch keeps the board it was submitted with
+    // a3_set_board3d: the same, with Board3Slot records; board_kind says which records board_slots holds (kBoardSlotsPlanar /
+    // kBoardSlots3D), board_kind_up which the device tables hold since the last upload
     std::vector<uint32_t> board_ids;
     std::vector<uint8_t> board_slots;
+    uint32_t board_kind = kBoardSlotsPlanar, board_kind_up = kBoardSlotsPlanar;
     uint64_t board_version = 0, board_dev_version = 0;
     std::vector<uint16_t> board_slot_up;   // (the sources of the last upload, untouched until the next one)
     std::vector<uint8_t> board_slots_up;
@@ -466,7 +470,7 @@ const void* charuco_params_for(a3_ctx* ctx, const a3_charuco_config& cfg) {
 // the board's and the ChArUco setting's device tables (upload_board, upload_charuco); nc: the chessboard corners of the setting in force
 BoardTables board_tables(const a3_ctx* ctx, uint32_t nc) {
     return {.slot_of = ctx->board_slot_of.as<uint16_t>(), .n_codes = ctx->n_codes, .slots = ctx->board_slot_rec.p, .cxy = ctx->charuco_tab.as<float>(),
-            .adj = ctx->charuco_tab.as<uint32_t>() + 2 * (size_t)nc, .nc = nc};
+            .adj = ctx->charuco_tab.as<uint32_t>() + 2 * (size_t)nc, .nc = nc, .slot_kind = ctx->board_kind_up};
 }
 // The decode stage on the context's buffers as the last enqueue_front / layout_zero_block left them: what the product path
 // (enqueue_back) and the probe (a3_debug_kernel_time) share.  The frames, the table size, the grid and the taps are the caller's.
@@ -567,8 +571,10 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
             pose.corner_stride = (uint32_t)(sizeof(a3_marker) / 4); pose.mode = b.pose_has_intr ? 1 : 0;
         }
         A3_HIP(launch_pose(st, pose));
-        if (b.board)   // one board pose per frame from the same device-resident markers (and refined corners), no extra round trip
-            A3_HIP(launch_board_pose(st, {.m = m, .board = board, .intr = intr, .W = back_W, .H = back_H, .out = ctx->board_buf.as<a3_board_pose>()}));
+        if (b.board) {   // one board pose per frame from the same device-resident markers (and refined corners), no extra round trip
+            const BoardPoseLaunch bp{.m = m, .board = board, .intr = intr, .W = back_W, .H = back_H, .out = ctx->board_buf.as<a3_board_pose>()};
+            A3_HIP(board.slot_kind == kBoardSlots3D ? launch_board3d_pose(st, bp) : launch_board_pose(st, bp));
+        }
         if (b.charuco)   // one ChArUco pose per frame from the records just written, the starts as the board pose takes them
             A3_HIP(launch_charuco_pose(st, {.m = m, .board = board, .counts = charuco_counts, .recs = ctx->charuco_buf.as<a3_charuco_corner>(), .und = charuco_und,
                                             .intr = intr, .W = back_W, .H = back_H, .out = ctx->charuco_pose_buf.as<a3_charuco_pose>()}));
@@ -1406,6 +1412,7 @@ static int upload_board(a3_ctx* ctx) {
     ctx->board_slot_up.assign(std::max<size_t>(ctx->n_codes, 1), 0xFFFF);
     for (size_t i = 0; i < ctx->board_ids.size(); i++) ctx->board_slot_up[ctx->board_ids[i]] = (uint16_t)i;
     ctx->board_slots_up = ctx->board_slots;
+    ctx->board_kind_up = ctx->board_kind;
     A3_HIP(ctx->board_slot_of.ensure(ctx->board_slot_up.size() * 2));
     A3_HIP(ctx->board_slot_rec.ensure(ctx->board_slots_up.size()));
     A3_HIP(hipMemcpyAsync(ctx->board_slot_of.p, ctx->board_slot_up.data(), ctx->board_slot_up.size() * 2, hipMemcpyHostToDevice, ctx->stream));
@@ -2351,9 +2358,33 @@ int a3_set_board(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size
     }
     ctx->board_ids.assign(ids, ids + n);
     ctx->board_slots.swap(slots);
+    ctx->board_kind = kBoardSlotsPlanar;   // (replaces a 3-D board too)
     ctx->board_version++;
     if (n == 0) ctx->recover = a3_recover_config{};   // (recovery needs a board)
     ctx->charuco_nc = 0;   // (a ChArUco setting names ids of the board it was checked against)
+    ctx->charuco_tab_h.clear();
+    ctx->charuco_version++;
+    return A3_OK;
+}
+
+// the 3-D form: the same tables with Board3Slot records; the settings that need a plane go (a3_board3d_check.h refuses them from here on)
+int a3_set_board3d(a3_ctx* ctx, const uint32_t* ids, const float* corners_xyz, size_t n) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (const char* m = check_board3d_call(ctx->busy(), ids, corners_xyz, n)) return fail(ctx, A3_ERR_INVALID, m);
+    std::vector<uint8_t> seen(ctx->n_codes, 0);
+    std::vector<uint8_t> slots(n * board3d_slot_bytes());
+    for (size_t i = 0; i < n; i++) {
+        if (ids[i] >= ctx->n_codes) return fail(ctx, A3_ERR_INVALID, "a3_set_board3d: an id is not in the dictionary");
+        if (seen[ids[i]]++) return fail(ctx, A3_ERR_INVALID, "a3_set_board3d: an id appears twice on the board");
+        if (const char* m = check_board3d_marker(corners_xyz + 12 * i)) return fail(ctx, A3_ERR_INVALID, m);
+        board3d_slot_from(corners_xyz + 12 * i, slots.data() + i * board3d_slot_bytes());
+    }
+    ctx->board_ids.assign(ids, ids + n);
+    ctx->board_slots.swap(slots);
+    ctx->board_kind = n ? kBoardSlots3D : kBoardSlotsPlanar;
+    ctx->board_version++;
+    ctx->recover = a3_recover_config{};   // (recovery and ChArUco need a plane)
+    ctx->charuco_nc = 0;
     ctx->charuco_tab_h.clear();
     ctx->charuco_version++;
     return A3_OK;
@@ -2371,7 +2402,7 @@ int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corner
     if (!ctx) return A3_ERR_INVALID;
     if (!out || (n_markers && (!ids || !corners_xy))) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: null argument");
     if (ctx->batch.active || ctx->pending_trivial) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: a submitted batch has not been collected");
-    if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: no board is set (a3_set_board)");
+    if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: no board is set (a3_set_board, a3_set_board3d)");
     if (!intr && (image_width == 0 || image_height == 0)) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: empty image");
     if (n_markers > (1u << 20)) return fail(ctx, A3_ERR_INVALID, "a3_estimate_board_pose: more than 2^20 markers in one call");
     A3_HIP(hipSetDevice(ctx->device));
@@ -2390,8 +2421,9 @@ int a3_estimate_board_pose(a3_ctx* ctx, const uint32_t* ids, const float* corner
         A3_HIP(launch_undistort_corners(ctx->stream, nullptr, d_pts, nullptr, (uint32_t)(n_markers * 4), *intr, ctx->dist, und.at(s_und), und.at(s_und_res)));
         d_pts = und.at(s_und);
     }
-    A3_HIP(launch_board_pose(ctx->stream, {.m = {.ids = in.at(s_ids), .pts = d_pts, .n = (uint32_t)n_markers, .n_frames = 1u}, .board = board_tables(ctx, 0),
-                                           .intr = intr, .W = image_width, .H = image_height, .out = res.at(s_out)}));
+    const BoardPoseLaunch bp{.m = {.ids = in.at(s_ids), .pts = d_pts, .n = (uint32_t)n_markers, .n_frames = 1u}, .board = board_tables(ctx, 0),
+                             .intr = intr, .W = image_width, .H = image_height, .out = res.at(s_out)};
+    A3_HIP(bp.board.slot_kind == kBoardSlots3D ? launch_board3d_pose(ctx->stream, bp) : launch_board_pose(ctx->stream, bp));
     A3_HIP(res.download(s_out, out));
     A3_HIP(hipStreamSynchronize(ctx->stream));
     return A3_OK;
@@ -2436,6 +2468,7 @@ int a3_set_board_recovery(a3_ctx* ctx, const a3_recover_config* cfg) {
     if (ctx->busy()) return fail(ctx, A3_ERR_INVALID, "a3_set_board_recovery: a submitted batch has not been collected");
     if (!cfg || cfg->mode == 0) { ctx->recover = a3_recover_config{}; return A3_OK; }
     if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_set_board_recovery: no board is set (a3_set_board)");
+    if (const char* m = check_recovery_board_kind(ctx->board_kind == kBoardSlots3D, cfg->mode)) return fail(ctx, A3_ERR_INVALID, m);
     if (int rc = check_recover_config(ctx, *cfg, "a3_set_board_recovery")) return rc;
     ctx->recover = *cfg;
     return A3_OK;
@@ -2465,6 +2498,7 @@ int a3_recover_markers(a3_ctx* ctx, const uint32_t* detected_ids, const uint32_t
     *out_n = 0;
     if (ctx->busy()) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: a submitted batch has not been collected");
     if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: no board is set (a3_set_board)");
+    if (const char* m = check_recover_markers_board_kind(ctx->board_kind == kBoardSlots3D)) return fail(ctx, A3_ERR_INVALID, m);
     if (cfg->mode != 1) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: a3_recover_config.mode must be 1");
     if (int rc = check_recover_config(ctx, *cfg, "a3_recover_markers")) return rc;
     if (n_detected > (1u << 20)) return fail(ctx, A3_ERR_INVALID, "a3_recover_markers: more than 2^20 detected markers in one call");
@@ -2528,6 +2562,7 @@ int a3_set_charuco(a3_ctx* ctx, const float* corners_xy, const uint32_t* adjacen
     if (n_corners > A3_CHARUCO_MAX_CORNERS) return fail(ctx, A3_ERR_INVALID, "a3_set_charuco: more than A3_CHARUCO_MAX_CORNERS corners");
     if (!corners_xy || !adjacent_ids) return fail(ctx, A3_ERR_INVALID, "a3_set_charuco: null corners or adjacent ids");
     if (ctx->board_ids.empty()) return fail(ctx, A3_ERR_INVALID, "a3_set_charuco: no board is set (a3_set_board)");
+    if (const char* m = check_charuco_board_kind(ctx->board_kind == kBoardSlots3D, n_corners)) return fail(ctx, A3_ERR_INVALID, m);
     a3_charuco_config c;
     a3_default_charuco_config(&c);
     if (cfg) c = *cfg;

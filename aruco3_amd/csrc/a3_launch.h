@@ -4,7 +4,7 @@
 // whose members all default to null / 0, built at the call site with designated initialisers, so an optional input is a member the
 // caller leaves out.  Groups that travel together to several launchers are one struct, built once and passed on (ContourChunk,
 // DecodeStage, MarkerSrc, BoardTables).  The records the kernels keep to themselves (EntryState, FinState, ProjRec, DecodeOut, BoardSlot,
-// RefineParams, the solvers' scratch) stay opaque here: the host sees their sizes and void pointers.
+// Board3Slot, RefineParams, the solvers' scratch) stay opaque here: the host sees their sizes and void pointers.
 #pragma once
 
 #include "a3_common.h"
@@ -150,10 +150,12 @@ struct MarkerSrc {
     const uint32_t* ids = nullptr; const float* pts = nullptr; uint32_t n = 0, n_frames = 0;
 };
 // the board's device tables (a3_set_board: id -> slot, n_codes entries; BoardSlot records) and the ChArUco table (a3_set_charuco: nc
-// chessboard corners cxy, their adjacent ids adj), nc = 0 without one
+// chessboard corners cxy, their adjacent ids adj), nc = 0 without one.  slot_kind says which records `slots` holds: kBoardSlotsPlanar
+// (a3_set_board: BoardSlot, what every launcher but launch_board3d_pose reads) or kBoardSlots3D (a3_set_board3d: Board3Slot)
+constexpr uint32_t kBoardSlotsPlanar = 0, kBoardSlots3D = 1;
 struct BoardTables {
     const uint16_t* slot_of = nullptr; uint32_t n_codes = 0; const void* slots = nullptr; const float* cxy = nullptr; const uint32_t* adj = nullptr;
-    uint32_t nc = 0;
+    uint32_t nc = 0, slot_kind = kBoardSlotsPlanar;
 };
 
 // ---- k_refine.hip -------------------------------------------------------------------------------------------------------------------
@@ -189,6 +191,13 @@ struct BoardPoseLaunch {
     MarkerSrc m; BoardTables board; const a3_intrinsics* intr = nullptr; uint32_t W = 0, H = 0; a3_board_pose* out = nullptr;
 };
 hipError_t launch_board_pose(hipStream_t st, const BoardPoseLaunch& b);
+
+// ---- k_board3d.hip ------------------------------------------------------------------------------------------------------------------
+size_t board3d_slot_bytes();
+void board3d_slot_from(const float xyz[12], void* out);   // one Board3Slot record from a checked marker's corners (a3_board3d_check.h)
+// one a3_board_pose per frame of b.m from a 3-D board: b.board.slots holds Board3Slot records and b.board.slot_kind says so
+// (kBoardSlots3D; anything else: hipErrorInvalidValue, nothing is launched).  Every other member as launch_board_pose takes it.
+hipError_t launch_board3d_pose(hipStream_t st, const BoardPoseLaunch& b);
 
 // ---- k_recover.hip ------------------------------------------------------------------------------------------------------------------
 // Board-aided recovery (a3_set_board_recovery).  Stage 1, one workgroup per frame: the board markers no marker of the frame carries,

@@ -415,6 +415,39 @@ int  a3_get_board_poses(a3_ctx *ctx, a3_board_pose *dst, size_t cap_frames, size
 int  a3_estimate_board_pose(a3_ctx *ctx, const uint32_t *ids, const float *corners_xy, size_t n_markers, const a3_intrinsics *intr,
                             uint32_t image_width, uint32_t image_height, a3_board_pose *out);
 
+/* 3-D boards: markers that are not coplanar (a cube with a marker on each face, a tool with markers round its shaft, two grid boards
+ * at a right angle; OpenCV's cv::aruco::Board with arbitrary objPoints).  NOT in the reference: an opt-in extension, off by default;
+ * with no 3-D board set no launch, buffer, copy or result of a batch changes.  A 3-D board is n markers (1 <= n <=
+ * A3_BOARD_MAX_MARKERS), each a dictionary id (unique, < the context's n_codes) and its four corners X0..X3 (x, y, z) in board units,
+ * in the order top-left, top-right, bottom-right, bottom-left AS SEEN FROM THE SIDE THE MARKER IS PRINTED ON: the order defines that
+ * side.  a3_set_board3d accepts a marker when, in double precision on the floats, with e_k = X_(k+1) - X_k and s = |X1 - X0|: all
+ * twelve numbers are finite; s > 0; every | |e_k| - s | <= 1e-3 s; every |e_k . e_(k+1)| <= 1e-3 s^2; and |X2 - (X1 + X3 - X0)| <=
+ * 1e-3 s (the marker is planar and a parallelogram).  Each refusal is A3_ERR_INVALID with its own message.
+ * One board per context: a3_set_board3d replaces a planar board and a3_set_board replaces a 3-D one.  Setting a 3-D board clears the
+ * ChArUco setting (as a3_set_board does) and switches board recovery off (as a3_set_board with n == 0 does); while a 3-D board is set,
+ * a3_set_charuco (n_corners > 0), a3_set_board_recovery (mode != 0) and a3_recover_markers return A3_ERR_INVALID: they need a plane,
+ * whose homography places the chessboard and the missing markers.  a3_get_board_poses and a3_estimate_board_pose serve whichever
+ * board is set, with the same record and the same meaning of its status, counts, rms_px and alt_rms_px.
+ * With a 3-D board set, every a3_detect_batch_pose* batch solves one board pose per frame on the device (k_board3d_pose, where
+ * k_board_pose runs for a planar board).  The contract is a3_set_board's above, word for word -- the correspondences, the duplicate
+ * rule, the normalisation, the start marker (the largest image quad with finite IPPE poses; ties: the lowest slot), the LM loop and
+ * its constants, the 64-lane summation order and its xor butterfly, the choice between the two starts, rms_px / alt_rms_px,
+ * A3_BOARD_NONE -- except for these three items; tests/board3d_oracle.c a3o_board3d_pose restates it:
+ *   - slot data (float, host, once per board): d = X1 - X0; s = sqrtf((d.x d.x + d.y d.y) + d.z d.z); e_x = d / s; v = X0 - X3;
+ *     k = (v.x e_x.x + v.y e_x.y) + v.z e_x.z; v' = v - k e_x (per component); e_y = v' / sqrtf((v'.x^2 + v'.y^2) + v'.z^2);
+ *     e_z = e_x x e_y, each component a b - c d ((e_x.y e_y.z - e_x.z e_y.y), (e_x.z e_y.x - e_x.x e_y.z), (e_x.x e_y.y - e_x.y e_y.x));
+ *     c = 0.25f * ((X0 + X1) + (X2 + X3)) per component.  (e_x, e_y, e_z, c) is the frame the IPPE solver's square lives in: corner 0
+ *     at (-s/2, s/2, 0), x to the right, y up, z out of the printed face;
+ *   - start: with (R_m, t_m) one of the start marker's two IPPE poses (a3_estimate_pose_normalized at marker size s),
+ *     R_b[r][j] = (R_m[r][0] e_x[j] + R_m[r][1] e_y[j]) + R_m[r][2] e_z[j], t_b[r] = t_m[r] - ((R_b[r][0] c.x + R_b[r][1] c.y) +
+ *     R_b[r][2] c.z);
+ *   - residual and Jacobian: q = R X with q_x = (R00 X + R01 Y) + R02 Z (q_y, q_z likewise), p = q + t; from q on, the evaluation
+ *     above unchanged (J_u, J_v, the 21 + 6 + 2 sums, z' = max(pz, 1e-5)).
+ * A marker seen from behind its printed side cannot be detected, so no test on the facing of a detected marker is made. */
+/* applies to batches submitted after the call; n == 0 clears the board (of either kind).  corners_xyz: 12 floats per marker.
+ * A3_ERR_INVALID while a submitted batch has not been collected. */
+int  a3_set_board3d(a3_ctx *ctx, const uint32_t *ids, const float *corners_xyz, size_t n);
+
 /* Board-aided recovery of markers the decoder rejected.  NOT in the reference: an opt-in extension (OpenCV's refineDetectedMarkers),
  * off by default; with it off no launch, buffer, copy or result of a batch changes.  With a board set (a3_set_board, with or without
  * a3_set_charuco) and recovery on, every a3_detect_batch* batch runs one more stage on the device, right behind the marker gather and

@@ -667,6 +667,7 @@ extern "C" {
     pub fn a3_get_board_poses(ctx: *mut A3Ctx, dst: *mut A3BoardPose, cap_frames: usize, n: *mut usize) -> c_int;
     pub fn a3_estimate_board_pose(ctx: *mut A3Ctx, ids: *const u32, corners_xy: *const f32, n_markers: usize, intr: *const A3Intrinsics,
                                   image_width: u32, image_height: u32, out: *mut A3BoardPose) -> c_int;
+    pub fn a3_set_board3d(ctx: *mut A3Ctx, ids: *const u32, corners_xyz: *const f32, n: usize) -> c_int;
     pub fn a3_default_recover_config(ctx: *const A3Ctx, cfg: *mut A3RecoverConfig) -> c_int;
     pub fn a3_set_board_recovery(ctx: *mut A3Ctx, cfg: *const A3RecoverConfig) -> c_int;
     pub fn a3_get_board_recovery(ctx: *const A3Ctx, cfg: *mut A3RecoverConfig) -> c_int;
