@@ -123,7 +123,7 @@ struct Batch {
     int profiling = 0, profile_every = 1;   // a3_set_profiling in force
     // enqueue_front
     int prof = 0;                // the profiling level of this enqueue (the sampled threshold-only mode times one batch in profile_every)
-    bool need_grey = false;      // the threshold kernel writes the grey plane (taps, or a window above 15)
+    bool need_grey = false;      // the threshold kernel writes the grey plane (taps, or a radius above 31)
     bool grey_src = false;       // ... and the decode stage samples it (always, unless a3_debug_sample_frames keeps a tapped batch on the frames)
     uint32_t max_cand = 0, patch_cap = 0, marker_cap = 0, guess = 0;
     // enqueue_chain
@@ -220,7 +220,7 @@ struct a3_ctx {
     BatchScratch* head = nullptr; DeviceCounters* counters = nullptr; uint32_t* per_frame = nullptr; uint32_t* frame_cursor = nullptr; uint32_t* cand_count = nullptr;
     uint32_t last_marker_total = 0;   // sizes the speculative marker read-back of the next batch
     DevBuf tmp_a, tmp_b, tmp_c, tmp_d;
-    DevBuf hsum;                // row sums of the grey plane (u16): the separable threshold path only (windows above 15)
+    DevBuf hsum;                // row sums of the grey plane (u16): the separable threshold path only (radii 32..128)
     DevBuf wtab;                // triangle-resize weights of a full patch (sample -> mark_size), written once at a3_create
     DevBuf pose_buf;            // a3_detect_batch_pose: both poses of every marker of the last batch (kept for a3_pack_detections)
     // The side results (kSides, a3_readback.h), by kind: where the batch in flight has them on the device (ensure_back_buffers), the copy
@@ -727,7 +727,7 @@ int enqueue_front(a3_ctx* ctx, Batch& b, bool held) {
     const size_t npx = (size_t)W * H;
     const uint32_t kMaxCand = ctx->hints.max_cand;
     // the grey plane is materialised only for readers outside the fused path: Detection.grey (debug taps) and the generic
-    // threshold kernels (windows above 15); the decode stage otherwise samples the caller's frames directly
+    // threshold kernels (radii above 31); the decode stage otherwise samples the caller's frames directly
     const bool big_window = b.K == 1 && threshold_writes_grey_plane(b.radius);   // (a set of two or more holds fused-kernel radii only)
     const uint32_t np = b.planes;   // the planes of the front half: n, or n x K with several threshold windows
     const uint32_t merged_cand = b.K > 1 ? merged_cand_capacity(b.K, kMaxCand) : kMaxCand;

@@ -1,8 +1,9 @@
-// The one host description of a pixel format (an A3_FMT_* of include/aruco3_hip.h): whether the value names one, how many bytes a pixel
+// The one description of a pixel format (an A3_FMT_* of include/aruco3_hip.h): whether the value names one, how many bytes a pixel
 // takes in all stride arithmetic, where a packed 4:2:2 pixel keeps its luma, which widths the format has, and the fewest bytes a row and
 // a frame span.  Host arithmetic on the public header only -- no HIP, no context -- so a plain C++ program can run every function
 // (tests/format_checks.cpp); a3_api.hip, a3_reduce_check.h and a3_rectify_check.h ask here instead of spelling the formats out.
-// (The kernels are templates on the format and keep their own compile-time constants: k_threshold_k1.h's RawRow<FMT>.)
+// The kernels that are templates on the format take their bytes per pixel from format_bpp too (k_threshold_k1.h's RawRow<FMT>,
+// k_rectify), and their launchers name the formats in one place, a3_launch.h's with_format.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -4,28 +4,55 @@
 // whose members all default to null / 0, built at the call site with designated initialisers, so an optional input is a member the
 // caller leaves out.  Groups that travel together to several launchers are one struct, built once and passed on (ContourChunk,
 // DecodeStage, MarkerSrc, BoardTables).  The records the kernels keep to themselves (EntryState, FinState, ProjRec, DecodeOut, BoardSlot,
-// Board3Slot, RefineParams, the solvers' scratch) stay opaque here: the host sees their sizes and void pointers.
+// Board3Slot, RefineParams, the solvers' scratch) stay opaque here: the host sees their sizes and void pointers.  Ahead of the
+// declarations: the two helpers with which a launcher turns a run-time format or radius into its kernel's template argument.
 #pragma once
 
+#include <type_traits>
+
 #include "a3_common.h"
+#include "a3_format.h"
+#include "a3_threshold_plan.h"   // threshold_path, threshold_writes_grey_plane
 
 namespace a3 {
 
+// ---- a launcher's run-time argument as a template argument of its kernel -------------------------------------------------------------
+// f(std::integral_constant<int, A3_FMT_*>{}) for the format fmt names, and what f returns; hipErrorInvalidValue for a value that names
+// none (every public entry has refused such a value -- format_valid -- before a launcher runs).  The one place that lists the formats
+// for the kernels that are templates on them.
+template <class F>
+hipError_t with_format(int fmt, F&& f) {
+    switch (fmt) {
+        case A3_FMT_RGB8: return f(std::integral_constant<int, A3_FMT_RGB8>{});
+        case A3_FMT_RGBA8: return f(std::integral_constant<int, A3_FMT_RGBA8>{});
+        case A3_FMT_L8: return f(std::integral_constant<int, A3_FMT_L8>{});
+        case A3_FMT_BGRA8: return f(std::integral_constant<int, A3_FMT_BGRA8>{});
+        case A3_FMT_YUYV8: return f(std::integral_constant<int, A3_FMT_YUYV8>{});
+        case A3_FMT_UYVY8: return f(std::integral_constant<int, A3_FMT_UYVY8>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+// f(std::integral_constant<int, R>{}) for the R in LO..HI that radius equals; hipErrorInvalidValue outside.  Instantiates f for every R
+// of the range and for no other.
+template <int LO, int HI, class F>
+hipError_t with_radius(uint32_t radius, F&& f) {
+    if constexpr (LO > HI) return hipErrorInvalidValue;
+    else return radius == (uint32_t)LO ? f(std::integral_constant<int, LO>{}) : with_radius<LO + 1, HI>(radius, f);
+}
+
 // ---- k_threshold.hip (+ _r1, _r2, _big): grey + adaptive threshold ----------------------------------------------------------
-// n frames of W x H pixels -> the packed image `bits`.  grey (nullable): the grey plane is written too; the separable path (see
-// threshold_writes_grey_plane) needs it and hsum_tmp (one u16 per pixel), the fused kernels need neither.  fmt: any A3_FMT_*; for
-// A3_FMT_YUYV8 / A3_FMT_UYVY8 (2 bytes per pixel, W even) the grey level is the luma byte as it stands (a3_format.h).
+// n frames of W x H pixels -> the packed image `bits`.  grey (nullable): the grey plane is written too; the separable and the
+// brute-force path (a3_threshold_plan.h: threshold_writes_grey_plane) need it, the separable one hsum_tmp (one u16 per pixel) as well,
+// the fused kernels need neither.  fmt: any A3_FMT_*; for A3_FMT_YUYV8 / A3_FMT_UYVY8 (2 bytes per pixel, W even) the grey level is the
+// luma byte as it stands (a3_format.h).
 struct ThresholdLaunch {
     const uint8_t* pixels = nullptr; int fmt = 0; size_t row_stride = 0, frame_stride = 0; int W = 0, H = 0; uint32_t n = 0, radius = 0;
     uint8_t* grey = nullptr; uint64_t* bits = nullptr; uint16_t* hsum_tmp = nullptr;
 };
 hipError_t launch_grey_threshold(hipStream_t st, const ThresholdLaunch& t);
-// this window takes the separable path, which reads a grey plane and a plane of row sums: radius 0 and radii above 31
-bool threshold_writes_grey_plane(uint32_t radius);
 hipError_t launch_k1_r1(hipStream_t st, const ThresholdLaunch& t);   // radii 1..3
 hipError_t launch_k1_r2(hipStream_t st, const ThresholdLaunch& t);   // radii 4..6
-bool ring_kernel_applies(uint32_t radius);                           // radii 8..31, any frame layout
-hipError_t launch_ring_threshold(hipStream_t st, const ThresholdLaunch& t);
+hipError_t launch_ring_threshold(hipStream_t st, const ThresholdLaunch& t);   // radii 8..31, any frame layout
 
 // ---- k_contours.hip: the contour stage ----------------------------------------------------------------------------------------
 // the tile tables of a batch: tile_darts[frames * tiles] | tile_off[frames * tiles] | second-half counts of k_dart_count[frames *

@@ -188,8 +188,9 @@ hipError_t launch_refine_edges(hipStream_t st, const RefineLaunch& r) {
     const RefineParams* rp = reinterpret_cast<const RefineParams*>(r.params);
     const EdgeParams p{rp->win_half, rp->max_iterations, rp->cells, rp->relative_win, rp->min_shift};
     const int fmt = r.src.fmt;
-    const EdgePixel px = fmt == A3_FMT_RGB8 ? EdgePixel{3, 0} : fmt == A3_FMT_RGBA8 || fmt == A3_FMT_BGRA8 ? EdgePixel{4, 0}
-                       : fmt == A3_FMT_YUYV8 ? EdgePixel{2, 0} : fmt == A3_FMT_UYVY8 ? EdgePixel{2, 1} : EdgePixel{1, 0};   // (L8, the grey plane)
+    // (the library's own grey plane: one byte per pixel, which is its grey level; format_bpp has 0 for it on purpose)
+    const bool plane = fmt == kFmtGreyPlane;
+    const EdgePixel px{plane ? 1u : (uint32_t)format_bpp(fmt), plane ? 0u : (uint32_t)std::max(format_luma_offset(fmt), 0)};
     const dim3 grid(std::min<uint32_t>((quads + 3u) / 4u, 1024u));
 #define A3_EDGE_LAUNCH(kind) hipLaunchKernelGGL(k_refine_edges<kind>, grid, dim3(256), 0, st, r.src, px, r.W, r.H, r.markers, r.n_dev, r.pts, r.cell_px, r.n, p, r.out)
     if (fmt == A3_FMT_RGB8 || fmt == A3_FMT_RGBA8) A3_EDGE_LAUNCH(1);

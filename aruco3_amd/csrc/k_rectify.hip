@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void k_rectify(const uint8_t* __restrict__ src
     // stands -- what the L8 form makes of a plane of those luma bytes
     constexpr bool yuv422 = GREY == A3_FMT_YUYV8 || GREY == A3_FMT_UYVY8;
     static_assert(BPP != 2 || yuv422, "two bytes per pixel: packed 4:2:2, the grey form");
-    static_assert(!grey || BPP == (GREY == A3_FMT_RGB8 ? 3 : (GREY == A3_FMT_L8 ? 1 : (yuv422 ? 2 : 4))), "the grey form's BPP is its format's");
+    static_assert(!grey || BPP == (int)format_bpp(GREY), "the grey form's BPP is its format's");
     constexpr int C0 = GREY == A3_FMT_UYVY8 ? 1 : 0, C1 = yuv422 ? C0 + 1 : (grey && BPP == 4 ? 3 : BPP);   // the bytes of a pixel that are blended
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t i = blockIdx.y * kTileH + wave, j0 = blockIdx.x * kTileW + lane * kRun;
@@ -236,13 +236,12 @@ hipError_t launch_rectify(hipStream_t st, const RectifyLaunch& l) {
     return hipGetLastError();
 }
 
-template <int MODEL> static void launch_grey_form(hipStream_t st, dim3 grid, dim3 block, int fmt, const uint8_t* src, uint8_t* grey, const RectifyParams& p) {
-    if (fmt == A3_FMT_L8) hipLaunchKernelGGL((k_rectify<1, MODEL, A3_FMT_L8>), grid, block, 0, st, src, grey, p);
-    else if (fmt == A3_FMT_RGB8) hipLaunchKernelGGL((k_rectify<3, MODEL, A3_FMT_RGB8>), grid, block, 0, st, src, grey, p);
-    else if (fmt == A3_FMT_RGBA8) hipLaunchKernelGGL((k_rectify<4, MODEL, A3_FMT_RGBA8>), grid, block, 0, st, src, grey, p);
-    else if (fmt == A3_FMT_YUYV8) hipLaunchKernelGGL((k_rectify<2, MODEL, A3_FMT_YUYV8>), grid, block, 0, st, src, grey, p);
-    else if (fmt == A3_FMT_UYVY8) hipLaunchKernelGGL((k_rectify<2, MODEL, A3_FMT_UYVY8>), grid, block, 0, st, src, grey, p);
-    else hipLaunchKernelGGL((k_rectify<4, MODEL, A3_FMT_BGRA8>), grid, block, 0, st, src, grey, p);
+template <int MODEL> static hipError_t launch_grey_form(hipStream_t st, dim3 grid, dim3 block, int fmt, const uint8_t* src, uint8_t* grey, const RectifyParams& p) {
+    return with_format(fmt, [&](auto F) {
+        constexpr int FMT = decltype(F)::value;
+        hipLaunchKernelGGL((k_rectify<(int)format_bpp(FMT), MODEL, FMT>), grid, block, 0, st, src, grey, p);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_rectify_grey(hipStream_t st, const RectifyGreyLaunch& l) {
@@ -252,9 +251,8 @@ hipError_t launch_rectify_grey(hipStream_t st, const RectifyGreyLaunch& l) {
     uint32_t tx, ty, tz;
     rectify_grid(p.dw, p.dh, l.n_frames, &tx, &ty, &tz);
     const dim3 grid(tx, ty, tz), block(WAVE * kTileH);
-    if (r.distortion.model == A3_DIST_FISHEYE) launch_grey_form<A3_DIST_FISHEYE>(st, grid, block, l.fmt, l.src, l.grey, p);
-    else launch_grey_form<A3_DIST_RATIONAL>(st, grid, block, l.fmt, l.src, l.grey, p);
-    return hipGetLastError();
+    return r.distortion.model == A3_DIST_FISHEYE ? launch_grey_form<A3_DIST_FISHEYE>(st, grid, block, l.fmt, l.src, l.grey, p)
+                                                 : launch_grey_form<A3_DIST_RATIONAL>(st, grid, block, l.fmt, l.src, l.grey, p);
 }
 
 }  // namespace a3

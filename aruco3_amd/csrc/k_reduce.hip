@@ -29,7 +29,8 @@
 
 namespace a3 {
 
-constexpr int kRun = T_LPX;             // consecutive source pixels of a lane
+constexpr int kRun = 16;                // consecutive source pixels of a lane
+static_assert(kRun == T_LPX, "a lane's run is what the threshold kernels' loaders fetch (a3_threshold_plan.h)");
 constexpr int kWaveRun = WAVE * kRun;   // source pixels of a wave: one row segment
 constexpr int kTileH = 4;               // output rows of a workgroup
 constexpr int kChunk = 4;               // frames a workgroup walks
@@ -162,13 +163,8 @@ hipError_t launch_reduce_frames(hipStream_t st, const ReduceLaunch& l) {
     p.w = l.W / l.factor; p.h = l.H / l.factor; p.n_frames = l.n_frames;
     p.aligned = (reinterpret_cast<uintptr_t>(l.src) % 16 == 0) && (l.src_row % 16 == 0) && (l.src_frame % 16 == 0);
     p.src_row = l.src_row; p.src_frame = l.src_frame; p.dst_row = l.dst_row; p.dst_frame = l.dst_frame;
-    if (l.fmt == A3_FMT_L8) launch_reduce_fmt<A3_FMT_L8>(st, l.factor, l.src, l.dst, p);
-    else if (l.fmt == A3_FMT_RGB8) launch_reduce_fmt<A3_FMT_RGB8>(st, l.factor, l.src, l.dst, p);
-    else if (l.fmt == A3_FMT_RGBA8) launch_reduce_fmt<A3_FMT_RGBA8>(st, l.factor, l.src, l.dst, p);
-    else if (l.fmt == A3_FMT_YUYV8) launch_reduce_fmt<A3_FMT_YUYV8>(st, l.factor, l.src, l.dst, p);   // (packed 4:2:2: grey_row keeps the luma bytes)
-    else if (l.fmt == A3_FMT_UYVY8) launch_reduce_fmt<A3_FMT_UYVY8>(st, l.factor, l.src, l.dst, p);
-    else launch_reduce_fmt<A3_FMT_BGRA8>(st, l.factor, l.src, l.dst, p);
-    return hipGetLastError();
+    // (packed 4:2:2: grey_row keeps the luma bytes)
+    return with_format(l.fmt, [&](auto F) { launch_reduce_fmt<decltype(F)::value>(st, l.factor, l.src, l.dst, p); return hipGetLastError(); });
 }
 
 __global__ __launch_bounds__(256) void k_scale_markers(a3_marker* __restrict__ markers, const unsigned int* __restrict__ n_dev, uint32_t cap, uint32_t factor) {

@@ -26,7 +26,7 @@
 namespace a3 {
 
 // ---- generic radius: plain kernels (correct for any threshold_window and any alignment, not tuned): what is left for them are
-// windows above 15 and radius 0 (k_threshold_big.hip: ring_kernel_applies) ----
+// radii above 31 and radius 0 (a3_threshold_plan.h: threshold_path) ----
 // four consecutive pixels per thread: dword loads and one dword store where the row is 4-byte aligned, bytes otherwise
 template <int FMT>
 __global__ void k_grey_generic(const uint8_t* __restrict__ pixels, size_t row_stride, size_t frame_stride, int W, int H,
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64) void k_threshold_generic(const uint8_t* __restr
     if (threadIdx.x == 0) bits[(size_t)blockIdx.z * wpr * H + (size_t)y * wpr + blockIdx.x] = m;
 }
 
-// Windows above 7 on this path, separable: horizontal sums of the grey plane into a u16 plane (2R+1 <= 257 values of at most 255), then a
+// Radii 32..128, separable: horizontal sums of the grey plane into a u16 plane (2R+1 <= 257 values of at most 255), then a
 // vertical running sum per column with the compare.  Plain kernels (no register ring: (2R+1)^2 * 256 no longer fits 16 bits), but
 // the work per pixel no longer grows with the window's AREA as in k_threshold_generic.
 // k_hsum_generic: a workgroup covers 1024 columns of one row, four consecutive outputs per thread (a sliding sum: 2R + 4 byte reads for
@@ -161,39 +161,34 @@ __global__ __launch_bounds__(64) void k_vsum_threshold_generic(const uint8_t* __
 }
 
 // ---- host launcher -------------------------------------------------------------------------
-// threshold windows the register-resident kernel covers: radii 1..kFusedMaxRadius.  Beyond 7 the packed 16-bit arithmetic ends --
-// (2R+1)^2 * 256 no longer fits a u16 from R = 8 on (289 * 256 = 73 984), so window sums and the compare would need 32-bit lanes and a ring
-// of 2R+1 rows no register file holds.
-// Radii 8..31 have a fused kernel of their own (k_threshold_big.hip: the grey ring in registers + LDS, 32-bit sums); what is left for
-// the separable path -- which needs a grey plane and a plane of row sums -- is radius 0 and radii above 31.
-constexpr uint32_t kFusedMaxRadius = 7;
-bool threshold_writes_grey_plane(uint32_t radius) { return (radius == 0 || radius > kFusedMaxRadius) && !ring_kernel_applies(radius); }
-
+// one launcher per path of a3_threshold_plan.h's threshold_path; the fused kernels of radii 1..3 and 4..6 are instantiated in
+// translation units of their own (k_threshold_r1.hip, _r2.hip), the ring kernel's in k_threshold_big.hip
 hipError_t launch_grey_threshold(hipStream_t st, const ThresholdLaunch& t) {
-    switch (t.radius) {
-        case 1: case 2: case 3: return launch_k1_r1(st, t);
-        case 4: case 5: case 6: return launch_k1_r2(st, t);
-        case 7: return launch_k1<7>(st, t);
-        default: break;
+    const int W = t.W, H = t.H, radius = (int)t.radius; const uint32_t n = t.n;
+    auto grey_plane = [&] {   // what the two plain paths read
+        return with_format(t.fmt, [&](auto F) {
+            hipLaunchKernelGGL(k_grey_generic<decltype(F)::value>, dim3((W + 255) / 256, H, n), dim3(64), 0, st, t.pixels, t.row_stride, t.frame_stride, W, H, t.grey);
+            return hipGetLastError();
+        });
+    };
+    switch (threshold_path(t.radius)) {
+        case ThresholdPath::K1: return t.radius <= 3 ? launch_k1_r1(st, t) : t.radius <= 6 ? launch_k1_r2(st, t) : launch_k1<7>(st, t);
+        case ThresholdPath::Ring: return launch_ring_threshold(st, t);
+        case ThresholdPath::Separable:   // row sums (<= 257 * 255 fit a u16), then a running column sum with the compare
+            if (t.hsum_tmp) {
+                if (hipError_t e = grey_plane(); e != hipSuccess) return e;
+                hipLaunchKernelGGL(k_hsum_generic, dim3((W + kHsumCols - 1) / kHsumCols, H, n), dim3(256), kHsumCols + 2 * ((t.radius + 3) & ~3u) + 16, st, t.grey, W, H, radius, t.hsum_tmp);
+                hipLaunchKernelGGL(k_vsum_threshold_generic, dim3(words_per_row((uint32_t)W), (H + kVsumRows - 1) / kVsumRows, n), dim3(64), 0, st, t.grey, t.hsum_tmp,
+                                   W, H, radius, t.bits);
+                return hipGetLastError();
+            }
+            [[fallthrough]];   // no plane of row sums: brute force, as ever
+        case ThresholdPath::Brute:
+            if (hipError_t e = grey_plane(); e != hipSuccess) return e;
+            hipLaunchKernelGGL(k_threshold_generic, dim3(words_per_row((uint32_t)W), H, n), dim3(64), 0, st, t.grey, W, H, radius, t.bits);
+            return hipGetLastError();
     }
-    if (ring_kernel_applies(t.radius)) return launch_ring_threshold(st, t);
-    const uint8_t* const pixels = t.pixels; uint8_t* const grey = t.grey; uint64_t* const bits = t.bits; uint16_t* const hsum_tmp = t.hsum_tmp;
-    const int fmt = t.fmt, W = t.W, H = t.H; const size_t row_stride = t.row_stride, frame_stride = t.frame_stride; const uint32_t n = t.n, radius = t.radius;
-    dim3 block(64), gridg((W + 255) / 256, H, n), grid1(words_per_row((uint32_t)W), H, n);
-    if (fmt == A3_FMT_RGB8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_RGB8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
-    else if (fmt == A3_FMT_RGBA8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_RGBA8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
-    else if (fmt == A3_FMT_BGRA8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_BGRA8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
-    else if (fmt == A3_FMT_YUYV8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_YUYV8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
-    else if (fmt == A3_FMT_UYVY8) hipLaunchKernelGGL(k_grey_generic<A3_FMT_UYVY8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
-    else hipLaunchKernelGGL(k_grey_generic<A3_FMT_L8>, gridg, block, 0, st, pixels, row_stride, frame_stride, W, H, grey);
-    if (hsum_tmp && radius <= 128u) {   // separable: row sums (<= 257 * 255 fit a u16), then a running column sum with the compare
-        hipLaunchKernelGGL(k_hsum_generic, dim3((W + kHsumCols - 1) / kHsumCols, H, n), dim3(256), kHsumCols + 2 * ((radius + 3) & ~3u) + 16, st, grey, W, H, (int)radius, hsum_tmp);
-        hipLaunchKernelGGL(k_vsum_threshold_generic, dim3(words_per_row((uint32_t)W), (H + kVsumRows - 1) / kVsumRows, n), dim3(64), 0, st, grey, hsum_tmp,
-                           W, H, (int)radius, bits);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_threshold_generic, grid1, block, 0, st, grey, W, H, (int)radius, bits);
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 }  // namespace a3

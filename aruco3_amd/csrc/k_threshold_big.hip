@@ -62,22 +62,8 @@ __device__ __forceinline__ void slide_chain(const uint32_t* E, uint32_t* S) {   
     }
 }
 
-// The ring's split.  RA rows (the youngest) in registers, NB = 2R + 1 - RA in LDS.  Two waves per SIMD -- eight per CU -- are worth a
-// factor 1.8 (measured: 0.41 against 0.72 ms for radius 16), and eight waves fit a CU's LDS with at most 19 KB of ring each: up to radius
-// 18 the split is R | R + 1; beyond, as long as the registers hold the rest without scratch (115 + 4 RA VGPRs for RGB with vector loads,
-// 12 more for four-byte pixels, 25 fewer for L8, ~40 more with per-pixel loads), the LDS part stays at 19 rows and the register part
-// grows (1.26-1.45 x of window 7); the largest radii fall back to R | R + 1 and one wave per SIMD (2.4-2.6 x).
-constexpr int kRingLdsRows8 = 19;
-constexpr int ring_reg_rows(int R, bool fast, int fmt) {   // (the limits: the largest radius whose instantiation needs no scratch)
-    const bool yuv422 = fmt == A3_FMT_YUYV8 || fmt == A3_FMT_UYVY8;   // 8 raw dwords per row in flight: between L8's 4 and RGB8's 12
-    const int last8 = !fast ? 19 : (fmt == A3_FMT_L8 ? 28 : (yuv422 ? 27 : (fmt == A3_FMT_RGB8 ? 26 : 24)));
-    return R + 1 <= kRingLdsRows8 ? R : (R <= last8 ? 2 * R + 1 - kRingLdsRows8 : R);
-}
-// apron lanes on either side of a wave and the output columns left to it
-constexpr int ring_halo_lanes(int R) { return R > 15 ? 2 : 1; }
-constexpr int ring_out_cols(int R) { return (64 - 2 * ring_halo_lanes(R)) * T_LPX; }
-
-// grid: 8 * ceil(frames / 8) * strips_x * strips_y workgroups of one wave; dynamic LDS: (R + 1) KB of ring + (flush_rows + T_PF) * 128 B
+// (The ring's split into RA rows in registers and NB in LDS, the apron lanes and the waves per SIMD: a3_threshold_plan.h.)
+// grid: 8 * ceil(frames / 8) * strips_x * strips_y workgroups of one wave; dynamic LDS: NB KB of ring + (flush_rows + T_PF) * 128 B
 template <int FMT, int R, bool FAST>
 __global__ __launch_bounds__(64, 2 * R + 1 - ring_reg_rows(R, FAST, FMT) <= kRingLdsRows8 ? 2 : 1) void k_grey_threshold_ring(const uint8_t* __restrict__ pixels, size_t row_stride, size_t frame_stride, int W, int H,
                                                                 int rows_per_wave, int strips_y, int n_frames, uint8_t* __restrict__ grey,
@@ -95,7 +81,7 @@ __global__ __launch_bounds__(64, 2 * R + 1 - ring_reg_rows(R, FAST, FMT) <= kRin
     uint4* s_ring = reinterpret_cast<uint4*>(s_raw);                                   // [NB][64]
     uint16_t* s_out = reinterpret_cast<uint16_t*>(s_raw + (size_t)NB * 1024);          // [flush_rows + PF][64]
     const int lane = threadIdx.x;
-    // every strip of a frame on one XCD, top to bottom (k_grey_threshold7's map_by_frame)
+    // every strip of a frame on one XCD, top to bottom (the rule of k_threshold_k1.h's strip_of)
     const int xcd = blockIdx.x & 7, kb = blockIdx.x >> 3;
     const int strips_x = (W + OUT - 1) / OUT, per_frame = strips_x * strips_y, idx = kb % per_frame;
     const int f = (kb / per_frame) * 8 + xcd;
@@ -247,82 +233,33 @@ __global__ __launch_bounds__(64, 2 * R + 1 - ring_reg_rows(R, FAST, FMT) <= kRin
 
 template <int R>
 hipError_t launch_ring(hipStream_t st, const ThresholdLaunch& t) {
-    const uint8_t* const pixels = t.pixels; uint8_t* const grey = t.grey; uint64_t* const bits = t.bits;
-    const int fmt = t.fmt, W = t.W, H = t.H; const size_t row_stride = t.row_stride, frame_stride = t.frame_stride; const uint32_t n = t.n;
-    constexpr int OUT = ring_out_cols(R);
-    uint8_t* bin = reinterpret_cast<uint8_t*>(bits);
+    const int W = t.W, H = t.H;
     if (W % 64 != 0) {  // packed rows end in padding bits that no strip writes
-        hipError_t e = hipMemsetAsync(bits, 0, (size_t)words_per_row((uint32_t)W) * 8 * H * n, st);
+        hipError_t e = hipMemsetAsync(t.bits, 0, (size_t)words_per_row((uint32_t)W) * 8 * H * t.n, st);
         if (e != hipSuccess) return e;
     }
-    const int aligned_in = ((uintptr_t)pixels % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0);
-    const bool fast = aligned_in && W % 16 == 0 && (uintptr_t)grey % 16 == 0;   // (as in launch_k1)
-    // waves per CU: two per SIMD while the ring's LDS part is at most 19 KB per wave (then at least 4 parked rows each), else one
-    const int NB = 2 * R + 1 - ring_reg_rows(R, fast, fmt), WPC = NB <= kRingLdsRows8 ? 8 : 4;
-    // strips: K1's model (time ~ rounds x (rows per strip + 2R))
-    const int strips_x = (W + OUT - 1) / OUT;
-    const long long slots = 256LL * WPC, cols = (long long)strips_x * n;
-    int best_sy = 1; double best_cost = 1e300;
-    for (int sy = 1; sy <= std::max(1, H / 16); sy++) {
-        const int rows = (H + sy - 1) / sy;
-        const long long waves = cols * ((H + rows - 1) / rows);
-        const double cost = (double)((waves + slots - 1) / slots) * (rows + 2 * R);
-        if (cost < best_cost - 1e-9) { best_cost = cost; best_sy = sy; }
-    }
-    const int rows_per_wave = (H + best_sy - 1) / best_sy;
-    const int strips_y = (H + rows_per_wave - 1) / rows_per_wave;
-    const int per_wave = (160 * 1024) / WPC - 64;   // (the allocation granule)
-    const int flush_rows = std::max(1, std::min({128, rows_per_wave, (per_wave - NB * 1024) / 128 - T_PF}));
-    const size_t lds_bytes = (size_t)NB * 1024 + (size_t)(flush_rows + T_PF) * 128;
-    if ((per_wave - NB * 1024) / 128 - T_PF < 1) return hipErrorInvalidValue;   // (cannot happen: 19 KB + 4 rows fit an eighth, 32 KB + 60 rows a quarter)
-    dim3 grid(8 * (((int)n + 7) / 8) * strips_x * strips_y), block(64);
-#define A3_LAUNCH_RING(F)                                                                                                              \
-    {                                                                                                                                  \
-        if (fast) hipLaunchKernelGGL((k_grey_threshold_ring<F, R, true>), grid, block, lds_bytes, st, pixels, row_stride, frame_stride, W, H, rows_per_wave, strips_y, \
-                                     (int)n, grey, bin, flush_rows, aligned_in);                                                       \
-        else hipLaunchKernelGGL((k_grey_threshold_ring<F, R, false>), grid, block, lds_bytes, st, pixels, row_stride, frame_stride, W, H, rows_per_wave, strips_y,    \
-                                (int)n, grey, bin, flush_rows, aligned_in);                                                            \
-    }
-    if (fmt == A3_FMT_RGB8) A3_LAUNCH_RING(A3_FMT_RGB8)
-    else if (fmt == A3_FMT_RGBA8) A3_LAUNCH_RING(A3_FMT_RGBA8)
-    else if (fmt == A3_FMT_BGRA8) A3_LAUNCH_RING(A3_FMT_BGRA8)
-    else if (fmt == A3_FMT_YUYV8) A3_LAUNCH_RING(A3_FMT_YUYV8)
-    else if (fmt == A3_FMT_UYVY8) A3_LAUNCH_RING(A3_FMT_UYVY8)
-    else A3_LAUNCH_RING(A3_FMT_L8)
-#undef A3_LAUNCH_RING
-    return hipGetLastError();
+    const int aligned_in = ((uintptr_t)t.pixels % 16 == 0) && (t.row_stride % 16 == 0) && (t.frame_stride % 16 == 0);
+    const bool fast = aligned_in && W % 16 == 0 && (uintptr_t)t.grey % 16 == 0;   // (as in launch_k1)
+    const RingPlan p = plan_ring(W, H, t.n, R, t.fmt, fast);
+    if (p.park_room < 1) return hipErrorInvalidValue;   // (cannot happen: a3_threshold_plan.h)
+    // (The kernel's row-by-row stores for flush_rows <= 0 are not launched: plan_ring's flush_rows is at least 1.  Taking them out, and
+    // moving the kernel to k_threshold_k1.h's strip_of and flush_parked, was built and timed: bit-exact and 2-3 % shorter with vector
+    // loads, but the compiler then allocated five per-pixel-load instantiations without AGPRs (radius 22 RGBA8 / BGRA8, 26 RGB8, 28
+    // YUYV8 / UYVY8) and the two that were timed ran 6-11 % longer.  The kernel's body and arguments stay as they were.)
+    const dim3 grid(strip_grid(p.s, t.n)), block(64);
+    return with_format(t.fmt, [&](auto F) {
+        auto launch = [&](auto FAST) {
+            hipLaunchKernelGGL((k_grey_threshold_ring<decltype(F)::value, R, decltype(FAST)::value>), grid, block, p.lds_bytes, st, t.pixels, t.row_stride,
+                               t.frame_stride, W, H, p.s.rows_per_wave, p.s.strips_y, (int)t.n, t.grey, reinterpret_cast<uint8_t*>(t.bits), p.flush_rows,
+                               aligned_in);
+            return hipGetLastError();
+        };
+        return fast ? launch(std::true_type{}) : launch(std::false_type{});
+    });
 }
 
-bool ring_kernel_applies(uint32_t radius) { return radius >= 8 && radius <= 31; }
-
 hipError_t launch_ring_threshold(hipStream_t st, const ThresholdLaunch& t) {
-    switch (t.radius) {
-        case 8: return launch_ring<8>(st, t);
-        case 9: return launch_ring<9>(st, t);
-        case 10: return launch_ring<10>(st, t);
-        case 11: return launch_ring<11>(st, t);
-        case 12: return launch_ring<12>(st, t);
-        case 13: return launch_ring<13>(st, t);
-        case 14: return launch_ring<14>(st, t);
-        case 15: return launch_ring<15>(st, t);
-        case 16: return launch_ring<16>(st, t);
-        case 17: return launch_ring<17>(st, t);
-        case 18: return launch_ring<18>(st, t);
-        case 19: return launch_ring<19>(st, t);
-        case 20: return launch_ring<20>(st, t);
-        case 21: return launch_ring<21>(st, t);
-        case 22: return launch_ring<22>(st, t);
-        case 23: return launch_ring<23>(st, t);
-        case 24: return launch_ring<24>(st, t);
-        case 25: return launch_ring<25>(st, t);
-        case 26: return launch_ring<26>(st, t);
-        case 27: return launch_ring<27>(st, t);
-        case 28: return launch_ring<28>(st, t);
-        case 29: return launch_ring<29>(st, t);
-        case 30: return launch_ring<30>(st, t);
-        case 31: return launch_ring<31>(st, t);
-        default: return hipErrorInvalidValue;
-    }
+    return with_radius<8, 31>(t.radius, [&](auto R) { return launch_ring<decltype(R)::value>(st, t); });
 }
 
 }  // namespace a3

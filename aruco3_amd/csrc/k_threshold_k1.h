@@ -3,24 +3,17 @@
 // only so that the instantiations compile in parallel.  Everything about the kernel is described in k_threshold.hip's header.
 #pragma once
 #include <algorithm>
-#include <utility>
+#include <type_traits>
 
 #include "a3_common.h"
 #include "a3_launch.h"
+#include "a3_threshold_plan.h"   // T_LPX, T_PF, T_WAVES, T_OUT and the launch plans
 
 namespace a3 {
 
 constexpr int T_R = 7;               // fast path radius (threshold_window = 7)
-// Pixels per lane and row: 256 VGPRs (the ring of row sums alone is 120), two waves per SIMD.  8 pixels per lane (144 VGPRs, three
-// waves per SIMD) was built to see whether occupancy was what kept the kernel (stores off) 0.025 ms above the bare reads of
-// tools/micro/readbench.hip.  It was not: 0.293 ms against 0.286 with stores off, 0.343 against 0.324 with them (docs/HISTORY.md
-// A.1); the difference to the microbenchmark is the 5 % of halo rows and the feeder lanes.
-constexpr int T_LPX = 16;
-constexpr int T_PF = 3;              // rows of loads in flight per lane
-constexpr int T_WAVES = 2;           // waves per SIMD (__launch_bounds__); every resident wave's LDS parking area must fit the CU
 constexpr int T_NG = T_LPX / 4;      // grey dwords per lane and row
 constexpr int T_NP = T_LPX / 2;      // packed pairs per lane and row: pixel j with pixel j + T_NP
-constexpr int T_OUT = 62 * T_LPX;    // output columns per wave (lanes 0 and 63 only feed their neighbours)
 typedef uint16_t out_bits_t;         // a lane's result bits of one row
 
 // Sums of packed u16 pairs: both halves at once with the plain 32-bit add / subtract.  No half ever carries into or borrows from the
@@ -31,7 +24,7 @@ __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) { return a + 
 __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) { return a - b; }
 
 template <int FMT> struct RawRow {
-    static constexpr int BPP = FMT == A3_FMT_RGB8 ? 3 : (FMT == A3_FMT_L8 ? 1 : ((FMT == A3_FMT_YUYV8 || FMT == A3_FMT_UYVY8) ? 2 : 4));
+    static constexpr int BPP = (int)format_bpp(FMT);
     static constexpr int NDW = T_LPX * BPP / 4;
     uint32_t d[NDW];
 };
@@ -202,6 +195,31 @@ __device__ __forceinline__ void row_sums(const uint32_t g[T_NG], uint32_t Hp[T_N
                            byte_pair(J + 8 - R, D[(J + 8 - R + T_NP) >> 2], D[(J + 8 - R) >> 2]));
 }
 
+// ---- the strip of a workgroup and the burst of parked rows (k_grey_threshold_ring in k_threshold_big.hip follows the same two rules in
+// its own body, which stays as it was timed: see launch_ring) ----
+// XCD-aware block -> strip mapping: the workgroup's frame, column strip and row strip; false past the last frame.  Workgroups are dealt
+// round-robin over the 8 XCDs (b and b+8 share one), each with its own L2.  Vertically adjacent strips of one column share 2R rows of
+// input and the column strips of a frame the lines of the packed image they both touch, so every strip of a frame is given to ONE XCD,
+// column by column and top to bottom: the shared rows are then L2 hits instead of a second trip over the fabric (~3 % against a
+// (frame, column) pair per XCD).  Placement only affects speed; any mapping is correct.  OUT: output columns per wave.
+template <int OUT>
+__device__ __forceinline__ bool strip_of(int W, int strips_y, int n_frames, int& f, int& sx, int& sy) {
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    const int strips_x = (W + OUT - 1) / OUT, per_frame = strips_x * strips_y, idx = k % per_frame;
+    f = (k / per_frame) * 8 + xcd;
+    sx = idx / strips_y; sy = idx % strips_y;
+    return f < n_frames;
+}
+// The result bits per lane and row are parked in LDS (s_out: rows of 64 lanes) and leave in bursts: 66 MB of small stores dribbling
+// into a saturating read stream cost K1 ~0.07 ms (HBM bus turnarounds: tools/micro/readbench.hip); the same bytes in a few large
+// bursts per wave cost about half of that.  Here the parked rows [0, nb) (row q is image row yb0 + dir * q) leave for the packed image,
+// one 2-byte store per lane and row (16-byte stores, eight rows per instruction, were bit-exact and 2-3 % slower in round 5).
+// bout: the frame's packed image, bpr bytes per row; xb: the byte of a row the lane's bits start at.
+__device__ __forceinline__ void flush_parked(const out_bits_t* s_out, int lane, bool owner, uint8_t* bout, size_t bpr, int xb, int nb, int yb0, int dir) {
+    if (owner)
+        for (int q = 0; q < nb; q++) *reinterpret_cast<out_bits_t*>(bout + (size_t)(yb0 + dir * q) * bpr + xb) = s_out[q * 64 + lane];
+}
+
 // One wave walks down a strip: lane l owns columns xs - T_LPX + T_LPX l .. + T_LPX - 1.  Per image row it converts its pixels
 // to grey, forms their 15-wide horizontal sums (row_sums) and slides a 15-row vertical window over those row sums, all as
 // packed u16 pairs (pixel j with pixel j + T_NP); the row 7 iterations old is then thresholded: sum < (L+1)*area.
@@ -213,33 +231,17 @@ __device__ __forceinline__ void row_sums(const uint32_t g[T_NG], uint32_t Hp[T_N
 // (row - NR) % NRING (for the default radius NR = NRING = 15: the very slot the new row overwrites).
 template <int FMT, bool FAST, int R = T_R>
 __global__ __launch_bounds__(64, T_WAVES) void k_grey_threshold7(const uint8_t* __restrict__ pixels, size_t row_stride, size_t frame_stride,
-                                                        int W, int H, int rows_per_wave, int strips_y, int n_pairs,
+                                                        int W, int H, int rows_per_wave, int strips_y, int n_frames,
                                                         uint8_t* __restrict__ grey,
-                                                        uint8_t* __restrict__ bits, int aligned_in, int aligned_out, int map_by_frame,
-                                                        int flush_rows) {
-    // flush_rows > 0: the result bits per lane and row are parked in LDS (flush_rows + 15 rows of 64 lanes) and leave in bursts
-    // of flush_rows rows.  66 MB of small stores dribbling into a saturating read stream cost K1 ~0.07 ms (HBM bus turnarounds:
-    // tools/micro/readbench.hip); the same bytes in a few large bursts per wave cost about half of that.
-    constexpr int NR = 2 * R + 1, NRING = ((NR + T_PF - 1) / T_PF) * T_PF, UNROLL = NRING;
+                                                        uint8_t* __restrict__ bits, int aligned_in, int aligned_out, int flush_rows) {
+    // the result bits are parked in LDS (flush_rows + UNROLL rows of 64 lanes) and leave in bursts of flush_rows (>= 1) rows
+    constexpr int NR = 2 * R + 1, NRING = k1_unroll(R), UNROLL = NRING;
     extern __shared__ uint8_t s_out_raw[];
     out_bits_t* s_out = reinterpret_cast<out_bits_t*>(s_out_raw);
     int n_buf = 0, y_buf0 = 0;
     const int lane = threadIdx.x;
-    // XCD-aware block -> strip mapping.  Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one), each
-    // with its own L2.  Vertically adjacent strips of one column share 14 rows of input, so all strips of a
-    // (frame, column) pair are given to ONE XCD, in top-to-bottom order: the shared rows are then L2 hits instead of a
-    // second trip over the fabric.  (Placement only affects speed; any mapping is correct.)
-    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int strips_x = (W + T_OUT - 1) / T_OUT;
-    int pair, sy;
-    if (map_by_frame) {   // every strip of a frame on one XCD: the column strips share the lines they both touch
-        const int per_frame = strips_x * strips_y, idx = k % per_frame;
-        pair = ((k / per_frame) * 8 + xcd) * strips_x + idx / strips_y;
-        sy = idx % strips_y;
-    } else { pair = (k / strips_y) * 8 + xcd; sy = k % strips_y; }
-    if (pair >= n_pairs) return;
-    const int sx = pair % strips_x;
-    const uint32_t f = pair / strips_x;
+    int f, sx, sy;
+    if (!strip_of<T_OUT>(W, strips_y, n_frames, f, sx, sy)) return;
     const uint8_t* frame = pixels + (size_t)f * frame_stride;
     uint8_t* gout = grey + (size_t)f * W * H;
     const bool write_grey = grey != nullptr;
@@ -283,13 +285,6 @@ __global__ __launch_bounds__(64, T_WAVES) void k_grey_threshold7(const uint8_t* 
     // the XCD's L2 instead of fetching them again from HBM.  The box filter is symmetric, so direction only changes
     // the order rows enter and leave the window.
     const int dir = (sy & 1) ? -1 : 1;
-    // the parked rows [0, nb) (row q is image row yb0 + dir * q) leave for the packed image, one 2-byte store per lane and row
-    // (16-byte stores, eight rows per instruction, were bit-exact and 2-3 % slower in round 5)
-    auto flush_parked = [&](int nb, int yb0) {
-        if (owner)
-            for (int q = 0; q < nb; q++)
-                *reinterpret_cast<out_bits_t*>(bout + (size_t)(yb0 + dir * q) * bpr + (x0 >> 3)) = s_out[q * 64 + lane];
-    };
     const int r_first = dir > 0 ? y_begin - R : y_end - 1 + R, n_rows = (y_end - y_begin) + 2 * R;
     RawRow<FMT> q[T_PF];
     // FAST: every load is unconditional (row and column clamped into the image) so that the loop body has no branch
@@ -397,79 +392,41 @@ __global__ __launch_bounds__(64, T_WAVES) void k_grey_threshold7(const uint8_t* 
             }
             // the bits of pixels 0 .. T_NP-1 sit in the low half of acc, those of pixels T_NP .. in the high half
             const uint32_t outb = __builtin_amdgcn_perm(0u, acc, 0x0C0C0200u);
-            if (flush_rows <= 0) {
-                if (owner) *reinterpret_cast<out_bits_t*>(bout + (size_t)y * bpr + (x0 >> 3)) = (out_bits_t)outb;
-            } else {
-                if (n_buf == 0) y_buf0 = y;
-                s_out[n_buf * 64 + lane] = (out_bits_t)outb;
-                n_buf++;
-            }
+            if (n_buf == 0) y_buf0 = y;
+            s_out[n_buf * 64 + lane] = (out_bits_t)outb;
+            n_buf++;
         }
         // (checked once per block of UNROLL rows, outside the unrolled body: the buffer holds flush_rows + UNROLL rows)
-        if (flush_rows > 0 && n_buf >= flush_rows) {   // wave-uniform
-            flush_parked(n_buf, y_buf0);
+        if (n_buf >= flush_rows) {   // wave-uniform
+            flush_parked(s_out, lane, owner, bout, bpr, x0 >> 3, n_buf, y_buf0, dir);
             n_buf = 0;
         }
     }
-    if (flush_rows > 0) flush_parked(n_buf, y_buf0);
+    flush_parked(s_out, lane, owner, bout, bpr, x0 >> 3, n_buf, y_buf0, dir);
 }
 
 // the register-resident kernel for one radius R in 1..7 (the default, 7, is the one every figure of DESIGN.md is about)
 template <int R>
 hipError_t launch_k1(hipStream_t st, const ThresholdLaunch& t) {
-    const uint8_t* const pixels = t.pixels; uint8_t* const grey = t.grey; uint64_t* const bits = t.bits;
-    const int fmt = t.fmt, W = t.W, H = t.H; const size_t row_stride = t.row_stride, frame_stride = t.frame_stride; const uint32_t n = t.n;
-    constexpr int NR = 2 * R + 1, UNROLL = ((NR + T_PF - 1) / T_PF) * T_PF;   // (as in the kernel)
-    const int aligned_in = ((uintptr_t)pixels % 16 == 0) && (row_stride % 16 == 0) && (frame_stride % 16 == 0);
-    const int aligned_out = (W % 16 == 0) && ((uintptr_t)grey % 16 == 0);
-    uint8_t* bin = reinterpret_cast<uint8_t*>(bits);
+    const int W = t.W, H = t.H;
+    const int aligned_in = ((uintptr_t)t.pixels % 16 == 0) && (t.row_stride % 16 == 0) && (t.frame_stride % 16 == 0);
+    const int aligned_out = (W % 16 == 0) && ((uintptr_t)t.grey % 16 == 0);
     if (W % 64 != 0) {  // packed rows end in padding bits that no tile writes
-        hipError_t e = hipMemsetAsync(bits, 0, (size_t)words_per_row((uint32_t)W) * 8 * H * n, st);
+        hipError_t e = hipMemsetAsync(t.bits, 0, (size_t)words_per_row((uint32_t)W) * 8 * H * t.n, st);
         if (e != hipSuccess) return e;
     }
-    // Rows per wave.  Every wave also reads and converts 2R rows outside its strip, so strips should be tall; but the
-    // chip holds 256 CUs x 4 SIMDs x T_WAVES waves at once and a launch runs in whole rounds of that many, so the
-    // number of strips should fill the last round.  Model: time ~ rounds x (rows per strip + 2R); take the best
-    // strip count (at least 16 rows per strip).  256 frames of 1920x1080, R = 7: 2 column strips x 4 strips of 270 rows = 2048 waves
-    // = exactly one round of two waves per SIMD.
-    const int strips_x = (W + T_OUT - 1) / T_OUT;
-    const long long slots = 256 * 4 * T_WAVES, cols = (long long)strips_x * n;
-    // (Strips of ONE row for a single small frame -- 480 waves of one 15-row block instead of 30 waves of two -- were tried in round 5:
-    // 23.0 us against 16.8 for one 640x480 frame; a wave's fixed costs outweigh the block saved.  The model stays at >= 16 rows.)
-    int best_sy = 1; double best_cost = 1e300;
-    for (int sy = 1; sy <= std::max(1, H / 16); sy++) {
-        const int rows = (H + sy - 1) / sy;
-        const long long waves = cols * ((H + rows - 1) / rows);
-        const double cost = (double)((waves + slots - 1) / slots) * (rows + 2 * R);
-        if (cost < best_cost - 1e-9) { best_cost = cost; best_sy = sy; }
-    }
-    const int rows_per_wave = (H + best_sy - 1) / best_sy;
-    const int strips_y = (H + rows_per_wave - 1) / rows_per_wave;
-    const int n_pairs = (int)n * strips_x;
-    // every strip of a frame on one XCD (1) or every (frame, column strip) pair on its own XCD (0).  By frame is ~3 % faster:
-    // the two column strips of a frame overlap by 32 columns and write the same lines of the packed image
-    const int map_by_frame = 1;
-    // rows of results a wave parks in LDS before it writes them out: 128 (+ UNROLL) rows x 64 lanes x 2 bytes = 18 KB per wave, and
-    // every resident wave's parking area must fit the CU's 160 KB (4 x T_WAVES waves)
-    constexpr int kFlushRows = 128;
-    static_assert((kFlushRows + UNROLL) * 64 * (int)sizeof(out_bits_t) * 4 * T_WAVES <= 160 * 1024, "the parked rows fit the LDS");
-    const int flush_rows = std::min(kFlushRows, rows_per_wave);
-    // (The kernel's map_by_frame == 0 branch and its row-by-row stores for flush_rows <= 0 are no longer launched.  Removing them
-    // changes K1's arguments and machine code, so it waits for a change that is timed on the GPU.)
-    const size_t lds_bytes = flush_rows > 0 ? (size_t)(flush_rows + UNROLL) * 64 * sizeof(out_bits_t) : 0;
-    dim3 grid(map_by_frame ? 8 * (((int)n + 7) / 8) * strips_x * strips_y : 8 * ((n_pairs + 7) / 8) * strips_y), block(64);
+    const K1Plan p = plan_k1(W, H, t.n, R);
+    const dim3 grid(strip_grid(p.s, t.n)), block(64);
     const bool fast = aligned_in && aligned_out;   // W % 16 == 0: a lane's 16 pixels are all inside or all outside
-#define A3_LAUNCH_K1(F, B) hipLaunchKernelGGL((k_grey_threshold7<F, B, R>), grid, block, lds_bytes, st, pixels, row_stride, frame_stride, W, H, \
-                                              rows_per_wave, strips_y, n_pairs, grey, bin, aligned_in, aligned_out, map_by_frame, flush_rows)
-    if (fmt == A3_FMT_RGB8) { if (fast) A3_LAUNCH_K1(A3_FMT_RGB8, true); else A3_LAUNCH_K1(A3_FMT_RGB8, false); }
-    else if (fmt == A3_FMT_RGBA8) { if (fast) A3_LAUNCH_K1(A3_FMT_RGBA8, true); else A3_LAUNCH_K1(A3_FMT_RGBA8, false); }
-    else if (fmt == A3_FMT_BGRA8) { if (fast) A3_LAUNCH_K1(A3_FMT_BGRA8, true); else A3_LAUNCH_K1(A3_FMT_BGRA8, false); }
-    else if (fmt == A3_FMT_YUYV8) { if (fast) A3_LAUNCH_K1(A3_FMT_YUYV8, true); else A3_LAUNCH_K1(A3_FMT_YUYV8, false); }
-    else if (fmt == A3_FMT_UYVY8) { if (fast) A3_LAUNCH_K1(A3_FMT_UYVY8, true); else A3_LAUNCH_K1(A3_FMT_UYVY8, false); }
-    else { if (fast) A3_LAUNCH_K1(A3_FMT_L8, true); else A3_LAUNCH_K1(A3_FMT_L8, false); }
-#undef A3_LAUNCH_K1
-    return hipGetLastError();
+    return with_format(t.fmt, [&](auto F) {
+        auto launch = [&](auto FAST) {
+            hipLaunchKernelGGL((k_grey_threshold7<decltype(F)::value, decltype(FAST)::value, R>), grid, block, p.lds_bytes, st, t.pixels, t.row_stride,
+                               t.frame_stride, W, H, p.s.rows_per_wave, p.s.strips_y, (int)t.n, t.grey, reinterpret_cast<uint8_t*>(t.bits), aligned_in,
+                               aligned_out, p.flush_rows);
+            return hipGetLastError();
+        };
+        return fast ? launch(std::true_type{}) : launch(std::false_type{});
+    });
 }
-
 
 }  // namespace a3

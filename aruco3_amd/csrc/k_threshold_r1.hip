@@ -4,12 +4,7 @@
 namespace a3 {
 
 hipError_t launch_k1_r1(hipStream_t st, const ThresholdLaunch& t) {
-    switch (t.radius) {
-        case 1: return launch_k1<1>(st, t);
-        case 2: return launch_k1<2>(st, t);
-        case 3: return launch_k1<3>(st, t);
-        default: return hipErrorInvalidValue;
-    }
+    return with_radius<1, 3>(t.radius, [&](auto R) { return launch_k1<decltype(R)::value>(st, t); });
 }
 
 }  // namespace a3

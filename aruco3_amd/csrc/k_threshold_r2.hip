@@ -4,12 +4,7 @@
 namespace a3 {
 
 hipError_t launch_k1_r2(hipStream_t st, const ThresholdLaunch& t) {
-    switch (t.radius) {
-        case 4: return launch_k1<4>(st, t);
-        case 5: return launch_k1<5>(st, t);
-        case 6: return launch_k1<6>(st, t);
-        default: return hipErrorInvalidValue;
-    }
+    return with_radius<4, 6>(t.radius, [&](auto R) { return launch_k1<decltype(R)::value>(st, t); });
 }
 
 }  // namespace a3

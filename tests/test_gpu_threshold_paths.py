@@ -1,6 +1,6 @@
 """Every launch path of the threshold stage against tests/threshold_util.py's numpy reference, bit for bit, through detect_batch:
 radii 1..7 (the register-resident kernel: every ring size, column strips, row strips in both directions, frames lower than the
-window, every pixel format, aligned and unaligned layouts, the parked rows' flush), 8..31 (the ring kernel), 32..128 (separable),
+window, every pixel format, aligned and unaligned layouts, the parked rows' flush), 8..31 (the ring kernel, its flush too), 32..128 (separable),
 above 128 (brute force) -- on contents that sit on the comparison's boundary.  The batches come from threshold_util's table, which
 tests/test_threshold_reference.py holds against the CPU oracle and shows to discriminate.  GPU only."""
 import numpy as np
@@ -123,11 +123,22 @@ def test_k1_parked_rows_flush(hip, dicts, oracle, radius, shape):
 # ---- d. radii 8..31 on the comparison's boundary ---------------------------------------------------------------------------
 @pytest.mark.parametrize("radius", tu.RING_RADII)
 def test_ring_kernel_boundary_contents(hip, dicts, oracle, radius):
-    """k_grey_threshold_ring with one (8, 15) and two (16, 31) apron lanes: knife(0), knife(253), all255, all0, stripes on 40 x 1009
-    (per-pixel loads) and 129 x 1040 (vector loads, two column strips)"""
+    """k_grey_threshold_ring with one (8, 15) and two (16, 19, 27, 31) apron lanes -- 19: the first radius with 19 rows of ring in LDS and
+    a longer register part, 27: RGB8 with vector loads back at R | R + 1 and one wave per SIMD --: knife(0), knife(253), all255, all0,
+    stripes on 40 x 1009 (per-pixel loads) and 129 x 1040 (vector loads, two column strips)"""
     det, ctx = _context(dicts, radius)
     for case in tu.ring_cases(radius):
         _check_case(hip, ctx, oracle, case)
+
+
+@pytest.mark.parametrize("radius,shape", [(8, "2048x16x300"), (8, "1024x16x260"), (31, "1024x16x200"), (31, "512x16x260")])
+def test_ring_parked_rows_flush(hip, dicts, oracle, radius, shape):
+    """k_grey_threshold_ring with strips taller than the rows a wave parks in LDS (84 at radius 8, 60 at 31): one strip per frame, and
+    two strips of 130 rows of which the second walks upwards (tests/test_threshold_plan.py holds the strips against the planner);
+    every frame is compared"""
+    det, ctx = _context(dicts, radius)
+    case = {f"{len(c.contents)}x{c.w}x{c.h}": c for c in tu.ring_flush_cases(radius)}[shape]
+    _check_case(hip, ctx, oracle, case)
 
 
 # ---- e. the separable and the brute-force path -----------------------------------------------------------------------------

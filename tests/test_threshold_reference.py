@@ -113,16 +113,3 @@ def test_impulses_blacken_their_footprints(radius):
             assert {x for x in (975, 976, 991, 992, 1007, 1008) if x < w} <= xs
             assert set(range(R)) | set(range(w - R, w)) <= xs
             assert set(range(R)) | set(range(h - R, h)) | {0, 16, 17, 33, 34, 50, 51, 67, 68, 84, 85, 99} <= ys
-
-
-def test_k1_geometry():
-    """the strips tests/test_gpu_threshold_paths.py relies on, from the restated cost model of launch_k1"""
-    for R in tu.K1_RADII:
-        assert tu.k1_geometry(1, 640, 100, R) == (1, 6, 17) and tu.k1_geometry(10, 1008, 100, R) == (2, 6, 17)
-        assert tu.k1_geometry(10, 1985, 100, R) == (3, 6, 17)
-        assert tu.k1_geometry(10, 993, 100, R)[0] == 2 and tu.k1_geometry(10, 992, 100, R)[0] == 1
-        assert tu.k1_geometry(2048, 16, 300, R) == (1, 1, 300)      # 300 rows: bursts of 128, 128 and a remainder
-        assert tu.k1_geometry(1024, 16, 260, R) == (1, 2, 130)      # 130 rows: a burst and a remainder of 2, the second strip upwards
-        flush = tu.flush_cases(R)
-        assert [(len(c.contents), c.h, c.w) for c in flush] == [(2048, 300, 16), (1024, 260, 16)]
-        assert all(tu.k1_geometry(len(c.contents), c.w, c.h, R)[2] > tu.K1_FLUSH_ROWS for c in flush)

@@ -44,18 +44,18 @@ def window_covers_frame(h, w, radius):
     return radius >= max(h, w) - 1
 
 
-# ---- the strip choice of the register-resident kernel ----------------------------------------------------------------------
+# ---- the strip choice of the two fused kernels ------------------------------------------------------------------------------
+# Mirrors of aruco3_amd/csrc/a3_threshold_plan.h, for building test shapes without a compiler; tests/test_threshold_plan.py holds them
+# against the compiled planner on every shape the tables below use.
 K1_STRIP_COLS = 992    # T_OUT: output columns per wave
 K1_FLUSH_ROWS = 128    # kFlushRows: rows of result bits a wave parks in LDS between bursts of stores
+RING_LDS_ROWS8 = 19    # kRingLdsRows8: rows of ring a wave may keep in LDS with two waves per SIMD
 
 
-def k1_geometry(n, w, h, radius):
-    """(strips_x, strips_y, rows_per_wave) of radii 1..7 for n frames of w x h.  Mirrors launch_k1 in
-    aruco3_amd/csrc/k_threshold_k1.h -- 2048 wave slots, time ~ rounds x (rows per strip + 2R), strips of at least 16 rows, the
-    smaller strip count on a tie -- and is changed together with it.  A wave flushes its parked rows every
-    min(K1_FLUSH_ROWS, rows_per_wave) rows (rounded up to the row loop's unroll), and odd strips walk upwards."""
-    strips_x = -(-w // K1_STRIP_COLS)
-    slots, cols = 2048, strips_x * n
+def _strips(n, w, h, radius, out_cols, slots):
+    """plan_strips: time ~ rounds x (rows per strip + 2R), strips of at least 16 rows, the smaller strip count on a tie"""
+    strips_x = -(-w // out_cols)
+    cols = strips_x * n
     best_sy, best_cost = 1, None
     for sy in range(1, max(1, h // 16) + 1):
         rows = -(-h // sy)
@@ -65,6 +65,25 @@ def k1_geometry(n, w, h, radius):
             best_sy, best_cost = sy, cost
     rows_per_wave = -(-h // best_sy)
     return strips_x, -(-h // rows_per_wave), rows_per_wave
+
+
+def k1_geometry(n, w, h, radius):
+    """(strips_x, strips_y, rows_per_wave) of radii 1..7 for n frames of w x h: plan_k1, 2048 wave slots.  A wave flushes its parked
+    rows every min(K1_FLUSH_ROWS, rows_per_wave) rows (rounded up to the row loop's unroll), and odd strips walk upwards."""
+    return _strips(n, w, h, radius, K1_STRIP_COLS, 2048)
+
+
+def ring_geometry(n, w, h, radius, fmt="RGB8", fast=True):
+    """(strips_x, strips_y, rows_per_wave, flush_rows) of radii 8..31: plan_ring.  fast: vector loads (aligned layout, w % 16 == 0).
+    Eight waves per CU while the ring's LDS part is at most RING_LDS_ROWS8 rows, else four; a wave's parked rows share its part of the
+    160 KB with the ring."""
+    last8 = 19 if not fast else {"L8": 28, "YUYV8": 27, "UYVY8": 27, "RGB8": 26}.get(fmt, 24)
+    reg = radius if radius + 1 <= RING_LDS_ROWS8 or radius > last8 else 2 * radius + 1 - RING_LDS_ROWS8
+    nb = 2 * radius + 1 - reg
+    wpc = 8 if nb <= RING_LDS_ROWS8 else 4
+    sx, sy, rows = _strips(n, w, h, radius, (60 if radius > 15 else 62) * 16, 256 * wpc)
+    room = (160 * 1024 // wpc - 64 - nb * 1024) // 128 - 3
+    return sx, sy, rows, max(1, min(K1_FLUSH_ROWS, rows, room))
 
 
 # ---- contents: grey planes as functions of (rng, h, w) ---------------------------------------------------------------------
@@ -214,7 +233,7 @@ def luma(px, fmt):
 
 
 K1_RADII = (1, 2, 3, 4, 5, 6, 7)
-RING_RADII = (8, 15, 16, 31)
+RING_RADII = (8, 15, 16, 19, 27, 31)   # 19: the first with 19 rows of ring in LDS and a longer register part; 27: RGB8 back at R | R + 1
 SEPARABLE_RADII = (32, 33, 64, 127, 128)
 BRUTE_RADII = (129, 200, 1000, 65535, 2**31 - 1)
 ALL_RADII = K1_RADII + RING_RADII + SEPARABLE_RADII + BRUTE_RADII
@@ -288,13 +307,27 @@ LAYOUTS = {
 }
 
 
+def _flush_contents(n):
+    return {f"{'knife100' if i & 1 else 'noise'}_{i}": (knife(100) if i & 1 else noise) for i in range(n)}
+
+
 def flush_cases(R):
     """radii 1..7, the parked rows' flush: 2048 frames of 16 x 300 are one strip of 300 rows per wave (two bursts of 128 rows and a
     remainder), 1024 frames of 16 x 260 two strips of 130 rows (a burst and a remainder of 2; the second walks upwards) -- by
-    k1_geometry, which tests/test_threshold_reference.py checks.  Noise in even frames, knife(100) in odd ones."""
-    def contents(n):
-        return {f"{'knife100' if i & 1 else 'noise'}_{i}": (knife(100) if i & 1 else noise) for i in range(n)}
-    return [Case("flush", R, 300, 16, "L8", contents(2048)), Case("flush", R, 260, 16, "L8", contents(1024))]
+    k1_geometry, which tests/test_threshold_plan.py checks.  Noise in even frames, knife(100) in odd ones."""
+    return [Case("flush", R, 300, 16, "L8", _flush_contents(2048)), Case("flush", R, 260, 16, "L8", _flush_contents(1024))]
+
+
+RING_FLUSH_RADII = (8, 31)
+
+
+def ring_flush_cases(R):
+    """the ring kernel's parked rows with strips taller than a burst, contents as flush_cases.  R = 8 (2048 wave slots, bursts of 84
+    rows): 2048 frames of 16 x 300 are one strip of 300 rows, 1024 of 16 x 260 two strips of 130, the second walking upwards.  R = 31
+    (1024 wave slots, bursts of 60 rows): 1024 frames of 16 x 200 are one strip of 200 rows, 512 of 16 x 260 two strips of 130 -- by
+    ring_geometry, which tests/test_threshold_plan.py checks."""
+    shapes = {8: ((2048, 300), (1024, 260)), 31: ((1024, 200), (512, 260))}[R]
+    return [Case("ringflush", R, h, 16, "L8", _flush_contents(n)) for n, h in shapes]
 
 
 def cases_of(radius):
@@ -302,5 +335,5 @@ def cases_of(radius):
     if radius in K1_RADII:
         return k1_cases(radius) + layout_cases(radius) + flush_cases(radius)
     if radius in RING_RADII:
-        return ring_cases(radius)
+        return ring_cases(radius) + (ring_flush_cases(radius) if radius in RING_FLUSH_RADII else [])
     return separable_cases(radius) if radius in SEPARABLE_RADII else brute_cases(radius)
