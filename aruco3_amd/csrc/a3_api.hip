@@ -2328,66 +2328,52 @@ int a3_refine_corners(a3_ctx* ctx, const void* pixels, int memory, int fmt, uint
 }
 
 // ---- board pose (an extension beyond the reference; contract in include/aruco3_hip.h) ----
-int a3_set_board(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size_t n) {
-    if (!ctx) return A3_ERR_INVALID;
-    if (n > A3_BOARD_MAX_MARKERS) return fail(ctx, A3_ERR_INVALID, "a3_set_board: more than A3_BOARD_MAX_MARKERS markers");
-    if (n && (!ids || !corners_xy)) return fail(ctx, A3_ERR_INVALID, "a3_set_board: null ids or corners");
+// What the two board setters share, behind their call checks: every id in the dictionary and named once, every marker checked and
+// turned into its slot record by marker(its floats, slot) (-> the refusal's message, or nullptr), then the tables swapped in.  A ChArUco
+// setting names ids of the board it was checked against, so it goes; recovery needs a (planar) board, so it goes unless keep_recovery.
+static int set_board_tables(a3_ctx* ctx, const uint32_t* ids, const float* corners, size_t floats, size_t n, size_t slot_bytes, uint32_t kind,
+                            bool keep_recovery, const char* unknown_id, const char* repeated_id, const char* (*marker)(const float*, void*)) {
     std::vector<uint8_t> seen(ctx->n_codes, 0);
-    std::vector<uint8_t> slots(n * board_slot_bytes());
+    std::vector<uint8_t> slots(n * slot_bytes);
     for (size_t i = 0; i < n; i++) {
-        if (ids[i] >= ctx->n_codes) return fail(ctx, A3_ERR_INVALID, "a3_set_board: an id is not in the dictionary");
-        if (seen[ids[i]]++) return fail(ctx, A3_ERR_INVALID, "a3_set_board: an id appears twice on the board");
-        const float* c = corners_xy + 8 * i;
-        for (int k = 0; k < 8; k++)
-            if (!std::isfinite(c[k])) return fail(ctx, A3_ERR_INVALID, "a3_set_board: a corner is not finite");
-        double ex[4], ey[4];
-        for (int k = 0; k < 4; k++) { ex[k] = (double)c[2 * ((k + 1) & 3)] - c[2 * k]; ey[k] = (double)c[2 * ((k + 1) & 3) + 1] - c[2 * k + 1]; }
-        const double s = std::sqrt(ex[0] * ex[0] + ey[0] * ey[0]);
-        if (!(s > 0.0)) return fail(ctx, A3_ERR_INVALID, "a3_set_board: a marker has no size");
-        for (int k = 0; k < 4; k++) {
-            const int k1 = (k + 1) & 3;
-            if (std::fabs(std::sqrt(ex[k] * ex[k] + ey[k] * ey[k]) - s) > 1e-3 * s)
-                return fail(ctx, A3_ERR_INVALID, "a3_set_board: a marker's sides differ (its corners must form a square)");
-            if (std::fabs(ex[k] * ex[k1] + ey[k] * ey[k1]) > 1e-3 * s * s)
-                return fail(ctx, A3_ERR_INVALID, "a3_set_board: a marker's corners are not at right angles (they must form a square)");
-        }
-        if (!(ex[0] * ey[1] - ey[0] * ex[1] < 0.0))
-            return fail(ctx, A3_ERR_INVALID, "a3_set_board: a marker is wound the wrong way (corner order top-left, top-right, bottom-right, "
-                                             "bottom-left with y up)");
-        board_slot_from(c, slots.data() + i * board_slot_bytes());
+        if (ids[i] >= ctx->n_codes) return fail(ctx, A3_ERR_INVALID, unknown_id);
+        if (seen[ids[i]]++) return fail(ctx, A3_ERR_INVALID, repeated_id);
+        if (const char* m = marker(corners + floats * i, slots.data() + i * slot_bytes)) return fail(ctx, A3_ERR_INVALID, m);
     }
     ctx->board_ids.assign(ids, ids + n);
     ctx->board_slots.swap(slots);
-    ctx->board_kind = kBoardSlotsPlanar;   // (replaces a 3-D board too)
+    ctx->board_kind = kind;
     ctx->board_version++;
-    if (n == 0) ctx->recover = a3_recover_config{};   // (recovery needs a board)
-    ctx->charuco_nc = 0;   // (a ChArUco setting names ids of the board it was checked against)
+    if (!keep_recovery) ctx->recover = a3_recover_config{};
+    ctx->charuco_nc = 0;
     ctx->charuco_tab_h.clear();
     ctx->charuco_version++;
     return A3_OK;
+}
+
+int a3_set_board(a3_ctx* ctx, const uint32_t* ids, const float* corners_xy, size_t n) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (const char* m = check_board_call(ids, corners_xy, n)) return fail(ctx, A3_ERR_INVALID, m);
+    return set_board_tables(ctx, ids, corners_xy, 8, n, board_slot_bytes(), kBoardSlotsPlanar /* (replaces a 3-D board too) */, n != 0,
+                            "a3_set_board: an id is not in the dictionary", "a3_set_board: an id appears twice on the board",
+                            [](const float* c, void* slot) {
+                                const char* m = check_board_marker(c);
+                                if (!m) board_slot_from(c, slot);
+                                return m;
+                            });
 }
 
 // the 3-D form: the same tables with Board3Slot records; the settings that need a plane go (a3_board3d_check.h refuses them from here on)
 int a3_set_board3d(a3_ctx* ctx, const uint32_t* ids, const float* corners_xyz, size_t n) {
     if (!ctx) return A3_ERR_INVALID;
     if (const char* m = check_board3d_call(ctx->busy(), ids, corners_xyz, n)) return fail(ctx, A3_ERR_INVALID, m);
-    std::vector<uint8_t> seen(ctx->n_codes, 0);
-    std::vector<uint8_t> slots(n * board3d_slot_bytes());
-    for (size_t i = 0; i < n; i++) {
-        if (ids[i] >= ctx->n_codes) return fail(ctx, A3_ERR_INVALID, "a3_set_board3d: an id is not in the dictionary");
-        if (seen[ids[i]]++) return fail(ctx, A3_ERR_INVALID, "a3_set_board3d: an id appears twice on the board");
-        if (const char* m = check_board3d_marker(corners_xyz + 12 * i)) return fail(ctx, A3_ERR_INVALID, m);
-        board3d_slot_from(corners_xyz + 12 * i, slots.data() + i * board3d_slot_bytes());
-    }
-    ctx->board_ids.assign(ids, ids + n);
-    ctx->board_slots.swap(slots);
-    ctx->board_kind = n ? kBoardSlots3D : kBoardSlotsPlanar;
-    ctx->board_version++;
-    ctx->recover = a3_recover_config{};   // (recovery and ChArUco need a plane)
-    ctx->charuco_nc = 0;
-    ctx->charuco_tab_h.clear();
-    ctx->charuco_version++;
-    return A3_OK;
+    return set_board_tables(ctx, ids, corners_xyz, 12, n, board3d_slot_bytes(), n ? kBoardSlots3D : kBoardSlotsPlanar, false,
+                            "a3_set_board3d: an id is not in the dictionary", "a3_set_board3d: an id appears twice on the board",
+                            [](const float* c, void* slot) {
+                                const char* m = check_board3d_marker(c);
+                                if (!m) board3d_slot_from(c, slot);
+                                return m;
+                            });
 }
 
 int a3_get_board_poses(a3_ctx* ctx, a3_board_pose* dst, size_t cap_frames, size_t* n) {

@@ -1,7 +1,8 @@
 // a3_board3d.h -- the 3-D board's pieces of include/aruco3_hip.h (a3_set_board3d) that a3_board.h's planar ones do not cover: the slot
-// record with three coordinates per corner and the marker's own frame, the correspondence of one corner, and the residual / Jacobian
-// sums with q = R (X, Y, Z).  Everything else (BoardArgs, the image side of a correspondence, board_lm, board_solve, board_cayley,
-// board_ippe, pose_finite, the butterflies) is a3_board.h's, used as it stands.  Built with -ffp-contract=off.
+// record with three coordinates per corner and the marker's own frame, the correspondence of one corner, the residual / Jacobian
+// sums with q = R (X, Y, Z), and Board3Markers, the model that hands them to a3_board.h's board_pose_body.  Everything else (BoardArgs,
+// the frame run, the duplicates, the start marker, the image side of a correspondence, board_lm, the counts) is a3_board.h's, used as
+// it stands.  Built with -ffp-contract=off.
 #pragma once
 #include "a3_board.h"
 
@@ -48,5 +49,22 @@ __device__ __forceinline__ void board3_accum(BoardAcc& s, const float R[9], cons
     const float eu = ru * sx, ev = rv * sy;
     s.pix += eu * eu + ev * ev;
 }
+
+struct Board3Markers : BoardMarkerRun {   // a3_set_board3d: k_board3d_pose (a3_board.h board_pose_body)
+    using Slot = Board3Slot;
+    struct Corr { float b[3], mx, my; };
+    __device__ static const Board3Slot* slots(const BoardArgs& a) { return board3_slots(a); }
+    __device__ bool corner(const BoardArgs& a, uint32_t c, Corr& o) const { return board3_corner(a, s_dup, first, c, o.b, &o.mx, &o.my); }
+    __device__ static void accum(BoardAcc& s, const float R[9], const float t[3], const Corr& o, float sx, float sy) {
+        board3_accum(s, R, t, o.b, o.mx, o.my, sx, sy);
+    }
+    // the start marker's IPPE pose carried through the marker's own frame (e_x, e_y, e_z, c) into the board's
+    __device__ static void start(const Board3Slot& bs, const a3_pose& pm, float R[9], float t[3]) {
+        const float* Rm = pm.rotation;
+        for (int r = 0; r < 3; r++)
+            for (int j = 0; j < 3; j++) R[3 * r + j] = (Rm[3 * r] * bs.ex[j] + Rm[3 * r + 1] * bs.ey[j]) + Rm[3 * r + 2] * bs.ez[j];
+        for (int r = 0; r < 3; r++) t[r] = pm.translation[r] - ((R[3 * r] * bs.c[0] + R[3 * r + 1] * bs.c[1]) + R[3 * r + 2] * bs.c[2]);
+    }
+};
 
 }  // namespace a3

@@ -2,12 +2,8 @@
 // an extension stated in include/aruco3_hip.h and restated on the CPU by tests/board_oracle.c (a3o_board_pose), in the same order
 // of operations.
 //
-// One workgroup of two waves per frame, one wave per IPPE start.  The frame's markers are a contiguous run of the device-resident marker list; its start
-// is the sum of per_frame over the frames before it.  Duplicate board ids are found with a per-wave LDS bitmap over the board
-// slots (2 x 32 words), built by the first wave.  Correspondences are not kept in LDS: a lane caches the first four corners it owns in registers and re-reads
-// the rest (marker id -> slot -> board corner, image corner) from L2 on every evaluation, so a frame with many markers costs
-// bandwidth, not occupancy.  Every sum ends in an xor butterfly, which leaves the same bits in every lane: the solve state and
-// the control flow are wave-uniform.
+// The kernel is a3_board.h's board_pose_body with the planar marker model (PlanarMarkers): the four corners of every board marker of the
+// frame that is not duplicated, each with its slot's board point.
 #include <algorithm>
 #include <cmath>
 
@@ -17,143 +13,7 @@
 
 namespace a3 {
 
-// Two waves per frame, one per IPPE start: each runs its start's Levenberg-Marquardt over the frame's corners with all 64 lanes
-// (the contract's summation order), so the two solves, each a serial chain of small reductions and a 6x6 solve, overlap.  The loop is
-// a3_board.h's board_lm written out in place: called through the template it compiles to a different schedule in this kernel, whose
-// code is kept as it was measured.
-__global__ __launch_bounds__(128) void k_board_pose(BoardArgs a) {
-    __shared__ uint32_t s_seen[A3_BOARD_MAX_MARKERS / 32], s_dup[A3_BOARD_MAX_MARKERS / 32];
-    __shared__ float s_res[2][16];   // per start: R (9), t (3), cost, pixel cost, evaluations (as bits)
-    const uint32_t f = blockIdx.x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    // ---- the frame's run of the marker list (both waves) ----
-    uint32_t first = 0, cnt = a.n;
-    if (a.markers) {
-        uint32_t before = 0;
-        for (uint32_t g = (uint32_t)lane; g < f; g += 64) before += a.per_frame[g];
-        first = wave_sum_u(before);
-        const uint32_t limit = min(a.n, *a.n_dev);
-        cnt = first >= limit ? 0u : min(a.per_frame[f], limit - first);
-    }
-    if (threadIdx.x < A3_BOARD_MAX_MARKERS / 32) { s_seen[threadIdx.x] = 0; s_dup[threadIdx.x] = 0; }
-    __syncthreads();
-    if (wave == 0)
-        for (uint32_t i = (uint32_t)lane; i < cnt; i += 64) {
-            const uint32_t slot = board_slot(a, first + i);
-            if (slot == kNoSlot) continue;
-            const uint32_t bit = 1u << (slot & 31);
-            if (atomicOr(&s_seen[slot >> 5], bit) & bit) atomicOr(&s_dup[slot >> 5], bit);
-        }
-    __syncthreads();
-    // ---- counts and the start marker: the largest image quad whose IPPE poses are finite, then the lowest slot (both waves) ----
-    uint32_t used = 0, rejected = 0, best_i = 0;
-    unsigned long long best_key = 0;
-    for (uint32_t i = (uint32_t)lane; i < cnt; i += 64) {
-        const uint32_t slot = board_slot(a, first + i);
-        if (slot == kNoSlot) continue;
-        if (board_dup(s_dup, slot)) { rejected++; continue; }
-        used++;
-        float x[4], y[4];
-        for (int k = 0; k < 4; k++) board_image_px(a, first + i, k, &x[k], &y[k]);
-        float s = 0.0f;
-        for (int k = 0; k < 4; k++) { const int k1 = (k + 1) & 3; s = s + (x[k] * y[k1] - x[k1] * y[k]); }
-        const float area = 0.5f * fabsf(s);
-        const unsigned long long key = ((unsigned long long)__float_as_uint(area) << 32) | (unsigned long long)(0xFFFFu - slot);
-        if (key > best_key) {
-            a3_pose q0, q1;
-            board_ippe(a, first + i, a.slots[slot].side, &q0, &q1);
-            if (pose_finite(q0) && pose_finite(q1)) { best_key = key; best_i = i; }
-        }
-    }
-    used = wave_sum_u(used);
-    rejected = wave_sum_u(rejected);
-    unsigned long long top = best_key;
-    for (int o = 32; o >= 1; o >>= 1) { const unsigned long long v = __shfl_xor(top, o); top = v > top ? v : top; }
-    if (top) {   // (uniform over the workgroup)
-        const unsigned long long owners = __ballot(best_key == top);
-        const uint32_t mi = first + (uint32_t)__shfl((int)best_i, (int)__builtin_ctzll(owners));
-        const BoardSlot& bs = a.slots[0xFFFFu - (uint32_t)(top & 0xFFFFu)];
-        a3_pose p[2];
-        board_ippe(a, mi, bs.side, &p[0], &p[1]);
-        const a3_pose& pm = wave ? p[1] : p[0];
-        const float sx = a.has_intr ? a.fx : a.iw, sy = a.has_intr ? a.fy : a.ih;
-        // ---- the lane's cached corners ----
-        float cbx[kBoardCache], cby[kBoardCache], cmx[kBoardCache], cmy[kBoardCache];
-        bool cok[kBoardCache];
-        for (int j = 0; j < kBoardCache; j++) {
-            const uint32_t c = (uint32_t)lane + 64u * (uint32_t)j;
-            cok[j] = c < 4 * cnt && board_corner(a, s_dup, first, c, &cbx[j], &cby[j], &cmx[j], &cmy[j]);
-        }
-        auto evaluate = [&](const float R[9], const float t[3], BoardAcc& s) {
-            for (int q = 0; q < 21; q++) s.h[q] = 0.0f;
-            for (int q = 0; q < 6; q++) s.g[q] = 0.0f;
-            s.cost = 0.0f; s.pix = 0.0f;
-            for (int j = 0; j < kBoardCache; j++)
-                if (cok[j]) board_accum(s, R, t, cbx[j], cby[j], cmx[j], cmy[j], sx, sy);
-            for (uint32_t c = (uint32_t)lane + 64u * kBoardCache; c < 4 * cnt; c += 64) {
-                float bx, by, mx, my;
-                if (board_corner(a, s_dup, first, c, &bx, &by, &mx, &my)) board_accum(s, R, t, bx, by, mx, my, sx, sy);
-            }
-            for (int q = 0; q < 21; q++) s.h[q] = wave_sum_f(s.h[q]);
-            for (int q = 0; q < 6; q++) s.g[q] = wave_sum_f(s.g[q]);
-            s.cost = wave_sum_f(s.cost);
-            s.pix = wave_sum_f(s.pix);
-        };
-        // ---- this wave's start, carried into the board frame, then Levenberg-Marquardt ----
-        float R[9], t[3];
-        const float* Rm = pm.rotation;
-        for (int r = 0; r < 3; r++) {
-            R[3 * r] = Rm[3 * r] * bs.cs - Rm[3 * r + 1] * bs.sn;
-            R[3 * r + 1] = Rm[3 * r] * bs.sn + Rm[3 * r + 1] * bs.cs;
-            R[3 * r + 2] = Rm[3 * r + 2];
-        }
-        for (int r = 0; r < 3; r++) t[r] = pm.translation[r] - (R[3 * r] * bs.cx + R[3 * r + 1] * bs.cy);
-        BoardAcc s;
-        evaluate(R, t, s);
-        uint32_t evals = 1;
-        float lambda = 1e-3f;
-        while (evals < A3_BOARD_MAX_EVALS && s.cost > 0.0f) {
-            float d[6];
-            if (!board_solve(s.h, s.g, lambda, d)) { lambda = lambda * 10.0f; evals++; continue; }
-            float Rn[9], tn[3];
-            board_cayley(d, R, Rn);
-            for (int r = 0; r < 3; r++) tn[r] = t[r] + d[3 + r];
-            BoardAcc s2;
-            evaluate(Rn, tn, s2);
-            evals++;
-            if (s2.cost < s.cost) {
-                const float rel = (s.cost - s2.cost) / s.cost;
-                for (int q = 0; q < 9; q++) R[q] = Rn[q];
-                for (int q = 0; q < 3; q++) t[q] = tn[q];
-                s = s2;
-                lambda = lambda / 10.0f;
-                if (rel < A3_BOARD_REL_TOL) break;
-            } else lambda = lambda * 10.0f;
-        }
-        if (lane == 0) {
-            for (int q = 0; q < 9; q++) s_res[wave][q] = R[q];
-            for (int q = 0; q < 3; q++) s_res[wave][9 + q] = t[q];
-            s_res[wave][12] = s.cost; s_res[wave][13] = s.pix; s_res[wave][14] = __uint_as_float(evals);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a3_board_pose rec{};
-        rec.markers_used = used;
-        rec.markers_rejected = rejected;
-        if (top) {
-            const int k = s_res[1][12] < s_res[0][12] ? 1 : 0;   // (ties: the first IPPE pose)
-            const float nc = (float)(4u * used);
-            rec.status = A3_BOARD_OK;
-            rec.iterations = __float_as_uint(s_res[k][14]);
-            rec.rms_px = sqrtf(s_res[k][13] / nc);
-            rec.alt_rms_px = sqrtf(s_res[1 - k][13] / nc);
-            for (int q = 0; q < 9; q++) rec.rotation[q] = s_res[k][q];
-            for (int q = 0; q < 3; q++) rec.translation[q] = s_res[k][9 + q];
-        }
-        a.out[f] = rec;
-    }
-}
+__global__ __launch_bounds__(128) void k_board_pose(BoardArgs a) { board_pose_body(a, PlanarMarkers{}, a.out); }
 
 size_t board_slot_bytes() { return sizeof(BoardSlot); }
 

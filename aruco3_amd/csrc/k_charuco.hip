@@ -10,8 +10,8 @@
 //   k_charuco_refine   one wave per reported corner, four per workgroup (grid: corner quads x frames): the frame's output offset is
 //                      the sum of the counts before it; the wave refines its corner (a3_subpix.h) and writes the record at offset +
 //                      rank, so the records come out ordered by (frame, id); the workgroup of the last frame also writes the total;
-//   k_charuco_pose     two waves per frame, one per IPPE start, as k_board_pose: the start from the board markers, then the
-//                      Levenberg-Marquardt of a3_board.h over the frame's records.
+//   k_charuco_pose     a3_board.h's board_pose_body with the record model (CharucoRecords): the start from the board markers as
+//                      k_board_pose takes it, then the Levenberg-Marquardt over the frame's records.
 // Per-frame slot arrays and a second launch, rather than a prefix over frames inside k_charuco_interp: the refinement wants one wave
 // per corner anyway, and that launch can take the frame offsets once every frame's count is final.
 #include <algorithm>
@@ -105,18 +105,6 @@ __device__ bool charuco_homography(const float* from, const float* to, float h[8
     return !(fabsf(det) < 1e-10f);
 }
 
-// the frame's run of the marker list: first index and count (every lane of every wave gets the same)
-__device__ __forceinline__ void charuco_frame_run(const BoardArgs& a, uint32_t f, int lane, uint32_t* first, uint32_t* cnt) {
-    *first = 0; *cnt = a.n;
-    if (a.markers) {
-        uint32_t before = 0;
-        for (uint32_t g = (uint32_t)lane; g < f; g += 64) before += a.per_frame[g];
-        *first = wave_sum_u(before);
-        const uint32_t limit = min(a.n, *a.n_dev);
-        *cnt = *first >= limit ? 0u : min(a.per_frame[f], limit - *first);
-    }
-}
-
 __global__ __launch_bounds__(256) void k_charuco_interp(BoardArgs a, CharucoArgs c, RefineParams p) {
     __shared__ uint32_t s_seen[A3_BOARD_MAX_MARKERS / 32], s_dup[A3_BOARD_MAX_MARKERS / 32];
     __shared__ float s_h[A3_BOARD_MAX_MARKERS][8];      // homography of the slot's marker
@@ -125,17 +113,9 @@ __global__ __launch_bounds__(256) void k_charuco_interp(BoardArgs a, CharucoArgs
     const uint32_t f = blockIdx.x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     uint32_t first, cnt;
-    charuco_frame_run(a, f, lane, &first, &cnt);
-    if (tid < A3_BOARD_MAX_MARKERS / 32) { s_seen[tid] = 0; s_dup[tid] = 0; }
+    board_frame_run(a.markers != nullptr, a.per_frame, a.n, a.n_dev, f, lane, &first, &cnt);
     for (int s = tid; s < A3_BOARD_MAX_MARKERS; s += 256) s_mi[s] = kNoAdj;
-    __syncthreads();
-    for (uint32_t i = (uint32_t)tid; i < cnt; i += 256) {
-        const uint32_t slot = board_slot(a, first + i);
-        if (slot == kNoSlot) continue;
-        const uint32_t bit = 1u << (slot & 31);
-        if (atomicOr(&s_seen[slot >> 5], bit) & bit) atomicOr(&s_dup[slot >> 5], bit);
-    }
-    __syncthreads();
+    board_mark_duplicates(s_seen, s_dup, cnt, true, (uint32_t)tid, 256u, [&](uint32_t i) { return board_slot(a, first + i); });
     for (uint32_t i = (uint32_t)tid; i < cnt; i += 256) {   // (a slot not duplicated belongs to one marker: one writer)
         const uint32_t slot = board_slot(a, first + i);
         if (slot == kNoSlot || board_dup(s_dup, slot)) continue;
@@ -241,118 +221,38 @@ __global__ __launch_bounds__(256) void k_charuco_refine(CharucoArgs c, RefinePar
     }
 }
 
-// Two waves per frame, one per IPPE start: the start exactly as k_board_pose takes it, then a3_board.h's LM over the frame's records.
-__global__ __launch_bounds__(128) void k_charuco_pose(BoardArgs a, CharucoArgs c, a3_charuco_pose* out) {
-    __shared__ uint32_t s_seen[A3_BOARD_MAX_MARKERS / 32], s_dup[A3_BOARD_MAX_MARKERS / 32];
-    __shared__ float s_res[2][16];   // per start: R (9), t (3), cost, pixel cost, evaluations (as bits)
-    const uint32_t f = blockIdx.x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint32_t first, cnt;
-    charuco_frame_run(a, f, lane, &first, &cnt);
-    uint32_t roff = 0;   // the frame's records
-    for (uint32_t g = (uint32_t)lane; g < f; g += 64) roff += c.counts[g];
-    roff = wave_sum_u(roff);
-    const uint32_t ncorn = c.counts[f];
-    if (threadIdx.x < A3_BOARD_MAX_MARKERS / 32) { s_seen[threadIdx.x] = 0; s_dup[threadIdx.x] = 0; }
-    __syncthreads();
-    if (wave == 0)
-        for (uint32_t i = (uint32_t)lane; i < cnt; i += 64) {
-            const uint32_t slot = board_slot(a, first + i);
-            if (slot == kNoSlot) continue;
-            const uint32_t bit = 1u << (slot & 31);
-            if (atomicOr(&s_seen[slot >> 5], bit) & bit) atomicOr(&s_dup[slot >> 5], bit);
-        }
-    __syncthreads();
-    // ---- the start marker: the largest image quad whose IPPE poses are finite, then the lowest slot ----
-    uint32_t best_i = 0;
-    unsigned long long best_key = 0;
-    for (uint32_t i = (uint32_t)lane; i < cnt; i += 64) {
-        const uint32_t slot = board_slot(a, first + i);
-        if (slot == kNoSlot || board_dup(s_dup, slot)) continue;
-        float x[4], y[4];
-        for (int k = 0; k < 4; k++) board_image_px(a, first + i, k, &x[k], &y[k]);
-        float s = 0.0f;
-        for (int k = 0; k < 4; k++) { const int k1 = (k + 1) & 3; s = s + (x[k] * y[k1] - x[k1] * y[k]); }
-        const float area = 0.5f * fabsf(s);
-        const unsigned long long key = ((unsigned long long)__float_as_uint(area) << 32) | (unsigned long long)(0xFFFFu - slot);
-        if (key > best_key) {
-            a3_pose q0, q1;
-            board_ippe(a, first + i, a.slots[slot].side, &q0, &q1);
-            if (pose_finite(q0) && pose_finite(q1)) { best_key = key; best_i = i; }
-        }
+// The record model of a3_board.h's board_pose_body: the start marker as k_board_pose takes it, the correspondences the frame's records
+// (chessboard corner id -> board point; the undistorted corner where the batch has one), solved when there are four or more.
+struct CharucoRecords {
+    using Slot = BoardSlot;
+    using Record = a3_charuco_pose;
+    using Corr = BoardCorr;
+    const CharucoArgs& c;
+    uint32_t roff = 0, ncorn = 0;   // the frame's records: the sum of the counts before it, its count
+    __device__ static const BoardSlot* slots(const BoardArgs& a) { return a.slots; }
+    __device__ void bind(const BoardArgs&, uint32_t f, int lane, uint32_t, uint32_t, const uint32_t*) {
+        for (uint32_t g = (uint32_t)lane; g < f; g += 64) roff += c.counts[g];
+        roff = wave_sum_u(roff);
+        ncorn = c.counts[f];
     }
-    unsigned long long top = best_key;
-    for (int o = 32; o >= 1; o >>= 1) { const unsigned long long v = __shfl_xor(top, o); top = v > top ? v : top; }
-    const bool solve = top && ncorn >= 4;   // (uniform over the workgroup)
-    if (solve) {
-        const unsigned long long owners = __ballot(best_key == top);
-        const uint32_t mi = first + (uint32_t)__shfl((int)best_i, (int)__builtin_ctzll(owners));
-        const BoardSlot& bs = a.slots[0xFFFFu - (uint32_t)(top & 0xFFFFu)];
-        a3_pose pp[2];
-        board_ippe(a, mi, bs.side, &pp[0], &pp[1]);
-        const a3_pose& pm = wave ? pp[1] : pp[0];
-        const float sx = a.has_intr ? a.fx : a.iw, sy = a.has_intr ? a.fy : a.ih;
-        // the record r of the frame: board point and normalised image point
-        auto corner = [&](uint32_t r, float* bx, float* by, float* mx, float* my) {
-            const a3_charuco_corner& rec = c.out[roff + r];
-            *bx = c.cxy[2 * rec.id]; *by = c.cxy[2 * rec.id + 1];
-            const float x = c.und ? c.und[2 * ((size_t)roff + r)] : rec.x, y = c.und ? c.und[2 * ((size_t)roff + r) + 1] : rec.y;
-            board_normalise(a, x, y, mx, my);
-        };
-        float cbx[kBoardCache], cby[kBoardCache], cmx[kBoardCache], cmy[kBoardCache];
-        for (int j = 0; j < kBoardCache; j++) {
-            const uint32_t r = (uint32_t)lane + 64u * (uint32_t)j;
-            if (r < ncorn) corner(r, &cbx[j], &cby[j], &cmx[j], &cmy[j]);
-        }
-        auto evaluate = [&](const float R[9], const float t[3], BoardAcc& s) {
-            for (int q = 0; q < 21; q++) s.h[q] = 0.0f;
-            for (int q = 0; q < 6; q++) s.g[q] = 0.0f;
-            s.cost = 0.0f; s.pix = 0.0f;
-            for (int j = 0; j < kBoardCache; j++)
-                if ((uint32_t)lane + 64u * (uint32_t)j < ncorn) board_accum(s, R, t, cbx[j], cby[j], cmx[j], cmy[j], sx, sy);
-            for (uint32_t r = (uint32_t)lane + 64u * kBoardCache; r < ncorn; r += 64) {
-                float bx, by, mx, my;
-                corner(r, &bx, &by, &mx, &my);
-                board_accum(s, R, t, bx, by, mx, my, sx, sy);
-            }
-            for (int q = 0; q < 21; q++) s.h[q] = wave_sum_f(s.h[q]);
-            for (int q = 0; q < 6; q++) s.g[q] = wave_sum_f(s.g[q]);
-            s.cost = wave_sum_f(s.cost);
-            s.pix = wave_sum_f(s.pix);
-        };
-        float R[9], t[3];
-        const float* Rm = pm.rotation;
-        for (int r = 0; r < 3; r++) {
-            R[3 * r] = Rm[3 * r] * bs.cs - Rm[3 * r + 1] * bs.sn;
-            R[3 * r + 1] = Rm[3 * r] * bs.sn + Rm[3 * r + 1] * bs.cs;
-            R[3 * r + 2] = Rm[3 * r + 2];
-        }
-        for (int r = 0; r < 3; r++) t[r] = pm.translation[r] - (R[3 * r] * bs.cx + R[3 * r + 1] * bs.cy);
-        BoardAcc s;
-        const uint32_t evals = board_lm(evaluate, R, t, s);
-        if (lane == 0) {
-            for (int q = 0; q < 9; q++) s_res[wave][q] = R[q];
-            for (int q = 0; q < 3; q++) s_res[wave][9 + q] = t[q];
-            s_res[wave][12] = s.cost; s_res[wave][13] = s.pix; s_res[wave][14] = __uint_as_float(evals);
-        }
+    __device__ uint32_t count() const { return ncorn; }
+    __device__ bool corner(const BoardArgs& a, uint32_t r, BoardCorr& o) const {
+        const a3_charuco_corner& rec = c.out[roff + r];
+        o.bx = c.cxy[2 * rec.id]; o.by = c.cxy[2 * rec.id + 1];
+        const float x = c.und ? c.und[2 * ((size_t)roff + r)] : rec.x, y = c.und ? c.und[2 * ((size_t)roff + r) + 1] : rec.y;
+        board_normalise(a, x, y, &o.mx, &o.my);
+        return true;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a3_charuco_pose rec{};
-        rec.corners_used = ncorn;
-        if (solve) {
-            const int k = s_res[1][12] < s_res[0][12] ? 1 : 0;   // (ties: the first IPPE pose)
-            const float nc = (float)ncorn;
-            rec.status = A3_BOARD_OK;
-            rec.iterations = __float_as_uint(s_res[k][14]);
-            rec.rms_px = sqrtf(s_res[k][13] / nc);
-            rec.alt_rms_px = sqrtf(s_res[1 - k][13] / nc);
-            for (int q = 0; q < 9; q++) rec.rotation[q] = s_res[k][q];
-            for (int q = 0; q < 3; q++) rec.translation[q] = s_res[k][9 + q];
-        }
-        out[f] = rec;
+    __device__ static void accum(BoardAcc& s, const float R[9], const float t[3], const BoardCorr& o, float sx, float sy) {
+        board_accum(s, R, t, o.bx, o.by, o.mx, o.my, sx, sy);
     }
-}
+    __device__ static void start(const BoardSlot& bs, const a3_pose& pm, float R[9], float t[3]) { board_planar_start(bs, pm, R, t); }
+    __device__ bool solves(bool top) const { return top && ncorn >= 4; }
+    __device__ float denominator(const BoardStart&) const { return (float)ncorn; }
+    __device__ void counts(a3_charuco_pose& rec, const BoardStart&) const { rec.corners_used = ncorn; }
+};
+
+__global__ __launch_bounds__(128) void k_charuco_pose(BoardArgs a, CharucoArgs c, a3_charuco_pose* out) { board_pose_body(a, CharucoRecords{c}, out); }
 
 hipError_t launch_charuco_corners(hipStream_t st, const CharucoCornersLaunch& l) {
     const uint32_t n_frames = l.m.n_frames, nc = l.board.nc;

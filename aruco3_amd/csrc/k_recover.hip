@@ -96,26 +96,14 @@ __global__ __launch_bounds__(kRecThreads) void k_recover_frames(RecoverLaunch a)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const uint32_t nb = min(a.n_slots, (uint32_t)A3_BOARD_MAX_MARKERS);
     const BoardSlot* slots = reinterpret_cast<const BoardSlot*>(a.board.slots);
-    // ---- the frame's run of the marker list (every wave) ----
-    uint32_t first = 0, cnt = a.n;
-    if (a.markers) {
-        uint32_t before = 0;
-        for (uint32_t g = (uint32_t)lane; g < f; g += 64) before += a.per_frame[g];
-        first = wave_sum_u(before);
-        const uint32_t limit = min(a.n, *a.n_dev);
-        cnt = first >= limit ? 0u : min(a.per_frame[f], limit - first);
-    }
+    uint32_t first, cnt;   // the frame's run of the marker list (every wave)
+    board_frame_run(a.markers != nullptr, a.per_frame, a.n, a.n_dev, f, lane, &first, &cnt);
     const uint32_t n_cand = a.outs ? min(a.fin_count[f], a.max_cand) : a.n_cand;
-    if (tid < A3_BOARD_MAX_MARKERS / 32) { s_seen[tid] = 0; s_dup[tid] = 0; }
     if (tid == 0) { s_ok = 0; s_nmiss = 0; s_nrec = 0; }
-    __syncthreads();
-    for (uint32_t i = (uint32_t)tid; i < cnt; i += kRecThreads) {
+    board_mark_duplicates(s_seen, s_dup, cnt, true, (uint32_t)tid, (uint32_t)kRecThreads, [&](uint32_t i) {
         const uint32_t slot = rec_marker_slot(a, first + i);
-        if (slot >= nb) continue;
-        const uint32_t bit = 1u << (slot & 31);
-        if (atomicOr(&s_seen[slot >> 5], bit) & bit) atomicOr(&s_dup[slot >> 5], bit);
-    }
-    __syncthreads();
+        return slot >= nb ? (uint32_t)kNoSlot : slot;   // (a slot past the board's does not count)
+    });
     if (wave == 0) {   // ---- step 1: correspondences in list order, then the homography ----
         uint32_t k = 0;
         for (uint32_t i0 = 0; i0 < cnt; i0 += 64) {

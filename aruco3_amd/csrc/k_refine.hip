@@ -2,9 +2,8 @@
 // keeps the integer contour corners: an extension stated in include/aruco3_hip.h, restated on the CPU by tests/refine_oracle.c
 // (a3o_refine_corners), which this kernel matches bit for bit.
 //
-// One wave64 per corner, four per workgroup (the four corners of one marker, or four consecutive caller corners).  The tile load and
-// the iteration below are a3_subpix.h's subpix_load_tile / subpix_iterate written out in place: called as functions they leave the
-// same arithmetic but a different schedule and register assignment in this kernel, whose code is kept as it was measured.
+// One wave64 per corner, four per workgroup (the four corners of one marker, or four consecutive caller corners); the tile load and
+// the iteration are a3_subpix.h's subpix_load_tile / subpix_iterate, as the ChArUco corner stage calls them.
 #include <algorithm>
 #include <cmath>
 
@@ -48,50 +47,11 @@ __global__ __launch_bounds__(256) void k_refine_corners(PixelSrc src, uint32_t W
         const int w = markers || cell_px ? refine_window(p, cell) : (int)p.win_half;
         const int T = 4 * w + 6;
         const int ox = (int)floorf(q0x) - 2 * w - 2, oy = (int)floorf(q0y) - 2 * w - 2;
-        uint8_t* tile = s_tile[wave];
-        if (live) {
-            const uint8_t* fb = src.base + (size_t)frame * src.frame_stride;
-            for (int t = lane; t < T * T; t += 64) {
-                const int x = min(max(ox + t % T, 0), (int)W - 1), y = min(max(oy + t / T, 0), (int)H - 1);
-                tile[t] = (uint8_t)refine_grey(fb, src.row_stride, src.fmt, (uint32_t)x, (uint32_t)y);
-            }
-            if (lane <= 2 * w) s_g[wave][lane] = p.g[w][lane];
-        }
+        if (live) subpix_load_tile(src, src.base + (size_t)frame * src.frame_stride, W, H, T, ox, oy, p, w, lane, s_tile[wave], s_g[wave]);
         __syncthreads();
         if (live) {
-            const float* g = s_g[wave];
-            const int side = 2 * w + 1, npx = side * side;
-            float cx = q0x, cy = q0y;
-            for (uint32_t it = 0; it < p.max_iterations; it++) {
-                float a = 0.0f, b = 0.0f, c2 = 0.0f, bb1 = 0.0f, bb2 = 0.0f;
-                for (int q = lane; q < npx; q += 64) {   // lane l: pixels l, l + 64, ... of the window, row-major
-                    const int i = q % side - w, j = q / side - w;
-                    const float m = g[i + w] * g[j + w];
-                    const float gx = refine_sample(tile, T, ox, oy, cx + (float)(i + 1), cy + (float)j) -
-                                     refine_sample(tile, T, ox, oy, cx + (float)(i - 1), cy + (float)j);
-                    const float gy = refine_sample(tile, T, ox, oy, cx + (float)i, cy + (float)(j + 1)) -
-                                     refine_sample(tile, T, ox, oy, cx + (float)i, cy + (float)(j - 1));
-                    const float fi = (float)i, fj = (float)j;
-                    a += gx * gx * m;
-                    b += gx * gy * m;
-                    c2 += gy * gy * m;
-                    bb1 += gx * gx * m * fi + gx * gy * m * fj;
-                    bb2 += gx * gy * m * fi + gy * gy * m * fj;
-                }
-                for (int o = 32; o >= 1; o >>= 1) {   // xor butterfly: a + b == b + a, so every lane ends with the same bits
-                    a += __shfl_xor(a, o); b += __shfl_xor(b, o); c2 += __shfl_xor(c2, o);
-                    bb1 += __shfl_xor(bb1, o); bb2 += __shfl_xor(bb2, o);
-                }
-                const float det = a * c2 - b * b;
-                if (det == 0.0f || !isfinite(det)) break;
-                const float s = 1.0f / det;
-                const float nx = cx + (c2 * s * bb1 - b * s * bb2), ny = cy + (-b * s * bb1 + a * s * bb2);
-                if (!(fabsf(nx - q0x) <= (float)w && fabsf(ny - q0y) <= (float)w)) { cx = q0x; cy = q0y; break; }
-                const float dx = nx - cx, dy = ny - cy;
-                cx = nx; cy = ny;
-                if (dx * dx + dy * dy <= eps2) break;
-            }
-            if (lane == 0) { out[2 * (size_t)k] = cx; out[2 * (size_t)k + 1] = cy; }
+            const float2 q = subpix_iterate(s_tile[wave], T, ox, oy, s_g[wave], w, q0x, q0y, p, eps2, lane);
+            if (lane == 0) { out[2 * (size_t)k] = q.x; out[2 * (size_t)k + 1] = q.y; }
         }
         __syncthreads();   // (the next unit overwrites the tiles)
     }

@@ -1,6 +1,6 @@
-// The argument checks of 3-D boards (aruco3_amd/csrc/a3_board3d_check.h): every refusal of a3_set_board3d with its message, the first
-// failing test deciding, every boundary that passes (sides, angles and planarity at exactly the tolerance, a marker in a plane that is
-// not axis-aligned), and the settings that are refused while a 3-D board is set.  Exits 0 and prints "ok: <n> checks" when every answer
+// The argument checks of boards (aruco3_amd/csrc/a3_board3d_check.h): every refusal of a3_set_board3d and of a3_set_board with its message,
+// the first failing test deciding, every boundary that passes (sides, angles and planarity at exactly the tolerance, a marker in a plane
+// that is not axis-aligned, a planar square in each of its four rotations), and the settings that are refused while a 3-D board is set.  Exits 0 and prints "ok: <n> checks" when every answer
 // is the expected one.  tests/test_board3d_checks.py compiles this with the address and undefined-behaviour sanitizers.
 #include <cmath>
 #include <cstdio>
@@ -28,6 +28,19 @@ const char* marker(P a, P b, P c, P d) {
     return a3::check_board3d_marker(v.data());
 }
 
+struct Q { float x, y; };
+const char* planar(Q a, Q b, Q c, Q d) {
+    const std::vector<float> v{a.x, a.y, b.x, b.y, c.x, c.y, d.x, d.y};   // (exactly eight)
+    return a3::check_board_marker(v.data());
+}
+
+constexpr const char* kFinite2 = "a3_set_board: a corner is not finite";
+constexpr const char* kSize2 = "a3_set_board: a marker has no size";
+constexpr const char* kSides2 = "a3_set_board: a marker's sides differ (its corners must form a square)";
+constexpr const char* kAngles2 = "a3_set_board: a marker's corners are not at right angles (they must form a square)";
+constexpr const char* kWinding2 = "a3_set_board: a marker is wound the wrong way (corner order top-left, top-right, bottom-right, bottom-left with y up)";
+constexpr const char* kMany2 = "a3_set_board: more than A3_BOARD_MAX_MARKERS markers";
+constexpr const char* kNull2 = "a3_set_board: null ids or corners";
 constexpr const char* kFinite = "a3_set_board3d: a corner is not finite";
 constexpr const char* kSize = "a3_set_board3d: a marker has no size";
 constexpr const char* kSides = "a3_set_board3d: a marker's sides differ (its corners must form a square)";
@@ -92,6 +105,39 @@ int main() {
     same("call_many_before_null", a3::check_board3d_call(false, nullptr, nullptr, A3_BOARD_MAX_MARKERS + 1), kMany);
     same("call_null_ids", a3::check_board3d_call(false, nullptr, xyz, 1), kNull);
     same("call_null_corners", a3::check_board3d_call(false, &id, nullptr, 1), kNull);
+    // ---- one planar marker: accepted, in each of the four rotations of the square (the corner order turns with it) ----
+    same("planar_square", planar({0, 0}, {10, 0}, {10, -10}, {0, -10}), nullptr);
+    same("planar_square_quarter_turn", planar({0, 0}, {0, 10}, {10, 10}, {10, 0}), nullptr);
+    same("planar_square_half_turn", planar({0, 0}, {-10, 0}, {-10, 10}, {0, 10}), nullptr);
+    same("planar_square_three_quarter_turn", planar({0, 0}, {0, -10}, {-10, -10}, {-10, 0}), nullptr);
+    same("planar_square_oblique", planar({3, 4}, {6, 8}, {10, 5}, {7, 1}), nullptr);   // (sides (3, 4), (4, -3): exact)
+    same("planar_tiny", planar({0, 0}, {1e-20f, 0}, {1e-20f, -1e-20f}, {0, -1e-20f}), nullptr);
+    // ... at exactly the tolerance (s = 1000: 1e-3 s = 1 and 1e-3 s^2 = 1000 exactly, in double), and just outside it
+    same("planar_sides_at_tol", planar({0, 0}, {1000, 0}, {1000, -1001}, {0, -1001}), nullptr);
+    same("planar_sides_at_tol_short", planar({0, 0}, {1000, 0}, {1000, -999}, {0, -999}), nullptr);
+    same("planar_angles_at_tol", planar({0, 0}, {1000, 0}, {1001, -1000}, {1, -1000}), nullptr);
+    same("planar_sides_past_tol", planar({0, 0}, {1000, 0}, {1000, -1001.5f}, {0, -1001.5f}), kSides2);
+    same("planar_sides_past_tol_short", planar({0, 0}, {1000, 0}, {1000, -998.5f}, {0, -998.5f}), kSides2);
+    same("planar_angles_past_tol", planar({0, 0}, {1000, 0}, {1002, -1000}, {2, -1000}), kAngles2);
+    // ---- one planar marker: refused, each from its first failing test ----
+    same("planar_nan_first", planar({nan, 0}, {10, 0}, {10, -10}, {0, -10}), kFinite2);
+    same("planar_inf_last", planar({0, 0}, {10, 0}, {10, -10}, {0, inf}), kFinite2);
+    same("planar_no_size", planar({3, 4}, {3, 4}, {3, 4}, {3, 4}), kSize2);
+    same("planar_no_size_first_side", planar({0, 0}, {0, 0}, {10, -10}, {0, -10}), kSize2);   // (before the sides are compared)
+    same("planar_rectangle", planar({0, 0}, {10, 0}, {10, -12}, {0, -12}), kSides2);
+    same("planar_rhombus", planar({0, 0}, {10, 0}, {16, -8}, {6, -8}), kAngles2);
+    same("planar_side_before_its_angle", planar({0, 0}, {10, 0}, {10, -12}, {3, -9}), kSides2);   // (side 1 comes before corner 1's angle)
+    same("planar_wound_the_other_way", planar({0, 0}, {0, -10}, {10, -10}, {10, 0}), kWinding2);
+    same("planar_square_before_winding", planar({0, 0}, {0, -12}, {10, -12}, {10, 0}), kSides2);   // (the winding is the last test)
+    // ---- a3_set_board's call ----
+    const float xy[8] = {0, 0, 10, 0, 10, -10, 0, -10};
+    same("planar_call_ok", a3::check_board_call(&id, xy, 1), nullptr);
+    same("planar_call_clear", a3::check_board_call(nullptr, nullptr, 0), nullptr);
+    same("planar_call_most", a3::check_board_call(&id, xy, A3_BOARD_MAX_MARKERS), nullptr);
+    same("planar_call_many", a3::check_board_call(&id, xy, A3_BOARD_MAX_MARKERS + 1), kMany2);
+    same("planar_call_many_before_null", a3::check_board_call(nullptr, nullptr, A3_BOARD_MAX_MARKERS + 1), kMany2);
+    same("planar_call_null_ids", a3::check_board_call(nullptr, xy, 1), kNull2);
+    same("planar_call_null_corners", a3::check_board_call(&id, nullptr, 1), kNull2);
     // ---- the settings that need a plane ----
     same("charuco_planar", a3::check_charuco_board_kind(false, 24), nullptr);
     same("charuco_3d", a3::check_charuco_board_kind(true, 24), kCharuco);

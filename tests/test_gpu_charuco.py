@@ -308,6 +308,33 @@ def test_records_beyond_the_read_back_guess():
             _same(r, expect)
 
 
+def test_pose_from_more_records_than_the_lanes_cache():
+    """one frame of the 20 x 20 board above: 361 records, so every lane of k_charuco_pose re-reads records beyond the 256 the wave
+    holds in registers, on every evaluation.  (On the CPU, the oracle alone on charuco_util.host_grey's drawing of this scene, from the
+    projected marker corners rounded to integers, yields 361 records of 361, with and without refinement.)"""
+    from aruco3_amd import _lib
+    from aruco3_amd.board import CharucoBoard
+
+    torch = _torch()
+    b = CharucoBoard(20, 20, 50.0, 35.0)
+    R, t = bu.board_pose_facing(b, 0.0, 0.0, 0.0, 1400.0)   # 50 px squares, frontal
+    frame = cu.render([cu.Scene(b, R, t)], _dict())
+    torch.cuda.synchronize()
+    ctx = _ctx(_dict(), b, refine=True)
+    m, per, _ = ctx.detect_batch_pose(frame.data_ptr(), _lib.MEM_DEVICE, _lib.FMT_RGB8, W, H, W * 3, W * H * 3, 1, 35.0, _lib.Intrinsics(W, H, *INTR),
+                                      out_cap=256)
+    assert int(per[0]) == 200
+    recs = ctx.charuco_corners()
+    assert len(recs) == 361 > 64 * 4   # (the lanes' cache: a3_board.h kBoardCache per lane)
+    got = ctx.charuco_poses()[0]
+    want = co.pose(b, m["id"], ctx.refined_corners(), recs, (W, H), INTR)
+    assert got["corners_used"] == want["corners_used"] == 361
+    assert got["status"] == want["status"] == 1
+    assert np.abs(got["rotation"] - want["rotation"]).max() < 1e-4
+    assert np.linalg.norm(got["translation"] - want["translation"]) <= 1e-4 * np.linalg.norm(want["translation"])
+    assert abs(float(got["rms_px"]) - float(want["rms_px"])) < 1e-3
+
+
 def test_submit_collect_deferred_and_gates():
     from aruco3_amd import _lib
     from aruco3_amd.aruco import BatchQueue, Detector, DetectorConfig
