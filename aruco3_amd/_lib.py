@@ -59,6 +59,8 @@ MAP_FRAME_USED, MAP_FRAME_UNUSED = 1, 2
 MAP_OBS_USED, MAP_OBS_DEGENERATE, MAP_OBS_UNREACHED = 1, 2, 3
 MAP_MAX_MARKERS, MAP_MAX_FRAMES, MAP_MAX_MAPS, MAP_MAX_CALL_FRAMES, MAP_MAX_CALL_OBSERVATIONS, MAP_START_OBSERVATIONS = 128, 4096, 1024, 65536, 262144, 8
 MAX_THRESHOLD_WINDOWS = 4   # A3_MAX_THRESHOLD_WINDOWS
+POLARITY_DARK, POLARITY_BOTH = 0, 1   # A3_POLARITY_*
+MARKER_INVERTED = 1                   # A3_MARKER_INVERTED
 STEP_NAMES = {0: "whole", 1: "decode_deferred", 2: "held_released_by_last", 3: "held_released_early", 4: "burst_last", 5: "held"}
 
 # every symbol include/aruco3_hip.h declares
@@ -78,6 +80,7 @@ SYMBOLS = [
     "a3_default_rectify", "a3_rectify_frames", "a3_set_rectification", "a3_get_rectification",
     "a3_reduce_frames", "a3_set_reduction", "a3_get_reduction",
     "a3_set_threshold_windows", "a3_get_threshold_windows",
+    "a3_set_marker_polarity", "a3_get_marker_polarity", "a3_get_marker_flags",
 ]
 CAND_DTYPE = np.dtype([("start_key", "<u4"), ("xy", "<u2", (8,))])      # a3_debug_cand (a3_internal.h)
 PROJ_DTYPE = np.dtype([("inv", "<f4", (9,)), ("ok", "<i4")])            # A3_DEBUG_PROJ_BYTES
@@ -528,6 +531,13 @@ def load():
         L.a3_set_reduction.argtypes = [vp, C.POINTER(ReductionRec)]
         L.a3_get_reduction.restype = C.c_int
         L.a3_get_reduction.argtypes = [vp, C.POINTER(ReductionRec), C.POINTER(C.c_int)]
+    if hasattr(L, "a3_set_marker_polarity"):   # (likewise inverted markers)
+        L.a3_set_marker_polarity.restype = C.c_int
+        L.a3_set_marker_polarity.argtypes = [vp, C.c_int]
+        L.a3_get_marker_polarity.restype = C.c_int
+        L.a3_get_marker_polarity.argtypes = [vp, C.POINTER(C.c_int)]
+        L.a3_get_marker_flags.restype = C.c_int
+        L.a3_get_marker_flags.argtypes = [vp, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
     if hasattr(L, "a3_set_threshold_windows"):   # (likewise several threshold windows)
         L.a3_set_threshold_windows.restype = C.c_int
         L.a3_set_threshold_windows.argtypes = [vp, C.POINTER(C.c_uint32), C.c_size_t]
@@ -1027,6 +1037,29 @@ class Context:
             raise ValueError("a threshold window radius is a uint32")
         arr = (C.c_uint32 * max(len(r), 1))(*r)
         check(load().a3_set_threshold_windows(self.handle, arr if r else None, len(r)), self.handle)
+
+    def set_marker_polarity(self, mode: int):
+        """a3_set_marker_polarity: POLARITY_DARK (the reference) or POLARITY_BOTH (bright-on-dark markers are read too); applies to
+        batches submitted afterwards"""
+        check(load().a3_set_marker_polarity(self.handle, int(mode)), self.handle)
+
+    def get_marker_polarity(self) -> int:
+        """a3_get_marker_polarity -> the mode in force"""
+        mode = C.c_int(0)
+        check(load().a3_get_marker_polarity(self.handle, C.byref(mode)), self.handle)
+        return int(mode.value)
+
+    def marker_flags(self) -> np.ndarray:
+        """a3_get_marker_flags: uint32 [n_markers] of the last collected batch, in marker order (MARKER_INVERTED: read inverted);
+        refused when that batch ran in mode POLARITY_DARK"""
+        n = C.c_size_t()
+        L = load()
+        rc = L.a3_get_marker_flags(self.handle, None, 0, C.byref(n))
+        if rc not in (OK, ERR_CAPACITY):
+            check(rc, self.handle)
+        out = np.zeros(max(n.value, 1), dtype=np.uint32)
+        check(L.a3_get_marker_flags(self.handle, _p(out, C.c_uint32), max(n.value, 1), C.byref(n)), self.handle)
+        return out[: n.value]
 
     def get_threshold_windows(self):
         """a3_get_threshold_windows -> the radii in force as a tuple (empty: off)"""

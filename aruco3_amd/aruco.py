@@ -124,6 +124,14 @@ def _apply_threshold_windows(ctx: _lib.Context, threshold_windows) -> None:
         ctx._windows_key = key
 
 
+def _apply_polarity(ctx: _lib.Context, inverted_markers: bool) -> None:
+    """hands the marker polarity (a3_set_marker_polarity) to a context: only on a change"""
+    mode = _lib.POLARITY_BOTH if inverted_markers else _lib.POLARITY_DARK
+    if getattr(ctx, "_polarity", _lib.POLARITY_DARK) != mode:
+        ctx.set_marker_polarity(mode)
+        ctx._polarity = mode
+
+
 def _one_view(reduction, rectification) -> None:
     if reduction is not None and rectification is not None:
         raise ValueError("a detector takes a reduction or a rectification, not both (a3_set_reduction refuses the pair)")
@@ -141,6 +149,7 @@ class Marker:
     corners_undistorted: Optional[List[Tuple[float, float]]] = None
     undistort_residual_px: Optional[List[float]] = None
     recovered: bool = False   # with Detector(recovery=...): the decoder rejected this quad, the board placed it (hamming_distance 255: bits not compared)
+    inverted: bool = False    # with Detector(inverted_markers=True): the marker is bright on dark and was read complemented (a3_get_marker_flags)
 
 
 @dataclass
@@ -234,7 +243,7 @@ class Detector:
     def __init__(self, config: DetectorConfig = None, dictionary: ARDictionary = None, device: int = 0,
                  refinement: Optional[CornerRefinement] = None, board=None, charuco_config: Optional[_lib.CharucoConfig] = None,
                  rectification: Optional[Rectification] = None, recovery=None, reduction: Optional[Reduction] = None,
-                 threshold_windows=None):
+                 threshold_windows=None, inverted_markers: bool = False):
         _one_view(reduction, rectification)
         if recovery is not None and board is None:
             raise ValueError("Detector(recovery=...) needs a board: recovery places rejected quads where the board says its markers are")
@@ -256,6 +265,9 @@ class Detector:
         # several adaptive-threshold windows (a3_set_threshold_windows; not in the reference): e.g. (3, 7, 15) -- every frame is
         # binarised at each radius and the candidates are merged on the device; one radius overrides config.threshold_window; None: off
         self.threshold_windows = threshold_windows
+        # bright-on-dark markers are read beside dark ones (a3_set_marker_polarity, OpenCV's detectInvertedMarker; not in the
+        # reference): Marker.inverted says which.  A bright rectangle is then a candidate marker too: see include/aruco3_hip.h
+        self.inverted_markers = inverted_markers
         self._ctx = None
         self._ctx_key = None
 
@@ -309,6 +321,7 @@ class Detector:
         _apply_rectification(self._ctx, self.rectification)
         _apply_reduction(self._ctx, self.reduction)
         _apply_threshold_windows(self._ctx, self.threshold_windows)
+        _apply_polarity(self._ctx, self.inverted_markers)
         return self._ctx
 
     # src/aruco.rs:52-121
@@ -333,12 +346,14 @@ class Detector:
         markers, per = ctx.detect_batch(ptr, mem, fmt, w, h, rs, fs, n, out_cap)
         refined = ctx.refined_corners() if refine else None
         rec = ctx.recovered_counts(n) if recover else None
+        flags = ctx.marker_flags() if self.inverted_markers else None
         out = []
         pos = 0
         for f in range(n):
             det = Detection()
             for i in range(pos, pos + int(per[f])):
-                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, recovered=_is_tail(rec, f, i - pos, per)))
+                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, recovered=_is_tail(rec, f, i - pos, per),
+                                           inverted=_inverted_at(flags, i)))
             pos += int(per[f])
             if populate:
                 view = (w // self.reduction.factor, h // self.reduction.factor) if self.reduction is not None else (w, h)
@@ -375,13 +390,15 @@ class Detector:
         refined = ctx.refined_corners() if refine else None
         undist = ctx.undistorted_corners() if dist else None
         rec = ctx.recovered_counts(n) if recover else None
+        flags = ctx.marker_flags() if self.inverted_markers else None
         out = []
         pos = 0
         for f in range(n):
             det = Detection()
             pp = []
             for i in range(pos, pos + int(per[f])):
-                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i), _is_tail(rec, f, i - pos, per)))
+                det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i), _is_tail(rec, f, i - pos, per),
+                                           _inverted_at(flags, i)))
                 pp.append(tuple(MarkerPose(float(q[0]), q[1:10].reshape(3, 3).copy(), q[10:13].copy()) for q in poses[i]))
             pos += int(per[f])
             out.append((det, pp))
@@ -416,7 +433,8 @@ class Detector:
         refined = ctx.refined_corners() if refine else None
         undist = ctx.undistorted_corners() if dist else None
         boards = ctx.board_poses()
-        dets = _detections(markers, per, refined, undist, ctx.recovered_counts(n) if recover else None)
+        dets = _detections(markers, per, refined, undist, ctx.recovered_counts(n) if recover else None,
+                           ctx.marker_flags() if self.inverted_markers else None)
         if _is_charuco(self.board):
             _fill_charuco(dets, ctx.charuco_corners())
         return [(d, BoardPose._from(boards[f])) for f, d in enumerate(dets)]
@@ -446,7 +464,8 @@ class Detector:
         markers, per, _ = ctx.detect_batch_pose(ptr, mem, fmt, w, h, rs, fs, n, marker_size_mm, intr, out_cap)
         refined = ctx.refined_corners() if refine else None
         undist = ctx.undistorted_corners() if dist else None
-        dets = _detections(markers, per, refined, undist, ctx.recovered_counts(n) if recover else None)
+        dets = _detections(markers, per, refined, undist, ctx.recovered_counts(n) if recover else None,
+                           ctx.marker_flags() if self.inverted_markers else None)
         _fill_charuco(dets, ctx.charuco_corners())
         poses = ctx.charuco_poses()
         return [(d, CharucoPose._from(poses[f])) for f, d in enumerate(dets)]
@@ -537,12 +556,12 @@ def _fill_charuco(dets: List[Detection], recs: np.ndarray) -> None:
         d.charuco_corners = np.stack([r["x"], r["y"]], axis=1).astype(np.float32).reshape(-1, 2)
 
 
-def _marker(m, refined=None, undist=None, recovered: bool = False) -> Marker:
+def _marker(m, refined=None, undist=None, recovered: bool = False, inverted: bool = False) -> Marker:
     c = m["corners"]
     return Marker(int(m["id"]), int(m["code"]), [(int(c[2 * i]), int(c[2 * i + 1])) for i in range(4)], int(m["hamming_distance"]),
                   None if refined is None else [(float(x), float(y)) for x, y in refined],
                   None if undist is None else [(float(x), float(y)) for x, y in undist[0]],
-                  None if undist is None else [float(r) for r in undist[1]], recovered)
+                  None if undist is None else [float(r) for r in undist[1]], recovered, inverted)
 
 
 def _undist_at(undist, i):
@@ -550,12 +569,18 @@ def _undist_at(undist, i):
     return None if undist is None else (undist[0][i], undist[1][i])
 
 
-def _detections(markers, per, refined=None, undist=None, rec=None) -> List[Detection]:
+def _inverted_at(flags, i) -> bool:
+    """marker i's A3_MARKER_INVERTED bit of Context.marker_flags() (None: the batch ran in mode DARK)"""
+    return flags is not None and bool(int(flags[i]) & _lib.MARKER_INVERTED)
+
+
+def _detections(markers, per, refined=None, undist=None, rec=None, flags=None) -> List[Detection]:
     out, pos = [], 0
     for f in range(len(per)):
         det = Detection()
         for i in range(pos, pos + int(per[f])):
-            det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i), _is_tail(rec, f, i - pos, per)))
+            det.markers.append(_marker(markers[i], refined[i] if refined is not None else None, _undist_at(undist, i), _is_tail(rec, f, i - pos, per),
+                                       _inverted_at(flags, i)))
         pos += int(per[f])
         out.append(det)
     return out
@@ -584,7 +609,9 @@ class BatchQueue:
         self._recovery = detector.recovery   # (likewise)
         self._reduction = detector.reduction   # (likewise)
         self._threshold_windows = detector.threshold_windows   # (likewise)
+        self._inverted = bool(detector.inverted_markers)   # (likewise)
         self._refine_on = [False] * depth
+        self._flags_on = [False] * depth
         self._keep = [None] * depth
         self._pose_batch = [False] * depth
         self._gates = gates
@@ -633,6 +660,8 @@ class BatchQueue:
         _apply_rectification(ctx, self._rectification)   # (this context's last batch has been collected: the queue is not full)
         _apply_reduction(ctx, self._reduction)
         _apply_threshold_windows(ctx, self._threshold_windows)
+        _apply_polarity(ctx, self._inverted)
+        self._flags_on[k] = self._inverted
         ctx.set_corner_refinement(self._refinement._c() if self._refinement is not None else None)
         self._refine_on[k] = self._refinement is not None
         if self._submitted < depth and self._board is not None:   # (each context's first batch: the board stays set on it)
@@ -660,7 +689,8 @@ class BatchQueue:
             self._keep[k] = None
         self.last_stepping = ctx.stats()["stepping"]
         dets = _detections(markers, per, ctx.refined_corners() if self._refine_on[k] else None,
-                           rec=ctx.recovered_counts(len(per)) if self._recovery is not None else None)
+                           rec=ctx.recovered_counts(len(per)) if self._recovery is not None else None,
+                           flags=ctx.marker_flags() if self._flags_on[k] else None)
         if _is_charuco(self._board):
             _fill_charuco(dets, ctx.charuco_corners())
         return dets

@@ -101,6 +101,9 @@ struct Batch {
     bool recover = false;
     a3_recover_config recover_cfg{};
     uint32_t recover_slots = 0, recover_cap = 0;   // board markers; records a frame's recovery can hold (ensure_back_buffers)
+    // a3_set_marker_polarity was A3_POLARITY_BOTH when the batch began: k_decode reads an all-lit border complemented, k_marker_flags
+    // leaves a flag word per marker for the edge fit and for a3_get_marker_flags
+    bool flags = false;
     uint32_t sides = 0;          // the side results all of this turns on, one bit per SideKind (a3_readback.h)
     bool has(int kind) const { return (sides >> kind & 1u) != 0; }
     // The call's frames as staged on the device (frames, of frames_W x frames_H pixels).  With a3_set_rectification or a3_set_reduction in
@@ -226,6 +229,9 @@ struct a3_ctx {
     // The side results (kSides, a3_readback.h), by kind: where the batch in flight has them on the device (ensure_back_buffers), the copy
     // finish_batch kept for the getters, and whether the last collected batch produced the kind.  (Poses have no kept copy: their flag
     // says that pose_buf holds the last batch's, for a3_pack_detections.)
+    // (The marker flags are a per-marker result outside the table -- a3_readback.h says why -- with members of their own below
+    // (flags_buf, flags_h, flags_valid): whoever changes how the per-marker kinds are sized, staged, re-fetched, kept or cleared changes
+    // the `b.flags` lines beside those loops in ensure_back_buffers, enqueue_back, finish_batch, begin_batch and finish_trivial too.)
     void* side_dev[kSideKinds] = {};
     std::vector<uint8_t> side_h[kSideKinds];
     bool side_valid[kSideKinds] = {};
@@ -235,6 +241,12 @@ struct a3_ctx {
     a3_refine_config refine_prm_cfg{};
     std::vector<float> refine_prm;
     DevBuf refined_buf;          // refined corners of the last batch on the device (8 floats per marker, marker order)
+    // a3_set_marker_polarity: the setting later batches capture; the flag words of the batch in flight on the device (marker order), the
+    // copy finish_batch kept for a3_get_marker_flags, and whether the last collected batch ran in mode A3_POLARITY_BOTH
+    int polarity = A3_POLARITY_DARK;
+    DevBuf flags_buf;
+    std::vector<uint32_t> flags_h;
+    bool flags_valid = false;
     // a3_set_board: the board later batches capture (board_ids; board_slots: one BoardSlot record per marker) and its device tables
     // (id -> slot, slot records), brought up to date at the next submit when board_version moved -- never while a batch of this
     // context is in flight, so a batch keeps the board it was submitted with
@@ -455,7 +467,7 @@ const void* refine_params_for(a3_ctx* ctx, const a3_refine_config& cfg) {
 // ChArUco: the per-frame slot records of charuco_tmp (the counts follow them)
 size_t charuco_slot_bytes(const Batch& b) { return ((size_t)b.n * b.charuco_nc * sizeof(a3_charuco_corner) + 255) & ~(size_t)255; }
 // what a3_readback.h lays a batch's staging out from
-ReadbackShape readback_shape(const Batch& b, size_t head_bytes) { return {b.n, b.guess, b.charuco_guess, head_bytes, b.want_pose, b.refined, b.undist, b.board, b.charuco, b.recover}; }
+ReadbackShape readback_shape(const Batch& b, size_t head_bytes) { return {b.n, b.guess, b.charuco_guess, head_bytes, b.want_pose, b.refined, b.undist, b.board, b.charuco, b.recover, b.flags}; }
 // the refinement kernel's parameters for the ChArUco setting `cfg` (its window and iteration settings; built once per setting)
 const void* charuco_params_for(a3_ctx* ctx, const a3_charuco_config& cfg) {
     if (ctx->charuco_prm.empty() || memcmp(&ctx->charuco_prm_cfg, &cfg, sizeof cfg) != 0) {
@@ -503,7 +515,7 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     // 166 against 161 us in alternating runs, a fence + ticket per workgroup and a serial tail costing more than the launch; removed.)
     DecodeStage dec = decode_stage(ctx);
     dec.n_frames = b.n; dec.max_cand = b.max_cand; dec.min_distance = min_corner_separation; dec.marker_cap = b.marker_cap;
-    dec.src = b.src; dec.W = (int)b.W; dec.H = (int)b.H; dec.few = b.n <= 64u;
+    dec.src = b.src; dec.W = (int)b.W; dec.H = (int)b.H; dec.few = b.n <= 64u; dec.inverted = b.flags;
     if (b.taps) dec.patches = ctx->patches.as<uint8_t>();
     dec.patch_cap = b.patch_cap;
     dec.grid_blocks = (int)std::min<uint32_t>(4096u, b.n * 128u);   // (grid-stride over the work list; 4096 workgroups that find nothing cost a one-frame call ~4 us)
@@ -530,6 +542,10 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
                                          .rec_cap = b.recover_cap, .rec_count = recovered, .n_frames = b.n, .out = ctx->markers_ptr, .out_cap = b.marker_cap,
                                          .per_frame = ctx->per_frame, .marker_total = d_marker_total, .err_flags = &ctx->head->err_flags}));
     }
+    uint32_t* const flags = b.flags ? ctx->flags_buf.as<uint32_t>() : nullptr;
+    if (b.flags)   // which markers of the final list were read inverted (ahead of the scaling and the refinement, which reads them)
+        A3_HIP(launch_marker_flags(st, {.markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap, .outs = dec.outs, .n_frames = b.n,
+                                        .max_cand = b.max_cand, .flags = flags}));
     // what everything behind the marker list samples and measures by: the decode stage's source, or with a reduction the caller's
     // full-size frames, on which the list's corners lie once k_scale_markers has mapped them up
     const bool reduced = b.plane == Batch::Plane::Reduced;
@@ -539,7 +555,7 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     float* const refined = b.refined ? ctx->refined_buf.as<float>() : nullptr;
     if (b.refined) {   // sub-pixel corners of the device-resident marker list, sampled from the same frames / grey plane as the decode stage
         const RefineLaunch rl{.src = back_src, .W = back_W, .H = back_H, .markers = ctx->markers_ptr, .n_dev = d_marker_total, .n = b.marker_cap,
-                              .params = refine_params_for(ctx, b.refine), .out = refined};
+                              .params = refine_params_for(ctx, b.refine), .out = refined, .flags = flags};
         A3_HIP(b.refine.method == A3_REFINE_EDGES ? launch_refine_edges(st, rl) : launch_refine_corners(st, rl));
     }
     if (b.undist)   // undistorted pixel corners of the same markers (of their refined corners with refinement on)
@@ -587,6 +603,7 @@ int enqueue_back(a3_ctx* ctx, hipStream_t st, const Batch& b) {
     A3_HIP(hipMemcpyAsync(ctx->pinned, ctx->head, rb.head.bytes + rb.markers.bytes, hipMemcpyDeviceToHost, st));
     for (int k = 0; k < kSideKinds; k++)
         if (b.has(k)) A3_HIP(stage(rb.side[k], ctx->side_dev[k]));
+    if (b.flags) A3_HIP(stage(rb.flags, flags));
     if (b.charuco) {
         A3_HIP(hipMemcpyAsync(at<uint8_t>(ctx->pinned, rb.charuco_total), charuco_counts + b.n, 4, hipMemcpyDeviceToHost, st));
         A3_HIP(stage(rb.charuco, ctx->charuco_buf.p));
@@ -663,6 +680,7 @@ int ensure_back_buffers(a3_ctx* ctx, Batch& b, size_t head_bytes) {
     if (b.want_pose) { A3_HIP(ctx->pose_buf.ensure((size_t)b.marker_cap * 2 * sizeof(a3_pose))); side[kSidePoses] = ctx->pose_buf.p; }
     if (b.refined) { A3_HIP(ctx->refined_buf.ensure((size_t)b.marker_cap * 8 * sizeof(float))); side[kSideRefined] = ctx->refined_buf.p; }
     if (b.board) { A3_HIP(ctx->board_buf.ensure((size_t)b.n * sizeof(a3_board_pose))); side[kSideBoard] = ctx->board_buf.p; }
+    if (b.flags) A3_HIP(ctx->flags_buf.ensure(std::max<size_t>(b.marker_cap, 1) * kFlagsRec));
     if (b.undist) {
         A3_HIP(ctx->undist_buf.ensure((size_t)b.marker_cap * 12 * sizeof(float)));
         side[kSideUndist] = ctx->undist_buf.p; side[kSideUndistRes] = ctx->undist_buf.as<float>() + (size_t)b.marker_cap * 8;
@@ -1053,6 +1071,7 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         A3_HIP(fetch(rb.markers, ctx->markers_ptr));
         for (int k = 0; k < kSideKinds; k++)
             if (b.has(k) && !kSides[k].per_frame) A3_HIP(fetch(rb.side[k], ctx->side_dev[k]));
+        if (b.flags) A3_HIP(fetch(rb.flags, ctx->flags_buf.p));
         A3_HIP(hipStreamSynchronize(ctx->stream));
     }
     if (total) {
@@ -1064,6 +1083,8 @@ int finish_batch(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, ui
         if (b.has(k) && !kSides[k].per_frame && kSides[k].kept) ctx->side_h[k].assign(h, h + (size_t)total * kSides[k].rec);
         ctx->side_valid[k] = b.has(k);
     }
+    if (b.flags) ctx->flags_h.assign(at<uint32_t>(hp, rb.flags), at<uint32_t>(hp, rb.flags) + total);
+    ctx->flags_valid = b.flags;
     ctx->charuco_valid = b.charuco;
     if (b.taps) {
         const uint32_t* hc32 = reinterpret_cast<const uint32_t*>(ctx->pinned_counts);
@@ -1270,7 +1291,7 @@ void a3_destroy(a3_ctx* ctx) {
                       &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_d, &ctx->hsum, &ctx->pose_buf, &ctx->wtab, &ctx->refined_buf,
                       &ctx->board_slot_of, &ctx->board_slot_rec, &ctx->board_buf, &ctx->undist_buf, &ctx->charuco_tab, &ctx->charuco_tmp,
                       &ctx->charuco_buf, &ctx->charuco_und, &ctx->charuco_pose_buf, &ctx->solve_in,
-                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out, &ctx->plane, &ctx->merged_count};
+                      &ctx->solve_scratch, &ctx->solve_big, &ctx->solve_out, &ctx->rect_in, &ctx->rect_out, &ctx->plane, &ctx->merged_count, &ctx->flags_buf};
     for (DevBuf* b : bufs) b->release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->pinned_counts) (void)hipHostFree(ctx->pinned_counts);
@@ -1479,6 +1500,8 @@ static int begin_batch(a3_ctx* ctx, const void* pixels, int memory, int fmt, uin
     b.taps = ctx->debug_taps;
     b.sample_frames = ctx->debug_sample_frames;
     b.profiling = ctx->profiling; b.profile_every = ctx->profile_every;
+    b.flags = ctx->polarity == A3_POLARITY_BOTH;
+    ctx->flags_valid = false;   // (as the kinds that begin_clears: a3_get_marker_flags is refused until this batch is collected)
     b.sides = sides_on(readback_shape(b, 0));
     for (int k = 0; k < kSideKinds; k++)
         if (kSides[k].begin_clears) ctx->side_valid[k] = false;
@@ -1514,6 +1537,7 @@ static void finish_trivial(a3_ctx* ctx, uint32_t* per_frame_count) {
         ctx->side_valid[k] = b.has(k);
     }
     ctx->h_charuco.clear(); ctx->charuco_valid = b.charuco;
+    ctx->flags_h.clear(); ctx->flags_valid = b.flags;
 }
 
 static int run_batch_with_retries(a3_ctx* ctx, a3_marker* out, a3_pose* poses, size_t out_cap, uint32_t* per_frame_count, size_t* out_n) {
@@ -2973,6 +2997,28 @@ int a3_get_threshold_windows(const a3_ctx* ctx, uint32_t* radii, size_t cap, siz
     if (ctx->n_windows > cap) return fail(const_cast<a3_ctx*>(ctx), A3_ERR_CAPACITY, "a3_get_threshold_windows: cap is smaller than the number of windows set");
     for (uint32_t k = 0; k < ctx->n_windows; k++) radii[k] = ctx->windows[k];
     return A3_OK;
+}
+
+// ---- inverted markers (an extension beyond the reference; contract in include/aruco3_hip.h) ----
+int a3_set_marker_polarity(a3_ctx* ctx, int mode) {
+    if (!ctx) return A3_ERR_INVALID;
+    if (mode != A3_POLARITY_DARK && mode != A3_POLARITY_BOTH) return fail(ctx, A3_ERR_INVALID, "a3_set_marker_polarity: unknown mode");
+    ctx->polarity = mode;
+    return A3_OK;
+}
+
+int a3_get_marker_polarity(const a3_ctx* ctx, int* mode) {
+    if (!ctx || !mode) return A3_ERR_INVALID;
+    *mode = ctx->polarity;
+    return A3_OK;
+}
+
+int a3_get_marker_flags(a3_ctx* ctx, uint32_t* dst, size_t cap_markers, size_t* n) {
+    if (!ctx || !n || (!dst && cap_markers)) return A3_ERR_INVALID;
+    *n = 0;
+    return get_last(ctx, ctx->flags_valid, ctx->flags_h.data(), ctx->flags_h.size() * kFlagsRec, kFlagsRec, dst, cap_markers, n,
+                    "a3_get_marker_flags: the last collected batch did not run in mode A3_POLARITY_BOTH",
+                    "a3_get_marker_flags: cap_markers is smaller than the number of markers");
 }
 
 int a3_get_reduction(const a3_ctx* ctx, a3_reduction* r, int* enabled) {

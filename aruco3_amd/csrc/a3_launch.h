@@ -134,10 +134,12 @@ struct DecodeStage {
     // caller then hands to launch_compact_markers as its cand_count.  big_scratch: needed when max_cand > frame_cand_lds_slots().
     uint32_t windows = 0, plane_cand = 0; uint32_t* merged_count = nullptr;
     // launch_decode: k_decode over the work list.  n: cells per side; patches (nullable, debug taps): patch_cap warped patches are kept;
-    // per_frame: nullable; few (at most 64 frames): all four waves of a workgroup run the stages behind the sampling.
+    // per_frame: nullable; few (at most 64 frames): all four waves of a workgroup run the stages behind the sampling.  inverted
+    // (a3_set_marker_polarity, A3_POLARITY_BOTH): k_decode's instantiations that read a bit matrix with an all-lit perimeter complemented
+    // and give it decode_ok 2; false: the instantiations without any of that.
     PixelSrc src{}; int W = 0, H = 0; uint32_t n = 0, max_taps = 0; const uint64_t* dict = nullptr; uint32_t n_codes = 0, tau = 0; int filter = 0;
     const float* wtab = nullptr; void* outs = nullptr; uint8_t* patches = nullptr; uint32_t patch_cap = 0; uint32_t* per_frame = nullptr;
-    int grid_blocks = 0; bool few = false;
+    int grid_blocks = 0; bool few = false, inverted = false;
     // ... a3_debug_kernel_time only: k_projection runs first (the product's projections come from k_frame_candidates); k_decode stops
     // early: 1 = no sampling, 2 / 3 / 4 = after sampling / Otsu / bits, 0 and 5 = the whole kernel
     bool projection = false; int variant = 0;
@@ -149,6 +151,16 @@ hipError_t launch_frame_candidates(hipStream_t st, const DecodeStage& d);
 hipError_t launch_merge_candidates(hipStream_t st, const DecodeStage& d);
 hipError_t launch_decode(hipStream_t st, const DecodeStage& d);
 hipError_t launch_compact_markers(hipStream_t st, const DecodeStage& d);
+// The flag words of a batch's final marker list (a3_get_marker_flags), one lane per marker: flags[i] = A3_MARKER_INVERTED when the
+// DecodeOut record at slot markers[i].frame * max_cand + markers[i].candidate_index has decode_ok == 2, else 0 (also for a marker whose
+// frame or index lies outside n_frames x max_cand).  markers: the list (capacity n, count *n_dev) as launch_compact_markers or
+// launch_recover_merge left it, frames batch-relative; outs: the DecodeOut records launch_decode wrote; flags: n words.  Runs ahead of
+// launch_scale_markers and the refinement, which reads the flags.
+struct MarkerFlagsLaunch {
+    const a3_marker* markers = nullptr; const unsigned int* n_dev = nullptr; uint32_t n = 0; const void* outs = nullptr;
+    uint32_t n_frames = 0, max_cand = 0; uint32_t* flags = nullptr;
+};
+hipError_t launch_marker_flags(hipStream_t st, const MarkerFlagsLaunch& m);
 hipError_t launch_weight_table(hipStream_t st, uint32_t S, uint32_t n, uint32_t max_taps, float* wtab);
 hipError_t launch_pack_detections(hipStream_t st, const a3_marker* markers, const a3_pose* poses, const uint32_t* per_frame, uint32_t n_frames,
                                   uint32_t first_frame_global, uint32_t maxm, void* dst, unsigned int* overflow);
@@ -195,6 +207,9 @@ struct RefineLaunch {
     const float* pts = nullptr, * cell_px = nullptr; uint32_t n = 0;
     const void* params = nullptr;   // refine_params()
     float* out = nullptr;
+    // launch_refine_edges with markers only (nullable): the list's flag words (launch_marker_flags); a marker flagged A3_MARKER_INVERTED
+    // is bright inside and its gradients are taken with the opposite sign.  nullptr, a zero word, stand-alone quads: dark inside.
+    const uint32_t* flags = nullptr;
 };
 hipError_t launch_refine_corners(hipStream_t st, const RefineLaunch& r);
 

@@ -11,11 +11,14 @@
 namespace a3 {
 
 // what the batch record knows: frames, markers and ChArUco records read back speculatively, the bytes of the head, what is switched on
-// (recover: the batch ran board-aided recovery)
-struct ReadbackShape { uint32_t n, guess, charuco_guess; size_t head_bytes; bool pose, refine, undist, board, charuco; bool recover = false; };
+// (recover: the batch ran board-aided recovery; flags: it ran in mode A3_POLARITY_BOTH and carries a flag word per marker)
+struct ReadbackShape { uint32_t n, guess, charuco_guess; size_t head_bytes; bool pose, refine, undist, board, charuco; bool recover = false; bool flags = false; };
 
 // The side results: arrays of fixed-size records that travel with a batch's marker list, in the order they lie in the staging buffer.
-// (The ChArUco corner records are not among them: a variable number, with a guess, a total and a tail fetch of their own.)
+// (The ChArUco corner records are not among them: a variable number, with a guess, a total and a tail fetch of their own.  Nor are the
+// marker flags of a3_get_marker_flags, one uint32_t per marker: the table's kinds are written out once more, by number, in
+// tests/readback_layout.cpp, so the flags have a span of their own behind everything else -- Readback::flags, kFlagsRec bytes a marker --
+// and every layout without them is byte for byte what it was.)
 enum SideKind { kSidePoses, kSideRefined, kSideBoard, kSideUndist, kSideUndistRes, kSideCharucoPoses, kSideRecovered, kSideKinds };
 struct SideDesc {
     size_t rec;                          // the bytes of one record
@@ -44,11 +47,12 @@ inline uint32_t sides_on(const ReadbackShape& s) {
 }
 
 struct Span { size_t off = 0, bytes = 0; };
-struct Readback { Span head, markers, charuco_total, charuco, side[kSideKinds]; size_t end = 0; };
+constexpr size_t kFlagsRec = sizeof(uint32_t);
+struct Readback { Span head, markers, charuco_total, charuco, side[kSideKinds], flags; size_t end = 0; };
 template <typename T> inline T* at(void* base, const Span& s) { return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + s.off); }
 
 // The spans follow each other without padding: head, markers, then the side results in the table's order, the ChArUco records directly
-// ahead of their poses; the span of a feature that is off is empty.  `refetch`: the layout of refetch_layout below.
+// ahead of their poses, the marker flags last; the span of a feature that is off is empty.  `refetch`: the layout of refetch_layout below.
 inline Readback readback_layout(const ReadbackShape& s, bool refetch = false) {
     Readback r;
     auto put = [&r](Span& sp, bool on, size_t count, size_t elem) { sp = {r.end, on ? count * elem : 0}; r.end += sp.bytes; };
@@ -62,6 +66,7 @@ inline Readback readback_layout(const ReadbackShape& s, bool refetch = false) {
         const SideDesc& d = kSides[k];
         put(r.side[k], d.on(s) && !(refetch && d.per_frame), d.per_frame ? s.n : s.guess, d.rec);
     }
+    put(r.flags, s.flags, s.guess, kFlagsRec);   // per marker: staged with the guess, fetched again with the whole list
     return r;
 }
 // The marker guess was short: the head, the per-frame kinds and the ChArUco records have been consumed, and the whole list of `total`

@@ -638,7 +638,10 @@ __device__ __forceinline__ void compact_frame_wave(uint32_t f, int lane, const D
 // sample order (round 1): 116 us; 64 threads, 8 x 8 blocked order: 98 us; 256 threads sampling, the first wave doing the rest:
 // 94 us -- and 7 us less than the 64-thread version inside the pipeline, where the frames are not in any cache.
 // Y422: the frames are packed 4:2:2 (src.fmt A3_FMT_YUYV8 / A3_FMT_UYVY8; see grey_tap)
-template <int NT, int PT, bool Y422 = false>
+// BOTH: a3_set_marker_polarity's A3_POLARITY_BOTH (include/aruco3_hip.h): a bit matrix whose perimeter is lit all round is read
+// complemented, and DecodeOut.decode_ok is 2 for it.  A template parameter for Y422's reason: with BOTH == false nothing below differs
+// from the kernel without it, so the default instantiations compile to what they were.
+template <int NT, int PT, bool Y422 = false, bool BOTH = false>
 __global__ __launch_bounds__(NT, kDecodeWaves) void k_decode(PixelSrc src, int W, int H, uint32_t first_frame,
                                                 const uint16_t* __restrict__ fin_xy, const uint32_t* __restrict__ work,
                                                 const unsigned int* __restrict__ work_count, uint32_t max_cand, uint32_t S, uint32_t n,
@@ -854,16 +857,24 @@ __global__ __launch_bounds__(NT, kDecodeWaves) void k_decode(PixelSrc src, int W
             {   // the marker's border must be black all round: one lane per border cell (left, right, top, bottom x n)
                 const uint32_t end = n ? n - 1 : 0;
                 int lit = 0;
+                [[maybe_unused]] int all_lit = 1;
                 for (uint32_t t = (uint32_t)tid; t < 4u * n; t += PT) {
                     const uint32_t side = t / n, i = t - side * n;
-                    lit |= s_bits[side == 0 ? i * n : (side == 1 ? i * n + end : (side == 2 ? i : end * n + i))];
+                    const int cell = s_bits[side == 0 ? i * n : (side == 1 ? i * n + end : (side == 2 ? i : end * n + i))];
+                    lit |= cell;
+                    if constexpr (BOTH) all_lit &= cell;
                 }
                 const int any_lit = (PT == NT ? __syncthreads_or(lit) : (int)(__ballot(lit) != 0ull));
+                if constexpr (BOTH) {   // no cell lit: read dark (this test first); every cell lit: read inverted; else no codes
+                    const int every_lit = (PT == NT ? __syncthreads_and(all_lit) : (int)(__ballot(!all_lit) == 0ull));
+                    if (tid == 0) s_have = !any_lit ? 1 : (every_lit ? 2 : 0);
+                } else
                 if (tid == 0) s_have = !any_lit;
             }
             POST_SYNC();
             {
                 const uint32_t inner = n >= 2 ? n - 2 : 0, cells = inner * inner;   // <= 64 cells, 4 rotations
+                [[maybe_unused]] const uint8_t flip = BOTH ? (uint8_t)(s_have == 2) : (uint8_t)0;
                 if (s_have) {
                     for (uint32_t t = (uint32_t)tid; t < 4u * cells; t += PT) {
                         const uint32_t r = t / cells, idx = t - r * cells;
@@ -871,7 +882,7 @@ __global__ __launch_bounds__(NT, kDecodeWaves) void k_decode(PixelSrc src, int W
                         // rotation r of the bit matrix, read row-major
                         uint32_t sy, sx;
                         rotated_source(r, n, y, x, &sy, &sx);
-                        if (s_bits[sy * n + sx]) atomicOr(reinterpret_cast<unsigned long long*>(&s_codes[r]), 1ull << (cells - 1 - idx));
+                        if (BOTH ? (s_bits[sy * n + sx] ^ flip) != 0 : s_bits[sy * n + sx] != 0) atomicOr(reinterpret_cast<unsigned long long*>(&s_codes[r]), 1ull << (cells - 1 - idx));
                     }
                 }
             }
@@ -1222,25 +1233,20 @@ hipError_t launch_decode(hipStream_t st, const DecodeStage& d) {
     // frames against 39), and on one wave -- no workgroup barriers -- when thousands of candidates are in flight and only the
     // throughput counts (BASELINE config 2: decode stage 0.123 ms against 0.130 with one wave per candidate throughout).
     const size_t lds = decode_lds_bytes(d.S, d.n, d.max_taps);
-    if (d.src.fmt == A3_FMT_YUYV8 || d.src.fmt == A3_FMT_UYVY8) {   // packed 4:2:2: the samplers' instantiation of their own (grey_tap)
-        if (d.few)
-            hipLaunchKernelGGL((k_decode<256, 256, true>), dim3(d.grid_blocks), dim3(256), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy, d.work,
-                               d.work_count, d.max_cand, d.S, d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab,
-                               reinterpret_cast<DecodeOut*>(d.outs), d.patches, d.patch_cap, d.per_frame, d.variant);
-        else
-            hipLaunchKernelGGL((k_decode<kDecodeThreads, 64, true>), dim3(d.grid_blocks), dim3(kDecodeThreads), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy,
-                               d.work, d.work_count, d.max_cand, d.S, d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab,
-                               reinterpret_cast<DecodeOut*>(d.outs), d.patches, d.patch_cap, d.per_frame, d.variant);
-        return hipGetLastError();
-    }
-    if (d.few)
-        hipLaunchKernelGGL((k_decode<256, 256>), dim3(d.grid_blocks), dim3(256), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy, d.work, d.work_count,
-                           d.max_cand, d.S, d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab, reinterpret_cast<DecodeOut*>(d.outs), d.patches,
-                           d.patch_cap, d.per_frame, d.variant);
-    else
-        hipLaunchKernelGGL((k_decode<kDecodeThreads, 64>), dim3(d.grid_blocks), dim3(kDecodeThreads), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy, d.work,
-                           d.work_count, d.max_cand, d.S, d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab, reinterpret_cast<DecodeOut*>(d.outs),
-                           d.patches, d.patch_cap, d.per_frame, d.variant);
+    // (packed 4:2:2: the samplers' instantiation of their own, grey_tap; inverted: a3_set_marker_polarity's A3_POLARITY_BOTH)
+    const bool y422 = d.src.fmt == A3_FMT_YUYV8 || d.src.fmt == A3_FMT_UYVY8;
+    auto launch = [&](auto kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(d.grid_blocks), dim3(threads), lds, st, d.src, d.W, d.H, d.first_frame, d.fin_xy, d.work, d.work_count, d.max_cand, d.S,
+                           d.n, d.max_taps, d.dict, d.n_codes, d.tau, d.filter, recs, d.wtab, reinterpret_cast<DecodeOut*>(d.outs), d.patches, d.patch_cap,
+                           d.per_frame, d.variant);
+    };
+    auto pick = [&](auto y, auto both) {
+        constexpr bool Y = decltype(y)::value, B = decltype(both)::value;
+        if (d.few) launch(k_decode<256, 256, Y, B>, 256);
+        else launch(k_decode<kDecodeThreads, 64, Y, B>, kDecodeThreads);
+    };
+    if (d.inverted) { if (y422) pick(std::true_type{}, std::true_type{}); else pick(std::false_type{}, std::true_type{}); }
+    else { if (y422) pick(std::true_type{}, std::false_type{}); else pick(std::false_type{}, std::false_type{}); }
     return hipGetLastError();
 }
 
@@ -1254,6 +1260,27 @@ hipError_t launch_compact_markers(hipStream_t st, const DecodeStage& c) {
     else
         hipLaunchKernelGGL(k_compact_markers, dim3(1), dim3(256), 0, st, outs, c.fin_xy, c.fin_count, c.n_frames, c.first_frame, c.max_cand, c.markers,
                            c.marker_cap, c.per_frame, c.marker_total, c.err_flags, c.cand_count, c.cand_pre_total);
+    return hipGetLastError();
+}
+
+// a3_get_marker_flags: one lane per marker of the final list (behind the gather and the recovery merge): A3_MARKER_INVERTED iff the
+// candidate the marker names was read inverted (decode_ok == 2).  A marker that names no slot of the tables gets 0.
+__global__ __launch_bounds__(256) void k_marker_flags(const a3_marker* __restrict__ markers, const unsigned int* __restrict__ n_dev, uint32_t cap,
+                                                      const DecodeOut* __restrict__ outs, uint32_t n_frames, uint32_t max_cand,
+                                                      uint32_t* __restrict__ flags) {
+    const uint32_t total = min(cap, *n_dev);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const uint32_t f = markers[i].frame, k = markers[i].candidate_index;
+        const bool in_table = f < n_frames && k < max_cand;
+        flags[i] = in_table && outs[(size_t)f * max_cand + k].decode_ok == 2 ? A3_MARKER_INVERTED : 0u;
+    }
+}
+
+hipError_t launch_marker_flags(hipStream_t st, const MarkerFlagsLaunch& m) {
+    if (m.n == 0) return hipSuccess;
+    const uint32_t want = (m.n + 255u) / 256u, blocks = want < 1024u ? want : 1024u;
+    hipLaunchKernelGGL(k_marker_flags, dim3(blocks), dim3(256), 0, st, m.markers, m.n_dev, m.n, reinterpret_cast<const DecodeOut*>(m.outs), m.n_frames,
+                       m.max_cand, m.flags);
     return hipGetLastError();
 }
 

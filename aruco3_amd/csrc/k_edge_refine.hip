@@ -76,10 +76,12 @@ __device__ __forceinline__ float edge_sample(const uint8_t* __restrict__ fb, uns
 
 // markers != nullptr: the accepted markers of a batch (min(n, *n_dev) of them), range from the quad's cell size.
 // markers == nullptr: n / 4 caller quads `pts` of frame 0, range from cell_px[4 u] (nullable).  out: 8 floats per quad.
+// flags (with markers; nullable): the list's flag words -- a3_set_marker_polarity's A3_POLARITY_BOTH.
 template <int kKind>
 __global__ __launch_bounds__(256) void k_refine_edges(PixelSrc src, EdgePixel pix, uint32_t W, uint32_t H, const a3_marker* __restrict__ markers,
                                                       const unsigned int* __restrict__ n_dev, const float* __restrict__ pts,
-                                                      const float* __restrict__ cell_px, uint32_t n, EdgeParams p, float* __restrict__ out) {
+                                                      const float* __restrict__ cell_px, uint32_t n, EdgeParams p, float* __restrict__ out,
+                                                      const uint32_t* __restrict__ flags /*nullable: every quad dark inside*/) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int side = lane >> 4, station = lane & 15;
     const uint32_t quads = markers ? min(n, *n_dev) : n / 4u;
@@ -111,6 +113,8 @@ __global__ __launch_bounds__(256) void k_refine_edges(PixelSrc src, EdgePixel pi
             have_cell = cell_px != nullptr;
             if (have_cell) cell = cell_px[4 * (size_t)u];
         }
+        // a marker flagged A3_MARKER_INVERTED is bright inside: g_j = S_(j-2) - S_(j+2), the exact negation (wave-uniform)
+        const bool inverted = markers && flags && (flags[u] & A3_MARKER_INVERTED) != 0u;
         const int r = have_cell ? edge_range(p, cell) : (int)p.win_half;
         const float reach = (float)(2 * r);
         const uint8_t* fb = src.base + (size_t)frame * src.frame_stride;
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(256) void k_refine_edges(PixelSrc src, EdgePixel pi
                 const float o = (float)i * 0.5f;
                 const float v = edge_sample<kKind>(fb, src.row_stride, pix, (int)W, (int)H, px + o * Nx, py + o * Ny);
                 if (i >= -2 * r + 2) {   // s0 = S_(i-4)
-                    const float gj = v - s0, oj = (float)(i - 2) * 0.5f;
+                    const float gj = inverted ? s0 - v : v - s0, oj = (float)(i - 2) * 0.5f;
                     const float wj = gj > 0.0f ? gj * gj : 0.0f;
                     gmax = gj > gmax ? gj : gmax;
                     sw += wj;
@@ -192,7 +196,7 @@ hipError_t launch_refine_edges(hipStream_t st, const RefineLaunch& r) {
     const bool plane = fmt == kFmtGreyPlane;
     const EdgePixel px{plane ? 1u : (uint32_t)format_bpp(fmt), plane ? 0u : (uint32_t)std::max(format_luma_offset(fmt), 0)};
     const dim3 grid(std::min<uint32_t>((quads + 3u) / 4u, 1024u));
-#define A3_EDGE_LAUNCH(kind) hipLaunchKernelGGL(k_refine_edges<kind>, grid, dim3(256), 0, st, r.src, px, r.W, r.H, r.markers, r.n_dev, r.pts, r.cell_px, r.n, p, r.out)
+#define A3_EDGE_LAUNCH(kind) hipLaunchKernelGGL(k_refine_edges<kind>, grid, dim3(256), 0, st, r.src, px, r.W, r.H, r.markers, r.n_dev, r.pts, r.cell_px, r.n, p, r.out, r.flags)
     if (fmt == A3_FMT_RGB8 || fmt == A3_FMT_RGBA8) A3_EDGE_LAUNCH(1);
     else if (fmt == A3_FMT_BGRA8) A3_EDGE_LAUNCH(2);
     else A3_EDGE_LAUNCH(0);

@@ -246,7 +246,9 @@ int  a3_host_unregister(void *p);
 int  a3_get_stats(const a3_ctx *ctx, a3_stats *stats);
 
 /* Detection.grey / .candidates / .homographies of the last batch (src/aruco.rs:16-21,115-120),
- * plus the thresholded image; host destinations. */
+ * plus the thresholded image; host destinations.  decode_ok of a candidate: 0 = no codes (its bit matrix failed the border test),
+ * 1 = read dark (no perimeter cell lit: the reference), 2 = read inverted (every perimeter cell lit; codes4 are the complemented
+ * matrix's).  2 only comes from a batch that ran in mode A3_POLARITY_BOTH (a3_set_marker_polarity). */
 int  a3_download_grey(a3_ctx *ctx, uint32_t frame, uint8_t *dst);
 int  a3_download_thresholded(a3_ctx *ctx, uint32_t frame, uint8_t *dst);
 int  a3_candidate_count(a3_ctx *ctx, uint32_t frame, uint32_t *n_pre, uint32_t *n_final);
@@ -331,7 +333,12 @@ int  a3_estimate_pose_normalized(a3_ctx *ctx, const float *points_xy, size_t n, 
  *   - c = c'; stop after a pass in which no corner moved more than min_shift in x or y, or after max_iterations passes (0: the start).
  * The fit assumes straight sides.  Through an uncorrected lens a side is curved, and the line fitted to its middle three quarters
  * meets its neighbour off the true corner by about the side's sagitta: use SUBPIX there, or rectify (a3_set_rectification) -- on
- * rectified frames the sides are straight again.  Out of scope: inverted (bright-inside) markers, and reverting single corners. */
+ * rectified frames the sides are straight again.
+ * Inverted (bright-inside) markers: in a batch that ran in mode A3_POLARITY_BOTH (a3_set_marker_polarity), a marker whose flag word is
+ * A3_MARKER_INVERTED takes g_j = S_(j-2) - S_(j+2) -- the negation, which is exact -- and every other line above stands as it is
+ * (tests/inverted_edge_oracle.c restates it with a polarity per quad).  A marker whose flag is 0, and every marker of a batch in mode
+ * A3_POLARITY_DARK, takes the arithmetic above.  SUBPIX does not depend on the polarity.  The stand-alone a3_refine_corners has no flags:
+ * its quads are dark inside.  Out of scope: reverting single corners. */
 enum { A3_REFINE_NONE = 0, A3_REFINE_SUBPIX = 1, A3_REFINE_EDGES = 2 };
 #define A3_REFINE_EDGES_LIVE_LEVEL 20   /* grey levels: the least outward gradient of a live station (method A3_REFINE_EDGES) */
 typedef struct a3_refine_config {
@@ -1338,6 +1345,39 @@ int  a3_get_reduction(const a3_ctx *ctx, a3_reduction *r, int *enabled);
 #define A3_MAX_THRESHOLD_WINDOWS 4
 int  a3_set_threshold_windows(a3_ctx *ctx, const uint32_t *radii, size_t n);   /* NULL or n = 0: off */
 int  a3_get_threshold_windows(const a3_ctx *ctx, uint32_t *radii, size_t cap, size_t *n);
+
+/* Inverted markers: bright-on-dark markers detected beside dark ones.  NOT in the reference, which rejects a quad whose perimeter cells
+ * are lit (src/aruco.rs:287-292): an opt-in extension (OpenCV's detectInvertedMarker), A3_POLARITY_DARK by default; a context that
+ * never sets A3_POLARITY_BOTH (or set A3_POLARITY_DARK last) launches exactly what it launched before and returns the same bits.
+ *
+ * The rule in mode A3_POLARITY_BOTH, on a candidate's n x n bit matrix exactly as it stands after resize and `> 127`:
+ *   - no perimeter cell lit: as in mode DARK (this test comes first); decode_ok = 1;
+ *   - every perimeter cell lit: every cell of the matrix is complemented; the four rotated codes, find_nearest, the choice of the
+ *     rotation, the tau filter and corners.rotate_left run on the complemented matrix exactly as they do on a dark marker's;
+ *     decode_ok = 2 (a3_download_homographies), and code and codes4 are the complemented matrix's;
+ *   - anything else: no codes, decode_ok = 0.
+ * Nothing ahead of the bit matrix changes: the contour stage traces the border of a bright quad on a dark ground as it traces a dark
+ * one's, so the quad is a candidate in either mode.
+ * a3_get_marker_flags: one word per marker of the last collected batch, in the order of `out`: A3_MARKER_INVERTED iff the decode_ok of
+ * the candidate that (frame, candidate_index) names is 2; all other bits are 0.  This holds for markers recovered from a board
+ * (a3_set_board_recovery) too: a recovered quad whose border was mixed has decode_ok 0 and flag 0.  Like a3_get_refined_corners:
+ * A3_ERR_INVALID when that batch ran in mode DARK, A3_ERR_CAPACITY when cap_markers is short (*n says how many there are); and
+ * A3_ERR_INVALID between a submit and its collect.  The flags follow the marker list through chunked batches, re-runs, the re-fetch of
+ * a list longer than its guess, and submit / collect.
+ * a3_set_marker_polarity applies to batches submitted after the call; a value other than the two modes is A3_ERR_INVALID and the
+ * setting stays.  Corner refinement by A3_REFINE_EDGES reads the flags (see there); SUBPIX, poses, boards, ChArUco, reduction,
+ * rectification and several threshold windows compose unchanged.
+ * BOTH accepts more than DARK on the same frame: a white quiet zone around a dark marker, or any bright rectangle, is itself a quad
+ * whose perimeter is lit all round, and its complemented interior is looked up like a marker's.  With filter_high_bit_errors on and a
+ * dictionary of large tau (ARUCO_MIP_36H12, CHILITAGS) such quads pass the filter often; with ARUCO and APRILTAG_16H5 none did on the
+ * project's test frames (DESIGN.md section 4.22 has the counts).  The markers read dark are the same in both modes.
+ * Out of scope: an inverted-only mode, polarity in a3_pack_detections records, inverted rendering in a3_synth_render, flags for the
+ * stand-alone a3_refine_corners, inverted ChArUco boards (the chessboard corner stage assumes dark markers on white squares). */
+enum { A3_POLARITY_DARK = 0 /* default: the reference */, A3_POLARITY_BOTH = 1 /* OpenCV's detectInvertedMarker */ };
+#define A3_MARKER_INVERTED 1u
+int  a3_set_marker_polarity(a3_ctx *ctx, int mode);            /* batches submitted after the call; another value: A3_ERR_INVALID */
+int  a3_get_marker_polarity(const a3_ctx *ctx, int *mode);
+int  a3_get_marker_flags(a3_ctx *ctx, uint32_t *dst, size_t cap_markers, size_t *n);   /* last collected batch, marker order */
 
 /* ARDictionary::find_nearest for n codes (src/dictionaries.rs:160-196) and calculate_tau (:129-138) */
 int  a3_find_nearest(a3_ctx *ctx, const uint64_t *bits, size_t n, uint32_t *idx, uint8_t *dist);

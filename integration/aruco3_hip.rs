@@ -75,6 +75,9 @@ pub const A3_PROFILE_THRESHOLD_SAMPLED: c_int = 3;
 pub const A3_REFINE_NONE: u32 = 0;
 pub const A3_REFINE_SUBPIX: u32 = 1;
 pub const A3_REFINE_EDGES: u32 = 2;
+pub const A3_POLARITY_DARK: c_int = 0; // a3_set_marker_polarity: the reference (default)
+pub const A3_POLARITY_BOTH: c_int = 1; // ... bright-on-dark markers are read too (OpenCV's detectInvertedMarker)
+pub const A3_MARKER_INVERTED: u32 = 1; // a3_get_marker_flags: the marker was read complemented
 pub const A3_BOARD_NONE: u32 = 0;
 pub const A3_BOARD_OK: u32 = 1;
 pub const A3_DIST_NONE: u32 = 0;
@@ -715,6 +718,9 @@ extern "C" {
     pub fn a3_get_reduction(ctx: *const A3Ctx, r: *mut A3Reduction, enabled: *mut c_int) -> c_int;
     pub fn a3_set_threshold_windows(ctx: *mut A3Ctx, radii: *const u32, n: usize) -> c_int;
     pub fn a3_get_threshold_windows(ctx: *const A3Ctx, radii: *mut u32, cap: usize, n: *mut usize) -> c_int;
+    pub fn a3_set_marker_polarity(ctx: *mut A3Ctx, mode: c_int) -> c_int;
+    pub fn a3_get_marker_polarity(ctx: *const A3Ctx, mode: *mut c_int) -> c_int;
+    pub fn a3_get_marker_flags(ctx: *mut A3Ctx, dst: *mut u32, cap_markers: usize, n: *mut usize) -> c_int;
     pub fn a3_calculate_tau(device: c_int, codes: *const u64, n_codes: usize, tau: *mut u8) -> c_int;
     pub fn a3_set_profiling(ctx: *mut A3Ctx, mode: c_int) -> c_int;
     pub fn a3_get_profile(ctx: *mut A3Ctx, stage: c_int, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
